@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- particle-steps/s of the device-resident SPH step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload C2|C3|C4|C5|dp=..,DL=..]
+    python bench.py --gpus N --steps K --warmup W [--workload C2|C3|C4|C5|dp=..,DL=..] [--dump-outputs DIR] [--full]
 
 A "step" is one full time step of SPH_Poiseuille.m:250-292 (density/KGC, viscous+gravity, transport
 shift, dt rule, Verlet integration, periodic wrap, neighbour rebuild) on synthetic particles that are
 resident in HBM when the timed region starts.  N=1 runs BASELINE.json's headline configuration
 (configs[1]: dp = 0.025, DL = 3, DH = 1 -> 5 760 particles); N>1 shards the channel into x-slabs, one
 rank per GPU.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the side measurements on top:
+per-kernel device times and the roofline of the dominant kernel, the C3/C4/C5 windows and the accuracy run of the
+default workload (aux), and the CPU baseline.  --dump-outputs DIR writes the state of the last timed step as .npy files.
 """
 from __future__ import annotations
 
@@ -41,6 +45,7 @@ BYTES_PER_WALL = {"k_density": 24, "k_kgc": 24, "k_forces": 48, "k_continuity": 
 # launch of those passes is credited with are SURVEY 8d's minus the fields it does not write.
 LAZY_UNWRITTEN = {"k_forces": 32, "k_continuity": 16}
 STEP_BYTES_FLUID, STEP_BYTES_WALL = 528, 120
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: the most all files together may hold
 _ALIAS = {"k_density_build": "k_density", "k_density_walk": "k_density", "k_density_dyn": "k_density",
           "k_continuity_clock": "k_continuity"}
 
@@ -96,6 +101,24 @@ def cpu_baseline(cfg, geo, prm, parts, budget_s=20.0):
                        f"{st['stats']['seconds_physics']:.1f}s OpenMP pair loops, {threads} threads)")
 
 
+def dump_outputs(out_dir, fields, st):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- Context.download(), state and
+    step outputs in the caller's row order, f64 -- as DIR/<field>.npy, and sim.npy = [step, t, dt, vmax].  When the
+    arrays exceed DUMP_BYTES_MAX, every one of them keeps the same rows, a seeded sample (rows.npy: their numbers)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(fields.values())))
+    row_bytes = sum(a[:1].nbytes for a in fields.values())
+    rows = None
+    if n * row_bytes > DUMP_BYTES_MAX - (1 << 16):  # (the margin holds the .npy headers and sim.npy)
+        k = (DUMP_BYTES_MAX - (1 << 16)) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    for name, a in fields.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a if rows is None else a[rows], dtype=np.float64))
+    np.save(os.path.join(out_dir, "sim.npy"), np.array([st["step"], st["t"], st["dt_last"], st["vmax"]], dtype=np.float64))
+
+
 def pmc_traffic(name, kernel, key="traffic_bytes"):
     """HBM-side bytes per launch of `kernel` from the committed rocprofv3 --pmc passes (profiles/pmc_traffic.json:
     2*FETCH_SIZE + WRITE_SIZE, the gfx950 read-side correction of MI355X_MICROARCH.md applied); None if not profiled.
@@ -108,8 +131,9 @@ def pmc_traffic(name, kernel, key="traffic_bytes"):
 
 
 def run_case(capi, cfg, geo, name, kw, steps, warmup, profile_steps, lpp=0, spg=0, lattice=False,
-             rebuild_every=0, skin_h=0.0, dynamic=0, sustained=None):
+             rebuild_every=0, skin_h=0.0, dynamic=0, sustained=None, dump=None):
     """Time `steps` resident steps of one workload; returns (result dict, prm, parts, pos, vel).
+    dump: directory for dump_outputs() of the last timed step, written before anything else runs on the context.
     sustained = (skip, n): afterwards run `skip` more steps untimed -- past the point where the synthetic start's jittered
     lattice has broken up -- and time another n: the rate a long physical run sustains, reported next to the window's."""
     import torch
@@ -141,6 +165,8 @@ def run_case(capi, cfg, geo, name, kw, steps, warmup, profile_steps, lpp=0, spg=
     g1 = ctx.graph_stats()
     assert st1["step"] - st0["step"] == steps, (st0, st1)
     replay = {k: g1[k] - g0[k] for k in ("slots_replayed", "slots_eager", "graphs_captured")}
+    if dump:
+        dump_outputs(dump, ctx.download(), st1)
     roof, kernels = None, {}
     if profile_steps > 0:  # per-kernel device time, live: HIP event pair around every launch on the ctx stream
         ctx.profile_enable(True)
@@ -261,15 +287,26 @@ def main():
     ap.add_argument("--rebuild-every", type=int, default=0, help="re-bin particles every K-th step (0 = auto)")
     ap.add_argument("--skin", type=float, default=0.0, help="cell skin in units of h (0 = sized from K)")
     ap.add_argument("--dynamic", type=int, default=0, help="device-side re-bin decision: 0 = by size, 1 = on, 2 = off")
-    ap.add_argument("--profile-steps", type=int, default=200, help="eager steps timed per kernel with HIP events")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the C4/C5 side measurements of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: per-kernel times + roofline, the C3/C4/C5 windows and accuracy run of the "
+                         "default workload (aux), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (f64, at most 64 MB)")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="with --full: eager steps timed per kernel with HIP events (default 200)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the side measurements of the default run")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--lattice", action="store_true", help="pristine lattice start instead of the developed state")
     ap.add_argument("--check-launch", action="store_true",
                     help="bring the ranks up, agree on the world size over the control plane, print the line's launch "
                          "fields (value null) and exit: no GPU call, no compute")
     args = ap.parse_args()
+    if args.profile_steps and not args.full:
+        ap.error("--profile-steps times kernels in a --full run only")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs writes the state of a --gpus 1 run only")
+    profile_steps = (200 if args.profile_steps is None else args.profile_steps) if args.full else 0
 
     # ---- launch decision: BEFORE anything touches the GPU (a process that has initialised HIP must never start
     # or become another GPU program; the parent below only spawns children and relays their exit code) ----
@@ -309,8 +346,9 @@ def main():
         return slab.bench_main(args, rank, world, local_rank)
 
     name, kw = parse_workload(args.workload or "C2")
-    r, prm, parts, pos, vel = run_case(capi, cfg, geo, name, kw, args.steps, args.warmup, args.profile_steps, args.lpp,
-                                       args.spg, args.lattice, args.rebuild_every, args.skin, args.dynamic)
+    r, prm, parts, pos, vel = run_case(capi, cfg, geo, name, kw, args.steps, args.warmup, profile_steps, args.lpp,
+                                       args.spg, args.lattice, args.rebuild_every, args.skin, args.dynamic,
+                                       dump=args.dump_outputs)
     value = r["value"]
     out = {
         "metric": "particle-steps/s", "value": value, "unit": "particle-steps/s", "n_gpus": 1,
@@ -327,7 +365,7 @@ def main():
                                    f"hipGraph replay of {r['replay']['slots_replayed']} slots + {r['replay']['slots_eager']} eager launches")},
         "roofline": r["roofline"], "kernels_ms": r["kernels_ms"], "sim": r["sim"],
     }
-    if not args.no_aux and args.workload is None:
+    if args.full and not args.no_aux and args.workload is None:
         # the headline case is launch-latency bound (5 760 particles); report the same loop at 0.5 M and 6.1 M
         # particles as well so the kernels' throughput regime is on record (not the headline value)
         out["aux"] = {}
@@ -354,7 +392,7 @@ def main():
                                "wall_shear": [full.tau_bottom, full.tau_top], "wall_shear_target": full.tau_target}
         except Exception as e:
             out["accuracy"] = {"error": repr(e)}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, geo, prm, dict(parts, pos=pos, vel=vel), args.cpu_budget)
         out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
     print(json.dumps(out))

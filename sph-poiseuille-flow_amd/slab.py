@@ -386,7 +386,7 @@ def join_native_ring(make_engine, capi, rank, dist, group=None, timeout_s=240.0)
 def bench_main(args, rank, world, local_rank):
     """bench.py --gpus N (N > 1).  Headline: weak scaling of the headline configuration -- every GPU holds one
     dp = 0.025, DL = 3 channel section (5 760 particles), the N-GPU channel is DL = 3 N long.  `aux`: the
-    6.1 M-particle channel (C5) cut into N slabs -- the strong-scaling case the north star quotes.
+    6.1 M-particle channel (C5) cut into N slabs -- the strong-scaling case the north star quotes (with --full).
 
     Control plane (id broadcast, agreement votes, barriers, the timing reduction) = torch.distributed on gloo; data plane =
     the library's own loop over its own dlopen'ed RCCL communicator (SPHX_SLAB_LOOP=native, the default with a GPU per
@@ -480,7 +480,7 @@ def bench_main(args, rank, world, local_rank):
         dist.destroy_process_group()
         raise SystemExit(4)
     aux = {}
-    if args.workload is None and not args.no_aux:
+    if args.full and args.workload is None and not args.no_aux:
         try:  # every rank takes the same path: partition() raises on all ranks or on none
             partition(n_cell_columns(cfg.params_from_values(end_time=1e9, **workloads["C5"])), world)
             aux["C5:strong"] = run_case("C5:strong", 40, 8)

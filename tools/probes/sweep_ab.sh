@@ -5,7 +5,7 @@ SW=$1; shift
 for wl in ${@:-C3 C4 C5}; do
   case $wl in C3) st=2000; wu=200;; C4) st=300; wu=40;; C5) st=100; wu=40;; *) st=1000; wu=100;; esac
   for v in "" "$SW"; do
-    out=$(env $v python3 bench.py --workload $wl --steps $st --warmup $wu --no-cpu-baseline --no-aux 2>/dev/null | tail -1)
+    out=$(env $v python3 bench.py --full --workload $wl --steps $st --warmup $wu --no-cpu-baseline --no-aux 2>/dev/null | tail -1)
     python3 - "$wl" "$v" "$out" <<'PY'
 import json, sys
 d = json.loads(sys.argv[3])

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 for spec in "C2 2000" "C3 2000" "C4 300" "C5 40"; do
   set -- $spec
-  timeout -k 10 200 python bench.py --workload $1 --steps $2 --warmup 40 --no-cpu-baseline --no-aux --profile-steps 20 2>gpurun_out/sweep_sizes_err.txt | python -c "
+  timeout -k 10 200 python bench.py --full --workload $1 --steps $2 --warmup 40 --no-cpu-baseline --no-aux --profile-steps 20 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 c=d['config']

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r3_ab2_${1:-x}; mkdir -p $O
 run() { # name lib workload steps warmup
-  SPHX_LIB=$2 python bench.py --workload $3 --steps $4 --warmup $5 --no-cpu-baseline --no-aux --profile-steps ${6:-0} 2>/dev/null | python -c "
+  SPHX_LIB=$2 python bench.py --full --workload $3 --steps $4 --warmup $5 --no-cpu-baseline --no-aux --profile-steps ${6:-0} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d.get('kernels_ms') or {}
 print('$1', '$3', f\"{1e3*d['ms_per_step']:.1f} us/step\", {a: round(1e3*b,1) for a,b in k.items()} if isinstance(k, dict) else '')"

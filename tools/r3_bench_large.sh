@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 TAG=${1:-x}; O=gpurun_out/r3_bench_$TAG; mkdir -p $O
 for spec in "C3 2000 200" "C4 300 40" "C5 100 40"; do
   set -- $spec
-  python bench.py --workload $1 --steps $2 --warmup $3 --no-cpu-baseline --no-aux --profile-steps 16 > $O/$1.json 2> $O/$1.err || echo "$1 failed"
+  python bench.py --full --workload $1 --steps $2 --warmup $3 --no-cpu-baseline --no-aux --profile-steps 16 > $O/$1.json 2> $O/$1.err || echo "$1 failed"
   python - $O/$1.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -2,12 +2,12 @@
 # Round-3 evidence: bench lines, rocprofv3 kernel traces of the same commands, PMC passes (C2, C5), slab-ring probes.
 cd $GRAFT_REPO_ROOT
 TAG=${1:-r3}; OUT=gpurun_out/final_$TAG; mkdir -p $OUT
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2> $OUT/bench_driver_style.err; echo "driver-style rc=$?"
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2> $OUT/bench_driver_style.err; echo "driver-style rc=$?"
 export TMPDIR=/tmp
 for wl in C2 C4 C5; do
   case $wl in C2) st=4000; wu=400;; C4) st=300; wu=40;; C5) st=100; wu=40;; esac
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$wl -- python3 bench.py --workload $wl \
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$wl -- python3 bench.py --full --workload $wl \
       --steps $st --warmup $wu --no-cpu-baseline --no-aux --profile-steps 16 > $OUT/trace_$wl.json 2> $OUT/trace_$wl.err
   f=$(find $OUT/trace_$wl -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $OUT/kernel_stats_$wl.csv
   echo "trace $wl done"

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r4m; mkdir -p $OUT
 timeout -k 10 600 python3 -m pytest tests -m gpu -q > $OUT/pytest.txt 2>&1; echo "pytest rc=$?"; tail -4 $OUT/pytest.txt
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python3 - <<'PY'
 import json
 d = json.load(open("gpurun_out/r4m/bench.json"))

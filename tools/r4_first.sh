@@ -5,9 +5,9 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r4a; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 420 python3 -m pytest tests -m gpu -x -q > $OUT/pytest.txt 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest.txt
-timeout -k 10 300 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-timeout -k 10 120 python3 bench.py --steps 20 --warmup 5 --no-aux > $OUT/bench_driver_style.json 2> $OUT/bench_driver_style.err; echo "driver-style rc=$?"
-timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_C3 -- python3 bench.py --workload C3 \
+timeout -k 10 300 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout -k 10 120 python3 bench.py --full --steps 20 --warmup 5 --no-aux > $OUT/bench_driver_style.json 2> $OUT/bench_driver_style.err; echo "driver-style rc=$?"
+timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_C3 -- python3 bench.py --full --workload C3 \
     --steps 2000 --warmup 100 --no-cpu-baseline --no-aux --profile-steps 64 > $OUT/trace_C3.json 2> $OUT/trace_C3.err
 f=$(find $OUT/trace_C3 -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $OUT/kernel_stats_C3.csv; rm -rf $OUT/trace_C3
 echo "trace C3 done"
