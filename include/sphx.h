@@ -259,6 +259,55 @@ int sphx_ctx_substeps(sphx_ctx *ctx, int *n_inner);
 int sphx_ctx_info(sphx_ctx *ctx, int *n_fluid, int *n_wall, int *n_cell_x, int *n_cell_y);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2a. Flow statistics: time-averaged velocity profiles accumulated on the device, inside the step loop.
+ *
+ *  Bins: the reference's profile binning (SPH_Poiseuille.m:579-605, profile.compute_binned_profile_mean):
+ *    n_bins y-bins over [0, DH] with edges[k] = k * (DH / n_bins) and edges[n_bins] = DH (numpy's linspace);
+ *    bin k holds edges[k] <= y < edges[k+1], the last bin also y == DH; fluid particles outside [0, DH] are
+ *    dropped.  Wall particles are never binned.
+ *  Bands: band 0 is the whole channel; bands 1 .. n_bands are x-bands (band_x[b-1], band_hw[b-1]) with the membership of
+ *    compute_mid_channel_profile: xw = x mod DL, d = |xw - xc|, d = min(d, DL - d), member when d <= hw.  The
+ *    reference's mid-channel monitor is (DL/2, max(dp, h)); a band around the periodic seam is (0, hw).
+ *  Per bin and band: particle samples N, sum u_x, sum u_x^2, sum u_y, sum u_y^2 over all samples; per context the
+ *    number of samples and the times of the first and the last one.  Only pos / vel are sampled.
+ *  Sample point: the state a completed step leaves -- exactly what sphx_ctx_download returns for pos / vel after that
+ *    step.  A step is sampled when its step count (sphx_status.step after it) is a multiple of `every` and it ends at
+ *    t >= t_from.  Dual-rate contexts sample once per outer step.  The sampling kernel closes every step slot (it skips
+ *    itself on the other steps) and is captured in the replayed graphs; enable / disable re-capture them, and with the
+ *    statistics off a step enqueues exactly the launches it does without this feature.
+ *  Determinism: a sample is summed exactly (int64 fixed point, scales picked per sample from the particle count and
+ *    2 max|v|) and added to double running sums bin by bin: two identical runs give bit-identical sums, independent of
+ *    particle order, re-binning and host chunking.  A velocity above that bound (a non-finite state) makes a later
+ *    read fail with SPHX:Stats:range.
+ *  Errors: SPHX:Stats:config (bad config), SPHX:Stats:band, SPHX:Stats:capacity, SPHX:Stats:disabled (SPHX_ERR_STATE),
+ *    SPHX:Stats:range (SPHX_ERR_STATE); every call on a slab context fails with SPHX_ERR_ARG, SPHX:Stats:slab.
+ * ---------------------------------------------------------------------------------------------- */
+
+typedef struct sphx_flow_stats_config {
+    int32_t n_bins;            /* 0 = max(20, floor(DH/dp + 0.5)), the reference's profile bins;
+                                  n_bins * (n_bands + 1) <= 1536                                          */
+    int32_t every;             /* sample every `every`-th completed step (step count % every == 0), >= 1 */
+    double t_from;             /* only steps ending at t >= t_from                                       */
+    int32_t n_bands;           /* 0..2 x-bands besides the whole channel                                 */
+    double band_x[2], band_hw[2];
+} sphx_flow_stats_config;
+
+/* (Re)configure and zero the statistics; waits for the stream.  Off by default. */
+int sphx_ctx_flow_stats_enable(sphx_ctx *ctx, const sphx_flow_stats_config *cfg);
+/* Stop sampling (no-op when off); the sums are dropped. */
+int sphx_ctx_flow_stats_disable(sphx_ctx *ctx);
+/* Zero the sums and the sample count after everything enqueued has been taken. */
+int sphx_ctx_flow_stats_reset(sphx_ctx *ctx);
+/* Add one sample of the current state (what sphx_ctx_download would return) now, without gating. */
+int sphx_ctx_flow_stats_sample(sphx_ctx *ctx);
+/* Sums of band `band` (0 = whole channel), n_bins entries each; any array may be NULL (all NULL: capacity is not
+ * checked, so n_bins can be asked for first).  Waits for and settles everything enqueued, like sphx_ctx_download.
+ * t_first / t_last: simulated times of the first / last sample (NaN before the first). */
+int sphx_ctx_flow_stats_read(sphx_ctx *ctx, int band, int capacity, int *n_bins, double *count, double *sum_ux,
+                             double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples,
+                             double *t_first, double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU).  The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

@@ -8,6 +8,8 @@ import os
 
 import numpy as np
 
+from .profile import flow_stats_profile
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPHX_LIB") or os.path.join(HERE, "csrc", "libsphx.so")  # SPHX_LIB: experiment builds
 _dp = C.POINTER(C.c_double)
@@ -34,6 +36,11 @@ class SphxParams(C.Structure):
                 ("dynamic_rebin", C.c_int32), ("skin_h", C.c_double)]
 
 
+class SphxFlowStatsConfig(C.Structure):
+    _fields_ = [("n_bins", C.c_int32), ("every", C.c_int32), ("t_from", C.c_double), ("n_bands", C.c_int32),
+                ("band_x", C.c_double * 2), ("band_hw", C.c_double * 2)]
+
+
 class SphxStatus(C.Structure):
     _fields_ = [("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("vmax", C.c_double),
                 ("step", C.c_int64), ("done", C.c_int32), ("device_status", C.c_int32)]
@@ -51,6 +58,8 @@ EXPORTS = [
     "sphx_ctx_prepare_steps", "sphx_ctx_graph_stats",
     "sphx_ctx_download", "sphx_ctx_monitor", "sphx_ctx_neighbor_list", "sphx_ctx_profile_enable",
     "sphx_ctx_profile_read", "sphx_ctx_info", "sphx_ctx_tuning", "sphx_ctx_substeps", "sphx_ctx_schedule", "sphx_ctx_kernel_forms", "sphx_ctx_grid_policy", "sphx_ctx_time_kernel",
+    "sphx_ctx_flow_stats_enable", "sphx_ctx_flow_stats_disable", "sphx_ctx_flow_stats_reset", "sphx_ctx_flow_stats_sample",
+    "sphx_ctx_flow_stats_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -123,6 +132,7 @@ class Context:
         drho_dt, mass = f64(drho_dt), f64(mass)
         assert pos.shape == (n_total, 2) and vel.shape == (n_total, 2) and wall_vel.shape == (n_total, 2)
         assert drho_dt.shape == (n_total,) and mass.shape == (n_total,)
+        self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
         check(lib().sphx_ctx_create(C.byref(self._h), C.byref(self.params), C.c_int(n_fluid), C.c_int(n_total),
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
@@ -221,6 +231,53 @@ class Context:
         check(lib().sphx_ctx_time_kernel(self._h, name.encode(), C.c_int(reps), C.byref(ms)))
         return ms.value
 
+    # ---- flow statistics (include/sphx.h section 2a): time-averaged velocity profiles accumulated on the device ----
+    def flow_stats_enable(self, n_bins=0, every=1, t_from=0.0, bands=()):
+        """Sample the state every `every`-th completed step ending at t >= t_from into n_bins y-bins (0: the reference's
+        max(20, round(DH/dp))) of the whole channel (band 0) and of up to two x-bands [(x_centre, half_width), ...]
+        (band 1, 2).  (Re)configures and zeroes the sums."""
+        cfg = flow_stats_config(n_bins, every, t_from, bands)
+        n = int(cfg.n_bins) or max(20, int(np.floor(self.params.DH / self.params.dp + 0.5)))
+        check(lib().sphx_ctx_flow_stats_enable(self._h, C.byref(cfg)))
+        self._flow_stats = (n, int(cfg.n_bands) + 1)
+
+    def flow_stats_disable(self):
+        check(lib().sphx_ctx_flow_stats_disable(self._h))
+        self._flow_stats = None
+
+    def flow_stats_reset(self):
+        self._flow_stats_on()
+        check(lib().sphx_ctx_flow_stats_reset(self._h))
+
+    def flow_stats_sample(self):
+        """Add one sample of the current state (what download() returns) now, whatever the gating."""
+        self._flow_stats_on()
+        check(lib().sphx_ctx_flow_stats_sample(self._h))
+
+    def flow_stats_sums(self, band=0) -> dict:
+        """The raw sums of one band: count, sum_ux, sum_ux2, sum_uy, sum_uy2 [n_bins], n_samples, t_first, t_last."""
+        n_bins, n_bands = self._flow_stats_on()
+        if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:Stats:band", f"band must be an integer in 0..{n_bands - 1}")
+        arrs = [np.zeros(n_bins) for _ in range(5)]
+        nb, ns, t0, t1 = C.c_int(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+        check(lib().sphx_ctx_flow_stats_read(self._h, C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), *[ptr(a) for a in arrs],
+                                             C.byref(ns), C.byref(t0), C.byref(t1)))
+        assert nb.value == n_bins, (nb.value, n_bins)
+        out = dict(zip(("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2"), arrs))
+        out.update(n_samples=ns.value, t_first=t0.value, t_last=t1.value)
+        return out
+
+    def flow_stats(self, band=0) -> dict:
+        """Time-averaged profile of one band (profile.flow_stats_profile): y_mid, count, u_mean, u_std, uy_mean, uy_std,
+        n_samples, t_first, t_last (+ the raw sums).  Empty bins give NaN means."""
+        return flow_stats_profile(self.params.DH, **self.flow_stats_sums(band))
+
+    def _flow_stats_on(self):
+        if self._flow_stats is None:
+            raise SphxError(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this context")
+        return self._flow_stats
+
     def profile_enable(self, on=True):
         check(lib().sphx_ctx_profile_enable(self._h, C.c_int(1 if on else 0)))
 
@@ -232,6 +289,37 @@ class Context:
         n = C.c_int(0)
         check(lib().sphx_ctx_profile_read(self._h, C.c_int(cap), names, avg, cnt, C.byref(n)))
         return {names[k].decode(): dict(avg_ms=avg[k], launches=cnt[k]) for k in range(min(n.value, cap))}
+
+
+def flow_stats_config(n_bins=0, every=1, t_from=0.0, bands=()) -> SphxFlowStatsConfig:
+    """Checked sphx_flow_stats_config; raises SphxError(SPHX:Stats:config) before anything reaches the device."""
+    def bad(msg):
+        return SphxError(SPHX_ERR_ARG, "SPHX:Stats:config", msg)
+
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+    if not is_int(n_bins) or n_bins < 0:
+        raise bad("n_bins must be an integer >= 0 (0 = the reference's profile bins)")
+    if not is_int(every) or every < 1:
+        raise bad("every must be an integer >= 1")
+    try:
+        t_from = float(t_from)
+        bands = [tuple(float(v) for v in b) for b in bands]
+    except (TypeError, ValueError):
+        raise bad("t_from must be a number and bands a sequence of (x_centre, half_width) pairs") from None
+    if np.isnan(t_from):
+        raise bad("t_from must not be NaN")
+    if len(bands) > 2 or any(len(b) != 2 for b in bands):
+        raise bad("at most two bands, each (x_centre, half_width)")
+    if any(not (np.isfinite(x) and np.isfinite(hw) and hw >= 0.0) for x, hw in bands):
+        raise bad("band centres must be finite and half-widths finite and >= 0")
+    if n_bins * (len(bands) + 1) > 1536:
+        raise bad("n_bins * (number of bands + 1) must not exceed 1536")
+    cfg = SphxFlowStatsConfig(n_bins=int(n_bins), every=int(every), t_from=t_from, n_bands=len(bands))
+    for k, (x, hw) in enumerate(bands):
+        cfg.band_x[k], cfg.band_hw[k] = x, hw
+    return cfg
 
 
 def _fetch_pairs(n):

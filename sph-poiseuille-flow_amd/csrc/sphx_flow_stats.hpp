@@ -1,0 +1,174 @@
+// sphx_flow_stats.hpp -- time-averaged velocity profiles of a resident context (include/sphx.h section 2, "flow
+// statistics"): one self-skipping launch at the end of every step slot bins the state the step left into the
+// reference's profile bins (SPH_Poiseuille.m:579-605) and adds it to running sums, without a host round trip.
+//
+// Determinism: a sample is summed EXACTLY, in int64 fixed point -- integer adds do not depend on the order they arrive
+// in, so neither the particle order (layouts, re-binnings) nor the dispatch order of the workgroups can change a bit.
+// Per sample the scales are powers of two picked from the particle count and a bound of 2 max|v| (Clock::vmax): with
+// n <= 2^L particles and |u| <= 2^e, u * 2^(62-L-e) and u^2 * 2^(62-L-2e) are below 2^(62-L), so no sum of n of them can
+// overflow.  A |u| above the bound (only a non-finite state can have one) raises a sticky flag and the read fails.
+// Each workgroup keeps the sample's counters in LDS, adds every non-zero one to the global integer sums with one
+// atomic, and the last workgroup out (ticket, agent-scope release / acquire) converts the integer sums to double, adds
+// them to the running sums bin by bin and clears them for the next sample.
+#pragma once
+#include "sphx_kernels.hpp"
+
+namespace sphx {
+
+constexpr int kStatsFields = 5;            // per bin and band: count, sum u_x, sum u_x^2, sum u_y, sum u_y^2
+constexpr int kStatsMaxBins = 1536;        // n_bands * n_bins (incl. band 0): 61 440 B of LDS counters per workgroup
+constexpr int kStatsBlock = 512;
+constexpr int kStatsMaxBlocks = 256;       // one workgroup per CU at most: every one of them flushes its counters
+constexpr int kStatsPerThread = 8;         // particles a thread takes before another workgroup is added: up to 4 096
+                                           // particles ONE workgroup finishes the sample by itself (no flush, no ticket).
+                                           // (32, i.e. one workgroup up to 16 k particles: C2 29.3 -> 32.2 us/step -- the
+                                           // LDS adds of one workgroup serialise on the few bins a wave's particles share)
+
+struct FlowStatsHead {
+    long long n_samples;
+    double t_first, t_last;
+    int range;   // sticky: some |u| of some sample exceeded the bound of that sample
+    int ticket;  // last workgroup out (zero between launches)
+};
+
+struct FlowStatsArgs {
+    const double2 *pos, *vel;   // the state to sample (fluid slots 0 .. clk->n-1, any order)
+    unsigned long long *isum;   // [n_bands][n_bins][kStatsFields] integer sums of the sample in flight (zero in between)
+    double *dsum;               // same layout: running sums over all samples
+    FlowStatsHead *head;
+    double DH, bin_w, DL;       // bin_w = DH / n_bins, the step of numpy's linspace
+    double t_from;
+    double band_x[2], band_hw[2];
+    int n_bins, n_bands;        // n_bands counts band 0 (the whole channel)
+    int every;                  // >= 1: in-loop sample, gated on the clock; 0: sample unconditionally
+};
+
+// y-bin of the reference's binning (numpy linspace edges, discretize semantics): edges[k] = k * bin_w for k < n_bins,
+// edges[n_bins] = DH; bin k holds edges[k] <= y < edges[k+1], the last bin also y == DH.  The quotient is a first guess
+// only: the comparisons against the edges decide, so a particle exactly on an edge lands where the host puts it.
+__device__ __forceinline__ int stats_bin(double y, double bin_w, int n_bins)
+{
+    int k = (int)(y / bin_w);
+    k = k < 0 ? 0 : (k > n_bins - 1 ? n_bins - 1 : k);
+    while (k > 0 && y < (double)k * bin_w) --k;
+    while (k < n_bins - 1 && y >= (double)(k + 1) * bin_w) ++k;
+    return k;
+}
+
+// compute_mid_channel_profile's membership: xw = x mod DL (numpy's sign rule), d = min(|xw - xc|, DL - |xw - xc|) <= hw
+__device__ __forceinline__ bool stats_in_band(double x, double DL, double xc, double hw)
+{
+    double m = fmod(x, DL);
+    if (m != 0.0 && m < 0.0) m += DL;
+    double d = fabs(m - xc);
+    d = fmin(d, DL - d);
+    return d <= hw;
+}
+
+__device__ __forceinline__ void stats_scales(double vmax, int n, int &s1, int &s2, double &bound)
+{
+    int L = 0;
+    while (L < 31 && (1 << L) < n) ++L;
+    int e = 0;
+    (void)frexp(fmax(2.0 * vmax, 0x1p-60), &e);  // 2 vmax < 2^e  (a NaN vmax leaves the floor: every |u| is then out of range)
+    bound = ldexp(1.0, e);
+    s1 = 62 - L - e;
+    s2 = 62 - L - 2 * e;
+}
+
+__device__ __forceinline__ void stats_add(unsigned long long *h, long long ux, long long ux2, long long uy, long long uy2)
+{
+    atomicAdd(h + 0, 1ull);
+    atomicAdd(h + 1, (unsigned long long)ux);  // (two's complement: signed sums wrap back to the right value)
+    atomicAdd(h + 2, (unsigned long long)ux2);
+    atomicAdd(h + 3, (unsigned long long)uy);
+    atomicAdd(h + 4, (unsigned long long)uy2);
+}
+
+// q: parity of the step slot this launch closes (in-loop samples: the slot ran iff run[q] is still set -- a clock update
+// only ever writes the flag of the NEXT slot).  The launch sits behind the slot's clock update, so clk->step / clk->t are
+// those of the step just completed.
+__global__ __launch_bounds__(kStatsBlock) void k_flow_stats(const Clock *clk, int q, FlowStatsArgs a)
+{
+    if (a.every > 0) {
+        if (!clk->run[q]) return;
+        if (clk->step % a.every != 0) return;
+        if (!(clk->t >= a.t_from)) return;
+    }
+    const int n = clk->n;
+    const double vmax = clk->vmax, t_now = clk->t;
+    extern __shared__ unsigned long long s_cnt[];  // [n_bands][n_bins][kStatsFields]
+    __shared__ int s_last;
+    const int nc = a.n_bands * a.n_bins * kStatsFields;
+    for (int k = threadIdx.x; k < nc; k += kStatsBlock) s_cnt[k] = 0ull;
+    __syncthreads();
+
+    int s1, s2;
+    double bound;
+    stats_scales(vmax, n, s1, s2, bound);
+    const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;  // a contiguous run of slots per workgroup (cell order:
+    const int i0 = (int)blockIdx.x * chunk;                        // only the workgroups over a band's columns touch it)
+    const int i1 = min(n, i0 + chunk);
+    bool out_of_range = false;
+    for (int i = i0 + (int)threadIdx.x; i < i1; i += kStatsBlock) {
+        const double2 p = a.pos[i], v = a.vel[i];
+        if (!(p.y >= 0.0 && p.y <= a.DH)) continue;  // outside [0, DH]: dropped, as discretize does
+        if (!(fabs(v.x) <= bound && fabs(v.y) <= bound)) { out_of_range = true; continue; }
+        const int k = stats_bin(p.y, a.bin_w, a.n_bins);
+        const long long ux = __double2ll_rn(ldexp(v.x, s1)), uy = __double2ll_rn(ldexp(v.y, s1));
+        const long long ux2 = __double2ll_rn(ldexp(v.x * v.x, s2)), uy2 = __double2ll_rn(ldexp(v.y * v.y, s2));
+        stats_add(s_cnt + (size_t)k * kStatsFields, ux, ux2, uy, uy2);
+        for (int b = 1; b < a.n_bands; ++b)
+            if (stats_in_band(p.x, a.DL, a.band_x[b - 1], a.band_hw[b - 1]))
+                stats_add(s_cnt + ((size_t)b * a.n_bins + k) * kStatsFields, ux, ux2, uy, uy2);
+    }
+    if (out_of_range) atomicOr(&a.head->range, 1);
+    __syncthreads();
+    // one thread per counter: the running sums grow in sample order, each by its own bin -- no summation tree
+    auto finish = [&](int k, unsigned long long v) {
+        const int f = k % kStatsFields;
+        const int s = f == 0 ? 0 : ((f & 1) ? s1 : s2);
+        a.dsum[k] += ldexp((double)(long long)v, -s);
+    };
+    auto finish_head = [&]() {
+        FlowStatsHead *h = a.head;
+        if (h->n_samples == 0) h->t_first = t_now;
+        h->t_last = t_now;
+        h->n_samples += 1;
+    };
+    if (gridDim.x == 1) {  // small channels: one workgroup holds the whole sample -- no global sums, no ticket
+        for (int k = threadIdx.x; k < nc; k += kStatsBlock)
+            if (s_cnt[k]) finish(k, s_cnt[k]);
+        if (threadIdx.x == 0) finish_head();
+        return;
+    }
+    for (int k = threadIdx.x; k < nc; k += kStatsBlock) {
+        const unsigned long long v = s_cnt[k];
+        if (v) atomicAdd(a.isum + k, v);
+    }
+    // last workgroup out: every wave drains its adds, one release at agent scope, then the ticket
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int drawn = __hip_atomic_fetch_add(&a.head->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = drawn == (int)gridDim.x - 1 ? 1 : 0;
+        if (s_last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!s_last) return;
+    for (int k = threadIdx.x; k < nc; k += kStatsBlock) {
+        const unsigned long long v = atomicExch(a.isum + k, 0ull);
+        if (v) finish(k, v);
+    }
+    if (threadIdx.x == 0) {
+        finish_head();
+        __hip_atomic_store(&a.head->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+}  // namespace sphx

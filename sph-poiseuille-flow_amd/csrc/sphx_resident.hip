@@ -14,6 +14,7 @@
 
 #include "sphx_common.hpp"
 #include "sphx_kernels.hpp"
+#include "sphx_flow_stats.hpp"
 
 namespace sphx {
 
@@ -192,6 +193,16 @@ struct sphx_ctx {
     bool lds_tiles_be = false;   // ... KGC and continuity too (2 lanes per particle, channel larger than the Infinity Cache)
     bool coded_lists = false;    // ... and the lists name tile slots instead of index differences (kSlotCodes, sphx_kernels.hpp)
     bool tail_clock = false;     // move steps carry their clock update in a tail workgroup of pass E (small channels)
+
+    // Flow statistics (sphx_ctx_flow_stats_*, sphx_flow_stats.hpp): when on, every step slot ends with k_flow_stats
+    struct FlowStats {
+        bool on = false;
+        sphx_flow_stats_config cfg{};
+        int n_bins = 0, n_bands = 1;  // (n_bands counts band 0)
+        DevBuf<unsigned long long> isum;
+        DevBuf<double> dsum;
+        DevBuf<FlowStatsHead> head;
+    } fstats;
 
     FluidSet view(int q, int l)
     {
@@ -652,6 +663,31 @@ void launch_step_dyn(sphx_ctx *c, int q)
     launch(c, "k_copyback", k_copyback, g1, bp, (const Clock *)clk, qf, cb);
 }
 
+// k_flow_stats on (pos, vel): every >= 1 = the in-loop sample closing step slot q, 0 = a sample of the state now
+void launch_flow_stats(sphx_ctx *c, int q, const double2 *pos, const double2 *vel, int every)
+{
+    const sphx_ctx::FlowStats &f = c->fstats;
+    FlowStatsArgs a{};
+    a.pos = pos; a.vel = vel;
+    a.isum = f.isum.get(); a.dsum = f.dsum.get(); a.head = f.head.get();
+    a.DH = c->prm.DH; a.bin_w = c->prm.DH / f.n_bins; a.DL = c->prm.DL;
+    a.t_from = f.cfg.t_from;
+    for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
+    a.n_bins = f.n_bins; a.n_bands = f.n_bands;
+    a.every = every;
+    const unsigned nb = std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kStatsBlock * kStatsPerThread), 1u, (unsigned)kStatsMaxBlocks);
+    const size_t shmem = (size_t)f.n_bands * f.n_bins * kStatsFields * sizeof(unsigned long long);
+    launch_s(c, "k_flow_stats", k_flow_stats, dim3(nb), dim3(kStatsBlock), shmem, (const Clock *)c->clock.get(), q, a);
+}
+
+// the state step slot q leaves is in S[1-q] on every schedule (a re-binning step reorders into S[1-q] too, a dynamic
+// context copies back into it); the launch comes after the slot's clock update, whichever kernel carries it
+void launch_slot_stats(sphx_ctx *c, int q)
+{
+    if (!c->fstats.on) return;
+    launch_flow_stats(c, q, c->fpos_[1 - q].get(), c->fvel_[1 - q].get(), c->fstats.cfg.every);
+}
+
 // host-side bookkeeping of one executed step
 void track_step(sphx_ctx *c)
 {
@@ -710,6 +746,7 @@ sphx_ctx::CachedGraph &get_graph(sphx_ctx *c, int cur, int lay, int pos, int n)
                 if (rebuild) { l ^= 1; p = 0; }
                 else ++p;
             }
+            launch_slot_stats(c, q);
             q ^= 1;
         }
     } catch (...) {
@@ -776,6 +813,7 @@ void enqueue_slots(sphx_ctx *c, int64_t slots, bool exact_tail, bool capture_onl
         if (!capture_only) {
             if (c->dyn) launch_step_dyn(c, c->cur);
             else launch_step(c, c->cur, c->lay, c->pos, slot_rebuilds(c));
+            launch_slot_stats(c, c->cur);
             c->slots_eager += 1;
         }
         track_step(c);
@@ -1716,6 +1754,138 @@ SPHX_EXPORT int sphx_ctx_profile_read(sphx_ctx *c, int capacity, const char **na
     }
     for (auto &v : c->timer.total_ms) v = 0.0;
     for (auto &v : c->timer.launches) v = 0;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- flow statistics (sphx_flow_stats.hpp) ----
+namespace {
+
+sphx_ctx *stats_ctx(sphx_ctx *c, bool need_on)
+{
+    require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
+    require(!c->is_slab, "SPHX:Stats:slab", "flow statistics are not available on slab contexts");
+    if (need_on && !c->fstats.on)
+        throw Error(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this context");
+    return c;
+}
+
+// the replayed graphs carry k_flow_stats (and its arguments) or not: a change of the setting re-captures them
+void stats_drop_graphs(sphx_ctx *c)
+{
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+    c->drop_graph();
+}
+
+void stats_zero(sphx_ctx *c)
+{
+    sphx_ctx::FlowStats &f = c->fstats;
+    f.isum.zero(c->stream);
+    f.dsum.zero(c->stream);
+    f.head.zero(c->stream);
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_config *cfg)
+{
+    SPHX_TRY
+    stats_ctx(c, false);
+    require(cfg != nullptr, "SPHX:Stats:config", "config must not be NULL");
+    require(cfg->n_bins >= 0, "SPHX:Stats:config", "n_bins must be >= 0 (0 = the reference's profile bins)");
+    require(cfg->every >= 1, "SPHX:Stats:config", "every must be >= 1");
+    require(!std::isnan(cfg->t_from), "SPHX:Stats:config", "t_from must not be NaN");
+    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, "SPHX:Stats:config", "n_bands must be 0, 1 or 2");
+    for (int b = 0; b < cfg->n_bands; ++b)
+        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, "SPHX:Stats:config",
+                "band centres must be finite and half-widths finite and >= 0");
+    const int n_bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(c->prm.DH / c->prm.dp + 0.5));
+    require((int64_t)n_bins * (cfg->n_bands + 1) <= kStatsMaxBins, "SPHX:Stats:config",
+            "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
+    stats_drop_graphs(c);
+    sphx_ctx::FlowStats &f = c->fstats;
+    f.cfg = *cfg;
+    for (int b = cfg->n_bands; b < 2; ++b) { f.cfg.band_x[b] = 0.0; f.cfg.band_hw[b] = 0.0; }
+    f.n_bins = n_bins;
+    f.n_bands = cfg->n_bands + 1;
+    const size_t nc = (size_t)f.n_bands * n_bins * kStatsFields;
+    f.isum.alloc(nc);
+    f.dsum.alloc(nc);
+    f.head.alloc(1);
+    stats_zero(c);
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+    f.on = true;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_flow_stats_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    stats_ctx(c, false);
+    if (!c->fstats.on) return SPHX_OK;
+    stats_drop_graphs(c);
+    sphx_ctx::FlowStats &f = c->fstats;
+    f.on = false;
+    f.isum.release();
+    f.dsum.release();
+    f.head.release();
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_flow_stats_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    stats_ctx(c, true);
+    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
+    stats_zero(c);
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_flow_stats_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    stats_ctx(c, true);
+    settle_owed(c);  // the state sphx_ctx_download would return
+    const FluidSet fs = c->view(c->cur, c->lay);
+    launch_flow_stats(c, 0, fs.pos, fs.vel, 0);
+    SPHX_HIP(hipGetLastError());
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_flow_stats_read(sphx_ctx *c, int band, int capacity, int *n_bins, double *count, double *sum_ux,
+                                         double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples,
+                                         double *t_first, double *t_last)
+{
+    SPHX_TRY
+    stats_ctx(c, true);
+    const sphx_ctx::FlowStats &f = c->fstats;
+    require(band >= 0 && band < f.n_bands, "SPHX:Stats:band", "band must be 0 (whole channel) .. n_bands");
+    double *out[kStatsFields] = {count, sum_ux, sum_ux2, sum_uy, sum_uy2};
+    bool any = false;
+    for (double *o : out) any = any || o != nullptr;
+    require(!any || capacity >= f.n_bins, "SPHX:Stats:capacity", "capacity is smaller than the number of bins");
+    settle_owed(c);
+    std::vector<double> sums((size_t)f.n_bins * kStatsFields);
+    FlowStatsHead h{};
+    SPHX_HIP(hipMemcpyAsync(sums.data(), f.dsum.get() + (size_t)band * f.n_bins * kStatsFields, sums.size() * sizeof(double),
+                            hipMemcpyDeviceToHost, c->stream));
+    SPHX_HIP(hipMemcpyAsync(&h, f.head.get(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+    if (h.range)
+        throw Error(SPHX_ERR_STATE, "SPHX:Stats:range", "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
+    if (n_bins) *n_bins = f.n_bins;
+    for (int j = 0; j < kStatsFields; ++j)
+        if (out[j])
+            for (int k = 0; k < f.n_bins; ++k) out[j][k] = sums[(size_t)k * kStatsFields + j];
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (n_samples) *n_samples = h.n_samples;
+    if (t_first) *t_first = h.n_samples ? h.t_first : nan;
+    if (t_last) *t_last = h.n_samples ? h.t_last : nan;
     return SPHX_OK;
     SPHX_CATCH
 }

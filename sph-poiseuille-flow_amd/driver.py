@@ -44,6 +44,7 @@ class RunResult:
     grid_policy: dict = field(default_factory=dict)  # resident engine: rebuild interval, skin, forced rebuilds
     full_profile_u: list = field(default_factory=list)  # whole-channel binned u_x(y) at every output point
     n_inner: int = 1  # inner sub-steps per counted step (> 1 only with the opt-in dual-rate loop)
+    time_avg: dict = None  # run(..., average_from=...): device-side time-averaged profiles and figures (see time_average)
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -72,8 +73,33 @@ def periodic_bounding(pos, n_fluid, DL):
     return pos
 
 
+def time_average(prm, whole, mid):
+    """Figures of a time window from the device's flow statistics (capi.Context.flow_stats of band 0 / the mid band).
+    U_max = g DH^2 / (8 nu), the centre-line speed of the analytic profile.
+      profile, mid_profile   the whole-channel and mid-band flow_stats dicts (u_mean, u_std, ... per bin)
+      u_exact, L2            analytic profile at the bin centres and l2_error of the time-averaged whole-channel u_mean
+      uy_rms_over_umax       sqrt(sum over bins of sum u_y^2 / sum over bins of N) / U_max (all particle samples)
+      ux_std_centre_over_umax  count-weighted RMS of the per-bin u_x spread u_std over the bins whose centres lie in
+                             [0.4, 0.6] DH, sqrt(sum N u_std^2 / sum N), / U_max
+      n_samples, t_first, t_last  the window actually sampled"""
+    u_max = prm.gravity_g * prm.DH ** 2 / (8.0 * prm.nu)
+    y = whole["y_mid"]
+    u_exact = prm.gravity_g / (2.0 * prm.nu) * y * (prm.DH - y)
+    N = whole["count"]
+    n_all = float(np.sum(N))
+    uy_rms = np.sqrt(np.sum(whole["sum_uy2"]) / n_all) if n_all > 0 else np.nan
+    centre = (y >= 0.4 * prm.DH) & (y <= 0.6 * prm.DH) & (N > 0)
+    n_c = float(np.sum(N[centre]))
+    ux_sd = np.sqrt(np.sum(N[centre] * whole["u_std"][centre] ** 2) / n_c) if n_c > 0 else np.nan
+    return dict(profile=whole, mid_profile=mid, y_mid=y, u_mean=whole["u_mean"], mid_u_mean=mid["u_mean"], u_exact=u_exact,
+                L2=l2_error(whole["u_mean"], u_exact), uy_rms_over_umax=float(uy_rms / u_max),
+                ux_std_centre_over_umax=float(ux_sd / u_max), U_max=u_max, n_samples=whole["n_samples"],
+                t_first=whole["t_first"], t_last=whole["t_last"])
+
+
 def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_particle=0, steps_per_graph=0,
-        rebuild_every=0, restart_path=None, postprocess_path=None, dual_rate=0, mat_format="auto"):
+        rebuild_every=0, restart_path=None, postprocess_path=None, dual_rate=0, mat_format="auto", average_from=None,
+        average_every=1):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -81,7 +107,13 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     (:295).  postprocess_path: write SPH_Poiseuille_postprocess.mat at the end (:305-306).  mat_format: "7.3" (HDF5, what
     the reference writes), "5", or "auto" = 7.3 where a libhdf5 can be loaded (restart.py); either is read back.
     dual_rate (resident engine, opt-in, NOT the reference's loop): up to that many acoustic sub-steps per outer step,
-    see sphx_params.dual_rate in include/sphx.h; the result then carries n_inner and steps counts outer steps."""
+    see sphx_params.dual_rate in include/sphx.h; the result then carries n_inner and steps counts outer steps.
+    average_from (resident engine): accumulate, on the device and inside the step loop, every average_every-th step ending
+    at t >= average_from into the reference's profile bins, for the whole channel and the mid-channel band (DL/2,
+    max(dp, h)); RunResult.time_avg then holds the time-averaged profiles, their L2 against u_exact and the stability
+    figures defined in time_average().  The output-point snapshots are taken as without it."""
+    if average_from is not None and engine != "resident":
+        raise ValueError("average_from needs the resident engine (the statistics are accumulated on the device)")
     parts = init_particles(prm) if parts is None else parts
     nf, nt = parts["n_fluid"], parts["n_total"]
     t_start, step_start, n_inner = 0.0, 0, 1
@@ -103,14 +135,17 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     mid_profiles.append(u0)
     tau_b = tau_t = 0.0
     policy = {}
+    time_avg = None
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
                            parts["wall_vel"], t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
                            steps_per_graph=steps_per_graph, rebuild_every=rebuild_every, dual_rate=dual_rate)
-        n_inner = ctx.substeps()
         t, step = t_start, step_start
         try:
+            n_inner = ctx.substeps()
+            if average_from is not None:
+                ctx.flow_stats_enable(n_bins=n_bins, every=average_every, t_from=average_from, bands=[(mid_x, mid_hw)])
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -136,6 +171,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
             d = ctx.download(fields=("pos", "vel"))
             pos, vel = d["pos"], d["vel"]
             policy = ctx.grid_policy()
+            if average_from is not None:
+                time_avg = time_average(prm, ctx.flow_stats(0), ctx.flow_stats(1))
         finally:
             ctx.close()
     elif engine == "mex":
@@ -189,4 +226,5 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     return RunResult(prm=prm, n_fluid=nf, n_total=nt, t=t, steps=int(step), wall_seconds=wall, pos=pos, vel=vel,
                      y_mid=y_mid, u_mean=u_mean, u_exact=u_exact, L2_error=l2_error(u_mean, u_exact),
                      profile_times=profile_times, mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t,
-                     tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2, grid_policy=policy, full_profile_u=full_profiles, n_inner=n_inner)
+                     tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2, grid_policy=policy, full_profile_u=full_profiles, n_inner=n_inner,
+                     time_avg=time_avg)

@@ -6,6 +6,11 @@
  *   [tau_bottom, tau_top, n_pairs] = sphx_ctx_mex('monitor', h)
  *   sphx_ctx_mex('prepare', h, n_steps)      % capture the graph an advance(h, t, n_steps) issued next replays
  *   [replayed, eager, captured] = sphx_ctx_mex('graph_stats', h)
+ *   sphx_ctx_mex('stats_enable', h, n_bins, every, t_from, bands)   % bands: [k x 2] (x_centre, half_width), k <= 2
+ *   sphx_ctx_mex('stats_disable', h)   /   sphx_ctx_mex('stats_reset', h)
+ *   sphx_ctx_mex('stats_sample', h)    % add one sample of the current state now
+ *   [N, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples, t_first, t_last] = sphx_ctx_mex('stats_read', h, band)
+ *       band 0 = whole channel, 1.. = the bands given; n_bins x 1 columns (flow statistics, include/sphx.h section 2a)
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -102,6 +107,48 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         plhs[0] = mxCreateDoubleScalar((double)a);
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)b);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar((double)g);
+    } else if (strcmp(cmd, "stats_enable") == 0) {
+        sphx_flow_stats_config fc;
+        const mxArray *b;
+        size_t nb, k;
+        arity(cmd, nrhs, 6, nlhs, 0);
+        b = prhs[5];
+        if (!mxIsDouble(b)) mexErrMsgIdAndTxt("SPHX:Stats:config", "stats_enable: bands must be a double [k x 2] array");
+        nb = mxGetNumberOfElements(b) == 0 ? 0 : mxGetM(b);
+        if (nb > 2 || (nb > 0 && mxGetN(b) != 2)) mexErrMsgIdAndTxt("SPHX:Stats:config", "stats_enable: bands must be [k x 2], k <= 2");
+        memset(&fc, 0, sizeof(fc));
+        fc.n_bins = (int32_t)mxGetScalar(prhs[2]);
+        fc.every = (int32_t)mxGetScalar(prhs[3]);
+        fc.t_from = mxGetScalar(prhs[4]);
+        fc.n_bands = (int32_t)nb;
+        for (k = 0; k < nb; ++k) { fc.band_x[k] = mxGetDoubles(b)[k]; fc.band_hw[k] = mxGetDoubles(b)[k + nb]; }
+        ok(sphx_ctx_flow_stats_enable(handle(prhs[1]), &fc));
+    } else if (strcmp(cmd, "stats_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_flow_stats_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "stats_reset") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_flow_stats_reset(handle(prhs[1])));
+    } else if (strcmp(cmd, "stats_sample") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_flow_stats_sample(handle(prhs[1])));
+    } else if (strcmp(cmd, "stats_read") == 0) {
+        sphx_ctx *c;
+        int band, n_bins = 0, k;
+        int64_t ns = 0;
+        double t0 = 0.0, t1 = 0.0, *out[5] = {0};
+        arity(cmd, nrhs, 3, nlhs, 8);
+        c = handle(prhs[1]);
+        band = (int)mxGetScalar(prhs[2]);
+        ok(sphx_ctx_flow_stats_read(c, band, 0, &n_bins, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL));
+        for (k = 0; k < 5 && k < (nlhs > 0 ? nlhs : 1); ++k) {
+            plhs[k] = mxCreateDoubleMatrix((mwSize)n_bins, 1, mxREAL);
+            out[k] = mxGetDoubles(plhs[k]);
+        }
+        ok(sphx_ctx_flow_stats_read(c, band, n_bins, NULL, out[0], out[1], out[2], out[3], out[4], &ns, &t0, &t1));
+        if (nlhs > 5) plhs[5] = mxCreateDoubleScalar((double)ns);
+        if (nlhs > 6) plhs[6] = mxCreateDoubleScalar(t0);
+        if (nlhs > 7) plhs[7] = mxCreateDoubleScalar(t1);
     } else if (strcmp(cmd, "destroy") == 0) {
         arity(cmd, nrhs, 2, nlhs, 0);
         sphx_ctx_destroy(handle(prhs[1]));

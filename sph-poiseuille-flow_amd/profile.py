@@ -2,6 +2,7 @@
 
 compute_binned_profile_mean / compute_mid_channel_profile: SPH_Poiseuille.m:579-605.
 final_profile: SPH_Poiseuille.m:617-623.  l2_error: SPH_Poiseuille_postprocess.m:37-42.
+flow_stats_profile: the sums of the device's flow statistics (include/sphx.h section 2a) as a profile.
 """
 from __future__ import annotations
 
@@ -52,3 +53,29 @@ def l2_error(u_mean, u_exact):
         raise ValueError("velocity profile bins are all empty")
     return float(np.sqrt(np.sum((u_mean[valid] - u_exact[valid]) ** 2)
                          / max(np.sum(u_exact[valid] ** 2), np.finfo(np.float64).eps)))
+
+
+def flow_stats_profile(DH, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples=0, t_first=np.nan, t_last=np.nan):
+    """Per-bin sums over particle samples -> time-averaged profile.  Bins are those of compute_binned_profile_mean over
+    [0, DH] (len(count) of them).  u_mean = sum u / N; u_std is the pooled spread of the particle samples in a bin,
+    sqrt(max(sum u^2 / N - u_mean^2, 0)); bins without samples give NaN, as compute_binned_profile_mean does."""
+    sums = [np.asarray(a, dtype=np.float64).ravel() for a in (count, sum_ux, sum_ux2, sum_uy, sum_uy2)]
+    N, sx, sxx, sy, syy = sums
+    n_bins = len(N)
+    edges = np.linspace(0.0, DH, n_bins + 1)
+    y_mid = 0.5 * (edges[:-1] + edges[1:])
+    empty = N == 0
+    Nd = np.where(empty, 1.0, N)
+
+    def mean_std(s, ss):
+        m = s / Nd
+        sd = np.sqrt(np.maximum(ss / Nd - m * m, 0.0))
+        m[empty] = np.nan
+        sd[empty] = np.nan
+        return m, sd
+
+    u_mean, u_std = mean_std(sx, sxx)
+    uy_mean, uy_std = mean_std(sy, syy)
+    return dict(y_mid=y_mid, count=N, u_mean=u_mean, u_std=u_std, uy_mean=uy_mean, uy_std=uy_std,
+                n_samples=int(n_samples), t_first=float(t_first), t_last=float(t_last),
+                sum_ux=sx, sum_ux2=sxx, sum_uy=sy, sum_uy2=syy)
