@@ -259,6 +259,52 @@ int sphx_ctx_substeps(sphx_ctx *ctx, int *n_inner);
 int sphx_ctx_info(sphx_ctx *ctx, int *n_fluid, int *n_wall, int *n_cell_x, int *n_cell_y);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2b. Batched contexts: M independent channels of ONE geometry stepped by the same launches (parameter sweeps,
+ *     ensembles of perturbed realisations).  A small channel leaves most of the GPU idle and pays a launch floor per
+ *     step; a batch gives every launch M times the workgroups.
+ *
+ *     Shared by all members (refused with SPHX:Batch:geometry, naming the field and the member, when they differ):
+ *     DL, DH, dp, h, rho0, inv_sigma0, t_end, n_fluid, n_total, the wall particles (positions, mass, wall_vel), the
+ *     cell grid, lanes_per_particle, steps_per_graph, rebuild_every, skin_h.  Per member: mu, c_f, p0, gravity_g,
+ *     transport_coeff and the fluid state.  Batches run the compact kernels only (16 or 32 lanes per particle: what a
+ *     context of up to ~30 k fluid particles runs; larger channels are refused with SPHX:Batch:size) and refuse
+ *     dual_rate > 1 and dynamic_rebin == 1 (SPHX:Batch:mode).  1 <= n_members <= 4096 (SPHX:Batch:members); device
+ *     memory bounds M further on larger channels (about 10 MB per member at 5 760 particles).
+ *
+ *     Every member keeps its own clock: its dt comes from its own state and parameters exactly as in a standalone
+ *     context, and a member that has reached t_target, used up max_steps or stopped on the drift bound sits out the
+ *     rest of the call.  Members that never fell out of step compute bit for bit what standalone contexts with the same
+ *     parameters compute.  When a call ends with members at different points of the re-binning schedule (they reached
+ *     one t_target in different step counts) or a member hit the drift bound, every member is re-binned at once into one
+ *     layout (a "realignment": summation order only); sphx_batch_info counts them.
+ *
+ *     Host arrays in MEX layout as in section 2, one block per member: pos / vel [n_members blocks of n_total x 2],
+ *     drho_dt [n_members blocks of n_total]; mass [n_total] and wall_vel [n_total x 2] are shared.  prm [n_members];
+ *     status [n_members].  A member that diverges stops the batch with SPHX_ERR_DIVERGED (the message names it).
+ * ---------------------------------------------------------------------------------------------- */
+
+typedef struct sphx_batch sphx_batch;
+
+int sphx_batch_create(sphx_batch **batch, int n_members, const sphx_params *prm, int n_fluid, int n_total,
+                      const double *pos, const double *vel, const double *drho_dt, const double *mass,
+                      const double *wall_vel, double t0, int64_t step0);
+void sphx_batch_destroy(sphx_batch *batch);
+/* sphx_ctx_advance for every member: one t_target, one max_steps (<= 0: unlimited) */
+int sphx_batch_advance(sphx_batch *batch, double t_target, int64_t max_steps, sphx_status *status);
+/* sphx_ctx_enqueue_steps / sphx_ctx_sync for every member */
+int sphx_batch_enqueue_steps(sphx_batch *batch, int64_t n_steps);
+int sphx_batch_sync(sphx_batch *batch, sphx_status *status);
+/* sphx_ctx_download / sphx_ctx_monitor of one member (SPHX:Batch:member when out of range) */
+int sphx_batch_download(sphx_batch *batch, int member, double *pos, double *vel, double *rho, double *p,
+                        double *drho_dt, double *force, double *force_prior, double *Vol, double *B);
+int sphx_batch_monitor(sphx_batch *batch, int member, double *tau_bottom, double *tau_top, double *n_pairs);
+/* the shared launch shape and grid policy; forced_rebuilds = realignments caused by the drift bound */
+int sphx_batch_info(sphx_batch *batch, int *n_members, int *lanes_per_particle, int *steps_per_graph,
+                    int *rebuild_every, double *skin, int64_t *forced_rebuilds, int64_t *realignments);
+int sphx_batch_graph_stats(sphx_batch *batch, int64_t *slots_replayed, int64_t *slots_eager,
+                           int64_t *graphs_captured);
+
+/* ------------------------------------------------------------------------------------------------
  * 2a. Flow statistics: time-averaged velocity profiles accumulated on the device, inside the step loop.
  *
  *  Bins: the reference's profile binning (SPH_Poiseuille.m:579-605, profile.compute_binned_profile_mean):

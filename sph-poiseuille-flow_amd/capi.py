@@ -63,6 +63,8 @@ EXPORTS = [
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
+    "sphx_batch_create", "sphx_batch_destroy", "sphx_batch_advance", "sphx_batch_enqueue_steps", "sphx_batch_sync",
+    "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
 ]
 
 _LIB = None
@@ -79,6 +81,7 @@ def lib() -> C.CDLL:
         for name in ("sphx_version", "sphx_last_error", "sphx_last_error_id"):
             getattr(L, name).restype = C.c_char_p
         L.sphx_ctx_destroy.restype = None
+        L.sphx_batch_destroy.restype = None
         _LIB = L
     return _LIB
 
@@ -116,6 +119,119 @@ def make_params(prm, t_end=None, transport_coeff=None, lanes_per_particle=0, ste
                       t_end=prm.t_end if t_end is None else t_end, sort_interval=int(prm.sort_interval),
                       lanes_per_particle=int(lanes_per_particle), steps_per_graph=int(steps_per_graph),
                       dual_rate=int(dual_rate), rebuild_every=int(rebuild_every), dynamic_rebin=int(dynamic_rebin), skin_h=float(skin_h))
+
+
+_FIELDS = ("pos", "vel", "rho", "p", "drho_dt", "force", "force_prior", "Vol", "B")
+
+
+def _field_buffers(nt, fields):
+    shapes = dict(pos=(nt, 2), vel=(nt, 2), rho=(nt,), p=(nt,), drho_dt=(nt,), force=(nt, 2),
+                  force_prior=(nt, 2), Vol=(nt,), B=(nt, 4))
+    out = {k: np.zeros(shapes[k], order="F") for k in fields}
+    return out, [ptr(out[k]) if k in out else None for k in _FIELDS]
+
+
+def _per_member(v, m, name):
+    """A scalar for every member, or one value per member."""
+    if v is None or np.isscalar(v):
+        return [v] * m
+    v = list(v)
+    if len(v) != m:
+        raise SphxError(SPHX_ERR_ARG, "SPHX:Batch:members", f"{name}: one value per member expected ({len(v)} for {m})")
+    return v
+
+
+class Batch:
+    """M channels of one geometry stepped by the same launches (sphx_batch, include/sphx.h section 2b).
+
+    prms: one parameter set per member (mu, c_f, p0, gravity_g, transport_coeff may differ; the geometry, t_end and the
+    launch shape must not).  pos_list / vel_list / drho_list: the members' states, MEX layout as for Context; mass and
+    wall_vel are shared.  transport_coeff may be a scalar or one value per member."""
+
+    def __init__(self, prms, n_fluid, n_total, pos_list, vel_list, drho_list, mass, wall_vel, t0=0.0, step0=0,
+                 t_end=None, transport_coeff=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,
+                 skin_h=0.0, dynamic_rebin=0, dual_rate=0):
+        self._h = C.c_void_p()
+        prms = list(prms)
+        m = len(prms)
+        if m < 1:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:Batch:members", "a batch needs at least one member")
+        self.n_members, self.n_fluid, self.n_total = m, int(n_fluid), int(n_total)
+        nt = self.n_total
+        tcs = _per_member(transport_coeff, m, "transport_coeff")
+        self.params = [make_params(p, t_end, tc, lanes_per_particle, steps_per_graph, rebuild_every, skin_h,
+                                   dynamic_rebin, dual_rate) for p, tc in zip(prms, tcs)]
+        states = []
+        for name, arrs, shape in (("pos", pos_list, (nt, 2)), ("vel", vel_list, (nt, 2)), ("drho_dt", drho_list, (nt,))):
+            arrs = [f64(a) for a in arrs]
+            if len(arrs) != m:
+                raise SphxError(SPHX_ERR_ARG, "SPHX:Batch:members", f"{name}: {len(arrs)} arrays for {m} members")
+            for k, a in enumerate(arrs):
+                if a.shape != shape:
+                    raise SphxError(SPHX_ERR_ARG, "SPHX:Batch:geometry",
+                                    f"member {k}: {name} has shape {a.shape}, the batch's n_total asks for {shape}")
+            # member blocks one after the other, each in MEX (column-major) layout
+            states.append(np.concatenate([a.ravel(order="F") for a in arrs]))
+        mass, wall_vel = f64(mass), f64(wall_vel)
+        if mass.shape != (nt,) or wall_vel.shape != (nt, 2):
+            raise SphxError(SPHX_ERR_ARG, "SPHX:Batch:geometry", "mass / wall_vel: shared arrays of n_total rows expected")
+        arr = (SphxParams * m)(*self.params)
+        check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
+                                      ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
+                                      C.c_double(t0), C.c_int64(step0)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().sphx_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _status(self, arr):
+        return [s.as_dict() for s in arr]
+
+    def advance(self, t_target, max_steps=0) -> list:
+        st = (SphxStatus * self.n_members)()
+        check(lib().sphx_batch_advance(self._h, C.c_double(t_target), C.c_int64(max_steps), st))
+        return self._status(st)
+
+    def enqueue_steps(self, n_steps):
+        check(lib().sphx_batch_enqueue_steps(self._h, C.c_int64(n_steps)))
+
+    def sync(self) -> list:
+        st = (SphxStatus * self.n_members)()
+        check(lib().sphx_batch_sync(self._h, st))
+        return self._status(st)
+
+    def download(self, member, fields=_FIELDS) -> dict:
+        out, args = _field_buffers(self.n_total, fields)
+        check(lib().sphx_batch_download(self._h, C.c_int(member), *args))
+        return out
+
+    def monitor(self, member, tau=True, pairs=False):
+        tb, tt, npairs = C.c_double(0), C.c_double(0), C.c_double(0)
+        check(lib().sphx_batch_monitor(self._h, C.c_int(member), C.byref(tb) if tau else None,
+                                       C.byref(tt) if tau else None, C.byref(npairs) if pairs else None))
+        return tb.value, tt.value, npairs.value
+
+    def info(self) -> dict:
+        m, lpp, spg, k = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        skin, forced, realign = C.c_double(0.0), C.c_int64(0), C.c_int64(0)
+        check(lib().sphx_batch_info(self._h, C.byref(m), C.byref(lpp), C.byref(spg), C.byref(k), C.byref(skin),
+                                    C.byref(forced), C.byref(realign)))
+        return dict(n_members=m.value, lanes_per_particle=lpp.value, steps_per_graph=spg.value, rebuild_every=k.value,
+                    skin=skin.value, forced_rebuilds=forced.value, realignments=realign.value)
+
+    def graph_stats(self) -> dict:
+        a, b, g = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().sphx_batch_graph_stats(self._h, C.byref(a), C.byref(b), C.byref(g)))
+        return dict(slots_replayed=a.value, slots_eager=b.value, graphs_captured=g.value)
 
 
 class Context:

@@ -1,0 +1,603 @@
+// sphx_batch.hpp -- batched contexts (include/sphx.h section 2b), part of the sphx_resident.hip translation unit.
+//
+// A batch steps M independent channels of one geometry with the launches of one: every step-slot kernel of the compact
+// context runs as its "_b" form on a grid of (workgroups of one member) x M, member = blockIdx.y (Members,
+// sphx_kernels.hpp).  Each member is an sphx_ctx whose device arrays are its blocks of batch-wide allocations (BatchArena):
+// the cold paths -- creation, initial sort, downloads, monitors -- are the single-context code run on that member.  The host
+// schedule (re-binning slots, graph phases) is the batch's; every member has its own clock, so a member that has reached
+// its target, used up its steps or stopped on the drift bound sits out the rest of the call.  When a call leaves members at
+// different phases of the schedule, or one of them stopped on the drift bound, every member is re-binned into one phase at
+// pos = 0 (a realignment) -- a change of summation order only.
+#pragma once
+
+struct sphx_batch {
+    int M = 0;
+    std::vector<sphx_ctx *> mem;  // mem[0]'s arrays are the bases of the batch-wide allocations
+    BatchArena arena;
+    hipStream_t stream = nullptr;
+    DevBuf<Phys> phys;
+    Members mb{};
+    Clock *h_clocks = nullptr;        // pinned [M]: all clocks in one copy
+    long long *h_budget = nullptr;    // pinned [M]: step budgets of an arm
+    DevBuf<long long> budget;
+    DevBuf<double> st_mass;           // realignment staging (one member at a time)
+    DevBuf<int> st_id, st_src, out_id;  // (out_id: [M x cap], see sphx_ctx::out_ids)
+    // host schedule, shared by all members
+    int cur = 0, lay = 0, pos = 0;
+    int64_t slot = 0, epoch_slot = 0;  // step slots the batch has taken (members in lockstep); drives the cool-down
+    int64_t cool_until = 0, cool_len = 0;
+    int64_t n_forced = 0, n_realign = 0;
+    std::map<std::array<int, 4>, hipGraphExec_t> graphs;
+    int64_t slots_replayed = 0, slots_eager = 0, graphs_captured = 0;
+    std::vector<int64_t> pending;     // per member: step count the sphx_batch_enqueue_steps calls since the last sync aim for
+
+    void drop_graphs()
+    {
+        for (auto &kv : graphs)
+            if (kv.second) (void)hipGraphExecDestroy(kv.second);
+        graphs.clear();
+    }
+    ~sphx_batch()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        drop_graphs();
+        for (sphx_ctx *c : mem) delete c;  // (before the arena their arrays live in)
+        mem.clear();
+        if (h_clocks) (void)hipHostFree(h_clocks);
+        if (h_budget) (void)hipHostFree(h_budget);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+constexpr int kMaxBatchMembers = 4096;  // (grid rows; memory runs out first on large channels: sphx_batch_create reports it)
+
+// ---- one step slot of the whole batch: launch_step of the compact kernels, on every member at once ----
+template <int LPP>
+void batch_step_t(sphx_batch *b, int q, int l, int pos, bool rebuild)
+{
+    sphx_ctx *c = b->mem[0];
+    const unsigned M = (unsigned)b->M;
+    const Members &mb = b->mb;
+    const int nb = c->n_blocks_particles;
+    const dim3 gp(nb, M), ge(nb + 1, M), gf(c->n_blocks_flat, M), bp(kBlock);
+    const int dmode = c->skin > 0.0 ? (pos == 0 ? 1 : 2) : 0;
+    const FluidSet s = c->view(q, l);
+    const int finish_half = c->fuse_ea ? 1 : 0;
+    auto pass_a = [&](const FluidTmp &t, int mode) {
+        if (mode == 0) launch(c, "k_density", k_density_b<LPP, 0>, gp, bp, mb, q, c->grid, s, t, c->walls, -1);
+        else if (mode == 1) launch(c, "k_density_build", k_density_b<LPP, 1>, gp, bp, mb, q, c->grid, s, t, c->walls, -1);
+        else launch(c, "k_density_walk", k_density_b<LPP, 2>, gp, bp, mb, q, c->grid, s, t, c->walls, -1);
+    };
+    auto passes_bc = [&](const FluidTmp &t) {
+        launch(c, "k_kgc", k_kgc_b<LPP>, gp, bp, mb, q, c->grid, s, t, c->walls, finish_half);
+        launch(c, "k_forces", k_forces_b<LPP>, gp, bp, mb, q, c->grid, s, t, c->walls, 0);
+    };
+    auto pass_e = [&](const FluidTmp &t, int do_hist, int tail) {
+        launch(c, tail ? "k_continuity_clock" : "k_continuity", k_continuity_b<LPP>, tail ? ge : gp, bp, mb, q, c->grid, s, t,
+               c->walls, do_hist, tail);
+    };
+    auto clock_scan = [&](int *start_next) {
+        launch(c, "k_clock_scan", k_clock_scan_b, dim3(1, M), dim3(kScanBlock), mb, q, (const double *)c->vpart.get(),
+               (const int *)c->flags.get(), start_next ? (const int *)c->count.get() : (const int *)nullptr, start_next,
+               c->grid.ncells, c->skin > 0.0 ? (const double *)c->dpart.get() : (const double *)nullptr, start_next ? 1 : 0,
+               c->half_skin(), c->vpart_reset());
+    };
+    if (!rebuild) {
+        const FluidSet o = c->view(1 - q, l);
+        FluidTmp t = c->fuse_ea ? c->tmp_par[q] : c->tmp;
+        t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
+        if (c->fuse_ea) {  // pass A of this step ran in the previous step's last launch, unless the grid is fresh
+            if (pos == 0) pass_a(t, 1);
+            passes_bc(t);
+            launch(c, "k_continuity_density", k_continuity_density_b<LPP>, dim3(2 * nb + 1, M), bp, mb, q, c->grid, s, t, c->walls,
+                   o, c->tmp_par[1 - q], 1);
+            return;
+        }
+        pass_a(t, dmode);
+        passes_bc(t);
+        pass_e(t, 0, c->tail_clock ? 1 : 0);
+        if (!c->tail_clock) clock_scan(nullptr);
+        return;
+    }
+    const FluidTmp &t = c->fuse_ea ? c->tmp_par[q] : c->tmp;
+    if (!c->fuse_ea || pos == 0) pass_a(t, c->fuse_ea ? 1 : dmode);
+    passes_bc(t);
+    pass_e(t, 1, 0);
+    const FluidSet d = c->view(1 - q, 1 - l);
+    clock_scan(d.start);
+    launch(c, "k_scatter", k_scatter_b, gf, bp, mb, q, (const int *)c->cellid.get(), c->count.get(), (const int *)d.start,
+           c->perm.get());
+    launch(c, "k_reorder", k_reorder_b, gf, bp, mb, q, (const int *)c->cellid.get(), (const int *)d.start,
+           (const int *)c->perm.get(), reorder_args(c->tmp.posn, c->tmp.veln, c->tmp.drhon, s.mass, s.id, d, c->tmp.src_of));
+}
+
+void batch_step(sphx_batch *b, int q, int l, int pos, bool rebuild)
+{
+    if (b->mem[0]->lpp == 16) batch_step_t<16>(b, q, l, pos, rebuild);
+    else batch_step_t<32>(b, q, l, pos, rebuild);
+}
+
+bool batch_slot_rebuilds(const sphx_batch *b)
+{
+    return b->pos >= b->mem[0]->rebuild_every - 1 || b->slot < b->cool_until;
+}
+
+void batch_track(sphx_batch *b)
+{
+    const bool rebuild = batch_slot_rebuilds(b);
+    b->slot += 1;
+    b->cur ^= 1;
+    if (rebuild) { b->lay ^= 1; b->pos = 0; }
+    else b->pos += 1;
+}
+
+hipGraphExec_t batch_graph(sphx_batch *b, int n)
+{
+    const std::array<int, 4> key{b->cur, b->lay, b->pos, n};
+    auto it = b->graphs.find(key);
+    if (it != b->graphs.end()) return it->second;
+    if (b->graphs.size() >= kMaxGraphs) {
+        SPHX_HIP(hipStreamSynchronize(b->stream));
+        b->drop_graphs();
+    }
+    const int K = b->mem[0]->rebuild_every;
+    SPHX_HIP(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
+    try {
+        int q = b->cur, l = b->lay, p = b->pos;
+        for (int j = 0; j < n; ++j) {
+            const bool rebuild = p == K - 1;
+            batch_step(b, q, l, p, rebuild);
+            if (rebuild) { l ^= 1; p = 0; }
+            else ++p;
+            q ^= 1;
+        }
+    } catch (...) {
+        hipGraph_t junk = nullptr;
+        (void)hipStreamEndCapture(b->stream, &junk);
+        if (junk) (void)hipGraphDestroy(junk);
+        throw;
+    }
+    hipGraph_t g = nullptr;
+    SPHX_HIP(hipStreamEndCapture(b->stream, &g));
+    hipGraphExec_t exec = nullptr;
+    const hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    SPHX_HIP(e);
+    b->graphs[key] = exec;
+    b->graphs_captured += 1;
+    return exec;
+}
+
+// enqueue_slots for a batch: whole graphs from any phase, exact tails as graphs of their own, cool-downs eagerly
+void batch_enqueue(sphx_batch *b, int64_t slots, bool exact_tail)
+{
+    int64_t left = slots;
+    while (left > 0) {
+        const int per_graph = graph_slots(b->mem[0]);
+        int n = 0;
+        if (b->slot >= b->cool_until) {
+            if (left >= per_graph) n = per_graph;
+            else if (exact_tail && left >= kMinGraphSlots) n = (int)left;
+        }
+        if (n > 0) {
+            SPHX_HIP(hipGraphLaunch(batch_graph(b, n), b->stream));
+            b->slots_replayed += n;
+            for (int k = 0; k < n; ++k) batch_track(b);
+            left -= n;
+            continue;
+        }
+        batch_step(b, b->cur, b->lay, b->pos, batch_slot_rebuilds(b));
+        b->slots_eager += 1;
+        batch_track(b);
+        --left;
+    }
+    SPHX_HIP(hipGetLastError());
+}
+
+// arm every member's clock: one budget for all (max_steps) or one per member (b->h_budget, budgets = true)
+void batch_arm(sphx_batch *b, double t_target, long long max_steps, bool budgets)
+{
+    for (sphx_ctx *c : b->mem) c->host_seq += 1;
+    const long long *dev_budget = nullptr;
+    if (budgets) {
+        SPHX_HIP(hipMemcpyAsync(b->budget.get(), b->h_budget, sizeof(long long) * b->M, hipMemcpyHostToDevice, b->stream));
+        dev_budget = b->budget.get();
+    }
+    hipLaunchKernelGGL(k_prepare_b, dim3(1, b->M), dim3(1), 0, b->stream, b->mb, t_target, max_steps, dev_budget, b->cur);
+    SPHX_HIP(hipGetLastError());
+}
+
+// every member at the batch's phase, epoch = now (its cool-down expressed in its own step count)
+void batch_set_epochs(sphx_batch *b)
+{
+    for (sphx_ctx *c : b->mem) {
+        c->cur = b->cur; c->lay = b->lay; c->pos = b->pos;
+        set_epoch(c);
+        c->cool_until = c->h_clock->step + std::max<int64_t>(0, b->cool_until - b->slot);
+    }
+    b->epoch_slot = b->slot;
+}
+
+// Re-bin member m from wherever its state is into (Q, L), pos 0.  The source is staged first, so any (Q, L) will do; the
+// outputs of the member's last step stay where they are, reachable through out_ids / src_of (see sphx_ctx::out_ids).
+void realign_member(sphx_batch *b, int m, int Q, int L)
+{
+    sphx_ctx *c = b->mem[m];
+    hipStream_t st = b->stream;
+    const int n = c->h_clock->n, q = c->cur, l = c->lay;
+    const FluidSet s = c->view(q, l), d = c->view(Q, L);
+    const bool outputs = c->have_step_outputs;
+    const bool mapped = outputs && (c->out_ids != nullptr || c->out_lay != l);  // src_of: current slot -> output slot
+    auto copy = [&](void *dst, const void *src, size_t bytes) {
+        SPHX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
+    };
+    if (outputs && !c->out_ids) {
+        int *ids = b->out_id.get() + (size_t)m * c->cap;
+        copy(ids, c->fid_[c->out_lay].get(), sizeof(int) * n);
+        c->out_ids = ids;
+    }
+    if (mapped) copy(b->st_src.get(), c->src_of.get(), sizeof(int) * n);
+    copy(c->posn.get(), s.pos, sizeof(double2) * n);
+    copy(c->veln.get(), s.vel, sizeof(double2) * n);
+    copy(c->drhon.get(), s.drho, sizeof(double) * n);
+    copy(b->st_mass.get(), s.mass, sizeof(double) * n);
+    copy(b->st_id.get(), s.id, sizeof(int) * n);
+    const dim3 g1(div_up(n, kBlock)), bp(kBlock);
+    hipLaunchKernelGGL(k_bin, g1, bp, 0, st, (const Clock *)nullptr, 0, c->grid, n, (const double2 *)c->posn.get(), c->cellid.get(),
+                       c->count.get());
+    hipLaunchKernelGGL(k_scan_only, dim3(1), dim3(kScanBlock), 0, st, (const Clock *)nullptr, 0, (const int *)c->count.get(), d.start,
+                       c->grid.ncells);
+    hipLaunchKernelGGL(k_scatter, g1, bp, 0, st, (const Clock *)nullptr, 0, n, (const int *)c->cellid.get(), c->count.get(),
+                       (const int *)d.start, c->perm.get());
+    hipLaunchKernelGGL(k_reorder, g1, bp, 0, st, (const Clock *)nullptr, 0, n, (const int *)c->cellid.get(), (const int *)d.start,
+                       (const int *)c->perm.get(),
+                       reorder_args(c->posn.get(), c->veln.get(), c->drhon.get(), b->st_mass.get(), b->st_id.get(), d, c->src_of.get()));
+    if (mapped) hipLaunchKernelGGL(k_compose, g1, bp, 0, st, n, (const int *)b->st_src.get(), c->src_of.get());
+    hipLaunchKernelGGL(k_rebinned, dim3(1), dim3(1), 0, st, c->clock.get());
+    SPHX_HIP(hipGetLastError());
+    c->cur = Q; c->lay = L; c->pos = 0;
+    c->h_clock->need_rebuild = 0;
+    c->h_clock->drift = 0.0;
+    if (c->h_pub) { c->h_pub->need_rebuild = 0; c->h_pub->drift = 0.0; }
+}
+
+// all members into one phase at pos 0; forced: because the drift bound was hit (batch-wide cool-down, as forced_rebuild)
+void realign(sphx_batch *b, bool forced)
+{
+    const int Q = 1 - b->mem[0]->cur, L = 1 - b->mem[0]->lay;
+    for (int m = 0; m < b->M; ++m) realign_member(b, m, Q, L);
+    SPHX_HIP(hipStreamSynchronize(b->stream));
+    b->cur = Q; b->lay = L; b->pos = 0;
+    b->n_realign += 1;
+    if (forced) {
+        const int64_t now = b->slot, K = b->mem[0]->rebuild_every;
+        const bool again = b->n_forced > 0 && now - b->cool_until <= 2 * K;
+        b->cool_len = again ? std::min<int64_t>(2 * std::max<int64_t>(b->cool_len, 16), 1024) : 16;
+        b->cool_until = now + b->cool_len;
+        b->n_forced += 1;
+        if (debug_switches().log)
+            fprintf(stderr, "sphx: batch forced re-binning #%lld at slot %lld\n", (long long)b->n_forced, (long long)now);
+    }
+    batch_set_epochs(b);
+}
+
+void batch_throw_on_status(const sphx_batch *b)
+{
+    for (int m = 0; m < b->M; ++m) {
+        const int st = b->mem[m]->h_clock->status;
+        if (st == 0) continue;
+        const std::string who = "member " + std::to_string(m) + ": ";
+        if (st == SPHX_ERR_GRID) throw Error(SPHX_ERR_GRID, "SPHX:Batch:grid", who + "neighbour list capacity exceeded on device");
+        throw Error(st, "SPHX:Batch:diverged", who + "device step loop raised a status (non-finite velocity)");
+    }
+}
+
+// Wait, read every clock, replay each member's executed steps from the epoch; realign when the members ended up at
+// different phases or one of them stopped on the drift bound.  Returns the steps each member executed.
+std::vector<int64_t> batch_read(sphx_batch *b)
+{
+    wait_stream(b->mem[0]);
+    SPHX_HIP(hipMemcpyAsync(b->h_clocks, b->mb.clk, sizeof(Clock) * b->M, hipMemcpyDeviceToHost, b->stream));
+    SPHX_HIP(hipStreamSynchronize(b->stream));
+    std::vector<int64_t> ex(b->M);
+    int64_t e_max = 0;
+    bool same = true, drift = false, bad = false;
+    for (int m = 0; m < b->M; ++m) {
+        sphx_ctx *c = b->mem[m];
+        *c->h_clock = b->h_clocks[m];
+        ex[m] = c->h_clock->step - c->epoch_step;
+        replay_executed(c);  // (ends with set_epoch)
+        if (ex[m] > 0) c->out_ids = nullptr;  // a new step wrote new outputs in the current layout
+        e_max = std::max(e_max, ex[m]);
+        const sphx_ctx *c0 = b->mem[0];
+        same = same && c->cur == c0->cur && c->lay == c0->lay && c->pos == c0->pos;
+        drift = drift || c->h_clock->need_rebuild;
+        bad = bad || c->h_clock->status != 0;
+    }
+    b->slot = b->epoch_slot + e_max;
+    if (bad) return ex;  // (the caller throws; nothing is stepped again)
+    if (same && !drift) {
+        b->cur = b->mem[0]->cur; b->lay = b->mem[0]->lay; b->pos = b->mem[0]->pos;
+        batch_set_epochs(b);
+    } else {
+        realign(b, drift);
+    }
+    return ex;
+}
+
+// Step every member until it reaches t_target (clipped to t_end) or its budget (h_budget semantics: < 0 unlimited)
+void batch_run(sphx_batch *b, double t_target, std::vector<int64_t> budget)
+{
+    for (int guard = 0; guard < 1000000; ++guard) {
+        batch_throw_on_status(b);
+        int64_t want = 0, most = 0;
+        bool limited = true;
+        for (int m = 0; m < b->M; ++m) {
+            const sphx_ctx *c = b->mem[m];
+            const Clock &k = *c->h_clock;
+            const double goal = std::min(t_target, k.t_end);
+            if (budget[m] == 0 || !(k.t < goal - 1e-12)) continue;
+            const double dt_est = host_dt_unclipped(c, k.vmax);
+            want = std::max<int64_t>(want, (int64_t)std::ceil(std::max(0.0, goal - k.t) / std::max(dt_est, 1e-12)) + 1);
+            if (budget[m] < 0) limited = false;
+            else most = std::max(most, budget[m]);
+        }
+        if (want == 0) break;
+        int64_t slots = std::min<int64_t>(want, b->n_forced ? 256 : 4096);
+        bool exact = false;
+        const int per_graph = graph_slots(b->mem[0]);
+        if (limited && slots >= most) { slots = most; exact = true; }
+        else if (slots > per_graph) slots = ((slots + per_graph - 1) / per_graph) * per_graph;
+        // (k_prepare: a budget <= 0 is "unlimited"; a member whose budget is used up is armed and disarmed at once, so that
+        //  it sits the call out)
+        for (int m = 0; m < b->M; ++m) b->h_budget[m] = budget[m] > 0 ? budget[m] : (budget[m] == 0 ? 1 : -1);
+        batch_arm(b, t_target, 0, true);
+        for (int m = 0; m < b->M; ++m)
+            if (budget[m] == 0) hipLaunchKernelGGL(k_disarm, dim3(1), dim3(1), 0, b->stream, b->mem[m]->clock.get());
+        batch_enqueue(b, slots, exact);
+        const std::vector<int64_t> ex = batch_read(b);
+        for (int m = 0; m < b->M; ++m)
+            if (budget[m] > 0) budget[m] = std::max<int64_t>(0, budget[m] - ex[m]);
+    }
+    batch_throw_on_status(b);
+    for (int m = 0; m < b->M; ++m) b->pending[m] = b->mem[m]->h_clock->step;
+    for (sphx_ctx *c : b->mem) c->pending_target = c->h_clock->step;
+}
+
+// what sphx_batch_enqueue_steps calls still owe, then status
+void batch_settle(sphx_batch *b)
+{
+    batch_read(b);
+    std::vector<int64_t> owed(b->M);
+    for (int m = 0; m < b->M; ++m) owed[m] = std::max<int64_t>(0, b->pending[m] - b->mem[m]->h_clock->step);
+    batch_run(b, std::numeric_limits<double>::infinity(), owed);
+}
+
+void batch_check_member(const sphx_batch *b, int m)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    if (m < 0 || m >= b->M)
+        throw Error(SPHX_ERR_ARG, "SPHX:Batch:member", "member " + std::to_string(m) + " out of range [0, " + std::to_string(b->M) + ")");
+}
+
+// argument checks (no device): shared fields, refused modes, the kernel forms members of this size would run
+void batch_check(int M, const sphx_params *prm, int n_fluid, int n_total, const double *pos, const double *vel,
+                 const double *drho_dt, const double *mass, const double *wall_vel)
+{
+    if (M < 1 || M > kMaxBatchMembers)
+        throw Error(SPHX_ERR_ARG, "SPHX:Batch:members", "n_members must be 1.." + std::to_string(kMaxBatchMembers));
+    require(prm != nullptr, "SPHX:Ctx:params", "params must not be NULL");
+    require(pos && vel && drho_dt && mass && wall_vel, "SPHX:Batch:null", "pos / vel / drho_dt / mass / wall_vel must not be NULL");
+    for (int m = 0; m < M; ++m) common_checks(&prm[m], n_fluid, n_total);
+    auto differs = [&](int m, const char *field) {
+        throw Error(SPHX_ERR_ARG, "SPHX:Batch:geometry",
+                    std::string("member ") + std::to_string(m) + ": " + field + " differs from member 0 (members share one geometry)");
+    };
+    const sphx_params &p0 = prm[0];
+    for (int m = 0; m < M; ++m) {
+        const sphx_params &p = prm[m];
+        if (p.dual_rate > 1)
+            throw Error(SPHX_ERR_ARG, "SPHX:Batch:mode", "member " + std::to_string(m) + ": batches run the single-rate loop (dual_rate <= 1)");
+        if (p.dynamic_rebin == 1)
+            throw Error(SPHX_ERR_ARG, "SPHX:Batch:mode", "member " + std::to_string(m) + ": batches re-bin on the host's schedule (dynamic_rebin != 1)");
+        if (p.dp != p0.dp) differs(m, "dp");
+        if (p.DL != p0.DL) differs(m, "DL");
+        if (p.DH != p0.DH) differs(m, "DH");
+        if (p.h != p0.h) differs(m, "h");
+        if (p.rho0 != p0.rho0) differs(m, "rho0");
+        if (p.inv_sigma0 != p0.inv_sigma0) differs(m, "inv_sigma0");
+        if (p.t_end != p0.t_end) differs(m, "t_end");
+        if (p.lanes_per_particle != p0.lanes_per_particle) differs(m, "lanes_per_particle");
+        if (p.steps_per_graph != p0.steps_per_graph) differs(m, "steps_per_graph");
+        if (p.rebuild_every != p0.rebuild_every) differs(m, "rebuild_every");
+        if (p.skin_h != p0.skin_h) differs(m, "skin_h");
+        if (p.dynamic_rebin != p0.dynamic_rebin) differs(m, "dynamic_rebin");
+    }
+    const size_t nt = (size_t)n_total, nf = (size_t)n_fluid;
+    for (int m = 1; m < M; ++m) {
+        const double *pm = pos + 2 * nt * m;
+        for (size_t k = nf; k < nt; ++k)
+            if (pm[k] != pos[k] || pm[nt + k] != pos[nt + k]) differs(m, "wall positions");
+    }
+    sphx_ctx c0;
+    for (int m = 0; m < M; ++m) {
+        sphx_ctx c;
+        ctx_configure(&c, &prm[m], n_fluid, n_total, pos + 2 * nt * m);
+        if (m == 0) ctx_configure(&c0, &prm[0], n_fluid, n_total, pos);
+        if (c.lpp < 16 || c.dyn)
+            throw Error(SPHX_ERR_ARG, "SPHX:Batch:size", "channels of this size run the large-channel kernels (" + std::to_string(c.lpp) +
+                                                          " lanes per particle" + (c.dyn ? ", device-decided re-binning" : "") +
+                                                          "); batches run the compact kernels (16 or 32 lanes per particle)");
+        if (c.grid.ncells > kBigScanCells || div_up((size_t)c.nf * c.lpp, kBlock) > (size_t)(4 * kMaxTile))
+            throw Error(SPHX_ERR_ARG, "SPHX:Batch:size", "channel too large for a batch (cells scanned by one workgroup, per-workgroup "
+                                                          "maxima reduced by one workgroup)");
+        if (c.lpp != c0.lpp) differs(m, "lanes per particle");
+        if (c.rebuild_every != c0.rebuild_every || c.skin != c0.skin) differs(m, "re-binning interval / skin");
+        if (c.grid.ncx != c0.grid.ncx || c.grid.ncy != c0.grid.ncy || c.grid.y0 != c0.grid.y0) differs(m, "cell grid (y extent)");
+    }
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_batch_create(sphx_batch **out, int n_members, const sphx_params *prm, int n_fluid, int n_total,
+                                  const double *pos, const double *vel, const double *drho_dt, const double *mass,
+                                  const double *wall_vel, double t0, int64_t step0)
+{
+    sphx_batch *b = nullptr;
+    try {
+        require(out != nullptr, "SPHX:Batch:out", "batch output pointer must not be NULL");
+        batch_check(n_members, prm, n_fluid, n_total, pos, vel, drho_dt, mass, wall_vel);
+        ensure_device();
+        const int M = n_members;
+        const size_t nt = (size_t)n_total;
+        b = new sphx_batch();
+        b->M = M;
+        b->arena.n_members = M;
+        b->pending.assign(M, step0);
+        SPHX_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+        std::vector<int> wid((size_t)std::max(n_total - n_fluid, 1));
+        for (int k = 0; k < n_total - n_fluid; ++k) wid[k] = n_fluid + k;
+        std::vector<Phys> ph(M);
+        for (int m = 0; m < M; ++m) {
+            sphx_ctx *c = new sphx_ctx();
+            b->mem.push_back(c);
+            const double *pm = pos + 2 * nt * m, *vm = vel + 2 * nt * m, *dm = drho_dt + nt * m;
+            ctx_configure(c, &prm[m], n_fluid, n_total, pm);
+            c->stream = b->stream;
+            c->own_stream = false;
+            c->arena = &b->arena;
+            c->member = m;
+            SPHX_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_clock), sizeof(Clock), hipHostMallocDefault));
+            ctx_alloc(c, n_fluid);
+            upload_fluid(c, n_fluid, pm, pm + nt, vm, vm + nt, dm, mass, nullptr, true);
+            if (m == 0) {
+                upload_walls(c, n_total - n_fluid, pm + n_fluid, pm + nt + n_fluid, mass + n_fluid, wall_vel + n_fluid,
+                             wall_vel + nt + n_fluid, wid.data(), true);
+            } else {  // walls, wall cells and grid: member 0's
+                const sphx_ctx *c0 = b->mem[0];
+                c->wpos.alias(c0->wpos.get(), c0->wpos.size()); c->wa.alias(c0->wa.get(), c0->wa.size());
+                c->wid.alias(c0->wid.get(), c0->wid.size()); c->wstart.alias(c0->wstart.get(), c0->wstart.size());
+                c->wrow_any.alias(c0->wrow_any.get(), c0->wrow_any.size());
+                c->walls = c0->walls;
+            }
+            init_clock(c, n_fluid, t0, step0);
+            ph[m] = c->phys;
+        }
+        sphx_ctx *c0 = b->mem[0];
+        for (sphx_ctx *c : b->mem) read_clock(c);
+        b->phys.alloc(M);
+        b->phys.upload(ph.data(), M, b->stream);
+        b->mb = Members{c0->clock.get(), b->phys.get(), (long long)c0->cap, c0->grid.ncells + 1, c0->n_vpart, c0->tmp.nl_stride,
+                        (long long)c0->tmp.nl_stride * c0->tmp.nl_cap, (long long)c0->tmp.nl_stride * c0->tmp.sl_cap};
+        if (M > 1 && (b->mem[1]->clock.get() != c0->clock.get() + 1 || b->mem[1]->fpos_[0].get() != c0->fpos_[0].get() + c0->cap ||
+                      b->mem[1]->nl_idx.get() != c0->nl_idx.get() + b->mb.list))
+            throw Error(SPHX_ERR_STATE, "SPHX:Batch:internal", "member arrays are not laid out at the member strides");
+        b->st_mass.alloc(c0->cap); b->st_id.alloc(c0->cap); b->st_src.alloc(c0->cap);
+        b->out_id.alloc((size_t)M * c0->cap);
+        b->budget.alloc(M);
+        SPHX_HIP(hipHostMalloc(reinterpret_cast<void **>(&b->h_clocks), sizeof(Clock) * M, hipHostMallocDefault));
+        SPHX_HIP(hipHostMalloc(reinterpret_cast<void **>(&b->h_budget), sizeof(long long) * M, hipHostMallocDefault));
+        SPHX_HIP(hipStreamSynchronize(b->stream));
+        batch_set_epochs(b);
+        if (prm[0].t_end > t0) (void)batch_graph(b, graph_slots(c0));
+        *out = b;
+        return SPHX_OK;
+    } catch (const Error &e) {
+        delete b;
+        return report(e);
+    } catch (const std::exception &e) {
+        delete b;
+        return report_unknown(e);
+    }
+}
+
+SPHX_EXPORT void sphx_batch_destroy(sphx_batch *b)
+{
+    delete b;
+}
+
+SPHX_EXPORT int sphx_batch_advance(sphx_batch *b, double t_target, int64_t max_steps, sphx_status *status)
+{
+    SPHX_TRY
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    batch_settle(b);  // sphx_batch_enqueue_steps calls may still be in flight
+    batch_run(b, t_target, std::vector<int64_t>(b->M, max_steps > 0 ? max_steps : -1));
+    if (status)
+        for (int m = 0; m < b->M; ++m) fill_status(b->mem[m], &status[m]);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_enqueue_steps(sphx_batch *b, int64_t n_steps)
+{
+    SPHX_TRY
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    require(n_steps > 0, "SPHX:Batch:steps", "n_steps must be positive");
+    // no host sync: a member that stopped early (end time, status, drift bound) stays stopped when k_prepare re-evaluates its
+    // loop condition; sphx_batch_sync realigns and takes the steps still owed
+    batch_arm(b, b->mem[0]->prm.t_end, (long long)n_steps, false);
+    batch_enqueue(b, n_steps, true);
+    for (int m = 0; m < b->M; ++m) b->pending[m] = std::max<int64_t>(b->pending[m], b->mem[m]->h_clock->step) + n_steps;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_sync(sphx_batch *b, sphx_status *status)
+{
+    SPHX_TRY
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    batch_settle(b);
+    if (status)
+        for (int m = 0; m < b->M; ++m) fill_status(b->mem[m], &status[m]);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_download(sphx_batch *b, int member, double *pos, double *vel, double *rho, double *p, double *drho_dt,
+                                    double *force, double *force_prior, double *Vol, double *B)
+{
+    SPHX_TRY
+    batch_check_member(b, member);
+    batch_settle(b);
+    SPHX_CATCH
+    return sphx_ctx_download(b->mem[member], pos, vel, rho, p, drho_dt, force, force_prior, Vol, B);
+}
+
+SPHX_EXPORT int sphx_batch_monitor(sphx_batch *b, int member, double *tau_bottom, double *tau_top, double *n_pairs)
+{
+    SPHX_TRY
+    batch_check_member(b, member);
+    batch_settle(b);
+    SPHX_CATCH
+    return sphx_ctx_monitor(b->mem[member], tau_bottom, tau_top, n_pairs);
+}
+
+SPHX_EXPORT int sphx_batch_info(sphx_batch *b, int *n_members, int *lanes_per_particle, int *steps_per_graph, int *rebuild_every,
+                                double *skin, int64_t *forced_rebuilds, int64_t *realignments)
+{
+    SPHX_TRY
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    const sphx_ctx *c = b->mem[0];
+    if (n_members) *n_members = b->M;
+    if (lanes_per_particle) *lanes_per_particle = c->lpp;
+    if (steps_per_graph) *steps_per_graph = graph_slots(c);
+    if (rebuild_every) *rebuild_every = c->rebuild_every;
+    if (skin) *skin = c->skin;
+    if (forced_rebuilds) *forced_rebuilds = b->n_forced;
+    if (realignments) *realignments = b->n_realign;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_graph_stats(sphx_batch *b, int64_t *slots_replayed, int64_t *slots_eager, int64_t *graphs_captured)
+{
+    SPHX_TRY
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    if (slots_replayed) *slots_replayed = b->slots_replayed;
+    if (slots_eager) *slots_eager = b->slots_eager;
+    if (graphs_captured) *graphs_captured = b->graphs_captured;
+    return SPHX_OK;
+    SPHX_CATCH
+}

@@ -171,6 +171,53 @@ struct Walls {
     int n;
 };
 
+// A batch (sphx_batch_*): M channels of one geometry stepped by the same launches.  Member m is blockIdx.y of every "_b"
+// kernel.  Each per-member array is ONE allocation of M blocks, member m's block at base + m * stride: the FluidSet /
+// FluidTmp / raw pointers a "_b" kernel receives are those of member 0, and member_view moves them to member m.  Walls and
+// Grid are shared and stored once; clocks and the parameters that may differ (Phys) are tables indexed by member.  The
+// bodies are the ones the single-channel kernels run (same source, same flags): a member's arithmetic is bit for bit that
+// of a standalone context.
+struct Members {
+    Clock *clk;         // [M]
+    const Phys *ph;     // [M]
+    long long part;     // stride of the per-particle arrays (FluidTmp::cap)
+    int cells;          // ... of cell ranges and histograms (ncells + 1)
+    int blocks;         // ... of the per-workgroup maxima (n_vpart)
+    int lanes;          // ... of the list row counts (nl_stride)
+    long long list, slist;  // ... of the step list and the superset list (nl_stride * nl_cap, nl_stride * sl_cap)
+};
+
+template <typename T>
+__device__ __forceinline__ T *member_ptr(T *p, long long stride, int m)
+{
+    return p ? p + stride * m : p;  // (nullptr stays nullptr: optional arrays)
+}
+
+__device__ __forceinline__ FluidSet member_set(const Members &mb, int m, FluidSet s)
+{
+    s.pos = member_ptr(s.pos, mb.part, m); s.vel = member_ptr(s.vel, mb.part, m);
+    s.drho = member_ptr(s.drho, mb.part, m); s.mass = member_ptr(s.mass, mb.part, m);
+    s.id = member_ptr(s.id, mb.part, m); s.cell = member_ptr(s.cell, mb.part, m); s.posb = member_ptr(s.posb, mb.part, m);
+    s.start = member_ptr(s.start, mb.cells, m);
+    return s;
+}
+
+__device__ __forceinline__ FluidTmp member_tmp(const Members &mb, int m, FluidTmp t)
+{
+    const long long P = mb.part;
+    t.posn = member_ptr(t.posn, P, m); t.veln = member_ptr(t.veln, P, m); t.drhon = member_ptr(t.drhon, P, m);
+    t.a = member_ptr(t.a, P, m); t.B = member_ptr(t.B, P, m); t.fp = member_ptr(t.fp, P, m); t.f = member_ptr(t.f, P, m);
+    t.rho_out = member_ptr(t.rho_out, P, m); t.p_out = member_ptr(t.p_out, P, m); t.vol = member_ptr(t.vol, P, m);
+    t.cellid = member_ptr(t.cellid, P, m); t.perm = member_ptr(t.perm, P, m); t.src_of = member_ptr(t.src_of, P, m);
+    t.count = member_ptr(t.count, (long long)mb.cells, m);
+    t.vpart = member_ptr(t.vpart, (long long)mb.blocks, m); t.dpart = member_ptr(t.dpart, (long long)mb.blocks, m);
+    t.nl_idx = member_ptr(t.nl_idx, mb.list, m); t.sl_idx = member_ptr(t.sl_idx, mb.slist, m);
+    t.nl_cnt = member_ptr(t.nl_cnt, (long long)mb.lanes, m); t.sl_cnt = member_ptr(t.sl_cnt, (long long)mb.lanes, m);
+    t.flags = member_ptr(t.flags, 1ll, m);
+    t.tile_sum = nullptr;  // (batches scan their cells in one workgroup, see sphx_batch_create)
+    return t;
+}
+
 __device__ __forceinline__ void cell_of(const Grid &g, double x, double y, int &cx, int &cy)
 {
     cx = (int)floor((x - g.x0) * g.inv_csx);
@@ -335,8 +382,8 @@ __device__ __forceinline__ bool slot_active(const Clock *clk, int qf)
 
 // one thread: arm the clock for an advance call.  vmax_in (optional) overrides the stored vmax (slab:
 // the all-reduced global value).
-__global__ void k_prepare(Clock *clk, Phys ph, double t_target, long long max_steps, int q0,
-                          const double *vmax_in)
+__device__ __forceinline__ void prepare_clock(Clock *clk, const Phys &ph, double t_target, long long max_steps, int q0,
+                                              const double *vmax_in)
 {
     Clock c = *clk;
     if (vmax_in) c.vmax = *vmax_in;
@@ -352,6 +399,18 @@ __global__ void k_prepare(Clock *clk, Phys ph, double t_target, long long max_st
     c.seq += 1;
     *clk = c;
     if (!go && c.pub) *c.pub = c;
+}
+__global__ void k_prepare(Clock *clk, Phys ph, double t_target, long long max_steps, int q0, const double *vmax_in)
+{
+    prepare_clock(clk, ph, t_target, max_steps, q0, vmax_in);
+}
+// batch: one workgroup of one thread per member; max_steps_of (optional): a step budget per member instead of max_steps
+__global__ __launch_bounds__(64) void k_prepare_b(Members mb, double t_target, long long max_steps, const long long *max_steps_of,
+                                                  int q0)
+{
+    const int m = (int)blockIdx.y;
+    const Phys ph = mb.ph[m];
+    prepare_clock(mb.clk + m, ph, t_target, max_steps_of ? max_steps_of[m] : max_steps, q0, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -674,14 +733,29 @@ __device__ __forceinline__ bool slab_part_skips(const Grid &g, const FluidSet &s
 // returns 786 us; one kernel holding both bodies 891 us (it runs at the register budget of the bigger one); one
 // body deciding per candidate at run time 795 us.
 template <int LPP, int MODE>
-__global__ __launch_bounds__(kBlock) void k_density(const Clock *clk, int q, Grid g, Phys ph,
-                                                    FluidSet s, FluidTmp t, Walls w, int cond_fresh)
+__device__ __forceinline__ void density_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
+                                             const FluidTmp &t, const Walls &w, int cond_fresh)
 {
     const int part = cond_fresh >= 0 ? cond_fresh >> kPassPartShift : 0;
     if (part) cond_fresh &= (1 << kPassPartShift) - 1;
     if (cond_fresh >= 0 && (clk->fresh != 0) != (cond_fresh != 0)) return;
     if (MODE == 2 && part && slab_part_skips<LPP>(g, s, xcd_block((int)blockIdx.x, (int)gridDim.x), part)) return;
     density_body<LPP, MODE>(clk, q, g, ph, s, t, w, (int)blockIdx.x, (int)gridDim.x, true);
+}
+template <int LPP, int MODE>
+__global__ __launch_bounds__(kBlock) void k_density(const Clock *clk, int q, Grid g, Phys ph,
+                                                    FluidSet s, FluidTmp t, Walls w, int cond_fresh)
+{
+    density_pass<LPP, MODE>(clk, q, g, ph, s, t, w, cond_fresh);
+}
+// (the "_b" wrappers take the run-time arguments of their single-channel kernels as run-time arguments too: a constant there
+//  would let the compiler merge the bodies' blocks differently, and its fused multiply-adds -- so the last bits -- with them)
+template <int LPP, int MODE>
+__global__ __launch_bounds__(kBlock) void k_density_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w, int cond_fresh)
+{
+    const int m = (int)blockIdx.y;
+    const Phys ph = mb.ph[m];
+    density_pass<LPP, MODE>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, cond_fresh);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -691,8 +765,8 @@ __global__ __launch_bounds__(kBlock) void k_density(const Clock *clk, int q, Gri
 // ---------------------------------------------------------------------------------------------
 // finish_half: pass A of this step ran inside the previous step's fused launch and left {p_half, rho_half} open
 template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_kgc(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
-                                                FluidTmp t, Walls w, int finish_half)
+__device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
+                                         const FluidTmp &t, const Walls &w, int finish_half)
 {
     SPHX_PASS_INDEX();
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
@@ -741,6 +815,19 @@ __global__ __launch_bounds__(kBlock) void k_kgc(const Clock *clk, int q, Grid g,
         }
     }
 }
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_kgc(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
+                                                FluidTmp t, Walls w, int finish_half)
+{
+    kgc_pass<LPP>(clk, q, g, ph, s, t, w, finish_half);
+}
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_kgc_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w, int finish_half)
+{
+    const int m = (int)blockIdx.y;
+    const Phys ph = mb.ph[m];
+    kgc_pass<LPP>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, finish_half);
+}
 
 // ---------------------------------------------------------------------------------------------
 // pass CD: viscous force (+gravity) [sph_physics_mex.c:469-545, SPH_Poiseuille.m:392], transport
@@ -754,8 +841,8 @@ __global__ __launch_bounds__(kBlock) void k_kgc(const Clock *clk, int q, Grid g,
 // are those of the first sub-step (t.fp), there is no transport shift, the particle moves on from t.posn; pair geometry
 // stays that of the start of the outer step (s.pos), velocities are the latest ones (s.vel = the previous sub-step's).
 template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_forces(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
-                                                   FluidTmp t, Walls w, int later)
+__device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
+                                            const FluidTmp &t, const Walls &w, int later)
 {
     SPHX_PASS_INDEX();
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
@@ -894,6 +981,19 @@ __global__ __launch_bounds__(kBlock) void k_forces(const Clock *clk, int q, Grid
         for (int k = 1; k < kBlock / 64; ++k) m = fmax(m, s_d2[k]);
         t.dpart[blk] = m;
     }
+}
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_forces(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
+                                                   FluidTmp t, Walls w, int later)
+{
+    forces_pass<LPP>(clk, q, g, ph, s, t, w, later);
+}
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_forces_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w, int later)
+{
+    const int m = (int)blockIdx.y;
+    const Phys ph = mb.ph[m];
+    forces_pass<LPP>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, later);
 }
 
 // =================================================================================================
@@ -2345,6 +2445,41 @@ __global__ __launch_bounds__(kBlock) void k_continuity_density(Clock *clk, int q
     else density_body<LPP, 2>(clk, q, g, ph, s_next, t_next, w, b - nb, nb, false);
 }
 
+// Batches (Members): pass E of the compact kernels (the tail workgroup of member m is workgroup nb of row m: it waits for the
+// per-workgroup maxima of its own member only) and the fused E|A launch
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_continuity_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w,
+                                                         int do_hist, int tail)
+{
+    const int m = (int)blockIdx.y;
+    Clock *clk = mb.clk + m;
+    const Phys ph = mb.ph[m];
+    const FluidTmp tm = member_tmp(mb, m, t);
+    const int nb = (int)gridDim.x - (tail ? 1 : 0);
+    if (tail && (int)blockIdx.x == nb) {
+        continuity_tail(clk, q, ph, tm, nb);
+        return;
+    }
+    continuity_body<LPP, false, 0>(clk, q, g, ph, member_set(mb, m, s), tm, w, do_hist, tail, (int)blockIdx.x, nb, nullptr,
+                                   nullptr, nullptr);
+}
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_continuity_density_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w,
+                                                                 FluidSet s_next, FluidTmp t_next, int with_tail)
+{
+    const int m = (int)blockIdx.y;
+    Clock *clk = mb.clk + m;
+    const Phys ph = mb.ph[m];
+    const int nb = ((int)gridDim.x - with_tail) / 2;
+    const int b = (int)blockIdx.x;
+    if (with_tail && b == 2 * nb) {
+        continuity_tail(clk, q, ph, member_tmp(mb, m, t), nb);
+        return;
+    }
+    if (b < nb) continuity_body<LPP, false, 0>(clk, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, 0, with_tail, b, nb, nullptr, nullptr, nullptr);
+    else density_body<LPP, 2>(clk, q, g, ph, member_set(mb, m, s_next), member_tmp(mb, m, t_next), w, b - nb, nb, false);
+}
+
 // the same with the large-channel forms of the two passes (mid-size channels: 4-8 lanes per particle, clock in the tail)
 template <int LPP>
 __global__ __launch_bounds__(kBlock) void k_continuity_density_w(Clock *clk, int q, Grid g, Phys ph, FluidSet s, FluidTmp t,
@@ -2478,12 +2613,12 @@ __global__ __launch_bounds__(kScanBlock) void k_max_tiles(const Clock *clk, int 
 //   dpart / rebuilt / half_skin: displacement bookkeeping of grids that are rebuilt only every few steps.
 //   slab_counters: slab mode -- the keep/left/right counters of k_slab_pack, zeroed for the next step (the unpack
 //   kernel of this step has read them).  vpart_reset: see continuity_tail.
-__global__ __launch_bounds__(kScanBlock) void k_clock_scan(Clock *clk, int q, Phys ph, int n_vpart,
-                                                           const double *vpart, const double *vmax_global,
-                                                           const int *flags, const int *count,
-                                                           int *start_next, int n_scan, const int *n_new,
-                                                           const double *dpart, int rebuilt, double half_skin,
-                                                           int *slab_counters, unsigned long long *vpart_reset, int dyn_K)
+__device__ __forceinline__ void clock_scan_body(Clock *clk, int q, const Phys &ph, int n_vpart,
+                                                const double *vpart, const double *vmax_global,
+                                                const int *flags, const int *count,
+                                                int *start_next, int n_scan, const int *n_new,
+                                                const double *dpart, int rebuilt, double half_skin,
+                                                int *slab_counters, unsigned long long *vpart_reset, int dyn_K)
 {
     // everything is requested before the run flag is looked at (stale values are harmless when the slot turns
     // out to be idle); only the thread that advances the clock loads it
@@ -2521,6 +2656,29 @@ __global__ __launch_bounds__(kScanBlock) void k_clock_scan(Clock *clk, int q, Ph
         for (int k = threadIdx.x; k < n_vpart; k += kScanBlock) vpart_reset[k] = kVpartEmpty;
     if (count) scan_counts(count, start_next, n_scan);
 }
+__global__ __launch_bounds__(kScanBlock) void k_clock_scan(Clock *clk, int q, Phys ph, int n_vpart,
+                                                           const double *vpart, const double *vmax_global,
+                                                           const int *flags, const int *count,
+                                                           int *start_next, int n_scan, const int *n_new,
+                                                           const double *dpart, int rebuilt, double half_skin,
+                                                           int *slab_counters, unsigned long long *vpart_reset, int dyn_K)
+{
+    clock_scan_body(clk, q, ph, n_vpart, vpart, vmax_global, flags, count, start_next, n_scan, n_new, dpart, rebuilt, half_skin,
+                    slab_counters, vpart_reset, dyn_K);
+}
+// batch: one workgroup per member (static schedule: no slab inputs, no device-decided re-binning)
+__global__ __launch_bounds__(kScanBlock) void k_clock_scan_b(Members mb, int q, const double *vpart, const int *flags,
+                                                             const int *count, int *start_next, int n_scan,
+                                                             const double *dpart, int rebuilt, double half_skin,
+                                                             unsigned long long *vpart_reset)
+{
+    const int m = (int)blockIdx.y;
+    const Phys ph = mb.ph[m];
+    clock_scan_body(mb.clk + m, q, ph, mb.blocks, member_ptr(vpart, (long long)mb.blocks, m), nullptr, member_ptr(flags, 1ll, m),
+                    member_ptr(count, (long long)mb.cells, m), member_ptr(start_next, (long long)mb.cells, m), n_scan, nullptr,
+                    member_ptr(dpart, (long long)mb.blocks, m), rebuilt, half_skin, nullptr,
+                    member_ptr(vpart_reset, (long long)mb.blocks, m), 0);
+}
 
 __global__ __launch_bounds__(kScanBlock) void k_scan_only(const Clock *clk, int q, const int *count, int *start, int n)
 {
@@ -2530,8 +2688,8 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_only(const Clock *clk, int 
 
 // Step kernel 6: place every particle index into its cell range (arrival order, made canonical by
 // k_reorder).  atomicSub counts the histogram back down to zero, ready for the next step.
-__global__ __launch_bounds__(kBlock) void k_scatter(const Clock *clk, int q, int n_fixed, const int *cellid,
-                                                    int *count, const int *start_next, int *perm)
+__device__ __forceinline__ void scatter_body(const Clock *clk, int q, int n_fixed, const int *cellid, int *count,
+                                             const int *start_next, int *perm)
 {
     if (clk && !slot_active(clk, q)) return;
     const int n = clk ? clk->n : n_fixed;
@@ -2561,6 +2719,18 @@ __global__ __launch_bounds__(kBlock) void k_scatter(const Clock *clk, int q, int
         }
     }
 }
+__global__ __launch_bounds__(kBlock) void k_scatter(const Clock *clk, int q, int n_fixed, const int *cellid,
+                                                    int *count, const int *start_next, int *perm)
+{
+    scatter_body(clk, q, n_fixed, cellid, count, start_next, perm);
+}
+__global__ __launch_bounds__(kBlock) void k_scatter_b(Members mb, int q, const int *cellid, int *count, const int *start_next,
+                                                      int *perm)
+{
+    const int m = (int)blockIdx.y;
+    scatter_body(mb.clk + m, q, 0, member_ptr(cellid, mb.part, m), member_ptr(count, (long long)mb.cells, m),
+                 member_ptr(start_next, (long long)mb.cells, m), member_ptr(perm, mb.part, m));
+}
 
 struct ReorderArgs {
     int n1, n2, n4;  // number of 8-, 16- and 32-byte fields
@@ -2580,8 +2750,8 @@ struct ReorderArgs {
 // Step kernel 7: canonical rank inside the cell (ascending particle id -> an order that does not
 // depend on arrival order, launch shape or domain decomposition) and the gather of every persistent
 // field into the new ordering.
-__global__ __launch_bounds__(kBlock) void k_reorder(const Clock *clk, int q, int n_fixed, const int *cellid,
-                                                    const int *start_next, const int *perm, ReorderArgs a)
+__device__ __forceinline__ void reorder_body(const Clock *clk, int q, int n_fixed, const int *cellid, const int *start_next,
+                                             const int *perm, const ReorderArgs &a)
 {
     if (clk && !slot_active(clk, q)) return;
     const int n = clk ? clk->n : n_fixed;
@@ -2609,12 +2779,42 @@ __global__ __launch_bounds__(kBlock) void k_reorder(const Clock *clk, int q, int
         if (a.slot_of_id) a.slot_of_id[my_id] = dst;
     }
 }
+__global__ __launch_bounds__(kBlock) void k_reorder(const Clock *clk, int q, int n_fixed, const int *cellid,
+                                                    const int *start_next, const int *perm, ReorderArgs a)
+{
+    reorder_body(clk, q, n_fixed, cellid, start_next, perm, a);
+}
+// batch: every field of a ReorderArgs is a per-particle array (slot_of_id is not used)
+__global__ __launch_bounds__(kBlock) void k_reorder_b(Members mb, int q, const int *cellid, const int *start_next,
+                                                      const int *perm, ReorderArgs a)
+{
+    const int m = (int)blockIdx.y;
+    const long long P = mb.part;
+#pragma unroll
+    for (int f = 0; f < 3; ++f) { a.src2[f] = member_ptr(a.src2[f], P, m); a.dst2[f] = member_ptr(a.dst2[f], P, m); }
+#pragma unroll
+    for (int f = 0; f < 2; ++f) { a.src1[f] = member_ptr(a.src1[f], P, m); a.dst1[f] = member_ptr(a.dst1[f], P, m); }
+    a.src4[0] = member_ptr(a.src4[0], P, m); a.dst4[0] = member_ptr(a.dst4[0], P, m);
+    a.id_src = member_ptr(a.id_src, P, m); a.id_dst = member_ptr(a.id_dst, P, m);
+    a.src_of = member_ptr(a.src_of, P, m); a.cell_dst = member_ptr(a.cell_dst, P, m);
+    a.slot_of_id = nullptr;
+    reorder_body(mb.clk + m, q, 0, member_ptr(cellid, P, m), member_ptr(start_next, (long long)mb.cells, m),
+                 member_ptr(perm, P, m), a);
+}
 
 // both step-slot flags off: whatever is enqueued next returns at once (sphx_ctx_prepare_steps warms graphs this way)
 __global__ void k_disarm(Clock *clk)
 {
     clk->run[0] = 0;
     clk->run[1] = 0;
+}
+
+// map[j] = via[map[j]]: a batch member re-binned again before its next step (realignment) keeps reaching the slots its last
+// step's outputs are stored in
+__global__ __launch_bounds__(kBlock) void k_compose(int n, const int *via, int *map)
+{
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j < n) map[j] = via[map[j]];
 }
 
 __global__ void k_rebinned(Clock *clk)

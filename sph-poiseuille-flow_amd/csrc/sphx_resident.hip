@@ -59,6 +59,10 @@ struct KernelTimer {
 
 using namespace sphx;
 
+namespace sphx {
+struct BatchArena;
+}
+
 struct sphx_ctx {
     sphx_params prm{};
     Grid grid{};
@@ -203,6 +207,11 @@ struct sphx_ctx {
         DevBuf<double> dsum;
         DevBuf<FlowStatsHead> head;
     } fstats;
+
+    // Member of a batch (sphx_batch_*): the device arrays are this member's blocks of batch-wide allocations (BatchArena)
+    sphx::BatchArena *arena = nullptr;
+    int member = 0;
+    const int *out_ids = nullptr;  // after a realignment: ids of the slots the last step's outputs are stored in (else fid_[out_lay])
 
     FluidSet view(int q, int l)
     {
@@ -847,6 +856,8 @@ void wait_stream(sphx_ctx *c)
     SPHX_HIP(hipStreamSynchronize(c->stream));
 }
 
+void replay_executed(sphx_ctx *c);
+
 void read_clock(sphx_ctx *c)
 {
     wait_stream(c);
@@ -857,7 +868,12 @@ void read_clock(sphx_ctx *c)
         SPHX_HIP(hipStreamSynchronize(c->stream));
     }
     c->timer.collect();
-    // replay the bookkeeping of the steps that really executed since the last read
+    replay_executed(c);
+}
+
+// replay the bookkeeping of the steps that really executed since the epoch (h_clock holds the device clock)
+void replay_executed(sphx_ctx *c)
+{
     const int64_t executed = (int64_t)c->h_clock->step - c->epoch_step;
     c->cur = c->epoch_cur; c->lay = c->epoch_lay; c->pos = c->epoch_pos; c->out_lay = c->epoch_out_lay;
     c->out_par = c->epoch_out_par;
@@ -994,6 +1010,41 @@ Phys make_phys(const sphx_params *prm)
     return ph;
 }
 
+}  // namespace
+
+namespace sphx {
+// The device arrays of the members of a batch: array X of member m is block m of one allocation of n_members blocks, so that
+// a "_b" kernel reaches every member's X from member 0's pointer (Members, sphx_kernels.hpp).  Keyed by where the DevBuf sits
+// in sphx_ctx -- every member asks for the same arrays in the same sizes.
+struct BatchArena {
+    int n_members = 1;
+    struct Block {
+        DevBuf<char> mem;
+        size_t bytes = 0;  // per member
+    };
+    std::map<size_t, Block> blocks;
+};
+}  // namespace sphx
+
+namespace {
+
+template <typename T>
+void dev_alloc(sphx_ctx *c, DevBuf<T> &b, size_t n)
+{
+    if (!c->arena) {
+        b.alloc(n);
+        return;
+    }
+    BatchArena::Block &blk = c->arena->blocks[(size_t)(reinterpret_cast<char *>(&b) - reinterpret_cast<char *>(c))];
+    const size_t bytes = n * sizeof(T);
+    if (!blk.mem.get() && bytes) {
+        blk.mem.alloc(bytes * (size_t)c->arena->n_members);
+        blk.bytes = bytes;
+    }
+    if (blk.bytes != bytes) throw Error(SPHX_ERR_STATE, "SPHX:Batch:internal", "members ask for arrays of different sizes");
+    b.alias(bytes ? reinterpret_cast<T *>(blk.mem.get() + bytes * (size_t)c->member) : nullptr, n);
+}
+
 // allocate every device array for `cap` particles and the grid of the context
 void ctx_alloc(sphx_ctx *c, int cap)
 {
@@ -1002,48 +1053,48 @@ void ctx_alloc(sphx_ctx *c, int cap)
     c->n_blocks_particles = (int)div_up((size_t)cap * c->lpp, kBlock);
     c->n_blocks_flat = (int)div_up((size_t)cap, kBlock);
     for (int k = 0; k < 2; ++k) {
-        c->fpos_[k].alloc(cap); c->fvel_[k].alloc(cap); c->fdrho_[k].alloc(cap); c->fmass_[k].alloc(cap);
-        c->fid_[k].alloc(cap); c->fstart_[k].alloc((size_t)g.ncells + 1); c->fcell_[k].alloc(cap);
-        if (c->skin > 0.0) c->fposb_[k].alloc(cap);
+        dev_alloc(c, c->fpos_[k], cap); dev_alloc(c, c->fvel_[k], cap); dev_alloc(c, c->fdrho_[k], cap); dev_alloc(c, c->fmass_[k], cap);
+        dev_alloc(c, c->fid_[k], cap); dev_alloc(c, c->fstart_[k], (size_t)g.ncells + 1); dev_alloc(c, c->fcell_[k], cap);
+        if (c->skin > 0.0) dev_alloc(c, c->fposb_[k], cap);
     }
-    c->posn.alloc(cap); c->veln.alloc(cap); c->ffp.alloc(cap); c->ff.alloc(cap); c->fa.alloc(cap); c->fB.alloc(cap);
-    c->drhon.alloc(cap); c->rho_out.alloc(cap); c->p_out.alloc(cap); c->fvol.alloc(cap); c->fvol.zero(c->stream);
+    dev_alloc(c, c->posn, cap); dev_alloc(c, c->veln, cap); dev_alloc(c, c->ffp, cap); dev_alloc(c, c->ff, cap); dev_alloc(c, c->fa, cap); dev_alloc(c, c->fB, cap);
+    dev_alloc(c, c->drhon, cap); dev_alloc(c, c->rho_out, cap); dev_alloc(c, c->p_out, cap); dev_alloc(c, c->fvol, cap); c->fvol.zero(c->stream);
     c->posn.zero(c->stream); c->veln.zero(c->stream); c->ffp.zero(c->stream); c->ff.zero(c->stream);
     c->fa.zero(c->stream); c->fB.zero(c->stream); c->drhon.zero(c->stream); c->rho_out.zero(c->stream); c->p_out.zero(c->stream);
     c->n_vpart = c->n_blocks_particles;
-    c->vpart.alloc(c->n_vpart);
+    dev_alloc(c, c->vpart, c->n_vpart);
     // Small channels with a skin: move steps are 4 launches, the clock update rides in pass E (continuity_tail);
     // vpart entries then double as "ready" flags and start out empty (all ones)
     c->tail_clock = c->skin > 0.0 && !c->is_slab && !c->dyn && c->n_vpart <= tail_clock_limit() && !debug_switches().no_tail_clock;
     // (skinned slabs: the same hand-over feeds slab_seal_tail)
     const bool vpart_flags = c->tail_clock || (c->is_slab && c->rebuild_every > 1);
     SPHX_HIP(hipMemsetAsync(c->vpart.get(), vpart_flags ? 0xFF : 0, (size_t)c->n_vpart * sizeof(double), c->stream));
-    c->dpart.alloc(c->n_vpart);
+    dev_alloc(c, c->dpart, c->n_vpart);
     c->dpart.zero(c->stream);
     c->n_vtiles = (!c->is_slab && c->n_vpart > 4 * kMaxTile) ? (int)div_up((size_t)c->n_vpart, kMaxTile) : 0;
-    if (c->n_vtiles) c->vtile.alloc(2 * (size_t)c->n_vtiles);
-    c->cellid.alloc(cap); c->count.alloc((size_t)g.ncells + 1); c->perm.alloc(cap); c->src_of.alloc(cap);
+    if (c->n_vtiles) dev_alloc(c, c->vtile, 2 * (size_t)c->n_vtiles);
+    dev_alloc(c, c->cellid, cap); dev_alloc(c, c->count, (size_t)g.ncells + 1); dev_alloc(c, c->perm, cap); dev_alloc(c, c->src_of, cap);
     c->count.zero(c->stream);
     const int nl_cap = nl_cap_for(c->lpp);
     const size_t stride = (size_t)c->n_blocks_particles * kBlock;  // one list column per launched lane
-    c->nl_idx.alloc(stride * nl_cap);
-    c->nl_cnt.alloc(stride);
+    dev_alloc(c, c->nl_idx, stride * nl_cap);
+    dev_alloc(c, c->nl_cnt, stride);
     c->nl_cnt.zero(c->stream);
     const size_t nl_words = (size_t)(nl_cap + 1) / 2;  // two 16-bit rows per word
-    if (c->walk_kernels) { c->nl_pk.alloc(stride * std::max<size_t>(nl_words, 2)); c->nl_pk.zero(c->stream); }
+    if (c->walk_kernels) { dev_alloc(c, c->nl_pk, stride * std::max<size_t>(nl_words, 2)); c->nl_pk.zero(c->stream); }
     const int sl_cap = c->skin > 0.0 ? (3 * nl_cap + 1) / 2 : 0;
     if (sl_cap) {
-        c->sl_idx.alloc(stride * sl_cap);
-        c->sl_cnt.alloc(stride);
+        dev_alloc(c, c->sl_idx, stride * sl_cap);
+        dev_alloc(c, c->sl_cnt, stride);
         c->sl_cnt.zero(c->stream);
-        if (c->walk_kernels) { c->sl_pk.alloc(stride * std::max<size_t>((size_t)(sl_cap + 1) / 2, 4)); c->sl_pk.zero(c->stream); }
+        if (c->walk_kernels) { dev_alloc(c, c->sl_pk, stride * std::max<size_t>((size_t)(sl_cap + 1) / 2, 4)); c->sl_pk.zero(c->stream); }
     }
     const double sl_r = 2.0 * c->prm.h + c->skin;
-    c->flags.alloc(1);
+    dev_alloc(c, c->flags, 1);
     c->flags.zero(c->stream);
     c->big_scan = g.ncells > kBigScanCells;
     c->n_tiles = (int)div_up((size_t)g.ncells, kScanBlock);
-    c->tile.alloc(2 * ((size_t)c->n_tiles + 1));
+    dev_alloc(c, c->tile, 2 * ((size_t)c->n_tiles + 1));
     c->tmp = FluidTmp{c->posn.get(), c->veln.get(), c->drhon.get(), c->fa.get(), c->fB.get(), c->ffp.get(), c->ff.get(),
                       c->rho_out.get(), c->p_out.get(), c->cellid.get(), c->count.get(), c->perm.get(), c->src_of.get(),
                       c->vpart.get(), c->dpart.get(), c->nl_idx.get(), c->nl_cnt.get(), c->flags.get(), c->tile.get(),
@@ -1053,7 +1104,7 @@ void ctx_alloc(sphx_ctx *c, int cap)
     //  inner sub-steps, runs on the compact kernels only)
     c->tmp.lazy_out = (c->walk_kernels && !debug_switches().no_lazy_out) ? (c->is_slab ? 2 : 1) : 0;
     if (c->walk_kernels) {  // (zeros = empty layouts until the first cell sweep has run)
-        c->tmap.alloc(8 * (size_t)c->n_blocks_particles); c->tmap.zero(c->stream);
+        dev_alloc(c, c->tmap, 8 * (size_t)c->n_blocks_particles); c->tmap.zero(c->stream);
         c->tmp.tmap = c->tmap.get();
     }
     // E|A fusion: small static-schedule channels on the compact kernels (the clock rides in the tail workgroup)
@@ -1061,12 +1112,12 @@ void ctx_alloc(sphx_ctx *c, int cap)
     c->tmp_par[0] = c->tmp;
     c->tmp_par[1] = c->tmp;
     if (c->fuse_ea) {
-        c->fa2.alloc(cap); c->fvol2.alloc(cap); c->fa2.zero(c->stream); c->fvol2.zero(c->stream);
-        c->nl_idx2.alloc(stride * nl_cap); c->nl_cnt2.alloc(stride); c->nl_cnt2.zero(c->stream);
+        dev_alloc(c, c->fa2, cap); dev_alloc(c, c->fvol2, cap); c->fa2.zero(c->stream); c->fvol2.zero(c->stream);
+        dev_alloc(c, c->nl_idx2, stride * nl_cap); dev_alloc(c, c->nl_cnt2, stride); c->nl_cnt2.zero(c->stream);
         c->tmp_par[1].a = c->fa2.get(); c->tmp_par[1].vol = c->fvol2.get();
         c->tmp_par[1].nl_idx = c->nl_idx2.get(); c->tmp_par[1].nl_cnt = c->nl_cnt2.get();
         if (c->walk_kernels) {
-            c->nl_pk2.alloc(stride * std::max<size_t>(nl_words, 2)); c->nl_pk2.zero(c->stream);
+            dev_alloc(c, c->nl_pk2, stride * std::max<size_t>(nl_words, 2)); c->nl_pk2.zero(c->stream);
             c->tmp_par[1].nl_pk = c->nl_pk2.get();
         }
     }
@@ -1074,10 +1125,10 @@ void ctx_alloc(sphx_ctx *c, int cap)
     // the step a fixed shape.  The number of inner sub-steps is fixed per context (the graphs are static): how many acoustic
     // steps fit into the viscous / body-force step, at most dual_rate.  Fine channels are viscous-limited: n_in = 1 there.
     c->n_in = (c->fuse_ea && c->lpp >= 16) ? dual_rate_substeps(c->prm) : 1;
-    if (c->n_in > 1) { c->vel2.alloc(cap); c->vel2.zero(c->stream); }
+    if (c->n_in > 1) { dev_alloc(c, c->vel2, cap); c->vel2.zero(c->stream); }
 
-    c->tau_part.alloc((size_t)2 * c->n_blocks_flat);
-    c->tau_out.alloc(2);
+    dev_alloc(c, c->tau_part, (size_t)2 * c->n_blocks_flat);
+    dev_alloc(c, c->tau_out, 2);
 }
 
 // upload n fluid particles (host SoA) and sort them into state 0 / layout 0
@@ -1138,7 +1189,7 @@ void upload_walls(sphx_ctx *c, int nw, const double *hx, const double *hy, const
 void init_clock(sphx_ctx *c, int n, double t0, int64_t step0)
 {
     hipStream_t s = c->stream;
-    c->clock.alloc(1);
+    dev_alloc(c, c->clock, 1);
     Clock k{};
     k.t = t0; k.dt = 0.0; k.dt_last = 0.0; k.t_target = t0; k.t_end = c->prm.t_end; k.vmax = 0.0;
     k.step = step0; k.steps_left = -1; k.run[0] = 0; k.run[1] = 0; k.status = 0; k.n = n;
@@ -1225,18 +1276,16 @@ void check_lpp(int lpp)
             "lanes_per_particle must be 1,2,4,8,16 or 32");
 }
 
-void ctx_setup(sphx_ctx *c, const sphx_params *prm, int n_fluid, int n_total, const double *pos, const double *vel,
-               const double *drho_dt, const double *mass, const double *wall_vel, double t0, int64_t step0)
+// what a context decides from its parameters and the particle extent, before the device is touched: lanes per particle,
+// re-binning interval and skin, cell grid, kernel forms
+void ctx_configure(sphx_ctx *c, const sphx_params *prm, int n_fluid, int n_total, const double *pos)
 {
-    common_checks(prm, n_fluid, n_total);
-    ensure_device();
     c->prm = *prm;
     c->nf = n_fluid;
     c->nt = n_total;
     c->nw = n_total - n_fluid;
-    const int nf = c->nf, nw = c->nw;
-    const size_t ntz = (size_t)n_total;
-    const double *px = pos, *py = pos + ntz;
+    const int nf = c->nf;
+    const double *py = pos + (size_t)n_total;
 
     c->lpp = prm->lanes_per_particle > 0 ? prm->lanes_per_particle : pick_lpp(nf);
     check_lpp(c->lpp);
@@ -1320,6 +1369,17 @@ void ctx_setup(sphx_ctx *c, const sphx_params *prm, int n_fluid, int n_total, co
     c->grid = g;
     c->phys = make_phys(prm);
     choose_kernel_forms(c, prm->lanes_per_particle > 0, (double)nf / g.ncx, nf);
+}
+
+void ctx_setup(sphx_ctx *c, const sphx_params *prm, int n_fluid, int n_total, const double *pos, const double *vel,
+               const double *drho_dt, const double *mass, const double *wall_vel, double t0, int64_t step0)
+{
+    common_checks(prm, n_fluid, n_total);
+    ensure_device();
+    ctx_configure(c, prm, n_fluid, n_total, pos);
+    const int nf = c->nf, nw = c->nw;
+    const size_t ntz = (size_t)n_total;
+    const double *px = pos, *py = pos + ntz;
 
     SPHX_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     SPHX_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_clock), sizeof(Clock), hipHostMallocDefault));
@@ -1552,7 +1612,7 @@ SPHX_EXPORT int sphx_ctx_download(sphx_ctx *c, double *pos, double *vel, double 
     const FluidSet fs = c->view(c->cur, c->lay);
     // ordering the step outputs are stored in: the layout the step ran in (static schedule), or -- dynamic contexts,
     // which re-bin in place -- the current ids reached through src_of when the last step ended with a re-binning
-    const int *id_old = c->dyn ? fs.id : c->fid_[c->out_lay].get();
+    const int *id_old = c->dyn ? fs.id : (c->out_ids ? c->out_ids : c->fid_[c->out_lay].get());
     const int *out_map = (c->dyn && c->h_clock->fresh) ? (const int *)c->src_of.get() : nullptr;
     DevBuf<double> stage((size_t)4 * nt);
     const dim3 gf(div_up(nf, kBlock)), gw(div_up(std::max(nw, 1), kBlock)), b(kBlock);
@@ -1613,7 +1673,7 @@ SPHX_EXPORT int sphx_ctx_monitor(sphx_ctx *c, double *tau_bottom, double *tau_to
         const int nblk = c->n_blocks_flat;
         hipLaunchKernelGGL(k_wall_shear, dim3(nblk), dim3(kBlock), 0, s, (const Clock *)c->clock.get(), c->grid, c->phys, fs,
                            c->tmp_par[c->fuse_ea ? c->out_par : 0], c->walls,
-                           (c->dyn ? c->h_clock->fresh != 0 : c->out_lay != c->lay) ? 1 : 0, c->tau_part.get());
+                           (c->dyn ? c->h_clock->fresh != 0 : (c->out_lay != c->lay || c->out_ids)) ? 1 : 0, c->tau_part.get());
         hipLaunchKernelGGL(k_tau_final, dim3(1), dim3(kScanBlock), 0, s, nblk, (const double *)c->tau_part.get(),
                            c->phys.DL, c->tau_out.get());
         double h[2];
@@ -3275,3 +3335,5 @@ SPHX_EXPORT int sphx_ctx_time_kernel(sphx_ctx *c, const char *name, int reps, do
     return SPHX_OK;
     SPHX_CATCH
 }
+
+#include "sphx_batch.hpp"

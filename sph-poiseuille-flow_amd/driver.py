@@ -228,3 +228,76 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                      profile_times=profile_times, mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t,
                      tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2, grid_policy=policy, full_profile_u=full_profiles, n_inner=n_inner,
                      time_avg=time_avg)
+
+
+def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,
+              restart_path=None, postprocess_path=None, average_from=None, log=None):
+    """run() for M channels of one geometry stepped together as one batch (capi.Batch, include/sphx.h section 2b): a
+    parameter sweep (mu, c_f, p0, gravity_g, transport_coeff) or an ensemble of realisations (parts_list).  Every member
+    reaches the same output points (output_interval and t_end are shared and must agree) and gets a RunResult of its own:
+    final profile and L2, the output-point profiles, tau.  The resident engine only; restart / post-process files and
+    average_from are single-channel features."""
+    prms = list(prms)
+    if engine != "resident":
+        raise ValueError("run_batch runs the resident engine only (a batch is device-resident)")
+    if restart_path or postprocess_path:
+        raise ValueError("run_batch writes no restart / post-process files (run() does, per channel)")
+    if average_from is not None:
+        raise ValueError("run_batch has no time averaging yet (flow statistics are a single-context feature)")
+    if not prms:
+        raise ValueError("run_batch needs at least one parameter set")
+    p0 = prms[0]
+    for k, p in enumerate(prms):
+        if p.output_interval != p0.output_interval or p.t_end != p0.t_end:
+            raise ValueError(f"member {k}: output_interval / t_end differ from member 0 (members share the output points)")
+    parts_list = [init_particles(p) for p in prms] if parts_list is None else list(parts_list)
+    if len(parts_list) != len(prms):
+        raise ValueError("parts_list needs one particle set per parameter set")
+    nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
+    M = len(prms)
+    n_bins = n_profile_bins(p0.DH, p0.dp)
+    mid_x, mid_hw = 0.5 * p0.DL, max(p0.dp, p0.h)
+    times = [0.0]
+    mids = [[compute_mid_channel_profile(pa["pos"][:nf], pa["vel"][:nf, 0], p0.DL, p0.DH, mid_x, mid_hw, n_bins)[1]]
+            for pa in parts_list]
+    fulls = [[] for _ in range(M)]
+    t0 = time.perf_counter()
+    with capi.Batch(prms, nf, nt, [pa["pos"] for pa in parts_list], [pa["vel"] for pa in parts_list],
+                    [pa["drho_dt"] for pa in parts_list], parts_list[0]["mass"], parts_list[0]["wall_vel"],
+                    lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
+                    rebuild_every=rebuild_every) as b:
+        t = 0.0
+        st = None
+        while t < p0.t_end - 1e-12:
+            target = min(t + p0.output_interval, p0.t_end)
+            st = b.advance(target)
+            t = min(s["t"] for s in st)
+            times.append(t)
+            for m in range(M):
+                d = b.download(m, fields=("pos", "vel"))
+                mids[m].append(compute_mid_channel_profile(d["pos"][:nf], d["vel"][:nf, 0], p0.DL, p0.DH, mid_x, mid_hw,
+                                                           n_bins)[1])
+                fulls[m].append(final_profile(np.column_stack([np.mod(d["pos"][:nf, 0], p0.DL), d["pos"][:nf, 1]]),
+                                              d["vel"][:nf, 0], prms[m])[1])
+            if log:
+                log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
+        wall = time.perf_counter() - t0
+        info = b.info()
+        out = []
+        for m, prm in enumerate(prms):
+            tau_b, tau_t, _ = b.monitor(m, tau=True)
+            d = b.download(m, fields=("pos", "vel"))
+            pos, vel = d["pos"], d["vel"]
+            fluid_pos = pos[:nf].copy()
+            fluid_pos[:, 0] = np.mod(fluid_pos[:, 0], prm.DL)
+            y_mid, u_mean, u_exact = final_profile(fluid_pos, vel[:nf, 0], prm)
+            s = st[m] if st else dict(t=0.0, step=0)
+            out.append(RunResult(prm=prm, n_fluid=nf, n_total=nt, t=s["t"], steps=int(s["step"]), wall_seconds=wall,
+                                 pos=pos, vel=vel, y_mid=y_mid, u_mean=u_mean, u_exact=u_exact,
+                                 L2_error=l2_error(u_mean, u_exact), profile_times=list(times), mid_profile_u=mids[m],
+                                 tau_bottom=tau_b, tau_top=tau_t, tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2,
+                                 grid_policy=dict(rebuild_every=info["rebuild_every"], skin=info["skin"],
+                                                  forced_rebuilds=info["forced_rebuilds"],
+                                                  realignments=info["realignments"]),
+                                 full_profile_u=fulls[m]))
+    return out

@@ -1,0 +1,183 @@
+"""-m gpu: batched contexts (sphx_batch_*, capi.Batch) -- M channels of one geometry stepped by the same launches.
+
+Members that never fell out of step must be bit for bit standalone contexts with the same parameters; members that reach
+one target time in different step counts are realigned (re-binned into one layout) and then match the oracle within the
+tolerances of test_gpu_resident.py.
+"""
+import numpy as np
+import pytest
+
+from helpers import assert_close, make_case
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("pos", "vel", "rho", "p", "drho_dt", "force", "force_prior", "Vol", "B")
+# members differ in mu, c_f, transport_coeff and the seed of their initial state
+VARIANTS = [dict(mu=0.1, c_f=15.0, transport_coeff=0.30, seed=7), dict(mu=0.15, c_f=17.0, transport_coeff=0.20, seed=8),
+            dict(mu=0.08, c_f=13.0, transport_coeff=0.30, seed=9), dict(mu=0.12, c_f=15.0, transport_coeff=0.10, seed=10)]
+
+
+def _members(cfgmod, geom, dp, DL, variants, jitter=0.2):
+    out = []
+    for v in variants:
+        prm, parts = make_case(cfgmod, geom, dp=dp, DL=DL, jitter=jitter, seed=v["seed"], developed=True, mu=v["mu"],
+                               c_f=v["c_f"], transport_coeff=v["transport_coeff"])
+        out.append((prm, parts))
+    return out
+
+
+def _batch(capi, members, **kw):
+    p0 = members[0][1]
+    return capi.Batch([m[0] for m in members], p0["n_fluid"], p0["n_total"], [m[1]["pos"] for m in members],
+                      [m[1]["vel"] for m in members], [m[1]["drho_dt"] for m in members], p0["mass"], p0["wall_vel"], **kw)
+
+
+def _ctx(capi, prm, parts, **kw):
+    return capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
+                        parts["wall_vel"], **kw)
+
+
+def _everything(dl, st, mon):
+    return dict(dl, t=st["t"], dt_last=st["dt_last"], step=st["step"], vmax=st["vmax"], tau=np.array(mon[:2]),
+                pairs=mon[2])
+
+
+def _assert_identical(a, b, what):
+    for k in a:
+        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), f"{what}: {k} differs"
+
+
+@pytest.mark.parametrize("lpp", [16, 32])
+@pytest.mark.parametrize("dp,DL", [(0.05, 3.0), (0.025, 1.5)])
+def test_bit_identical_to_standalone(cfgmod, geom, capi, dp, DL, lpp):
+    members = _members(cfgmod, geom, dp, DL, VARIANTS)
+    kw = dict(t_end=1e9, lanes_per_particle=lpp)
+    with _batch(capi, members, **kw) as b:
+        K = b.info()["rebuild_every"]
+        assert b.info()["lanes_per_particle"] == lpp and K > 1
+    n = 3 * K + 1  # crosses at least two scheduled re-binnings
+    for eager in (False, True):
+        with _batch(capi, members, **kw) as b:
+            if eager:  # one-step calls: every slot launched eagerly
+                for _ in range(n):
+                    sts = b.advance(1e9, max_steps=1)
+                assert b.graph_stats()["slots_eager"] >= n
+            else:
+                sts = b.advance(1e9, max_steps=n)
+                assert b.graph_stats()["slots_replayed"] > 0
+            got = [_everything(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
+            assert b.info()["realignments"] == 0
+        for m, (prm, parts) in enumerate(members):
+            with _ctx(capi, prm, parts, **kw) as ctx:
+                st = ctx.advance(1e9, max_steps=n)
+                ref = _everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
+            assert got[m]["step"] == n
+            _assert_identical(got[m], ref, f"member {m} eager={eager} dp={dp} lpp={lpp}")
+
+
+def test_single_member_equals_standalone(cfgmod, geom, capi):
+    members = _members(cfgmod, geom, 0.025, 1.5, VARIANTS[1:2])
+    with _batch(capi, members, t_end=1e9) as b:
+        st = b.advance(1e9, max_steps=37)[0]
+        got = _everything(b.download(0), st, b.monitor(0, tau=True, pairs=True))
+    with _ctx(capi, *members[0], t_end=1e9) as ctx:
+        st = ctx.advance(1e9, max_steps=37)
+        ref = _everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
+    _assert_identical(got, ref, "M = 1")
+
+
+def test_no_cross_talk(cfgmod, geom, capi):
+    variants = [dict(VARIANTS[k % 4], seed=100 + k) for k in range(64)]
+    members = _members(cfgmod, geom, 0.05, 3.0, variants)
+    kw = dict(t_end=1e9, lanes_per_particle=16)
+
+    def run(mem):
+        with _batch(capi, mem, **kw) as b:
+            b.advance(1e9, max_steps=20)
+            return {m: b.download(m) for m in (0, 5, 31, 63)}
+
+    base = run(members)
+    prm5, parts5 = members[5]
+    pert = dict(parts5, vel=parts5["vel"].copy(order="F"))
+    pert["vel"][: parts5["n_fluid"], 1] += 1e-3
+    other = run(members[:5] + [(prm5, pert)] + members[6:])
+    for m in (0, 31, 63):
+        _assert_identical(other[m], base[m], f"member {m} after perturbing member 5")
+    assert not np.array_equal(other[5]["vel"], base[5]["vel"])
+
+
+def _oracle_check(got, ref):
+    for k in FIELDS:
+        assert_close(got[k], ref[k], rtol=1e-9, atol_scale=1e-10, name=k)
+
+
+def test_time_target_realigns_and_matches_oracle(cfgmod, geom, capi, oracle):
+    # different c_f: one target time in different step counts
+    variants = [dict(VARIANTS[0], c_f=15.0), dict(VARIANTS[1], c_f=21.0), dict(VARIANTS[2], c_f=11.0)]
+    members = _members(cfgmod, geom, 0.05, 3.0, variants)
+    dt0 = 0.25 * members[0][0].h / (15.0 + 1.5)
+    t1, t2 = 10.3 * dt0, 17.9 * dt0
+    with _batch(capi, members, t_end=1e9, lanes_per_particle=16) as b:
+        sts = b.advance(t1)
+        steps = [s["step"] for s in sts]
+        assert len(set(steps)) > 1, steps
+        assert all(s["done"] == 1 and abs(s["t"] - t1) < 1e-12 for s in sts)
+        assert b.info()["realignments"] >= 1
+        first = [b.download(m) for m in range(3)]
+        sts2 = b.advance(t2)
+        second = [b.download(m) for m in range(3)]
+        taus = [b.monitor(m, tau=True) for m in range(3)]
+    for m, (prm, parts) in enumerate(members):
+        ref = oracle.run(prm, parts, t_end=t1, output_interval=t1, enable_sort=False)
+        assert steps[m] == ref["stats"]["steps"]
+        _oracle_check(first[m], ref)
+        ref2 = oracle.run(prm, parts, t_end=t2, output_interval=t1, enable_sort=False)
+        assert sts2[m]["step"] == ref2["stats"]["steps"]
+        _oracle_check(second[m], ref2)
+        assert_close(np.array(taus[m][:2]), np.array([ref2["stats"]["tau_bottom"], ref2["stats"]["tau_top"]]), rtol=1e-8,
+                     atol_scale=1e-9, name="tau")
+
+
+def test_drift_forced_rebinning_matches_oracle(cfgmod, geom, capi, oracle):
+    """A skin far too thin for K (as test_gpu_grid_skin.py): the device stops the members, the batch re-bins all of them."""
+    members = _members(cfgmod, geom, 0.05, 3.0, VARIANTS[:3], jitter=0.3)
+    n = 24
+    with _batch(capi, members, t_end=1e9, lanes_per_particle=16, rebuild_every=8, skin_h=0.03) as b:
+        sts = b.advance(1e9, max_steps=n)
+        got = [b.download(m) for m in range(3)]
+        info = b.info()
+    assert info["forced_rebuilds"] > 0 and info["realignments"] >= info["forced_rebuilds"]
+    for m, (prm, parts) in enumerate(members):
+        assert sts[m]["step"] == n
+        ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n, enable_sort=False)
+        _oracle_check(got[m], ref)
+
+
+def test_diverging_member_is_named(cfgmod, geom, capi):
+    members = _members(cfgmod, geom, 0.05, 1.5, VARIANTS[:3], jitter=0.1)
+    prm2, parts2 = members[2]
+    bad = dict(parts2, vel=parts2["vel"].copy(order="F"))
+    bad["vel"][3, 0] = np.nan
+    members[2] = (prm2, bad)
+    with _batch(capi, members, t_end=1e9) as b:
+        with pytest.raises(capi.SphxError) as e:
+            b.advance(1e9, max_steps=4)
+    assert e.value.code == capi.SPHX_ERR_DIVERGED
+    assert "member 2" in e.value.message
+
+
+def test_run_batch_matches_run(cfgmod, geom, driver):
+    prms = [cfgmod.params_from_values(dp=0.025, DL=1.5, mu=mu, end_time=0.004, output_interval=0.002)
+            for mu in (0.1, 0.15, 0.2)]
+    res = driver.run_batch(prms)
+    assert len(res) == 3
+    for prm, r in zip(prms, res):
+        one = driver.run(prm)
+        assert r.steps == one.steps and abs(r.t - one.t) < 1e-12
+        if r.grid_policy["realignments"] == 0:
+            assert r.L2_error == one.L2_error
+            assert np.array_equal(r.u_mean, one.u_mean, equal_nan=True)
+        else:
+            assert abs(r.L2_error - one.L2_error) <= 1e-9
+            assert np.allclose(r.u_mean, one.u_mean, rtol=0, atol=1e-9, equal_nan=True)
+        assert len(r.full_profile_u) == len(one.full_profile_u)
