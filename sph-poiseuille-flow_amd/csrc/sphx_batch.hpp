@@ -22,25 +22,15 @@ struct sphx_batch {
     DevBuf<long long> budget;
     DevBuf<double> st_mass;           // realignment staging (one member at a time)
     DevBuf<int> st_id, st_src, out_id;  // (out_id: [M x cap], see sphx_ctx::out_ids)
-    // host schedule, shared by all members
-    int cur = 0, lay = 0, pos = 0;
-    int64_t slot = 0, epoch_slot = 0;  // step slots the batch has taken (members in lockstep); drives the cool-down
-    int64_t cool_until = 0, cool_len = 0;
-    int64_t n_forced = 0, n_realign = 0;
-    std::map<std::array<int, 4>, hipGraphExec_t> graphs;
-    int64_t slots_replayed = 0, slots_eager = 0, graphs_captured = 0;
+    Schedule sched;                   // shared by all members: sched.slot counts the step slots the batch has taken (lockstep)
+    int64_t epoch_slot = 0;           // sched.slot when the members' epochs were set
+    int64_t n_realign = 0;
     std::vector<int64_t> pending;     // per member: step count the sphx_batch_enqueue_steps calls since the last sync aim for
 
-    void drop_graphs()
-    {
-        for (auto &kv : graphs)
-            if (kv.second) (void)hipGraphExecDestroy(kv.second);
-        graphs.clear();
-    }
     ~sphx_batch()
     {
         if (stream) (void)hipStreamSynchronize(stream);
-        drop_graphs();
+        sched.drop_graphs();
         for (sphx_ctx *c : mem) delete c;  // (before the arena their arrays live in)
         mem.clear();
         if (h_clocks) (void)hipHostFree(h_clocks);
@@ -113,87 +103,13 @@ void batch_step_t(sphx_batch *b, int q, int l, int pos, bool rebuild)
            (const int *)c->perm.get(), reorder_args(c->tmp.posn, c->tmp.veln, c->tmp.drhon, s.mass, s.id, d, c->tmp.src_of));
 }
 
-void batch_step(sphx_batch *b, int q, int l, int pos, bool rebuild)
+// the batch's step slot, for the shared schedule code (capture_slots, enqueue_slots)
+auto batch_slot(sphx_batch *b)
 {
-    if (b->mem[0]->lpp == 16) batch_step_t<16>(b, q, l, pos, rebuild);
-    else batch_step_t<32>(b, q, l, pos, rebuild);
-}
-
-bool batch_slot_rebuilds(const sphx_batch *b)
-{
-    return b->pos >= b->mem[0]->rebuild_every - 1 || b->slot < b->cool_until;
-}
-
-void batch_track(sphx_batch *b)
-{
-    const bool rebuild = batch_slot_rebuilds(b);
-    b->slot += 1;
-    b->cur ^= 1;
-    if (rebuild) { b->lay ^= 1; b->pos = 0; }
-    else b->pos += 1;
-}
-
-hipGraphExec_t batch_graph(sphx_batch *b, int n)
-{
-    const std::array<int, 4> key{b->cur, b->lay, b->pos, n};
-    auto it = b->graphs.find(key);
-    if (it != b->graphs.end()) return it->second;
-    if (b->graphs.size() >= kMaxGraphs) {
-        SPHX_HIP(hipStreamSynchronize(b->stream));
-        b->drop_graphs();
-    }
-    const int K = b->mem[0]->rebuild_every;
-    SPHX_HIP(hipStreamBeginCapture(b->stream, hipStreamCaptureModeThreadLocal));
-    try {
-        int q = b->cur, l = b->lay, p = b->pos;
-        for (int j = 0; j < n; ++j) {
-            const bool rebuild = p == K - 1;
-            batch_step(b, q, l, p, rebuild);
-            if (rebuild) { l ^= 1; p = 0; }
-            else ++p;
-            q ^= 1;
-        }
-    } catch (...) {
-        hipGraph_t junk = nullptr;
-        (void)hipStreamEndCapture(b->stream, &junk);
-        if (junk) (void)hipGraphDestroy(junk);
-        throw;
-    }
-    hipGraph_t g = nullptr;
-    SPHX_HIP(hipStreamEndCapture(b->stream, &g));
-    hipGraphExec_t exec = nullptr;
-    const hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    SPHX_HIP(e);
-    b->graphs[key] = exec;
-    b->graphs_captured += 1;
-    return exec;
-}
-
-// enqueue_slots for a batch: whole graphs from any phase, exact tails as graphs of their own, cool-downs eagerly
-void batch_enqueue(sphx_batch *b, int64_t slots, bool exact_tail)
-{
-    int64_t left = slots;
-    while (left > 0) {
-        const int per_graph = graph_slots(b->mem[0]);
-        int n = 0;
-        if (b->slot >= b->cool_until) {
-            if (left >= per_graph) n = per_graph;
-            else if (exact_tail && left >= kMinGraphSlots) n = (int)left;
-        }
-        if (n > 0) {
-            SPHX_HIP(hipGraphLaunch(batch_graph(b, n), b->stream));
-            b->slots_replayed += n;
-            for (int k = 0; k < n; ++k) batch_track(b);
-            left -= n;
-            continue;
-        }
-        batch_step(b, b->cur, b->lay, b->pos, batch_slot_rebuilds(b));
-        b->slots_eager += 1;
-        batch_track(b);
-        --left;
-    }
-    SPHX_HIP(hipGetLastError());
+    return [b](int q, int l, int pos, bool rebuild) {
+        if (b->mem[0]->lpp == 16) batch_step_t<16>(b, q, l, pos, rebuild);
+        else batch_step_t<32>(b, q, l, pos, rebuild);
+    };
 }
 
 // arm every member's clock: one budget for all (max_steps) or one per member (b->h_budget, budgets = true)
@@ -205,7 +121,7 @@ void batch_arm(sphx_batch *b, double t_target, long long max_steps, bool budgets
         SPHX_HIP(hipMemcpyAsync(b->budget.get(), b->h_budget, sizeof(long long) * b->M, hipMemcpyHostToDevice, b->stream));
         dev_budget = b->budget.get();
     }
-    hipLaunchKernelGGL(k_prepare_b, dim3(1, b->M), dim3(1), 0, b->stream, b->mb, t_target, max_steps, dev_budget, b->cur);
+    hipLaunchKernelGGL(k_prepare_b, dim3(1, b->M), dim3(1), 0, b->stream, b->mb, t_target, max_steps, dev_budget, b->sched.cur);
     SPHX_HIP(hipGetLastError());
 }
 
@@ -213,11 +129,11 @@ void batch_arm(sphx_batch *b, double t_target, long long max_steps, bool budgets
 void batch_set_epochs(sphx_batch *b)
 {
     for (sphx_ctx *c : b->mem) {
-        c->cur = b->cur; c->lay = b->lay; c->pos = b->pos;
+        c->sched.cur = b->sched.cur; c->sched.lay = b->sched.lay; c->sched.pos = b->sched.pos;
         set_epoch(c);
-        c->cool_until = c->h_clock->step + std::max<int64_t>(0, b->cool_until - b->slot);
+        c->sched.cool_until = c->h_clock->step + std::max<int64_t>(0, b->sched.cool_until - b->sched.slot);
     }
-    b->epoch_slot = b->slot;
+    b->epoch_slot = b->sched.slot;
 }
 
 // Re-bin member m from wherever its state is into (Q, L), pos 0.  The source is staged first, so any (Q, L) will do; the
@@ -226,7 +142,7 @@ void realign_member(sphx_batch *b, int m, int Q, int L)
 {
     sphx_ctx *c = b->mem[m];
     hipStream_t st = b->stream;
-    const int n = c->h_clock->n, q = c->cur, l = c->lay;
+    const int n = c->h_clock->n, q = c->sched.cur, l = c->sched.lay;
     const FluidSet s = c->view(q, l), d = c->view(Q, L);
     const bool outputs = c->have_step_outputs;
     const bool mapped = outputs && (c->out_ids != nullptr || c->out_lay != l);  // src_of: current slot -> output slot
@@ -244,20 +160,12 @@ void realign_member(sphx_batch *b, int m, int Q, int L)
     copy(c->drhon.get(), s.drho, sizeof(double) * n);
     copy(b->st_mass.get(), s.mass, sizeof(double) * n);
     copy(b->st_id.get(), s.id, sizeof(int) * n);
-    const dim3 g1(div_up(n, kBlock)), bp(kBlock);
-    hipLaunchKernelGGL(k_bin, g1, bp, 0, st, (const Clock *)nullptr, 0, c->grid, n, (const double2 *)c->posn.get(), c->cellid.get(),
-                       c->count.get());
-    hipLaunchKernelGGL(k_scan_only, dim3(1), dim3(kScanBlock), 0, st, (const Clock *)nullptr, 0, (const int *)c->count.get(), d.start,
-                       c->grid.ncells);
-    hipLaunchKernelGGL(k_scatter, g1, bp, 0, st, (const Clock *)nullptr, 0, n, (const int *)c->cellid.get(), c->count.get(),
-                       (const int *)d.start, c->perm.get());
-    hipLaunchKernelGGL(k_reorder, g1, bp, 0, st, (const Clock *)nullptr, 0, n, (const int *)c->cellid.get(), (const int *)d.start,
-                       (const int *)c->perm.get(),
-                       reorder_args(c->posn.get(), c->veln.get(), c->drhon.get(), b->st_mass.get(), b->st_id.get(), d, c->src_of.get()));
-    if (mapped) hipLaunchKernelGGL(k_compose, g1, bp, 0, st, n, (const int *)b->st_src.get(), c->src_of.get());
+    host_rebin(c, n, c->posn.get(), c->cellid.get(), c->count.get(), d.start, c->perm.get(),
+               reorder_args(c->posn.get(), c->veln.get(), c->drhon.get(), b->st_mass.get(), b->st_id.get(), d, c->src_of.get()));
+    if (mapped) hipLaunchKernelGGL(k_compose, dim3(div_up(n, kBlock)), dim3(kBlock), 0, st, n, (const int *)b->st_src.get(), c->src_of.get());
     hipLaunchKernelGGL(k_rebinned, dim3(1), dim3(1), 0, st, c->clock.get());
     SPHX_HIP(hipGetLastError());
-    c->cur = Q; c->lay = L; c->pos = 0;
+    c->sched.cur = Q; c->sched.lay = L; c->sched.pos = 0;
     c->h_clock->need_rebuild = 0;
     c->h_clock->drift = 0.0;
     if (c->h_pub) { c->h_pub->need_rebuild = 0; c->h_pub->drift = 0.0; }
@@ -266,19 +174,16 @@ void realign_member(sphx_batch *b, int m, int Q, int L)
 // all members into one phase at pos 0; forced: because the drift bound was hit (batch-wide cool-down, as forced_rebuild)
 void realign(sphx_batch *b, bool forced)
 {
-    const int Q = 1 - b->mem[0]->cur, L = 1 - b->mem[0]->lay;
+    Schedule &s = b->sched;
+    const int Q = 1 - b->mem[0]->sched.cur, L = 1 - b->mem[0]->sched.lay;
     for (int m = 0; m < b->M; ++m) realign_member(b, m, Q, L);
     SPHX_HIP(hipStreamSynchronize(b->stream));
-    b->cur = Q; b->lay = L; b->pos = 0;
+    s.cur = Q; s.lay = L; s.pos = 0;
     b->n_realign += 1;
     if (forced) {
-        const int64_t now = b->slot, K = b->mem[0]->rebuild_every;
-        const bool again = b->n_forced > 0 && now - b->cool_until <= 2 * K;
-        b->cool_len = again ? std::min<int64_t>(2 * std::max<int64_t>(b->cool_len, 16), 1024) : 16;
-        b->cool_until = now + b->cool_len;
-        b->n_forced += 1;
+        s.cool_down(s.slot, b->mem[0]->rebuild_every);
         if (debug_switches().log)
-            fprintf(stderr, "sphx: batch forced re-binning #%lld at slot %lld\n", (long long)b->n_forced, (long long)now);
+            fprintf(stderr, "sphx: batch forced re-binning #%lld at slot %lld\n", (long long)s.n_forced, (long long)s.slot);
     }
     batch_set_epochs(b);
 }
@@ -312,14 +217,15 @@ std::vector<int64_t> batch_read(sphx_batch *b)
         if (ex[m] > 0) c->out_ids = nullptr;  // a new step wrote new outputs in the current layout
         e_max = std::max(e_max, ex[m]);
         const sphx_ctx *c0 = b->mem[0];
-        same = same && c->cur == c0->cur && c->lay == c0->lay && c->pos == c0->pos;
+        same = same && c->sched.cur == c0->sched.cur && c->sched.lay == c0->sched.lay && c->sched.pos == c0->sched.pos;
         drift = drift || c->h_clock->need_rebuild;
         bad = bad || c->h_clock->status != 0;
     }
-    b->slot = b->epoch_slot + e_max;
+    b->sched.slot = b->epoch_slot + e_max;
     if (bad) return ex;  // (the caller throws; nothing is stepped again)
     if (same && !drift) {
-        b->cur = b->mem[0]->cur; b->lay = b->mem[0]->lay; b->pos = b->mem[0]->pos;
+        const Schedule &s0 = b->mem[0]->sched;
+        b->sched.cur = s0.cur; b->sched.lay = s0.lay; b->sched.pos = s0.pos;
         batch_set_epochs(b);
     } else {
         realign(b, drift);
@@ -345,9 +251,9 @@ void batch_run(sphx_batch *b, double t_target, std::vector<int64_t> budget)
             else most = std::max(most, budget[m]);
         }
         if (want == 0) break;
-        int64_t slots = std::min<int64_t>(want, b->n_forced ? 256 : 4096);
+        int64_t slots = std::min<int64_t>(want, b->sched.n_forced ? 256 : 4096);
         bool exact = false;
-        const int per_graph = graph_slots(b->mem[0]);
+        const int K = b->mem[0]->rebuild_every, per_graph = graph_slots(b->mem[0]);
         if (limited && slots >= most) { slots = most; exact = true; }
         else if (slots > per_graph) slots = ((slots + per_graph - 1) / per_graph) * per_graph;
         // (k_prepare: a budget <= 0 is "unlimited"; a member whose budget is used up is armed and disarmed at once, so that
@@ -356,7 +262,7 @@ void batch_run(sphx_batch *b, double t_target, std::vector<int64_t> budget)
         batch_arm(b, t_target, 0, true);
         for (int m = 0; m < b->M; ++m)
             if (budget[m] == 0) hipLaunchKernelGGL(k_disarm, dim3(1), dim3(1), 0, b->stream, b->mem[m]->clock.get());
-        batch_enqueue(b, slots, exact);
+        enqueue_slots(b->sched, b->stream, K, per_graph, slots, exact, batch_slot(b), [b, K] { b->sched.advance(K); });
         const std::vector<int64_t> ex = batch_read(b);
         for (int m = 0; m < b->M; ++m)
             if (budget[m] > 0) budget[m] = std::max<int64_t>(0, budget[m] - ex[m]);
@@ -501,7 +407,7 @@ SPHX_EXPORT int sphx_batch_create(sphx_batch **out, int n_members, const sphx_pa
         SPHX_HIP(hipHostMalloc(reinterpret_cast<void **>(&b->h_budget), sizeof(long long) * M, hipHostMallocDefault));
         SPHX_HIP(hipStreamSynchronize(b->stream));
         batch_set_epochs(b);
-        if (prm[0].t_end > t0) (void)batch_graph(b, graph_slots(c0));
+        if (prm[0].t_end > t0) (void)capture_slots(b->sched, b->stream, c0->rebuild_every, graph_slots(c0), batch_slot(b));
         *out = b;
         return SPHX_OK;
     } catch (const Error &e) {
@@ -537,8 +443,9 @@ SPHX_EXPORT int sphx_batch_enqueue_steps(sphx_batch *b, int64_t n_steps)
     require(n_steps > 0, "SPHX:Batch:steps", "n_steps must be positive");
     // no host sync: a member that stopped early (end time, status, drift bound) stays stopped when k_prepare re-evaluates its
     // loop condition; sphx_batch_sync realigns and takes the steps still owed
+    const int K = b->mem[0]->rebuild_every;
     batch_arm(b, b->mem[0]->prm.t_end, (long long)n_steps, false);
-    batch_enqueue(b, n_steps, true);
+    enqueue_slots(b->sched, b->stream, K, graph_slots(b->mem[0]), n_steps, true, batch_slot(b), [b, K] { b->sched.advance(K); });
     for (int m = 0; m < b->M; ++m) b->pending[m] = std::max<int64_t>(b->pending[m], b->mem[m]->h_clock->step) + n_steps;
     return SPHX_OK;
     SPHX_CATCH
@@ -585,7 +492,7 @@ SPHX_EXPORT int sphx_batch_info(sphx_batch *b, int *n_members, int *lanes_per_pa
     if (steps_per_graph) *steps_per_graph = graph_slots(c);
     if (rebuild_every) *rebuild_every = c->rebuild_every;
     if (skin) *skin = c->skin;
-    if (forced_rebuilds) *forced_rebuilds = b->n_forced;
+    if (forced_rebuilds) *forced_rebuilds = b->sched.n_forced;
     if (realignments) *realignments = b->n_realign;
     return SPHX_OK;
     SPHX_CATCH
@@ -595,9 +502,9 @@ SPHX_EXPORT int sphx_batch_graph_stats(sphx_batch *b, int64_t *slots_replayed, i
 {
     SPHX_TRY
     require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    if (slots_replayed) *slots_replayed = b->slots_replayed;
-    if (slots_eager) *slots_eager = b->slots_eager;
-    if (graphs_captured) *graphs_captured = b->graphs_captured;
+    if (slots_replayed) *slots_replayed = b->sched.slots_replayed;
+    if (slots_eager) *slots_eager = b->sched.slots_eager;
+    if (graphs_captured) *graphs_captured = b->sched.graphs_captured;
     return SPHX_OK;
     SPHX_CATCH
 }

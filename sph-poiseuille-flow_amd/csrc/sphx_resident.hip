@@ -55,6 +55,63 @@ struct KernelTimer {
     }
 };
 
+// The host's step-slot schedule of a context, of a batch and of each member of a batch.  A step slot is the set of launches
+// of one step; it does nothing when the device clock says the loop has stopped.  The phase: state buffers S[cur]
+// (x,y,vx,vy,drho), layout buffers L[lay] (mass,id,start,cell), `pos` = steps taken since the grid was built.  `slot` is the
+// step index the next enqueued slot will have if every slot before it executes.
+struct Schedule {
+    int cur = 0, lay = 0, pos = 0;
+    int64_t slot = 0;
+    int64_t cool_until = 0;  // after a forced re-binning every slot up to this index re-bins (cool-down)
+    int64_t cool_len = 0;    // length of the last cool-down (doubles when forced re-binnings keep coming)
+    int64_t n_forced = 0;    // forced re-binnings so far
+    // Replayable graphs, keyed by the phase they were captured from and their length: {cur, lay, pos, slots}.  A graph
+    // of graph_slots() slots (a multiple of the 2K-step period) hands the phase back unchanged, so a long run replays
+    // ONE graph whatever phase it was entered at; exact-length batches (sphx_ctx_enqueue_steps, advance with
+    // max_steps -- a caller logging every 20 steps) get a graph per (phase, length), captured the first time that
+    // combination comes up (or ahead of time by sphx_ctx_prepare_steps).
+    struct Graph { hipGraphExec_t exec = nullptr; bool launched = false; };
+    std::map<std::array<int, 4>, Graph> graphs;
+    int64_t slots_replayed = 0, slots_eager = 0, graphs_captured = 0;
+
+    // A forced re-binning is answered with a COOL-DOWN: for the next cool_len steps every step re-bins (exactly the loop
+    // without a skin), then the schedule returns to K.  What outruns the skin is almost always one particle making a
+    // few large transport shifts in a row (max over millions of particles: at 0.5-6 M particles it happens every few
+    // thousand steps); shrinking K for thousands of steps -- the first policy -- cost 30 % of the throughput of long
+    // runs at those sizes.  cool_until only changes at forced re-binnings (device-side events): the schedule stays
+    // independent of how the host chunks its calls.
+    bool rebuilds(int K) const { return pos >= K - 1 || slot < cool_until; }
+
+    // one slot on; returns whether it re-binned
+    bool advance(int K)
+    {
+        const bool rebuild = rebuilds(K);
+        slot += 1;
+        cur ^= 1;
+        if (rebuild) { lay ^= 1; pos = 0; }
+        else pos += 1;
+        return rebuild;
+    }
+
+    // a forced re-binning at slot `now`: 16 slots of cool-down, doubled (up to 1024) while the next forced re-binning
+    // follows the previous cool-down within two re-binning cycles, so a flow that really is too fast for the skin
+    // degrades to re-binning every step
+    void cool_down(int64_t now, int K)
+    {
+        const bool again = n_forced > 0 && now - cool_until <= 2 * (int64_t)K;
+        cool_len = again ? std::min<int64_t>(2 * std::max<int64_t>(cool_len, 16), 1024) : 16;
+        cool_until = now + cool_len;
+        n_forced += 1;
+    }
+
+    void drop_graphs()
+    {
+        for (auto &kv : graphs)
+            if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
+        graphs.clear();
+    }
+};
+
 }  // namespace sphx
 
 using namespace sphx;
@@ -82,19 +139,15 @@ struct sphx_ctx {
     // device clock tracks the largest drift (Clock::drift) and stops the loop before the bound is violated.
     double skin = 0.0;
     int rebuild_every = 1;       // re-binning interval K (constant)
-    int64_t cool_until = 0;      // after a forced rebuild every step up to this step index re-bins (cool-down)
-    int64_t cool_len = 0;        // length of the last cool-down (doubles when forced rebuilds keep coming)
-    int64_t prov_step = 0;       // step index the next enqueued slot will have if every slot before it executes
 
-    // where the current state lives: state buffers S[cur] (x,y,vx,vy,drho), layout buffers L[lay]
-    // (mass,id,start,cell); `pos` = steps taken since the grid was built.  Derived from the device step count.
-    int cur = 0, lay = 0, pos = 0;
+    // where the current state lives (Schedule: phase, cool-down, graphs); the phase is derived from the device step count
+    Schedule sched;
     int64_t epoch_step = 0;      // step count at which (epoch_cur, epoch_lay, epoch_pos, ...) held
     int epoch_cur = 0, epoch_lay = 0, epoch_pos = 0;
     int epoch_out_lay = 0;
     int out_lay = 0;             // layout the per-step outputs (rho,p,force,Vol,B) are stored in; when it is not
                                  // `lay`, tmp.src_of maps current slots to the slots of those outputs
-    int64_t n_forced_rebuilds = 0, last_forced_step = 0;
+    int64_t last_forced_step = 0;
     int64_t n_rebins = 0, epoch_n_rebins = 0;  // re-binnings executed by step slots of the static schedule (not the forced ones)
     int64_t pending_target = 0;  // step count the sphx_ctx_enqueue_steps calls since the last sync aim for
     bool have_step_outputs = false;
@@ -124,14 +177,6 @@ struct sphx_ctx {
     int n_blocks_particles = 0;  // grid of the LPP kernels (capacity based)
     int n_blocks_flat = 0;       // grid of one-thread-per-particle kernels
 
-    // Replayable graphs, keyed by the phase they were captured from and their length: {cur, lay, pos, slots}.  A graph
-    // of graph_slots() slots (a multiple of the 2K-step period) hands the phase back unchanged, so a long run replays
-    // ONE graph whatever phase it was entered at; exact-length batches (sphx_ctx_enqueue_steps, advance with
-    // max_steps -- a caller logging every 20 steps) get a graph per (phase, length), captured the first time that
-    // combination comes up (or ahead of time by sphx_ctx_prepare_steps).
-    struct CachedGraph { hipGraphExec_t exec = nullptr; bool launched = false; };
-    std::map<std::array<int, 4>, CachedGraph> graphs;
-    int64_t slots_replayed = 0, slots_eager = 0, graphs_captured = 0;
     int64_t chunk_slots = 128;   // slots enqueued between two host looks at the clock (adaptive, see advance)
     bool profiling = false;
     KernelTimer timer;
@@ -224,17 +269,10 @@ struct sphx_ctx {
         return tail_clock ? reinterpret_cast<unsigned long long *>(vpart.get()) : nullptr;
     }
 
-    void drop_graph()
-    {
-        for (auto &kv : graphs)
-            if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        graphs.clear();
-    }
-
     ~sphx_ctx()
     {
         if (stream) (void)hipStreamSynchronize(stream);  // the buffers go back to the pool: nothing may still use them
-        drop_graph();
+        sched.drop_graphs();
         if (steps_graph) (void)hipGraphExecDestroy(steps_graph);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
@@ -479,16 +517,15 @@ void launch_physics_any(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t
     }
 }
 
-// exclusive scan of the cell histogram into start_next (three kernels on big grids)
-void launch_cell_scan(sphx_ctx *c, const Clock *clk, int q, int *start_next)
+// exclusive scan of the cell histogram `count` into start_next (three kernels on big grids)
+void launch_cell_scan(sphx_ctx *c, const Clock *clk, int q, const int *count, int *start_next)
 {
     if (!c->big_scan) {
-        launch(c, "k_scan", k_scan_only, dim3(1), dim3(kScanBlock), clk, q, (const int *)c->count.get(), start_next,
-               c->grid.ncells);
+        launch(c, "k_scan", k_scan_only, dim3(1), dim3(kScanBlock), clk, q, count, start_next, c->grid.ncells);
     } else {
         int *tile_sum = c->tile.get(), *tile_off = c->tile.get() + c->n_tiles + 1;
-        launch(c, "k_scan_tiles", k_scan_tiles, dim3(c->n_tiles), dim3(kScanBlock), clk, q, (const int *)c->count.get(),
-               start_next, tile_sum, c->grid.ncells);
+        launch(c, "k_scan_tiles", k_scan_tiles, dim3(c->n_tiles), dim3(kScanBlock), clk, q, count, start_next, tile_sum,
+               c->grid.ncells);
         launch(c, "k_scan_sums", k_scan_only, dim3(1), dim3(kScanBlock), clk, q, (const int *)tile_sum, tile_off, c->n_tiles);
         launch(c, "k_scan_add", k_scan_add, dim3(c->n_tiles), dim3(kScanBlock), clk, q, start_next, (const int *)tile_off,
                c->grid.ncells, c->n_tiles);
@@ -624,16 +661,6 @@ void launch_step(sphx_ctx *c, int q, int l, int pos, bool rebuild)
     launch_scatter_reorder(c, clk, q, reorder_args(c->tmp.posn, c->tmp.veln, c->tmp.drhon, s.mass, s.id, d, c->tmp.src_of), d);
 }
 
-// A forced rebuild is answered with a COOL-DOWN: for the next cool_len steps every step re-bins (exactly the loop
-// without a skin), then the schedule returns to K.  What outruns the skin is almost always one particle making a
-// few large transport shifts in a row (max over millions of particles: at 0.5-6 M particles it happens every few
-// thousand steps); shrinking K for thousands of steps -- the first policy -- cost 30 % of the throughput of long
-// runs at those sizes.  The cool-down starts at 16 steps and doubles (up to 1024) while forced rebuilds keep coming
-// right after it ends, so a flow that really is too fast for the skin degrades to re-binning every step.
-// cool_until only changes at forced rebuilds (device-side events): the schedule stays independent of how the host
-// chunks its calls.
-bool slot_rebuilds(const sphx_ctx *c) { return c->pos >= c->rebuild_every - 1 || c->prov_step < c->cool_until; }
-
 // One step slot of a dynamic context: the four passes on S[q] writing the new state into S[1-q], the clock (which
 // decides rebuild_now), then the re-binning chain, every kernel of which returns at once unless rebuild_now is set:
 // histogram of the new positions, scan, scatter, id-canonical reorder into temporaries, copy back in place.
@@ -665,7 +692,7 @@ void launch_step_dyn(sphx_ctx *c, int q)
                      lean ? o.start : c->fstart_[1].get(), lean ? o.cell : c->fcell_[1].get(), lean ? o.posb : c->fposb_[1].get()};
     launch(c, "k_bin", k_bin, g1, bp, (const Clock *)clk, qf | kOnlyIfNoHistogram, c->grid, 0, (const double2 *)o.pos,
            c->cellid.get(), c->count.get());  // drift-triggered re-binnings only: pass E bins on the scheduled ones
-    launch_cell_scan(c, clk, qf, d.start);
+    launch_cell_scan(c, clk, qf, c->count.get(), d.start);
     launch_scatter_reorder(c, clk, qf, reorder_args(o.pos, o.vel, o.drho, s.mass, s.id, d, c->tmp.src_of), d, kDynBlocks);
     CopyBack cb{d.pos, d.vel, d.posb, o.pos, o.vel, o.posb, d.drho, d.mass, o.drho, o.mass, d.id, d.cell, d.start,
                 o.id, o.cell, o.start, c->grid.ncells + 1, lean ? 1 : 0};
@@ -697,21 +724,18 @@ void launch_slot_stats(sphx_ctx *c, int q)
     launch_flow_stats(c, q, c->fpos_[1 - q].get(), c->fvel_[1 - q].get(), c->fstats.cfg.every);
 }
 
-// host-side bookkeeping of one executed step
+// host-side bookkeeping of one step slot
 void track_step(sphx_ctx *c)
 {
-    if (c->dyn) {
-        c->prov_step += 1;
-        c->cur ^= 1;
+    Schedule &s = c->sched;
+    if (c->dyn) {  // the layout is rebuilt in place: only the parity alternates (lay and pos stay 0, the graphs go by cur)
+        s.slot += 1;
+        s.cur ^= 1;
         return;
     }
-    const bool rebuild = slot_rebuilds(c);
-    c->prov_step += 1;
-    c->out_lay = c->lay;  // outputs are stored in the layout the step ran in; after a rebuild tmp.src_of maps to it
-    c->out_par = c->cur;  // ... and (fuse_ea) in the record buffers of the step's state parity
-    c->cur ^= 1;
-    if (rebuild) { c->lay ^= 1; c->pos = 0; c->n_rebins += 1; }
-    else c->pos += 1;
+    c->out_lay = s.lay;  // outputs are stored in the layout the step ran in; after a rebuild tmp.src_of maps to it
+    c->out_par = s.cur;  // ... and (fuse_ea) in the record buffers of the step's state parity
+    if (s.advance(c->rebuild_every)) c->n_rebins += 1;
 }
 
 // arm the device clock for a batch (k_prepare) and count it (Clock::seq / sphx_ctx::host_seq)
@@ -730,117 +754,143 @@ int graph_slots(const sphx_ctx *c)
 constexpr int kMinGraphSlots = 4;    // shorter exact batches are launched eagerly (a replay costs ~50 us of host time)
 constexpr size_t kMaxGraphs = 96;    // cache bound: 2 * 2 * K phases for a caller with one cadence, K <= 16 in practice
 
-// the graph of `n` step slots entered at phase (cur, lay, pos) of the static schedule (dynamic contexts: only cur matters)
-sphx_ctx::CachedGraph &get_graph(sphx_ctx *c, int cur, int lay, int pos, int n)
+// ---- the step-slot schedule of contexts and batches: slot(q, l, p, rebuild) launches one step slot at phase (q, l, p) ----
+
+// How many of the `left` slots still to enqueue from the phase of s go into one graph: a whole graph of per_graph slots
+// (0: none), or -- exact_tail: the caller asked for exactly this many steps -- a shorter tail of at least kMinGraphSlots.
+// 0: the next slot is launched eagerly, as is every slot of a cool-down (every slot re-bins, see Schedule::rebuilds).
+int graph_run(const Schedule &s, int64_t left, int per_graph, bool exact_tail)
 {
-    const std::array<int, 4> key{cur, c->dyn ? 0 : lay, c->dyn ? 0 : pos, n};
-    auto it = c->graphs.find(key);
-    if (it != c->graphs.end()) return it->second;
-    if (c->graphs.size() >= kMaxGraphs) {
-        SPHX_HIP(hipStreamSynchronize(c->stream));  // earlier batches may still be replaying the graphs about to be destroyed
-        c->drop_graph();
+    if (s.slot < s.cool_until) return 0;
+    if (left >= per_graph) return per_graph;
+    return exact_tail && left >= kMinGraphSlots ? (int)left : 0;
+}
+
+// the graph of `n` step slots entered at the phase of s (static schedule: every K-th slot re-bins), captured on stream st
+// the first time it is asked for
+template <typename Slot>
+Schedule::Graph &capture_slots(Schedule &s, hipStream_t st, int K, int n, const Slot &slot)
+{
+    const std::array<int, 4> key{s.cur, s.lay, s.pos, n};
+    auto it = s.graphs.find(key);
+    if (it != s.graphs.end()) return it->second;
+    if (s.graphs.size() >= kMaxGraphs) {
+        SPHX_HIP(hipStreamSynchronize(st));  // earlier batches may still be replaying the graphs about to be destroyed
+        s.drop_graphs();
     }
-    const int K = c->rebuild_every;
-    const bool prof = c->profiling;
-    c->profiling = false;
-    SPHX_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    SPHX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     try {
-        int q = cur, l = lay, p = pos;
+        int q = s.cur, l = s.lay, p = s.pos;
         for (int j = 0; j < n; ++j) {
-            if (c->dyn) {
-                launch_step_dyn(c, q);
-            } else {
-                const bool rebuild = p == K - 1;
-                launch_step(c, q, l, p, rebuild);
-                if (rebuild) { l ^= 1; p = 0; }
-                else ++p;
-            }
-            launch_slot_stats(c, q);
+            const bool rebuild = p == K - 1;
+            slot(q, l, p, rebuild);
+            if (rebuild) { l ^= 1; p = 0; }
+            else ++p;
             q ^= 1;
         }
     } catch (...) {
         hipGraph_t junk = nullptr;
-        (void)hipStreamEndCapture(c->stream, &junk);
+        (void)hipStreamEndCapture(st, &junk);
         if (junk) (void)hipGraphDestroy(junk);
-        c->profiling = prof;
         throw;
     }
-    c->profiling = prof;
     hipGraph_t g = nullptr;
-    SPHX_HIP(hipStreamEndCapture(c->stream, &g));
+    SPHX_HIP(hipStreamEndCapture(st, &g));
     hipGraphExec_t exec = nullptr;
     const hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     SPHX_HIP(e);
-    sphx_ctx::CachedGraph &g_new = c->graphs[key];
-    g_new.exec = exec;
-    c->graphs_captured += 1;
-    return g_new;
+    Schedule::Graph &cached = s.graphs[key];
+    cached.exec = exec;
+    s.graphs_captured += 1;
+    return cached;
 }
 
-// Enqueue `slots` step slots from the current (cur, lay, pos); slots that find run[q]==0 are no-ops.  Whole graphs
-// are replayed from ANY phase of the static schedule (see sphx_ctx::graphs); what is left over is launched eagerly,
-// or -- exact_tail: the caller asked for exactly this many steps -- replayed as a graph of its own.  Only a cool-down
-// (every slot re-bins, see slot_rebuilds) runs eagerly throughout.  The host copies of cur/lay/pos advance as if
-// every slot executed; read_clock() recomputes them from the executed step count.
-// capture_only: build the graphs this call would replay, launch nothing (sphx_ctx_prepare_steps).
-void enqueue_slots(sphx_ctx *c, int64_t slots, bool exact_tail, bool capture_only = false)
+// Enqueue `slots` step slots from the phase of s on stream st; slots that find run[q]==0 are no-ops.  Whole graphs are
+// replayed from ANY phase of the static schedule (see Schedule::graphs), exact tails as graphs of their own (graph_run),
+// the rest is launched eagerly.  track() is the caller's bookkeeping of one slot (Schedule::advance at the least): the
+// phase advances as if every slot executed, the caller recomputes it from the executed step counts.
+template <typename Slot, typename Track>
+void enqueue_slots(Schedule &s, hipStream_t st, int K, int per_graph, int64_t slots, bool exact_tail, const Slot &slot,
+                   const Track &track)
 {
-    int64_t left = slots;
-    // capture_only walks the phases on copies
-    const int cur0 = c->cur, lay0 = c->lay, pos0 = c->pos, out_lay0 = c->out_lay;
-    const int64_t prov0 = c->prov_step;
-    while (left > 0) {
-        const int per_graph = graph_slots(c);
-        const bool steady = c->prov_step >= c->cool_until;
-        int n = 0;
-        if (!c->profiling && steady) {
-            if (left >= per_graph) n = per_graph;
-            else if (exact_tail && left >= kMinGraphSlots) n = (int)left;
-        }
+    for (int64_t left = slots; left > 0;) {
+        const int n = graph_run(s, left, per_graph, exact_tail);
         if (n > 0) {
-            sphx_ctx::CachedGraph &cg = get_graph(c, c->cur, c->lay, c->pos, n);
-            if (capture_only) {
-                // First replays are slow (~4 us per step slot on ROCm 7.2: the executable graph is set up on the device
-                // at its first launch, hipGraphUpload does not take that over): a graph that has never run is replayed
-                // once now with the clock disarmed (k_disarm, see sphx_ctx_prepare_steps), so every kernel of every slot
-                // returns at once and nothing changes.  Small channels only: there a step is ~20 us; on millions of
-                // particles a first replay is noise and an idle pass over the arrays is not free.
-                if (!cg.launched && c->n_blocks_particles <= 8192) {
-                    SPHX_HIP(hipGraphLaunch(cg.exec, c->stream));
-                    cg.launched = true;
-                }
-            } else {
-                SPHX_HIP(hipGraphLaunch(cg.exec, c->stream));
-                cg.launched = true;
-                c->slots_replayed += n;
-            }
-            for (int k = 0; k < n; ++k) track_step(c);
+            Schedule::Graph &g = capture_slots(s, st, K, n, slot);
+            SPHX_HIP(hipGraphLaunch(g.exec, st));
+            g.launched = true;
+            s.slots_replayed += n;
+            for (int k = 0; k < n; ++k) track();
             left -= n;
-            continue;
+        } else {
+            slot(s.cur, s.lay, s.pos, s.rebuilds(K));
+            s.slots_eager += 1;
+            track();
+            left -= 1;
         }
-        if (!capture_only) {
-            if (c->dyn) launch_step_dyn(c, c->cur);
-            else launch_step(c, c->cur, c->lay, c->pos, slot_rebuilds(c));
-            launch_slot_stats(c, c->cur);
-            c->slots_eager += 1;
+    }
+    SPHX_HIP(hipGetLastError());
+}
+
+// ---- a context's side of it ----
+
+// one step slot of a context: the static schedule's launches or a dynamic context's, then the slot's k_flow_stats
+auto ctx_slot(sphx_ctx *c)
+{
+    return [c](int q, int l, int p, bool rebuild) {
+        if (c->dyn) launch_step_dyn(c, q);
+        else launch_step(c, q, l, p, rebuild);
+        launch_slot_stats(c, q);
+    };
+}
+
+// graph length of a context's enqueues; 0 while profiling: every slot runs eagerly between its event pairs, and no graph is
+// captured with them
+int ctx_graph_slots(const sphx_ctx *c) { return c->profiling ? 0 : graph_slots(c); }
+
+// enqueue_slots for a context; read_clock() recomputes the phase from the executed step count
+void ctx_enqueue(sphx_ctx *c, int64_t slots, bool exact_tail)
+{
+    enqueue_slots(c->sched, c->stream, c->rebuild_every, ctx_graph_slots(c), slots, exact_tail, ctx_slot(c),
+                  [c] { track_step(c); });
+}
+
+// Capture the graphs ctx_enqueue(c, slots, true) would replay, walking the phases on copies; no step is launched
+// (sphx_ctx_prepare_steps).  First replays are slow (~4 us per step slot on ROCm 7.2: the executable graph is set up on the
+// device at its first launch, hipGraphUpload does not take that over): a graph that has never run is replayed once now with
+// the clock disarmed (k_disarm, see sphx_ctx_prepare_steps), so every kernel of every slot returns at once and nothing
+// changes.  Small channels only: there a step is ~20 us; on millions of particles a first replay is noise and an idle pass
+// over the arrays is not free.
+void prepare_graphs(sphx_ctx *c, int64_t slots)
+{
+    Schedule &s = c->sched;
+    const int cur0 = s.cur, lay0 = s.lay, pos0 = s.pos, out_lay0 = c->out_lay;
+    const int64_t slot0 = s.slot;
+    for (int64_t left = slots; left > 0;) {
+        const int n = graph_run(s, left, ctx_graph_slots(c), true);
+        if (n > 0) {
+            Schedule::Graph &g = capture_slots(s, c->stream, c->rebuild_every, n, ctx_slot(c));
+            if (!g.launched && c->n_blocks_particles <= 8192) {
+                SPHX_HIP(hipGraphLaunch(g.exec, c->stream));
+                g.launched = true;
+            }
         }
-        track_step(c);
-        --left;
+        const int taken = std::max(n, 1);
+        for (int k = 0; k < taken; ++k) track_step(c);
+        left -= taken;
     }
-    if (capture_only) {
-        c->cur = cur0; c->lay = lay0; c->pos = pos0; c->out_lay = out_lay0; c->prov_step = prov0;
-    }
+    s.cur = cur0; s.lay = lay0; s.pos = pos0; c->out_lay = out_lay0; s.slot = slot0;
     SPHX_HIP(hipGetLastError());
 }
 
 void set_epoch(sphx_ctx *c)
 {
     c->epoch_step = c->h_clock->step;
-    c->epoch_cur = c->cur; c->epoch_lay = c->lay; c->epoch_pos = c->pos; c->epoch_out_lay = c->out_lay;
+    c->epoch_cur = c->sched.cur; c->epoch_lay = c->sched.lay; c->epoch_pos = c->sched.pos; c->epoch_out_lay = c->out_lay;
     c->epoch_out_par = c->out_par;
     c->epoch_n_rebins = c->n_rebins;
-    c->prov_step = c->epoch_step;
+    c->sched.slot = c->epoch_step;
 }
 
 // wait for the stream: poll for a while (a blocking wait costs ~10 us of wake-up latency, which a 20-step batch of a
@@ -875,21 +925,22 @@ void read_clock(sphx_ctx *c)
 void replay_executed(sphx_ctx *c)
 {
     const int64_t executed = (int64_t)c->h_clock->step - c->epoch_step;
-    c->cur = c->epoch_cur; c->lay = c->epoch_lay; c->pos = c->epoch_pos; c->out_lay = c->epoch_out_lay;
+    Schedule &s = c->sched;
+    s.cur = c->epoch_cur; s.lay = c->epoch_lay; s.pos = c->epoch_pos; c->out_lay = c->epoch_out_lay;
     c->out_par = c->epoch_out_par;
     c->n_rebins = c->epoch_n_rebins;
-    c->prov_step = c->epoch_step;
+    s.slot = c->epoch_step;
     if (executed > 0) {
         int64_t left = executed;
         if (c->dyn) {  // only the parity matters
-            c->prov_step += left - (left & 1);
+            s.slot += left - (left & 1);
             left &= 1;
         }
         while (left > 0) {
-            if (c->prov_step >= c->cool_until && left > 4 * c->rebuild_every) {
+            if (s.slot >= s.cool_until && left > 4 * c->rebuild_every) {
                 // steady interval: (cur, lay, pos) repeats every 2K steps -> skip whole periods
                 const int64_t period = 2 * c->rebuild_every, skip = ((left - 1) / period - 1) * period;
-                if (skip > 0) { c->prov_step += skip; left -= skip; c->n_rebins += 2 * (skip / period); }
+                if (skip > 0) { s.slot += skip; left -= skip; c->n_rebins += 2 * (skip / period); }
             }
             track_step(c);
             --left;
@@ -899,47 +950,50 @@ void replay_executed(sphx_ctx *c)
     set_epoch(c);
 }
 
+// Sort n particles into cell order without a clock (context creation, forced re-binnings, realignments of batch members):
+// histogram of the positions `pos`, scan into `start`, scatter, and the gather `ra` into that order.  Not timed.
+void host_rebin(sphx_ctx *c, int n, const double2 *pos, int *cellid, int *count, int *start, int *perm, const ReorderArgs &ra)
+{
+    if (n <= 0) {
+        SPHX_HIP(hipMemsetAsync(start, 0, ((size_t)c->grid.ncells + 1) * sizeof(int), c->stream));
+        return;
+    }
+    const bool prof = c->profiling;
+    c->profiling = false;
+    const dim3 g1(div_up(n, kBlock)), bp(kBlock);
+    launch(c, "k_bin", k_bin, g1, bp, (const Clock *)nullptr, 0, c->grid, n, pos, cellid, count);
+    launch_cell_scan(c, nullptr, 0, count, start);
+    launch(c, "k_scatter", k_scatter, g1, bp, (const Clock *)nullptr, 0, n, (const int *)cellid, count, (const int *)start, perm);
+    launch(c, "k_reorder", k_reorder, g1, bp, (const Clock *)nullptr, 0, n, (const int *)cellid, (const int *)start,
+           (const int *)perm, ra);
+    c->profiling = prof;
+    SPHX_HIP(hipGetLastError());
+}
+
 // Re-bin the current state into the other buffers without taking a step: the device stopped the loop because
 // some particle drifted further than skin/2 from where it was binned.  Happens only when the flow is faster than
-// the skin was sized for; the rebuild interval shrinks by one when it happens in back-to-back cycles.
+// the skin was sized for; a cool-down follows (Schedule::cool_down).
 void forced_rebuild(sphx_ctx *c)
 {
-    const int q = c->cur, l = c->lay;
+    const int q = c->sched.cur, l = c->sched.lay;
     if (c->have_step_outputs && c->out_lay != l)
         throw Error(SPHX_ERR_STATE, "SPHX:Ctx:rebuild", "internal: forced rebuild straight after a rebuild step");
     const FluidSet s = c->view(q, l), d = c->view(1 - q, 1 - l);
-    hipStream_t st = c->stream;
-    const int n = c->h_clock->n;
-    const dim3 g1(c->n_blocks_flat), bp(kBlock);
-    const bool prof = c->profiling;
-    c->profiling = false;
-    hipLaunchKernelGGL(k_bin, g1, bp, 0, st, (const Clock *)nullptr, 0, c->grid, n, (const double2 *)s.pos, c->cellid.get(),
-                       c->count.get());
-    launch_cell_scan(c, nullptr, 0, d.start);
-    hipLaunchKernelGGL(k_scatter, g1, bp, 0, st, (const Clock *)nullptr, 0, n, (const int *)c->cellid.get(), c->count.get(),
-                       (const int *)d.start, c->perm.get());
     // src_of: new slot -> slot of the layout the last step's outputs (rho, p, force, Vol, B) are stored in
-    hipLaunchKernelGGL(k_reorder, g1, bp, 0, st, (const Clock *)nullptr, 0, n, (const int *)c->cellid.get(),
-                       (const int *)d.start, (const int *)c->perm.get(),
-                       reorder_args(s.pos, s.vel, s.drho, s.mass, s.id, d, c->tmp.src_of));
-    hipLaunchKernelGGL(k_rebinned, dim3(1), dim3(1), 0, st, c->clock.get());
-    c->profiling = prof;
+    host_rebin(c, c->h_clock->n, s.pos, c->cellid.get(), c->count.get(), d.start, c->perm.get(),
+               reorder_args(s.pos, s.vel, s.drho, s.mass, s.id, d, c->tmp.src_of));
+    hipLaunchKernelGGL(k_rebinned, dim3(1), dim3(1), 0, c->stream, c->clock.get());
     SPHX_HIP(hipGetLastError());
-    c->cur = 1 - q; c->lay = 1 - l; c->pos = 0;  // out_lay stays l
+    c->sched.cur = 1 - q; c->sched.lay = 1 - l; c->sched.pos = 0;  // out_lay stays l
     c->h_clock->need_rebuild = 0;
     c->h_clock->drift = 0.0;
     if (c->h_pub) { c->h_pub->need_rebuild = 0; c->h_pub->drift = 0.0; }  // (the published copy may be read again before the next batch)
-    // cool-down (see slot_rebuilds): 16 steps, doubled while the next forced rebuild follows the previous cool-down
-    // within two rebuild cycles
     const int64_t now = c->h_clock->step;
-    const bool again = c->n_forced_rebuilds > 0 && now - c->cool_until <= 2 * (int64_t)c->rebuild_every;
-    c->cool_len = again ? std::min<int64_t>(2 * std::max<int64_t>(c->cool_len, 16), 1024) : 16;
-    c->cool_until = now + c->cool_len;
+    c->sched.cool_down(now, c->rebuild_every);
     if (debug_switches().log)
         fprintf(stderr, "sphx: forced rebuild #%lld at step %lld (drift bound hit): re-binning every step for %lld steps\n",
-                (long long)c->n_forced_rebuilds + 1, (long long)now, (long long)c->cool_len);
+                (long long)c->sched.n_forced, (long long)now, (long long)c->sched.cool_len);
     c->last_forced_step = now;
-    c->n_forced_rebuilds += 1;
     set_epoch(c);
 }
 
@@ -979,24 +1033,6 @@ int pick_lpp(int nf)
 
 // rows of the per-lane neighbour list: >= 96 entries per particle (fluid ring ~30-45 + wall ring up to ~20)
 int nl_cap_for(int lpp) { return std::max(96 / lpp, 16); }
-
-// sort `n` particles given in arbitrary order into cell order on the device (context creation)
-void initial_sort(sphx_ctx *c, const Grid &g, int n, const double2 *pos, int *cellid, int *count, int *start, int *perm,
-                  const ReorderArgs &ra)
-{
-    hipStream_t s = c->stream;
-    if (n <= 0) {
-        SPHX_HIP(hipMemsetAsync(start, 0, ((size_t)g.ncells + 1) * sizeof(int), s));
-        return;
-    }
-    hipLaunchKernelGGL(k_bin, dim3(div_up(n, kBlock)), dim3(kBlock), 0, s, (const Clock *)nullptr, 0, g, n, pos, cellid, count);
-    hipLaunchKernelGGL(k_scan_only, dim3(1), dim3(kScanBlock), 0, s, (const Clock *)nullptr, 0, (const int *)count, start, g.ncells);
-    hipLaunchKernelGGL(k_scatter, dim3(div_up(n, kBlock)), dim3(kBlock), 0, s, (const Clock *)nullptr, 0, n,
-                       (const int *)cellid, count, (const int *)start, perm);
-    hipLaunchKernelGGL(k_reorder, dim3(div_up(n, kBlock)), dim3(kBlock), 0, s, (const Clock *)nullptr, 0, n,
-                       (const int *)cellid, (const int *)start, (const int *)perm, ra);
-    SPHX_HIP(hipGetLastError());
-}
 
 Phys make_phys(const sphx_params *prm)
 {
@@ -1147,8 +1183,8 @@ void upload_fluid(sphx_ctx *c, int n, const double *hx, const double *hy, const 
         if (wrap) hipLaunchKernelGGL(k_wrap_x, dim3(div_up(n, kBlock)), dim3(kBlock), 0, s, n, c->posn.get(), c->prm.DL);
     }
     const FluidSet d = c->view(0, 0);
-    initial_sort(c, c->grid, n, c->posn.get(), c->cellid.get(), c->count.get(), d.start, c->perm.get(),
-                 reorder_args(c->posn.get(), c->veln.get(), c->drhon.get(), c->fmass_[1].get(), c->fid_[1].get(), d, nullptr));
+    host_rebin(c, n, c->posn.get(), c->cellid.get(), c->count.get(), d.start, c->perm.get(),
+               reorder_args(c->posn.get(), c->veln.get(), c->drhon.get(), c->fmass_[1].get(), c->fid_[1].get(), d, nullptr));
     SPHX_HIP(hipStreamSynchronize(s));  // host staging vectors die after this
 }
 
@@ -1179,7 +1215,7 @@ void upload_walls(sphx_ctx *c, int nw, const double *hx, const double *hy, const
     ra.n2 = 1; ra.src2[0] = tpos.get(); ra.dst2[0] = c->wpos.get();
     ra.n4 = 1; ra.src4[0] = ta.get(); ra.dst4[0] = c->wa.get();
     ra.id_src = tid.get(); ra.id_dst = c->wid.get(); ra.src_of = nullptr; ra.cell_dst = nullptr;
-    initial_sort(c, g, nw, tpos.get(), tcell.get(), tcount.get(), c->wstart.get(), tperm.get(), ra);
+    host_rebin(c, nw, tpos.get(), tcell.get(), tcount.get(), c->wstart.get(), tperm.get(), ra);
     hipLaunchKernelGGL(k_row_any, dim3(div_up(g.ncy, 64)), dim3(64), 0, s, g, (const int *)c->wstart.get(), c->wrow_any.get());
     SPHX_HIP(hipGetLastError());
     SPHX_HIP(hipStreamSynchronize(s));  // temporaries die here
@@ -1210,7 +1246,7 @@ void init_clock(sphx_ctx *c, int n, double t0, int64_t step0)
     hipLaunchKernelGGL(k_vmax_init, dim3(1), dim3(kScanBlock), 0, s, c->clock.get(), c->grid, (const double2 *)c->fpos_[0].get(),
                        (const double2 *)c->fvel_[0].get(), (double *)nullptr);
     SPHX_HIP(hipGetLastError());
-    c->cur = 0; c->lay = 0; c->pos = 0; c->out_lay = 0;
+    c->sched.cur = 0; c->sched.lay = 0; c->sched.pos = 0; c->out_lay = 0;
     set_epoch(c);
     c->pending_target = step0;
 }
@@ -1392,7 +1428,7 @@ void ctx_setup(sphx_ctx *c, const sphx_params *prm, int n_fluid, int n_total, co
     read_clock(c);
     // capture the step graphs now, not inside somebody's timed region (a few ms) -- unless this context can never
     // step (the one-shot contexts behind sphx_neighbor_search)
-    if (prm->t_end > t0) (void)get_graph(c, c->cur, c->lay, c->pos, graph_slots(c));
+    if (prm->t_end > t0) (void)capture_slots(c->sched, c->stream, c->rebuild_every, graph_slots(c), ctx_slot(c));
 }
 
 // emit the MEX-convention pair list of the current ordering into the ctx-held buffers
@@ -1401,7 +1437,7 @@ void emit_pairs(sphx_ctx *c, bool fill)
     const int nf = c->nf;
     hipStream_t s = c->stream;
     DevBuf<int> cnt(nf), off((size_t)nf + 1);
-    const FluidSet fs = c->view(c->cur, c->lay);
+    const FluidSet fs = c->view(c->sched.cur, c->sched.lay);
     const Clock *clk = c->clock.get();
     const dim3 g1(div_up(nf, kBlock)), b1(kBlock);
     hipLaunchKernelGGL(k_pairs<0>, g1, b1, 0, s, clk, c->grid, c->phys, fs, c->walls, cnt.get(), (const int *)nullptr,
@@ -1479,7 +1515,7 @@ SPHX_EXPORT int sphx_ctx_advance(sphx_ctx *c, double t_target, int64_t max_steps
     read_clock(c);  // steps enqueued with sphx_ctx_enqueue_steps may still be in flight
     for (int guard = 0; guard < 1000000; ++guard) {
         if (c->h_clock->need_rebuild && c->h_clock->status == 0) forced_rebuild(c);
-        arm_clock(c, t_target, (long long)max_steps, c->cur, (const double *)nullptr);
+        arm_clock(c, t_target, (long long)max_steps, c->sched.cur, (const double *)nullptr);
         // how many slots this call needs, from the unclipped dt; over-provision to whole graphs when unlimited
         const Clock &k = *c->h_clock;
         const double dt_est = host_dt_unclipped(c, k.vmax);
@@ -1494,13 +1530,13 @@ SPHX_EXPORT int sphx_ctx_advance(sphx_ctx *c, double t_target, int64_t max_steps
         else if (!c->profiling && slots > per_graph) slots = ((slots + per_graph - 1) / per_graph) * per_graph;
         if (slots < 1) slots = 1;
         const int64_t step_before = c->h_clock->step;
-        enqueue_slots(c, slots, exact);
+        ctx_enqueue(c, slots, exact);
         read_clock(c);
         const int64_t executed = c->h_clock->step - step_before;
         // ... and in between by how often it has been stopping: behind a stop the rest of the chunk drains as empty launches
         // (half a 4096-slot chunk: ~35 ms at 0.5 M particles, measured), a look at the clock costs ~40 us -- chunks of 1/16 of
         // the steps since the last forced rebuild keep both near 0.5 us per step.
-        const int64_t cap = c->n_forced_rebuilds == 0
+        const int64_t cap = c->sched.n_forced == 0
                                 ? 4096
                                 : std::clamp<int64_t>((c->h_clock->step - c->last_forced_step) / 16, 64, 4096);
         c->chunk_slots = c->h_clock->need_rebuild ? 64 : std::min<int64_t>(cap, 2 * c->chunk_slots);
@@ -1528,8 +1564,8 @@ SPHX_EXPORT int sphx_ctx_enqueue_steps(sphx_ctx *c, int64_t n_steps)
     // no host sync here: if an earlier batch stopped early (end time, status, stale grid) the loop condition is
     // still false when k_prepare re-evaluates it, so every slot of this batch is a no-op; sphx_ctx_sync sorts
     // out the grid and takes the steps that are still owed
-    arm_clock(c, c->prm.t_end, (long long)n_steps, c->cur, (const double *)nullptr);
-    enqueue_slots(c, n_steps, true);
+    arm_clock(c, c->prm.t_end, (long long)n_steps, c->sched.cur, (const double *)nullptr);
+    ctx_enqueue(c, n_steps, true);
     c->pending_target = std::max<int64_t>(c->pending_target, c->h_clock->step) + n_steps;
     return SPHX_OK;
     SPHX_CATCH
@@ -1544,7 +1580,7 @@ SPHX_EXPORT int sphx_ctx_prepare_steps(sphx_ctx *c, int64_t n_steps)
     read_clock(c);  // the phase the next batch starts from
     if (c->h_clock->need_rebuild && c->h_clock->status == 0) forced_rebuild(c);
     hipLaunchKernelGGL(k_disarm, dim3(1), dim3(1), 0, c->stream, c->clock.get());  // (every batch re-arms with k_prepare)
-    enqueue_slots(c, n_steps, true, true);
+    prepare_graphs(c, n_steps);
     SPHX_HIP(hipStreamSynchronize(c->stream));
     return SPHX_OK;
     SPHX_CATCH
@@ -1554,9 +1590,9 @@ SPHX_EXPORT int sphx_ctx_graph_stats(sphx_ctx *c, int64_t *slots_replayed, int64
 {
     SPHX_TRY
     require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
-    if (slots_replayed) *slots_replayed = c->slots_replayed;
-    if (slots_eager) *slots_eager = c->slots_eager;
-    if (graphs_captured) *graphs_captured = c->graphs_captured;
+    if (slots_replayed) *slots_replayed = c->sched.slots_replayed;
+    if (slots_eager) *slots_eager = c->sched.slots_eager;
+    if (graphs_captured) *graphs_captured = c->sched.graphs_captured;
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1577,8 +1613,8 @@ static void settle_owed(sphx_ctx *c)
             c->chunk_slots = 64;
         }
         const int64_t n = std::min(owed, c->chunk_slots);
-        arm_clock(c, c->prm.t_end, (long long)n, c->cur, (const double *)nullptr);
-        enqueue_slots(c, n, false);
+        arm_clock(c, c->prm.t_end, (long long)n, c->sched.cur, (const double *)nullptr);
+        ctx_enqueue(c, n, false);
         read_clock(c);
         if (!c->h_clock->need_rebuild) c->chunk_slots = std::min<int64_t>(4096, 2 * c->chunk_slots);
     }
@@ -1609,7 +1645,7 @@ SPHX_EXPORT int sphx_ctx_download(sphx_ctx *c, double *pos, double *vel, double 
         throw Error(SPHX_ERR_STATE, "SPHX:Ctx:download", "rho/p/force/Vol/B exist only after at least one step");
     const int nf = c->nf, nw = c->nw, nt = c->nt;
     hipStream_t s = c->stream;
-    const FluidSet fs = c->view(c->cur, c->lay);
+    const FluidSet fs = c->view(c->sched.cur, c->sched.lay);
     // ordering the step outputs are stored in: the layout the step ran in (static schedule), or -- dynamic contexts,
     // which re-bin in place -- the current ids reached through src_of when the last step ended with a re-binning
     const int *id_old = c->dyn ? fs.id : (c->out_ids ? c->out_ids : c->fid_[c->out_lay].get());
@@ -1666,14 +1702,14 @@ SPHX_EXPORT int sphx_ctx_monitor(sphx_ctx *c, double *tau_bottom, double *tau_to
     settle_owed(c);
     if (c->h_clock->need_rebuild && c->h_clock->status == 0) forced_rebuild(c);  // the pair sweeps need valid bins
     hipStream_t s = c->stream;
-    const FluidSet fs = c->view(c->cur, c->lay);
+    const FluidSet fs = c->view(c->sched.cur, c->sched.lay);
     if (tau_bottom || tau_top) {
         if (!c->have_step_outputs)
             throw Error(SPHX_ERR_STATE, "SPHX:Ctx:monitor", "wall shear needs Vol/B of a completed step");
         const int nblk = c->n_blocks_flat;
         hipLaunchKernelGGL(k_wall_shear, dim3(nblk), dim3(kBlock), 0, s, (const Clock *)c->clock.get(), c->grid, c->phys, fs,
                            c->tmp_par[c->fuse_ea ? c->out_par : 0], c->walls,
-                           (c->dyn ? c->h_clock->fresh != 0 : (c->out_lay != c->lay || c->out_ids)) ? 1 : 0, c->tau_part.get());
+                           (c->dyn ? c->h_clock->fresh != 0 : (c->out_lay != c->sched.lay || c->out_ids)) ? 1 : 0, c->tau_part.get());
         hipLaunchKernelGGL(k_tau_final, dim3(1), dim3(kScanBlock), 0, s, nblk, (const double *)c->tau_part.get(),
                            c->phys.DL, c->tau_out.get());
         double h[2];
@@ -1834,7 +1870,7 @@ sphx_ctx *stats_ctx(sphx_ctx *c, bool need_on)
 void stats_drop_graphs(sphx_ctx *c)
 {
     SPHX_HIP(hipStreamSynchronize(c->stream));
-    c->drop_graph();
+    c->sched.drop_graphs();
 }
 
 void stats_zero(sphx_ctx *c)
@@ -1910,7 +1946,7 @@ SPHX_EXPORT int sphx_ctx_flow_stats_sample(sphx_ctx *c)
     SPHX_TRY
     stats_ctx(c, true);
     settle_owed(c);  // the state sphx_ctx_download would return
-    const FluidSet fs = c->view(c->cur, c->lay);
+    const FluidSet fs = c->view(c->sched.cur, c->sched.lay);
     launch_flow_stats(c, 0, fs.pos, fs.vel, 0);
     SPHX_HIP(hipGetLastError());
     return SPHX_OK;
@@ -1969,7 +2005,7 @@ SPHX_EXPORT int sphx_ctx_grid_policy(sphx_ctx *c, int *rebuild_every, double *sk
     require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
     if (rebuild_every) *rebuild_every = c->rebuild_every;
     if (skin) *skin = c->skin;
-    if (forced_rebuilds) *forced_rebuilds = c->dyn ? (int64_t)c->h_clock->n_drift_rebuilds : c->n_forced_rebuilds;
+    if (forced_rebuilds) *forced_rebuilds = c->dyn ? (int64_t)c->h_clock->n_drift_rebuilds : c->sched.n_forced;
     if (drift) *drift = c->h_clock->drift;
     return SPHX_OK;
     SPHX_CATCH
@@ -2224,7 +2260,7 @@ SPHX_EXPORT int sphx_slab_local_vmax(sphx_ctx *c, double *vmax_dev)
     SPHX_TRY
     require(c != nullptr && c->is_slab && vmax_dev != nullptr, "SPHX:Slab:ctx", "not a slab context");
     require(c->rebuild_every == 1, "SPHX:Slab:protocol", "local_vmax / prepare / compute / finish drive a slab created with rebuild_every = 1");
-    const FluidSet fs = c->view(c->cur, c->cur);
+    const FluidSet fs = c->view(c->sched.cur, c->sched.cur);
     hipLaunchKernelGGL(k_vmax_init, dim3(1), dim3(kScanBlock), 0, c->stream, c->clock.get(), c->grid, (const double2 *)fs.pos,
                        (const double2 *)fs.vel, vmax_dev);
     SPHX_HIP(hipGetLastError());
@@ -2238,7 +2274,7 @@ SPHX_EXPORT int sphx_slab_prepare(sphx_ctx *c, double t_target, int64_t max_step
     SPHX_TRY
     require(c != nullptr && c->is_slab, "SPHX:Slab:ctx", "not a slab context");
     require(c->rebuild_every == 1, "SPHX:Slab:protocol", "local_vmax / prepare / compute / finish drive a slab created with rebuild_every = 1");
-    arm_clock(c, t_target, (long long)max_steps, c->cur, vmax_global_dev);
+    arm_clock(c, t_target, (long long)max_steps, c->sched.cur, vmax_global_dev);
     SPHX_HIP(hipGetLastError());
     return SPHX_OK;
     SPHX_CATCH
@@ -2249,7 +2285,7 @@ namespace {
 // first half of a slab step on the context's stream: the four neighbour passes, pack, seal + local max |v|
 void slab_compute_impl(sphx_ctx *c, double *send_left_dev, double *send_right_dev, double *vmax_local_dev)
 {
-    const int q = c->cur;
+    const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
     auto body = [&]() {
         launch_physics_any(c, q, c->view(q, q), c->tmp, 0);
@@ -2268,7 +2304,7 @@ void slab_compute_impl(sphx_ctx *c, double *send_left_dev, double *send_right_de
 // second half: unpack the received messages, clock update with the global max |v|, cell rebuild
 void slab_finish_impl(sphx_ctx *c, const double *recv_left_dev, const double *recv_right_dev, const double *vmax_global_dev)
 {
-    const int q = c->cur;
+    const int q = c->sched.cur;
     Clock *clk = c->clock.get();
     const dim3 bp(kBlock);
     auto body = [&]() {
@@ -2299,7 +2335,7 @@ void slab_finish_impl(sphx_ctx *c, const double *recv_left_dev, const double *re
     const void *key[3] = {recv_left_dev, recv_right_dev, vmax_global_dev};
     slab_half(c, 1, q, key, body);
     SPHX_HIP(hipGetLastError());
-    c->cur ^= 1;
+    c->sched.cur ^= 1;
     c->slab_steps_enqueued += 1;
 }
 
@@ -2661,13 +2697,13 @@ SPHX_EXPORT int sphx_slab_comm_destroy(sphx_ctx *c)
 namespace {
 
 // ---- one step of a skinned slab, in four phases separated by the three exchanges (see SlabLists) ----
-FluidSet slab_new_state(sphx_ctx *c) { return c->view(1 - c->cur, 0); }  // S[1-q] with the (in-place) layout arrays
+FluidSet slab_new_state(sphx_ctx *c) { return c->view(1 - c->sched.cur, 0); }  // S[1-q] with the (in-place) layout arrays
 
 constexpr int kTicketBlocks = 1024;  // largest grid of the kernels that end with last_workgroup_out (~20 ns per ticket)
 
 void slab_phase1(sphx_ctx *c)  // passes A..E into S[1-q]; the tail workgroup of pass E leaves the local maxima in vmax_l[0..1]
 {
-    const int q = c->cur;
+    const int q = c->sched.cur;
     const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
     FluidTmp t = c->tmp;
     t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
@@ -2691,7 +2727,7 @@ void slab_pass_a(sphx_ctx *c, int q, int dmode, int part)
 }
 void slab_phase1_abc(sphx_ctx *c)
 {
-    const int q = c->cur;
+    const int q = c->sched.cur;
     const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
     FluidTmp t = c->tmp;
     t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
@@ -2705,12 +2741,12 @@ void slab_phase1_abc(sphx_ctx *c)
 // workgroups of the NEXT step's pass A need nothing the exchange brings -- they run while it is under way
 void slab_pass_a_interior(sphx_ctx *c)
 {
-    slab_pass_a(c, c->cur, 4, 1);
+    slab_pass_a(c, c->sched.cur, 4, 1);
     c->a_interior_done = true;
 }
 void slab_local_maxima_of_step(sphx_ctx *c, hipStream_t aux)
 {
-    const int q = c->cur;
+    const int q = c->sched.cur;
     const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
     hipLaunchKernelGGL(k_slab_maxima, dim3(kSlabMaxBlocks), dim3(kBlock), 0, aux, (const Clock *)c->clock.get(), q, c->grid,
                        c->n_vpart, (const double *)c->dpart.get(), (const double2 *)o.vel, (const int *)s.cell, c->max_part.get(),
@@ -2718,7 +2754,7 @@ void slab_local_maxima_of_step(sphx_ctx *c, hipStream_t aux)
 }
 void slab_phase1_e(sphx_ctx *c)
 {
-    const int q = c->cur;
+    const int q = c->sched.cur;
     const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
     FluidTmp t = c->tmp;
     t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
@@ -2727,7 +2763,7 @@ void slab_phase1_e(sphx_ctx *c)
 
 void slab_phase2(sphx_ctx *c)  // global maxima known: re-binning decision, message A, clock -- one launch
 {
-    const int q = c->cur;
+    const int q = c->sched.cur;
     SlabPack p = c->pack;
     p.send_l = c->msg_sl.get();
     p.send_r = c->msg_sr.get();
@@ -2740,14 +2776,14 @@ void slab_phase2(sphx_ctx *c)  // global maxima known: re-binning decision, mess
 void slab_phase3(sphx_ctx *c)  // message A arrived (and with it the ids of the lists the neighbours made in the previous step):
                                // refresh the halo copies, or re-bin and make the lists of the next cycle
 {
-    const int q = c->cur, qf = q | kOnlyIfRebuild;
+    const int q = c->sched.cur, qf = q | kOnlyIfRebuild;
     Clock *clk = c->clock.get();
     const FluidSet d = slab_new_state(c);
     launch(c, "k_slab_unpack3", k_slab_unpack3, dim3(div_up((size_t)2 * c->msg_cap, kBlock)), dim3(kBlock), clk, q, c->grid, d,
            c->pack, c->lists, (const double *)c->msg_rl.get(), (const double *)c->msg_rr.get(), (const int *)c->ids_r_[0].get(),
            (const int *)c->ids_r_[1].get(), c->n_new.get(), c->flags.get(), c->ticket.get());
     const int kRebinBlocks = 4096;  // grid-stride: on the steps that do not re-bin these launches return at once
-    launch_cell_scan(c, clk, qf, d.start);
+    launch_cell_scan(c, clk, qf, c->count.get(), d.start);
     launch_scatter_reorder(c, clk, qf,
                            reorder_args(c->kpos.get(), c->kvel.get(), c->kdrho.get(), c->kmass.get(), c->kid.get(), d, nullptr,
                                         c->slot_of_id.get()),
@@ -2759,14 +2795,14 @@ void slab_phase3(sphx_ctx *c)  // message A arrived (and with it the ids of the 
 void slab_phase4(sphx_ctx *c)  // host bookkeeping of the step (the ids made in phase 3 travel with the next step's message A)
 {
     SPHX_HIP(hipGetLastError());
-    c->cur ^= 1;
+    c->sched.cur ^= 1;
     c->slab_steps_enqueued += 1;
 }
 
 // the exchange lists of the first cycle (the layout of slab_setup): send lists + ids out, then (ids in) receive slots
 void slab_lists_out(sphx_ctx *c)
 {
-    const FluidSet d = c->view(c->cur, 0);
+    const FluidSet d = c->view(c->sched.cur, 0);
     SPHX_HIP(hipMemsetAsync(c->send_cnt.get(), 0, 2 * sizeof(int), c->stream));
     hipLaunchKernelGGL(k_slab_sendlist, dim3(std::min(c->n_blocks_flat, kTicketBlocks)), dim3(kBlock), 0, c->stream,
                        (const Clock *)c->clock.get(), 0, c->grid, d, c->pack, c->lists, c->flags.get(), 1, c->ticket.get());
@@ -2775,14 +2811,14 @@ void slab_lists_in(sphx_ctx *c)
 {
     hipLaunchKernelGGL(k_slab_recvslots, dim3(div_up((size_t)2 * c->msg_cap, kBlock)), dim3(kBlock), 0, c->stream,
                        (const Clock *)c->clock.get(), 0, c->pack, c->lists, (const int *)c->ids_r_[0].get(),
-                       (const int *)c->ids_r_[1].get(), (const int *)c->view(c->cur, 0).id, c->flags.get(), 1);
+                       (const int *)c->ids_r_[1].get(), (const int *)c->view(c->sched.cur, 0).id, c->flags.get(), 1);
     SPHX_HIP(hipGetLastError());
     c->lists_ready = true;
 }
 
 void slab_local_maxima(sphx_ctx *c)  // arming: max |v| of the owned particles of the current state, drift 0
 {
-    const FluidSet fs = c->view(c->cur, c->rebuild_every > 1 ? 0 : c->cur);
+    const FluidSet fs = c->view(c->sched.cur, c->rebuild_every > 1 ? 0 : c->sched.cur);
     SPHX_HIP(hipMemsetAsync(c->vmax_l.get(), 0, 2 * sizeof(double), c->stream));
     hipLaunchKernelGGL(k_vmax_init, dim3(1), dim3(kScanBlock), 0, c->stream, c->clock.get(), c->grid, (const double2 *)fs.pos,
                        (const double2 *)fs.vel, c->vmax_l.get(), (const int *)fs.cell);
@@ -2957,7 +2993,7 @@ struct GroupLoop {
                 // workgroups of the next step's pass A, which the neighbours need not wait for (the in-process ring keeps the
                 // copies that stand in for the exchange on the slab's own stream: what it tests is the split itself)
                 if (!serial) SPHX_HIP(hipEventRecord(c->ev_received, c->stream));
-                slab_pass_a(c, 1 - c->cur, 4, 1);
+                slab_pass_a(c, 1 - c->sched.cur, 4, 1);
                 c->a_interior_done = true;
             }
         } else {
@@ -3003,7 +3039,7 @@ struct GroupLoop {
     bool graph_matches() const
     {
         const sphx_ctx *c0 = ctxs[0];
-        if (!c0->steps_graph || (int)c0->steps_graph_ring.size() != n || c0->steps_graph_cur != c0->cur) return false;
+        if (!c0->steps_graph || (int)c0->steps_graph_ring.size() != n || c0->steps_graph_cur != c0->sched.cur) return false;
         for (int r = 0; r < n; ++r) if (c0->steps_graph_ring[r] != ctxs[r]) return false;
         return true;
     }
@@ -3061,9 +3097,9 @@ SPHX_EXPORT int sphx_slab_run(sphx_ctx *c, double t_target, int64_t n_steps)
     if (c->slab_steps_enqueued == 0) {
         slab_local_maxima(c);
         loop.R.check(loop.R.AllReduce(vl, vg, 2, ncclDouble, ncclMax, c->comm, loop.st), "ncclAllReduce");
-        arm_clock(c, t_target, (long long)n_steps, c->cur, (const double *)vg);
+        arm_clock(c, t_target, (long long)n_steps, c->sched.cur, (const double *)vg);
     } else {
-        arm_clock(c, t_target, (long long)n_steps, c->cur, (const double *)nullptr);
+        arm_clock(c, t_target, (long long)n_steps, c->sched.cur, (const double *)nullptr);
     }
     if (skinned && !c->lists_ready) {
         slab_lists_out(c);
@@ -3071,7 +3107,7 @@ SPHX_EXPORT int sphx_slab_run(sphx_ctx *c, double t_target, int64_t n_steps)
         slab_lists_in(c);
     }
     int64_t k = 0;
-    if (c->steps_graph && c->steps_graph_cur == c->cur)  // whole replays of the step graph (sphx_slab_graph_prepare) ...
+    if (c->steps_graph && c->steps_graph_cur == c->sched.cur)  // whole replays of the step graph (sphx_slab_graph_prepare) ...
         for (; n_steps - k >= kSlabGraphSteps; k += kSlabGraphSteps) {
             SPHX_HIP(hipGraphLaunch(c->steps_graph, loop.st));
             c->slab_steps_enqueued += kSlabGraphSteps;
@@ -3101,7 +3137,7 @@ SPHX_EXPORT int sphx_slab_group_run(sphx_ctx **ctxs, int n, double t_target, int
         sphx_ctx *c = ctxs[r];
         loop.wait_others(r, &sphx_ctx::ev_computed);
         if (fresh_state) loop.max_of_all(c);
-        arm_clock(c, t_target, (long long)n_steps, c->cur, fresh_state ? (const double *)c->vmax_g.get() : (const double *)nullptr);
+        arm_clock(c, t_target, (long long)n_steps, c->sched.cur, fresh_state ? (const double *)c->vmax_g.get() : (const double *)nullptr);
         if (loop.skinned && !c->lists_ready) slab_lists_out(c);
     }
     loop.done(&sphx_ctx::ev_received);
@@ -3144,7 +3180,7 @@ SPHX_EXPORT int sphx_slab_graph_prepare(sphx_ctx **ctxs, int n)
     }
     if (c0->steps_graph) { (void)hipGraphExecDestroy(c0->steps_graph); c0->steps_graph = nullptr; }
     const int64_t enq0 = c0->slab_steps_enqueued;
-    const int cur0 = c0->cur;
+    const int cur0 = c0->sched.cur;
     hipStream_t s0 = c0->stream;
     hipGraph_t g = nullptr;
     // An in-process ring is captured as ONE chain on slab 0's stream (the slabs take turns phase by phase): a graph whose
@@ -3169,7 +3205,7 @@ SPHX_EXPORT int sphx_slab_graph_prepare(sphx_ctx **ctxs, int n)
     } catch (...) {
         abandon_capture(s0);
         restore_streams();
-        for (int r = 0; r < n; ++r) { ctxs[r]->cur = cur0; ctxs[r]->slab_steps_enqueued = enq0; }
+        for (int r = 0; r < n; ++r) { ctxs[r]->sched.cur = cur0; ctxs[r]->slab_steps_enqueued = enq0; }
         throw;
     }
     restore_streams();
@@ -3228,7 +3264,7 @@ SPHX_EXPORT int sphx_slab_snapshot(sphx_ctx *c, int capacity, int *n, double *x,
     *n = m;
     require(capacity >= m, "SPHX:Slab:capacity", "snapshot arrays are too short");
     const bool skinned = c->rebuild_every > 1;
-    const FluidSet fs = c->view(c->cur, skinned ? 0 : c->cur);
+    const FluidSet fs = c->view(c->sched.cur, skinned ? 0 : c->sched.cur);
     hipStream_t s = c->stream;
     auto dl = [&](const void *src, void *dst, size_t bytes) {
         if (dst && m) SPHX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
@@ -3281,27 +3317,27 @@ SPHX_EXPORT int sphx_ctx_time_kernel(sphx_ctx *c, const char *name, int reps, do
     hipEvent_t a = nullptr, b = nullptr;
     try {
         // arm run[cur] so the kernels execute; no step slot follows, so the clock does not advance
-        arm_clock(c, c->prm.t_end, (long long)1, c->cur, (const double *)nullptr);
-        const FluidSet fs = c->view(c->cur, c->lay);
-        const int dmode = c->dyn ? 3 : (c->skin > 0.0 ? (c->pos == 0 ? 1 : 2) : 0);
-        const FluidTmp &tt = c->tmp_par[c->fuse_ea ? c->cur : 0];  // (fuse_ea: the records / list of the current state parity)
+        arm_clock(c, c->prm.t_end, (long long)1, c->sched.cur, (const double *)nullptr);
+        const FluidSet fs = c->view(c->sched.cur, c->sched.lay);
+        const int dmode = c->dyn ? 3 : (c->skin > 0.0 ? (c->sched.pos == 0 ? 1 : 2) : 0);
+        const FluidTmp &tt = c->tmp_par[c->fuse_ea ? c->sched.cur : 0];  // (fuse_ea: the records / list of the current state parity)
         // make every temporary the timed kernel reads valid.  Where pass A of the coming step came with the last step's final
         // launch its list and records are there already, and stay: a timing call should not change what follows (the
         // stand-alone pass is a different kernel and may round differently in the last bit).
-        if (c->fuse_ea && c->pos != 0) {
-            for (int pass = 2; pass <= 4; ++pass) launch_physics_any(c, c->cur, fs, tt, 0, pass, dmode);
+        if (c->fuse_ea && c->sched.pos != 0) {
+            for (int pass = 2; pass <= 4; ++pass) launch_physics_any(c, c->sched.cur, fs, tt, 0, pass, dmode);
         } else {
-            launch_physics_any(c, c->cur, fs, tt, 0, 0, dmode);
+            launch_physics_any(c, c->sched.cur, fs, tt, 0, 0, dmode);
         }
         SPHX_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         for (int k = 0; k < reps; ++k) {
             if (only == 5) {  // (writes the other parity's list / records and the other state's drho: all rewritten by the next step)
                 FluidTmp te = tt;
-                const FluidSet o = c->view(1 - c->cur, c->lay);
+                const FluidSet o = c->view(1 - c->sched.cur, c->sched.lay);
                 te.posn = o.pos; te.veln = o.vel; te.drhon = o.drho;
-                launch_fused_ea(c, c->cur, fs, te, o, c->tmp_par[1 - c->cur], 0);
+                launch_fused_ea(c, c->sched.cur, fs, te, o, c->tmp_par[1 - c->sched.cur], 0);
             } else {
-                launch_physics_any(c, c->cur, fs, tt, 0, only, dmode);
+                launch_physics_any(c, c->sched.cur, fs, tt, 0, only, dmode);
             }
         }
         SPHX_HIP(hipStreamEndCapture(c->stream, &g));
