@@ -354,6 +354,35 @@ int sphx_ctx_flow_stats_read(sphx_ctx *ctx, int band, int capacity, int *n_bins,
                              double *t_first, double *t_last);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2c. Flow statistics of a batch (section 2b): the statistics of section 2a for every member at once.
+ *
+ *  One config for all members (bins and bands come from the shared geometry); every member has its own sums, sample
+ *  count, t_first / t_last and range flag.  Each member is sampled on its own clock with the gating of section 2a, so a
+ *  member that sits out slots (it reached t_target, used up its steps, stopped on the drift bound) is not sampled in
+ *  them.  A member's sums are bit for bit those of a standalone context with the same parameters and config that took
+ *  the same steps; realignments move particles only and change no sum.  With the statistics on, every step slot of the
+ *  batch ends with one sampling launch for all members; off, a slot enqueues exactly the launches it does without this
+ *  feature.  Enable / disable wait for the stream and re-capture the batch's graphs.  The sums take
+ *  2 * n_members * (n_bands + 1) * n_bins * 5 doubles of device memory; when they do not fit, enable fails and the
+ *  batch goes on without statistics.
+ *  Errors: SPHX:Batch:null (NULL batch), SPHX:Stats:config, SPHX:Stats:band, SPHX:Stats:capacity, SPHX:Stats:disabled as in
+ *  section 2a; SPHX:Stats:range names the member whose flag is set.
+ * ---------------------------------------------------------------------------------------------- */
+
+int sphx_batch_flow_stats_enable(sphx_batch *batch, const sphx_flow_stats_config *cfg);
+int sphx_batch_flow_stats_disable(sphx_batch *batch);
+/* settles what is enqueued, then zeroes */
+int sphx_batch_flow_stats_reset(sphx_batch *batch);
+/* settles; samples what sphx_batch_download returns, every member, without gating */
+int sphx_batch_flow_stats_sample(sphx_batch *batch);
+/* One call for all members.  Per-bin arrays are n_members blocks of `capacity` doubles (member m at m * capacity);
+ * n_samples / t_first / t_last are [n_members].  All NULL: capacity is not checked.  Settles first, as
+ * sphx_batch_download does. */
+int sphx_batch_flow_stats_read(sphx_batch *batch, int band, int capacity, int *n_bins, double *count, double *sum_ux,
+                               double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples,
+                               double *t_first, double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU).  The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

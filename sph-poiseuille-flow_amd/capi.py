@@ -65,6 +65,8 @@ EXPORTS = [
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
     "sphx_batch_create", "sphx_batch_destroy", "sphx_batch_advance", "sphx_batch_enqueue_steps", "sphx_batch_sync",
     "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
+    "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",
+    "sphx_batch_flow_stats_sample", "sphx_batch_flow_stats_read",
 ]
 
 _LIB = None
@@ -175,6 +177,7 @@ class Batch:
         mass, wall_vel = f64(mass), f64(wall_vel)
         if mass.shape != (nt,) or wall_vel.shape != (nt, 2):
             raise SphxError(SPHX_ERR_ARG, "SPHX:Batch:geometry", "mass / wall_vel: shared arrays of n_total rows expected")
+        self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
         arr = (SphxParams * m)(*self.params)
         check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
@@ -232,6 +235,57 @@ class Batch:
         a, b, g = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(lib().sphx_batch_graph_stats(self._h, C.byref(a), C.byref(b), C.byref(g)))
         return dict(slots_replayed=a.value, slots_eager=b.value, graphs_captured=g.value)
+
+    # ---- flow statistics of every member (include/sphx.h section 2c): Context.flow_stats_* for all members at once ----
+    def flow_stats_enable(self, n_bins=0, every=1, t_from=0.0, bands=()):
+        """Context.flow_stats_enable with one config for all members; each member is sampled on its own clock."""
+        cfg = flow_stats_config(n_bins, every, t_from, bands)
+        p0 = self.params[0]
+        n = int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5)))
+        check(lib().sphx_batch_flow_stats_enable(self._h, C.byref(cfg)))
+        self._flow_stats = (n, int(cfg.n_bands) + 1)
+
+    def flow_stats_disable(self):
+        check(lib().sphx_batch_flow_stats_disable(self._h))
+        self._flow_stats = None
+
+    def flow_stats_reset(self):
+        self._flow_stats_on()
+        check(lib().sphx_batch_flow_stats_reset(self._h))
+
+    def flow_stats_sample(self):
+        """Add one sample of every member's current state (what download() returns) now, whatever the gating."""
+        self._flow_stats_on()
+        check(lib().sphx_batch_flow_stats_sample(self._h))
+
+    def flow_stats_sums(self, band=0) -> list:
+        """One dict per member in the format of Context.flow_stats_sums, from one read of all members."""
+        n_bins, n_bands = self._flow_stats_on()
+        if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:Stats:band", f"band must be an integer in 0..{n_bands - 1}")
+        m = self.n_members
+        arrs = [np.zeros(m * n_bins) for _ in range(5)]
+        ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
+        nb = C.c_int(0)
+        check(lib().sphx_batch_flow_stats_read(self._h, C.c_int(int(band)), C.c_int(n_bins), C.byref(nb),
+                                               *[ptr(a) for a in arrs], ns.ctypes.data_as(C.POINTER(C.c_int64)), ptr(t0),
+                                               ptr(t1)))
+        assert nb.value == n_bins, (nb.value, n_bins)
+        out = []
+        for k in range(m):
+            d = {f: a[k * n_bins:(k + 1) * n_bins].copy() for f, a in zip(("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2"), arrs)}
+            d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
+            out.append(d)
+        return out
+
+    def flow_stats(self, band=0) -> list:
+        """One profile.flow_stats_profile dict per member."""
+        return [flow_stats_profile(self.params[0].DH, **s) for s in self.flow_stats_sums(band)]
+
+    def _flow_stats_on(self):
+        if self._flow_stats is None:
+            raise SphxError(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this batch")
+        return self._flow_stats
 
 
 class Context:

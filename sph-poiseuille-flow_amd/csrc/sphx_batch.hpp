@@ -26,6 +26,9 @@ struct sphx_batch {
     int64_t epoch_slot = 0;           // sched.slot when the members' epochs were set
     int64_t n_realign = 0;
     std::vector<int64_t> pending;     // per member: step count the sphx_batch_enqueue_steps calls since the last sync aim for
+    sphx_ctx::FlowStats fstats;       // flow statistics (sphx_batch_flow_stats_*): one config for all members, sums and heads
+                                      // in M blocks (member m's at m * n_bands * n_bins * kStatsFields, head m); the
+                                      // members' own fstats stay off
 
     ~sphx_batch()
     {
@@ -103,12 +106,25 @@ void batch_step_t(sphx_batch *b, int q, int l, int pos, bool rebuild)
            (const int *)c->perm.get(), reorder_args(c->tmp.posn, c->tmp.veln, c->tmp.drhon, s.mass, s.id, d, c->tmp.src_of));
 }
 
-// the batch's step slot, for the shared schedule code (capture_slots, enqueue_slots)
+// k_flow_stats_b on every member's (pos, vel), given as member 0's: every >= 1 = the in-loop sample closing step slot q,
+// 0 = a sample of the state now
+void batch_launch_stats(sphx_batch *b, int q, const double2 *pos, const double2 *vel, int every)
+{
+    sphx_ctx *c = b->mem[0];
+    const sphx_ctx::FlowStats &f = b->fstats;
+    launch_s(c, "k_flow_stats", k_flow_stats_b, dim3(flow_stats_blocks(c), b->M), dim3(kStatsBlock), flow_stats_shmem(f), b->mb,
+             q, flow_stats_args(c, f, pos, vel, every));
+}
+
+// the batch's step slot, for the shared schedule code (capture_slots, enqueue_slots); with the statistics on it ends with
+// the sample of S[1-q], the state the slot leaves (as launch_slot_stats)
 auto batch_slot(sphx_batch *b)
 {
     return [b](int q, int l, int pos, bool rebuild) {
         if (b->mem[0]->lpp == 16) batch_step_t<16>(b, q, l, pos, rebuild);
         else batch_step_t<32>(b, q, l, pos, rebuild);
+        if (b->fstats.on)
+            batch_launch_stats(b, q, b->mem[0]->fpos_[1 - q].get(), b->mem[0]->fvel_[1 - q].get(), b->fstats.cfg.every);
     };
 }
 
@@ -286,6 +302,34 @@ void batch_check_member(const sphx_batch *b, int m)
     require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
     if (m < 0 || m >= b->M)
         throw Error(SPHX_ERR_ARG, "SPHX:Batch:member", "member " + std::to_string(m) + " out of range [0, " + std::to_string(b->M) + ")");
+}
+
+sphx_batch *batch_stats(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    if (need_on && !b->fstats.on)
+        throw Error(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this batch");
+    return b;
+}
+
+// the replayed graphs carry k_flow_stats_b (and its arguments) or not: a change of the setting re-captures them
+void batch_stats_off(sphx_batch *b)
+{
+    SPHX_HIP(hipStreamSynchronize(b->stream));
+    b->sched.drop_graphs();
+    sphx_ctx::FlowStats &f = b->fstats;
+    f.on = false;
+    f.isum.release();
+    f.dsum.release();
+    f.head.release();
+}
+
+void batch_stats_zero(sphx_batch *b)
+{
+    sphx_ctx::FlowStats &f = b->fstats;
+    f.isum.zero(b->stream);
+    f.dsum.zero(b->stream);
+    f.head.zero(b->stream);
 }
 
 // argument checks (no device): shared fields, refused modes, the kernel forms members of this size would run
@@ -505,6 +549,111 @@ SPHX_EXPORT int sphx_batch_graph_stats(sphx_batch *b, int64_t *slots_replayed, i
     if (slots_replayed) *slots_replayed = b->sched.slots_replayed;
     if (slots_eager) *slots_eager = b->sched.slots_eager;
     if (graphs_captured) *graphs_captured = b->sched.graphs_captured;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- flow statistics of every member (include/sphx.h section 2c) ----
+
+SPHX_EXPORT int sphx_batch_flow_stats_enable(sphx_batch *b, const sphx_flow_stats_config *cfg)
+{
+    SPHX_TRY
+    batch_stats(b, false);
+    sphx_ctx::FlowStats checked;
+    stats_configure(checked, b->mem[0]->prm, cfg);  // (bins and bands come from the shared geometry)
+    batch_stats_off(b);
+    sphx_ctx::FlowStats &f = b->fstats;
+    f.cfg = checked.cfg;
+    f.n_bins = checked.n_bins;
+    f.n_bands = checked.n_bands;
+    const size_t nc = (size_t)f.n_bands * f.n_bins * kStatsFields * b->M;
+    try {
+        f.isum.alloc(nc);
+        f.dsum.alloc(nc);
+        f.head.alloc(b->M);
+    } catch (...) {  // out of device memory: the batch goes on without statistics
+        f.isum.release();
+        f.dsum.release();
+        f.head.release();
+        (void)hipGetLastError();
+        throw;
+    }
+    batch_stats_zero(b);
+    SPHX_HIP(hipStreamSynchronize(b->stream));
+    f.on = true;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_flow_stats_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_stats(b, false);
+    if (b->fstats.on) batch_stats_off(b);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_flow_stats_reset(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_stats(b, true);
+    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
+    batch_stats_zero(b);
+    SPHX_HIP(hipStreamSynchronize(b->stream));
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_flow_stats_sample(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_stats(b, true);
+    batch_settle(b);  // every member at the batch's phase: the state sphx_batch_download would return
+    const FluidSet fs = b->mem[0]->view(b->sched.cur, b->sched.lay);
+    batch_launch_stats(b, 0, fs.pos, fs.vel, 0);
+    SPHX_HIP(hipGetLastError());
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_flow_stats_read(sphx_batch *b, int band, int capacity, int *n_bins, double *count, double *sum_ux,
+                                           double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples,
+                                           double *t_first, double *t_last)
+{
+    SPHX_TRY
+    batch_stats(b, true);
+    const sphx_ctx::FlowStats &f = b->fstats;
+    require(band >= 0 && band < f.n_bands, "SPHX:Stats:band", "band must be 0 (whole channel) .. n_bands");
+    double *out[kStatsFields] = {count, sum_ux, sum_ux2, sum_uy, sum_uy2};
+    bool any = false;
+    for (double *o : out) any = any || o != nullptr;
+    require(!any || capacity >= f.n_bins, "SPHX:Stats:capacity", "capacity is smaller than the number of bins");
+    batch_settle(b);
+    const int M = b->M;
+    const size_t row = (size_t)f.n_bins * kStatsFields, block = (size_t)f.n_bands * row;
+    std::vector<double> sums(any ? (size_t)M * row : 0);
+    std::vector<FlowStatsHead> h(M);
+    if (any)  // band `band` of every member's block, one copy
+        SPHX_HIP(hipMemcpy2DAsync(sums.data(), row * sizeof(double), f.dsum.get() + (size_t)band * row, block * sizeof(double),
+                                  row * sizeof(double), M, hipMemcpyDeviceToHost, b->stream));
+    SPHX_HIP(hipMemcpyAsync(h.data(), f.head.get(), sizeof(FlowStatsHead) * M, hipMemcpyDeviceToHost, b->stream));
+    SPHX_HIP(hipStreamSynchronize(b->stream));
+    for (int m = 0; m < M; ++m)
+        if (h[m].range)
+            throw Error(SPHX_ERR_STATE, "SPHX:Stats:range", "member " + std::to_string(m) +
+                                                           ": a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
+    if (n_bins) *n_bins = f.n_bins;
+    for (int j = 0; j < kStatsFields; ++j)
+        if (out[j])
+            for (int m = 0; m < M; ++m)
+                for (int k = 0; k < f.n_bins; ++k) out[j][(size_t)m * capacity + k] = sums[(size_t)m * row + (size_t)k * kStatsFields + j];
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int m = 0; m < M; ++m) {
+        if (n_samples) n_samples[m] = h[m].n_samples;
+        if (t_first) t_first[m] = h[m].n_samples ? h[m].t_first : nan;
+        if (t_last) t_last[m] = h[m].n_samples ? h[m].t_last : nan;
+    }
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -1,6 +1,7 @@
-// sphx_flow_stats.hpp -- time-averaged velocity profiles of a resident context (include/sphx.h section 2, "flow
-// statistics"): one self-skipping launch at the end of every step slot bins the state the step left into the
-// reference's profile bins (SPH_Poiseuille.m:579-605) and adds it to running sums, without a host round trip.
+// sphx_flow_stats.hpp -- time-averaged velocity profiles of a resident context (include/sphx.h section 2a, "flow
+// statistics") and of every member of a batch (section 2c, k_flow_stats_b): one self-skipping launch at the end of every
+// step slot bins the state the step left into the reference's profile bins (SPH_Poiseuille.m:579-605) and adds it to
+// running sums, without a host round trip.
 //
 // Determinism: a sample is summed EXACTLY, in int64 fixed point -- integer adds do not depend on the order they arrive
 // in, so neither the particle order (layouts, re-binnings) nor the dispatch order of the workgroups can change a bit.
@@ -85,10 +86,33 @@ __device__ __forceinline__ void stats_add(unsigned long long *h, long long ux, l
     atomicAdd(h + 4, (unsigned long long)uy2);
 }
 
+// where the arrays of the sampled channel are: the context's own ...
+struct StatsOwn {
+    __device__ const double2 *pos(const FlowStatsArgs &a) const { return a.pos; }
+    __device__ const double2 *vel(const FlowStatsArgs &a) const { return a.vel; }
+    __device__ unsigned long long *isum(const FlowStatsArgs &a) const { return a.isum; }
+    __device__ double *dsum(const FlowStatsArgs &a) const { return a.dsum; }
+    __device__ FlowStatsHead *head(const FlowStatsArgs &a) const { return a.head; }
+};
+
+// ... or member m's blocks of a batch's: state at m * part, sums at m * n_bands * n_bins * kStatsFields, head m
+struct StatsMember {
+    long long part;
+    int m;
+    __device__ long long sums(const FlowStatsArgs &a) const { return (long long)m * a.n_bands * a.n_bins * kStatsFields; }
+    __device__ const double2 *pos(const FlowStatsArgs &a) const { return a.pos + part * m; }
+    __device__ const double2 *vel(const FlowStatsArgs &a) const { return a.vel + part * m; }
+    __device__ unsigned long long *isum(const FlowStatsArgs &a) const { return a.isum + sums(a); }
+    __device__ double *dsum(const FlowStatsArgs &a) const { return a.dsum + sums(a); }
+    __device__ FlowStatsHead *head(const FlowStatsArgs &a) const { return a.head + m; }
+};
+
 // q: parity of the step slot this launch closes (in-loop samples: the slot ran iff run[q] is still set -- a clock update
 // only ever writes the flag of the NEXT slot).  The launch sits behind the slot's clock update, so clk->step / clk->t are
-// those of the step just completed.
-__global__ __launch_bounds__(kStatsBlock) void k_flow_stats(const Clock *clk, int q, FlowStatsArgs a)
+// those of the step just completed.  The sample of one channel, on clock clk, shared by the gridDim.x workgroups of a grid
+// row; `at` says where the channel's arrays are: a's own pointers (StatsOwn) or a batch member's blocks (StatsMember).
+template <typename At>
+__device__ __forceinline__ void flow_stats_body(const Clock *clk, int q, const FlowStatsArgs &a, const At &at)
 {
     if (a.every > 0) {
         if (!clk->run[q]) return;
@@ -111,7 +135,7 @@ __global__ __launch_bounds__(kStatsBlock) void k_flow_stats(const Clock *clk, in
     const int i1 = min(n, i0 + chunk);
     bool out_of_range = false;
     for (int i = i0 + (int)threadIdx.x; i < i1; i += kStatsBlock) {
-        const double2 p = a.pos[i], v = a.vel[i];
+        const double2 p = at.pos(a)[i], v = at.vel(a)[i];
         if (!(p.y >= 0.0 && p.y <= a.DH)) continue;  // outside [0, DH]: dropped, as discretize does
         if (!(fabs(v.x) <= bound && fabs(v.y) <= bound)) { out_of_range = true; continue; }
         const int k = stats_bin(p.y, a.bin_w, a.n_bins);
@@ -122,16 +146,16 @@ __global__ __launch_bounds__(kStatsBlock) void k_flow_stats(const Clock *clk, in
             if (stats_in_band(p.x, a.DL, a.band_x[b - 1], a.band_hw[b - 1]))
                 stats_add(s_cnt + ((size_t)b * a.n_bins + k) * kStatsFields, ux, ux2, uy, uy2);
     }
-    if (out_of_range) atomicOr(&a.head->range, 1);
+    if (out_of_range) atomicOr(&at.head(a)->range, 1);
     __syncthreads();
     // one thread per counter: the running sums grow in sample order, each by its own bin -- no summation tree
     auto finish = [&](int k, unsigned long long v) {
         const int f = k % kStatsFields;
         const int s = f == 0 ? 0 : ((f & 1) ? s1 : s2);
-        a.dsum[k] += ldexp((double)(long long)v, -s);
+        at.dsum(a)[k] += ldexp((double)(long long)v, -s);
     };
     auto finish_head = [&]() {
-        FlowStatsHead *h = a.head;
+        FlowStatsHead *h = at.head(a);
         if (h->n_samples == 0) h->t_first = t_now;
         h->t_last = t_now;
         h->n_samples += 1;
@@ -144,7 +168,7 @@ __global__ __launch_bounds__(kStatsBlock) void k_flow_stats(const Clock *clk, in
     }
     for (int k = threadIdx.x; k < nc; k += kStatsBlock) {
         const unsigned long long v = s_cnt[k];
-        if (v) atomicAdd(a.isum + k, v);
+        if (v) atomicAdd(at.isum(a) + k, v);
     }
     // last workgroup out: every wave drains its adds, one release at agent scope, then the ticket
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -152,7 +176,7 @@ __global__ __launch_bounds__(kStatsBlock) void k_flow_stats(const Clock *clk, in
     if (threadIdx.x == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int drawn = __hip_atomic_fetch_add(&a.head->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int drawn = __hip_atomic_fetch_add(&at.head(a)->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_last = drawn == (int)gridDim.x - 1 ? 1 : 0;
         if (s_last) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -162,13 +186,27 @@ __global__ __launch_bounds__(kStatsBlock) void k_flow_stats(const Clock *clk, in
     __syncthreads();
     if (!s_last) return;
     for (int k = threadIdx.x; k < nc; k += kStatsBlock) {
-        const unsigned long long v = atomicExch(a.isum + k, 0ull);
+        const unsigned long long v = atomicExch(at.isum(a) + k, 0ull);
         if (v) finish(k, v);
     }
     if (threadIdx.x == 0) {
         finish_head();
-        __hip_atomic_store(&a.head->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&at.head(a)->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+__global__ __launch_bounds__(kStatsBlock) void k_flow_stats(const Clock *clk, int q, FlowStatsArgs a)
+{
+    flow_stats_body(clk, q, a, StatsOwn{});
+}
+
+// batch (sphx_batch_flow_stats_*): member m = blockIdx.y samples its own state (pos / vel at m * Members::part) on its own
+// clock into its own block of sums (m * n_bands * n_bins * kStatsFields) and its own head; gridDim.x workgroups per member.
+// The sums are exact, so the workgroup count gives the same bits as a context's.
+__global__ __launch_bounds__(kStatsBlock) void k_flow_stats_b(Members mb, int q, FlowStatsArgs a)
+{
+    const int m = (int)blockIdx.y;
+    flow_stats_body(mb.clk + m, q, a, StatsMember{mb.part, m});
 }
 
 }  // namespace sphx

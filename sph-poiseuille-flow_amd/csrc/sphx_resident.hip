@@ -699,10 +699,9 @@ void launch_step_dyn(sphx_ctx *c, int q)
     launch(c, "k_copyback", k_copyback, g1, bp, (const Clock *)clk, qf, cb);
 }
 
-// k_flow_stats on (pos, vel): every >= 1 = the in-loop sample closing step slot q, 0 = a sample of the state now
-void launch_flow_stats(sphx_ctx *c, int q, const double2 *pos, const double2 *vel, int every)
+// the arguments of k_flow_stats (k_flow_stats_b: member 0's pointers) for statistics f of channels like c
+FlowStatsArgs flow_stats_args(const sphx_ctx *c, const sphx_ctx::FlowStats &f, const double2 *pos, const double2 *vel, int every)
 {
-    const sphx_ctx::FlowStats &f = c->fstats;
     FlowStatsArgs a{};
     a.pos = pos; a.vel = vel;
     a.isum = f.isum.get(); a.dsum = f.dsum.get(); a.head = f.head.get();
@@ -711,9 +710,22 @@ void launch_flow_stats(sphx_ctx *c, int q, const double2 *pos, const double2 *ve
     for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
     a.n_bins = f.n_bins; a.n_bands = f.n_bands;
     a.every = every;
-    const unsigned nb = std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kStatsBlock * kStatsPerThread), 1u, (unsigned)kStatsMaxBlocks);
-    const size_t shmem = (size_t)f.n_bands * f.n_bins * kStatsFields * sizeof(unsigned long long);
-    launch_s(c, "k_flow_stats", k_flow_stats, dim3(nb), dim3(kStatsBlock), shmem, (const Clock *)c->clock.get(), q, a);
+    return a;
+}
+
+// workgroups of one channel's sample, and their LDS counters
+unsigned flow_stats_blocks(const sphx_ctx *c)
+{
+    return std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kStatsBlock * kStatsPerThread), 1u, (unsigned)kStatsMaxBlocks);
+}
+size_t flow_stats_shmem(const sphx_ctx::FlowStats &f) { return (size_t)f.n_bands * f.n_bins * kStatsFields * sizeof(unsigned long long); }
+
+// k_flow_stats on (pos, vel): every >= 1 = the in-loop sample closing step slot q, 0 = a sample of the state now
+void launch_flow_stats(sphx_ctx *c, int q, const double2 *pos, const double2 *vel, int every)
+{
+    const sphx_ctx::FlowStats &f = c->fstats;
+    launch_s(c, "k_flow_stats", k_flow_stats, dim3(flow_stats_blocks(c)), dim3(kStatsBlock), flow_stats_shmem(f),
+             (const Clock *)c->clock.get(), q, flow_stats_args(c, f, pos, vel, every));
 }
 
 // the state step slot q leaves is in S[1-q] on every schedule (a re-binning step reorders into S[1-q] too, a dynamic
@@ -1881,12 +1893,9 @@ void stats_zero(sphx_ctx *c)
     f.head.zero(c->stream);
 }
 
-}  // namespace
-
-SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_config *cfg)
+// the checked configuration cfg of channels with parameters prm into f (cfg, n_bins, n_bands); SPHX:Stats:config errors
+void stats_configure(sphx_ctx::FlowStats &f, const sphx_params &prm, const sphx_flow_stats_config *cfg)
 {
-    SPHX_TRY
-    stats_ctx(c, false);
     require(cfg != nullptr, "SPHX:Stats:config", "config must not be NULL");
     require(cfg->n_bins >= 0, "SPHX:Stats:config", "n_bins must be >= 0 (0 = the reference's profile bins)");
     require(cfg->every >= 1, "SPHX:Stats:config", "every must be >= 1");
@@ -1895,16 +1904,29 @@ SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_co
     for (int b = 0; b < cfg->n_bands; ++b)
         require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, "SPHX:Stats:config",
                 "band centres must be finite and half-widths finite and >= 0");
-    const int n_bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(c->prm.DH / c->prm.dp + 0.5));
+    const int n_bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
     require((int64_t)n_bins * (cfg->n_bands + 1) <= kStatsMaxBins, "SPHX:Stats:config",
             "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
-    stats_drop_graphs(c);
-    sphx_ctx::FlowStats &f = c->fstats;
     f.cfg = *cfg;
     for (int b = cfg->n_bands; b < 2; ++b) { f.cfg.band_x[b] = 0.0; f.cfg.band_hw[b] = 0.0; }
     f.n_bins = n_bins;
     f.n_bands = cfg->n_bands + 1;
-    const size_t nc = (size_t)f.n_bands * n_bins * kStatsFields;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_config *cfg)
+{
+    SPHX_TRY
+    stats_ctx(c, false);
+    sphx_ctx::FlowStats checked;
+    stats_configure(checked, c->prm, cfg);
+    stats_drop_graphs(c);
+    sphx_ctx::FlowStats &f = c->fstats;
+    f.cfg = checked.cfg;
+    f.n_bins = checked.n_bins;
+    f.n_bands = checked.n_bands;
+    const size_t nc = (size_t)f.n_bands * f.n_bins * kStatsFields;
     f.isum.alloc(nc);
     f.dsum.alloc(nc);
     f.head.alloc(1);

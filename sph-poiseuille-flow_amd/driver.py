@@ -19,7 +19,7 @@ from . import capi
 from .geometry import init_particles
 from .mex_surface import sph_neighbor_search_mex, sph_physics_shell_mex
 from . import restart
-from .profile import compute_mid_channel_profile, final_profile, l2_error, n_profile_bins
+from .profile import compute_mid_channel_profile, final_profile, flow_stats_profile, l2_error, n_profile_bins, pool_flow_stats
 
 
 @dataclass
@@ -235,8 +235,8 @@ def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, st
     """run() for M channels of one geometry stepped together as one batch (capi.Batch, include/sphx.h section 2b): a
     parameter sweep (mu, c_f, p0, gravity_g, transport_coeff) or an ensemble of realisations (parts_list).  Every member
     reaches the same output points (output_interval and t_end are shared and must agree) and gets a RunResult of its own:
-    final profile and L2, the output-point profiles, tau.  The resident engine only; restart / post-process files and
-    average_from are single-channel features."""
+    final profile and L2, the output-point profiles, tau.  The resident engine only; restart / post-process files are
+    single-channel features, and time averaging of a batch is run_ensemble's."""
     prms = list(prms)
     if engine != "resident":
         raise ValueError("run_batch runs the resident engine only (a batch is device-resident)")
@@ -301,3 +301,85 @@ def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, st
                                                   realignments=info["realignments"]),
                                  full_profile_u=fulls[m]))
     return out
+
+
+@dataclass
+class EnsembleResult:
+    members: list        # one RunResult per member: final profile and L2, tau, time_avg (time_average of its own sums)
+    pooled: dict         # members sharing mu, c_f, p0, gravity_g, transport_coeff: time_average of the pooled sums plus
+                         # u_mean_se, L2_members, L2_mean, L2_std; None for a parameter sweep
+    wall_seconds: float
+    grid_policy: dict = field(default_factory=dict)
+
+
+_PHYSICS = ("mu", "c_f", "p0", "gravity_g", "transport_coeff")
+
+
+def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_per_particle=0, steps_per_graph=0,
+                 rebuild_every=0, log=None):
+    """Time-averaged profiles of M channels of one geometry stepped as one batch (capi.Batch), averaged on the device
+    inside the step loop (include/sphx.h section 2c) as run(average_from=...) does for one channel: every
+    average_every-th step ending at t >= average_from, whole channel and the mid-channel band (DL/2, max(dp, h)).  The
+    members advance output point by output point as in run_batch, so their trajectories are run_batch's; nothing is
+    downloaded before the end.  parts_list: the members' initial states (e.g. geometry.perturbed_particles), default the
+    lattice.  Returns an EnsembleResult."""
+    prms = list(prms)
+    if not prms:
+        raise ValueError("run_ensemble needs at least one parameter set")
+    if average_from is None or np.isnan(float(average_from)):
+        raise ValueError("run_ensemble needs average_from (the start of the averaging window)")
+    p0 = prms[0]
+    for k, p in enumerate(prms):
+        if p.output_interval != p0.output_interval or p.t_end != p0.t_end:
+            raise ValueError(f"member {k}: output_interval / t_end differ from member 0 (members share the output points)")
+    parts_list = [init_particles(p) for p in prms] if parts_list is None else list(parts_list)
+    if len(parts_list) != len(prms):
+        raise ValueError("parts_list needs one particle set per parameter set")
+    nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
+    M = len(prms)
+    n_bins = n_profile_bins(p0.DH, p0.dp)
+    mid_x, mid_hw = 0.5 * p0.DL, max(p0.dp, p0.h)
+    times = [0.0]
+    t0 = time.perf_counter()
+    with capi.Batch(prms, nf, nt, [pa["pos"] for pa in parts_list], [pa["vel"] for pa in parts_list],
+                    [pa["drho_dt"] for pa in parts_list], parts_list[0]["mass"], parts_list[0]["wall_vel"],
+                    lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
+                    rebuild_every=rebuild_every) as b:
+        b.flow_stats_enable(n_bins=n_bins, every=average_every, t_from=float(average_from), bands=[(mid_x, mid_hw)])
+        t = 0.0
+        st = None
+        while t < p0.t_end - 1e-12:
+            target = min(t + p0.output_interval, p0.t_end)
+            st = b.advance(target)
+            t = min(s["t"] for s in st)
+            times.append(t)
+            if log:
+                log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
+        wall = time.perf_counter() - t0
+        info = b.info()
+        whole, mid = b.flow_stats_sums(0), b.flow_stats_sums(1)
+        policy = dict(rebuild_every=info["rebuild_every"], skin=info["skin"], forced_rebuilds=info["forced_rebuilds"],
+                      realignments=info["realignments"])
+        members = []
+        for m, prm in enumerate(prms):
+            tau_b, tau_t, _ = b.monitor(m, tau=True)
+            d = b.download(m, fields=("pos", "vel"))
+            pos, vel = d["pos"], d["vel"]
+            fluid_pos = pos[:nf].copy()
+            fluid_pos[:, 0] = np.mod(fluid_pos[:, 0], prm.DL)
+            y_mid, u_mean, u_exact = final_profile(fluid_pos, vel[:nf, 0], prm)
+            s = st[m] if st else dict(t=0.0, step=0)
+            ta = time_average(prm, flow_stats_profile(prm.DH, **whole[m]), flow_stats_profile(prm.DH, **mid[m]))
+            members.append(RunResult(prm=prm, n_fluid=nf, n_total=nt, t=s["t"], steps=int(s["step"]), wall_seconds=wall,
+                                     pos=pos, vel=vel, y_mid=y_mid, u_mean=u_mean, u_exact=u_exact,
+                                     L2_error=l2_error(u_mean, u_exact), profile_times=list(times), tau_bottom=tau_b,
+                                     tau_top=tau_t, tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2,
+                                     grid_policy=dict(policy), time_avg=ta))
+    pooled = None
+    if all(getattr(p, k) == getattr(p0, k) for p in prms for k in _PHYSICS):
+        pw, pm = pool_flow_stats(p0.DH, whole), pool_flow_stats(p0.DH, mid)
+        pooled = time_average(p0, pw, pm)
+        L2s = [r.time_avg["L2"] for r in members]
+        pooled.update(u_mean_se=pw["u_mean_se"], L2_members=L2s, L2_mean=float(np.mean(L2s)),
+                      L2_std=float(np.std(L2s, ddof=1)) if M > 1 else float("nan"))
+    return EnsembleResult(members=members, pooled=pooled, wall_seconds=wall, grid_policy=policy)

@@ -84,3 +84,17 @@ def developed_state(prm, parts, jitter=0.05, seed=12345):
     y = pos[:nf, 1]
     vel[:nf, 0] = prm.gravity_g / (2.0 * prm.nu) * y * (prm.DH - y)
     return pos, vel
+
+
+def perturbed_particles(prm, jitter, seed):
+    """init_particles with every fluid position moved by a uniform +-jitter*dp in x and y and x wrapped into [0, DL), at
+    rest: one realisation of an ensemble (driver.run_ensemble).  Deterministic per seed."""
+    parts = init_particles(prm)
+    rng = np.random.default_rng(seed)
+    nf = parts["n_fluid"]
+    pos = parts["pos"].copy(order="F")
+    pos[:nf, :] += (rng.random((nf, 2)) * 2.0 - 1.0) * jitter * prm.dp
+    x = pos[:nf, 0] - np.floor(pos[:nf, 0] / prm.DL) * prm.DL
+    pos[:nf, 0] = np.where(x >= prm.DL, x - prm.DL, x)  # (a tiny negative x rounds to DL)
+    parts["pos"] = pos
+    return parts

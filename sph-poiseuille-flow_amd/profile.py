@@ -3,6 +3,7 @@
 compute_binned_profile_mean / compute_mid_channel_profile: SPH_Poiseuille.m:579-605.
 final_profile: SPH_Poiseuille.m:617-623.  l2_error: SPH_Poiseuille_postprocess.m:37-42.
 flow_stats_profile: the sums of the device's flow statistics (include/sphx.h section 2a) as a profile.
+pool_flow_stats: the sums of several channels (the members of a batch, section 2c) as one ensemble-averaged profile.
 """
 from __future__ import annotations
 
@@ -79,3 +80,37 @@ def flow_stats_profile(DH, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples=0,
     return dict(y_mid=y_mid, count=N, u_mean=u_mean, u_std=u_std, uy_mean=uy_mean, uy_std=uy_std,
                 n_samples=int(n_samples), t_first=float(t_first), t_last=float(t_last),
                 sum_ux=sx, sum_ux2=sxx, sum_uy=sy, sum_uy2=syy)
+
+
+_SUMS = ("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2")
+
+
+def pool_flow_stats(DH, sums_list):
+    """Ensemble- and time-averaged profile of several channels' flow-statistics sums (dicts as capi.Batch.flow_stats_sums
+    returns, one per member): the per-bin sums are added in member order and turned into flow_stats_profile of the total;
+    n_samples is the total over the members, t_first / t_last the earliest / latest sample.  Adds
+      u_mean_se   per bin, the standard error across members of the members' own time-averaged u_mean,
+                  std(ddof=1) / sqrt(M); NaN for M < 2 and in bins that are empty for some member
+      n_members   M"""
+    sums_list = list(sums_list)
+    if not sums_list:
+        raise ValueError("pool_flow_stats needs the sums of at least one member")
+    per = [[np.asarray(s[k], dtype=np.float64).ravel() for k in _SUMS] for s in sums_list]
+    total = [a.copy() for a in per[0]]
+    for member in per[1:]:
+        for k in range(len(_SUMS)):
+            total[k] = total[k] + member[k]
+    n_samples = sum(int(s.get("n_samples", 0)) for s in sums_list)
+    t_first = [float(s.get("t_first", np.nan)) for s in sums_list]
+    t_last = [float(s.get("t_last", np.nan)) for s in sums_list]
+    t_first = min((t for t in t_first if not np.isnan(t)), default=np.nan)
+    t_last = max((t for t in t_last if not np.isnan(t)), default=np.nan)
+    out = flow_stats_profile(DH, *total, n_samples=n_samples, t_first=t_first, t_last=t_last)
+    M = len(per)
+    se = np.full(len(total[0]), np.nan)
+    if M >= 2:
+        means = np.stack([flow_stats_profile(DH, *member)["u_mean"] for member in per])
+        ok = ~np.any(np.isnan(means), axis=0)
+        se[ok] = np.std(means[:, ok], axis=0, ddof=1) / np.sqrt(M)
+    out.update(u_mean_se=se, n_members=M)
+    return out
