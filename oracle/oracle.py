@@ -34,8 +34,38 @@ class OrcRunStats(C.Structure):
                 ("dt_last", C.c_double), ("n_pairs_last", C.c_double)]
 
 
+REF_OUT = os.path.join(_HERE, "_ref")
+REF_LIBS = {"neighbor": os.path.join(REF_OUT, "sph_neighbor_search_mex.so"),
+            "physics": os.path.join(REF_OUT, "sph_physics_mex.so")}
+
+
+def reference_dir() -> str:
+    """Checkout of the reference project: $SPHX_REFERENCE_DIR, else a directory `reference` (holding mex/sph_physics_mex.c)
+    next to this repository or next to one of the directories above it."""
+    env = os.environ.get("SPHX_REFERENCE_DIR")
+    if env:
+        return env
+    d = os.path.dirname(_HERE)
+    while True:
+        up = os.path.dirname(d)
+        cand = os.path.join(up, "reference")
+        if os.path.isfile(os.path.join(cand, "mex", "sph_physics_mex.c")) or up == d:
+            return cand
+        d = up
+
+
+def build_reference() -> bool:
+    """`make ref`: the reference's two MEX files against tests/stubs (see oracle/Makefile) -> oracle/_ref/.  Without a
+    reference checkout nothing is done and whatever oracle/_ref/ holds is kept.  -> True where both libraries exist."""
+    ref = reference_dir()
+    if os.path.isdir(os.path.join(ref, "mex")):
+        subprocess.check_call(["make", "-s", "-C", _HERE, "ref", "REF_DIR=" + ref])
+    return all(os.path.exists(p) for p in REF_LIBS.values())
+
+
 def build(force: bool = False) -> None:
-    """Compile both oracle flavours with gcc (see oracle/Makefile)."""
+    """Compile both oracle flavours with gcc, and the reference's MEX files where a checkout exists (see oracle/Makefile)."""
+    build_reference()
     targets = [os.path.join(_HERE, n) for n in ("libsph_oracle.so", "libsph_oracle_omp.so")]
     src = os.path.join(_HERE, "sph_oracle.c")
     if not force and all(os.path.exists(t) and os.path.getmtime(t) >= os.path.getmtime(src) for t in targets):

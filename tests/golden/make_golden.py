@@ -1,12 +1,18 @@
-"""Generate tests/golden/oracle_small.npz: seeded inputs and the CPU oracle's outputs for the neighbour
-search, the eight physics modes and a 5-step loop on an 840-particle channel.
+"""Generate the two fixtures of tests/golden: seeded inputs and the outputs of the neighbour search, the eight physics
+modes and a 5-step loop on a small channel.
 
-The reference itself cannot be run in this image (its MEX sources need MATLAB's mex.h), so these vectors
-are produced by oracle/sph_oracle.c -- the restatement that tests/test_oracle_anchor.py ties to the
-figures recorded from the reference (pair counts, step counts, L2).  The fixture pins the oracle against
+oracle_small.npz (840 particles, default parameters) is written by oracle/sph_oracle.c, the restatement of the reference
+that tests/test_reference_anchor.py holds bit for bit against the reference's own code.  It pins the oracle against
 regressions and lets the GPU parity tests run against committed data.
 
-    python tests/golden/make_golden.py
+reference_small.npz (720 particles: DH = 0.8, rho0 = 2.5, moving walls, uneven mass, non-default mu, c_f, U_bulk,
+transport_coeff -- helpers.make_variant) is written by the reference's own two MEX files, built unmodified against the mocked
+MATLAB C API into oracle/_ref/ (`make -C oracle ref`, needs a checkout of the reference), and called through
+tests/mex_mock.py; its five steps are driver.run(engine="mex") over those binaries.  It holds only arrays that the reference's
+programs read or wrote.  tests/test_oracle_anchor.py reproduces it from the oracle, tests/test_gpu_golden.py compares the HIP
+kernels with it directly.
+
+    python tests/golden/make_golden.py [oracle|reference]       (default: both, the second where oracle/_ref/ can be had)
 """
 import importlib
 import os
@@ -19,7 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 import oracle  # noqa: E402
-from helpers import make_case  # noqa: E402
+import mex_mock  # noqa: E402
+from helpers import make_case, make_variant  # noqa: E402
 
 pkg = importlib.import_module("sph-poiseuille-flow_amd")
 
@@ -72,5 +79,72 @@ def main():
     print("wrote", path, os.path.getsize(path), "bytes;", len(nb[0]), "pairs")
 
 
+REFERENCE_CASE = dict(dp=0.05, DL=1.5, DH=0.8, rho0=2.5, mu=0.07, c_f=12.0, U_bulk=0.4, transport_coeff=0.1)
+
+
+def reference_case(cfgmod, geom, **kw):
+    return make_variant(cfgmod, geom, jitter=0.25, seed=2025, developed=True, **REFERENCE_CASE, **kw)
+
+
+def main_reference():
+    ref = mex_mock.reference_mex()
+    if ref is None:
+        print("reference_small.npz not written: neither oracle/_ref/ nor a reference checkout")
+        return 1
+    phys = ref.sph_physics_shell_mex
+    prm, parts = reference_case(pkg.config, pkg.geometry)
+    nf, nt = parts["n_fluid"], parts["n_total"]
+    mass, pos, vel, wv, drho = (parts[k] for k in ("mass", "pos", "vel", "wall_vel", "drho_dt"))
+    nb = ref.sph_neighbor_search_mex(pos, nf, nt, prm.h, prm.DL)
+    p6 = tuple(nb[:5]) + (nb[6],)
+    out = dict(REFERENCE_CASE, n_fluid=nf, n_total=nt, pos=pos, vel=vel, drho_dt=drho, mass=mass, wall_vel=wv)
+    for k, name in enumerate(("pair_i", "pair_j", "dx", "dy", "r", "W", "dW")):
+        out["nb_" + name] = nb[k]
+    rho, Vol, B = phys("density_correction", *nb, mass, nf, nt, prm.rho0, prm.h, prm.inv_sigma0)
+    out.update(rho=rho, Vol=Vol, B=B)
+    fv = phys("viscous_force", *p6, vel, Vol, B, prm.mu, prm.h, nf, nt, mass, wv)
+    out["viscous_force"] = fv
+    out["transport_pos_default"] = phys("transport_correction", *p6, Vol, B, pos, prm.h, nf, nt)
+    out["transport_pos_coeff"] = phys("transport_correction", *p6, Vol, B, pos, prm.h, nf, nt, prm.transport_coeff)
+    fp = fv.copy(order="F")
+    fp[:nf, 0] += mass[:nf] * prm.gravity_g
+    dt = 0.25 * prm.h / (prm.c_f + 1.0)
+    out.update(force_prior=fp, dt=dt)
+    common = (Vol, B, rho, mass, pos, vel, drho, fp, dt, nf, nt, prm.rho0, prm.p0, prm.c_f, wv)
+    for n, v in zip(("rho", "p", "pos", "force", "drho"), phys("integration_1st", *p6, *common)):
+        out["int1_" + n] = v
+    vel_new = vel.copy(order="F")
+    vel_new[:nf] += (fp[:nf] + out["int1_force"][:nf]) / mass[:nf, None] * dt
+    out["int2_vel_in"] = vel_new
+    for n, v in zip(("pos", "drho", "zeros"), phys("integration_2nd", *p6, Vol, out["int1_rho"], out["int1_pos"], vel_new, dt, nf,
+                                                   nt, wv)):
+        out["int2_" + n] = v
+    for n, v in zip(("rho", "p", "pos", "vel", "drho", "force"), phys("integration_verlet", *p6, *common)):
+        out["verlet_" + n] = v
+    adv = phys("advance_shell_step", *nb, mass, pos, vel, wv, rho, drho, dt, nf, nt, prm.rho0, prm.p0, prm.c_f, prm.mu, prm.h,
+               prm.inv_sigma0, prm.gravity_g)
+    for n, v in zip(("rho", "p", "pos", "vel", "drho", "force", "force_prior", "Vol", "B"), adv):
+        out["advance_" + n] = v
+    out["tau"] = np.array(phys("wall_shear_monitor", *p6, pos, vel, wv, Vol, B, nf, prm.DL, prm.DH, prm.mu, prm.h))
+    # five steps of the driver's MEX loop over the reference's binaries: four at the dt rule's own size and a fifth clipped to
+    # t_end (the loop stops on a time, not on a step count)
+    t_end = 4.5 * pkg.driver.verlet_time_step(vel[:nf], prm.c_f, prm.h, prm.nu, prm.gravity_g, 1e9)
+    prm5, _ = reference_case(pkg.config, pkg.geometry, end_time=t_end, output_interval=t_end)
+    res, state = mex_mock.run_driver_loop(pkg.driver, ref, prm5, parts)
+    assert res.steps == 5, res.steps
+    for k in ("pos", "vel", "rho", "p", "drho_dt", "force", "force_prior", "Vol", "B"):
+        out["run5_" + k] = np.asarray(state[k])
+    out.update(run5_t_end=t_end, run5_t=res.t, run5_steps=res.steps, run5_dt_last=state["dt"],
+               run5_tau=np.array([res.tau_bottom, res.tau_top]), run5_n_pairs=float(state["n_pairs"]))
+    path = os.path.join(HERE, "reference_small.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes;", nt, "particles,", len(nb[0]), "pairs")
+    return 0
+
+
 if __name__ == "__main__":
-    main()
+    which = sys.argv[1] if len(sys.argv) > 1 else "both"
+    if which in ("oracle", "both"):
+        main()
+    if which in ("reference", "both"):
+        sys.exit(main_reference())

@@ -25,6 +25,35 @@ def make_case(cfgmod, geom, dp=0.05, DL=3.0, seed=1234, jitter=0.2, developed=Tr
     return prm, parts
 
 
+def make_variant(cfgmod, geom, seed=1234, top_ux=0.8, bottom_ux=-0.3, uy_sigma=0.05, mass_spread=0.2, **kw):
+    """make_case plus what the reference takes as plain arguments and make_case leaves at zero / uniform: moving walls and
+    uneven mass.  Top wall u_x = top_ux, bottom wall u_x = bottom_ux (different sign and size), each times 1 + 0.05 U(-1,1)
+    per wall particle, u_y = uy_sigma N(0,1) per wall particle: every wall particle has its own velocity and x != y, so an
+    index or component mix-up shows.  The fluid rows of wall_vel, which nothing may read, hold decoys of order 3.  Mass is
+    multiplied by 1 + mass_spread U(-1,1) per particle, walls included.  rho0, DH, mu, c_f, U_bulk, transport_coeff go
+    through **kw to params_from_values as in make_case.  Deterministic for a given seed."""
+    prm, parts = make_case(cfgmod, geom, seed=seed, **kw)
+    nf, nt = parts["n_fluid"], parts["n_total"]
+    rng = np.random.default_rng(seed + 7919)
+    wv = np.zeros((nt, 2), order="F")
+    top = parts["pos"][nf:, 1] > 0.5 * prm.DH
+    wv[nf:, 0] = np.where(top, top_ux, bottom_ux) * (1 + 0.05 * (rng.random(nt - nf) * 2 - 1))
+    wv[nf:, 1] = uy_sigma * rng.standard_normal(nt - nf)
+    wv[:nf, 0] = 3.0 + 0.5 * rng.random(nf)
+    wv[:nf, 1] = -3.0 - 0.5 * rng.random(nf)
+    mass = parts["mass"] * (1 + mass_spread * (rng.random(nt) * 2 - 1))
+    parts.update(wall_vel=wv, mass=mass)
+    return prm, parts
+
+
+def with_density_floor(parts, rows=(3, 40), drho=-1e6):
+    """A copy of parts whose drho_dt drives rho + dt/2 drho_dt of a few fluid particles below 1e-10 on the next step: the
+    reference then takes rho0 for the half-step density (sph_physics_mex.c, `if (rho_half < 1e-10)`), so p = 0 there."""
+    out = dict(parts, drho_dt=np.array(parts["drho_dt"], copy=True))
+    out["drho_dt"][list(rows)] = drho
+    return out
+
+
 def canon_pairs(nb):
     """Sort a pair list by (i, j) so two lists can be compared as sets."""
     pi, pj = nb[0].astype(np.int64), nb[1].astype(np.int64)
@@ -55,7 +84,8 @@ def field_atol(prm, parts, nb, dt):
     dWV = float(np.max(np.abs(nb[6]))) * float(np.max(parts["mass"])) / prm.rho0 if len(nb[6]) else 1.0
     m = float(np.min(parts["mass"]))
     vol = float(np.max(parts["mass"])) / prm.rho0
-    vmax = float(np.max(np.abs(parts["vel"]))) + prm.gravity_g * dt
+    vmax = max(float(np.max(np.abs(parts["vel"]))), float(np.max(np.abs(parts["wall_vel"][parts["n_fluid"]:]), initial=0.0)))
+    vmax += prm.gravity_g * dt
     a_rho = eps * prm.rho0
     a_p = eps * prm.p0
     a_F = 30 * dWV * vol * (a_p + eps * prm.mu * vmax / prm.h)

@@ -3,6 +3,8 @@ of MATLAB's C API the gateways use -- there is no MATLAB in the image) and calls
 
     gw = Gateway("sph_neighbor_search_gateway.c")
     pair_i, pair_j, dx, dy, r, W, dW = gw(7, pos, n_fluid, n_total, h, DL)      # nlhs first, then prhs
+Gateway(lib=path) opens a shared object that was already linked with mex_mock.c: the reference's own MEX files, built by
+`make -C oracle ref` into oracle/_ref/ (ReferenceMex below gives them the call surface of mex_surface.py).
 Arguments: str -> char array, int / float -> double scalar, numpy array -> double matrix (column-major), dict -> scalar struct
 of double scalars, Handle -> uint64 scalar.  Errors raised through mexErrMsgIdAndTxt come back as MexError(identifier, message)."""
 import ctypes as C
@@ -50,8 +52,9 @@ def build(source):
 
 
 class Gateway:
-    def __init__(self, source):
-        L = C.CDLL(build(source))
+    def __init__(self, source=None, lib=None):
+        assert (source is None) != (lib is None), "give a gateway source under matlab/ or a built shared object"
+        L = C.CDLL(build(source) if lib is None else lib)
         self.L = L
         vp = C.c_void_p
         for name, res, args in (("mock_doubles", vp, [C.c_size_t, C.c_size_t, vp]), ("mock_string", vp, [C.c_char_p]),
@@ -111,3 +114,71 @@ class Gateway:
 
     def lock_count(self):
         return self.L.mock_lock_count()
+
+
+class ReferenceMex:
+    """The reference's two MEX functions (oracle/_ref/*.so) behind the call surface of mex_surface.py:
+    sph_neighbor_search_mex(pos, n_fluid, n_total, h, DL) and sph_physics_shell_mex(mode, *args, nargout=None)."""
+    NLHS = dict(density_correction=3, viscous_force=1, transport_correction=1, integration_1st=5, integration_2nd=3,
+                integration_verlet=6, advance_shell_step=9, wall_shear_monitor=2)
+    MexError = MexError
+
+    def __init__(self, neighbor_lib, physics_lib):
+        self.neighbor, self.physics = Gateway(lib=neighbor_lib), Gateway(lib=physics_lib)
+
+    def sph_neighbor_search_mex(self, *args, nargout=7):
+        return tuple(self.neighbor(nargout, *args))
+
+    def sph_physics_shell_mex(self, *args, nargout=None):
+        mode = args[0] if args and isinstance(args[0], str) else None
+        n = self.NLHS.get(mode, 1) if nargout is None else nargout
+        out = self.physics(n, *args)
+        return out[0] if n == 1 else tuple(out)
+
+
+def reference_mex():
+    """-> ReferenceMex over oracle/_ref/, built first where a reference checkout exists; None where there is neither."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import oracle
+    if not oracle.build_reference():
+        return None
+    return ReferenceMex(oracle.REF_LIBS["neighbor"], oracle.REF_LIBS["physics"])
+
+
+class LoopRecorder:
+    """A MEX surface as driver.run(engine="mex") calls it, keeping what the last step saw: the inputs and outputs of its
+    integration_verlet, Vol and B of its density_correction, the pair count of its last search."""
+
+    def __init__(self, surface):
+        self.surface, self.last = surface, {}
+
+    def neighbor(self, *a):
+        nb = self.surface.sph_neighbor_search_mex(*a)
+        self.last["n_pairs"] = len(nb[0])
+        return nb
+
+    def physics(self, mode, *a):
+        out = self.surface.sph_physics_shell_mex(mode, *a)
+        if mode == "density_correction":
+            self.last["Vol"], self.last["B"] = out[1], out[2]
+        elif mode == "integration_verlet":
+            self.last["force_prior"], self.last["dt"] = np.array(a[13], order="F", copy=True), float(a[14])
+            for k, v in zip(("rho", "p", "pos", "vel", "drho_dt", "force"), out):
+                self.last[k] = v
+        return out
+
+
+def run_driver_loop(driver, surface, prm, parts):
+    """driver.run(prm, engine="mex", parts=parts) with `surface` (ReferenceMex) in place of the HIP MEX surface.
+    -> (RunResult, state after the last step: the nine fields of Context.download, dt, n_pairs)."""
+    rec = LoopRecorder(surface)
+    saved = driver.sph_neighbor_search_mex, driver.sph_physics_shell_mex
+    driver.sph_neighbor_search_mex, driver.sph_physics_shell_mex = rec.neighbor, rec.physics
+    try:
+        res = driver.run(prm, engine="mex", parts=parts)
+    finally:
+        driver.sph_neighbor_search_mex, driver.sph_physics_shell_mex = saved
+    state = dict(rec.last, pos=res.pos, vel=res.vel)
+    state["force_prior"][parts["n_fluid"]:] = 0.0   # (the driver zeroes the wall rows of its own copy)
+    return res, state

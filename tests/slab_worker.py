@@ -149,17 +149,22 @@ def main():
     ap.add_argument("--dp", type=float, default=0.05)
     ap.add_argument("--DL", type=float, default=3.0)
     ap.add_argument("--lpp", type=int, default=0)
+    ap.add_argument("--moving-walls", action="store_true", help="helpers.make_variant: moving walls, uneven mass, rho0 = 2.5")
     ap.add_argument("--native", action="store_true", help="hip engine: the library's own loop over RCCL (one GPU per rank)")
     ap.add_argument("--graph", action="store_true", help="--native: replay the steps as a captured hipGraph after the first four")
     args = ap.parse_args()
     import torch
     import torch.distributed as dist
-    from helpers import assert_close, make_case
+    from helpers import assert_close, make_case, make_variant
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     dist.init_process_group("gloo")
     pkg = importlib.import_module(PKG)
     slab = importlib.import_module(PKG + ".slab")
-    prm, parts = make_case(pkg.config, pkg.geometry, dp=args.dp, DL=args.DL, jitter=0.2, seed=11, developed=True, end_time=1e9)
+    if args.moving_walls:
+        prm, parts = make_variant(pkg.config, pkg.geometry, dp=args.dp, DL=args.DL, jitter=0.2, seed=11, developed=True,
+                                  end_time=1e9, rho0=2.5, transport_coeff=0.1)
+    else:
+        prm, parts = make_case(pkg.config, pkg.geometry, dp=args.dp, DL=args.DL, jitter=0.2, seed=11, developed=True, end_time=1e9)
     nf = parts["n_fluid"]
     if args.native:
         # the library's own loop over its own RCCL communicator (one GPU per rank); the ranks agree over gloo that

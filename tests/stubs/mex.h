@@ -2,11 +2,13 @@
  * tests/stubs/mex.h -- TEST INFRASTRUCTURE, not MATLAB's header.
  *
  * A mock of the small subset of MATLAB's documented C Matrix / MEX API (R2018a interleaved-complex API: mxGetDoubles ...)
- * that THIS repository's gateways use (the .c files under sph-poiseuille-flow_amd/matlab).  It exists so that those three files can be
- * compiled with -Wall -Werror and driven by tests/test_matlab_gateways.py in an image that has no MATLAB: argument
- * unpacking, arity / shape checks, error identifiers and the calls into libsphx are then exercised for real, through
- * tests/stubs/mex_mock.c.  Nothing of the reference is built with it, and passing these tests says nothing about MATLAB
- * itself -- a maintainer still builds the gateways with `mex` (ensure_sphx_mex_compiled.m).
+ * that this repository's gateways (the .c files under sph-poiseuille-flow_amd/matlab) and the reference's two MEX files use.
+ * It exists so that our three gateways can be compiled with -Wall -Werror and driven by tests/test_matlab_gateways.py
+ * without MATLAB (argument unpacking, arity / shape checks, error identifiers and the calls into libsphx are then
+ * exercised for real, through tests/stubs/mex_mock.c), and so that oracle/Makefile can build the reference's own
+ * sph_neighbor_search_mex.c / sph_physics_mex.c, unmodified, into oracle/_ref/ for tests/test_reference_anchor.py.
+ * Passing these tests says nothing about MATLAB itself -- a maintainer still builds the gateways with `mex`
+ * (ensure_sphx_mex_compiled.m).
  * Prototypes follow the public documentation of the API (names, argument order and types).
  */
 #ifndef SPHX_TEST_MEX_H
@@ -44,6 +46,13 @@ mxArray *mxCreateNumericMatrix(mwSize m, mwSize n, mxClassID classid, mxComplexi
 mxArray *mxCreateStructMatrix(mwSize m, mwSize n, int nfields, const char **fieldnames);
 void mxSetField(mxArray *a, mwIndex index, const char *fieldname, mxArray *value);
 mxArray *mxGetField(const mxArray *a, mwIndex index, const char *fieldname);
+mxArray *mxCreateString(const char *str);
+mxArray *mxDuplicateArray(const mxArray *a);
+void mxDestroyArray(mxArray *a);
+void *mxMalloc(mwSize n);
+void *mxCalloc(mwSize n, mwSize size);
+void *mxRealloc(void *ptr, mwSize size);
+void mxFree(void *ptr);
 void mexErrMsgIdAndTxt(const char *identifier, const char *fmt, ...);
 void mexLock(void);
 void mexUnlock(void);

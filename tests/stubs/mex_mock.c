@@ -1,7 +1,9 @@
 /*
  * tests/stubs/mex_mock.c -- TEST INFRASTRUCTURE: a minimal runtime behind tests/stubs/mex.h (see there), linked into one
- * shared object per gateway by tests/mex_mock.py.  Arrays are heap blocks on one list (mock_free_all); mexErrMsgIdAndTxt
- * records identifier + message and long-jumps back to mock_call, as MATLAB returns to the prompt.
+ * shared object per gateway by tests/mex_mock.py (and into the reference's MEX files by oracle/Makefile).  Arrays are heap
+ * blocks on one list, mxMalloc blocks on a second one (both emptied by mock_free_all, as MATLAB's memory manager does when a
+ * MEX function returns or errors out); mexErrMsgIdAndTxt records identifier + message and long-jumps back to mock_call, as
+ * MATLAB returns to the prompt.
  */
 #include <setjmp.h>
 #include <stdarg.h>
@@ -88,6 +90,76 @@ mxArray *mxGetField(const mxArray *a, mwIndex index, const char *name)
     for (k = 0; k < a->nfields; ++k) if (strcmp(a->names[k], name) == 0) return a->fields[k];
     return NULL;
 }
+mxArray *mxCreateString(const char *str)
+{
+    const size_t len = str ? strlen(str) : 0;
+    mxArray *a = fresh(mxCHAR_CLASS, 1, len, 1);
+    if (len) memcpy(a->data, str, len);
+    return a;
+}
+static size_t elem_size(mxClassID cls)
+{
+    if (cls == mxCHAR_CLASS || cls == mxSTRUCT_CLASS) return 1;
+    return cls == mxDOUBLE_CLASS || cls == mxUINT64_CLASS || cls == mxINT64_CLASS ? 8 : 4;
+}
+mxArray *mxDuplicateArray(const mxArray *a)
+{
+    mxArray *b;
+    int k;
+    if (a->cls == mxSTRUCT_CLASS) {
+        b = mxCreateStructMatrix(a->m, a->n, a->nfields, (const char **)a->names);
+        for (k = 0; k < a->nfields; ++k) b->fields[k] = a->fields[k] ? mxDuplicateArray(a->fields[k]) : NULL;
+        return b;
+    }
+    b = fresh(a->cls, a->m, a->n, elem_size(a->cls));
+    if (a->m * a->n > 0) memcpy(b->data, a->data, a->m * a->n * elem_size(a->cls));
+    return b;
+}
+/* The block stays on the list until mock_free_all: nothing is freed twice, and a destroyed array that the caller still
+ * holds in plhs[] cannot dangle. */
+void mxDestroyArray(mxArray *a) { (void)a; }
+
+/* mxMalloc family: blocks carry a list header so that an error exit (longjmp) does not leak them. */
+typedef struct block_tag { struct block_tag *prev, *next; size_t size; double align_; } block;
+static block *g_blocks = NULL;
+static void block_link(block *b) { b->prev = NULL; b->next = g_blocks; if (g_blocks) g_blocks->prev = b; g_blocks = b; }
+static void block_unlink(block *b)
+{
+    if (b->prev) b->prev->next = b->next; else g_blocks = b->next;
+    if (b->next) b->next->prev = b->prev;
+}
+void *mxMalloc(mwSize n)
+{
+    block *b = (block *)malloc(sizeof(block) + (n ? n : 1));
+    if (!b) return NULL;
+    b->size = n; block_link(b);
+    return b + 1;
+}
+void *mxCalloc(mwSize n, mwSize size)
+{
+    void *p;
+    if (size && n > (size_t)-1 / size) return NULL;
+    p = mxMalloc(n * size);
+    if (p) memset(p, 0, n * size);
+    return p;
+}
+void *mxRealloc(void *ptr, mwSize size)
+{
+    block *b, *nb;
+    if (!ptr) return mxMalloc(size);
+    b = (block *)ptr - 1;
+    block_unlink(b);
+    nb = (block *)realloc(b, sizeof(block) + (size ? size : 1));
+    if (!nb) { block_link(b); return NULL; }
+    nb->size = size; block_link(nb);
+    return nb + 1;
+}
+void mxFree(void *ptr)
+{
+    if (!ptr) return;
+    block_unlink((block *)ptr - 1);
+    free((block *)ptr - 1);
+}
 void mexErrMsgIdAndTxt(const char *identifier, const char *fmt, ...)
 {
     va_list ap;
@@ -145,6 +217,7 @@ mxArray *mock_field(const mxArray *a, int k) { return a->fields[k]; }
 int mock_lock_count(void) { return g_locks; }
 void mock_free_all(void)
 {
+    while (g_blocks) { block *b = g_blocks; g_blocks = b->next; free(b); }
     while (g_all) {
         mxArray *a = g_all;
         int k;

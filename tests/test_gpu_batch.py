@@ -7,7 +7,7 @@ tolerances of test_gpu_resident.py.
 import numpy as np
 import pytest
 
-from helpers import assert_close, make_case
+from helpers import assert_close, make_case, make_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -73,6 +73,35 @@ def test_bit_identical_to_standalone(cfgmod, geom, capi, dp, DL, lpp):
                 ref = _everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
             assert got[m]["step"] == n
             _assert_identical(got[m], ref, f"member {m} eager={eager} dp={dp} lpp={lpp}")
+
+
+def test_shared_moving_walls_and_uneven_mass(cfgmod, geom, capi, oracle):
+    """One batch whose shared walls move and whose shared mass is uneven (helpers.make_variant, rho0 = 2.5); members differ in
+    mu, c_f, transport_coeff and their state as above.  Bit for bit the standalone contexts; member 1 against the oracle."""
+    members = []
+    for v in VARIANTS:
+        prm, parts = make_variant(cfgmod, geom, dp=0.05, DL=1.5, jitter=0.2, seed=v["seed"], developed=True, rho0=2.5, mu=v["mu"],
+                                  c_f=v["c_f"], transport_coeff=v["transport_coeff"])
+        if members:  # walls and masses are the batch's, not the member's
+            parts.update(mass=members[0][1]["mass"], wall_vel=members[0][1]["wall_vel"])
+        members.append((prm, parts))
+    kw = dict(t_end=1e9, lanes_per_particle=16)
+    with _batch(capi, members, **kw) as b:
+        n = 2 * b.info()["rebuild_every"] + 3
+        sts = b.advance(1e9, max_steps=n)
+        got = [_everything(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
+        assert b.info()["realignments"] == 0
+    for m, (prm, parts) in enumerate(members):
+        with _ctx(capi, prm, parts, **kw) as ctx:
+            st = ctx.advance(1e9, max_steps=n)
+            ref = _everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
+        _assert_identical(got[m], ref, f"member {m}, moving walls")
+    prm, parts = members[1]
+    ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n, enable_sort=False)
+    _oracle_check(got[1], ref)
+    assert_close(got[1]["tau"][0], ref["stats"]["tau_bottom"], rtol=1e-8, atol_scale=1e-9, name="tau_bottom")
+    assert_close(got[1]["tau"][1], ref["stats"]["tau_top"], rtol=1e-8, atol_scale=1e-9, name="tau_top")
+    assert got[1]["pairs"] == ref["stats"]["n_pairs_last"]
 
 
 def test_single_member_equals_standalone(cfgmod, geom, capi):

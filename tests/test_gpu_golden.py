@@ -1,5 +1,6 @@
-"""-m gpu: HIP path against the committed golden fixture (tests/golden/oracle_small.npz, produced by
-tests/golden/make_golden.py) -- runs without building the oracle."""
+"""-m gpu: HIP path against the committed golden fixtures (tests/golden/oracle_small.npz, and reference_small.npz, which
+the reference's own MEX binaries wrote: the one place where a HIP kernel is compared with the reference's output and not the
+oracle's; both produced by tests/golden/make_golden.py) -- runs without building the oracle."""
 import os
 
 import numpy as np
@@ -69,3 +70,53 @@ def test_golden_resident_five_steps(gold, capi):
         assert_close(got[k], g["run5_" + k], rtol=1e-9, atol_scale=1e-10, name=k)
     assert npairs == float(g["run5_n_pairs"])
     assert_close(np.array([tb, tt]), g["run5_tau"], rtol=1e-8, atol_scale=1e-9, name="tau")
+
+
+@pytest.fixture(scope="module")
+def refgold(cfgmod):
+    from test_oracle_anchor import reference_fixture
+    return reference_fixture(cfgmod)
+
+
+def test_reference_golden_neighbor_list(refgold, mex):
+    test_golden_neighbor_list(refgold, mex)
+
+
+def test_reference_golden_modes(refgold, mex):
+    """Moving walls, uneven mass, rho0 = 2.5, DH = 0.8: every mode against what the reference's binary returned."""
+    g, prm, nb, parts = refgold
+    nf, nt = parts["n_fluid"], parts["n_total"]
+    assert prm.rho0 == 2.5 and prm.DH == 0.8 and np.all(parts["wall_vel"][nf:] != 0)
+    test_golden_modes(refgold, mex)
+    p6 = nb[:5] + (nb[6],)
+    dt = float(g["dt"])
+    at = field_atol(prm, parts, nb, dt)
+    tp = mex.sph_physics_shell_mex("transport_correction", *p6, g["Vol"], g["B"], parts["pos"], prm.h, nf, nt, prm.transport_coeff)
+    assert_close(tp, g["transport_pos_coeff"], rtol=1e-13, atol_scale=1e-14, name="transport(coeff)")
+    common = (g["Vol"], g["B"], g["rho"], parts["mass"], parts["pos"], parts["vel"], parts["drho_dt"], g["force_prior"], dt,
+              nf, nt, prm.rho0, prm.p0, prm.c_f, parts["wall_vel"])
+    for got, n in zip(mex.sph_physics_shell_mex("integration_1st", *p6, *common), ("rho", "p", "pos", "force", "drho")):
+        assert_close(got, g["int1_" + n], rtol=1e-10, atol=at[n], name="int1." + n)
+    got2 = mex.sph_physics_shell_mex("integration_2nd", *p6, g["Vol"], g["int1_rho"], g["int1_pos"], g["int2_vel_in"], dt, nf, nt,
+                                     parts["wall_vel"])
+    for got, n in zip(got2, ("pos", "drho", "zeros")):
+        assert_close(got, g["int2_" + n], rtol=1e-10, atol=at[n], name="int2." + n)
+
+
+@pytest.mark.parametrize("lpp", [0, 2])
+def test_reference_golden_resident_five_steps(refgold, capi, lpp):
+    g, prm, nb, parts = refgold
+    t_end = float(g["run5_t_end"])
+    with capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
+                      parts["wall_vel"], t_end=1e9, lanes_per_particle=lpp) as ctx:
+        st = ctx.advance(t_end)
+        got = ctx.download()
+        tb, tt, npairs = ctx.monitor(tau=True, pairs=True)
+    assert st["step"] == int(g["run5_steps"]) == 5 and abs(st["t"] - float(g["run5_t"])) < 1e-15
+    assert abs(st["dt_last"] - float(g["run5_dt_last"])) <= 1e-12 * float(g["run5_dt_last"])
+    for k in ("pos", "vel", "rho", "p", "drho_dt", "force", "force_prior", "Vol", "B"):
+        assert_close(got[k], g["run5_" + k], rtol=1e-9, atol_scale=1e-10, name=k)
+    assert npairs == float(g["run5_n_pairs"])
+    assert_close(np.array([tb, tt]), g["run5_tau"], rtol=1e-8, atol_scale=1e-9, name="tau")
+    assert_close(tb, g["run5_tau"][0], rtol=1e-8, atol_scale=1e-9, name="tau_bottom")
+    assert_close(tt, g["run5_tau"][1], rtol=1e-8, atol_scale=1e-9, name="tau_top")

@@ -10,7 +10,7 @@ test_gpu_resident.py, and identical schedules must give identical bits.
 import numpy as np
 import pytest
 
-from helpers import assert_close, canon_pairs, make_case
+from helpers import assert_close, canon_pairs, make_case, make_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -27,6 +27,13 @@ def calm_case(cfgmod, geom):
     """Slightly disordered lattice at rest: nothing outruns the default skin in the first few hundred steps, so the
     static re-binning schedule runs undisturbed (tests of the graph bookkeeping)."""
     return make_case(cfgmod, geom, dp=0.04, DL=3.0, jitter=0.05, seed=11, developed=False)
+
+
+@pytest.fixture(scope="module")
+def moving_case(cfgmod, geom):
+    """Moving walls, uneven mass, rho0 = 2.5 (helpers.make_variant): wall velocities and masses must come through the
+    permutation of every re-binning and through the frozen-list steps in between."""
+    return make_variant(cfgmod, geom, dp=0.04, DL=1.5, jitter=0.3, seed=11, developed=True, rho0=2.5, transport_coeff=0.1)
 
 
 def _ctx(capi, prm, parts, **kw):
@@ -60,6 +67,28 @@ def test_any_rebuild_interval_matches_oracle(case, capi, oracle, K, n_steps):
     assert npairs == ref["stats"]["n_pairs_last"]
     assert_close(np.array([tb, tt]), np.array([ref["stats"]["tau_bottom"], ref["stats"]["tau_top"]]), rtol=1e-8,
                  atol_scale=1e-9, name="tau")
+
+
+@pytest.mark.parametrize("kw", [dict(rebuild_every=5, lanes_per_particle=8), dict(rebuild_every=8, lanes_per_particle=2),
+                                dict(rebuild_every=8, lanes_per_particle=16),
+                                dict(rebuild_every=5, lanes_per_particle=4, dynamic_rebin=1),
+                                dict(rebuild_every=8, lanes_per_particle=2, dynamic_rebin=1)])
+def test_moving_walls_and_uneven_mass_across_rebinnings(moving_case, capi, oracle, kw):
+    prm, parts = moving_case
+    n_steps = 35
+    ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_steps, enable_sort=False)
+    with _ctx(capi, prm, parts, **kw) as ctx:
+        assert ctx.grid_policy()["rebuild_every"] == kw["rebuild_every"]
+        assert ctx.schedule()["dynamic"] == kw.get("dynamic_rebin", 0)
+        st = ctx.advance(1e9, max_steps=n_steps)
+        got = ctx.download()
+        tb, tt, npairs = ctx.monitor(tau=True, pairs=True)
+        assert ctx.schedule()["rebins"] + ctx.grid_policy()["forced_rebuilds"] >= 1
+    assert st["step"] == n_steps
+    _check(got, ref, f"moving{kw}")
+    assert npairs == ref["stats"]["n_pairs_last"]
+    assert_close(tb, ref["stats"]["tau_bottom"], rtol=1e-8, atol_scale=1e-9, name="tau_bottom")
+    assert_close(tt, ref["stats"]["tau_top"], rtol=1e-8, atol_scale=1e-9, name="tau_top")
 
 
 def test_undersized_skin_forces_rebuilds_and_stays_exact(case, capi, oracle):

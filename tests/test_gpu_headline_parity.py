@@ -22,7 +22,7 @@ missed or doubled neighbour changes rho by ~1e-2 relative).  Integer work (pair 
 import numpy as np
 import pytest
 
-from helpers import make_case
+from helpers import make_case, make_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +47,17 @@ def _errors(got, ref):
 def test_default_headline_context_matches_oracle_across_rebinning(name, dp, DL, jitter, lanes, n_steps, cfgmod, geom, capi,
                                                                   oracle, capsys):
     prm, parts = make_case(cfgmod, geom, dp=dp, DL=DL, jitter=jitter, seed=21, developed=True)
+    _default_context_matches_oracle(name, prm, parts, lanes, n_steps, capi, oracle, capsys)
+
+
+def test_default_headline_context_with_moving_walls_and_uneven_mass(cfgmod, geom, capi, oracle, capsys):
+    """The same context and the same checks on a small channel whose walls move, whose masses are uneven and whose rho0 is
+    2.5 (helpers.make_variant), over two scheduled re-binnings."""
+    prm, parts = make_variant(cfgmod, geom, dp=0.04, DL=3.0, jitter=0.2, seed=21, developed=True, rho0=2.5, transport_coeff=0.1)
+    _default_context_matches_oracle("C1 moving walls", prm, parts, 32, 35, capi, oracle, capsys)
+
+
+def _default_context_matches_oracle(name, prm, parts, lanes, n_steps, capi, oracle, capsys):
     nf, nt = parts["n_fluid"], parts["n_total"]
     with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
                       t_end=1e9) as ctx:  # every tuning knob left at its default: this is bench.py's context

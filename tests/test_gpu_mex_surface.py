@@ -8,7 +8,7 @@ membership, 1e-14 relative on dx,dy,r and 1e-12 on W,dW.
 import numpy as np
 import pytest
 
-from helpers import assert_close, canon_pairs, field_atol, make_case
+from helpers import assert_close, canon_pairs, field_atol, make_case, make_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -17,13 +17,17 @@ CASES = [
     dict(dp=0.05, DL=3.0, jitter=0.2, developed=True),    # disordered + developed state
     dict(dp=0.04, DL=3.0, jitter=0.3, developed=True),    # DL/2h non-integer: seam handling
     dict(dp=0.025, DL=1.0, jitter=0.25, developed=True),  # short periodic box, many seam pairs
+    # moving walls (every wall particle its own velocity), uneven mass, rho0 != 1: what make_case leaves at zero / one
+    dict(variant=True, dp=0.05, DL=3.0, jitter=0.2, developed=True, rho0=2.5, transport_coeff=0.1),
+    dict(variant=True, dp=0.04, DL=1.3, DH=0.8, jitter=0.25, developed=True, rho0=0.37),  # DH != 1: the top / bottom split of tau
 ]
 
 
 @pytest.fixture(scope="module", params=range(len(CASES)))
 def case(request, cfgmod, geom, oracle):
-    kw = CASES[request.param]
-    prm, parts = make_case(cfgmod, geom, seed=100 + request.param, **kw)
+    kw = dict(CASES[request.param])
+    make = make_variant if kw.pop("variant", False) else make_case
+    prm, parts = make(cfgmod, geom, seed=100 + request.param, **kw)
     nb = oracle.neighbor_search(parts["pos"], parts["n_fluid"], parts["n_total"], prm.h, prm.DL)
     return prm, parts, nb
 
@@ -75,7 +79,7 @@ def test_viscous_force(case, mex, oracle):
 def test_transport_correction(case, mex, oracle):
     prm, parts, nb, nf, nt, rho, Vol, B = _state(case, oracle)
     p6 = nb[:5] + (nb[6],)
-    for coeff in (None, 0.30):
+    for coeff in (None, 0.30, prm.transport_coeff):
         ref = oracle.transport_correction(nb, Vol, B, parts["pos"], prm.h, nf, nt, 0.2 if coeff is None else coeff)
         args = (Vol, B, parts["pos"], prm.h, nf, nt) + (() if coeff is None else (coeff,))
         got = mex.sph_physics_shell_mex("transport_correction", *p6, *args)

@@ -8,7 +8,7 @@ statistics (profile, step count) -- see test_gpu_longrun.py.
 import numpy as np
 import pytest
 
-from helpers import assert_close, canon_pairs, make_case
+from helpers import assert_close, canon_pairs, make_case, make_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -27,8 +27,30 @@ def _ctx(capi, prm, parts, lpp, **kw):
                         parts["mass"], parts["wall_vel"], lanes_per_particle=lpp, **kw)
 
 
+# moving walls + uneven mass (helpers.make_variant) with rho0 != 1, and the same on a channel of height DH = 0.8
+VARIANTS = {"rho25": dict(dp=0.05, DL=1.5, jitter=0.2, rho0=2.5, transport_coeff=0.1),
+            "DH08": dict(dp=0.04, DL=1.3, DH=0.8, jitter=0.25, rho0=0.37)}
+
+
+@pytest.fixture(scope="module", params=list(VARIANTS))
+def variant(request, cfgmod, geom):
+    return make_variant(cfgmod, geom, seed=7, developed=True, **VARIANTS[request.param])
+
+
 @pytest.mark.parametrize("n_steps", [1, 3, 10])
 def test_steps_match_oracle(case, capi, oracle, n_steps):
+    _steps_match_oracle(case, capi, oracle, n_steps)
+
+
+@pytest.mark.parametrize("n_steps", [1, 3, 10])
+@pytest.mark.parametrize("lpp", [1, 2, 4, 8, 16, 32])  # up to 8 lanes the large-channel walk forms, from 16 the compact ones
+def test_steps_match_oracle_with_moving_walls_uneven_mass_and_rho0(variant, lpp, capi, oracle, n_steps):
+    prm, parts = variant
+    assert prm.rho0 != 1.0 and np.ptp(parts["mass"][:parts["n_fluid"]]) > 0 and np.all(parts["wall_vel"][parts["n_fluid"]:] != 0)
+    _steps_match_oracle((prm, parts, lpp), capi, oracle, n_steps)
+
+
+def _steps_match_oracle(case, capi, oracle, n_steps):
     prm, parts, lpp = case
     nf = parts["n_fluid"]
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_steps, enable_sort=False)
@@ -45,8 +67,29 @@ def test_steps_match_oracle(case, capi, oracle, n_steps):
     assert npairs == ref["stats"]["n_pairs_last"]
     assert_close(np.array([tb, tt]), np.array([ref["stats"]["tau_bottom"], ref["stats"]["tau_top"]]), rtol=1e-8,
                  atol_scale=1e-9, name="tau")
+    assert_close(tb, ref["stats"]["tau_bottom"], rtol=1e-8, atol_scale=1e-9, name="tau_bottom")  # one by one: with moving walls
+    assert_close(tt, ref["stats"]["tau_top"], rtol=1e-8, atol_scale=1e-9, name="tau_top")        # the two differ in size
     assert abs(st["vmax"] - ref["stats"]["vmax"]) <= 1e-9 * ref["stats"]["vmax"]
     assert np.all(got["pos"][:nf, 0] >= 0) and np.all(got["pos"][:nf, 0] <= prm.DL)
+
+
+def test_driver_carries_wall_velocities_and_masses(cfgmod, geom, driver, oracle):
+    """driver.run(prm, parts=...) on the moving-wall variant: the resident engine against the six MEX-surface calls per step
+    of engine="mex" (both HIP), and both against the oracle's loop -- the driver's own plumbing of wall_vel and mass."""
+    kw = dict(dp=0.05, DL=1.5, jitter=0.2, seed=13, developed=True, rho0=2.5, mu=0.07, c_f=12.0, U_bulk=0.4, transport_coeff=0.1)
+    prm0, parts = make_variant(cfgmod, geom, **kw)
+    t_end = 6.5 * 0.25 * prm0.h / (prm0.c_f + 3.0)
+    prm, _ = make_variant(cfgmod, geom, end_time=t_end, output_interval=t_end, **kw)
+    ref = oracle.run(prm, parts, enable_sort=False)
+    a = driver.run(prm, parts=parts, engine="resident")
+    b = driver.run(prm, parts=parts, engine="mex")
+    for name, r in (("resident", a), ("mex", b)):
+        assert r.steps == ref["stats"]["steps"] >= 6 and abs(r.t - t_end) < 1e-12, (name, r.steps, r.t)
+        assert_close(r.pos, ref["pos"], rtol=1e-9, atol_scale=1e-10, name=name + ".pos")
+        assert_close(r.vel, ref["vel"], rtol=1e-9, atol_scale=1e-10, name=name + ".vel")
+        assert_close(r.tau_bottom, ref["stats"]["tau_bottom"], rtol=1e-8, atol_scale=1e-9, name=name + ".tau_bottom")
+        assert_close(r.tau_top, ref["stats"]["tau_top"], rtol=1e-8, atol_scale=1e-9, name=name + ".tau_top")
+    assert_close(a.vel, b.vel, rtol=1e-9, atol_scale=1e-10, name="resident against mex: vel")
 
 
 def test_bitwise_repeatable_and_lpp_consistent(case, capi):

@@ -1,7 +1,9 @@
 """Pins for the CPU oracle (not gpu).
 
-The reference ships no tests or golden vectors and cannot be built here (mex.h), so the restatement is
-anchored on what IS recorded from the reference itself in BASELINE.md section 2 / SURVEY.md section 8:
+tests/test_reference_anchor.py holds the oracle bit for bit against the reference's own C code where a checkout of the
+reference (or oracle/_ref/ built from one) exists.  Everywhere, the restatement is anchored on what is recorded from the
+reference itself -- the fixture golden/reference_small.npz, written by the reference's binaries -- and in BASELINE.md
+section 2 / SURVEY.md section 8:
   * the pair count of sph_neighbor_search_mex on the reference's own initial lattice at four
     resolutions (exact integers);
   * the analytic Poiseuille solution the reference validates against (postprocess L2 < 5 %);
@@ -16,6 +18,7 @@ import pytest
 from helpers import assert_close, canon_pairs
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "oracle_small.npz")
+REF_GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "reference_small.npz")
 
 
 @pytest.mark.parametrize("dp,DL,n_fluid,n_wall,pairs", [(0.05, 3.0, 1200, 480, 12660), (0.04, 3.0, 1875, 600, 19575),
@@ -117,6 +120,66 @@ def test_golden_fixture_reproduced(cfgmod, oracle):
     run = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=5, enable_sort=False)
     for k in ("pos", "vel", "drho_dt", "rho", "p"):
         assert np.array_equal(run[k], g["run5_" + k]), k
+
+
+def reference_fixture(cfgmod, **kw):
+    """-> (npz, prm, pair list, parts) of golden/reference_small.npz, the fixture written by the reference's own binaries."""
+    g = np.load(REF_GOLDEN)
+    prm = cfgmod.params_from_values(**{k: float(g[k]) for k in ("dp", "DL", "DH", "rho0", "mu", "c_f", "U_bulk", "transport_coeff")}, **kw)
+    nb = tuple(g["nb_" + n] for n in ("pair_i", "pair_j", "dx", "dy", "r", "W", "dW"))
+    parts = dict(n_fluid=int(g["n_fluid"]), n_total=int(g["n_total"]), pos=g["pos"], vel=g["vel"], drho_dt=g["drho_dt"],
+                 mass=g["mass"], wall_vel=g["wall_vel"])
+    return g, prm, nb, parts
+
+
+def test_reference_fixture_reproduced(cfgmod, oracle):
+    """golden/reference_small.npz holds what the reference's own MEX binaries returned (make_golden.py reference): the oracle
+    must reproduce the pair list and all eight modes bit for bit, pair order included, and the five steps of the
+    reference-driven loop within the bound of test_reference_anchor.py's loop test (ten times the differences measured there,
+    never above 1e-12; here both loops clip the last dt to the same t_end)."""
+    g, prm, nb, parts = reference_fixture(cfgmod)
+    nf, nt = parts["n_fluid"], parts["n_total"]
+    mass, pos, vel, wv, drho = (parts[k] for k in ("mass", "pos", "vel", "wall_vel", "drho_dt"))
+    assert prm.rho0 == 2.5 and prm.DH == 0.8 and np.all(wv[nf:] != 0) and np.ptp(mass[:nf]) > 0
+
+    def same(a, key):
+        a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(g[key], dtype=np.float64)
+        assert a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64)), \
+            f"{key}: max |oracle - reference| = {np.max(np.abs(a - b)):.3e}"
+
+    for got, name in zip(oracle.neighbor_search(pos, nf, nt, prm.h, prm.DL), ("pair_i", "pair_j", "dx", "dy", "r", "W", "dW")):
+        same(got, "nb_" + name)
+    rho, Vol, B = oracle.density_correction(nb, mass, nf, nt, prm.rho0, prm.h, prm.inv_sigma0)
+    same(rho, "rho"); same(Vol, "Vol"); same(B, "B")
+    same(oracle.viscous_force(nb, vel, Vol, B, prm.mu, prm.h, nf, nt, mass, wv), "viscous_force")
+    same(oracle.transport_correction(nb, Vol, B, pos, prm.h, nf, nt, 0.2), "transport_pos_default")
+    same(oracle.transport_correction(nb, Vol, B, pos, prm.h, nf, nt, prm.transport_coeff), "transport_pos_coeff")
+    dt, fp = float(g["dt"]), g["force_prior"]
+    common = (Vol, B, rho, mass, pos, vel, drho, fp, dt, nf, nt, prm.rho0, prm.p0, prm.c_f, wv)
+    for got, n in zip(oracle.integration_1st(nb, *common), ("rho", "p", "pos", "force", "drho")):
+        same(got, "int1_" + n)
+    for got, n in zip(oracle.integration_2nd(nb, Vol, g["int1_rho"], g["int1_pos"], g["int2_vel_in"], dt, nf, nt, wv),
+                      ("pos", "drho", "zeros")):
+        same(got, "int2_" + n)
+    for got, n in zip(oracle.integration_verlet(nb, *common), ("rho", "p", "pos", "vel", "drho", "force")):
+        same(got, "verlet_" + n)
+    adv = oracle.advance_shell_step(nb, mass, pos, vel, wv, rho, drho, dt, nf, nt, prm.rho0, prm.p0, prm.c_f, prm.mu, prm.h,
+                                    prm.inv_sigma0, prm.gravity_g)
+    for got, n in zip(adv, ("rho", "p", "pos", "vel", "drho", "force", "force_prior", "Vol", "B")):
+        same(got, "advance_" + n)
+    same(np.array(oracle.wall_shear_monitor(nb, pos, vel, wv, Vol, B, nf, prm.DL, prm.DH, prm.mu, prm.h)), "tau")
+    # the five steps
+    from test_reference_anchor import LOOP_BOUND, MEASURED_LOOP
+    t_end = float(g["run5_t_end"])
+    run = oracle.run(prm, parts, t_end=t_end, output_interval=t_end, enable_sort=False)
+    rs = run["stats"]
+    assert rs["steps"] == int(g["run5_steps"]) == 5 and rs["n_pairs_last"] == float(g["run5_n_pairs"])
+    diffs = dict(t=abs(rs["t"] - float(g["run5_t"])) / t_end, dt=abs(rs["dt_last"] - float(g["run5_dt_last"])) / rs["dt_last"],
+                 tau=float(np.max(np.abs(np.array([rs["tau_bottom"], rs["tau_top"]]) - g["run5_tau"])) / np.max(np.abs(g["run5_tau"]))))
+    for k in ("pos", "vel", "rho", "p", "drho_dt", "force", "force_prior", "Vol", "B"):
+        diffs[k] = float(np.max(np.abs(run[k] - g["run5_" + k])) / np.max(np.abs(g["run5_" + k])))
+    for k, v in diffs.items():
+        assert v <= min(10 * MEASURED_LOOP[k], LOOP_BOUND), (k, v, diffs)
 
 
 def test_omp_oracle_agrees_with_serial(cfgmod, geom, oracle):

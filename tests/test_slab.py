@@ -18,9 +18,11 @@ def _launch(world, *extra, port):
     return subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
 
 
-@pytest.mark.parametrize("world,DL", [(2, 3.0), (3, 3.0)])
-def test_slab_decomposition_oracle_engine_gloo(world, DL, oracle):
-    r = _launch(world, "--engine", "oracle", "--steps", "4", "--dp", "0.05", "--DL", str(DL), port=29511 + world)
+@pytest.mark.parametrize("world,DL,extra", [(2, 3.0, ()), (3, 3.0, ()), (2, 3.0, ("--moving-walls",))],
+                         ids=["2-3.0", "3-3.0", "2-3.0-moving-walls"])
+def test_slab_decomposition_oracle_engine_gloo(world, DL, extra, oracle):
+    r = _launch(world, "--engine", "oracle", "--steps", "4", "--dp", "0.05", "--DL", str(DL), *extra,
+                port=29511 + world + 10 * len(extra))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "OK" in r.stdout
 
@@ -109,6 +111,8 @@ def test_slab_hip_two_ranks_half_million_particles():
     (2, 0.05, 3.0, 47, dict(calls=[3, 25, 19], graph_after=0)),
     (3, 0.05, 4.5, 36, dict(calls=[4, 32], graph_after=0, rebuild_every=4)),
     (2, 0.04, 3.0, 42, dict(calls=[2, 40], graph_after=0, rebuild_every=8, skin_h=0.05)),  # drift-triggered re-binnings inside replays
+    # moving walls, uneven mass, rho0 = 2.5 (helpers.make_variant): wall velocities and masses go through slab_setup's own upload
+    (2, 0.05, 3.0, 27, dict(moving_walls=True, rebuild_every=5)),
 ])
 def test_slab_native_ring_in_one_process(world, dp, DL, steps, kw):
     """The library's own step loop (sphx_slab_group_run: every slab of the ring in this process, device-to-device
@@ -118,12 +122,16 @@ def test_slab_native_ring_in_one_process(world, dp, DL, steps, kw):
     import numpy as np
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from helpers import assert_close, make_case
+    from helpers import assert_close, make_case, make_variant
     pkg = importlib.import_module("sph-poiseuille-flow_amd")
     slab = importlib.import_module("sph-poiseuille-flow_amd.slab")
-    prm, parts = make_case(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9)
-    nf, nt = parts["n_fluid"], parts["n_total"]
     kw = dict(kw)
+    if kw.pop("moving_walls", False):
+        prm, parts = make_variant(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9,
+                                  rho0=2.5, transport_coeff=0.1)
+    else:
+        prm, parts = make_case(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9)
+    nf, nt = parts["n_fluid"], parts["n_total"]
     calls = kw.pop("calls", [steps])  # the run in several calls: the ids of a re-binning in a call's last step travel with the next call
     graph_after = kw.pop("graph_after", None)
     overlap = kw.pop("overlap", None)  # which form of the skinned step (read by the library when a slab's buffers are made)
