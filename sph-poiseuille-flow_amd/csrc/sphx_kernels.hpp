@@ -4,7 +4,8 @@
 // transport_correction -> verlet_time_step -> integration_verlet -> periodic wrap -> neighbour
 // rebuild) is four neighbour passes with no host round trip,
 //     A k_density (list + density)  ->  B k_kgc  ->  CD k_forces  ->  E k_continuity (+ clock)
-// followed on every K-th step by the re-binning chain k_clock_scan -> k_scatter -> k_reorder.  On small channels pass E
+// followed on every K-th step by the re-binning chain k_clock_scan -> k_scatter -> k_reorder (small channels: folded into
+// passes CD and E of that step instead, k_forces_hist -> k_continuity_rebin).  On small channels pass E
 // of a step and pass A of the next one share a launch (k_continuity_density): 3 launches per step.  Design (long form
 // in DESIGN.md):
 //   * particles are sorted by cell, cell id = cx*ncy + cy (y fastest): the 3x3 neighbourhood of a cell is
@@ -263,6 +264,19 @@ __device__ __forceinline__ bool duplicate_column(const Grid &g, int ox)
 {
     return (g.ncx == 1 && ox != 0) || (g.ncx == 2 && ox == 1);
 }
+
+// Folded re-binning (k_forces_hist, k_continuity_rebin): is cell c_new one of the 3 x 3 cells around c_old (columns wrap on a
+// periodic grid of at least three columns)?  Between two re-binnings nobody moves further than half a skin plus one step, far
+// less than a cell, so every member of a new cell was binned in that cell's 3 x 3 neighbourhood.
+__device__ __forceinline__ bool rebin_near(const Grid &g, int c_old, int c_new)
+{
+    const int ox = c_old / g.ncy, oy = c_old - ox * g.ncy;
+    const int nx = c_new / g.ncy, ny = c_new - nx * g.ncy;
+    int dx = abs(nx - ox);
+    if (g.periodic && dx == g.ncx - 1) dx = 1;
+    return dx <= 1 && abs(ny - oy) <= 1;
+}
+constexpr int kFoldCells = 2048;  // the folded re-binning scans the histogram in LDS in every workgroup: fewer cells than this
 
 // the value of the other lane of a pair (lanes 2k, 2k + 1): one DPP move (quad_perm [1 0 3 2]), no LDS crossbar, no ballot
 __device__ __forceinline__ int pair_partner(int v) { return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true); }
@@ -748,6 +762,17 @@ __global__ __launch_bounds__(kBlock) void k_density(const Clock *clk, int q, Gri
 {
     density_pass<LPP, MODE>(clk, q, g, ph, s, t, w, cond_fresh);
 }
+// Contexts whose re-binning step is folded into passes CD and E (k_forces_hist, k_continuity_rebin): nobody counts the cell
+// histogram back down there (k_scatter's atomicSub did), and the tail workgroup of pass E advances the clock while the other
+// workgroups still read it.  The cell sweep of the step after a re-binning -- always the next launch that runs -- clears it.
+// (idle slot or not: a histogram is taken and used up inside one step slot, never across this launch)
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_density_zero(const Clock *clk, int q, Grid g, Phys ph,
+                                                         FluidSet s, FluidTmp t, Walls w, int cond_fresh)
+{
+    for (int k = (int)(blockIdx.x * kBlock + threadIdx.x); k < g.ncells; k += (int)(gridDim.x * kBlock)) t.count[k] = 0;
+    density_pass<LPP, 1>(clk, q, g, ph, s, t, w, cond_fresh);
+}
 // (the "_b" wrappers take the run-time arguments of their single-channel kernels as run-time arguments too: a constant there
 //  would let the compiler merge the bodies' blocks differently, and its fused multiply-adds -- so the last bits -- with them)
 template <int LPP, int MODE>
@@ -840,11 +865,16 @@ __global__ __launch_bounds__(kBlock) void k_kgc_b(Members mb, int q, Grid g, Flu
 // later = 1 (dual-rate loop, inner sub-steps after the first): the pressure part only -- viscous force and gravity
 // are those of the first sub-step (t.fp), there is no transport shift, the particle moves on from t.posn; pair geometry
 // stays that of the start of the outer step (s.pos), velocities are the latest ones (s.vel = the previous sub-step's).
-template <int LPP>
+// HIST (the step that re-bins, contexts with a folded re-binning step, see k_continuity_rebin): the lead lane holds the new
+// position, so the cell histogram is taken here instead of in pass E, which then finds it complete.  A particle that lands
+// further than one cell from where it was binned raises the grid flag: pass E of this step looks for the members of a new cell
+// only that far (rebin_near), and its tail workgroup turns the flag into SPHX_ERR_GRID.
+template <int LPP, bool HIST = false>
 __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                             const FluidTmp &t, const Walls &w, int later)
 {
     SPHX_PASS_INDEX();
+    const int c_binned = (HIST && in_cap && sub == 0) ? s.cell[i] : 0;
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
     const double2 vi = in_cap ? s.vel[i] : make_double2(0.0, 0.0);
     const double4 ai = in_cap ? t.a[i] : make_double4(1.0, 0.0, 0.0, 0.0);
@@ -870,6 +900,7 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     const double Voli = ai.x, p_i = ai.y, rhoh_i = ai.z;
     const double b11i = Bi.x, b12i = Bi.y, b21i = Bi.z, b22i = Bi.w;
     int first_wall = 1 << 20;  // wall neighbours are appended behind the fluid ones: this lane's rows >= first_wall
+    int h_cell = -1;           // HIST: the new cell of the lead lane's particle
     if (active) {
         for (int m = 0; m < nn_all; ++m) {
             const int e = m == 0 ? e_row0 : (m == 1 ? e_row1 : (LPP <= 8 && m == 2 ? e_row2 : (LPP <= 8 && m == 3 ? e_row3 : t.nl_idx[(size_t)m * t.nl_stride + tid])));
@@ -970,16 +1001,39 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
         t.veln[i] = make_double2(vxn, vyn);
         if (!later) t.fp[i] = make_double2(fpx, fpy);
         t.f[i] = make_double2(fx, fy);
+        if (HIST) {
+            int cx, cy;
+            cell_of(g, g.periodic ? wrap_x(xo, ph.DL) : xo, yo, cx, cy);
+            h_cell = cx * g.ncy + cy;
+            t.cellid[i] = h_cell;
+            if (!rebin_near(g, c_binned, h_cell)) atomicOr(t.flags, 1);
+        }
     }
     // largest drift from the binning positions (bounds how stale the cell grid may get, see Clock::drift)
     d2 = wave_max(d2);
     __shared__ double s_d2[kBlock / 64];
+    __shared__ int s_hc[HIST ? kBlock / LPP : 1];
     if ((threadIdx.x & 63) == 0) s_d2[threadIdx.x >> 6] = d2;
+    if (HIST && sub == 0) s_hc[threadIdx.x / LPP] = h_cell;
     __syncthreads();
     if (threadIdx.x == 0) {
         double m = s_d2[0];
         for (int k = 1; k < kBlock / 64; ++k) m = fmax(m, s_d2[k]);
         t.dpart[blk] = m;
+    }
+    // HIST: a workgroup's particles are neighbours in the old ordering and land in two or three cells: one atomic per cell and
+    // workgroup instead of one per particle (fifteen particles of a cell, in as many workgroups on eight L2s, queue up on one word)
+    if (HIST && threadIdx.x < kBlock / LPP) {
+        const int c = s_hc[threadIdx.x];
+        int same = 0;
+        bool first = true;
+#pragma unroll
+        for (int k = 0; k < kBlock / LPP; ++k) {
+            const bool eq = s_hc[k] == c;
+            same += eq ? 1 : 0;
+            if (eq && k < (int)threadIdx.x) first = false;
+        }
+        if (c >= 0 && first) atomicAdd(&t.count[c], same);
     }
 }
 template <int LPP>
@@ -987,6 +1041,12 @@ __global__ __launch_bounds__(kBlock) void k_forces(const Clock *clk, int q, Grid
                                                    FluidTmp t, Walls w, int later)
 {
     forces_pass<LPP>(clk, q, g, ph, s, t, w, later);
+}
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_forces_hist(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
+                                                        FluidTmp t, Walls w, int later)
+{
+    forces_pass<LPP, true>(clk, q, g, ph, s, t, w, later);
 }
 template <int LPP>
 __global__ __launch_bounds__(kBlock) void k_forces_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w, int later)
@@ -2095,7 +2155,8 @@ __device__ __forceinline__ void clock_step(Clock *clk, Clock c, int q, const Phy
 // atomic (past the non-coherent L2), the tail polls with agent-scope atomic loads and puts the "empty" pattern
 // back for the next step.  Nobody waits for the tail, so it cannot deadlock whatever the dispatch order; a grid
 // barrier (all wait for all) was measured at 70-90 us for 600 workgroups, this costs the tail ~1-2 us.
-__device__ __forceinline__ void continuity_tail(Clock *clk, int q, const Phys &ph, const FluidTmp &t, int nb)
+// rebuilt: the step ends with a fresh grid (k_continuity_rebin), as k_clock_scan's argument of that name
+__device__ __forceinline__ void continuity_tail(Clock *clk, int q, const Phys &ph, const FluidTmp &t, int nb, int rebuilt = 0)
 {
     if (!clk->run[q]) {
         if (threadIdx.x == 0) clk->run[1 - q] = 0;  // idle slot keeps the following slots idle
@@ -2129,7 +2190,7 @@ __device__ __forceinline__ void continuity_tail(Clock *clk, int q, const Phys &p
     if (threadIdx.x == 0) {
         for (int k = 1; k < kBlock / 64; ++k) { m = fmax(m, s_m[k]); d = fmax(d, s_d[k]); lost |= s_l[k]; }
         if (lost) c0.status = SPHX_ERR_DIVERGED;
-        clock_step(clk, c0, q, ph, sqrt(m), fl, -1, track ? sqrt(d) : -1.0, 0, t.half_skin);
+        clock_step(clk, c0, q, ph, sqrt(m), fl, -1, track ? sqrt(d) : -1.0, rebuilt, t.half_skin);
     }
 }
 
@@ -2174,12 +2235,22 @@ __device__ __forceinline__ void slab_seal_tail(const Clock *clk, int q, const Fl
 // WALK: the large-channel form of the walk (see the "_w" kernels): entries ahead, fluid / wall loops, fold hoisted
 // (bid, nb: this workgroup's index among the nb workgroups of the pass; c_*: the LDS tile arrays of the calling kernel)
 // CODED: slot-coded list entries (kSlotCodes)
-template <int LPP, bool WALK, int TILE, bool CODED = false>
+// REBIN (compact kernels, k_continuity_rebin): the pass also re-bins.  Pass CD of the step has taken the histogram of the new
+// cells (k_forces_hist).  The slot of a particle in the new ordering is canonical -- new cell first, then ascending id
+// (reorder_body) -- so nobody has to wait for anybody: every workgroup scans the histogram in LDS, the lanes of a particle
+// count the members of its new cell with a smaller id among the particles BINNED in the 3 x 3 cells around that cell (three
+// runs of the old layout, see rebin_near), and the lead lane stores the persistent fields straight into the other state and
+// layout `d`.  Histogram, new cells, ids and the runs are requested in the prologue, the first kFoldAhead candidates of every
+// lane in front of the walk.  Workgroup 0 stores the new cell ranges.
+constexpr int kFoldAhead = 8;
+template <int LPP, bool WALK, int TILE, bool CODED = false, bool REBIN = false>
 __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                                 const FluidTmp &t, const Walls &w, int do_hist, int tail, int bid, int nb,
-                                                double2 *c_pos, double2 *c_vel, double *c_vol, int next_half = 0)
+                                                double2 *c_pos, double2 *c_vel, double *c_vol, int next_half = 0,
+                                                const FluidSet &d = FluidSet{})
 {
     static_assert(!CODED || (WALK && TILE == kSlotCodes), "slot-coded lists: this pass stages the whole layout");
+    static_assert(!REBIN || (!WALK && TILE == 0 && LPP >= 16), "the folded re-binning belongs to the compact kernels");
     const int blk = xcd_block(bid, nb);
     const int tid = blk * kBlock + threadIdx.x;
     const int i = tid / LPP, sub = tid % LPP;
@@ -2206,11 +2277,37 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
     const bool lead = in_cap && sub == 0;
     const double4 a_own = lead ? t.a[i] : make_double4(0.0, 0.0, 0.0, 0.0);
     const double rhoh_i = a_own.z;
-    const double2 pn = (lead && do_hist) ? t.posn[i] : make_double2(0.0, 0.0);  // (requested whenever a histogram is possible)
+    const double2 pn = (lead && (do_hist || REBIN)) ? t.posn[i] : make_double2(0.0, 0.0);  // (requested whenever a histogram is possible)
+    // REBIN: the particle's new cell and id (every lane of the group), what only the lead lane moves, this thread's share of the
+    // histogram, and the three runs of the old layout that hold whoever can land in the new cell
+    constexpr int kPer = kFoldCells / kBlock;
+    int r_cnew = 0, r_id = 0, r_cold = 0, r_lo[3] = {0, 0, 0}, r_n[3] = {0, 0, 0}, r_hist[REBIN ? kPer : 1];
+    double r_mass = 0.0;
+    if (REBIN) {
+        r_cnew = in_cap ? t.cellid[i] : 0;
+        r_id = in_cap ? s.id[i] : 0;
+        r_cold = lead ? s.cell[i] : 0;
+        r_mass = lead ? s.mass[i] : 0.0;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) r_hist[j] = t.count[min((int)threadIdx.x * kPer + j, g.ncells)];
+    }
     const TileMap layout = (WALK && TILE > 0) ? tile_map_of(t, blk) : TileMap{0, 0, 0, 0, 0, 0};
     const double dt = clk->dt;
     const bool want_out = !WALK || step_outputs_wanted(clk, t);
     const int cell_own = (g.own_by_cell && lead) ? s.cell[i] : 0;
+    if (REBIN) {  // (behind the clock's loads: these wait for the new cell)
+        r_cnew = min(max(r_cnew, 0), g.ncells - 1);  // (slots beyond the population hold no cell: any valid one keeps the loads in bounds)
+        const int cxn = r_cnew / g.ncy, cyn = r_cnew - cxn * g.ncy;
+        const int cylo = max(cyn - 1, 0), cyhi = min(cyn + 1, g.ncy - 1);
+#pragma unroll
+        for (int ox = -1; ox <= 1; ++ox) {
+            int col = cxn + ox;  // (at least three columns, periodic: the three are distinct)
+            if (col < 0) col += g.ncx;
+            else if (col >= g.ncx) col -= g.ncx;
+            r_lo[ox + 1] = s.start[col * g.ncy + cylo];
+            r_n[ox + 1] = s.start[col * g.ncy + cyhi + 1] - r_lo[ox + 1];
+        }
+    }
     if (!clk->run[q]) return;
     const int n_now = clk->n;
     const bool active = i < n_now;
@@ -2261,6 +2358,38 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
         }
     };
     if (!WALK) publish_vmax();
+    __shared__ int r_start[REBIN ? kFoldCells + 1 : 1], r_wave[REBIN ? kBlock / 64 + 1 : 1];
+    const int r_nv = r_n[0] + r_n[1] + r_n[2];
+    auto r_slot = [&](int v) { return v < r_n[0] ? r_lo[0] + v : (v < r_n[0] + r_n[1] ? r_lo[1] + (v - r_n[0]) : r_lo[2] + (v - r_n[0] - r_n[1])); };
+    int r_ccell[REBIN ? kFoldAhead : 1], r_cid[REBIN ? kFoldAhead : 1];
+    if (REBIN) {
+        // exclusive scan of the histogram: the cell ranges of the new ordering, r_start[ncells] = the population
+        int sum = 0, total;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const int v = (int)threadIdx.x * kPer + j < g.ncells ? r_hist[j] : 0;
+            r_hist[j] = sum;
+            sum += v;
+        }
+        const int base = block_exclusive_scan_t<kBlock>(sum, total, r_wave);
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const int c = (int)threadIdx.x * kPer + j;
+            if (c <= g.ncells) {
+                r_start[c] = base + r_hist[j];
+                if (bid == 0) d.start[c] = base + r_hist[j];
+            }
+        }
+        __syncthreads();
+        // the first candidates of every lane: their new cells and ids (slot 0 stands in where a lane has fewer)
+#pragma unroll
+        for (int j = 0; j < kFoldAhead; ++j) {
+            const int v = sub + j * LPP;
+            const int k = v < r_nv ? r_slot(v) : 0;
+            r_ccell[j] = t.cellid[k];
+            r_cid[j] = s.id[k];
+        }
+    }
     if (WALK) {
         const int rows = active ? nn_all : 0, rows_fl = active ? list_fluid_rows(packed) : 0;
         TileMap tm{0, 0, 0, 0, 0, 0};
@@ -2360,6 +2489,19 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
         }
     }
     rate = group_sum<LPP>(rate);
+    int r_rank = 0;
+    if (REBIN) {
+        if (active) {
+#pragma unroll
+            for (int j = 0; j < kFoldAhead; ++j)
+                r_rank += (sub + j * LPP < r_nv && r_ccell[j] == r_cnew && r_cid[j] < r_id) ? 1 : 0;
+            for (int v = sub + kFoldAhead * LPP; v < r_nv; v += LPP) {
+                const int k = r_slot(v);
+                r_rank += (t.cellid[k] == r_cnew && s.id[k] < r_id) ? 1 : 0;
+            }
+        }
+        r_rank = (int)group_sum<LPP>((double)r_rank);  // (exact: a handful)
+    }
     if (active && sub == 0) {
         const double rhoh = rhoh_i;
         const double drho_new = rate * rhoh;
@@ -2374,6 +2516,23 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
             double rhoh2, p2;
             half_state(ph, rho, drho_new, dt, rhoh2, p2);
             t.a[i] = make_double4(a_own.x, p2, rhoh2, rho);
+        }
+        if (REBIN) {
+            const int dst = r_start[r_cnew] + r_rank;
+            // (the clock does not test the drift of the step that re-bins: a particle that is not where the count looked for it
+            //  must not take a slot somebody else may own -- pass CD has raised the flag already, the step ends in SPHX_ERR_GRID)
+            if (rebin_near(g, r_cold, r_cnew) && (unsigned)dst < (unsigned)t.cap) {
+                d.pos[dst] = pn;
+                d.vel[dst] = vi;
+                if (d.posb) d.posb[dst] = pn;
+                d.drho[dst] = drho_new;
+                d.mass[dst] = r_mass;
+                d.id[dst] = r_id;
+                d.cell[dst] = r_cnew;
+                t.src_of[dst] = i;
+            } else {
+                atomicOr(t.flags, 1);
+            }
         }
         if (hist) {
             int cx, cy;
@@ -2422,6 +2581,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WALK ? 8
         return;
     }
     continuity_body<LPP, WALK, TILE, CODED>(clk, q, g, ph, s, t, w, do_hist, tail, (int)blockIdx.x, nb, c_pos, c_vel, c_vol, next_half);
+}
+
+// Small channels, the step that re-bins: pass E with the re-binning folded in (continuity_body, REBIN) and the clock in the tail
+// workgroup, which advances it as k_clock_scan does on such a step.  d: the state / layout the new ordering goes to.
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_continuity_rebin(Clock *clk, int q, Grid g, Phys ph, FluidSet s, FluidTmp t, Walls w,
+                                                             FluidSet d)
+{
+    const int nb = (int)gridDim.x - 1;
+    if ((int)blockIdx.x == nb) {
+        continuity_tail(clk, q, ph, t, nb, 1);
+        return;
+    }
+    continuity_body<LPP, false, 0, false, true>(clk, q, g, ph, s, t, w, 0, 1, (int)blockIdx.x, nb, nullptr, nullptr, nullptr, 0, d);
 }
 
 // Small channels, steps that do not re-bin: pass E of this step and pass A of the NEXT step in one launch, side by

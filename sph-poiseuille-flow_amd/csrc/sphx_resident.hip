@@ -228,6 +228,9 @@ struct sphx_ctx {
     // (k_continuity_density).  The neighbour list and the {Vol, p, rho_h, rho} records then exist once per state parity:
     // tmp_par[p] is `tmp` with the buffers of parity p; out_par = the parity of the last executed step (its Vol).
     bool fuse_ea = false;
+    // ... and the step that re-bins is three launches: pass CD takes the histogram (k_forces_hist), pass E re-bins and carries the
+    // clock (k_continuity_rebin) -- no k_clock_scan / k_scatter / k_reorder; the next cell sweep clears the histogram (k_density_zero)
+    bool fold_rebin = false;
     bool lds_tiles_a = false;    // pass A's walk gathers the candidate positions from an LDS tile
     bool sweep_kernels = false;  // pass A's cell sweep in its large-channel form (k_density_sweep_w)
     int n_in = 1;                // dual-rate loop: inner sub-steps per step slot (1 = the reference's single-rate loop)
@@ -296,12 +299,14 @@ struct sphx_ctx {
 namespace {
 
 // A/B switches for measurements, all behind ONE environment variable read once per process:
-//   SPHX_DEBUG_SWITCHES=no_tail_clock,no_fuse_ea,no_lds_tiles,no_coded_lists,no_lazy_out,forces_tile_320,log
+//   SPHX_DEBUG_SWITCHES=no_tail_clock,no_fuse_ea,no_fold_rebin,no_lds_tiles,no_coded_lists,no_lazy_out,forces_tile_320,log
 // (no_tail_clock: the clock update as a launch of its own on every step; no_fuse_ea: passes E and A in separate launches;
+//  no_fold_rebin: small channels re-bin with the chain k_clock_scan -> k_scatter -> k_reorder behind pass E;
 //  no_lds_tiles: large-channel passes gather from global memory; no_coded_lists: index differences in every list, never tile
 //  slots; no_lazy_out: force, force_prior, rho, p written by every step (FluidTmp::lazy_out); log: forced re-binnings and timer
 //  problems on stderr)
 struct DebugSwitches {
+    bool no_fold_rebin = false;
     bool no_tail_clock = false, no_fuse_ea = false, no_lds_tiles = false, no_coded_lists = false, no_lazy_out = false, log = false;
     bool no_slab_overlap = false;  // skinned slabs: the local maxima from pass E's tail workgroup, the all-reduce on the step's only stream (round 3)
     bool full_copyback = false;  // dynamic contexts: the in-place re-binning copies the whole layout back (round 3)
@@ -318,6 +323,7 @@ const DebugSwitches &debug_switches()
         auto has = [&](const char *name) { return ("," + v + ",").find(std::string(",") + name + ",") != std::string::npos; };
         d.no_tail_clock = has("no_tail_clock");
         d.no_fuse_ea = has("no_fuse_ea");
+        d.no_fold_rebin = has("no_fold_rebin");
         d.no_lds_tiles = has("no_lds_tiles");
         d.no_coded_lists = has("no_coded_lists");
         d.no_lazy_out = has("no_lazy_out");
@@ -419,6 +425,7 @@ void launch_physics(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, in
         // small channels: the compact kernels (32-bit lists)
         if (!only || only == 1) {
             if (dmode == 0) launch(c, "k_density", k_density<LPP, 0>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, -1);
+            else if (dmode == 1 && c->fold_rebin) launch(c, "k_density_build", k_density_zero<LPP>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, -1);
             else if (dmode == 1) launch(c, "k_density_build", k_density<LPP, 1>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, -1);
             else {
                 // dmode 2: walk the superset list; 3 (dynamic contexts): build and walk, each skipping itself according to the
@@ -554,6 +561,23 @@ void launch_fused_ea_w(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t,
     launch(c, "k_continuity_density", k_continuity_density_w<LPP>, dim3(2 * c->n_blocks_particles + tail), dim3(kBlock),
            c->clock.get(), q, c->grid, c->phys, s, t, c->walls, sn, tn, tail);
 }
+// The folded re-binning step (sphx_ctx::fold_rebin): pass CD with the histogram, then pass E re-binning into view d
+template <int LPP>
+void launch_fold_rebin_t(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &d)
+{
+    const dim3 gp(c->n_blocks_particles), bp(kBlock);
+    launch(c, "k_forces_hist", k_forces_hist<LPP>, gp, bp, (const Clock *)c->clock.get(), q, c->grid, c->phys, s, t, c->walls, 0);
+    launch(c, "k_continuity_rebin", k_continuity_rebin<LPP>, dim3(c->n_blocks_particles + 1), bp, c->clock.get(), q, c->grid,
+           c->phys, s, t, c->walls, d);
+}
+void launch_fold_rebin(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &d)
+{
+    switch (c->lpp) {
+        case 16: launch_fold_rebin_t<16>(c, q, s, t, d); break;
+        case 32: launch_fold_rebin_t<32>(c, q, s, t, d); break;
+        default: throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fold", "internal: folded re-binning step at this lane count");
+    }
+}
 // tail = 0: without the clock workgroup (kernel timing)
 void launch_fused_ea(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &sn, const FluidTmp &tn, int tail = 1)
 {
@@ -637,6 +661,10 @@ void launch_step(sphx_ctx *c, int q, int l, int pos, bool rebuild)
         FluidTmp t = c->tmp_par[q];
         if (pos == 0) launch_physics_any(c, q, s, t, 1, 1, 1);
         launch_physics_any(c, q, s, t, 1, 2);
+        if (c->fold_rebin) {  // three launches: the histogram rides in pass CD, re-binning and clock in pass E
+            launch_fold_rebin(c, q, s, t, c->view(1 - q, 1 - l));
+            return;
+        }
         inner_substeps(t);
         launch_physics_any(c, q, s, t, 1, 4);
     } else {
@@ -970,6 +998,8 @@ void host_rebin(sphx_ctx *c, int n, const double2 *pos, int *cellid, int *count,
         SPHX_HIP(hipMemsetAsync(start, 0, ((size_t)c->grid.ncells + 1) * sizeof(int), c->stream));
         return;
     }
+    // (a folded re-binning step leaves its histogram for the next cell sweep to clear: the batch may have ended in between)
+    if (c->fold_rebin && count == c->count.get()) SPHX_HIP(hipMemsetAsync(count, 0, ((size_t)c->grid.ncells + 1) * sizeof(int), c->stream));
     const bool prof = c->profiling;
     c->profiling = false;
     const dim3 g1(div_up(n, kBlock)), bp(kBlock);
@@ -1174,6 +1204,10 @@ void ctx_alloc(sphx_ctx *c, int cap)
     // steps fit into the viscous / body-force step, at most dual_rate.  Fine channels are viscous-limited: n_in = 1 there.
     c->n_in = (c->fuse_ea && c->lpp >= 16) ? dual_rate_substeps(c->prm) : 1;
     if (c->n_in > 1) { dev_alloc(c, c->vel2, cap); c->vel2.zero(c->stream); }
+    // Folded re-binning step: the compact kernels with the fused E|A launch, single-rate, a periodic grid of at least three
+    // columns (the +-1 columns of a cell are distinct) small enough for every workgroup to scan in LDS (kFoldCells)
+    c->fold_rebin = c->fuse_ea && c->lpp >= 16 && c->n_in == 1 && !c->arena && !c->big_scan && c->n_vtiles == 0 &&
+                    g.periodic && g.ncx >= 3 && g.ncells < kFoldCells && !debug_switches().no_fold_rebin;
 
     dev_alloc(c, c->tau_part, (size_t)2 * c->n_blocks_flat);
     dev_alloc(c, c->tau_out, 2);
