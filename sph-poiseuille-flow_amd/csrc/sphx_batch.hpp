@@ -79,8 +79,7 @@ void batch_step_t(sphx_batch *b, int q, int l, int pos, bool rebuild)
     };
     if (!rebuild) {
         const FluidSet o = c->view(1 - q, l);
-        FluidTmp t = c->fuse_ea ? c->tmp_par[q] : c->tmp;
-        t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
+        const FluidTmp t = writing_into(c->fuse_ea ? c->tmp_par[q] : c->tmp, o);
         if (c->fuse_ea) {  // pass A of this step ran in the previous step's last launch, unless the grid is fresh
             if (pos == 0) pass_a(t, 1);
             passes_bc(t);

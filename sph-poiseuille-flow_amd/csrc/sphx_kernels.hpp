@@ -1694,7 +1694,7 @@ __device__ __forceinline__ void density_sweep_body_w(const Clock *clk, int q, co
 }
 
 // n_tiles: workgroup-sized tiles of the pass; the grid may be smaller (grid-stride over the tiles: the conditional launches
-// of a dynamic context, which are idle most of the time, see launch_physics)
+// of a dynamic context, which are idle most of the time, see launch_pass_a)
 template <int LPP, int MODE, bool CODED = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CODED ? 6 : 5))) void k_density_sweep_w(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
                                                             FluidTmp t, Walls w, int cond_fresh, int n_tiles)

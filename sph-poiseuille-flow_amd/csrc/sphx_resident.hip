@@ -211,7 +211,6 @@ struct sphx_ctx {
     DevBuf<double> max_part;
     DevBuf<int> ticket2;
     hipEvent_t ev_p = nullptr, ev_u = nullptr;  // "message A is packed" / "the halo is refreshed (or the layout rebuilt)"
-    int pass_a_part = 0;           // what the next launch of pass A's walk covers: 0 all, 1 interior, 2 boundary workgroups (slab_part_skips)
     bool a_interior_done = false;  // the interior workgroups of the coming step's pass A were launched behind this step's pack3
     // Whole slab steps as ONE replayable graph (sphx_slab_graph_prepare): kSlabGraphSteps steps of the native loop -- kernels,
     // the RCCL calls (sphx_slab_run) or the device-to-device copies and cross-stream dependencies of an in-process ring
@@ -407,136 +406,223 @@ int dual_rate_substeps(const sphx_params &prm)
     return std::max(1, std::min(fit, (int)prm.dual_rate));
 }
 
-// The four neighbour passes on state view `s`, writing the end-of-step state through t.posn / veln / drhon.
-// only: 0 = all four, 1..4 = just density / kgc / forces / continuity (kernel timing)
-// dmode: 0 = pass A sweeps the cells; 1 = sweeps and writes the superset list (first step after a re-bin);
-//        2 = walks the superset list
-// tail: pass E gets one workgroup more, which advances the clock (no k_clock_scan after this step)
-// inner (dual-rate loop, compact kernels only): this launch of pass CD / E belongs to an inner sub-step -- CD does the
-//        pressure part only, E hands the next sub-step its half-step density
-template <int LPP>
-void launch_physics(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, int do_hist, int only, int dmode, int tail, int inner)
-{
-    const dim3 gp(c->n_blocks_particles), bp(kBlock);
-    const Clock *clk = c->clock.get();
-    const dim3 ge(c->n_blocks_particles + (tail ? 1 : 0));  // tail: 1 = clock, 2 = a slab's local maxima (slab_seal_tail)
-    const char *name_e = tail ? "k_continuity_clock" : "k_continuity";
-    if constexpr (LPP >= 16) {
-        // small channels: the compact kernels (32-bit lists)
-        if (!only || only == 1) {
-            if (dmode == 0) launch(c, "k_density", k_density<LPP, 0>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, -1);
-            else if (dmode == 1 && c->fold_rebin) launch(c, "k_density_build", k_density_zero<LPP>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, -1);
-            else if (dmode == 1) launch(c, "k_density_build", k_density<LPP, 1>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, -1);
-            else {
-                // dmode 2: walk the superset list; 3 (dynamic contexts): build and walk, each skipping itself according to the
-                // clock's `fresh`
-                // (dmode 4, slabs: the walk alone, on a grid that is not fresh; pass_a_part: interior / boundary workgroups only)
-                const int cond = dmode == 2 ? -1 : (c->pass_a_part << kPassPartShift);
-                if (dmode == 3) launch(c, "k_density_build", k_density<LPP, 1>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, 1);
-                launch(c, "k_density_walk", k_density<LPP, 2>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, cond);
-            }
-        }
-        if (!only || only == 2) launch(c, "k_kgc", k_kgc<LPP>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, c->fuse_ea ? 1 : 0);
-        if (!only || only == 3) launch(c, inner ? "k_forces_inner" : "k_forces", k_forces<LPP>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, inner);
-        if (!only || only == 4)
-            launch(c, inner ? "k_continuity_inner" : name_e, k_continuity<LPP, false, 0>, ge, bp, c->clock.get(), q, c->grid, c->phys, s, t, c->walls, do_hist, tail, inner);
-    } else {
-        // large channels (few lanes per particle): the "_w" forms, see sphx_kernels.hpp -- fluid list entries are 16-bit index
-        // differences, so builders and walkers always go together
-        constexpr int T = tile_slots(LPP);
-        if (!only || only == 1) {
-            auto sweep = [&](const char *name, auto mode, int cond) {  // the cell sweep: mode 0 writes the step's list, mode 1 the superset list as well
-                constexpr int M = decltype(mode)::value;
-                // the build variant of a dynamic context is idle on four steps out of five: a grid-stride launch of an eighth
-                // of the workgroups costs an eighth to skip (6 M particles: 47 k idle workgroups were ~70 us of every step)
-                const unsigned nb = cond >= 0 ? std::max<unsigned>(1u, (unsigned)c->n_blocks_particles / 8u) : (unsigned)c->n_blocks_particles;
-                if constexpr (LPP == 2) {
-                    if (c->coded_lists) {
-                        launch(c, name, k_density_sweep_w<LPP, M, true>, dim3(nb), bp, clk, q, c->grid, c->phys, s, t, c->walls, cond, c->n_blocks_particles);
-                        return;
-                    }
-                }
-                launch(c, name, k_density_sweep_w<LPP, M>, dim3(nb), bp, clk, q, c->grid, c->phys, s, t, c->walls, cond, c->n_blocks_particles);
-            };
-            if (dmode == 0) sweep("k_density", std::integral_constant<int, 0>{}, -1);
-            else if (dmode == 1) sweep("k_density_build", std::integral_constant<int, 1>{}, -1);
-            else {
-                const int cond = dmode == 2 ? -1 : (c->pass_a_part << kPassPartShift);  // (dmode 4: see the compact kernels)
-                if (dmode == 3) sweep("k_density_build", std::integral_constant<int, 1>{}, 1);
-                bool done = false;
-                if constexpr (LPP == 2) {
-                    if (c->coded_lists) {
-                        launch(c, "k_density_walk", k_density_w<LPP, kSlotCodes, true>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, cond);
-                        done = true;
-                    }
-                }
-                if (done) {}
-                else if (c->lds_tiles_a) launch(c, "k_density_walk", k_density_w<LPP, T>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, cond);
-                else launch(c, "k_density_walk", k_density_w<LPP, 0>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, cond);
-            }
-        }
-        // LDS tiles (tile_ranges): the force pass always; KGC and continuity where measured to pay (lds_tiles_be)
-        bool coded = false;  // slot-coded lists (2 lanes per particle, every pass with a tile): the CODED forms of the same kernels
-        if constexpr (LPP == 2) coded = c->coded_lists;
-        if (!only || only == 2) {
-            if constexpr (LPP == 2) {
-                if (coded) launch(c, "k_kgc", k_kgc_w<LPP, kSlotCodes, true>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, c->fuse_ea ? 1 : 0);
-            }
-            if (coded) {}
-            else if (c->lds_tiles_be) launch(c, "k_kgc", k_kgc_w<LPP, T>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, c->fuse_ea ? 1 : 0);
-            else launch(c, "k_kgc", k_kgc_w<LPP, 0>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls, c->fuse_ea ? 1 : 0);
-        }
-        if (!only || only == 3) {
-            if constexpr (LPP == 2) {
-                // (the whole layout, four workgroups per CU: with 320 slots, five per CU, a quarter of the neighbours came from
-                //  global memory in nearly every trip of every wave -- 6 M particles 516 -> 489 us, forces_tile_320 for the old size)
-                if (coded) {
-                    if (debug_switches().forces_tile == 320) launch(c, "k_forces", k_forces_w<LPP, 320, true>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls);
-                    else launch(c, "k_forces", k_forces_w<LPP, kForceSlots, true>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls);
-                }
-            }
-            if (coded) {}
-            else if (c->lds_tiles) launch(c, "k_forces", k_forces_w<LPP, (LPP <= 2 ? 320 : T)>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls);
-            else launch(c, "k_forces", k_forces_w<LPP, 0>, gp, bp, clk, q, c->grid, c->phys, s, t, c->walls);
-        }
-        if (!only || only == 4) {
-            if constexpr (LPP == 2) {
-                if (coded) launch(c, name_e, k_continuity<LPP, true, kSlotCodes, true>, ge, bp, c->clock.get(), q, c->grid, c->phys, s, t, c->walls, do_hist, tail, 0);
-            }
-            if (coded) {}
-            else if (c->lds_tiles_be) launch(c, name_e, k_continuity<LPP, true, T>, ge, bp, c->clock.get(), q, c->grid, c->phys, s, t, c->walls, do_hist, tail, 0);
-            else launch(c, name_e, k_continuity<LPP, true, 0>, ge, bp, c->clock.get(), q, c->grid, c->phys, s, t, c->walls, do_hist, tail, 0);
-        }
-    }
-}
+// ---- The four neighbour passes on state view `s`, writing the end-of-step state through t.posn / veln / drhon ----
 
-void launch_physics_any(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, int do_hist, int only = 0, int dmode = 0,
-                        int tail = 0, int inner = 0)
+// What pass A does.  Sweep: sweeps the cells; SweepBuild: sweeps and writes the superset list (first step after a re-bin);
+// Walk: walks the superset list; DynBuildWalk (dynamic contexts): build and walk, each skipping itself according to the
+// clock's `fresh`; SlabWalk (slabs): the walk alone, on a grid that is not fresh
+enum class PassA { Sweep, SweepBuild, Walk, DynBuildWalk, SlabWalk };
+// The workgroups a slab's walk covers (slab_part_skips; the values are its `part`)
+enum class SlabPart { All = 0, Interior = 1, Boundary = 2 };
+// Pass E gets one workgroup more (the values are the kernels' `tail`), which advances the clock -- no k_clock_scan after
+// this step -- or leaves a slab's local maxima (slab_seal_tail)
+enum class Tail { None = 0, Clock = 1, SlabMaxima = 2 };
+// Dual-rate loop, compact kernels only: this launch of pass CD / E belongs to an inner sub-step -- CD does the pressure part
+// only, E hands the next sub-step its half-step density
+enum class Rate { Outer = 0, Inner = 1 };
+// Pass E's histogram of the new positions (the values are continuity_body's do_hist).  ThisStep: this step re-bins (static
+// schedule); hist_from_step(K): a dynamic context, from the K-th step since the last re-binning on
+enum class Hist : int { None = 0, ThisStep = 1 };
+Hist hist_from_step(int K) { return Hist(100 + K); }
+// The walk kernels' cond_fresh (density_pass): kAlways, kIfFresh, or "not on a fresh grid" with the slab part above it
+constexpr int kAlways = -1, kIfFresh = 1;
+int unless_fresh(SlabPart part) { return (int)part << kPassPartShift; }
+
+// f(std::integral_constant<int, LPP>) for the context's lanes per particle
+template <typename F>
+void with_lpp(const sphx_ctx *c, F &&f)
 {
     switch (c->lpp) {
-        case 1: launch_physics<1>(c, q, s, t, do_hist, only, dmode, tail, inner); break;
-        case 2: launch_physics<2>(c, q, s, t, do_hist, only, dmode, tail, inner); break;
-        case 4: launch_physics<4>(c, q, s, t, do_hist, only, dmode, tail, inner); break;
-        case 8: launch_physics<8>(c, q, s, t, do_hist, only, dmode, tail, inner); break;
-        case 16: launch_physics<16>(c, q, s, t, do_hist, only, dmode, tail, inner); break;
-        case 32: launch_physics<32>(c, q, s, t, do_hist, only, dmode, tail, inner); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        case 16: f(std::integral_constant<int, 16>{}); break;
+        case 32: f(std::integral_constant<int, 32>{}); break;
         default: throw Error(SPHX_ERR_ARG, "SPHX:Ctx:lpp", "lanes_per_particle must be 1,2,4,8,16 or 32");
     }
 }
 
-// exclusive scan of the cell histogram `count` into start_next (three kernels on big grids)
+// The form of a large-channel ("_w") kernel, handed to f as compile-time TILE / CODED: slot-coded lists (2 lanes per particle,
+// every pass with a tile: the CODED forms of the same kernels) on a tile of TILE_CODED slots, an LDS tile of TILE_LDS slots
+// (tile_ranges), or gathers from global memory
+template <int LPP, int TILE_CODED, int TILE_LDS, typename F>
+void with_form(const sphx_ctx *c, bool lds, F &&f)
+{
+    if constexpr (LPP == 2) {
+        if (c->coded_lists) { f(std::integral_constant<int, TILE_CODED>{}, std::true_type{}); return; }
+    }
+    if (lds) f(std::integral_constant<int, TILE_LDS>{}, std::false_type{});
+    else f(std::integral_constant<int, 0>{}, std::false_type{});
+}
+
+// every pass kernel takes (clock, q, grid, phys, S, temporaries, walls) first
+template <typename K, typename... X>
+void launch_pass(sphx_ctx *c, const char *name, K kernel, unsigned blocks, int q, const FluidSet &s, const FluidTmp &t, X... extra)
+{
+    launch(c, name, kernel, dim3(blocks), dim3(kBlock), c->clock.get(), q, c->grid, c->phys, s, t, c->walls, extra...);
+}
+
+// 16 / 32 lanes per particle (small channels) run the compact kernels (32-bit lists); fewer lanes (large channels) the "_w"
+// forms, see sphx_kernels.hpp -- fluid list entries are 16-bit index differences, so builders and walkers always go together.
+// LDS tiles: the force pass always; KGC and continuity where measured to pay (lds_tiles_be)
+void launch_pass_a(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, PassA mode, SlabPart part = SlabPart::All)
+{
+    const unsigned np = c->n_blocks_particles;
+    const bool walks = mode == PassA::Walk || mode == PassA::DynBuildWalk || mode == PassA::SlabWalk;
+    const bool sweeps = !walks || mode == PassA::DynBuildWalk;
+    const bool builds = mode == PassA::SweepBuild || mode == PassA::DynBuildWalk;
+    const char *sweep_name = builds ? "k_density_build" : "k_density";
+    const int cond_sweep = mode == PassA::DynBuildWalk ? kIfFresh : kAlways;
+    const int cond_walk = mode == PassA::Walk ? kAlways : unless_fresh(part);
+    with_lpp(c, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        if constexpr (LPP >= 16) {
+            if (mode == PassA::Sweep) launch_pass(c, sweep_name, k_density<LPP, 0>, np, q, s, t, cond_sweep);
+            else if (mode == PassA::SweepBuild && c->fold_rebin) launch_pass(c, sweep_name, k_density_zero<LPP>, np, q, s, t, cond_sweep);
+            else if (sweeps) launch_pass(c, sweep_name, k_density<LPP, 1>, np, q, s, t, cond_sweep);
+            if (walks) launch_pass(c, "k_density_walk", k_density<LPP, 2>, np, q, s, t, cond_walk);
+        } else {
+            // the cell sweep: mode 0 writes the step's list, mode 1 the superset list as well
+            // the build variant of a dynamic context is idle on four steps out of five: a grid-stride launch of an eighth
+            // of the workgroups costs an eighth to skip (6 M particles: 47 k idle workgroups were ~70 us of every step)
+            const unsigned nb = cond_sweep >= 0 ? std::max<unsigned>(1u, (unsigned)c->n_blocks_particles / 8u) : (unsigned)c->n_blocks_particles;
+            if (sweeps)
+                with_form<LPP, 0, 0>(c, false, [&](auto, auto coded) {
+                    constexpr bool CODED = decltype(coded)::value;
+                    if (builds) launch_pass(c, sweep_name, k_density_sweep_w<LPP, 1, CODED>, nb, q, s, t, cond_sweep, c->n_blocks_particles);
+                    else launch_pass(c, sweep_name, k_density_sweep_w<LPP, 0, CODED>, nb, q, s, t, cond_sweep, c->n_blocks_particles);
+                });
+            if (walks)
+                with_form<LPP, kSlotCodes, tile_slots(LPP)>(c, c->lds_tiles_a, [&](auto tile, auto coded) {
+                    launch_pass(c, "k_density_walk", k_density_w<LPP, decltype(tile)::value, decltype(coded)::value>, np, q, s, t, cond_walk);
+                });
+        }
+    });
+}
+
+void launch_pass_b(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t)
+{
+    const unsigned np = c->n_blocks_particles;
+    const int finish_half = c->fuse_ea ? 1 : 0;
+    with_lpp(c, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        if constexpr (LPP >= 16)
+            launch_pass(c, "k_kgc", k_kgc<LPP>, np, q, s, t, finish_half);
+        else
+            with_form<LPP, kSlotCodes, tile_slots(LPP)>(c, c->lds_tiles_be, [&](auto tile, auto coded) {
+                launch_pass(c, "k_kgc", k_kgc_w<LPP, decltype(tile)::value, decltype(coded)::value>, np, q, s, t, finish_half);
+            });
+    });
+}
+
+void launch_pass_cd(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Rate rate = Rate::Outer)
+{
+    const unsigned np = c->n_blocks_particles;
+    with_lpp(c, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        if constexpr (LPP >= 16) {
+            launch_pass(c, rate == Rate::Inner ? "k_forces_inner" : "k_forces", k_forces<LPP>, np, q, s, t, (int)rate);
+        } else {
+            auto forces = [&](auto tile, auto coded) {
+                launch_pass(c, "k_forces", k_forces_w<LPP, decltype(tile)::value, decltype(coded)::value>, np, q, s, t);
+            };
+            constexpr int TILE_LDS = LPP <= 2 ? 320 : tile_slots(LPP);
+            // (the whole layout, four workgroups per CU: with 320 slots, five per CU, a quarter of the neighbours came from
+            //  global memory in nearly every trip of every wave -- 6 M particles 516 -> 489 us, forces_tile_320 for the old size)
+            if (debug_switches().forces_tile == 320) with_form<LPP, 320, TILE_LDS>(c, c->lds_tiles, forces);
+            else with_form<LPP, kForceSlots, TILE_LDS>(c, c->lds_tiles, forces);
+        }
+    });
+}
+
+void launch_pass_e(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Tail tail = Tail::None, Hist hist = Hist::None,
+                   Rate rate = Rate::Outer)
+{
+    const unsigned ne = c->n_blocks_particles + (tail != Tail::None ? 1 : 0);
+    const char *name = rate == Rate::Inner ? "k_continuity_inner" : tail != Tail::None ? "k_continuity_clock" : "k_continuity";
+    with_lpp(c, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        if constexpr (LPP >= 16)
+            launch_pass(c, name, k_continuity<LPP, false, 0>, ne, q, s, t, (int)hist, (int)tail, (int)rate);
+        else
+            with_form<LPP, kSlotCodes, tile_slots(LPP)>(c, c->lds_tiles_be, [&](auto tile, auto coded) {
+                launch_pass(c, name, k_continuity<LPP, true, decltype(tile)::value, decltype(coded)::value>, ne, q, s, t, (int)hist, (int)tail, 0);
+            });
+    });
+}
+
+// all four, as the steps that launch every pass on its own run them
+void launch_passes(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, PassA mode, Tail tail = Tail::None, Hist hist = Hist::None)
+{
+    launch_pass_a(c, q, s, t, mode);
+    launch_pass_b(c, q, s, t);
+    launch_pass_cd(c, q, s, t);
+    launch_pass_e(c, q, s, t, tail, hist);
+}
+
+// `t` with its end-of-step outputs going straight into state view o
+FluidTmp writing_into(FluidTmp t, const FluidSet &o)
+{
+    t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
+    return t;
+}
+
+// Exclusive scan of the cell histogram `count` into start_next.  single(count, start, n, of_tiles) launches the one-workgroup
+// kernel that scans: the histogram itself or, on big grids, the tile sums between k_scan_tiles and k_scan_add
+template <typename F>
+void launch_scan_around(sphx_ctx *c, const Clock *clk, int q, const int *count, int *start_next, F &&single)
+{
+    if (!c->big_scan) { single(count, start_next, c->grid.ncells, false); return; }
+    int *tile_sum = c->tile.get(), *tile_off = c->tile.get() + c->n_tiles + 1;
+    launch(c, "k_scan_tiles", k_scan_tiles, dim3(c->n_tiles), dim3(kScanBlock), clk, q, count, start_next, tile_sum, c->grid.ncells);
+    single((const int *)tile_sum, tile_off, c->n_tiles, true);
+    launch(c, "k_scan_add", k_scan_add, dim3(c->n_tiles), dim3(kScanBlock), clk, q, start_next, (const int *)tile_off,
+           c->grid.ncells, c->n_tiles);
+}
 void launch_cell_scan(sphx_ctx *c, const Clock *clk, int q, const int *count, int *start_next)
 {
-    if (!c->big_scan) {
-        launch(c, "k_scan", k_scan_only, dim3(1), dim3(kScanBlock), clk, q, count, start_next, c->grid.ncells);
-    } else {
-        int *tile_sum = c->tile.get(), *tile_off = c->tile.get() + c->n_tiles + 1;
-        launch(c, "k_scan_tiles", k_scan_tiles, dim3(c->n_tiles), dim3(kScanBlock), clk, q, count, start_next, tile_sum,
-               c->grid.ncells);
-        launch(c, "k_scan_sums", k_scan_only, dim3(1), dim3(kScanBlock), clk, q, (const int *)tile_sum, tile_off, c->n_tiles);
-        launch(c, "k_scan_add", k_scan_add, dim3(c->n_tiles), dim3(kScanBlock), clk, q, start_next, (const int *)tile_off,
-               c->grid.ncells, c->n_tiles);
+    launch_scan_around(c, clk, q, count, start_next, [&](const int *cnt, int *start, int n, bool of_tiles) {
+        launch(c, of_tiles ? "k_scan_sums" : "k_scan", k_scan_only, dim3(1), dim3(kScanBlock), clk, q, cnt, start, n);
+    });
+}
+
+// What k_clock_scan gets besides the context's own (clock_scan_body, sphx_kernels.hpp); every default is "absent"
+struct ClockScan {
+    const double *vpart = nullptr;        // the per-block maxima of |v|^2 the kernel reduces ...
+    const double *vmax_global = nullptr;  // ... or (slabs) the all-reduced max |v| that replaces the reduction
+    const int *count = nullptr;           // the cell histogram ...
+    int *start_next = nullptr;            // ... and the cell starts it is scanned into (steps that re-bin)
+    const int *n_new = nullptr;           // slabs: the new particle count
+    const double *dpart = nullptr;        // the per-block maxima of the squared drift (grids with a skin)
+    int rebuilt = 0;                      // the step ends with a fresh grid
+    double half_skin = 0.0;
+    int *slab_counters = nullptr;
+    unsigned long long *vpart_reset = nullptr;
+    int dyn_K = 0;                        // dynamic contexts: the re-binning interval the clock decides rebuild_now by
+};
+// Finish the clock of step slot q -- and, where a.start_next is given, scan the cell histogram in the same single-workgroup kernel
+// (on big grids: the tile sums, between k_scan_tiles and k_scan_add)
+void launch_clock_scan(sphx_ctx *c, int q, ClockScan a)
+{
+    Clock *clk = c->clock.get();
+    // what k_clock_scan reduces: the per-block maxima, or (many blocks) their per-tile maxima
+    int n_red = a.vpart ? c->n_vpart : 0;
+    if (a.vpart && c->n_vtiles) {
+        double *vtile = c->vtile.get(), *dtile = vtile + c->n_vtiles;
+        launch(c, "k_max_tiles", k_max_tiles, dim3(c->n_vtiles), dim3(kScanBlock), (const Clock *)clk, q, c->n_vpart, a.vpart,
+               a.dpart, vtile, dtile);
+        a.vpart = vtile;
+        if (a.dpart) a.dpart = dtile;
+        n_red = c->n_vtiles;
     }
+    auto clock = [&](const int *cnt, int *start, int n, bool) {
+        launch(c, "k_clock_scan", k_clock_scan, dim3(1), dim3(kScanBlock), clk, q, c->phys, n_red, a.vpart, a.vmax_global,
+               (const int *)c->flags.get(), cnt, start, n, a.n_new, a.dpart, a.rebuilt, a.half_skin, a.slab_counters,
+               a.vpart_reset, a.dyn_K);
+    };
+    if (a.start_next) launch_scan_around(c, clk, q, a.count, a.start_next, clock);  // clock update and cell scan share one single-block kernel
+    else clock(nullptr, nullptr, 0, false);
 }
 
 // index -> cell slot, then the gather of the persistent fields into destination view d
@@ -549,26 +635,12 @@ void launch_scatter_reorder(sphx_ctx *c, const Clock *clk, int q, const ReorderA
            (const int *)c->perm.get(), ra);
 }
 
-template <int LPP>
-void launch_fused_ea_t(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &sn, const FluidTmp &tn, int tail)
-{
-    launch(c, "k_continuity_density", k_continuity_density<LPP>, dim3(2 * c->n_blocks_particles + tail), dim3(kBlock),
-           c->clock.get(), q, c->grid, c->phys, s, t, c->walls, sn, tn, tail);
-}
-template <int LPP>
-void launch_fused_ea_w(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &sn, const FluidTmp &tn, int tail)
-{
-    launch(c, "k_continuity_density", k_continuity_density_w<LPP>, dim3(2 * c->n_blocks_particles + tail), dim3(kBlock),
-           c->clock.get(), q, c->grid, c->phys, s, t, c->walls, sn, tn, tail);
-}
 // The folded re-binning step (sphx_ctx::fold_rebin): pass CD with the histogram, then pass E re-binning into view d
 template <int LPP>
 void launch_fold_rebin_t(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &d)
 {
-    const dim3 gp(c->n_blocks_particles), bp(kBlock);
-    launch(c, "k_forces_hist", k_forces_hist<LPP>, gp, bp, (const Clock *)c->clock.get(), q, c->grid, c->phys, s, t, c->walls, 0);
-    launch(c, "k_continuity_rebin", k_continuity_rebin<LPP>, dim3(c->n_blocks_particles + 1), bp, c->clock.get(), q, c->grid,
-           c->phys, s, t, c->walls, d);
+    launch_pass(c, "k_forces_hist", k_forces_hist<LPP>, c->n_blocks_particles, q, s, t, 0);
+    launch_pass(c, "k_continuity_rebin", k_continuity_rebin<LPP>, c->n_blocks_particles + 1, q, s, t, d);
 }
 void launch_fold_rebin(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &d)
 {
@@ -578,15 +650,16 @@ void launch_fold_rebin(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t,
         default: throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fold", "internal: folded re-binning step at this lane count");
     }
 }
-// tail = 0: without the clock workgroup (kernel timing)
-void launch_fused_ea(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &sn, const FluidTmp &tn, int tail = 1)
+// Pass E of a step and pass A of the next in one launch.  Tail::None: without the clock workgroup (kernel timing)
+void launch_fused_ea(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &sn, const FluidTmp &tn, Tail tail = Tail::Clock)
 {
+    auto go = [&](auto kernel) { launch_pass(c, "k_continuity_density", kernel, 2 * c->n_blocks_particles + (int)tail, q, s, t, sn, tn, (int)tail); };
     switch (c->lpp) {  // 16 / 32 lanes per particle: the compact kernels; fewer: their large-channel forms
-        case 2: launch_fused_ea_w<2>(c, q, s, t, sn, tn, tail); break;
-        case 4: launch_fused_ea_w<4>(c, q, s, t, sn, tn, tail); break;
-        case 8: launch_fused_ea_w<8>(c, q, s, t, sn, tn, tail); break;
-        case 16: launch_fused_ea_t<16>(c, q, s, t, sn, tn, tail); break;
-        case 32: launch_fused_ea_t<32>(c, q, s, t, sn, tn, tail); break;
+        case 2: go(k_continuity_density_w<2>); break;
+        case 4: go(k_continuity_density_w<4>); break;
+        case 8: go(k_continuity_density_w<8>); break;
+        case 16: go(k_continuity_density<16>); break;
+        case 32: go(k_continuity_density<32>); break;
         default: throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fuse", "internal: fused E|A launch at this lane count");
     }
 }
@@ -595,98 +668,68 @@ void launch_fused_ea(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, c
 // (7 launches); otherwise the passes write the new state straight into S[1-q] and the layout stays (5 launches).
 void launch_step(sphx_ctx *c, int q, int l, int pos, bool rebuild)
 {
-    Clock *clk = c->clock.get();
-    const int dmode = c->skin > 0.0 ? (pos == 0 ? 1 : 2) : 0;
+    const PassA mode = c->skin > 0.0 ? (pos == 0 ? PassA::SweepBuild : PassA::Walk) : PassA::Sweep;
     const FluidSet s = c->view(q, l);
-    const bool track = c->skin > 0.0;
-    const double *dpart = track ? (const double *)c->dpart.get() : nullptr;
-    // what k_clock_scan reduces: the per-block maxima, or (many blocks) their per-tile maxima
-    const double *vsrc = c->vpart.get();
-    int n_red = c->n_vpart;
-    const double *dpart_blocks = dpart;  // the per-block array (dpart is redirected to the tiles below)
-    auto pre_reduce = [c, clk, q, dpart_blocks]() {
-        if (c->n_vtiles == 0) return;
-        launch(c, "k_max_tiles", k_max_tiles, dim3(c->n_vtiles), dim3(kScanBlock), (const Clock *)clk, q, c->n_vpart,
-               (const double *)c->vpart.get(), dpart_blocks, c->vtile.get(), c->vtile.get() + c->n_vtiles);
-    };
-    if (c->n_vtiles) {
-        vsrc = c->vtile.get();
-        if (dpart) dpart = c->vtile.get() + c->n_vtiles;
-        n_red = c->n_vtiles;
-    }
+    ClockScan clock;
+    clock.vpart = c->vpart.get();
+    if (c->skin > 0.0) clock.dpart = c->dpart.get();
+    clock.half_skin = c->half_skin();
+    clock.vpart_reset = c->vpart_reset();
     // Dual-rate loop: passes CD and E of the inner sub-steps 1 .. n_in-1 (CD of sub-step 0 comes first, E of the last
     // sub-step after).  Sub-step m reads the velocities W_m and writes W_m+1; the W alternate between the step's output
     // array and vel2 so that the last one lands in the output array.
     auto inner_substeps = [c, q, &s](FluidTmp &t) {
-        if (c->n_in <= 1) { launch_physics_any(c, q, s, t, 0, 3); return; }
-        double2 *const w_final = t.veln;
+        double2 *const w_final = t.veln;  // (n_in = 1: W_1 is the output array, pass CD alone)
         auto w_of = [&](int m) { return ((c->n_in - m) & 1) ? c->vel2.get() : w_final; };  // W_m, m = 1 .. n_in
         FluidSet sm = s;
         t.veln = w_of(1);
-        launch_physics_any(c, q, sm, t, 0, 3);
+        launch_pass_cd(c, q, sm, t);
         for (int m = 1; m < c->n_in; ++m) {
-            launch_physics_any(c, q, sm, t, 0, 4, 0, 0, 1);  // E of sub-step m-1: rho, drho and the next half-step state
+            launch_pass_e(c, q, sm, t, Tail::None, Hist::None, Rate::Inner);  // E of sub-step m-1: rho, drho and the next half-step state
             sm.vel = w_of(m);
             t.veln = w_of(m + 1);
-            launch_physics_any(c, q, sm, t, 0, 3, 0, 0, 1);  // CD of sub-step m (pressure part)
+            launch_pass_cd(c, q, sm, t, Rate::Inner);  // CD of sub-step m (pressure part)
         }
     };
     if (!rebuild && c->fuse_ea) {
         // pass A of this step ran inside the previous step's last launch, unless this is the first step on a fresh grid
-        FluidTmp t = c->tmp_par[q], tn = c->tmp_par[1 - q];
         const FluidSet o = c->view(1 - q, l);
-        t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
-        if (pos == 0) launch_physics_any(c, q, s, t, 0, 1, 1);
-        launch_physics_any(c, q, s, t, 0, 2);
+        FluidTmp t = writing_into(c->tmp_par[q], o);
+        if (pos == 0) launch_pass_a(c, q, s, t, PassA::SweepBuild);
+        launch_pass_b(c, q, s, t);
         inner_substeps(t);
-        launch_fused_ea(c, q, s, t, o, tn);
+        launch_fused_ea(c, q, s, t, o, c->tmp_par[1 - q]);
         return;
     }
     if (!rebuild) {
-        FluidTmp t = c->tmp;
-        const FluidSet o = c->view(1 - q, l);
-        t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
+        const FluidTmp t = writing_into(c->tmp, c->view(1 - q, l));
         if (c->tail_clock) {  // 4 launches: the last workgroup of pass E advances the clock
-            launch_physics_any(c, q, s, t, 0, 0, dmode, 1);
+            launch_passes(c, q, s, t, mode, Tail::Clock);
             return;
         }
-        launch_physics_any(c, q, s, t, 0, 0, dmode);
-        pre_reduce();
-        launch(c, "k_clock_scan", k_clock_scan, dim3(1), dim3(kScanBlock), clk, q, c->phys, n_red,
-               vsrc, (const double *)nullptr, (const int *)c->flags.get(), (const int *)nullptr,
-               (int *)nullptr, 0, (const int *)nullptr, dpart, 0, c->half_skin(), (int *)nullptr, c->vpart_reset(), 0);
+        launch_passes(c, q, s, t, mode);
+        launch_clock_scan(c, q, clock);
         return;
     }
     if (c->fuse_ea) {  // re-binning step: pass A came with the previous step (or stands alone at pos 0), E has a launch of its own
         FluidTmp t = c->tmp_par[q];
-        if (pos == 0) launch_physics_any(c, q, s, t, 1, 1, 1);
-        launch_physics_any(c, q, s, t, 1, 2);
+        if (pos == 0) launch_pass_a(c, q, s, t, PassA::SweepBuild);
+        launch_pass_b(c, q, s, t);
         if (c->fold_rebin) {  // three launches: the histogram rides in pass CD, re-binning and clock in pass E
             launch_fold_rebin(c, q, s, t, c->view(1 - q, 1 - l));
             return;
         }
         inner_substeps(t);
-        launch_physics_any(c, q, s, t, 1, 4);
+        launch_pass_e(c, q, s, t, Tail::None, Hist::ThisStep);
     } else {
-        launch_physics_any(c, q, s, c->tmp, 1, 0, dmode);
+        launch_passes(c, q, s, c->tmp, mode, Tail::None, Hist::ThisStep);
     }
-    pre_reduce();
     const FluidSet d = c->view(1 - q, 1 - l);
-    if (!c->big_scan) {  // clock update and cell scan share one single-block kernel
-        launch(c, "k_clock_scan", k_clock_scan, dim3(1), dim3(kScanBlock), clk, q, c->phys, n_red,
-               vsrc, (const double *)nullptr, (const int *)c->flags.get(),
-               (const int *)c->count.get(), d.start, c->grid.ncells, (const int *)nullptr, dpart, 1, c->half_skin(), (int *)nullptr, c->vpart_reset(), 0);
-    } else {
-        int *tile_sum = c->tile.get(), *tile_off = c->tile.get() + c->n_tiles + 1;
-        launch(c, "k_scan_tiles", k_scan_tiles, dim3(c->n_tiles), dim3(kScanBlock), (const Clock *)clk, q,
-               (const int *)c->count.get(), d.start, tile_sum, c->grid.ncells);
-        launch(c, "k_clock_scan", k_clock_scan, dim3(1), dim3(kScanBlock), clk, q, c->phys, n_red,
-               vsrc, (const double *)nullptr, (const int *)c->flags.get(), (const int *)tile_sum,
-               tile_off, c->n_tiles, (const int *)nullptr, dpart, 1, c->half_skin(), (int *)nullptr, c->vpart_reset(), 0);
-        launch(c, "k_scan_add", k_scan_add, dim3(c->n_tiles), dim3(kScanBlock), (const Clock *)clk, q, d.start,
-               (const int *)tile_off, c->grid.ncells, c->n_tiles);
-    }
-    launch_scatter_reorder(c, clk, q, reorder_args(c->tmp.posn, c->tmp.veln, c->tmp.drhon, s.mass, s.id, d, c->tmp.src_of), d);
+    clock.count = c->count.get();
+    clock.start_next = d.start;
+    clock.rebuilt = 1;
+    launch_clock_scan(c, q, clock);
+    launch_scatter_reorder(c, c->clock.get(), q, reorder_args(c->tmp.posn, c->tmp.veln, c->tmp.drhon, s.mass, s.id, d, c->tmp.src_of), d);
 }
 
 // One step slot of a dynamic context: the four passes on S[q] writing the new state into S[1-q], the clock (which
@@ -696,19 +739,13 @@ void launch_step_dyn(sphx_ctx *c, int q)
 {
     Clock *clk = c->clock.get();
     const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
-    FluidTmp t = c->tmp;
-    t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
-    launch_physics_any(c, q, s, t, 100 + c->rebuild_every, 0, 3);
-    const double *vsrc = c->vpart.get(), *dsrc = c->dpart.get();
-    int n_red = c->n_vpart;
-    if (c->n_vtiles) {
-        launch(c, "k_max_tiles", k_max_tiles, dim3(c->n_vtiles), dim3(kScanBlock), (const Clock *)clk, q, c->n_vpart,
-               (const double *)c->vpart.get(), (const double *)c->dpart.get(), c->vtile.get(), c->vtile.get() + c->n_vtiles);
-        vsrc = c->vtile.get(); dsrc = c->vtile.get() + c->n_vtiles; n_red = c->n_vtiles;
-    }
-    launch(c, "k_clock_scan", k_clock_scan, dim3(1), dim3(kScanBlock), clk, q, c->phys, n_red, vsrc, (const double *)nullptr,
-           (const int *)c->flags.get(), (const int *)nullptr, (int *)nullptr, 0, (const int *)nullptr, dsrc, 0, c->half_skin(),
-           (int *)nullptr, (unsigned long long *)nullptr, c->rebuild_every);
+    launch_passes(c, q, s, writing_into(c->tmp, o), PassA::DynBuildWalk, Tail::None, hist_from_step(c->rebuild_every));
+    ClockScan clock;
+    clock.vpart = c->vpart.get();
+    clock.dpart = c->dpart.get();
+    clock.half_skin = c->half_skin();
+    clock.dyn_K = c->rebuild_every;
+    launch_clock_scan(c, q, clock);
     const int qf = q | kOnlyIfRebuild;
     const int kDynBlocks = 4096;  // grid-stride kernels: a launch that skips costs ~3 us instead of an empty 24k-block grid
     const dim3 g1(std::min(c->n_blocks_flat, kDynBlocks)), bp(kBlock);
@@ -2344,7 +2381,7 @@ void slab_compute_impl(sphx_ctx *c, double *send_left_dev, double *send_right_de
     const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
     auto body = [&]() {
-        launch_physics_any(c, q, c->view(q, q), c->tmp, 0);
+        launch_passes(c, q, c->view(q, q), c->tmp, PassA::Sweep);
         SlabPack p = c->pack;
         p.send_l = send_left_dev;
         p.send_r = send_right_dev;
@@ -2371,20 +2408,14 @@ void slab_finish_impl(sphx_ctx *c, const double *recv_left_dev, const double *re
         // and the reset of the pack counters.  It arms run[1-q]; the remaining kernels of this slot still test
         // run[q], and from here on clk->n is the new particle count.
         const FluidSet d = c->view(1 - q, 1 - q);
-        if (!c->big_scan) {
-            launch(c, "k_clock_scan", k_clock_scan, dim3(1), dim3(kScanBlock), clk, q, c->phys, 0, (const double *)nullptr,
-                   vmax_global_dev, (const int *)c->flags.get(), (const int *)c->count.get(), d.start, c->grid.ncells,
-                   (const int *)c->n_new.get(), (const double *)nullptr, 1, 0.0, c->counters.get(), (unsigned long long *)nullptr, 0);
-        } else {
-            int *tile_sum = c->tile.get(), *tile_off = c->tile.get() + c->n_tiles + 1;
-            launch(c, "k_scan_tiles", k_scan_tiles, dim3(c->n_tiles), dim3(kScanBlock), (const Clock *)clk, q,
-                   (const int *)c->count.get(), d.start, tile_sum, c->grid.ncells);
-            launch(c, "k_clock_scan", k_clock_scan, dim3(1), dim3(kScanBlock), clk, q, c->phys, 0, (const double *)nullptr,
-                   vmax_global_dev, (const int *)c->flags.get(), (const int *)tile_sum, tile_off, c->n_tiles,
-                   (const int *)c->n_new.get(), (const double *)nullptr, 1, 0.0, c->counters.get(), (unsigned long long *)nullptr, 0);
-            launch(c, "k_scan_add", k_scan_add, dim3(c->n_tiles), dim3(kScanBlock), (const Clock *)clk, q, d.start,
-                   (const int *)tile_off, c->grid.ncells, c->n_tiles);
-        }
+        ClockScan clock;
+        clock.vmax_global = vmax_global_dev;
+        clock.count = c->count.get();
+        clock.start_next = d.start;
+        clock.n_new = c->n_new.get();
+        clock.rebuilt = 1;
+        clock.slab_counters = c->counters.get();
+        launch_clock_scan(c, q, clock);
         launch_scatter_reorder(c, clk, q,
                                reorder_args(c->kpos.get(), c->kvel.get(), c->kdrho.get(), c->kmass.get(), c->kid.get(), d, nullptr), d);
     };
@@ -2757,64 +2788,53 @@ FluidSet slab_new_state(sphx_ctx *c) { return c->view(1 - c->sched.cur, 0); }  /
 
 constexpr int kTicketBlocks = 1024;  // largest grid of the kernels that end with last_workgroup_out (~20 ns per ticket)
 
+// the step slot of parity q: S[q], and the passes' temporaries writing the new state into S[1-q]
+struct SlabSlot {
+    const int q;
+    const FluidSet s, o;
+    FluidTmp t;
+    SlabSlot(sphx_ctx *c, int q_) : q(q_), s(c->view(q_, 0)), o(c->view(1 - q_, 0)), t(writing_into(c->tmp, o)) {}
+};
+
 void slab_phase1(sphx_ctx *c)  // passes A..E into S[1-q]; the tail workgroup of pass E leaves the local maxima in vmax_l[0..1]
 {
-    const int q = c->sched.cur;
-    const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
-    FluidTmp t = c->tmp;
-    t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
-    t.seal_out = c->vmax_l.get();
-    launch_physics_any(c, q, s, t, 0, 0, 3, 2);
+    SlabSlot k(c, c->sched.cur);
+    k.t.seal_out = c->vmax_l.get();
+    launch_passes(c, k.q, k.s, k.t, PassA::DynBuildWalk, Tail::SlabMaxima);
 }
 
 // ... in three pieces (contexts with a second stream, see sphx_ctx::stream2): passes A, B, CD on the slab's stream; the local
 // maxima -- both exist once pass CD is through -- on `aux`, where the all-reduce follows them; pass E, without a tail, on the
 // slab's stream again, beside the two
-// pass A of the step slot of parity q on S[q]: dmode 3 = the cell sweep (fresh grid only) and the walk of `part` (0 all,
-// 1 interior, 2 boundary workgroups, see slab_part_skips); dmode 4 = that walk alone
-void slab_pass_a(sphx_ctx *c, int q, int dmode, int part)
-{
-    const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
-    FluidTmp t = c->tmp;
-    t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
-    c->pass_a_part = part;
-    launch_physics_any(c, q, s, t, 0, 1, dmode);
-    c->pass_a_part = 0;
-}
 void slab_phase1_abc(sphx_ctx *c)
 {
-    const int q = c->sched.cur;
-    const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
-    FluidTmp t = c->tmp;
-    t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
+    const SlabSlot k(c, c->sched.cur);
     // (the interior workgroups of this pass A may have run already, behind the previous step's pack3: slab_pass_a_interior)
-    slab_pass_a(c, q, 3, c->a_interior_done ? 2 : 0);
+    launch_pass_a(c, k.q, k.s, k.t, PassA::DynBuildWalk, c->a_interior_done ? SlabPart::Boundary : SlabPart::All);
     c->a_interior_done = false;
-    launch_physics_any(c, q, s, t, 0, 2);
-    launch_physics_any(c, q, s, t, 0, 3);
+    launch_pass_b(c, k.q, k.s, k.t);
+    launch_pass_cd(c, k.q, k.s, k.t);
 }
 // message A of the step just taken is packed, the clock advanced, the host's parity flipped (slab_phase4): the interior
-// workgroups of the NEXT step's pass A need nothing the exchange brings -- they run while it is under way
-void slab_pass_a_interior(sphx_ctx *c)
+// workgroups of the NEXT step's pass A (the step slot of parity q) need nothing the exchange brings -- they run while it is
+// under way
+void slab_pass_a_interior(sphx_ctx *c, int q)
 {
-    slab_pass_a(c, c->sched.cur, 4, 1);
+    const SlabSlot k(c, q);
+    launch_pass_a(c, k.q, k.s, k.t, PassA::SlabWalk, SlabPart::Interior);
     c->a_interior_done = true;
 }
 void slab_local_maxima_of_step(sphx_ctx *c, hipStream_t aux)
 {
-    const int q = c->sched.cur;
-    const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
-    hipLaunchKernelGGL(k_slab_maxima, dim3(kSlabMaxBlocks), dim3(kBlock), 0, aux, (const Clock *)c->clock.get(), q, c->grid,
-                       c->n_vpart, (const double *)c->dpart.get(), (const double2 *)o.vel, (const int *)s.cell, c->max_part.get(),
+    const SlabSlot k(c, c->sched.cur);
+    hipLaunchKernelGGL(k_slab_maxima, dim3(kSlabMaxBlocks), dim3(kBlock), 0, aux, (const Clock *)c->clock.get(), k.q, c->grid,
+                       c->n_vpart, (const double *)c->dpart.get(), (const double2 *)k.o.vel, (const int *)k.s.cell, c->max_part.get(),
                        c->vmax_l.get(), c->ticket2.get());
 }
 void slab_phase1_e(sphx_ctx *c)
 {
-    const int q = c->sched.cur;
-    const FluidSet s = c->view(q, 0), o = c->view(1 - q, 0);
-    FluidTmp t = c->tmp;
-    t.posn = o.pos; t.veln = o.vel; t.drhon = o.drho;
-    launch_physics_any(c, q, s, t, 0, 4);
+    const SlabSlot k(c, c->sched.cur);
+    launch_pass_e(c, k.q, k.s, k.t);
 }
 
 void slab_phase2(sphx_ctx *c)  // global maxima known: re-binning decision, message A, clock -- one launch
@@ -2951,7 +2971,7 @@ struct RcclLoop {
             }
             SPHX_HIP(hipEventRecord(c->ev_u, c->stream2));
             slab_phase4(c);
-            slab_pass_a_interior(c);
+            slab_pass_a_interior(c, c->sched.cur);
             SPHX_HIP(hipStreamWaitEvent(st, c->ev_u, 0));
         } else if (c->stream2) {  // (under stream capture: the same pieces in one chain)
             slab_phase1_abc(c);
@@ -3049,8 +3069,7 @@ struct GroupLoop {
                 // workgroups of the next step's pass A, which the neighbours need not wait for (the in-process ring keeps the
                 // copies that stand in for the exchange on the slab's own stream: what it tests is the split itself)
                 if (!serial) SPHX_HIP(hipEventRecord(c->ev_received, c->stream));
-                slab_pass_a(c, 1 - c->sched.cur, 4, 1);
-                c->a_interior_done = true;
+                slab_pass_a_interior(c, 1 - c->sched.cur);
             }
         } else {
         for (int r = 0; r < n; ++r) {
@@ -3357,13 +3376,13 @@ SPHX_EXPORT int sphx_ctx_time_kernel(sphx_ctx *c, const char *name, int reps, do
     require(c != nullptr && name != nullptr && avg_ms != nullptr && reps > 0, "SPHX:Ctx:null", "bad arguments");
     require(!c->is_slab, "SPHX:Ctx:slab", "not available on a slab context");
     const std::string n(name);
-    int only = 0;
-    if (n == "k_density" || n == "k_density_build" || n == "k_density_walk" || n == "k_density_dyn") only = 1;
-    else if (n == "k_kgc") only = 2;
-    else if (n == "k_forces") only = 3;
-    else if (n == "k_continuity" || n == "k_continuity_clock") only = 4;
-    else if (n == "k_continuity_density" && c->fuse_ea) only = 5;  // pass E and the next pass A in one launch
-    require(only != 0, "SPHX:Ctx:kernel", "time_kernel knows k_density, k_kgc, k_forces, k_continuity (and k_continuity_density)");
+    enum class Pass { None, A, B, CD, E, EA } pass = Pass::None;
+    if (n == "k_density" || n == "k_density_build" || n == "k_density_walk" || n == "k_density_dyn") pass = Pass::A;
+    else if (n == "k_kgc") pass = Pass::B;
+    else if (n == "k_forces") pass = Pass::CD;
+    else if (n == "k_continuity" || n == "k_continuity_clock") pass = Pass::E;
+    else if (n == "k_continuity_density" && c->fuse_ea) pass = Pass::EA;  // pass E and the next pass A in one launch
+    require(pass != Pass::None, "SPHX:Ctx:kernel", "time_kernel knows k_density, k_kgc, k_forces, k_continuity (and k_continuity_density)");
     read_clock(c);
     if (c->h_clock->need_rebuild && c->h_clock->status == 0) forced_rebuild(c);
     const bool prof = c->profiling;
@@ -3374,26 +3393,27 @@ SPHX_EXPORT int sphx_ctx_time_kernel(sphx_ctx *c, const char *name, int reps, do
     try {
         // arm run[cur] so the kernels execute; no step slot follows, so the clock does not advance
         arm_clock(c, c->prm.t_end, (long long)1, c->sched.cur, (const double *)nullptr);
-        const FluidSet fs = c->view(c->sched.cur, c->sched.lay);
-        const int dmode = c->dyn ? 3 : (c->skin > 0.0 ? (c->sched.pos == 0 ? 1 : 2) : 0);
-        const FluidTmp &tt = c->tmp_par[c->fuse_ea ? c->sched.cur : 0];  // (fuse_ea: the records / list of the current state parity)
+        const int q = c->sched.cur;
+        const FluidSet fs = c->view(q, c->sched.lay);
+        const PassA mode = c->dyn ? PassA::DynBuildWalk
+                                  : (c->skin > 0.0 ? (c->sched.pos == 0 ? PassA::SweepBuild : PassA::Walk) : PassA::Sweep);
+        const FluidTmp &tt = c->tmp_par[c->fuse_ea ? q : 0];  // (fuse_ea: the records / list of the current state parity)
         // make every temporary the timed kernel reads valid.  Where pass A of the coming step came with the last step's final
         // launch its list and records are there already, and stay: a timing call should not change what follows (the
         // stand-alone pass is a different kernel and may round differently in the last bit).
-        if (c->fuse_ea && c->sched.pos != 0) {
-            for (int pass = 2; pass <= 4; ++pass) launch_physics_any(c, c->sched.cur, fs, tt, 0, pass, dmode);
-        } else {
-            launch_physics_any(c, c->sched.cur, fs, tt, 0, 0, dmode);
-        }
+        if (!(c->fuse_ea && c->sched.pos != 0)) launch_pass_a(c, q, fs, tt, mode);
+        launch_pass_b(c, q, fs, tt);
+        launch_pass_cd(c, q, fs, tt);
+        launch_pass_e(c, q, fs, tt);
         SPHX_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         for (int k = 0; k < reps; ++k) {
-            if (only == 5) {  // (writes the other parity's list / records and the other state's drho: all rewritten by the next step)
-                FluidTmp te = tt;
-                const FluidSet o = c->view(1 - c->sched.cur, c->sched.lay);
-                te.posn = o.pos; te.veln = o.vel; te.drhon = o.drho;
-                launch_fused_ea(c, c->sched.cur, fs, te, o, c->tmp_par[1 - c->sched.cur], 0);
-            } else {
-                launch_physics_any(c, c->sched.cur, fs, tt, 0, only, dmode);
+            if (pass == Pass::A) launch_pass_a(c, q, fs, tt, mode);
+            else if (pass == Pass::B) launch_pass_b(c, q, fs, tt);
+            else if (pass == Pass::CD) launch_pass_cd(c, q, fs, tt);
+            else if (pass == Pass::E) launch_pass_e(c, q, fs, tt);
+            else {  // Pass::EA (writes the other parity's list / records and the other state's drho: all rewritten by the next step)
+                const FluidSet o = c->view(1 - q, c->sched.lay);
+                launch_fused_ea(c, q, fs, writing_into(tt, o), o, c->tmp_par[1 - q], Tail::None);
             }
         }
         SPHX_HIP(hipStreamEndCapture(c->stream, &g));
