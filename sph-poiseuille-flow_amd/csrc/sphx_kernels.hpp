@@ -508,6 +508,24 @@ __device__ __forceinline__ int wrap_index(int k, int n) { return k < 0 ? k + n :
     const bool in_cap = i < t.cap
 #define SPHX_PASS_INDEX() SPHX_PASS_INDEX_AT((int)blockIdx.x, (int)gridDim.x)
 
+// Compact kernels at 16 and 32 lanes per particle (kRowsAhead): a pass is a chain of dependent memory round trips behind a launch,
+// so what it asks for has to leave in as few request waves as there are true dependences:
+//   wave 1 (behind the arguments): the clock's words, the particle's own records, the row count and the first rows of the list;
+//   wave 2 (behind the rows): the neighbour records of ALL of those rows, before the first one is used.
+// Left alone, the compiler sinks a load into the branch that uses its value -- the rows behind the count, row 1's records
+// behind row 0's arithmetic -- and every sunk load is one more round trip on the critical path.  requests_issued() closes a
+// wave: loads cannot move across it (to the compiler it may write memory), and it costs no instruction and no wait.
+// A lane that does not own a prefetched row asks for its own particle's records instead: rows beyond a lane's count hold
+// stale words, and no address is ever formed from one.  The arithmetic stays in row order, so every sum keeps its bits.
+// The arguments come first: a pass reads 25-40 of the ~220 dwords of its kernels' argument segment, and the compiler loads each
+// where it is first used -- six to twelve scalar round trips, one behind the other, before wave 1 has left.  Every pass
+// therefore opens with SPHX_WAVE1_ARGS(...), an empty asm statement that takes as scalar operands the arguments wave 1 forms
+// its addresses from: their loads leave together and one wait covers them.  The rest is loaded as before, further down.
+template <int LPP>
+constexpr bool kRowsAhead = LPP >= 16;
+__device__ __forceinline__ void requests_issued() { asm volatile("" ::: "memory"); }
+#define SPHX_WAVE1_ARGS(...) asm volatile("" ::__VA_ARGS__)
+
 // ---------------------------------------------------------------------------------------------
 // pass A: candidate sweep -> neighbour list; number-density summation -> rho, Vol
 // (mex/sph_physics_mex.c:188-234) and the half-step density/pressure of integration_1st's pre-pass
@@ -522,7 +540,9 @@ template <int LPP, int MODE>
 __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                              const FluidTmp &t, const Walls &w, int bid, int nblk, bool half)
 {
-
+    if (MODE == 2 && kRowsAhead<LPP>)
+        SPHX_WAVE1_ARGS("s"(clk), "s"(q), "s"(s.pos), "s"(s.cell), "s"(s.mass), "s"(s.drho), "s"(t.cap), "s"(t.sl_cnt), "s"(t.sl_idx),
+                        "s"(t.nl_stride));
     SPHX_PASS_INDEX_AT(bid, nblk);
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
     const int ci = in_cap ? s.cell[i] : 0;
@@ -530,15 +550,24 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
     const double mass_i = lead ? s.mass[i] : 1.0, drho_i = lead ? s.drho[i] : 0.0;
     // list-walking variant: row count and the first two rows are requested here as well (a lane rarely owns more
     // at 32 lanes per particle): count -> entry -> position becomes {count, entries} -> position
-    int ns = 0, e_row0 = 0, e_row1 = 0;
+    // (kRowsAhead: the first kAhead rows -- 64 candidates; the superset list holds about 48 of them at skin 1.05 h, so three
+    //  rows for every lane at 16 lanes per particle and a fourth for some -- and the clock's words in the same wave)
+    constexpr int kAhead = (MODE == 2 && kRowsAhead<LPP>) ? 64 / LPP : 2;
+    int ns = 0, e_row0 = 0, e_row1 = 0, e_row2 = 0, e_row3 = 0;
     if (MODE == 2) {
         ns = list_rows(t.sl_cnt[tid]);
         e_row0 = t.sl_idx[tid];
         e_row1 = t.sl_idx[(size_t)t.nl_stride + tid];
+        if (kAhead > 2) {
+            e_row2 = t.sl_idx[2 * (size_t)t.nl_stride + tid];
+            e_row3 = t.sl_idx[3 * (size_t)t.nl_stride + tid];
+        }
     }
     const double dt = clk->dt;
-    if (!clk->run[q]) return;
-    const bool active = i < clk->n;
+    const int run_q = clk->run[q], n_now = clk->n;
+    if (MODE == 2 && kRowsAhead<LPP>) requests_issued();
+    if (!run_q) return;
+    const bool active = i < n_now;
     double s_in = 0.0, s_ct = 0.0;
     int cnt = 0, scnt = 0, cnt_fl = 0, scnt_fl = 0;
     const int lane = threadIdx.x & 63, gbase = lane & ~(LPP - 1);
@@ -591,15 +620,11 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
         const int rows = group_extreme<LPP, true>(ns);  // (= lane 0's: it owns the most rows)
         if (active) {
             const double xi = pi.x, yi = pi.y;
-            for (int m = 0; m < rows; ++m) {
+            // one candidate (has: this lane owns the row; e = 0 where it does not)
+            auto test = [&](bool has, int e, const double2 pj, double Volw) {
                 bool acc = false;
-                int e = 0;
-                if (m < ns) {
-                    e = m == 0 ? e_row0 : (m == 1 ? e_row1 : t.sl_idx[(size_t)m * t.nl_stride + tid]);
+                if (has) {
                     const bool wall = (e & kWallBit) != 0;
-                    const int k = e & (kWallBit - 1);
-                    const double2 pj = (wall ? w.pos : (const double2 *)s.pos)[k];
-                    const double Volw = wall ? w.a[k].x : 0.0;  // requested with the position, not after the distance test
                     const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
                     const double r2 = dx * dx + dy * dy;
                     if (r2 > kR2Min && r2 < ph.kc.rcut2) {
@@ -619,6 +644,40 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
                     cnt_fl += LPP == 1 ? ((acc && !wall_row) ? 1 : 0) : __popc(group_bits(acc && !wall_row));
                     push(acc, e);
                 }
+            };
+            if (kRowsAhead<LPP>) {
+                // the positions of all prefetched rows in one wave (Vol of a wall candidate with them; a fluid row re-reads its
+                // position's first word there, so that the request needs no branch)
+                int e_pre[kAhead];
+                double2 p_pre[kAhead];
+                double v_pre[kAhead];
+#pragma unroll
+                for (int m = 0; m < kAhead; ++m) {
+                    const int e_m = m == 0 ? e_row0 : (m == 1 ? e_row1 : (m == 2 ? e_row2 : e_row3));
+                    e_pre[m] = m < ns ? e_m : 0;
+                    const bool wall = (e_pre[m] & kWallBit) != 0;
+                    const int k = m < ns ? (e_pre[m] & (kWallBit - 1)) : i;
+                    const double2 *pp = (wall ? w.pos : (const double2 *)s.pos) + k;
+                    p_pre[m] = *pp;
+                    v_pre[m] = *(wall ? &w.a[k].x : &pp->x);
+                }
+                requests_issued();
+#pragma unroll
+                for (int m = 0; m < kAhead; ++m)
+                    if (m < rows) test(m < ns, e_pre[m], p_pre[m], v_pre[m]);
+            }
+            for (int m = kRowsAhead<LPP> ? kAhead : 0; m < rows; ++m) {
+                int e = 0;
+                double2 pj = make_double2(0.0, 0.0);
+                double Volw = 0.0;
+                if (m < ns) {
+                    e = m == 0 ? e_row0 : (m == 1 ? e_row1 : t.sl_idx[(size_t)m * t.nl_stride + tid]);
+                    const bool wall = (e & kWallBit) != 0;
+                    const int k = e & (kWallBit - 1);
+                    pj = (wall ? w.pos : (const double2 *)s.pos)[k];
+                    Volw = wall ? w.a[k].x : 0.0;  // requested with the position, not after the distance test
+                }
+                test(m < ns, e, pj, Volw);
             }
             if (cnt > t.nl_cap * LPP) { atomicOr(t.flags, 1); cnt = t.nl_cap * LPP; }
             cnt_fl = min(cnt_fl, cnt);
@@ -793,6 +852,9 @@ template <int LPP>
 __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                          const FluidTmp &t, const Walls &w, int finish_half)
 {
+    if (kRowsAhead<LPP>)
+        SPHX_WAVE1_ARGS("s"(clk), "s"(q), "s"(s.pos), "s"(s.drho), "s"(t.a), "s"(t.cap), "s"(t.nl_cnt), "s"(t.nl_idx), "s"(t.nl_stride),
+                        "s"(finish_half), "s"((int)gridDim.x));
     SPHX_PASS_INDEX();
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
     const bool closes = finish_half && in_cap && sub == 0;
@@ -805,17 +867,20 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
     // (rows 2 and 3 only where lanes own that many: few lanes per particle)
     const int e_row2 = LPP <= 8 ? t.nl_idx[2 * (size_t)t.nl_stride + tid] : 0;
     const int e_row3 = LPP <= 8 ? t.nl_idx[3 * (size_t)t.nl_stride + tid] : 0;
-    if (!clk->run[q]) return;
-    const bool active = i < clk->n;
+    const double dt = clk->dt;
+    const int run_q = clk->run[q], n_now = clk->n;
+    if (kRowsAhead<LPP>) requests_issued();
+    if (!run_q) return;
+    const bool active = i < n_now;
     double a11 = 0.0, a12 = 0.0, a21 = 0.0, a22 = 0.0;
     if (active) {
         const double xi = pi.x, yi = pi.y;
-        for (int m = 0; m < nn_all; ++m) {
-            const int e = m == 0 ? e_row0 : (m == 1 ? e_row1 : (LPP <= 8 && m == 2 ? e_row2 : (LPP <= 8 && m == 3 ? e_row3 : t.nl_idx[(size_t)m * t.nl_stride + tid])));
+        auto fetch = [&](int e, int k, double2 &pj, double &Volj) {
             const bool wall = (e & kWallBit) != 0;
-            const int k = e & (kWallBit - 1);
-            const double2 pj = (wall ? w.pos : (const double2 *)s.pos)[k];
-            const double Volj = wall ? w.a[k].x : t.vol[k];
+            pj = (wall ? w.pos : (const double2 *)s.pos)[k];
+            Volj = *(wall ? &w.a[k].x : (const double *)&t.vol[k]);
+        };
+        auto term = [&](const double2 pj, double Volj) {
             const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
             const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
             const double ex = dx * inv_r, ey = dy * inv_r;
@@ -824,6 +889,23 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
             a12 -= dx * (fxj * ey);
             a21 -= dy * (fxj * ex);
             a22 -= dy * (fxj * ey);
+        };
+        if (kRowsAhead<LPP>) {  // rows 0 and 1: both rows' records in one wave
+            const int e0 = nn_all > 0 ? e_row0 : 0, e1 = nn_all > 1 ? e_row1 : 0;
+            double2 p0, p1;
+            double V0, V1;
+            fetch(e0, nn_all > 0 ? (e0 & (kWallBit - 1)) : i, p0, V0);
+            fetch(e1, nn_all > 1 ? (e1 & (kWallBit - 1)) : i, p1, V1);
+            requests_issued();
+            if (nn_all > 0) term(p0, V0);
+            if (nn_all > 1) term(p1, V1);
+        }
+        for (int m = kRowsAhead<LPP> ? 2 : 0; m < nn_all; ++m) {
+            const int e = m == 0 ? e_row0 : (m == 1 ? e_row1 : (LPP <= 8 && m == 2 ? e_row2 : (LPP <= 8 && m == 3 ? e_row3 : t.nl_idx[(size_t)m * t.nl_stride + tid])));
+            double2 pj;
+            double Volj;
+            fetch(e, e & (kWallBit - 1), pj, Volj);
+            term(pj, Volj);
         }
     }
     a11 = group_sum<LPP>(a11);
@@ -835,7 +917,7 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
         t.B[i] = make_double4(B.m11, B.m12, B.m21, B.m22);
         if (finish_half) {
             double rhoh, p_half;
-            half_state(ph, a_own.w, drho_own, clk->dt, rhoh, p_half);
+            half_state(ph, a_own.w, drho_own, dt, rhoh, p_half);
             t.a[i] = make_double4(a_own.x, p_half, rhoh, a_own.w);
         }
     }
@@ -873,6 +955,9 @@ template <int LPP, bool HIST = false>
 __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                             const FluidTmp &t, const Walls &w, int later)
 {
+    if (kRowsAhead<LPP>)
+        SPHX_WAVE1_ARGS("s"(clk), "s"(q), "s"(s.pos), "s"(s.vel), "s"(t.a), "s"(t.B), "s"(s.mass), "s"(t.cap), "s"(t.nl_cnt),
+                        "s"(t.nl_idx), "s"(t.nl_stride), "s"(s.posb), "s"(later), "s"((int)gridDim.x));
     SPHX_PASS_INDEX();
     const int c_binned = (HIST && in_cap && sub == 0) ? s.cell[i] : 0;
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
@@ -892,8 +977,10 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     const double2 fp_own = (later && in_cap) ? t.fp[i] : make_double2(0.0, 0.0);
     const double2 p_now = (later && in_cap && sub == 0) ? t.posn[i] : make_double2(0.0, 0.0);
     const double dt = clk->dt;
-    if (!clk->run[q]) return;
-    const bool active = i < clk->n;
+    const int run_q = clk->run[q], n_now = clk->n;
+    if (kRowsAhead<LPP>) requests_issued();
+    if (!run_q) return;
+    const bool active = i < n_now;
     const double h = ph.kc.h;
     double ax = 0.0, ay = 0.0, ix = 0.0, iy = 0.0, px = 0.0, py = 0.0, d2 = 0.0;
     const double xi = pi.x, yi = pi.y, vxi = vi.x, vyi = vi.y;
@@ -901,58 +988,98 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     const double b11i = Bi.x, b12i = Bi.y, b21i = Bi.z, b22i = Bi.w;
     int first_wall = 1 << 20;  // wall neighbours are appended behind the fluid ones: this lane's rows >= first_wall
     int h_cell = -1;           // HIST: the new cell of the lead lane's particle
+    // kRowsAhead: rows 0 and 1 of the lane -- {position, a} of either kind of neighbour, velocity and B of a fluid one (a wall
+    // row asks for the particle's own) -- are requested in one wave; the wall rows among them keep position and volume in
+    // registers for the second wall loop, which otherwise reads its entries and records again behind the group sums
+    double2 pj0 = make_double2(0.0, 0.0), pj1 = pj0;
+    double4 aj0 = make_double4(0.0, 0.0, 0.0, 0.0), aj1 = aj0;
+    auto fluid_term = [&](const double2 pj, const double2 vj, const double4 aj, const double4 Bj) {
+        const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
+        const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
+        const double ex = dx * inv_r, ey = dy * inv_r;
+        const double dW = spline_dW_in(ph.kc, r);
+        const double Volj = aj.x;
+        const double tx = (b11i + Bj.x) * ex + (b12i + Bj.y) * ey;
+        const double ty = (b21i + Bj.z) * ex + (b22i + Bj.w) * ey;
+        const double eBe = ex * tx + ey * ty;
+        const double vxj = vj.x, vyj = vj.y;
+        const double dWVj = dW * Volj;
+        if (!later) {
+            // viscous
+            const double coeff = eBe * ph.mu * dWVj * rcp_nr(r + 0.01 * h);
+            ax += coeff * (vxi - vxj);
+            ay += coeff * (vyi - vyj);
+            // transport
+            ix -= dWVj * tx;
+            iy -= dWVj * ty;
+        }
+        // pressure (Riemann-dissipated face pressure)
+        const double p_j = aj.y;
+        const double rho_bar = 0.5 * (rhoh_i + aj.z);
+        const double un_l = vxi * ex + vyi * ey, un_r = vxj * ex + vyj * ey;
+        const double beta = riemann_beta(un_l, un_r, ph.c_f);
+        const double p_avg = 0.5 * (p_i + p_j);
+        const double p_star = p_avg + 0.5 * beta * rho_bar * (un_l - un_r);
+        const double p_face = 0.5 * (p_avg + p_star);
+        px -= (p_face * tx) * dWVj;
+        py -= (p_face * ty) * dWVj;
+    };
+    auto wall_term = [&](const double2 pj, const double4 wj) {
+        const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
+        const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
+        const double ex = dx * inv_r, ey = dy * inv_r;
+        const double dWVj = spline_dW_in(ph.kc, r) * wj.x;
+        const double tx = b11i * ex + b12i * ey, ty = b21i * ex + b22i * ey;
+        const double eBe = ex * tx + ey * ty;
+        const double coeff = 4.0 * eBe * ph.mu * dWVj * rcp_nr(r + 0.01 * h);
+        ax += coeff * (vxi - wj.y);
+        ay += coeff * (vyi - wj.z);
+        ix -= 2.0 * dWVj * tx;
+        iy -= 2.0 * dWVj * ty;
+    };
     if (active) {
-        for (int m = 0; m < nn_all; ++m) {
+        if (kRowsAhead<LPP>) {
+            const bool has0 = nn_all > 0, has1 = nn_all > 1;
+            const bool w0 = has0 && (e_row0 & kWallBit) != 0, w1 = has1 && (e_row1 & kWallBit) != 0;
+            const int k0 = has0 ? (e_row0 & (kWallBit - 1)) : i, k1 = has1 ? (e_row1 & (kWallBit - 1)) : i;
+            const int kf0 = w0 ? i : k0, kf1 = w1 ? i : k1;
+            pj0 = (w0 ? w.pos : (const double2 *)s.pos)[k0];
+            aj0 = (w0 ? w.a : (const double4 *)t.a)[k0];
+            const double2 vj0 = s.vel[kf0];
+            const double4 Bj0 = t.B[kf0];
+            pj1 = (w1 ? w.pos : (const double2 *)s.pos)[k1];
+            aj1 = (w1 ? w.a : (const double4 *)t.a)[k1];
+            const double2 vj1 = s.vel[kf1];
+            const double4 Bj1 = t.B[kf1];
+            requests_issued();
+            if (has0) {
+                if (!w0) fluid_term(pj0, vj0, aj0, Bj0);
+                else {
+                    first_wall = 0;
+                    if (!later) wall_term(pj0, aj0);  // (wall entries contribute to the pressure part in the second loop only)
+                }
+            }
+            if (has1) {
+                if (!w1) fluid_term(pj1, vj1, aj1, Bj1);
+                else {
+                    first_wall = min(first_wall, 1);
+                    if (!later) wall_term(pj1, aj1);
+                }
+            }
+        }
+        for (int m = kRowsAhead<LPP> ? 2 : 0; m < nn_all; ++m) {
             const int e = m == 0 ? e_row0 : (m == 1 ? e_row1 : (LPP <= 8 && m == 2 ? e_row2 : (LPP <= 8 && m == 3 ? e_row3 : t.nl_idx[(size_t)m * t.nl_stride + tid])));
             const int k = e & (kWallBit - 1);
             if (!(e & kWallBit)) {
                 const double2 pj = s.pos[k], vj = s.vel[k];
                 const double4 aj = t.a[k], Bj = t.B[k];
-                const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-                const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-                const double ex = dx * inv_r, ey = dy * inv_r;
-                const double dW = spline_dW_in(ph.kc, r);
-                const double Volj = aj.x;
-                const double tx = (b11i + Bj.x) * ex + (b12i + Bj.y) * ey;
-                const double ty = (b21i + Bj.z) * ex + (b22i + Bj.w) * ey;
-                const double eBe = ex * tx + ey * ty;
-                const double vxj = vj.x, vyj = vj.y;
-                const double dWVj = dW * Volj;
-                if (!later) {
-                    // viscous
-                    const double coeff = eBe * ph.mu * dWVj * rcp_nr(r + 0.01 * h);
-                    ax += coeff * (vxi - vxj);
-                    ay += coeff * (vyi - vyj);
-                    // transport
-                    ix -= dWVj * tx;
-                    iy -= dWVj * ty;
-                }
-                // pressure (Riemann-dissipated face pressure)
-                const double p_j = aj.y;
-                const double rho_bar = 0.5 * (rhoh_i + aj.z);
-                const double un_l = vxi * ex + vyi * ey, un_r = vxj * ex + vyj * ey;
-                const double beta = riemann_beta(un_l, un_r, ph.c_f);
-                const double p_avg = 0.5 * (p_i + p_j);
-                const double p_star = p_avg + 0.5 * beta * rho_bar * (un_l - un_r);
-                const double p_face = 0.5 * (p_avg + p_star);
-                px -= (p_face * tx) * dWVj;
-                py -= (p_face * ty) * dWVj;
+                fluid_term(pj, vj, aj, Bj);
             } else {
                 first_wall = min(first_wall, m);
                 if (later) continue;  // (wall entries contribute to the pressure part in the second loop only)
                 const double2 pj = w.pos[k];
                 const double4 wj = w.a[k];
-                const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-                const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-                const double ex = dx * inv_r, ey = dy * inv_r;
-                const double dWVj = spline_dW_in(ph.kc, r) * wj.x;
-                const double tx = b11i * ex + b12i * ey, ty = b21i * ex + b22i * ey;
-                const double eBe = ex * tx + ey * ty;
-                const double coeff = 4.0 * eBe * ph.mu * dWVj * rcp_nr(r + 0.01 * h);
-                ax += coeff * (vxi - wj.y);
-                ay += coeff * (vyi - wj.z);
-                ix -= 2.0 * dWVj * tx;
-                iy -= 2.0 * dWVj * ty;
+                wall_term(pj, wj);
             }
         }
     }
@@ -965,18 +1092,24 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     const double inv_m = rcp_nr(mi);
     if (active) {
         const double acx = fpx * inv_m, acy = fpy * inv_m;
-        for (int m = first_wall; m < nn_all; ++m) {
-            const int k = t.nl_idx[(size_t)m * t.nl_stride + tid] & (kWallBit - 1);
-            const double2 pj = w.pos[k];
+        auto wall_pressure = [&](const double2 pj, double Volw) {
             const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
             const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
             const double ex = dx * inv_r, ey = dy * inv_r;
-            const double dWVj = spline_dW_in(ph.kc, r) * w.a[k].x;
+            const double dWVj = spline_dW_in(ph.kc, r) * Volw;
             const double face = -(acx * ex + acy * ey);
             const double p_wall = p_i + rhoh_i * r * fmax(0.0, face);
             const double tx = b11i * ex + b12i * ey, ty = b21i * ex + b22i * ey;
             px -= (p_i + p_wall) * dWVj * tx;
             py -= (p_i + p_wall) * dWVj * ty;
+        };
+        if (kRowsAhead<LPP>) {  // (the prefetched rows from registers; lanes with more wall rows read the rest again)
+            if (first_wall <= 0 && nn_all > 0) wall_pressure(pj0, aj0.x);
+            if (first_wall <= 1 && nn_all > 1) wall_pressure(pj1, aj1.x);
+        }
+        for (int m = kRowsAhead<LPP> ? max(first_wall, 2) : first_wall; m < nn_all; ++m) {
+            const int k = t.nl_idx[(size_t)m * t.nl_stride + tid] & (kWallBit - 1);
+            wall_pressure(w.pos[k], w.a[k].x);
         }
     }
     px = group_sum<LPP>(px);
@@ -2251,6 +2384,8 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
 {
     static_assert(!CODED || (WALK && TILE == kSlotCodes), "slot-coded lists: this pass stages the whole layout");
     static_assert(!REBIN || (!WALK && TILE == 0 && LPP >= 16), "the folded re-binning belongs to the compact kernels");
+    if (!WALK && kRowsAhead<LPP>)
+        SPHX_WAVE1_ARGS("s"(clk), "s"(q), "s"(s.pos), "s"(t.veln), "s"(t.a), "s"(t.cap), "s"(t.nl_cnt), "s"(t.nl_idx), "s"(t.nl_stride));
     const int blk = xcd_block(bid, nb);
     const int tid = blk * kBlock + threadIdx.x;
     const int i = tid / LPP, sub = tid % LPP;
@@ -2262,6 +2397,12 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
         }
         return;
     }
+    // kRowsAhead: this pass reads the clock through a pointer somebody writes (the tail workgroup), so with vector loads, which
+    // come back in order -- the words the pass waits for first are asked for first, in one go
+    constexpr bool kAhead = !WALK && kRowsAhead<LPP>;
+    int run_first = 0, n_first = 0;
+    double dt_first = 0.0;
+    if (kAhead) { run_first = clk->run[q]; n_first = clk->n; dt_first = clk->dt; }
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
     const double2 vi = in_cap ? t.veln[i] : make_double2(0.0, 0.0);
     const int packed = t.nl_cnt[tid];
@@ -2292,9 +2433,10 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
         for (int j = 0; j < kPer; ++j) r_hist[j] = t.count[min((int)threadIdx.x * kPer + j, g.ncells)];
     }
     const TileMap layout = (WALK && TILE > 0) ? tile_map_of(t, blk) : TileMap{0, 0, 0, 0, 0, 0};
-    const double dt = clk->dt;
+    const double dt = kAhead ? dt_first : clk->dt;
     const bool want_out = !WALK || step_outputs_wanted(clk, t);
     const int cell_own = (g.own_by_cell && lead) ? s.cell[i] : 0;
+    if (kAhead) requests_issued();
     if (REBIN) {  // (behind the clock's loads: these wait for the new cell)
         r_cnew = min(max(r_cnew, 0), g.ncells - 1);  // (slots beyond the population hold no cell: any valid one keeps the loads in bounds)
         const int cxn = r_cnew / g.ncy, cyn = r_cnew - cxn * g.ncy;
@@ -2308,8 +2450,8 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
             r_n[ox + 1] = s.start[col * g.ncy + cyhi + 1] - r_lo[ox + 1];
         }
     }
-    if (!clk->run[q]) return;
-    const int n_now = clk->n;
+    if (!(kAhead ? run_first : clk->run[q])) return;
+    const int n_now = kAhead ? n_first : clk->n;
     const bool active = i < n_now;
     double rate = 0.0;
     const double xi = pi.x, yi = pi.y, vxi = vi.x, vyi = vi.y;
@@ -2466,7 +2608,36 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
             term(min_image(g, xi - pj.x), yi - pj.y, 2.0 * wj.y - vxi, 2.0 * wj.z - vyi, wj.x);
         });
     } else if (active) {
-        for (int m = 0; m < nn_all; ++m) {
+        auto term = [&](const double2 pj, const double2 vj, double Volj) {
+            const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
+            const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
+            const double ex = dx * inv_r, ey = dy * inv_r;
+            const double u_jump = (vxi - vj.x) * ex + (vyi - vj.y) * ey;
+            rate += u_jump * spline_dW_sel(ph.kc, r) * Volj;
+        };
+        if (kAhead) {
+            // rows 0 and 1: both rows' records in one wave -- position, volume and velocity of either kind of neighbour through
+            // selected pointers (a wall's record is {Vol, vx, vy, -}), so that the requests need no branch
+            double2 pj_[2], uj_[2];
+            double Vj_[2];
+            bool wall_[2];
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const int e = m < nn_all ? (m == 0 ? e_row0 : e_row1) : 0;
+                wall_[m] = (e & kWallBit) != 0;
+                const int k = m < nn_all ? (e & (kWallBit - 1)) : i;
+                pj_[m] = (wall_[m] ? w.pos : (const double2 *)s.pos)[k];
+                Vj_[m] = *(wall_[m] ? &w.a[k].x : (const double *)&t.vol[k]);
+                uj_[m].x = *(wall_[m] ? &w.a[k].y : (const double *)&t.veln[k].x);
+                uj_[m].y = *(wall_[m] ? &w.a[k].z : (const double *)&t.veln[k].y);
+            }
+            requests_issued();
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+                if (m < nn_all)
+                    term(pj_[m], wall_[m] ? make_double2(2.0 * uj_[m].x - vxi, 2.0 * uj_[m].y - vyi) : uj_[m], Vj_[m]);  // mirrored wall velocity
+        }
+        for (int m = kAhead ? 2 : 0; m < nn_all; ++m) {
             const int e = m == 0 ? e_row0 : (m == 1 ? e_row1 : (LPP <= 8 && m == 2 ? e_row2 : (LPP <= 8 && m == 3 ? e_row3 : t.nl_idx[(size_t)m * t.nl_stride + tid])));
             const bool wall = (e & kWallBit) != 0;
             const int k = e & (kWallBit - 1);
@@ -2481,11 +2652,7 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
                 Volj = t.vol[k];
                 vj = t.veln[k];
             }
-            const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-            const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-            const double ex = dx * inv_r, ey = dy * inv_r;
-            const double u_jump = (vxi - vj.x) * ex + (vyi - vj.y) * ey;
-            rate += u_jump * spline_dW_sel(ph.kc, r) * Volj;
+            term(pj, vj, Volj);
         }
     }
     rate = group_sum<LPP>(rate);
