@@ -150,9 +150,13 @@ typedef struct sphx_params {
                                    force, transport shift once -- of up to dual_rate acoustic sub-steps of pressure /
                                    continuity.  The count is fixed per context: as many acoustic steps as fit into the
                                    viscous / body-force step (1 on fine channels, which are viscous-limited, and on
-                                   contexts that are not eligible; sphx_ctx_substeps reports it).  Not reference
-                                   behaviour: validated against the analytic profile only (2 sub-steps reproduce the
-                                   single-rate L2 and wall shear at dp = 0.05 / 0.025 / 0.02; 4 is noisier at dp = 0.05). */
+                                   contexts that are not eligible; sphx_ctx_substeps reports it).  Not the reference's
+                                   loop, but composed of its operators: tests/dual_rate_reference.py takes the reference's
+                                   neighbour search, density / KGC, viscous force and transport shift once and its
+                                   integration_verlet n_in times on the carried state (same pairs, Vol, B, force_prior), and
+                                   tests/test_gpu_dual_rate_parity.py compares every field with it.  Against the analytic
+                                   profile, 2 sub-steps reproduce the single-rate L2 and wall shear at dp = 0.05 / 0.025 /
+                                   0.02; 4 is noisier at dp = 0.05. */
     int32_t rebuild_every;      /* 0 = auto; K >= 1: particles are re-binned into cells every K-th step; in
                                    between, sweeps are centred on the cell a particle was binned into and
                                    the cells carry a skin (results do not depend on K beyond summation

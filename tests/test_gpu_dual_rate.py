@@ -1,6 +1,8 @@
 """-m gpu: the opt-in dual-rate loop (sphx_params.dual_rate).  It is NOT the reference's
-loop (SPH_Poiseuille.m:250-292 takes one acoustic step per density summation), so there is no oracle for it: the
-checks are that asking for it changes nothing unless it is eligible, that the default path is untouched, and that
+loop (SPH_Poiseuille.m:250-292 takes one acoustic step per density summation).  Its reference is tests/dual_rate_reference.py --
+the oracle's neighbour search, density / KGC, viscous force and transport shift once per outer step, then its
+integration_verlet n_in times on the carried state -- and tests/test_gpu_dual_rate_parity.py compares the loop with it particle
+by particle.  The checks here are those of the loop as a whole: that asking for it changes nothing unless it is eligible, that the default path is untouched, and that
 the physics it produces matches the single-rate run against the analytic profile (SPH_Poiseuille_postprocess.m:67-80)
 and the wall-shear target g*rho0*DH/2."""
 import numpy as np

@@ -12,12 +12,16 @@ scheduled re-binning of step 16.
 
 Reference and tolerances: oracle.run on the same state, the nine fields, t, dt and max |v| as tests/test_gpu_headline_parity.py
 compares them, at that file's bound for 20 steps (RTOL[20] = 1e-10 in max|a - b| / max|b| per field: the two sides evaluate the
-same formulas in a different summation order).  The dual-rate loop is not the reference's loop and has no oracle
-(tests/test_gpu_dual_rate.py): its case compares 16 lanes per particle with 32 -- the same formulas, the rows dealt differently
-over the lanes, so again a different summation order -- at the same bound.  Every case also runs twice and must repeat to the bit.
+same formulas in a different summation order).  The dual-rate loop is not the reference's loop; its reference is
+tests/dual_rate_reference.py, the oracle's functions composed into outer steps and inner sub-steps (more cases of it:
+tests/test_gpu_dual_rate_parity.py).  Its case compares 16 lanes per particle with 32 -- the same formulas, the rows dealt
+differently over the lanes, so again a different summation order -- and each of the two with that reference, all at the same
+bound.  Every case also runs twice and must repeat to the bit.
 """
 import numpy as np
 import pytest
+
+import dual_rate_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -140,8 +144,9 @@ def test_16_lanes_more_than_two_rows_with_wall_rows_among_them(cfgmod, geom, cap
     _check_against_oracle("16 lanes, squeezed", capi, oracle, capsys, prm, parts, 16)
 
 
-def test_dual_rate_16_lanes_against_32(cfgmod, geom, capi, capsys):
+def test_dual_rate_16_lanes_against_32(cfgmod, geom, capi, oracle, capsys):
     prm, parts = _start(cfgmod, geom)
+    ref = dual_rate_reference.run(prm, parts, 2, max_outer=6)
     out = {}
     for lanes in (16, 32):
         st, got, info = _run(capi, prm, parts, n_steps=6, lanes_per_particle=lanes, dual_rate=2)
@@ -159,3 +164,13 @@ def test_dual_rate_16_lanes_against_32(cfgmod, geom, capi, capsys):
     assert abs(sa["dt_last"] - sb["dt_last"]) <= RTOL * sb["dt_last"]
     for k, e in err.items():
         assert e <= RTOL, f"dual rate:{k}: {e:.3e} > {RTOL:.0e}"
+    for lanes, (st, got) in out.items():  # ... and each of them against the reference of the dual-rate loop
+        err = _errors(got, ref)
+        with capsys.disabled():
+            print(f"[load chains] dual rate, {lanes} lanes against the reference: max rel err "
+                  + " ".join(f"{k}={v:.1e}" for k, v in err.items()))
+        assert st["step"] == ref["steps"] == 6 and abs(st["t"] - ref["t"]) <= 1e-12 * ref["t"]
+        assert abs(st["dt_last"] - ref["dt_last"]) <= RTOL * ref["dt_last"]
+        assert abs(st["vmax"] - ref["vmax"]) <= RTOL * ref["vmax"]
+        for k, e in err.items():
+            assert e <= RTOL, f"dual rate, {lanes} lanes against the reference:{k}: {e:.3e} > {RTOL:.0e}"
