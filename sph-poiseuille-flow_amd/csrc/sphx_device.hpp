@@ -117,6 +117,65 @@ __device__ __forceinline__ double rsqrt_nr(double x)
     return fma(y * e, fma(e, 0.375, 0.5), y);
 }
 
+// Geometry of a pair at separation (dx, dy), r^2 > kR2Min: the distance and the unit vector from ONE reciprocal square root
+// (r = r^2 / r, no square root and no division)
+struct PairGeom {
+    double r, ex, ey;
+};
+__device__ __forceinline__ PairGeom pair_geom(double dx, double dy)
+{
+    const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
+    return PairGeom{r, dx * inv_r, dy * inv_r};
+}
+
+// KGC moment term of one neighbour (the sums of sph_physics_mex.c:239-366): A -= (dx, dy) (dW Vol_j e)^T
+__device__ __forceinline__ void kgc_moment_add(const KernelConst &kc, double dx, double dy, double Volj, double &a11, double &a12,
+                                               double &a21, double &a22)
+{
+    const auto [r, ex, ey] = pair_geom(dx, dy);
+    const double fxj = spline_dW_in(kc, r) * Volj;
+    a11 -= dx * (fxj * ex);
+    a12 -= dx * (fxj * ey);
+    a21 -= dy * (fxj * ex);
+    a22 -= dy * (fxj * ey);
+}
+
+// continuity term of one neighbour (sph_physics_mex.c:1090-1108): the velocity jump v_i - u_j along the pair axis
+// (both velocities, not their difference: the subtraction stays behind the geometry, where both forms of pass E had it)
+__device__ __forceinline__ void continuity_add(const KernelConst &kc, double dx, double dy, double vxi, double vyi, double ujx,
+                                               double ujy, double Volj, double &rate)
+{
+    const auto [r, ex, ey] = pair_geom(dx, dy);
+    rate += ((vxi - ujx) * ex + (vyi - ujy) * ey) * spline_dW_sel(kc, r) * Volj;
+}
+
+// What the wall viscous and transport terms of pass CD share (Bi = {b11, b12, b21, b22} of the particle; a wall particle has
+// no B of its own): the distance, dW Vol_w, t = B_i e and e . t
+struct WallPair {
+    double r, dWVj, tx, ty, eBe;
+};
+__device__ __forceinline__ WallPair wall_pair(const KernelConst &kc, double dx, double dy, double Volw, const double4 &Bi)
+{
+    const auto [r, ex, ey] = pair_geom(dx, dy);
+    const double dWVj = spline_dW_in(kc, r) * Volw;
+    const double tx = Bi.x * ex + Bi.y * ey, ty = Bi.z * ex + Bi.w * ey;
+    return WallPair{r, dWVj, tx, ty, ex * tx + ey * ty};
+}
+
+// wall pressure term of pass CD (sph_physics_mex.c:931-934): the wall's pressure mirrors the particle's, raised by the
+// particle's acceleration (acx, acy) = force_prior / m towards the wall
+__device__ __forceinline__ void wall_pressure_add(const KernelConst &kc, double dx, double dy, double Volw, const double4 &Bi,
+                                                  double acx, double acy, double p_i, double rhoh_i, double &px, double &py)
+{
+    const auto [r, ex, ey] = pair_geom(dx, dy);
+    const double dWVj = spline_dW_in(kc, r) * Volw;
+    const double face = -(acx * ex + acy * ey);
+    const double p_wall = p_i + rhoh_i * r * fmax(0.0, face);
+    const double tx = Bi.x * ex + Bi.y * ey, ty = Bi.z * ex + Bi.w * ey;
+    px -= (p_i + p_wall) * dWVj * tx;
+    py -= (p_i + p_wall) * dWVj * ty;
+}
+
 // rho from the two sigma sums; sigma_inner already includes W(0).
 __device__ __forceinline__ double density_from_sigma(double sigma_inner, double sigma_contact,
                                                      double mass_i, double rho0, double inv_sigma0)

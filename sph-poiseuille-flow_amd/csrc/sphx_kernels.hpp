@@ -265,6 +265,29 @@ __device__ __forceinline__ bool duplicate_column(const Grid &g, int ox)
     return (g.ncx == 1 && ox != 0) || (g.ncx == 2 && ox == 1);
 }
 
+// Column cx + ox (ox = -1, 0, 1) of the three that hold a cell's neighbours -> col.  False: there is none -- beyond the end of an
+// open window, or the same column as another of the three.
+__device__ __forceinline__ bool neighbour_column(const Grid &g, int cx, int ox, int &col)
+{
+    col = cx + ox;
+    bool ok = true;
+    if (g.periodic) {
+        if (duplicate_column(g, ox)) ok = false;
+        if (col < 0) col += g.ncx;
+        else if (col >= g.ncx) col -= g.ncx;
+    } else if (col < 0 || col >= g.ncx) {
+        ok = false;
+    }
+    return ok;
+}
+// Three index ranges walked as ONE virtual index range (a group of lanes then needs one or two trips instead of one or two
+// per range, and each trip's loads are independent of the previous trip's): position v -> index; n0, n1: the lengths of the
+// first two ranges
+__device__ __forceinline__ int ranges_index(int lo0, int lo1, int lo2, int n0, int n1, int v)
+{
+    return v < n0 ? lo0 + v : (v < n0 + n1 ? lo1 + (v - n0) : lo2 + (v - n0 - n1));
+}
+
 // Folded re-binning (k_forces_hist, k_continuity_rebin): is cell c_new one of the 3 x 3 cells around c_old (columns wrap on a
 // periodic grid of at least three columns)?  Between two re-binnings nobody moves further than half a skin plus one step, far
 // less than a cell, so every member of a new cell was binned in that cell's 3 x 3 neighbourhood.
@@ -327,6 +350,30 @@ __device__ __forceinline__ double group_sum(double v)
     return v;
 }
 
+// Pass CD, lead lane: squared drift of the particle's new position from where it was binned (pb: its FluidSet::posb record) --
+// zero for a particle a slab does not own, infinite for a NaN: the maximum has to see it
+__device__ __forceinline__ double tracked_drift2(const Grid &g, const FluidSet &s, int i, double xo, double yo, const double2 pb)
+{
+    if (g.own_by_cell && !owns(g, 0.0, s.cell[i])) return 0.0;  // (a slab bounds the drift of what it owns)
+    const double ddx = min_image(g, xo - pb.x), ddy = yo - pb.y;
+    const double d2 = ddx * ddx + ddy * ddy;
+    return d2 != d2 ? INFINITY : d2;
+}
+// ... and its maximum over the workgroup -> t.dpart[blk]: the largest drift from the binning positions bounds how stale the cell
+// grid may get (Clock::drift).  Every thread of the workgroup calls this (one barrier).
+__device__ __forceinline__ void store_block_drift(const FluidTmp &t, int blk, double d2)
+{
+    d2 = wave_max(d2);
+    __shared__ double s_d2[kBlock / 64];
+    if ((threadIdx.x & 63) == 0) s_d2[threadIdx.x >> 6] = d2;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = s_d2[0];
+        for (int k = 1; k < kBlock / 64; ++k) m = fmax(m, s_d2[k]);
+        t.dpart[blk] = m;
+    }
+}
+
 // Visit the candidates of the three cell columns around (cx,cy): body(k).
 template <int LPP, typename Body>
 __device__ __forceinline__ void sweep(const Grid &g, const int *__restrict__ start, int cx, int cy,
@@ -335,14 +382,8 @@ __device__ __forceinline__ void sweep(const Grid &g, const int *__restrict__ sta
     const int cylo = max(cy - 1, 0), cyhi = min(cy + 1, g.ncy - 1);
 #pragma unroll
     for (int ox = -1; ox <= 1; ++ox) {
-        int col = cx + ox;
-        if (g.periodic) {
-            if (duplicate_column(g, ox)) continue;
-            if (col < 0) col += g.ncx;
-            else if (col >= g.ncx) col -= g.ncx;
-        } else if (col < 0 || col >= g.ncx) {
-            continue;
-        }
+        int col;
+        if (!neighbour_column(g, cx, ox, col)) continue;
         const int base = col * g.ncy;
         const int lo = start[base + cylo], hi = start[base + cyhi + 1];
         for (int k = lo + sub; k < hi; k += LPP) body(k);
@@ -440,6 +481,13 @@ constexpr int kWallBit = 1 << 30;
 // nl_cnt[lane]: rows this lane owns (low half) and how many of them, the first ones, hold fluid neighbours (high half)
 __device__ __forceinline__ int list_rows(int packed) { return packed & 0x3fff; }
 __device__ __forceinline__ int list_fluid_rows(int packed) { return packed >> 16; }
+// ... and the word of lane `sub` of a particle with cnt neighbours: the lane owns entries sub, sub + LPP, ...  Fluid neighbours
+// come first (cnt_fl of them), so a lane's rows are its fluid rows followed by its wall rows.
+template <int LPP>
+__device__ __forceinline__ int list_row_counts(int cnt, int cnt_fl, int sub)
+{
+    return (cnt > sub ? (cnt - sub + LPP - 1) / LPP : 0) | ((cnt_fl > sub ? (cnt_fl - sub + LPP - 1) / LPP : 0) << 16);
+}
 // Bits 14 and 15 of a lane's packed counts (slot-coded lists only, see kSlotCodes): some fluid entry of the lane's column of the
 // SUPERSET list -- so of every list walked until the next re-binning -- names something beyond the first kForceSlots /
 // kSlotCodes slots of the workgroup's layout.  Set by the cell sweep, handed on by pass A's walk.  A wavefront none of whose
@@ -499,6 +547,72 @@ __device__ __forceinline__ int code_of_row(const int *pk, int stride, int row, i
 // ... and back: only wavefronts near the periodic seam can hold a particle whose neighbours wrap (see near_seam)
 __device__ __forceinline__ int wrap_index(int k, int n) { return k < 0 ? k + n : (k >= n ? k - n : k); }
 
+// Appending to a list (pass A).  The LPP lanes of a particle test LPP consecutive candidates at a time (uniform trip count over
+// the group); accepted ones are packed with ballot + popcount.  A group (LPP <= 32 aligned lanes) lies in one 32-bit half of
+// the wave's ballot: 32-bit shifts / popcounts (the candidate loop of the sweeping variants is VALU-bound).
+template <int LPP>
+struct LaneGroup {
+    int sub, lane, half_shift, row_base;  // row_base: list column of lane 0 of this group
+    unsigned grp_mask, below_me;
+    __device__ __forceinline__ LaneGroup(int tid, int sub)
+        : sub(sub), lane(threadIdx.x & 63), half_shift((lane & ~(LPP - 1)) & 31), row_base(tid - sub),
+          grp_mask(LPP >= 32 ? 0xffffffffu : ((1u << (LPP & 31)) - 1u)), below_me((1u << sub) - 1u)  // sub <= 31
+    {
+    }
+    __device__ __forceinline__ unsigned bits(bool acc) const  // who of the group accepts: bit k = its lane k
+    {
+        const unsigned long long bal = __ballot(acc);
+        const unsigned half = lane < 32 ? (unsigned)bal : (unsigned)(bal >> 32);
+        return (half >> half_shift) & grp_mask;
+    }
+};
+// compact lists (32-bit entries, nl_idx / sl_idx of `cap` rows): the group's accepted entries go behind the n it holds
+template <int LPP>
+__device__ __forceinline__ void list_push(const LaneGroup<LPP> &lg, int *idx, int cap, int stride, int &n, bool acc, int entry)
+{
+    if (LPP == 1) {
+        if (acc) {
+            if (n < cap) idx[(size_t)n * stride + lg.row_base] = entry;
+            ++n;
+        }
+    } else {
+        const unsigned grp = lg.bits(acc);
+        if (acc) {
+            const int m = n + __popc(grp & lg.below_me);
+            if (m / LPP < cap) idx[(size_t)(m / LPP) * stride + lg.row_base + (m % LPP)] = entry;
+        }
+        n += __popc(grp);
+    }
+}
+// large-channel lists: a fluid entry goes to the packed list pk (16 bits: the index difference to the group's particle, or a
+// slot code), a wall entry to the 32-bit one
+// (2 lanes per particle: who else accepts is one DPP move away -- the ballot, the half select, the shift and the two
+//  popcounts were 9 of the ~55 vector instructions of a candidate in a pass that is ALU-bound; unsigned row arithmetic:
+//  m / LPP on a signed m costs a sign fix-up per use)
+template <int LPP>
+__device__ __forceinline__ void list_push_w(const LaneGroup<LPP> &lg, int *idx, int *pk, int cap, int stride, int &n, bool acc,
+                                            int entry, bool wall)
+{
+    int below, all;
+    if constexpr (LPP == 2) {
+        const int mine = acc ? 1 : 0, other = pair_partner(mine);
+        below = lg.sub ? other : 0;
+        all = mine + other;
+    } else {
+        const unsigned grp = LPP == 1 ? (acc ? 1u : 0u) : lg.bits(acc);
+        below = __popc(grp & lg.below_me);
+        all = __popc(grp);
+    }
+    if (acc) {
+        const unsigned m = (unsigned)(n + below), row = m / LPP, col = (unsigned)lg.row_base + m % LPP;
+        if ((int)row < cap) {
+            if (wall) idx[(size_t)row * stride + col] = entry;
+            else put_delta(pk, stride, (int)row, (int)col, entry);
+        }
+    }
+    n += all;
+}
+
 // Prologue shared by the passes: everything whose address does not depend on the clock is requested
 // BEFORE the run flag is looked at, so the clock read overlaps the particle's own loads.
 #define SPHX_PASS_INDEX_AT(bid, nblk)                                      \
@@ -525,12 +639,49 @@ template <int LPP>
 constexpr bool kRowsAhead = LPP >= 16;
 __device__ __forceinline__ void requests_issued() { asm volatile("" ::: "memory"); }
 #define SPHX_WAVE1_ARGS(...) asm volatile("" ::__VA_ARGS__)
+// The first rows of a lane's list column, requested together with the row count (at 32 lanes per particle a lane rarely owns
+// more than two): count -> entry -> neighbour data becomes {count, entries} -> neighbour data.
+// (rows 2 and 3 only where lanes own that many: few lanes per particle)
+template <int LPP>
+struct FirstRows {
+    int e0, e1, e2, e3;
+    __device__ __forceinline__ FirstRows(const int *idx, int stride, int tid)
+        : e0(idx[tid]), e1(idx[(size_t)stride + tid]), e2(LPP <= 8 ? idx[2 * (size_t)stride + tid] : 0),
+          e3(LPP <= 8 ? idx[3 * (size_t)stride + tid] : 0)
+    {
+    }
+    __device__ __forceinline__ int row(int m, const int *idx, int stride, int tid) const  // entry of row m of the column
+    {
+        return m == 0 ? e0 : (m == 1 ? e1 : (LPP <= 8 && m == 2 ? e2 : (LPP <= 8 && m == 3 ? e3 : idx[(size_t)m * stride + tid])));
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 // pass A: candidate sweep -> neighbour list; number-density summation -> rho, Vol
 // (mex/sph_physics_mex.c:188-234) and the half-step density/pressure of integration_1st's pre-pass
 // (:857-862), which only needs own-particle data.
 // ---------------------------------------------------------------------------------------------
+// the half-step density / pressure of a particle (integration_1st's pre-pass, sph_physics_mex.c:857-862)
+__device__ __forceinline__ void half_state(const Phys &ph, double rho, double drho, double dt, double &rhoh, double &ph_)
+{
+    rhoh = rho + 0.5 * dt * drho;
+    if (rhoh < 1e-10) rhoh = ph.rho0;
+    ph_ = eos_pressure(rhoh, ph.rho0, ph.p0);
+}
+
+// Pass A's lead lane, all three forms: the sigma sums of particle i -> rho and Vol, and its record t.a = {Vol, p_half, rho_half,
+// rho} (half: with the half-step pair; otherwise pass B completes the record, see density_body)
+__device__ __forceinline__ void store_density(const Phys &ph, const FluidTmp &t, int i, double s_in, double s_ct, double mass_i,
+                                              double drho_i, double dt, bool half)
+{
+    const double rho = density_from_sigma(ph.w0 + s_in, s_ct, mass_i, ph.rho0, ph.inv_sigma0);
+    const double vol = mass_i / rho;
+    double rhoh, p_half;
+    half_state(ph, rho, drho_i, dt, rhoh, p_half);
+    t.a[i] = half ? make_double4(vol, p_half, rhoh, rho) : make_double4(vol, 0.0, 0.0, rho);
+    t.vol[i] = vol;
+}
+
 // MODE 0: sweep the cells, write the step's list.  MODE 1: same sweep, also write the superset list.
 // MODE 2: walk the superset list instead of the cells.
 // bid / nblk: the workgroup's index among the nblk workgroups of this pass (the fused launch k_continuity_density runs the
@@ -570,50 +721,9 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
     const bool active = i < n_now;
     double s_in = 0.0, s_ct = 0.0;
     int cnt = 0, scnt = 0, cnt_fl = 0, scnt_fl = 0;
-    const int lane = threadIdx.x & 63, gbase = lane & ~(LPP - 1);
-    const int row_base = tid - sub;  // list column of lane 0 of this group
-    // the LPP lanes of a particle test LPP consecutive candidates at a time (uniform trip count over the
-    // group); accepted ones are packed with ballot + popcount
-    // a group (LPP <= 32 aligned lanes) lies in one 32-bit half of the wave's ballot: 32-bit shifts / popcounts
-    // (the candidate loop of the sweeping variants is VALU-bound)
-    const int half_shift = gbase & 31;
-    const unsigned grp_mask = LPP >= 32 ? 0xffffffffu : ((1u << (LPP & 31)) - 1u);
-    const unsigned below_me = (1u << sub) - 1u;  // sub <= 31
-    auto group_bits = [&](bool acc) -> unsigned {
-        const unsigned long long bal = __ballot(acc);
-        const unsigned half = lane < 32 ? (unsigned)bal : (unsigned)(bal >> 32);
-        return (half >> half_shift) & grp_mask;
-    };
-    auto push = [&](bool acc, int entry) {
-        if (LPP == 1) {
-            if (acc) {
-                if (cnt < t.nl_cap) t.nl_idx[(size_t)cnt * t.nl_stride + tid] = entry;
-                ++cnt;
-            }
-        } else {
-            const unsigned grp = group_bits(acc);
-            if (acc) {
-                const int m = cnt + __popc(grp & below_me);
-                if (m / LPP < t.nl_cap) t.nl_idx[(size_t)(m / LPP) * t.nl_stride + row_base + (m % LPP)] = entry;
-            }
-            cnt += __popc(grp);
-        }
-    };
-    auto push_super = [&](bool acc, int entry) {
-        if (LPP == 1) {
-            if (acc) {
-                if (scnt < t.sl_cap) t.sl_idx[(size_t)scnt * t.nl_stride + tid] = entry;
-                ++scnt;
-            }
-        } else {
-            const unsigned grp = group_bits(acc);
-            if (acc) {
-                const int m = scnt + __popc(grp & below_me);
-                if (m / LPP < t.sl_cap) t.sl_idx[(size_t)(m / LPP) * t.nl_stride + row_base + (m % LPP)] = entry;
-            }
-            scnt += __popc(grp);
-        }
-    };
+    const LaneGroup<LPP> lg(tid, sub);
+    auto push = [&](bool acc, int entry) { list_push(lg, t.nl_idx, t.nl_cap, t.nl_stride, cnt, acc, entry); };
+    auto push_super = [&](bool acc, int entry) { list_push(lg, t.sl_idx, t.sl_cap, t.nl_stride, scnt, acc, entry); };
     constexpr bool walk = MODE == 2;
     constexpr bool record = MODE == 1;  // also write the superset list
     if (walk) {
@@ -641,7 +751,7 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
                     push(acc, e);
                     cnt_fl = cnt;
                 } else {
-                    cnt_fl += LPP == 1 ? ((acc && !wall_row) ? 1 : 0) : __popc(group_bits(acc && !wall_row));
+                    cnt_fl += LPP == 1 ? ((acc && !wall_row) ? 1 : 0) : __popc(lg.bits(acc && !wall_row));
                     push(acc, e);
                 }
             };
@@ -687,28 +797,18 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
         const int cx = ci / g.ncy, cy = ci - cx * g.ncy;
         const int cylo = max(cy - 1, 0), cyhi = min(cy + 1, g.ncy - 1);
         const bool near_wall = w.row_any[cy] != 0;
-        // cell ranges of the three columns, fluid and wall, requested together
+        // cell ranges of the three columns, fluid and wall, requested together; each set is walked as one range (ranges_index)
         int lo[3], hi[3], wlo[3], whi[3];
 #pragma unroll
         for (int ox = -1; ox <= 1; ++ox) {
-            int col = cx + ox;
-            bool ok = true;
-            if (g.periodic) {
-                if (duplicate_column(g, ox)) ok = false;
-                if (col < 0) col += g.ncx;
-                else if (col >= g.ncx) col -= g.ncx;
-            } else if (col < 0 || col >= g.ncx) {
-                ok = false;
-            }
+            int col;
+            const bool ok = neighbour_column(g, cx, ox, col);
             const int c0 = col * g.ncy + cylo, c1 = col * g.ncy + cyhi + 1;
             lo[ox + 1] = ok ? s.start[c0] : 0;
             hi[ox + 1] = ok ? s.start[c1] : 0;
             wlo[ox + 1] = ok ? w.start[c0] : 0;
             whi[ox + 1] = ok ? w.start[c1] : 0;
         }
-        // The three fluid ranges (and, next to a wall, the three wall ranges) are walked as ONE virtual index range:
-        // a group of 32 lanes then needs one or two trips instead of one or two per column, and each trip's
-        // loads are independent of the previous trip's packing.
         const int n0 = hi[0] - lo[0], n1 = hi[1] - lo[1], n2 = hi[2] - lo[2];
         const int nfl = n0 + n1 + n2;
         for (int vb = 0; vb < nfl; vb += LPP) {
@@ -716,7 +816,7 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
             bool acc = false, wide = false;
             int k = 0;
             if (v < nfl) {
-                k = v < n0 ? lo[0] + v : (v < n0 + n1 ? lo[1] + (v - n0) : lo[2] + (v - n0 - n1));
+                k = ranges_index(lo[0], lo[1], lo[2], n0, n1, v);
                 const double2 pj = s.pos[k];
                 const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
                 const double r2 = dx * dx + dy * dy;
@@ -739,7 +839,7 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
                 bool acc = false, wide = false;
                 int k = 0;
                 if (v < nwl) {
-                    k = v < w0 ? wlo[0] + v : (v < w0 + w1 ? wlo[1] + (v - w0) : wlo[2] + (v - w0 - w1));
+                    k = ranges_index(wlo[0], wlo[1], wlo[2], w0, w1, v);
                     const double2 pj = w.pos[k];
                     const double Volj = w.a[k].x;  // requested with the position, not after the distance test
                     const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
@@ -759,31 +859,12 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
         if (record && scnt > t.sl_cap * LPP) { atomicOr(t.flags, 1); scnt = t.sl_cap * LPP; }
         scnt_fl = min(scnt_fl, scnt);
     }
-    // cnt is the particle's neighbour count (identical in all lanes of the group); lane `sub` owns entries
-    // sub, sub+LPP, ...  Fluid neighbours come first (cnt_fl of them), so a lane's rows are its fluid rows followed by
-    // its wall rows: both counts are stored (list_rows / list_fluid_rows).
-    if (tid < t.nl_stride)
-        t.nl_cnt[tid] = (cnt > sub ? (cnt - sub + LPP - 1) / LPP : 0) | ((cnt_fl > sub ? (cnt_fl - sub + LPP - 1) / LPP : 0) << 16);
-    if (record && tid < t.nl_stride)
-        t.sl_cnt[tid] = (scnt > sub ? (scnt - sub + LPP - 1) / LPP : 0) | ((scnt_fl > sub ? (scnt_fl - sub + LPP - 1) / LPP : 0) << 16);
+    // cnt is the particle's neighbour count (identical in all lanes of the group)
+    if (tid < t.nl_stride) t.nl_cnt[tid] = list_row_counts<LPP>(cnt, cnt_fl, sub);
+    if (record && tid < t.nl_stride) t.sl_cnt[tid] = list_row_counts<LPP>(scnt, scnt_fl, sub);
     s_in = group_sum<LPP>(s_in);
     s_ct = group_sum<LPP>(s_ct);
-    if (active && sub == 0) {
-        const double m = mass_i;
-        const double rho = density_from_sigma(ph.w0 + s_in, s_ct, m, ph.rho0, ph.inv_sigma0);
-        double rhoh = rho + 0.5 * dt * drho_i;
-        if (rhoh < 1e-10) rhoh = ph.rho0;
-        t.a[i] = half ? make_double4(m / rho, eos_pressure(rhoh, ph.rho0, ph.p0), rhoh, rho) : make_double4(m / rho, 0.0, 0.0, rho);
-        t.vol[i] = m / rho;
-    }
-}
-
-// the half-step density / pressure of a particle (integration_1st's pre-pass, sph_physics_mex.c:857-862)
-__device__ __forceinline__ void half_state(const Phys &ph, double rho, double drho, double dt, double &rhoh, double &ph_)
-{
-    rhoh = rho + 0.5 * dt * drho;
-    if (rhoh < 1e-10) rhoh = ph.rho0;
-    ph_ = eos_pressure(rhoh, ph.rho0, ph.p0);
+    if (active && sub == 0) store_density(ph, t, i, s_in, s_ct, mass_i, drho_i, dt, half);
 }
 
 // Slabs, frozen steps: pass A of the next step in two launches, so that the halo exchange of this step hides behind the
@@ -861,12 +942,7 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
     const double4 a_own = closes ? t.a[i] : make_double4(0.0, 0.0, 0.0, 0.0);
     const double drho_own = closes ? s.drho[i] : 0.0;
     const int nn_all = list_rows(t.nl_cnt[tid]);
-    // the first rows are requested together with the count (at 32 lanes per particle a lane rarely owns more than
-    // two): count -> entry -> neighbour data becomes {count, entries} -> neighbour data
-    const int e_row0 = t.nl_idx[tid], e_row1 = t.nl_idx[(size_t)t.nl_stride + tid];
-    // (rows 2 and 3 only where lanes own that many: few lanes per particle)
-    const int e_row2 = LPP <= 8 ? t.nl_idx[2 * (size_t)t.nl_stride + tid] : 0;
-    const int e_row3 = LPP <= 8 ? t.nl_idx[3 * (size_t)t.nl_stride + tid] : 0;
+    const FirstRows<LPP> first(t.nl_idx, t.nl_stride, tid);
     const double dt = clk->dt;
     const int run_q = clk->run[q], n_now = clk->n;
     if (kRowsAhead<LPP>) requests_issued();
@@ -881,17 +957,10 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
             Volj = *(wall ? &w.a[k].x : (const double *)&t.vol[k]);
         };
         auto term = [&](const double2 pj, double Volj) {
-            const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-            const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-            const double ex = dx * inv_r, ey = dy * inv_r;
-            const double fxj = spline_dW_in(ph.kc, r) * Volj;
-            a11 -= dx * (fxj * ex);
-            a12 -= dx * (fxj * ey);
-            a21 -= dy * (fxj * ex);
-            a22 -= dy * (fxj * ey);
+            kgc_moment_add(ph.kc, min_image(g, xi - pj.x), yi - pj.y, Volj, a11, a12, a21, a22);
         };
         if (kRowsAhead<LPP>) {  // rows 0 and 1: both rows' records in one wave
-            const int e0 = nn_all > 0 ? e_row0 : 0, e1 = nn_all > 1 ? e_row1 : 0;
+            const int e0 = nn_all > 0 ? first.e0 : 0, e1 = nn_all > 1 ? first.e1 : 0;
             double2 p0, p1;
             double V0, V1;
             fetch(e0, nn_all > 0 ? (e0 & (kWallBit - 1)) : i, p0, V0);
@@ -901,7 +970,7 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
             if (nn_all > 1) term(p1, V1);
         }
         for (int m = kRowsAhead<LPP> ? 2 : 0; m < nn_all; ++m) {
-            const int e = m == 0 ? e_row0 : (m == 1 ? e_row1 : (LPP <= 8 && m == 2 ? e_row2 : (LPP <= 8 && m == 3 ? e_row3 : t.nl_idx[(size_t)m * t.nl_stride + tid])));
+            const int e = first.row(m, t.nl_idx, t.nl_stride, tid);
             double2 pj;
             double Volj;
             fetch(e, e & (kWallBit - 1), pj, Volj);
@@ -966,12 +1035,7 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     const double4 Bi = in_cap ? t.B[i] : make_double4(1.0, 0.0, 0.0, 1.0);
     const double mi = in_cap ? s.mass[i] : 1.0;
     const int nn_all = list_rows(t.nl_cnt[tid]);
-    // the first rows are requested together with the count (at 32 lanes per particle a lane rarely owns more than
-    // two): count -> entry -> neighbour data becomes {count, entries} -> neighbour data
-    const int e_row0 = t.nl_idx[tid], e_row1 = t.nl_idx[(size_t)t.nl_stride + tid];
-    // (rows 2 and 3 only where lanes own that many: few lanes per particle)
-    const int e_row2 = LPP <= 8 ? t.nl_idx[2 * (size_t)t.nl_stride + tid] : 0;
-    const int e_row3 = LPP <= 8 ? t.nl_idx[3 * (size_t)t.nl_stride + tid] : 0;
+    const FirstRows<LPP> first(t.nl_idx, t.nl_stride, tid);
     const bool tracked = s.posb != nullptr;
     const double2 pb = (tracked && in_cap && sub == 0) ? s.posb[i] : make_double2(0.0, 0.0);
     const double2 fp_own = (later && in_cap) ? t.fp[i] : make_double2(0.0, 0.0);
@@ -994,9 +1058,7 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     double2 pj0 = make_double2(0.0, 0.0), pj1 = pj0;
     double4 aj0 = make_double4(0.0, 0.0, 0.0, 0.0), aj1 = aj0;
     auto fluid_term = [&](const double2 pj, const double2 vj, const double4 aj, const double4 Bj) {
-        const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-        const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-        const double ex = dx * inv_r, ey = dy * inv_r;
+        const auto [r, ex, ey] = pair_geom(min_image(g, xi - pj.x), yi - pj.y);
         const double dW = spline_dW_in(ph.kc, r);
         const double Volj = aj.x;
         const double tx = (b11i + Bj.x) * ex + (b12i + Bj.y) * ey;
@@ -1025,23 +1087,18 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
         py -= (p_face * ty) * dWVj;
     };
     auto wall_term = [&](const double2 pj, const double4 wj) {
-        const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-        const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-        const double ex = dx * inv_r, ey = dy * inv_r;
-        const double dWVj = spline_dW_in(ph.kc, r) * wj.x;
-        const double tx = b11i * ex + b12i * ey, ty = b21i * ex + b22i * ey;
-        const double eBe = ex * tx + ey * ty;
-        const double coeff = 4.0 * eBe * ph.mu * dWVj * rcp_nr(r + 0.01 * h);
+        const WallPair wp = wall_pair(ph.kc, min_image(g, xi - pj.x), yi - pj.y, wj.x, Bi);
+        const double coeff = 4.0 * wp.eBe * ph.mu * wp.dWVj * rcp_nr(wp.r + 0.01 * h);
         ax += coeff * (vxi - wj.y);
         ay += coeff * (vyi - wj.z);
-        ix -= 2.0 * dWVj * tx;
-        iy -= 2.0 * dWVj * ty;
+        ix -= 2.0 * wp.dWVj * wp.tx;
+        iy -= 2.0 * wp.dWVj * wp.ty;
     };
     if (active) {
         if (kRowsAhead<LPP>) {
             const bool has0 = nn_all > 0, has1 = nn_all > 1;
-            const bool w0 = has0 && (e_row0 & kWallBit) != 0, w1 = has1 && (e_row1 & kWallBit) != 0;
-            const int k0 = has0 ? (e_row0 & (kWallBit - 1)) : i, k1 = has1 ? (e_row1 & (kWallBit - 1)) : i;
+            const bool w0 = has0 && (first.e0 & kWallBit) != 0, w1 = has1 && (first.e1 & kWallBit) != 0;
+            const int k0 = has0 ? (first.e0 & (kWallBit - 1)) : i, k1 = has1 ? (first.e1 & (kWallBit - 1)) : i;
             const int kf0 = w0 ? i : k0, kf1 = w1 ? i : k1;
             pj0 = (w0 ? w.pos : (const double2 *)s.pos)[k0];
             aj0 = (w0 ? w.a : (const double4 *)t.a)[k0];
@@ -1068,7 +1125,7 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
             }
         }
         for (int m = kRowsAhead<LPP> ? 2 : 0; m < nn_all; ++m) {
-            const int e = m == 0 ? e_row0 : (m == 1 ? e_row1 : (LPP <= 8 && m == 2 ? e_row2 : (LPP <= 8 && m == 3 ? e_row3 : t.nl_idx[(size_t)m * t.nl_stride + tid])));
+            const int e = first.row(m, t.nl_idx, t.nl_stride, tid);
             const int k = e & (kWallBit - 1);
             if (!(e & kWallBit)) {
                 const double2 pj = s.pos[k], vj = s.vel[k];
@@ -1093,15 +1150,7 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     if (active) {
         const double acx = fpx * inv_m, acy = fpy * inv_m;
         auto wall_pressure = [&](const double2 pj, double Volw) {
-            const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-            const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-            const double ex = dx * inv_r, ey = dy * inv_r;
-            const double dWVj = spline_dW_in(ph.kc, r) * Volw;
-            const double face = -(acx * ex + acy * ey);
-            const double p_wall = p_i + rhoh_i * r * fmax(0.0, face);
-            const double tx = b11i * ex + b12i * ey, ty = b21i * ex + b22i * ey;
-            px -= (p_i + p_wall) * dWVj * tx;
-            py -= (p_i + p_wall) * dWVj * ty;
+            wall_pressure_add(ph.kc, min_image(g, xi - pj.x), yi - pj.y, Volw, Bi, acx, acy, p_i, rhoh_i, px, py);
         };
         if (kRowsAhead<LPP>) {  // (the prefetched rows from registers; lanes with more wall rows read the rest again)
             if (first_wall <= 0 && nn_all > 0) wall_pressure(pj0, aj0.x);
@@ -1125,11 +1174,7 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
         yo += 0.5 * dt * vyi;
         xo += 0.5 * dt * vxn;
         yo += 0.5 * dt * vyn;
-        if (tracked && (!g.own_by_cell || owns(g, 0.0, s.cell[i]))) {  // (a slab bounds the drift of what it owns)
-            const double ddx = min_image(g, xo - pb.x), ddy = yo - pb.y;
-            d2 = ddx * ddx + ddy * ddy;
-            if (d2 != d2) d2 = INFINITY;
-        }
+        if (tracked) d2 = tracked_drift2(g, s, i, xo, yo, pb);
         t.posn[i] = make_double2(g.periodic ? wrap_x(xo, ph.DL) : xo, yo);  // a slab wraps when particles change owner
         t.veln[i] = make_double2(vxn, vyn);
         if (!later) t.fp[i] = make_double2(fpx, fpy);
@@ -1142,18 +1187,9 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
             if (!rebin_near(g, c_binned, h_cell)) atomicOr(t.flags, 1);
         }
     }
-    // largest drift from the binning positions (bounds how stale the cell grid may get, see Clock::drift)
-    d2 = wave_max(d2);
-    __shared__ double s_d2[kBlock / 64];
     __shared__ int s_hc[HIST ? kBlock / LPP : 1];
-    if ((threadIdx.x & 63) == 0) s_d2[threadIdx.x >> 6] = d2;
     if (HIST && sub == 0) s_hc[threadIdx.x / LPP] = h_cell;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double m = s_d2[0];
-        for (int k = 1; k < kBlock / 64; ++k) m = fmax(m, s_d2[k]);
-        t.dpart[blk] = m;
-    }
+    store_block_drift(t, blk, d2);  // (its barrier also closes s_hc)
     // HIST: a workgroup's particles are neighbours in the old ordering and land in two or three cells: one atomic per cell and
     // workgroup instead of one per particle (fifteen particles of a cell, in as many workgroups on eight L2s, queue up on one word)
     if (HIST && threadIdx.x < kBlock / LPP) {
@@ -1243,6 +1279,44 @@ __device__ __forceinline__ void walk_fluid_rows(const FluidTmp &t, int tid, int 
     }
 }
 
+// The five forms of a fluid-row walk (large-channel passes B, CD and E), one per wavefront:
+//   slot-coded lists: near the periodic seam (fold) / every entry in the tile (all_near, see kFarTileBit) / the general one;
+//   index differences: near the seam (wrap and fold) / plain.
+// near(code), coded(code), plain(k) fetch the neighbour's record, a struct whose member p is its position; pair(record, dx)
+// is the pair term, dx folded where it has to be.  The fetches stay the callers' own: their early returns and LDS-qualified reads
+// keep the compiler from merging the tile arm and the global arm into FLAT loads through selected pointers (see k_kgc_w).
+template <bool CODED, typename Near, typename Coded, typename Plain, typename Pair>
+__device__ __forceinline__ void walk_fluid_forms(const Grid &g, const FluidTmp &t, int tid, int i, int n_now, int rows_fl, int w0, int w1,
+                                                 double xi, bool seam, bool all_near, Near &&near, Coded &&coded, Plain &&plain,
+                                                 Pair &&pair)
+{
+    if (CODED && seam)
+        walk_fluid_rows<true>(t, tid, i, rows_fl, w0, w1, [&](int e) {
+            const auto n = coded(e);
+            pair(n, min_image(g, xi - n.p.x));
+        });
+    else if (CODED && all_near)
+        walk_fluid_rows<true>(t, tid, i, rows_fl, w0, w1, [&](int e) {
+            const auto n = near(e);
+            pair(n, xi - n.p.x);
+        });
+    else if (CODED)
+        walk_fluid_rows<true>(t, tid, i, rows_fl, w0, w1, [&](int e) {
+            const auto n = coded(e);
+            pair(n, xi - n.p.x);
+        });
+    else if (seam)
+        walk_fluid_rows(t, tid, i, rows_fl, w0, w1, [&](int k) {
+            const auto n = plain(wrap_index(k, n_now));
+            pair(n, min_image(g, xi - n.p.x));
+        });
+    else
+        walk_fluid_rows(t, tid, i, rows_fl, w0, w1, [&](int k) {
+            const auto n = plain(k);
+            pair(n, xi - n.p.x);
+        });
+}
+
 // Rows [rows_fl, rows) hold wall neighbours (only next to a wall): body(k)
 template <typename Body>
 __device__ __forceinline__ void walk_wall_rows(const FluidTmp &t, int tid, int rows_fl, int rows, Body &&body)
@@ -1268,7 +1342,7 @@ struct TileMap {
     __device__ __forceinline__ int total() const { return len0 + len1 + len2; }
     __device__ __forceinline__ int index(int sl) const  // staged slot -> particle
     {
-        return sl < len0 ? lo0 + sl : (sl < len0 + len1 ? lo1 + (sl - len0) : lo2 + (sl - len0 - len1));
+        return ranges_index(lo0, lo1, lo2, len0, len1, sl);
     }
     __device__ __forceinline__ int slot(int k) const  // particle -> staged slot, -1: not staged
     {
@@ -1330,6 +1404,25 @@ __device__ __forceinline__ TileMap staged_map(const TileMap &layout, int blk, in
     return layout.capped(cap);
 }
 
+// Staging a tile: thread x fills slots x and x + kBlock of the staged map tm -- store(slot, load(particle)) -- and the workgroup
+// meets at a barrier.  Both of a thread's slots are requested before either is waited for: as a loop, the second trip's
+// loads left only after the first trip's had come back and gone to LDS -- a memory round trip more in the prologue every
+// workgroup of the CU waits through.
+template <int TILE, typename Load, typename Store>
+__device__ __forceinline__ void stage_tile(const TileMap &tm, Load &&load, Store &&store)
+{
+    static_assert(TILE <= 2 * kBlock, "two slots per thread");
+    const int total = tm.total(), sl0 = threadIdx.x, sl1 = threadIdx.x + kBlock;
+    const bool h0 = sl0 < total, h1 = sl1 < total;
+    const int k0 = tm.index(h0 ? sl0 : 0) + n2_prologue_cost(sl0, tm), k1 = tm.index(h1 ? sl1 : 0) + n2_prologue_cost(sl1, tm);
+    decltype(load(0)) r0, r1;
+    if (h0) r0 = load(k0);
+    if (h1) r1 = load(k1);
+    if (h0) store(sl0, r0);
+    if (h1) store(sl1, r1);
+    __syncthreads();
+}
+
 // the particle a slot-coded entry of particle i names (full: the layout at capacity kSlotCodes); the passes call this only for
 // the entries their tile does not hold
 __device__ __forceinline__ int coded_index(const TileMap &full, int code, int i, int n)
@@ -1358,15 +1451,8 @@ __device__ __forceinline__ TileMap tile_ranges(const Grid &g, const FluidSet &s,
     int lo[3], len[3];
 #pragma unroll
     for (int ox = -1; ox <= 1; ++ox) {
-        int col = cx + ox;
-        bool ok = true;
-        if (g.periodic) {
-            if (duplicate_column(g, ox)) ok = false;
-            if (col < 0) col += g.ncx;
-            else if (col >= g.ncx) col -= g.ncx;
-        } else if (col < 0 || col >= g.ncx) {
-            ok = false;
-        }
+        int col;
+        const bool ok = neighbour_column(g, cx, ox, col);
         const int a0 = ok ? s.start[col * g.ncy + ra] : 0, a1 = ok ? s.start[col * g.ncy + rb] : 0;
         lo[ox + 1] = a0;
         len[ox + 1] = a1 - a0;
@@ -1426,55 +1512,13 @@ __device__ __forceinline__ void density_walk_body(const Clock *clk, int q, const
     TileMap tm{0, 0, 0, 0, 0, 0};
     if (TILE > 0) {  // candidate positions of the workgroup's three-column neighbourhood staged in LDS (see tile_ranges)
         tm = staged_map<LPP>(layout, blk, n_now, TILE);
-        static_assert(TILE <= 2 * kBlock, "two slots per thread");
-        {  // (both of a thread's slots requested before either is waited for: see k_forces_w)
-            const int total = tm.total(), sl0 = threadIdx.x, sl1 = threadIdx.x + kBlock;
-            const bool h0 = sl0 < total, h1 = sl1 < total;
-            const int k0 = tm.index(h0 ? sl0 : 0) + n2_prologue_cost(sl0, tm), k1 = tm.index(h1 ? sl1 : 0) + n2_prologue_cost(sl1, tm);
-            double2 p0, p1;
-            if (h0) p0 = s.pos[k0];
-            if (h1) p1 = s.pos[k1];
-            if (h0) c_pos[sl0] = p0;
-            if (h1) c_pos[sl1] = p1;
-        }
-        __syncthreads();
+        stage_tile<TILE>(tm, [&](int k) { return s.pos[k]; }, [&](int sl, const double2 &p) { c_pos[sl] = p; });
     }
-    const int lane = threadIdx.x & 63, gbase = lane & ~(LPP - 1);
-    const int row_base = tid - sub;
-    const int half_shift = gbase & 31;
-    const unsigned grp_mask = LPP >= 32 ? 0xffffffffu : ((1u << (LPP & 31)) - 1u);
-    const unsigned below_me = (1u << sub) - 1u;
-    auto group_bits = [&](bool acc) -> unsigned {
-        const unsigned long long bal = __ballot(acc);
-        const unsigned half = lane < 32 ? (unsigned)bal : (unsigned)(bal >> 32);
-        return (half >> half_shift) & grp_mask;
-    };
+    const LaneGroup<LPP> lg(tid, sub);
     int cnt = 0;
     // the step's list takes the candidate's entry as it stands in the superset list: a fluid entry is the index difference to
     // THIS particle in both, a wall entry the wall slot
-    // (2 lanes per particle: who else accepts is one DPP move away -- the ballot, the half select, the shift and the two
-    //  popcounts were 9 of the ~55 vector instructions of a candidate in a pass that is ALU-bound; unsigned row arithmetic:
-    //  m / LPP on a signed m costs a sign fix-up per use)
-    auto push = [&](bool acc, int entry, bool wall) {
-        int below, all;
-        if constexpr (LPP == 2) {
-            const int mine = acc ? 1 : 0, other = pair_partner(mine);
-            below = sub ? other : 0;
-            all = mine + other;
-        } else {
-            const unsigned grp = LPP == 1 ? (acc ? 1u : 0u) : group_bits(acc);
-            below = __popc(grp & below_me);
-            all = __popc(grp);
-        }
-        if (acc) {
-            const unsigned m = (unsigned)(cnt + below), row = m / LPP, col = (unsigned)row_base + m % LPP;
-            if ((int)row < t.nl_cap) {
-                if (wall) t.nl_idx[(size_t)row * t.nl_stride + col] = entry;
-                else put_delta(t.nl_pk, t.nl_stride, (int)row, (int)col, entry);
-            }
-        }
-        cnt += all;
-    };
+    auto push = [&](bool acc, int entry, bool wall) { list_push_w(lg, t.nl_idx, t.nl_pk, t.nl_cap, t.nl_stride, cnt, acc, entry, wall); };
     const int ns = active ? list_rows(spacked) : 0;
     // group-uniform trip counts: lane 0 of the group owns the most rows, its last lane the fewest fluid rows
     const int rows_all = group_extreme<LPP, true>(ns);
@@ -1585,24 +1629,16 @@ __device__ __forceinline__ void density_walk_body(const Clock *clk, int q, const
                 else s_in += W;
             }
         }
-        cnt_fl += LPP == 1 ? ((acc && !wall) ? 1 : 0) : __popc(group_bits(acc && !wall));
+        cnt_fl += LPP == 1 ? ((acc && !wall) ? 1 : 0) : __popc(lg.bits(acc && !wall));
         push(acc, e, wall);
     }
     if (active && cnt > t.nl_cap * LPP) { atomicOr(t.flags, 1); cnt = t.nl_cap * LPP; }
     cnt_fl = min(cnt_fl, cnt);
     if (tid < t.nl_stride)
-        t.nl_cnt[tid] = (cnt > sub ? (cnt - sub + LPP - 1) / LPP : 0) | ((cnt_fl > sub ? (cnt_fl - sub + LPP - 1) / LPP : 0) << 16) |
-                        (CODED ? spacked & (kFarForcesBit | kFarTileBit) : 0);
+        t.nl_cnt[tid] = list_row_counts<LPP>(cnt, cnt_fl, sub) | (CODED ? spacked & (kFarForcesBit | kFarTileBit) : 0);
     s_in = group_sum<LPP>(s_in);
     s_ct = group_sum<LPP>(s_ct);
-    if (active && sub == 0) {
-        const double rho = density_from_sigma(ph.w0 + s_in, s_ct, mass_i, ph.rho0, ph.inv_sigma0);
-        double rhoh = rho + 0.5 * dt * drho_i;
-        if (rhoh < 1e-10) rhoh = ph.rho0;
-        t.a[i] = half ? make_double4(mass_i / rho, eos_pressure(rhoh, ph.rho0, ph.p0), rhoh, rho)
-                      : make_double4(mass_i / rho, 0.0, 0.0, rho);
-        t.vol[i] = mass_i / rho;
-    }
+    if (active && sub == 0) store_density(ph, t, i, s_in, s_ct, mass_i, drho_i, dt, half);
 }
 
 // pass A, sweeping the cells (see density_body MODE 0 / 1), large-channel form.  At a few lanes per particle a lane tests
@@ -1636,36 +1672,9 @@ __device__ __forceinline__ void density_sweep_body_w(const Clock *clk, int q, co
     }
     double s_in = 0.0, s_ct = 0.0;
     int cnt = 0, scnt = 0;
-    const int lane = threadIdx.x & 63, gbase = lane & ~(LPP - 1);
-    const int row_base = tid - sub;
-    const int half_shift = gbase & 31;
-    const unsigned grp_mask = LPP >= 32 ? 0xffffffffu : ((1u << (LPP & 31)) - 1u);
-    const unsigned below_me = (1u << sub) - 1u;
-    auto group_bits = [&](bool acc) -> unsigned {
-        const unsigned long long bal = __ballot(acc);
-        const unsigned half_ = lane < 32 ? (unsigned)bal : (unsigned)(bal >> 32);
-        return (half_ >> half_shift) & grp_mask;
-    };
-    // fluid entries go to the packed list as index differences to this group's particle, wall entries to the 32-bit one
-    auto push_to = [&](int *idx, int *pk, int cap, int &n, bool acc, int entry, bool wall) {  // (see push of density_walk_body)
-        int below, all;
-        if constexpr (LPP == 2) {
-            const int mine = acc ? 1 : 0, other = pair_partner(mine);
-            below = sub ? other : 0;
-            all = mine + other;
-        } else {
-            const unsigned grp = LPP == 1 ? (acc ? 1u : 0u) : group_bits(acc);
-            below = __popc(grp & below_me);
-            all = __popc(grp);
-        }
-        if (acc) {
-            const unsigned m = (unsigned)(n + below), row = m / LPP, col = (unsigned)row_base + m % LPP;
-            if ((int)row < cap) {
-                if (wall) idx[(size_t)row * t.nl_stride + col] = entry;
-                else put_delta(pk, t.nl_stride, (int)row, (int)col, entry);
-            }
-        }
-        n += all;
+    const LaneGroup<LPP> lg(tid, sub);
+    auto push_to = [&](int *idx, int *pk, int cap, int &n, bool acc, int entry, bool wall) {
+        list_push_w(lg, idx, pk, cap, t.nl_stride, n, acc, entry, wall);
     };
     const double xi = pi.x, yi = pi.y;
     int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, wlo[3] = {0, 0, 0}, whi[3] = {0, 0, 0};
@@ -1676,15 +1685,8 @@ __device__ __forceinline__ void density_sweep_body_w(const Clock *clk, int q, co
         near_wall = w.row_any[cy] != 0;
 #pragma unroll
         for (int ox = -1; ox <= 1; ++ox) {
-            int col = cx + ox;
-            bool ok = true;
-            if (g.periodic) {
-                if (duplicate_column(g, ox)) ok = false;
-                if (col < 0) col += g.ncx;
-                else if (col >= g.ncx) col -= g.ncx;
-            } else if (col < 0 || col >= g.ncx) {
-                ok = false;
-            }
+            int col;
+            const bool ok = neighbour_column(g, cx, ox, col);
             const int c0 = col * g.ncy + cylo, c1 = col * g.ncy + cyhi + 1;
             lo[ox + 1] = ok ? s.start[c0] : 0;
             hi[ox + 1] = ok ? s.start[c1] : 0;
@@ -1692,7 +1694,7 @@ __device__ __forceinline__ void density_sweep_body_w(const Clock *clk, int q, co
             whi[ox + 1] = ok ? w.start[c1] : 0;
         }
     }
-    // the three ranges as ONE virtual index range (see density_body); a group's lanes take LPP consecutive candidates per trip
+    // the three ranges as one (see ranges_index); a group's lanes take LPP consecutive candidates per trip
     const int n0 = hi[0] - lo[0], n1 = hi[1] - lo[1], n2 = hi[2] - lo[2];
     const int nfl = n0 + n1 + n2;
     // v -> particle index: two independent selects (a nested choice of three becomes branches, or a table in scratch memory)
@@ -1784,7 +1786,7 @@ __device__ __forceinline__ void density_sweep_body_w(const Clock *clk, int q, co
     if (near_wall) {
         const int w0 = whi[0] - wlo[0], w1 = whi[1] - wlo[1], w2 = whi[2] - wlo[2];
         const int nwl = w0 + w1 + w2;
-        auto wall_index = [&](int v) { return v < w0 ? wlo[0] + v : (v < w0 + w1 ? wlo[1] + (v - w0) : wlo[2] + (v - w0 - w1)); };
+        auto wall_index = [&](int v) { return ranges_index(wlo[0], wlo[1], wlo[2], w0, w1, v); };
         if (nwl > 0) {
             int ka = wall_index(min(sub, nwl - 1));
             double2 pa = w.pos[ka];
@@ -1810,20 +1812,11 @@ __device__ __forceinline__ void density_sweep_body_w(const Clock *clk, int q, co
     if (record && active && scnt > t.sl_cap * LPP) { atomicOr(t.flags, 1); scnt = t.sl_cap * LPP; }
     scnt_fl = min(scnt_fl, scnt);
     const int far_bits = CODED ? far_parked[threadIdx.x] : 0;
-    if (tid < t.nl_stride)
-        t.nl_cnt[tid] = (cnt > sub ? (cnt - sub + LPP - 1) / LPP : 0) | ((cnt_fl > sub ? (cnt_fl - sub + LPP - 1) / LPP : 0) << 16) | far_bits;
-    if (record && tid < t.nl_stride)
-        t.sl_cnt[tid] = (scnt > sub ? (scnt - sub + LPP - 1) / LPP : 0) | ((scnt_fl > sub ? (scnt_fl - sub + LPP - 1) / LPP : 0) << 16) | far_bits;
+    if (tid < t.nl_stride) t.nl_cnt[tid] = list_row_counts<LPP>(cnt, cnt_fl, sub) | far_bits;
+    if (record && tid < t.nl_stride) t.sl_cnt[tid] = list_row_counts<LPP>(scnt, scnt_fl, sub) | far_bits;
     s_in = group_sum<LPP>(s_in);
     s_ct = group_sum<LPP>(s_ct);
-    if (active && sub == 0) {
-        const double rho = density_from_sigma(ph.w0 + s_in, s_ct, mass_i, ph.rho0, ph.inv_sigma0);
-        double rhoh = rho + 0.5 * dt * drho_i;
-        if (rhoh < 1e-10) rhoh = ph.rho0;
-        t.a[i] = half ? make_double4(mass_i / rho, eos_pressure(rhoh, ph.rho0, ph.p0), rhoh, rho)
-                      : make_double4(mass_i / rho, 0.0, 0.0, rho);
-        t.vol[i] = mass_i / rho;
-    }
+    if (active && sub == 0) store_density(ph, t, i, s_in, s_ct, mass_i, drho_i, dt, half);
 }
 
 // n_tiles: workgroup-sized tiles of the pass; the grid may be smaller (grid-stride over the tiles: the conditional launches
@@ -1874,19 +1867,9 @@ __global__ __launch_bounds__(kBlock) void k_kgc_w(const Clock *clk, int q, Grid 
     TileMap tm{0, 0, 0, 0, 0, 0};
     if (TILE > 0) {
         tm = staged_map<LPP>(layout, blk, n_now, TILE);
-        static_assert(TILE <= 2 * kBlock, "two slots per thread");
-        {  // (both of a thread's slots requested before either is waited for: see k_forces_w)
-            const int total = tm.total(), sl0 = threadIdx.x, sl1 = threadIdx.x + kBlock;
-            const bool h0 = sl0 < total, h1 = sl1 < total;
-            const int k0 = tm.index(h0 ? sl0 : 0) + n2_prologue_cost(sl0, tm), k1 = tm.index(h1 ? sl1 : 0) + n2_prologue_cost(sl1, tm);
-            double2 p0, p1;
-            double u0, u1;
-            if (h0) { p0 = s.pos[k0]; u0 = t.vol[k0]; }
-            if (h1) { p1 = s.pos[k1]; u1 = t.vol[k1]; }
-            if (h0) { c_pos[sl0] = p0; c_vol[sl0] = u0; }
-            if (h1) { c_pos[sl1] = p1; c_vol[sl1] = u1; }
-        }
-        __syncthreads();
+        struct Rec { double2 p; double vol; };
+        stage_tile<TILE>(tm, [&](int k) { return Rec{s.pos[k], t.vol[k]}; },
+                         [&](int sl, const Rec &r) { c_pos[sl] = r.p; c_vol[sl] = r.vol; });
     }
     // (early return, not if/else: the compiler would merge the two arms into one FLAT load through a selected pointer)
     auto fetch = [&](int k, double2 &pj, double &Volj) {
@@ -1899,15 +1882,7 @@ __global__ __launch_bounds__(kBlock) void k_kgc_w(const Clock *clk, int q, Grid 
     const int rows = active ? list_rows(packed) : 0, rows_fl = active ? list_fluid_rows(packed) : 0;
     const double xi = pi.x, yi = pi.y;
     double a11 = 0.0, a12 = 0.0, a21 = 0.0, a22 = 0.0;
-    auto term = [&](double dx, double dy, double Volj) {
-        const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-        const double ex = dx * inv_r, ey = dy * inv_r;
-        const double fxj = spline_dW_in(ph.kc, r) * Volj;
-        a11 -= dx * (fxj * ex);
-        a12 -= dx * (fxj * ey);
-        a21 -= dy * (fxj * ex);
-        a22 -= dy * (fxj * ey);
-    };
+    auto term = [&](double dx, double dy, double Volj) { kgc_moment_add(ph.kc, dx, dy, Volj, a11, a12, a21, a22); };
     auto fetch_code = [&](int e, double2 &pj, double &Volj) {  // (CODED; early return: see above)
         // (LDS-qualified reads: with plain ones the compiler folds both arms into FLAT loads through selected pointers)
 #if SPHX_EXP_PRETEND_COMPLETE_TILE & 2
@@ -1919,6 +1894,7 @@ __global__ __launch_bounds__(kBlock) void k_kgc_w(const Clock *clk, int q, Grid 
     };
     const bool seam = __any(active && near_seam(g, xi));
     const bool all_near = CODED && !__any(packed & kFarTileBit);  // (see kFarTileBit)
+    // (the five forms written out, not through walk_fluid_forms: with it k_kgc_w<2, 480, true> takes two scalar registers more)
     if (CODED && seam)
         walk_fluid_rows<true>(t, tid, i, rows_fl, w0, w1, [&](int e) {
             double2 pj; double Volj;
@@ -2014,22 +1990,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TILE > 4
     TileMap tm{0, 0, 0, 0, 0, 0};
     if (TILE > 0) {
         tm = staged_map<LPP>(layout, blk, n_now, TILE);
-        // (a thread stages up to two slots: both requested before either is waited for -- as a loop, the second trip's
-        //  loads left only after the first trip's had come back and gone to LDS: a memory round trip more in the prologue
-        //  every workgroup of the CU waits through)
-        static_assert(TILE <= 2 * kBlock, "two slots per thread");
-        {
-            const int total = tm.total(), sl0 = threadIdx.x, sl1 = threadIdx.x + kBlock;
-            const bool h0 = sl0 < total, h1 = sl1 < total;
-            const int k0 = tm.index(h0 ? sl0 : 0) + n2_prologue_cost(sl0, tm), k1 = tm.index(h1 ? sl1 : 0) + n2_prologue_cost(sl1, tm);
-            double2 p0, v0, p1, v1;
-            double4 a0, B0, a1, B1;
-            if (h0) { p0 = s.pos[k0]; v0 = s.vel[k0]; a0 = t.a[k0]; B0 = t.B[k0]; }
-            if (h1) { p1 = s.pos[k1]; v1 = s.vel[k1]; a1 = t.a[k1]; B1 = t.B[k1]; }
-            if (h0) { c_pos[sl0] = p0; c_vel[sl0] = v0; c_vp[sl0] = make_double2(a0.x, a0.y); c_rh[sl0] = a0.z; c_B[sl0] = B0; }
-            if (h1) { c_pos[sl1] = p1; c_vel[sl1] = v1; c_vp[sl1] = make_double2(a1.x, a1.y); c_rh[sl1] = a1.z; c_B[sl1] = B1; }
-        }
-        __syncthreads();
+        stage_tile<TILE>(tm, [&](int k) { return FluidNb{s.pos[k], s.vel[k], t.a[k], t.B[k]}; }, [&](int sl, const FluidNb &n) {
+            c_pos[sl] = n.p; c_vel[sl] = n.v; c_vp[sl] = make_double2(n.a.x, n.a.y); c_rh[sl] = n.a.z; c_B[sl] = n.B;
+        });
     }
     const int n_staged = tm.total();
     auto fetch_code = [&](int e) {  // (CODED)
@@ -2073,9 +2036,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TILE > 4
     //   * mu is multiplied into the viscous sums once, after the walk.
     const double c_f8 = 0.125 * ph.c_f;
     auto fluid_pair = [&](const FluidNb &n, double dx) {
-        const double dy = yi - n.p.y;
-        const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-        const double ex = dx * inv_r, ey = dy * inv_r;
+        const auto [r, ex, ey] = pair_geom(dx, yi - n.p.y);
         const double dWVj = spline_dW_in(ph.kc, r) * n.a.x;
         const double tx = (b11i + n.B.x) * ex + (b12i + n.B.y) * ey;
         const double ty = (b21i + n.B.z) * ex + (b22i + n.B.w) * ey;
@@ -2098,48 +2059,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TILE > 4
     };
     const bool seam = __any(active && near_seam(g, xi));
     const bool all_near = CODED && TILE == kForceSlots && !__any(packed & kFarForcesBit);  // (see kFarTileBit)
-    if (CODED && seam)
-        walk_fluid_rows<true>(t, tid, i, rows_fl, w0, w1, [&](int e) {
-            const FluidNb n = fetch_code(e);
-            fluid_pair(n, min_image(g, xi - n.p.x));
-        });
-    else if (CODED && all_near)
-        walk_fluid_rows<true>(t, tid, i, rows_fl, w0, w1, [&](int e) {
-            FluidNb n;
-            const double2 vp = lds_double2(c_vp, e);
-            n.p = lds_double2(c_pos, e); n.v = lds_double2(c_vel, e); n.a = make_double4(vp.x, vp.y, lds_double(c_rh, e), 0.0); n.B = lds_double4(c_B, e);
-            fluid_pair(n, xi - n.p.x);
-        });
-    else if (CODED)
-        walk_fluid_rows<true>(t, tid, i, rows_fl, w0, w1, [&](int e) {
-            const FluidNb n = fetch_code(e);
-            fluid_pair(n, xi - n.p.x);
-        });
-    else if (seam)
-        walk_fluid_rows(t, tid, i, rows_fl, w0, w1, [&](int k) {
-            const FluidNb n = fetch(wrap_index(k, n_now));
-            fluid_pair(n, min_image(g, xi - n.p.x));
-        });
-    else
-        walk_fluid_rows(t, tid, i, rows_fl, w0, w1, [&](int k) {
-            const FluidNb n = fetch(k);
-            fluid_pair(n, xi - n.p.x);
-        });
+    auto fetch_near = [&](int e) {  // (CODED, all_near)
+        FluidNb n;
+        const double2 vp = lds_double2(c_vp, e);
+        n.p = lds_double2(c_pos, e); n.v = lds_double2(c_vel, e); n.a = make_double4(vp.x, vp.y, lds_double(c_rh, e), 0.0); n.B = lds_double4(c_B, e);
+        return n;
+    };
+    walk_fluid_forms<CODED>(g, t, tid, i, n_now, rows_fl, w0, w1, xi, seam, all_near, fetch_near, fetch_code, fetch, fluid_pair);
     // wall neighbours: viscous and transport now, pressure once force_prior is complete (p_wall needs it, :931-934)
     walk_wall_rows(t, tid, rows_fl, rows, [&](int k) {
         const double2 pj = w.pos[k];
         const double4 wj = w.a[k];
-        const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-        const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-        const double ex = dx * inv_r, ey = dy * inv_r;
-        const double dWVj = spline_dW_in(ph.kc, r) * wj.x;
-        const double tx = b11i * ex + b12i * ey, ty = b21i * ex + b22i * ey;
-        const double eBe = ex * tx + ey * ty;
-        const double coeff = 4.0 * eBe * dWVj * rcp_nr(r + soft);  // (mu: after the walk, see fluid_pair)
+        const WallPair wp = wall_pair(ph.kc, min_image(g, xi - pj.x), yi - pj.y, wj.x, Bi);
+        const double coeff = 4.0 * wp.eBe * wp.dWVj * rcp_nr(wp.r + soft);  // (mu: after the walk, see fluid_pair)
         ax += coeff * (vxi - wj.y);
         ay += coeff * (vyi - wj.z);
-        ix -= 2.0 * dWVj * tx;
-        iy -= 2.0 * dWVj * ty;
+        ix -= 2.0 * wp.dWVj * wp.tx;
+        iy -= 2.0 * wp.dWVj * wp.ty;
     });
     ax = group_sum<LPP>(ax) * ph.mu;
     ay = group_sum<LPP>(ay) * ph.mu;
@@ -2152,15 +2088,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TILE > 4
         const double acx = fpx * inv_m, acy = fpy * inv_m;
         walk_wall_rows(t, tid, rows_fl, rows, [&](int k) {
             const double2 pj = w.pos[k];
-            const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-            const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-            const double ex = dx * inv_r, ey = dy * inv_r;
-            const double dWVj = spline_dW_in(ph.kc, r) * w.a[k].x;
-            const double face = -(acx * ex + acy * ey);
-            const double p_wall = p_i + rhoh_i * r * fmax(0.0, face);
-            const double tx = b11i * ex + b12i * ey, ty = b21i * ex + b22i * ey;
-            px -= (p_i + p_wall) * dWVj * tx;
-            py -= (p_i + p_wall) * dWVj * ty;
+            wall_pressure_add(ph.kc, min_image(g, xi - pj.x), yi - pj.y, w.a[k].x, Bi, acx, acy, p_i, rhoh_i, px, py);
         });
     }
     px = group_sum<LPP>(px);
@@ -2177,11 +2105,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TILE > 4
         yo += 0.5 * dt * vyi;
         xo += 0.5 * dt * vxn;
         yo += 0.5 * dt * vyn;
-        if (tracked && (!g.own_by_cell || owns(g, 0.0, s.cell[i]))) {  // (a slab bounds the drift of what it owns)
-            const double ddx = min_image(g, xo - pb.x), ddy = yo - pb.y;
-            d2 = ddx * ddx + ddy * ddy;
-            if (d2 != d2) d2 = INFINITY;
-        }
+        if (tracked) d2 = tracked_drift2(g, s, i, xo, yo, pb);
         // periodic wrap (SPH_Poiseuille.m:570-577): a step moves a particle by a tiny fraction of DL, so x - floor(x/DL) DL
         // is x - DL, x + DL or x -- the same values without the division (a slab wraps when particles change owner)
         if (g.periodic) xo = xo >= ph.DL ? xo - ph.DL : (xo < 0.0 ? xo + ph.DL : xo);
@@ -2192,16 +2116,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TILE > 4
             t.f[i] = make_double2(fx, fy);
         }
     }
-    // largest drift from the binning positions (bounds how stale the cell grid may get, see Clock::drift)
-    d2 = wave_max(d2);
-    __shared__ double s_d2[kBlock / 64];
-    if ((threadIdx.x & 63) == 0) s_d2[threadIdx.x >> 6] = d2;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double m = s_d2[0];
-        for (int k = 1; k < kBlock / 64; ++k) m = fmax(m, s_d2[k]);
-        t.dpart[blk] = m;
-    }
+    store_block_drift(t, blk, d2);
 }
 
 // block-wide exclusive scan of one int per thread (NT threads); returns the block total
@@ -2376,6 +2291,146 @@ __device__ __forceinline__ void slab_seal_tail(const Clock *clk, int q, const Fl
 // layout `d`.  Histogram, new cells, ids and the runs are requested in the prologue, the first kFoldAhead candidates of every
 // lane in front of the walk.  Workgroup 0 stores the new cell ranges.
 constexpr int kFoldAhead = 8;
+// What a thread holds of the folded re-binning: the particle's new cell and id (every lane of the group), what only the lead lane
+// moves, this thread's share of the histogram, the three runs of the old layout that hold whoever can land in the new cell, and
+// the new cells and ids of the lane's first kFoldAhead candidates
+struct FoldRebin {
+    static constexpr int kPer = kFoldCells / kBlock;
+    int cnew = 0, id = 0, cold = 0, lo[3] = {0, 0, 0}, n[3] = {0, 0, 0}, hist[kPer], ccell[kFoldAhead], cid[kFoldAhead];
+    double mass = 0.0;
+    __device__ __forceinline__ int candidates() const { return n[0] + n[1] + n[2]; }
+    __device__ __forceinline__ int slot(int v) const { return ranges_index(lo[0], lo[1], lo[2], n[0], n[1], v); }
+};
+// load: what the prologue requests ...
+__device__ __forceinline__ void fold_load(FoldRebin &r, const Grid &g, const FluidSet &s, const FluidTmp &t, int i, bool in_cap, bool lead)
+{
+    r.cnew = in_cap ? t.cellid[i] : 0;
+    r.id = in_cap ? s.id[i] : 0;
+    r.cold = lead ? s.cell[i] : 0;
+    r.mass = lead ? s.mass[i] : 0.0;
+#pragma unroll
+    for (int j = 0; j < FoldRebin::kPer; ++j) r.hist[j] = t.count[min((int)threadIdx.x * FoldRebin::kPer + j, g.ncells)];
+}
+// ... and, behind the clock's loads (these wait for the new cell), the three runs
+__device__ __forceinline__ void fold_runs(FoldRebin &r, const Grid &g, const FluidSet &s)
+{
+    r.cnew = min(max(r.cnew, 0), g.ncells - 1);  // (slots beyond the population hold no cell: any valid one keeps the loads in bounds)
+    const int cxn = r.cnew / g.ncy, cyn = r.cnew - cxn * g.ncy;
+    const int cylo = max(cyn - 1, 0), cyhi = min(cyn + 1, g.ncy - 1);
+#pragma unroll
+    for (int ox = -1; ox <= 1; ++ox) {
+        int col = cxn + ox;  // (at least three columns, periodic: the three are distinct -- neighbour_column's tests are not needed)
+        if (col < 0) col += g.ncx;
+        else if (col >= g.ncx) col -= g.ncx;
+        r.lo[ox + 1] = s.start[col * g.ncy + cylo];
+        r.n[ox + 1] = s.start[col * g.ncy + cyhi + 1] - r.lo[ox + 1];
+    }
+}
+// scan: exclusive scan of the histogram -- the cell ranges of the new ordering, r_start[ncells] = the population (workgroup 0 stores
+// them to the new layout d) -- and the requests for the first candidates of every lane (slot 0 stands in where a lane has fewer)
+template <int LPP>
+__device__ __forceinline__ void fold_scan(FoldRebin &r, const Grid &g, const FluidSet &s, const FluidTmp &t, const FluidSet &d, int bid,
+                                          int sub, int *r_start, int *r_wave)
+{
+    int sum = 0, total;
+#pragma unroll
+    for (int j = 0; j < FoldRebin::kPer; ++j) {
+        const int v = (int)threadIdx.x * FoldRebin::kPer + j < g.ncells ? r.hist[j] : 0;
+        r.hist[j] = sum;
+        sum += v;
+    }
+    const int base = block_exclusive_scan_t<kBlock>(sum, total, r_wave);
+#pragma unroll
+    for (int j = 0; j < FoldRebin::kPer; ++j) {
+        const int c = (int)threadIdx.x * FoldRebin::kPer + j;
+        if (c <= g.ncells) {
+            r_start[c] = base + r.hist[j];
+            if (bid == 0) d.start[c] = base + r.hist[j];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kFoldAhead; ++j) {
+        const int v = sub + j * LPP;
+        const int k = v < r.candidates() ? r.slot(v) : 0;
+        r.ccell[j] = t.cellid[k];
+        r.cid[j] = s.id[k];
+    }
+}
+// rank: the members of the particle's new cell with a smaller id, counted by the lanes of its group
+template <int LPP>
+__device__ __forceinline__ int fold_rank(const FoldRebin &r, const FluidSet &s, const FluidTmp &t, int sub, bool active)
+{
+    int rank = 0;
+    if (active) {
+        const int nv = r.candidates();
+#pragma unroll
+        for (int j = 0; j < kFoldAhead; ++j) rank += (sub + j * LPP < nv && r.ccell[j] == r.cnew && r.cid[j] < r.id) ? 1 : 0;
+        for (int v = sub + kFoldAhead * LPP; v < nv; v += LPP) {
+            const int k = r.slot(v);
+            rank += (t.cellid[k] == r.cnew && s.id[k] < r.id) ? 1 : 0;
+        }
+    }
+    return (int)group_sum<LPP>((double)rank);  // (exact: a handful)
+}
+// store (lead lane): the persistent fields of particle i straight into their slot of the other state and layout d
+__device__ __forceinline__ void fold_store(const FoldRebin &r, const Grid &g, const FluidTmp &t, const FluidSet &d, const int *r_start,
+                                           int rank, int i, const double2 pn, const double2 vi, double drho_new)
+{
+    const int dst = r_start[r.cnew] + rank;
+    // (the clock does not test the drift of the step that re-bins: a particle that is not where the count looked for it
+    //  must not take a slot somebody else may own -- pass CD has raised the flag already, the step ends in SPHX_ERR_GRID)
+    if (rebin_near(g, r.cold, r.cnew) && (unsigned)dst < (unsigned)t.cap) {
+        d.pos[dst] = pn;
+        d.vel[dst] = vi;
+        if (d.posb) d.posb[dst] = pn;
+        d.drho[dst] = drho_new;
+        d.mass[dst] = r.mass;
+        d.id[dst] = r.id;
+        d.cell[dst] = r.cnew;
+        t.src_of[dst] = i;
+    } else {
+        atomicOr(t.flags, 1);
+    }
+}
+
+// Tiled form of pass E: the cell histogram goes through LDS.  A particle's new cell lies within a cell or two of the workgroup's
+// old ones, so the workgroup counts into a window of kCols x kRows cells around its first particle's cell with LDS atomics and
+// adds the window to the global histogram once -- 6 M global atomics, ~60 per cell and step, were 135 us of the pass on every
+// step that takes the histogram (6 M particles).  Anything outside the window is counted globally as before.
+struct HistWindow {
+    static constexpr int kCols = 3, kRows = 48, kLead = 4, kCells = kCols * kRows;
+    int cx0 = 0, r0 = 0;
+    // open: place the window and clear it (a barrier has to follow: the one behind the tile staging)
+    __device__ __forceinline__ void open(const Grid &g, int c_first, int *h_win)
+    {
+        cx0 = c_first / g.ncy - 1;
+        r0 = c_first % g.ncy - kLead;
+        if (threadIdx.x < kCells) h_win[threadIdx.x] = 0;
+    }
+    // count: one particle in cell (cx, cy); false: outside the window
+    __device__ __forceinline__ bool count(const Grid &g, int cx, int cy, int *h_win) const
+    {
+        int dcol = cx - cx0;
+        if (g.periodic) dcol = dcol < 0 ? dcol + g.ncx : (dcol >= g.ncx ? dcol - g.ncx : dcol);
+        const int drow = cy - r0;
+        if ((unsigned)dcol >= (unsigned)kCols || (unsigned)drow >= (unsigned)kRows) return false;
+        atomicAdd(&h_win[dcol * kRows + drow], 1);
+        return true;
+    }
+    // flush (behind a barrier): the window's counts into the global histogram
+    __device__ __forceinline__ void flush(const Grid &g, const FluidTmp &t, const int *h_win) const
+    {
+        if (threadIdx.x >= kCells) return;
+        const int v = h_win[threadIdx.x];
+        if (v) {
+            int col = cx0 + (int)threadIdx.x / kRows;
+            if (g.periodic) col = col < 0 ? col + g.ncx : (col >= g.ncx ? col - g.ncx : col);
+            const int row = r0 + (int)threadIdx.x % kRows;
+            atomicAdd(&t.count[col * g.ncy + row], v);  // (v > 0: somebody's cell, so col and row are inside the grid)
+        }
+    }
+};
 template <int LPP, bool WALK, int TILE, bool CODED = false, bool REBIN = false>
 __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                                 const FluidTmp &t, const Walls &w, int do_hist, int tail, int bid, int nb,
@@ -2407,49 +2462,20 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
     const double2 vi = in_cap ? t.veln[i] : make_double2(0.0, 0.0);
     const int packed = t.nl_cnt[tid];
     const int nn_all = list_rows(packed);
-    // the first rows are requested together with the count (at 32 lanes per particle a lane rarely owns more than
-    // two): count -> entry -> neighbour data becomes {count, entries} -> neighbour data
     // (WALK: the first two words of the packed fluid rows, see FluidTmp::nl_pk)
-    const int *first_rows = WALK ? t.nl_pk : t.nl_idx;
-    const int e_row0 = first_rows[tid], e_row1 = first_rows[(size_t)t.nl_stride + tid];
-    // (rows 2 and 3 only where lanes own that many: few lanes per particle)
-    const int e_row2 = (!WALK && LPP <= 8) ? t.nl_idx[2 * (size_t)t.nl_stride + tid] : 0;
-    const int e_row3 = (!WALK && LPP <= 8) ? t.nl_idx[3 * (size_t)t.nl_stride + tid] : 0;
+    const FirstRows<LPP> first(WALK ? t.nl_pk : t.nl_idx, t.nl_stride, tid);
     const bool lead = in_cap && sub == 0;
     const double4 a_own = lead ? t.a[i] : make_double4(0.0, 0.0, 0.0, 0.0);
     const double rhoh_i = a_own.z;
     const double2 pn = (lead && (do_hist || REBIN)) ? t.posn[i] : make_double2(0.0, 0.0);  // (requested whenever a histogram is possible)
-    // REBIN: the particle's new cell and id (every lane of the group), what only the lead lane moves, this thread's share of the
-    // histogram, and the three runs of the old layout that hold whoever can land in the new cell
-    constexpr int kPer = kFoldCells / kBlock;
-    int r_cnew = 0, r_id = 0, r_cold = 0, r_lo[3] = {0, 0, 0}, r_n[3] = {0, 0, 0}, r_hist[REBIN ? kPer : 1];
-    double r_mass = 0.0;
-    if (REBIN) {
-        r_cnew = in_cap ? t.cellid[i] : 0;
-        r_id = in_cap ? s.id[i] : 0;
-        r_cold = lead ? s.cell[i] : 0;
-        r_mass = lead ? s.mass[i] : 0.0;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) r_hist[j] = t.count[min((int)threadIdx.x * kPer + j, g.ncells)];
-    }
+    FoldRebin fold;
+    if (REBIN) fold_load(fold, g, s, t, i, in_cap, lead);
     const TileMap layout = (WALK && TILE > 0) ? tile_map_of(t, blk) : TileMap{0, 0, 0, 0, 0, 0};
     const double dt = kAhead ? dt_first : clk->dt;
     const bool want_out = !WALK || step_outputs_wanted(clk, t);
     const int cell_own = (g.own_by_cell && lead) ? s.cell[i] : 0;
     if (kAhead) requests_issued();
-    if (REBIN) {  // (behind the clock's loads: these wait for the new cell)
-        r_cnew = min(max(r_cnew, 0), g.ncells - 1);  // (slots beyond the population hold no cell: any valid one keeps the loads in bounds)
-        const int cxn = r_cnew / g.ncy, cyn = r_cnew - cxn * g.ncy;
-        const int cylo = max(cyn - 1, 0), cyhi = min(cyn + 1, g.ncy - 1);
-#pragma unroll
-        for (int ox = -1; ox <= 1; ++ox) {
-            int col = cxn + ox;  // (at least three columns, periodic: the three are distinct)
-            if (col < 0) col += g.ncx;
-            else if (col >= g.ncx) col -= g.ncx;
-            r_lo[ox + 1] = s.start[col * g.ncy + cylo];
-            r_n[ox + 1] = s.start[col * g.ncy + cyhi + 1] - r_lo[ox + 1];
-        }
-    }
+    if (REBIN) fold_runs(fold, g, s);
     if (!(kAhead ? run_first : clk->run[q])) return;
     const int n_now = kAhead ? n_first : clk->n;
     const bool active = i < n_now;
@@ -2458,20 +2484,10 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
     // do_hist: 1 = this step re-bins (static schedule); 100 + K = dynamic context: the K-th step since the last re-binning will
     // re-bin whatever the drift says, so its histogram can be taken here (k_bin then skips)
     const bool hist = do_hist == 1 || (do_hist >= 100 && clk->pos_count >= do_hist - 101);
-    // Tiled form: the cell histogram goes through LDS.  A particle's new cell lies within a cell or two of the workgroup's old
-    // ones, so the workgroup counts into a window of kHistCols x kHistRows cells around its first particle's cell with LDS
-    // atomics and adds the window to the global histogram once -- 6 M global atomics, ~60 per cell and step, were 135 us of the
-    // pass on every step that takes the histogram (6 M particles).  Anything outside the window is counted globally as before.
-    constexpr bool kHistWindow = WALK && TILE > 0;
-    constexpr int kHistCols = 3, kHistRows = 48, kHistLead = 4;
-    __shared__ int h_win[kHistWindow ? kHistCols * kHistRows : 1];
-    int h_cx0 = 0, h_r0 = 0;
-    if (kHistWindow && hist) {
-        const int c_first = s.cell[min(blk * (kBlock / LPP), max(n_now - 1, 0))];
-        h_cx0 = c_first / g.ncy - 1;
-        h_r0 = c_first % g.ncy - kHistLead;
-        if (threadIdx.x < kHistCols * kHistRows) h_win[threadIdx.x] = 0;  // (the barrier behind the tile staging covers this)
-    }
+    constexpr bool kHistWindow = WALK && TILE > 0;  // (tiled form: the histogram goes through LDS)
+    __shared__ int h_win[kHistWindow ? HistWindow::kCells : 1];
+    HistWindow window;
+    if (kHistWindow && hist) window.open(g, s.cell[min(blk * (kBlock / LPP), max(n_now - 1, 0))], h_win);
     // The workgroup's entry of the max |v|^2 reduction needs nothing but the particles' own records.  The compact kernels (small
     // channels) publish it HERE, before the walk, so that the tail workgroup reduces and advances the clock while the walks are
     // still running -- the clock update used to start when the last workgroup had finished (C1 14.55 -> 14.25, C2 17.55 -> 17.35
@@ -2501,107 +2517,42 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
     };
     if (!WALK) publish_vmax();
     __shared__ int r_start[REBIN ? kFoldCells + 1 : 1], r_wave[REBIN ? kBlock / 64 + 1 : 1];
-    const int r_nv = r_n[0] + r_n[1] + r_n[2];
-    auto r_slot = [&](int v) { return v < r_n[0] ? r_lo[0] + v : (v < r_n[0] + r_n[1] ? r_lo[1] + (v - r_n[0]) : r_lo[2] + (v - r_n[0] - r_n[1])); };
-    int r_ccell[REBIN ? kFoldAhead : 1], r_cid[REBIN ? kFoldAhead : 1];
-    if (REBIN) {
-        // exclusive scan of the histogram: the cell ranges of the new ordering, r_start[ncells] = the population
-        int sum = 0, total;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-            const int v = (int)threadIdx.x * kPer + j < g.ncells ? r_hist[j] : 0;
-            r_hist[j] = sum;
-            sum += v;
-        }
-        const int base = block_exclusive_scan_t<kBlock>(sum, total, r_wave);
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-            const int c = (int)threadIdx.x * kPer + j;
-            if (c <= g.ncells) {
-                r_start[c] = base + r_hist[j];
-                if (bid == 0) d.start[c] = base + r_hist[j];
-            }
-        }
-        __syncthreads();
-        // the first candidates of every lane: their new cells and ids (slot 0 stands in where a lane has fewer)
-#pragma unroll
-        for (int j = 0; j < kFoldAhead; ++j) {
-            const int v = sub + j * LPP;
-            const int k = v < r_nv ? r_slot(v) : 0;
-            r_ccell[j] = t.cellid[k];
-            r_cid[j] = s.id[k];
-        }
-    }
+    if (REBIN) fold_scan<LPP>(fold, g, s, t, d, bid, sub, r_start, r_wave);
     if (WALK) {
         const int rows = active ? nn_all : 0, rows_fl = active ? list_fluid_rows(packed) : 0;
+        struct Nb {  // what the pass reads of a fluid neighbour
+            double2 p, v;
+            double vol;
+        };
         TileMap tm{0, 0, 0, 0, 0, 0};
         if (TILE > 0) {
             tm = staged_map<LPP>(layout, blk, n_now, TILE);
-            static_assert(TILE <= 2 * kBlock, "two slots per thread");
-            {  // (both of a thread's slots requested before either is waited for: see k_forces_w)
-                const int total = tm.total(), sl0 = threadIdx.x, sl1 = threadIdx.x + kBlock;
-                const bool h0 = sl0 < total, h1 = sl1 < total;
-                const int k0 = tm.index(h0 ? sl0 : 0) + n2_prologue_cost(sl0, tm), k1 = tm.index(h1 ? sl1 : 0) + n2_prologue_cost(sl1, tm);
-                double2 p0, p1, v0, v1;
-                double u0, u1;
-                if (h0) { p0 = s.pos[k0]; v0 = t.veln[k0]; u0 = t.vol[k0]; }
-                if (h1) { p1 = s.pos[k1]; v1 = t.veln[k1]; u1 = t.vol[k1]; }
-                if (h0) { c_pos[sl0] = p0; c_vel[sl0] = v0; c_vol[sl0] = u0; }
-                if (h1) { c_pos[sl1] = p1; c_vel[sl1] = v1; c_vol[sl1] = u1; }
-            }
-            __syncthreads();
+            stage_tile<TILE>(tm, [&](int k) { return Nb{s.pos[k], t.veln[k], t.vol[k]}; },
+                             [&](int sl, const Nb &n) { c_pos[sl] = n.p; c_vel[sl] = n.v; c_vol[sl] = n.vol; });
         }
-        auto fetch = [&](int k, double2 &pj, double2 &vj, double &Volj) {
+        auto fetch_near = [&](int e) { return Nb{lds_double2(c_pos, e), lds_double2(c_vel, e), lds_double(c_vol, e)}; };
+        auto fetch = [&](int k) {
             if (TILE > 0) {  // (early return, not if/else: see k_kgc_w)
                 const int slot = tm.slot(k);
-                if (slot >= 0) { pj = lds_double2(c_pos, slot); vj = lds_double2(c_vel, slot); Volj = lds_double(c_vol, slot); return; }
+                if (slot >= 0) return fetch_near(slot);
             }
-            pj = s.pos[k]; vj = t.veln[k]; Volj = t.vol[k];
+            return Nb{s.pos[k], t.veln[k], t.vol[k]};
         };
         auto term = [&](double dx, double dy, double ujx, double ujy, double Volj) {
-            const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-            const double ex = dx * inv_r, ey = dy * inv_r;
-            rate += ((vxi - ujx) * ex + (vyi - ujy) * ey) * spline_dW_sel(ph.kc, r) * Volj;
+            continuity_add(ph.kc, dx, dy, vxi, vyi, ujx, ujy, Volj, rate);
         };
-        auto fetch_code = [&](int e, double2 &pj, double2 &vj, double &Volj) {  // (CODED)
+        auto fetch_code = [&](int e) {  // (CODED)
 #if SPHX_EXP_PRETEND_COMPLETE_TILE & 8
             e = min(e, kSlotCodes - 1);  // MEASUREMENT ONLY, see k_forces_w
 #endif
-            if (e < kSlotCodes) { pj = lds_double2(c_pos, e); vj = lds_double2(c_vel, e); Volj = lds_double(c_vol, e); return; }
+            if (e < kSlotCodes) return fetch_near(e);
             const int k = wrap_index(i + e - kCodeBias, n_now);
-            pj = s.pos[k]; vj = t.veln[k]; Volj = t.vol[k];
+            return Nb{s.pos[k], t.veln[k], t.vol[k]};
         };
         const bool seam = __any(active && near_seam(g, xi));
         const bool all_near = CODED && !__any(packed & kFarTileBit);  // (see kFarTileBit)
-        if (CODED && seam)
-            walk_fluid_rows<true>(t, tid, i, rows_fl, e_row0, e_row1, [&](int e) {
-                double2 pj, vj; double Volj;
-                fetch_code(e, pj, vj, Volj);
-                term(min_image(g, xi - pj.x), yi - pj.y, vj.x, vj.y, Volj);
-            });
-        else if (CODED && all_near)
-            walk_fluid_rows<true>(t, tid, i, rows_fl, e_row0, e_row1, [&](int e) {
-                const double2 pj = lds_double2(c_pos, e), vj = lds_double2(c_vel, e);
-                term(xi - pj.x, yi - pj.y, vj.x, vj.y, lds_double(c_vol, e));
-            });
-        else if (CODED)
-            walk_fluid_rows<true>(t, tid, i, rows_fl, e_row0, e_row1, [&](int e) {
-                double2 pj, vj; double Volj;
-                fetch_code(e, pj, vj, Volj);
-                term(xi - pj.x, yi - pj.y, vj.x, vj.y, Volj);
-            });
-        else if (seam)
-            walk_fluid_rows(t, tid, i, rows_fl, e_row0, e_row1, [&](int k) {
-                double2 pj, vj; double Volj;
-                fetch(wrap_index(k, n_now), pj, vj, Volj);
-                term(min_image(g, xi - pj.x), yi - pj.y, vj.x, vj.y, Volj);
-            });
-        else
-            walk_fluid_rows(t, tid, i, rows_fl, e_row0, e_row1, [&](int k) {
-                double2 pj, vj; double Volj;
-                fetch(k, pj, vj, Volj);
-                term(xi - pj.x, yi - pj.y, vj.x, vj.y, Volj);
-            });
+        walk_fluid_forms<CODED>(g, t, tid, i, n_now, rows_fl, first.e0, first.e1, xi, seam, all_near, fetch_near, fetch_code, fetch,
+                                [&](const Nb &n, double dx) { term(dx, yi - n.p.y, n.v.x, n.v.y, n.vol); });
         walk_wall_rows(t, tid, rows_fl, rows, [&](int k) {
             const double2 pj = w.pos[k];
             const double4 wj = w.a[k];  // {Vol, vx, vy, -}; the wall presents its velocity mirrored through the particle's
@@ -2609,11 +2560,7 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
         });
     } else if (active) {
         auto term = [&](const double2 pj, const double2 vj, double Volj) {
-            const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
-            const double r2 = dx * dx + dy * dy, inv_r = rsqrt_nr(r2), r = r2 * inv_r;
-            const double ex = dx * inv_r, ey = dy * inv_r;
-            const double u_jump = (vxi - vj.x) * ex + (vyi - vj.y) * ey;
-            rate += u_jump * spline_dW_sel(ph.kc, r) * Volj;
+            continuity_add(ph.kc, min_image(g, xi - pj.x), yi - pj.y, vxi, vyi, vj.x, vj.y, Volj, rate);
         };
         if (kAhead) {
             // rows 0 and 1: both rows' records in one wave -- position, volume and velocity of either kind of neighbour through
@@ -2623,7 +2570,7 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
             bool wall_[2];
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
-                const int e = m < nn_all ? (m == 0 ? e_row0 : e_row1) : 0;
+                const int e = m < nn_all ? (m == 0 ? first.e0 : first.e1) : 0;
                 wall_[m] = (e & kWallBit) != 0;
                 const int k = m < nn_all ? (e & (kWallBit - 1)) : i;
                 pj_[m] = (wall_[m] ? w.pos : (const double2 *)s.pos)[k];
@@ -2638,7 +2585,7 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
                     term(pj_[m], wall_[m] ? make_double2(2.0 * uj_[m].x - vxi, 2.0 * uj_[m].y - vyi) : uj_[m], Vj_[m]);  // mirrored wall velocity
         }
         for (int m = kAhead ? 2 : 0; m < nn_all; ++m) {
-            const int e = m == 0 ? e_row0 : (m == 1 ? e_row1 : (LPP <= 8 && m == 2 ? e_row2 : (LPP <= 8 && m == 3 ? e_row3 : t.nl_idx[(size_t)m * t.nl_stride + tid])));
+            const int e = first.row(m, t.nl_idx, t.nl_stride, tid);
             const bool wall = (e & kWallBit) != 0;
             const int k = e & (kWallBit - 1);
             const double2 pj = (wall ? w.pos : (const double2 *)s.pos)[k];
@@ -2656,19 +2603,7 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
         }
     }
     rate = group_sum<LPP>(rate);
-    int r_rank = 0;
-    if (REBIN) {
-        if (active) {
-#pragma unroll
-            for (int j = 0; j < kFoldAhead; ++j)
-                r_rank += (sub + j * LPP < r_nv && r_ccell[j] == r_cnew && r_cid[j] < r_id) ? 1 : 0;
-            for (int v = sub + kFoldAhead * LPP; v < r_nv; v += LPP) {
-                const int k = r_slot(v);
-                r_rank += (t.cellid[k] == r_cnew && s.id[k] < r_id) ? 1 : 0;
-            }
-        }
-        r_rank = (int)group_sum<LPP>((double)r_rank);  // (exact: a handful)
-    }
+    const int r_rank = REBIN ? fold_rank<LPP>(fold, s, t, sub, active) : 0;
     if (active && sub == 0) {
         const double rhoh = rhoh_i;
         const double drho_new = rate * rhoh;
@@ -2684,51 +2619,17 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
             half_state(ph, rho, drho_new, dt, rhoh2, p2);
             t.a[i] = make_double4(a_own.x, p2, rhoh2, rho);
         }
-        if (REBIN) {
-            const int dst = r_start[r_cnew] + r_rank;
-            // (the clock does not test the drift of the step that re-bins: a particle that is not where the count looked for it
-            //  must not take a slot somebody else may own -- pass CD has raised the flag already, the step ends in SPHX_ERR_GRID)
-            if (rebin_near(g, r_cold, r_cnew) && (unsigned)dst < (unsigned)t.cap) {
-                d.pos[dst] = pn;
-                d.vel[dst] = vi;
-                if (d.posb) d.posb[dst] = pn;
-                d.drho[dst] = drho_new;
-                d.mass[dst] = r_mass;
-                d.id[dst] = r_id;
-                d.cell[dst] = r_cnew;
-                t.src_of[dst] = i;
-            } else {
-                atomicOr(t.flags, 1);
-            }
-        }
+        if (REBIN) fold_store(fold, g, t, d, r_start, r_rank, i, pn, vi, drho_new);
         if (hist) {
             int cx, cy;
             cell_of(g, pn.x, pn.y, cx, cy);
             const int c = cx * g.ncy + cy;
             t.cellid[i] = c;
-            bool counted = false;
-            if (kHistWindow) {
-                int dcol = cx - h_cx0;
-                if (g.periodic) dcol = dcol < 0 ? dcol + g.ncx : (dcol >= g.ncx ? dcol - g.ncx : dcol);
-                const int drow = cy - h_r0;
-                if ((unsigned)dcol < (unsigned)kHistCols && (unsigned)drow < (unsigned)kHistRows) {
-                    atomicAdd(&h_win[dcol * kHistRows + drow], 1);
-                    counted = true;
-                }
-            }
-            if (!counted) atomicAdd(&t.count[c], 1);
+            if (!(kHistWindow && window.count(g, cx, cy, h_win))) atomicAdd(&t.count[c], 1);
         }
     }
     if (WALK) publish_vmax();  // (its barrier also closes the window histogram)
-    if (kHistWindow && hist && threadIdx.x < kHistCols * kHistRows) {
-        const int v = h_win[threadIdx.x];
-        if (v) {
-            int col = h_cx0 + (int)threadIdx.x / kHistRows;
-            if (g.periodic) col = col < 0 ? col + g.ncx : (col >= g.ncx ? col - g.ncx : col);
-            const int row = h_r0 + (int)threadIdx.x % kHistRows;
-            atomicAdd(&t.count[col * g.ncy + row], v);  // (v > 0: somebody's cell, so col and row are inside the grid)
-        }
-    }
+    if (kHistWindow && hist) window.flush(g, t, h_win);
 }
 
 // (waves_per_eu: the large-channel forms of passes E and A fit eight waves per SIMD by their vector registers (62-67) but took 106

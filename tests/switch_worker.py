@@ -5,6 +5,9 @@ line: the kernel forms and the schedule the context chose, the worst error per f
 end (whatever the comparison said).
 
     SPHX_DEBUG_SWITCHES=tiles_be_from_1 python tests/switch_worker.py --lpp 2 --steps 35
+
+--dump DIR also writes what was downloaded -- the nine fields, t, dt_last, vmax, the pair count and both tau -- as .npy files, so
+that two builds of the library (SPHX_LIB) can be compared byte for byte on the same case.
 """
 import argparse
 import importlib
@@ -27,6 +30,7 @@ def main():
     ap.add_argument("--lpp", type=int, default=2)
     ap.add_argument("--steps", type=int, default=35)
     ap.add_argument("--dynamic", action="store_true", help="dynamic re-binning, every 8th step")
+    ap.add_argument("--dump", metavar="DIR", help="also write the downloaded fields and scalars as DIR/*.npy")
     args = ap.parse_args()
     import oracle
     from helpers import assert_close, make_variant
@@ -44,6 +48,11 @@ def main():
         got = ctx.download()
         tb, tt, npairs = ctx.monitor(tau=True, pairs=True)
         sched_after, pol = ctx.schedule(), ctx.grid_policy()
+    if args.dump:
+        os.makedirs(args.dump, exist_ok=True)
+        scalars = dict(t=st["t"], dt_last=st["dt_last"], vmax=st["vmax"], pairs=npairs, tau_bottom=tb, tau_top=tt)
+        for k, v in list((k, got[k]) for k in FIELDS) + list(scalars.items()):
+            np.save(os.path.join(args.dump, k + ".npy"), np.asarray(v))
     rs = ref["stats"]
     failures, errors = [], {}
 
