@@ -387,6 +387,56 @@ int sphx_batch_flow_stats_read(sphx_batch *batch, int band, int capacity, int *n
                                double *t_first, double *t_last);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2d. Step history: the scalar series of a run -- wall shear, kinetic energy, bulk velocity, dt and max |v| per step --
+ *     recorded on the device, inside the step loop.  The reference computes the wall shear after every step
+ *     (SPH_Poiseuille.m:281-283) and logs it with dt, vmax and the pair count (:285-291); sphx_ctx_monitor gives it at the
+ *     price of a host round trip per call.
+ *
+ *  A record is SPHX_HISTORY_FIELDS doubles describing the state a completed step leaves -- exactly what sphx_ctx_download /
+ *  sphx_ctx_monitor / sphx_status would report if called after that step:
+ *    0 step            sphx_status.step after the step (exact as a double)
+ *    1 t               sphx_status.t
+ *    2 dt              sphx_status.dt_last (dual-rate contexts: the inner dt; t advanced by n_inner * dt)
+ *    3 vmax            sphx_status.vmax
+ *    4 tau_bottom      as sphx_ctx_monitor (sph_physics_mex.c:1713-1742): new neighbour structure and new pos / vel, with
+ *    5 tau_top           Vol / B of the step just finished
+ *    6 kinetic_energy  sum over the fluid particles of 1/2 mass (u_x^2 + u_y^2)
+ *    7 u_bulk          arithmetic mean of u_x over the fluid particles
+ *  Gating: as for the flow statistics (section 2a).  A step is recorded when its step count (sphx_status.step after it) is
+ *    a multiple of `every` and it ends at t >= t_from.  Dual-rate contexts record once per outer step.  A step slot that did
+ *    not run records nothing.
+ *  Buffer: `capacity` records live in device memory and are filled in step order.  When the buffer is full further records
+ *    are dropped and counted in n_dropped; it does not wrap.
+ *  Off by default.  With it off a step slot enqueues exactly the launches it does without this feature; on, every step slot
+ *    ends with one more launch (k_step_history, which skips itself on the steps gated out) that is captured in the
+ *    replayed graphs; enable / disable re-capture them.  Independent of the flow statistics: both may be on at once.
+ *  Determinism: no floating-point atomics; two identical runs give bit-identical records.  How the host chunks its calls
+ *    changes the summation order of fields 4-7 only (the re-binning phase differs after a stop on the drift bound).
+ *  Batches (section 2b) have no step history.
+ *  Errors: SPHX:History:config (every < 1, capacity < 1 or > 1 << 22, non-finite t_from, or the allocation fails: the
+ *    context then goes on without a history), SPHX:History:disabled (SPHX_ERR_STATE: a call that needs the history while
+ *    it is off), SPHX:History:capacity (the caller's buffer is smaller than n_records); every call on a slab context fails
+ *    with SPHX_ERR_ARG, SPHX:History:slab.
+ * ---------------------------------------------------------------------------------------------- */
+
+#define SPHX_HISTORY_FIELDS 8
+
+typedef struct sphx_history_config {
+    int32_t every;     /* record every `every`-th completed step (step count % every == 0), >= 1 */
+    int32_t capacity;  /* records the device buffer holds, 1 .. 1 << 22                          */
+    double t_from;     /* only steps ending at t >= t_from                                       */
+} sphx_history_config;
+
+/* (Re)configure and empty the buffer; waits for the stream. */
+int sphx_ctx_history_enable(sphx_ctx *ctx, const sphx_history_config *cfg);
+/* Stop recording (no-op when off); the records are dropped. */
+int sphx_ctx_history_disable(sphx_ctx *ctx);
+/* The records so far, in step order: records [capacity][SPHX_HISTORY_FIELDS], row-major (NULL: only the counts are
+ * reported and capacity is not checked).  Waits for and settles everything enqueued, like sphx_ctx_download.  drain != 0:
+ * the buffer is emptied and n_dropped zeroed after copying. */
+int sphx_ctx_history_read(sphx_ctx *ctx, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU).  The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

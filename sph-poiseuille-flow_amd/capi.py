@@ -41,6 +41,14 @@ class SphxFlowStatsConfig(C.Structure):
                 ("band_x", C.c_double * 2), ("band_hw", C.c_double * 2)]
 
 
+class SphxHistoryConfig(C.Structure):
+    _fields_ = [("every", C.c_int32), ("capacity", C.c_int32), ("t_from", C.c_double)]
+
+
+# a record of the step history (include/sphx.h section 2d), in the order the library writes it
+HISTORY_FIELDS = ("step", "t", "dt", "vmax", "tau_bottom", "tau_top", "kinetic_energy", "u_bulk")
+
+
 class SphxStatus(C.Structure):
     _fields_ = [("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("vmax", C.c_double),
                 ("step", C.c_int64), ("done", C.c_int32), ("device_status", C.c_int32)]
@@ -60,6 +68,7 @@ EXPORTS = [
     "sphx_ctx_profile_read", "sphx_ctx_info", "sphx_ctx_tuning", "sphx_ctx_substeps", "sphx_ctx_schedule", "sphx_ctx_kernel_forms", "sphx_ctx_grid_policy", "sphx_ctx_time_kernel",
     "sphx_ctx_flow_stats_enable", "sphx_ctx_flow_stats_disable", "sphx_ctx_flow_stats_reset", "sphx_ctx_flow_stats_sample",
     "sphx_ctx_flow_stats_read",
+    "sphx_ctx_history_enable", "sphx_ctx_history_disable", "sphx_ctx_history_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -448,6 +457,32 @@ class Context:
             raise SphxError(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this context")
         return self._flow_stats
 
+    # ---- step history (include/sphx.h section 2d): wall shear, energy, bulk velocity, dt and vmax per step, recorded on the device ----
+    def history_enable(self, every=1, capacity=65536, t_from=0.0):
+        """Record every `every`-th completed step ending at t >= t_from into a device buffer of `capacity` records
+        ((re)configures and empties it).  Records that find the buffer full are dropped and counted."""
+        cfg = history_config(every, capacity, t_from)
+        check(lib().sphx_ctx_history_enable(self._h, C.byref(cfg)))
+
+    def history_disable(self):
+        check(lib().sphx_ctx_history_disable(self._h))
+
+    def history_records(self, drain=False):
+        """-> (records [n x 8] in the order of HISTORY_FIELDS, n_dropped); drain empties the buffer after the copy."""
+        n, dropped = C.c_int(0), C.c_int64(0)
+        check(lib().sphx_ctx_history_read(self._h, C.c_int(0), None, C.byref(n), C.byref(dropped), C.c_int(0)))
+        rec = np.zeros((n.value, len(HISTORY_FIELDS)))
+        check(lib().sphx_ctx_history_read(self._h, C.c_int(n.value), ptr(rec), C.byref(n), C.byref(dropped),
+                                          C.c_int(1 if drain else 0)))
+        assert n.value == rec.shape[0], (n.value, rec.shape)
+        return rec, dropped.value
+
+    def history(self, drain=False) -> dict:
+        """The records so far as 1-D arrays step (int64), t, dt, vmax, tau_bottom, tau_top, kinetic_energy, u_bulk, plus
+        n_dropped."""
+        rec, dropped = self.history_records(drain)
+        return history_dict(rec, dropped)
+
     def profile_enable(self, on=True):
         check(lib().sphx_ctx_profile_enable(self._h, C.c_int(1 if on else 0)))
 
@@ -490,6 +525,36 @@ def flow_stats_config(n_bins=0, every=1, t_from=0.0, bands=()) -> SphxFlowStatsC
     for k, (x, hw) in enumerate(bands):
         cfg.band_x[k], cfg.band_hw[k] = x, hw
     return cfg
+
+
+def history_config(every=1, capacity=65536, t_from=0.0) -> SphxHistoryConfig:
+    """Checked sphx_history_config; raises SphxError(SPHX:History:config) before anything reaches the device."""
+    def bad(msg):
+        return SphxError(SPHX_ERR_ARG, "SPHX:History:config", msg)
+
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+    if not is_int(every) or every < 1:
+        raise bad("every must be an integer >= 1")
+    if not is_int(capacity) or not 1 <= capacity <= 1 << 22:
+        raise bad("capacity must be an integer in 1 .. 1 << 22")
+    try:
+        t_from = float(t_from)
+    except (TypeError, ValueError):
+        raise bad("t_from must be a number") from None
+    if not np.isfinite(t_from):
+        raise bad("t_from must be finite")
+    return SphxHistoryConfig(every=int(every), capacity=int(capacity), t_from=t_from)
+
+
+def history_dict(records, n_dropped=0) -> dict:
+    """Records [n x 8] -> {field: 1-D array} in the order of HISTORY_FIELDS (step as int64) plus n_dropped."""
+    records = np.asarray(records, dtype=np.float64).reshape(-1, len(HISTORY_FIELDS))
+    out = {k: np.ascontiguousarray(records[:, j]) for j, k in enumerate(HISTORY_FIELDS)}
+    out["step"] = out["step"].astype(np.int64)
+    out["n_dropped"] = int(n_dropped)
+    return out
 
 
 def _fetch_pairs(n):

@@ -1,0 +1,173 @@
+// sphx_history.hpp -- the step history of a resident context (include/sphx.h section 2d): one self-skipping launch at the
+// end of every step slot reduces the state the step left to one record of kHistoryFields doubles -- step, t, dt, vmax of the
+// device clock, the wall shear of SPH_Poiseuille.m:281-283, the kinetic energy and the bulk velocity -- and appends it to a
+// record buffer in device memory, without a host round trip.
+//
+// The wall-shear term is k_wall_shear's, term for term (sphx_kernels.hpp; kept as a copy here so that the monitor's kernel
+// stays what it is): the wall cells around the cell a particle was binned into, new pos / vel, Vol / B of the step just
+// finished.  Where those records are is the launch's business (launch_slot_history): the buffers of the finished step's
+// parity, read through src_of when the slot re-binned -- known at capture time on the static schedule, Clock::fresh on a
+// dynamic one.
+//
+// Determinism: no floating-point atomics.  A workgroup takes a contiguous run of slots, reduces inside the wave with
+// shuffles and across its waves in LDS (wave order), and leaves four partial sums; the last workgroup out (ticket,
+// agent-scope release / acquire as in k_flow_stats) adds the partials in index order and writes the record.  Two identical
+// runs give identical bits; another layout of the particles (re-binning phase, host chunking) changes the summation order
+// only.  A channel small enough for one workgroup finishes without partials and ticket.
+#pragma once
+#include "../../include/sphx.h"
+#include "sphx_kernels.hpp"
+
+namespace sphx {
+
+constexpr int kHistoryFields = SPHX_HISTORY_FIELDS;  // step, t, dt, vmax, tau_bottom, tau_top, kinetic_energy, u_bulk
+constexpr int kHistorySums = 4;                      // wall force bottom / top, kinetic energy, sum u_x
+constexpr int kHistoryBlock = 512;
+constexpr int kHistoryMaxBlocks = 256;               // one workgroup per CU at most: every one of them draws a ticket
+constexpr int kHistoryPerThread = 4;                 // particles a thread takes before another workgroup is added: up to
+                                                     // 2 048 particles ONE workgroup writes the record by itself
+constexpr int kHistoryMaxCapacity = 1 << 22;         // records (256 MB)
+
+// the counters of the record buffer, in a block of their own (Clock must not grow, see sphx_kernels.hpp); only the last
+// workgroup out of a launch touches them
+struct HistoryHead {
+    long long n_records;  // records in the buffer, filled in step order
+    long long n_dropped;  // records that found the buffer full
+    int ticket;           // last workgroup out (zero between launches)
+    int pad;
+};
+
+enum HistorySrc : int {
+    kHistoryInPlace = 0,   // Vol / B of slot i are at i
+    kHistorySrcOf = 1,     // the slot re-binned: at src_of[i]
+    kHistoryByClock = 2,   // dynamic contexts: at src_of[i] when the step ended with a re-binning (Clock::fresh)
+};
+
+struct HistoryArgs {
+    double *records;       // [capacity][kHistoryFields]
+    double *part;          // [kHistoryMaxBlocks][kHistorySums] per-workgroup partial sums
+    HistoryHead *head;
+    double t_from;
+    int capacity;
+    int every;             // >= 1
+    int src;               // HistorySrc
+};
+
+// one fluid particle's contribution to the wall force sums: sph_physics_mex.c:1713-1742 as k_wall_shear evaluates it
+__device__ __forceinline__ void history_wall_terms(const Grid &g, const Phys &ph, const FluidSet &s, const FluidTmp &t,
+                                                   const Walls &w, int i, bool use_src, double2 p, double2 v, double &fb,
+                                                   double &ft)
+{
+    const double xi = p.x, yi = p.y;
+    int cx, cy;
+    binned_cell(g, s, i, cx, cy);
+    if (!(w.row_any[cy] && xi >= g.own_lo && xi < g.own_hi)) return;
+    const int o = use_src ? t.src_of[i] : i;
+    const double Voli = t.a[o].x;
+    const double4 Bo = t.B[o];
+    const double b11 = Bo.x, b12 = Bo.y, b21 = Bo.z, b22 = Bo.w;
+    const double vxi = v.x;
+    sweep<1>(g, w.start, cx, cy, 0, [&](int k) {
+        const double2 pj = w.pos[k];
+        const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
+        const double r2 = dx * dx + dy * dy;
+        if (r2 > kR2Min && r2 < ph.kc.rcut2) {
+            const double4 wj = w.a[k];
+            const double r = sqrt(r2);
+            const double ex = dx / r, ey = dy / r;
+            const double eBe = ex * (b11 * ex + b12 * ey) + ey * (b21 * ex + b22 * ey);
+            const double f = 4.0 * ph.mu * eBe * spline_dW(ph.kc, r) * wj.x * (vxi - wj.y) / (r + 0.01 * ph.kc.h) * Voli;
+            const double yj = pj.y;
+            // (selects, not branches around the adds: the sums stay in registers -- k_wall_shear's if / else if puts them
+            //  in scratch; adding 0.0 changes no bit of a sum)
+            const bool bottom = yj <= 0.0;
+            fb += bottom ? f : 0.0;
+            ft += !bottom && yj >= ph.DH ? f : 0.0;
+        }
+    });
+}
+
+// q: parity of the step slot this launch closes (the slot ran iff run[q] is still set -- a clock update only ever writes the
+// flag of the NEXT slot).  The launch sits behind the slot's clock update, so clk->step / t / dt_last / vmax are those of the
+// step just completed; s is the state it left, t holds its Vol / B.
+__global__ __launch_bounds__(kHistoryBlock) void k_step_history(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
+                                                                 FluidTmp t, Walls w, HistoryArgs a)
+{
+    if (!clk->run[q]) return;
+    if (clk->step % a.every != 0) return;
+    if (!(clk->t >= a.t_from)) return;
+    const int n = clk->n;
+    const bool use_src = a.src == kHistoryByClock ? clk->fresh != 0 : a.src == kHistorySrcOf;
+    const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;  // a contiguous run of slots per workgroup
+    const int i0 = (int)blockIdx.x * chunk;
+    const int i1 = min(n, i0 + chunk);
+    double fb = 0.0, ft = 0.0, ke = 0.0, su = 0.0;  // wall force bottom, top; kinetic energy; sum u_x
+    for (int i = i0 + (int)threadIdx.x; i < i1; i += kHistoryBlock) {
+        const double2 p = s.pos[i], v = s.vel[i];
+        ke += 0.5 * s.mass[i] * (v.x * v.x + v.y * v.y);
+        su += v.x;
+        history_wall_terms(g, ph, s, t, w, i, use_src, p, v, fb, ft);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        fb += __shfl_xor(fb, off);
+        ft += __shfl_xor(ft, off);
+        ke += __shfl_xor(ke, off);
+        su += __shfl_xor(su, off);
+    }
+    constexpr int kWaves = kHistoryBlock / 64;
+    __shared__ double s_wave[kHistorySums][kWaves];
+    __shared__ double s_tot[kHistorySums];
+    __shared__ int s_last;
+    if ((threadIdx.x & 63) == 0) {
+        const int wv = threadIdx.x >> 6;
+        s_wave[0][wv] = fb; s_wave[1][wv] = ft; s_wave[2][wv] = ke; s_wave[3][wv] = su;
+    }
+    __syncthreads();
+    // thread f adds field f: the waves of this workgroup in wave order, then (several workgroups) the partials in index order
+    double tot = 0.0;
+    if (threadIdx.x < kHistorySums)
+        for (int k = 0; k < kWaves; ++k) tot += s_wave[threadIdx.x][k];
+    if (gridDim.x > 1) {
+        if (threadIdx.x < kHistorySums) a.part[(size_t)blockIdx.x * kHistorySums + threadIdx.x] = tot;
+        // last workgroup out: the partials drained, one release at agent scope, then the ticket
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const int drawn = __hip_atomic_fetch_add(&a.head->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            s_last = drawn == (int)gridDim.x - 1 ? 1 : 0;
+            if (s_last) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+        __syncthreads();
+        if (!s_last) return;
+        if (threadIdx.x < kHistorySums) {
+            tot = 0.0;
+            for (int b = 0; b < (int)gridDim.x; ++b)
+                tot += __hip_atomic_load(a.part + (size_t)b * kHistorySums + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (threadIdx.x < kHistorySums) s_tot[threadIdx.x] = tot;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    // the record, by the one thread that also advances the counters: plain vector stores
+    HistoryHead *h = a.head;
+    const long long at = h->n_records;
+    if (at < (long long)a.capacity) {
+        double2 *rec = reinterpret_cast<double2 *>(a.records + (size_t)at * kHistoryFields);
+        rec[0] = make_double2((double)clk->step, clk->t);
+        rec[1] = make_double2(clk->dt_last, clk->vmax);
+        rec[2] = make_double2(-s_tot[0] / ph.DL, -s_tot[1] / ph.DL);  // (k_tau_final: -sum / DL)
+        rec[3] = make_double2(s_tot[2], s_tot[3] / (double)n);
+        h->n_records = at + 1;
+    } else {
+        h->n_dropped += 1;
+    }
+    if (gridDim.x > 1) __hip_atomic_store(&h->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+}  // namespace sphx

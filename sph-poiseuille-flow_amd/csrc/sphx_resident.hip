@@ -15,6 +15,7 @@
 #include "sphx_common.hpp"
 #include "sphx_kernels.hpp"
 #include "sphx_flow_stats.hpp"
+#include "sphx_history.hpp"
 
 namespace sphx {
 
@@ -254,6 +255,14 @@ struct sphx_ctx {
         DevBuf<double> dsum;
         DevBuf<FlowStatsHead> head;
     } fstats;
+
+    // Step history (sphx_ctx_history_*, sphx_history.hpp): when on, every step slot ends with k_step_history
+    struct History {
+        bool on = false;
+        sphx_history_config cfg{};
+        DevBuf<double> records, part;
+        DevBuf<HistoryHead> head;
+    } hist;
 
     // Member of a batch (sphx_batch_*): the device arrays are this member's blocks of batch-wide allocations (BatchArena)
     sphx::BatchArena *arena = nullptr;
@@ -801,6 +810,26 @@ void launch_slot_stats(sphx_ctx *c, int q)
     launch_flow_stats(c, q, c->fpos_[1 - q].get(), c->fvel_[1 - q].get(), c->fstats.cfg.every);
 }
 
+// k_step_history behind step slot q, which ran on layout l: the state it left is S[1-q] -- in the other layout when the slot
+// re-binned -- and Vol / B of the finished step are where sphx_ctx_monitor looks them up after it: the record buffers of the
+// step's parity (fuse_ea), in the order of the layout the step ran in, so read through src_of when the slot re-binned.  The
+// static schedule knows that when the launch is made (or captured); a dynamic context re-bins in place and says so in
+// Clock::fresh.
+void launch_slot_history(sphx_ctx *c, int q, int l, bool rebuild)
+{
+    const sphx_ctx::History &h = c->hist;
+    if (!h.on) return;
+    const FluidSet s = c->dyn ? c->view(1 - q, 0) : c->view(1 - q, rebuild ? 1 - l : l);
+    HistoryArgs a{};
+    a.records = h.records.get(); a.part = h.part.get(); a.head = h.head.get();
+    a.t_from = h.cfg.t_from; a.capacity = h.cfg.capacity; a.every = h.cfg.every;
+    a.src = c->dyn ? kHistoryByClock : (rebuild ? kHistorySrcOf : kHistoryInPlace);
+    const unsigned blocks =
+        std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kHistoryBlock * kHistoryPerThread), 1u, (unsigned)kHistoryMaxBlocks);
+    launch(c, "k_step_history", k_step_history, dim3(blocks), dim3(kHistoryBlock), (const Clock *)c->clock.get(), q, c->grid,
+           c->phys, s, c->tmp_par[c->fuse_ea ? q : 0], c->walls, a);
+}
+
 // host-side bookkeeping of one step slot
 void track_step(sphx_ctx *c)
 {
@@ -912,13 +941,15 @@ void enqueue_slots(Schedule &s, hipStream_t st, int K, int per_graph, int64_t sl
 
 // ---- a context's side of it ----
 
-// one step slot of a context: the static schedule's launches or a dynamic context's, then the slot's k_flow_stats
+// one step slot of a context: the static schedule's launches or a dynamic context's, then the slot's k_flow_stats and
+// k_step_history (each only where it is on)
 auto ctx_slot(sphx_ctx *c)
 {
     return [c](int q, int l, int p, bool rebuild) {
         if (c->dyn) launch_step_dyn(c, q);
         else launch_step(c, q, l, p, rebuild);
         launch_slot_stats(c, q);
+        launch_slot_history(c, q, l, rebuild);
     };
 }
 
@@ -2075,6 +2106,93 @@ SPHX_EXPORT int sphx_ctx_flow_stats_read(sphx_ctx *c, int band, int capacity, in
     if (n_samples) *n_samples = h.n_samples;
     if (t_first) *t_first = h.n_samples ? h.t_first : nan;
     if (t_last) *t_last = h.n_samples ? h.t_last : nan;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- step history (sphx_history.hpp) ----
+namespace {
+
+sphx_ctx *history_ctx(sphx_ctx *c, bool need_on)
+{
+    require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
+    require(!c->is_slab, "SPHX:History:slab", "the step history is not available on slab contexts");
+    if (need_on && !c->hist.on)
+        throw Error(SPHX_ERR_STATE, "SPHX:History:disabled", "the step history is not enabled on this context");
+    return c;
+}
+
+void history_release(sphx_ctx::History &h)
+{
+    h.on = false;
+    h.records.release();
+    h.part.release();
+    h.head.release();
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_history_enable(sphx_ctx *c, const sphx_history_config *cfg)
+{
+    SPHX_TRY
+    history_ctx(c, false);
+    require(cfg != nullptr, "SPHX:History:config", "config must not be NULL");
+    require(cfg->every >= 1, "SPHX:History:config", "every must be >= 1");
+    require(cfg->capacity >= 1 && cfg->capacity <= kHistoryMaxCapacity, "SPHX:History:config", "capacity must be 1 .. 1 << 22 records");
+    require(std::isfinite(cfg->t_from), "SPHX:History:config", "t_from must be finite");
+    stats_drop_graphs(c);  // the replayed graphs carry k_step_history (and its arguments) or not
+    sphx_ctx::History &h = c->hist;
+    history_release(h);
+    try {
+        h.records.alloc((size_t)cfg->capacity * kHistoryFields);
+        h.part.alloc((size_t)kHistoryMaxBlocks * kHistorySums);
+        h.head.alloc(1);
+        h.head.zero(c->stream);
+        SPHX_HIP(hipStreamSynchronize(c->stream));
+    } catch (const Error &e) {
+        history_release(h);
+        (void)hipGetLastError();
+        throw Error(SPHX_ERR_ARG, "SPHX:History:config", std::string("the record buffer could not be set up: ") + e.what());
+    }
+    h.cfg = *cfg;
+    h.on = true;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_history_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    history_ctx(c, false);
+    if (!c->hist.on) return SPHX_OK;
+    stats_drop_graphs(c);
+    history_release(c->hist);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_history_read(sphx_ctx *c, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    history_ctx(c, true);
+    settle_owed(c);  // (the records of everything enqueued)
+    sphx_ctx::History &h = c->hist;
+    HistoryHead head{};
+    SPHX_HIP(hipMemcpyAsync(&head, h.head.get(), sizeof(head), hipMemcpyDeviceToHost, c->stream));
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+    const long long n = head.n_records;
+    if (n < 0 || n > (long long)h.cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:History:state", "internal: record count out of range");
+    require(records == nullptr || (long long)capacity >= n, "SPHX:History:capacity", "capacity is smaller than the number of records");
+    if (records && n > 0) {
+        SPHX_HIP(hipMemcpyAsync(records, h.records.get(), (size_t)n * kHistoryFields * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        SPHX_HIP(hipStreamSynchronize(c->stream));
+    }
+    if (n_records) *n_records = (int)n;
+    if (n_dropped) *n_dropped = (int64_t)head.n_dropped;
+    if (drain) {
+        h.head.zero(c->stream);
+        SPHX_HIP(hipStreamSynchronize(c->stream));
+    }
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -45,6 +45,7 @@ class RunResult:
     full_profile_u: list = field(default_factory=list)  # whole-channel binned u_x(y) at every output point
     n_inner: int = 1  # inner sub-steps per counted step (> 1 only with the opt-in dual-rate loop)
     time_avg: dict = None  # run(..., average_from=...): device-side time-averaged profiles and figures (see time_average)
+    history: dict = None  # run(..., history_every=...): the device-side step history of the whole run (capi.Context.history)
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -97,9 +98,49 @@ def time_average(prm, whole, mid):
                 t_first=whole["t_first"], t_last=whole["t_last"])
 
 
+def history_figures(prm, hist, t_from=0.0, tol=0.05):
+    """Figures of a step history (capi.Context.history / RunResult.history) against the analytic flow, on the host.
+      tau_bottom_mean, tau_top_mean, u_bulk_mean   dt-weighted time means over the records with t >= t_from (a record
+                             stands for the step that ended at its t, so its weight is its dt; NaN without such records)
+      tau_target, u_bulk_exact   g rho0 DH / 2 and the analytic bulk velocity g DH^2 / (12 nu)
+      tau_bottom_dev, tau_top_dev, u_bulk_dev   relative deviation of the means, (mean - exact) / exact
+      t_settled              the first t from which |tau - tau_target| / tau_target of BOTH walls stays below tol up to
+                             the last record (over all records, whatever t_from; NaN if the last record is outside)
+      n_records              records that entered the means"""
+    t, dt = np.asarray(hist["t"], dtype=np.float64), np.asarray(hist["dt"], dtype=np.float64)
+    tau_target = prm.gravity_g * prm.rho0 * prm.DH / 2.0
+    u_exact = prm.gravity_g * prm.DH ** 2 / (12.0 * prm.nu)
+    sel = t >= t_from
+    w = dt[sel]
+    wsum = float(np.sum(w))
+
+    def mean(key):  # (about the first value: a constant series gives that value exactly)
+        v = np.asarray(hist[key], dtype=np.float64)[sel]
+        return float(v[0] + np.sum(w * (v - v[0])) / wsum) if wsum > 0.0 else float("nan")
+
+    out = dict(tau_target=tau_target, u_bulk_exact=u_exact, n_records=int(np.count_nonzero(sel)), tol=tol)
+    for key, exact in (("tau_bottom", tau_target), ("tau_top", tau_target), ("u_bulk", u_exact)):
+        out[key + "_mean"] = mean(key)
+        out[key + "_dev"] = (out[key + "_mean"] - exact) / exact
+    dev = np.maximum(np.abs(np.asarray(hist["tau_bottom"], dtype=np.float64) - tau_target),
+                     np.abs(np.asarray(hist["tau_top"], dtype=np.float64) - tau_target)) / abs(tau_target)
+    outside = np.flatnonzero(~(dev < tol))
+    first_inside = 0 if len(outside) == 0 else int(outside[-1]) + 1
+    out["t_settled"] = float(t[first_inside]) if first_inside < len(t) else float("nan")
+    return out
+
+
+def _concat_history(chunks):
+    if not chunks:
+        return capi.history_dict(np.zeros((0, len(capi.HISTORY_FIELDS))))
+    out = {k: np.concatenate([c[k] for c in chunks]) for k in capi.HISTORY_FIELDS}
+    out["n_dropped"] = int(sum(c["n_dropped"] for c in chunks))
+    return out
+
+
 def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_particle=0, steps_per_graph=0,
         rebuild_every=0, restart_path=None, postprocess_path=None, dual_rate=0, mat_format="auto", average_from=None,
-        average_every=1):
+        average_every=1, history_every=None, history_capacity=65536):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -111,9 +152,15 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     average_from (resident engine): accumulate, on the device and inside the step loop, every average_every-th step ending
     at t >= average_from into the reference's profile bins, for the whole channel and the mid-channel band (DL/2,
     max(dp, h)); RunResult.time_avg then holds the time-averaged profiles, their L2 against u_exact and the stability
-    figures defined in time_average().  The output-point snapshots are taken as without it."""
+    figures defined in time_average().  The output-point snapshots are taken as without it.
+    history_every (resident engine): record every history_every-th step on the device (include/sphx.h section 2d: step, t,
+    dt, vmax, tau_bottom, tau_top, kinetic_energy, u_bulk); the buffer (history_capacity records) is drained at every
+    output point, so a capacity that holds one output interval suffices, and RunResult.history is the series of the
+    whole run (history_figures() turns it into means and a settling time)."""
     if average_from is not None and engine != "resident":
         raise ValueError("average_from needs the resident engine (the statistics are accumulated on the device)")
+    if history_every is not None and engine != "resident":
+        raise ValueError("history_every needs the resident engine (the history is recorded on the device)")
     parts = init_particles(prm) if parts is None else parts
     nf, nt = parts["n_fluid"], parts["n_total"]
     t_start, step_start, n_inner = 0.0, 0, 1
@@ -136,6 +183,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     tau_b = tau_t = 0.0
     policy = {}
     time_avg = None
+    history, history_chunks = None, []
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
@@ -146,6 +194,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
             n_inner = ctx.substeps()
             if average_from is not None:
                 ctx.flow_stats_enable(n_bins=n_bins, every=average_every, t_from=average_from, bands=[(mid_x, mid_hw)])
+            if history_every is not None:
+                ctx.history_enable(every=history_every, capacity=history_capacity)
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -162,6 +212,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 mid_profiles.append(u)
                 full_profiles.append(final_profile(np.column_stack([np.mod(d["pos"][:nf, 0], prm.DL), d["pos"][:nf, 1]]),
                                                    d["vel"][:nf, 0], prm)[1])
+                if history_every is not None:
+                    history_chunks.append(ctx.history(drain=True))
                 if restart_path:
                     restart.save_restart(restart_path, prm.config_signature, dict(d, t=t, step=step), fmt=mat_format)
                 if log:
@@ -173,6 +225,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
             policy = ctx.grid_policy()
             if average_from is not None:
                 time_avg = time_average(prm, ctx.flow_stats(0), ctx.flow_stats(1))
+            if history_every is not None:
+                history = _concat_history(history_chunks)
         finally:
             ctx.close()
     elif engine == "mex":
@@ -227,11 +281,11 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                      y_mid=y_mid, u_mean=u_mean, u_exact=u_exact, L2_error=l2_error(u_mean, u_exact),
                      profile_times=profile_times, mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t,
                      tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2, grid_policy=policy, full_profile_u=full_profiles, n_inner=n_inner,
-                     time_avg=time_avg)
+                     time_avg=time_avg, history=history)
 
 
 def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,
-              restart_path=None, postprocess_path=None, average_from=None, log=None):
+              restart_path=None, postprocess_path=None, average_from=None, log=None, history_every=None):
     """run() for M channels of one geometry stepped together as one batch (capi.Batch, include/sphx.h section 2b): a
     parameter sweep (mu, c_f, p0, gravity_g, transport_coeff) or an ensemble of realisations (parts_list).  Every member
     reaches the same output points (output_interval and t_end are shared and must agree) and gets a RunResult of its own:
@@ -244,6 +298,8 @@ def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, st
         raise ValueError("run_batch writes no restart / post-process files (run() does, per channel)")
     if average_from is not None:
         raise ValueError("run_batch has no time averaging yet (flow statistics are a single-context feature)")
+    if history_every is not None:
+        raise ValueError("run_batch has no step history (the history is a single-context feature)")
     if not prms:
         raise ValueError("run_batch needs at least one parameter set")
     p0 = prms[0]
@@ -316,7 +372,7 @@ _PHYSICS = ("mu", "c_f", "p0", "gravity_g", "transport_coeff")
 
 
 def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_per_particle=0, steps_per_graph=0,
-                 rebuild_every=0, log=None):
+                 rebuild_every=0, log=None, history_every=None):
     """Time-averaged profiles of M channels of one geometry stepped as one batch (capi.Batch), averaged on the device
     inside the step loop (include/sphx.h section 2c) as run(average_from=...) does for one channel: every
     average_every-th step ending at t >= average_from, whole channel and the mid-channel band (DL/2, max(dp, h)).  The
@@ -324,6 +380,8 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
     downloaded before the end.  parts_list: the members' initial states (e.g. geometry.perturbed_particles), default the
     lattice.  Returns an EnsembleResult."""
     prms = list(prms)
+    if history_every is not None:
+        raise ValueError("run_ensemble has no step history (the history is a single-context feature)")
     if not prms:
         raise ValueError("run_ensemble needs at least one parameter set")
     if average_from is None or np.isnan(float(average_from)):

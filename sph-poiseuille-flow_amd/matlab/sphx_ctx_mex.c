@@ -11,6 +11,10 @@
  *   sphx_ctx_mex('stats_sample', h)    % add one sample of the current state now
  *   [N, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples, t_first, t_last] = sphx_ctx_mex('stats_read', h, band)
  *       band 0 = whole channel, 1.. = the bands given; n_bins x 1 columns (flow statistics, include/sphx.h section 2a)
+ *   sphx_ctx_mex('history_enable', h, every, capacity, t_from)   /   sphx_ctx_mex('history_disable', h)
+ *   [records, n_dropped] = sphx_ctx_mex('history_read', h, drain)
+ *       records: n x 8, one row per recorded step: step, t, dt, vmax, tau_bottom, tau_top, kinetic_energy, u_bulk (step
+ *       history, include/sphx.h section 2d); drain ~= 0 empties the device buffer
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -149,6 +153,34 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 5) plhs[5] = mxCreateDoubleScalar((double)ns);
         if (nlhs > 6) plhs[6] = mxCreateDoubleScalar(t0);
         if (nlhs > 7) plhs[7] = mxCreateDoubleScalar(t1);
+    } else if (strcmp(cmd, "history_enable") == 0) {
+        sphx_history_config hc;
+        arity(cmd, nrhs, 5, nlhs, 0);
+        memset(&hc, 0, sizeof(hc));
+        hc.every = (int32_t)mxGetScalar(prhs[2]);
+        hc.capacity = (int32_t)mxGetScalar(prhs[3]);
+        hc.t_from = mxGetScalar(prhs[4]);
+        ok(sphx_ctx_history_enable(handle(prhs[1]), &hc));
+    } else if (strcmp(cmd, "history_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_history_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "history_read") == 0) {
+        sphx_ctx *c;
+        int n = 0, got = 0, k, f, drain;
+        int64_t dropped = 0;
+        double *rows, *out;
+        arity(cmd, nrhs, 3, nlhs, 2);
+        c = handle(prhs[1]);
+        drain = mxGetScalar(prhs[2]) != 0.0;
+        ok(sphx_ctx_history_read(c, 0, NULL, &n, NULL, 0));
+        rows = (double *)mxMalloc((size_t)(n > 0 ? n : 1) * SPHX_HISTORY_FIELDS * sizeof(double));
+        ok(sphx_ctx_history_read(c, n, rows, &got, &dropped, drain));  /* (nothing is stepped in between: got == n) */
+        plhs[0] = mxCreateDoubleMatrix((mwSize)got, SPHX_HISTORY_FIELDS, mxREAL);
+        out = mxGetDoubles(plhs[0]);
+        for (k = 0; k < got; ++k)  /* the library's rows are records; MATLAB stores columns */
+            for (f = 0; f < SPHX_HISTORY_FIELDS; ++f) out[(size_t)f * got + k] = rows[(size_t)k * SPHX_HISTORY_FIELDS + f];
+        mxFree(rows);
+        if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)dropped);
     } else if (strcmp(cmd, "destroy") == 0) {
         arity(cmd, nrhs, 2, nlhs, 0);
         sphx_ctx_destroy(handle(prhs[1]));
