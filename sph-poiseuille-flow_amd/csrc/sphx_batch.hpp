@@ -3,7 +3,9 @@
 // A batch steps M independent channels of one geometry with the launches of one: every step-slot kernel of the compact
 // context runs as its "_b" form on a grid of (workgroups of one member) x M, member = blockIdx.y (Members,
 // sphx_kernels.hpp).  Each member is an sphx_ctx whose device arrays are its blocks of batch-wide allocations (BatchArena):
-// the cold paths -- creation, initial sort, downloads, monitors -- are the single-context code run on that member.  The host
+// the cold paths -- creation, initial sort, downloads, monitors -- are the single-context code run on that member.  So is the
+// step: the batch enqueues a context's step slot (ctx_slot: launch_step, then the slot's flow statistics) on member 0, which
+// carries the member table, and the launch layer puts every kernel into its batch form (launch_forms).  The host
 // schedule (re-binning slots, graph phases) is the batch's; every member has its own clock, so a member that has reached
 // its target, used up its steps or stopped on the drift bound sits out the rest of the call.  When a call leaves members at
 // different phases of the schedule, or one of them stopped on the drift bound, every member is re-binned into one phase at
@@ -26,9 +28,7 @@ struct sphx_batch {
     int64_t epoch_slot = 0;           // sched.slot when the members' epochs were set
     int64_t n_realign = 0;
     std::vector<int64_t> pending;     // per member: step count the sphx_batch_enqueue_steps calls since the last sync aim for
-    sphx_ctx::FlowStats fstats;       // flow statistics (sphx_batch_flow_stats_*): one config for all members, sums and heads
-                                      // in M blocks (member m's at m * n_bands * n_bins * kStatsFields, head m); the
-                                      // members' own fstats stay off
+    // (flow statistics, sphx_batch_flow_stats_*: mem[0]->fstats, for all M members)
 
     ~sphx_batch()
     {
@@ -45,87 +45,6 @@ struct sphx_batch {
 namespace {
 
 constexpr int kMaxBatchMembers = 4096;  // (grid rows; memory runs out first on large channels: sphx_batch_create reports it)
-
-// ---- one step slot of the whole batch: launch_step of the compact kernels, on every member at once ----
-template <int LPP>
-void batch_step_t(sphx_batch *b, int q, int l, int pos, bool rebuild)
-{
-    sphx_ctx *c = b->mem[0];
-    const unsigned M = (unsigned)b->M;
-    const Members &mb = b->mb;
-    const int nb = c->n_blocks_particles;
-    const dim3 gp(nb, M), ge(nb + 1, M), gf(c->n_blocks_flat, M), bp(kBlock);
-    const int dmode = c->skin > 0.0 ? (pos == 0 ? 1 : 2) : 0;
-    const FluidSet s = c->view(q, l);
-    const int finish_half = c->fuse_ea ? 1 : 0;
-    auto pass_a = [&](const FluidTmp &t, int mode) {
-        if (mode == 0) launch(c, "k_density", k_density_b<LPP, 0>, gp, bp, mb, q, c->grid, s, t, c->walls, -1);
-        else if (mode == 1) launch(c, "k_density_build", k_density_b<LPP, 1>, gp, bp, mb, q, c->grid, s, t, c->walls, -1);
-        else launch(c, "k_density_walk", k_density_b<LPP, 2>, gp, bp, mb, q, c->grid, s, t, c->walls, -1);
-    };
-    auto passes_bc = [&](const FluidTmp &t) {
-        launch(c, "k_kgc", k_kgc_b<LPP>, gp, bp, mb, q, c->grid, s, t, c->walls, finish_half);
-        launch(c, "k_forces", k_forces_b<LPP>, gp, bp, mb, q, c->grid, s, t, c->walls, 0);
-    };
-    auto pass_e = [&](const FluidTmp &t, int do_hist, int tail) {
-        launch(c, tail ? "k_continuity_clock" : "k_continuity", k_continuity_b<LPP>, tail ? ge : gp, bp, mb, q, c->grid, s, t,
-               c->walls, do_hist, tail);
-    };
-    auto clock_scan = [&](int *start_next) {
-        launch(c, "k_clock_scan", k_clock_scan_b, dim3(1, M), dim3(kScanBlock), mb, q, (const double *)c->vpart.get(),
-               (const int *)c->flags.get(), start_next ? (const int *)c->count.get() : (const int *)nullptr, start_next,
-               c->grid.ncells, c->skin > 0.0 ? (const double *)c->dpart.get() : (const double *)nullptr, start_next ? 1 : 0,
-               c->half_skin(), c->vpart_reset());
-    };
-    if (!rebuild) {
-        const FluidSet o = c->view(1 - q, l);
-        const FluidTmp t = writing_into(c->fuse_ea ? c->tmp_par[q] : c->tmp, o);
-        if (c->fuse_ea) {  // pass A of this step ran in the previous step's last launch, unless the grid is fresh
-            if (pos == 0) pass_a(t, 1);
-            passes_bc(t);
-            launch(c, "k_continuity_density", k_continuity_density_b<LPP>, dim3(2 * nb + 1, M), bp, mb, q, c->grid, s, t, c->walls,
-                   o, c->tmp_par[1 - q], 1);
-            return;
-        }
-        pass_a(t, dmode);
-        passes_bc(t);
-        pass_e(t, 0, c->tail_clock ? 1 : 0);
-        if (!c->tail_clock) clock_scan(nullptr);
-        return;
-    }
-    const FluidTmp &t = c->fuse_ea ? c->tmp_par[q] : c->tmp;
-    if (!c->fuse_ea || pos == 0) pass_a(t, c->fuse_ea ? 1 : dmode);
-    passes_bc(t);
-    pass_e(t, 1, 0);
-    const FluidSet d = c->view(1 - q, 1 - l);
-    clock_scan(d.start);
-    launch(c, "k_scatter", k_scatter_b, gf, bp, mb, q, (const int *)c->cellid.get(), c->count.get(), (const int *)d.start,
-           c->perm.get());
-    launch(c, "k_reorder", k_reorder_b, gf, bp, mb, q, (const int *)c->cellid.get(), (const int *)d.start,
-           (const int *)c->perm.get(), reorder_args(c->tmp.posn, c->tmp.veln, c->tmp.drhon, s.mass, s.id, d, c->tmp.src_of));
-}
-
-// k_flow_stats_b on every member's (pos, vel), given as member 0's: every >= 1 = the in-loop sample closing step slot q,
-// 0 = a sample of the state now
-void batch_launch_stats(sphx_batch *b, int q, const double2 *pos, const double2 *vel, int every)
-{
-    sphx_ctx *c = b->mem[0];
-    const sphx_ctx::FlowStats &f = b->fstats;
-    launch_s(c, "k_flow_stats", k_flow_stats_b, dim3(flow_stats_blocks(c), b->M), dim3(kStatsBlock), flow_stats_shmem(f), b->mb,
-             q, flow_stats_args(c, f, pos, vel, every));
-}
-
-// the batch's step slot, for the shared schedule code (capture_slots, enqueue_slots); with the statistics on it ends with
-// the sample of S[1-q], the state the slot leaves (as launch_slot_stats)
-auto batch_slot(sphx_batch *b)
-{
-    return [b](int q, int l, int pos, bool rebuild) {
-        if (b->mem[0]->lpp == 16) batch_step_t<16>(b, q, l, pos, rebuild);
-        else batch_step_t<32>(b, q, l, pos, rebuild);
-        if (b->fstats.on)
-            batch_launch_stats(b, q, b->mem[0]->fpos_[1 - q].get(), b->mem[0]->fvel_[1 - q].get(), b->fstats.cfg.every);
-    };
-}
 
 // arm every member's clock: one budget for all (max_steps) or one per member (b->h_budget, budgets = true)
 void batch_arm(sphx_batch *b, double t_target, long long max_steps, bool budgets)
@@ -277,7 +196,7 @@ void batch_run(sphx_batch *b, double t_target, std::vector<int64_t> budget)
         batch_arm(b, t_target, 0, true);
         for (int m = 0; m < b->M; ++m)
             if (budget[m] == 0) hipLaunchKernelGGL(k_disarm, dim3(1), dim3(1), 0, b->stream, b->mem[m]->clock.get());
-        enqueue_slots(b->sched, b->stream, K, per_graph, slots, exact, batch_slot(b), [b, K] { b->sched.advance(K); });
+        enqueue_slots(b->sched, b->stream, K, per_graph, slots, exact, ctx_slot(b->mem[0]), [b, K] { b->sched.advance(K); });
         const std::vector<int64_t> ex = batch_read(b);
         for (int m = 0; m < b->M; ++m)
             if (budget[m] > 0) budget[m] = std::max<int64_t>(0, budget[m] - ex[m]);
@@ -303,32 +222,14 @@ void batch_check_member(const sphx_batch *b, int m)
         throw Error(SPHX_ERR_ARG, "SPHX:Batch:member", "member " + std::to_string(m) + " out of range [0, " + std::to_string(b->M) + ")");
 }
 
-sphx_batch *batch_stats(sphx_batch *b, bool need_on)
+// the batch's flow statistics (member 0's, see sphx_ctx::fstats)
+FlowStats &batch_stats(sphx_batch *b, bool need_on)
 {
     require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    if (need_on && !b->fstats.on)
+    FlowStats &f = b->mem[0]->fstats;
+    if (need_on && !f.on)
         throw Error(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this batch");
-    return b;
-}
-
-// the replayed graphs carry k_flow_stats_b (and its arguments) or not: a change of the setting re-captures them
-void batch_stats_off(sphx_batch *b)
-{
-    SPHX_HIP(hipStreamSynchronize(b->stream));
-    b->sched.drop_graphs();
-    sphx_ctx::FlowStats &f = b->fstats;
-    f.on = false;
-    f.isum.release();
-    f.dsum.release();
-    f.head.release();
-}
-
-void batch_stats_zero(sphx_batch *b)
-{
-    sphx_ctx::FlowStats &f = b->fstats;
-    f.isum.zero(b->stream);
-    f.dsum.zero(b->stream);
-    f.head.zero(b->stream);
+    return f;
 }
 
 // argument checks (no device): shared fields, refused modes, the kernel forms members of this size would run
@@ -440,6 +341,8 @@ SPHX_EXPORT int sphx_batch_create(sphx_batch **out, int n_members, const sphx_pa
         b->phys.upload(ph.data(), M, b->stream);
         b->mb = Members{c0->clock.get(), b->phys.get(), (long long)c0->cap, c0->grid.ncells + 1, c0->n_vpart, c0->tmp.nl_stride,
                         (long long)c0->tmp.nl_stride * c0->tmp.nl_cap, (long long)c0->tmp.nl_stride * c0->tmp.sl_cap};
+        c0->members = &b->mb;  // member 0 stands for the batch in the step's launch layer
+        c0->n_members = M;
         if (M > 1 && (b->mem[1]->clock.get() != c0->clock.get() + 1 || b->mem[1]->fpos_[0].get() != c0->fpos_[0].get() + c0->cap ||
                       b->mem[1]->nl_idx.get() != c0->nl_idx.get() + b->mb.list))
             throw Error(SPHX_ERR_STATE, "SPHX:Batch:internal", "member arrays are not laid out at the member strides");
@@ -450,7 +353,7 @@ SPHX_EXPORT int sphx_batch_create(sphx_batch **out, int n_members, const sphx_pa
         SPHX_HIP(hipHostMalloc(reinterpret_cast<void **>(&b->h_budget), sizeof(long long) * M, hipHostMallocDefault));
         SPHX_HIP(hipStreamSynchronize(b->stream));
         batch_set_epochs(b);
-        if (prm[0].t_end > t0) (void)capture_slots(b->sched, b->stream, c0->rebuild_every, graph_slots(c0), batch_slot(b));
+        if (prm[0].t_end > t0) (void)capture_slots(b->sched, b->stream, c0->rebuild_every, graph_slots(c0), ctx_slot(b->mem[0]));
         *out = b;
         return SPHX_OK;
     } catch (const Error &e) {
@@ -488,7 +391,7 @@ SPHX_EXPORT int sphx_batch_enqueue_steps(sphx_batch *b, int64_t n_steps)
     // loop condition; sphx_batch_sync realigns and takes the steps still owed
     const int K = b->mem[0]->rebuild_every;
     batch_arm(b, b->mem[0]->prm.t_end, (long long)n_steps, false);
-    enqueue_slots(b->sched, b->stream, K, graph_slots(b->mem[0]), n_steps, true, batch_slot(b), [b, K] { b->sched.advance(K); });
+    enqueue_slots(b->sched, b->stream, K, graph_slots(b->mem[0]), n_steps, true, ctx_slot(b->mem[0]), [b, K] { b->sched.advance(K); });
     for (int m = 0; m < b->M; ++m) b->pending[m] = std::max<int64_t>(b->pending[m], b->mem[m]->h_clock->step) + n_steps;
     return SPHX_OK;
     SPHX_CATCH
@@ -557,29 +460,11 @@ SPHX_EXPORT int sphx_batch_graph_stats(sphx_batch *b, int64_t *slots_replayed, i
 SPHX_EXPORT int sphx_batch_flow_stats_enable(sphx_batch *b, const sphx_flow_stats_config *cfg)
 {
     SPHX_TRY
-    batch_stats(b, false);
-    sphx_ctx::FlowStats checked;
-    stats_configure(checked, b->mem[0]->prm, cfg);  // (bins and bands come from the shared geometry)
-    batch_stats_off(b);
-    sphx_ctx::FlowStats &f = b->fstats;
-    f.cfg = checked.cfg;
-    f.n_bins = checked.n_bins;
-    f.n_bands = checked.n_bands;
-    const size_t nc = (size_t)f.n_bands * f.n_bins * kStatsFields * b->M;
-    try {
-        f.isum.alloc(nc);
-        f.dsum.alloc(nc);
-        f.head.alloc(b->M);
-    } catch (...) {  // out of device memory: the batch goes on without statistics
-        f.isum.release();
-        f.dsum.release();
-        f.head.release();
-        (void)hipGetLastError();
-        throw;
-    }
-    batch_stats_zero(b);
-    SPHX_HIP(hipStreamSynchronize(b->stream));
-    f.on = true;
+    FlowStats &f = batch_stats(b, false);
+    FlowStats checked;
+    checked.configure(b->mem[0]->prm, cfg);  // (bins and bands come from the shared geometry)
+    stats_off(f, b->sched, b->stream);
+    f.enable(checked, b->M, b->stream);  // (out of device memory: the batch goes on without statistics)
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -587,8 +472,8 @@ SPHX_EXPORT int sphx_batch_flow_stats_enable(sphx_batch *b, const sphx_flow_stat
 SPHX_EXPORT int sphx_batch_flow_stats_disable(sphx_batch *b)
 {
     SPHX_TRY
-    batch_stats(b, false);
-    if (b->fstats.on) batch_stats_off(b);
+    FlowStats &f = batch_stats(b, false);
+    if (f.on) stats_off(f, b->sched, b->stream);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -596,9 +481,9 @@ SPHX_EXPORT int sphx_batch_flow_stats_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_flow_stats_reset(sphx_batch *b)
 {
     SPHX_TRY
-    batch_stats(b, true);
+    FlowStats &f = batch_stats(b, true);
     batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
-    batch_stats_zero(b);
+    f.zero(b->stream);
     SPHX_HIP(hipStreamSynchronize(b->stream));
     return SPHX_OK;
     SPHX_CATCH
@@ -610,7 +495,7 @@ SPHX_EXPORT int sphx_batch_flow_stats_sample(sphx_batch *b)
     batch_stats(b, true);
     batch_settle(b);  // every member at the batch's phase: the state sphx_batch_download would return
     const FluidSet fs = b->mem[0]->view(b->sched.cur, b->sched.lay);
-    batch_launch_stats(b, 0, fs.pos, fs.vel, 0);
+    launch_flow_stats(b->mem[0], 0, fs.pos, fs.vel, 0);
     SPHX_HIP(hipGetLastError());
     return SPHX_OK;
     SPHX_CATCH
@@ -621,38 +506,9 @@ SPHX_EXPORT int sphx_batch_flow_stats_read(sphx_batch *b, int band, int capacity
                                            double *t_first, double *t_last)
 {
     SPHX_TRY
-    batch_stats(b, true);
-    const sphx_ctx::FlowStats &f = b->fstats;
-    require(band >= 0 && band < f.n_bands, "SPHX:Stats:band", "band must be 0 (whole channel) .. n_bands");
-    double *out[kStatsFields] = {count, sum_ux, sum_ux2, sum_uy, sum_uy2};
-    bool any = false;
-    for (double *o : out) any = any || o != nullptr;
-    require(!any || capacity >= f.n_bins, "SPHX:Stats:capacity", "capacity is smaller than the number of bins");
-    batch_settle(b);
-    const int M = b->M;
-    const size_t row = (size_t)f.n_bins * kStatsFields, block = (size_t)f.n_bands * row;
-    std::vector<double> sums(any ? (size_t)M * row : 0);
-    std::vector<FlowStatsHead> h(M);
-    if (any)  // band `band` of every member's block, one copy
-        SPHX_HIP(hipMemcpy2DAsync(sums.data(), row * sizeof(double), f.dsum.get() + (size_t)band * row, block * sizeof(double),
-                                  row * sizeof(double), M, hipMemcpyDeviceToHost, b->stream));
-    SPHX_HIP(hipMemcpyAsync(h.data(), f.head.get(), sizeof(FlowStatsHead) * M, hipMemcpyDeviceToHost, b->stream));
-    SPHX_HIP(hipStreamSynchronize(b->stream));
-    for (int m = 0; m < M; ++m)
-        if (h[m].range)
-            throw Error(SPHX_ERR_STATE, "SPHX:Stats:range", "member " + std::to_string(m) +
-                                                           ": a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
-    if (n_bins) *n_bins = f.n_bins;
-    for (int j = 0; j < kStatsFields; ++j)
-        if (out[j])
-            for (int m = 0; m < M; ++m)
-                for (int k = 0; k < f.n_bins; ++k) out[j][(size_t)m * capacity + k] = sums[(size_t)m * row + (size_t)k * kStatsFields + j];
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int m = 0; m < M; ++m) {
-        if (n_samples) n_samples[m] = h[m].n_samples;
-        if (t_first) t_first[m] = h[m].n_samples ? h[m].t_first : nan;
-        if (t_last) t_last[m] = h[m].n_samples ? h[m].t_last : nan;
-    }
+    const FlowStats &f = batch_stats(b, true);
+    stats_read(f, b->stream, [b] { batch_settle(b); }, band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples,
+               t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -113,6 +113,30 @@ struct Schedule {
     }
 };
 
+// Flow statistics (sphx_ctx_flow_stats_*, sphx_batch_flow_stats_*; sphx_flow_stats.hpp) of a context or of the M members of
+// a batch: one configuration, running sums and heads in M blocks (member m's sums at m * block(), its head at m).  While they
+// are on, every step slot ends with k_flow_stats (launch_slot_stats).
+struct FlowStats {
+    bool on = false;
+    int members = 1;
+    sphx_flow_stats_config cfg{};
+    int n_bins = 0, n_bands = 1;  // (n_bands counts band 0)
+    DevBuf<unsigned long long> isum;
+    DevBuf<double> dsum;
+    DevBuf<FlowStatsHead> head;
+
+    size_t row() const { return (size_t)n_bins * kStatsFields; }  // the sums of one band ...
+    size_t block() const { return (size_t)n_bands * row(); }      // ... and of one member
+    size_t shmem() const { return block() * sizeof(unsigned long long); }  // the LDS counters of a workgroup
+
+    void configure(const sphx_params &prm, const sphx_flow_stats_config *cfg);
+    void enable(const FlowStats &checked, int M, hipStream_t st);
+    void zero(hipStream_t st) { isum.zero(st); dsum.zero(st); head.zero(st); }
+    void release() { isum.release(); dsum.release(); head.release(); }
+    void read(hipStream_t st, int band, int stride, bool sums, double *const out[kStatsFields], int64_t *n_samples, double *t_first,
+              double *t_last) const;
+};
+
 }  // namespace sphx
 
 using namespace sphx;
@@ -246,15 +270,7 @@ struct sphx_ctx {
     bool coded_lists = false;    // ... and the lists name tile slots instead of index differences (kSlotCodes, sphx_kernels.hpp)
     bool tail_clock = false;     // move steps carry their clock update in a tail workgroup of pass E (small channels)
 
-    // Flow statistics (sphx_ctx_flow_stats_*, sphx_flow_stats.hpp): when on, every step slot ends with k_flow_stats
-    struct FlowStats {
-        bool on = false;
-        sphx_flow_stats_config cfg{};
-        int n_bins = 0, n_bands = 1;  // (n_bands counts band 0)
-        DevBuf<unsigned long long> isum;
-        DevBuf<double> dsum;
-        DevBuf<FlowStatsHead> head;
-    } fstats;
+    FlowStats fstats;  // (of a batch: member 0's serves every member, the other members' stay off)
 
     // Step history (sphx_ctx_history_*, sphx_history.hpp): when on, every step slot ends with k_step_history
     struct History {
@@ -268,6 +284,9 @@ struct sphx_ctx {
     sphx::BatchArena *arena = nullptr;
     int member = 0;
     const int *out_ids = nullptr;  // after a realignment: ids of the slots the last step's outputs are stored in (else fid_[out_lay])
+    // Member 0 stands for the whole batch in the step's launch layer (launch_forms): the batch's member table and M
+    const Members *members = nullptr;
+    int n_members = 1;
 
     FluidSet view(int q, int l)
     {
@@ -465,11 +484,68 @@ void with_form(const sphx_ctx *c, bool lds, F &&f)
     else f(std::integral_constant<int, 0>{}, std::false_type{});
 }
 
+// ---- Where a batch differs.  The step slots of a batch are launched on its member 0 (sphx_ctx::members), and a kernel of the
+// step runs in its batch form there: the "_b" wrapper of the same body (Members, sphx_kernels.hpp) on a grid of M rows, member =
+// blockIdx.y, taking (members, q, ...) for (clock, q, ...) and every pointer as member 0's.  launch_forms is the only place that
+// tells the two apart; only the compact kernels have batch forms. ----
+
+// a step kernel named together with its batch form (nullptr: it has none)
+template <typename K, typename KB = std::nullptr_t>
+struct Forms {
+    K one;
+    KB batch = nullptr;
+};
+template <typename K, typename KB> Forms(K, KB) -> Forms<K, KB>;
+template <typename K> Forms(K) -> Forms<K>;
+
+// An argument of the single form that its batch form does not take: per_member -- the batch form has it by member, from the
+// Members table; single_only -- it is fixed at zero there, and so must be zero for a batch
+template <typename T, bool MustBeZero>
+struct NotInBatch { T v; };
+template <typename T> NotInBatch<T, false> per_member(T v) { return {v}; }
+template <typename T> NotInBatch<T, true> single_only(T v) { return {v}; }
+
+[[noreturn]] void no_batch_form(const char *name)
+{
+    throw Error(SPHX_ERR_STATE, "SPHX:Batch:internal", std::string("internal: a batch met ") + name + ", which has no batch form here");
+}
+// a launch of the step that no batch may reach
+void single_form_only(const sphx_ctx *c, const char *name) { if (c->members) no_batch_form(name); }
+
+template <typename T> std::tuple<T> single_arg(const T &x) { return std::tuple<T>(x); }
+template <typename T, bool Z> std::tuple<T> single_arg(NotInBatch<T, Z> x) { return std::tuple<T>(x.v); }
+template <typename T> std::tuple<T> batch_arg(const char *, const T &x) { return std::tuple<T>(x); }
+template <typename T, bool Z> std::tuple<> batch_arg(const char *name, NotInBatch<T, Z> x)
+{
+    if constexpr (Z) { if (!(x.v == T{})) no_batch_form(name); }
+    return {};
+}
+
+// kernel k on `blocks` workgroups (per member) of `block` threads: k.one(clock, q, args...) or k.batch(members, q, args...)
+template <typename C, typename... P, typename KB, typename... A>
+void launch_forms(sphx_ctx *c, const char *name, Forms<void (*)(C, P...), KB> k, unsigned blocks, unsigned block, size_t shmem, int q, const A &... args)
+{
+    if (!c->members) {
+        std::apply([&](const auto &... a) { launch_s(c, name, k.one, dim3(blocks), dim3(block), shmem, static_cast<C>(c->clock.get()), q, a...); },
+                   std::tuple_cat(single_arg(args)...));
+    } else if constexpr (std::is_null_pointer_v<KB>) {
+        no_batch_form(name);
+    } else {
+        std::apply([&](const auto &... a) { launch_s(c, name, k.batch, dim3(blocks, c->n_members), dim3(block), shmem, *c->members, q, a...); },
+                   std::tuple_cat(batch_arg(name, args)...));
+    }
+}
+
 // every pass kernel takes (clock, q, grid, phys, S, temporaries, walls) first
-template <typename K, typename... X>
+template <typename K, typename KB, typename... X>
+void launch_pass(sphx_ctx *c, const char *name, Forms<K, KB> k, unsigned blocks, int q, const FluidSet &s, const FluidTmp &t, X... extra)
+{
+    launch_forms(c, name, k, blocks, kBlock, 0, q, c->grid, per_member(c->phys), s, t, c->walls, extra...);
+}
+template <typename K, typename... X>  // (a pass kernel that has no batch form)
 void launch_pass(sphx_ctx *c, const char *name, K kernel, unsigned blocks, int q, const FluidSet &s, const FluidTmp &t, X... extra)
 {
-    launch(c, name, kernel, dim3(blocks), dim3(kBlock), c->clock.get(), q, c->grid, c->phys, s, t, c->walls, extra...);
+    launch_pass(c, name, Forms{kernel}, blocks, q, s, t, extra...);
 }
 
 // 16 / 32 lanes per particle (small channels) run the compact kernels (32-bit lists); fewer lanes (large channels) the "_w"
@@ -487,10 +563,10 @@ void launch_pass_a(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Pas
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16) {
-            if (mode == PassA::Sweep) launch_pass(c, sweep_name, k_density<LPP, 0>, np, q, s, t, cond_sweep);
+            if (mode == PassA::Sweep) launch_pass(c, sweep_name, Forms{k_density<LPP, 0>, k_density_b<LPP, 0>}, np, q, s, t, cond_sweep);
             else if (mode == PassA::SweepBuild && c->fold_rebin) launch_pass(c, sweep_name, k_density_zero<LPP>, np, q, s, t, cond_sweep);
-            else if (sweeps) launch_pass(c, sweep_name, k_density<LPP, 1>, np, q, s, t, cond_sweep);
-            if (walks) launch_pass(c, "k_density_walk", k_density<LPP, 2>, np, q, s, t, cond_walk);
+            else if (sweeps) launch_pass(c, sweep_name, Forms{k_density<LPP, 1>, k_density_b<LPP, 1>}, np, q, s, t, cond_sweep);
+            if (walks) launch_pass(c, "k_density_walk", Forms{k_density<LPP, 2>, k_density_b<LPP, 2>}, np, q, s, t, cond_walk);
         } else {
             // the cell sweep: mode 0 writes the step's list, mode 1 the superset list as well
             // the build variant of a dynamic context is idle on four steps out of five: a grid-stride launch of an eighth
@@ -517,7 +593,7 @@ void launch_pass_b(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t)
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16)
-            launch_pass(c, "k_kgc", k_kgc<LPP>, np, q, s, t, finish_half);
+            launch_pass(c, "k_kgc", Forms{k_kgc<LPP>, k_kgc_b<LPP>}, np, q, s, t, finish_half);
         else
             with_form<LPP, kSlotCodes, tile_slots(LPP)>(c, c->lds_tiles_be, [&](auto tile, auto coded) {
                 launch_pass(c, "k_kgc", k_kgc_w<LPP, decltype(tile)::value, decltype(coded)::value>, np, q, s, t, finish_half);
@@ -531,7 +607,7 @@ void launch_pass_cd(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Ra
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16) {
-            launch_pass(c, rate == Rate::Inner ? "k_forces_inner" : "k_forces", k_forces<LPP>, np, q, s, t, (int)rate);
+            launch_pass(c, rate == Rate::Inner ? "k_forces_inner" : "k_forces", Forms{k_forces<LPP>, k_forces_b<LPP>}, np, q, s, t, (int)rate);
         } else {
             auto forces = [&](auto tile, auto coded) {
                 launch_pass(c, "k_forces", k_forces_w<LPP, decltype(tile)::value, decltype(coded)::value>, np, q, s, t);
@@ -553,7 +629,8 @@ void launch_pass_e(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Tai
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16)
-            launch_pass(c, name, k_continuity<LPP, false, 0>, ne, q, s, t, (int)hist, (int)tail, (int)rate);
+            launch_pass(c, name, Forms{k_continuity<LPP, false, 0>, k_continuity_b<LPP>}, ne, q, s, t, (int)hist, (int)tail,
+                        single_only((int)rate));
         else
             with_form<LPP, kSlotCodes, tile_slots(LPP)>(c, c->lds_tiles_be, [&](auto tile, auto coded) {
                 launch_pass(c, name, k_continuity<LPP, true, decltype(tile)::value, decltype(coded)::value>, ne, q, s, t, (int)hist, (int)tail, 0);
@@ -619,58 +696,60 @@ void launch_clock_scan(sphx_ctx *c, int q, ClockScan a)
     int n_red = a.vpart ? c->n_vpart : 0;
     if (a.vpart && c->n_vtiles) {
         double *vtile = c->vtile.get(), *dtile = vtile + c->n_vtiles;
+        single_form_only(c, "k_max_tiles");
         launch(c, "k_max_tiles", k_max_tiles, dim3(c->n_vtiles), dim3(kScanBlock), (const Clock *)clk, q, c->n_vpart, a.vpart,
                a.dpart, vtile, dtile);
         a.vpart = vtile;
         if (a.dpart) a.dpart = dtile;
         n_red = c->n_vtiles;
     }
-    auto clock = [&](const int *cnt, int *start, int n, bool) {
-        launch(c, "k_clock_scan", k_clock_scan, dim3(1), dim3(kScanBlock), clk, q, c->phys, n_red, a.vpart, a.vmax_global,
-               (const int *)c->flags.get(), cnt, start, n, a.n_new, a.dpart, a.rebuilt, a.half_skin, a.slab_counters,
-               a.vpart_reset, a.dyn_K);
+    auto clock = [&](const int *cnt, int *start, int n, bool of_tiles) {
+        if (of_tiles) single_form_only(c, "k_clock_scan of tile sums");
+        launch_forms(c, "k_clock_scan", Forms{k_clock_scan, k_clock_scan_b}, 1, kScanBlock, 0, q, per_member(c->phys), per_member(n_red),
+                     a.vpart, single_only(a.vmax_global), (const int *)c->flags.get(), cnt, start, n, single_only(a.n_new), a.dpart,
+                     a.rebuilt, a.half_skin, single_only(a.slab_counters), a.vpart_reset, single_only(a.dyn_K));
     };
     if (a.start_next) launch_scan_around(c, clk, q, a.count, a.start_next, clock);  // clock update and cell scan share one single-block kernel
     else clock(nullptr, nullptr, 0, false);
 }
 
 // index -> cell slot, then the gather of the persistent fields into destination view d
-void launch_scatter_reorder(sphx_ctx *c, const Clock *clk, int q, const ReorderArgs &ra, const FluidSet &d, int max_blocks = 0)
+void launch_scatter_reorder(sphx_ctx *c, int q, const ReorderArgs &ra, const FluidSet &d, int max_blocks = 0)
 {
-    const dim3 g1(max_blocks > 0 ? std::min(c->n_blocks_flat, max_blocks) : c->n_blocks_flat), bp(kBlock);
-    launch(c, "k_scatter", k_scatter, g1, bp, clk, q, 0, (const int *)c->cellid.get(), c->count.get(), (const int *)d.start,
-           c->perm.get());
-    launch(c, "k_reorder", k_reorder, g1, bp, clk, q, 0, (const int *)c->cellid.get(), (const int *)d.start,
-           (const int *)c->perm.get(), ra);
+    const unsigned g1 = max_blocks > 0 ? std::min(c->n_blocks_flat, max_blocks) : c->n_blocks_flat;
+    const int n_fixed = 0;  // (the count is the clock's)
+    launch_forms(c, "k_scatter", Forms{k_scatter, k_scatter_b}, g1, kBlock, 0, q, single_only(n_fixed), (const int *)c->cellid.get(),
+                 c->count.get(), (const int *)d.start, c->perm.get());
+    launch_forms(c, "k_reorder", Forms{k_reorder, k_reorder_b}, g1, kBlock, 0, q, single_only(n_fixed), (const int *)c->cellid.get(),
+                 (const int *)d.start, (const int *)c->perm.get(), ra);
 }
 
 // The folded re-binning step (sphx_ctx::fold_rebin): pass CD with the histogram, then pass E re-binning into view d
-template <int LPP>
-void launch_fold_rebin_t(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &d)
-{
-    launch_pass(c, "k_forces_hist", k_forces_hist<LPP>, c->n_blocks_particles, q, s, t, 0);
-    launch_pass(c, "k_continuity_rebin", k_continuity_rebin<LPP>, c->n_blocks_particles + 1, q, s, t, d);
-}
 void launch_fold_rebin(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &d)
 {
-    switch (c->lpp) {
-        case 16: launch_fold_rebin_t<16>(c, q, s, t, d); break;
-        case 32: launch_fold_rebin_t<32>(c, q, s, t, d); break;
-        default: throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fold", "internal: folded re-binning step at this lane count");
-    }
+    with_lpp(c, [&](auto lpp) {
+        constexpr int LPP = decltype(lpp)::value;
+        if constexpr (LPP >= 16) {
+            launch_pass(c, "k_forces_hist", k_forces_hist<LPP>, c->n_blocks_particles, q, s, t, 0);
+            launch_pass(c, "k_continuity_rebin", k_continuity_rebin<LPP>, c->n_blocks_particles + 1, q, s, t, d);
+        } else {
+            throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fold", "internal: folded re-binning step at this lane count");
+        }
+    });
 }
 // Pass E of a step and pass A of the next in one launch.  Tail::None: without the clock workgroup (kernel timing)
 void launch_fused_ea(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &sn, const FluidTmp &tn, Tail tail = Tail::Clock)
 {
-    auto go = [&](auto kernel) { launch_pass(c, "k_continuity_density", kernel, 2 * c->n_blocks_particles + (int)tail, q, s, t, sn, tn, (int)tail); };
-    switch (c->lpp) {  // 16 / 32 lanes per particle: the compact kernels; fewer: their large-channel forms
-        case 2: go(k_continuity_density_w<2>); break;
-        case 4: go(k_continuity_density_w<4>); break;
-        case 8: go(k_continuity_density_w<8>); break;
-        case 16: go(k_continuity_density<16>); break;
-        case 32: go(k_continuity_density<32>); break;
-        default: throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fuse", "internal: fused E|A launch at this lane count");
-    }
+    const unsigned blocks = 2 * c->n_blocks_particles + (int)tail;
+    with_lpp(c, [&](auto lpp) {  // 16 / 32 lanes per particle: the compact kernels; fewer: their large-channel forms
+        constexpr int LPP = decltype(lpp)::value;
+        if constexpr (LPP >= 16)
+            launch_pass(c, "k_continuity_density", Forms{k_continuity_density<LPP>, k_continuity_density_b<LPP>}, blocks, q, s, t, sn, tn, (int)tail);
+        else if constexpr (LPP >= 2)
+            launch_pass(c, "k_continuity_density", k_continuity_density_w<LPP>, blocks, q, s, t, sn, tn, (int)tail);
+        else
+            throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fuse", "internal: fused E|A launch at this lane count");
+    });
 }
 
 // One single-GPU step slot: state S[q], layout L[l].  rebuild: the step ends with re-binning into S[1-q], L[1-l]
@@ -738,7 +817,7 @@ void launch_step(sphx_ctx *c, int q, int l, int pos, bool rebuild)
     clock.start_next = d.start;
     clock.rebuilt = 1;
     launch_clock_scan(c, q, clock);
-    launch_scatter_reorder(c, c->clock.get(), q, reorder_args(c->tmp.posn, c->tmp.veln, c->tmp.drhon, s.mass, s.id, d, c->tmp.src_of), d);
+    launch_scatter_reorder(c, q, reorder_args(c->tmp.posn, c->tmp.veln, c->tmp.drhon, s.mass, s.id, d, c->tmp.src_of), d);
 }
 
 // One step slot of a dynamic context: the four passes on S[q] writing the new state into S[1-q], the clock (which
@@ -767,15 +846,17 @@ void launch_step_dyn(sphx_ctx *c, int q)
     launch(c, "k_bin", k_bin, g1, bp, (const Clock *)clk, qf | kOnlyIfNoHistogram, c->grid, 0, (const double2 *)o.pos,
            c->cellid.get(), c->count.get());  // drift-triggered re-binnings only: pass E bins on the scheduled ones
     launch_cell_scan(c, clk, qf, c->count.get(), d.start);
-    launch_scatter_reorder(c, clk, qf, reorder_args(o.pos, o.vel, o.drho, s.mass, s.id, d, c->tmp.src_of), d, kDynBlocks);
+    launch_scatter_reorder(c, qf, reorder_args(o.pos, o.vel, o.drho, s.mass, s.id, d, c->tmp.src_of), d, kDynBlocks);
     CopyBack cb{d.pos, d.vel, d.posb, o.pos, o.vel, o.posb, d.drho, d.mass, o.drho, o.mass, d.id, d.cell, d.start,
                 o.id, o.cell, o.start, c->grid.ncells + 1, lean ? 1 : 0};
     launch(c, "k_copyback", k_copyback, g1, bp, (const Clock *)clk, qf, cb);
 }
 
-// the arguments of k_flow_stats (k_flow_stats_b: member 0's pointers) for statistics f of channels like c
-FlowStatsArgs flow_stats_args(const sphx_ctx *c, const sphx_ctx::FlowStats &f, const double2 *pos, const double2 *vel, int every)
+// k_flow_stats on (pos, vel) -- of a batch: member 0's -- into c->fstats: every >= 1 = the in-loop sample closing step slot q,
+// 0 = a sample of the state now
+void launch_flow_stats(sphx_ctx *c, int q, const double2 *pos, const double2 *vel, int every)
 {
+    const FlowStats &f = c->fstats;
     FlowStatsArgs a{};
     a.pos = pos; a.vel = vel;
     a.isum = f.isum.get(); a.dsum = f.dsum.get(); a.head = f.head.get();
@@ -784,22 +865,9 @@ FlowStatsArgs flow_stats_args(const sphx_ctx *c, const sphx_ctx::FlowStats &f, c
     for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
     a.n_bins = f.n_bins; a.n_bands = f.n_bands;
     a.every = every;
-    return a;
-}
-
-// workgroups of one channel's sample, and their LDS counters
-unsigned flow_stats_blocks(const sphx_ctx *c)
-{
-    return std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kStatsBlock * kStatsPerThread), 1u, (unsigned)kStatsMaxBlocks);
-}
-size_t flow_stats_shmem(const sphx_ctx::FlowStats &f) { return (size_t)f.n_bands * f.n_bins * kStatsFields * sizeof(unsigned long long); }
-
-// k_flow_stats on (pos, vel): every >= 1 = the in-loop sample closing step slot q, 0 = a sample of the state now
-void launch_flow_stats(sphx_ctx *c, int q, const double2 *pos, const double2 *vel, int every)
-{
-    const sphx_ctx::FlowStats &f = c->fstats;
-    launch_s(c, "k_flow_stats", k_flow_stats, dim3(flow_stats_blocks(c)), dim3(kStatsBlock), flow_stats_shmem(f),
-             (const Clock *)c->clock.get(), q, flow_stats_args(c, f, pos, vel, every));
+    // workgroups of one channel's sample
+    const unsigned blocks = std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kStatsBlock * kStatsPerThread), 1u, (unsigned)kStatsMaxBlocks);
+    launch_forms(c, "k_flow_stats", Forms{k_flow_stats, k_flow_stats_b}, blocks, kStatsBlock, f.shmem(), q, a);
 }
 
 // the state step slot q leaves is in S[1-q] on every schedule (a re-binning step reorders into S[1-q] too, a dynamic
@@ -819,6 +887,7 @@ void launch_slot_history(sphx_ctx *c, int q, int l, bool rebuild)
 {
     const sphx_ctx::History &h = c->hist;
     if (!h.on) return;
+    single_form_only(c, "k_step_history");
     const FluidSet s = c->dyn ? c->view(1 - q, 0) : c->view(1 - q, rebuild ? 1 - l : l);
     HistoryArgs a{};
     a.records = h.records.get(); a.part = h.part.get(); a.head = h.head.get();
@@ -1980,23 +2049,24 @@ sphx_ctx *stats_ctx(sphx_ctx *c, bool need_on)
     return c;
 }
 
-// the replayed graphs carry k_flow_stats (and its arguments) or not: a change of the setting re-captures them
-void stats_drop_graphs(sphx_ctx *c)
+// the replayed graphs of schedule s carry k_flow_stats (and its arguments) or not: a change of the setting re-captures them
+void stats_drop_graphs(Schedule &s, hipStream_t st)
 {
-    SPHX_HIP(hipStreamSynchronize(c->stream));
-    c->sched.drop_graphs();
+    SPHX_HIP(hipStreamSynchronize(st));
+    s.drop_graphs();
 }
 
-void stats_zero(sphx_ctx *c)
+void stats_off(FlowStats &f, Schedule &s, hipStream_t st)
 {
-    sphx_ctx::FlowStats &f = c->fstats;
-    f.isum.zero(c->stream);
-    f.dsum.zero(c->stream);
-    f.head.zero(c->stream);
+    stats_drop_graphs(s, st);
+    f.on = false;
+    f.release();
 }
 
-// the checked configuration cfg of channels with parameters prm into f (cfg, n_bins, n_bands); SPHX:Stats:config errors
-void stats_configure(sphx_ctx::FlowStats &f, const sphx_params &prm, const sphx_flow_stats_config *cfg)
+}  // namespace
+
+// the checked configuration cfg of channels with parameters prm (cfg, n_bins, n_bands); SPHX:Stats:config errors
+void FlowStats::configure(const sphx_params &prm, const sphx_flow_stats_config *cfg)
 {
     require(cfg != nullptr, "SPHX:Stats:config", "config must not be NULL");
     require(cfg->n_bins >= 0, "SPHX:Stats:config", "n_bins must be >= 0 (0 = the reference's profile bins)");
@@ -2006,13 +2076,80 @@ void stats_configure(sphx_ctx::FlowStats &f, const sphx_params &prm, const sphx_
     for (int b = 0; b < cfg->n_bands; ++b)
         require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, "SPHX:Stats:config",
                 "band centres must be finite and half-widths finite and >= 0");
-    const int n_bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
-    require((int64_t)n_bins * (cfg->n_bands + 1) <= kStatsMaxBins, "SPHX:Stats:config",
+    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
+    require((int64_t)bins * (cfg->n_bands + 1) <= kStatsMaxBins, "SPHX:Stats:config",
             "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
-    f.cfg = *cfg;
-    for (int b = cfg->n_bands; b < 2; ++b) { f.cfg.band_x[b] = 0.0; f.cfg.band_hw[b] = 0.0; }
-    f.n_bins = n_bins;
-    f.n_bands = cfg->n_bands + 1;
+    this->cfg = *cfg;
+    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
+    n_bins = bins;
+    n_bands = cfg->n_bands + 1;
+}
+
+// on, with the checked configuration and zeroed sums for M members; out of device memory: it stays off, with nothing allocated
+void FlowStats::enable(const FlowStats &checked, int M, hipStream_t st)
+{
+    cfg = checked.cfg;
+    n_bins = checked.n_bins;
+    n_bands = checked.n_bands;
+    members = M;
+    try {
+        isum.alloc(block() * M);
+        dsum.alloc(block() * M);
+        head.alloc(M);
+    } catch (...) {
+        release();
+        (void)hipGetLastError();
+        throw;
+    }
+    zero(st);
+    SPHX_HIP(hipStreamSynchronize(st));
+    on = true;
+}
+
+// Band `band` of every member's sums (sums: into out[field][m * stride + bin], where out[field] is given) and the heads
+// (n_samples[m], t_first[m], t_last[m], where given).  SPHX:Stats:range when a member's sticky flag is up.
+void FlowStats::read(hipStream_t st, int band, int stride, bool sums, double *const out[kStatsFields], int64_t *n_samples,
+                     double *t_first, double *t_last) const
+{
+    const int M = members;
+    std::vector<double> host(sums ? (size_t)M * row() : 0);
+    std::vector<FlowStatsHead> h(M);
+    if (sums)  // one copy: a row of every member's block
+        SPHX_HIP(hipMemcpy2DAsync(host.data(), row() * sizeof(double), dsum.get() + (size_t)band * row(), block() * sizeof(double),
+                                  row() * sizeof(double), M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(FlowStatsHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    for (int m = 0; m < M; ++m)
+        if (h[m].range)
+            throw Error(SPHX_ERR_STATE, "SPHX:Stats:range", (M > 1 ? "member " + std::to_string(m) + ": " : std::string()) +
+                                                           "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
+    for (int j = 0; j < kStatsFields; ++j)
+        if (out[j])
+            for (int m = 0; m < M; ++m)
+                for (int k = 0; k < n_bins; ++k) out[j][(size_t)m * stride + k] = host[(size_t)m * row() + (size_t)k * kStatsFields + j];
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int m = 0; m < M; ++m) {
+        if (n_samples) n_samples[m] = h[m].n_samples;
+        if (t_first) t_first[m] = h[m].n_samples ? h[m].t_first : nan;
+        if (t_last) t_last[m] = h[m].n_samples ? h[m].t_last : nan;
+    }
+}
+
+namespace {
+
+// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
+template <typename Settle>
+void stats_read(const FlowStats &f, hipStream_t st, Settle &&settle, int band, int capacity, int *n_bins, double *count, double *sum_ux,
+                double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples, double *t_first, double *t_last)
+{
+    require(band >= 0 && band < f.n_bands, "SPHX:Stats:band", "band must be 0 (whole channel) .. n_bands");
+    double *const out[kStatsFields] = {count, sum_ux, sum_ux2, sum_uy, sum_uy2};
+    bool any = false;
+    for (double *o : out) any = any || o != nullptr;
+    require(!any || capacity >= f.n_bins, "SPHX:Stats:capacity", "capacity is smaller than the number of bins");
+    settle();
+    f.read(st, band, capacity, any, out, n_samples, t_first, t_last);
+    if (n_bins) *n_bins = f.n_bins;
 }
 
 }  // namespace
@@ -2021,20 +2158,10 @@ SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_co
 {
     SPHX_TRY
     stats_ctx(c, false);
-    sphx_ctx::FlowStats checked;
-    stats_configure(checked, c->prm, cfg);
-    stats_drop_graphs(c);
-    sphx_ctx::FlowStats &f = c->fstats;
-    f.cfg = checked.cfg;
-    f.n_bins = checked.n_bins;
-    f.n_bands = checked.n_bands;
-    const size_t nc = (size_t)f.n_bands * f.n_bins * kStatsFields;
-    f.isum.alloc(nc);
-    f.dsum.alloc(nc);
-    f.head.alloc(1);
-    stats_zero(c);
-    SPHX_HIP(hipStreamSynchronize(c->stream));
-    f.on = true;
+    FlowStats checked;
+    checked.configure(c->prm, cfg);
+    stats_off(c->fstats, c->sched, c->stream);
+    c->fstats.enable(checked, 1, c->stream);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2043,13 +2170,7 @@ SPHX_EXPORT int sphx_ctx_flow_stats_disable(sphx_ctx *c)
 {
     SPHX_TRY
     stats_ctx(c, false);
-    if (!c->fstats.on) return SPHX_OK;
-    stats_drop_graphs(c);
-    sphx_ctx::FlowStats &f = c->fstats;
-    f.on = false;
-    f.isum.release();
-    f.dsum.release();
-    f.head.release();
+    if (c->fstats.on) stats_off(c->fstats, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2059,7 +2180,7 @@ SPHX_EXPORT int sphx_ctx_flow_stats_reset(sphx_ctx *c)
     SPHX_TRY
     stats_ctx(c, true);
     settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
-    stats_zero(c);
+    c->fstats.zero(c->stream);
     SPHX_HIP(hipStreamSynchronize(c->stream));
     return SPHX_OK;
     SPHX_CATCH
@@ -2083,29 +2204,8 @@ SPHX_EXPORT int sphx_ctx_flow_stats_read(sphx_ctx *c, int band, int capacity, in
 {
     SPHX_TRY
     stats_ctx(c, true);
-    const sphx_ctx::FlowStats &f = c->fstats;
-    require(band >= 0 && band < f.n_bands, "SPHX:Stats:band", "band must be 0 (whole channel) .. n_bands");
-    double *out[kStatsFields] = {count, sum_ux, sum_ux2, sum_uy, sum_uy2};
-    bool any = false;
-    for (double *o : out) any = any || o != nullptr;
-    require(!any || capacity >= f.n_bins, "SPHX:Stats:capacity", "capacity is smaller than the number of bins");
-    settle_owed(c);
-    std::vector<double> sums((size_t)f.n_bins * kStatsFields);
-    FlowStatsHead h{};
-    SPHX_HIP(hipMemcpyAsync(sums.data(), f.dsum.get() + (size_t)band * f.n_bins * kStatsFields, sums.size() * sizeof(double),
-                            hipMemcpyDeviceToHost, c->stream));
-    SPHX_HIP(hipMemcpyAsync(&h, f.head.get(), sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    SPHX_HIP(hipStreamSynchronize(c->stream));
-    if (h.range)
-        throw Error(SPHX_ERR_STATE, "SPHX:Stats:range", "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
-    if (n_bins) *n_bins = f.n_bins;
-    for (int j = 0; j < kStatsFields; ++j)
-        if (out[j])
-            for (int k = 0; k < f.n_bins; ++k) out[j][k] = sums[(size_t)k * kStatsFields + j];
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (n_samples) *n_samples = h.n_samples;
-    if (t_first) *t_first = h.n_samples ? h.t_first : nan;
-    if (t_last) *t_last = h.n_samples ? h.t_last : nan;
+    stats_read(c->fstats, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples,
+               t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2140,7 +2240,7 @@ SPHX_EXPORT int sphx_ctx_history_enable(sphx_ctx *c, const sphx_history_config *
     require(cfg->every >= 1, "SPHX:History:config", "every must be >= 1");
     require(cfg->capacity >= 1 && cfg->capacity <= kHistoryMaxCapacity, "SPHX:History:config", "capacity must be 1 .. 1 << 22 records");
     require(std::isfinite(cfg->t_from), "SPHX:History:config", "t_from must be finite");
-    stats_drop_graphs(c);  // the replayed graphs carry k_step_history (and its arguments) or not
+    stats_drop_graphs(c->sched, c->stream);  // the replayed graphs carry k_step_history (and its arguments) or not
     sphx_ctx::History &h = c->hist;
     history_release(h);
     try {
@@ -2165,7 +2265,7 @@ SPHX_EXPORT int sphx_ctx_history_disable(sphx_ctx *c)
     SPHX_TRY
     history_ctx(c, false);
     if (!c->hist.on) return SPHX_OK;
-    stats_drop_graphs(c);
+    stats_drop_graphs(c->sched, c->stream);
     history_release(c->hist);
     return SPHX_OK;
     SPHX_CATCH
@@ -2534,7 +2634,7 @@ void slab_finish_impl(sphx_ctx *c, const double *recv_left_dev, const double *re
         clock.rebuilt = 1;
         clock.slab_counters = c->counters.get();
         launch_clock_scan(c, q, clock);
-        launch_scatter_reorder(c, clk, q,
+        launch_scatter_reorder(c, q,
                                reorder_args(c->kpos.get(), c->kvel.get(), c->kdrho.get(), c->kmass.get(), c->kid.get(), d, nullptr), d);
     };
     const void *key[3] = {recv_left_dev, recv_right_dev, vmax_global_dev};
@@ -2978,7 +3078,7 @@ void slab_phase3(sphx_ctx *c)  // message A arrived (and with it the ids of the 
            (const int *)c->ids_r_[1].get(), c->n_new.get(), c->flags.get(), c->ticket.get());
     const int kRebinBlocks = 4096;  // grid-stride: on the steps that do not re-bin these launches return at once
     launch_cell_scan(c, clk, qf, c->count.get(), d.start);
-    launch_scatter_reorder(c, clk, qf,
+    launch_scatter_reorder(c, qf,
                            reorder_args(c->kpos.get(), c->kvel.get(), c->kdrho.get(), c->kmass.get(), c->kid.get(), d, nullptr,
                                         c->slot_of_id.get()),
                            d, kRebinBlocks);

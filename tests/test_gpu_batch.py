@@ -104,6 +104,32 @@ def test_shared_moving_walls_and_uneven_mass(cfgmod, geom, capi, oracle):
     assert got[1]["pairs"] == ref["stats"]["n_pairs_last"]
 
 
+def test_rebuild_every_one_bit_identical_to_standalone(cfgmod, geom, capi):
+    """No skin: every slot re-bins and the clock is a launch of its own (k_clock_scan with the cell scan), as one call and
+    as one-step calls."""
+    members = _members(cfgmod, geom, 0.05, 1.5, VARIANTS[:3])
+    kw = dict(t_end=1e9, lanes_per_particle=16, rebuild_every=1)
+    n = 9
+    refs = []
+    for prm, parts in members:
+        with _ctx(capi, prm, parts, **kw) as ctx:
+            st = ctx.advance(1e9, max_steps=n)
+            refs.append(_everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True)))
+    for eager in (False, True):
+        with _batch(capi, members, **kw) as b:
+            assert b.info()["rebuild_every"] == 1
+            if eager:
+                for _ in range(n):
+                    sts = b.advance(1e9, max_steps=1)
+            else:
+                sts = b.advance(1e9, max_steps=n)
+            got = [_everything(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
+            assert b.info()["realignments"] == 0
+        for m in range(len(members)):
+            assert got[m]["step"] == n
+            _assert_identical(got[m], refs[m], f"member {m} eager={eager}, rebuild_every=1")
+
+
 def test_single_member_equals_standalone(cfgmod, geom, capi):
     members = _members(cfgmod, geom, 0.025, 1.5, VARIANTS[1:2])
     with _batch(capi, members, t_end=1e9) as b:

@@ -1,9 +1,10 @@
 """Manual probe (not a test): the aggregate rate of a batched context (include/sphx.h section 2b) against one standalone context.
-    python tools/probes/probe_batch.py [--case C2 --case dp04] [--members 1,2,4,...] [--steps N] [--reps R]
+    python tools/probes/probe_batch.py [--case C2 --case dp04] [--members 1,2,4,...] [--steps N] [--reps R] [--call S]
 Per case (C2 = dp 0.025, DL 3; dp04 = dp 0.04, DL 3; developed parabolic start, members jittered by their own seed) and
 member count M: warmed graphs, then R timed rounds of enqueue_steps(N) + sync around a host clock, standalone and batch
 alternating.  Rate = M * n_total * N / seconds (particle-steps/s).  One JSON line per (case, M): the rounds, their median,
-and the ratio of the batch's median aggregate rate to the standalone's."""
+and the ratio of the batch's median aggregate rate to the standalone's.  --call S enqueues the N steps of a round in calls of S
+steps: below the shortest graph (4 steps) every slot is launched eagerly, which is where host time per launch shows."""
 import argparse
 import importlib
 import json
@@ -35,13 +36,16 @@ def member_state(prm, seed):
     return dict(parts, pos=pos, vel=vel)
 
 
-def rounds(obj, steps, reps, sink):
-    obj.enqueue_steps(steps)  # warm: graphs captured and replayed once
-    obj.sync()
+def rounds(obj, steps, reps, sink, call):
+    def enqueue():
+        for _ in range(steps // call):
+            obj.enqueue_steps(call)
+        obj.sync()
+
+    enqueue()  # warm: graphs captured and replayed once
     for _ in range(reps):
         t0 = time.perf_counter()
-        obj.enqueue_steps(steps)
-        obj.sync()
+        enqueue()
         sink.append(time.perf_counter() - t0)
 
 
@@ -51,7 +55,10 @@ def main():
     ap.add_argument("--members", default="1,2,4,8,16,32,64,256")
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--call", type=int, default=0, help="steps per enqueue_steps call (0: one call per round); must divide --steps")
     a = ap.parse_args()
+    call = a.call or a.steps
+    assert a.steps % call == 0, "--call must divide --steps"
     for name in a.case or ["C2", "dp04"]:
         prm = config.params_from_values(**CASES[name])
         for M in [int(x) for x in a.members.split(",")]:
@@ -63,17 +70,17 @@ def main():
                     capi.Batch([prm] * M, nf, nt, [s["pos"] for s in states], [s["vel"] for s in states],
                                [s["drho_dt"] for s in states], states[0]["mass"], states[0]["wall_vel"], t_end=1e9) as b:
                 for _ in range(2):  # alternate, so that drifts of the clock or of the box hit both
-                    rounds(ctx, a.steps, (a.reps + 1) // 2, single)
-                    rounds(b, a.steps, (a.reps + 1) // 2, batch)
+                    rounds(ctx, a.steps, (a.reps + 1) // 2, single, call)
+                    rounds(b, a.steps, (a.reps + 1) // 2, batch, call)
                 info, gs = b.info(), b.graph_stats()
             work = nt * a.steps
             r1 = [work / s for s in single]
             rM = [M * work / s for s in batch]
-            print(json.dumps(dict(case=name, n_total=nt, members=M, steps=a.steps, lanes=info["lanes_per_particle"],
+            print(json.dumps(dict(case=name, n_total=nt, members=M, steps=a.steps, call=call, lanes=info["lanes_per_particle"],
                                   rebuild_every=info["rebuild_every"], realignments=info["realignments"],
                                   forced_rebuilds=info["forced_rebuilds"], slots_eager=gs["slots_eager"],
-                                  single_us_per_step=[round(1e6 * s / a.steps, 2) for s in single],
-                                  batch_us_per_step=[round(1e6 * s / a.steps, 2) for s in batch],
+                                  single_us_per_step=[round(1e6 * s / a.steps, 3) for s in single],
+                                  batch_us_per_step=[round(1e6 * s / a.steps, 3) for s in batch],
                                   single_rate=statistics.median(r1), batch_rate=statistics.median(rM),
                                   batch_rate_min=min(rM), batch_rate_max=max(rM),
                                   ratio=statistics.median(rM) / statistics.median(r1))), flush=True)
