@@ -16,6 +16,9 @@ HEADERS = ["sphx_common.hpp", "sphx_device.hpp", "sphx_kernels.hpp", "sphx_flow_
 LIB = os.path.join(CSRC, "libsphx.so")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
+# sphx_resident.hip: the leading scalar / pointer parameters of a kernel, up to 14 dwords, arrive in registers with the wave
+# (csrc/sphx_kernels.hpp, "Leading arguments"); the option counts parameters and stops at the first struct passed by value
+SOURCE_FLAGS = {"sphx_resident.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"]}
 
 
 def _hipcc() -> str:
@@ -39,8 +42,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     objs = []
     for src in srcs:
         obj = src[:-4] + ".o"
-        if force or _stale(obj, [src] + hdrs):
-            cmd = [hipcc] + FLAGS + ["-c", src, "-o", obj]
+        if force or _stale(obj, [src, os.path.abspath(__file__)] + hdrs):
+            cmd = [hipcc] + FLAGS + SOURCE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd))
             subprocess.check_call(cmd)

@@ -624,21 +624,35 @@ __device__ __forceinline__ void list_push_w(const LaneGroup<LPP> &lg, int *idx, 
 
 // Compact kernels at 16 and 32 lanes per particle (kRowsAhead): a pass is a chain of dependent memory round trips behind a launch,
 // so what it asks for has to leave in as few request waves as there are true dependences:
-//   wave 1 (behind the arguments): the clock's words, the particle's own records, the row count and the first rows of the list;
+//   wave 1: the clock's words, the row count and the first rows of the list (ListHead: addressed from leading arguments, no
+//           scalar wait in front), the particle's own records (behind the one scalar batch, SPHX_ARGS_BATCH);
 //   wave 2 (behind the rows): the neighbour records of ALL of those rows, before the first one is used.
 // Left alone, the compiler sinks a load into the branch that uses its value -- the rows behind the count, row 1's records
 // behind row 0's arithmetic -- and every sunk load is one more round trip on the critical path.  requests_issued() closes a
 // wave: loads cannot move across it (to the compiler it may write memory), and it costs no instruction and no wait.
 // A lane that does not own a prefetched row asks for its own particle's records instead: rows beyond a lane's count hold
 // stale words, and no address is ever formed from one.  The arithmetic stays in row order, so every sum keeps its bits.
-// The arguments come first: a pass reads 25-40 of the ~220 dwords of its kernels' argument segment, and the compiler loads each
-// where it is first used -- six to twelve scalar round trips, one behind the other, before wave 1 has left.  Every pass
-// therefore opens with SPHX_WAVE1_ARGS(...), an empty asm statement that takes as scalar operands the arguments wave 1 forms
-// its addresses from: their loads leave together and one wait covers them.  The rest is loaded as before, further down.
+// The arguments: a pass reads 25-40 of the ~220 dwords of its kernels' argument segment, and the compiler loads each where it is
+// first used -- six to twelve scalar round trips, one behind the other.  An empty asm statement that takes arguments as scalar
+// operands makes their loads leave together, with one wait (SPHX_ARGS_BATCH below, "Leading arguments").
 template <int LPP>
 constexpr bool kRowsAhead = LPP >= 16;
 __device__ __forceinline__ void requests_issued() { asm volatile("" ::: "memory"); }
-#define SPHX_WAVE1_ARGS(...) asm volatile("" ::__VA_ARGS__)
+// Leading arguments.  The single-channel forms of these kernels take what wave 1 forms its first addresses from -- the clock,
+// the number of workgroups of the pass, the row counts, the list and its stride, and as many own-record pointers as fit -- as
+// plain parameters IN FRONT of the structs: built with -amdgpu-kernarg-preload-count the first 14 dwords of the argument
+// segment arrive in scalar registers together with the wave (the preload stops at the first struct passed by value), so the
+// list loads leave without a scalar round trip in front of them.  The kernel writes the values over the fields of its own
+// copies of FluidSet / FluidTmp before it calls the body: the body cannot read the struct's copy of a hot value, and the
+// host takes each from the very view it passes by value (hot_* in sphx_resident.hip).  Everything else a pass reads of its
+// arguments is named by ONE SPHX_ARGS_BATCH(...) behind the list loads: those scalar loads leave together at the top of the
+// kernel and are in flight while wave 1 is; the own records that missed the preload go out when they land.
+// `shape` = the workgroups of the pass (the tail workgroup not counted) and the pass's small flag in one dword.
+constexpr int kShapeBits = 24;
+__host__ __device__ inline int pass_shape(int nblk, int flag) { return (int)(((unsigned)flag << kShapeBits) | (unsigned)nblk); }
+__device__ __forceinline__ int shape_blocks(int shape) { return shape & ((1 << kShapeBits) - 1); }
+__device__ __forceinline__ int shape_flag(int shape) { return shape >> kShapeBits; }  // (signed: -1 comes back as -1)
+#define SPHX_ARGS_BATCH(...) asm volatile("" ::__VA_ARGS__)
 // The first rows of a lane's list column, requested together with the row count (at 32 lanes per particle a lane rarely owns
 // more than two): count -> entry -> neighbour data becomes {count, entries} -> neighbour data.
 // (rows 2 and 3 only where lanes own that many: few lanes per particle)
@@ -650,9 +664,26 @@ struct FirstRows {
           e3(LPP <= 8 ? idx[3 * (size_t)stride + tid] : 0)
     {
     }
+    __device__ __forceinline__ FirstRows(int e0, int e1) : e0(e0), e1(e1), e2(0), e3(0) {}  // (requested already: ListHead)
     __device__ __forceinline__ int row(int m, const int *idx, int stride, int tid) const  // entry of row m of the column
     {
         return m == 0 ? e0 : (m == 1 ? e1 : (LPP <= 8 && m == 2 ? e2 : (LPP <= 8 && m == 3 ? e3 : idx[(size_t)m * stride + tid])));
+    }
+};
+
+// The part of wave 1 whose addresses come from leading arguments alone: the lane's packed row count, its first two rows and
+// the clock's words.  Requested in front of SPHX_ARGS_BATCH, so nothing scalar stands between the launch and these loads.
+// (Passes B, CD and A read the clock through a pointer to const with scalar loads: they name run, n and dt in their batch, so
+//  that the clock's words leave with it and not behind the own records.)
+struct ListHead {
+    int packed = 0, e0 = 0, e1 = 0, run = 0, n = 0;
+    double dt = 0.0;
+    __device__ __forceinline__ void request(const Clock *clk, int q, const int *cnt, const int *idx, int stride, int tid)
+    {
+        run = clk->run[q]; n = clk->n; dt = clk->dt;
+        packed = cnt[tid];
+        e0 = idx[tid];
+        e1 = idx[(size_t)stride + tid];
     }
 };
 
@@ -691,10 +722,25 @@ template <int LPP, int MODE>
 __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                              const FluidTmp &t, const Walls &w, int bid, int nblk, bool half)
 {
-    if (MODE == 2 && kRowsAhead<LPP>)
-        SPHX_WAVE1_ARGS("s"(clk), "s"(q), "s"(s.pos), "s"(s.cell), "s"(s.mass), "s"(s.drho), "s"(t.cap), "s"(t.sl_cnt), "s"(t.sl_idx),
-                        "s"(t.nl_stride));
     SPHX_PASS_INDEX_AT(bid, nblk);
+    // the walk at 16 / 32 lanes: row count, first rows and the clock's words leave first (leading arguments, see ListHead)
+    constexpr bool kHot = MODE == 2 && kRowsAhead<LPP>;
+    constexpr int kAhead = kHot ? 64 / LPP : 2;
+    int ns = 0, e_row0 = 0, e_row1 = 0, e_row2 = 0, e_row3 = 0, run_h = 0, n_h = 0;
+    double dt_h = 0.0;
+    if (kHot) {
+        dt_h = clk->dt; run_h = clk->run[q]; n_h = clk->n;
+        ns = list_rows(t.sl_cnt[tid]);
+        e_row0 = t.sl_idx[tid];
+        e_row1 = t.sl_idx[(size_t)t.nl_stride + tid];
+        if (kAhead > 2) {
+            e_row2 = t.sl_idx[2 * (size_t)t.nl_stride + tid];
+            e_row3 = t.sl_idx[3 * (size_t)t.nl_stride + tid];
+        }
+        SPHX_ARGS_BATCH("s"(s.pos), "s"(s.mass), "s"(s.drho), "s"(t.cap), "s"(t.nl_cnt), "s"(t.nl_idx), "s"(t.nl_cap), "s"(t.a),
+                        "s"(t.vol), "s"(w.pos), "s"(w.a), "s"(g.DL), "s"(g.half_DL), "s"(ph.kc.rcut2), "s"(ph.kc.inv_h),
+                        "s"(ph.kc.sigma), "s"(ph.w0), "s"(ph.rho0), "s"(ph.inv_sigma0), "s"(run_h), "s"(n_h), "s"(dt_h));
+    }
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
     const int ci = in_cap ? s.cell[i] : 0;
     const bool lead = in_cap && sub == 0;  // the lane that finishes the particle
@@ -703,20 +749,14 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
     // at 32 lanes per particle): count -> entry -> position becomes {count, entries} -> position
     // (kRowsAhead: the first kAhead rows -- 64 candidates; the superset list holds about 48 of them at skin 1.05 h, so three
     //  rows for every lane at 16 lanes per particle and a fourth for some -- and the clock's words in the same wave)
-    constexpr int kAhead = (MODE == 2 && kRowsAhead<LPP>) ? 64 / LPP : 2;
-    int ns = 0, e_row0 = 0, e_row1 = 0, e_row2 = 0, e_row3 = 0;
-    if (MODE == 2) {
+    if (MODE == 2 && !kHot) {
         ns = list_rows(t.sl_cnt[tid]);
         e_row0 = t.sl_idx[tid];
         e_row1 = t.sl_idx[(size_t)t.nl_stride + tid];
-        if (kAhead > 2) {
-            e_row2 = t.sl_idx[2 * (size_t)t.nl_stride + tid];
-            e_row3 = t.sl_idx[3 * (size_t)t.nl_stride + tid];
-        }
     }
-    const double dt = clk->dt;
-    const int run_q = clk->run[q], n_now = clk->n;
-    if (MODE == 2 && kRowsAhead<LPP>) requests_issued();
+    const double dt = kHot ? dt_h : clk->dt;
+    const int run_q = kHot ? run_h : clk->run[q], n_now = kHot ? n_h : clk->n;
+    if (kHot) requests_issued();
     if (!run_q) return;
     const bool active = i < n_now;
     double s_in = 0.0, s_ct = 0.0;
@@ -888,19 +928,28 @@ __device__ __forceinline__ bool slab_part_skips(const Grid &g, const FluidSet &s
 // body deciding per candidate at run time 795 us.
 template <int LPP, int MODE>
 __device__ __forceinline__ void density_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
-                                             const FluidTmp &t, const Walls &w, int cond_fresh)
+                                             const FluidTmp &t, const Walls &w, int cond_fresh, int nblk)
 {
     const int part = cond_fresh >= 0 ? cond_fresh >> kPassPartShift : 0;
     if (part) cond_fresh &= (1 << kPassPartShift) - 1;
     if (cond_fresh >= 0 && (clk->fresh != 0) != (cond_fresh != 0)) return;
-    if (MODE == 2 && part && slab_part_skips<LPP>(g, s, xcd_block((int)blockIdx.x, (int)gridDim.x), part)) return;
-    density_body<LPP, MODE>(clk, q, g, ph, s, t, w, (int)blockIdx.x, (int)gridDim.x, true);
+    if (MODE == 2 && part && slab_part_skips<LPP>(g, s, xcd_block((int)blockIdx.x, nblk), part)) return;
+    density_body<LPP, MODE>(clk, q, g, ph, s, t, w, (int)blockIdx.x, nblk, true);
 }
 template <int LPP, int MODE>
 __global__ __launch_bounds__(kBlock) void k_density(const Clock *clk, int q, Grid g, Phys ph,
                                                     FluidSet s, FluidTmp t, Walls w, int cond_fresh)
 {
-    density_pass<LPP, MODE>(clk, q, g, ph, s, t, w, cond_fresh);
+    density_pass<LPP, MODE>(clk, q, g, ph, s, t, w, cond_fresh, (int)gridDim.x);
+}
+// The walk at 16 / 32 lanes per particle with leading arguments (shape: cond_fresh)
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_density_walk(const Clock *clk, int q, int shape, int *sl_cnt, int *sl_idx, int nl_stride,
+                                                         int cap, double2 *pos, double *mass, Grid g, Phys ph, FluidSet s,
+                                                         FluidTmp t, Walls w)
+{
+    t.sl_cnt = sl_cnt; t.sl_idx = sl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; s.mass = mass;
+    density_pass<LPP, 2>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
 }
 // Contexts whose re-binning step is folded into passes CD and E (k_forces_hist, k_continuity_rebin): nobody counts the cell
 // histogram back down there (k_scatter's atomicSub did), and the tail workgroup of pass E advances the clock while the other
@@ -911,7 +960,7 @@ __global__ __launch_bounds__(kBlock) void k_density_zero(const Clock *clk, int q
                                                          FluidSet s, FluidTmp t, Walls w, int cond_fresh)
 {
     for (int k = (int)(blockIdx.x * kBlock + threadIdx.x); k < g.ncells; k += (int)(gridDim.x * kBlock)) t.count[k] = 0;
-    density_pass<LPP, 1>(clk, q, g, ph, s, t, w, cond_fresh);
+    density_pass<LPP, 1>(clk, q, g, ph, s, t, w, cond_fresh, (int)gridDim.x);
 }
 // (the "_b" wrappers take the run-time arguments of their single-channel kernels as run-time arguments too: a constant there
 //  would let the compiler merge the bodies' blocks differently, and its fused multiply-adds -- so the last bits -- with them)
@@ -920,7 +969,7 @@ __global__ __launch_bounds__(kBlock) void k_density_b(Members mb, int q, Grid g,
 {
     const int m = (int)blockIdx.y;
     const Phys ph = mb.ph[m];
-    density_pass<LPP, MODE>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, cond_fresh);
+    density_pass<LPP, MODE>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, cond_fresh, (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -931,20 +980,24 @@ __global__ __launch_bounds__(kBlock) void k_density_b(Members mb, int q, Grid g,
 // finish_half: pass A of this step ran inside the previous step's fused launch and left {p_half, rho_half} open
 template <int LPP>
 __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
-                                         const FluidTmp &t, const Walls &w, int finish_half)
+                                         const FluidTmp &t, const Walls &w, int finish_half, int nblk)
 {
-    if (kRowsAhead<LPP>)
-        SPHX_WAVE1_ARGS("s"(clk), "s"(q), "s"(s.pos), "s"(s.drho), "s"(t.a), "s"(t.cap), "s"(t.nl_cnt), "s"(t.nl_idx), "s"(t.nl_stride),
-                        "s"(finish_half), "s"((int)gridDim.x));
-    SPHX_PASS_INDEX();
+    SPHX_PASS_INDEX_AT((int)blockIdx.x, nblk);
+    ListHead head;
+    if (kRowsAhead<LPP>) {
+        head.request(clk, q, t.nl_cnt, t.nl_idx, t.nl_stride, tid);
+        SPHX_ARGS_BATCH("s"(s.pos), "s"(s.drho), "s"(t.a), "s"(t.B), "s"(t.cap), "s"(t.vol), "s"(w.pos), "s"(w.a), "s"(g.DL),
+                        "s"(g.half_DL), "s"(ph.kc.h), "s"(ph.kc.inv_h), "s"(ph.kc.sigma_over_h), "s"(ph.rho0), "s"(ph.p0), "s"(head.run),
+                        "s"(head.n), "s"(head.dt));
+    }
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
     const bool closes = finish_half && in_cap && sub == 0;
     const double4 a_own = closes ? t.a[i] : make_double4(0.0, 0.0, 0.0, 0.0);
     const double drho_own = closes ? s.drho[i] : 0.0;
-    const int nn_all = list_rows(t.nl_cnt[tid]);
-    const FirstRows<LPP> first(t.nl_idx, t.nl_stride, tid);
-    const double dt = clk->dt;
-    const int run_q = clk->run[q], n_now = clk->n;
+    const int nn_all = list_rows(kRowsAhead<LPP> ? head.packed : t.nl_cnt[tid]);
+    const FirstRows<LPP> first = kRowsAhead<LPP> ? FirstRows<LPP>(head.e0, head.e1) : FirstRows<LPP>(t.nl_idx, t.nl_stride, tid);
+    const double dt = kRowsAhead<LPP> ? head.dt : clk->dt;
+    const int run_q = kRowsAhead<LPP> ? head.run : clk->run[q], n_now = kRowsAhead<LPP> ? head.n : clk->n;
     if (kRowsAhead<LPP>) requests_issued();
     if (!run_q) return;
     const bool active = i < n_now;
@@ -992,17 +1045,18 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
     }
 }
 template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_kgc(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
-                                                FluidTmp t, Walls w, int finish_half)
+__global__ __launch_bounds__(kBlock) void k_kgc(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride, int cap,
+                                                double2 *pos, double4 *a, Grid g, Phys ph, FluidSet s, FluidTmp t, Walls w)
 {
-    kgc_pass<LPP>(clk, q, g, ph, s, t, w, finish_half);
+    t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; t.a = a;  // shape: finish_half
+    kgc_pass<LPP>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
 }
 template <int LPP>
 __global__ __launch_bounds__(kBlock) void k_kgc_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w, int finish_half)
 {
     const int m = (int)blockIdx.y;
     const Phys ph = mb.ph[m];
-    kgc_pass<LPP>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, finish_half);
+    kgc_pass<LPP>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, finish_half, (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1022,26 +1076,30 @@ __global__ __launch_bounds__(kBlock) void k_kgc_b(Members mb, int q, Grid g, Flu
 // only that far (rebin_near), and its tail workgroup turns the flag into SPHX_ERR_GRID.
 template <int LPP, bool HIST = false>
 __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
-                                            const FluidTmp &t, const Walls &w, int later)
+                                            const FluidTmp &t, const Walls &w, int later, int nblk)
 {
-    if (kRowsAhead<LPP>)
-        SPHX_WAVE1_ARGS("s"(clk), "s"(q), "s"(s.pos), "s"(s.vel), "s"(t.a), "s"(t.B), "s"(s.mass), "s"(t.cap), "s"(t.nl_cnt),
-                        "s"(t.nl_idx), "s"(t.nl_stride), "s"(s.posb), "s"(later), "s"((int)gridDim.x));
-    SPHX_PASS_INDEX();
+    SPHX_PASS_INDEX_AT((int)blockIdx.x, nblk);
+    ListHead head;
+    if (kRowsAhead<LPP>) {
+        head.request(clk, q, t.nl_cnt, t.nl_idx, t.nl_stride, tid);
+        SPHX_ARGS_BATCH("s"(s.pos), "s"(s.vel), "s"(t.a), "s"(t.B), "s"(s.mass), "s"(t.cap), "s"(s.posb), "s"(t.fp), "s"(t.posn),
+                        "s"(w.pos), "s"(w.a), "s"(g.DL), "s"(g.half_DL), "s"(ph.kc.h), "s"(ph.kc.inv_h), "s"(ph.kc.sigma_over_h),
+                        "s"(ph.mu), "s"(ph.c_f), "s"(ph.g), "s"(ph.tc), "s"(ph.DL), "s"(head.run), "s"(head.n), "s"(head.dt));
+    }
     const int c_binned = (HIST && in_cap && sub == 0) ? s.cell[i] : 0;
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
     const double2 vi = in_cap ? s.vel[i] : make_double2(0.0, 0.0);
     const double4 ai = in_cap ? t.a[i] : make_double4(1.0, 0.0, 0.0, 0.0);
     const double4 Bi = in_cap ? t.B[i] : make_double4(1.0, 0.0, 0.0, 1.0);
     const double mi = in_cap ? s.mass[i] : 1.0;
-    const int nn_all = list_rows(t.nl_cnt[tid]);
-    const FirstRows<LPP> first(t.nl_idx, t.nl_stride, tid);
+    const int nn_all = list_rows(kRowsAhead<LPP> ? head.packed : t.nl_cnt[tid]);
+    const FirstRows<LPP> first = kRowsAhead<LPP> ? FirstRows<LPP>(head.e0, head.e1) : FirstRows<LPP>(t.nl_idx, t.nl_stride, tid);
     const bool tracked = s.posb != nullptr;
     const double2 pb = (tracked && in_cap && sub == 0) ? s.posb[i] : make_double2(0.0, 0.0);
     const double2 fp_own = (later && in_cap) ? t.fp[i] : make_double2(0.0, 0.0);
     const double2 p_now = (later && in_cap && sub == 0) ? t.posn[i] : make_double2(0.0, 0.0);
-    const double dt = clk->dt;
-    const int run_q = clk->run[q], n_now = clk->n;
+    const double dt = kRowsAhead<LPP> ? head.dt : clk->dt;
+    const int run_q = kRowsAhead<LPP> ? head.run : clk->run[q], n_now = kRowsAhead<LPP> ? head.n : clk->n;
     if (kRowsAhead<LPP>) requests_issued();
     if (!run_q) return;
     const bool active = i < n_now;
@@ -1206,23 +1264,26 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     }
 }
 template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_forces(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
-                                                   FluidTmp t, Walls w, int later)
+__global__ __launch_bounds__(kBlock) void k_forces(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride, int cap,
+                                                   double2 *pos, double2 *vel, Grid g, Phys ph, FluidSet s, FluidTmp t, Walls w)
 {
-    forces_pass<LPP>(clk, q, g, ph, s, t, w, later);
+    t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; s.vel = vel;  // shape: later
+    forces_pass<LPP>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
 }
 template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_forces_hist(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
-                                                        FluidTmp t, Walls w, int later)
+__global__ __launch_bounds__(kBlock) void k_forces_hist(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride,
+                                                        int cap, double2 *pos, double2 *vel, Grid g, Phys ph, FluidSet s, FluidTmp t,
+                                                        Walls w)
 {
-    forces_pass<LPP, true>(clk, q, g, ph, s, t, w, later);
+    t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; s.vel = vel;
+    forces_pass<LPP, true>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
 }
 template <int LPP>
 __global__ __launch_bounds__(kBlock) void k_forces_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w, int later)
 {
     const int m = (int)blockIdx.y;
     const Phys ph = mb.ph[m];
-    forces_pass<LPP>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, later);
+    forces_pass<LPP>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, later, (int)gridDim.x);
 }
 
 // =================================================================================================
@@ -2439,8 +2500,6 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
 {
     static_assert(!CODED || (WALK && TILE == kSlotCodes), "slot-coded lists: this pass stages the whole layout");
     static_assert(!REBIN || (!WALK && TILE == 0 && LPP >= 16), "the folded re-binning belongs to the compact kernels");
-    if (!WALK && kRowsAhead<LPP>)
-        SPHX_WAVE1_ARGS("s"(clk), "s"(q), "s"(s.pos), "s"(t.veln), "s"(t.a), "s"(t.cap), "s"(t.nl_cnt), "s"(t.nl_idx), "s"(t.nl_stride));
     const int blk = xcd_block(bid, nb);
     const int tid = blk * kBlock + threadIdx.x;
     const int i = tid / LPP, sub = tid % LPP;
@@ -2455,15 +2514,20 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
     // kRowsAhead: this pass reads the clock through a pointer somebody writes (the tail workgroup), so with vector loads, which
     // come back in order -- the words the pass waits for first are asked for first, in one go
     constexpr bool kAhead = !WALK && kRowsAhead<LPP>;
-    int run_first = 0, n_first = 0;
-    double dt_first = 0.0;
-    if (kAhead) { run_first = clk->run[q]; n_first = clk->n; dt_first = clk->dt; }
+    ListHead head;
+    if (kAhead) {
+        head.request(clk, q, t.nl_cnt, t.nl_idx, t.nl_stride, tid);
+        SPHX_ARGS_BATCH("s"(s.pos), "s"(t.veln), "s"(t.a), "s"(t.cap), "s"(t.posn), "s"(t.vol), "s"(t.vpart), "s"(w.pos), "s"(w.a),
+                        "s"(g.DL), "s"(g.half_DL), "s"(g.own_by_cell), "s"(ph.kc.h), "s"(ph.kc.inv_h), "s"(ph.kc.sigma_over_h));
+    }
+    const int run_first = head.run, n_first = head.n;
+    const double dt_first = head.dt;
     const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
     const double2 vi = in_cap ? t.veln[i] : make_double2(0.0, 0.0);
-    const int packed = t.nl_cnt[tid];
+    const int packed = kAhead ? head.packed : t.nl_cnt[tid];
     const int nn_all = list_rows(packed);
     // (WALK: the first two words of the packed fluid rows, see FluidTmp::nl_pk)
-    const FirstRows<LPP> first(WALK ? t.nl_pk : t.nl_idx, t.nl_stride, tid);
+    const FirstRows<LPP> first = kAhead ? FirstRows<LPP>(head.e0, head.e1) : FirstRows<LPP>(WALK ? t.nl_pk : t.nl_idx, t.nl_stride, tid);
     const bool lead = in_cap && sub == 0;
     const double4 a_own = lead ? t.a[i] : make_double4(0.0, 0.0, 0.0, 0.0);
     const double rhoh_i = a_own.z;
@@ -2651,13 +2715,31 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WALK ? 8
     continuity_body<LPP, WALK, TILE, CODED>(clk, q, g, ph, s, t, w, do_hist, tail, (int)blockIdx.x, nb, c_pos, c_vel, c_vol, next_half);
 }
 
+// Pass E of the compact kernels at 16 / 32 lanes per particle with leading arguments (shape: the workgroups of the pass, tail)
+template <int LPP>
+__global__ __launch_bounds__(kBlock) void k_continuity_compact(Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride,
+                                                               int cap, double2 *pos, double2 *veln, Grid g, Phys ph, FluidSet s,
+                                                               FluidTmp t, Walls w, int do_hist, int next_half)
+{
+    t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; t.veln = veln;
+    const int nb = shape_blocks(shape), tail = shape_flag(shape);
+    if (tail && (int)blockIdx.x == nb) {
+        if (tail == 2) slab_seal_tail(clk, q, t, nb);
+        else continuity_tail(clk, q, ph, t, nb);
+        return;
+    }
+    continuity_body<LPP, false, 0>(clk, q, g, ph, s, t, w, do_hist, tail, (int)blockIdx.x, nb, nullptr, nullptr, nullptr, next_half);
+}
+
 // Small channels, the step that re-bins: pass E with the re-binning folded in (continuity_body, REBIN) and the clock in the tail
 // workgroup, which advances it as k_clock_scan does on such a step.  d: the state / layout the new ordering goes to.
 template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_continuity_rebin(Clock *clk, int q, Grid g, Phys ph, FluidSet s, FluidTmp t, Walls w,
-                                                             FluidSet d)
+__global__ __launch_bounds__(kBlock) void k_continuity_rebin(Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride,
+                                                             int cap, double2 *pos, double2 *veln, Grid g, Phys ph, FluidSet s,
+                                                             FluidTmp t, Walls w, FluidSet d)
 {
-    const int nb = (int)gridDim.x - 1;
+    t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; t.veln = veln;
+    const int nb = shape_blocks(shape);
     if ((int)blockIdx.x == nb) {
         continuity_tail(clk, q, ph, t, nb, 1);
         return;
@@ -2673,10 +2755,15 @@ __global__ __launch_bounds__(kBlock) void k_continuity_rebin(Clock *clk, int q, 
 // half-step density and pressure, which need the next step's dt (the tail workgroup of this very launch computes it):
 // pass B of the next step closes that (k_kgc, finish_half); workgroup 2 nb: the clock (continuity_tail).
 template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_continuity_density(Clock *clk, int q, Grid g, Phys ph, FluidSet s, FluidTmp t,
-                                                               Walls w, FluidSet s_next, FluidTmp t_next, int with_tail)
+__global__ __launch_bounds__(kBlock) void k_continuity_density(Clock *clk, int q, int shape, int *e_cnt, int *e_idx, int *a_cnt,
+                                                               int *a_idx, int e_stride, int a_stride, Grid g, Phys ph, FluidSet s,
+                                                               FluidTmp t, Walls w, FluidSet s_next, FluidTmp t_next)
 {
-    const int nb = ((int)gridDim.x - with_tail) / 2;  // (with_tail = 0: kernel timing, the clock must not advance)
+    // (fourteen dwords hold the lists of both halves and nothing else: the own records of either go out behind the scalar batch;
+    //  the two strides side by side: an int in front of a pointer costs a dword of padding, and the last one would miss the preload)
+    t.nl_cnt = e_cnt; t.nl_idx = e_idx; t.nl_stride = e_stride;
+    t_next.sl_cnt = a_cnt; t_next.sl_idx = a_idx; t_next.nl_stride = a_stride;
+    const int nb = shape_blocks(shape), with_tail = shape_flag(shape);  // (with_tail = 0: kernel timing, the clock must not advance)
     const int b = (int)blockIdx.x;
     if (with_tail && b == 2 * nb) {
         continuity_tail(clk, q, ph, t, nb);

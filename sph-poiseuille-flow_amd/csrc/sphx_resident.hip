@@ -504,6 +504,10 @@ template <typename T, bool MustBeZero>
 struct NotInBatch { T v; };
 template <typename T> NotInBatch<T, false> per_member(T v) { return {v}; }
 template <typename T> NotInBatch<T, true> single_only(T v) { return {v}; }
+// ... and one only the batch form takes (the single form has it among its leading arguments, see hot_list)
+template <typename T>
+struct OnlyInBatch { T v; };
+template <typename T> OnlyInBatch<T> batch_only(T v) { return {v}; }
 
 [[noreturn]] void no_batch_form(const char *name)
 {
@@ -514,7 +518,9 @@ void single_form_only(const sphx_ctx *c, const char *name) { if (c->members) no_
 
 template <typename T> std::tuple<T> single_arg(const T &x) { return std::tuple<T>(x); }
 template <typename T, bool Z> std::tuple<T> single_arg(NotInBatch<T, Z> x) { return std::tuple<T>(x.v); }
+template <typename T> std::tuple<> single_arg(OnlyInBatch<T>) { return {}; }
 template <typename T> std::tuple<T> batch_arg(const char *, const T &x) { return std::tuple<T>(x); }
+template <typename T> std::tuple<T> batch_arg(const char *, OnlyInBatch<T> x) { return std::tuple<T>(x.v); }
 template <typename T, bool Z> std::tuple<> batch_arg(const char *name, NotInBatch<T, Z> x)
 {
     if constexpr (Z) { if (!(x.v == T{})) no_batch_form(name); }
@@ -548,6 +554,32 @@ void launch_pass(sphx_ctx *c, const char *name, K kernel, unsigned blocks, int q
     launch_pass(c, name, Forms{kernel}, blocks, q, s, t, extra...);
 }
 
+// The compact kernels at 16 / 32 lanes per particle take a block of leading arguments in front of (grid, phys, S, ...): at most
+// fourteen dwords with the clock and q, delivered in registers with the wave (sphx_kernels.hpp, "Leading arguments").  Each
+// kernel writes them over the fields of the structs it gets by value, so every value is taken HERE, from the very views the
+// same launch passes -- s, t for a pass of the step, sn, tn for the A half of the fused launch.  A batch form has none of
+// them: it derives its views from the Members table.
+// shape (workgroups of the pass without its tail, the pass's flag), row counts, list, stride, capacity
+auto hot_list(unsigned nblk, int flag, const FluidTmp &t) { return std::make_tuple(pass_shape((int)nblk, flag), t.nl_cnt, t.nl_idx, t.nl_stride, t.cap); }
+auto hot_kgc(unsigned nblk, int flag, const FluidSet &s, const FluidTmp &t) { return std::tuple_cat(hot_list(nblk, flag, t), std::make_tuple(s.pos, t.a)); }
+auto hot_forces(unsigned nblk, int flag, const FluidSet &s, const FluidTmp &t) { return std::tuple_cat(hot_list(nblk, flag, t), std::make_tuple(s.pos, s.vel)); }
+auto hot_continuity(unsigned nblk, int flag, const FluidSet &s, const FluidTmp &t) { return std::tuple_cat(hot_list(nblk, flag, t), std::make_tuple(s.pos, t.veln)); }
+auto hot_walk(unsigned nblk, int flag, const FluidSet &s, const FluidTmp &t)  // (the superset list)
+{
+    return std::make_tuple(pass_shape((int)nblk, flag), t.sl_cnt, t.sl_idx, t.nl_stride, t.cap, s.pos, s.mass);
+}
+auto hot_fused(unsigned nblk, int flag, const FluidTmp &t, const FluidTmp &tn)  // (pass E's list, the superset list of pass A's side)
+{
+    return std::make_tuple(pass_shape((int)nblk, flag), t.nl_cnt, t.nl_idx, tn.sl_cnt, tn.sl_idx, t.nl_stride, tn.nl_stride);
+}
+template <typename K, typename KB, typename... H, typename... X>
+void launch_pass_hot(sphx_ctx *c, const char *name, Forms<K, KB> k, unsigned blocks, int q, const std::tuple<H...> &hot, const FluidSet &s,
+                     const FluidTmp &t, X... extra)
+{
+    std::apply([&](auto... h) { launch_forms(c, name, k, blocks, kBlock, 0, q, per_member(h)..., c->grid, per_member(c->phys), s, t, c->walls, extra...); },
+               hot);
+}
+
 // 16 / 32 lanes per particle (small channels) run the compact kernels (32-bit lists); fewer lanes (large channels) the "_w"
 // forms, see sphx_kernels.hpp -- fluid list entries are 16-bit index differences, so builders and walkers always go together.
 // LDS tiles: the force pass always; KGC and continuity where measured to pay (lds_tiles_be)
@@ -566,7 +598,9 @@ void launch_pass_a(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Pas
             if (mode == PassA::Sweep) launch_pass(c, sweep_name, Forms{k_density<LPP, 0>, k_density_b<LPP, 0>}, np, q, s, t, cond_sweep);
             else if (mode == PassA::SweepBuild && c->fold_rebin) launch_pass(c, sweep_name, k_density_zero<LPP>, np, q, s, t, cond_sweep);
             else if (sweeps) launch_pass(c, sweep_name, Forms{k_density<LPP, 1>, k_density_b<LPP, 1>}, np, q, s, t, cond_sweep);
-            if (walks) launch_pass(c, "k_density_walk", Forms{k_density<LPP, 2>, k_density_b<LPP, 2>}, np, q, s, t, cond_walk);
+            if (walks)
+                launch_pass_hot(c, "k_density_walk", Forms{k_density_walk<LPP>, k_density_b<LPP, 2>}, np, q, hot_walk(np, cond_walk, s, t), s, t,
+                                batch_only(cond_walk));
         } else {
             // the cell sweep: mode 0 writes the step's list, mode 1 the superset list as well
             // the build variant of a dynamic context is idle on four steps out of five: a grid-stride launch of an eighth
@@ -593,7 +627,7 @@ void launch_pass_b(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t)
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16)
-            launch_pass(c, "k_kgc", Forms{k_kgc<LPP>, k_kgc_b<LPP>}, np, q, s, t, finish_half);
+            launch_pass_hot(c, "k_kgc", Forms{k_kgc<LPP>, k_kgc_b<LPP>}, np, q, hot_kgc(np, finish_half, s, t), s, t, batch_only(finish_half));
         else
             with_form<LPP, kSlotCodes, tile_slots(LPP)>(c, c->lds_tiles_be, [&](auto tile, auto coded) {
                 launch_pass(c, "k_kgc", k_kgc_w<LPP, decltype(tile)::value, decltype(coded)::value>, np, q, s, t, finish_half);
@@ -607,7 +641,8 @@ void launch_pass_cd(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Ra
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16) {
-            launch_pass(c, rate == Rate::Inner ? "k_forces_inner" : "k_forces", Forms{k_forces<LPP>, k_forces_b<LPP>}, np, q, s, t, (int)rate);
+            launch_pass_hot(c, rate == Rate::Inner ? "k_forces_inner" : "k_forces", Forms{k_forces<LPP>, k_forces_b<LPP>}, np, q,
+                            hot_forces(np, (int)rate, s, t), s, t, batch_only((int)rate));
         } else {
             auto forces = [&](auto tile, auto coded) {
                 launch_pass(c, "k_forces", k_forces_w<LPP, decltype(tile)::value, decltype(coded)::value>, np, q, s, t);
@@ -629,8 +664,8 @@ void launch_pass_e(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Tai
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16)
-            launch_pass(c, name, Forms{k_continuity<LPP, false, 0>, k_continuity_b<LPP>}, ne, q, s, t, (int)hist, (int)tail,
-                        single_only((int)rate));
+            launch_pass_hot(c, name, Forms{k_continuity_compact<LPP>, k_continuity_b<LPP>}, ne, q,
+                            hot_continuity(c->n_blocks_particles, (int)tail, s, t), s, t, (int)hist, batch_only((int)tail), single_only((int)rate));
         else
             with_form<LPP, kSlotCodes, tile_slots(LPP)>(c, c->lds_tiles_be, [&](auto tile, auto coded) {
                 launch_pass(c, name, k_continuity<LPP, true, decltype(tile)::value, decltype(coded)::value>, ne, q, s, t, (int)hist, (int)tail, 0);
@@ -730,8 +765,9 @@ void launch_fold_rebin(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t,
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16) {
-            launch_pass(c, "k_forces_hist", k_forces_hist<LPP>, c->n_blocks_particles, q, s, t, 0);
-            launch_pass(c, "k_continuity_rebin", k_continuity_rebin<LPP>, c->n_blocks_particles + 1, q, s, t, d);
+            const unsigned np = c->n_blocks_particles;
+            launch_pass_hot(c, "k_forces_hist", Forms{k_forces_hist<LPP>}, np, q, hot_forces(np, 0, s, t), s, t);
+            launch_pass_hot(c, "k_continuity_rebin", Forms{k_continuity_rebin<LPP>}, np + 1, q, hot_continuity(np, 1, s, t), s, t, d);
         } else {
             throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fold", "internal: folded re-binning step at this lane count");
         }
@@ -744,7 +780,8 @@ void launch_fused_ea(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, c
     with_lpp(c, [&](auto lpp) {  // 16 / 32 lanes per particle: the compact kernels; fewer: their large-channel forms
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16)
-            launch_pass(c, "k_continuity_density", Forms{k_continuity_density<LPP>, k_continuity_density_b<LPP>}, blocks, q, s, t, sn, tn, (int)tail);
+            launch_pass_hot(c, "k_continuity_density", Forms{k_continuity_density<LPP>, k_continuity_density_b<LPP>}, blocks, q,
+                            hot_fused(c->n_blocks_particles, (int)tail, t, tn), s, t, sn, tn, batch_only((int)tail));
         else if constexpr (LPP >= 2)
             launch_pass(c, "k_continuity_density", k_continuity_density_w<LPP>, blocks, q, s, t, sn, tn, (int)tail);
         else

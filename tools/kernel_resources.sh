@@ -1,9 +1,10 @@
 #!/bin/bash
 # Registers, LDS and occupancy of every kernel of sphx_resident.hip as compiled for gfx950 (no GPU needed):
 #   [SPHX_EXTRA_FLAGS=-D...] tools/kernel_resources.sh [filter-regex] > table
+# (with build.py's kernel-argument preload option; `preload`: the dwords of leading arguments a wave gets in registers)
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 S=/tmp/sphx_resident_$$.s
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only $SPHX_EXTRA_FLAGS -S -o $S "$ROOT/sph-poiseuille-flow_amd/csrc/sphx_resident.hip" || exit 1
+/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -mllvm -amdgpu-kernarg-preload-count=14 $SPHX_EXTRA_FLAGS -S -o $S "$ROOT/sph-poiseuille-flow_amd/csrc/sphx_resident.hip" || exit 1
 python3 - "$S" "${1:-.}" <<'PY'
 import re, subprocess, sys
 txt = open(sys.argv[1]).read()
@@ -21,6 +22,6 @@ for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, 
     ag = (re.search(r"; NumAgprs:\s*(\d+)", tail) or [0, "?"])[1]
     sg = (re.search(r"; TotalNumSgprs:\s*(\d+)", tail) or [0, "?"])[1]
     sc = (re.search(r"; ScratchSize:\s*(\d+)", tail) or [0, "?"])[1]
-    print(f"{dem:90s} vgpr {vg:>3} agpr {ag:>3} sgpr {sg:>3} lds {g('group_segment_fixed_size'):>6} scratch {sc:>4} occupancy {occ}")
+    print(f"{dem:90s} vgpr {vg:>3} agpr {ag:>3} sgpr {sg:>3} lds {g('group_segment_fixed_size'):>6} scratch {sc:>4} occupancy {occ} preload {g('user_sgpr_kernarg_preload_length'):>2}")
 PY
 rm -f $S

@@ -8,7 +8,9 @@ Prints, in program order, the scalar loads, the vector loads, the wait instructi
 later branch jumps back to) of every kernel whose mangled name contains a pattern -- nothing else.  Runs of loads are folded
 into one line each ("s_load x5: dwordx2 dwordx4 ..."), so that a request wave reads as one line and every line between two
 waits is one link of the chain.  A summary counts the waits in front of the first DEPENDENT request: the first vector load
-issued behind a wait for vector loads, so one whose address may come out of memory (the first neighbour gather of a pass)."""
+issued behind a wait for vector loads, so one whose address may come out of memory (the first neighbour gather of a pass).
+A kernel built for kernel-argument preload starts with a prologue that loads its leading arguments itself and branches to the
+256-byte-aligned entry a wave with preloaded arguments starts at: the listing marks that entry, and the summary counts from it."""
 import re
 import subprocess
 import sys
@@ -40,6 +42,11 @@ def chain(lines, start, end):
             labels[m.group(1)] = len(body)
             body.append((k + 1, "label", m.group(1)))
             continue
+        if re.match(r"^\t\.p2align\s+8", lines[k]) and body and body[-1][1] == "s_branch":
+            # a kernel built for kernel-argument preload: what stood above is the prologue that loads the leading arguments
+            # itself (firmware without preload enters there); a wave that got them in registers enters HERE, 256 bytes on
+            body.append((k + 1, "entry", ""))
+            continue
         m = re.match(r"^\t([a-z_0-9]+)\s*([^;]*)", lines[k])
         if m and not m.group(1).startswith("."):
             body.append((k + 1, m.group(1), m.group(2).strip()))
@@ -59,6 +66,11 @@ def chain(lines, start, end):
 
     waits_s, waits_v, first_gather = 0, 0, None
     for ln, op, args in body:
+        if op == "entry":
+            flush()
+            out.append((ln, "---- entry with preloaded arguments (the lines above: the fallback prologue, not run then) ----"))
+            waits_s, waits_v, first_gather = 0, 0, None  # the summary counts the preloaded path
+            continue
         if op == "label":
             if args in loops:
                 flush()
