@@ -437,6 +437,66 @@ int sphx_ctx_history_disable(sphx_ctx *ctx);
 int sphx_ctx_history_read(sphx_ctx *ctx, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2e. Field maps: the velocity field sampled on a regular grid in x and y, accumulated on the device, inside the step
+ *     loop.  The reference's result figure interpolates u_x onto such a grid on the host (panel (b) of
+ *     SPH_Poiseuille_postprocess.m:184-201); a y-binned profile (section 2a) averages over x by construction and cannot
+ *     show a seam defect or a standing structure along x.
+ *
+ *  Nodes: nx x ny of them, x_i = i * (DL / (nx - 1)) with x_{nx-1} = DL, y_k = k * (DH / (ny - 1)) with y_{ny-1} = DH
+ *    (numpy's and MATLAB's linspace, both ends included).  nx = 0 / ny = 0: the reference's shape 2 * round(DL / dp),
+ *    2 * round(DH / dp) (postprocess.m:185-186).  Column 0 and column nx - 1 are the same physical line of the periodic
+ *    channel.  Node (i, k) is stored at i * ny + k: y fastest, like the cells -- a MATLAB [ny x nx] matrix in
+ *    column-major order.
+ *  One sample at a node: Shepard interpolation over the fluid particles, from pos and vel of the state sphx_ctx_download
+ *    would return and nothing else.  dx = minimum image of x_node - x_j, dy = y_node - y_j; a particle contributes when
+ *    dx^2 + dy^2 < (2h)^2 (no lower cut: a particle on a node contributes W(0)); W is the two-piece cubic spline of the
+ *    physics (sigma = 10 / (7 pi h^2)); S0 = sum W, S1 = sum W u_x, S2 = sum W u_y.  with_walls = 1: the wall particles
+ *    enter the same three sums with their wall velocity (the no-slip picture); the default is fluid only.  For DL < 4h a
+ *    particle counts by its nearest image only, as in the neighbour search.
+ *  Accumulated per node, as six planes of nx * ny doubles, when S0 > 0: count += 1, sum_w += S0 * dp^2 (about 1 inside
+ *    the fluid, about 0.4 at a wall node with fluid only), sum_ux += S1 / S0, sum_uy += S2 / S0, sum_ux2 += (S1 / S0)^2,
+ *    sum_uy2 += (S2 / S0)^2.  A node with no contributor is skipped for that sample; a node never sampled reads back
+ *    with count = 0.  Per context: n_samples and the times of the first and the last sample (NaN before the first).
+ *  Gating: as in sections 2a and 2d.  A step is sampled when its step count (sphx_status.step after it) is a multiple of
+ *    `every` and it ends at t >= t_from.  Dual-rate contexts sample once per outer step.  A step slot that did not run
+ *    samples nothing.
+ *  Determinism: every node is owned by one thread, which adds its candidates in an order that depends on the particle
+ *    layout only; no atomics.  Two identical runs give bit-identical planes; another layout (another re-binning phase,
+ *    e.g. after a stop on the drift bound) changes the summation order only.
+ *  Off by default.  With it off a step slot enqueues exactly the launches it does without this feature; on, every step
+ *    slot ends with one more launch (k_field_map, behind k_flow_stats and k_step_history; it skips itself on the steps
+ *    gated out) that is captured in the replayed graphs; enable / disable re-capture them.  Independent of the flow
+ *    statistics and the step history: all three may be on at once.  The planes take 6 * nx * ny doubles of device memory.
+ *  Batches (section 2b) and slabs have no field maps.
+ *  Errors: SPHX:Field:config (nx or ny equal to 1 or negative, nx * ny > 1 << 25, every < 1, NaN t_from, with_walls not
+ *    0 or 1, or the allocation fails: the context then goes on without a map), SPHX:Field:disabled (SPHX_ERR_STATE: a
+ *    call that needs the map while it is off), SPHX:Field:capacity (the caller's arrays are smaller than nx * ny); every
+ *    call on a slab context fails with SPHX_ERR_ARG, SPHX:Field:slab.
+ * ---------------------------------------------------------------------------------------------- */
+
+typedef struct sphx_field_map_config {
+    int32_t nx, ny;      /* nodes along x / y, both ends included; 0 = 2 * round(DL / dp), 2 * round(DH / dp); never 1 */
+    int32_t every;       /* sample every `every`-th completed step (step count % every == 0), >= 1 */
+    int32_t with_walls;  /* 1: wall particles contribute with their wall velocity; 0: fluid only   */
+    double t_from;       /* only steps ending at t >= t_from                                       */
+} sphx_field_map_config;
+
+/* (Re)configure and zero the map; waits for the stream.  Off by default. */
+int sphx_ctx_field_map_enable(sphx_ctx *ctx, const sphx_field_map_config *cfg);
+/* Stop sampling (no-op when off); the sums are dropped. */
+int sphx_ctx_field_map_disable(sphx_ctx *ctx);
+/* Zero the sums and the sample count after everything enqueued has been taken. */
+int sphx_ctx_field_map_reset(sphx_ctx *ctx);
+/* Add one sample of the current state (what sphx_ctx_download would return) now, without gating. */
+int sphx_ctx_field_map_sample(sphx_ctx *ctx);
+/* The six planes, nx * ny entries each, node (i, k) at i * ny + k; any array may be NULL (all NULL: capacity is not
+ * checked, so the shape can be asked for first).  Waits for and settles everything enqueued, like sphx_ctx_download.
+ * t_first / t_last: simulated times of the first / last sample (NaN before the first). */
+int sphx_ctx_field_map_read(sphx_ctx *ctx, int capacity, int *nx, int *ny, double *count, double *sum_w,
+                            double *sum_ux, double *sum_uy, double *sum_ux2, double *sum_uy2, int64_t *n_samples,
+                            double *t_first, double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU).  The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

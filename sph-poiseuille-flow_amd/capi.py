@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from .profile import flow_stats_profile
+from .profile import FIELD_MAP_PLANES, field_map_means, flow_stats_profile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPHX_LIB") or os.path.join(HERE, "csrc", "libsphx.so")  # SPHX_LIB: experiment builds
@@ -45,6 +45,10 @@ class SphxHistoryConfig(C.Structure):
     _fields_ = [("every", C.c_int32), ("capacity", C.c_int32), ("t_from", C.c_double)]
 
 
+class SphxFieldMapConfig(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("every", C.c_int32), ("with_walls", C.c_int32), ("t_from", C.c_double)]
+
+
 # a record of the step history (include/sphx.h section 2d), in the order the library writes it
 HISTORY_FIELDS = ("step", "t", "dt", "vmax", "tau_bottom", "tau_top", "kinetic_energy", "u_bulk")
 
@@ -69,6 +73,8 @@ EXPORTS = [
     "sphx_ctx_flow_stats_enable", "sphx_ctx_flow_stats_disable", "sphx_ctx_flow_stats_reset", "sphx_ctx_flow_stats_sample",
     "sphx_ctx_flow_stats_read",
     "sphx_ctx_history_enable", "sphx_ctx_history_disable", "sphx_ctx_history_read",
+    "sphx_ctx_field_map_enable", "sphx_ctx_field_map_disable", "sphx_ctx_field_map_reset", "sphx_ctx_field_map_sample",
+    "sphx_ctx_field_map_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -312,6 +318,7 @@ class Context:
         assert pos.shape == (n_total, 2) and vel.shape == (n_total, 2) and wall_vel.shape == (n_total, 2)
         assert drho_dt.shape == (n_total,) and mass.shape == (n_total,)
         self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
+        self._field_map = None   # (nx, ny) while the field map is on
         check(lib().sphx_ctx_create(C.byref(self._h), C.byref(self.params), C.c_int(n_fluid), C.c_int(n_total),
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
@@ -483,6 +490,52 @@ class Context:
         rec, dropped = self.history_records(drain)
         return history_dict(rec, dropped)
 
+    # ---- field map (include/sphx.h section 2e): the velocity field on a regular grid in x and y, accumulated on the device ----
+    def field_map_enable(self, nx=0, ny=0, every=1, t_from=0.0, with_walls=False):
+        """Sample the state every `every`-th completed step ending at t >= t_from onto nx x ny nodes over [0, DL] x [0, DH],
+        ends included (0: the reference's 2 round(DL/dp), 2 round(DH/dp)), by Shepard interpolation over the fluid
+        particles -- and, with_walls, the wall particles with their wall velocity.  (Re)configures and zeroes the map."""
+        cfg = field_map_config(nx, ny, every, t_from, with_walls)
+        shape = field_map_shape(self.params, nx, ny)
+        check(lib().sphx_ctx_field_map_enable(self._h, C.byref(cfg)))
+        self._field_map = shape
+
+    def field_map_disable(self):
+        check(lib().sphx_ctx_field_map_disable(self._h))
+        self._field_map = None
+
+    def field_map_reset(self):
+        self._field_map_on()
+        check(lib().sphx_ctx_field_map_reset(self._h))
+
+    def field_map_sample(self):
+        """Add one sample of the current state (what download() returns) now, whatever the gating."""
+        self._field_map_on()
+        check(lib().sphx_ctx_field_map_sample(self._h))
+
+    def field_map_sums(self) -> dict:
+        """The raw planes count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2 as [ny, nx] arrays, plus n_samples, t_first, t_last."""
+        nx, ny = self._field_map_on()
+        arrs = [np.zeros(nx * ny) for _ in FIELD_MAP_PLANES]
+        gx, gy, ns, t0, t1 = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+        check(lib().sphx_ctx_field_map_read(self._h, C.c_int(nx * ny), C.byref(gx), C.byref(gy), *[ptr(a) for a in arrs],
+                                            C.byref(ns), C.byref(t0), C.byref(t1)))
+        assert (gx.value, gy.value) == (nx, ny), (gx.value, gy.value, nx, ny)
+        # node (i, k) at i * ny + k: the rows of the [ny, nx] array are the y-levels
+        out = {k: np.ascontiguousarray(a.reshape(nx, ny).T) for k, a in zip(FIELD_MAP_PLANES, arrs)}
+        out.update(n_samples=ns.value, t_first=t0.value, t_last=t1.value)
+        return out
+
+    def field_map(self) -> dict:
+        """The time-averaged map (profile.field_map_means): x [nx], y [ny] and count, weight, u_x, u_y, u_x_std, u_y_std as
+        [ny, nx] arrays (NaN where count == 0), n_samples, t_first, t_last."""
+        return field_map_means(self.params.DL, self.params.DH, **self.field_map_sums())
+
+    def _field_map_on(self):
+        if self._field_map is None:
+            raise SphxError(SPHX_ERR_STATE, "SPHX:Field:disabled", "the field map is not enabled on this context")
+        return self._field_map
+
     def profile_enable(self, on=True):
         check(lib().sphx_ctx_profile_enable(self._h, C.c_int(1 if on else 0)))
 
@@ -546,6 +599,38 @@ def history_config(every=1, capacity=65536, t_from=0.0) -> SphxHistoryConfig:
     if not np.isfinite(t_from):
         raise bad("t_from must be finite")
     return SphxHistoryConfig(every=int(every), capacity=int(capacity), t_from=t_from)
+
+
+def field_map_shape(prm, nx=0, ny=0):
+    """(nx, ny) of a field map on a channel with parameters prm: 0 = the reference's 2 round(DL/dp), 2 round(DH/dp)
+    (SPH_Poiseuille_postprocess.m:185-186)."""
+    return (int(nx) or 2 * int(np.floor(prm.DL / prm.dp + 0.5)), int(ny) or 2 * int(np.floor(prm.DH / prm.dp + 0.5)))
+
+
+def field_map_config(nx=0, ny=0, every=1, t_from=0.0, with_walls=False) -> SphxFieldMapConfig:
+    """Checked sphx_field_map_config; raises SphxError(SPHX:Field:config) before anything reaches the device."""
+    def bad(msg):
+        return SphxError(SPHX_ERR_ARG, "SPHX:Field:config", msg)
+
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+    for name, v in (("nx", nx), ("ny", ny)):
+        if not is_int(v) or v < 0 or v == 1:
+            raise bad(f"{name} must be an integer >= 2, or 0 for the reference's shape")
+    if nx * ny > 1 << 25:
+        raise bad("nx * ny must not exceed 1 << 25 nodes")
+    if not is_int(every) or every < 1:
+        raise bad("every must be an integer >= 1")
+    try:
+        t_from = float(t_from)
+    except (TypeError, ValueError):
+        raise bad("t_from must be a number") from None
+    if np.isnan(t_from):
+        raise bad("t_from must not be NaN")
+    if not (isinstance(with_walls, (bool, np.bool_)) or (is_int(with_walls) and with_walls in (0, 1))):
+        raise bad("with_walls must be a bool (or 0 / 1)")
+    return SphxFieldMapConfig(nx=int(nx), ny=int(ny), every=int(every), with_walls=int(with_walls), t_from=t_from)
 
 
 def history_dict(records, n_dropped=0) -> dict:

@@ -1,0 +1,150 @@
+// sphx_field_map.hpp -- velocity-field maps of a resident context (include/sphx.h section 2e): one self-skipping launch at
+// the end of every step slot interpolates the velocity of the state the step left onto a regular nx x ny grid of nodes
+// (both ends included in x and y, the shape of panel (b) of SPH_Poiseuille_postprocess.m:184-201 by default) and adds
+// the sample to running sums per node, without a host round trip.
+//
+// One sample at a node is Shepard interpolation with the cubic spline of spline_W over every particle within 2h
+// (minimum image in x, no lower cut): S0 = sum W, S1 = sum W u_x, S2 = sum W u_y, and S1 / S0, S2 / S0 where S0 > 0.
+//
+// Why the 3 x 3 sweep suffices.  A node finds the cell its own coordinates fall into (cell_of) and walks the three cell
+// columns around it (field_columns: the columns, rows and slot order of sweep<1>, through neighbour_column -- a period
+// of one or two columns is visited once per distinct column and the minimum-image fold picks the nearest image,
+// duplicate_column).  The sweep is centred on the NODE's cell, not on a cell something was binned into, while the
+// particles of a cell range are those BINNED there, which may since have drifted.  A particle within 2h of the node was
+// binned at most 2h + drift from it; the cells are 2h + skin wide in x and y, so as long as the drift stays below the
+// whole skin that binning position lies in the node's cell or one next to it.  The clock stops (or re-bins) at a drift
+// of skin / 2: every state a sample can see -- the one a step slot left, the one a stopped loop left for
+// sphx_ctx_download -- is inside the bound with half the skin to spare.  Wall particles do not move at all.
+//
+// Mapping: one thread per node, a wave covers an 8 x 8 tile of nodes (about 4 dp x 4 dp at the default shape, one and a
+// half cells), so the lanes of a wave walk nearly the same candidate runs and their 16-byte loads of pos / vel hit the
+// same cache lines; consecutive node indices along y would spread a wave over about twelve cells.  Wave tiles are
+// numbered y fastest, like the cells and the nodes.  The grid grows with the node count (four wave tiles a workgroup).
+//
+// Determinism: every node is owned by one thread, which adds the candidates in the sweep's column and slot order and
+// updates the six sums of its node with plain loads and stores: no atomics, no ticket.  Two identical runs give identical
+// bits; another layout of the particles (re-binning phase, host chunking) changes the summation order only.  The head is
+// written by thread 0 of workgroup 0 alone.
+#pragma once
+#include "../../include/sphx.h"
+#include "sphx_kernels.hpp"
+
+namespace sphx {
+
+constexpr int kFieldPlanes = 6;             // count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2: planes of nx * ny doubles
+constexpr int kFieldTile = 8;               // a wave's tile of nodes: kFieldTile x kFieldTile = 64 lanes
+constexpr int kFieldBlock = 256;            // four wave tiles per workgroup
+constexpr long long kFieldMaxNodes = 1ll << 25;  // 6 planes: 1.5 GB
+
+struct FieldMapHead {
+    long long n_samples;
+    double t_first, t_last;
+};
+
+struct FieldMapArgs {
+    double *planes;        // [kFieldPlanes][nx * ny], node (i, k) at i * ny + k
+    FieldMapHead *head;
+    double step_x, step_y; // DL / (nx - 1), DH / (ny - 1): the step of numpy's linspace
+    double dp2;            // dp^2: sum_w accumulates S0 dp^2
+    double t_from;
+    int nx, ny;
+    int tiles_y, n_tiles;  // wave tiles along y, and in all
+    int every;             // >= 1: in-loop sample, gated on the clock; 0: sample unconditionally
+    int with_walls;        // 1: the wall particles enter the sums with their wall velocity
+};
+
+struct FieldSums {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;  // sum W, sum W u_x, sum W u_y
+};
+
+// The candidates of the three cell columns around (cx, cy) -- sweep<1>'s columns, rows and slot order -- added to S for the node
+// at (xn, yn).  kFieldAhead candidates a trip: their positions AND velocities are requested before the first one is looked at
+// (a slot beyond the run repeats the run's last one and is not added), so a trip costs one memory round trip where one
+// candidate a trip cost one per candidate and a second, dependent one per hit -- at a few thousand particles a wave is alone
+// on its SIMD and the sample is that chain of round trips.  The order of the adds is the slot order either way.
+constexpr int kFieldAhead = 4;
+template <typename Vel>
+__device__ __forceinline__ void field_columns(const Grid &g, const KernelConst &kc, const int *__restrict__ start, int cx, int cy,
+                                              double xn, double yn, FieldSums &S, const double2 *__restrict__ pos, Vel &&vel)
+{
+    const int cylo = max(cy - 1, 0), cyhi = min(cy + 1, g.ncy - 1);
+#pragma unroll 1
+    for (int ox = -1; ox <= 1; ++ox) {
+        int col;
+        if (!neighbour_column(g, cx, ox, col)) continue;
+        const int base = col * g.ncy;
+        const int lo = start[base + cylo], hi = start[base + cyhi + 1];
+        for (int k = lo; k < hi; k += kFieldAhead) {
+            double2 p[kFieldAhead], v[kFieldAhead];
+#pragma unroll
+            for (int u = 0; u < kFieldAhead; ++u) {
+                const int j = min(k + u, hi - 1);
+                p[u] = pos[j];
+                v[u] = vel(j);
+            }
+#pragma unroll
+            for (int u = 0; u < kFieldAhead; ++u) {
+                const double dx = min_image(g, xn - p[u].x), dy = yn - p[u].y;
+                const double r2 = dx * dx + dy * dy;
+                if (k + u < hi && r2 < kc.rcut2) {
+                    const double W = spline_W(kc, sqrt(r2));
+                    S.s0 += W;
+                    S.s1 += W * v[u].x;
+                    S.s2 += W * v[u].y;
+                }
+            }
+        }
+    }
+}
+
+// q: parity of the step slot this launch closes (in-loop samples: the slot ran iff run[q] is still set -- a clock update
+// only ever writes the flag of the NEXT slot).  The launch sits behind the slot's clock update, so clk->step / clk->t are
+// those of the step just completed; s is the state it left (pos, vel and the cell ranges of the layout it is stored in).
+__global__ __launch_bounds__(kFieldBlock) void k_field_map(const Clock *clk, int q, Grid g, Phys ph, FluidSet s, Walls w,
+                                                           FieldMapArgs a)
+{
+    if (a.every > 0) {
+        if (!clk->run[q]) return;
+        if (clk->step % a.every != 0) return;
+        if (!(clk->t >= a.t_from)) return;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {  // the head, by one thread: plain vector stores
+        FieldMapHead *h = a.head;
+        const double t_now = clk->t;
+        const long long ns = h->n_samples;
+        if (ns == 0) h->t_first = t_now;
+        h->t_last = t_now;
+        h->n_samples = ns + 1;
+    }
+    const int lane = (int)threadIdx.x & 63;
+    const int tile = (int)blockIdx.x * (kFieldBlock / 64) + ((int)threadIdx.x >> 6);
+    if (tile >= a.n_tiles) return;
+    const int tx = tile / a.tiles_y, ty = tile - tx * a.tiles_y;
+    const int i = tx * kFieldTile + (lane >> 3), k = ty * kFieldTile + (lane & 7);
+    if (i >= a.nx || k >= a.ny) return;
+    // numpy's linspace: i * step, the last node the end itself
+    const double xn = i == a.nx - 1 ? ph.DL : (double)i * a.step_x;
+    const double yn = k == a.ny - 1 ? ph.DH : (double)k * a.step_y;
+    int cx, cy;
+    cell_of(g, xn, yn, cx, cy);
+    FieldSums S;
+    field_columns(g, ph.kc, s.start, cx, cy, xn, yn, S, s.pos, [&](int j) { return s.vel[j]; });
+    if (a.with_walls && w.row_any[cy])
+        field_columns(g, ph.kc, w.start, cx, cy, xn, yn, S, w.pos, [&](int j) {
+            const double4 wj = w.a[j];  // {Vol, vx, vy, 0}
+            return make_double2(wj.y, wj.z);
+        });
+    const double S0 = S.s0, S1 = S.s1, S2 = S.s2;
+    if (!(S0 > 0.0)) return;  // no contributor: the node is skipped for this sample
+    const size_t nn = (size_t)a.nx * (size_t)a.ny, at = (size_t)i * (size_t)a.ny + (size_t)k;
+    const double ux = S1 / S0, uy = S2 / S0;
+    double *p = a.planes + at;
+    p[0] += 1.0;
+    p[nn] += S0 * a.dp2;
+    p[2 * nn] += ux;
+    p[3 * nn] += uy;
+    p[4 * nn] += ux * ux;
+    p[5 * nn] += uy * uy;
+}
+
+}  // namespace sphx

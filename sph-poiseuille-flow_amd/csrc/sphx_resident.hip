@@ -16,6 +16,7 @@
 #include "sphx_kernels.hpp"
 #include "sphx_flow_stats.hpp"
 #include "sphx_history.hpp"
+#include "sphx_field_map.hpp"
 
 namespace sphx {
 
@@ -279,6 +280,16 @@ struct sphx_ctx {
         DevBuf<double> records, part;
         DevBuf<HistoryHead> head;
     } hist;
+
+    // Velocity-field map (sphx_ctx_field_map_*, sphx_field_map.hpp): when on, every step slot ends with k_field_map
+    struct FieldMap {
+        bool on = false;
+        sphx_field_map_config cfg{};
+        int nx = 0, ny = 0;  // the shape in force (cfg.nx / cfg.ny = 0: the reference's)
+        DevBuf<double> planes;
+        DevBuf<FieldMapHead> head;
+        size_t nodes() const { return (size_t)nx * (size_t)ny; }
+    } fmap;
 
     // Member of a batch (sphx_batch_*): the device arrays are this member's blocks of batch-wide allocations (BatchArena)
     sphx::BatchArena *arena = nullptr;
@@ -936,6 +947,35 @@ void launch_slot_history(sphx_ctx *c, int q, int l, bool rebuild)
            c->phys, s, c->tmp_par[c->fuse_ea ? q : 0], c->walls, a);
 }
 
+// k_field_map on state s (pos, vel and the cell ranges of the layout it is stored in) into c->fmap: every >= 1 = the in-loop
+// sample closing step slot q, 0 = a sample of the state now
+void launch_field_map(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    const sphx_ctx::FieldMap &f = c->fmap;
+    single_form_only(c, "k_field_map");
+    FieldMapArgs a{};
+    a.planes = f.planes.get(); a.head = f.head.get();
+    a.step_x = c->prm.DL / (f.nx - 1); a.step_y = c->prm.DH / (f.ny - 1);
+    a.dp2 = c->prm.dp * c->prm.dp;
+    a.t_from = f.cfg.t_from;
+    a.nx = f.nx; a.ny = f.ny;
+    a.tiles_y = (int)div_up((size_t)f.ny, (size_t)kFieldTile);
+    a.n_tiles = (int)div_up((size_t)f.nx, (size_t)kFieldTile) * a.tiles_y;
+    a.every = every;
+    a.with_walls = f.cfg.with_walls && c->nw > 0 ? 1 : 0;
+    const unsigned blocks = div_up((size_t)a.n_tiles, (size_t)(kFieldBlock / 64));
+    launch(c, "k_field_map", k_field_map, dim3(blocks), dim3(kFieldBlock), (const Clock *)c->clock.get(), q, c->grid, c->phys, s,
+           c->walls, a);
+}
+
+// k_field_map behind step slot q, which ran on layout l: the view launch_slot_history picks -- the state the slot left is
+// S[1-q], in the other layout when the slot re-binned (a dynamic context re-bins in place)
+void launch_slot_field(sphx_ctx *c, int q, int l, bool rebuild)
+{
+    if (!c->fmap.on) return;
+    launch_field_map(c, q, c->dyn ? c->view(1 - q, 0) : c->view(1 - q, rebuild ? 1 - l : l), c->fmap.cfg.every);
+}
+
 // host-side bookkeeping of one step slot
 void track_step(sphx_ctx *c)
 {
@@ -1048,7 +1088,7 @@ void enqueue_slots(Schedule &s, hipStream_t st, int K, int per_graph, int64_t sl
 // ---- a context's side of it ----
 
 // one step slot of a context: the static schedule's launches or a dynamic context's, then the slot's k_flow_stats and
-// k_step_history (each only where it is on)
+// k_step_history and k_field_map (each only where it is on)
 auto ctx_slot(sphx_ctx *c)
 {
     return [c](int q, int l, int p, bool rebuild) {
@@ -1056,6 +1096,7 @@ auto ctx_slot(sphx_ctx *c)
         else launch_step(c, q, l, p, rebuild);
         launch_slot_stats(c, q);
         launch_slot_history(c, q, l, rebuild);
+        launch_slot_field(c, q, l, rebuild);
     };
 }
 
@@ -2330,6 +2371,130 @@ SPHX_EXPORT int sphx_ctx_history_read(sphx_ctx *c, int capacity, double *records
         h.head.zero(c->stream);
         SPHX_HIP(hipStreamSynchronize(c->stream));
     }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- velocity-field map (sphx_field_map.hpp) ----
+namespace {
+
+sphx_ctx *field_ctx(sphx_ctx *c, bool need_on)
+{
+    require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
+    require(!c->is_slab, "SPHX:Field:slab", "field maps are not available on slab contexts");
+    if (need_on && !c->fmap.on)
+        throw Error(SPHX_ERR_STATE, "SPHX:Field:disabled", "the field map is not enabled on this context");
+    return c;
+}
+
+void field_release(sphx_ctx::FieldMap &f)
+{
+    f.on = false;
+    f.planes.release();
+    f.head.release();
+}
+
+void field_zero(sphx_ctx *c)
+{
+    c->fmap.planes.zero(c->stream);
+    c->fmap.head.zero(c->stream);
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_config *cfg)
+{
+    SPHX_TRY
+    field_ctx(c, false);
+    require(cfg != nullptr, "SPHX:Field:config", "config must not be NULL");
+    require(cfg->nx == 0 || cfg->nx >= 2, "SPHX:Field:config", "nx must be 0 (the reference's shape) or >= 2");
+    require(cfg->ny == 0 || cfg->ny >= 2, "SPHX:Field:config", "ny must be 0 (the reference's shape) or >= 2");
+    require(cfg->every >= 1, "SPHX:Field:config", "every must be >= 1");
+    require(!std::isnan(cfg->t_from), "SPHX:Field:config", "t_from must not be NaN");
+    require(cfg->with_walls == 0 || cfg->with_walls == 1, "SPHX:Field:config", "with_walls must be 0 or 1");
+    // 0: the grid of SPH_Poiseuille_postprocess.m:185-186
+    const double nx = cfg->nx > 0 ? (double)cfg->nx : 2.0 * std::floor(c->prm.DL / c->prm.dp + 0.5);
+    const double ny = cfg->ny > 0 ? (double)cfg->ny : 2.0 * std::floor(c->prm.DH / c->prm.dp + 0.5);
+    require(nx >= 2.0 && ny >= 2.0, "SPHX:Field:config", "the reference's shape has fewer than 2 nodes along x or y: give nx and ny");
+    require(nx * ny <= (double)kFieldMaxNodes, "SPHX:Field:config", "nx * ny must not exceed 1 << 25 nodes");
+    stats_drop_graphs(c->sched, c->stream);  // the replayed graphs carry k_field_map (and its arguments) or not
+    sphx_ctx::FieldMap &f = c->fmap;
+    field_release(f);
+    f.nx = (int)nx;
+    f.ny = (int)ny;
+    try {
+        f.planes.alloc(f.nodes() * kFieldPlanes);
+        f.head.alloc(1);
+        field_zero(c);
+    } catch (const Error &e) {
+        field_release(f);
+        (void)hipGetLastError();
+        throw Error(SPHX_ERR_ARG, "SPHX:Field:config", std::string("the map could not be set up: ") + e.what());
+    }
+    f.cfg = *cfg;
+    f.on = true;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_field_map_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    field_ctx(c, false);
+    if (!c->fmap.on) return SPHX_OK;
+    stats_drop_graphs(c->sched, c->stream);
+    field_release(c->fmap);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_field_map_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    field_ctx(c, true);
+    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
+    field_zero(c);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_field_map_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    field_ctx(c, true);
+    settle_owed(c);  // the state sphx_ctx_download would return
+    launch_field_map(c, 0, c->view(c->sched.cur, c->sched.lay), 0);
+    SPHX_HIP(hipGetLastError());
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_field_map_read(sphx_ctx *c, int capacity, int *nx, int *ny, double *count, double *sum_w, double *sum_ux,
+                                        double *sum_uy, double *sum_ux2, double *sum_uy2, int64_t *n_samples, double *t_first,
+                                        double *t_last)
+{
+    SPHX_TRY
+    field_ctx(c, true);
+    const sphx_ctx::FieldMap &f = c->fmap;
+    double *const out[kFieldPlanes] = {count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2};
+    bool any = false;
+    for (double *o : out) any = any || o != nullptr;
+    require(!any || (size_t)std::max(capacity, 0) >= f.nodes(), "SPHX:Field:capacity", "capacity is smaller than nx * ny");
+    settle_owed(c);  // (the samples of everything enqueued)
+    FieldMapHead head{};
+    for (int j = 0; j < kFieldPlanes; ++j)
+        if (out[j])
+            SPHX_HIP(hipMemcpyAsync(out[j], f.planes.get() + (size_t)j * f.nodes(), f.nodes() * sizeof(double), hipMemcpyDeviceToHost,
+                                    c->stream));
+    SPHX_HIP(hipMemcpyAsync(&head, f.head.get(), sizeof(head), hipMemcpyDeviceToHost, c->stream));
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (nx) *nx = f.nx;
+    if (ny) *ny = f.ny;
+    if (n_samples) *n_samples = (int64_t)head.n_samples;
+    if (t_first) *t_first = head.n_samples ? head.t_first : nan;
+    if (t_last) *t_last = head.n_samples ? head.t_last : nan;
     return SPHX_OK;
     SPHX_CATCH
 }

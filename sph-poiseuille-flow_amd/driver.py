@@ -46,6 +46,7 @@ class RunResult:
     n_inner: int = 1  # inner sub-steps per counted step (> 1 only with the opt-in dual-rate loop)
     time_avg: dict = None  # run(..., average_from=...): device-side time-averaged profiles and figures (see time_average)
     history: dict = None  # run(..., history_every=...): the device-side step history of the whole run (capi.Context.history)
+    field_avg: dict = None  # run(..., field_from=...): the device-side time-averaged velocity map (capi.Context.field_map)
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -130,6 +131,36 @@ def history_figures(prm, hist, t_from=0.0, tol=0.05):
     return out
 
 
+def field_figures(prm, field):
+    """Figures of a velocity map (capi.Context.field_map / RunResult.field_avg, or profile.shepard_field of one state: x, y,
+    u_x, u_y as [ny, nx] arrays) against the analytic flow, on the host.  Nodes never sampled (NaN) are left out.
+      u_row_mean, u_exact    the x-mean of u_x per row and the analytic profile at the rows' y
+      rows, L2               the rows at least 2h from both walls, and l2_error of u_row_mean against u_exact over them
+      x_spread, ix, iy       the largest deviation of a node's u_x from its row's x-mean over those rows, in % of U_max, and
+                             the node where it occurs (a seam defect shows up at ix near 0 or nx - 1)
+      uy_rms                 RMS of u_y over all sampled nodes
+      U_max                  g DH^2 / (8 nu)"""
+    y = np.asarray(field["y"], dtype=np.float64)
+    ux, uy = np.asarray(field["u_x"], dtype=np.float64), np.asarray(field["u_y"], dtype=np.float64)
+    u_max = prm.gravity_g * prm.DH ** 2 / (8.0 * prm.nu)
+    u_exact = prm.gravity_g / (2.0 * prm.nu) * y * (prm.DH - y)
+    ok = ~np.isnan(ux)
+    n_row = np.maximum(ok.sum(axis=1), 1)
+    first = np.where(ok.any(axis=1), ux[np.arange(len(y)), np.argmax(ok, axis=1)], np.nan)
+    # (about the row's first sampled node: a row of equal values gives that value exactly)
+    row_mean = first + np.where(ok, ux - first[:, None], 0.0).sum(axis=1) / n_row
+    rows = (y >= 2.0 * prm.h) & (y <= prm.DH - 2.0 * prm.h)
+    sel = rows & ~np.isnan(row_mean)
+    dev = np.where(ok & rows[:, None], np.abs(ux - row_mean[:, None]), -1.0)
+    iy, ix = np.unravel_index(int(np.argmax(dev)), dev.shape)
+    x_spread = 100.0 * float(dev[iy, ix]) / u_max if dev[iy, ix] >= 0.0 else float("nan")
+    uy_ok = uy[~np.isnan(uy)]
+    return dict(u_row_mean=row_mean, u_exact=u_exact, rows=rows,
+                L2=l2_error(np.where(sel, row_mean, np.nan), u_exact) if sel.any() else float("nan"),
+                x_spread=x_spread, ix=int(ix), iy=int(iy),
+                uy_rms=float(np.sqrt(np.mean(uy_ok * uy_ok))) if uy_ok.size else float("nan"), U_max=u_max)
+
+
 def _concat_history(chunks):
     if not chunks:
         return capi.history_dict(np.zeros((0, len(capi.HISTORY_FIELDS))))
@@ -140,7 +171,8 @@ def _concat_history(chunks):
 
 def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_particle=0, steps_per_graph=0,
         rebuild_every=0, restart_path=None, postprocess_path=None, dual_rate=0, mat_format="auto", average_from=None,
-        average_every=1, history_every=None, history_capacity=65536):
+        average_every=1, history_every=None, history_capacity=65536, field_from=None, field_every=1, field_shape=None,
+        field_walls=False):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -156,7 +188,14 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     history_every (resident engine): record every history_every-th step on the device (include/sphx.h section 2d: step, t,
     dt, vmax, tau_bottom, tau_top, kinetic_energy, u_bulk); the buffer (history_capacity records) is drained at every
     output point, so a capacity that holds one output interval suffices, and RunResult.history is the series of the
-    whole run (history_figures() turns it into means and a settling time)."""
+    whole run (history_figures() turns it into means and a settling time).
+    field_from (resident engine): accumulate, on the device and inside the step loop, every field_every-th step ending at
+    t >= field_from into a velocity map on a regular grid (include/sphx.h section 2e; field_shape = (nx, ny), None = the
+    reference's 2 round(DL/dp) x 2 round(DH/dp); field_walls: the wall particles contribute with their wall velocity);
+    RunResult.field_avg is capi.Context.field_map() at the end (field_figures() turns it into an x-mean profile, its L2
+    and the spread along x).  A map of the final state of any engine: profile.shepard_field(res.pos[:nf], res.vel[:nf], ...)."""
+    if field_from is not None and engine != "resident":
+        raise ValueError("field_from needs the resident engine (the map is accumulated on the device)")
     if average_from is not None and engine != "resident":
         raise ValueError("average_from needs the resident engine (the statistics are accumulated on the device)")
     if history_every is not None and engine != "resident":
@@ -184,6 +223,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     policy = {}
     time_avg = None
     history, history_chunks = None, []
+    field_avg = None
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
@@ -196,6 +236,9 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 ctx.flow_stats_enable(n_bins=n_bins, every=average_every, t_from=average_from, bands=[(mid_x, mid_hw)])
             if history_every is not None:
                 ctx.history_enable(every=history_every, capacity=history_capacity)
+            if field_from is not None:
+                fnx, fny = field_shape if field_shape is not None else (0, 0)
+                ctx.field_map_enable(nx=fnx, ny=fny, every=field_every, t_from=field_from, with_walls=field_walls)
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -227,6 +270,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 time_avg = time_average(prm, ctx.flow_stats(0), ctx.flow_stats(1))
             if history_every is not None:
                 history = _concat_history(history_chunks)
+            if field_from is not None:
+                field_avg = ctx.field_map()
         finally:
             ctx.close()
     elif engine == "mex":
@@ -281,7 +326,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                      y_mid=y_mid, u_mean=u_mean, u_exact=u_exact, L2_error=l2_error(u_mean, u_exact),
                      profile_times=profile_times, mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t,
                      tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2, grid_policy=policy, full_profile_u=full_profiles, n_inner=n_inner,
-                     time_avg=time_avg, history=history)
+                     time_avg=time_avg, history=history, field_avg=field_avg)
 
 
 def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,

@@ -15,6 +15,11 @@
  *   [records, n_dropped] = sphx_ctx_mex('history_read', h, drain)
  *       records: n x 8, one row per recorded step: step, t, dt, vmax, tau_bottom, tau_top, kinetic_energy, u_bulk (step
  *       history, include/sphx.h section 2d); drain ~= 0 empties the device buffer
+ *   sphx_ctx_mex('field_enable', h, nx, ny, every, t_from, with_walls)   % nx = 0 / ny = 0: the reference's grid shape
+ *   sphx_ctx_mex('field_disable', h)   /   sphx_ctx_mex('field_reset', h)
+ *   sphx_ctx_mex('field_sample', h)    % add one sample of the current state now
+ *   [count, w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples, t_first, t_last] = sphx_ctx_mex('field_read', h)
+ *       [ny x nx] matrices over linspace(0, DL, nx) x linspace(0, DH, ny) (field map, include/sphx.h section 2e)
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -181,6 +186,41 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
             for (f = 0; f < SPHX_HISTORY_FIELDS; ++f) out[(size_t)f * got + k] = rows[(size_t)k * SPHX_HISTORY_FIELDS + f];
         mxFree(rows);
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)dropped);
+    } else if (strcmp(cmd, "field_enable") == 0) {
+        sphx_field_map_config mc;
+        arity(cmd, nrhs, 7, nlhs, 0);
+        memset(&mc, 0, sizeof(mc));
+        mc.nx = (int32_t)mxGetScalar(prhs[2]);
+        mc.ny = (int32_t)mxGetScalar(prhs[3]);
+        mc.every = (int32_t)mxGetScalar(prhs[4]);
+        mc.t_from = mxGetScalar(prhs[5]);
+        mc.with_walls = (int32_t)mxGetScalar(prhs[6]);
+        ok(sphx_ctx_field_map_enable(handle(prhs[1]), &mc));
+    } else if (strcmp(cmd, "field_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_field_map_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "field_reset") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_field_map_reset(handle(prhs[1])));
+    } else if (strcmp(cmd, "field_sample") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_field_map_sample(handle(prhs[1])));
+    } else if (strcmp(cmd, "field_read") == 0) {
+        sphx_ctx *c;
+        int nx = 0, ny = 0, k;
+        int64_t ns = 0;
+        double t0 = 0.0, t1 = 0.0, *out[6] = {0};
+        arity(cmd, nrhs, 2, nlhs, 9);
+        c = handle(prhs[1]);
+        ok(sphx_ctx_field_map_read(c, 0, &nx, &ny, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL));
+        for (k = 0; k < 6 && k < (nlhs > 0 ? nlhs : 1); ++k) {  /* node (i, k) at i * ny + k: a column-major [ny x nx] matrix */
+            plhs[k] = mxCreateDoubleMatrix((mwSize)ny, (mwSize)nx, mxREAL);
+            out[k] = mxGetDoubles(plhs[k]);
+        }
+        ok(sphx_ctx_field_map_read(c, nx * ny, NULL, NULL, out[0], out[1], out[2], out[3], out[4], out[5], &ns, &t0, &t1));
+        if (nlhs > 6) plhs[6] = mxCreateDoubleScalar((double)ns);
+        if (nlhs > 7) plhs[7] = mxCreateDoubleScalar(t0);
+        if (nlhs > 8) plhs[8] = mxCreateDoubleScalar(t1);
     } else if (strcmp(cmd, "destroy") == 0) {
         arity(cmd, nrhs, 2, nlhs, 0);
         sphx_ctx_destroy(handle(prhs[1]));

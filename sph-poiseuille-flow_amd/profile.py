@@ -4,6 +4,7 @@ compute_binned_profile_mean / compute_mid_channel_profile: SPH_Poiseuille.m:579-
 final_profile: SPH_Poiseuille.m:617-623.  l2_error: SPH_Poiseuille_postprocess.m:37-42.
 flow_stats_profile: the sums of the device's flow statistics (include/sphx.h section 2a) as a profile.
 pool_flow_stats: the sums of several channels (the members of a batch, section 2c) as one ensemble-averaged profile.
+shepard_field: one sample of the device's field map (include/sphx.h section 2e) in numpy; field_map_means: its sums as a map.
 """
 from __future__ import annotations
 
@@ -114,3 +115,74 @@ def pool_flow_stats(DH, sums_list):
         se[ok] = np.std(means[:, ok], axis=0, ddof=1) / np.sqrt(M)
     out.update(u_mean_se=se, n_members=M)
     return out
+
+
+def field_map_nodes(DL, DH, nx, ny):
+    """The node coordinates of a field map (include/sphx.h section 2e): linspace over [0, DL] and [0, DH], ends included."""
+    return np.linspace(0.0, DL, nx), np.linspace(0.0, DH, ny)
+
+
+def shepard_field(pos, vel, DL, DH, h, nx, ny, wall_pos=None, wall_vel=None, chunk=2048, nodes=None):
+    """One sample of the field map of include/sphx.h section 2e, in numpy: Shepard interpolation of vel onto the nx x ny
+    nodes with the cubic spline of the physics over every particle within 2h (minimum image in x -- the nearest image
+    only -- and no lower cut).  pos / vel: the fluid rows [n x 2]; wall_pos / wall_vel: wall rows that enter the same sums
+    (with_walls).  Chunked over nodes (chunk x n distances at a time).
+    Returns x [nx], y [ny] and S0 = sum W, S1 = sum W u_x, S2 = sum W u_y, u_x = S1 / S0, u_y = S2 / S0 (NaN where S0 == 0)
+    as [ny, nx] arrays -- or, with nodes = flat node indices i * ny + k, as 1-D arrays over just those nodes.  The oracle of
+    the device kernel and the host route to a map of a final state that never was on the device."""
+    pos, vel = np.asarray(pos, dtype=np.float64), np.asarray(vel, dtype=np.float64)
+    if wall_pos is not None:
+        pos = np.concatenate([pos, np.asarray(wall_pos, dtype=np.float64)])
+        vel = np.concatenate([vel, np.asarray(wall_vel, dtype=np.float64)])
+    xs, ys = field_map_nodes(DL, DH, nx, ny)
+    flat = np.arange(nx * ny) if nodes is None else np.asarray(nodes, dtype=np.int64)
+    X, Y = xs[flat // ny], ys[flat % ny]
+    sigma, half, rcut2 = 10.0 / (7.0 * np.pi * h * h), 0.5 * DL, (2.0 * h) * (2.0 * h)
+    px, py, ux, uy = pos[:, 0], pos[:, 1], vel[:, 0], vel[:, 1]
+    S = np.zeros((3, len(flat)))
+    for a in range(0, len(flat), chunk):
+        dx = X[a:a + chunk, None] - px[None, :]
+        dx -= DL * np.round(dx / DL)  # the nearest image (x in [0, DL): at most one period, the device's single fold)
+        dy = Y[a:a + chunk, None] - py[None, :]
+        r2 = dx * dx + dy * dy
+        q = np.sqrt(r2) / h
+        tq = 2.0 - q
+        W = np.where(q < 1.0, sigma * (1.0 - 1.5 * q * q + 0.75 * q * q * q), sigma * 0.25 * tq * tq * tq)
+        W = np.where(r2 < rcut2, W, 0.0)
+        S[0, a:a + chunk] = W.sum(axis=1)
+        S[1, a:a + chunk] = W @ ux
+        S[2, a:a + chunk] = W @ uy
+    hit = S[0] > 0.0
+    safe = np.where(hit, S[0], 1.0)
+    fields = dict(S0=S[0], S1=S[1], S2=S[2], u_x=np.where(hit, S[1] / safe, np.nan), u_y=np.where(hit, S[2] / safe, np.nan))
+    if nodes is None:
+        fields = {k: np.ascontiguousarray(v.reshape(nx, ny).T) for k, v in fields.items()}
+    return dict(x=xs, y=ys, **fields)
+
+
+FIELD_MAP_PLANES = ("count", "sum_w", "sum_ux", "sum_uy", "sum_ux2", "sum_uy2")
+
+
+def field_map_means(DL, DH, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples=0, t_first=np.nan, t_last=np.nan):
+    """The six planes of a field map ([ny, nx] each) -> the time-averaged map: x, y, count, weight = sum_w / count (about 1
+    inside the fluid), u_x, u_y = the mean of the per-sample Shepard values, u_x_std, u_y_std = their spread over the
+    samples, sqrt(max(sum u^2 / N - mean^2, 0)); NaN where count == 0."""
+    N, sw, sx, sy, sxx, syy = [np.asarray(a, dtype=np.float64) for a in (count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2)]
+    ny, nx = N.shape
+    xs, ys = field_map_nodes(DL, DH, nx, ny)
+    empty = N == 0
+    Nd = np.where(empty, 1.0, N)
+
+    def mean_std(s, ss):
+        m = s / Nd
+        sd = np.sqrt(np.maximum(ss / Nd - m * m, 0.0))
+        m[empty] = np.nan
+        sd[empty] = np.nan
+        return m, sd
+
+    u_x, u_x_std = mean_std(sx, sxx)
+    u_y, u_y_std = mean_std(sy, syy)
+    weight = sw / Nd
+    weight[empty] = np.nan
+    return dict(x=xs, y=ys, count=N, weight=weight, u_x=u_x, u_y=u_y, u_x_std=u_x_std, u_y_std=u_y_std,
+                n_samples=int(n_samples), t_first=float(t_first), t_last=float(t_last))
