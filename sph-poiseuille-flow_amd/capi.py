@@ -265,43 +265,22 @@ class Batch:
         self._flow_stats = None
 
     def flow_stats_reset(self):
-        self._flow_stats_on()
+        _stats_on(self._flow_stats, "batch")
         check(lib().sphx_batch_flow_stats_reset(self._h))
 
     def flow_stats_sample(self):
         """Add one sample of every member's current state (what download() returns) now, whatever the gating."""
-        self._flow_stats_on()
+        _stats_on(self._flow_stats, "batch")
         check(lib().sphx_batch_flow_stats_sample(self._h))
 
     def flow_stats_sums(self, band=0) -> list:
         """One dict per member in the format of Context.flow_stats_sums, from one read of all members."""
-        n_bins, n_bands = self._flow_stats_on()
-        if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 0 <= band < n_bands:
-            raise SphxError(SPHX_ERR_ARG, "SPHX:Stats:band", f"band must be an integer in 0..{n_bands - 1}")
-        m = self.n_members
-        arrs = [np.zeros(m * n_bins) for _ in range(5)]
-        ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
-        nb = C.c_int(0)
-        check(lib().sphx_batch_flow_stats_read(self._h, C.c_int(int(band)), C.c_int(n_bins), C.byref(nb),
-                                               *[ptr(a) for a in arrs], ns.ctypes.data_as(C.POINTER(C.c_int64)), ptr(t0),
-                                               ptr(t1)))
-        assert nb.value == n_bins, (nb.value, n_bins)
-        out = []
-        for k in range(m):
-            d = {f: a[k * n_bins:(k + 1) * n_bins].copy() for f, a in zip(("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2"), arrs)}
-            d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
-            out.append(d)
-        return out
+        return _flow_stats_read("sphx_batch_flow_stats_read", self._h, _stats_on(self._flow_stats, "batch"), band,
+                                self.n_members)
 
     def flow_stats(self, band=0) -> list:
         """One profile.flow_stats_profile dict per member."""
         return [flow_stats_profile(self.params[0].DH, **s) for s in self.flow_stats_sums(band)]
-
-    def _flow_stats_on(self):
-        if self._flow_stats is None:
-            raise SphxError(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this batch")
-        return self._flow_stats
-
 
 class Context:
     """Device-resident simulation state (sphx_ctx)."""
@@ -432,37 +411,22 @@ class Context:
         self._flow_stats = None
 
     def flow_stats_reset(self):
-        self._flow_stats_on()
+        _stats_on(self._flow_stats, "context")
         check(lib().sphx_ctx_flow_stats_reset(self._h))
 
     def flow_stats_sample(self):
         """Add one sample of the current state (what download() returns) now, whatever the gating."""
-        self._flow_stats_on()
+        _stats_on(self._flow_stats, "context")
         check(lib().sphx_ctx_flow_stats_sample(self._h))
 
     def flow_stats_sums(self, band=0) -> dict:
         """The raw sums of one band: count, sum_ux, sum_ux2, sum_uy, sum_uy2 [n_bins], n_samples, t_first, t_last."""
-        n_bins, n_bands = self._flow_stats_on()
-        if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or not 0 <= band < n_bands:
-            raise SphxError(SPHX_ERR_ARG, "SPHX:Stats:band", f"band must be an integer in 0..{n_bands - 1}")
-        arrs = [np.zeros(n_bins) for _ in range(5)]
-        nb, ns, t0, t1 = C.c_int(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-        check(lib().sphx_ctx_flow_stats_read(self._h, C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), *[ptr(a) for a in arrs],
-                                             C.byref(ns), C.byref(t0), C.byref(t1)))
-        assert nb.value == n_bins, (nb.value, n_bins)
-        out = dict(zip(("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2"), arrs))
-        out.update(n_samples=ns.value, t_first=t0.value, t_last=t1.value)
-        return out
+        return _flow_stats_read("sphx_ctx_flow_stats_read", self._h, _stats_on(self._flow_stats, "context"), band, 1)[0]
 
     def flow_stats(self, band=0) -> dict:
         """Time-averaged profile of one band (profile.flow_stats_profile): y_mid, count, u_mean, u_std, uy_mean, uy_std,
         n_samples, t_first, t_last (+ the raw sums).  Empty bins give NaN means."""
         return flow_stats_profile(self.params.DH, **self.flow_stats_sums(band))
-
-    def _flow_stats_on(self):
-        if self._flow_stats is None:
-            raise SphxError(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this context")
-        return self._flow_stats
 
     # ---- step history (include/sphx.h section 2d): wall shear, energy, bulk velocity, dt and vmax per step, recorded on the device ----
     def history_enable(self, every=1, capacity=65536, t_from=0.0):
@@ -505,17 +469,17 @@ class Context:
         self._field_map = None
 
     def field_map_reset(self):
-        self._field_map_on()
+        _field_on(self._field_map)
         check(lib().sphx_ctx_field_map_reset(self._h))
 
     def field_map_sample(self):
         """Add one sample of the current state (what download() returns) now, whatever the gating."""
-        self._field_map_on()
+        _field_on(self._field_map)
         check(lib().sphx_ctx_field_map_sample(self._h))
 
     def field_map_sums(self) -> dict:
         """The raw planes count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2 as [ny, nx] arrays, plus n_samples, t_first, t_last."""
-        nx, ny = self._field_map_on()
+        nx, ny = _field_on(self._field_map)
         arrs = [np.zeros(nx * ny) for _ in FIELD_MAP_PLANES]
         gx, gy, ns, t0, t1 = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
         check(lib().sphx_ctx_field_map_read(self._h, C.c_int(nx * ny), C.byref(gx), C.byref(gy), *[ptr(a) for a in arrs],
@@ -531,11 +495,6 @@ class Context:
         [ny, nx] arrays (NaN where count == 0), n_samples, t_first, t_last."""
         return field_map_means(self.params.DL, self.params.DH, **self.field_map_sums())
 
-    def _field_map_on(self):
-        if self._field_map is None:
-            raise SphxError(SPHX_ERR_STATE, "SPHX:Field:disabled", "the field map is not enabled on this context")
-        return self._field_map
-
     def profile_enable(self, on=True):
         check(lib().sphx_ctx_profile_enable(self._h, C.c_int(1 if on else 0)))
 
@@ -549,32 +508,88 @@ class Context:
         return {names[k].decode(): dict(avg_ms=avg[k], launches=cnt[k]) for k in range(min(n.value, cap))}
 
 
-def flow_stats_config(n_bins=0, every=1, t_from=0.0, bands=()) -> SphxFlowStatsConfig:
-    """Checked sphx_flow_stats_config; raises SphxError(SPHX:Stats:config) before anything reaches the device."""
-    def bad(msg):
-        return SphxError(SPHX_ERR_ARG, "SPHX:Stats:config", msg)
+def _enabled(state, stem, text):
+    """state, what a sampler's enable left in the wrapper; SPHX:<stem>:disabled while it is off (None)."""
+    if state is None:
+        raise SphxError(SPHX_ERR_STATE, f"SPHX:{stem}:disabled", text)
+    return state
 
-    def is_int(v):
-        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
-    if not is_int(n_bins) or n_bins < 0:
-        raise bad("n_bins must be an integer >= 0 (0 = the reference's profile bins)")
-    if not is_int(every) or every < 1:
+def _stats_on(state, where):
+    return _enabled(state, "Stats", f"flow statistics are not enabled on this {where}")
+
+
+def _field_on(state):
+    return _enabled(state, "Field", "the field map is not enabled on this context")
+
+
+def _flow_stats_read(read, handle, enabled, band, m) -> list:
+    """One call of `read` (sphx_ctx_ / sphx_batch_flow_stats_read) for band `band` of m channels -> a dict per channel: count, sum_ux,
+    sum_ux2, sum_uy, sum_uy2 [n_bins], n_samples, t_first, t_last."""
+    n_bins, n_bands = enabled
+    if not _is_int(band) or not 0 <= band < n_bands:
+        raise SphxError(SPHX_ERR_ARG, "SPHX:Stats:band", f"band must be an integer in 0..{n_bands - 1}")
+    arrs = [np.zeros(m * n_bins) for _ in range(5)]
+    ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
+    nb = C.c_int(0)
+    check(getattr(lib(), read)(handle, C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), *[ptr(a) for a in arrs],
+               ns.ctypes.data_as(C.POINTER(C.c_int64)), ptr(t0), ptr(t1)))
+    assert nb.value == n_bins, (nb.value, n_bins)
+    out = []
+    for k in range(m):
+        d = {f: a[k * n_bins:(k + 1) * n_bins].copy() for f, a in zip(("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2"), arrs)}
+        d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
+        out.append(d)
+    return out
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _config_error(stem):
+    """bad(msg) -> the SPHX:<stem>:config error of a validator."""
+    return lambda msg: SphxError(SPHX_ERR_ARG, f"SPHX:{stem}:config", msg)
+
+
+def _check_every(every, bad) -> int:
+    if not _is_int(every) or every < 1:
         raise bad("every must be an integer >= 1")
+    return int(every)
+
+
+def _check_t_from(t_from, bad, finite=False, not_a_number="t_from must be a number") -> float:
+    """t_from as a float: never NaN; finite: not infinite either (the history's records carry it)."""
     try:
         t_from = float(t_from)
-        bands = [tuple(float(v) for v in b) for b in bands]
     except (TypeError, ValueError):
-        raise bad("t_from must be a number and bands a sequence of (x_centre, half_width) pairs") from None
+        raise bad(not_a_number) from None
+    if finite and not np.isfinite(t_from):
+        raise bad("t_from must be finite")
     if np.isnan(t_from):
         raise bad("t_from must not be NaN")
+    return t_from
+
+
+def flow_stats_config(n_bins=0, every=1, t_from=0.0, bands=()) -> SphxFlowStatsConfig:
+    """Checked sphx_flow_stats_config; raises SphxError(SPHX:Stats:config) before anything reaches the device."""
+    bad = _config_error("Stats")
+    not_numbers = "t_from must be a number and bands a sequence of (x_centre, half_width) pairs"
+    if not _is_int(n_bins) or n_bins < 0:
+        raise bad("n_bins must be an integer >= 0 (0 = the reference's profile bins)")
+    every = _check_every(every, bad)
+    try:
+        bands = [tuple(float(v) for v in b) for b in bands]
+    except (TypeError, ValueError):
+        raise bad(not_numbers) from None
+    t_from = _check_t_from(t_from, bad, not_a_number=not_numbers)
     if len(bands) > 2 or any(len(b) != 2 for b in bands):
         raise bad("at most two bands, each (x_centre, half_width)")
     if any(not (np.isfinite(x) and np.isfinite(hw) and hw >= 0.0) for x, hw in bands):
         raise bad("band centres must be finite and half-widths finite and >= 0")
     if n_bins * (len(bands) + 1) > 1536:
         raise bad("n_bins * (number of bands + 1) must not exceed 1536")
-    cfg = SphxFlowStatsConfig(n_bins=int(n_bins), every=int(every), t_from=t_from, n_bands=len(bands))
+    cfg = SphxFlowStatsConfig(n_bins=int(n_bins), every=every, t_from=t_from, n_bands=len(bands))
     for k, (x, hw) in enumerate(bands):
         cfg.band_x[k], cfg.band_hw[k] = x, hw
     return cfg
@@ -582,23 +597,11 @@ def flow_stats_config(n_bins=0, every=1, t_from=0.0, bands=()) -> SphxFlowStatsC
 
 def history_config(every=1, capacity=65536, t_from=0.0) -> SphxHistoryConfig:
     """Checked sphx_history_config; raises SphxError(SPHX:History:config) before anything reaches the device."""
-    def bad(msg):
-        return SphxError(SPHX_ERR_ARG, "SPHX:History:config", msg)
-
-    def is_int(v):
-        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
-    if not is_int(every) or every < 1:
-        raise bad("every must be an integer >= 1")
-    if not is_int(capacity) or not 1 <= capacity <= 1 << 22:
+    bad = _config_error("History")
+    every = _check_every(every, bad)
+    if not _is_int(capacity) or not 1 <= capacity <= 1 << 22:
         raise bad("capacity must be an integer in 1 .. 1 << 22")
-    try:
-        t_from = float(t_from)
-    except (TypeError, ValueError):
-        raise bad("t_from must be a number") from None
-    if not np.isfinite(t_from):
-        raise bad("t_from must be finite")
-    return SphxHistoryConfig(every=int(every), capacity=int(capacity), t_from=t_from)
+    return SphxHistoryConfig(every=every, capacity=int(capacity), t_from=_check_t_from(t_from, bad, finite=True))
 
 
 def field_map_shape(prm, nx=0, ny=0):
@@ -609,28 +612,17 @@ def field_map_shape(prm, nx=0, ny=0):
 
 def field_map_config(nx=0, ny=0, every=1, t_from=0.0, with_walls=False) -> SphxFieldMapConfig:
     """Checked sphx_field_map_config; raises SphxError(SPHX:Field:config) before anything reaches the device."""
-    def bad(msg):
-        return SphxError(SPHX_ERR_ARG, "SPHX:Field:config", msg)
-
-    def is_int(v):
-        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-
+    bad = _config_error("Field")
     for name, v in (("nx", nx), ("ny", ny)):
-        if not is_int(v) or v < 0 or v == 1:
+        if not _is_int(v) or v < 0 or v == 1:
             raise bad(f"{name} must be an integer >= 2, or 0 for the reference's shape")
     if nx * ny > 1 << 25:
         raise bad("nx * ny must not exceed 1 << 25 nodes")
-    if not is_int(every) or every < 1:
-        raise bad("every must be an integer >= 1")
-    try:
-        t_from = float(t_from)
-    except (TypeError, ValueError):
-        raise bad("t_from must be a number") from None
-    if np.isnan(t_from):
-        raise bad("t_from must not be NaN")
-    if not (isinstance(with_walls, (bool, np.bool_)) or (is_int(with_walls) and with_walls in (0, 1))):
+    every = _check_every(every, bad)
+    t_from = _check_t_from(t_from, bad)
+    if not (isinstance(with_walls, (bool, np.bool_)) or (_is_int(with_walls) and with_walls in (0, 1))):
         raise bad("with_walls must be a bool (or 0 / 1)")
-    return SphxFieldMapConfig(nx=int(nx), ny=int(ny), every=int(every), with_walls=int(with_walls), t_from=t_from)
+    return SphxFieldMapConfig(nx=int(nx), ny=int(ny), every=every, with_walls=int(with_walls), t_from=t_from)
 
 
 def history_dict(records, n_dropped=0) -> dict:

@@ -227,8 +227,7 @@ FlowStats &batch_stats(sphx_batch *b, bool need_on)
 {
     require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
     FlowStats &f = b->mem[0]->fstats;
-    if (need_on && !f.on)
-        throw Error(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this batch");
+    sampler_check(kStatsNames, false, f.on, need_on, "batch");
     return f;
 }
 
@@ -460,11 +459,8 @@ SPHX_EXPORT int sphx_batch_graph_stats(sphx_batch *b, int64_t *slots_replayed, i
 SPHX_EXPORT int sphx_batch_flow_stats_enable(sphx_batch *b, const sphx_flow_stats_config *cfg)
 {
     SPHX_TRY
-    FlowStats &f = batch_stats(b, false);
-    FlowStats checked;
-    checked.configure(b->mem[0]->prm, cfg);  // (bins and bands come from the shared geometry)
-    stats_off(f, b->sched, b->stream);
-    f.enable(checked, b->M, b->stream);  // (out of device memory: the batch goes on without statistics)
+    // (bins and bands come from the shared geometry; out of device memory: the batch goes on without statistics)
+    stats_enable(batch_stats(b, false), b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -473,7 +469,7 @@ SPHX_EXPORT int sphx_batch_flow_stats_disable(sphx_batch *b)
 {
     SPHX_TRY
     FlowStats &f = batch_stats(b, false);
-    if (f.on) stats_off(f, b->sched, b->stream);
+    if (f.on) sampler_off(f, b->sched, b->stream);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -483,8 +479,7 @@ SPHX_EXPORT int sphx_batch_flow_stats_reset(sphx_batch *b)
     SPHX_TRY
     FlowStats &f = batch_stats(b, true);
     batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
-    f.zero(b->stream);
-    SPHX_HIP(hipStreamSynchronize(b->stream));
+    sampler_zero(f, b->stream);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -493,10 +488,8 @@ SPHX_EXPORT int sphx_batch_flow_stats_sample(sphx_batch *b)
 {
     SPHX_TRY
     batch_stats(b, true);
-    batch_settle(b);  // every member at the batch's phase: the state sphx_batch_download would return
-    const FluidSet fs = b->mem[0]->view(b->sched.cur, b->sched.lay);
-    launch_flow_stats(b->mem[0], 0, fs.pos, fs.vel, 0);
-    SPHX_HIP(hipGetLastError());
+    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
+    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_flow_stats);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -1,7 +1,7 @@
-// sphx_field_map.hpp -- velocity-field maps of a resident context (include/sphx.h section 2e): one self-skipping launch at
-// the end of every step slot interpolates the velocity of the state the step left onto a regular nx x ny grid of nodes
+// sphx_field_map.hpp -- velocity-field maps of a resident context (include/sphx.h section 2e): a slot sampler
+// (sphx_slot_sample.hpp) that interpolates the velocity of the state the step left onto a regular nx x ny grid of nodes
 // (both ends included in x and y, the shape of panel (b) of SPH_Poiseuille_postprocess.m:184-201 by default) and adds
-// the sample to running sums per node, without a host round trip.
+// the sample to running sums per node.
 //
 // One sample at a node is Shepard interpolation with the cubic spline of spline_W over every particle within 2h
 // (minimum image in x, no lower cut): S0 = sum W, S1 = sum W u_x, S2 = sum W u_y, and S1 / S0, S2 / S0 where S0 > 0.
@@ -27,7 +27,7 @@
 // written by thread 0 of workgroup 0 alone.
 #pragma once
 #include "../../include/sphx.h"
-#include "sphx_kernels.hpp"
+#include "sphx_slot_sample.hpp"
 
 namespace sphx {
 
@@ -97,25 +97,13 @@ __device__ __forceinline__ void field_columns(const Grid &g, const KernelConst &
     }
 }
 
-// q: parity of the step slot this launch closes (in-loop samples: the slot ran iff run[q] is still set -- a clock update
-// only ever writes the flag of the NEXT slot).  The launch sits behind the slot's clock update, so clk->step / clk->t are
-// those of the step just completed; s is the state it left (pos, vel and the cell ranges of the layout it is stored in).
+// q: parity of the step slot this launch closes; s is the state the step left (pos, vel and the cell ranges of the layout it
+// is stored in).
 __global__ __launch_bounds__(kFieldBlock) void k_field_map(const Clock *clk, int q, Grid g, Phys ph, FluidSet s, Walls w,
                                                            FieldMapArgs a)
 {
-    if (a.every > 0) {
-        if (!clk->run[q]) return;
-        if (clk->step % a.every != 0) return;
-        if (!(clk->t >= a.t_from)) return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {  // the head, by one thread: plain vector stores
-        FieldMapHead *h = a.head;
-        const double t_now = clk->t;
-        const long long ns = h->n_samples;
-        if (ns == 0) h->t_first = t_now;
-        h->t_last = t_now;
-        h->n_samples = ns + 1;
-    }
+    if (!sample_due(clk, q, a.every, a.t_from)) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) note_sample(a.head, clk->t);  // the head, by one thread: plain vector stores
     const int lane = (int)threadIdx.x & 63;
     const int tile = (int)blockIdx.x * (kFieldBlock / 64) + ((int)threadIdx.x >> 6);
     if (tile >= a.n_tiles) return;

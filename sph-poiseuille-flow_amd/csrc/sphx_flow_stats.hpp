@@ -1,7 +1,6 @@
 // sphx_flow_stats.hpp -- time-averaged velocity profiles of a resident context (include/sphx.h section 2a, "flow
-// statistics") and of every member of a batch (section 2c, k_flow_stats_b): one self-skipping launch at the end of every
-// step slot bins the state the step left into the reference's profile bins (SPH_Poiseuille.m:579-605) and adds it to
-// running sums, without a host round trip.
+// statistics") and of every member of a batch (section 2c, k_flow_stats_b): a slot sampler (sphx_slot_sample.hpp) that
+// bins the state the step left into the reference's profile bins (SPH_Poiseuille.m:579-605) and adds it to running sums.
 //
 // Determinism: a sample is summed EXACTLY, in int64 fixed point -- integer adds do not depend on the order they arrive
 // in, so neither the particle order (layouts, re-binnings) nor the dispatch order of the workgroups can change a bit.
@@ -9,10 +8,10 @@
 // n <= 2^L particles and |u| <= 2^e, u * 2^(62-L-e) and u^2 * 2^(62-L-2e) are below 2^(62-L), so no sum of n of them can
 // overflow.  A |u| above the bound (only a non-finite state can have one) raises a sticky flag and the read fails.
 // Each workgroup keeps the sample's counters in LDS, adds every non-zero one to the global integer sums with one
-// atomic, and the last workgroup out (ticket, agent-scope release / acquire) converts the integer sums to double, adds
-// them to the running sums bin by bin and clears them for the next sample.
+// atomic, and the last workgroup out (last_out_fenced) converts the integer sums to double, adds them to the running
+// sums bin by bin and clears them for the next sample.
 #pragma once
-#include "sphx_kernels.hpp"
+#include "sphx_slot_sample.hpp"
 
 namespace sphx {
 
@@ -107,18 +106,12 @@ struct StatsMember {
     __device__ FlowStatsHead *head(const FlowStatsArgs &a) const { return a.head + m; }
 };
 
-// q: parity of the step slot this launch closes (in-loop samples: the slot ran iff run[q] is still set -- a clock update
-// only ever writes the flag of the NEXT slot).  The launch sits behind the slot's clock update, so clk->step / clk->t are
-// those of the step just completed.  The sample of one channel, on clock clk, shared by the gridDim.x workgroups of a grid
+// The sample of one channel closing the step slot of parity q, on clock clk, shared by the gridDim.x workgroups of a grid
 // row; `at` says where the channel's arrays are: a's own pointers (StatsOwn) or a batch member's blocks (StatsMember).
 template <typename At>
 __device__ __forceinline__ void flow_stats_body(const Clock *clk, int q, const FlowStatsArgs &a, const At &at)
 {
-    if (a.every > 0) {
-        if (!clk->run[q]) return;
-        if (clk->step % a.every != 0) return;
-        if (!(clk->t >= a.t_from)) return;
-    }
+    if (!sample_due(clk, q, a.every, a.t_from)) return;
     const int n = clk->n;
     const double vmax = clk->vmax, t_now = clk->t;
     extern __shared__ unsigned long long s_cnt[];  // [n_bands][n_bins][kStatsFields]
@@ -154,43 +147,24 @@ __device__ __forceinline__ void flow_stats_body(const Clock *clk, int q, const F
         const int s = f == 0 ? 0 : ((f & 1) ? s1 : s2);
         at.dsum(a)[k] += ldexp((double)(long long)v, -s);
     };
-    auto finish_head = [&]() {
-        FlowStatsHead *h = at.head(a);
-        if (h->n_samples == 0) h->t_first = t_now;
-        h->t_last = t_now;
-        h->n_samples += 1;
-    };
     if (gridDim.x == 1) {  // small channels: one workgroup holds the whole sample -- no global sums, no ticket
         for (int k = threadIdx.x; k < nc; k += kStatsBlock)
             if (s_cnt[k]) finish(k, s_cnt[k]);
-        if (threadIdx.x == 0) finish_head();
+        if (threadIdx.x == 0) note_sample(at.head(a), t_now);
         return;
     }
     for (int k = threadIdx.x; k < nc; k += kStatsBlock) {
         const unsigned long long v = s_cnt[k];
         if (v) atomicAdd(at.isum(a) + k, v);
     }
-    // last workgroup out: every wave drains its adds, one release at agent scope, then the ticket
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int drawn = __hip_atomic_fetch_add(&at.head(a)->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = drawn == (int)gridDim.x - 1 ? 1 : 0;
-        if (s_last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-    }
-    __syncthreads();
+    last_out_fenced(&at.head(a)->ticket, s_last);
     if (!s_last) return;
     for (int k = threadIdx.x; k < nc; k += kStatsBlock) {
         const unsigned long long v = atomicExch(at.isum(a) + k, 0ull);
         if (v) finish(k, v);
     }
     if (threadIdx.x == 0) {
-        finish_head();
+        note_sample(at.head(a), t_now);
         __hip_atomic_store(&at.head(a)->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }

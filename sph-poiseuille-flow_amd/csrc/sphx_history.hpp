@@ -1,22 +1,22 @@
-// sphx_history.hpp -- the step history of a resident context (include/sphx.h section 2d): one self-skipping launch at the
-// end of every step slot reduces the state the step left to one record of kHistoryFields doubles -- step, t, dt, vmax of the
-// device clock, the wall shear of SPH_Poiseuille.m:281-283, the kinetic energy and the bulk velocity -- and appends it to a
-// record buffer in device memory, without a host round trip.
+// sphx_history.hpp -- the step history of a resident context (include/sphx.h section 2d): a slot sampler
+// (sphx_slot_sample.hpp) that reduces the state the step left to one record of kHistoryFields doubles -- step, t, dt, vmax of
+// the device clock, the wall shear of SPH_Poiseuille.m:281-283, the kinetic energy and the bulk velocity -- and appends it to
+// a record buffer in device memory.
 //
 // The wall-shear term is k_wall_shear's, term for term (sphx_kernels.hpp; kept as a copy here so that the monitor's kernel
 // stays what it is): the wall cells around the cell a particle was binned into, new pos / vel, Vol / B of the step just
-// finished.  Where those records are is the launch's business (launch_slot_history): the buffers of the finished step's
+// finished.  Where those records are is the launch's business (launch_history, sphx_samplers.hpp): the buffers of the finished step's
 // parity, read through src_of when the slot re-binned -- known at capture time on the static schedule, Clock::fresh on a
 // dynamic one.
 //
 // Determinism: no floating-point atomics.  A workgroup takes a contiguous run of slots, reduces inside the wave with
-// shuffles and across its waves in LDS (wave order), and leaves four partial sums; the last workgroup out (ticket,
-// agent-scope release / acquire as in k_flow_stats) adds the partials in index order and writes the record.  Two identical
+// shuffles and across its waves in LDS (wave order), and leaves four partial sums; the last workgroup out
+// (last_out_fenced) adds the partials in index order and writes the record.  Two identical
 // runs give identical bits; another layout of the particles (re-binning phase, host chunking) changes the summation order
 // only.  A channel small enough for one workgroup finishes without partials and ticket.
 #pragma once
 #include "../../include/sphx.h"
-#include "sphx_kernels.hpp"
+#include "sphx_slot_sample.hpp"
 
 namespace sphx {
 
@@ -87,15 +87,11 @@ __device__ __forceinline__ void history_wall_terms(const Grid &g, const Phys &ph
     });
 }
 
-// q: parity of the step slot this launch closes (the slot ran iff run[q] is still set -- a clock update only ever writes the
-// flag of the NEXT slot).  The launch sits behind the slot's clock update, so clk->step / t / dt_last / vmax are those of the
-// step just completed; s is the state it left, t holds its Vol / B.
+// q: parity of the step slot this launch closes; s is the state the step left, t holds its Vol / B.
 __global__ __launch_bounds__(kHistoryBlock) void k_step_history(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
                                                                  FluidTmp t, Walls w, HistoryArgs a)
 {
-    if (!clk->run[q]) return;
-    if (clk->step % a.every != 0) return;
-    if (!(clk->t >= a.t_from)) return;
+    if (!slot_due(clk, q, a.every, a.t_from)) return;
     const int n = clk->n;
     const bool use_src = a.src == kHistoryByClock ? clk->fresh != 0 : a.src == kHistorySrcOf;
     const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;  // a contiguous run of slots per workgroup
@@ -130,20 +126,7 @@ __global__ __launch_bounds__(kHistoryBlock) void k_step_history(const Clock *clk
         for (int k = 0; k < kWaves; ++k) tot += s_wave[threadIdx.x][k];
     if (gridDim.x > 1) {
         if (threadIdx.x < kHistorySums) a.part[(size_t)blockIdx.x * kHistorySums + threadIdx.x] = tot;
-        // last workgroup out: the partials drained, one release at agent scope, then the ticket
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int drawn = __hip_atomic_fetch_add(&a.head->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = drawn == (int)gridDim.x - 1 ? 1 : 0;
-            if (s_last) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        }
-        __syncthreads();
+        last_out_fenced(&a.head->ticket, s_last);
         if (!s_last) return;
         if (threadIdx.x < kHistorySums) {
             tot = 0.0;

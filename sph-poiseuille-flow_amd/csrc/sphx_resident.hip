@@ -14,9 +14,7 @@
 
 #include "sphx_common.hpp"
 #include "sphx_kernels.hpp"
-#include "sphx_flow_stats.hpp"
-#include "sphx_history.hpp"
-#include "sphx_field_map.hpp"
+#include "sphx_sampler_state.hpp"
 
 namespace sphx {
 
@@ -112,30 +110,6 @@ struct Schedule {
             if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
         graphs.clear();
     }
-};
-
-// Flow statistics (sphx_ctx_flow_stats_*, sphx_batch_flow_stats_*; sphx_flow_stats.hpp) of a context or of the M members of
-// a batch: one configuration, running sums and heads in M blocks (member m's sums at m * block(), its head at m).  While they
-// are on, every step slot ends with k_flow_stats (launch_slot_stats).
-struct FlowStats {
-    bool on = false;
-    int members = 1;
-    sphx_flow_stats_config cfg{};
-    int n_bins = 0, n_bands = 1;  // (n_bands counts band 0)
-    DevBuf<unsigned long long> isum;
-    DevBuf<double> dsum;
-    DevBuf<FlowStatsHead> head;
-
-    size_t row() const { return (size_t)n_bins * kStatsFields; }  // the sums of one band ...
-    size_t block() const { return (size_t)n_bands * row(); }      // ... and of one member
-    size_t shmem() const { return block() * sizeof(unsigned long long); }  // the LDS counters of a workgroup
-
-    void configure(const sphx_params &prm, const sphx_flow_stats_config *cfg);
-    void enable(const FlowStats &checked, int M, hipStream_t st);
-    void zero(hipStream_t st) { isum.zero(st); dsum.zero(st); head.zero(st); }
-    void release() { isum.release(); dsum.release(); head.release(); }
-    void read(hipStream_t st, int band, int stride, bool sums, double *const out[kStatsFields], int64_t *n_samples, double *t_first,
-              double *t_last) const;
 };
 
 }  // namespace sphx
@@ -271,25 +245,10 @@ struct sphx_ctx {
     bool coded_lists = false;    // ... and the lists name tile slots instead of index differences (kSlotCodes, sphx_kernels.hpp)
     bool tail_clock = false;     // move steps carry their clock update in a tail workgroup of pass E (small channels)
 
+    // slot samplers (sphx_sampler_state.hpp): while one is on, every step slot ends with its launch
     FlowStats fstats;  // (of a batch: member 0's serves every member, the other members' stay off)
-
-    // Step history (sphx_ctx_history_*, sphx_history.hpp): when on, every step slot ends with k_step_history
-    struct History {
-        bool on = false;
-        sphx_history_config cfg{};
-        DevBuf<double> records, part;
-        DevBuf<HistoryHead> head;
-    } hist;
-
-    // Velocity-field map (sphx_ctx_field_map_*, sphx_field_map.hpp): when on, every step slot ends with k_field_map
-    struct FieldMap {
-        bool on = false;
-        sphx_field_map_config cfg{};
-        int nx = 0, ny = 0;  // the shape in force (cfg.nx / cfg.ny = 0: the reference's)
-        DevBuf<double> planes;
-        DevBuf<FieldMapHead> head;
-        size_t nodes() const { return (size_t)nx * (size_t)ny; }
-    } fmap;
+    History hist;
+    FieldMap fmap;
 
     // Member of a batch (sphx_batch_*): the device arrays are this member's blocks of batch-wide allocations (BatchArena)
     sphx::BatchArena *arena = nullptr;
@@ -900,82 +859,6 @@ void launch_step_dyn(sphx_ctx *c, int q)
     launch(c, "k_copyback", k_copyback, g1, bp, (const Clock *)clk, qf, cb);
 }
 
-// k_flow_stats on (pos, vel) -- of a batch: member 0's -- into c->fstats: every >= 1 = the in-loop sample closing step slot q,
-// 0 = a sample of the state now
-void launch_flow_stats(sphx_ctx *c, int q, const double2 *pos, const double2 *vel, int every)
-{
-    const FlowStats &f = c->fstats;
-    FlowStatsArgs a{};
-    a.pos = pos; a.vel = vel;
-    a.isum = f.isum.get(); a.dsum = f.dsum.get(); a.head = f.head.get();
-    a.DH = c->prm.DH; a.bin_w = c->prm.DH / f.n_bins; a.DL = c->prm.DL;
-    a.t_from = f.cfg.t_from;
-    for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
-    a.n_bins = f.n_bins; a.n_bands = f.n_bands;
-    a.every = every;
-    // workgroups of one channel's sample
-    const unsigned blocks = std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kStatsBlock * kStatsPerThread), 1u, (unsigned)kStatsMaxBlocks);
-    launch_forms(c, "k_flow_stats", Forms{k_flow_stats, k_flow_stats_b}, blocks, kStatsBlock, f.shmem(), q, a);
-}
-
-// the state step slot q leaves is in S[1-q] on every schedule (a re-binning step reorders into S[1-q] too, a dynamic
-// context copies back into it); the launch comes after the slot's clock update, whichever kernel carries it
-void launch_slot_stats(sphx_ctx *c, int q)
-{
-    if (!c->fstats.on) return;
-    launch_flow_stats(c, q, c->fpos_[1 - q].get(), c->fvel_[1 - q].get(), c->fstats.cfg.every);
-}
-
-// k_step_history behind step slot q, which ran on layout l: the state it left is S[1-q] -- in the other layout when the slot
-// re-binned -- and Vol / B of the finished step are where sphx_ctx_monitor looks them up after it: the record buffers of the
-// step's parity (fuse_ea), in the order of the layout the step ran in, so read through src_of when the slot re-binned.  The
-// static schedule knows that when the launch is made (or captured); a dynamic context re-bins in place and says so in
-// Clock::fresh.
-void launch_slot_history(sphx_ctx *c, int q, int l, bool rebuild)
-{
-    const sphx_ctx::History &h = c->hist;
-    if (!h.on) return;
-    single_form_only(c, "k_step_history");
-    const FluidSet s = c->dyn ? c->view(1 - q, 0) : c->view(1 - q, rebuild ? 1 - l : l);
-    HistoryArgs a{};
-    a.records = h.records.get(); a.part = h.part.get(); a.head = h.head.get();
-    a.t_from = h.cfg.t_from; a.capacity = h.cfg.capacity; a.every = h.cfg.every;
-    a.src = c->dyn ? kHistoryByClock : (rebuild ? kHistorySrcOf : kHistoryInPlace);
-    const unsigned blocks =
-        std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kHistoryBlock * kHistoryPerThread), 1u, (unsigned)kHistoryMaxBlocks);
-    launch(c, "k_step_history", k_step_history, dim3(blocks), dim3(kHistoryBlock), (const Clock *)c->clock.get(), q, c->grid,
-           c->phys, s, c->tmp_par[c->fuse_ea ? q : 0], c->walls, a);
-}
-
-// k_field_map on state s (pos, vel and the cell ranges of the layout it is stored in) into c->fmap: every >= 1 = the in-loop
-// sample closing step slot q, 0 = a sample of the state now
-void launch_field_map(sphx_ctx *c, int q, const FluidSet &s, int every)
-{
-    const sphx_ctx::FieldMap &f = c->fmap;
-    single_form_only(c, "k_field_map");
-    FieldMapArgs a{};
-    a.planes = f.planes.get(); a.head = f.head.get();
-    a.step_x = c->prm.DL / (f.nx - 1); a.step_y = c->prm.DH / (f.ny - 1);
-    a.dp2 = c->prm.dp * c->prm.dp;
-    a.t_from = f.cfg.t_from;
-    a.nx = f.nx; a.ny = f.ny;
-    a.tiles_y = (int)div_up((size_t)f.ny, (size_t)kFieldTile);
-    a.n_tiles = (int)div_up((size_t)f.nx, (size_t)kFieldTile) * a.tiles_y;
-    a.every = every;
-    a.with_walls = f.cfg.with_walls && c->nw > 0 ? 1 : 0;
-    const unsigned blocks = div_up((size_t)a.n_tiles, (size_t)(kFieldBlock / 64));
-    launch(c, "k_field_map", k_field_map, dim3(blocks), dim3(kFieldBlock), (const Clock *)c->clock.get(), q, c->grid, c->phys, s,
-           c->walls, a);
-}
-
-// k_field_map behind step slot q, which ran on layout l: the view launch_slot_history picks -- the state the slot left is
-// S[1-q], in the other layout when the slot re-binned (a dynamic context re-bins in place)
-void launch_slot_field(sphx_ctx *c, int q, int l, bool rebuild)
-{
-    if (!c->fmap.on) return;
-    launch_field_map(c, q, c->dyn ? c->view(1 - q, 0) : c->view(1 - q, rebuild ? 1 - l : l), c->fmap.cfg.every);
-}
-
 // host-side bookkeeping of one step slot
 void track_step(sphx_ctx *c)
 {
@@ -1087,16 +970,13 @@ void enqueue_slots(Schedule &s, hipStream_t st, int K, int per_graph, int64_t sl
 
 // ---- a context's side of it ----
 
-// one step slot of a context: the static schedule's launches or a dynamic context's, then the slot's k_flow_stats and
-// k_step_history and k_field_map (each only where it is on)
+// one step slot of a context: the static schedule's launches or a dynamic context's, then the slot samplers that are on
 auto ctx_slot(sphx_ctx *c)
 {
     return [c](int q, int l, int p, bool rebuild) {
         if (c->dyn) launch_step_dyn(c, q);
         else launch_step(c, q, l, p, rebuild);
-        launch_slot_stats(c, q);
-        launch_slot_history(c, q, l, rebuild);
-        launch_slot_field(c, q, l, rebuild);
+        launch_slot_samplers(c, q, l, rebuild);
     };
 }
 
@@ -2115,389 +1995,7 @@ SPHX_EXPORT int sphx_ctx_profile_read(sphx_ctx *c, int capacity, const char **na
     SPHX_CATCH
 }
 
-// ---- flow statistics (sphx_flow_stats.hpp) ----
-namespace {
-
-sphx_ctx *stats_ctx(sphx_ctx *c, bool need_on)
-{
-    require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
-    require(!c->is_slab, "SPHX:Stats:slab", "flow statistics are not available on slab contexts");
-    if (need_on && !c->fstats.on)
-        throw Error(SPHX_ERR_STATE, "SPHX:Stats:disabled", "flow statistics are not enabled on this context");
-    return c;
-}
-
-// the replayed graphs of schedule s carry k_flow_stats (and its arguments) or not: a change of the setting re-captures them
-void stats_drop_graphs(Schedule &s, hipStream_t st)
-{
-    SPHX_HIP(hipStreamSynchronize(st));
-    s.drop_graphs();
-}
-
-void stats_off(FlowStats &f, Schedule &s, hipStream_t st)
-{
-    stats_drop_graphs(s, st);
-    f.on = false;
-    f.release();
-}
-
-}  // namespace
-
-// the checked configuration cfg of channels with parameters prm (cfg, n_bins, n_bands); SPHX:Stats:config errors
-void FlowStats::configure(const sphx_params &prm, const sphx_flow_stats_config *cfg)
-{
-    require(cfg != nullptr, "SPHX:Stats:config", "config must not be NULL");
-    require(cfg->n_bins >= 0, "SPHX:Stats:config", "n_bins must be >= 0 (0 = the reference's profile bins)");
-    require(cfg->every >= 1, "SPHX:Stats:config", "every must be >= 1");
-    require(!std::isnan(cfg->t_from), "SPHX:Stats:config", "t_from must not be NaN");
-    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, "SPHX:Stats:config", "n_bands must be 0, 1 or 2");
-    for (int b = 0; b < cfg->n_bands; ++b)
-        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, "SPHX:Stats:config",
-                "band centres must be finite and half-widths finite and >= 0");
-    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
-    require((int64_t)bins * (cfg->n_bands + 1) <= kStatsMaxBins, "SPHX:Stats:config",
-            "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
-    this->cfg = *cfg;
-    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
-    n_bins = bins;
-    n_bands = cfg->n_bands + 1;
-}
-
-// on, with the checked configuration and zeroed sums for M members; out of device memory: it stays off, with nothing allocated
-void FlowStats::enable(const FlowStats &checked, int M, hipStream_t st)
-{
-    cfg = checked.cfg;
-    n_bins = checked.n_bins;
-    n_bands = checked.n_bands;
-    members = M;
-    try {
-        isum.alloc(block() * M);
-        dsum.alloc(block() * M);
-        head.alloc(M);
-    } catch (...) {
-        release();
-        (void)hipGetLastError();
-        throw;
-    }
-    zero(st);
-    SPHX_HIP(hipStreamSynchronize(st));
-    on = true;
-}
-
-// Band `band` of every member's sums (sums: into out[field][m * stride + bin], where out[field] is given) and the heads
-// (n_samples[m], t_first[m], t_last[m], where given).  SPHX:Stats:range when a member's sticky flag is up.
-void FlowStats::read(hipStream_t st, int band, int stride, bool sums, double *const out[kStatsFields], int64_t *n_samples,
-                     double *t_first, double *t_last) const
-{
-    const int M = members;
-    std::vector<double> host(sums ? (size_t)M * row() : 0);
-    std::vector<FlowStatsHead> h(M);
-    if (sums)  // one copy: a row of every member's block
-        SPHX_HIP(hipMemcpy2DAsync(host.data(), row() * sizeof(double), dsum.get() + (size_t)band * row(), block() * sizeof(double),
-                                  row() * sizeof(double), M, hipMemcpyDeviceToHost, st));
-    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(FlowStatsHead) * M, hipMemcpyDeviceToHost, st));
-    SPHX_HIP(hipStreamSynchronize(st));
-    for (int m = 0; m < M; ++m)
-        if (h[m].range)
-            throw Error(SPHX_ERR_STATE, "SPHX:Stats:range", (M > 1 ? "member " + std::to_string(m) + ": " : std::string()) +
-                                                           "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
-    for (int j = 0; j < kStatsFields; ++j)
-        if (out[j])
-            for (int m = 0; m < M; ++m)
-                for (int k = 0; k < n_bins; ++k) out[j][(size_t)m * stride + k] = host[(size_t)m * row() + (size_t)k * kStatsFields + j];
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int m = 0; m < M; ++m) {
-        if (n_samples) n_samples[m] = h[m].n_samples;
-        if (t_first) t_first[m] = h[m].n_samples ? h[m].t_first : nan;
-        if (t_last) t_last[m] = h[m].n_samples ? h[m].t_last : nan;
-    }
-}
-
-namespace {
-
-// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
-template <typename Settle>
-void stats_read(const FlowStats &f, hipStream_t st, Settle &&settle, int band, int capacity, int *n_bins, double *count, double *sum_ux,
-                double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples, double *t_first, double *t_last)
-{
-    require(band >= 0 && band < f.n_bands, "SPHX:Stats:band", "band must be 0 (whole channel) .. n_bands");
-    double *const out[kStatsFields] = {count, sum_ux, sum_ux2, sum_uy, sum_uy2};
-    bool any = false;
-    for (double *o : out) any = any || o != nullptr;
-    require(!any || capacity >= f.n_bins, "SPHX:Stats:capacity", "capacity is smaller than the number of bins");
-    settle();
-    f.read(st, band, capacity, any, out, n_samples, t_first, t_last);
-    if (n_bins) *n_bins = f.n_bins;
-}
-
-}  // namespace
-
-SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_config *cfg)
-{
-    SPHX_TRY
-    stats_ctx(c, false);
-    FlowStats checked;
-    checked.configure(c->prm, cfg);
-    stats_off(c->fstats, c->sched, c->stream);
-    c->fstats.enable(checked, 1, c->stream);
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_flow_stats_disable(sphx_ctx *c)
-{
-    SPHX_TRY
-    stats_ctx(c, false);
-    if (c->fstats.on) stats_off(c->fstats, c->sched, c->stream);
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_flow_stats_reset(sphx_ctx *c)
-{
-    SPHX_TRY
-    stats_ctx(c, true);
-    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
-    c->fstats.zero(c->stream);
-    SPHX_HIP(hipStreamSynchronize(c->stream));
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_flow_stats_sample(sphx_ctx *c)
-{
-    SPHX_TRY
-    stats_ctx(c, true);
-    settle_owed(c);  // the state sphx_ctx_download would return
-    const FluidSet fs = c->view(c->sched.cur, c->sched.lay);
-    launch_flow_stats(c, 0, fs.pos, fs.vel, 0);
-    SPHX_HIP(hipGetLastError());
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_flow_stats_read(sphx_ctx *c, int band, int capacity, int *n_bins, double *count, double *sum_ux,
-                                         double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples,
-                                         double *t_first, double *t_last)
-{
-    SPHX_TRY
-    stats_ctx(c, true);
-    stats_read(c->fstats, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples,
-               t_first, t_last);
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-// ---- step history (sphx_history.hpp) ----
-namespace {
-
-sphx_ctx *history_ctx(sphx_ctx *c, bool need_on)
-{
-    require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
-    require(!c->is_slab, "SPHX:History:slab", "the step history is not available on slab contexts");
-    if (need_on && !c->hist.on)
-        throw Error(SPHX_ERR_STATE, "SPHX:History:disabled", "the step history is not enabled on this context");
-    return c;
-}
-
-void history_release(sphx_ctx::History &h)
-{
-    h.on = false;
-    h.records.release();
-    h.part.release();
-    h.head.release();
-}
-
-}  // namespace
-
-SPHX_EXPORT int sphx_ctx_history_enable(sphx_ctx *c, const sphx_history_config *cfg)
-{
-    SPHX_TRY
-    history_ctx(c, false);
-    require(cfg != nullptr, "SPHX:History:config", "config must not be NULL");
-    require(cfg->every >= 1, "SPHX:History:config", "every must be >= 1");
-    require(cfg->capacity >= 1 && cfg->capacity <= kHistoryMaxCapacity, "SPHX:History:config", "capacity must be 1 .. 1 << 22 records");
-    require(std::isfinite(cfg->t_from), "SPHX:History:config", "t_from must be finite");
-    stats_drop_graphs(c->sched, c->stream);  // the replayed graphs carry k_step_history (and its arguments) or not
-    sphx_ctx::History &h = c->hist;
-    history_release(h);
-    try {
-        h.records.alloc((size_t)cfg->capacity * kHistoryFields);
-        h.part.alloc((size_t)kHistoryMaxBlocks * kHistorySums);
-        h.head.alloc(1);
-        h.head.zero(c->stream);
-        SPHX_HIP(hipStreamSynchronize(c->stream));
-    } catch (const Error &e) {
-        history_release(h);
-        (void)hipGetLastError();
-        throw Error(SPHX_ERR_ARG, "SPHX:History:config", std::string("the record buffer could not be set up: ") + e.what());
-    }
-    h.cfg = *cfg;
-    h.on = true;
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_history_disable(sphx_ctx *c)
-{
-    SPHX_TRY
-    history_ctx(c, false);
-    if (!c->hist.on) return SPHX_OK;
-    stats_drop_graphs(c->sched, c->stream);
-    history_release(c->hist);
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_history_read(sphx_ctx *c, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain)
-{
-    SPHX_TRY
-    history_ctx(c, true);
-    settle_owed(c);  // (the records of everything enqueued)
-    sphx_ctx::History &h = c->hist;
-    HistoryHead head{};
-    SPHX_HIP(hipMemcpyAsync(&head, h.head.get(), sizeof(head), hipMemcpyDeviceToHost, c->stream));
-    SPHX_HIP(hipStreamSynchronize(c->stream));
-    const long long n = head.n_records;
-    if (n < 0 || n > (long long)h.cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:History:state", "internal: record count out of range");
-    require(records == nullptr || (long long)capacity >= n, "SPHX:History:capacity", "capacity is smaller than the number of records");
-    if (records && n > 0) {
-        SPHX_HIP(hipMemcpyAsync(records, h.records.get(), (size_t)n * kHistoryFields * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        SPHX_HIP(hipStreamSynchronize(c->stream));
-    }
-    if (n_records) *n_records = (int)n;
-    if (n_dropped) *n_dropped = (int64_t)head.n_dropped;
-    if (drain) {
-        h.head.zero(c->stream);
-        SPHX_HIP(hipStreamSynchronize(c->stream));
-    }
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-// ---- velocity-field map (sphx_field_map.hpp) ----
-namespace {
-
-sphx_ctx *field_ctx(sphx_ctx *c, bool need_on)
-{
-    require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
-    require(!c->is_slab, "SPHX:Field:slab", "field maps are not available on slab contexts");
-    if (need_on && !c->fmap.on)
-        throw Error(SPHX_ERR_STATE, "SPHX:Field:disabled", "the field map is not enabled on this context");
-    return c;
-}
-
-void field_release(sphx_ctx::FieldMap &f)
-{
-    f.on = false;
-    f.planes.release();
-    f.head.release();
-}
-
-void field_zero(sphx_ctx *c)
-{
-    c->fmap.planes.zero(c->stream);
-    c->fmap.head.zero(c->stream);
-    SPHX_HIP(hipStreamSynchronize(c->stream));
-}
-
-}  // namespace
-
-SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_config *cfg)
-{
-    SPHX_TRY
-    field_ctx(c, false);
-    require(cfg != nullptr, "SPHX:Field:config", "config must not be NULL");
-    require(cfg->nx == 0 || cfg->nx >= 2, "SPHX:Field:config", "nx must be 0 (the reference's shape) or >= 2");
-    require(cfg->ny == 0 || cfg->ny >= 2, "SPHX:Field:config", "ny must be 0 (the reference's shape) or >= 2");
-    require(cfg->every >= 1, "SPHX:Field:config", "every must be >= 1");
-    require(!std::isnan(cfg->t_from), "SPHX:Field:config", "t_from must not be NaN");
-    require(cfg->with_walls == 0 || cfg->with_walls == 1, "SPHX:Field:config", "with_walls must be 0 or 1");
-    // 0: the grid of SPH_Poiseuille_postprocess.m:185-186
-    const double nx = cfg->nx > 0 ? (double)cfg->nx : 2.0 * std::floor(c->prm.DL / c->prm.dp + 0.5);
-    const double ny = cfg->ny > 0 ? (double)cfg->ny : 2.0 * std::floor(c->prm.DH / c->prm.dp + 0.5);
-    require(nx >= 2.0 && ny >= 2.0, "SPHX:Field:config", "the reference's shape has fewer than 2 nodes along x or y: give nx and ny");
-    require(nx * ny <= (double)kFieldMaxNodes, "SPHX:Field:config", "nx * ny must not exceed 1 << 25 nodes");
-    stats_drop_graphs(c->sched, c->stream);  // the replayed graphs carry k_field_map (and its arguments) or not
-    sphx_ctx::FieldMap &f = c->fmap;
-    field_release(f);
-    f.nx = (int)nx;
-    f.ny = (int)ny;
-    try {
-        f.planes.alloc(f.nodes() * kFieldPlanes);
-        f.head.alloc(1);
-        field_zero(c);
-    } catch (const Error &e) {
-        field_release(f);
-        (void)hipGetLastError();
-        throw Error(SPHX_ERR_ARG, "SPHX:Field:config", std::string("the map could not be set up: ") + e.what());
-    }
-    f.cfg = *cfg;
-    f.on = true;
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_field_map_disable(sphx_ctx *c)
-{
-    SPHX_TRY
-    field_ctx(c, false);
-    if (!c->fmap.on) return SPHX_OK;
-    stats_drop_graphs(c->sched, c->stream);
-    field_release(c->fmap);
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_field_map_reset(sphx_ctx *c)
-{
-    SPHX_TRY
-    field_ctx(c, true);
-    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
-    field_zero(c);
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_field_map_sample(sphx_ctx *c)
-{
-    SPHX_TRY
-    field_ctx(c, true);
-    settle_owed(c);  // the state sphx_ctx_download would return
-    launch_field_map(c, 0, c->view(c->sched.cur, c->sched.lay), 0);
-    SPHX_HIP(hipGetLastError());
-    return SPHX_OK;
-    SPHX_CATCH
-}
-
-SPHX_EXPORT int sphx_ctx_field_map_read(sphx_ctx *c, int capacity, int *nx, int *ny, double *count, double *sum_w, double *sum_ux,
-                                        double *sum_uy, double *sum_ux2, double *sum_uy2, int64_t *n_samples, double *t_first,
-                                        double *t_last)
-{
-    SPHX_TRY
-    field_ctx(c, true);
-    const sphx_ctx::FieldMap &f = c->fmap;
-    double *const out[kFieldPlanes] = {count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2};
-    bool any = false;
-    for (double *o : out) any = any || o != nullptr;
-    require(!any || (size_t)std::max(capacity, 0) >= f.nodes(), "SPHX:Field:capacity", "capacity is smaller than nx * ny");
-    settle_owed(c);  // (the samples of everything enqueued)
-    FieldMapHead head{};
-    for (int j = 0; j < kFieldPlanes; ++j)
-        if (out[j])
-            SPHX_HIP(hipMemcpyAsync(out[j], f.planes.get() + (size_t)j * f.nodes(), f.nodes() * sizeof(double), hipMemcpyDeviceToHost,
-                                    c->stream));
-    SPHX_HIP(hipMemcpyAsync(&head, f.head.get(), sizeof(head), hipMemcpyDeviceToHost, c->stream));
-    SPHX_HIP(hipStreamSynchronize(c->stream));
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (nx) *nx = f.nx;
-    if (ny) *ny = f.ny;
-    if (n_samples) *n_samples = (int64_t)head.n_samples;
-    if (t_first) *t_first = head.n_samples ? head.t_first : nan;
-    if (t_last) *t_last = head.n_samples ? head.t_last : nan;
-    return SPHX_OK;
-    SPHX_CATCH
-}
+#include "sphx_samplers.hpp"  // the slot samplers: launches, lifecycle, sphx_ctx_flow_stats_* / history_* / field_map_*
 
 SPHX_EXPORT int sphx_ctx_info(sphx_ctx *c, int *n_fluid, int *n_wall, int *n_cell_x, int *n_cell_y)
 {

@@ -1,0 +1,63 @@
+// sphx_sampler_state.hpp -- host state of the slot samplers ("Slot samplers"), part of the
+// sphx_resident.hip translation unit: what sphx_ctx holds of each.  Launches, lifecycle and entry points: sphx_samplers.hpp.
+#pragma once
+#include "sphx_common.hpp"
+#include "sphx_flow_stats.hpp"
+#include "sphx_history.hpp"
+#include "sphx_field_map.hpp"
+
+struct sphx_ctx;
+
+namespace sphx {
+
+// Flow statistics (sphx_ctx_flow_stats_*, sphx_batch_flow_stats_*; sphx_flow_stats.hpp) of a context or of the M members of
+// a batch: one configuration, running sums and heads in M blocks (member m's sums at m * block(), its head at m).
+struct FlowStats {
+    bool on = false;
+    int members = 1;
+    sphx_flow_stats_config cfg{};
+    int n_bins = 0, n_bands = 1;  // (n_bands counts band 0)
+    DevBuf<unsigned long long> isum;
+    DevBuf<double> dsum;
+    DevBuf<FlowStatsHead> head;
+
+    size_t row() const { return (size_t)n_bins * kStatsFields; }  // the sums of one band ...
+    size_t block() const { return (size_t)n_bands * row(); }      // ... and of one member
+    size_t shmem() const { return block() * sizeof(unsigned long long); }  // the LDS counters of a workgroup
+
+    void configure(const sphx_params &prm, const sphx_flow_stats_config *cfg);
+    void alloc(const FlowStats &checked, int M);
+    void zero(hipStream_t st) { isum.zero(st); dsum.zero(st); head.zero(st); }
+    void release() { isum.release(); dsum.release(); head.release(); }
+    void read(hipStream_t st, int band, int stride, bool sums, double *const out[kStatsFields], int64_t *n_samples, double *t_first,
+              double *t_last) const;
+};
+
+// Step history (sphx_ctx_history_*, sphx_history.hpp)
+struct History {
+    bool on = false;
+    sphx_history_config cfg{};
+    DevBuf<double> records, part;
+    DevBuf<HistoryHead> head;
+
+    void zero(hipStream_t st) { head.zero(st); }  // (the counters: records beyond n_records are never read)
+    void release() { records.release(); part.release(); head.release(); }
+};
+
+// Velocity-field map (sphx_ctx_field_map_*, sphx_field_map.hpp)
+struct FieldMap {
+    bool on = false;
+    sphx_field_map_config cfg{};
+    int nx = 0, ny = 0;  // the shape in force (cfg.nx / cfg.ny = 0: the reference's)
+    DevBuf<double> planes;
+    DevBuf<FieldMapHead> head;
+
+    size_t nodes() const { return (size_t)nx * (size_t)ny; }
+    void zero(hipStream_t st) { planes.zero(st); head.zero(st); }
+    void release() { planes.release(); head.release(); }
+};
+
+// the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map (sphx_samplers.hpp)
+void launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild);
+
+}  // namespace sphx

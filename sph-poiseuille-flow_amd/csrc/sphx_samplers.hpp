@@ -1,0 +1,442 @@
+// sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
+// translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d) and
+// the velocity-field map (2e).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// sphx_history.hpp and sphx_field_map.hpp.  What the three share -- the context check, on / off, the view a slot leaves,
+// "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
+#pragma once
+
+namespace {
+
+// ---- shared ----
+
+// identifier stem (SPHX:<stem>:slab / :disabled / :config) and message texts of a sampler
+struct SamplerNames {
+    const char *stem;
+    const char *no_slab;
+    const char *off;        // ... "context" or "batch"
+    const char *no_memory;  // enable, out of device memory: SPHX_ERR_ARG / SPHX:<stem>:config with this text in front of the
+                            // allocator's; nullptr: the allocator's error goes out as it is
+};
+constexpr SamplerNames kStatsNames{"Stats", "flow statistics are not available on slab contexts",
+                                   "flow statistics are not enabled on this ", nullptr};
+constexpr SamplerNames kHistoryNames{"History", "the step history is not available on slab contexts",
+                                     "the step history is not enabled on this ", "the record buffer could not be set up: "};
+constexpr SamplerNames kFieldNames{"Field", "field maps are not available on slab contexts", "the field map is not enabled on this ",
+                                   "the map could not be set up: "};
+
+std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
+
+// no sampler on slabs; need_on: the call needs it enabled on this `where` ("context" / "batch")
+void sampler_check(const SamplerNames &n, bool is_slab, bool on, bool need_on, const char *where)
+{
+    if (is_slab) throw Error(SPHX_ERR_ARG, sampler_id(n, "slab"), n.no_slab);
+    if (need_on && !on) throw Error(SPHX_ERR_STATE, sampler_id(n, "disabled"), std::string(n.off) + where);
+}
+
+// the checked sampler `which` of context c
+template <typename S>
+S &sampler_of(sphx_ctx *c, S sphx_ctx::*which, const SamplerNames &n, bool need_on)
+{
+    require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
+    sampler_check(n, c->is_slab, (c->*which).on, need_on, "context");
+    return c->*which;
+}
+
+// The replayed graphs of schedule s carry a sampler's launch (and its arguments) or not: a change of the setting waits for
+// what is enqueued and drops them, so the next enqueue captures them again.
+template <typename S>
+void sampler_off(S &x, Schedule &s, hipStream_t st)
+{
+    SPHX_HIP(hipStreamSynchronize(st));
+    s.drop_graphs();
+    x.on = false;
+    x.release();
+}
+
+template <typename S>
+void sampler_zero(S &x, hipStream_t st)
+{
+    x.zero(st);
+    SPHX_HIP(hipStreamSynchronize(st));
+}
+
+// On, with what alloc() sets up, zeroed.  The caller has made every check of the configuration: a refused enable leaves a
+// running sampler untouched.  Out of device memory the sampler stays off with nothing allocated; flow statistics hand the
+// allocator's error on as it is, history and field map report theirs as a configuration error (SamplerNames::no_memory).
+template <typename S, typename Alloc>
+void sampler_on(S &x, const SamplerNames &n, Schedule &s, hipStream_t st, Alloc &&alloc)
+{
+    sampler_off(x, s, st);
+    try {
+        alloc();
+        sampler_zero(x, st);
+    } catch (const Error &e) {
+        x.release();
+        (void)hipGetLastError();
+        if (!n.no_memory) throw;
+        throw Error(SPHX_ERR_ARG, sampler_id(n, "config"), std::string(n.no_memory) + e.what());
+    }
+    x.on = true;
+}
+
+// The state step slot q, which ran on layout l, leaves: S[1-q] on every schedule (a re-binning step reorders into S[1-q]
+// too, a dynamic context copies back into it), in the other layout when the slot re-binned (a dynamic context re-bins in
+// place).  A sampler's launch comes after the slot's clock update, whichever kernel carries it.
+FluidSet slot_end_view(sphx_ctx *c, int q, int l, bool rebuild)
+{
+    return c->dyn ? c->view(1 - q, 0) : c->view(1 - q, rebuild ? 1 - l : l);
+}
+
+// a sample of the state now: settle() what is owed -- the state a download would return -- then launch(c, q, state, every)
+// with every = 0 on the current view of schedule s
+template <typename Settle, typename Launch>
+void sample_now(sphx_ctx *c, const Schedule &s, Settle &&settle, Launch &&launch)
+{
+    settle();
+    launch(c, 0, c->view(s.cur, s.lay), 0);
+    SPHX_HIP(hipGetLastError());
+}
+
+// a head's sample count and times, where asked for; no sample yet: the times are NaN
+template <typename Head>
+void read_head(const Head &h, int64_t *n_samples, double *t_first, double *t_last)
+{
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    if (n_samples) *n_samples = (int64_t)h.n_samples;
+    if (t_first) *t_first = h.n_samples ? h.t_first : nan;
+    if (t_last) *t_last = h.n_samples ? h.t_last : nan;
+}
+
+// ---- launches: every >= 1 = the in-loop sample closing step slot q, 0 = a sample of the state now ----
+
+// k_flow_stats on state s -- of a batch: member 0's -- into c->fstats
+void launch_flow_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    const FlowStats &f = c->fstats;
+    FlowStatsArgs a{};
+    a.pos = s.pos; a.vel = s.vel;
+    a.isum = f.isum.get(); a.dsum = f.dsum.get(); a.head = f.head.get();
+    a.DH = c->prm.DH; a.bin_w = c->prm.DH / f.n_bins; a.DL = c->prm.DL;
+    a.t_from = f.cfg.t_from;
+    for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
+    a.n_bins = f.n_bins; a.n_bands = f.n_bands;
+    a.every = every;
+    // workgroups of one channel's sample
+    const unsigned blocks = std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kStatsBlock * kStatsPerThread), 1u, (unsigned)kStatsMaxBlocks);
+    launch_forms(c, "k_flow_stats", Forms{k_flow_stats, k_flow_stats_b}, blocks, kStatsBlock, f.shmem(), q, a);
+}
+
+// k_step_history behind step slot q, which left state s: Vol / B of the finished step are where sphx_ctx_monitor looks them
+// up after it: the record buffers of the step's parity (fuse_ea), in the order of the layout the step ran in, so read
+// through src_of when the slot re-binned.  The static schedule knows that when the launch is made (or captured); a dynamic
+// context re-bins in place and says so in Clock::fresh.
+void launch_history(sphx_ctx *c, int q, const FluidSet &s, bool rebuild)
+{
+    const History &h = c->hist;
+    single_form_only(c, "k_step_history");
+    HistoryArgs a{};
+    a.records = h.records.get(); a.part = h.part.get(); a.head = h.head.get();
+    a.t_from = h.cfg.t_from; a.capacity = h.cfg.capacity; a.every = h.cfg.every;
+    a.src = c->dyn ? kHistoryByClock : (rebuild ? kHistorySrcOf : kHistoryInPlace);
+    const unsigned blocks =
+        std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kHistoryBlock * kHistoryPerThread), 1u, (unsigned)kHistoryMaxBlocks);
+    launch(c, "k_step_history", k_step_history, dim3(blocks), dim3(kHistoryBlock), (const Clock *)c->clock.get(), q, c->grid,
+           c->phys, s, c->tmp_par[c->fuse_ea ? q : 0], c->walls, a);
+}
+
+// k_field_map on state s (pos, vel and the cell ranges of the layout it is stored in) into c->fmap
+void launch_field_map(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    const FieldMap &f = c->fmap;
+    single_form_only(c, "k_field_map");
+    FieldMapArgs a{};
+    a.planes = f.planes.get(); a.head = f.head.get();
+    a.step_x = c->prm.DL / (f.nx - 1); a.step_y = c->prm.DH / (f.ny - 1);
+    a.dp2 = c->prm.dp * c->prm.dp;
+    a.t_from = f.cfg.t_from;
+    a.nx = f.nx; a.ny = f.ny;
+    a.tiles_y = (int)div_up((size_t)f.ny, (size_t)kFieldTile);
+    a.n_tiles = (int)div_up((size_t)f.nx, (size_t)kFieldTile) * a.tiles_y;
+    a.every = every;
+    a.with_walls = f.cfg.with_walls && c->nw > 0 ? 1 : 0;
+    const unsigned blocks = div_up((size_t)a.n_tiles, (size_t)(kFieldBlock / 64));
+    launch(c, "k_field_map", k_field_map, dim3(blocks), dim3(kFieldBlock), (const Clock *)c->clock.get(), q, c->grid, c->phys, s,
+           c->walls, a);
+}
+
+}  // namespace
+
+void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
+{
+    const FluidSet s = slot_end_view(c, q, l, rebuild);
+    if (c->fstats.on) launch_flow_stats(c, q, s, c->fstats.cfg.every);
+    if (c->hist.on) launch_history(c, q, s, rebuild);
+    if (c->fmap.on) launch_field_map(c, q, s, c->fmap.cfg.every);
+}
+
+// ---- flow statistics ----
+
+// the checked configuration cfg of channels with parameters prm (cfg, n_bins, n_bands); SPHX:Stats:config errors
+void FlowStats::configure(const sphx_params &prm, const sphx_flow_stats_config *cfg)
+{
+    require(cfg != nullptr, "SPHX:Stats:config", "config must not be NULL");
+    require(cfg->n_bins >= 0, "SPHX:Stats:config", "n_bins must be >= 0 (0 = the reference's profile bins)");
+    require(cfg->every >= 1, "SPHX:Stats:config", "every must be >= 1");
+    require(!std::isnan(cfg->t_from), "SPHX:Stats:config", "t_from must not be NaN");
+    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, "SPHX:Stats:config", "n_bands must be 0, 1 or 2");
+    for (int b = 0; b < cfg->n_bands; ++b)
+        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, "SPHX:Stats:config",
+                "band centres must be finite and half-widths finite and >= 0");
+    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
+    require((int64_t)bins * (cfg->n_bands + 1) <= kStatsMaxBins, "SPHX:Stats:config",
+            "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
+    this->cfg = *cfg;
+    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
+    n_bins = bins;
+    n_bands = cfg->n_bands + 1;
+}
+
+// the checked configuration, and sums and heads for M members
+void FlowStats::alloc(const FlowStats &checked, int M)
+{
+    cfg = checked.cfg;
+    n_bins = checked.n_bins;
+    n_bands = checked.n_bands;
+    members = M;
+    isum.alloc(block() * M);
+    dsum.alloc(block() * M);
+    head.alloc(M);
+}
+
+// Band `band` of every member's sums (sums: into out[field][m * stride + bin], where out[field] is given) and the heads
+// (n_samples[m], t_first[m], t_last[m], where given).  SPHX:Stats:range when a member's sticky flag is up.
+void FlowStats::read(hipStream_t st, int band, int stride, bool sums, double *const out[kStatsFields], int64_t *n_samples,
+                     double *t_first, double *t_last) const
+{
+    const int M = members;
+    std::vector<double> host(sums ? (size_t)M * row() : 0);
+    std::vector<FlowStatsHead> h(M);
+    if (sums)  // one copy: a row of every member's block
+        SPHX_HIP(hipMemcpy2DAsync(host.data(), row() * sizeof(double), dsum.get() + (size_t)band * row(), block() * sizeof(double),
+                                  row() * sizeof(double), M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(FlowStatsHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    for (int m = 0; m < M; ++m)
+        if (h[m].range)
+            throw Error(SPHX_ERR_STATE, "SPHX:Stats:range", (M > 1 ? "member " + std::to_string(m) + ": " : std::string()) +
+                                                           "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
+    for (int j = 0; j < kStatsFields; ++j)
+        if (out[j])
+            for (int m = 0; m < M; ++m)
+                for (int k = 0; k < n_bins; ++k) out[j][(size_t)m * stride + k] = host[(size_t)m * row() + (size_t)k * kStatsFields + j];
+    for (int m = 0; m < M; ++m)
+        read_head(h[m], n_samples ? n_samples + m : nullptr, t_first ? t_first + m : nullptr, t_last ? t_last + m : nullptr);
+}
+
+namespace {
+
+// enable for M members on schedule s: every check of cfg first
+void stats_enable(FlowStats &f, const sphx_params &prm, const sphx_flow_stats_config *cfg, int M, Schedule &s, hipStream_t st)
+{
+    FlowStats checked;
+    checked.configure(prm, cfg);
+    sampler_on(f, kStatsNames, s, st, [&] { f.alloc(checked, M); });
+}
+
+// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
+template <typename Settle>
+void stats_read(const FlowStats &f, hipStream_t st, Settle &&settle, int band, int capacity, int *n_bins, double *count, double *sum_ux,
+                double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples, double *t_first, double *t_last)
+{
+    require(band >= 0 && band < f.n_bands, "SPHX:Stats:band", "band must be 0 (whole channel) .. n_bands");
+    double *const out[kStatsFields] = {count, sum_ux, sum_ux2, sum_uy, sum_uy2};
+    bool any = false;
+    for (double *o : out) any = any || o != nullptr;
+    require(!any || capacity >= f.n_bins, "SPHX:Stats:capacity", "capacity is smaller than the number of bins");
+    settle();
+    f.read(st, band, capacity, any, out, n_samples, t_first, t_last);
+    if (n_bins) *n_bins = f.n_bins;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_config *cfg)
+{
+    SPHX_TRY
+    FlowStats &f = sampler_of(c, &sphx_ctx::fstats, kStatsNames, false);
+    stats_enable(f, c->prm, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_flow_stats_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    FlowStats &f = sampler_of(c, &sphx_ctx::fstats, kStatsNames, false);
+    if (f.on) sampler_off(f, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_flow_stats_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    FlowStats &f = sampler_of(c, &sphx_ctx::fstats, kStatsNames, true);
+    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_flow_stats_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampler_of(c, &sphx_ctx::fstats, kStatsNames, true);
+    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_flow_stats);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_flow_stats_read(sphx_ctx *c, int band, int capacity, int *n_bins, double *count, double *sum_ux,
+                                         double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples,
+                                         double *t_first, double *t_last)
+{
+    SPHX_TRY
+    const FlowStats &f = sampler_of(c, &sphx_ctx::fstats, kStatsNames, true);
+    stats_read(f, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples,
+               t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- step history ----
+
+SPHX_EXPORT int sphx_ctx_history_enable(sphx_ctx *c, const sphx_history_config *cfg)
+{
+    SPHX_TRY
+    History &h = sampler_of(c, &sphx_ctx::hist, kHistoryNames, false);
+    require(cfg != nullptr, "SPHX:History:config", "config must not be NULL");
+    require(cfg->every >= 1, "SPHX:History:config", "every must be >= 1");
+    require(cfg->capacity >= 1 && cfg->capacity <= kHistoryMaxCapacity, "SPHX:History:config", "capacity must be 1 .. 1 << 22 records");
+    require(std::isfinite(cfg->t_from), "SPHX:History:config", "t_from must be finite");
+    sampler_on(h, kHistoryNames, c->sched, c->stream, [&] {
+        h.records.alloc((size_t)cfg->capacity * kHistoryFields);
+        h.part.alloc((size_t)kHistoryMaxBlocks * kHistorySums);
+        h.head.alloc(1);
+        h.cfg = *cfg;
+    });
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_history_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    History &h = sampler_of(c, &sphx_ctx::hist, kHistoryNames, false);
+    if (h.on) sampler_off(h, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_history_read(sphx_ctx *c, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    History &h = sampler_of(c, &sphx_ctx::hist, kHistoryNames, true);
+    settle_owed(c);  // (the records of everything enqueued)
+    HistoryHead head{};
+    SPHX_HIP(hipMemcpyAsync(&head, h.head.get(), sizeof(head), hipMemcpyDeviceToHost, c->stream));
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+    const long long n = head.n_records;
+    if (n < 0 || n > (long long)h.cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:History:state", "internal: record count out of range");
+    require(records == nullptr || (long long)capacity >= n, "SPHX:History:capacity", "capacity is smaller than the number of records");
+    if (records && n > 0) {
+        SPHX_HIP(hipMemcpyAsync(records, h.records.get(), (size_t)n * kHistoryFields * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        SPHX_HIP(hipStreamSynchronize(c->stream));
+    }
+    if (n_records) *n_records = (int)n;
+    if (n_dropped) *n_dropped = (int64_t)head.n_dropped;
+    if (drain) sampler_zero(h, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- velocity-field map ----
+
+SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_config *cfg)
+{
+    SPHX_TRY
+    FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, false);
+    require(cfg != nullptr, "SPHX:Field:config", "config must not be NULL");
+    require(cfg->nx == 0 || cfg->nx >= 2, "SPHX:Field:config", "nx must be 0 (the reference's shape) or >= 2");
+    require(cfg->ny == 0 || cfg->ny >= 2, "SPHX:Field:config", "ny must be 0 (the reference's shape) or >= 2");
+    require(cfg->every >= 1, "SPHX:Field:config", "every must be >= 1");
+    require(!std::isnan(cfg->t_from), "SPHX:Field:config", "t_from must not be NaN");
+    require(cfg->with_walls == 0 || cfg->with_walls == 1, "SPHX:Field:config", "with_walls must be 0 or 1");
+    // 0: the grid of SPH_Poiseuille_postprocess.m:185-186
+    const double nx = cfg->nx > 0 ? (double)cfg->nx : 2.0 * std::floor(c->prm.DL / c->prm.dp + 0.5);
+    const double ny = cfg->ny > 0 ? (double)cfg->ny : 2.0 * std::floor(c->prm.DH / c->prm.dp + 0.5);
+    require(nx >= 2.0 && ny >= 2.0, "SPHX:Field:config", "the reference's shape has fewer than 2 nodes along x or y: give nx and ny");
+    require(nx * ny <= (double)kFieldMaxNodes, "SPHX:Field:config", "nx * ny must not exceed 1 << 25 nodes");
+    sampler_on(f, kFieldNames, c->sched, c->stream, [&] {
+        f.nx = (int)nx;
+        f.ny = (int)ny;
+        f.planes.alloc(f.nodes() * kFieldPlanes);
+        f.head.alloc(1);
+        f.cfg = *cfg;
+    });
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_field_map_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, false);
+    if (f.on) sampler_off(f, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_field_map_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, true);
+    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_field_map_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampler_of(c, &sphx_ctx::fmap, kFieldNames, true);
+    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_field_map);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_field_map_read(sphx_ctx *c, int capacity, int *nx, int *ny, double *count, double *sum_w, double *sum_ux,
+                                        double *sum_uy, double *sum_ux2, double *sum_uy2, int64_t *n_samples, double *t_first,
+                                        double *t_last)
+{
+    SPHX_TRY
+    const FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, true);
+    double *const out[kFieldPlanes] = {count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2};
+    bool any = false;
+    for (double *o : out) any = any || o != nullptr;
+    require(!any || (size_t)std::max(capacity, 0) >= f.nodes(), "SPHX:Field:capacity", "capacity is smaller than nx * ny");
+    settle_owed(c);  // (the samples of everything enqueued)
+    FieldMapHead head{};
+    for (int j = 0; j < kFieldPlanes; ++j)
+        if (out[j])
+            SPHX_HIP(hipMemcpyAsync(out[j], f.planes.get() + (size_t)j * f.nodes(), f.nodes() * sizeof(double), hipMemcpyDeviceToHost,
+                                    c->stream));
+    SPHX_HIP(hipMemcpyAsync(&head, f.head.get(), sizeof(head), hipMemcpyDeviceToHost, c->stream));
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+    if (nx) *nx = f.nx;
+    if (ny) *ny = f.ny;
+    read_head(head, n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
