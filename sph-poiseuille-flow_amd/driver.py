@@ -77,12 +77,13 @@ def periodic_bounding(pos, n_fluid, DL):
 
 def time_average(prm, whole, mid):
     """Figures of a time window from the device's flow statistics (capi.Context.flow_stats of band 0 / the mid band).
-    U_max = g DH^2 / (8 nu), the centre-line speed of the analytic profile.
+    U_max = g DH^2 / (8 nu), the centre-line speed of the analytic profile: signed, negative for a leftward flow; the rms
+    and spread figures are magnitudes and are divided by |U_max|.
       profile, mid_profile   the whole-channel and mid-band flow_stats dicts (u_mean, u_std, ... per bin)
       u_exact, L2            analytic profile at the bin centres and l2_error of the time-averaged whole-channel u_mean
-      uy_rms_over_umax       sqrt(sum over bins of sum u_y^2 / sum over bins of N) / U_max (all particle samples)
+      uy_rms_over_umax       sqrt(sum over bins of sum u_y^2 / sum over bins of N) / |U_max| (all particle samples)
       ux_std_centre_over_umax  count-weighted RMS of the per-bin u_x spread u_std over the bins whose centres lie in
-                             [0.4, 0.6] DH, sqrt(sum N u_std^2 / sum N), / U_max
+                             [0.4, 0.6] DH, sqrt(sum N u_std^2 / sum N), / |U_max|
       n_samples, t_first, t_last  the window actually sampled"""
     u_max = prm.gravity_g * prm.DH ** 2 / (8.0 * prm.nu)
     y = whole["y_mid"]
@@ -94,8 +95,8 @@ def time_average(prm, whole, mid):
     n_c = float(np.sum(N[centre]))
     ux_sd = np.sqrt(np.sum(N[centre] * whole["u_std"][centre] ** 2) / n_c) if n_c > 0 else np.nan
     return dict(profile=whole, mid_profile=mid, y_mid=y, u_mean=whole["u_mean"], mid_u_mean=mid["u_mean"], u_exact=u_exact,
-                L2=l2_error(whole["u_mean"], u_exact), uy_rms_over_umax=float(uy_rms / u_max),
-                ux_std_centre_over_umax=float(ux_sd / u_max), U_max=u_max, n_samples=whole["n_samples"],
+                L2=l2_error(whole["u_mean"], u_exact), uy_rms_over_umax=float(uy_rms / abs(u_max)),
+                ux_std_centre_over_umax=float(ux_sd / abs(u_max)), U_max=u_max, n_samples=whole["n_samples"],
                 t_first=whole["t_first"], t_last=whole["t_last"])
 
 
@@ -136,10 +137,10 @@ def field_figures(prm, field):
     u_x, u_y as [ny, nx] arrays) against the analytic flow, on the host.  Nodes never sampled (NaN) are left out.
       u_row_mean, u_exact    the x-mean of u_x per row and the analytic profile at the rows' y
       rows, L2               the rows at least 2h from both walls, and l2_error of u_row_mean against u_exact over them
-      x_spread, ix, iy       the largest deviation of a node's u_x from its row's x-mean over those rows, in % of U_max, and
+      x_spread, ix, iy       the largest deviation of a node's u_x from its row's x-mean over those rows, in % of |U_max|, and
                              the node where it occurs (a seam defect shows up at ix near 0 or nx - 1)
       uy_rms                 RMS of u_y over all sampled nodes
-      U_max                  g DH^2 / (8 nu)"""
+      U_max                  g DH^2 / (8 nu), signed"""
     y = np.asarray(field["y"], dtype=np.float64)
     ux, uy = np.asarray(field["u_x"], dtype=np.float64), np.asarray(field["u_y"], dtype=np.float64)
     u_max = prm.gravity_g * prm.DH ** 2 / (8.0 * prm.nu)
@@ -153,7 +154,7 @@ def field_figures(prm, field):
     sel = rows & ~np.isnan(row_mean)
     dev = np.where(ok & rows[:, None], np.abs(ux - row_mean[:, None]), -1.0)
     iy, ix = np.unravel_index(int(np.argmax(dev)), dev.shape)
-    x_spread = 100.0 * float(dev[iy, ix]) / u_max if dev[iy, ix] >= 0.0 else float("nan")
+    x_spread = 100.0 * float(dev[iy, ix]) / abs(u_max) if dev[iy, ix] >= 0.0 else float("nan")
     uy_ok = uy[~np.isnan(uy)]
     return dict(u_row_mean=row_mean, u_exact=u_exact, rows=rows,
                 L2=l2_error(np.where(sel, row_mean, np.nan), u_exact) if sel.any() else float("nan"),

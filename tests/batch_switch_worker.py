@@ -1,6 +1,7 @@
 """Child process of tests/test_gpu_batch_switches.py: SPHX_DEBUG_SWITCHES is read once per process, so every switch set runs in
 a fresh one.  Builds the moving-wall batch of test_gpu_batch.py (helpers.make_variant: moving walls, uneven mass, rho0 = 2.5;
-dp 0.05, DL 1.5, four members) and the same four channels as standalone contexts, enables flow statistics on all of them
+dp 0.05, DL 1.5, four members) or, with --case regimes, the four members of test_gpu_regimes.py (default physics, flow to the
+left, c_f = 0.3, mu = 2 on fixed walls) and the same four channels as standalone contexts, enables flow statistics on all of them
 (every step, one band at DL/2), advances 2K+3 steps and compares member by member, bit for bit: the nine fields, t, dt_last,
 vmax, step, both tau, the pair count, and the raw flow-statistics sums of both bands.  Prints ONE JSON line: the schedule a
 standalone context chose, what the batch says about itself, and what differed.  Exit code 0: ran to the end (whatever the
@@ -46,12 +47,18 @@ def main():
     ap.add_argument("--rebuild-every", type=int, default=0, help="0: the library's choice")
     ap.add_argument("--mode", choices=("graph", "eager"), default="graph", help="eager: one-step calls")
     ap.add_argument("--dump", metavar="DIR", help="also write what the batch returned as DIR/*.npy")
+    ap.add_argument("--skin-h", type=float, default=0.0, help="cell skin in units of h (0: the library's choice)")
+    ap.add_argument("--case", choices=("", "regimes"), default="", help="regimes: the four members of test_gpu_regimes.py")
     args = ap.parse_args()
     from helpers import make_variant
     pkg = importlib.import_module("sph-poiseuille-flow_amd")
     capi = pkg.capi
     members = []
-    for v in VARIANTS:
+    if args.case == "regimes":  # default physics, flow to the left, c_f = 0.3, mu = 2: fixed walls and even mass, shared as they are
+        import regime_cases
+        members = [getattr(regime_cases, name)(pkg.config, pkg.geometry, "small")
+                   for name in ("default", "leftward_plain", "capped", "viscous_plain")]
+    for v in VARIANTS if not members else ():
         prm, parts = make_variant(pkg.config, pkg.geometry, dp=0.05, DL=1.5, jitter=0.2, seed=v["seed"], developed=True, rho0=2.5,
                                   mu=v["mu"], c_f=v["c_f"], transport_coeff=v["transport_coeff"])
         if members:  # walls and masses are the batch's, not the member's
@@ -60,6 +67,8 @@ def main():
     kw = dict(t_end=1e9, lanes_per_particle=args.lpp)
     if args.rebuild_every:
         kw["rebuild_every"] = args.rebuild_every
+    if args.skin_h:
+        kw["skin_h"] = args.skin_h
     stats = dict(every=1, bands=[(0.75, 0.2)])  # one band at DL/2
 
     def advance(obj, n):
@@ -98,7 +107,7 @@ def main():
         for m, g in enumerate(got):
             for k, v in g.items():
                 np.save(os.path.join(args.dump, f"m{m}_{k}.npy"), np.asarray(v))
-    print(json.dumps(dict(switches=os.environ.get("SPHX_DEBUG_SWITCHES", ""), lpp=args.lpp, mode=args.mode, steps=n,
+    print(json.dumps(dict(switches=os.environ.get("SPHX_DEBUG_SWITCHES", ""), lpp=args.lpp, mode=args.mode, case=args.case, steps=n,
                           steps_taken=[int(g["step"]) for g in got], schedule=sched, rebins=rebins, info=info,
                           graph_stats=graph_stats, n_samples=[int(g["stats0_n_samples"]) for g in got], differs=differs)),
           flush=True)

@@ -123,9 +123,10 @@ def run(prm, parts, n_in, t_target=1e9, t_end=1e9, max_outer=0, state=None, wron
 
 # ---- the shared starts: 600 fluid particles, dp = 0.05, DL = 1.5, DH = 1 ----
 
-def plain(cfgmod, geom):
-    """The start of tests/test_gpu_load_chains.py: developed profile, positions jittered by 0.2 dp."""
-    prm = cfgmod.params_from_values(dp=DP, DL=DL)
+def plain(cfgmod, geom, **kw):
+    """The start of tests/test_gpu_load_chains.py: developed profile, positions jittered by 0.2 dp.  kw: other physics, as
+    U_bulk < 0 of the start "left" (g, and with it the developed profile, point to the left)."""
+    prm = cfgmod.params_from_values(dp=DP, DL=DL, **kw)
     parts = dict(geom.init_particles(prm))
     pos, vel = geom.developed_state(prm, parts, jitter=0.2, seed=21)
     assert parts["n_fluid"] == 600 and abs(prm.DH - 1.0) < 1e-12
@@ -195,12 +196,15 @@ GPU_CASES = {
     "I": ("plain", (16,), 2, 10),  # with rebuild_every = 4
     "J": ("plain", (16,), 2, 5),   # advance(2.5 Dt_first): 3 outer steps, then 2 more
     "K": ("bottom", (16,), 4, 3),  # max |v| > c_f / (n_in - 1): the advective limit sets Dt
+    "L": ("left", (16,), 2, 10),   # U_bulk < 0: the flow, and the seam crossings, to the left
 }
 
 
 def start(cfgmod, geom, name):
     if name == "plain":
         return plain(cfgmod, geom)
+    if name == "left":
+        return plain(cfgmod, geom, U_bulk=-0.666667)
     if name == "variant":
         return variant(cfgmod, geom)
     return squeezed(cfgmod, geom, SQUEEZE_CENTRES[name])

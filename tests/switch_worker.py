@@ -1,6 +1,7 @@
 """Child process of tests/test_gpu_switches.py: SPHX_DEBUG_SWITCHES is read once per process, so every switch set runs in a
-fresh one.  Steps the moving-wall variant (helpers.make_variant: moving walls, uneven mass, rho0 = 2.5; 2 880 particles)
-across its re-binnings, compares every field with the oracle at the tolerances of test_gpu_resident.py and prints ONE JSON
+fresh one.  Steps the moving-wall variant (helpers.make_variant: moving walls, uneven mass, rho0 = 2.5; 2 880 particles) or,
+with --case NAME, a regime case of tests/regime_cases.py at the same size (left_capped: the same variant mirrored, flowing to
+the left, with c_f = 0.3) across its re-binnings, compares every field with the oracle at the tolerances of test_gpu_resident.py and prints ONE JSON
 line: the kernel forms and the schedule the context chose, the worst error per field, and what failed.  Exit code 0: ran to the
 end (whatever the comparison said).
 
@@ -31,13 +32,19 @@ def main():
     ap.add_argument("--steps", type=int, default=35)
     ap.add_argument("--dynamic", action="store_true", help="dynamic re-binning, every 8th step")
     ap.add_argument("--dump", metavar="DIR", help="also write the downloaded fields and scalars as DIR/*.npy")
+    ap.add_argument("--case", default="", help="a name of tests/regime_cases.py's CASES at its worker size in place of the "
+                                               "moving-wall variant")
     args = ap.parse_args()
     import oracle
     from helpers import assert_close, make_variant
     pkg = importlib.import_module("sph-poiseuille-flow_amd")
     capi = pkg.capi
-    prm, parts = make_variant(pkg.config, pkg.geometry, dp=0.025, DL=1.5, jitter=0.25, seed=31, developed=True, rho0=2.5,
-                              transport_coeff=0.1)
+    if args.case:
+        import regime_cases
+        prm, parts = regime_cases.CASES[args.case](pkg.config, pkg.geometry, "worker")
+    else:
+        prm, parts = make_variant(pkg.config, pkg.geometry, dp=0.025, DL=1.5, jitter=0.25, seed=31, developed=True, rho0=2.5,
+                                  transport_coeff=0.1)
     nf, nt = parts["n_fluid"], parts["n_total"]
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=args.steps, enable_sort=False)
     kw = dict(dynamic_rebin=1, rebuild_every=8) if args.dynamic else {}
@@ -77,7 +84,10 @@ def main():
         failures.append(f"vmax {st['vmax']!r} vs {rs['vmax']!r}")
     if npairs != rs["n_pairs_last"]:
         failures.append(f"pairs {npairs} vs {rs['n_pairs_last']}")
-    print(json.dumps(dict(switches=os.environ.get("SPHX_DEBUG_SWITCHES", ""), lpp=args.lpp, n_total=nt, steps=int(st["step"]),
+    nf_x = got["pos"][:nf, 0]
+    if not (np.all(nf_x >= 0.0) and np.all(nf_x <= prm.DL)):
+        failures.append(f"x outside [0, DL]: {float(nf_x.min())!r} .. {float(nf_x.max())!r}")
+    print(json.dumps(dict(switches=os.environ.get("SPHX_DEBUG_SWITCHES", ""), lpp=args.lpp, case=args.case, n_total=nt, steps=int(st["step"]),
                           forms=forms, schedule=sched, rebins=int(sched_after["rebins"] - sched["rebins"]),
                           forced_rebuilds=int(pol["forced_rebuilds"]), errors=errors, failures=failures)), flush=True)
     return 0

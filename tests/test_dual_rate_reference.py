@@ -18,7 +18,7 @@ COMBOS = sorted({(c[0], c[2], c[3]) for k, c in drr.GPU_CASES.items() if k != "J
 
 @pytest.fixture(scope="module")
 def starts(cfgmod, geom, oracle):
-    return {name: drr.start(cfgmod, geom, name) for name in ("plain", "bottom", "top", "seam", "variant")}
+    return {name: drr.start(cfgmod, geom, name) for name in ("plain", "bottom", "top", "seam", "variant", "left")}
 
 
 @pytest.fixture(scope="module")
@@ -175,3 +175,19 @@ def test_squeezed_starts_have_wall_neighbours_behind_the_second_row(name, starts
     p0 = starts["plain"][1]
     assert np.array_equal(parts["vel"], p0["vel"]) and np.array_equal(parts["pos"][nf:], p0["pos"][nf:])
     assert 0 < np.any(parts["pos"][:nf] != p0["pos"][:nf], axis=1).sum() < 80
+
+
+def test_left_start_is_the_plain_one_mirrored_in_its_velocity(starts):
+    (prm, parts), (prm0, p0) = starts["left"], starts["plain"]
+    nf = parts["n_fluid"]
+    assert prm.gravity_g == -prm0.gravity_g < 0 and np.array_equal(parts["pos"], p0["pos"])
+    assert np.array_equal(parts["vel"], -p0["vel"]) and np.all(parts["vel"][:nf, 0] < 0)
+    assert [drr.substeps(prm, d) for d in (2, 3, 4)] == [2, 3, 4]
+    # ten outer steps of two cross the seam to the left (measured: one particle) and never to the right
+    st, left, right = None, 0, 0
+    for _ in range(drr.GPU_CASES["L"][3]):
+        x0 = np.array((st or parts)["pos"][:nf, 0])
+        st = drr.run(prm, parts, 2, max_outer=1, state=st)
+        left += int(np.count_nonzero(st["pos"][:nf, 0] - x0 > 0.5 * prm.DL))
+        right += int(np.count_nonzero(st["pos"][:nf, 0] - x0 < -0.5 * prm.DL))
+    assert left >= 1 and right == 0, (left, right)

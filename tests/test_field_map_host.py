@@ -173,3 +173,33 @@ def test_driver_refuses_the_mex_engine(cfgmod, driver):
     prm = cfgmod.params_from_values(dp=0.05, DL=3.0, end_time=0.01, output_interval=0.01)
     with pytest.raises(ValueError, match="resident"):
         driver.run(prm, engine="mex", field_from=0.0)
+
+
+def test_figures_of_a_mirrored_flow(cfgmod, driver):
+    """x -> DL - x, u_x -> -u_x, g -> -g: the same flow seen from behind.  L2, x_spread (in % of |U_max|) and uy_rms are equal
+    and not negative, the bump is found at the mirrored node, U_max and the row means flip their sign.  (A spread divided
+    by a signed U_max came out negative for every leftward flow and passed any `x_spread < tol`.)"""
+    nx, ny = 120, 40
+    rng = np.random.default_rng(5)
+    noise = 0.01 * rng.standard_normal((ny, nx))
+    uy = 0.02 * rng.standard_normal((ny, nx))
+    out = {}
+    for sign in (1, -1):
+        prm = cfgmod.params_from_values(dp=0.05, DL=3.0, U_bulk=sign * 0.666667)
+        y = np.linspace(0.0, prm.DH, ny)
+        u = np.repeat((prm.gravity_g / (2.0 * prm.nu) * y * (prm.DH - y))[:, None], nx, axis=1) + sign * noise
+        u[ny // 2, 2] += sign * 0.05
+        u[3, 77] = np.nan
+        m = _map(prm, nx, ny, u if sign > 0 else u[:, ::-1].copy())
+        m["u_y"] = uy if sign > 0 else uy[:, ::-1].copy()
+        out[sign] = driver.field_figures(prm, m)
+    a, b = out[1], out[-1]
+    assert a["U_max"] > 0 and b["U_max"] == -a["U_max"]
+    assert (a["ix"], a["iy"]) == (2, ny // 2) and (b["ix"], b["iy"]) == (nx - 3, ny // 2)
+    assert a["x_spread"] > 4.0                        # 5 % of U_max = 1 on top of the noise
+    for k in ("L2", "x_spread", "uy_rms"):
+        assert a[k] > 0 and b[k] >= 0, (k, a[k], b[k])
+        assert abs(a[k] - b[k]) <= 1e-12 * a[k], (k, a[k], b[k])
+    ok = ~np.isnan(a["u_row_mean"])
+    np.testing.assert_allclose(b["u_row_mean"][ok], -a["u_row_mean"][ok], rtol=1e-12)
+    assert np.array_equal(b["u_exact"], -a["u_exact"])

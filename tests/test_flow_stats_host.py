@@ -127,3 +127,26 @@ def test_time_average_figures(driver, profmod, cfgmod):
     assert ta["uy_rms_over_umax"] == pytest.approx(0.3 / u_max, rel=1e-12)
     assert ta["ux_std_centre_over_umax"] == pytest.approx(0.2 / u_max, rel=1e-6)
     assert ta["n_samples"] == 5 and (ta["t_first"], ta["t_last"]) == (1.0, 2.0)
+
+
+def test_time_average_figures_of_a_mirrored_flow(driver, profmod, cfgmod):
+    """A leftward flow (U_bulk < 0: g, u_x and U_max negative) is the mirror image of a rightward one: L2 and the rms and
+    spread figures, which are magnitudes over |U_max|, are the same and not negative; U_max flips its sign."""
+    n_bins = 20
+    rng = np.random.default_rng(11)
+    N = rng.integers(5, 30, n_bins).astype(np.float64)
+    noise, uy2 = 0.02 * rng.standard_normal(n_bins), 0.09 * (1 + rng.random(n_bins))
+    out = {}
+    for sign in (1, -1):
+        prm = cfgmod.params_from_values(dp=0.05, DL=3.0, U_bulk=sign * 0.666667)
+        y = np.linspace(0.0, prm.DH, n_bins + 1)
+        y_mid = 0.5 * (y[:-1] + y[1:])
+        u = prm.gravity_g / (2 * prm.nu) * y_mid * (prm.DH - y_mid) + sign * noise
+        whole = profmod.flow_stats_profile(prm.DH, N, N * u, N * (u * u + 0.04), np.zeros(n_bins), N * uy2, 5, 1.0, 2.0)
+        out[sign] = driver.time_average(prm, whole, whole)
+    a, b = out[1], out[-1]
+    assert a["U_max"] > 0 and b["U_max"] == -a["U_max"]
+    assert np.array_equal(b["u_exact"], -a["u_exact"])
+    for k in ("L2", "uy_rms_over_umax", "ux_std_centre_over_umax"):
+        assert a[k] > 0 and b[k] >= 0, (k, a[k], b[k])
+        assert abs(a[k] - b[k]) <= 1e-12 * a[k], (k, a[k], b[k])

@@ -26,10 +26,22 @@ SETS = [("", 16, 1, 1), ("", 32, 1, 1), ("no_fuse_ea", 16, 0, 1), ("no_fuse_ea",
 
 @pytest.mark.parametrize("switches,lpp,fuse_ea,tail_clock", SETS, ids=[f"{s or 'none'}-lpp{l}" for s, l, *_ in SETS])
 def test_batch_switch_set_bit_identical_to_standalone(switches, lpp, fuse_ea, tail_clock):
+    _run_set(switches, lpp, fuse_ea, tail_clock, [])
+
+
+def test_batch_own_clock_launch_in_four_regimes():
+    """The clock launch of its own (no_tail_clock), whose dt limits are per member: the members of
+    test_gpu_regimes.regime_members -- default physics (acoustic dt), flow to the left, c_f = 0.3 and mu = 2 (both limited by
+    their viscous dt, five times and a quarter of the default's) -- with K = 4 and a skin of 1.6 h, so that no member outruns
+    the skin (a forced re-binning re-bins all members of a batch, which the standalone contexts would not do)."""
+    _run_set("no_tail_clock", 16, 0, 0, ["--case", "regimes", "--rebuild-every", "4", "--skin-h", "1.6"])
+
+
+def _run_set(switches, lpp, fuse_ea, tail_clock, extra):
     if _abnormal:
         pytest.fail(f"not started: an earlier child ended abnormally ({_abnormal[0]})")
     env = dict(os.environ, SPHX_DEBUG_SWITCHES=switches)
-    cmd = [sys.executable, WORKER, "--lpp", str(lpp)]
+    cmd = [sys.executable, WORKER, "--lpp", str(lpp)] + extra
     try:
         r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=CHILD_SECONDS)
     except subprocess.TimeoutExpired as e:

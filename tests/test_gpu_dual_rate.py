@@ -40,6 +40,14 @@ def test_dual_rate_needs_an_eligible_context(cfgmod, geom, capi):
     prm, parts = make_case(cfgmod, geom, dp=0.025, DL=2.0, jitter=0.0, seed=1, developed=False)
     with _ctx(capi, prm, parts, dual_rate=2, lanes_per_particle=8) as ctx:
         assert ctx.substeps() == 1
+    # viscous-limited by its physics at a small size (regime_cases.viscous, mu = 2): floor(min(dt_visc, dt_body) / dt_ac) < 2
+    import dual_rate_reference as drr
+    import regime_cases
+    vprm, vparts = regime_cases.viscous(cfgmod, geom, "small")
+    assert drr.substeps(vprm, 4) == 1
+    for lanes in (16, 32):
+        with _ctx(capi, vprm, vparts, dual_rate=4, lanes_per_particle=lanes) as ctx:
+            assert ctx.substeps() == 1
     with pytest.raises(capi.SphxError):
         _ctx(capi, prm, parts, dual_rate=9)
     # the range check does not depend on eligibility (few lanes per particle, negative values)

@@ -26,6 +26,7 @@ in the kernels (forces_pass with later = 1, continuity_body with next_half = 1, 
   J  plain, 16 lanes, n_in 2, advance(2.5 Dt_first) then advance(1e9, max_steps = 2)   the last outer step clipped to the
      target, then resumed; compared after each call
   K  squeezed at the bottom wall, 16 lanes, n_in 4, 3 outer   max |v| ~ 9 > c_f / 3: the advective limit of next_dt sets Dt
+  L  plain with U_bulk < 0, 16 lanes, n_in 2, 10 outer   the flow to the left: the periodic wrap xo < 0 in the inner sub-steps
 
 Bound: RTOL = 1e-10 in max|a - b| / max|b| per field and for dt and max |v| -- tests/test_gpu_headline_parity.py's bound for up
 to 35 steps of the same formulas in another summation order; t to 1e-12 relative; the step count exactly.  Every case runs
@@ -82,7 +83,7 @@ def _check(name, capi, capsys, prm, parts, lanes, n_in, calls, **kw):
     return info, outs
 
 
-# cases A to H of drr.GPU_CASES (the table whose starts and lengths the CPU tests check for conditioning), one per lane count
+# cases A to H, K and L of drr.GPU_CASES (the table whose starts and lengths the CPU tests check for conditioning), one per lane count
 STEPPED = [(k if len(lanes) == 1 else f"{k}{l}", start, l, n_in, n_outer)
            for k, (start, lanes, n_in, n_outer) in drr.GPU_CASES.items() if k not in ("I", "J") for l in lanes]
 
@@ -93,7 +94,7 @@ def test_dual_rate_matches_the_reference(case, start, lanes, n_in, n_outer, cfgm
     n_all, n_wall = drr.counts_within(prm, parts, 2.0 * prm.h)
     if start in ("bottom", "top", "seam"):  # more than two rows of 16, wall rows behind the prefetched ones
         assert np.any((n_all > 32) & (n_wall > 0))
-    elif start == "plain":
+    elif start in ("plain", "left"):
         assert 16 < n_all.max() <= 32
     _, outs = _check(f"{case} {start} {lanes} lanes", capi, capsys, prm, parts, lanes, n_in, [(1e9, n_outer)])
     st = outs[0][0]

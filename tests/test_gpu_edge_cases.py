@@ -195,3 +195,8 @@ def test_tall_columns_fall_back_to_the_compact_kernels(cfgmod, geom, capi, oracl
     assert st["step"] == 3 and abs(st["t"] - ref["stats"]["t"]) <= 1e-13 * ref["stats"]["t"]
     for k in ("pos", "vel", "drho_dt", "rho"):
         assert_close(got[k], ref[k], rtol=1e-9, atol_scale=1e-10, name=k)
+    # dp this fine makes the steps viscous-limited (0.125 h^2 / nu = 3.3e-8 against an acoustic 2.5e-6): say so, and hold the
+    # clock of the compact kernels to it
+    dt_viscous = 0.125 * prm.h * prm.h / prm.nu
+    assert ref["stats"]["dt_last"] == dt_viscous and dt_viscous < 0.1 * 0.25 * prm.h / (prm.c_f + ref["stats"]["vmax"])
+    assert abs(st["dt_last"] - dt_viscous) <= 1e-12 * dt_viscous

@@ -27,6 +27,7 @@ CASES = {
     "two_cols_06": (0.1, 0.6, dict(), dict()),
     "one_col": (0.1, 0.4, dict(), dict(developed=False)),              # one column, two images within 2h
     "dp01_multi": (0.01, 3.0, dict(), dict()),                         # 30 k particles, 120 k nodes: many workgroups
+    "leftward": (0.05, 3.0, dict(), dict(U_bulk=-0.666667)),           # g < 0: u_x negative at every node
 }
 PLANES = ("count", "sum_w", "sum_ux", "sum_uy", "sum_ux2", "sum_uy2")
 BOUND = 1e-12
@@ -122,6 +123,10 @@ def test_sample_now_matches_numpy(cfgmod, geom, capi, profmod, name):
         f = profmod.shepard_field(pos, vel, prm.DL, prm.DH, prm.h, nx, ny)
     print(f"{name}: min S0 dp^2 = {np.min(f['S0']) * prm.dp ** 2:.3f}")
     _assert_planes_match(got, _numpy_planes(profmod, prm, f), name)
+    if name == "leftward":
+        # (at least 2h from the walls: next to them a jittered particle with y < 0 carries the parabola's other sign)
+        inner = (f["y"] >= 2.0 * prm.h) & (f["y"] <= prm.DH - 2.0 * prm.h)
+        assert prm.gravity_g < 0 and inner.sum() >= ny - 14 and np.all(got["sum_ux"][inner] < 0) and np.all(f["u_x"][inner] < 0)
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------

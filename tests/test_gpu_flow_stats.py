@@ -13,23 +13,24 @@ from helpers import make_case
 
 pytestmark = pytest.mark.gpu
 
-# (dp, DL, context options): compact kernels at both sizes and several lane counts, the large-channel ("walk") kernels,
+# (dp, DL, context options, make_case options): compact kernels at both sizes and several lane counts, the large-channel ("walk") kernels,
 # a device-decided (dynamic) schedule and the dual-rate loop
 CASES = {
-    "dp05_auto": (0.05, 3.0, dict()),
-    "dp05_lpp32": (0.05, 3.0, dict(lanes_per_particle=32)),
-    "dp025_lpp16": (0.025, 1.5, dict(lanes_per_particle=16)),
-    "dp025_walk": (0.025, 1.5, dict(lanes_per_particle=4)),
-    "dp05_dynamic": (0.05, 3.0, dict(dynamic_rebin=1)),
-    "dp025_dual": (0.025, 1.5, dict(lanes_per_particle=16, dual_rate=2)),
-    "dp01_multi": (0.01, 3.0, dict()),  # 30 k fluid particles: several workgroups per sample (global sums + ticket)
+    "dp05_auto": (0.05, 3.0, dict(), dict()),
+    "dp05_lpp32": (0.05, 3.0, dict(lanes_per_particle=32), dict()),
+    "dp025_lpp16": (0.025, 1.5, dict(lanes_per_particle=16), dict()),
+    "dp025_walk": (0.025, 1.5, dict(lanes_per_particle=4), dict()),
+    "dp05_dynamic": (0.05, 3.0, dict(dynamic_rebin=1), dict()),
+    "dp025_dual": (0.025, 1.5, dict(lanes_per_particle=16, dual_rate=2), dict()),
+    "dp01_multi": (0.01, 3.0, dict(), dict()),  # 30 k fluid particles: several workgroups per sample (global sums + ticket)
+    "leftward": (0.05, 3.0, dict(), dict(U_bulk=-0.666667)),  # g < 0: u_x, its sums and means negative, the wrap at x < 0
 }
 FIELDS = ("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2")
 
 
 def _case(cfgmod, geom, name, seed=11):
-    dp, DL, kw = CASES[name]
-    prm, parts = make_case(cfgmod, geom, dp=dp, DL=DL, jitter=0.2, seed=seed, developed=True)
+    dp, DL, kw, mk = CASES[name]
+    prm, parts = make_case(cfgmod, geom, **dict(dict(dp=dp, DL=DL, jitter=0.2, seed=seed, developed=True), **mk))
     return prm, parts, kw
 
 
@@ -114,6 +115,12 @@ def test_sample_now_matches_numpy(cfgmod, geom, capi, profmod, name):
     assert np.array_equal(np.isnan(mid["u_mean"]), np.isnan(u_mid))
     ok = ~np.isnan(u_mid)
     np.testing.assert_allclose(mid["u_mean"][ok], u_mid[ok], rtol=1e-12, atol=1e-14)
+    if name == "leftward":
+        # (bins at least 2h from the walls: next to them a jittered particle with y < 0 carries the parabola's other sign)
+        inner = (mid["y_mid"] >= 2.0 * prm.h) & (mid["y_mid"] <= prm.DH - 2.0 * prm.h)
+        assert prm.gravity_g < 0 and inner.sum() >= n_bins - 8 and np.all(mid["u_mean"][inner & ok] < 0) and (inner & ok).sum() >= inner.sum() - 1
+        for b in range(3):
+            assert np.all(got[b]["sum_ux"][inner & (got[b]["count"] > 0)] < 0)
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------

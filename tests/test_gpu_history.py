@@ -81,6 +81,13 @@ def plain_series(cfgmod, geom, oracle):
 
 
 @pytest.fixture(scope="module")
+def left_series(cfgmod, geom, oracle):
+    # plain_series mirrored: U_bulk < 0, so g, u_bulk and both tau are negative
+    prm, parts = make_case(cfgmod, geom, dp=0.05, DL=3.0, U_bulk=-0.666667)
+    return prm, parts, _oracle_rows(oracle, prm, parts, 36)
+
+
+@pytest.fixture(scope="module")
 def variant_series(cfgmod, geom, oracle):
     # moving walls (top and bottom differ in size and sign), uneven mass, rho0 != 1
     prm, parts = make_variant(cfgmod, geom, seed=7, developed=True, dp=0.05, DL=1.5, jitter=0.2, rho0=2.5, transport_coeff=0.1)
@@ -109,7 +116,18 @@ def _assert_series_matches_oracle(hist, want, what):
 
 
 def test_series_matches_the_oracle_step_by_step(capi, plain_series):
-    prm, parts, want = plain_series
+    _series_matches_the_oracle_step_by_step(capi, plain_series, "dp05")
+
+
+def test_series_matches_the_oracle_step_by_step_leftward(capi, left_series):
+    prm, parts, want = left_series
+    assert prm.gravity_g < 0 and np.all(want[:, 4:6] < 0) and np.all(want[:, 7] < 0)    # both tau and u_bulk of the oracle
+    hist = _series_matches_the_oracle_step_by_step(capi, left_series, "dp05 leftward")
+    assert np.all(hist["tau_bottom"] < 0) and np.all(hist["tau_top"] < 0) and np.all(hist["u_bulk"] < 0)
+
+
+def _series_matches_the_oracle_step_by_step(capi, series, what):
+    prm, parts, want = series
     # from one step to the next every field moves by far more than the tolerances: a record taken a step early or late fails
     assert np.all(np.abs(np.diff(want[:, 1:], axis=0)) >= 1e-6 * np.abs(want[1:, 1:]))
     with _ctx(capi, prm, parts) as ctx:
@@ -118,7 +136,8 @@ def test_series_matches_the_oracle_step_by_step(capi, plain_series):
         rebins = ctx.schedule()["rebins"]
         hist = ctx.history()
     assert rebins >= 2, f"only {rebins} re-binnings: both Vol / B lookups must be exercised"
-    _assert_series_matches_oracle(hist, want, "dp05")
+    _assert_series_matches_oracle(hist, want, what)
+    return hist
 
 
 @pytest.mark.parametrize("lpp", [16, 4])

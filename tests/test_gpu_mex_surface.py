@@ -8,6 +8,7 @@ membership, 1e-14 relative on dx,dy,r and 1e-12 on W,dW.
 import numpy as np
 import pytest
 
+import regime_cases
 from helpers import assert_close, canon_pairs, field_atol, make_case, make_variant
 
 pytestmark = pytest.mark.gpu
@@ -20,12 +21,21 @@ CASES = [
     # moving walls (every wall particle its own velocity), uneven mass, rho0 != 1: what make_case leaves at zero / one
     dict(variant=True, dp=0.05, DL=3.0, jitter=0.2, developed=True, rho0=2.5, transport_coeff=0.1),
     dict(variant=True, dp=0.04, DL=1.3, DH=0.8, jitter=0.25, developed=True, rho0=0.37),  # DH != 1: the top / bottom split of tau
+    # tests/regime_cases.py at its small size (census in tests/test_regime_cases.py): the flow and the moving walls mirrored;
+    # c_f = 0.3, so 604 of 5 739 fluid pairs sit on the cap of the Riemann dissipation and 2 262 on its linear part; two rows
+    # whose drho_dt of -1e6 takes the half-step density through the floor of integration_1st / _verlet / advance_shell_step
+    dict(regime="leftward"),
+    dict(regime="capped"),
+    dict(regime="floor"),
 ]
 
 
 @pytest.fixture(scope="module", params=range(len(CASES)))
 def case(request, cfgmod, geom, oracle):
     kw = dict(CASES[request.param])
+    if "regime" in kw:
+        prm, parts = regime_cases.CASES[kw["regime"]](cfgmod, geom, "small")
+        return prm, parts, oracle.neighbor_search(parts["pos"], parts["n_fluid"], parts["n_total"], prm.h, prm.DL)
     make = make_variant if kw.pop("variant", False) else make_case
     prm, parts = make(cfgmod, geom, seed=100 + request.param, **kw)
     nb = oracle.neighbor_search(parts["pos"], parts["n_fluid"], parts["n_total"], prm.h, prm.DL)
@@ -116,6 +126,46 @@ def test_integration_1st_2nd_verlet(case, mex, oracle):
     gotv = mex.sph_physics_shell_mex("integration_verlet", *p6, *common)
     for g, r, name in zip(gotv, refv, ("rho", "p", "pos", "vel", "drho", "force")):
         assert_close(g, r, rtol=1e-10, atol=at[name], name="verlet." + name)
+
+
+def closing_floor_inputs(cfgmod, geom, oracle):
+    """The small `capped` state and a dt so large that integration_verlet's CLOSING density update rho_half + dt / 2 drho_dt
+    falls below 1e-10 on some rows (sph_physics_mex.c:1440-1450; the resident loop cannot get there: its acoustic dt keeps
+    dt / 2 drho_dt / rho below 1).  dt_big starts at 4 rho0 / max(-drho_dt) of one step at the standard dt; the velocity a step
+    ends with, and so its drho_dt, grows with dt, and at that dt_big (8.0) the oracle floors 304 of the 600 rows at the end and
+    194 at the half step: dt_big is halved until the oracle floors fewer than half the rows at the end and none at the half
+    step (1.005: 270 rows), so that both sides of the closing branch stay well populated and it alone is what is tested.
+    -> nb, the arguments after the pair list, dt_big, the oracle's result at dt_big, the fluid rows it floored at the end."""
+    prm, parts = regime_cases.capped(cfgmod, geom, "small")
+    nf, nt = parts["n_fluid"], parts["n_total"]
+    nb = oracle.neighbor_search(parts["pos"], nf, nt, prm.h, prm.DL)
+    rho, Vol, B = oracle.density_correction(nb, parts["mass"], nf, nt, prm.rho0, prm.h, prm.inv_sigma0)
+    fp = _force_prior(prm, parts, nb, nf, nt, Vol, B, oracle)
+    args = lambda dt: (Vol, B, rho, parts["mass"], parts["pos"], parts["vel"], parts["drho_dt"], fp, dt, nf, nt, prm.rho0,
+                       prm.p0, prm.c_f, parts["wall_vel"])
+    drho_new = oracle.integration_verlet(nb, *args(0.25 * prm.h / (prm.c_f + 1.0)))[4]
+    dt_big = 4.0 * prm.rho0 / float(np.max(-drho_new[:nf]))
+    for _ in range(8):
+        ref = oracle.integration_verlet(nb, *args(dt_big))
+        floored = np.flatnonzero((ref[0][:nf] == prm.rho0) & (ref[1][:nf] == 0.0))
+        if len(floored) < nf // 2 and np.all(rho[:nf] + 0.5 * dt_big * parts["drho_dt"][:nf] >= 1e-10):
+            break
+        dt_big *= 0.5
+    return prm, parts, nb, args(dt_big), dt_big, ref, floored
+
+
+def test_integration_verlet_closing_density_floor(cfgmod, geom, mex, oracle):
+    prm, parts, nb, common, dt_big, ref, floored = closing_floor_inputs(cfgmod, geom, oracle)
+    nf = parts["n_fluid"]
+    assert 1 <= len(floored) < nf // 2, len(floored)
+    # floored at the END: the half-step density of these rows was a regular one
+    rho_half = common[2][:nf] + 0.5 * dt_big * parts["drho_dt"][:nf]
+    assert np.all(rho_half >= 1e-10)
+    got = mex.sph_physics_shell_mex("integration_verlet", *(nb[:5] + (nb[6],)), *common)
+    at = field_atol(prm, parts, nb, dt_big)
+    for g, r, name in zip(got, ref, ("rho", "p", "pos", "vel", "drho", "force")):
+        assert_close(g, r, rtol=1e-10, atol=at[name], name="verlet(dt_big)." + name)
+    assert np.all(got[0][floored] == prm.rho0) and np.all(got[1][floored] == 0.0)
 
 
 def test_advance_shell_step(case, mex, oracle):

@@ -12,7 +12,15 @@ limit: 35 steps of the moving-wall variant across its re-binnings, every field a
 test_gpu_resident.py.  Each test asserts that the forms it means were in fact chosen (Context.kernel_forms / schedule).
 kernel_forms has no entry for lazy_out: for no_lazy_out only its precondition (walk kernels) can be asserted.  After a child
 that ends by a signal, an abort or its time limit no further child is started: that end is to be diagnosed from what the child
-printed, not run again."""
+printed, not run again.
+
+The default state flows to the right, stays two decades below the cap of the Riemann dissipation and is limited by the
+acoustic dt on every step, so a wrong folded constant of the cap, a wrong wrap at x < 0 or a wrong viscous limit in one of the
+force-pass, list or clock forms selected here would change nothing above.  test_switch_set_matches_oracle_left_capped runs the
+sets that change the force pass, the lists or the clock once more on regime_cases.left_capped at the worker's size (--case):
+the same variant mirrored, c_f = 0.3.  Over its 35 steps the oracle counts 266 to 531 fluid pairs on the cap, 130 crossings of
+the seam to the left and the viscous limit on every step (tests/test_regime_cases.py asserts it); the flow outruns the cell
+skin, so drift-forced re-binnings and their cool-down are on the way as well."""
 import json
 import os
 import subprocess
@@ -46,13 +54,31 @@ SETS = [
 ]
 
 
+# the sets that change the force pass, the lists or the clock
+REGIME_SETS = [s for s in SETS if (s[0], s[1], s[2]) in {
+    ("", 2, False), ("", 16, False), ("tiles_be_from_1", 2, False), ("tiles_be_from_1,no_coded_lists", 2, False),
+    ("no_lds_tiles", 2, False), ("no_tail_clock", 2, False), ("no_tail_clock", 16, False), ("", 2, True)}]
+assert len(REGIME_SETS) == 8
+
+
 @pytest.mark.parametrize("switches,lpp,dynamic,forms,fuse_ea,tail_clock", SETS,
                          ids=[f"{s or 'none'}-lpp{l}{'-dyn' if d else ''}" for s, l, d, *_ in SETS])
 def test_switch_set_matches_oracle(switches, lpp, dynamic, forms, fuse_ea, tail_clock):
+    _run_set(switches, lpp, dynamic, forms, fuse_ea, tail_clock, "")
+
+
+@pytest.mark.parametrize("switches,lpp,dynamic,forms,fuse_ea,tail_clock", REGIME_SETS,
+                         ids=[f"{s or 'none'}-lpp{l}{'-dyn' if d else ''}" for s, l, d, *_ in REGIME_SETS])
+def test_switch_set_matches_oracle_left_capped(switches, lpp, dynamic, forms, fuse_ea, tail_clock):
+    _run_set(switches, lpp, dynamic, forms, fuse_ea, tail_clock, "left_capped")
+
+
+def _run_set(switches, lpp, dynamic, forms, fuse_ea, tail_clock, case):
     if _abnormal:
         pytest.fail(f"not started: an earlier child ended abnormally ({_abnormal[0]})")
     env = dict(os.environ, SPHX_DEBUG_SWITCHES=switches)
     cmd = [sys.executable, WORKER, "--lpp", str(lpp), "--steps", "35"] + (["--dynamic"] if dynamic else [])
+    cmd += ["--case", case] if case else []
     try:
         r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=CHILD_SECONDS)
     except subprocess.TimeoutExpired as e:
@@ -64,7 +90,9 @@ def test_switch_set_matches_oracle(switches, lpp, dynamic, forms, fuse_ea, tail_
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-3000:] + r.stderr[-3000:]
     out = json.loads(lines[0])
-    assert out["switches"] == switches and out["steps"] == 35
+    assert out["switches"] == switches and out["steps"] == 35 and out["case"] == case
+    print(f"[switches] {case or 'variant'} [{switches}] lpp {lpp}{' dynamic' if dynamic else ''}: rebins {out['rebins']} forced "
+          f"{out['forced_rebuilds']} worst {max(out['errors'].values()):.1e} {out['errors']}")
     assert out["forms"] == forms, out["forms"]
     assert (out["schedule"]["fuse_ea"], out["schedule"]["tail_clock"], out["schedule"]["dynamic"]) == (fuse_ea, tail_clock, int(dynamic)), out["schedule"]
     assert out["rebins"] + out["forced_rebuilds"] >= 2, out      # 35 steps: re-binned at least twice on every schedule

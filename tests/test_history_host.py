@@ -144,3 +144,24 @@ def test_figures_honour_unequal_dt_weights(cfgmod, driver):
     assert f["tau_top_mean"] == (1 * 8 + 0 - 4 * 2) / 8
     assert f["u_bulk_mean"] == 0.5
     np.testing.assert_allclose(f["u_bulk_dev"], (0.5 - ub) / ub, rtol=1e-15)
+
+
+def test_figures_of_a_mirrored_flow(cfgmod, driver):
+    """g -> -g, tau and u_bulk -> their negatives: the means and the targets flip their sign, the relative deviations and
+    t_settled (|tau - tau_target| over |tau_target|) stay."""
+    T, dt, tol = 0.4, 1e-3, 0.02
+    t = dt * np.arange(1, 2001)
+    out = {}
+    for sign in (1, -1):
+        prm = cfgmod.params_from_values(dp=0.05, DL=3.0, U_bulk=sign * 0.666667)
+        tau, ub = _exact(prm)
+        assert np.sign(tau) == sign and np.sign(ub) == sign
+        hist = _hist(t, dt, tau * (1.0 - np.exp(-t / T)), tau * (1.0 + np.exp(-2.0 * t / T)), ub * (1.0 - np.exp(-t / T)))
+        out[sign] = driver.history_figures(prm, hist, t_from=0.5, tol=tol)
+    a, b = out[1], out[-1]
+    assert np.isfinite(a["t_settled"]) and a["t_settled"] > 1.0 and b["t_settled"] == a["t_settled"]
+    for k in ("tau_target", "u_bulk_exact", "tau_bottom_mean", "tau_top_mean", "u_bulk_mean"):
+        assert a[k] > 0 and abs(b[k] + a[k]) <= 1e-12 * a[k], (k, a[k], b[k])
+    for k in ("tau_bottom_dev", "tau_top_dev", "u_bulk_dev"):
+        assert abs(b[k] - a[k]) <= 1e-12 * abs(a[k]), (k, a[k], b[k])
+    assert a["n_records"] == b["n_records"]

@@ -206,6 +206,32 @@ def test_sort_keeps_physics(cfgmod, geom, oracle):
         assert_close(back, a[k], rtol=1e-9, atol_scale=1e-11, name=k)
 
 
+def test_dt_rule_equals_the_drivers_on_every_limit(cfgmod, geom, oracle, driver):
+    """oracle.verlet_time_step against driver.verlet_time_step (the dt rule on the reference's side of the time loop of
+    test_reference_anchor.py), bit for bit, where each of the four limits binds and at the floor of 1e-12.  The body-limited
+    input is regime_cases.body's (gravity_g set directly, which no config derives)."""
+    import regime_cases as rc
+    seen = set()
+    for name, builder, remain in (("A", rc.default, 1.0), ("V", rc.viscous, 1.0), ("B", rc.body, 1.0), ("R", rc.default, 1e-5),
+                                  ("floor", rc.default, 0.0), ("floor", rc.body, -3e-13), ("B", rc.body, 1e9),
+                                  ("V", rc.viscous_plain, 1e9), ("A", rc.left_capped, 1.0)):
+        prm, parts = builder(cfgmod, geom, "small")
+        nf = parts["n_fluid"]
+        got = oracle.verlet_time_step(parts["vel"], nf, prm.c_f, prm.h, prm.nu, prm.gravity_g, remain)
+        want = driver.verlet_time_step(parts["vel"][:nf], prm.c_f, prm.h, prm.nu, prm.gravity_g, remain)
+        assert np.float64(got).tobytes() == np.float64(want).tobytes(), (name, got, want)
+        vmax = float(np.max(np.hypot(parts["vel"][:nf, 0], parts["vel"][:nf, 1])))
+        limit = dict(A=0.25 * prm.h / (prm.c_f + vmax), V=rc.dt_viscous(prm), B=rc.dt_body(prm), R=remain, floor=1e-12)[name]
+        assert abs(got - limit) <= 1e-13 * limit, (name, got, limit)     # the limit meant is the one that binds
+        seen.add(name)
+    assert seen == {"A", "V", "B", "R", "floor"}
+    # the negated body force gives the same dt, and no fluid rows at all leave v_max at 0
+    prm, parts = rc.body(cfgmod, geom, "small")
+    for g in (prm.gravity_g, -prm.gravity_g):
+        assert oracle.verlet_time_step(parts["vel"], 0, prm.c_f, prm.h, prm.nu, g, 1.0) == \
+            driver.verlet_time_step(parts["vel"][:0], prm.c_f, prm.h, prm.nu, g, 1.0) == rc.dt_body(prm)
+
+
 # Realisations recorded in this container (round 4; oracle, lattice at rest -> t = 20 s; L2 of the y-binned u_x profile at
 # t = 16, 17, 18, 19, 20 s | L2 of the profile AVERAGED over those five instants | steps):
 #   dp 0.05 (reference: 19 771 steps, 1.42 % at 20 s)

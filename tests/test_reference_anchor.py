@@ -15,7 +15,8 @@ import pytest
 
 import mex_mock
 import reference_ids_worker
-from helpers import make_case, make_variant, with_density_floor
+import regime_cases
+from helpers import make_case, make_variant
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "reference_small.npz")
@@ -41,11 +42,6 @@ def _outside(cfgmod, geom):
     return prm, parts
 
 
-def _density_floor(cfgmod, geom):
-    prm, parts = make_variant(cfgmod, geom, dp=0.05, DL=1.5, seed=109, rho0=2.5, transport_coeff=0.1)
-    return prm, with_density_floor(parts)
-
-
 CASES = {
     "lattice": lambda c, g: make_case(c, g, dp=0.05, DL=3.0, jitter=0.0, developed=False, seed=100),
     "dp004_jitter03": lambda c, g: make_case(c, g, dp=0.04, DL=3.0, jitter=0.3, seed=102),
@@ -55,13 +51,19 @@ CASES = {
     "DH08_rho037": lambda c, g: make_case(c, g, dp=0.04, DL=1.3, DH=0.8, seed=106, rho0=0.37, mu=0.2, c_f=20.0),
     "moving_walls": lambda c, g: make_variant(c, g, dp=0.05, DL=1.5, seed=107, rho0=2.5, transport_coeff=0.1),
     "moving_walls_DH08": lambda c, g: make_variant(c, g, dp=0.04, DL=1.3, DH=0.8, seed=108, rho0=0.37),
-    "density_floor": _density_floor,
+    "density_floor": lambda c, g: regime_cases.floor(c, g, "small"),
     "coincident_isolated": _defects,
     "outside_cell_rows": _outside,
     "two_columns_07": lambda c, g: make_case(c, g, dp=0.1, DL=0.7, jitter=0.25, seed=9),
     "two_columns_06": lambda c, g: make_case(c, g, dp=0.1, DL=0.6, jitter=0.25, seed=9),
     "one_column_04": lambda c, g: make_case(c, g, dp=0.1, DL=0.4, jitter=0.2, seed=4, developed=False),
     "one_column_02": lambda c, g: make_case(c, g, dp=0.1, DL=0.2, jitter=0.2, seed=4, developed=False),
+    # the regimes of tests/regime_cases.py: leftward flow, capped Riemann dissipation, viscous-limited dt (its floor case is
+    # density_floor above)
+    "leftward": lambda c, g: regime_cases.leftward(c, g, "small"),
+    "capped": lambda c, g: regime_cases.capped(c, g, "small"),
+    "left_capped": lambda c, g: regime_cases.left_capped(c, g, "small"),
+    "viscous": lambda c, g: regime_cases.viscous(c, g, "small"),
 }
 
 
@@ -197,6 +199,9 @@ def loop_differences(driver, ref, oracle, cfgmod, prm_kw, parts, n_steps):
 LOOP_CASES = {
     "default": (False, dict(dp=0.05, DL=1.5, jitter=0.2, seed=7), {}),
     "moving_walls": (True, dict(dp=0.05, DL=1.5, jitter=0.2, seed=7), dict(rho0=2.5, mu=0.07, c_f=12.0, U_bulk=0.4, transport_coeff=0.1)),
+    "leftward": (False, dict(dp=0.05, DL=1.5, jitter=0.2, seed=7), dict(U_bulk=-0.666667)),
+    "capped": (False, dict(dp=0.05, DL=1.5, jitter=0.2, seed=7), dict(c_f=0.3)),
+    "viscous": (False, dict(dp=0.05, DL=1.5, jitter=0.2, seed=7), dict(mu=2.0)),
 }
 
 

@@ -113,6 +113,10 @@ def test_slab_hip_two_ranks_half_million_particles():
     (2, 0.04, 3.0, 42, dict(calls=[2, 40], graph_after=0, rebuild_every=8, skin_h=0.05)),  # drift-triggered re-binnings inside replays
     # moving walls, uneven mass, rho0 = 2.5 (helpers.make_variant): wall velocities and masses go through slab_setup's own upload
     (2, 0.05, 3.0, 27, dict(moving_walls=True, rebuild_every=5)),
+    # the same variant mirrored (U_bulk < 0, the walls' velocities negated): ownership migrates to the LEFT neighbour and across
+    # rank 0's left edge, the periodic wrap is the one of x < 0
+    (2, 0.05, 3.0, 27, dict(leftward=True, rebuild_every=5)),
+    (3, 0.05, 4.5, 23, dict(leftward=True, rebuild_every=4, overlap="always")),
 ])
 def test_slab_native_ring_in_one_process(world, dp, DL, steps, kw):
     """The library's own step loop (sphx_slab_group_run: every slab of the ring in this process, device-to-device
@@ -129,6 +133,10 @@ def test_slab_native_ring_in_one_process(world, dp, DL, steps, kw):
     if kw.pop("moving_walls", False):
         prm, parts = make_variant(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9,
                                   rho0=2.5, transport_coeff=0.1)
+    elif kw.pop("leftward", False):
+        prm, parts = make_variant(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9,
+                                  U_bulk=-0.666667, top_ux=-0.8, bottom_ux=0.3, rho0=2.5, transport_coeff=0.1)
+        assert prm.gravity_g < 0 and np.all(parts["vel"][:parts["n_fluid"], 0] < 0)
     else:
         prm, parts = make_case(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9)
     nf, nt = parts["n_fluid"], parts["n_total"]
