@@ -412,7 +412,7 @@ int sphx_batch_flow_stats_read(sphx_batch *batch, int band, int capacity, int *n
  *    replayed graphs; enable / disable re-capture them.  Independent of the flow statistics: both may be on at once.
  *  Determinism: no floating-point atomics; two identical runs give bit-identical records.  How the host chunks its calls
  *    changes the summation order of fields 4-7 only (the re-binning phase differs after a stop on the drift bound).
- *  Batches (section 2b) have no step history.
+ *  Batches (section 2b) record one history per member: section 2f.
  *  Errors: SPHX:History:config (every < 1, capacity < 1 or > 1 << 22, non-finite t_from, or the allocation fails: the
  *    context then goes on without a history), SPHX:History:disabled (SPHX_ERR_STATE: a call that needs the history while
  *    it is off), SPHX:History:capacity (the caller's buffer is smaller than n_records); every call on a slab context fails
@@ -495,6 +495,37 @@ int sphx_ctx_field_map_sample(sphx_ctx *ctx);
 int sphx_ctx_field_map_read(sphx_ctx *ctx, int capacity, int *nx, int *ny, double *count, double *sum_w,
                             double *sum_ux, double *sum_uy, double *sum_ux2, double *sum_uy2, int64_t *n_samples,
                             double *t_first, double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2f. Step history of a batch (section 2b): the history of section 2d for every member at once.
+ *
+ *  One config for all members; `capacity` is per member.  Every member has its own record buffer, n_records and
+ *  n_dropped, and is recorded on its own clock with the gating of section 2d, so a member that sits out slots (it reached
+ *  t_target, used up its steps, stopped on the drift bound) records nothing in them and its counters are not touched.  A
+ *  member's records are bit for bit those of a standalone context with the same parameters and config that took the same
+ *  steps: the same workgroups per member, the same runs of particles per workgroup, the same order of the partial sums.
+ *  After a realignment (section 2b) a member's particles are laid out differently, which changes the summation order of
+ *  fields 4-7 only, as a stop on the drift bound does for a context.  With the history on, every step slot of the batch
+ *  ends with one recording launch for all members (k_step_history_b); off, a slot enqueues exactly the launches it does
+ *  without this feature.  Enable / disable wait for the stream and re-capture the batch's graphs.  Independent of the
+ *  batch's flow statistics (section 2c): both may be on at once.
+ *  Memory: n_members * capacity * SPHX_HISTORY_FIELDS doubles.  Besides the per-member bound of section 2d,
+ *  n_members * capacity must not exceed 1 << 24 records (1 GiB); when the buffers do not fit, enable fails and the batch
+ *  goes on without a history.  A refused enable leaves a running history, and its records, untouched.
+ *  Errors: SPHX:Batch:null (NULL batch), SPHX:History:config (as in section 2d, or n_members * capacity > 1 << 24),
+ *  SPHX:History:disabled, SPHX:History:capacity (the caller's capacity is below the largest n_records of any member).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* (Re)configure and empty every member's buffer; waits for the stream. */
+int sphx_batch_history_enable(sphx_batch *batch, const sphx_history_config *cfg);
+/* Stop recording (no-op when off); the records are dropped. */
+int sphx_batch_history_disable(sphx_batch *batch);
+/* One call for all members.  records is [n_members][capacity][SPHX_HISTORY_FIELDS], row-major: member m's records so far,
+ * in step order, fill rows 0 .. n_records[m] - 1 of its block and the other rows are left as they are (NULL: only the
+ * counts are reported and capacity is not checked).  n_records and n_dropped are [n_members]; either may be NULL.  Settles
+ * first, as sphx_batch_download does.  drain != 0: every member's buffer is emptied and its n_dropped zeroed after
+ * copying. */
+int sphx_batch_history_read(sphx_batch *batch, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU).  The channel is cut into n_ranks slabs of whole cell columns; each

@@ -82,6 +82,7 @@ EXPORTS = [
     "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
     "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",
     "sphx_batch_flow_stats_sample", "sphx_batch_flow_stats_read",
+    "sphx_batch_history_enable", "sphx_batch_history_disable", "sphx_batch_history_read",
 ]
 
 _LIB = None
@@ -281,6 +282,34 @@ class Batch:
     def flow_stats(self, band=0) -> list:
         """One profile.flow_stats_profile dict per member."""
         return [flow_stats_profile(self.params[0].DH, **s) for s in self.flow_stats_sums(band)]
+
+    # ---- step history of every member (include/sphx.h section 2f): Context.history_* for all members at once ----
+    def history_enable(self, every=1, capacity=65536, t_from=0.0):
+        """Context.history_enable with one config for all members; `capacity` records per member, each member recorded on
+        its own clock.  n_members * capacity must not exceed 1 << 24."""
+        cfg = history_config(every, capacity, t_from, n_members=self.n_members)
+        check(lib().sphx_batch_history_enable(self._h, C.byref(cfg)))
+
+    def history_disable(self):
+        check(lib().sphx_batch_history_disable(self._h))
+
+    def history_records(self, drain=False) -> list:
+        """-> [(records [n_m x 8] in the order of HISTORY_FIELDS, n_dropped), ...] per member, from one read of all
+        members; drain empties every member's buffer after the copy."""
+        m = self.n_members
+        n, dropped = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
+        pn, pd = n.ctypes.data_as(C.POINTER(C.c_int)), dropped.ctypes.data_as(C.POINTER(C.c_int64))
+        check(lib().sphx_batch_history_read(self._h, C.c_int(0), None, pn, pd, C.c_int(0)))
+        cap = max(int(n.max()), 1)
+        rec = np.zeros((m, cap, len(HISTORY_FIELDS)))
+        want = n.copy()
+        check(lib().sphx_batch_history_read(self._h, C.c_int(cap), ptr(rec), pn, pd, C.c_int(1 if drain else 0)))
+        assert np.array_equal(n, want), (n, want)
+        return [(rec[k, :n[k]].copy(), int(dropped[k])) for k in range(m)]
+
+    def history(self, drain=False) -> list:
+        """One history_dict per member (see Context.history)."""
+        return [history_dict(rec, dropped) for rec, dropped in self.history_records(drain)]
 
 class Context:
     """Device-resident simulation state (sphx_ctx)."""
@@ -595,12 +624,15 @@ def flow_stats_config(n_bins=0, every=1, t_from=0.0, bands=()) -> SphxFlowStatsC
     return cfg
 
 
-def history_config(every=1, capacity=65536, t_from=0.0) -> SphxHistoryConfig:
-    """Checked sphx_history_config; raises SphxError(SPHX:History:config) before anything reaches the device."""
+def history_config(every=1, capacity=65536, t_from=0.0, n_members=1) -> SphxHistoryConfig:
+    """Checked sphx_history_config; raises SphxError(SPHX:History:config) before anything reaches the device.  n_members:
+    the channels that get `capacity` records each (a batch's members)."""
     bad = _config_error("History")
     every = _check_every(every, bad)
     if not _is_int(capacity) or not 1 <= capacity <= 1 << 22:
         raise bad("capacity must be an integer in 1 .. 1 << 22")
+    if n_members * capacity > 1 << 24:
+        raise bad("n_members * capacity must not exceed 1 << 24 records")
     return SphxHistoryConfig(every=every, capacity=int(capacity), t_from=_check_t_from(t_from, bad, finite=True))
 
 

@@ -28,7 +28,7 @@ struct sphx_batch {
     int64_t epoch_slot = 0;           // sched.slot when the members' epochs were set
     int64_t n_realign = 0;
     std::vector<int64_t> pending;     // per member: step count the sphx_batch_enqueue_steps calls since the last sync aim for
-    // (flow statistics, sphx_batch_flow_stats_*: mem[0]->fstats, for all M members)
+    // (flow statistics, sphx_batch_flow_stats_*, and step history, sphx_batch_history_*: mem[0]->fstats / hist, for all M members)
 
     ~sphx_batch()
     {
@@ -229,6 +229,15 @@ FlowStats &batch_stats(sphx_batch *b, bool need_on)
     FlowStats &f = b->mem[0]->fstats;
     sampler_check(kStatsNames, false, f.on, need_on, "batch");
     return f;
+}
+
+// the batch's step history (member 0's, see sphx_ctx::hist)
+History &batch_history(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    History &h = b->mem[0]->hist;
+    sampler_check(kHistoryNames, false, h.on, need_on, "batch");
+    return h;
 }
 
 // argument checks (no device): shared fields, refused modes, the kernel forms members of this size would run
@@ -502,6 +511,37 @@ SPHX_EXPORT int sphx_batch_flow_stats_read(sphx_batch *b, int band, int capacity
     const FlowStats &f = batch_stats(b, true);
     stats_read(f, b->stream, [b] { batch_settle(b); }, band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples,
                t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- step history of every member (include/sphx.h section 2f) ----
+
+SPHX_EXPORT int sphx_batch_history_enable(sphx_batch *b, const sphx_history_config *cfg)
+{
+    SPHX_TRY
+    // (out of device memory: the batch goes on without a history)
+    History &h = batch_history(b, false);
+    history_enable(h, cfg, b->M, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_history_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    History &h = batch_history(b, false);
+    if (h.on) sampler_off(h, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_history_read(sphx_batch *b, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    History &h = batch_history(b, true);
+    batch_settle(b);  // (the records of everything enqueued)
+    h.read(b->stream, capacity, records, n_records, n_dropped, drain != 0);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -1,7 +1,7 @@
-// sphx_history.hpp -- the step history of a resident context (include/sphx.h section 2d): a slot sampler
-// (sphx_slot_sample.hpp) that reduces the state the step left to one record of kHistoryFields doubles -- step, t, dt, vmax of
-// the device clock, the wall shear of SPH_Poiseuille.m:281-283, the kinetic energy and the bulk velocity -- and appends it to
-// a record buffer in device memory.
+// sphx_history.hpp -- the step history of a resident context (include/sphx.h section 2d) and of every member of a batch
+// (section 2f, k_step_history_b): a slot sampler (sphx_slot_sample.hpp) that reduces the state the step left to one record
+// of kHistoryFields doubles -- step, t, dt, vmax of the device clock, the wall shear of SPH_Poiseuille.m:281-283, the kinetic
+// energy and the bulk velocity -- and appends it to a record buffer in device memory.
 //
 // The wall-shear term is k_wall_shear's, term for term (sphx_kernels.hpp; kept as a copy here so that the monitor's kernel
 // stays what it is): the wall cells around the cell a particle was binned into, new pos / vel, Vol / B of the step just
@@ -26,7 +26,8 @@ constexpr int kHistoryBlock = 512;
 constexpr int kHistoryMaxBlocks = 256;               // one workgroup per CU at most: every one of them draws a ticket
 constexpr int kHistoryPerThread = 4;                 // particles a thread takes before another workgroup is added: up to
                                                      // 2 048 particles ONE workgroup writes the record by itself
-constexpr int kHistoryMaxCapacity = 1 << 22;         // records (256 MB)
+constexpr int kHistoryMaxCapacity = 1 << 22;         // records (256 MB) of one channel
+constexpr long long kHistoryMaxTotal = 1ll << 24;    // records (1 GiB) of all members of a batch together
 
 // the counters of the record buffer, in a block of their own (Clock must not grow, see sphx_kernels.hpp); only the last
 // workgroup out of a launch touches them
@@ -87,9 +88,10 @@ __device__ __forceinline__ void history_wall_terms(const Grid &g, const Phys &ph
     });
 }
 
-// q: parity of the step slot this launch closes; s is the state the step left, t holds its Vol / B.
-__global__ __launch_bounds__(kHistoryBlock) void k_step_history(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
-                                                                 FluidTmp t, Walls w, HistoryArgs a)
+// The record of one channel closing the step slot of parity q, on clock clk, shared by the gridDim.x workgroups of a grid row;
+// s is the state the step left, t holds its Vol / B; a's records / part / head are that channel's own.
+__device__ __forceinline__ void step_history_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
+                                                  const FluidTmp &t, const Walls &w, const HistoryArgs &a)
 {
     if (!slot_due(clk, q, a.every, a.t_from)) return;
     const int n = clk->n;
@@ -151,6 +153,29 @@ __global__ __launch_bounds__(kHistoryBlock) void k_step_history(const Clock *clk
         h->n_dropped += 1;
     }
     if (gridDim.x > 1) __hip_atomic_store(&h->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// q: parity of the step slot this launch closes
+__global__ __launch_bounds__(kHistoryBlock) void k_step_history(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
+                                                                 FluidTmp t, Walls w, HistoryArgs a)
+{
+    step_history_body(clk, q, g, ph, s, t, w, a);
+}
+
+// batch (sphx_batch_history_*): member m = blockIdx.y records its own state (member_set / member_tmp of the views, which are
+// member 0's) on its own clock and parameters into its own block of records (m * capacity * kHistoryFields), its own partials
+// (m * kHistoryMaxBlocks * kHistorySums) and its own head: ticket, n_records and n_dropped are per member.  gridDim.x is the
+// workgroup count of a context of this size, each workgroup takes the same contiguous run and the winner adds the partials
+// in the same order: a member's record is bit for bit a standalone context's.
+__global__ __launch_bounds__(kHistoryBlock) void k_step_history_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w,
+                                                                   HistoryArgs a)
+{
+    const int m = (int)blockIdx.y;
+    const Phys ph = mb.ph[m];
+    a.records += (size_t)m * (size_t)a.capacity * kHistoryFields;
+    a.part += (size_t)m * kHistoryMaxBlocks * kHistorySums;
+    a.head += m;
+    step_history_body(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, a);
 }
 
 }  // namespace sphx

@@ -33,15 +33,21 @@ struct FlowStats {
               double *t_last) const;
 };
 
-// Step history (sphx_ctx_history_*, sphx_history.hpp)
+// Step history (sphx_ctx_history_*, sphx_batch_history_*; sphx_history.hpp) of a context or of the M members of a batch: one
+// configuration, member m's records at m * cfg.capacity * kHistoryFields, its partials at m * kHistoryMaxBlocks *
+// kHistorySums, its head at m.
 struct History {
     bool on = false;
+    int members = 1;
     sphx_history_config cfg{};
     DevBuf<double> records, part;
     DevBuf<HistoryHead> head;
 
+    static void check(const sphx_history_config *cfg, int M);
+    void alloc(const sphx_history_config &checked, int M);
     void zero(hipStream_t st) { head.zero(st); }  // (the counters: records beyond n_records are never read)
     void release() { records.release(); part.release(); head.release(); }
+    void read(hipStream_t st, int capacity, double *records, int *n_records, int64_t *n_dropped, bool drain);
 };
 
 // Velocity-field map (sphx_ctx_field_map_*, sphx_field_map.hpp)

@@ -126,22 +126,23 @@ void launch_flow_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
     launch_forms(c, "k_flow_stats", Forms{k_flow_stats, k_flow_stats_b}, blocks, kStatsBlock, f.shmem(), q, a);
 }
 
-// k_step_history behind step slot q, which left state s: Vol / B of the finished step are where sphx_ctx_monitor looks them
-// up after it: the record buffers of the step's parity (fuse_ea), in the order of the layout the step ran in, so read
-// through src_of when the slot re-binned.  The static schedule knows that when the launch is made (or captured); a dynamic
-// context re-bins in place and says so in Clock::fresh.
+// k_step_history behind step slot q, which left state s -- of a batch: member 0's -- into c->hist: Vol / B of the finished step
+// are where sphx_ctx_monitor looks them up after it: the record buffers of the step's parity (fuse_ea), in the order of the
+// layout the step ran in, so read through src_of when the slot re-binned.  The static schedule knows that when the launch is
+// made (or captured); a dynamic context re-bins in place and says so in Clock::fresh.  A batch runs the static schedule, and
+// its shared slot's `rebuild` holds for every member that runs in the slot.
 void launch_history(sphx_ctx *c, int q, const FluidSet &s, bool rebuild)
 {
     const History &h = c->hist;
-    single_form_only(c, "k_step_history");
     HistoryArgs a{};
     a.records = h.records.get(); a.part = h.part.get(); a.head = h.head.get();
     a.t_from = h.cfg.t_from; a.capacity = h.cfg.capacity; a.every = h.cfg.every;
     a.src = c->dyn ? kHistoryByClock : (rebuild ? kHistorySrcOf : kHistoryInPlace);
+    // workgroups of one channel's record
     const unsigned blocks =
         std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kHistoryBlock * kHistoryPerThread), 1u, (unsigned)kHistoryMaxBlocks);
-    launch(c, "k_step_history", k_step_history, dim3(blocks), dim3(kHistoryBlock), (const Clock *)c->clock.get(), q, c->grid,
-           c->phys, s, c->tmp_par[c->fuse_ea ? q : 0], c->walls, a);
+    launch_forms(c, "k_step_history", Forms{k_step_history, k_step_history_b}, blocks, kHistoryBlock, 0, q, c->grid,
+                 per_member(c->phys), s, c->tmp_par[c->fuse_ea ? q : 0], c->walls, a);
 }
 
 // k_field_map on state s (pos, vel and the cell ranges of the layout it is stored in) into c->fmap
@@ -311,20 +312,76 @@ SPHX_EXPORT int sphx_ctx_flow_stats_read(sphx_ctx *c, int band, int capacity, in
 
 // ---- step history ----
 
+// every check of a configuration for M channels; SPHX:History:config errors
+void History::check(const sphx_history_config *cfg, int M)
+{
+    require(cfg != nullptr, "SPHX:History:config", "config must not be NULL");
+    require(cfg->every >= 1, "SPHX:History:config", "every must be >= 1");
+    require(cfg->capacity >= 1 && cfg->capacity <= kHistoryMaxCapacity, "SPHX:History:config", "capacity must be 1 .. 1 << 22 records");
+    require((int64_t)M * cfg->capacity <= kHistoryMaxTotal, "SPHX:History:config",
+            "n_members * capacity must not exceed 1 << 24 records");
+    require(std::isfinite(cfg->t_from), "SPHX:History:config", "t_from must be finite");
+}
+
+// the checked configuration, and records, partials and heads for M members
+void History::alloc(const sphx_history_config &checked, int M)
+{
+    records.alloc((size_t)M * checked.capacity * kHistoryFields);
+    part.alloc((size_t)M * kHistoryMaxBlocks * kHistorySums);
+    head.alloc(M);
+    cfg = checked;
+    members = M;
+}
+
+// Every member's counts (n_records[m], n_dropped[m], where given) and, with `records`, its filled rows into
+// records[m][0 .. n_records[m])[kHistoryFields] of a [members][capacity][kHistoryFields] array; drain empties every buffer.
+// SPHX:History:capacity when `records` is given and capacity is below the largest count: nothing is copied or drained then.
+void History::read(hipStream_t st, int capacity, double *out, int *n_records, int64_t *n_dropped, bool drain)
+{
+    const int M = members;
+    std::vector<HistoryHead> h(M);
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(HistoryHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    long long most = 0;
+    for (int m = 0; m < M; ++m) {
+        const long long n = h[m].n_records;
+        if (n < 0 || n > (long long)cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:History:state", "internal: record count out of range");
+        most = std::max(most, n);
+    }
+    require(out == nullptr || (long long)capacity >= most, "SPHX:History:capacity", "capacity is smaller than the number of records");
+    if (out && most > 0) {
+        for (int m = 0; m < M; ++m)  // only the filled rows of each member's block
+            if (h[m].n_records > 0)
+                SPHX_HIP(hipMemcpyAsync(out + (size_t)m * capacity * kHistoryFields, records.get() + (size_t)m * cfg.capacity * kHistoryFields,
+                                        (size_t)h[m].n_records * kHistoryFields * sizeof(double), hipMemcpyDeviceToHost, st));
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+    for (int m = 0; m < M; ++m) {
+        if (n_records) n_records[m] = (int)h[m].n_records;
+        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
+    }
+    if (drain) {
+        zero(st);
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+}
+
+namespace {
+
+// enable for M members on schedule s: every check of cfg first
+void history_enable(History &h, const sphx_history_config *cfg, int M, Schedule &s, hipStream_t st)
+{
+    History::check(cfg, M);
+    sampler_on(h, kHistoryNames, s, st, [&] { h.alloc(*cfg, M); });
+}
+
+}  // namespace
+
 SPHX_EXPORT int sphx_ctx_history_enable(sphx_ctx *c, const sphx_history_config *cfg)
 {
     SPHX_TRY
     History &h = sampler_of(c, &sphx_ctx::hist, kHistoryNames, false);
-    require(cfg != nullptr, "SPHX:History:config", "config must not be NULL");
-    require(cfg->every >= 1, "SPHX:History:config", "every must be >= 1");
-    require(cfg->capacity >= 1 && cfg->capacity <= kHistoryMaxCapacity, "SPHX:History:config", "capacity must be 1 .. 1 << 22 records");
-    require(std::isfinite(cfg->t_from), "SPHX:History:config", "t_from must be finite");
-    sampler_on(h, kHistoryNames, c->sched, c->stream, [&] {
-        h.records.alloc((size_t)cfg->capacity * kHistoryFields);
-        h.part.alloc((size_t)kHistoryMaxBlocks * kHistorySums);
-        h.head.alloc(1);
-        h.cfg = *cfg;
-    });
+    history_enable(h, cfg, 1, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -343,19 +400,7 @@ SPHX_EXPORT int sphx_ctx_history_read(sphx_ctx *c, int capacity, double *records
     SPHX_TRY
     History &h = sampler_of(c, &sphx_ctx::hist, kHistoryNames, true);
     settle_owed(c);  // (the records of everything enqueued)
-    HistoryHead head{};
-    SPHX_HIP(hipMemcpyAsync(&head, h.head.get(), sizeof(head), hipMemcpyDeviceToHost, c->stream));
-    SPHX_HIP(hipStreamSynchronize(c->stream));
-    const long long n = head.n_records;
-    if (n < 0 || n > (long long)h.cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:History:state", "internal: record count out of range");
-    require(records == nullptr || (long long)capacity >= n, "SPHX:History:capacity", "capacity is smaller than the number of records");
-    if (records && n > 0) {
-        SPHX_HIP(hipMemcpyAsync(records, h.records.get(), (size_t)n * kHistoryFields * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        SPHX_HIP(hipStreamSynchronize(c->stream));
-    }
-    if (n_records) *n_records = (int)n;
-    if (n_dropped) *n_dropped = (int64_t)head.n_dropped;
-    if (drain) sampler_zero(h, c->stream);
+    h.read(c->stream, capacity, records, n_records, n_dropped, drain != 0);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -330,6 +330,39 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                      time_avg=time_avg, history=history, field_avg=field_avg)
 
 
+def _batch_inputs(prms, parts_list):
+    """What the batch drivers ask of their (non-empty) inputs: one set of output points, one particle set per member."""
+    p0 = prms[0]
+    for k, p in enumerate(prms):
+        if p.output_interval != p0.output_interval or p.t_end != p0.t_end:
+            raise ValueError(f"member {k}: output_interval / t_end differ from member 0 (members share the output points)")
+    parts_list = [init_particles(p) for p in prms] if parts_list is None else list(parts_list)
+    if len(parts_list) != len(prms):
+        raise ValueError("parts_list needs one particle set per parameter set")
+    return parts_list
+
+
+def _batch_policy(b):
+    info = b.info()
+    return dict(rebuild_every=info["rebuild_every"], skin=info["skin"], forced_rebuilds=info["forced_rebuilds"],
+                realignments=info["realignments"])
+
+
+def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
+    """Member m's RunResult at the end of a batch run: final state, profile and L2, tau of the last step."""
+    tau_b, tau_t, _ = b.monitor(m, tau=True)
+    d = b.download(m, fields=("pos", "vel"))
+    pos, vel = d["pos"], d["vel"]
+    fluid_pos = pos[:nf].copy()
+    fluid_pos[:, 0] = np.mod(fluid_pos[:, 0], prm.DL)
+    y_mid, u_mean, u_exact = final_profile(fluid_pos, vel[:nf, 0], prm)
+    s = st[m] if st else dict(t=0.0, step=0)
+    return RunResult(prm=prm, n_fluid=nf, n_total=nt, t=s["t"], steps=int(s["step"]), wall_seconds=wall, pos=pos, vel=vel,
+                     y_mid=y_mid, u_mean=u_mean, u_exact=u_exact, L2_error=l2_error(u_mean, u_exact),
+                     profile_times=list(times), tau_bottom=tau_b, tau_top=tau_t,
+                     tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2, grid_policy=dict(policy), **extra)
+
+
 def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,
               restart_path=None, postprocess_path=None, average_from=None, log=None, history_every=None):
     """run() for M channels of one geometry stepped together as one batch (capi.Batch, include/sphx.h section 2b): a
@@ -345,16 +378,11 @@ def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, st
     if average_from is not None:
         raise ValueError("run_batch has no time averaging yet (flow statistics are a single-context feature)")
     if history_every is not None:
-        raise ValueError("run_batch has no step history (the history is a single-context feature)")
+        raise ValueError("run_batch records no step history (run_sweep does, for every member)")
     if not prms:
         raise ValueError("run_batch needs at least one parameter set")
     p0 = prms[0]
-    for k, p in enumerate(prms):
-        if p.output_interval != p0.output_interval or p.t_end != p0.t_end:
-            raise ValueError(f"member {k}: output_interval / t_end differ from member 0 (members share the output points)")
-    parts_list = [init_particles(p) for p in prms] if parts_list is None else list(parts_list)
-    if len(parts_list) != len(prms):
-        raise ValueError("parts_list needs one particle set per parameter set")
+    parts_list = _batch_inputs(prms, parts_list)
     nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
     M = len(prms)
     n_bins = n_profile_bins(p0.DH, p0.dp)
@@ -427,18 +455,13 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
     lattice.  Returns an EnsembleResult."""
     prms = list(prms)
     if history_every is not None:
-        raise ValueError("run_ensemble has no step history (the history is a single-context feature)")
+        raise ValueError("run_ensemble records no step history (run_sweep does, for every member)")
     if not prms:
         raise ValueError("run_ensemble needs at least one parameter set")
     if average_from is None or np.isnan(float(average_from)):
         raise ValueError("run_ensemble needs average_from (the start of the averaging window)")
     p0 = prms[0]
-    for k, p in enumerate(prms):
-        if p.output_interval != p0.output_interval or p.t_end != p0.t_end:
-            raise ValueError(f"member {k}: output_interval / t_end differ from member 0 (members share the output points)")
-    parts_list = [init_particles(p) for p in prms] if parts_list is None else list(parts_list)
-    if len(parts_list) != len(prms):
-        raise ValueError("parts_list needs one particle set per parameter set")
+    parts_list = _batch_inputs(prms, parts_list)
     nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
     M = len(prms)
     n_bins = n_profile_bins(p0.DH, p0.dp)
@@ -460,25 +483,10 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
             if log:
                 log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
         wall = time.perf_counter() - t0
-        info = b.info()
         whole, mid = b.flow_stats_sums(0), b.flow_stats_sums(1)
-        policy = dict(rebuild_every=info["rebuild_every"], skin=info["skin"], forced_rebuilds=info["forced_rebuilds"],
-                      realignments=info["realignments"])
-        members = []
-        for m, prm in enumerate(prms):
-            tau_b, tau_t, _ = b.monitor(m, tau=True)
-            d = b.download(m, fields=("pos", "vel"))
-            pos, vel = d["pos"], d["vel"]
-            fluid_pos = pos[:nf].copy()
-            fluid_pos[:, 0] = np.mod(fluid_pos[:, 0], prm.DL)
-            y_mid, u_mean, u_exact = final_profile(fluid_pos, vel[:nf, 0], prm)
-            s = st[m] if st else dict(t=0.0, step=0)
-            ta = time_average(prm, flow_stats_profile(prm.DH, **whole[m]), flow_stats_profile(prm.DH, **mid[m]))
-            members.append(RunResult(prm=prm, n_fluid=nf, n_total=nt, t=s["t"], steps=int(s["step"]), wall_seconds=wall,
-                                     pos=pos, vel=vel, y_mid=y_mid, u_mean=u_mean, u_exact=u_exact,
-                                     L2_error=l2_error(u_mean, u_exact), profile_times=list(times), tau_bottom=tau_b,
-                                     tau_top=tau_t, tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2,
-                                     grid_policy=dict(policy), time_avg=ta))
+        policy = _batch_policy(b)
+        members = [_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, time_avg=time_average(
+            prm, flow_stats_profile(prm.DH, **whole[m]), flow_stats_profile(prm.DH, **mid[m]))) for m, prm in enumerate(prms)]
     pooled = None
     if all(getattr(p, k) == getattr(p0, k) for p in prms for k in _PHYSICS):
         pw, pm = pool_flow_stats(p0.DH, whole), pool_flow_stats(p0.DH, mid)
@@ -487,3 +495,86 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
         pooled.update(u_mean_se=pw["u_mean_se"], L2_members=L2s, L2_mean=float(np.mean(L2s)),
                       L2_std=float(np.std(L2s, ddof=1)) if M > 1 else float("nan"))
     return EnsembleResult(members=members, pooled=pooled, wall_seconds=wall, grid_policy=policy)
+
+
+@dataclass
+class SweepResult:
+    members: list        # one RunResult per member: final profile and L2, tau, history (the whole run's series), time_avg
+                         # (with average_from)
+    table: dict          # [M] arrays: the _PHYSICS values, steps, every figure of history_figures(), n_dropped
+    wall_seconds: float
+    grid_policy: dict = field(default_factory=dict)
+
+
+def sweep_table(prms, histories, steps, history_from=0.0, settle_tol=0.05):
+    """The table of a sweep: one [M] array per column -- the members' _PHYSICS values, their step counts, every figure of
+    history_figures(prm_m, history_m, t_from=history_from, tol=settle_tol), and the records member m lost (n_dropped).  A
+    member without a record at t >= history_from has NaN means and deviations."""
+    figs = [history_figures(p, h, t_from=history_from, tol=settle_tol) for p, h in zip(prms, histories)]
+    table = {k: np.array([float(getattr(p, k)) for p in prms]) for k in _PHYSICS}
+    table["steps"] = np.array([int(n) for n in steps], dtype=np.int64)
+    for k in (figs[0] if figs else ()):
+        table[k] = np.array([f[k] for f in figs])
+    table["n_dropped"] = np.array([int(h["n_dropped"]) for h in histories], dtype=np.int64)
+    return table
+
+
+def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0, settle_tol=0.05, average_from=None,
+              average_every=1, parts_list=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0, log=None):
+    """A parameter sweep: M channels of one geometry that differ in mu, c_f, p0, gravity_g, transport_coeff, stepped as one
+    batch (capi.Batch) with every member's step history recorded on the device, inside the step loop (include/sphx.h
+    section 2f) as run(history_every=...) does for one channel.  The members advance output point by output point as in
+    run_batch, so their trajectories are run_batch's; the record buffers (history_capacity records per member) are drained
+    at every output point, so a capacity that holds one output interval suffices, and nothing else is downloaded before
+    the end.  history_from: the start of the window the table's means are taken over (every history_every-th step of the
+    whole run is recorded); settle_tol: the band of t_settled (history_figures).  average_from: the batch's flow
+    statistics as well, as in run_ensemble -- every average_every-th step ending at t >= average_from -- and each member
+    gets a time_avg.  A member that lost records to a full buffer raises RuntimeError, which names the member and the
+    capacity the output interval needed.  Returns a SweepResult."""
+    prms = list(prms)
+    if not prms:
+        raise ValueError("run_sweep needs at least one parameter set")
+    p0 = prms[0]
+    parts_list = _batch_inputs(prms, parts_list)
+    nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
+    M = len(prms)
+    n_bins = n_profile_bins(p0.DH, p0.dp)
+    mid_x, mid_hw = 0.5 * p0.DL, max(p0.dp, p0.h)
+    times = [0.0]
+    chunks = [[] for _ in range(M)]
+    t0 = time.perf_counter()
+    with capi.Batch(prms, nf, nt, [pa["pos"] for pa in parts_list], [pa["vel"] for pa in parts_list],
+                    [pa["drho_dt"] for pa in parts_list], parts_list[0]["mass"], parts_list[0]["wall_vel"],
+                    lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
+                    rebuild_every=rebuild_every) as b:
+        b.history_enable(every=history_every, capacity=history_capacity)
+        if average_from is not None:
+            b.flow_stats_enable(n_bins=n_bins, every=average_every, t_from=float(average_from), bands=[(mid_x, mid_hw)])
+        t = 0.0
+        st = None
+        while t < p0.t_end - 1e-12:
+            target = min(t + p0.output_interval, p0.t_end)
+            st = b.advance(target)
+            t = min(s["t"] for s in st)
+            times.append(t)
+            for m, h in enumerate(b.history(drain=True)):
+                if h["n_dropped"]:
+                    raise RuntimeError(f"member {m}: the step history lost {h['n_dropped']} records before t={t:.6f}; the "
+                                       f"output interval needs history_capacity >= {len(h['step']) + h['n_dropped']} "
+                                       f"(it is {history_capacity})")
+                chunks[m].append(h)
+            if log:
+                log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
+        wall = time.perf_counter() - t0
+        policy = _batch_policy(b)
+        whole = mid = None
+        if average_from is not None:
+            whole, mid = b.flow_stats_sums(0), b.flow_stats_sums(1)
+        members = []
+        for m, prm in enumerate(prms):
+            ta = None if whole is None else time_average(prm, flow_stats_profile(prm.DH, **whole[m]),
+                                                         flow_stats_profile(prm.DH, **mid[m]))
+            members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, history=_concat_history(chunks[m]),
+                                                time_avg=ta))
+    table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
+    return SweepResult(members=members, table=table, wall_seconds=wall, grid_policy=policy)
