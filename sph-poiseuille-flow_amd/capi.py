@@ -159,12 +159,170 @@ def _per_member(v, m, name):
     return v
 
 
-class Batch:
+_STATE = ("pos", "vel", "drho_dt", "mass", "wall_vel")
+
+
+class _Stepped:
+    """What a context and a batch bind alike: the handle's lifecycle, stepping, the flow statistics and the step history.  A
+    subclass names its symbol stem, the word of its "not enabled on this ..." errors and whether it has many channels: a
+    context returns one status / dict / (records, n_dropped) pair, a batch a list with one entry per member."""
+    _stem = _where = None
+    _many = False
+
+    def _call(self, name, *args):
+        check(getattr(lib(), self._stem + name)(self._h, *args))
+
+    def _channels(self) -> int:
+        return self.n_members if self._many else 1
+
+    def _params0(self) -> SphxParams:
+        return self.params[0] if self._many else self.params
+
+    def _each(self, per_channel):
+        return per_channel if self._many else per_channel[0]
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(lib(), self._stem + "destroy")(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # advance, enqueue_steps and sync sit inside timed loops (bench.py): they go to the library without a helper in between
+    def _status(self, name, *args):
+        st = (SphxStatus * (self.n_members if self._many else 1))()
+        check(getattr(lib(), self._stem + name)(self._h, *args, st))
+        return [s.as_dict() for s in st] if self._many else st[0].as_dict()
+
+    def advance(self, t_target, max_steps=0):
+        return self._status("advance", C.c_double(t_target), C.c_int64(max_steps))
+
+    def enqueue_steps(self, n_steps):
+        check(getattr(lib(), self._stem + "enqueue_steps")(self._h, C.c_int64(n_steps)))
+
+    def sync(self):
+        return self._status("sync")
+
+    def graph_stats(self) -> dict:
+        a, b, g = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._call("graph_stats", C.byref(a), C.byref(b), C.byref(g))
+        return dict(slots_replayed=a.value, slots_eager=b.value, graphs_captured=g.value)
+
+    def _download(self, fields, *member):
+        out, args = _field_buffers(self.n_total, fields)
+        self._call("download", *member, *args)
+        return out
+
+    def _monitor(self, tau, pairs, *member):
+        tb, tt, npairs = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._call("monitor", *member, C.byref(tb) if tau else None, C.byref(tt) if tau else None,
+                   C.byref(npairs) if pairs else None)
+        return tb.value, tt.value, npairs.value
+
+    # ---- flow statistics (include/sphx.h sections 2a, 2c): time-averaged velocity profiles accumulated on the device ----
+    def flow_stats_enable(self, n_bins=0, every=1, t_from=0.0, bands=()):
+        """Sample the state every `every`-th completed step ending at t >= t_from into n_bins y-bins (0: the reference's
+        max(20, round(DH/dp))) of the whole channel (band 0) and of up to two x-bands [(x_centre, half_width), ...]
+        (band 1, 2).  (Re)configures and zeroes the sums.  A batch: one config for all members, each sampled on its own clock."""
+        cfg = flow_stats_config(n_bins, every, t_from, bands)
+        p0 = self._params0()
+        n = int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5)))
+        self._call("flow_stats_enable", C.byref(cfg))
+        self._flow_stats = (n, int(cfg.n_bands) + 1)  # (n_bins, n_bands incl. band 0) while the flow statistics are on
+
+    def flow_stats_disable(self):
+        self._call("flow_stats_disable")
+        self._flow_stats = None
+
+    def _stats_on(self):
+        return _enabled(self._flow_stats, "Stats", f"flow statistics are not enabled on this {self._where}")
+
+    def flow_stats_reset(self):
+        self._stats_on()
+        self._call("flow_stats_reset")
+
+    def flow_stats_sample(self):
+        """Add one sample of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
+        self._stats_on()
+        self._call("flow_stats_sample")
+
+    def flow_stats_sums(self, band=0):
+        """The raw sums of one band: count, sum_ux, sum_ux2, sum_uy, sum_uy2 [n_bins], n_samples, t_first, t_last; a batch: one
+        such dict per member, from one read of all members."""
+        n_bins, n_bands = self._stats_on()
+        if not _is_int(band) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:Stats:band", f"band must be an integer in 0..{n_bands - 1}")
+        m = self._channels()
+        arrs = [np.zeros(m * n_bins) for _ in range(5)]
+        ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
+        nb = C.c_int(0)
+        self._call("flow_stats_read", C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), *[ptr(a) for a in arrs],
+                   ns.ctypes.data_as(C.POINTER(C.c_int64)), ptr(t0), ptr(t1))
+        assert nb.value == n_bins, (nb.value, n_bins)
+        out = []
+        for k in range(m):
+            d = {f: a[k * n_bins:(k + 1) * n_bins].copy() for f, a in zip(("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2"), arrs)}
+            d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
+            out.append(d)
+        return self._each(out)
+
+    def flow_stats(self, band=0):
+        """Time-averaged profile of one band (profile.flow_stats_profile): y_mid, count, u_mean, u_std, uy_mean, uy_std,
+        n_samples, t_first, t_last (+ the raw sums).  Empty bins give NaN means.  A batch: one such dict per member."""
+        DH = self._params0().DH
+        sums = self.flow_stats_sums(band)
+        return [flow_stats_profile(DH, **s) for s in sums] if self._many else flow_stats_profile(DH, **sums)
+
+    # ---- step history (include/sphx.h sections 2d, 2f): wall shear, energy, bulk velocity, dt and vmax per step, recorded on the device ----
+    def history_enable(self, every=1, capacity=65536, t_from=0.0):
+        """Record every `every`-th completed step ending at t >= t_from into a device buffer of `capacity` records
+        ((re)configures and empties it).  Records that find the buffer full are dropped and counted.  A batch: one config for
+        all members, `capacity` records per member, each recorded on its own clock; n_members * capacity must not exceed
+        1 << 24."""
+        cfg = history_config(every, capacity, t_from, n_members=self._channels())
+        self._call("history_enable", C.byref(cfg))
+
+    def history_disable(self):
+        self._call("history_disable")
+
+    def history_records(self, drain=False):
+        """-> (records [n x 8] in the order of HISTORY_FIELDS, n_dropped); drain empties the buffer after the copy.  A batch:
+        one such pair per member, from one read of all members."""
+        m = self._channels()
+        n, dropped = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
+
+        def read(cap, rec, drain):  # the counts always; the records into rec [m x cap x 8] where there is one
+            self._call("history_read", C.c_int(cap), ptr(rec), n.ctypes.data_as(C.POINTER(C.c_int)),
+                       dropped.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(1 if drain else 0))
+
+        read(0, None, False)
+        cap, want = max(int(n.max()), 1), n.copy()
+        rec = np.zeros((m, cap, len(HISTORY_FIELDS)))
+        read(cap, rec, drain)
+        assert np.array_equal(n, want), (n, want)
+        return self._each([(rec[k, :n[k]].copy(), int(dropped[k])) for k in range(m)])
+
+    def history(self, drain=False):
+        """The records so far as 1-D arrays step (int64), t, dt, vmax, tau_bottom, tau_top, kinetic_energy, u_bulk, plus
+        n_dropped (history_dict); a batch: one such dict per member."""
+        recs = self.history_records(drain)
+        return [history_dict(*r) for r in recs] if self._many else history_dict(*recs)
+
+
+class Batch(_Stepped):
     """M channels of one geometry stepped by the same launches (sphx_batch, include/sphx.h section 2b).
 
     prms: one parameter set per member (mu, c_f, p0, gravity_g, transport_coeff may differ; the geometry, t_end and the
     launch shape must not).  pos_list / vel_list / drho_list: the members' states, MEX layout as for Context; mass and
-    wall_vel are shared.  transport_coeff may be a scalar or one value per member."""
+    wall_vel are shared.  transport_coeff may be a scalar or one value per member.  advance / sync, flow_stats_* and
+    history_* are a context's for all members at once: one entry per member."""
+    _stem, _where, _many = "sphx_batch_", "batch", True
 
     def __init__(self, prms, n_fluid, n_total, pos_list, vel_list, drho_list, mass, wall_vel, t0=0.0, step0=0,
                  t_end=None, transport_coeff=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,
@@ -199,120 +357,34 @@ class Batch:
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
                                       C.c_double(t0), C.c_int64(step0)))
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sphx_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _status(self, arr):
-        return [s.as_dict() for s in arr]
-
-    def advance(self, t_target, max_steps=0) -> list:
-        st = (SphxStatus * self.n_members)()
-        check(lib().sphx_batch_advance(self._h, C.c_double(t_target), C.c_int64(max_steps), st))
-        return self._status(st)
-
-    def enqueue_steps(self, n_steps):
-        check(lib().sphx_batch_enqueue_steps(self._h, C.c_int64(n_steps)))
-
-    def sync(self) -> list:
-        st = (SphxStatus * self.n_members)()
-        check(lib().sphx_batch_sync(self._h, st))
-        return self._status(st)
+    @classmethod
+    def from_parts(cls, prms, parts_list, **kw):
+        """A batch of the particle sets parts_list (dicts of geometry.init_particles), one per member; mass and wall_vel are
+        member 0's.  kw: the keywords of Batch(); an array given there (pos_list=, ..., mass=, wall_vel=) wins over the dicts'."""
+        p0 = parts_list[0]
+        states = [kw.pop(name, [pa[k] for pa in parts_list])
+                  for name, k in (("pos_list", "pos"), ("vel_list", "vel"), ("drho_list", "drho_dt"))]
+        return cls(prms, p0["n_fluid"], p0["n_total"], *states, kw.pop("mass", p0["mass"]),
+                   kw.pop("wall_vel", p0["wall_vel"]), **kw)
 
     def download(self, member, fields=_FIELDS) -> dict:
-        out, args = _field_buffers(self.n_total, fields)
-        check(lib().sphx_batch_download(self._h, C.c_int(member), *args))
-        return out
+        return self._download(fields, C.c_int(member))
 
     def monitor(self, member, tau=True, pairs=False):
-        tb, tt, npairs = C.c_double(0), C.c_double(0), C.c_double(0)
-        check(lib().sphx_batch_monitor(self._h, C.c_int(member), C.byref(tb) if tau else None,
-                                       C.byref(tt) if tau else None, C.byref(npairs) if pairs else None))
-        return tb.value, tt.value, npairs.value
+        return self._monitor(tau, pairs, C.c_int(member))
 
     def info(self) -> dict:
         m, lpp, spg, k = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         skin, forced, realign = C.c_double(0.0), C.c_int64(0), C.c_int64(0)
-        check(lib().sphx_batch_info(self._h, C.byref(m), C.byref(lpp), C.byref(spg), C.byref(k), C.byref(skin),
-                                    C.byref(forced), C.byref(realign)))
+        self._call("info", C.byref(m), C.byref(lpp), C.byref(spg), C.byref(k), C.byref(skin), C.byref(forced),
+                   C.byref(realign))
         return dict(n_members=m.value, lanes_per_particle=lpp.value, steps_per_graph=spg.value, rebuild_every=k.value,
                     skin=skin.value, forced_rebuilds=forced.value, realignments=realign.value)
 
-    def graph_stats(self) -> dict:
-        a, b, g = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(lib().sphx_batch_graph_stats(self._h, C.byref(a), C.byref(b), C.byref(g)))
-        return dict(slots_replayed=a.value, slots_eager=b.value, graphs_captured=g.value)
 
-    # ---- flow statistics of every member (include/sphx.h section 2c): Context.flow_stats_* for all members at once ----
-    def flow_stats_enable(self, n_bins=0, every=1, t_from=0.0, bands=()):
-        """Context.flow_stats_enable with one config for all members; each member is sampled on its own clock."""
-        cfg = flow_stats_config(n_bins, every, t_from, bands)
-        p0 = self.params[0]
-        n = int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5)))
-        check(lib().sphx_batch_flow_stats_enable(self._h, C.byref(cfg)))
-        self._flow_stats = (n, int(cfg.n_bands) + 1)
-
-    def flow_stats_disable(self):
-        check(lib().sphx_batch_flow_stats_disable(self._h))
-        self._flow_stats = None
-
-    def flow_stats_reset(self):
-        _stats_on(self._flow_stats, "batch")
-        check(lib().sphx_batch_flow_stats_reset(self._h))
-
-    def flow_stats_sample(self):
-        """Add one sample of every member's current state (what download() returns) now, whatever the gating."""
-        _stats_on(self._flow_stats, "batch")
-        check(lib().sphx_batch_flow_stats_sample(self._h))
-
-    def flow_stats_sums(self, band=0) -> list:
-        """One dict per member in the format of Context.flow_stats_sums, from one read of all members."""
-        return _flow_stats_read("sphx_batch_flow_stats_read", self._h, _stats_on(self._flow_stats, "batch"), band,
-                                self.n_members)
-
-    def flow_stats(self, band=0) -> list:
-        """One profile.flow_stats_profile dict per member."""
-        return [flow_stats_profile(self.params[0].DH, **s) for s in self.flow_stats_sums(band)]
-
-    # ---- step history of every member (include/sphx.h section 2f): Context.history_* for all members at once ----
-    def history_enable(self, every=1, capacity=65536, t_from=0.0):
-        """Context.history_enable with one config for all members; `capacity` records per member, each member recorded on
-        its own clock.  n_members * capacity must not exceed 1 << 24."""
-        cfg = history_config(every, capacity, t_from, n_members=self.n_members)
-        check(lib().sphx_batch_history_enable(self._h, C.byref(cfg)))
-
-    def history_disable(self):
-        check(lib().sphx_batch_history_disable(self._h))
-
-    def history_records(self, drain=False) -> list:
-        """-> [(records [n_m x 8] in the order of HISTORY_FIELDS, n_dropped), ...] per member, from one read of all
-        members; drain empties every member's buffer after the copy."""
-        m = self.n_members
-        n, dropped = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
-        pn, pd = n.ctypes.data_as(C.POINTER(C.c_int)), dropped.ctypes.data_as(C.POINTER(C.c_int64))
-        check(lib().sphx_batch_history_read(self._h, C.c_int(0), None, pn, pd, C.c_int(0)))
-        cap = max(int(n.max()), 1)
-        rec = np.zeros((m, cap, len(HISTORY_FIELDS)))
-        want = n.copy()
-        check(lib().sphx_batch_history_read(self._h, C.c_int(cap), ptr(rec), pn, pd, C.c_int(1 if drain else 0)))
-        assert np.array_equal(n, want), (n, want)
-        return [(rec[k, :n[k]].copy(), int(dropped[k])) for k in range(m)]
-
-    def history(self, drain=False) -> list:
-        """One history_dict per member (see Context.history)."""
-        return [history_dict(rec, dropped) for rec, dropped in self.history_records(drain)]
-
-class Context:
+class Context(_Stepped):
     """Device-resident simulation state (sphx_ctx)."""
+    _stem, _where = "sphx_ctx_", "context"
 
     def __init__(self, prm, n_fluid, n_total, pos, vel, drho_dt, mass, wall_vel, t0=0.0, step0=0,
                  t_end=None, transport_coeff=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,
@@ -331,56 +403,21 @@ class Context:
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().sphx_ctx_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def advance(self, t_target, max_steps=0) -> dict:
-        st = SphxStatus()
-        check(lib().sphx_ctx_advance(self._h, C.c_double(t_target), C.c_int64(max_steps), C.byref(st)))
-        return st.as_dict()
-
-    def enqueue_steps(self, n_steps):
-        check(lib().sphx_ctx_enqueue_steps(self._h, C.c_int64(n_steps)))
-
-    def sync(self) -> dict:
-        st = SphxStatus()
-        check(lib().sphx_ctx_sync(self._h, C.byref(st)))
-        return st.as_dict()
+    @classmethod
+    def from_parts(cls, prm, parts, **kw):
+        """A context of the particle set parts (a dict of geometry.init_particles).  kw: the keywords of Context(); an array
+        given there (pos=, vel=, drho_dt=, mass=, wall_vel=) wins over the dict's."""
+        return cls(prm, parts["n_fluid"], parts["n_total"], *[kw.pop(k, parts[k]) for k in _STATE], **kw)
 
     def prepare_steps(self, n_steps):
         """Capture (without running) the graphs the next enqueue_steps(n_steps) / advance(max_steps=n_steps) replays."""
-        check(lib().sphx_ctx_prepare_steps(self._h, C.c_int64(n_steps)))
+        self._call("prepare_steps", C.c_int64(n_steps))
 
-    def graph_stats(self) -> dict:
-        a, b, g = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        check(lib().sphx_ctx_graph_stats(self._h, C.byref(a), C.byref(b), C.byref(g)))
-        return dict(slots_replayed=a.value, slots_eager=b.value, graphs_captured=g.value)
-
-    def download(self, fields=("pos", "vel", "rho", "p", "drho_dt", "force", "force_prior", "Vol", "B")) -> dict:
-        nt = self.n_total
-        shapes = dict(pos=(nt, 2), vel=(nt, 2), rho=(nt,), p=(nt,), drho_dt=(nt,), force=(nt, 2),
-                      force_prior=(nt, 2), Vol=(nt,), B=(nt, 4))
-        order = ("pos", "vel", "rho", "p", "drho_dt", "force", "force_prior", "Vol", "B")
-        out = {k: np.zeros(shapes[k], order="F") for k in fields}
-        args = [ptr(out[k]) if k in out else None for k in order]
-        check(lib().sphx_ctx_download(self._h, *args))
-        return out
+    def download(self, fields=_FIELDS) -> dict:
+        return self._download(fields)
 
     def monitor(self, tau=True, pairs=False):
-        tb, tt, npairs = C.c_double(0), C.c_double(0), C.c_double(0)
-        check(lib().sphx_ctx_monitor(self._h, C.byref(tb) if tau else None, C.byref(tt) if tau else None,
-                                     C.byref(npairs) if pairs else None))
-        return tb.value, tt.value, npairs.value
+        return self._monitor(tau, pairs)
 
     def neighbor_list(self):
         n = C.c_size_t(0)
@@ -424,64 +461,6 @@ class Context:
         ms = C.c_double(0.0)
         check(lib().sphx_ctx_time_kernel(self._h, name.encode(), C.c_int(reps), C.byref(ms)))
         return ms.value
-
-    # ---- flow statistics (include/sphx.h section 2a): time-averaged velocity profiles accumulated on the device ----
-    def flow_stats_enable(self, n_bins=0, every=1, t_from=0.0, bands=()):
-        """Sample the state every `every`-th completed step ending at t >= t_from into n_bins y-bins (0: the reference's
-        max(20, round(DH/dp))) of the whole channel (band 0) and of up to two x-bands [(x_centre, half_width), ...]
-        (band 1, 2).  (Re)configures and zeroes the sums."""
-        cfg = flow_stats_config(n_bins, every, t_from, bands)
-        n = int(cfg.n_bins) or max(20, int(np.floor(self.params.DH / self.params.dp + 0.5)))
-        check(lib().sphx_ctx_flow_stats_enable(self._h, C.byref(cfg)))
-        self._flow_stats = (n, int(cfg.n_bands) + 1)
-
-    def flow_stats_disable(self):
-        check(lib().sphx_ctx_flow_stats_disable(self._h))
-        self._flow_stats = None
-
-    def flow_stats_reset(self):
-        _stats_on(self._flow_stats, "context")
-        check(lib().sphx_ctx_flow_stats_reset(self._h))
-
-    def flow_stats_sample(self):
-        """Add one sample of the current state (what download() returns) now, whatever the gating."""
-        _stats_on(self._flow_stats, "context")
-        check(lib().sphx_ctx_flow_stats_sample(self._h))
-
-    def flow_stats_sums(self, band=0) -> dict:
-        """The raw sums of one band: count, sum_ux, sum_ux2, sum_uy, sum_uy2 [n_bins], n_samples, t_first, t_last."""
-        return _flow_stats_read("sphx_ctx_flow_stats_read", self._h, _stats_on(self._flow_stats, "context"), band, 1)[0]
-
-    def flow_stats(self, band=0) -> dict:
-        """Time-averaged profile of one band (profile.flow_stats_profile): y_mid, count, u_mean, u_std, uy_mean, uy_std,
-        n_samples, t_first, t_last (+ the raw sums).  Empty bins give NaN means."""
-        return flow_stats_profile(self.params.DH, **self.flow_stats_sums(band))
-
-    # ---- step history (include/sphx.h section 2d): wall shear, energy, bulk velocity, dt and vmax per step, recorded on the device ----
-    def history_enable(self, every=1, capacity=65536, t_from=0.0):
-        """Record every `every`-th completed step ending at t >= t_from into a device buffer of `capacity` records
-        ((re)configures and empties it).  Records that find the buffer full are dropped and counted."""
-        cfg = history_config(every, capacity, t_from)
-        check(lib().sphx_ctx_history_enable(self._h, C.byref(cfg)))
-
-    def history_disable(self):
-        check(lib().sphx_ctx_history_disable(self._h))
-
-    def history_records(self, drain=False):
-        """-> (records [n x 8] in the order of HISTORY_FIELDS, n_dropped); drain empties the buffer after the copy."""
-        n, dropped = C.c_int(0), C.c_int64(0)
-        check(lib().sphx_ctx_history_read(self._h, C.c_int(0), None, C.byref(n), C.byref(dropped), C.c_int(0)))
-        rec = np.zeros((n.value, len(HISTORY_FIELDS)))
-        check(lib().sphx_ctx_history_read(self._h, C.c_int(n.value), ptr(rec), C.byref(n), C.byref(dropped),
-                                          C.c_int(1 if drain else 0)))
-        assert n.value == rec.shape[0], (n.value, rec.shape)
-        return rec, dropped.value
-
-    def history(self, drain=False) -> dict:
-        """The records so far as 1-D arrays step (int64), t, dt, vmax, tau_bottom, tau_top, kinetic_energy, u_bulk, plus
-        n_dropped."""
-        rec, dropped = self.history_records(drain)
-        return history_dict(rec, dropped)
 
     # ---- field map (include/sphx.h section 2e): the velocity field on a regular grid in x and y, accumulated on the device ----
     def field_map_enable(self, nx=0, ny=0, every=1, t_from=0.0, with_walls=False):
@@ -544,32 +523,8 @@ def _enabled(state, stem, text):
     return state
 
 
-def _stats_on(state, where):
-    return _enabled(state, "Stats", f"flow statistics are not enabled on this {where}")
-
-
 def _field_on(state):
     return _enabled(state, "Field", "the field map is not enabled on this context")
-
-
-def _flow_stats_read(read, handle, enabled, band, m) -> list:
-    """One call of `read` (sphx_ctx_ / sphx_batch_flow_stats_read) for band `band` of m channels -> a dict per channel: count, sum_ux,
-    sum_ux2, sum_uy, sum_uy2 [n_bins], n_samples, t_first, t_last."""
-    n_bins, n_bands = enabled
-    if not _is_int(band) or not 0 <= band < n_bands:
-        raise SphxError(SPHX_ERR_ARG, "SPHX:Stats:band", f"band must be an integer in 0..{n_bands - 1}")
-    arrs = [np.zeros(m * n_bins) for _ in range(5)]
-    ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
-    nb = C.c_int(0)
-    check(getattr(lib(), read)(handle, C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), *[ptr(a) for a in arrs],
-               ns.ctypes.data_as(C.POINTER(C.c_int64)), ptr(t0), ptr(t1)))
-    assert nb.value == n_bins, (nb.value, n_bins)
-    out = []
-    for k in range(m):
-        d = {f: a[k * n_bins:(k + 1) * n_bins].copy() for f, a in zip(("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2"), arrs)}
-        d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
-        out.append(d)
-    return out
 
 
 def _is_int(v):

@@ -227,9 +227,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     field_avg = None
     t0 = time.perf_counter()
     if engine == "resident":
-        ctx = capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                           parts["wall_vel"], t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
-                           steps_per_graph=steps_per_graph, rebuild_every=rebuild_every, dual_rate=dual_rate)
+        ctx = capi.Context.from_parts(prm, parts, t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
+                                      steps_per_graph=steps_per_graph, rebuild_every=rebuild_every, dual_rate=dual_rate)
         t, step = t_start, step_start
         try:
             n_inner = ctx.substeps()
@@ -316,18 +315,23 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
         pos, vel = S["pos"], S["vel"]
     else:
         raise ValueError("engine must be 'resident' or 'mex'")
-    fluid_pos = pos[:nf].copy()
-    fluid_pos[:, 0] = np.mod(fluid_pos[:, 0], prm.DL)
-    y_mid, u_mean, u_exact = final_profile(fluid_pos, vel[:nf, 0], prm)
     if postprocess_path:
         restart.save_postprocess_data(postprocess_path, restart.make_postprocess_data(
             prm, nf, pos, vel, n_bins, profile_times, np.column_stack([np.nan_to_num(u, nan=np.nan) for u in mid_profiles])),
                                       fmt=mat_format)
-    return RunResult(prm=prm, n_fluid=nf, n_total=nt, t=t, steps=int(step), wall_seconds=wall, pos=pos, vel=vel,
-                     y_mid=y_mid, u_mean=u_mean, u_exact=u_exact, L2_error=l2_error(u_mean, u_exact),
-                     profile_times=profile_times, mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t,
-                     tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2, grid_policy=policy, full_profile_u=full_profiles, n_inner=n_inner,
-                     time_avg=time_avg, history=history, field_avg=field_avg)
+    return _run_result(prm, nf, nt, pos, vel, t=t, steps=int(step), wall_seconds=wall, profile_times=profile_times,
+                       mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t, grid_policy=policy,
+                       full_profile_u=full_profiles, n_inner=n_inner, time_avg=time_avg, history=history, field_avg=field_avg)
+
+
+def _run_result(prm, nf, nt, pos, vel, **fields):
+    """The RunResult of a final state: x wrapped into the channel, the final profile and its L2 against the analytic one,
+    tau_target; `fields` are the RunResult fields the caller knows."""
+    fluid_pos = pos[:nf].copy()
+    fluid_pos[:, 0] = np.mod(fluid_pos[:, 0], prm.DL)
+    y_mid, u_mean, u_exact = final_profile(fluid_pos, vel[:nf, 0], prm)
+    return RunResult(prm=prm, n_fluid=nf, n_total=nt, pos=pos, vel=vel, y_mid=y_mid, u_mean=u_mean, u_exact=u_exact,
+                     L2_error=l2_error(u_mean, u_exact), tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2, **fields)
 
 
 def _batch_inputs(prms, parts_list):
@@ -352,15 +356,80 @@ def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
     """Member m's RunResult at the end of a batch run: final state, profile and L2, tau of the last step."""
     tau_b, tau_t, _ = b.monitor(m, tau=True)
     d = b.download(m, fields=("pos", "vel"))
-    pos, vel = d["pos"], d["vel"]
-    fluid_pos = pos[:nf].copy()
-    fluid_pos[:, 0] = np.mod(fluid_pos[:, 0], prm.DL)
-    y_mid, u_mean, u_exact = final_profile(fluid_pos, vel[:nf, 0], prm)
     s = st[m] if st else dict(t=0.0, step=0)
-    return RunResult(prm=prm, n_fluid=nf, n_total=nt, t=s["t"], steps=int(s["step"]), wall_seconds=wall, pos=pos, vel=vel,
-                     y_mid=y_mid, u_mean=u_mean, u_exact=u_exact, L2_error=l2_error(u_mean, u_exact),
-                     profile_times=list(times), tau_bottom=tau_b, tau_top=tau_t,
-                     tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2, grid_policy=dict(policy), **extra)
+    return _run_result(prm, nf, nt, d["pos"], d["vel"], t=s["t"], steps=int(s["step"]), wall_seconds=wall,
+                       profile_times=list(times), tau_bottom=tau_b, tau_top=tau_t, grid_policy=dict(policy), **extra)
+
+
+def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None):
+    """The batch run behind run_batch, run_ensemble and run_sweep (`name`, for the refusals): check and default the inputs,
+    open the batch with the launch keywords `launch`, enable what was asked for, advance output point by output point, build
+    every member's RunResult.
+      snapshots  download every member at every output point: its mid_profile_u and full_profile_u
+      average    (average_from, average_every): the flow statistics of the whole channel and the mid-channel band (DL/2,
+                 max(dp, h)); every member gets a time_avg
+      history    (history_every, history_capacity): the step history, drained at every output point; every member gets a
+                 history, and one that lost records raises RuntimeError
+    -> the members, the wall seconds, the grid policy, and with average the raw sums (whole, mid) of all members."""
+    prms = list(prms)
+    if not prms:
+        raise ValueError(f"{name} needs at least one parameter set")
+    p0 = prms[0]
+    parts_list = _batch_inputs(prms, parts_list)
+    nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
+    M = len(prms)
+    n_bins = n_profile_bins(p0.DH, p0.dp)
+    mid_x, mid_hw = 0.5 * p0.DL, max(p0.dp, p0.h)
+
+    def mid_profile(d):
+        return compute_mid_channel_profile(d["pos"][:nf], d["vel"][:nf, 0], p0.DL, p0.DH, mid_x, mid_hw, n_bins)[1]
+
+    times = [0.0]
+    mids = [[mid_profile(pa)] for pa in parts_list] if snapshots else None
+    fulls = [[] for _ in range(M)]
+    chunks = [[] for _ in range(M)]
+    t0 = time.perf_counter()
+    with capi.Batch.from_parts(prms, parts_list, **launch) as b:
+        if history:
+            b.history_enable(every=history[0], capacity=history[1])
+        if average:
+            b.flow_stats_enable(n_bins=n_bins, every=average[1], t_from=float(average[0]), bands=[(mid_x, mid_hw)])
+        t = 0.0
+        st = None
+        while t < p0.t_end - 1e-12:
+            target = min(t + p0.output_interval, p0.t_end)
+            st = b.advance(target)
+            t = min(s["t"] for s in st)
+            times.append(t)
+            if snapshots:
+                for m in range(M):
+                    d = b.download(m, fields=("pos", "vel"))
+                    mids[m].append(mid_profile(d))
+                    fulls[m].append(final_profile(np.column_stack([np.mod(d["pos"][:nf, 0], p0.DL), d["pos"][:nf, 1]]),
+                                                  d["vel"][:nf, 0], prms[m])[1])
+            if history:
+                for m, h in enumerate(b.history(drain=True)):
+                    if h["n_dropped"]:
+                        raise RuntimeError(f"member {m}: the step history lost {h['n_dropped']} records before t={t:.6f}; "
+                                           f"the output interval needs history_capacity >= "
+                                           f"{len(h['step']) + h['n_dropped']} (it is {history[1]})")
+                    chunks[m].append(h)
+            if log:
+                log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
+        wall = time.perf_counter() - t0
+        policy = _batch_policy(b)
+        sums = (b.flow_stats_sums(0), b.flow_stats_sums(1)) if average else None
+        members = []
+        for m, prm in enumerate(prms):
+            extra = {}
+            if snapshots:
+                extra.update(mid_profile_u=mids[m], full_profile_u=fulls[m])
+            if average:
+                extra.update(time_avg=time_average(prm, *[flow_stats_profile(prm.DH, **band[m]) for band in sums]))
+            if history:
+                extra.update(history=_concat_history(chunks[m]))
+            members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra))
+    return members, wall, policy, sums
 
 
 def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,
@@ -370,67 +439,16 @@ def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, st
     reaches the same output points (output_interval and t_end are shared and must agree) and gets a RunResult of its own:
     final profile and L2, the output-point profiles, tau.  The resident engine only; restart / post-process files are
     single-channel features, and time averaging of a batch is run_ensemble's."""
-    prms = list(prms)
     if engine != "resident":
         raise ValueError("run_batch runs the resident engine only (a batch is device-resident)")
     if restart_path or postprocess_path:
         raise ValueError("run_batch writes no restart / post-process files (run() does, per channel)")
     if average_from is not None:
-        raise ValueError("run_batch has no time averaging yet (flow statistics are a single-context feature)")
+        raise ValueError("run_batch does no time averaging (run_ensemble and run_sweep do, for every member)")
     if history_every is not None:
         raise ValueError("run_batch records no step history (run_sweep does, for every member)")
-    if not prms:
-        raise ValueError("run_batch needs at least one parameter set")
-    p0 = prms[0]
-    parts_list = _batch_inputs(prms, parts_list)
-    nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
-    M = len(prms)
-    n_bins = n_profile_bins(p0.DH, p0.dp)
-    mid_x, mid_hw = 0.5 * p0.DL, max(p0.dp, p0.h)
-    times = [0.0]
-    mids = [[compute_mid_channel_profile(pa["pos"][:nf], pa["vel"][:nf, 0], p0.DL, p0.DH, mid_x, mid_hw, n_bins)[1]]
-            for pa in parts_list]
-    fulls = [[] for _ in range(M)]
-    t0 = time.perf_counter()
-    with capi.Batch(prms, nf, nt, [pa["pos"] for pa in parts_list], [pa["vel"] for pa in parts_list],
-                    [pa["drho_dt"] for pa in parts_list], parts_list[0]["mass"], parts_list[0]["wall_vel"],
-                    lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
-                    rebuild_every=rebuild_every) as b:
-        t = 0.0
-        st = None
-        while t < p0.t_end - 1e-12:
-            target = min(t + p0.output_interval, p0.t_end)
-            st = b.advance(target)
-            t = min(s["t"] for s in st)
-            times.append(t)
-            for m in range(M):
-                d = b.download(m, fields=("pos", "vel"))
-                mids[m].append(compute_mid_channel_profile(d["pos"][:nf], d["vel"][:nf, 0], p0.DL, p0.DH, mid_x, mid_hw,
-                                                           n_bins)[1])
-                fulls[m].append(final_profile(np.column_stack([np.mod(d["pos"][:nf, 0], p0.DL), d["pos"][:nf, 1]]),
-                                              d["vel"][:nf, 0], prms[m])[1])
-            if log:
-                log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
-        wall = time.perf_counter() - t0
-        info = b.info()
-        out = []
-        for m, prm in enumerate(prms):
-            tau_b, tau_t, _ = b.monitor(m, tau=True)
-            d = b.download(m, fields=("pos", "vel"))
-            pos, vel = d["pos"], d["vel"]
-            fluid_pos = pos[:nf].copy()
-            fluid_pos[:, 0] = np.mod(fluid_pos[:, 0], prm.DL)
-            y_mid, u_mean, u_exact = final_profile(fluid_pos, vel[:nf, 0], prm)
-            s = st[m] if st else dict(t=0.0, step=0)
-            out.append(RunResult(prm=prm, n_fluid=nf, n_total=nt, t=s["t"], steps=int(s["step"]), wall_seconds=wall,
-                                 pos=pos, vel=vel, y_mid=y_mid, u_mean=u_mean, u_exact=u_exact,
-                                 L2_error=l2_error(u_mean, u_exact), profile_times=list(times), mid_profile_u=mids[m],
-                                 tau_bottom=tau_b, tau_top=tau_t, tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2,
-                                 grid_policy=dict(rebuild_every=info["rebuild_every"], skin=info["skin"],
-                                                  forced_rebuilds=info["forced_rebuilds"],
-                                                  realignments=info["realignments"]),
-                                 full_profile_u=fulls[m]))
-    return out
+    return _run_batch("run_batch", prms, parts_list, dict(lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
+                                                          rebuild_every=rebuild_every), log, snapshots=True)[0]
 
 
 @dataclass
@@ -456,37 +474,12 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
     prms = list(prms)
     if history_every is not None:
         raise ValueError("run_ensemble records no step history (run_sweep does, for every member)")
-    if not prms:
-        raise ValueError("run_ensemble needs at least one parameter set")
-    if average_from is None or np.isnan(float(average_from)):
+    if prms and (average_from is None or np.isnan(float(average_from))):  # (no parameter set: refused first, below)
         raise ValueError("run_ensemble needs average_from (the start of the averaging window)")
-    p0 = prms[0]
-    parts_list = _batch_inputs(prms, parts_list)
-    nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
-    M = len(prms)
-    n_bins = n_profile_bins(p0.DH, p0.dp)
-    mid_x, mid_hw = 0.5 * p0.DL, max(p0.dp, p0.h)
-    times = [0.0]
-    t0 = time.perf_counter()
-    with capi.Batch(prms, nf, nt, [pa["pos"] for pa in parts_list], [pa["vel"] for pa in parts_list],
-                    [pa["drho_dt"] for pa in parts_list], parts_list[0]["mass"], parts_list[0]["wall_vel"],
-                    lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
-                    rebuild_every=rebuild_every) as b:
-        b.flow_stats_enable(n_bins=n_bins, every=average_every, t_from=float(average_from), bands=[(mid_x, mid_hw)])
-        t = 0.0
-        st = None
-        while t < p0.t_end - 1e-12:
-            target = min(t + p0.output_interval, p0.t_end)
-            st = b.advance(target)
-            t = min(s["t"] for s in st)
-            times.append(t)
-            if log:
-                log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
-        wall = time.perf_counter() - t0
-        whole, mid = b.flow_stats_sums(0), b.flow_stats_sums(1)
-        policy = _batch_policy(b)
-        members = [_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, time_avg=time_average(
-            prm, flow_stats_profile(prm.DH, **whole[m]), flow_stats_profile(prm.DH, **mid[m]))) for m, prm in enumerate(prms)]
+    members, wall, policy, (whole, mid) = _run_batch(
+        "run_ensemble", prms, parts_list, dict(lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
+                                               rebuild_every=rebuild_every), log, average=(average_from, average_every))
+    p0, M = prms[0], len(prms)
     pooled = None
     if all(getattr(p, k) == getattr(p0, k) for p in prms for k in _PHYSICS):
         pw, pm = pool_flow_stats(p0.DH, whole), pool_flow_stats(p0.DH, mid)
@@ -532,49 +525,9 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     gets a time_avg.  A member that lost records to a full buffer raises RuntimeError, which names the member and the
     capacity the output interval needed.  Returns a SweepResult."""
     prms = list(prms)
-    if not prms:
-        raise ValueError("run_sweep needs at least one parameter set")
-    p0 = prms[0]
-    parts_list = _batch_inputs(prms, parts_list)
-    nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
-    M = len(prms)
-    n_bins = n_profile_bins(p0.DH, p0.dp)
-    mid_x, mid_hw = 0.5 * p0.DL, max(p0.dp, p0.h)
-    times = [0.0]
-    chunks = [[] for _ in range(M)]
-    t0 = time.perf_counter()
-    with capi.Batch(prms, nf, nt, [pa["pos"] for pa in parts_list], [pa["vel"] for pa in parts_list],
-                    [pa["drho_dt"] for pa in parts_list], parts_list[0]["mass"], parts_list[0]["wall_vel"],
-                    lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
-                    rebuild_every=rebuild_every) as b:
-        b.history_enable(every=history_every, capacity=history_capacity)
-        if average_from is not None:
-            b.flow_stats_enable(n_bins=n_bins, every=average_every, t_from=float(average_from), bands=[(mid_x, mid_hw)])
-        t = 0.0
-        st = None
-        while t < p0.t_end - 1e-12:
-            target = min(t + p0.output_interval, p0.t_end)
-            st = b.advance(target)
-            t = min(s["t"] for s in st)
-            times.append(t)
-            for m, h in enumerate(b.history(drain=True)):
-                if h["n_dropped"]:
-                    raise RuntimeError(f"member {m}: the step history lost {h['n_dropped']} records before t={t:.6f}; the "
-                                       f"output interval needs history_capacity >= {len(h['step']) + h['n_dropped']} "
-                                       f"(it is {history_capacity})")
-                chunks[m].append(h)
-            if log:
-                log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
-        wall = time.perf_counter() - t0
-        policy = _batch_policy(b)
-        whole = mid = None
-        if average_from is not None:
-            whole, mid = b.flow_stats_sums(0), b.flow_stats_sums(1)
-        members = []
-        for m, prm in enumerate(prms):
-            ta = None if whole is None else time_average(prm, flow_stats_profile(prm.DH, **whole[m]),
-                                                         flow_stats_profile(prm.DH, **mid[m]))
-            members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, history=_concat_history(chunks[m]),
-                                                time_avg=ta))
+    members, wall, policy, _ = _run_batch(
+        "run_sweep", prms, parts_list, dict(lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
+                                            rebuild_every=rebuild_every), log, history=(history_every, history_capacity),
+        average=None if average_from is None else (average_from, average_every))
     table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
     return SweepResult(members=members, table=table, wall_seconds=wall, grid_policy=policy)

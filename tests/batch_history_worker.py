@@ -36,9 +36,7 @@ def main():
     members = [make_case(pkg.config, pkg.geometry, dp=0.05, DL=3.0, jitter=0.2, seed=v["seed"], developed=True, mu=v["mu"],
                          c_f=v["c_f"], transport_coeff=v["transport_coeff"]) for v in VARIANTS]
     kw = dict(t_end=1e9, lanes_per_particle=args.lpp)
-    p0 = members[0][1]
-    with capi.Batch([m[0] for m in members], p0["n_fluid"], p0["n_total"], [m[1]["pos"] for m in members],
-                    [m[1]["vel"] for m in members], [m[1]["drho_dt"] for m in members], p0["mass"], p0["wall_vel"], **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         n = 2 * b.info()["rebuild_every"] + 3
         b.history_enable(every=1)
         sts = b.advance(1e9, max_steps=n)
@@ -46,8 +44,7 @@ def main():
         info = b.info()
     differs, sched, rebins = [], None, []
     for m, (prm, parts) in enumerate(members):
-        with capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                          parts["wall_vel"], **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, **kw) as ctx:
             before = ctx.schedule()
             ctx.history_enable(every=1)
             st = ctx.advance(1e9, max_steps=n)

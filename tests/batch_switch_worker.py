@@ -78,9 +78,7 @@ def main():
             st = obj.advance(1e9, max_steps=1)
         return st
 
-    p0 = members[0][1]
-    with capi.Batch([m[0] for m in members], p0["n_fluid"], p0["n_total"], [m[1]["pos"] for m in members],
-                    [m[1]["vel"] for m in members], [m[1]["drho_dt"] for m in members], p0["mass"], p0["wall_vel"], **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         info = b.info()
         n = 2 * info["rebuild_every"] + 3
         b.flow_stats_enable(**stats)
@@ -91,8 +89,7 @@ def main():
         info, graph_stats = b.info(), b.graph_stats()
     differs, sched, rebins = [], None, []
     for m, (prm, parts) in enumerate(members):
-        with capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                          parts["wall_vel"], **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, **kw) as ctx:
             before = ctx.schedule()
             ctx.flow_stats_enable(**stats)
             st = advance(ctx, n)

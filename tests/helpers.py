@@ -94,3 +94,107 @@ def field_atol(prm, parts, nb, dt):
     return dict(rho=a_rho + 0.5 * dt * a_drho, p=a_p + prm.p0 / prm.rho0 * 0.5 * dt * a_drho, force=a_F,
                 force_prior=a_F, vel=a_v, drho=a_drho, drho_dt=a_drho, pos=eps * prm.DL + dt * a_v, Vol=eps * vol,
                 B=1e-12, zeros=0.0)
+
+
+# ---- what several GPU test files share ----
+HISTORY_FIELDS = ("step", "t", "dt", "vmax", "tau_bottom", "tau_top", "kinetic_energy", "u_bulk")
+STATS_FIELDS = ("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2")
+
+
+def batch_members(cfgmod, geom, dp, DL, variants, jitter=0.2):
+    """One (prm, parts) per variant (mu, c_f, transport_coeff, seed): capi.Batch.from_parts(*zip(*members)) is their batch."""
+    return [make_case(cfgmod, geom, dp=dp, DL=DL, jitter=jitter, seed=v["seed"], developed=True, mu=v["mu"], c_f=v["c_f"],
+                      transport_coeff=v["transport_coeff"]) for v in variants]
+
+
+def full_state(dl, st, mon):
+    """Everything a context or a batch member can be asked for after a step: download(), the status, monitor()."""
+    return dict(dl, t=st["t"], dt_last=st["dt_last"], step=st["step"], vmax=st["vmax"], tau=np.array(mon[:2]),
+                pairs=mon[2])
+
+
+def stats_bands(prm):
+    hw = max(prm.dp, prm.h)
+    return [(0.5 * prm.DL, hw), (0.0, hw)]  # mid-channel and the periodic seam
+
+
+def rel_err(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.abs(a - b) / np.maximum(np.abs(b), 1e-300)
+
+
+def err_id(capi, fn, *args):
+    """(error id, status) of a C ABI call that must be refused."""
+    rc = fn(*args)
+    assert rc != capi.SPHX_OK
+    return capi.lib().sphx_last_error_id().decode(), rc
+
+
+def gateway_cfg(prm, t_end):
+    return dict(DL=prm.DL, DH=prm.DH, dp=prm.dp, h=prm.h, rho0=prm.rho0, mu=prm.mu, c_f=prm.c_f, p0=prm.p0,
+                inv_sigma0=prm.inv_sigma0, gravity_g=prm.gravity_g, transport_coeff=prm.transport_coeff,
+                t_end=t_end, sort_interval=prm.sort_interval)
+
+
+def profiled_launches(ctx, n):
+    ctx.profile_enable(True)
+    ctx.advance(1e9, max_steps=n)
+    prof = ctx.profile_read()
+    ctx.profile_enable(False)
+    return {k: v["launches"] for k, v in prof.items() if v["launches"] > 0}  # (names seen earlier stay listed with 0)
+
+
+def check_kernel_form(ctx, name):
+    """The case `name` of a sampler test's CASES table runs the form of the step it is named after."""
+    if name == "dp025_walk":
+        assert ctx.kernel_forms()["walk_kernels"]
+    if name == "dp05_dynamic":
+        assert ctx.schedule()["dynamic"]
+    if name == "dp025_dual":
+        assert ctx.substeps() > 1
+    if name.startswith("two_cols"):
+        assert ctx.info()["n_cell_x"] == 2
+    if name == "one_col":
+        assert ctx.info()["n_cell_x"] == 1
+
+
+def assert_sums_identical(a, b, what, fields=STATS_FIELDS):
+    """Two lists of a sampler's raw sums, one dict per band: every array bit for bit, the same window."""
+    for band, (x, y) in enumerate(zip(a, b)):
+        for k in fields:
+            assert np.array_equal(x[k], y[k]), f"{what}: band {band} {k}"
+        assert (x["n_samples"], x["t_first"], x["t_last"]) == (y["n_samples"], y["t_first"], y["t_last"]), what
+
+
+def oracle_history_rows(oracle, prm, parts, n_steps):
+    """row k-1 = what the oracle's loop leaves after k steps (restarted from the initial state for every row)"""
+    nf = parts["n_fluid"]
+    rows = np.zeros((n_steps, 8))
+    for k in range(1, n_steps + 1):
+        ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=k, enable_sort=False)
+        s, v, m = ref["stats"], ref["vel"][:nf], ref["mass"][:nf]
+        assert s["steps"] == k
+        rows[k - 1] = (k, s["t"], s["dt_last"], s["vmax"], s["tau_bottom"], s["tau_top"],
+                       np.sum(0.5 * m * (v[:, 0] ** 2 + v[:, 1] ** 2)), np.mean(v[:, 0]))
+    return rows
+
+
+def assert_history_matches_oracle(hist, want, what):
+    n = len(want)
+    assert list(hist["step"]) == list(range(1, n + 1)) and hist["n_dropped"] == 0, what
+    got = {k: hist[k] for k in HISTORY_FIELDS}
+    ref = {k: want[:, j] for j, k in enumerate(HISTORY_FIELDS)}
+    tau_got = np.column_stack([got["tau_bottom"], got["tau_top"]])
+    tau_ref = np.column_stack([ref["tau_bottom"], ref["tau_top"]])
+    tau_scale = np.max(np.abs(tau_ref), axis=1, keepdims=True)
+    print(f"{what}: max rel err t {rel_err(got['t'], ref['t']).max():.2e} dt {rel_err(got['dt'], ref['dt']).max():.2e} "
+          f"vmax {rel_err(got['vmax'], ref['vmax']).max():.2e} tau (of the pair's larger) "
+          f"{(np.abs(tau_got - tau_ref) / tau_scale).max():.2e} kinetic_energy "
+          f"{rel_err(got['kinetic_energy'], ref['kinetic_energy']).max():.2e} u_bulk {rel_err(got['u_bulk'], ref['u_bulk']).max():.2e}")
+    assert np.all(np.abs(got["t"] - ref["t"]) <= 1e-13 * ref["t"]), what
+    assert np.all(np.abs(got["dt"] - ref["dt"]) <= 1e-12 * ref["dt"]), what
+    assert np.all(np.abs(got["vmax"] - ref["vmax"]) <= 1e-9 * ref["vmax"]), what
+    for k in range(n):  # the pair of one step together, as tests/test_gpu_resident.py compares monitor() with the oracle
+        assert_close(tau_got[k], tau_ref[k], rtol=1e-8, atol_scale=1e-9, name=f"{what}: tau of step {k + 1}")
+    assert np.all(rel_err(got["kinetic_energy"], ref["kinetic_energy"]) <= 1e-8), what
+    assert np.all(rel_err(got["u_bulk"], ref["u_bulk"]) <= 1e-8), what

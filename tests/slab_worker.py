@@ -199,8 +199,7 @@ def main():
     if rank == 0:
         pos, vel, drho = got
         if args.engine == "hip":
-            with pkg.capi.Context(prm, nf, parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                                  parts["wall_vel"], t_end=1e9, lanes_per_particle=args.lpp) as ctx:
+            with pkg.capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=args.lpp) as ctx:
                 rs = ctx.advance(1e9, max_steps=args.steps)
                 ref = ctx.download(fields=("pos", "vel", "drho_dt"))
             t_ref = rs["t"]

@@ -48,8 +48,7 @@ def main():
     nf, nt = parts["n_fluid"], parts["n_total"]
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=args.steps, enable_sort=False)
     kw = dict(dynamic_rebin=1, rebuild_every=8) if args.dynamic else {}
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"], t_end=1e9,
-                      lanes_per_particle=args.lpp, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=args.lpp, **kw) as ctx:
         forms, sched = ctx.kernel_forms(), ctx.schedule()
         st = ctx.advance(1e9, max_steps=args.steps)
         got = ctx.download()

@@ -62,6 +62,10 @@ class _NoBatch:
     def __init__(self, *a, **k):
         raise AssertionError("a batch was created before the arguments were checked")
 
+    @classmethod
+    def from_parts(cls, *a, **k):
+        cls()
+
 
 def test_run_sweep_refusals(cfgmod, geom, driver, monkeypatch):
     monkeypatch.setattr(driver.capi, "Batch", _NoBatch)

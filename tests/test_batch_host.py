@@ -33,12 +33,6 @@ def _members(cfgmod, geom, n=3, **kw):
     return [_case(cfgmod, geom, seed=10 + k, **kw) for k in range(n)]
 
 
-def _batch(capi, members, **kw):
-    p0 = members[0][1]
-    return capi.Batch([m[0] for m in members], p0["n_fluid"], p0["n_total"], [m[1]["pos"] for m in members],
-                      [m[1]["vel"] for m in members], [m[1]["drho_dt"] for m in members], p0["mass"], p0["wall_vel"], **kw)
-
-
 def _refused(capi, ident, fn):
     with pytest.raises(capi.SphxError) as e:
         fn()
@@ -50,7 +44,7 @@ def test_mismatched_dp_is_refused(cfgmod, geom, capi):
     members = _members(cfgmod, geom)
     prm1 = cfgmod.params_from_values(dp=0.05000001, DL=3.0)
     members[1] = (prm1, members[1][1])
-    err = _refused(capi, "SPHX:Batch:geometry", lambda: _batch(capi, members, t_end=1.0))
+    err = _refused(capi, "SPHX:Batch:geometry", lambda: capi.Batch.from_parts(*zip(*members), t_end=1.0))
     assert "member 1" in err.message and "dp" in err.message
 
 
@@ -76,7 +70,7 @@ def test_mismatched_n_total_is_refused(cfgmod, geom, capi):
     prm, parts = members[1]
     short = dict(parts, pos=parts["pos"][:-1], vel=parts["vel"][:-1], drho_dt=parts["drho_dt"][:-1])
     members[1] = (prm, short)
-    err = _refused(capi, "SPHX:Batch:geometry", lambda: _batch(capi, members, t_end=1.0))
+    err = _refused(capi, "SPHX:Batch:geometry", lambda: capi.Batch.from_parts(*zip(*members), t_end=1.0))
     assert "member 1" in err.message
 
 
@@ -86,18 +80,19 @@ def test_different_walls_are_refused(cfgmod, geom, capi):
     moved = dict(parts, pos=parts["pos"].copy(order="F"))
     moved["pos"][parts["n_fluid"] + 2, 1] += 1e-3
     members[1] = (prm, moved)
-    err = _refused(capi, "SPHX:Batch:geometry", lambda: _batch(capi, members, t_end=1.0))
+    err = _refused(capi, "SPHX:Batch:geometry", lambda: capi.Batch.from_parts(*zip(*members), t_end=1.0))
     assert "wall positions" in err.message
 
 
 @pytest.mark.parametrize("kw", [dict(dual_rate=2), dict(dynamic_rebin=1)])
 def test_refused_modes(cfgmod, geom, capi, kw):
-    _refused(capi, "SPHX:Batch:mode", lambda: _batch(capi, _members(cfgmod, geom), t_end=1.0, **kw))
+    _refused(capi, "SPHX:Batch:mode", lambda: capi.Batch.from_parts(*zip(*_members(cfgmod, geom)), t_end=1.0, **kw))
 
 
 @pytest.mark.parametrize("lpp", [2, 8])
 def test_large_channel_lane_counts_are_refused(cfgmod, geom, capi, lpp):
-    _refused(capi, "SPHX:Batch:size", lambda: _batch(capi, _members(cfgmod, geom), t_end=1.0, lanes_per_particle=lpp))
+    _refused(capi, "SPHX:Batch:size",
+             lambda: capi.Batch.from_parts(*zip(*_members(cfgmod, geom)), t_end=1.0, lanes_per_particle=lpp))
 
 
 def test_member_count(cfgmod, geom, capi):

@@ -7,7 +7,7 @@ tolerances of test_gpu_resident.py.
 import numpy as np
 import pytest
 
-from helpers import assert_close, make_case, make_variant
+from helpers import assert_close, batch_members, full_state, make_variant
 
 pytestmark = pytest.mark.gpu
 
@@ -15,31 +15,6 @@ FIELDS = ("pos", "vel", "rho", "p", "drho_dt", "force", "force_prior", "Vol", "B
 # members differ in mu, c_f, transport_coeff and the seed of their initial state
 VARIANTS = [dict(mu=0.1, c_f=15.0, transport_coeff=0.30, seed=7), dict(mu=0.15, c_f=17.0, transport_coeff=0.20, seed=8),
             dict(mu=0.08, c_f=13.0, transport_coeff=0.30, seed=9), dict(mu=0.12, c_f=15.0, transport_coeff=0.10, seed=10)]
-
-
-def _members(cfgmod, geom, dp, DL, variants, jitter=0.2):
-    out = []
-    for v in variants:
-        prm, parts = make_case(cfgmod, geom, dp=dp, DL=DL, jitter=jitter, seed=v["seed"], developed=True, mu=v["mu"],
-                               c_f=v["c_f"], transport_coeff=v["transport_coeff"])
-        out.append((prm, parts))
-    return out
-
-
-def _batch(capi, members, **kw):
-    p0 = members[0][1]
-    return capi.Batch([m[0] for m in members], p0["n_fluid"], p0["n_total"], [m[1]["pos"] for m in members],
-                      [m[1]["vel"] for m in members], [m[1]["drho_dt"] for m in members], p0["mass"], p0["wall_vel"], **kw)
-
-
-def _ctx(capi, prm, parts, **kw):
-    return capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                        parts["wall_vel"], **kw)
-
-
-def _everything(dl, st, mon):
-    return dict(dl, t=st["t"], dt_last=st["dt_last"], step=st["step"], vmax=st["vmax"], tau=np.array(mon[:2]),
-                pairs=mon[2])
 
 
 def _assert_identical(a, b, what):
@@ -50,14 +25,14 @@ def _assert_identical(a, b, what):
 @pytest.mark.parametrize("lpp", [16, 32])
 @pytest.mark.parametrize("dp,DL", [(0.05, 3.0), (0.025, 1.5)])
 def test_bit_identical_to_standalone(cfgmod, geom, capi, dp, DL, lpp):
-    members = _members(cfgmod, geom, dp, DL, VARIANTS)
+    members = batch_members(cfgmod, geom, dp, DL, VARIANTS)
     kw = dict(t_end=1e9, lanes_per_particle=lpp)
-    with _batch(capi, members, **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         K = b.info()["rebuild_every"]
         assert b.info()["lanes_per_particle"] == lpp and K > 1
     n = 3 * K + 1  # crosses at least two scheduled re-binnings
     for eager in (False, True):
-        with _batch(capi, members, **kw) as b:
+        with capi.Batch.from_parts(*zip(*members), **kw) as b:
             if eager:  # one-step calls: every slot launched eagerly
                 for _ in range(n):
                     sts = b.advance(1e9, max_steps=1)
@@ -65,12 +40,12 @@ def test_bit_identical_to_standalone(cfgmod, geom, capi, dp, DL, lpp):
             else:
                 sts = b.advance(1e9, max_steps=n)
                 assert b.graph_stats()["slots_replayed"] > 0
-            got = [_everything(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
+            got = [full_state(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
             assert b.info()["realignments"] == 0
         for m, (prm, parts) in enumerate(members):
-            with _ctx(capi, prm, parts, **kw) as ctx:
+            with capi.Context.from_parts(prm, parts, **kw) as ctx:
                 st = ctx.advance(1e9, max_steps=n)
-                ref = _everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
+                ref = full_state(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
             assert got[m]["step"] == n
             _assert_identical(got[m], ref, f"member {m} eager={eager} dp={dp} lpp={lpp}")
 
@@ -86,15 +61,15 @@ def test_shared_moving_walls_and_uneven_mass(cfgmod, geom, capi, oracle):
             parts.update(mass=members[0][1]["mass"], wall_vel=members[0][1]["wall_vel"])
         members.append((prm, parts))
     kw = dict(t_end=1e9, lanes_per_particle=16)
-    with _batch(capi, members, **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         n = 2 * b.info()["rebuild_every"] + 3
         sts = b.advance(1e9, max_steps=n)
-        got = [_everything(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
+        got = [full_state(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
         assert b.info()["realignments"] == 0
     for m, (prm, parts) in enumerate(members):
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, **kw) as ctx:
             st = ctx.advance(1e9, max_steps=n)
-            ref = _everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
+            ref = full_state(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
         _assert_identical(got[m], ref, f"member {m}, moving walls")
     prm, parts = members[1]
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n, enable_sort=False)
@@ -107,23 +82,23 @@ def test_shared_moving_walls_and_uneven_mass(cfgmod, geom, capi, oracle):
 def test_rebuild_every_one_bit_identical_to_standalone(cfgmod, geom, capi):
     """No skin: every slot re-bins and the clock is a launch of its own (k_clock_scan with the cell scan), as one call and
     as one-step calls."""
-    members = _members(cfgmod, geom, 0.05, 1.5, VARIANTS[:3])
+    members = batch_members(cfgmod, geom, 0.05, 1.5, VARIANTS[:3])
     kw = dict(t_end=1e9, lanes_per_particle=16, rebuild_every=1)
     n = 9
     refs = []
     for prm, parts in members:
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, **kw) as ctx:
             st = ctx.advance(1e9, max_steps=n)
-            refs.append(_everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True)))
+            refs.append(full_state(ctx.download(), st, ctx.monitor(tau=True, pairs=True)))
     for eager in (False, True):
-        with _batch(capi, members, **kw) as b:
+        with capi.Batch.from_parts(*zip(*members), **kw) as b:
             assert b.info()["rebuild_every"] == 1
             if eager:
                 for _ in range(n):
                     sts = b.advance(1e9, max_steps=1)
             else:
                 sts = b.advance(1e9, max_steps=n)
-            got = [_everything(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
+            got = [full_state(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
             assert b.info()["realignments"] == 0
         for m in range(len(members)):
             assert got[m]["step"] == n
@@ -131,23 +106,23 @@ def test_rebuild_every_one_bit_identical_to_standalone(cfgmod, geom, capi):
 
 
 def test_single_member_equals_standalone(cfgmod, geom, capi):
-    members = _members(cfgmod, geom, 0.025, 1.5, VARIANTS[1:2])
-    with _batch(capi, members, t_end=1e9) as b:
+    members = batch_members(cfgmod, geom, 0.025, 1.5, VARIANTS[1:2])
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
         st = b.advance(1e9, max_steps=37)[0]
-        got = _everything(b.download(0), st, b.monitor(0, tau=True, pairs=True))
-    with _ctx(capi, *members[0], t_end=1e9) as ctx:
+        got = full_state(b.download(0), st, b.monitor(0, tau=True, pairs=True))
+    with capi.Context.from_parts(*members[0], t_end=1e9) as ctx:
         st = ctx.advance(1e9, max_steps=37)
-        ref = _everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
+        ref = full_state(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
     _assert_identical(got, ref, "M = 1")
 
 
 def test_no_cross_talk(cfgmod, geom, capi):
     variants = [dict(VARIANTS[k % 4], seed=100 + k) for k in range(64)]
-    members = _members(cfgmod, geom, 0.05, 3.0, variants)
+    members = batch_members(cfgmod, geom, 0.05, 3.0, variants)
     kw = dict(t_end=1e9, lanes_per_particle=16)
 
     def run(mem):
-        with _batch(capi, mem, **kw) as b:
+        with capi.Batch.from_parts(*zip(*mem), **kw) as b:
             b.advance(1e9, max_steps=20)
             return {m: b.download(m) for m in (0, 5, 31, 63)}
 
@@ -169,10 +144,10 @@ def _oracle_check(got, ref):
 def test_time_target_realigns_and_matches_oracle(cfgmod, geom, capi, oracle):
     # different c_f: one target time in different step counts
     variants = [dict(VARIANTS[0], c_f=15.0), dict(VARIANTS[1], c_f=21.0), dict(VARIANTS[2], c_f=11.0)]
-    members = _members(cfgmod, geom, 0.05, 3.0, variants)
+    members = batch_members(cfgmod, geom, 0.05, 3.0, variants)
     dt0 = 0.25 * members[0][0].h / (15.0 + 1.5)
     t1, t2 = 10.3 * dt0, 17.9 * dt0
-    with _batch(capi, members, t_end=1e9, lanes_per_particle=16) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9, lanes_per_particle=16) as b:
         sts = b.advance(t1)
         steps = [s["step"] for s in sts]
         assert len(set(steps)) > 1, steps
@@ -195,9 +170,9 @@ def test_time_target_realigns_and_matches_oracle(cfgmod, geom, capi, oracle):
 
 def test_drift_forced_rebinning_matches_oracle(cfgmod, geom, capi, oracle):
     """A skin far too thin for K (as test_gpu_grid_skin.py): the device stops the members, the batch re-bins all of them."""
-    members = _members(cfgmod, geom, 0.05, 3.0, VARIANTS[:3], jitter=0.3)
+    members = batch_members(cfgmod, geom, 0.05, 3.0, VARIANTS[:3], jitter=0.3)
     n = 24
-    with _batch(capi, members, t_end=1e9, lanes_per_particle=16, rebuild_every=8, skin_h=0.03) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9, lanes_per_particle=16, rebuild_every=8, skin_h=0.03) as b:
         sts = b.advance(1e9, max_steps=n)
         got = [b.download(m) for m in range(3)]
         info = b.info()
@@ -209,12 +184,12 @@ def test_drift_forced_rebinning_matches_oracle(cfgmod, geom, capi, oracle):
 
 
 def test_diverging_member_is_named(cfgmod, geom, capi):
-    members = _members(cfgmod, geom, 0.05, 1.5, VARIANTS[:3], jitter=0.1)
+    members = batch_members(cfgmod, geom, 0.05, 1.5, VARIANTS[:3], jitter=0.1)
     prm2, parts2 = members[2]
     bad = dict(parts2, vel=parts2["vel"].copy(order="F"))
     bad["vel"][3, 0] = np.nan
     members[2] = (prm2, bad)
-    with _batch(capi, members, t_end=1e9) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
         with pytest.raises(capi.SphxError) as e:
             b.advance(1e9, max_steps=4)
     assert e.value.code == capi.SPHX_ERR_DIVERGED

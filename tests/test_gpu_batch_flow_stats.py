@@ -7,11 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import make_case
+from helpers import assert_sums_identical, batch_members, err_id, stats_bands
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2")
 VARIANTS = [dict(mu=0.1, c_f=15.0, transport_coeff=0.30, seed=7), dict(mu=0.15, c_f=17.0, transport_coeff=0.20, seed=8),
             dict(mu=0.08, c_f=13.0, transport_coeff=0.30, seed=9), dict(mu=0.12, c_f=15.0, transport_coeff=0.10, seed=10)]
 # (dp, DL): k_flow_stats_b runs ceil(n_fluid / 4096) workgroups per member (as k_flow_stats per context)
@@ -21,38 +20,10 @@ SIZES = {
 }
 
 
-def _members(cfgmod, geom, dp, DL, variants, jitter=0.2):
-    return [make_case(cfgmod, geom, dp=dp, DL=DL, jitter=jitter, seed=v["seed"], developed=True, mu=v["mu"], c_f=v["c_f"],
-                      transport_coeff=v["transport_coeff"]) for v in variants]
-
-
-def _batch(capi, members, **kw):
-    p0 = members[0][1]
-    return capi.Batch([m[0] for m in members], p0["n_fluid"], p0["n_total"], [m[1]["pos"] for m in members],
-                      [m[1]["vel"] for m in members], [m[1]["drho_dt"] for m in members], p0["mass"], p0["wall_vel"], **kw)
-
-
-def _ctx(capi, prm, parts, **kw):
-    return capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                        parts["wall_vel"], **kw)
-
-
-def _bands(prm):
-    hw = max(prm.dp, prm.h)
-    return [(0.5 * prm.DL, hw), (0.0, hw)]  # mid-channel and the periodic seam
-
-
 def _batch_sums(b, n_bands=3):
     """[member][band] sums dicts"""
     per_band = [b.flow_stats_sums(k) for k in range(n_bands)]
     return [[per_band[k][m] for k in range(n_bands)] for m in range(b.n_members)]
-
-
-def _assert_identical(a, b, what):
-    for band, (x, y) in enumerate(zip(a, b)):
-        for k in FIELDS:
-            assert np.array_equal(x[k], y[k]), f"{what}: band {band} {k}"
-        assert (x["n_samples"], x["t_first"], x["t_last"]) == (y["n_samples"], y["t_first"], y["t_last"]), what
 
 
 # 1 ---------------------------------------------------------------------------------------------------------------
@@ -60,24 +31,24 @@ def _assert_identical(a, b, what):
 @pytest.mark.parametrize("size", list(SIZES))
 def test_members_equal_standalone_contexts(cfgmod, geom, capi, size, lpp):
     dp, DL = SIZES[size]
-    members = _members(cfgmod, geom, dp, DL, VARIANTS)
+    members = batch_members(cfgmod, geom, dp, DL, VARIANTS)
     kw = dict(t_end=1e9, lanes_per_particle=lpp)
-    with _batch(capi, members, **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         K = b.info()["rebuild_every"]
         assert b.info()["lanes_per_particle"] == lpp and K > 1
     n = 3 * K + 1  # crosses re-binnings
-    with _ctx(capi, *members[0], **kw) as ctx:
+    with capi.Context.from_parts(*members[0], **kw) as ctx:
         t_mid = ctx.advance(1e9, max_steps=n // 2)["t"]
-    cfg = dict(every=3, t_from=t_mid, bands=_bands(members[0][0]))
+    cfg = dict(every=3, t_from=t_mid, bands=stats_bands(members[0][0]))
     refs = []
     for prm, parts in members:
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, **kw) as ctx:
             ctx.flow_stats_enable(**cfg)
             assert ctx.advance(1e9, max_steps=n)["step"] == n
             refs.append([ctx.flow_stats_sums(k) for k in range(3)])
     assert all(0 < r[0]["n_samples"] < n // 3 for r in refs)
     for eager in (False, True):
-        with _batch(capi, members, **kw) as b:
+        with capi.Batch.from_parts(*zip(*members), **kw) as b:
             b.flow_stats_enable(**cfg)
             if eager:
                 for _ in range(n):
@@ -90,21 +61,21 @@ def test_members_equal_standalone_contexts(cfgmod, geom, capi, size, lpp):
             assert b.info()["realignments"] == 0
         for m in range(len(members)):
             assert sts[m]["step"] == n
-            _assert_identical(got[m], refs[m], f"{size} lpp={lpp} eager={eager} member {m}")
+            assert_sums_identical(got[m], refs[m], f"{size} lpp={lpp} eager={eager} member {m}")
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("size", list(SIZES))
 def test_in_loop_equals_sampling_between_steps(cfgmod, geom, capi, size):
     dp, DL = SIZES[size]
-    members = _members(cfgmod, geom, dp, DL, VARIANTS[:3])
-    bands = _bands(members[0][0])
+    members = batch_members(cfgmod, geom, dp, DL, VARIANTS[:3])
+    bands = stats_bands(members[0][0])
     N = 40
-    with _batch(capi, members, t_end=1e9) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
         b.flow_stats_enable(every=1, bands=bands)
         b.advance(1e9, max_steps=N)
         in_loop = _batch_sums(b)
-    with _batch(capi, members, t_end=1e9) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
         b.flow_stats_enable(every=10 ** 9, bands=bands)
         for _ in range(N):
             b.advance(1e9, max_steps=1)
@@ -112,13 +83,13 @@ def test_in_loop_equals_sampling_between_steps(cfgmod, geom, capi, size):
         between = _batch_sums(b)
     for m in range(len(members)):
         assert in_loop[m][0]["n_samples"] == N
-        _assert_identical(in_loop[m], between[m], f"{size} member {m}: in-loop vs between steps")
+        assert_sums_identical(in_loop[m], between[m], f"{size} member {m}: in-loop vs between steps")
 
 
 # 3 ---------------------------------------------------------------------------------------------------------------
 def _dt_members(cfgmod, geom):
     variants = [dict(VARIANTS[0], c_f=15.0), dict(VARIANTS[1], c_f=21.0), dict(VARIANTS[2], c_f=11.0)]
-    members = _members(cfgmod, geom, 0.05, 3.0, variants)
+    members = batch_members(cfgmod, geom, 0.05, 3.0, variants)
     dt0 = 0.25 * members[0][0].h / (15.0 + 1.5)
     return members, 10.3 * dt0, 17.9 * dt0
 
@@ -126,8 +97,8 @@ def _dt_members(cfgmod, geom):
 @pytest.mark.parametrize("chunks", [False, True])
 def test_idle_members_are_not_sampled(cfgmod, geom, capi, chunks):
     members, t1, t2 = _dt_members(cfgmod, geom)
-    with _batch(capi, members, t_end=1e9, lanes_per_particle=16) as b:
-        b.flow_stats_enable(every=1, t_from=0.0, bands=_bands(members[0][0]))
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9, lanes_per_particle=16) as b:
+        b.flow_stats_enable(every=1, t_from=0.0, bands=stats_bands(members[0][0]))
         if chunks:
             b.advance(t1)
         sts = b.advance(t2)
@@ -146,9 +117,9 @@ def test_no_effect_on_the_physics(cfgmod, geom, capi):
     members, t1, t2 = _dt_members(cfgmod, geom)
     outs = []
     for on in (False, True):
-        with _batch(capi, members, t_end=1e9, lanes_per_particle=16) as b:
+        with capi.Batch.from_parts(*zip(*members), t_end=1e9, lanes_per_particle=16) as b:
             if on:
-                b.flow_stats_enable(every=1, bands=_bands(members[0][0]))
+                b.flow_stats_enable(every=1, bands=stats_bands(members[0][0]))
             b.advance(t1)
             sts = b.advance(t2)
             assert b.info()["realignments"] >= 1
@@ -160,12 +131,12 @@ def test_no_effect_on_the_physics(cfgmod, geom, capi):
 
 
 def test_toggling_recaptures_graphs_and_keeps_the_states(cfgmod, geom, capi):
-    members = _members(cfgmod, geom, 0.05, 3.0, VARIANTS[:3])
+    members = batch_members(cfgmod, geom, 0.05, 3.0, VARIANTS[:3])
     kw = dict(t_end=1e9, lanes_per_particle=16)
-    with _batch(capi, members, **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         b.advance(1e9, max_steps=96)
         plain = [b.download(m, fields=("pos", "vel", "drho_dt")) for m in range(3)]
-    with _batch(capi, members, **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         b.advance(1e9, max_steps=32)                       # graphs without the sampling kernel
         g0 = b.graph_stats()["graphs_captured"]
         b.flow_stats_enable(every=1)
@@ -191,39 +162,33 @@ def test_toggling_recaptures_graphs_and_keeps_the_states(cfgmod, geom, capi):
 
 
 # 5 ---------------------------------------------------------------------------------------------------------------
-def _err(capi, fn, *args):
-    rc = fn(*args)
-    assert rc != capi.SPHX_OK
-    return capi.lib().sphx_last_error_id().decode(), rc
-
-
 def test_error_identifiers(cfgmod, geom, capi):
     L = capi.lib()
-    members = _members(cfgmod, geom, 0.05, 3.0, VARIANTS[:2])
-    with _batch(capi, members, t_end=1e9) as b:
+    members = batch_members(cfgmod, geom, 0.05, 3.0, VARIANTS[:2])
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
         h = b._h
         none8 = (None, *[None] * 5, None, None, None)
-        assert _err(capi, L.sphx_batch_flow_stats_read, h, 0, 0, *none8) == ("SPHX:Stats:disabled", capi.SPHX_ERR_STATE)
-        assert _err(capi, L.sphx_batch_flow_stats_sample, h)[0] == "SPHX:Stats:disabled"
-        assert _err(capi, L.sphx_batch_flow_stats_reset, h)[0] == "SPHX:Stats:disabled"
+        assert err_id(capi, L.sphx_batch_flow_stats_read, h, 0, 0, *none8) == ("SPHX:Stats:disabled", capi.SPHX_ERR_STATE)
+        assert err_id(capi, L.sphx_batch_flow_stats_sample, h)[0] == "SPHX:Stats:disabled"
+        assert err_id(capi, L.sphx_batch_flow_stats_reset, h)[0] == "SPHX:Stats:disabled"
         assert L.sphx_batch_flow_stats_disable(h) == capi.SPHX_OK  # (off already: no-op)
         for bad in (dict(every=0), dict(every=-1), dict(n_bands=3), dict(n_bins=-1), dict(n_bins=1000)):
             c2 = capi.SphxFlowStatsConfig(n_bins=0, every=1, t_from=0.0, n_bands=1)
             for k, v in bad.items():
                 setattr(c2, k, v)
-            assert _err(capi, L.sphx_batch_flow_stats_enable, h, C.byref(c2)) == ("SPHX:Stats:config", capi.SPHX_ERR_ARG), bad
-        assert _err(capi, L.sphx_batch_flow_stats_enable, h, None)[0] == "SPHX:Stats:config"
-        assert _err(capi, L.sphx_batch_flow_stats_read, h, 0, 0, *none8)[0] == "SPHX:Stats:disabled"  # still off
+            assert err_id(capi, L.sphx_batch_flow_stats_enable, h, C.byref(c2)) == ("SPHX:Stats:config", capi.SPHX_ERR_ARG), bad
+        assert err_id(capi, L.sphx_batch_flow_stats_enable, h, None)[0] == "SPHX:Stats:config"
+        assert err_id(capi, L.sphx_batch_flow_stats_read, h, 0, 0, *none8)[0] == "SPHX:Stats:disabled"  # still off
         cfg = capi.SphxFlowStatsConfig(n_bins=0, every=1, t_from=0.0, n_bands=1)
         assert L.sphx_batch_flow_stats_enable(h, C.byref(cfg)) == capi.SPHX_OK
         buf = [np.zeros(2 * 64) for _ in range(5)]
         args = [capi.ptr(x) for x in buf]
-        assert _err(capi, L.sphx_batch_flow_stats_read, h, 2, 64, None, *args, None, None, None)[0] == "SPHX:Stats:band"
-        assert _err(capi, L.sphx_batch_flow_stats_read, h, -1, 64, None, *args, None, None, None)[0] == "SPHX:Stats:band"
+        assert err_id(capi, L.sphx_batch_flow_stats_read, h, 2, 64, None, *args, None, None, None)[0] == "SPHX:Stats:band"
+        assert err_id(capi, L.sphx_batch_flow_stats_read, h, -1, 64, None, *args, None, None, None)[0] == "SPHX:Stats:band"
         n = C.c_int(0)
         assert L.sphx_batch_flow_stats_read(h, 0, 0, C.byref(n), *none8[1:]) == capi.SPHX_OK
         assert n.value == 20
-        assert _err(capi, L.sphx_batch_flow_stats_read, h, 0, n.value - 1, None, *args, None, None, None)[0] == "SPHX:Stats:capacity"
+        assert err_id(capi, L.sphx_batch_flow_stats_read, h, 0, n.value - 1, None, *args, None, None, None)[0] == "SPHX:Stats:capacity"
         ns = np.zeros(2, dtype=np.int64)
         assert L.sphx_batch_flow_stats_read(h, 1, 64, None, *args, ns.ctypes.data_as(C.POINTER(C.c_int64)), None, None) == capi.SPHX_OK
         assert list(ns) == [0, 0]

@@ -14,7 +14,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import assert_close, make_case
+from helpers import assert_history_matches_oracle, batch_members, err_id, make_case, oracle_history_rows, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -30,31 +30,10 @@ SIZES = {
 }
 
 
-def _members(cfgmod, geom, dp, DL, variants, jitter=0.2):
-    return [make_case(cfgmod, geom, dp=dp, DL=DL, jitter=jitter, seed=v["seed"], developed=True, mu=v["mu"], c_f=v["c_f"],
-                      transport_coeff=v["transport_coeff"]) for v in variants]
-
-
-def _batch(capi, members, **kw):
-    p0 = members[0][1]
-    return capi.Batch([m[0] for m in members], p0["n_fluid"], p0["n_total"], [m[1]["pos"] for m in members],
-                      [m[1]["vel"] for m in members], [m[1]["drho_dt"] for m in members], p0["mass"], p0["wall_vel"], **kw)
-
-
-def _ctx(capi, prm, parts, **kw):
-    return capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                        parts["wall_vel"], **kw)
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return np.abs(a - b) / np.maximum(np.abs(b), 1e-300)
-
-
 def _dt_members(cfgmod, geom):
     """members whose dt differ (c_f 15 / 21 / 11): they need different step counts to one target time"""
     variants = [dict(VARIANTS[0], c_f=15.0), dict(VARIANTS[1], c_f=21.0), dict(VARIANTS[2], c_f=11.0)]
-    members = _members(cfgmod, geom, 0.05, 3.0, variants)
+    members = batch_members(cfgmod, geom, 0.05, 3.0, variants)
     dt0 = 0.25 * members[0][0].h / (15.0 + 1.5)
     return members, 10.3 * dt0, 17.9 * dt0
 
@@ -64,20 +43,20 @@ def _dt_members(cfgmod, geom):
 @pytest.mark.parametrize("size", list(SIZES))
 def test_members_equal_standalone_contexts(cfgmod, geom, capi, size, lpp):
     dp, DL = SIZES[size]
-    members = _members(cfgmod, geom, dp, DL, VARIANTS)
+    members = batch_members(cfgmod, geom, dp, DL, VARIANTS)
     nf = members[0][1]["n_fluid"]
     assert -(-nf // 2048) == (1 if size == "one_workgroup" else 3)
     kw = dict(t_end=1e9, lanes_per_particle=lpp)
-    with _batch(capi, members, **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         K = b.info()["rebuild_every"]
         assert b.info()["lanes_per_particle"] == lpp and K > 1
     n = 3 * K + 1  # crosses re-binnings
-    with _ctx(capi, *members[0], **kw) as ctx:
+    with capi.Context.from_parts(*members[0], **kw) as ctx:
         t_mid = ctx.advance(1e9, max_steps=n // 2)["t"]
     cfg = dict(every=3, t_from=t_mid)
     refs = []
     for prm, parts in members:
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, **kw) as ctx:
             ctx.history_enable(**cfg)
             assert ctx.advance(1e9, max_steps=n)["step"] == n
             assert ctx.schedule()["rebins"] >= 2
@@ -87,9 +66,9 @@ def test_members_equal_standalone_contexts(cfgmod, geom, capi, size, lpp):
     for a in range(len(members)):
         for c in range(a + 1, len(members)):
             k = min(len(refs[a]["step"]), len(refs[c]["step"]))
-            assert k > 0 and np.all(_rel(refs[a]["tau_bottom"][:k], refs[c]["tau_bottom"][:k]) > 1e-3), (a, c)
+            assert k > 0 and np.all(rel_err(refs[a]["tau_bottom"][:k], refs[c]["tau_bottom"][:k]) > 1e-3), (a, c)
     for eager in (False, True):
-        with _batch(capi, members, **kw) as b:
+        with capi.Batch.from_parts(*zip(*members), **kw) as b:
             b.history_enable(**cfg)
             if eager:
                 for _ in range(n):
@@ -108,52 +87,18 @@ def test_members_equal_standalone_contexts(cfgmod, geom, capi, size, lpp):
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------
-def _oracle_rows(oracle, prm, parts, n_steps):
-    """row k-1 = what the oracle's loop leaves after k steps (restarted from the initial state for every row)"""
-    nf = parts["n_fluid"]
-    rows = np.zeros((n_steps, 8))
-    for k in range(1, n_steps + 1):
-        ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=k, enable_sort=False)
-        s, v, m = ref["stats"], ref["vel"][:nf], ref["mass"][:nf]
-        assert s["steps"] == k
-        rows[k - 1] = (k, s["t"], s["dt_last"], s["vmax"], s["tau_bottom"], s["tau_top"],
-                       np.sum(0.5 * m * (v[:, 0] ** 2 + v[:, 1] ** 2)), np.mean(v[:, 0]))
-    return rows
-
-
-def _assert_series_matches_oracle(hist, want, what):
-    n = len(want)
-    assert list(hist["step"]) == list(range(1, n + 1)) and hist["n_dropped"] == 0, what
-    got = {k: hist[k] for k in FIELDS}
-    ref = {k: want[:, j] for j, k in enumerate(FIELDS)}
-    tau_got = np.column_stack([got["tau_bottom"], got["tau_top"]])
-    tau_ref = np.column_stack([ref["tau_bottom"], ref["tau_top"]])
-    tau_scale = np.max(np.abs(tau_ref), axis=1, keepdims=True)
-    print(f"{what}: max rel err t {_rel(got['t'], ref['t']).max():.2e} dt {_rel(got['dt'], ref['dt']).max():.2e} "
-          f"vmax {_rel(got['vmax'], ref['vmax']).max():.2e} tau (of the pair's larger) "
-          f"{(np.abs(tau_got - tau_ref) / tau_scale).max():.2e} kinetic_energy "
-          f"{_rel(got['kinetic_energy'], ref['kinetic_energy']).max():.2e} u_bulk {_rel(got['u_bulk'], ref['u_bulk']).max():.2e}")
-    assert np.all(np.abs(got["t"] - ref["t"]) <= 1e-13 * ref["t"]), what
-    assert np.all(np.abs(got["dt"] - ref["dt"]) <= 1e-12 * ref["dt"]), what
-    assert np.all(np.abs(got["vmax"] - ref["vmax"]) <= 1e-9 * ref["vmax"]), what
-    for k in range(n):  # the pair of one step together, as tests/test_gpu_history.py does
-        assert_close(tau_got[k], tau_ref[k], rtol=1e-8, atol_scale=1e-9, name=f"{what}: tau of step {k + 1}")
-    assert np.all(_rel(got["kinetic_energy"], ref["kinetic_energy"]) <= 1e-8), what
-    assert np.all(_rel(got["u_bulk"], ref["u_bulk"]) <= 1e-8), what
-
-
 def test_series_match_the_oracle_step_by_step(cfgmod, geom, capi, oracle):
     n = 12
     members = [make_case(cfgmod, geom, dp=0.05, DL=3.0, jitter=0.2, seed=21, developed=True, mu=0.1),
                make_case(cfgmod, geom, dp=0.05, DL=3.0, jitter=0.2, seed=22, developed=True, mu=0.15, U_bulk=-0.666667),
                make_case(cfgmod, geom, dp=0.05, DL=3.0, jitter=0.2, seed=23, developed=True, mu=0.07)]
     assert members[1][0].gravity_g < 0
-    want = [_oracle_rows(oracle, prm, parts, n) for prm, parts in members]
+    want = [oracle_history_rows(oracle, prm, parts, n) for prm, parts in members]
     for w in want:
         # from one step to the next every field moves by far more than the tolerances: a record taken a step early or late fails
         assert np.all(np.abs(np.diff(w[:, 1:], axis=0)) >= 1e-6 * np.abs(w[1:, 1:]))
     assert np.all(want[1][:, 4:6] < 0) and np.all(want[1][:, 7] < 0)
-    with _batch(capi, members, t_end=1e9, rebuild_every=4) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9, rebuild_every=4) as b:
         assert b.info()["rebuild_every"] == 4
         b.history_enable(every=1)
         sts = b.advance(1e9, max_steps=n)
@@ -166,7 +111,7 @@ def test_series_match_the_oracle_step_by_step(cfgmod, geom, capi, oracle):
     assert slots >= n and (slots - 1) // info["rebuild_every"] >= 2, (slots, info)
     for m in range(3):
         assert sts[m]["step"] == n
-        _assert_series_matches_oracle(got[m], want[m], f"member {m}")
+        assert_history_matches_oracle(got[m], want[m], f"member {m}")
     assert np.all(got[1]["tau_bottom"] < 0) and np.all(got[1]["tau_top"] < 0) and np.all(got[1]["u_bulk"] < 0)
 
 
@@ -174,9 +119,9 @@ def test_series_match_the_oracle_step_by_step(cfgmod, geom, capi, oracle):
 @pytest.mark.parametrize("size", list(SIZES))
 def test_last_record_is_what_the_host_path_reports(cfgmod, geom, capi, size):
     dp, DL = SIZES[size]
-    members = _members(cfgmod, geom, dp, DL, VARIANTS[:3])
+    members = batch_members(cfgmod, geom, dp, DL, VARIANTS[:3])
     nf = members[0][1]["n_fluid"]
-    with _batch(capi, members, t_end=1e9) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
         b.history_enable(every=1)
         sts = b.advance(1e9, max_steps=45)
         got = b.history()
@@ -188,8 +133,8 @@ def test_last_record_is_what_the_host_path_reports(cfgmod, geom, capi, size):
         mass = members[m][1]["mass"][:nf]
         ke = float(np.sum(0.5 * mass * (vels[m][:, 0] ** 2 + vels[m][:, 1] ** 2)))
         ub = float(np.mean(vels[m][:, 0]))
-        err = dict(tau_bottom=_rel(h["tau_bottom"][-1], mons[m][0]), tau_top=_rel(h["tau_top"][-1], mons[m][1]),
-                   kinetic_energy=_rel(h["kinetic_energy"][-1], ke), u_bulk=_rel(h["u_bulk"][-1], ub))
+        err = dict(tau_bottom=rel_err(h["tau_bottom"][-1], mons[m][0]), tau_top=rel_err(h["tau_top"][-1], mons[m][1]),
+                   kinetic_energy=rel_err(h["kinetic_energy"][-1], ke), u_bulk=rel_err(h["u_bulk"][-1], ub))
         print(size, m, {k: f"{float(v):.2e}" for k, v in err.items()})
         for k, v in err.items():
             assert v <= 1e-12, f"{size} member {m}: {k} off by {float(v):.3e} (summation order only)"
@@ -199,7 +144,7 @@ def test_last_record_is_what_the_host_path_reports(cfgmod, geom, capi, size):
 @pytest.mark.parametrize("chunks", [False, True])
 def test_idle_members_record_nothing(cfgmod, geom, capi, chunks):
     members, t1, t2 = _dt_members(cfgmod, geom)
-    with _batch(capi, members, t_end=1e9, lanes_per_particle=16) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9, lanes_per_particle=16) as b:
         b.history_enable(every=1)
         if chunks:
             b.advance(t1)
@@ -218,7 +163,7 @@ def test_idle_members_record_nothing(cfgmod, geom, capi, chunks):
 # 5 ---------------------------------------------------------------------------------------------------------------
 def test_full_buffers_are_per_member(cfgmod, geom, capi):
     members, _, t2 = _dt_members(cfgmod, geom)
-    with _batch(capi, members, t_end=1e9, lanes_per_particle=16) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9, lanes_per_particle=16) as b:
         b.history_enable(every=1, capacity=5)
         sts = b.advance(t2)
         steps = [s["step"] for s in sts]
@@ -243,7 +188,7 @@ def test_no_feedback_on_the_physics(cfgmod, geom, capi):
     members, t1, t2 = _dt_members(cfgmod, geom)
     outs = []
     for on in (False, True):
-        with _batch(capi, members, t_end=1e9, lanes_per_particle=16) as b:
+        with capi.Batch.from_parts(*zip(*members), t_end=1e9, lanes_per_particle=16) as b:
             if on:
                 b.history_enable(every=1)
             b.advance(t1)
@@ -258,12 +203,12 @@ def test_no_feedback_on_the_physics(cfgmod, geom, capi):
 
 # 7 ---------------------------------------------------------------------------------------------------------------
 def test_toggling_recaptures_graphs_and_keeps_the_states(cfgmod, geom, capi):
-    members = _members(cfgmod, geom, 0.05, 3.0, VARIANTS[:3])
+    members = batch_members(cfgmod, geom, 0.05, 3.0, VARIANTS[:3])
     kw = dict(t_end=1e9, lanes_per_particle=16)
-    with _batch(capi, members, **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         b.advance(1e9, max_steps=96)
         plain = [b.download(m, fields=("pos", "vel", "drho_dt")) for m in range(3)]
-    with _batch(capi, members, **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         b.advance(1e9, max_steps=32)                       # graphs without the history kernel
         g0 = b.graph_stats()["graphs_captured"]
         b.history_enable(every=1)
@@ -287,10 +232,10 @@ def test_toggling_recaptures_graphs_and_keeps_the_states(cfgmod, geom, capi):
 
 # 8 ---------------------------------------------------------------------------------------------------------------
 def test_independent_of_the_batch_flow_statistics(cfgmod, geom, capi):
-    members = _members(cfgmod, geom, 0.05, 3.0, VARIANTS[:3])
+    members = batch_members(cfgmod, geom, 0.05, 3.0, VARIANTS[:3])
     runs = {}
     for hist, stats in ((True, False), (False, True), (True, True)):
-        with _batch(capi, members, t_end=1e9) as b:
+        with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
             if stats:
                 b.flow_stats_enable(every=3)
             if hist:
@@ -311,10 +256,10 @@ def test_independent_of_the_batch_flow_statistics(cfgmod, geom, capi):
 # 9 ---------------------------------------------------------------------------------------------------------------
 def test_repeatable(cfgmod, geom, capi):
     dp, DL = SIZES["three_workgroups"]
-    members = _members(cfgmod, geom, dp, DL, VARIANTS[:3])
+    members = batch_members(cfgmod, geom, dp, DL, VARIANTS[:3])
     runs = []
     for _ in range(2):
-        with _batch(capi, members, t_end=1e9) as b:
+        with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
             b.history_enable(every=1)
             b.advance(1e9, max_steps=60)
             runs.append(b.history_records())
@@ -324,41 +269,35 @@ def test_repeatable(cfgmod, geom, capi):
 
 
 # 10 --------------------------------------------------------------------------------------------------------------
-def _err(capi, fn, *args):
-    rc = fn(*args)
-    assert rc != capi.SPHX_OK
-    return capi.lib().sphx_last_error_id().decode(), rc
-
-
 def test_error_identifiers(cfgmod, geom, capi):
     L = capi.lib()
     M = 5  # 5 * (1 << 22) records exceed the cap on n_members * capacity, 1 << 24
-    members = _members(cfgmod, geom, 0.05, 3.0, (VARIANTS + VARIANTS[:1])[:M])
+    members = batch_members(cfgmod, geom, 0.05, 3.0, (VARIANTS + VARIANTS[:1])[:M])
     n = np.full(M, -1, dtype=np.int32)
     dropped = np.full(M, -1, dtype=np.int64)
     pn, pd = n.ctypes.data_as(C.POINTER(C.c_int)), dropped.ctypes.data_as(C.POINTER(C.c_int64))
     ok = capi.SphxHistoryConfig(every=1, capacity=16, t_from=0.0)
     for fn, args in ((L.sphx_batch_history_enable, (C.byref(ok),)), (L.sphx_batch_history_disable, ()),
                      (L.sphx_batch_history_read, (0, None, None, None, 0))):
-        assert _err(capi, fn, None, *args) == ("SPHX:Batch:null", capi.SPHX_ERR_ARG)
+        assert err_id(capi, fn, None, *args) == ("SPHX:Batch:null", capi.SPHX_ERR_ARG)
     bad_configs = (dict(every=0), dict(every=-1), dict(capacity=0), dict(capacity=-5), dict(capacity=(1 << 22) + 1),
                    dict(capacity=1 << 22), dict(capacity=(1 << 24) // M + 1),  # (the last two: n_members * capacity > 1 << 24)
                    dict(t_from=float("nan")), dict(t_from=float("inf")), dict(t_from=-float("inf")))
-    with _batch(capi, members, t_end=1e9) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
         h = b._h
-        assert _err(capi, L.sphx_batch_history_read, h, 0, None, pn, pd, 0) == ("SPHX:History:disabled", capi.SPHX_ERR_STATE)
+        assert err_id(capi, L.sphx_batch_history_read, h, 0, None, pn, pd, 0) == ("SPHX:History:disabled", capi.SPHX_ERR_STATE)
         assert L.sphx_batch_history_disable(h) == capi.SPHX_OK       # no-op when off
         for bad in bad_configs:
             c2 = capi.SphxHistoryConfig(every=1, capacity=16, t_from=0.0)
             for k, v in bad.items():
                 setattr(c2, k, v)
-            assert _err(capi, L.sphx_batch_history_enable, h, C.byref(c2)) == ("SPHX:History:config", capi.SPHX_ERR_ARG), bad
-        assert _err(capi, L.sphx_batch_history_enable, h, None) == ("SPHX:History:config", capi.SPHX_ERR_ARG)
+            assert err_id(capi, L.sphx_batch_history_enable, h, C.byref(c2)) == ("SPHX:History:config", capi.SPHX_ERR_ARG), bad
+        assert err_id(capi, L.sphx_batch_history_enable, h, None) == ("SPHX:History:config", capi.SPHX_ERR_ARG)
         with pytest.raises(capi.SphxError) as e:
             b.history_enable(capacity=1 << 22)
         assert e.value.identifier == "SPHX:History:config"
         # a refused config leaves the batch without a history, and stepping
-        assert _err(capi, L.sphx_batch_history_read, h, 0, None, None, None, 0)[0] == "SPHX:History:disabled"
+        assert err_id(capi, L.sphx_batch_history_read, h, 0, None, None, None, 0)[0] == "SPHX:History:disabled"
         assert [s["step"] for s in b.advance(1e9, max_steps=3)] == [3] * M
         assert L.sphx_batch_history_enable(h, C.byref(ok)) == capi.SPHX_OK
         b.advance(1e9, max_steps=5)
@@ -369,9 +308,9 @@ def test_error_identifiers(cfgmod, geom, capi):
             c2 = capi.SphxHistoryConfig(every=1, capacity=16, t_from=0.0)
             for k, v in bad.items():
                 setattr(c2, k, v)
-            assert _err(capi, L.sphx_batch_history_enable, h, C.byref(c2))[0] == "SPHX:History:config", bad
+            assert err_id(capi, L.sphx_batch_history_enable, h, C.byref(c2))[0] == "SPHX:History:config", bad
         buf = np.full((M, 5, 8), -1.0)
-        assert _err(capi, L.sphx_batch_history_read, h, 4, capi.ptr(buf), None, None, 1) == \
+        assert err_id(capi, L.sphx_batch_history_read, h, 4, capi.ptr(buf), None, None, 1) == \
             ("SPHX:History:capacity", capi.SPHX_ERR_ARG)
         assert np.all(buf == -1.0)
         wide = np.full((M, 7, 8), -1.0)                                # ... and nothing was drained; rows beyond n_records stay
@@ -425,7 +364,7 @@ def test_run_sweep(cfgmod, driver):
         assert r.steps > 30 and h["n_dropped"] == 0 and r.time_avg is None
         assert list(h["step"]) == list(range(1, r.steps + 1)), m      # no gap and no repeat across the three drains
         assert h["t"][-1] == r.t and np.all(np.diff(h["t"]) > 0)
-        assert _rel(h["tau_bottom"][-1], r.tau_bottom) <= 1e-12 and _rel(h["tau_top"][-1], r.tau_top) <= 1e-12
+        assert rel_err(h["tau_bottom"][-1], r.tau_bottom) <= 1e-12 and rel_err(h["tau_top"][-1], r.tau_top) <= 1e-12
         fig = driver.history_figures(prms[m], h, t_from=0.03, tol=0.5)
         assert 0 < fig["n_records"] < r.steps
         for k, v in fig.items():

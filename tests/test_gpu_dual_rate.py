@@ -13,17 +13,11 @@ from helpers import make_case
 pytestmark = pytest.mark.gpu
 
 
-def _ctx(capi, prm, parts, **kw):
-    nf, nt = parts["n_fluid"], parts["n_total"]
-    return capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                        t_end=1e9, **kw)
-
-
 def test_dual_rate_off_is_the_default_path(cfgmod, geom, capi):
     prm, parts = make_case(cfgmod, geom, dp=0.025, DL=2.0, jitter=0.1, seed=3, developed=True)
     outs = []
     for dr in (0, 1):
-        with _ctx(capi, prm, parts, dual_rate=dr) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, dual_rate=dr) as ctx:
             assert ctx.substeps() == 1
             st = ctx.advance(1e9, max_steps=40)
             outs.append((st, ctx.download()))
@@ -35,10 +29,10 @@ def test_dual_rate_off_is_the_default_path(cfgmod, geom, capi):
 def test_dual_rate_needs_an_eligible_context(cfgmod, geom, capi):
     # viscous-limited (fine) channel: no acoustic sub-step fits, and large channels run other kernels
     prm, parts = make_case(cfgmod, geom, dp=0.005, DL=0.5, jitter=0.0, seed=1, developed=False)
-    with _ctx(capi, prm, parts, dual_rate=4) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, dual_rate=4) as ctx:
         assert ctx.substeps() == 1
     prm, parts = make_case(cfgmod, geom, dp=0.025, DL=2.0, jitter=0.0, seed=1, developed=False)
-    with _ctx(capi, prm, parts, dual_rate=2, lanes_per_particle=8) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, dual_rate=2, lanes_per_particle=8) as ctx:
         assert ctx.substeps() == 1
     # viscous-limited by its physics at a small size (regime_cases.viscous, mu = 2): floor(min(dt_visc, dt_body) / dt_ac) < 2
     import dual_rate_reference as drr
@@ -46,27 +40,27 @@ def test_dual_rate_needs_an_eligible_context(cfgmod, geom, capi):
     vprm, vparts = regime_cases.viscous(cfgmod, geom, "small")
     assert drr.substeps(vprm, 4) == 1
     for lanes in (16, 32):
-        with _ctx(capi, vprm, vparts, dual_rate=4, lanes_per_particle=lanes) as ctx:
+        with capi.Context.from_parts(vprm, vparts, t_end=1e9, dual_rate=4, lanes_per_particle=lanes) as ctx:
             assert ctx.substeps() == 1
     with pytest.raises(capi.SphxError):
-        _ctx(capi, prm, parts, dual_rate=9)
+        capi.Context.from_parts(prm, parts, t_end=1e9, dual_rate=9)
     # the range check does not depend on eligibility (few lanes per particle, negative values)
     for bad, kw in ((9, dict(lanes_per_particle=8)), (-1, dict()), (5, dict(lanes_per_particle=2))):
         with pytest.raises(capi.SphxError) as ei:
-            _ctx(capi, prm, parts, dual_rate=bad, **kw)
+            capi.Context.from_parts(prm, parts, t_end=1e9, dual_rate=bad, **kw)
         assert ei.value.identifier == "SPHX:Ctx:dual_rate"
 
 
 def test_dual_rate_outer_step_advances_time_by_all_substeps(cfgmod, geom, capi):
     prm, parts = make_case(cfgmod, geom, dp=0.025, DL=2.0, jitter=0.05, seed=2, developed=True)
-    with _ctx(capi, prm, parts, dual_rate=2) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, dual_rate=2) as ctx:
         assert ctx.substeps() == 2
         st1 = ctx.advance(1e9, max_steps=1)
         assert st1["step"] == 1 and abs(st1["t"] - 2 * st1["dt_last"]) <= 1e-15
         st = ctx.advance(1e9, max_steps=60)  # crosses re-binning steps (K = 8)
         got = ctx.download()
         assert st["step"] == 61 and ctx.grid_policy()["rebuild_every"] < 60
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ref_st = ctx.advance(st["t"])
         ref = ctx.download()
     # same simulated time by both loops from the same start: the fields agree to the time-integration error

@@ -44,9 +44,7 @@ RTOL = 1e-10  # tests/test_gpu_headline_parity.py, RTOL[20] and RTOL[35]
 
 def _gpu(capi, prm, parts, calls, **kw):
     """calls: [(t_target, max_steps), ...] -> context facts, [(status, download) after each call]."""
-    nf, nt = parts["n_fluid"], parts["n_total"]
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"], t_end=1e9,
-                      **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         info = dict(tuning=ctx.tuning(), policy=ctx.grid_policy(), sched=ctx.schedule(), substeps=ctx.substeps())
         outs = []
         for t_target, max_steps in calls:

@@ -42,8 +42,7 @@ def test_coincident_and_isolated_particles(cfgmod, geom, mex, oracle, capi):
     # the resident loop keeps agreeing with the oracle on this state
     run = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=3, enable_sort=False)
     for lpp in (1, 4):
-        with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                          t_end=1e9, lanes_per_particle=lpp) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp) as ctx:
             ctx.advance(1e9, max_steps=3)
             out = ctx.download()
         for k in ("pos", "vel", "rho", "drho_dt", "B"):
@@ -85,11 +84,10 @@ def test_particle_outside_the_cell_rows(cfgmod, geom, capi, oracle):
     """A fluid particle above the top wall block is clamped into the last cell row (neighbor.c:275-276); it has
     no neighbours there and must not disturb anything else."""
     prm, parts = make_case(cfgmod, geom, dp=0.05, DL=1.5, jitter=0.1, seed=5, developed=True)
-    nf, nt = parts["n_fluid"], parts["n_total"]
     parts["pos"][5] = (0.4, 2.5)
     parts["vel"][5] = (0.0, 0.0)
     run = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=2, enable_sort=False)
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"], t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=2)
         out = ctx.download(fields=("pos", "vel", "drho_dt"))
     for k in out:
@@ -99,8 +97,7 @@ def test_particle_outside_the_cell_rows(cfgmod, geom, capi, oracle):
 def test_non_finite_velocity_raises_device_status(cfgmod, geom, capi):
     prm, parts = make_case(cfgmod, geom, dp=0.05, DL=1.5, jitter=0.1, seed=5)
     parts["vel"][3, 0] = np.nan
-    with capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                      parts["wall_vel"], t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         with pytest.raises(capi.SphxError) as e:
             ctx.advance(1e9, max_steps=4)
         assert e.value.code == capi.SPHX_ERR_DIVERGED
@@ -109,12 +106,10 @@ def test_non_finite_velocity_raises_device_status(cfgmod, geom, capi):
 def test_neighbour_list_overflow_is_reported(cfgmod, geom, capi):
     """More than 64 neighbours inside 2h: the device raises SPHX_ERR_GRID instead of truncating silently."""
     prm, parts = make_case(cfgmod, geom, dp=0.05, DL=1.5, jitter=0.0, seed=5, developed=False)
-    nf = parts["n_fluid"]
     rng = np.random.default_rng(0)
     parts["pos"][:90, 0] = 0.75 + 0.02 * rng.random(90)
     parts["pos"][:90, 1] = 0.50 + 0.02 * rng.random(90)
-    with capi.Context(prm, nf, parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                      parts["wall_vel"], t_end=1e9, lanes_per_particle=1) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=1) as ctx:
         with pytest.raises(capi.SphxError) as e:
             ctx.advance(1e9, max_steps=2)
         assert e.value.code == capi.SPHX_ERR_GRID
@@ -149,8 +144,7 @@ def test_two_column_channel_matches_oracle(cfgmod, geom, mex, capi, oracle, DL):
     assert_close(a[4], b[4], rtol=1e-13, atol=1e-15 * prm.DL, name="r")
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=4, enable_sort=False)
     for lpp in (0, 4, 2):  # automatic (compact kernels) and the large-channel kernel forms (cell sweep with the duplicate column)
-        with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                          t_end=1e9, lanes_per_particle=lpp) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp) as ctx:
             assert ctx.info()["n_cell_x"] == 2 and ctx.grid_policy()["rebuild_every"] == 1
             ctx.advance(1e9, max_steps=4)
             got = ctx.download()

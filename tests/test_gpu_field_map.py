@@ -13,7 +13,7 @@ import pytest
 
 import mex_mock
 from field_map_cases import void_case
-from helpers import make_case, make_variant
+from helpers import assert_sums_identical, check_kernel_form, err_id, gateway_cfg, make_case, make_variant, profiled_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -39,25 +39,6 @@ def _case(cfgmod, geom, name, seed=11):
     return prm, parts, kw
 
 
-def _ctx(capi, prm, parts, **kw):
-    nf, nt = parts["n_fluid"], parts["n_total"]
-    return capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                        t_end=1e9, **kw)
-
-
-def _check_form(ctx, name):
-    if name == "dp025_walk":
-        assert ctx.kernel_forms()["walk_kernels"]
-    if name == "dp05_dynamic":
-        assert ctx.schedule()["dynamic"]
-    if name == "dp025_dual":
-        assert ctx.substeps() > 1
-    if name.startswith("two_cols"):
-        assert ctx.info()["n_cell_x"] == 2
-    if name == "one_col":
-        assert ctx.info()["n_cell_x"] == 1
-
-
 def _numpy_planes(profmod, prm, f):
     """One sample's six planes from shepard_field's sums (whole grid [ny, nx] or picked nodes)."""
     hit = f["S0"] > 0.0
@@ -75,10 +56,8 @@ def _assert_planes_match(got, want, what):
         assert err <= BOUND * scale, f"{what}: {k} off by {err / scale:.3e} of the largest |value|"
 
 
-def _assert_identical(a, b, what):
-    for k in PLANES:
-        assert np.array_equal(a[k], b[k]), f"{what}: {k}"
-    assert (a["n_samples"], a["t_first"], a["t_last"]) == (b["n_samples"], b["t_first"], b["t_last"]), what
+def _assert_map_identical(a, b, what):
+    assert_sums_identical([a], [b], what, PLANES)
 
 
 def _assert_close(a, b, what):
@@ -102,8 +81,8 @@ def _picked_nodes(nx, ny, n=2000, seed=5):
 def test_sample_now_matches_numpy(cfgmod, geom, capi, profmod, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     nf = parts["n_fluid"]
-    with _ctx(capi, prm, parts, **kw) as ctx:
-        _check_form(ctx, name)
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
+        check_kernel_form(ctx, name)
         ctx.field_map_enable(every=10 ** 9)
         ctx.advance(1e9, max_steps=7)
         ctx.field_map_sample()
@@ -133,7 +112,7 @@ def test_sample_now_matches_numpy(cfgmod, geom, capi, profmod, name):
 def test_walls_enter_with_their_velocity(cfgmod, geom, capi, profmod):
     prm, parts = make_variant(cfgmod, geom, dp=0.05, DL=1.5, jitter=0.2, seed=11, developed=True)
     nf = parts["n_fluid"]
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.field_map_enable(every=10 ** 9, with_walls=True)
         ctx.advance(1e9, max_steps=7)
         ctx.field_map_sample()
@@ -151,7 +130,7 @@ def test_walls_enter_with_their_velocity(cfgmod, geom, capi, profmod):
 def test_void_nodes_are_skipped(cfgmod, geom, capi, profmod):
     prm, parts = void_case(cfgmod, geom)
     nf = parts["n_fluid"]
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.field_map_enable()
         ctx.field_map_sample()                               # no step taken: the state as uploaded
         d = ctx.download(fields=("pos", "vel"))
@@ -173,7 +152,7 @@ def test_void_nodes_are_skipped(cfgmod, geom, capi, profmod):
 def test_in_loop_equals_sampling_between_steps(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     N = 48
-    with _ctx(capi, prm, parts, **kw) as ctx:            # in the loop, one advance call (graph replays)
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:  # in the loop, one advance call (graph replays)
         ctx.field_map_enable(every=1)
         st = ctx.advance(1e9, max_steps=N)
         assert st["step"] == N
@@ -182,7 +161,7 @@ def test_in_loop_equals_sampling_between_steps(cfgmod, geom, capi, name):
         in_loop = ctx.field_map_sums()
     assert rebins >= 2, f"{name}: only {rebins} re-binnings in {N} steps"
     assert in_loop["n_samples"] == N and np.all(in_loop["count"] == N)
-    with _ctx(capi, prm, parts, **kw) as ctx:            # from the host, after every single step
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:  # from the host, after every single step
         ctx.field_map_enable(every=10 ** 9)
         for _ in range(N):
             ctx.advance(1e9, max_steps=1)
@@ -190,15 +169,15 @@ def test_in_loop_equals_sampling_between_steps(cfgmod, geom, capi, name):
         forced_b = ctx.grid_policy()["forced_rebuilds"]
         between = ctx.field_map_sums()
     # (a stop on the drift bound changes the re-binning phase, and with it the order a node sums its candidates in)
-    same = _assert_identical if forced_a == 0 and forced_b == 0 else _assert_close
+    same = _assert_map_identical if forced_a == 0 and forced_b == 0 else _assert_close
     same(in_loop, between, f"{name}: in-loop vs between steps")
-    with _ctx(capi, prm, parts, **kw) as ctx:            # in the loop, chunked calls (eager slots and short graphs)
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:  # in the loop, chunked calls (eager slots and short graphs)
         ctx.field_map_enable(every=1)
         for n in (1, 3, 5, 11, 28):
             ctx.advance(1e9, max_steps=n)
         forced_c = ctx.grid_policy()["forced_rebuilds"]
         chunked = ctx.field_map_sums()
-    same = _assert_identical if forced_a == 0 and forced_c == 0 else _assert_close
+    same = _assert_map_identical if forced_a == 0 and forced_c == 0 else _assert_close
     same(in_loop, chunked, f"{name}: one call vs chunked")
 
 
@@ -207,11 +186,11 @@ def test_in_loop_equals_sampling_between_steps(cfgmod, geom, capi, name):
 def test_gating_every_and_t_from(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     N, every = 40, 3
-    with _ctx(capi, prm, parts, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         statuses = [ctx.advance(1e9, max_steps=1) for _ in range(N)]
     t_from = 0.5 * (statuses[N // 2]["t"] + statuses[N // 2 + 1]["t"])
     want = [s for s in statuses if s["step"] % every == 0 and s["t"] >= t_from]
-    with _ctx(capi, prm, parts, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         ctx.field_map_enable(every=every, t_from=t_from)
         ctx.advance(1e9, max_steps=N)
         got = ctx.field_map()
@@ -226,7 +205,7 @@ def test_no_feedback_on_the_physics(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     outs = []
     for on in (False, True):
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
             if on:
                 ctx.field_map_enable(every=1, with_walls=True)
                 ctx.flow_stats_enable(every=1)
@@ -241,24 +220,16 @@ def test_no_feedback_on_the_physics(cfgmod, geom, capi, name):
 
 
 # 7 ---------------------------------------------------------------------------------------------------------------
-def _profiled_launches(ctx, n):
-    ctx.profile_enable(True)
-    ctx.advance(1e9, max_steps=n)
-    prof = ctx.profile_read()
-    ctx.profile_enable(False)
-    return {k: v["launches"] for k, v in prof.items() if v["launches"] > 0}  # (names seen earlier stay listed with 0)
-
-
 def test_off_means_no_extra_launch(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
-    with _ctx(capi, prm, parts) as ctx:                   # steps 1-20 and 21-40: the same re-binning phases as below
-        never = _profiled_launches(ctx, 20)
-        never2 = _profiled_launches(ctx, 20)
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:  # steps 1-20 and 21-40: the same re-binning phases as below
+        never = profiled_launches(ctx, 20)
+        never2 = profiled_launches(ctx, 20)
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.field_map_enable(every=1)
-        on = _profiled_launches(ctx, 20)
+        on = profiled_launches(ctx, 20)
         ctx.field_map_disable()
-        off = _profiled_launches(ctx, 20)
+        off = profiled_launches(ctx, 20)
     assert "k_field_map" not in never and "k_field_map" not in never2 and "k_field_map" not in off
     assert on.pop("k_field_map") == 20
     assert on == never and off == never2
@@ -266,7 +237,7 @@ def test_off_means_no_extra_launch(cfgmod, geom, capi):
 
 def test_enable_disable_take_effect_on_existing_graphs(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=64)                    # graphs exist without the sampling kernel
         ctx.field_map_enable(every=1)
         ctx.advance(1e9, max_steps=64)
@@ -296,37 +267,31 @@ def test_repeatable(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     runs = []
     for _ in range(2):
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
             ctx.field_map_enable(every=1)
             ctx.advance(1e9, max_steps=40)
             runs.append(ctx.field_map_sums())
-    _assert_identical(runs[0], runs[1], name)
+    _assert_map_identical(runs[0], runs[1], name)
 
 
 # 9 ---------------------------------------------------------------------------------------------------------------
-def _err(capi, fn, *args):
-    rc = fn(*args)
-    assert rc != capi.SPHX_OK
-    return capi.lib().sphx_last_error_id().decode(), rc
-
-
 def test_error_identifiers(cfgmod, geom, capi, pkg):
     L = capi.lib()
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
     nothing = (None, None, *[None] * 6, None, None, None)
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         h = ctx._h
-        assert _err(capi, L.sphx_ctx_field_map_read, h, 0, *nothing) == ("SPHX:Field:disabled", capi.SPHX_ERR_STATE)
-        assert _err(capi, L.sphx_ctx_field_map_sample, h) == ("SPHX:Field:disabled", capi.SPHX_ERR_STATE)
-        assert _err(capi, L.sphx_ctx_field_map_reset, h) == ("SPHX:Field:disabled", capi.SPHX_ERR_STATE)
+        assert err_id(capi, L.sphx_ctx_field_map_read, h, 0, *nothing) == ("SPHX:Field:disabled", capi.SPHX_ERR_STATE)
+        assert err_id(capi, L.sphx_ctx_field_map_sample, h) == ("SPHX:Field:disabled", capi.SPHX_ERR_STATE)
+        assert err_id(capi, L.sphx_ctx_field_map_reset, h) == ("SPHX:Field:disabled", capi.SPHX_ERR_STATE)
         assert L.sphx_ctx_field_map_disable(h) == capi.SPHX_OK       # a no-op when off
         for bad in (dict(nx=1), dict(ny=1), dict(nx=-2), dict(ny=-1), dict(nx=1 << 13, ny=(1 << 12) + 1), dict(every=0),
                     dict(every=-1), dict(t_from=float("nan")), dict(with_walls=2), dict(with_walls=-1)):
             c2 = capi.SphxFieldMapConfig(nx=0, ny=0, every=1, with_walls=0, t_from=0.0)
             for k, v in bad.items():
                 setattr(c2, k, v)
-            assert _err(capi, L.sphx_ctx_field_map_enable, h, C.byref(c2)) == ("SPHX:Field:config", capi.SPHX_ERR_ARG), bad
-        assert _err(capi, L.sphx_ctx_field_map_enable, h, None) == ("SPHX:Field:config", capi.SPHX_ERR_ARG)
+            assert err_id(capi, L.sphx_ctx_field_map_enable, h, C.byref(c2)) == ("SPHX:Field:config", capi.SPHX_ERR_ARG), bad
+        assert err_id(capi, L.sphx_ctx_field_map_enable, h, None) == ("SPHX:Field:config", capi.SPHX_ERR_ARG)
         with pytest.raises(capi.SphxError) as e:
             ctx.field_map_enable(every=0)
         assert e.value.identifier == "SPHX:Field:config"
@@ -338,7 +303,7 @@ def test_error_identifiers(cfgmod, geom, capi, pkg):
         buf = np.zeros(4800)
         for slot in range(6):
             arrs = [capi.ptr(buf) if k == slot else None for k in range(6)]
-            assert _err(capi, L.sphx_ctx_field_map_read, h, 4799, None, None, *arrs, None, None, None)[0] == "SPHX:Field:capacity"
+            assert err_id(capi, L.sphx_ctx_field_map_read, h, 4799, None, None, *arrs, None, None, None)[0] == "SPHX:Field:capacity"
         assert L.sphx_ctx_field_map_read(h, 4800, None, None, capi.ptr(buf), *[None] * 5, None, None, None) == capi.SPHX_OK
     eng = pkg.slab.HipSlabEngine(prm, parts, 0, 2, 0, t_end=1e9, native=True)
     try:
@@ -346,7 +311,7 @@ def test_error_identifiers(cfgmod, geom, capi, pkg):
         for fn, args in ((L.sphx_ctx_field_map_enable, (C.byref(cfg),)), (L.sphx_ctx_field_map_disable, ()),
                          (L.sphx_ctx_field_map_reset, ()), (L.sphx_ctx_field_map_sample, ()),
                          (L.sphx_ctx_field_map_read, (0, *nothing))):
-            assert _err(capi, fn, eng._h, *args) == ("SPHX:Field:slab", capi.SPHX_ERR_ARG)
+            assert err_id(capi, fn, eng._h, *args) == ("SPHX:Field:slab", capi.SPHX_ERR_ARG)
     finally:
         eng.close()
 
@@ -364,18 +329,12 @@ def test_driver_fills_field_avg(cfgmod, driver):
 
 
 # 11 --------------------------------------------------------------------------------------------------------------
-def _cfg(prm, t_end):
-    return dict(DL=prm.DL, DH=prm.DH, dp=prm.dp, h=prm.h, rho0=prm.rho0, mu=prm.mu, c_f=prm.c_f, p0=prm.p0,
-                inv_sigma0=prm.inv_sigma0, gravity_g=prm.gravity_g, transport_coeff=prm.transport_coeff,
-                t_end=t_end, sort_interval=prm.sort_interval)
-
-
 def test_matlab_gateway_field_commands(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
     gw = mex_mock.Gateway("sphx_ctx_mex.c")
     nf, nt = parts["n_fluid"], parts["n_total"]
     state = (parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"])
-    (h,) = gw(1, "create", _cfg(prm, 1e9), nf, nt, *state, 0.0, 0)
+    (h,) = gw(1, "create", gateway_cfg(prm, 1e9), nf, nt, *state, 0.0, 0)
     try:
         with pytest.raises(mex_mock.MexError) as e:
             gw(9, "field_read", h)
@@ -392,7 +351,7 @@ def test_matlab_gateway_field_commands(cfgmod, geom, capi):
         assert e.value.identifier == "SPHX:Field:disabled"
     finally:
         gw(0, "destroy", h)
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.field_map_enable(every=2, with_walls=True)
         ctx.advance(1e9, max_steps=30)
         ctx.field_map_sample()

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import mex_mock
-from helpers import make_case
+from helpers import assert_sums_identical, check_kernel_form, err_id, gateway_cfg, make_case, profiled_launches, stats_bands
 
 pytestmark = pytest.mark.gpu
 
@@ -32,26 +32,6 @@ def _case(cfgmod, geom, name, seed=11):
     dp, DL, kw, mk = CASES[name]
     prm, parts = make_case(cfgmod, geom, **dict(dict(dp=dp, DL=DL, jitter=0.2, seed=seed, developed=True), **mk))
     return prm, parts, kw
-
-
-def _ctx(capi, prm, parts, **kw):
-    nf, nt = parts["n_fluid"], parts["n_total"]
-    return capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                        t_end=1e9, **kw)
-
-
-def _bands(prm):
-    hw = max(prm.dp, prm.h)
-    return [(0.5 * prm.DL, hw), (0.0, hw)]
-
-
-def _check_form(ctx, name):
-    if name == "dp025_walk":
-        assert ctx.kernel_forms()["walk_kernels"]
-    if name == "dp05_dynamic":
-        assert ctx.schedule()["dynamic"]
-    if name == "dp025_dual":
-        assert ctx.substeps() > 1
 
 
 def _numpy_sums(pos, vel, prm, n_bins, band=None):
@@ -84,22 +64,15 @@ def _all_sums(ctx, n_bands=3):
     return [ctx.flow_stats_sums(b) for b in range(n_bands)]
 
 
-def _assert_identical(a, b, what):
-    for band, (x, y) in enumerate(zip(a, b)):
-        for k in FIELDS:
-            assert np.array_equal(x[k], y[k]), f"{what}: band {band} {k}"
-        assert (x["n_samples"], x["t_first"], x["t_last"]) == (y["n_samples"], y["t_first"], y["t_last"]), what
-
-
 # 1 ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(CASES))
 def test_sample_now_matches_numpy(cfgmod, geom, capi, profmod, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     nf = parts["n_fluid"]
     n_bins = profmod.n_profile_bins(prm.DH, prm.dp)
-    bands = _bands(prm)
-    with _ctx(capi, prm, parts, **kw) as ctx:
-        _check_form(ctx, name)
+    bands = stats_bands(prm)
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
+        check_kernel_form(ctx, name)
         ctx.flow_stats_enable(every=10 ** 9, bands=bands)
         ctx.advance(1e9, max_steps=7)
         ctx.flow_stats_sample()
@@ -135,7 +108,7 @@ def test_particles_on_edges_and_outside(cfgmod, geom, capi, profmod):
     assert idx[-1] < nf
     pos[idx, 1] = specials
     parts = dict(parts, pos=pos)
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.flow_stats_enable(n_bins=n_bins, every=10 ** 9)
         ctx.flow_stats_sample()
         d = ctx.download(fields=("pos", "vel"))
@@ -153,9 +126,9 @@ def test_particles_on_edges_and_outside(cfgmod, geom, capi, profmod):
 @pytest.mark.parametrize("name", ["dp05_auto", "dp025_lpp16", "dp025_walk", "dp05_dynamic", "dp025_dual", "dp01_multi"])
 def test_in_loop_equals_sampling_between_steps(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
-    bands = _bands(prm)
+    bands = stats_bands(prm)
     N = 48
-    with _ctx(capi, prm, parts, **kw) as ctx:            # in the loop, one advance call (graph replays)
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:  # in the loop, one advance call (graph replays)
         ctx.flow_stats_enable(every=1, bands=bands)
         st = ctx.advance(1e9, max_steps=N)
         assert st["step"] == N
@@ -163,19 +136,19 @@ def test_in_loop_equals_sampling_between_steps(cfgmod, geom, capi, name):
         in_loop = _all_sums(ctx)
     assert rebins >= 2, f"{name}: only {rebins} re-binnings in {N} steps"
     assert in_loop[0]["n_samples"] == N
-    with _ctx(capi, prm, parts, **kw) as ctx:            # from the host, after every single step
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:  # from the host, after every single step
         ctx.flow_stats_enable(every=10 ** 9, bands=bands)
         for _ in range(N):
             ctx.advance(1e9, max_steps=1)
             ctx.flow_stats_sample()
         between = _all_sums(ctx)
-    _assert_identical(in_loop, between, f"{name}: in-loop vs between steps")
-    with _ctx(capi, prm, parts, **kw) as ctx:            # in the loop, chunked calls (eager slots and short graphs)
+    assert_sums_identical(in_loop, between, f"{name}: in-loop vs between steps")
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:  # in the loop, chunked calls (eager slots and short graphs)
         ctx.flow_stats_enable(every=1, bands=bands)
         for n in (1, 3, 5, 11, 28):
             ctx.advance(1e9, max_steps=n)
         chunked = _all_sums(ctx)
-    _assert_identical(in_loop, chunked, f"{name}: one call vs chunked")
+    assert_sums_identical(in_loop, chunked, f"{name}: one call vs chunked")
 
 
 # 4 ---------------------------------------------------------------------------------------------------------------
@@ -183,11 +156,11 @@ def test_in_loop_equals_sampling_between_steps(cfgmod, geom, capi, name):
 def test_gating_every_and_t_from(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     N, every = 40, 3
-    with _ctx(capi, prm, parts, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         statuses = [ctx.advance(1e9, max_steps=1) for _ in range(N)]
     t_from = 0.5 * (statuses[N // 2]["t"] + statuses[N // 2 + 1]["t"])
     want = [s for s in statuses if s["step"] % every == 0 and s["t"] >= t_from]
-    with _ctx(capi, prm, parts, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         ctx.flow_stats_enable(every=every, t_from=t_from)
         ctx.advance(1e9, max_steps=N)
         got = ctx.flow_stats(0)
@@ -201,9 +174,9 @@ def test_no_feedback_on_the_physics(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     outs = []
     for on in (False, True):
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
             if on:
-                ctx.flow_stats_enable(every=1, bands=_bands(prm))
+                ctx.flow_stats_enable(every=1, bands=stats_bands(prm))
             st = ctx.advance(1e9, max_steps=45)
             outs.append((st, ctx.download(fields=("pos", "vel", "drho_dt"))))
     assert outs[0][0] == outs[1][0]
@@ -211,24 +184,16 @@ def test_no_feedback_on_the_physics(cfgmod, geom, capi, name):
         assert np.array_equal(outs[0][1][k], outs[1][1][k]), k
 
 
-def _profiled_launches(ctx, n):
-    ctx.profile_enable(True)
-    ctx.advance(1e9, max_steps=n)
-    prof = ctx.profile_read()
-    ctx.profile_enable(False)
-    return {k: v["launches"] for k, v in prof.items() if v["launches"] > 0}  # (names seen earlier stay listed with 0)
-
-
 def test_off_means_no_extra_launch(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
-    with _ctx(capi, prm, parts) as ctx:                   # steps 1-20 and 21-40: the same re-binning phases as below
-        never = _profiled_launches(ctx, 20)
-        never2 = _profiled_launches(ctx, 20)
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:  # steps 1-20 and 21-40: the same re-binning phases as below
+        never = profiled_launches(ctx, 20)
+        never2 = profiled_launches(ctx, 20)
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.flow_stats_enable(every=1)
-        on = _profiled_launches(ctx, 20)
+        on = profiled_launches(ctx, 20)
         ctx.flow_stats_disable()
-        off = _profiled_launches(ctx, 20)
+        off = profiled_launches(ctx, 20)
     assert "k_flow_stats" not in never and "k_flow_stats" not in never2 and "k_flow_stats" not in off
     assert on.pop("k_flow_stats") == 20
     assert on == never and off == never2
@@ -236,7 +201,7 @@ def test_off_means_no_extra_launch(cfgmod, geom, capi):
 
 def test_enable_disable_take_effect_on_existing_graphs(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=64)                    # graphs exist without the sampling kernel
         ctx.flow_stats_enable(every=1)
         ctx.advance(1e9, max_steps=64)
@@ -264,51 +229,45 @@ def test_repeatable(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     runs = []
     for _ in range(2):
-        with _ctx(capi, prm, parts, **kw) as ctx:
-            ctx.flow_stats_enable(every=1, bands=_bands(prm))
+        with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
+            ctx.flow_stats_enable(every=1, bands=stats_bands(prm))
             ctx.advance(1e9, max_steps=60)
             runs.append(_all_sums(ctx))
-    _assert_identical(runs[0], runs[1], name)
+    assert_sums_identical(runs[0], runs[1], name)
 
 
 # 7 ---------------------------------------------------------------------------------------------------------------
-def _err(capi, fn, *args):
-    rc = fn(*args)
-    assert rc != capi.SPHX_OK
-    return capi.lib().sphx_last_error_id().decode(), rc
-
-
 def test_error_identifiers(cfgmod, geom, capi, pkg):
     L = capi.lib()
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         h = ctx._h
         cfg = capi.SphxFlowStatsConfig(n_bins=0, every=1, t_from=0.0, n_bands=1)
-        assert _err(capi, L.sphx_ctx_flow_stats_read, h, 0, 0, None, *[None] * 5, None, None, None)[0] == "SPHX:Stats:disabled"
-        assert _err(capi, L.sphx_ctx_flow_stats_sample, h)[0] == "SPHX:Stats:disabled"
+        assert err_id(capi, L.sphx_ctx_flow_stats_read, h, 0, 0, None, *[None] * 5, None, None, None)[0] == "SPHX:Stats:disabled"
+        assert err_id(capi, L.sphx_ctx_flow_stats_sample, h)[0] == "SPHX:Stats:disabled"
         for bad in (dict(every=0), dict(every=-1), dict(n_bands=3), dict(n_bins=-1), dict(n_bins=1000)):
             c2 = capi.SphxFlowStatsConfig(n_bins=0, every=1, t_from=0.0, n_bands=1)
             for k, v in bad.items():
                 setattr(c2, k, v)
-            assert _err(capi, L.sphx_ctx_flow_stats_enable, h, C.byref(c2)) == ("SPHX:Stats:config", capi.SPHX_ERR_ARG), bad
+            assert err_id(capi, L.sphx_ctx_flow_stats_enable, h, C.byref(c2)) == ("SPHX:Stats:config", capi.SPHX_ERR_ARG), bad
         with pytest.raises(capi.SphxError) as e:
             ctx.flow_stats_enable(every=0)
         assert e.value.identifier == "SPHX:Stats:config"
         assert L.sphx_ctx_flow_stats_enable(h, C.byref(cfg)) == capi.SPHX_OK
         n = C.c_int(0)
         buf = [np.zeros(64) for _ in range(5)]
-        assert _err(capi, L.sphx_ctx_flow_stats_read, h, 2, 64, None, *[capi.ptr(b) for b in buf], None, None, None)[0] == "SPHX:Stats:band"
-        assert _err(capi, L.sphx_ctx_flow_stats_read, h, -1, 64, None, *[capi.ptr(b) for b in buf], None, None, None)[0] == "SPHX:Stats:band"
+        assert err_id(capi, L.sphx_ctx_flow_stats_read, h, 2, 64, None, *[capi.ptr(b) for b in buf], None, None, None)[0] == "SPHX:Stats:band"
+        assert err_id(capi, L.sphx_ctx_flow_stats_read, h, -1, 64, None, *[capi.ptr(b) for b in buf], None, None, None)[0] == "SPHX:Stats:band"
         assert L.sphx_ctx_flow_stats_read(h, 0, 0, C.byref(n), *[None] * 5, None, None, None) == capi.SPHX_OK
         assert n.value == 20
-        assert _err(capi, L.sphx_ctx_flow_stats_read, h, 0, n.value - 1, None, *[capi.ptr(b) for b in buf], None, None, None)[0] == "SPHX:Stats:capacity"
+        assert err_id(capi, L.sphx_ctx_flow_stats_read, h, 0, n.value - 1, None, *[capi.ptr(b) for b in buf], None, None, None)[0] == "SPHX:Stats:capacity"
     eng = pkg.slab.HipSlabEngine(prm, parts, 0, 2, 0, t_end=1e9, native=True)
     try:
         cfg = capi.SphxFlowStatsConfig(n_bins=0, every=1, t_from=0.0, n_bands=0)
         for fn, args in ((L.sphx_ctx_flow_stats_enable, (C.byref(cfg),)), (L.sphx_ctx_flow_stats_disable, ()),
                          (L.sphx_ctx_flow_stats_reset, ()), (L.sphx_ctx_flow_stats_sample, ()),
                          (L.sphx_ctx_flow_stats_read, (0, 0, None, *[None] * 5, None, None, None))):
-            assert _err(capi, fn, eng._h, *args) == ("SPHX:Stats:slab", capi.SPHX_ERR_ARG)
+            assert err_id(capi, fn, eng._h, *args) == ("SPHX:Stats:slab", capi.SPHX_ERR_ARG)
     finally:
         eng.close()
 
@@ -326,19 +285,13 @@ def test_time_averaged_profile_meets_the_acceptance_bar(cfgmod, driver):
 
 
 # 9 ---------------------------------------------------------------------------------------------------------------
-def _cfg(prm, t_end):
-    return dict(DL=prm.DL, DH=prm.DH, dp=prm.dp, h=prm.h, rho0=prm.rho0, mu=prm.mu, c_f=prm.c_f, p0=prm.p0,
-                inv_sigma0=prm.inv_sigma0, gravity_g=prm.gravity_g, transport_coeff=prm.transport_coeff,
-                t_end=t_end, sort_interval=prm.sort_interval)
-
-
 def test_matlab_gateway_stats_commands(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
     gw = mex_mock.Gateway("sphx_ctx_mex.c")
     nf, nt = parts["n_fluid"], parts["n_total"]
     state = (parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"])
-    bands = np.array(_bands(prm))
-    (h,) = gw(1, "create", _cfg(prm, 1e9), nf, nt, *state, 0.0, 0)
+    bands = np.array(stats_bands(prm))
+    (h,) = gw(1, "create", gateway_cfg(prm, 1e9), nf, nt, *state, 0.0, 0)
     try:
         gw(0, "stats_enable", h, 0, 2, 0.0, bands)
         gw(1, "advance", h, 1e9, 30)
@@ -349,7 +302,7 @@ def test_matlab_gateway_stats_commands(cfgmod, geom, capi):
         assert e.value.identifier == "SPHX:Stats:band"
     finally:
         gw(0, "destroy", h)
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.flow_stats_enable(every=2, bands=[tuple(b) for b in bands])
         ctx.advance(1e9, max_steps=30)
         ctx.flow_stats_sample()

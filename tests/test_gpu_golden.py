@@ -60,8 +60,7 @@ def test_golden_modes(gold, mex):
 
 def test_golden_resident_five_steps(gold, capi):
     g, prm, nb, parts = gold
-    with capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                      parts["wall_vel"], t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         st = ctx.advance(1e9, max_steps=5)
         got = ctx.download()
         tb, tt, npairs = ctx.monitor(tau=True, pairs=True)
@@ -107,8 +106,7 @@ def test_reference_golden_modes(refgold, mex):
 def test_reference_golden_resident_five_steps(refgold, capi, lpp):
     g, prm, nb, parts = refgold
     t_end = float(g["run5_t_end"])
-    with capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                      parts["wall_vel"], t_end=1e9, lanes_per_particle=lpp) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp) as ctx:
         st = ctx.advance(t_end)
         got = ctx.download()
         tb, tt, npairs = ctx.monitor(tau=True, pairs=True)

@@ -36,11 +36,6 @@ def moving_case(cfgmod, geom):
     return make_variant(cfgmod, geom, dp=0.04, DL=1.5, jitter=0.3, seed=11, developed=True, rho0=2.5, transport_coeff=0.1)
 
 
-def _ctx(capi, prm, parts, **kw):
-    return capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"],
-                        parts["mass"], parts["wall_vel"], t_end=1e9, **kw)
-
-
 def _pol(ctx):
     p = ctx.grid_policy()
     return p["rebuild_every"], p["skin"], p["forced_rebuilds"]
@@ -56,7 +51,7 @@ def _check(got, ref, tag):
 def test_any_rebuild_interval_matches_oracle(case, capi, oracle, K, n_steps):
     prm, parts = case
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_steps, enable_sort=False)
-    with _ctx(capi, prm, parts, rebuild_every=K, lanes_per_particle=8) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, rebuild_every=K, lanes_per_particle=8) as ctx:
         pol = ctx.grid_policy()
         assert pol["rebuild_every"] == K and (pol["skin"] > 0) == (K > 1)
         st = ctx.advance(1e9, max_steps=n_steps)
@@ -77,7 +72,7 @@ def test_moving_walls_and_uneven_mass_across_rebinnings(moving_case, capi, oracl
     prm, parts = moving_case
     n_steps = 35
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_steps, enable_sort=False)
-    with _ctx(capi, prm, parts, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         assert ctx.grid_policy()["rebuild_every"] == kw["rebuild_every"]
         assert ctx.schedule()["dynamic"] == kw.get("dynamic_rebin", 0)
         st = ctx.advance(1e9, max_steps=n_steps)
@@ -96,7 +91,7 @@ def test_undersized_skin_forces_rebuilds_and_stays_exact(case, capi, oracle):
     prm, parts = case
     n_steps = 12
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_steps, enable_sort=False)
-    with _ctx(capi, prm, parts, rebuild_every=8, skin_h=0.03, lanes_per_particle=4) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, rebuild_every=8, skin_h=0.03, lanes_per_particle=4) as ctx:
         st = ctx.advance(1e9, max_steps=n_steps)
         pol = ctx.grid_policy()
         got = ctx.download()
@@ -116,17 +111,17 @@ def test_call_pattern_does_not_change_the_bits(case, capi, kw):
     prm, parts = case
     n = 23
     outs = []
-    with _ctx(capi, prm, parts, steps_per_graph=4, **kw) as a:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, steps_per_graph=4, **kw) as a:
         a.advance(1e9, max_steps=n)
         outs.append(a.download(fields=("pos", "vel", "drho_dt", "rho", "Vol")))
         pol_a = _pol(a)
-    with _ctx(capi, prm, parts, steps_per_graph=4, **kw) as b:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, steps_per_graph=4, **kw) as b:
         for _ in range(n):
             st = b.advance(1e9, max_steps=1)
         assert st["step"] == n
         outs.append(b.download(fields=("pos", "vel", "drho_dt", "rho", "Vol")))
         assert _pol(b) == pol_a
-    with _ctx(capi, prm, parts, steps_per_graph=4, **kw) as c:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, steps_per_graph=4, **kw) as c:
         c.enqueue_steps(9)
         c.enqueue_steps(6)
         st = c.sync()
@@ -150,15 +145,15 @@ def test_large_channel_kernels_hand_out_the_last_step_of_any_batch(case, capi, l
     n = 13
     fields = ("pos", "vel", "rho", "p", "drho_dt", "force", "force_prior", "Vol", "B")
     outs = []
-    with _ctx(capi, prm, parts, lanes_per_particle=lpp, rebuild_every=5) as a:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp, rebuild_every=5) as a:
         assert a.kernel_forms()["walk_kernels"]
         st_a = a.advance(1e9, max_steps=n)
         outs.append(a.download(fields=fields))
-    with _ctx(capi, prm, parts, lanes_per_particle=lpp, rebuild_every=5) as b:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp, rebuild_every=5) as b:
         for _ in range(n):
             b.advance(1e9, max_steps=1)
         outs.append(b.download(fields=fields))
-    with _ctx(capi, prm, parts, lanes_per_particle=lpp, rebuild_every=5) as c:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp, rebuild_every=5) as c:
         c.enqueue_steps(4)
         c.enqueue_steps(6)
         c.sync()
@@ -166,7 +161,7 @@ def test_large_channel_kernels_hand_out_the_last_step_of_any_batch(case, capi, l
         c.enqueue_steps(3)
         c.sync()
         outs.append(c.download(fields=fields))
-    with _ctx(capi, prm, parts, lanes_per_particle=lpp, rebuild_every=5) as d:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp, rebuild_every=5) as d:
         d.advance(1e9, max_steps=10)
         ten = d.download(fields=fields)                      # ... are those of a batch that ends there
         st_d = d.advance(st_a["t"], max_steps=0)             # the rest by target time: the step that reaches it is the last
@@ -189,18 +184,18 @@ def test_download_without_a_sync_takes_the_steps_a_stopped_batch_owes(case, capi
     called straight away, without sphx_ctx_sync, must first take the owed steps like sync does: state AND outputs of step n."""
     prm, parts = case
     n = 23
-    with _ctx(capi, prm, parts, lanes_per_particle=lpp, rebuild_every=8, skin_h=0.03) as a:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp, rebuild_every=8, skin_h=0.03) as a:
         assert a.kernel_forms()["walk_kernels"]
         a.enqueue_steps(n)
         st_a = a.sync()
         assert st_a["step"] == n and a.grid_policy()["forced_rebuilds"] > 0  # (the batch did stop on the way)
         ref = a.download(fields=FIELDS)
         tau_ref = a.monitor(tau=True, pairs=True)
-    with _ctx(capi, prm, parts, lanes_per_particle=lpp, rebuild_every=8, skin_h=0.03) as b:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp, rebuild_every=8, skin_h=0.03) as b:
         b.enqueue_steps(n)
         got = b.download(fields=FIELDS)   # no sync
         assert b.sync()["step"] == n
-    with _ctx(capi, prm, parts, lanes_per_particle=lpp, rebuild_every=8, skin_h=0.03) as c:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp, rebuild_every=8, skin_h=0.03) as c:
         c.enqueue_steps(n)
         tau_got = c.monitor(tau=True, pairs=True)   # no sync
         assert c.sync()["step"] == n
@@ -215,7 +210,7 @@ def test_cool_downs_follow_a_fixed_schedule(case, capi):
     prm, parts = case
     kw = dict(rebuild_every=6, skin_h=0.04, steps_per_graph=8, lanes_per_particle=8)
     n = 2300
-    with _ctx(capi, prm, parts, **kw) as a:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as a:
         a.advance(1e9, max_steps=40)
         early = a.grid_policy()
         a.advance(1e9, max_steps=n - 40)
@@ -223,7 +218,7 @@ def test_cool_downs_follow_a_fixed_schedule(case, capi):
         pol_a = _pol(a)
     assert early["rebuild_every"] == 6 and early["forced_rebuilds"] >= 2
     assert pol_a[2] > early["forced_rebuilds"]  # after each cool-down it tried the interval again (and was stopped again)
-    with _ctx(capi, prm, parts, **kw) as b:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as b:
         done = 0
         for chunk in (700, 1, 323, 1000, 276):
             b.enqueue_steps(chunk)
@@ -242,7 +237,7 @@ def test_graphs_replay_from_any_phase(calm_case, capi):
     at a different phase on every call: each (phase, length) gets its graph once, after that every call is pure
     replay -- and gives the bits of one long call."""
     prm, parts = calm_case
-    with _ctx(capi, prm, parts, rebuild_every=8) as a:  # K = 8, 20-step calls: pos cycles 5, 1, 5, ... and lay flips
+    with capi.Context.from_parts(prm, parts, t_end=1e9, rebuild_every=8) as a:  # K = 8, 20-step calls: pos cycles 5, 1, 5, ... and lay flips
         a.advance(1e9, max_steps=5)                     # start misaligned (pos = 5)
         for _ in range(8):
             a.advance(1e9, max_steps=20)
@@ -255,7 +250,7 @@ def test_graphs_replay_from_any_phase(calm_case, capi):
     assert hot["graphs_captured"] == warm["graphs_captured"]                 # nothing new to capture
     assert hot["slots_eager"] == warm["slots_eager"]                         # and nothing launched eagerly
     assert hot["slots_replayed"] - warm["slots_replayed"] == 8 * 20
-    with _ctx(capi, prm, parts, rebuild_every=8) as b:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, rebuild_every=8) as b:
         b.advance(1e9, max_steps=5 + 16 * 20)
         Bd = b.download(fields=("pos", "vel", "drho_dt"))
     for k in A:
@@ -266,11 +261,11 @@ def test_graphs_replay_after_a_forced_rebuild(case, capi):
     """A forced rebuild flips the state parity without taking a step; with an even K the context then never returns
     to the phase its first graph was captured from.  It must keep replaying graphs all the same."""
     prm, parts = case
-    with _ctx(capi, prm, parts, rebuild_every=8, skin_h=0.03, lanes_per_particle=4) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, rebuild_every=8, skin_h=0.03, lanes_per_particle=4) as ctx:
         ctx.advance(1e9, max_steps=12)
         assert ctx.grid_policy()["forced_rebuilds"] >= 1
     # a skin that is adequate most of the time: forced rebuilds are rare events followed by a 16-step cool-down
-    with _ctx(capi, prm, parts, rebuild_every=8, skin_h=0.25, steps_per_graph=16) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, rebuild_every=8, skin_h=0.25, steps_per_graph=16) as ctx:
         ctx.advance(1e9, max_steps=3000)
         pol, g0 = ctx.grid_policy(), ctx.graph_stats()
         ctx.advance(1e9, max_steps=1600)
@@ -284,7 +279,7 @@ def test_graphs_replay_after_a_forced_rebuild(case, capi):
 
 def test_prepare_steps_makes_the_next_batch_pure_replay(calm_case, capi):
     prm, parts = calm_case
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.enqueue_steps(5)
         ctx.sync()
         ctx.prepare_steps(20)
@@ -301,7 +296,7 @@ def test_prepare_steps_makes_the_next_batch_pure_replay(calm_case, capi):
 def test_pair_list_between_rebuilds(case, capi, oracle, n_steps):
     """The MEX-convention pair list taken from a stale (but still valid) grid equals a fresh search."""
     prm, parts = case
-    with _ctx(capi, prm, parts, rebuild_every=5) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, rebuild_every=5) as ctx:
         ctx.advance(1e9, max_steps=n_steps)
         nb = ctx.neighbor_list()
         pos = ctx.download(fields=("pos",))["pos"]
@@ -314,7 +309,7 @@ def test_pair_list_between_rebuilds(case, capi, oracle, n_steps):
 def test_narrow_domain_falls_back_to_every_step(cfgmod, geom, capi):
     """DL too short for three skinned cell columns -> K = 1, no skin (the periodic sweep needs ncx >= 3)."""
     prm, parts = make_case(cfgmod, geom, dp=0.05, DL=0.45, jitter=0.1, seed=3, developed=True)
-    with _ctx(capi, prm, parts, rebuild_every=6, skin_h=0.5) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, rebuild_every=6, skin_h=0.5) as ctx:
         pol = ctx.grid_policy()
         assert pol["rebuild_every"] == 1 and pol["skin"] == 0.0
         assert ctx.advance(1e9, max_steps=3)["step"] == 3
@@ -329,7 +324,7 @@ def test_dynamic_rebinning_matches_oracle(case, capi, oracle, kw, n_steps):
     (nearly) every step, decided on the device without the host."""
     prm, parts = case
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_steps, enable_sort=False)
-    with _ctx(capi, prm, parts, dynamic_rebin=1, lanes_per_particle=4, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, dynamic_rebin=1, lanes_per_particle=4, **kw) as ctx:
         st = ctx.advance(1e9, max_steps=n_steps)
         got = ctx.download()
         tb, tt, npairs = ctx.monitor(tau=True, pairs=True)
@@ -349,7 +344,7 @@ def test_dynamic_rebinning_is_chunk_invariant_and_repeatable(case, capi):
     n = 61
     outs = []
     for pattern in ("one", "single", "batches", "one"):
-        with _ctx(capi, prm, parts, **kw) as c:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as c:
             if pattern == "one":
                 c.advance(1e9, max_steps=n)
             elif pattern == "single":
@@ -371,7 +366,7 @@ def test_dynamic_pair_list_and_outputs_right_after_a_rebinning(case, capi, oracl
     prm, parts = case
     for n_steps in (3, 4):  # K = 4: step 4 ends with a re-binning, step 3 does not
         ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_steps, enable_sort=False)
-        with _ctx(capi, prm, parts, dynamic_rebin=1, rebuild_every=4) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, dynamic_rebin=1, rebuild_every=4) as ctx:
             ctx.advance(1e9, max_steps=n_steps)
             got = ctx.download()
             nb = ctx.neighbor_list()

@@ -59,8 +59,7 @@ def test_default_headline_context_with_moving_walls_and_uneven_mass(cfgmod, geom
 
 def _default_context_matches_oracle(name, prm, parts, lanes, n_steps, capi, oracle, capsys):
     nf, nt = parts["n_fluid"], parts["n_total"]
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                      t_end=1e9) as ctx:  # every tuning knob left at its default: this is bench.py's context
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:  # every tuning knob left at its default: this is bench.py's context
         tun, pol = ctx.tuning(), ctx.grid_policy()
         sched = ctx.schedule()
         st = ctx.advance(1e9, max_steps=n_steps)
@@ -104,8 +103,7 @@ def test_headline_context_from_the_reference_lattice(cfgmod, geom, capi, oracle)
     nf, nt = parts["n_fluid"], parts["n_total"]
     assert (nf, nt) == (4800, 5760)
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=35, enable_sort=False)
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                      t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         st = ctx.advance(1e9, max_steps=35)
         got = ctx.download()
         _, _, npairs = ctx.monitor(tau=False, pairs=True)

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import mex_mock
-from helpers import assert_close, make_case, make_variant
+from helpers import (assert_history_matches_oracle, check_kernel_form, err_id, gateway_cfg, make_case, make_variant,
+                     oracle_history_rows, profiled_launches, rel_err)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,26 +34,6 @@ def _case(cfgmod, geom, name, seed=11):
     return prm, parts, kw
 
 
-def _ctx(capi, prm, parts, **kw):
-    nf, nt = parts["n_fluid"], parts["n_total"]
-    return capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                        t_end=1e9, **kw)
-
-
-def _check_form(ctx, name):
-    if name == "dp025_walk":
-        assert ctx.kernel_forms()["walk_kernels"]
-    if name == "dp05_dynamic":
-        assert ctx.schedule()["dynamic"]
-    if name == "dp025_dual":
-        assert ctx.substeps() > 1
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return np.abs(a - b) / np.maximum(np.abs(b), 1e-300)
-
-
 def _host_sums(parts, d):
     """kinetic energy and bulk velocity of a downloaded state, as the header defines them"""
     nf = parts["n_fluid"]
@@ -61,58 +42,24 @@ def _host_sums(parts, d):
 
 
 # 1 ---------------------------------------------------------------------------------------------------------------
-def _oracle_rows(oracle, prm, parts, n_steps):
-    """row k-1 = what the oracle's loop leaves after k steps (restarted from the initial state for every row)"""
-    nf = parts["n_fluid"]
-    rows = np.zeros((n_steps, 8))
-    for k in range(1, n_steps + 1):
-        ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=k, enable_sort=False)
-        s, v, m = ref["stats"], ref["vel"][:nf], ref["mass"][:nf]
-        assert s["steps"] == k
-        rows[k - 1] = (k, s["t"], s["dt_last"], s["vmax"], s["tau_bottom"], s["tau_top"],
-                       np.sum(0.5 * m * (v[:, 0] ** 2 + v[:, 1] ** 2)), np.mean(v[:, 0]))
-    return rows
-
-
 @pytest.fixture(scope="module")
 def plain_series(cfgmod, geom, oracle):
     prm, parts = make_case(cfgmod, geom, dp=0.05, DL=3.0)
-    return prm, parts, _oracle_rows(oracle, prm, parts, 36)
+    return prm, parts, oracle_history_rows(oracle, prm, parts, 36)
 
 
 @pytest.fixture(scope="module")
 def left_series(cfgmod, geom, oracle):
     # plain_series mirrored: U_bulk < 0, so g, u_bulk and both tau are negative
     prm, parts = make_case(cfgmod, geom, dp=0.05, DL=3.0, U_bulk=-0.666667)
-    return prm, parts, _oracle_rows(oracle, prm, parts, 36)
+    return prm, parts, oracle_history_rows(oracle, prm, parts, 36)
 
 
 @pytest.fixture(scope="module")
 def variant_series(cfgmod, geom, oracle):
     # moving walls (top and bottom differ in size and sign), uneven mass, rho0 != 1
     prm, parts = make_variant(cfgmod, geom, seed=7, developed=True, dp=0.05, DL=1.5, jitter=0.2, rho0=2.5, transport_coeff=0.1)
-    return prm, parts, _oracle_rows(oracle, prm, parts, 12)
-
-
-def _assert_series_matches_oracle(hist, want, what):
-    n = len(want)
-    assert list(hist["step"]) == list(range(1, n + 1)) and hist["n_dropped"] == 0, what
-    got = {k: hist[k] for k in FIELDS}
-    ref = {k: want[:, j] for j, k in enumerate(FIELDS)}
-    tau_got = np.column_stack([got["tau_bottom"], got["tau_top"]])
-    tau_ref = np.column_stack([ref["tau_bottom"], ref["tau_top"]])
-    tau_scale = np.max(np.abs(tau_ref), axis=1, keepdims=True)
-    print(f"{what}: max rel err t {_rel(got['t'], ref['t']).max():.2e} dt {_rel(got['dt'], ref['dt']).max():.2e} "
-          f"vmax {_rel(got['vmax'], ref['vmax']).max():.2e} tau (of the pair's larger) "
-          f"{(np.abs(tau_got - tau_ref) / tau_scale).max():.2e} kinetic_energy "
-          f"{_rel(got['kinetic_energy'], ref['kinetic_energy']).max():.2e} u_bulk {_rel(got['u_bulk'], ref['u_bulk']).max():.2e}")
-    assert np.all(np.abs(got["t"] - ref["t"]) <= 1e-13 * ref["t"]), what
-    assert np.all(np.abs(got["dt"] - ref["dt"]) <= 1e-12 * ref["dt"]), what
-    assert np.all(np.abs(got["vmax"] - ref["vmax"]) <= 1e-9 * ref["vmax"]), what
-    for k in range(n):  # the pair of one step together, as tests/test_gpu_resident.py compares monitor() with the oracle
-        assert_close(tau_got[k], tau_ref[k], rtol=1e-8, atol_scale=1e-9, name=f"{what}: tau of step {k + 1}")
-    assert np.all(_rel(got["kinetic_energy"], ref["kinetic_energy"]) <= 1e-8), what
-    assert np.all(_rel(got["u_bulk"], ref["u_bulk"]) <= 1e-8), what
+    return prm, parts, oracle_history_rows(oracle, prm, parts, 12)
 
 
 def test_series_matches_the_oracle_step_by_step(capi, plain_series):
@@ -130,36 +77,36 @@ def _series_matches_the_oracle_step_by_step(capi, series, what):
     prm, parts, want = series
     # from one step to the next every field moves by far more than the tolerances: a record taken a step early or late fails
     assert np.all(np.abs(np.diff(want[:, 1:], axis=0)) >= 1e-6 * np.abs(want[1:, 1:]))
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.history_enable(every=1)
         assert ctx.advance(1e9, max_steps=len(want))["step"] == len(want)
         rebins = ctx.schedule()["rebins"]
         hist = ctx.history()
     assert rebins >= 2, f"only {rebins} re-binnings: both Vol / B lookups must be exercised"
-    _assert_series_matches_oracle(hist, want, what)
+    assert_history_matches_oracle(hist, want, what)
     return hist
 
 
 @pytest.mark.parametrize("lpp", [16, 4])
 def test_series_matches_the_oracle_with_moving_walls_and_uneven_mass(capi, variant_series, lpp):
     prm, parts, want = variant_series
-    assert np.all(want[:, 4] * want[:, 5] < 0) and np.all(_rel(want[:, 4], -want[:, 5]) > 0.1)  # tau_bottom != tau_top
-    with _ctx(capi, prm, parts, lanes_per_particle=lpp, rebuild_every=4) as ctx:
+    assert np.all(want[:, 4] * want[:, 5] < 0) and np.all(rel_err(want[:, 4], -want[:, 5]) > 0.1)  # tau_bottom != tau_top
+    with capi.Context.from_parts(prm, parts, t_end=1e9, lanes_per_particle=lpp, rebuild_every=4) as ctx:
         assert ctx.kernel_forms()["walk_kernels"] == (lpp == 4)
         ctx.history_enable(every=1)
         assert ctx.advance(1e9, max_steps=len(want))["step"] == len(want)
         rebins = ctx.schedule()["rebins"]
         hist = ctx.history()
     assert rebins >= 2
-    _assert_series_matches_oracle(hist, want, f"variant lpp {lpp}")
+    assert_history_matches_oracle(hist, want, f"variant lpp {lpp}")
 
 
 # 2 ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(CASES))
 def test_last_record_is_what_the_host_path_reports(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
-    with _ctx(capi, prm, parts, **kw) as ctx:
-        _check_form(ctx, name)
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
+        check_kernel_form(ctx, name)
         ctx.history_enable(every=1)
         st = ctx.advance(1e9, max_steps=45)
         hist = ctx.history()
@@ -167,8 +114,8 @@ def test_last_record_is_what_the_host_path_reports(cfgmod, geom, capi, name):
         ke, ub = _host_sums(parts, ctx.download(fields=("vel",)))
     assert len(hist["step"]) == 45 and hist["n_dropped"] == 0
     assert (hist["step"][-1], hist["t"][-1], hist["dt"][-1], hist["vmax"][-1]) == (st["step"], st["t"], st["dt_last"], st["vmax"])
-    err = dict(tau_bottom=_rel(hist["tau_bottom"][-1], tb), tau_top=_rel(hist["tau_top"][-1], tt),
-               kinetic_energy=_rel(hist["kinetic_energy"][-1], ke), u_bulk=_rel(hist["u_bulk"][-1], ub))
+    err = dict(tau_bottom=rel_err(hist["tau_bottom"][-1], tb), tau_top=rel_err(hist["tau_top"][-1], tt),
+               kinetic_energy=rel_err(hist["kinetic_energy"][-1], ke), u_bulk=rel_err(hist["u_bulk"][-1], ub))
     print(name, {k: f"{float(v):.2e}" for k, v in err.items()})
     for k, v in err.items():
         assert v <= 1e-12, f"{name}: {k} off by {float(v):.3e} (summation order only)"
@@ -180,7 +127,7 @@ def test_chunked_calls_record_the_same_series(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     runs = []
     for chunks in ((45,), (7, 13, 25)):
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
             ctx.history_enable(every=1)
             for n in chunks:
                 ctx.advance(1e9, max_steps=n)
@@ -190,7 +137,7 @@ def test_chunked_calls_record_the_same_series(cfgmod, geom, capi, name):
     for k in CLOCK:
         assert np.array_equal(one[k], chunked[k]), f"{name}: {k}"
     for k in SUMS:
-        err = _rel(chunked[k], one[k]).max()
+        err = rel_err(chunked[k], one[k]).max()
         assert err <= 1e-12, f"{name}: {k} off by {err:.3e}"
 
 
@@ -199,11 +146,11 @@ def test_chunked_calls_record_the_same_series(cfgmod, geom, capi, name):
 def test_gating_every_and_t_from(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     N, every = 40, 3
-    with _ctx(capi, prm, parts, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         statuses = [ctx.advance(1e9, max_steps=1) for _ in range(N)]
     t_from = 0.5 * (statuses[N // 2]["t"] + statuses[N // 2 + 1]["t"])
     want = [s for s in statuses if s["step"] % every == 0 and s["t"] >= t_from]
-    with _ctx(capi, prm, parts, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         ctx.history_enable(every=every, t_from=t_from)
         ctx.advance(1e9, max_steps=N)
         hist = ctx.history()
@@ -214,7 +161,7 @@ def test_gating_every_and_t_from(cfgmod, geom, capi, name):
 
 def test_full_buffer_drops_and_drain_resumes(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.history_enable(every=1, capacity=10)
         ctx.advance(1e9, max_steps=25)
         full = ctx.history()
@@ -238,7 +185,7 @@ def test_no_feedback_on_the_physics(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     outs = []
     for on in (False, True):
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
             if on:
                 ctx.history_enable(every=1)
             st = ctx.advance(1e9, max_steps=45)
@@ -248,25 +195,17 @@ def test_no_feedback_on_the_physics(cfgmod, geom, capi, name):
         assert np.array_equal(outs[0][1][k], outs[1][1][k]), k
 
 
-def _profiled_launches(ctx, n):
-    ctx.profile_enable(True)
-    ctx.advance(1e9, max_steps=n)
-    prof = ctx.profile_read()
-    ctx.profile_enable(False)
-    return {k: v["launches"] for k, v in prof.items() if v["launches"] > 0}  # (names seen earlier stay listed with 0)
-
-
 def test_off_means_no_extra_launch(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
-    with _ctx(capi, prm, parts) as ctx:                   # steps 1-20 and 21-40: the same re-binning phases as below
-        never = _profiled_launches(ctx, 20)
-        never2 = _profiled_launches(ctx, 20)
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:  # steps 1-20 and 21-40: the same re-binning phases as below
+        never = profiled_launches(ctx, 20)
+        never2 = profiled_launches(ctx, 20)
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.history_enable(every=4)                       # one launch per slot whatever the stride: it skips itself
-        on = _profiled_launches(ctx, 20)
+        on = profiled_launches(ctx, 20)
         assert list(ctx.history()["step"]) == [4, 8, 12, 16, 20]
         ctx.history_disable()
-        off = _profiled_launches(ctx, 20)
+        off = profiled_launches(ctx, 20)
     assert "k_step_history" not in never and "k_step_history" not in never2 and "k_step_history" not in off
     assert on.pop("k_step_history") == 20
     assert on == never and off == never2
@@ -274,11 +213,11 @@ def test_off_means_no_extra_launch(cfgmod, geom, capi):
 
 def test_independent_of_the_flow_statistics(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.history_enable(every=2)
         ctx.advance(1e9, max_steps=30)
         alone = ctx.history()
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.flow_stats_enable(every=3)
         ctx.history_enable(every=2)
         ctx.advance(1e9, max_steps=30)
@@ -295,7 +234,7 @@ def test_independent_of_the_flow_statistics(cfgmod, geom, capi):
 # 6 ---------------------------------------------------------------------------------------------------------------
 def test_enable_disable_take_effect_on_existing_graphs(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=64)                    # graphs exist without the history kernel
         ctx.history_enable(every=1)
         ctx.advance(1e9, max_steps=64)
@@ -321,7 +260,7 @@ def test_repeatable(cfgmod, geom, capi, name):
     prm, parts, kw = _case(cfgmod, geom, name)
     runs = []
     for _ in range(2):
-        with _ctx(capi, prm, parts, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
             ctx.history_enable(every=1)
             ctx.advance(1e9, max_steps=60)
             runs.append(ctx.history_records())
@@ -330,19 +269,13 @@ def test_repeatable(cfgmod, geom, capi, name):
 
 
 # 8 ---------------------------------------------------------------------------------------------------------------
-def _err(capi, fn, *args):
-    rc = fn(*args)
-    assert rc != capi.SPHX_OK
-    return capi.lib().sphx_last_error_id().decode(), rc
-
-
 def test_error_identifiers(cfgmod, geom, capi, pkg):
     L = capi.lib()
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
     n, dropped = C.c_int(-1), C.c_int64(-1)
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         h = ctx._h
-        assert _err(capi, L.sphx_ctx_history_read, h, 0, None, C.byref(n), C.byref(dropped), 0) == \
+        assert err_id(capi, L.sphx_ctx_history_read, h, 0, None, C.byref(n), C.byref(dropped), 0) == \
             ("SPHX:History:disabled", capi.SPHX_ERR_STATE)
         assert L.sphx_ctx_history_disable(h) == capi.SPHX_OK       # no-op when off
         for bad in (dict(every=0), dict(every=-1), dict(capacity=0), dict(capacity=-5), dict(capacity=(1 << 22) + 1),
@@ -350,13 +283,13 @@ def test_error_identifiers(cfgmod, geom, capi, pkg):
             c2 = capi.SphxHistoryConfig(every=1, capacity=16, t_from=0.0)
             for k, v in bad.items():
                 setattr(c2, k, v)
-            assert _err(capi, L.sphx_ctx_history_enable, h, C.byref(c2)) == ("SPHX:History:config", capi.SPHX_ERR_ARG), bad
-        assert _err(capi, L.sphx_ctx_history_enable, h, None) == ("SPHX:History:config", capi.SPHX_ERR_ARG)
+            assert err_id(capi, L.sphx_ctx_history_enable, h, C.byref(c2)) == ("SPHX:History:config", capi.SPHX_ERR_ARG), bad
+        assert err_id(capi, L.sphx_ctx_history_enable, h, None) == ("SPHX:History:config", capi.SPHX_ERR_ARG)
         with pytest.raises(capi.SphxError) as e:
             ctx.history_enable(every=0)
         assert e.value.identifier == "SPHX:History:config"
         # a refused config leaves the context without a history, and stepping
-        assert _err(capi, L.sphx_ctx_history_read, h, 0, None, None, None, 0)[0] == "SPHX:History:disabled"
+        assert err_id(capi, L.sphx_ctx_history_read, h, 0, None, None, None, 0)[0] == "SPHX:History:disabled"
         assert ctx.advance(1e9, max_steps=3)["step"] == 3
         cfg = capi.SphxHistoryConfig(every=1, capacity=16, t_from=0.0)
         assert L.sphx_ctx_history_enable(h, C.byref(cfg)) == capi.SPHX_OK
@@ -364,7 +297,7 @@ def test_error_identifiers(cfgmod, geom, capi, pkg):
         assert L.sphx_ctx_history_read(h, 0, None, C.byref(n), C.byref(dropped), 0) == capi.SPHX_OK   # counts only
         assert (n.value, dropped.value) == (5, 0)
         buf = np.full((5, 8), -1.0)
-        assert _err(capi, L.sphx_ctx_history_read, h, 4, capi.ptr(buf), None, None, 1) == \
+        assert err_id(capi, L.sphx_ctx_history_read, h, 4, capi.ptr(buf), None, None, 1) == \
             ("SPHX:History:capacity", capi.SPHX_ERR_ARG)
         assert np.all(buf == -1.0)
         assert L.sphx_ctx_history_read(h, 5, capi.ptr(buf), C.byref(n), None, 0) == capi.SPHX_OK      # ... and nothing was drained
@@ -374,24 +307,18 @@ def test_error_identifiers(cfgmod, geom, capi, pkg):
         cfg = capi.SphxHistoryConfig(every=1, capacity=16, t_from=0.0)
         for fn, args in ((L.sphx_ctx_history_enable, (C.byref(cfg),)), (L.sphx_ctx_history_disable, ()),
                          (L.sphx_ctx_history_read, (0, None, None, None, 0))):
-            assert _err(capi, fn, eng._h, *args) == ("SPHX:History:slab", capi.SPHX_ERR_ARG)
+            assert err_id(capi, fn, eng._h, *args) == ("SPHX:History:slab", capi.SPHX_ERR_ARG)
     finally:
         eng.close()
 
 
 # 9 ---------------------------------------------------------------------------------------------------------------
-def _cfg(prm, t_end):
-    return dict(DL=prm.DL, DH=prm.DH, dp=prm.dp, h=prm.h, rho0=prm.rho0, mu=prm.mu, c_f=prm.c_f, p0=prm.p0,
-                inv_sigma0=prm.inv_sigma0, gravity_g=prm.gravity_g, transport_coeff=prm.transport_coeff,
-                t_end=t_end, sort_interval=prm.sort_interval)
-
-
 def test_matlab_gateway_history_commands(cfgmod, geom, capi):
     prm, parts, kw = _case(cfgmod, geom, "dp05_auto")
     gw = mex_mock.Gateway("sphx_ctx_mex.c")
     nf, nt = parts["n_fluid"], parts["n_total"]
     state = (parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"])
-    (h,) = gw(1, "create", _cfg(prm, 1e9), nf, nt, *state, 0.0, 0)
+    (h,) = gw(1, "create", gateway_cfg(prm, 1e9), nf, nt, *state, 0.0, 0)
     try:
         with pytest.raises(mex_mock.MexError) as e:
             gw(2, "history_read", h, 0)
@@ -403,7 +330,7 @@ def test_matlab_gateway_history_commands(cfgmod, geom, capi):
         gw(0, "history_disable", h)
     finally:
         gw(0, "destroy", h)
-    with _ctx(capi, prm, parts) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.history_enable(every=2, capacity=12)
         ctx.advance(1e9, max_steps=30)
         want, want_dropped = ctx.history_records()
@@ -425,8 +352,8 @@ def test_driver_returns_the_history_of_the_whole_run(cfgmod, driver):
     # the run's last tau is the monitor's of the last step; the history's last record is that step when it is even
     last = driver.run(prm, history_every=1, history_capacity=4096)
     assert last.steps == res.steps and last.history["step"][-1] == last.steps
-    assert _rel(last.history["tau_bottom"][-1], last.tau_bottom) <= 1e-12
-    assert _rel(last.history["tau_top"][-1], last.tau_top) <= 1e-12
+    assert rel_err(last.history["tau_bottom"][-1], last.tau_bottom) <= 1e-12
+    assert rel_err(last.history["tau_top"][-1], last.tau_top) <= 1e-12
     for k in FIELDS:                                                 # every second record of the full series, bit for bit
         assert np.array_equal(last.history[k][1::2], hist[k]), k
     fig = driver.history_figures(prm, last.history, t_from=0.1)

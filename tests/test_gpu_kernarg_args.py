@@ -47,14 +47,9 @@ def _oracle(oracle, prm, parts, n_steps):
     return _REF[n_steps]
 
 
-def _ctx(capi, prm, parts, **kw):
-    return capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                        parts["wall_vel"], t_end=1e9, **kw)
-
-
 def _run(capi, prm, parts, calls, **kw):
     """calls: the step budgets of successive advance() calls -> last status, download, facts about the context"""
-    with _ctx(capi, prm, parts, **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         info = dict(tuning=ctx.tuning(), policy=ctx.grid_policy(), sched=ctx.schedule(), substeps=ctx.substeps())
         for n in calls:
             st = ctx.advance(1e9, max_steps=n)
@@ -139,11 +134,8 @@ def test_dual_rate_packed_flag(cfgmod, geom, capi, capsys):
 
 def test_batch_members_are_standalone_contexts(cfgmod, geom, capi):
     starts = [_start(cfgmod, geom, seed) for seed in (21, 22, 23)]
-    p0 = starts[0][1]
     assert not np.array_equal(starts[0][1]["pos"], starts[1][1]["pos"])
-    with capi.Batch([s[0] for s in starts], p0["n_fluid"], p0["n_total"], [s[1]["pos"] for s in starts],
-                    [s[1]["vel"] for s in starts], [s[1]["drho_dt"] for s in starts], p0["mass"], p0["wall_vel"], t_end=1e9,
-                    lanes_per_particle=16) as b:
+    with capi.Batch.from_parts(*zip(*starts), t_end=1e9, lanes_per_particle=16) as b:
         sts = b.advance(1e9, max_steps=20)
         got = [b.download(m) for m in range(3)]
         assert b.info()["lanes_per_particle"] == 16 and b.info()["realignments"] == 0

@@ -39,9 +39,8 @@ CASES = [("C3", 0.01, 6.0, 10, dict(lpp=4, dynamic=False, big_scan=False, fuse_e
 
 
 def _compare(name, prm, parts, n_steps, capi, oracle, expect, **ctx_kw):
-    nf, nt = parts["n_fluid"], parts["n_total"]
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                      t_end=1e9, **ctx_kw) as ctx:
+    nf = parts["n_fluid"]
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **ctx_kw) as ctx:
         info, tun, pol, sched, forms = ctx.info(), ctx.tuning(), ctx.grid_policy(), ctx.schedule(), ctx.kernel_forms()
         st = ctx.advance(1e9, max_steps=n_steps)
         got = ctx.download()
@@ -106,8 +105,7 @@ def test_c3_lattice_start_matches_oracle(cfgmod, geom, capi, oracle):
     nf, nt = parts["n_fluid"], parts["n_total"]
     assert (nf, nt) == (60000, 64800)
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=3, enable_sort=False)
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                      t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         st = ctx.advance(1e9, max_steps=3)
         got = ctx.download()
         _, _, npairs = ctx.monitor(tau=False, pairs=True)

@@ -60,9 +60,7 @@ def _counts_within(prm, parts, radius):
 
 
 def _run(capi, prm, parts, n_steps=N_STEPS, **kw):
-    nf, nt = parts["n_fluid"], parts["n_total"]
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"], t_end=1e9,
-                      **kw) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
         info = dict(tuning=ctx.tuning(), policy=ctx.grid_policy(), sched=ctx.schedule(), substeps=ctx.substeps())
         st = ctx.advance(1e9, max_steps=n_steps)
         got = ctx.download()

@@ -14,8 +14,8 @@ import numpy as np
 import pytest
 
 import regime_cases as rc
-from helpers import assert_close
-from test_gpu_resident import _ctx, _steps_match_oracle
+from helpers import assert_close, full_state
+from test_gpu_resident import _steps_match_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -44,7 +44,7 @@ def test_every_kernel_family_in_every_regime(name, lanes, n_steps, cfgmod, geom,
     _steps_match_oracle((prm, parts, lanes), capi, oracle, n_steps)
     # once more for what that comparison does not look at: the schedule, the first dt, the errors as figures
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_steps, enable_sort=False)
-    with _ctx(capi, prm, parts, lanes, t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lanes, t_end=1e9) as ctx:
         forms, before = ctx.kernel_forms(), ctx.schedule()
         first = ctx.advance(1e9, max_steps=1)
         st = ctx.advance(1e9, max_steps=n_steps - 1)
@@ -89,7 +89,7 @@ def test_density_floor_on_the_device(lanes, n_steps, cfgmod, geom, capi, oracle)
     _steps_match_oracle((prm, parts, lanes), capi, oracle, n_steps)
     if n_steps == 1:
         ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=1, enable_sort=False)
-        with _ctx(capi, prm, parts, lanes, t_end=1e9) as ctx:
+        with capi.Context.from_parts(prm, parts, lanes_per_particle=lanes, t_end=1e9) as ctx:
             st = ctx.advance(1e9, max_steps=1)
             got = ctx.download(fields=("rho", "p", "drho_dt"))
         rows = list(rc.FLOOR_ROWS)
@@ -110,7 +110,7 @@ def test_call_patterns_agree_to_the_bit(name, lanes, cfgmod, geom, capi):
     n = 13
     outs = []
     for kw, single in ((dict(), False), (dict(steps_per_graph=4), False), (dict(steps_per_graph=4), True)):
-        with _ctx(capi, prm, parts, lanes, t_end=1e9, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, lanes_per_particle=lanes, t_end=1e9, **kw) as ctx:
             if single:
                 for _ in range(n):
                     st = ctx.advance(1e9, max_steps=1)
@@ -136,7 +136,7 @@ def test_target_time_clipping(name, lanes, cfgmod, geom, capi, oracle):
     n_ref = ref["stats"]["steps"]
     before = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_ref - 1, enable_sort=False)["stats"]["dt_last"]
     assert n_ref >= 8 and ref["stats"]["dt_last"] < 0.9 * before                      # the last step was clipped
-    with _ctx(capi, prm, parts, lanes, t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lanes, t_end=1e9) as ctx:
         st = ctx.advance(target)
         assert st["done"] == 1 and abs(st["t"] - target) < 1e-12
         assert st["step"] == ref["stats"]["steps"]
@@ -163,16 +163,6 @@ def regime_members(cfgmod, geom, size="small"):
     return members
 
 
-def _batch(capi, members, **kw):
-    p0 = members[0][1]
-    return capi.Batch([m[0] for m in members], p0["n_fluid"], p0["n_total"], [m[1]["pos"] for m in members],
-                      [m[1]["vel"] for m in members], [m[1]["drho_dt"] for m in members], p0["mass"], p0["wall_vel"], **kw)
-
-
-def _everything(dl, st, mon):
-    return dict(dl, t=st["t"], dt_last=st["dt_last"], step=st["step"], vmax=st["vmax"], tau=np.array(mon[:2]), pairs=mon[2])
-
-
 @pytest.mark.parametrize("lanes", [16, 32])
 def test_batch_of_four_regimes_is_bit_identical_to_standalone(lanes, cfgmod, geom, capi):
     """enqueue_steps(20) on the batch and on four standalone contexts.  A member that never fell out of step is bit for bit its
@@ -184,19 +174,18 @@ def test_batch_of_four_regimes_is_bit_identical_to_standalone(lanes, cfgmod, geo
     members = regime_members(cfgmod, geom)
     kw = dict(t_end=1e9, lanes_per_particle=lanes, rebuild_every=4, skin_h=1.6)
     n = 20
-    with _batch(capi, members, **kw) as b:
+    with capi.Batch.from_parts(*zip(*members), **kw) as b:
         assert b.info()["lanes_per_particle"] == lanes and b.info()["rebuild_every"] == 4
         b.enqueue_steps(n)
         sts = b.sync()
-        got = [_everything(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
+        got = [full_state(b.download(m), sts[m], b.monitor(m, tau=True, pairs=True)) for m in range(len(members))]
         info = b.info()
     assert info["realignments"] == 0 and info["forced_rebuilds"] == 0, info
     for m, (prm, parts) in enumerate(members):
-        with capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                          parts["wall_vel"], **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, **kw) as ctx:
             ctx.enqueue_steps(n)
             st = ctx.sync()
-            ref = _everything(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
+            ref = full_state(ctx.download(), st, ctx.monitor(tau=True, pairs=True))
             assert ctx.grid_policy()["forced_rebuilds"] == 0
         assert got[m]["step"] == n
         for k in ref:
@@ -212,7 +201,7 @@ def test_batch_of_four_regimes_reaches_one_time_in_different_step_counts(lanes, 
     members = regime_members(cfgmod, geom)
     dt0 = 0.25 * members[0][0].h / (15.0 + 1.5)
     t1 = 10.3 * dt0
-    with _batch(capi, members, t_end=1e9, lanes_per_particle=lanes) as b:
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9, lanes_per_particle=lanes) as b:
         sts = b.advance(t1)
         got = [b.download(m) for m in range(len(members))]
         taus = [b.monitor(m, tau=True, pairs=True) for m in range(len(members))]

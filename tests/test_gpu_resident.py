@@ -22,11 +22,6 @@ def case(request, cfgmod, geom):
     return prm, parts, lpp
 
 
-def _ctx(capi, prm, parts, lpp, **kw):
-    return capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"],
-                        parts["mass"], parts["wall_vel"], lanes_per_particle=lpp, **kw)
-
-
 # moving walls + uneven mass (helpers.make_variant) with rho0 != 1, and the same on a channel of height DH = 0.8
 VARIANTS = {"rho25": dict(dp=0.05, DL=1.5, jitter=0.2, rho0=2.5, transport_coeff=0.1),
             "DH08": dict(dp=0.04, DL=1.3, DH=0.8, jitter=0.25, rho0=0.37)}
@@ -54,7 +49,7 @@ def _steps_match_oracle(case, capi, oracle, n_steps):
     prm, parts, lpp = case
     nf = parts["n_fluid"]
     ref = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=n_steps, enable_sort=False)
-    with _ctx(capi, prm, parts, lpp, t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lpp, t_end=1e9) as ctx:
         st = ctx.advance(1e9, max_steps=n_steps)
         got = ctx.download()
         tb, tt, npairs = ctx.monitor(tau=True, pairs=True)
@@ -98,7 +93,7 @@ def test_bitwise_repeatable_and_lpp_consistent(case, capi):
     prm, parts, lpp = case
     outs = []
     for l in (lpp, lpp, 8 if lpp != 8 else 2):
-        with _ctx(capi, prm, parts, l, t_end=1e9) as ctx:
+        with capi.Context.from_parts(prm, parts, lanes_per_particle=l, t_end=1e9) as ctx:
             ctx.advance(1e9, max_steps=6)
             outs.append(ctx.download(fields=("pos", "vel", "drho_dt")))
     for k in ("pos", "vel", "drho_dt"):
@@ -109,10 +104,10 @@ def test_bitwise_repeatable_and_lpp_consistent(case, capi):
 def test_graph_and_eager_agree(case, capi):
     """hipGraph replay (steps_per_graph=4) and per-step advance calls give identical bits."""
     prm, parts, lpp = case
-    with _ctx(capi, prm, parts, lpp, t_end=1e9, steps_per_graph=4) as a:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lpp, t_end=1e9, steps_per_graph=4) as a:
         a.advance(1e9, max_steps=13)
         A = a.download(fields=("pos", "vel", "drho_dt"))
-    with _ctx(capi, prm, parts, lpp, t_end=1e9, steps_per_graph=4) as b:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lpp, t_end=1e9, steps_per_graph=4) as b:
         for _ in range(13):
             st = b.advance(1e9, max_steps=1)
         assert st["step"] == 13
@@ -127,7 +122,7 @@ def test_target_time_clipping(case, capi, oracle):
     dt0 = 0.25 * prm.h / (prm.c_f + 1.5)
     target = 7.3 * dt0
     ref = oracle.run(prm, parts, t_end=target, output_interval=target, enable_sort=False)
-    with _ctx(capi, prm, parts, lpp, t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lpp, t_end=1e9) as ctx:
         st = ctx.advance(target)
         assert st["done"] == 1 and abs(st["t"] - target) < 1e-12
         assert st["step"] == ref["stats"]["steps"]
@@ -139,7 +134,7 @@ def test_target_time_clipping(case, capi, oracle):
 
 def test_ctx_neighbor_list_matches_oracle(case, capi, oracle):
     prm, parts, lpp = case
-    with _ctx(capi, prm, parts, lpp, t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lpp, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=2)
         nb = ctx.neighbor_list()
         pos = ctx.download(fields=("pos",))["pos"]
@@ -152,7 +147,7 @@ def test_ctx_neighbor_list_matches_oracle(case, capi, oracle):
 def test_time_kernel_leaves_state_untouched(case, capi):
     """sphx_ctx_time_kernel replays one neighbour pass in a graph; it may only touch per-step temporaries."""
     prm, parts, lpp = case
-    with _ctx(capi, prm, parts, lpp, t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lpp, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=3)
         before = ctx.download(fields=("pos", "vel", "drho_dt"))
         for name in ("k_density", "k_kgc", "k_forces", "k_continuity"):
@@ -166,10 +161,10 @@ def test_time_kernel_leaves_state_untouched(case, capi):
         assert st["step"] == 5
     for k in before:
         assert np.array_equal(before[k], after[k]), k
-    with _ctx(capi, prm, parts, lpp, t_end=1e9) as ref:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lpp, t_end=1e9) as ref:
         ref.advance(1e9, max_steps=5)
         want = ref.download(fields=("pos", "vel", "drho_dt"))
-    with _ctx(capi, prm, parts, lpp, t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, lanes_per_particle=lpp, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=3)
         ctx.time_kernel("k_forces", reps=4)
         ctx.advance(1e9, max_steps=2)

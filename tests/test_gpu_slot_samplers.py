@@ -28,13 +28,6 @@ def case(request, cfgmod, geom):
     return request.param, prm, parts, kw
 
 
-def _ctx(capi, case):
-    _, prm, parts, kw = case
-    nf, nt = parts["n_fluid"], parts["n_total"]
-    return capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                        t_end=1e9, **kw)
-
-
 def _enable(ctx, case, which):
     DL = case[1].DL
     if "stats" in which:
@@ -76,7 +69,7 @@ def test_each_sampler_alone_and_all_three_together_give_the_same_bits(capi, case
     all3 = ("stats", "history", "field")
     runs, tails = {}, {}
     for which in (("stats",), ("history",), ("field",), all3):
-        with _ctx(capi, case) as ctx:
+        with capi.Context.from_parts(case[1], case[2], t_end=1e9, **case[3]) as ctx:
             _enable(ctx, case, which)
             st = ctx.advance(1e9, max_steps=40)
             assert st["step"] == 40
@@ -107,7 +100,7 @@ def test_each_sampler_alone_and_all_three_together_give_the_same_bits(capi, case
 # (b) ---------------------------------------------------------------------------------------------------------------
 def test_enabling_and_disabling_one_sampler_leaves_the_others_alone(capi, case):
     name = case[0]
-    with _ctx(capi, case) as ctx:
+    with capi.Context.from_parts(case[1], case[2], t_end=1e9, **case[3]) as ctx:
         _enable(ctx, case, ("stats", "history"))
         ctx.advance(1e9, max_steps=10)
         _enable(ctx, case, ("field",))
@@ -120,19 +113,19 @@ def test_enabling_and_disabling_one_sampler_leaves_the_others_alone(capi, case):
             ctx.history_records()
         assert e.value.identifier == "SPHX:History:disabled"
     # the same 30 steps, in the same three calls, with one sampler each
-    with _ctx(capi, case) as ctx:
+    with capi.Context.from_parts(case[1], case[2], t_end=1e9, **case[3]) as ctx:
         _enable(ctx, case, ("stats",))
         for _ in range(3):
             ctx.advance(1e9, max_steps=10)
         _assert_same_bits(stats, _outputs(ctx, ("stats",)), f"{name}: statistics of 30 steps")
     assert stats["stats0/n_samples"] == 30
-    with _ctx(capi, case) as ctx:
+    with capi.Context.from_parts(case[1], case[2], t_end=1e9, **case[3]) as ctx:
         _enable(ctx, case, ("history",))
         for _ in range(2):
             ctx.advance(1e9, max_steps=10)
         _assert_same_bits(history, _outputs(ctx, ("history",)), f"{name}: history of steps 1..20")
     assert list(history["history/records"][:, 0]) == list(range(1, 21)) and history["history/n_dropped"] == 0
-    with _ctx(capi, case) as ctx:
+    with capi.Context.from_parts(case[1], case[2], t_end=1e9, **case[3]) as ctx:
         t10 = ctx.advance(1e9, max_steps=10)["t"]
         _enable(ctx, case, ("field",))
         for _ in range(2):
@@ -152,7 +145,7 @@ def test_a_refused_enable_leaves_a_running_sampler_as_it_was(capi, case):
         ("SPHX:History:config", L.sphx_ctx_history_enable, capi.SphxHistoryConfig(every=1, capacity=0, t_from=0.0)),
         ("SPHX:Field:config", L.sphx_ctx_field_map_enable, capi.SphxFieldMapConfig(nx=1, ny=0, every=1, with_walls=0, t_from=0.0)),
     )
-    with _ctx(capi, case) as ctx:
+    with capi.Context.from_parts(case[1], case[2], t_end=1e9, **case[3]) as ctx:
         _enable(ctx, case, all3)
         ctx.advance(1e9, max_steps=10)
         before = _outputs(ctx, all3)
@@ -166,7 +159,7 @@ def test_a_refused_enable_leaves_a_running_sampler_as_it_was(capi, case):
     assert after["stats0/n_samples"] == 15 and after["field/n_samples"] == 15
     assert list(after["history/records"][:, 0]) == list(range(1, 16))
     # ... and they are the samples of an undisturbed run of the same calls
-    with _ctx(capi, case) as ctx:
+    with capi.Context.from_parts(case[1], case[2], t_end=1e9, **case[3]) as ctx:
         _enable(ctx, case, all3)
         ctx.advance(1e9, max_steps=10)
         ctx.advance(1e9, max_steps=5)

@@ -147,8 +147,7 @@ def test_no_device_means_loud_failure_not_cpu_fallback(capi, mex, cfgmod, geom):
         mex.sph_neighbor_search_mex(parts["pos"], parts["n_fluid"], parts["n_total"], prm.h, prm.DL)
     assert e.value.identifier == "SPHX:NoDevice"
     with pytest.raises(capi.SphxError) as e2:
-        capi.Context(prm, parts["n_fluid"], parts["n_total"], parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"],
-                     parts["wall_vel"])
+        capi.Context.from_parts(prm, parts)
     assert e2.value.code == capi.SPHX_ERR_DEVICE
 
 

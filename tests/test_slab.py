@@ -139,7 +139,7 @@ def test_slab_native_ring_in_one_process(world, dp, DL, steps, kw):
         assert prm.gravity_g < 0 and np.all(parts["vel"][:parts["n_fluid"], 0] < 0)
     else:
         prm, parts = make_case(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9)
-    nf, nt = parts["n_fluid"], parts["n_total"]
+    nf = parts["n_fluid"]
     calls = kw.pop("calls", [steps])  # the run in several calls: the ids of a re-binning in a call's last step travel with the next call
     graph_after = kw.pop("graph_after", None)
     overlap = kw.pop("overlap", None)  # which form of the skinned step (read by the library when a slab's buffers are made)
@@ -170,8 +170,7 @@ def test_slab_native_ring_in_one_process(world, dp, DL, steps, kw):
         pos[i, 0], pos[i, 1], vel[i, 0], vel[i, 1], drho[i] = sn["x"][o], sn["y"][o], sn["vx"][o], sn["vy"][o], sn["drho"][o]
         np.add.at(seen, i, 1)
     assert np.all(seen == 1), (int((seen == 0).sum()), int((seen > 1).sum()))
-    with pkg.capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                          t_end=1e9) as ctx:
+    with pkg.capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         rs = ctx.advance(1e9, max_steps=steps)
         ref = ctx.download(fields=("pos", "vel", "drho_dt"))
     for st in sts:

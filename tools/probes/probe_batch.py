@@ -63,12 +63,10 @@ def main():
         prm = config.params_from_values(**CASES[name])
         for M in [int(x) for x in a.members.split(",")]:
             states = [member_state(prm, 1000 + m) for m in range(M)]
-            nf, nt = states[0]["n_fluid"], states[0]["n_total"]
+            nt = states[0]["n_total"]
             single, batch = [], []
-            with capi.Context(prm, nf, nt, states[0]["pos"], states[0]["vel"], states[0]["drho_dt"], states[0]["mass"],
-                              states[0]["wall_vel"], t_end=1e9) as ctx, \
-                    capi.Batch([prm] * M, nf, nt, [s["pos"] for s in states], [s["vel"] for s in states],
-                               [s["drho_dt"] for s in states], states[0]["mass"], states[0]["wall_vel"], t_end=1e9) as b:
+            with capi.Context.from_parts(prm, states[0], t_end=1e9) as ctx, \
+                    capi.Batch.from_parts([prm] * M, states, t_end=1e9) as b:
                 for _ in range(2):  # alternate, so that drifts of the clock or of the box hit both
                     rounds(ctx, a.steps, (a.reps + 1) // 2, single, call)
                     rounds(b, a.steps, (a.reps + 1) // 2, batch, call)

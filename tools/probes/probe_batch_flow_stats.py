@@ -78,15 +78,14 @@ def main():
     band = (0.5 * prm.DL, max(prm.dp, prm.h))
     if not a.no_single:
         s = member_state(prm, 1000)
-        nf, nt = s["n_fluid"], s["n_total"]
-        with capi.Context(prm, nf, nt, s["pos"], s["vel"], s["drho_dt"], s["mass"], s["wall_vel"], t_end=1e9) as ctx:
+        nt = s["n_total"]
+        with capi.Context.from_parts(prm, s, t_end=1e9) as ctx:
             us = run_modes(ctx, modes, a.steps, a.reps, n_bins, band)
         print(json.dumps(summary(0, nt, a.steps, us, dict(standalone=True))), flush=True)
     for M in [int(x) for x in a.members.split(",")]:
         states = [member_state(prm, 1000 + m) for m in range(M)]
-        nf, nt = states[0]["n_fluid"], states[0]["n_total"]
-        with capi.Batch([prm] * M, nf, nt, [s["pos"] for s in states], [s["vel"] for s in states],
-                        [s["drho_dt"] for s in states], states[0]["mass"], states[0]["wall_vel"], t_end=1e9) as b:
+        nt = states[0]["n_total"]
+        with capi.Batch.from_parts([prm] * M, states, t_end=1e9) as b:
             us = run_modes(b, modes, a.steps, a.reps, n_bins, band)
             info, gs = b.info(), b.graph_stats()
         print(json.dumps(summary(M, nt, a.steps, us, dict(lanes=info["lanes_per_particle"], realignments=info["realignments"],

@@ -98,8 +98,8 @@ def main():
         prm = config.params_from_values(dp=dp, DL=3.0)
         if not a.no_single:
             s = member_state(prm, 1000)
-            nf, nt = s["n_fluid"], s["n_total"]
-            with capi.Context(prm, nf, nt, s["pos"], s["vel"], s["drho_dt"], s["mass"], s["wall_vel"], t_end=1e9) as ctx:
+            nt = s["n_total"]
+            with capi.Context.from_parts(prm, s, t_end=1e9) as ctx:
                 us = run_modes(ctx, modes, a.steps, a.reps, capacity)
                 extra = dict(standalone=True)
                 if not a.off_only:
@@ -115,9 +115,8 @@ def main():
             print(json.dumps(summary(dp, 0, nt, a.steps, us, extra)), flush=True)
         for M in [int(x) for x in a.members.split(",")]:
             states = [member_state(prm, 1000 + m) for m in range(M)]
-            nf, nt = states[0]["n_fluid"], states[0]["n_total"]
-            with capi.Batch([prm] * M, nf, nt, [s["pos"] for s in states], [s["vel"] for s in states],
-                            [s["drho_dt"] for s in states], states[0]["mass"], states[0]["wall_vel"], t_end=1e9) as b:
+            nt = states[0]["n_total"]
+            with capi.Batch.from_parts([prm] * M, states, t_end=1e9) as b:
                 us = run_modes(b, modes, a.steps, a.reps, capacity)
                 extra = {}
                 if not a.off_only:

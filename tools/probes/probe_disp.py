@@ -11,7 +11,7 @@ for wl in ("C2", "C3"):
         prm = cfg.params_from_values(end_time=1e9, **kw)
         parts = geo.init_particles(prm)
         pos, vel = (parts["pos"], parts["vel"]) if start == "lattice" else geo.developed_state(prm, parts, jitter=0.05, seed=12345)
-        ctx = capi.Context(prm, parts["n_fluid"], parts["n_total"], pos, vel, parts["drho_dt"], parts["mass"], parts["wall_vel"], t_end=1e9, rebuild_every=64, skin_h=1.0)
+        ctx = capi.Context.from_parts(prm, parts, pos=pos, vel=vel, t_end=1e9, rebuild_every=64, skin_h=1.0)
         out, prev = [], 0.0
         worst = 0.0
         for k in range(3000):

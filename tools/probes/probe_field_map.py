@@ -61,8 +61,7 @@ def probe(name, steps, rounds, warm, modes, trace_steps, host_nodes):
     nx, ny = capi.field_map_shape(prm)
     out = dict(workload=name, n_fluid=nf, n_total=nt, nx=nx, ny=ny, steps=steps, rounds=rounds, lib=capi.LIB_PATH,
                us={m: [] for m in modes})
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                      t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=warm)
         if trace_steps:
             ctx.field_map_enable(every=1)

@@ -48,8 +48,7 @@ def probe(name, steps, reps, warm):
     n_bins = profile.n_profile_bins(prm.DH, prm.dp)
     band = (0.5 * prm.DL, max(prm.dp, prm.h))
     out = dict(workload=name, n_fluid=nf, n_total=nt, n_bins=n_bins, steps=steps, reps=reps, us_off=[], us_on=[])
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                      t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=warm)
         for _ in range(reps):
             ctx.flow_stats_disable()

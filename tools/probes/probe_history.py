@@ -62,8 +62,7 @@ def probe(name, steps, reps, warm, off_only):
     capacity = min(1 << 22, reps * steps + 64)
     us = dict(off=[], every1=[], every16=[], host_driven=[])
     out = dict(workload=name, library=capi.LIB_PATH, n_fluid=nf, n_total=nt, steps=steps, reps=reps)
-    with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                      t_end=1e9) as ctx:
+    with capi.Context.from_parts(prm, parts, t_end=1e9) as ctx:
         ctx.advance(1e9, max_steps=warm)
         for _ in range(reps):
             if not off_only:

@@ -10,7 +10,7 @@ steps = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 prm = cfg.params_from_values(end_time=1e9, **W[name])
 parts = geo.init_particles(prm)
 pos, vel = geo.developed_state(prm, parts, jitter=0.05, seed=12345)
-ctx = capi.Context(prm, parts["n_fluid"], parts["n_total"], pos, vel, parts["drho_dt"], parts["mass"], parts["wall_vel"], t_end=1e9)
+ctx = capi.Context.from_parts(prm, parts, pos=pos, vel=vel, t_end=1e9)
 dt = 1.0
 if steps > 0:  # steps = 0: kernel timings on the initial state only (experiment builds with broken physics)
     ctx.enqueue_steps(40); ctx.sync()

@@ -7,8 +7,8 @@ dp, DL, t_end, nwin = (float(sys.argv[1]), float(sys.argv[2]), float(sys.argv[3]
 dyn = int(sys.argv[5]) if len(sys.argv) > 5 else 0
 prm = pkg.config.params_from_values(dp=dp, DL=DL, end_time=t_end, output_interval=t_end)
 parts = pkg.geometry.init_particles(prm)
-nf, nt = parts["n_fluid"], parts["n_total"]
-with pkg.capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"], dynamic_rebin=dyn) as ctx:
+nf = parts["n_fluid"]
+with pkg.capi.Context.from_parts(prm, parts, dynamic_rebin=dyn) as ctx:
     step0, forced0 = 0, 0
     t_all = time.perf_counter()
     for w in range(nwin):

@@ -34,9 +34,7 @@ def dump(path):
     out = {}
     for name, (dp, DL, kw) in CASES.items():
         prm, parts = make_case(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True)
-        nf, nt = parts["n_fluid"], parts["n_total"]
-        with capi.Context(prm, nf, nt, parts["pos"], parts["vel"], parts["drho_dt"], parts["mass"], parts["wall_vel"],
-                          t_end=1e9, **kw) as ctx:
+        with capi.Context.from_parts(prm, parts, t_end=1e9, **kw) as ctx:
             ctx.flow_stats_enable(bands=((0.5 * DL, 0.1 * DL),))
             ctx.history_enable(capacity=64)
             ctx.field_map_enable()

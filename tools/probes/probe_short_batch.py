@@ -8,7 +8,7 @@ cfg, geo, capi = pkg.config, pkg.geometry, pkg.capi
 prm = cfg.params_from_values(dp=0.025, DL=3.0, end_time=1e9)
 parts = geo.init_particles(prm)
 pos, vel = geo.developed_state(prm, parts, jitter=0.05, seed=12345)
-ctx = capi.Context(prm, parts["n_fluid"], parts["n_total"], pos, vel, parts["drho_dt"], parts["mass"], parts["wall_vel"], t_end=1e9)
+ctx = capi.Context.from_parts(prm, parts, pos=pos, vel=vel, t_end=1e9)
 ctx.enqueue_steps(5); ctx.sync()
 
 for n in (20, 40, 80, 160, 640):

@@ -32,7 +32,7 @@ if graph:
 t0 = time.perf_counter(); slab.HipSlabEngine.group_run(engines, steps); [e.sync() for e in engines]; ring = (time.perf_counter() - t0) / steps
 lay = engines[0].layout()
 for e in engines: e.close()
-ctx = capi.Context(prm, parts["n_fluid"], parts["n_total"], pos, vel, parts["drho_dt"], parts["mass"], parts["wall_vel"], t_end=1e9)
+ctx = capi.Context.from_parts(prm, parts, pos=pos, vel=vel, t_end=1e9)
 ctx.enqueue_steps(40); ctx.sync()
 t0 = time.perf_counter(); ctx.enqueue_steps(steps); ctx.sync(); one = (time.perf_counter() - t0) / steps
 print(f"{name}: ring of {world} slabs on one device{' (ONE stream)' if one_stream else ''}{' (step graph)' if graph else ''}{f' K={K}' if K else ''} {1e6*ring:.1f} us/step, single context "

@@ -15,9 +15,8 @@ pkg = importlib.import_module(bench.PKG)
 name, kw = bench.parse_workload(%r)
 prm = pkg.config.params_from_values(end_time=1e9, **kw)
 parts = pkg.geometry.init_particles(prm)
-nf, nt = parts["n_fluid"], parts["n_total"]
 pos, vel = pkg.geometry.developed_state(prm, parts, jitter=0.05, seed=12345)
-with pkg.capi.Context(prm, nf, nt, pos, vel, parts["drho_dt"], parts["mass"], parts["wall_vel"], t_end=1e9) as ctx:
+with pkg.capi.Context.from_parts(prm, parts, pos=pos, vel=vel, t_end=1e9) as ctx:
     if %d > 0:  # (a measurement variant whose kernels compute wrong results is timed on the start state)
         ctx.advance(1e9, max_steps=%d)
         ctx.sync()
