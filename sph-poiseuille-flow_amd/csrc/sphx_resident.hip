@@ -2223,15 +2223,6 @@ void slab_setup(sphx_ctx *c, const sphx_params *prm, int n_fluid, int n_total, c
 
 }  // namespace
 
-namespace {
-
-// run one half of a slab step (whole steps are replayed as graphs by sphx_slab_graph_prepare; graphs of half a step --
-// the exchange sits between the halves -- cost more host time than the ten plain launches they held)
-template <typename Body>
-void slab_half(sphx_ctx *, int, int, const void *const[3], Body &&body) { body(); }
-
-}  // namespace
-
 SPHX_EXPORT int sphx_slab_create(sphx_ctx **out, const sphx_params *prm, int n_fluid, int n_total, const double *pos,
                                  const double *vel, const double *drho_dt, const double *mass, const double *wall_vel,
                                  double t0, int64_t step0, int rank, int n_ranks, int halo_cols, void *hip_stream)
@@ -2298,17 +2289,13 @@ void slab_compute_impl(sphx_ctx *c, double *send_left_dev, double *send_right_de
 {
     const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
-    auto body = [&]() {
-        launch_passes(c, q, c->view(q, q), c->tmp, PassA::Sweep);
-        SlabPack p = c->pack;
-        p.send_l = send_left_dev;
-        p.send_r = send_right_dev;
-        launch(c, "k_slab_pack", k_slab_pack, dim3(c->n_blocks_flat), dim3(kBlock), clk, q, c->grid, c->view(q, q), c->tmp, p);
-        launch(c, "k_slab_seal_vmax", k_slab_seal_vmax, dim3(1), dim3(kScanBlock), clk, q, p, c->n_vpart,
-               (const double *)c->vpart.get(), vmax_local_dev);
-    };
-    const void *key[3] = {send_left_dev, send_right_dev, vmax_local_dev};
-    slab_half(c, 0, q, key, body);
+    launch_passes(c, q, c->view(q, q), c->tmp, PassA::Sweep);
+    SlabPack p = c->pack;
+    p.send_l = send_left_dev;
+    p.send_r = send_right_dev;
+    launch(c, "k_slab_pack", k_slab_pack, dim3(c->n_blocks_flat), dim3(kBlock), clk, q, c->grid, c->view(q, q), c->tmp, p);
+    launch(c, "k_slab_seal_vmax", k_slab_seal_vmax, dim3(1), dim3(kScanBlock), clk, q, p, c->n_vpart,
+           (const double *)c->vpart.get(), vmax_local_dev);
     SPHX_HIP(hipGetLastError());
 }
 
@@ -2318,27 +2305,23 @@ void slab_finish_impl(sphx_ctx *c, const double *recv_left_dev, const double *re
     const int q = c->sched.cur;
     Clock *clk = c->clock.get();
     const dim3 bp(kBlock);
-    auto body = [&]() {
-        // kept particles were binned by the pack kernel, the received ones are binned here
-        launch(c, "k_slab_unpack", k_slab_unpack, dim3(div_up((size_t)2 * c->msg_cap, kBlock)), bp, (const Clock *)clk, q,
-               c->grid, c->pack, recv_left_dev, recv_right_dev, c->n_new.get(), c->flags.get());
-        // clock: t += dt, new particle count, next dt from the global max |v| -- and the scan of the cell histogram
-        // and the reset of the pack counters.  It arms run[1-q]; the remaining kernels of this slot still test
-        // run[q], and from here on clk->n is the new particle count.
-        const FluidSet d = c->view(1 - q, 1 - q);
-        ClockScan clock;
-        clock.vmax_global = vmax_global_dev;
-        clock.count = c->count.get();
-        clock.start_next = d.start;
-        clock.n_new = c->n_new.get();
-        clock.rebuilt = 1;
-        clock.slab_counters = c->counters.get();
-        launch_clock_scan(c, q, clock);
-        launch_scatter_reorder(c, q,
-                               reorder_args(c->kpos.get(), c->kvel.get(), c->kdrho.get(), c->kmass.get(), c->kid.get(), d, nullptr), d);
-    };
-    const void *key[3] = {recv_left_dev, recv_right_dev, vmax_global_dev};
-    slab_half(c, 1, q, key, body);
+    // kept particles were binned by the pack kernel, the received ones are binned here
+    launch(c, "k_slab_unpack", k_slab_unpack, dim3(div_up((size_t)2 * c->msg_cap, kBlock)), bp, (const Clock *)clk, q,
+           c->grid, c->pack, recv_left_dev, recv_right_dev, c->n_new.get(), c->flags.get());
+    // clock: t += dt, new particle count, next dt from the global max |v| -- and the scan of the cell histogram
+    // and the reset of the pack counters.  It arms run[1-q]; the remaining kernels of this slot still test
+    // run[q], and from here on clk->n is the new particle count.
+    const FluidSet d = c->view(1 - q, 1 - q);
+    ClockScan clock;
+    clock.vmax_global = vmax_global_dev;
+    clock.count = c->count.get();
+    clock.start_next = d.start;
+    clock.n_new = c->n_new.get();
+    clock.rebuilt = 1;
+    clock.slab_counters = c->counters.get();
+    launch_clock_scan(c, q, clock);
+    launch_scatter_reorder(c, q,
+                           reorder_args(c->kpos.get(), c->kvel.get(), c->kdrho.get(), c->kmass.get(), c->kid.get(), d, nullptr), d);
     SPHX_HIP(hipGetLastError());
     c->sched.cur ^= 1;
     c->slab_steps_enqueued += 1;
@@ -2376,6 +2359,7 @@ SPHX_EXPORT int sphx_slab_finish(sphx_ctx *c, const double *recv_left_dev, const
 //                        neighbours: direct xGMI hops) and one 8-byte all-reduce;
 //   sphx_slab_group_run  all slabs of the ring live in one process on one device (tests, rehearsals on a one-GPU box):
 //                        the same loop with device-to-device copies as the transport and events for the ordering.
+// Both are slab_run / slab_step over a transport (RcclRing, InProcessRing): every step form is stated once.
 // librccl is loaded when the first communicator is made (dlopen: PyTorch carries its own copy of the library and the two
 // must not be linked into one image twice), so a box without RCCL can still run everything single-GPU.
 // =================================================================================================
@@ -2432,6 +2416,44 @@ struct Rccl {
     void check(ncclResult_t e, const char *what)
     {
         if (e != ncclSuccess) throw Error(SPHX_ERR_DEVICE, "SPHX:Slab:rccl", std::string(what) + ": " + GetErrorString(e));
+    }
+};
+
+// The RCCL calls of the native loop as functions of (communicator, ring neighbours; stream, buffers, counts): RcclRing issues
+// them for a rank of a real ring, the self-tests on a communicator of one rank that is its own neighbour (left = right = 0).
+struct Wire {
+    Rccl &R;
+    ncclComm_t comm;
+    int left, right;
+    // My left message is my left neighbour's "from the right" message and vice versa; with two ranks both go to the same
+    // peer, which posts its receives in the order the sends are posted here.
+    void ring(hipStream_t st, const void *to_l, const void *to_r, void *from_l, void *from_r, size_t count, ncclDataType_t ty)
+    {
+        R.check(R.GroupStart(), "ncclGroupStart");
+        R.check(R.Send(to_l, count, ty, left, comm, st), "ncclSend");
+        R.check(R.Send(to_r, count, ty, right, comm, st), "ncclSend");
+        R.check(R.Recv(from_r, count, ty, right, comm, st), "ncclRecv");
+        R.check(R.Recv(from_l, count, ty, left, comm, st), "ncclRecv");
+        R.check(R.GroupEnd(), "ncclGroupEnd");
+    }
+    // the exchange of a skinned step: message A and the list ids of the previous step in ONE group (four sends, four receives)
+    void ring_step(hipStream_t st, const double *msg_to_l, const double *msg_to_r, const int *ids_to_l, const int *ids_to_r,
+                   double *msg_from_l, double *msg_from_r, int *ids_from_l, int *ids_from_r, size_t n_msg, size_t n_ids)
+    {
+        R.check(R.GroupStart(), "ncclGroupStart");
+        R.check(R.Send(msg_to_l, n_msg, ncclDouble, left, comm, st), "ncclSend");
+        R.check(R.Send(msg_to_r, n_msg, ncclDouble, right, comm, st), "ncclSend");
+        R.check(R.Send(ids_to_l, n_ids, ncclInt32, left, comm, st), "ncclSend");
+        R.check(R.Send(ids_to_r, n_ids, ncclInt32, right, comm, st), "ncclSend");
+        R.check(R.Recv(msg_from_r, n_msg, ncclDouble, right, comm, st), "ncclRecv");
+        R.check(R.Recv(msg_from_l, n_msg, ncclDouble, left, comm, st), "ncclRecv");
+        R.check(R.Recv(ids_from_r, n_ids, ncclInt32, right, comm, st), "ncclRecv");
+        R.check(R.Recv(ids_from_l, n_ids, ncclInt32, left, comm, st), "ncclRecv");
+        R.check(R.GroupEnd(), "ncclGroupEnd");
+    }
+    void max(hipStream_t st, const double *mine, double *of_all, size_t count)
+    {
+        R.check(R.AllReduce(mine, of_all, count, ncclDouble, ncclMax, comm, st), "ncclAllReduce");
     }
 };
 
@@ -2551,16 +2573,9 @@ SPHX_EXPORT int sphx_comm_selftest(void)
         sl.upload(hl.data(), n, st); sr.upload(hr.data(), n, st); il.upload(kl.data(), n, st); ir.upload(kr.data(), n, st);
         v.upload(hv, 2, st);
         rl.zero(st); rr.zero(st); jl.zero(st); jr.zero(st); vg.zero(st);
-        auto ring = [&](const void *to_l, const void *to_r, void *from_l, void *from_r, ncclDataType_t ty) {
-            R.check(R.GroupStart(), "ncclGroupStart");
-            R.check(R.Send(to_l, n, ty, 0, comm, st), "ncclSend");
-            R.check(R.Send(to_r, n, ty, 0, comm, st), "ncclSend");
-            R.check(R.Recv(from_r, n, ty, 0, comm, st), "ncclRecv");
-            R.check(R.Recv(from_l, n, ty, 0, comm, st), "ncclRecv");
-            R.check(R.GroupEnd(), "ncclGroupEnd");
-        };
-        ring(sl.get(), sr.get(), rl.get(), rr.get(), ncclDouble);
-        ring(il.get(), ir.get(), jl.get(), jr.get(), ncclInt32);
+        Wire w{R, comm, 0, 0};
+        w.ring(st, sl.get(), sr.get(), rl.get(), rr.get(), n, ncclDouble);
+        w.ring(st, il.get(), ir.get(), jl.get(), jr.get(), n, ncclInt32);
         SPHX_HIP(hipMemcpyAsync(got_l.data(), rl.get(), n * sizeof(double), hipMemcpyDeviceToHost, st));
         SPHX_HIP(hipMemcpyAsync(got_r.data(), rr.get(), n * sizeof(double), hipMemcpyDeviceToHost, st));
         SPHX_HIP(hipMemcpyAsync(gi_l.data(), jl.get(), n * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2569,17 +2584,8 @@ SPHX_EXPORT int sphx_comm_selftest(void)
         const bool ok_two = got_r == hl && got_l == hr && gi_r == kl && gi_l == kr;
         // ... and the exchange of a skinned step: both messages and both id lists in ONE group (four sends, four receives)
         rl.zero(st); rr.zero(st); jl.zero(st); jr.zero(st);
-        R.check(R.GroupStart(), "ncclGroupStart");
-        R.check(R.Send(sl.get(), n, ncclDouble, 0, comm, st), "ncclSend");
-        R.check(R.Send(sr.get(), n, ncclDouble, 0, comm, st), "ncclSend");
-        R.check(R.Send(il.get(), n, ncclInt32, 0, comm, st), "ncclSend");
-        R.check(R.Send(ir.get(), n, ncclInt32, 0, comm, st), "ncclSend");
-        R.check(R.Recv(rr.get(), n, ncclDouble, 0, comm, st), "ncclRecv");
-        R.check(R.Recv(rl.get(), n, ncclDouble, 0, comm, st), "ncclRecv");
-        R.check(R.Recv(jr.get(), n, ncclInt32, 0, comm, st), "ncclRecv");
-        R.check(R.Recv(jl.get(), n, ncclInt32, 0, comm, st), "ncclRecv");
-        R.check(R.GroupEnd(), "ncclGroupEnd");
-        R.check(R.AllReduce(v.get(), vg.get(), 2, ncclDouble, ncclMax, comm, st), "ncclAllReduce");
+        w.ring_step(st, sl.get(), sr.get(), il.get(), ir.get(), rl.get(), rr.get(), jl.get(), jr.get(), n, n);
+        w.max(st, v.get(), vg.get(), 2);
         SPHX_HIP(hipMemcpyAsync(got_l.data(), rl.get(), n * sizeof(double), hipMemcpyDeviceToHost, st));
         SPHX_HIP(hipMemcpyAsync(got_r.data(), rr.get(), n * sizeof(double), hipMemcpyDeviceToHost, st));
         SPHX_HIP(hipMemcpyAsync(gi_l.data(), jl.get(), n * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2621,18 +2627,10 @@ SPHX_EXPORT int sphx_comm_selftest_graph(void)
     std::vector<double> hl(n), hr(n), got_l(n), got_r(n);
     std::vector<int> kl(n), kr(n), gi_l(n), gi_r(n);
     bool ok = true;
+    Wire w{R, comm, 0, 0};
     auto exchange = [&]() {
-        R.check(R.AllReduce(v.get(), vg.get(), 2, ncclDouble, ncclMax, comm, st), "ncclAllReduce");
-        R.check(R.GroupStart(), "ncclGroupStart");
-        R.check(R.Send(sl.get(), n, ncclDouble, 0, comm, st), "ncclSend");
-        R.check(R.Send(sr.get(), n, ncclDouble, 0, comm, st), "ncclSend");
-        R.check(R.Send(il.get(), n, ncclInt32, 0, comm, st), "ncclSend");
-        R.check(R.Send(ir.get(), n, ncclInt32, 0, comm, st), "ncclSend");
-        R.check(R.Recv(rr.get(), n, ncclDouble, 0, comm, st), "ncclRecv");
-        R.check(R.Recv(rl.get(), n, ncclDouble, 0, comm, st), "ncclRecv");
-        R.check(R.Recv(jr.get(), n, ncclInt32, 0, comm, st), "ncclRecv");
-        R.check(R.Recv(jl.get(), n, ncclInt32, 0, comm, st), "ncclRecv");
-        R.check(R.GroupEnd(), "ncclGroupEnd");
+        w.max(st, v.get(), vg.get(), 2);
+        w.ring_step(st, sl.get(), sr.get(), il.get(), ir.get(), rl.get(), rr.get(), jl.get(), jr.get(), n, n);
     };
     try {
         SPHX_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -2733,9 +2731,9 @@ void slab_phase1_abc(sphx_ctx *c)
     launch_pass_b(c, k.q, k.s, k.t);
     launch_pass_cd(c, k.q, k.s, k.t);
 }
-// message A of the step just taken is packed, the clock advanced, the host's parity flipped (slab_phase4): the interior
-// workgroups of the NEXT step's pass A (the step slot of parity q) need nothing the exchange brings -- they run while it is
-// under way
+// message A of the step being taken is packed, the clock advanced (the host's parity flips only in slab_phase4: q is the
+// parity it will have): the interior workgroups of the NEXT step's pass A (the step slot of parity q) need nothing the
+// exchange brings -- they run while it is under way
 void slab_pass_a_interior(sphx_ctx *c, int q)
 {
     const SlabSlot k(c, q);
@@ -2824,234 +2822,268 @@ namespace {
 
 constexpr int kSlabGraphSteps = 10;  // steps per replay of a slab's step graph (even: the state parity comes back)
 
-// ---- one rank per process: the steps of sphx_slab_run on the context's stream (eagerly, or under stream capture) ----
-struct RcclLoop {
+// ---- The transports beneath the step: which slabs this process drives, the all-reduce(max) of vmax_l into vmax_g, the three
+// exchanges (messages; ids; both in one group), the phase boundaries.  The step forms below are written once against them -- a
+// template parameter, as Forms is in the launch layer: no virtual call on the step path -- so the in-process ring of the tests
+// runs the statements the RCCL loop runs.  What really differs between the two is a named member with its reason. ----
+using SlabEvent = hipEvent_t sphx_ctx::*;
+
+// what `to` gets from here on comes after what `from` has got so far
+void order_after(hipEvent_t ev, hipStream_t from, hipStream_t to)
+{
+    SPHX_HIP(hipEventRecord(ev, from));
+    SPHX_HIP(hipStreamWaitEvent(to, ev, 0));
+}
+
+// one rank per process: RCCL on the slab's streams.  RCCL orders the ranks by itself: the phase boundaries are empty.
+struct RcclRing {
     sphx_ctx *c;
-    Rccl &R;
-    hipStream_t st;
-    int left, right;
+    Wire w;
     size_t n_msg, n_ids;
-    explicit RcclLoop(sphx_ctx *ctx)
-        : c(ctx), R(Rccl::get()), st(ctx->stream), left((ctx->rank + ctx->n_ranks - 1) % ctx->n_ranks),
-          right((ctx->rank + 1) % ctx->n_ranks), n_msg(1 + 7 * (size_t)ctx->msg_cap), n_ids(1 + (size_t)ctx->msg_cap) {}
-    // My left message is my left neighbour's "from the right" message and vice versa; with two ranks both go to the same
-    // peer, which posts its receives in the order the sends are posted here.
-    void ring(const void *to_l, const void *to_r, void *from_l, void *from_r, size_t count, ncclDataType_t ty)
+    bool captured = false;  // under stream capture: everything on the one capturing stream
+    explicit RcclRing(sphx_ctx *ctx)
+        : c(ctx), w{Rccl::get(), ctx->comm, (ctx->rank + ctx->n_ranks - 1) % ctx->n_ranks, (ctx->rank + 1) % ctx->n_ranks},
+          n_msg(1 + 7 * (size_t)ctx->msg_cap), n_ids(1 + (size_t)ctx->msg_cap) {}
+    sphx_ctx **begin() { return &c; }
+    sphx_ctx **end() { return &c + 1; }
+    // the protocol form reduces max |v| alone (8 bytes on the wire per step): nothing measures a drift when every step re-bins
+    static constexpr size_t kProtocolMaxima = 1;
+    // a captured split step does not launch the interior of the next pass A: on one stream the early launch hides nothing and
+    // costs a launch per step
+    static constexpr bool kInteriorWhenCaptured = false;
+    void all_reduce(sphx_ctx *, hipStream_t st, size_t count) { w.max(st, c->vmax_l.get(), c->vmax_g.get(), count); }
+    void exchange_msgs(sphx_ctx *, hipStream_t st)
     {
-        R.check(R.GroupStart(), "ncclGroupStart");
-        R.check(R.Send(to_l, count, ty, left, c->comm, st), "ncclSend");
-        R.check(R.Send(to_r, count, ty, right, c->comm, st), "ncclSend");
-        R.check(R.Recv(from_r, count, ty, right, c->comm, st), "ncclRecv");
-        R.check(R.Recv(from_l, count, ty, left, c->comm, st), "ncclRecv");
-        R.check(R.GroupEnd(), "ncclGroupEnd");
+        w.ring(st, c->msg_sl.get(), c->msg_sr.get(), c->msg_rl.get(), c->msg_rr.get(), n_msg, ncclDouble);
     }
-    // the exchange of a skinned step: message A and the list ids of the previous step in ONE group
-    void ring_step()
+    void exchange_ids(sphx_ctx *, hipStream_t st)
     {
-        R.check(R.GroupStart(), "ncclGroupStart");
-        R.check(R.Send(c->msg_sl.get(), n_msg, ncclDouble, left, c->comm, st), "ncclSend");
-        R.check(R.Send(c->msg_sr.get(), n_msg, ncclDouble, right, c->comm, st), "ncclSend");
-        R.check(R.Send(c->ids_s_[0].get(), n_ids, ncclInt32, left, c->comm, st), "ncclSend");
-        R.check(R.Send(c->ids_s_[1].get(), n_ids, ncclInt32, right, c->comm, st), "ncclSend");
-        R.check(R.Recv(c->msg_rr.get(), n_msg, ncclDouble, right, c->comm, st), "ncclRecv");
-        R.check(R.Recv(c->msg_rl.get(), n_msg, ncclDouble, left, c->comm, st), "ncclRecv");
-        R.check(R.Recv(c->ids_r_[1].get(), n_ids, ncclInt32, right, c->comm, st), "ncclRecv");
-        R.check(R.Recv(c->ids_r_[0].get(), n_ids, ncclInt32, left, c->comm, st), "ncclRecv");
-        R.check(R.GroupEnd(), "ncclGroupEnd");
+        w.ring(st, c->ids_s_[0].get(), c->ids_s_[1].get(), c->ids_r_[0].get(), c->ids_r_[1].get(), n_ids, ncclInt32);
     }
-    void step()
+    void exchange_step(sphx_ctx *, hipStream_t st)
     {
-        double *vl = c->vmax_l.get(), *vg = c->vmax_g.get();
-        if (c->rebuild_every <= 1) {
-            slab_compute_impl(c, c->msg_sl.get(), c->msg_sr.get(), vl);
-            R.check(R.AllReduce(vl, vg, 1, ncclDouble, ncclMax, c->comm, st), "ncclAllReduce");
-            ring(c->msg_sl.get(), c->msg_sr.get(), c->msg_rl.get(), c->msg_rr.get(), n_msg, ncclDouble);
-            slab_finish_impl(c, c->msg_rl.get(), c->msg_rr.get(), vg);
-        } else if (c->stream2 && !serial_aux) {
-            // the maxima and the all-reduce on the second stream, beside pass E; then the exchange and what follows it on the
-            // second stream, beside the interior workgroups of the next step's pass A
-            slab_phase1_abc(c);
-            SPHX_HIP(hipEventRecord(c->ev_cd, st));
-            SPHX_HIP(hipStreamWaitEvent(c->stream2, c->ev_cd, 0));
-            slab_local_maxima_of_step(c, c->stream2);
-            R.check(R.AllReduce(vl, vg, 2, ncclDouble, ncclMax, c->comm, c->stream2), "ncclAllReduce");
-            SPHX_HIP(hipEventRecord(c->ev_ar, c->stream2));
-            slab_phase1_e(c);
-            SPHX_HIP(hipStreamWaitEvent(st, c->ev_ar, 0));
-            slab_phase2(c);
-            SPHX_HIP(hipEventRecord(c->ev_p, st));
-            SPHX_HIP(hipStreamWaitEvent(c->stream2, c->ev_p, 0));
-            {
-                hipStream_t keep = st;
-                st = c->stream2; c->stream = c->stream2;  // (ring_step and slab_phase3 enqueue on "the" stream)
-                try { ring_step(); slab_phase3(c); } catch (...) { st = keep; c->stream = keep; throw; }
-                st = keep; c->stream = keep;
-            }
-            SPHX_HIP(hipEventRecord(c->ev_u, c->stream2));
-            slab_phase4(c);
-            slab_pass_a_interior(c, c->sched.cur);
-            SPHX_HIP(hipStreamWaitEvent(st, c->ev_u, 0));
-        } else if (c->stream2) {  // (under stream capture: the same pieces in one chain)
-            slab_phase1_abc(c);
-            slab_local_maxima_of_step(c, st);
-            R.check(R.AllReduce(vl, vg, 2, ncclDouble, ncclMax, c->comm, st), "ncclAllReduce");
-            slab_phase1_e(c);
-            slab_phase2(c);
-            ring_step();
-            slab_phase3(c);
-            slab_phase4(c);
-        } else {
-            slab_phase1(c);
-            R.check(R.AllReduce(vl, vg, 2, ncclDouble, ncclMax, c->comm, st), "ncclAllReduce");
-            slab_phase2(c);
-            ring_step();
-            slab_phase3(c);
-            slab_phase4(c);
-        }
+        w.ring_step(st, c->msg_sl.get(), c->msg_sr.get(), c->ids_s_[0].get(), c->ids_s_[1].get(), c->msg_rl.get(), c->msg_rr.get(),
+                    c->ids_r_[0].get(), c->ids_r_[1].get(), n_msg, n_ids);
     }
-    bool serial_aux = false;  // true under stream capture: everything on the one capturing stream
+    void done(sphx_ctx *, SlabEvent, hipStream_t) {}
+    void done_all(SlabEvent) {}
+    void wait_others(sphx_ctx *, SlabEvent, hipStream_t) {}
+    void gather_on_first() {}  // (a replay of the step graph: one stream, nothing to order)
+    void release_from_first() {}
+    // The split form's exchange and phase 3 run on the second stream, beside the interior workgroups of the next step's pass A:
+    // the point-to-point latencies are what the split hides.  ev_p: "message A is packed", ev_u: "the halo is refreshed".
+    hipStream_t exchange_stream(sphx_ctx *) const { return captured ? c->stream : c->stream2; }
+    void hand_over(sphx_ctx *) { if (!captured) order_after(c->ev_p, c->stream, c->stream2); }
+    void hand_back(sphx_ctx *) { if (!captured) order_after(c->ev_u, c->stream2, c->stream); }
 };
 
-// ---- all slabs of the ring in one process: the same steps with device-to-device copies and events ----
-struct GroupLoop {
+// all slabs of the ring in one process on one device: k_max_of and device-to-device copies, events for the ordering
+struct InProcessRing {
     sphx_ctx **ctxs;
     int n;
     PtrList vls{};
-    bool skinned;
-    bool serial = false;  // every slab enqueues on the same stream: stream order is the only ordering needed
     size_t msg_bytes, ids_bytes;
-    GroupLoop(sphx_ctx **cs, int count) : ctxs(cs), n(count)
+    bool captured = false;  // every slab enqueues on the same stream: stream order is the only ordering needed
+    InProcessRing(sphx_ctx **cs, int count) : ctxs(cs), n(count)
     {
         for (int r = 0; r < n; ++r) vls.p[r] = ctxs[r]->vmax_l.get();
-        skinned = ctxs[0]->rebuild_every > 1;
         msg_bytes = (1 + 7 * (size_t)ctxs[0]->msg_cap) * sizeof(double);
         ids_bytes = (1 + (size_t)ctxs[0]->msg_cap) * sizeof(int);
     }
-    // A phase boundary of the ring: every rank records "my outputs of this phase are complete" and, before it touches
-    // anything another rank produced (or overwrites what another rank may still be reading), waits for all the others.
-    void done(hipEvent_t sphx_ctx::*ev)
+    sphx_ctx **begin() { return ctxs; }
+    sphx_ctx **end() { return ctxs + n; }
+    static constexpr size_t kProtocolMaxima = 2;  // k_max_of costs the same for both components (the drift entry is 0)
+    // under capture the interior of the next pass A is still launched early: what the ring tests is the split of pass A itself
+    static constexpr bool kInteriorWhenCaptured = true;
+    sphx_ctx *left_of(sphx_ctx *c) const { return ctxs[(c->rank + n - 1) % n]; }
+    sphx_ctx *right_of(sphx_ctx *c) const { return ctxs[(c->rank + 1) % n]; }
+    void all_reduce(sphx_ctx *c, hipStream_t st, size_t count)  // thread j: component j
     {
-        if (serial) return;
-        for (int r = 0; r < n; ++r) SPHX_HIP(hipEventRecord(ctxs[r]->*ev, ctxs[r]->stream));
+        hipLaunchKernelGGL(k_max_of, dim3(1), dim3((unsigned)count), 0, st, n, vls, c->vmax_g.get());
     }
-    void wait_others(int r, hipEvent_t sphx_ctx::*ev)
+    void exchange_msgs(sphx_ctx *c, hipStream_t st)  // what my ring neighbours addressed to me
     {
-        if (serial) return;
-        for (int o = 0; o < n; ++o) if (o != r) SPHX_HIP(hipStreamWaitEvent(ctxs[r]->stream, ctxs[o]->*ev, 0));
+        SPHX_HIP(hipMemcpyAsync(c->msg_rl.get(), left_of(c)->msg_sr.get(), msg_bytes, hipMemcpyDeviceToDevice, st));
+        SPHX_HIP(hipMemcpyAsync(c->msg_rr.get(), right_of(c)->msg_sl.get(), msg_bytes, hipMemcpyDeviceToDevice, st));
     }
-    void max_of_all(sphx_ctx *c) { hipLaunchKernelGGL(k_max_of, dim3(1), dim3(2), 0, c->stream, n, vls, c->vmax_g.get()); }
-    void copy_msgs(int r)  // what my ring neighbours addressed to me
+    void exchange_ids(sphx_ctx *c, hipStream_t st)
     {
-        sphx_ctx *c = ctxs[r], *L = ctxs[(r + n - 1) % n], *Rr = ctxs[(r + 1) % n];
-        SPHX_HIP(hipMemcpyAsync(c->msg_rl.get(), L->msg_sr.get(), msg_bytes, hipMemcpyDeviceToDevice, c->stream));
-        SPHX_HIP(hipMemcpyAsync(c->msg_rr.get(), Rr->msg_sl.get(), msg_bytes, hipMemcpyDeviceToDevice, c->stream));
+        SPHX_HIP(hipMemcpyAsync(c->ids_r_[0].get(), left_of(c)->ids_s_[1].get(), ids_bytes, hipMemcpyDeviceToDevice, st));
+        SPHX_HIP(hipMemcpyAsync(c->ids_r_[1].get(), right_of(c)->ids_s_[0].get(), ids_bytes, hipMemcpyDeviceToDevice, st));
     }
-    void copy_ids(int r)
+    void exchange_step(sphx_ctx *c, hipStream_t st) { exchange_msgs(c, st); exchange_ids(c, st); }
+    // A phase boundary of the ring: every slab records "my outputs of this phase are complete" and, before it touches
+    // anything another slab produced (or overwrites what another slab may still be reading), waits for all the others.
+    void done(sphx_ctx *c, SlabEvent ev, hipStream_t st) { if (!captured) SPHX_HIP(hipEventRecord(c->*ev, st)); }
+    void done_all(SlabEvent ev) { for (sphx_ctx *c : *this) done(c, ev, c->stream); }
+    void wait_others(sphx_ctx *c, SlabEvent ev, hipStream_t st)
     {
-        sphx_ctx *c = ctxs[r], *L = ctxs[(r + n - 1) % n], *Rr = ctxs[(r + 1) % n];
-        SPHX_HIP(hipMemcpyAsync(c->ids_r_[0].get(), L->ids_s_[1].get(), ids_bytes, hipMemcpyDeviceToDevice, c->stream));
-        SPHX_HIP(hipMemcpyAsync(c->ids_r_[1].get(), Rr->ids_s_[0].get(), ids_bytes, hipMemcpyDeviceToDevice, c->stream));
+        if (captured) return;
+        for (sphx_ctx *o : *this) if (o != c) SPHX_HIP(hipStreamWaitEvent(st, o->*ev, 0));
     }
-    // entry_waits: the slabs first wait until the others have consumed their previous messages and maxima (not the first
-    // step of a captured graph: what came before is ordered by the launch, see replay())
-    void step(bool entry_waits = true)
+    // the copies that stand in for the exchange, and phase 3 behind them, stay on the slab's own stream: the neighbours wait for
+    // this slab's message A at ev_received, recorded in front of the interior of pass A, and need no second hand-over
+    hipStream_t exchange_stream(sphx_ctx *c) const { return c->stream; }
+    void hand_over(sphx_ctx *) {}
+    void hand_back(sphx_ctx *) {}
+    // a replay of slab 0's step graph: everything the slabs enqueued before it is ordered ahead of it, everything they enqueue
+    // afterwards behind it
+    void gather_on_first() { for (int r = 1; r < n; ++r) order_after(ctxs[r]->ev_join, ctxs[r]->stream, ctxs[0]->stream); }
+    void release_from_first()
     {
-        const bool overlap = skinned && ctxs[0]->stream2 != nullptr;
-        if (overlap) {
-            // passes A, B, CD; the local maxima on every slab's second stream (serial: on the one stream); pass E beside them;
-            // the stand-in for the all-reduce on the second stream once everybody's maxima are out; join in front of pack3
-            auto aux = [&](sphx_ctx *c) { return serial ? c->stream : c->stream2; };
-            for (int r = 0; r < n; ++r) {
-                sphx_ctx *c = ctxs[r];
-                if (entry_waits) wait_others(r, &sphx_ctx::ev_received);
-                slab_phase1_abc(c);
-                if (!serial) {
-                    SPHX_HIP(hipEventRecord(c->ev_cd, c->stream));
-                    SPHX_HIP(hipStreamWaitEvent(c->stream2, c->ev_cd, 0));
-                }
-                slab_local_maxima_of_step(c, aux(c));
-                if (!serial) SPHX_HIP(hipEventRecord(c->ev_max, c->stream2));
-            }
-            for (int r = 0; r < n; ++r) slab_phase1_e(ctxs[r]);
-            for (int r = 0; r < n; ++r) {  // "all-reduce", decision, message A
-                sphx_ctx *c = ctxs[r];
-                if (!serial)
-                    for (int o = 0; o < n; ++o) if (o != r) SPHX_HIP(hipStreamWaitEvent(c->stream2, ctxs[o]->ev_max, 0));
-                hipLaunchKernelGGL(k_max_of, dim3(1), dim3(2), 0, aux(c), n, vls, c->vmax_g.get());
-                if (!serial) {
-                    SPHX_HIP(hipEventRecord(c->ev_ar, c->stream2));
-                    SPHX_HIP(hipStreamWaitEvent(c->stream, c->ev_ar, 0));
-                }
-                slab_phase2(c);
-                // "my maxima have been read by me, my message A is complete" -- recorded HERE, in front of the interior
-                // workgroups of the next step's pass A, which the neighbours need not wait for (the in-process ring keeps the
-                // copies that stand in for the exchange on the slab's own stream: what it tests is the split itself)
-                if (!serial) SPHX_HIP(hipEventRecord(c->ev_received, c->stream));
-                slab_pass_a_interior(c, 1 - c->sched.cur);
-            }
-        } else {
-        for (int r = 0; r < n; ++r) {
-            sphx_ctx *c = ctxs[r];
-            if (entry_waits) wait_others(r, &sphx_ctx::ev_received);
-            if (skinned) slab_phase1(c);
-            else slab_compute_impl(c, c->msg_sl.get(), c->msg_sr.get(), c->vmax_l.get());
-        }
-        done(&sphx_ctx::ev_computed);
-        if (!skinned) {
-            for (int r = 0; r < n; ++r) {
-                sphx_ctx *c = ctxs[r];
-                wait_others(r, &sphx_ctx::ev_computed);
-                copy_msgs(r);
-                max_of_all(c);
-            }
-            done(&sphx_ctx::ev_received);
-            for (int r = 0; r < n; ++r) slab_finish_impl(ctxs[r], ctxs[r]->msg_rl.get(), ctxs[r]->msg_rr.get(), ctxs[r]->vmax_g.get());
-            return;
-        }
-        for (int r = 0; r < n; ++r) {  // "all-reduce", decision, message A
-            sphx_ctx *c = ctxs[r];
-            wait_others(r, &sphx_ctx::ev_computed);
-            max_of_all(c);
-            slab_phase2(c);
-        }
-        }
-        if (!overlap) done(&sphx_ctx::ev_received);  // (reused: "my maxima have been read by me, my message A is complete")
-        for (int r = 0; r < n; ++r) {  // message A and the ids of the previous step's lists in
-            wait_others(r, &sphx_ctx::ev_received);
-            copy_msgs(r);
-            copy_ids(r);
-        }
-        done(&sphx_ctx::ev_computed);  // (reused: "I have taken what the neighbours addressed to me")
-        for (int r = 0; r < n; ++r) {  // halo refresh or re-binning chain; the lists / ids of the next cycle overwrite the old ones
-            wait_others(r, &sphx_ctx::ev_computed);
-            slab_phase3(ctxs[r]);
-            slab_phase4(ctxs[r]);
-        }
-        done(&sphx_ctx::ev_received);
-    }
-    bool graph_matches() const
-    {
-        const sphx_ctx *c0 = ctxs[0];
-        if (!c0->steps_graph || (int)c0->steps_graph_ring.size() != n || c0->steps_graph_cur != c0->sched.cur) return false;
-        for (int r = 0; r < n; ++r) if (c0->steps_graph_ring[r] != ctxs[r]) return false;
-        return true;
-    }
-    // one replay of slab 0's step graph: everything the slabs enqueued before it is ordered ahead of it, everything they
-    // enqueue afterwards behind it
-    void replay()
-    {
-        sphx_ctx *c0 = ctxs[0];
-        for (int r = 1; r < n; ++r) {
-            SPHX_HIP(hipEventRecord(ctxs[r]->ev_join, ctxs[r]->stream));
-            SPHX_HIP(hipStreamWaitEvent(c0->stream, ctxs[r]->ev_join, 0));
-        }
-        SPHX_HIP(hipGraphLaunch(c0->steps_graph, c0->stream));
-        SPHX_HIP(hipEventRecord(c0->ev_fork, c0->stream));
-        for (int r = 1; r < n; ++r) SPHX_HIP(hipStreamWaitEvent(ctxs[r]->stream, c0->ev_fork, 0));
-        done(&sphx_ctx::ev_received);  // (the eager steps that may follow wait for these)
-        for (int r = 0; r < n; ++r) { ctxs[r]->slab_steps_enqueued += kSlabGraphSteps; ctxs[r]->a_interior_done = false; }
+        SPHX_HIP(hipEventRecord(ctxs[0]->ev_fork, ctxs[0]->stream));
+        for (int r = 1; r < n; ++r) SPHX_HIP(hipStreamWaitEvent(ctxs[r]->stream, ctxs[0]->ev_fork, 0));
     }
 };
+
+// slab_phase3 enqueues on "the" stream of its context: run it on another one for a scope
+struct OnStream {
+    sphx_ctx *c;
+    hipStream_t own;
+    OnStream(sphx_ctx *ctx, hipStream_t st) : c(ctx), own(ctx->stream) { c->stream = st; }
+    ~OnStream() { c->stream = own; }
+};
+
+// ---- the three forms of a step.  Each starts with the slabs waiting until the others have consumed their previous messages
+// and maxima (ev_received). ----
+
+// rebuild_every = 1, the protocol of compute / finish: re-binning every step, whole messages
+template <typename T> void step_protocol(T &t)
+{
+    for (sphx_ctx *c : t) {
+        t.wait_others(c, &sphx_ctx::ev_received, c->stream);
+        slab_compute_impl(c, c->msg_sl.get(), c->msg_sr.get(), c->vmax_l.get());
+    }
+    t.done_all(&sphx_ctx::ev_computed);
+    for (sphx_ctx *c : t) {
+        t.wait_others(c, &sphx_ctx::ev_computed, c->stream);
+        t.all_reduce(c, c->stream, T::kProtocolMaxima);
+        t.exchange_msgs(c, c->stream);
+    }
+    t.done_all(&sphx_ctx::ev_received);
+    for (sphx_ctx *c : t) slab_finish_impl(c, c->msg_rl.get(), c->msg_rr.get(), c->vmax_g.get());
+}
+
+// second half of both skinned forms: message A and the ids of the previous step's lists in; halo refresh or re-binning chain
+// (the lists / ids of the next cycle overwrite the old ones); host bookkeeping.  split: on the transport's exchange stream.
+template <typename T> void step_exchange_and_after(T &t, bool split)
+{
+    auto xs = [&](sphx_ctx *c) { return split ? t.exchange_stream(c) : c->stream; };
+    for (sphx_ctx *c : t) {
+        t.wait_others(c, &sphx_ctx::ev_received, c->stream);
+        t.exchange_step(c, xs(c));
+    }
+    t.done_all(&sphx_ctx::ev_computed);  // (reused: "I have taken what the neighbours addressed to me")
+    for (sphx_ctx *c : t) {
+        t.wait_others(c, &sphx_ctx::ev_computed, c->stream);
+        { OnStream on(c, xs(c)); slab_phase3(c); }
+        if (split) t.hand_back(c);
+        slab_phase4(c);
+    }
+    t.done_all(&sphx_ctx::ev_received);
+}
+
+// the skinned step as one chain per slab (below ~150 k particles per slab, see slab_native_buffers)
+template <typename T> void step_chain(T &t)
+{
+    for (sphx_ctx *c : t) {
+        t.wait_others(c, &sphx_ctx::ev_received, c->stream);
+        slab_phase1(c);
+    }
+    t.done_all(&sphx_ctx::ev_computed);
+    for (sphx_ctx *c : t) {  // all-reduce, decision, message A
+        t.wait_others(c, &sphx_ctx::ev_computed, c->stream);
+        t.all_reduce(c, c->stream, 2);
+        slab_phase2(c);
+    }
+    t.done_all(&sphx_ctx::ev_received);  // (reused: "my maxima have been read by me, my message A is complete")
+    step_exchange_and_after(t, false);
+}
+
+// The skinned step on two streams: passes A, B, CD; the local maxima and the all-reduce on the second stream (fork ev_cd, join
+// ev_ar in front of pack3) beside pass E; the exchange beside the interior workgroups of the next step's pass A.  Under stream
+// capture (t.captured): the same pieces in one chain on the capturing stream, no events.
+template <typename T> void step_split(T &t)
+{
+    const bool two = !t.captured;
+    auto aux = [&](sphx_ctx *c) { return two ? c->stream2 : c->stream; };
+    for (sphx_ctx *c : t) {
+        t.wait_others(c, &sphx_ctx::ev_received, c->stream);
+        slab_phase1_abc(c);
+        if (two) order_after(c->ev_cd, c->stream, c->stream2);
+        slab_local_maxima_of_step(c, aux(c));
+        t.done(c, &sphx_ctx::ev_max, aux(c));  // "my local maxima are out"
+    }
+    for (sphx_ctx *c : t) {  // all-reduce beside pass E, decision, message A
+        t.wait_others(c, &sphx_ctx::ev_max, aux(c));
+        t.all_reduce(c, aux(c), 2);
+        slab_phase1_e(c);
+        if (two) order_after(c->ev_ar, c->stream2, c->stream);
+        slab_phase2(c);
+        // "my maxima have been read by me, my message A is complete" -- recorded HERE, in front of the interior workgroups of
+        // the next step's pass A, which the neighbours need not wait for
+        t.done(c, &sphx_ctx::ev_received, c->stream);
+        t.hand_over(c);
+        if (two || T::kInteriorWhenCaptured) slab_pass_a_interior(c, 1 - c->sched.cur);  // (phase 4 flips the parity)
+    }
+    step_exchange_and_after(t, true);
+}
+
+template <typename T> void slab_step(T &t)
+{
+    const sphx_ctx *c0 = *t.begin();
+    if (c0->rebuild_every <= 1) step_protocol(t);
+    else if (c0->stream2) step_split(t);
+    else step_chain(t);
+}
+
+template <typename T> void slab_replay(T &t)  // one replay of the step graph, on the first slab's stream
+{
+    sphx_ctx *c0 = *t.begin();
+    t.gather_on_first();
+    SPHX_HIP(hipGraphLaunch(c0->steps_graph, c0->stream));
+    t.release_from_first();
+    t.done_all(&sphx_ctx::ev_received);  // (the eager steps that may follow wait for these)
+    for (sphx_ctx *c : t) { c->slab_steps_enqueued += kSlabGraphSteps; c->a_interior_done = false; }
+}
+
+// n_steps steps of the slabs of t: arm, first exchange lists, whole replays of the step graph, the rest step by step
+template <typename T> void slab_run(T &t, double t_target, int64_t n_steps)
+{
+    const sphx_ctx *c0 = *t.begin();
+    const bool skinned = c0->rebuild_every > 1;
+    // Arm the clock with the global max |v| of the current state: after a step the clock holds it already (the all-reduced
+    // value that step's dt rule used); only a state that has never been stepped needs the reduction (k_vmax_init is one
+    // workgroup over the whole slab: 0.9 ms at 0.76 M particles)
+    bool fresh_state = false;
+    for (sphx_ctx *c : t) {
+        c->a_interior_done = false;  // (whatever the previous call launched ahead found the loop stopped: the first step sweeps / walks everything)
+        fresh_state = fresh_state || c->slab_steps_enqueued == 0;
+    }
+    for (sphx_ctx *c : t) if (fresh_state) slab_local_maxima(c);
+    t.done_all(&sphx_ctx::ev_computed);
+    for (sphx_ctx *c : t) {
+        t.wait_others(c, &sphx_ctx::ev_computed, c->stream);
+        if (fresh_state) t.all_reduce(c, c->stream, 2);
+        arm_clock(c, t_target, (long long)n_steps, c->sched.cur, fresh_state ? (const double *)c->vmax_g.get() : (const double *)nullptr);
+        if (skinned && !c->lists_ready) slab_lists_out(c);
+    }
+    t.done_all(&sphx_ctx::ev_received);
+    if (skinned && !c0->lists_ready) {
+        for (sphx_ctx *c : t) {
+            t.wait_others(c, &sphx_ctx::ev_received, c->stream);
+            t.exchange_ids(c, c->stream);
+            slab_lists_in(c);
+        }
+        t.done_all(&sphx_ctx::ev_received);
+    }
+    int64_t k = 0;
+    if (c0->steps_graph && c0->steps_graph_cur == c0->sched.cur &&  // whole replays of the step graph (sphx_slab_graph_prepare) ...
+        std::equal(t.begin(), t.end(), c0->steps_graph_ring.begin(), c0->steps_graph_ring.end()))
+        for (; n_steps - k >= kSlabGraphSteps; k += kSlabGraphSteps) slab_replay(t);
+    for (; k < n_steps; ++k) slab_step(t);  // ... the rest step by step
+    SPHX_HIP(hipGetLastError());
+}
 
 void check_ring(sphx_ctx **ctxs, int n)
 {
@@ -3080,34 +3112,8 @@ SPHX_EXPORT int sphx_slab_run(sphx_ctx *c, double t_target, int64_t n_steps)
     require(c != nullptr && c->is_slab, "SPHX:Slab:ctx", "not a slab context");
     require(c->comm != nullptr, "SPHX:Slab:rccl", "sphx_slab_comm_init first");
     require(n_steps > 0, "SPHX:Ctx:steps", "n_steps must be positive");
-    RcclLoop loop(c);
-    double *vl = c->vmax_l.get(), *vg = c->vmax_g.get();
-    const bool skinned = c->rebuild_every > 1;
-    c->a_interior_done = false;  // (whatever the previous call launched ahead found the loop stopped: the first step sweeps / walks everything)
-    // arm the clock with the global max |v| of the current state: after a step the clock holds it already (the all-reduced
-    // value that step's dt rule used); only a state that has never been stepped needs the reduction (k_vmax_init is one
-    // workgroup over the whole slab: 0.9 ms at 0.76 M particles)
-    if (c->slab_steps_enqueued == 0) {
-        slab_local_maxima(c);
-        loop.R.check(loop.R.AllReduce(vl, vg, 2, ncclDouble, ncclMax, c->comm, loop.st), "ncclAllReduce");
-        arm_clock(c, t_target, (long long)n_steps, c->sched.cur, (const double *)vg);
-    } else {
-        arm_clock(c, t_target, (long long)n_steps, c->sched.cur, (const double *)nullptr);
-    }
-    if (skinned && !c->lists_ready) {
-        slab_lists_out(c);
-        loop.ring(c->ids_s_[0].get(), c->ids_s_[1].get(), c->ids_r_[0].get(), c->ids_r_[1].get(), loop.n_ids, ncclInt32);
-        slab_lists_in(c);
-    }
-    int64_t k = 0;
-    if (c->steps_graph && c->steps_graph_cur == c->sched.cur)  // whole replays of the step graph (sphx_slab_graph_prepare) ...
-        for (; n_steps - k >= kSlabGraphSteps; k += kSlabGraphSteps) {
-            SPHX_HIP(hipGraphLaunch(c->steps_graph, loop.st));
-            c->slab_steps_enqueued += kSlabGraphSteps;
-            c->a_interior_done = false;
-        }
-    for (; k < n_steps; ++k) loop.step();  // ... the rest step by step
-    SPHX_HIP(hipGetLastError());
+    RcclRing t(c);
+    slab_run(t, t_target, n_steps);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -3117,39 +3123,71 @@ SPHX_EXPORT int sphx_slab_group_run(sphx_ctx **ctxs, int n, double t_target, int
     SPHX_TRY
     check_ring(ctxs, n);
     require(n_steps > 0, "SPHX:Ctx:steps", "n_steps must be positive");
-    GroupLoop loop(ctxs, n);
-    for (int r = 0; r < n; ++r) ctxs[r]->a_interior_done = false;  // (see sphx_slab_run)
-    // arm: local maxima -> global -> clock (a state that has been stepped: the clock holds the global maximum already, see
-    // sphx_slab_run); first exchange lists
-    bool fresh_state = false;
-    for (int r = 0; r < n; ++r) fresh_state = fresh_state || ctxs[r]->slab_steps_enqueued == 0;
-    if (fresh_state)
-        for (int r = 0; r < n; ++r) slab_local_maxima(ctxs[r]);
-    loop.done(&sphx_ctx::ev_computed);
-    for (int r = 0; r < n; ++r) {
-        sphx_ctx *c = ctxs[r];
-        loop.wait_others(r, &sphx_ctx::ev_computed);
-        if (fresh_state) loop.max_of_all(c);
-        arm_clock(c, t_target, (long long)n_steps, c->sched.cur, fresh_state ? (const double *)c->vmax_g.get() : (const double *)nullptr);
-        if (loop.skinned && !c->lists_ready) slab_lists_out(c);
-    }
-    loop.done(&sphx_ctx::ev_received);
-    if (loop.skinned && !ctxs[0]->lists_ready) {
-        for (int r = 0; r < n; ++r) {
-            loop.wait_others(r, &sphx_ctx::ev_received);
-            loop.copy_ids(r);
-            slab_lists_in(ctxs[r]);
-        }
-        loop.done(&sphx_ctx::ev_received);
-    }
-    int64_t k = 0;
-    if (loop.graph_matches())
-        for (; n_steps - k >= kSlabGraphSteps; k += kSlabGraphSteps) loop.replay();
-    for (; k < n_steps; ++k) loop.step();
-    SPHX_HIP(hipGetLastError());
+    InProcessRing t(ctxs, n);
+    slab_run(t, t_target, n_steps);
     return SPHX_OK;
     SPHX_CATCH
 }
+
+namespace {
+
+template <typename T> void slab_graph_prepare(T &t)
+{
+    sphx_ctx *c0 = *t.begin();
+    for (sphx_ctx *c : t) {
+        require(c->lists_ready && c->slab_steps_enqueued >= 2, "SPHX:Slab:graph",
+                "run at least two steps before capturing the step graph");
+        SPHX_HIP(hipStreamSynchronize(c->stream));
+    }
+    if (c0->steps_graph) { (void)hipGraphExecDestroy(c0->steps_graph); c0->steps_graph = nullptr; }
+    const int64_t enq0 = c0->slab_steps_enqueued;
+    const int cur0 = c0->sched.cur;
+    hipStream_t s0 = c0->stream;
+    hipGraph_t g = nullptr;
+    // An in-process ring is captured as ONE chain on slab 0's stream (the slabs take turns phase by phase): a graph whose
+    // branches meet at every phase boundary replays slower than the eager loop on ROCm 7.2 (0.25 M particles per slab: 334
+    // against 289 us/step), and the slabs of a ring share one device anyway.
+    std::vector<hipStream_t> own_streams;
+    for (sphx_ctx *c : t) {
+        own_streams.push_back(c->stream);
+        c->stream = s0;
+        c->a_interior_done = false;  // (the graph's first step sweeps / walks everything)
+    }
+    auto restore_streams = [&]() { size_t r = 0; for (sphx_ctx *c : t) c->stream = own_streams[r++]; };
+    const hipError_t e_begin = hipStreamBeginCapture(s0, hipStreamCaptureModeRelaxed);
+    if (e_begin != hipSuccess) { restore_streams(); SPHX_HIP(e_begin); }
+    t.captured = true;
+    try {
+        for (int k = 0; k < kSlabGraphSteps; ++k) slab_step(t);
+    } catch (...) {
+        abandon_capture(s0);
+        restore_streams();
+        for (sphx_ctx *c : t) { c->sched.cur = cur0; c->slab_steps_enqueued = enq0; }
+        throw;
+    }
+    t.captured = false;
+    restore_streams();
+    for (sphx_ctx *c : t) { c->slab_steps_enqueued -= kSlabGraphSteps; c->a_interior_done = false; }  // nothing has executed
+    const hipError_t e_end = hipStreamEndCapture(s0, &g);
+    if (e_end != hipSuccess) { (void)hipGetLastError(); if (g) (void)hipGraphDestroy(g); SPHX_HIP(e_end); }
+    hipGraphExec_t exec = nullptr;
+    const hipError_t e_inst = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    SPHX_HIP(e_inst);
+    // warm replay with the clock disarmed: every kernel returns at once, the messages that travel are ignored (ids made by
+    // the last real step are delivered -- that is what the next real step would have done first)
+    for (sphx_ctx *c : t) hipLaunchKernelGGL(k_disarm, dim3(1), dim3(1), 0, c->stream, c->clock.get());
+    c0->steps_graph = exec;
+    c0->steps_graph_cur = cur0;
+    c0->steps_graph_ring.assign(t.begin(), t.end());
+    slab_replay(t);
+    for (sphx_ctx *c : t) {
+        c->slab_steps_enqueued -= kSlabGraphSteps;  // (the warm replay stepped nothing)
+        SPHX_HIP(hipStreamSynchronize(c->stream));
+    }
+}
+
+}  // namespace
 
 // Capture kSlabGraphSteps whole steps of the native loop into one graph; sphx_slab_run / sphx_slab_group_run then replay it
 // for every full batch of that many steps and launch only the remainder step by step.  n = 1: the context of this
@@ -3162,67 +3200,16 @@ SPHX_EXPORT int sphx_slab_graph_prepare(sphx_ctx **ctxs, int n)
 {
     SPHX_TRY
     require(ctxs != nullptr && n >= 1 && ctxs[0] != nullptr && ctxs[0]->is_slab, "SPHX:Slab:ctx", "not a slab context");
-    sphx_ctx *c0 = ctxs[0];
-    require(c0->rebuild_every > 1, "SPHX:Slab:protocol", "step graphs are for skinned slabs (rebuild_every != 1)");
-    if (n == 1) require(c0->comm != nullptr, "SPHX:Slab:rccl", "sphx_slab_comm_init first");
-    else check_ring(ctxs, n);
-    for (int r = 0; r < n; ++r) {
-        require(ctxs[r]->lists_ready && ctxs[r]->slab_steps_enqueued >= 2, "SPHX:Slab:graph",
-                "run at least two steps before capturing the step graph");
-        SPHX_HIP(hipStreamSynchronize(ctxs[r]->stream));
-    }
-    if (c0->steps_graph) { (void)hipGraphExecDestroy(c0->steps_graph); c0->steps_graph = nullptr; }
-    const int64_t enq0 = c0->slab_steps_enqueued;
-    const int cur0 = c0->sched.cur;
-    hipStream_t s0 = c0->stream;
-    hipGraph_t g = nullptr;
-    // An in-process ring is captured as ONE chain on slab 0's stream (the slabs take turns phase by phase): a graph whose
-    // branches meet at every phase boundary replays slower than the eager loop on ROCm 7.2 (0.25 M particles per slab: 334
-    // against 289 us/step), and the slabs of a ring share one device anyway.
-    std::vector<hipStream_t> own_streams(n);
-    for (int r = 0; r < n; ++r) { own_streams[r] = ctxs[r]->stream; ctxs[r]->stream = s0; }
-    auto restore_streams = [&]() { for (int r = 0; r < n; ++r) ctxs[r]->stream = own_streams[r]; };
-    for (int r = 0; r < n; ++r) ctxs[r]->a_interior_done = false;  // (the graph's first step sweeps / walks everything)
-    const hipError_t e_begin = hipStreamBeginCapture(s0, hipStreamCaptureModeRelaxed);
-    if (e_begin != hipSuccess) { restore_streams(); SPHX_HIP(e_begin); }
-    try {
-        if (n == 1) {
-            RcclLoop loop(c0);
-            loop.serial_aux = true;
-            for (int k = 0; k < kSlabGraphSteps; ++k) loop.step();
-        } else {
-            GroupLoop loop(ctxs, n);
-            loop.serial = true;
-            for (int k = 0; k < kSlabGraphSteps; ++k) loop.step();
-        }
-    } catch (...) {
-        abandon_capture(s0);
-        restore_streams();
-        for (int r = 0; r < n; ++r) { ctxs[r]->sched.cur = cur0; ctxs[r]->slab_steps_enqueued = enq0; }
-        throw;
-    }
-    restore_streams();
-    for (int r = 0; r < n; ++r) { ctxs[r]->slab_steps_enqueued -= kSlabGraphSteps; ctxs[r]->a_interior_done = false; }  // nothing has executed
-    const hipError_t e_end = hipStreamEndCapture(s0, &g);
-    if (e_end != hipSuccess) { (void)hipGetLastError(); if (g) (void)hipGraphDestroy(g); SPHX_HIP(e_end); }
-    hipGraphExec_t exec = nullptr;
-    const hipError_t e_inst = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    SPHX_HIP(e_inst);
-    // warm replay with the clock disarmed: every kernel returns at once, the messages that travel are ignored (ids made by
-    // the last real step are delivered -- that is what the next real step would have done first)
-    for (int r = 0; r < n; ++r) hipLaunchKernelGGL(k_disarm, dim3(1), dim3(1), 0, ctxs[r]->stream, ctxs[r]->clock.get());
-    c0->steps_graph = exec;
-    c0->steps_graph_cur = cur0;
-    c0->steps_graph_ring.assign(ctxs, ctxs + n);
-    if (n == 1) {
-        SPHX_HIP(hipGraphLaunch(exec, s0));
+    require(ctxs[0]->rebuild_every > 1, "SPHX:Slab:protocol", "step graphs are for skinned slabs (rebuild_every != 1)");
+    if (n == 1) {  // (the one choice of transport)
+        require(ctxs[0]->comm != nullptr, "SPHX:Slab:rccl", "sphx_slab_comm_init first");
+        RcclRing t(ctxs[0]);
+        slab_graph_prepare(t);
     } else {
-        GroupLoop loop(ctxs, n);
-        loop.replay();
-        for (int r = 0; r < n; ++r) ctxs[r]->slab_steps_enqueued -= kSlabGraphSteps;
+        check_ring(ctxs, n);
+        InProcessRing t(ctxs, n);
+        slab_graph_prepare(t);
     }
-    for (int r = 0; r < n; ++r) SPHX_HIP(hipStreamSynchronize(ctxs[r]->stream));
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -117,6 +117,10 @@ def test_slab_hip_two_ranks_half_million_particles():
     # rank 0's left edge, the periodic wrap is the one of x < 0
     (2, 0.05, 3.0, 27, dict(leftward=True, rebuild_every=5)),
     (3, 0.05, 4.5, 23, dict(leftward=True, rebuild_every=4, overlap="always")),
+    # the two-stream step as a replayed graph: its pieces in one chain, the interior of the next pass A still launched early
+    # (last in the list: the ids of the cases above stay as they were)
+    (2, 0.05, 3.0, 47, dict(calls=[3, 25, 19], graph_after=0, overlap="always")),
+    (3, 0.05, 4.5, 36, dict(calls=[4, 32], graph_after=0, rebuild_every=4, overlap="always")),
 ])
 def test_slab_native_ring_in_one_process(world, dp, DL, steps, kw):
     """The library's own step loop (sphx_slab_group_run: every slab of the ring in this process, device-to-device
