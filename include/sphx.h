@@ -467,7 +467,7 @@ int sphx_ctx_history_read(sphx_ctx *ctx, int capacity, double *records, int *n_r
  *    slot ends with one more launch (k_field_map, behind k_flow_stats and k_step_history; it skips itself on the steps
  *    gated out) that is captured in the replayed graphs; enable / disable re-capture them.  Independent of the flow
  *    statistics and the step history: all three may be on at once.  The planes take 6 * nx * ny doubles of device memory.
- *  Batches (section 2b) and slabs have no field maps.
+ *  Batches (section 2b) keep one map per member: section 2g.  Slabs have no field maps.
  *  Errors: SPHX:Field:config (nx or ny equal to 1 or negative, nx * ny > 1 << 25, every < 1, NaN t_from, with_walls not
  *    0 or 1, or the allocation fails: the context then goes on without a map), SPHX:Field:disabled (SPHX_ERR_STATE: a
  *    call that needs the map while it is off), SPHX:Field:capacity (the caller's arrays are smaller than nx * ny); every
@@ -526,6 +526,43 @@ int sphx_batch_history_disable(sphx_batch *batch);
  * first, as sphx_batch_download does.  drain != 0: every member's buffer is emptied and its n_dropped zeroed after
  * copying. */
 int sphx_batch_history_read(sphx_batch *batch, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2g. Field maps of a batch (section 2b): the map of section 2e for every member at once.
+ *
+ *  One config for all members; the shape comes from the shared geometry.  Every member has its own six planes, sample
+ *  count and t_first / t_last, and is sampled on its own clock with the gating of section 2e, so a member that sits out
+ *  slots (it reached t_target, used up its steps, stopped on the drift bound) is not sampled in them and neither its
+ *  planes nor its count are touched.  A member's planes are bit for bit those of a standalone context with the same
+ *  parameters and config that took the same steps: the same thread owns a node and adds its candidates in the same
+ *  order.  After a realignment (section 2b) a member's particles are laid out differently, which changes the summation
+ *  order only, as a stop on the drift bound does for a context.  With the map on, every step slot of the batch ends
+ *  with one sampling launch for all members (k_field_map_b, behind the batch's statistics and history launches); off, a
+ *  slot enqueues exactly the launches it does without this feature.  Enable / disable wait for the stream and
+ *  re-capture the batch's graphs.  Independent of the batch's flow statistics (section 2c) and step history
+ *  (section 2f): all three may be on at once.
+ *  Memory: n_members * 6 * nx * ny doubles.  n_members * nx * ny must not exceed 1 << 25 nodes; when the planes do not
+ *  fit, enable fails and the batch goes on without a map.  A refused enable leaves a running map, and its sums,
+ *  untouched.
+ *  Errors: SPHX:Batch:null (NULL batch), SPHX:Field:config (as in section 2e, or n_members * nx * ny > 1 << 25),
+ *  SPHX:Field:disabled, SPHX:Field:capacity (the caller's capacity is below nx * ny).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* (Re)configure and zero every member's map; waits for the stream. */
+int sphx_batch_field_map_enable(sphx_batch *batch, const sphx_field_map_config *cfg);
+/* Stop sampling (no-op when off); the sums are dropped. */
+int sphx_batch_field_map_disable(sphx_batch *batch);
+/* settles what is enqueued, then zeroes */
+int sphx_batch_field_map_reset(sphx_batch *batch);
+/* settles; samples what sphx_batch_download returns, every member, without gating */
+int sphx_batch_field_map_sample(sphx_batch *batch);
+/* One call for all members.  Each plane array is n_members blocks of `capacity` doubles: member m at m * capacity, node
+ * (i, k) at i * ny + k within it, the rest of a block left as it is; any array may be NULL (all NULL: capacity is not
+ * checked, so the shape can be asked for first).  n_samples / t_first / t_last are [n_members].  Settles first, as
+ * sphx_batch_download does. */
+int sphx_batch_field_map_read(sphx_batch *batch, int capacity, int *nx, int *ny, double *count, double *sum_w,
+                              double *sum_ux, double *sum_uy, double *sum_ux2, double *sum_uy2, int64_t *n_samples,
+                              double *t_first, double *t_last);
 
 /* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU).  The channel is cut into n_ranks slabs of whole cell columns; each

@@ -83,6 +83,8 @@ EXPORTS = [
     "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",
     "sphx_batch_flow_stats_sample", "sphx_batch_flow_stats_read",
     "sphx_batch_history_enable", "sphx_batch_history_disable", "sphx_batch_history_read",
+    "sphx_batch_field_map_enable", "sphx_batch_field_map_disable", "sphx_batch_field_map_reset", "sphx_batch_field_map_sample",
+    "sphx_batch_field_map_read",
 ]
 
 _LIB = None
@@ -163,7 +165,8 @@ _STATE = ("pos", "vel", "drho_dt", "mass", "wall_vel")
 
 
 class _Stepped:
-    """What a context and a batch bind alike: the handle's lifecycle, stepping, the flow statistics and the step history.  A
+    """What a context and a batch bind alike: the handle's lifecycle, stepping, the flow statistics, the step history and the
+    field map.  A
     subclass names its symbol stem, the word of its "not enabled on this ..." errors and whether it has many channels: a
     context returns one status / dict / (records, n_dropped) pair, a batch a list with one entry per member."""
     _stem = _where = None
@@ -315,13 +318,68 @@ class _Stepped:
         return [history_dict(*r) for r in recs] if self._many else history_dict(*recs)
 
 
+    # ---- field map (include/sphx.h sections 2e, 2g): the velocity field on a regular grid in x and y, accumulated on the device ----
+    def field_map_enable(self, nx=0, ny=0, every=1, t_from=0.0, with_walls=False):
+        """Sample the state every `every`-th completed step ending at t >= t_from onto nx x ny nodes over [0, DL] x [0, DH],
+        ends included (0: the reference's 2 round(DL/dp), 2 round(DH/dp)), by Shepard interpolation over the fluid
+        particles -- and, with_walls, the wall particles with their wall velocity.  (Re)configures and zeroes the map.  A
+        batch: one config and shape for all members, each sampled on its own clock; n_members * nx * ny must not exceed
+        1 << 25."""
+        cfg = field_map_config(nx, ny, every, t_from, with_walls, n_members=self._channels())
+        shape = field_map_shape(self._params0(), nx, ny)
+        self._call("field_map_enable", C.byref(cfg))
+        self._field_map = shape  # (nx, ny) while the field map is on
+
+    def field_map_disable(self):
+        self._call("field_map_disable")
+        self._field_map = None
+
+    def _field_on(self):
+        return _enabled(self._field_map, "Field", f"the field map is not enabled on this {self._where}")
+
+    def field_map_reset(self):
+        self._field_on()
+        self._call("field_map_reset")
+
+    def field_map_sample(self):
+        """Add one sample of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
+        self._field_on()
+        self._call("field_map_sample")
+
+    def field_map_sums(self):
+        """The raw planes count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2 as [ny, nx] arrays, plus n_samples, t_first, t_last; a
+        batch: one such dict per member, from one read of all members."""
+        nx, ny = self._field_on()
+        m, nn = self._channels(), nx * ny
+        arrs = [np.zeros(m * nn) for _ in FIELD_MAP_PLANES]
+        ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
+        gx, gy = C.c_int(0), C.c_int(0)
+        self._call("field_map_read", C.c_int(nn), C.byref(gx), C.byref(gy), *[ptr(a) for a in arrs],
+                   ns.ctypes.data_as(C.POINTER(C.c_int64)), ptr(t0), ptr(t1))
+        assert (gx.value, gy.value) == (nx, ny), (gx.value, gy.value, nx, ny)
+        out = []
+        for k in range(m):
+            # node (i, k) at i * ny + k: the rows of the [ny, nx] array are the y-levels
+            d = {f: np.ascontiguousarray(a[k * nn:(k + 1) * nn].reshape(nx, ny).T) for f, a in zip(FIELD_MAP_PLANES, arrs)}
+            d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
+            out.append(d)
+        return self._each(out)
+
+    def field_map(self):
+        """The time-averaged map (profile.field_map_means): x [nx], y [ny] and count, weight, u_x, u_y, u_x_std, u_y_std as
+        [ny, nx] arrays (NaN where count == 0), n_samples, t_first, t_last.  A batch: one such dict per member."""
+        p0 = self._params0()
+        sums = self.field_map_sums()
+        return [field_map_means(p0.DL, p0.DH, **s) for s in sums] if self._many else field_map_means(p0.DL, p0.DH, **sums)
+
+
 class Batch(_Stepped):
     """M channels of one geometry stepped by the same launches (sphx_batch, include/sphx.h section 2b).
 
     prms: one parameter set per member (mu, c_f, p0, gravity_g, transport_coeff may differ; the geometry, t_end and the
     launch shape must not).  pos_list / vel_list / drho_list: the members' states, MEX layout as for Context; mass and
-    wall_vel are shared.  transport_coeff may be a scalar or one value per member.  advance / sync, flow_stats_* and
-    history_* are a context's for all members at once: one entry per member."""
+    wall_vel are shared.  transport_coeff may be a scalar or one value per member.  advance / sync, flow_stats_*,
+    history_* and field_map_* are a context's for all members at once: one entry per member."""
     _stem, _where, _many = "sphx_batch_", "batch", True
 
     def __init__(self, prms, n_fluid, n_total, pos_list, vel_list, drho_list, mass, wall_vel, t0=0.0, step0=0,
@@ -352,6 +410,7 @@ class Batch(_Stepped):
         if mass.shape != (nt,) or wall_vel.shape != (nt, 2):
             raise SphxError(SPHX_ERR_ARG, "SPHX:Batch:geometry", "mass / wall_vel: shared arrays of n_total rows expected")
         self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
+        self._field_map = None   # (nx, ny) while the field map is on
         arr = (SphxParams * m)(*self.params)
         check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
@@ -462,47 +521,6 @@ class Context(_Stepped):
         check(lib().sphx_ctx_time_kernel(self._h, name.encode(), C.c_int(reps), C.byref(ms)))
         return ms.value
 
-    # ---- field map (include/sphx.h section 2e): the velocity field on a regular grid in x and y, accumulated on the device ----
-    def field_map_enable(self, nx=0, ny=0, every=1, t_from=0.0, with_walls=False):
-        """Sample the state every `every`-th completed step ending at t >= t_from onto nx x ny nodes over [0, DL] x [0, DH],
-        ends included (0: the reference's 2 round(DL/dp), 2 round(DH/dp)), by Shepard interpolation over the fluid
-        particles -- and, with_walls, the wall particles with their wall velocity.  (Re)configures and zeroes the map."""
-        cfg = field_map_config(nx, ny, every, t_from, with_walls)
-        shape = field_map_shape(self.params, nx, ny)
-        check(lib().sphx_ctx_field_map_enable(self._h, C.byref(cfg)))
-        self._field_map = shape
-
-    def field_map_disable(self):
-        check(lib().sphx_ctx_field_map_disable(self._h))
-        self._field_map = None
-
-    def field_map_reset(self):
-        _field_on(self._field_map)
-        check(lib().sphx_ctx_field_map_reset(self._h))
-
-    def field_map_sample(self):
-        """Add one sample of the current state (what download() returns) now, whatever the gating."""
-        _field_on(self._field_map)
-        check(lib().sphx_ctx_field_map_sample(self._h))
-
-    def field_map_sums(self) -> dict:
-        """The raw planes count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2 as [ny, nx] arrays, plus n_samples, t_first, t_last."""
-        nx, ny = _field_on(self._field_map)
-        arrs = [np.zeros(nx * ny) for _ in FIELD_MAP_PLANES]
-        gx, gy, ns, t0, t1 = C.c_int(0), C.c_int(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
-        check(lib().sphx_ctx_field_map_read(self._h, C.c_int(nx * ny), C.byref(gx), C.byref(gy), *[ptr(a) for a in arrs],
-                                            C.byref(ns), C.byref(t0), C.byref(t1)))
-        assert (gx.value, gy.value) == (nx, ny), (gx.value, gy.value, nx, ny)
-        # node (i, k) at i * ny + k: the rows of the [ny, nx] array are the y-levels
-        out = {k: np.ascontiguousarray(a.reshape(nx, ny).T) for k, a in zip(FIELD_MAP_PLANES, arrs)}
-        out.update(n_samples=ns.value, t_first=t0.value, t_last=t1.value)
-        return out
-
-    def field_map(self) -> dict:
-        """The time-averaged map (profile.field_map_means): x [nx], y [ny] and count, weight, u_x, u_y, u_x_std, u_y_std as
-        [ny, nx] arrays (NaN where count == 0), n_samples, t_first, t_last."""
-        return field_map_means(self.params.DL, self.params.DH, **self.field_map_sums())
-
     def profile_enable(self, on=True):
         check(lib().sphx_ctx_profile_enable(self._h, C.c_int(1 if on else 0)))
 
@@ -521,10 +539,6 @@ def _enabled(state, stem, text):
     if state is None:
         raise SphxError(SPHX_ERR_STATE, f"SPHX:{stem}:disabled", text)
     return state
-
-
-def _field_on(state):
-    return _enabled(state, "Field", "the field map is not enabled on this context")
 
 
 def _is_int(v):
@@ -597,14 +611,15 @@ def field_map_shape(prm, nx=0, ny=0):
     return (int(nx) or 2 * int(np.floor(prm.DL / prm.dp + 0.5)), int(ny) or 2 * int(np.floor(prm.DH / prm.dp + 0.5)))
 
 
-def field_map_config(nx=0, ny=0, every=1, t_from=0.0, with_walls=False) -> SphxFieldMapConfig:
-    """Checked sphx_field_map_config; raises SphxError(SPHX:Field:config) before anything reaches the device."""
+def field_map_config(nx=0, ny=0, every=1, t_from=0.0, with_walls=False, n_members=1) -> SphxFieldMapConfig:
+    """Checked sphx_field_map_config; raises SphxError(SPHX:Field:config) before anything reaches the device.  n_members: the
+    channels that get nx x ny nodes each (a batch's members)."""
     bad = _config_error("Field")
     for name, v in (("nx", nx), ("ny", ny)):
         if not _is_int(v) or v < 0 or v == 1:
             raise bad(f"{name} must be an integer >= 2, or 0 for the reference's shape")
-    if nx * ny > 1 << 25:
-        raise bad("nx * ny must not exceed 1 << 25 nodes")
+    if n_members * nx * ny > 1 << 25:
+        raise bad(("n_members * " if n_members > 1 else "") + "nx * ny must not exceed 1 << 25 nodes")
     every = _check_every(every, bad)
     t_from = _check_t_from(t_from, bad)
     if not (isinstance(with_walls, (bool, np.bool_)) or (_is_int(with_walls) and with_walls in (0, 1))):

@@ -28,7 +28,8 @@ struct sphx_batch {
     int64_t epoch_slot = 0;           // sched.slot when the members' epochs were set
     int64_t n_realign = 0;
     std::vector<int64_t> pending;     // per member: step count the sphx_batch_enqueue_steps calls since the last sync aim for
-    // (flow statistics, sphx_batch_flow_stats_*, and step history, sphx_batch_history_*: mem[0]->fstats / hist, for all M members)
+    // (flow statistics, sphx_batch_flow_stats_*, step history, sphx_batch_history_*, and field map, sphx_batch_field_map_*:
+    //  mem[0]->fstats / hist / fmap, for all M members)
 
     ~sphx_batch()
     {
@@ -238,6 +239,15 @@ History &batch_history(sphx_batch *b, bool need_on)
     History &h = b->mem[0]->hist;
     sampler_check(kHistoryNames, false, h.on, need_on, "batch");
     return h;
+}
+
+// the batch's field map (member 0's, see sphx_ctx::fmap)
+FieldMap &batch_field_map(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    FieldMap &f = b->mem[0]->fmap;
+    sampler_check(kFieldNames, false, f.on, need_on, "batch");
+    return f;
 }
 
 // argument checks (no device): shared fields, refused modes, the kernel forms members of this size would run
@@ -542,6 +552,59 @@ SPHX_EXPORT int sphx_batch_history_read(sphx_batch *b, int capacity, double *rec
     History &h = batch_history(b, true);
     batch_settle(b);  // (the records of everything enqueued)
     h.read(b->stream, capacity, records, n_records, n_dropped, drain != 0);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- velocity-field map of every member (include/sphx.h section 2g) ----
+
+SPHX_EXPORT int sphx_batch_field_map_enable(sphx_batch *b, const sphx_field_map_config *cfg)
+{
+    SPHX_TRY
+    // (the shape comes from the shared geometry; out of device memory: the batch goes on without a map)
+    FieldMap &f = batch_field_map(b, false);
+    field_enable(f, b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_field_map_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    FieldMap &f = batch_field_map(b, false);
+    if (f.on) sampler_off(f, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_field_map_reset(sphx_batch *b)
+{
+    SPHX_TRY
+    FieldMap &f = batch_field_map(b, true);
+    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_field_map_sample(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_field_map(b, true);
+    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
+    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_field_map);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_field_map_read(sphx_batch *b, int capacity, int *nx, int *ny, double *count, double *sum_w, double *sum_ux,
+                                          double *sum_uy, double *sum_ux2, double *sum_uy2, int64_t *n_samples, double *t_first,
+                                          double *t_last)
+{
+    SPHX_TRY
+    const FieldMap &f = batch_field_map(b, true);
+    field_read(f, b->stream, [b] { batch_settle(b); }, capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples,
+               t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -1,5 +1,5 @@
-// sphx_field_map.hpp -- velocity-field maps of a resident context (include/sphx.h section 2e): a slot sampler
-// (sphx_slot_sample.hpp) that interpolates the velocity of the state the step left onto a regular nx x ny grid of nodes
+// sphx_field_map.hpp -- velocity-field maps of a resident context (include/sphx.h section 2e) and of every member of a
+// batch (section 2g, k_field_map_b): a slot sampler (sphx_slot_sample.hpp) that interpolates the velocity of the state the step left onto a regular nx x ny grid of nodes
 // (both ends included in x and y, the shape of panel (b) of SPH_Poiseuille_postprocess.m:184-201 by default) and adds
 // the sample to running sums per node.
 //
@@ -24,7 +24,7 @@
 // Determinism: every node is owned by one thread, which adds the candidates in the sweep's column and slot order and
 // updates the six sums of its node with plain loads and stores: no atomics, no ticket.  Two identical runs give identical
 // bits; another layout of the particles (re-binning phase, host chunking) changes the summation order only.  The head is
-// written by thread 0 of workgroup 0 alone.
+// written by thread 0 of workgroup 0 alone (of a batch: of workgroup 0 of the member's grid row).
 #pragma once
 #include "../../include/sphx.h"
 #include "sphx_slot_sample.hpp"
@@ -42,8 +42,8 @@ struct FieldMapHead {
 };
 
 struct FieldMapArgs {
-    double *planes;        // [kFieldPlanes][nx * ny], node (i, k) at i * ny + k
-    FieldMapHead *head;
+    double *planes;        // [kFieldPlanes][nx * ny], node (i, k) at i * ny + k (of a batch: member 0's, member m's block behind)
+    FieldMapHead *head;    // (of a batch: [M])
     double step_x, step_y; // DL / (nx - 1), DH / (ny - 1): the step of numpy's linspace
     double dp2;            // dp^2: sum_w accumulates S0 dp^2
     double t_from;
@@ -97,10 +97,10 @@ __device__ __forceinline__ void field_columns(const Grid &g, const KernelConst &
     }
 }
 
-// q: parity of the step slot this launch closes; s is the state the step left (pos, vel and the cell ranges of the layout it
-// is stored in).
-__global__ __launch_bounds__(kFieldBlock) void k_field_map(const Clock *clk, int q, Grid g, Phys ph, FluidSet s, Walls w,
-                                                           FieldMapArgs a)
+// The sample of one channel closing the step slot of parity q, on clock clk, by the gridDim.x workgroups of a grid row; s is the
+// state the step left (pos, vel and the cell ranges of the layout it is stored in); a's planes and head are that channel's own.
+__device__ __forceinline__ void field_map_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
+                                               const Walls &w, const FieldMapArgs &a)
 {
     if (!sample_due(clk, q, a.every, a.t_from)) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) note_sample(a.head, clk->t);  // the head, by one thread: plain vector stores
@@ -133,6 +133,27 @@ __global__ __launch_bounds__(kFieldBlock) void k_field_map(const Clock *clk, int
     p[3 * nn] += uy;
     p[4 * nn] += ux * ux;
     p[5 * nn] += uy * uy;
+}
+
+// q: parity of the step slot this launch closes
+__global__ __launch_bounds__(kFieldBlock) void k_field_map(const Clock *clk, int q, Grid g, Phys ph, FluidSet s, Walls w,
+                                                           FieldMapArgs a)
+{
+    field_map_body(clk, q, g, ph, s, w, a);
+}
+
+// batch (sphx_batch_field_map_*): member m = blockIdx.y samples its own state (member_set of the view, which is member 0's) on
+// its own clock and parameters into its own six planes (m * kFieldPlanes * nx * ny) and its own head; Grid and Walls are
+// shared.  gridDim.x is the workgroup count of a context's map of this shape, every node is owned by the same thread of the
+// same workgroup of the row and adds its candidates in the same order: a member's planes are bit for bit a standalone
+// context's.  A member whose gate is closed returns before it touches its head or its planes.
+__global__ __launch_bounds__(kFieldBlock) void k_field_map_b(Members mb, int q, Grid g, FluidSet s, Walls w, FieldMapArgs a)
+{
+    const int m = (int)blockIdx.y;
+    const Phys ph = mb.ph[m];
+    a.planes += (size_t)m * kFieldPlanes * (size_t)a.nx * (size_t)a.ny;
+    a.head += m;
+    field_map_body(mb.clk + m, q, g, ph, member_set(mb, m, s), w, a);
 }
 
 }  // namespace sphx

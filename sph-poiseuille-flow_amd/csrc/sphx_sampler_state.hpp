@@ -50,17 +50,23 @@ struct History {
     void read(hipStream_t st, int capacity, double *records, int *n_records, int64_t *n_dropped, bool drain);
 };
 
-// Velocity-field map (sphx_ctx_field_map_*, sphx_field_map.hpp)
+// Velocity-field map (sphx_ctx_field_map_*, sphx_batch_field_map_*; sphx_field_map.hpp) of a context or of the M members of a
+// batch: one configuration and shape, member m's six planes at m * block(), its head at m.
 struct FieldMap {
     bool on = false;
+    int members = 1;
     sphx_field_map_config cfg{};
     int nx = 0, ny = 0;  // the shape in force (cfg.nx / cfg.ny = 0: the reference's)
     DevBuf<double> planes;
     DevBuf<FieldMapHead> head;
 
     size_t nodes() const { return (size_t)nx * (size_t)ny; }
+    size_t block() const { return nodes() * kFieldPlanes; }  // the planes of one member
+    void check(const sphx_params &prm, const sphx_field_map_config *cfg, int M);
+    void alloc(const FieldMap &checked, int M);
     void zero(hipStream_t st) { planes.zero(st); head.zero(st); }
     void release() { planes.release(); head.release(); }
+    void read(hipStream_t st, int stride, double *const out[kFieldPlanes], int64_t *n_samples, double *t_first, double *t_last) const;
 };
 
 // the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map (sphx_samplers.hpp)

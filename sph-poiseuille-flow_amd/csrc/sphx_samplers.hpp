@@ -1,6 +1,6 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
-// translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d) and
-// the velocity-field map (2e).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
+// and the velocity-field map (2e; 2g).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp and sphx_field_map.hpp.  What the three share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -145,11 +145,10 @@ void launch_history(sphx_ctx *c, int q, const FluidSet &s, bool rebuild)
                  per_member(c->phys), s, c->tmp_par[c->fuse_ea ? q : 0], c->walls, a);
 }
 
-// k_field_map on state s (pos, vel and the cell ranges of the layout it is stored in) into c->fmap
+// k_field_map on state s (pos, vel and the cell ranges of the layout it is stored in) -- of a batch: member 0's -- into c->fmap
 void launch_field_map(sphx_ctx *c, int q, const FluidSet &s, int every)
 {
     const FieldMap &f = c->fmap;
-    single_form_only(c, "k_field_map");
     FieldMapArgs a{};
     a.planes = f.planes.get(); a.head = f.head.get();
     a.step_x = c->prm.DL / (f.nx - 1); a.step_y = c->prm.DH / (f.ny - 1);
@@ -160,9 +159,10 @@ void launch_field_map(sphx_ctx *c, int q, const FluidSet &s, int every)
     a.n_tiles = (int)div_up((size_t)f.nx, (size_t)kFieldTile) * a.tiles_y;
     a.every = every;
     a.with_walls = f.cfg.with_walls && c->nw > 0 ? 1 : 0;
+    // workgroups of one channel's sample
     const unsigned blocks = div_up((size_t)a.n_tiles, (size_t)(kFieldBlock / 64));
-    launch(c, "k_field_map", k_field_map, dim3(blocks), dim3(kFieldBlock), (const Clock *)c->clock.get(), q, c->grid, c->phys, s,
-           c->walls, a);
+    launch_forms(c, "k_field_map", Forms{k_field_map, k_field_map_b}, blocks, kFieldBlock, 0, q, c->grid, per_member(c->phys), s,
+                 c->walls, a);
 }
 
 }  // namespace
@@ -407,10 +407,9 @@ SPHX_EXPORT int sphx_ctx_history_read(sphx_ctx *c, int capacity, double *records
 
 // ---- velocity-field map ----
 
-SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_config *cfg)
+// every check of a configuration for M channels with parameters prm (cfg and the shape in force); SPHX:Field:config errors
+void FieldMap::check(const sphx_params &prm, const sphx_field_map_config *cfg, int M)
 {
-    SPHX_TRY
-    FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, false);
     require(cfg != nullptr, "SPHX:Field:config", "config must not be NULL");
     require(cfg->nx == 0 || cfg->nx >= 2, "SPHX:Field:config", "nx must be 0 (the reference's shape) or >= 2");
     require(cfg->ny == 0 || cfg->ny >= 2, "SPHX:Field:config", "ny must be 0 (the reference's shape) or >= 2");
@@ -418,17 +417,77 @@ SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_conf
     require(!std::isnan(cfg->t_from), "SPHX:Field:config", "t_from must not be NaN");
     require(cfg->with_walls == 0 || cfg->with_walls == 1, "SPHX:Field:config", "with_walls must be 0 or 1");
     // 0: the grid of SPH_Poiseuille_postprocess.m:185-186
-    const double nx = cfg->nx > 0 ? (double)cfg->nx : 2.0 * std::floor(c->prm.DL / c->prm.dp + 0.5);
-    const double ny = cfg->ny > 0 ? (double)cfg->ny : 2.0 * std::floor(c->prm.DH / c->prm.dp + 0.5);
-    require(nx >= 2.0 && ny >= 2.0, "SPHX:Field:config", "the reference's shape has fewer than 2 nodes along x or y: give nx and ny");
-    require(nx * ny <= (double)kFieldMaxNodes, "SPHX:Field:config", "nx * ny must not exceed 1 << 25 nodes");
-    sampler_on(f, kFieldNames, c->sched, c->stream, [&] {
-        f.nx = (int)nx;
-        f.ny = (int)ny;
-        f.planes.alloc(f.nodes() * kFieldPlanes);
-        f.head.alloc(1);
-        f.cfg = *cfg;
-    });
+    const double gx = cfg->nx > 0 ? (double)cfg->nx : 2.0 * std::floor(prm.DL / prm.dp + 0.5);
+    const double gy = cfg->ny > 0 ? (double)cfg->ny : 2.0 * std::floor(prm.DH / prm.dp + 0.5);
+    require(gx >= 2.0 && gy >= 2.0, "SPHX:Field:config", "the reference's shape has fewer than 2 nodes along x or y: give nx and ny");
+    if (!((double)M * gx * gy <= (double)kFieldMaxNodes))
+        throw Error(SPHX_ERR_ARG, "SPHX:Field:config", std::string(M > 1 ? "n_members * " : "") + "nx * ny must not exceed 1 << 25 nodes");
+    this->cfg = *cfg;
+    nx = (int)gx;
+    ny = (int)gy;
+}
+
+// the checked configuration and shape, and planes and heads for M members
+void FieldMap::alloc(const FieldMap &checked, int M)
+{
+    cfg = checked.cfg;
+    nx = checked.nx;
+    ny = checked.ny;
+    members = M;
+    planes.alloc(block() * M);
+    head.alloc(M);
+}
+
+// Every member's planes (into out[plane][m * stride + node], where out[plane] is given) and heads (n_samples[m], t_first[m],
+// t_last[m], where given)
+void FieldMap::read(hipStream_t st, int stride, double *const out[kFieldPlanes], int64_t *n_samples, double *t_first,
+                    double *t_last) const
+{
+    const int M = members;
+    std::vector<FieldMapHead> h(M);
+    for (int j = 0; j < kFieldPlanes; ++j)
+        if (out[j])
+            for (int m = 0; m < M; ++m)
+                SPHX_HIP(hipMemcpyAsync(out[j] + (size_t)m * stride, planes.get() + (size_t)m * block() + (size_t)j * nodes(),
+                                        nodes() * sizeof(double), hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(FieldMapHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    for (int m = 0; m < M; ++m)
+        read_head(h[m], n_samples ? n_samples + m : nullptr, t_first ? t_first + m : nullptr, t_last ? t_last + m : nullptr);
+}
+
+namespace {
+
+// enable for M members of channels with parameters prm on schedule s: every check of cfg first
+void field_enable(FieldMap &f, const sphx_params &prm, const sphx_field_map_config *cfg, int M, Schedule &s, hipStream_t st)
+{
+    FieldMap checked;
+    checked.check(prm, cfg, M);
+    sampler_on(f, kFieldNames, s, st, [&] { f.alloc(checked, M); });
+}
+
+// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
+template <typename Settle>
+void field_read(const FieldMap &f, hipStream_t st, Settle &&settle, int capacity, int *nx, int *ny, double *count, double *sum_w,
+                double *sum_ux, double *sum_uy, double *sum_ux2, double *sum_uy2, int64_t *n_samples, double *t_first, double *t_last)
+{
+    double *const out[kFieldPlanes] = {count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2};
+    bool any = false;
+    for (double *o : out) any = any || o != nullptr;
+    require(!any || (size_t)std::max(capacity, 0) >= f.nodes(), "SPHX:Field:capacity", "capacity is smaller than nx * ny");
+    settle();  // (the samples of everything enqueued)
+    f.read(st, capacity, out, n_samples, t_first, t_last);
+    if (nx) *nx = f.nx;
+    if (ny) *ny = f.ny;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_config *cfg)
+{
+    SPHX_TRY
+    FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, false);
+    field_enable(f, c->prm, cfg, 1, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -467,21 +526,8 @@ SPHX_EXPORT int sphx_ctx_field_map_read(sphx_ctx *c, int capacity, int *nx, int 
 {
     SPHX_TRY
     const FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, true);
-    double *const out[kFieldPlanes] = {count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2};
-    bool any = false;
-    for (double *o : out) any = any || o != nullptr;
-    require(!any || (size_t)std::max(capacity, 0) >= f.nodes(), "SPHX:Field:capacity", "capacity is smaller than nx * ny");
-    settle_owed(c);  // (the samples of everything enqueued)
-    FieldMapHead head{};
-    for (int j = 0; j < kFieldPlanes; ++j)
-        if (out[j])
-            SPHX_HIP(hipMemcpyAsync(out[j], f.planes.get() + (size_t)j * f.nodes(), f.nodes() * sizeof(double), hipMemcpyDeviceToHost,
-                                    c->stream));
-    SPHX_HIP(hipMemcpyAsync(&head, f.head.get(), sizeof(head), hipMemcpyDeviceToHost, c->stream));
-    SPHX_HIP(hipStreamSynchronize(c->stream));
-    if (nx) *nx = f.nx;
-    if (ny) *ny = f.ny;
-    read_head(head, n_samples, t_first, t_last);
+    field_read(f, c->stream, [c] { settle_owed(c); }, capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples,
+               t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }

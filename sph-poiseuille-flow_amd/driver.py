@@ -19,7 +19,8 @@ from . import capi
 from .geometry import init_particles
 from .mex_surface import sph_neighbor_search_mex, sph_physics_shell_mex
 from . import restart
-from .profile import compute_mid_channel_profile, final_profile, flow_stats_profile, l2_error, n_profile_bins, pool_flow_stats
+from .profile import (compute_mid_channel_profile, field_map_means, final_profile, flow_stats_profile, l2_error, n_profile_bins, pool_field_maps,
+                      pool_flow_stats)
 
 
 @dataclass
@@ -46,7 +47,8 @@ class RunResult:
     n_inner: int = 1  # inner sub-steps per counted step (> 1 only with the opt-in dual-rate loop)
     time_avg: dict = None  # run(..., average_from=...): device-side time-averaged profiles and figures (see time_average)
     history: dict = None  # run(..., history_every=...): the device-side step history of the whole run (capi.Context.history)
-    field_avg: dict = None  # run(..., field_from=...): the device-side time-averaged velocity map (capi.Context.field_map)
+    field_avg: dict = None  # run(..., field_from=...): the device-side time-averaged velocity map (capi.Context.field_map); a
+                            # member of run_ensemble / run_sweep(..., field_from=...): its own (capi.Batch.field_map)
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -361,7 +363,7 @@ def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
                        profile_times=list(times), tau_bottom=tau_b, tau_top=tau_t, grid_policy=dict(policy), **extra)
 
 
-def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None):
+def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None):
     """The batch run behind run_batch, run_ensemble and run_sweep (`name`, for the refusals): check and default the inputs,
     open the batch with the launch keywords `launch`, enable what was asked for, advance output point by output point, build
     every member's RunResult.
@@ -370,7 +372,10 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                  max(dp, h)); every member gets a time_avg
       history    (history_every, history_capacity): the step history, drained at every output point; every member gets a
                  history, and one that lost records raises RuntimeError
-    -> the members, the wall seconds, the grid policy, and with average the raw sums (whole, mid) of all members."""
+      field      (field_from, field_every, field_shape, field_walls): the velocity map of include/sphx.h section 2g, enabled
+                 before the first advance and read once at the end; every member gets a field_avg
+    -> the members, the wall seconds, the grid policy, with average the raw sums (whole, mid) of all members, and with field the
+    raw planes of all members."""
     prms = list(prms)
     if not prms:
         raise ValueError(f"{name} needs at least one parameter set")
@@ -394,6 +399,9 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
             b.history_enable(every=history[0], capacity=history[1])
         if average:
             b.flow_stats_enable(n_bins=n_bins, every=average[1], t_from=float(average[0]), bands=[(mid_x, mid_hw)])
+        if field:
+            fnx, fny = field[2] if field[2] is not None else (0, 0)
+            b.field_map_enable(nx=fnx, ny=fny, every=field[1], t_from=field[0], with_walls=field[3])
         t = 0.0
         st = None
         while t < p0.t_end - 1e-12:
@@ -419,6 +427,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         wall = time.perf_counter() - t0
         policy = _batch_policy(b)
         sums = (b.flow_stats_sums(0), b.flow_stats_sums(1)) if average else None
+        planes = b.field_map_sums() if field else None
         members = []
         for m, prm in enumerate(prms):
             extra = {}
@@ -428,12 +437,19 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                 extra.update(time_avg=time_average(prm, *[flow_stats_profile(prm.DH, **band[m]) for band in sums]))
             if history:
                 extra.update(history=_concat_history(chunks[m]))
+            if field:
+                extra.update(field_avg=field_map_means(prm.DL, prm.DH, **planes[m]))
             members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra))
-    return members, wall, policy, sums
+    return members, wall, policy, sums, planes
+
+
+def _field_request(field_from, field_every, field_shape, field_walls):
+    """the `field` of _run_batch: None without field_from"""
+    return None if field_from is None else (field_from, field_every, field_shape, field_walls)
 
 
 def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,
-              restart_path=None, postprocess_path=None, average_from=None, log=None, history_every=None):
+              restart_path=None, postprocess_path=None, average_from=None, log=None, history_every=None, field_from=None):
     """run() for M channels of one geometry stepped together as one batch (capi.Batch, include/sphx.h section 2b): a
     parameter sweep (mu, c_f, p0, gravity_g, transport_coeff) or an ensemble of realisations (parts_list).  Every member
     reaches the same output points (output_interval and t_end are shared and must agree) and gets a RunResult of its own:
@@ -447,54 +463,64 @@ def run_batch(prms, parts_list=None, engine="resident", lanes_per_particle=0, st
         raise ValueError("run_batch does no time averaging (run_ensemble and run_sweep do, for every member)")
     if history_every is not None:
         raise ValueError("run_batch records no step history (run_sweep does, for every member)")
+    if field_from is not None:
+        raise ValueError("run_batch accumulates no field map (run_ensemble and run_sweep do, for every member)")
     return _run_batch("run_batch", prms, parts_list, dict(lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
                                                           rebuild_every=rebuild_every), log, snapshots=True)[0]
 
 
 @dataclass
 class EnsembleResult:
-    members: list        # one RunResult per member: final profile and L2, tau, time_avg (time_average of its own sums)
+    members: list        # one RunResult per member: final profile and L2, tau, time_avg (time_average of its own sums),
+                         # field_avg (with field_from)
     pooled: dict         # members sharing mu, c_f, p0, gravity_g, transport_coeff: time_average of the pooled sums plus
                          # u_mean_se, L2_members, L2_mean, L2_std; None for a parameter sweep
     wall_seconds: float
     grid_policy: dict = field(default_factory=dict)
+    pooled_field: dict = None  # with field_from, under the condition of `pooled`: profile.pool_field_maps of the members' planes
 
 
 _PHYSICS = ("mu", "c_f", "p0", "gravity_g", "transport_coeff")
 
 
 def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_per_particle=0, steps_per_graph=0,
-                 rebuild_every=0, log=None, history_every=None):
+                 rebuild_every=0, log=None, history_every=None, field_from=None, field_every=1, field_shape=None,
+                 field_walls=False):
     """Time-averaged profiles of M channels of one geometry stepped as one batch (capi.Batch), averaged on the device
     inside the step loop (include/sphx.h section 2c) as run(average_from=...) does for one channel: every
     average_every-th step ending at t >= average_from, whole channel and the mid-channel band (DL/2, max(dp, h)).  The
     members advance output point by output point as in run_batch, so their trajectories are run_batch's; nothing is
     downloaded before the end.  parts_list: the members' initial states (e.g. geometry.perturbed_particles), default the
-    lattice.  Returns an EnsembleResult."""
+    lattice.  field_from: every member's velocity map as well (include/sphx.h section 2g), with the keywords of run(): every
+    member gets a field_avg, and members that share their physics a pooled_field.  Returns an EnsembleResult."""
     prms = list(prms)
     if history_every is not None:
         raise ValueError("run_ensemble records no step history (run_sweep does, for every member)")
     if prms and (average_from is None or np.isnan(float(average_from))):  # (no parameter set: refused first, below)
         raise ValueError("run_ensemble needs average_from (the start of the averaging window)")
-    members, wall, policy, (whole, mid) = _run_batch(
+    members, wall, policy, (whole, mid), planes = _run_batch(
         "run_ensemble", prms, parts_list, dict(lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
-                                               rebuild_every=rebuild_every), log, average=(average_from, average_every))
+                                               rebuild_every=rebuild_every), log, average=(average_from, average_every),
+        field=_field_request(field_from, field_every, field_shape, field_walls))
     p0, M = prms[0], len(prms)
-    pooled = None
+    pooled = pooled_field = None
     if all(getattr(p, k) == getattr(p0, k) for p in prms for k in _PHYSICS):
         pw, pm = pool_flow_stats(p0.DH, whole), pool_flow_stats(p0.DH, mid)
         pooled = time_average(p0, pw, pm)
         L2s = [r.time_avg["L2"] for r in members]
         pooled.update(u_mean_se=pw["u_mean_se"], L2_members=L2s, L2_mean=float(np.mean(L2s)),
                       L2_std=float(np.std(L2s, ddof=1)) if M > 1 else float("nan"))
-    return EnsembleResult(members=members, pooled=pooled, wall_seconds=wall, grid_policy=policy)
+        if planes is not None:
+            pooled_field = pool_field_maps(p0.DL, p0.DH, planes)
+    return EnsembleResult(members=members, pooled=pooled, wall_seconds=wall, grid_policy=policy, pooled_field=pooled_field)
 
 
 @dataclass
 class SweepResult:
     members: list        # one RunResult per member: final profile and L2, tau, history (the whole run's series), time_avg
-                         # (with average_from)
-    table: dict          # [M] arrays: the _PHYSICS values, steps, every figure of history_figures(), n_dropped
+                         # (with average_from), field_avg (with field_from)
+    table: dict          # [M] arrays: the _PHYSICS values, steps, every figure of history_figures(), n_dropped; with
+                         # field_from also field_L2, field_x_spread, field_ix, field_uy_rms (field_figures of field_avg)
     wall_seconds: float
     grid_policy: dict = field(default_factory=dict)
 
@@ -512,8 +538,19 @@ def sweep_table(prms, histories, steps, history_from=0.0, settle_tol=0.05):
     return table
 
 
+_FIELD_COLUMNS = (("field_L2", "L2"), ("field_x_spread", "x_spread"), ("field_ix", "ix"), ("field_uy_rms", "uy_rms"))
+
+
+def field_table(prms, field_avgs):
+    """The field-map columns of a sweep's table, one [M] array each: field_L2, field_x_spread, field_ix, field_uy_rms =
+    L2, x_spread, ix, uy_rms of field_figures(prm_m, field_avg_m)."""
+    figs = [field_figures(p, f) for p, f in zip(prms, field_avgs)]
+    return {col: np.array([f[k] for f in figs]) for col, k in _FIELD_COLUMNS}
+
+
 def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0, settle_tol=0.05, average_from=None,
-              average_every=1, parts_list=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0, log=None):
+              average_every=1, parts_list=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0, log=None,
+              field_from=None, field_every=1, field_shape=None, field_walls=False):
     """A parameter sweep: M channels of one geometry that differ in mu, c_f, p0, gravity_g, transport_coeff, stepped as one
     batch (capi.Batch) with every member's step history recorded on the device, inside the step loop (include/sphx.h
     section 2f) as run(history_every=...) does for one channel.  The members advance output point by output point as in
@@ -522,12 +559,17 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     the end.  history_from: the start of the window the table's means are taken over (every history_every-th step of the
     whole run is recorded); settle_tol: the band of t_settled (history_figures).  average_from: the batch's flow
     statistics as well, as in run_ensemble -- every average_every-th step ending at t >= average_from -- and each member
-    gets a time_avg.  A member that lost records to a full buffer raises RuntimeError, which names the member and the
+    gets a time_avg.  field_from: every member's velocity map as well (include/sphx.h section 2g), with the keywords of
+    run(): each member gets a field_avg and the table the columns field_L2, field_x_spread, field_ix, field_uy_rms of
+    field_figures(prm_m, field_avg_m).  A member that lost records to a full buffer raises RuntimeError, which names the member and the
     capacity the output interval needed.  Returns a SweepResult."""
     prms = list(prms)
-    members, wall, policy, _ = _run_batch(
+    members, wall, policy, _, planes = _run_batch(
         "run_sweep", prms, parts_list, dict(lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
                                             rebuild_every=rebuild_every), log, history=(history_every, history_capacity),
-        average=None if average_from is None else (average_from, average_every))
+        average=None if average_from is None else (average_from, average_every),
+        field=_field_request(field_from, field_every, field_shape, field_walls))
     table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
+    if planes is not None:
+        table.update(field_table(prms, [r.field_avg for r in members]))
     return SweepResult(members=members, table=table, wall_seconds=wall, grid_policy=policy)

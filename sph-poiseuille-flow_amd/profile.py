@@ -5,6 +5,7 @@ final_profile: SPH_Poiseuille.m:617-623.  l2_error: SPH_Poiseuille_postprocess.m
 flow_stats_profile: the sums of the device's flow statistics (include/sphx.h section 2a) as a profile.
 pool_flow_stats: the sums of several channels (the members of a batch, section 2c) as one ensemble-averaged profile.
 shepard_field: one sample of the device's field map (include/sphx.h section 2e) in numpy; field_map_means: its sums as a map.
+pool_field_maps: the planes of several channels (the members of a batch, section 2g) as one ensemble-averaged map.
 """
 from __future__ import annotations
 
@@ -101,11 +102,7 @@ def pool_flow_stats(DH, sums_list):
     for member in per[1:]:
         for k in range(len(_SUMS)):
             total[k] = total[k] + member[k]
-    n_samples = sum(int(s.get("n_samples", 0)) for s in sums_list)
-    t_first = [float(s.get("t_first", np.nan)) for s in sums_list]
-    t_last = [float(s.get("t_last", np.nan)) for s in sums_list]
-    t_first = min((t for t in t_first if not np.isnan(t)), default=np.nan)
-    t_last = max((t for t in t_last if not np.isnan(t)), default=np.nan)
+    n_samples, t_first, t_last = _window(sums_list)
     out = flow_stats_profile(DH, *total, n_samples=n_samples, t_first=t_first, t_last=t_last)
     M = len(per)
     se = np.full(len(total[0]), np.nan)
@@ -115,6 +112,15 @@ def pool_flow_stats(DH, sums_list):
         se[ok] = np.std(means[:, ok], axis=0, ddof=1) / np.sqrt(M)
     out.update(u_mean_se=se, n_members=M)
     return out
+
+
+def _window(sums_list):
+    """n_samples in all, and the earliest t_first / latest t_last, of several channels' sums"""
+    n_samples = sum(int(s.get("n_samples", 0)) for s in sums_list)
+    t_first = [float(s.get("t_first", np.nan)) for s in sums_list]
+    t_last = [float(s.get("t_last", np.nan)) for s in sums_list]
+    return (n_samples, min((t for t in t_first if not np.isnan(t)), default=np.nan),
+            max((t for t in t_last if not np.isnan(t)), default=np.nan))
 
 
 def field_map_nodes(DL, DH, nx, ny):
@@ -186,3 +192,30 @@ def field_map_means(DL, DH, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_sa
     weight[empty] = np.nan
     return dict(x=xs, y=ys, count=N, weight=weight, u_x=u_x, u_y=u_y, u_x_std=u_x_std, u_y_std=u_y_std,
                 n_samples=int(n_samples), t_first=float(t_first), t_last=float(t_last))
+
+
+def pool_field_maps(DL, DH, sums_list):
+    """Ensemble- and time-averaged map of several channels' field-map planes (dicts as capi.Batch.field_map_sums returns, one
+    per member, all of one shape): the six planes are added in member order and turned into field_map_means of the total;
+    n_samples is the total over the members, t_first / t_last the earliest / latest sample.  Adds
+      u_x_se      per node, the standard error across members of the members' own time-averaged u_x,
+                  std(ddof=1) / sqrt(M); NaN for M < 2 and at nodes some member never sampled
+      n_members   M"""
+    sums_list = list(sums_list)
+    if not sums_list:
+        raise ValueError("pool_field_maps needs the planes of at least one member")
+    per = [[np.asarray(s[k], dtype=np.float64) for k in FIELD_MAP_PLANES] for s in sums_list]
+    total = [a.copy() for a in per[0]]
+    for member in per[1:]:
+        for k in range(len(FIELD_MAP_PLANES)):
+            total[k] = total[k] + member[k]
+    n_samples, t_first, t_last = _window(sums_list)
+    out = field_map_means(DL, DH, *total, n_samples=n_samples, t_first=t_first, t_last=t_last)
+    M = len(per)
+    se = np.full(total[0].shape, np.nan)
+    if M >= 2:
+        means = np.stack([field_map_means(DL, DH, *member)["u_x"] for member in per])
+        ok = ~np.any(np.isnan(means), axis=0)
+        se[ok] = np.std(means[:, ok], axis=0, ddof=1) / np.sqrt(M)
+    out.update(u_x_se=se, n_members=M)
+    return out
