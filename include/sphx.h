@@ -636,6 +636,43 @@ int sphx_slab_sync(sphx_ctx *ctx, sphx_status *status);
 int sphx_slab_snapshot(sphx_ctx *ctx, int capacity, int *n, double *x, double *y, double *vx,
                        double *vy, double *drho, int *id, int *owned);
 
+/* ------------------------------------------------------------------------------------------------
+ * 3a. Samplers of a slab ring: the flow statistics of section 2a and the step history of section 2d for the slabs of
+ *    the library's own loops (sphx_slab_run, sphx_slab_group_run), so that a ring reports its time-averaged profile
+ *    and the settling of its wall shear without a snapshot per sample.  The config structs, their checks, the layouts
+ *    and the SPHX:Stats:* / SPHX:History:* identifiers are those of sections 2a / 2d; sphx_ctx_flow_stats_*,
+ *    sphx_ctx_history_* and sphx_ctx_field_map_* keep refusing a slab (SPHX:Stats:slab, SPHX:History:slab,
+ *    SPHX:Field:slab).
+ *    A slab samples, at the end of a step, the fluid particles it OWNS (those sphx_slab_snapshot marks owned), never its
+ *    halo copies, and what a read returns are the slab's PARTIAL sums: the ring's value is the sum over the ranks.
+ *      flow statistics: every array elementwise, count included; n_samples, t_first and t_last are the same on every
+ *        rank.  Band membership goes by x mod DL, whatever frame a slab keeps x in.  The sums are exact integers per
+ *        sample, so the pooled sums do not depend on how the channel is cut.
+ *      history: fields 0..3 of a record (step, t, dt, vmax) come from the clock and are the same on every rank;
+ *        fields 4..7 are additive: tau_bottom / tau_top = -(the slab's wall-force sum) / DL, kinetic_energy = the
+ *        slab's sum, u_bulk = (the slab's sum of u_x) / the GLOBAL n_fluid.  The ring's record is fields 0..3 of any
+ *        rank and the sum over the ranks of fields 4..7.  capacity and n_dropped are per slab; every slab records
+ *        the same steps.
+ *    Every call refuses a context that is not a slab with SPHX:Slab:ctx and a slab created for the caller-driven
+ *    protocol (rebuild_every == 1) with SPHX:Slab:protocol.  A read, reset or disable waits for the slab's stream(s)
+ *    itself, whether sphx_slab_sync has been called for the enqueued steps or not.  Enabling or disabling a sampler
+ *    drops a step graph prepared with sphx_slab_graph_prepare (on any slab of an in-process ring: the ring's): the
+ *    loops run eagerly until it is prepared again, and the new graph carries the launches.  There is no "sample now"
+ *    call and no field map on slabs.
+ * ---------------------------------------------------------------------------------------------- */
+int sphx_slab_flow_stats_enable(sphx_ctx *ctx, const sphx_flow_stats_config *cfg);
+int sphx_slab_flow_stats_disable(sphx_ctx *ctx);
+/* Clears the sums and the sample count (SPHX:Stats:disabled while the sampler is off, as for the read). */
+int sphx_slab_flow_stats_reset(sphx_ctx *ctx);
+/* The slab's partial sums of one band; arguments as sphx_ctx_flow_stats_read. */
+int sphx_slab_flow_stats_read(sphx_ctx *ctx, int band, int capacity, int *n_bins, double *count, double *sum_ux,
+                              double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples, double *t_first,
+                              double *t_last);
+int sphx_slab_history_enable(sphx_ctx *ctx, const sphx_history_config *cfg);
+int sphx_slab_history_disable(sphx_ctx *ctx);
+/* The slab's records (fields 4..7: its partials); arguments as sphx_ctx_history_read (SPHX:History:disabled while off). */
+int sphx_slab_history_read(sphx_ctx *ctx, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,8 @@ EXPORTS = [
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
+    "sphx_slab_flow_stats_enable", "sphx_slab_flow_stats_disable", "sphx_slab_flow_stats_reset", "sphx_slab_flow_stats_read",
+    "sphx_slab_history_enable", "sphx_slab_history_disable", "sphx_slab_history_read",
     "sphx_batch_create", "sphx_batch_destroy", "sphx_batch_advance", "sphx_batch_enqueue_steps", "sphx_batch_sync",
     "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
     "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",
@@ -164,11 +166,10 @@ def _per_member(v, m, name):
 _STATE = ("pos", "vel", "drho_dt", "mass", "wall_vel")
 
 
-class _Stepped:
-    """What a context and a batch bind alike: the handle's lifecycle, stepping, the flow statistics, the step history and the
-    field map.  A
+class _Sampled:
+    """What a context, a batch and a slab of a ring bind alike: the flow statistics' sums and the step history's records.  A
     subclass names its symbol stem, the word of its "not enabled on this ..." errors and whether it has many channels: a
-    context returns one status / dict / (records, n_dropped) pair, a batch a list with one entry per member."""
+    context or a slab returns one dict / (records, n_dropped) pair, a batch a list with one entry per member."""
     _stem = _where = None
     _many = False
 
@@ -183,6 +184,82 @@ class _Stepped:
 
     def _each(self, per_channel):
         return per_channel if self._many else per_channel[0]
+
+    # ---- flow statistics (include/sphx.h sections 2a, 2c): time-averaged velocity profiles accumulated on the device ----
+    def flow_stats_enable(self, n_bins=0, every=1, t_from=0.0, bands=()):
+        """Sample the state every `every`-th completed step ending at t >= t_from into n_bins y-bins (0: the reference's
+        max(20, round(DH/dp))) of the whole channel (band 0) and of up to two x-bands [(x_centre, half_width), ...]
+        (band 1, 2).  (Re)configures and zeroes the sums.  A batch: one config for all members, each sampled on its own clock."""
+        cfg = flow_stats_config(n_bins, every, t_from, bands)
+        p0 = self._params0()
+        n = int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5)))
+        self._call("flow_stats_enable", C.byref(cfg))
+        self._flow_stats = (n, int(cfg.n_bands) + 1)  # (n_bins, n_bands incl. band 0) while the flow statistics are on
+
+    def flow_stats_disable(self):
+        self._call("flow_stats_disable")
+        self._flow_stats = None
+
+    def _stats_on(self):
+        return _enabled(self._flow_stats, "Stats", f"flow statistics are not enabled on this {self._where}")
+
+    def flow_stats_reset(self):
+        self._stats_on()
+        self._call("flow_stats_reset")
+
+    def flow_stats_sums(self, band=0):
+        """The raw sums of one band: count, sum_ux, sum_ux2, sum_uy, sum_uy2 [n_bins], n_samples, t_first, t_last; a batch: one
+        such dict per member, from one read of all members."""
+        n_bins, n_bands = self._stats_on()
+        if not _is_int(band) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:Stats:band", f"band must be an integer in 0..{n_bands - 1}")
+        m = self._channels()
+        arrs = [np.zeros(m * n_bins) for _ in range(5)]
+        ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
+        nb = C.c_int(0)
+        self._call("flow_stats_read", C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), *[ptr(a) for a in arrs],
+                   ns.ctypes.data_as(C.POINTER(C.c_int64)), ptr(t0), ptr(t1))
+        assert nb.value == n_bins, (nb.value, n_bins)
+        out = []
+        for k in range(m):
+            d = {f: a[k * n_bins:(k + 1) * n_bins].copy() for f, a in zip(("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2"), arrs)}
+            d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
+            out.append(d)
+        return self._each(out)
+
+    # ---- step history (include/sphx.h sections 2d, 2f): wall shear, energy, bulk velocity, dt and vmax per step, recorded on the device ----
+    def history_enable(self, every=1, capacity=65536, t_from=0.0):
+        """Record every `every`-th completed step ending at t >= t_from into a device buffer of `capacity` records
+        ((re)configures and empties it).  Records that find the buffer full are dropped and counted.  A batch: one config for
+        all members, `capacity` records per member, each recorded on its own clock; n_members * capacity must not exceed
+        1 << 24."""
+        cfg = history_config(every, capacity, t_from, n_members=self._channels())
+        self._call("history_enable", C.byref(cfg))
+
+    def history_disable(self):
+        self._call("history_disable")
+
+    def history_records(self, drain=False):
+        """-> (records [n x 8] in the order of HISTORY_FIELDS, n_dropped); drain empties the buffer after the copy.  A batch:
+        one such pair per member, from one read of all members."""
+        m = self._channels()
+        n, dropped = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
+
+        def read(cap, rec, drain):  # the counts always; the records into rec [m x cap x 8] where there is one
+            self._call("history_read", C.c_int(cap), ptr(rec), n.ctypes.data_as(C.POINTER(C.c_int)),
+                       dropped.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(1 if drain else 0))
+
+        read(0, None, False)
+        cap, want = max(int(n.max()), 1), n.copy()
+        rec = np.zeros((m, cap, len(HISTORY_FIELDS)))
+        read(cap, rec, drain)
+        assert np.array_equal(n, want), (n, want)
+        return self._each([(rec[k, :n[k]].copy(), int(dropped[k])) for k in range(m)])
+
+
+class _Stepped(_Sampled):
+    """What a context and a batch bind alike on top of that: the handle's lifecycle, stepping, "sample now", the profiles
+    and dicts made of the sums and records, and the field map."""
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -228,52 +305,11 @@ class _Stepped:
                    C.byref(npairs) if pairs else None)
         return tb.value, tt.value, npairs.value
 
-    # ---- flow statistics (include/sphx.h sections 2a, 2c): time-averaged velocity profiles accumulated on the device ----
-    def flow_stats_enable(self, n_bins=0, every=1, t_from=0.0, bands=()):
-        """Sample the state every `every`-th completed step ending at t >= t_from into n_bins y-bins (0: the reference's
-        max(20, round(DH/dp))) of the whole channel (band 0) and of up to two x-bands [(x_centre, half_width), ...]
-        (band 1, 2).  (Re)configures and zeroes the sums.  A batch: one config for all members, each sampled on its own clock."""
-        cfg = flow_stats_config(n_bins, every, t_from, bands)
-        p0 = self._params0()
-        n = int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5)))
-        self._call("flow_stats_enable", C.byref(cfg))
-        self._flow_stats = (n, int(cfg.n_bands) + 1)  # (n_bins, n_bands incl. band 0) while the flow statistics are on
-
-    def flow_stats_disable(self):
-        self._call("flow_stats_disable")
-        self._flow_stats = None
-
-    def _stats_on(self):
-        return _enabled(self._flow_stats, "Stats", f"flow statistics are not enabled on this {self._where}")
-
-    def flow_stats_reset(self):
-        self._stats_on()
-        self._call("flow_stats_reset")
-
+    # ---- flow statistics (include/sphx.h sections 2a, 2c): "sample now" and the profile ----
     def flow_stats_sample(self):
         """Add one sample of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
         self._stats_on()
         self._call("flow_stats_sample")
-
-    def flow_stats_sums(self, band=0):
-        """The raw sums of one band: count, sum_ux, sum_ux2, sum_uy, sum_uy2 [n_bins], n_samples, t_first, t_last; a batch: one
-        such dict per member, from one read of all members."""
-        n_bins, n_bands = self._stats_on()
-        if not _is_int(band) or not 0 <= band < n_bands:
-            raise SphxError(SPHX_ERR_ARG, "SPHX:Stats:band", f"band must be an integer in 0..{n_bands - 1}")
-        m = self._channels()
-        arrs = [np.zeros(m * n_bins) for _ in range(5)]
-        ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
-        nb = C.c_int(0)
-        self._call("flow_stats_read", C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), *[ptr(a) for a in arrs],
-                   ns.ctypes.data_as(C.POINTER(C.c_int64)), ptr(t0), ptr(t1))
-        assert nb.value == n_bins, (nb.value, n_bins)
-        out = []
-        for k in range(m):
-            d = {f: a[k * n_bins:(k + 1) * n_bins].copy() for f, a in zip(("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2"), arrs)}
-            d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
-            out.append(d)
-        return self._each(out)
 
     def flow_stats(self, band=0):
         """Time-averaged profile of one band (profile.flow_stats_profile): y_mid, count, u_mean, u_std, uy_mean, uy_std,
@@ -282,35 +318,7 @@ class _Stepped:
         sums = self.flow_stats_sums(band)
         return [flow_stats_profile(DH, **s) for s in sums] if self._many else flow_stats_profile(DH, **sums)
 
-    # ---- step history (include/sphx.h sections 2d, 2f): wall shear, energy, bulk velocity, dt and vmax per step, recorded on the device ----
-    def history_enable(self, every=1, capacity=65536, t_from=0.0):
-        """Record every `every`-th completed step ending at t >= t_from into a device buffer of `capacity` records
-        ((re)configures and empties it).  Records that find the buffer full are dropped and counted.  A batch: one config for
-        all members, `capacity` records per member, each recorded on its own clock; n_members * capacity must not exceed
-        1 << 24."""
-        cfg = history_config(every, capacity, t_from, n_members=self._channels())
-        self._call("history_enable", C.byref(cfg))
-
-    def history_disable(self):
-        self._call("history_disable")
-
-    def history_records(self, drain=False):
-        """-> (records [n x 8] in the order of HISTORY_FIELDS, n_dropped); drain empties the buffer after the copy.  A batch:
-        one such pair per member, from one read of all members."""
-        m = self._channels()
-        n, dropped = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
-
-        def read(cap, rec, drain):  # the counts always; the records into rec [m x cap x 8] where there is one
-            self._call("history_read", C.c_int(cap), ptr(rec), n.ctypes.data_as(C.POINTER(C.c_int)),
-                       dropped.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(1 if drain else 0))
-
-        read(0, None, False)
-        cap, want = max(int(n.max()), 1), n.copy()
-        rec = np.zeros((m, cap, len(HISTORY_FIELDS)))
-        read(cap, rec, drain)
-        assert np.array_equal(n, want), (n, want)
-        return self._each([(rec[k, :n[k]].copy(), int(dropped[k])) for k in range(m)])
-
+    # ---- step history (include/sphx.h sections 2d, 2f): the records as a dict ----
     def history(self, drain=False):
         """The records so far as 1-D arrays step (int64), t, dt, vmax, tau_bottom, tau_top, kinetic_energy, u_bulk, plus
         n_dropped (history_dict); a batch: one such dict per member."""

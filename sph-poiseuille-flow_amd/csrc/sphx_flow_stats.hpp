@@ -1,5 +1,6 @@
 // sphx_flow_stats.hpp -- time-averaged velocity profiles of a resident context (include/sphx.h section 2a, "flow
-// statistics") and of every member of a batch (section 2c, k_flow_stats_b): a slot sampler (sphx_slot_sample.hpp) that
+// statistics"), of every member of a batch (section 2c, k_flow_stats_b) and of a slab of a ring (section 3a,
+// k_flow_stats_s: the particles the slab owns): a slot sampler (sphx_slot_sample.hpp) that
 // bins the state the step left into the reference's profile bins (SPH_Poiseuille.m:579-605) and adds it to running sums.
 //
 // Determinism: a sample is summed EXACTLY, in int64 fixed point -- integer adds do not depend on the order they arrive
@@ -85,8 +86,9 @@ __device__ __forceinline__ void stats_add(unsigned long long *h, long long ux, l
     atomicAdd(h + 4, (unsigned long long)uy2);
 }
 
-// where the arrays of the sampled channel are: the context's own ...
+// where the arrays of the sampled channel are, and which of its slots count (mine): the context's own, all of them ...
 struct StatsOwn {
+    __device__ bool mine(int, double) const { return true; }
     __device__ const double2 *pos(const FlowStatsArgs &a) const { return a.pos; }
     __device__ const double2 *vel(const FlowStatsArgs &a) const { return a.vel; }
     __device__ unsigned long long *isum(const FlowStatsArgs &a) const { return a.isum; }
@@ -98,12 +100,22 @@ struct StatsOwn {
 struct StatsMember {
     long long part;
     int m;
+    __device__ bool mine(int, double) const { return true; }
     __device__ long long sums(const FlowStatsArgs &a) const { return (long long)m * a.n_bands * a.n_bins * kStatsFields; }
     __device__ const double2 *pos(const FlowStatsArgs &a) const { return a.pos + part * m; }
     __device__ const double2 *vel(const FlowStatsArgs &a) const { return a.vel + part * m; }
     __device__ unsigned long long *isum(const FlowStatsArgs &a) const { return a.isum + sums(a); }
     __device__ double *dsum(const FlowStatsArgs &a) const { return a.dsum + sums(a); }
     __device__ FlowStatsHead *head(const FlowStatsArgs &a) const { return a.head + m; }
+};
+
+// ... or a slab's own, of which the particles it owns count (owns(): by position on a protocol grid, by the column slot i was
+// binned into on a skinned slab): the halo copies are sampled by the slabs that own them, so the sums of the ring's slabs
+// add up to the channel's.  cell: the layout the step ran in.
+struct StatsSlab : StatsOwn {
+    Grid g;
+    const int *cell;
+    __device__ bool mine(int i, double x) const { return owns(g, x, g.own_by_cell ? cell[i] : 0); }
 };
 
 // The sample of one channel closing the step slot of parity q, on clock clk, shared by the gridDim.x workgroups of a grid
@@ -129,6 +141,7 @@ __device__ __forceinline__ void flow_stats_body(const Clock *clk, int q, const F
     bool out_of_range = false;
     for (int i = i0 + (int)threadIdx.x; i < i1; i += kStatsBlock) {
         const double2 p = at.pos(a)[i], v = at.vel(a)[i];
+        if (!at.mine(i, p.x)) continue;
         if (!(p.y >= 0.0 && p.y <= a.DH)) continue;  // outside [0, DH]: dropped, as discretize does
         if (!(fabs(v.x) <= bound && fabs(v.y) <= bound)) { out_of_range = true; continue; }
         const int k = stats_bin(p.y, a.bin_w, a.n_bins);
@@ -181,6 +194,17 @@ __global__ __launch_bounds__(kStatsBlock) void k_flow_stats_b(Members mb, int q,
 {
     const int m = (int)blockIdx.y;
     flow_stats_body(mb.clk + m, q, a, StatsMember{mb.part, m});
+}
+
+// slab of a ring (sphx_slab_flow_stats_*): the particles this slab owns, of the clk->n it holds, into its own partial sums --
+// exact integers, so the ring's sums (the slabs' added up) do not depend on how the channel is cut.  x is in the frame of the
+// slab's window: the first slab may hold x < 0 and the last x >= DL, which stats_in_band's fmod brings back into [0, DL).
+__global__ __launch_bounds__(kStatsBlock) void k_flow_stats_s(const Clock *clk, int q, FlowStatsArgs a, Grid g, const int *cell)
+{
+    StatsSlab at;
+    at.g = g;
+    at.cell = cell;
+    flow_stats_body(clk, q, a, at);
 }
 
 }  // namespace sphx

@@ -1,6 +1,6 @@
-// sphx_history.hpp -- the step history of a resident context (include/sphx.h section 2d) and of every member of a batch
-// (section 2f, k_step_history_b): a slot sampler (sphx_slot_sample.hpp) that reduces the state the step left to one record
-// of kHistoryFields doubles -- step, t, dt, vmax of the device clock, the wall shear of SPH_Poiseuille.m:281-283, the kinetic
+// sphx_history.hpp -- the step history of a resident context (include/sphx.h section 2d), of every member of a batch
+// (section 2f, k_step_history_b) and of a slab of a ring (section 3a, k_step_history_s): a slot sampler
+// (sphx_slot_sample.hpp) that reduces the state the step left to one record of kHistoryFields doubles -- step, t, dt, vmax of the device clock, the wall shear of SPH_Poiseuille.m:281-283, the kinetic
 // energy and the bulk velocity -- and appends it to a record buffer in device memory.
 //
 // The wall-shear term is k_wall_shear's, term for term (sphx_kernels.hpp; kept as a copy here so that the monitor's kernel
@@ -55,6 +55,8 @@ struct HistoryArgs {
 };
 
 // one fluid particle's contribution to the wall force sums: sph_physics_mex.c:1713-1742 as k_wall_shear evaluates it
+// (kSlab: the caller has already asked owns() -- a skinned slab owns by the binned column, not by position)
+template <bool kSlab = false>
 __device__ __forceinline__ void history_wall_terms(const Grid &g, const Phys &ph, const FluidSet &s, const FluidTmp &t,
                                                    const Walls &w, int i, bool use_src, double2 p, double2 v, double &fb,
                                                    double &ft)
@@ -62,7 +64,11 @@ __device__ __forceinline__ void history_wall_terms(const Grid &g, const Phys &ph
     const double xi = p.x, yi = p.y;
     int cx, cy;
     binned_cell(g, s, i, cx, cy);
-    if (!(w.row_any[cy] && xi >= g.own_lo && xi < g.own_hi)) return;
+    if constexpr (kSlab) {
+        if (!w.row_any[cy]) return;
+    } else {
+        if (!(w.row_any[cy] && xi >= g.own_lo && xi < g.own_hi)) return;
+    }
     const int o = use_src ? t.src_of[i] : i;
     const double Voli = t.a[o].x;
     const double4 Bo = t.B[o];
@@ -90,8 +96,12 @@ __device__ __forceinline__ void history_wall_terms(const Grid &g, const Phys &ph
 
 // The record of one channel closing the step slot of parity q, on clock clk, shared by the gridDim.x workgroups of a grid row;
 // s is the state the step left, t holds its Vol / B; a's records / part / head are that channel's own.
+// kSlab: the channel is a slab of a ring -- of the clk->n particles it holds only those it owns (owns()) enter the sums, and
+// u_bulk is the slab's sum of u_x over the n_bulk fluid particles of the WHOLE channel: the four sums are additive partials,
+// the ring's record is the sum over its slabs.
+template <bool kSlab = false>
 __device__ __forceinline__ void step_history_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
-                                                  const FluidTmp &t, const Walls &w, const HistoryArgs &a)
+                                                  const FluidTmp &t, const Walls &w, const HistoryArgs &a, int n_bulk = 0)
 {
     if (!slot_due(clk, q, a.every, a.t_from)) return;
     const int n = clk->n;
@@ -102,9 +112,12 @@ __device__ __forceinline__ void step_history_body(const Clock *clk, int q, const
     double fb = 0.0, ft = 0.0, ke = 0.0, su = 0.0;  // wall force bottom, top; kinetic energy; sum u_x
     for (int i = i0 + (int)threadIdx.x; i < i1; i += kHistoryBlock) {
         const double2 p = s.pos[i], v = s.vel[i];
+        if constexpr (kSlab) {
+            if (!owns(g, p.x, g.own_by_cell ? s.cell[i] : 0)) continue;  // (a halo copy: its owner sums it)
+        }
         ke += 0.5 * s.mass[i] * (v.x * v.x + v.y * v.y);
         su += v.x;
-        history_wall_terms(g, ph, s, t, w, i, use_src, p, v, fb, ft);
+        history_wall_terms<kSlab>(g, ph, s, t, w, i, use_src, p, v, fb, ft);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -147,7 +160,7 @@ __device__ __forceinline__ void step_history_body(const Clock *clk, int q, const
         rec[0] = make_double2((double)clk->step, clk->t);
         rec[1] = make_double2(clk->dt_last, clk->vmax);
         rec[2] = make_double2(-s_tot[0] / ph.DL, -s_tot[1] / ph.DL);  // (k_tau_final: -sum / DL)
-        rec[3] = make_double2(s_tot[2], s_tot[3] / (double)n);
+        rec[3] = make_double2(s_tot[2], s_tot[3] / (double)(kSlab ? n_bulk : n));
         h->n_records = at + 1;
     } else {
         h->n_dropped += 1;
@@ -176,6 +189,15 @@ __global__ __launch_bounds__(kHistoryBlock) void k_step_history_b(Members mb, in
     a.part += (size_t)m * kHistoryMaxBlocks * kHistorySums;
     a.head += m;
     step_history_body(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, a);
+}
+
+// slab of a ring (sphx_slab_history_*): the record of the particles this slab owns.  Launched behind k_slab_pack3 and in front of
+// everything of phase 3 (sphx_samplers.hpp, launch_slab_samplers): s, t and the cell array are those of the layout the step ran
+// in, so Vol / B of slot i are at i (kHistoryInPlace) whether the step ends with a re-binning or not.
+__global__ __launch_bounds__(kHistoryBlock) void k_step_history_s(const Clock *clk, int q, Grid g, Phys ph, FluidSet s,
+                                                                   FluidTmp t, Walls w, HistoryArgs a, int n_bulk)
+{
+    step_history_body<true>(clk, q, g, ph, s, t, w, a, n_bulk);
 }
 
 }  // namespace sphx

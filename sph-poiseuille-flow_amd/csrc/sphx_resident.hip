@@ -218,6 +218,10 @@ struct sphx_ctx {
     hipGraphExec_t steps_graph = nullptr;
     std::vector<const sphx_ctx *> steps_graph_ring;  // the contexts the graph was captured for
     int steps_graph_cur = 0;                          // ... and the state parity it starts from
+    // The graph carries the launches of the slab samplers that were on when it was captured (sphx_slab_flow_stats_* /
+    // sphx_slab_history_*): every enable / disable counts up the slab's sampler_epoch, and the graph is replayed only while the
+    // epochs of the ring's slabs still add up to what they were at the capture
+    int64_t sampler_epoch = 0, steps_graph_epochs = 0;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
     // Dynamic re-binning (large channels): the device decides when to re-bin, every step carries the (self-skipping)
@@ -2997,6 +3001,7 @@ template <typename T> void step_chain(T &t)
         slab_phase2(c);
     }
     t.done_all(&sphx_ctx::ev_received);  // (reused: "my maxima have been read by me, my message A is complete")
+    for (sphx_ctx *c : t) launch_slab_samplers(c);  // (in front of the exchange and phase 3, which follow on this stream)
     step_exchange_and_after(t, false);
 }
 
@@ -3023,10 +3028,22 @@ template <typename T> void step_split(T &t)
         // "my maxima have been read by me, my message A is complete" -- recorded HERE, in front of the interior workgroups of
         // the next step's pass A, which the neighbours need not wait for
         t.done(c, &sphx_ctx::ev_received, c->stream);
+        // The samplers read S[1-q], Vol / B and the cell array of the step: in front of the hand-over, behind which phase 3 may
+        // overwrite the first and the last on the exchange stream, and in front of the interior of the next pass A, which
+        // overwrites Vol
+        launch_slab_samplers(c);
         t.hand_over(c);
         if (two || T::kInteriorWhenCaptured) slab_pass_a_interior(c, 1 - c->sched.cur);  // (phase 4 flips the parity)
     }
     step_exchange_and_after(t, true);
+}
+
+// what the slabs' enable / disable calls of their samplers have counted up so far (sphx_ctx::sampler_epoch)
+template <typename T> int64_t sampler_epochs(T &t)
+{
+    int64_t sum = 0;
+    for (sphx_ctx *c : t) sum += c->sampler_epoch;
+    return sum;
 }
 
 template <typename T> void slab_step(T &t)
@@ -3078,7 +3095,8 @@ template <typename T> void slab_run(T &t, double t_target, int64_t n_steps)
         t.done_all(&sphx_ctx::ev_received);
     }
     int64_t k = 0;
-    if (c0->steps_graph && c0->steps_graph_cur == c0->sched.cur &&  // whole replays of the step graph (sphx_slab_graph_prepare) ...
+    if (c0->steps_graph && c0->steps_graph_cur == c0->sched.cur && c0->steps_graph_epochs == sampler_epochs(t) &&
+        // whole replays of the step graph (sphx_slab_graph_prepare) ...
         std::equal(t.begin(), t.end(), c0->steps_graph_ring.begin(), c0->steps_graph_ring.end()))
         for (; n_steps - k >= kSlabGraphSteps; k += kSlabGraphSteps) slab_replay(t);
     for (; k < n_steps; ++k) slab_step(t);  // ... the rest step by step
@@ -3180,6 +3198,7 @@ template <typename T> void slab_graph_prepare(T &t)
     c0->steps_graph = exec;
     c0->steps_graph_cur = cur0;
     c0->steps_graph_ring.assign(t.begin(), t.end());
+    c0->steps_graph_epochs = sampler_epochs(t);
     slab_replay(t);
     for (sphx_ctx *c : t) {
         c->slab_steps_enqueued -= kSlabGraphSteps;  // (the warm replay stepped nothing)

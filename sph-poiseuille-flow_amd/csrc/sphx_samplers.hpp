@@ -1,6 +1,6 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
-// and the velocity-field map (2e; 2g).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// and the velocity-field map (2e; 2g); the first two also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp and sphx_field_map.hpp.  What the three share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -109,8 +109,8 @@ void read_head(const Head &h, int64_t *n_samples, double *t_first, double *t_las
 
 // ---- launches: every >= 1 = the in-loop sample closing step slot q, 0 = a sample of the state now ----
 
-// k_flow_stats on state s -- of a batch: member 0's -- into c->fstats
-void launch_flow_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
+// the arguments of a flow-statistics launch on state s into c->fstats
+FlowStatsArgs flow_stats_args(sphx_ctx *c, const FluidSet &s, int every)
 {
     const FlowStats &f = c->fstats;
     FlowStatsArgs a{};
@@ -121,9 +121,37 @@ void launch_flow_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
     for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
     a.n_bins = f.n_bins; a.n_bands = f.n_bands;
     a.every = every;
-    // workgroups of one channel's sample
-    const unsigned blocks = std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kStatsBlock * kStatsPerThread), 1u, (unsigned)kStatsMaxBlocks);
-    launch_forms(c, "k_flow_stats", Forms{k_flow_stats, k_flow_stats_b}, blocks, kStatsBlock, f.shmem(), q, a);
+    return a;
+}
+
+// workgroups of the sample of a channel that holds n particles
+unsigned flow_stats_blocks(size_t n)
+{
+    return std::clamp<unsigned>(div_up(n, (size_t)kStatsBlock * kStatsPerThread), 1u, (unsigned)kStatsMaxBlocks);
+}
+
+// k_flow_stats on state s -- of a batch: member 0's -- into c->fstats
+void launch_flow_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    launch_forms(c, "k_flow_stats", Forms{k_flow_stats, k_flow_stats_b}, flow_stats_blocks((size_t)c->nf), kStatsBlock, c->fstats.shmem(), q,
+                 flow_stats_args(c, s, every));
+}
+
+// the arguments of a history launch into c->hist; src: where Vol / B of a slot are (HistorySrc)
+HistoryArgs history_args(sphx_ctx *c, int src)
+{
+    const History &h = c->hist;
+    HistoryArgs a{};
+    a.records = h.records.get(); a.part = h.part.get(); a.head = h.head.get();
+    a.t_from = h.cfg.t_from; a.capacity = h.cfg.capacity; a.every = h.cfg.every;
+    a.src = src;
+    return a;
+}
+
+// workgroups of the record of a channel that holds n particles
+unsigned history_blocks(size_t n)
+{
+    return std::clamp<unsigned>(div_up(n, (size_t)kHistoryBlock * kHistoryPerThread), 1u, (unsigned)kHistoryMaxBlocks);
 }
 
 // k_step_history behind step slot q, which left state s -- of a batch: member 0's -- into c->hist: Vol / B of the finished step
@@ -133,15 +161,8 @@ void launch_flow_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
 // its shared slot's `rebuild` holds for every member that runs in the slot.
 void launch_history(sphx_ctx *c, int q, const FluidSet &s, bool rebuild)
 {
-    const History &h = c->hist;
-    HistoryArgs a{};
-    a.records = h.records.get(); a.part = h.part.get(); a.head = h.head.get();
-    a.t_from = h.cfg.t_from; a.capacity = h.cfg.capacity; a.every = h.cfg.every;
-    a.src = c->dyn ? kHistoryByClock : (rebuild ? kHistorySrcOf : kHistoryInPlace);
-    // workgroups of one channel's record
-    const unsigned blocks =
-        std::clamp<unsigned>(div_up((size_t)c->nf, (size_t)kHistoryBlock * kHistoryPerThread), 1u, (unsigned)kHistoryMaxBlocks);
-    launch_forms(c, "k_step_history", Forms{k_step_history, k_step_history_b}, blocks, kHistoryBlock, 0, q, c->grid,
+    const HistoryArgs a = history_args(c, c->dyn ? kHistoryByClock : (rebuild ? kHistorySrcOf : kHistoryInPlace));
+    launch_forms(c, "k_step_history", Forms{k_step_history, k_step_history_b}, history_blocks((size_t)c->nf), kHistoryBlock, 0, q, c->grid,
                  per_member(c->phys), s, c->tmp_par[c->fuse_ea ? q : 0], c->walls, a);
 }
 
@@ -528,6 +549,149 @@ SPHX_EXPORT int sphx_ctx_field_map_read(sphx_ctx *c, int capacity, int *nx, int 
     const FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, true);
     field_read(f, c->stream, [c] { settle_owed(c); }, capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples,
                t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- samplers of a slab ring (include/sphx.h section 3a) ----
+// Flow statistics and step history of a skinned slab, recorded inside the library's own loops (sphx_slab_run,
+// sphx_slab_group_run): a slab samples the particles it OWNS, what it keeps are partial sums, and the ring's value is the sum
+// over its slabs.  The configurations, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* identifiers are a
+// context's (sections 2a, 2d); sphx_ctx_flow_stats_* / sphx_ctx_history_* keep refusing a slab.
+
+namespace {
+
+// The samplers of slab c that are on, behind k_slab_pack3 of the step slot the host's parity names (slab_phase4 flips it
+// later) and in front of everything of phase 3: the clock is the finished step's, S[1-q] holds the owned particles' new state,
+// Vol / B (c->tmp) and the layout arrays (cell, mass) are those of the layout the step ran in -- clk->n is still that
+// layout's count (k_slab_unpack3 sets the new one), so a re-binning step needs no src_of.  One self-skipping launch each,
+// on the slab's stream; both off: nothing is enqueued.
+void launch_slab_samplers(sphx_ctx *c)
+{
+    if (!c->fstats.on && !c->hist.on) return;
+    const int q = c->sched.cur;
+    const Clock *clk = c->clock.get();
+    const FluidSet s = c->view(1 - q, 0);
+    // (workgroups from the capacity: what a slab holds changes with every re-binning, a launch captured in a graph does not)
+    if (c->fstats.on)
+        launch_s(c, "k_flow_stats_s", k_flow_stats_s, dim3(flow_stats_blocks((size_t)c->cap)), dim3(kStatsBlock), c->fstats.shmem(), clk, q,
+                 flow_stats_args(c, s, c->fstats.cfg.every), c->grid, (const int *)s.cell);
+    if (c->hist.on)
+        launch_s(c, "k_step_history_s", k_step_history_s, dim3(history_blocks((size_t)c->cap)), dim3(kHistoryBlock), 0, clk, q, c->grid,
+                 c->phys, s, c->tmp, c->walls, history_args(c, kHistoryInPlace), c->nf);
+}
+
+// a slab of the native loops, or SPHX:Slab:ctx / SPHX:Slab:protocol
+sphx_ctx *sampled_slab(sphx_ctx *c)
+{
+    require(c != nullptr && c->is_slab, "SPHX:Slab:ctx", "not a slab context");
+    require(c->rebuild_every > 1, "SPHX:Slab:protocol",
+            "the samplers of a slab live in sphx_slab_run / sphx_slab_group_run (a slab created with rebuild_every != 1)");
+    return c;
+}
+
+// everything enqueued for slab c has run: its stream (a replayed ring graph runs ahead of it, release_from_first) and, where it
+// has one, its second stream
+void slab_settle(sphx_ctx *c)
+{
+    SPHX_HIP(hipStreamSynchronize(c->stream));
+    if (c->stream2) SPHX_HIP(hipStreamSynchronize(c->stream2));
+}
+
+// A sampler of slab c goes on or off: a prepared step graph carries the launches as they were, so it is dropped -- this slab's
+// own here, a ring's (held by its slab 0) by the epoch that slab_run compares -- and the loop runs eagerly until
+// sphx_slab_graph_prepare is called again
+void slab_samplers_changed(sphx_ctx *c)
+{
+    slab_settle(c);
+    c->sampler_epoch += 1;
+    if (c->steps_graph) { (void)hipGraphExecDestroy(c->steps_graph); c->steps_graph = nullptr; }
+}
+
+template <typename S>
+S &slab_sampler_on(sphx_ctx *c, S sphx_ctx::*which, const SamplerNames &n)
+{
+    if (!(c->*which).on) throw Error(SPHX_ERR_STATE, sampler_id(n, "disabled"), std::string(n.off) + "slab");
+    return c->*which;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_slab_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_config *cfg)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    FlowStats checked;
+    checked.configure(c->prm, cfg);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
+    slab_samplers_changed(c);
+    stats_enable(c->fstats, c->prm, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_flow_stats_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    if (c->fstats.on) {
+        slab_samplers_changed(c);
+        sampler_off(c->fstats, c->sched, c->stream);
+    }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_flow_stats_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    FlowStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::fstats, kStatsNames);
+    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_flow_stats_read(sphx_ctx *c, int band, int capacity, int *n_bins, double *count, double *sum_ux,
+                                          double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples,
+                                          double *t_first, double *t_last)
+{
+    SPHX_TRY
+    const FlowStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::fstats, kStatsNames);
+    stats_read(f, c->stream, [c] { slab_settle(c); }, band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples,
+               t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_history_enable(sphx_ctx *c, const sphx_history_config *cfg)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    History::check(cfg, 1);
+    slab_samplers_changed(c);
+    history_enable(c->hist, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_history_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    if (c->hist.on) {
+        slab_samplers_changed(c);
+        sampler_off(c->hist, c->sched, c->stream);
+    }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_history_read(sphx_ctx *c, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    History &h = slab_sampler_on(sampled_slab(c), &sphx_ctx::hist, kHistoryNames);
+    slab_settle(c);  // (the records of everything enqueued)
+    h.read(c->stream, capacity, records, n_records, n_dropped, drain != 0);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -14,6 +14,8 @@ Layers:
                       through host memory for CPU tests and single-GPU rehearsals)
   HipSlabEngine    -- the per-rank compute engine (libsphx slab context)
   SlabDriver       -- step loop = engine.compute -> exchange -> engine.finish
+  pool_ring_* / ring_* / all_reduce_ring_*
+                   -- the ring's flow statistics and step history from the slabs' partial sums
   bench_main()     -- bench.py's multi-GPU leg
 """
 from __future__ import annotations
@@ -25,6 +27,9 @@ import os
 import time
 
 import numpy as np
+
+from . import capi as _capi
+from .profile import flow_stats_profile
 
 HALO_COLS = 4  # four dependent neighbour passes per step, each reaching one >=2h column further
 
@@ -107,8 +112,15 @@ class RingExchange:
             dist.all_reduce(vmax, op=dist.ReduceOp.MAX, group=self.group)
 
 
-class HipSlabEngine:
-    """libsphx slab context of one rank; device buffers are torch tensors so RCCL can move them."""
+class HipSlabEngine(_capi._Sampled):
+    """libsphx slab context of one rank; device buffers are torch tensors so RCCL can move them.
+
+    Native engines (the library's own loops) have a context's flow_stats_enable / _disable / _reset / flow_stats_sums(band) and
+    history_enable / _disable / history_records(drain) (capi._Sampled; include/sphx.h section 3a), recorded inside run() /
+    group_run().  What they return are this slab's PARTIAL sums over the particles it owns: pool_ring_sums / pool_ring_history
+    (ring_flow_stats / ring_history, all_reduce_ring_*) make the ring's.  Enabling or disabling drops a graph made by
+    graph_prepare()."""
+    _stem, _where = "sphx_slab_", "slab"
 
     def __init__(self, prm, parts, rank, world, device, lanes_per_particle=0, halo_cols=HALO_COLS, t_end=None,
                  pos=None, vel=None, drho_dt=None, native=False, rebuild_every=0, skin_h=0.0, hip_stream=None):
@@ -118,6 +130,7 @@ class HipSlabEngine:
         from . import capi
         self.capi = capi
         self.rank, self.world, self.native = rank, world, native
+        self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
         capi.set_device(device)
         if not native:
             import torch
@@ -236,6 +249,101 @@ class HipSlabEngine:
             self.close()
         except Exception:  # interpreter shutdown: module globals may already be gone
             pass
+
+
+# ---- diagnostics of a ring: the slabs' partial sums made into the channel's (include/sphx.h section 3a) ----
+_SUMS = ("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2")
+_HEAD = ("n_samples", "t_first", "t_last")
+_CLOCK_FIELDS = 4  # step, t, dt, vmax of a history record: the same on every rank; the fields behind them are additive
+
+
+def _same(a, b):
+    return a == b or (a != a and b != b)  # (no sample yet: the times are NaN on every rank)
+
+
+def _check_heads_agree(heads):
+    """heads: [(n_samples, t_first, t_last)] per rank -- every slab of a ring samples the same steps."""
+    for r, h in enumerate(heads):
+        if not all(_same(x, y) for x, y in zip(h, heads[0])):
+            raise ValueError(f"rank {r} sampled {dict(zip(_HEAD, h))}, rank 0 {dict(zip(_HEAD, heads[0]))}: "
+                             "the slabs of one ring sample the same steps")
+
+
+def pool_ring_sums(sums_list) -> dict:
+    """The ring's flow-statistics sums of one band from the ranks' partial sums (HipSlabEngine.flow_stats_sums, in rank
+    order): every array added elementwise, count included; n_samples, t_first and t_last must agree between the ranks."""
+    sums_list = list(sums_list)
+    _check_heads_agree([tuple(s[k] for k in _HEAD) for s in sums_list])
+    out = {k: np.sum([np.asarray(s[k], dtype=np.float64) for s in sums_list], axis=0) for k in _SUMS}
+    out.update({k: sums_list[0][k] for k in _HEAD})
+    return out
+
+
+def _check_steps_agree(steps_list):
+    for r, st in enumerate(steps_list):
+        if not np.array_equal(st, steps_list[0]):
+            raise ValueError(f"rank {r} recorded steps {st!r}, rank 0 {steps_list[0]!r}: the slabs of one ring record the same steps")
+
+
+def pool_ring_history(records_list) -> dict:
+    """The ring's step history (capi.history_dict's form) from the ranks' (records [n x 8], n_dropped) pairs
+    (HipSlabEngine.history_records, in rank order): step, t, dt, vmax of rank 0, the other fields summed over the ranks;
+    the ranks' step columns must agree.  n_dropped is rank 0's (capacity and drops are per slab and agree)."""
+    recs = [np.asarray(r, dtype=np.float64).reshape(-1, len(_capi.HISTORY_FIELDS)) for r, _ in records_list]
+    _check_steps_agree([r[:, 0] for r in recs])
+    out = recs[0].copy()
+    out[:, _CLOCK_FIELDS:] = np.sum([r[:, _CLOCK_FIELDS:] for r in recs], axis=0)
+    return _capi.history_dict(out, records_list[0][1])
+
+
+def ring_flow_stats(engines, band=0) -> dict:
+    """Time-averaged profile of one band of an in-process ring (profile.flow_stats_profile of the pooled sums)."""
+    return flow_stats_profile(engines[0].params.DH, **pool_ring_sums([e.flow_stats_sums(band) for e in engines]))
+
+
+def ring_history(engines, drain=False) -> dict:
+    """The step history of an in-process ring (pool_ring_history of every slab's records)."""
+    return pool_ring_history([e.history_records(drain) for e in engines])
+
+
+def _all_gathered(dist, row, group):
+    """[world x len(row)] float64: every rank's row (control plane: CPU tensors, gloo)."""
+    import torch
+    mine = torch.tensor(np.asarray(row, dtype=np.float64))
+    rows = [torch.empty_like(mine) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(rows, mine, group=group)
+    return [r.numpy() for r in rows]
+
+
+def _all_reduced(dist, a, group):
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).copy())
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.numpy()
+
+
+def all_reduce_ring_sums(sums, dist, group=None) -> dict:
+    """One rank per process: the ring's sums from this rank's (pool_ring_sums over the control-plane group that
+    join_native_ring uses -- float64 on the CPU); every rank gets them.  Collective; raises on every rank when the ranks'
+    n_samples, t_first or t_last differ."""
+    _check_heads_agree([tuple(h) for h in _all_gathered(dist, [float(sums[k]) for k in _HEAD], group)])
+    total = _all_reduced(dist, np.stack([np.asarray(sums[k], dtype=np.float64) for k in _SUMS]), group)
+    out = {k: total[j] for j, k in enumerate(_SUMS)}
+    out.update({k: sums[k] for k in _HEAD})
+    return out
+
+
+def all_reduce_ring_history(records, dist, group=None) -> dict:
+    """One rank per process: the ring's step history from this rank's (records, n_dropped) pair, as pool_ring_history; every
+    rank gets it.  Collective; raises on every rank when the ranks' step columns differ."""
+    rec = np.asarray(records[0], dtype=np.float64).reshape(-1, len(_capi.HISTORY_FIELDS))
+    counts = _all_gathered(dist, [float(len(rec))], group)
+    if any(c[0] != counts[0][0] for c in counts):
+        raise ValueError(f"the ranks hold {[int(c[0]) for c in counts]} records: the slabs of one ring record the same steps")
+    _check_steps_agree(_all_gathered(dist, rec[:, 0], group))
+    out = rec.copy()
+    out[:, _CLOCK_FIELDS:] = _all_reduced(dist, rec[:, _CLOCK_FIELDS:], group)
+    return _capi.history_dict(out, records[1])
 
 
 class SlabDriver:
