@@ -467,7 +467,7 @@ int sphx_ctx_history_read(sphx_ctx *ctx, int capacity, double *records, int *n_r
  *    slot ends with one more launch (k_field_map, behind k_flow_stats and k_step_history; it skips itself on the steps
  *    gated out) that is captured in the replayed graphs; enable / disable re-capture them.  Independent of the flow
  *    statistics and the step history: all three may be on at once.  The planes take 6 * nx * ny doubles of device memory.
- *  Batches (section 2b) keep one map per member: section 2g.  Slabs have no field maps.
+ *  Batches (section 2b) keep one map per member: section 2g.  The slabs of a ring each keep a block of node columns: section 3a.
  *  Errors: SPHX:Field:config (nx or ny equal to 1 or negative, nx * ny > 1 << 25, every < 1, NaN t_from, with_walls not
  *    0 or 1, or the allocation fails: the context then goes on without a map), SPHX:Field:disabled (SPHX_ERR_STATE: a
  *    call that needs the map while it is off), SPHX:Field:capacity (the caller's arrays are smaller than nx * ny); every
@@ -637,14 +637,16 @@ int sphx_slab_snapshot(sphx_ctx *ctx, int capacity, int *n, double *x, double *y
                        double *vy, double *drho, int *id, int *owned);
 
 /* ------------------------------------------------------------------------------------------------
- * 3a. Samplers of a slab ring: the flow statistics of section 2a and the step history of section 2d for the slabs of
- *    the library's own loops (sphx_slab_run, sphx_slab_group_run), so that a ring reports its time-averaged profile
- *    and the settling of its wall shear without a snapshot per sample.  The config structs, their checks, the layouts
- *    and the SPHX:Stats:* / SPHX:History:* identifiers are those of sections 2a / 2d; sphx_ctx_flow_stats_*,
+ * 3a. Samplers of a slab ring: the flow statistics of section 2a, the step history of section 2d and the velocity-field
+ *    map of section 2e for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that a ring
+ *    reports its time-averaged profile, the settling of its wall shear and its averaged field without a snapshot per
+ *    sample.  The config structs, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* / SPHX:Field:*
+ *    identifiers are those of sections 2a / 2d / 2e; sphx_ctx_flow_stats_*,
  *    sphx_ctx_history_* and sphx_ctx_field_map_* keep refusing a slab (SPHX:Stats:slab, SPHX:History:slab,
  *    SPHX:Field:slab).
- *    A slab samples, at the end of a step, the fluid particles it OWNS (those sphx_slab_snapshot marks owned), never its
- *    halo copies, and what a read returns are the slab's PARTIAL sums: the ring's value is the sum over the ranks.
+ *    Statistics and history: a slab samples, at the end of a step, the fluid particles it OWNS (those sphx_slab_snapshot
+ *    marks owned), never its halo copies, and what a read returns are the slab's PARTIAL sums: the ring's value is the
+ *    sum over the ranks.
  *      flow statistics: every array elementwise, count included; n_samples, t_first and t_last are the same on every
  *        rank.  Band membership goes by x mod DL, whatever frame a slab keeps x in.  The sums are exact integers per
  *        sample, so the pooled sums do not depend on how the channel is cut.
@@ -653,12 +655,25 @@ int sphx_slab_snapshot(sphx_ctx *ctx, int capacity, int *n, double *x, double *y
  *        slab's sum, u_bulk = (the slab's sum of u_x) / the GLOBAL n_fluid.  The ring's record is fields 0..3 of any
  *        rank and the sum over the ranks of fields 4..7.  capacity and n_dropped are per slab; every slab records
  *        the same steps.
+ *    Field map: a node's sample is a ratio (S1 / S0 and its square are accumulated per sample), so partial sums over
+ *    owned particles could not be pooled.  The NODES are divided instead: of the nx x ny grid of section 2e (linspace
+ *    over [0, DL] and [0, DH], ends included) a slab owns the node columns i_lo <= i < i_hi, all ny rows of each, and
+ *    computes the COMPLETE sample of each of its nodes from the particles it owns and from its halo copies, which
+ *    carry the finished step's state in the cell columns next to the owned ones.  The blocks of ranks 0 .. G-1
+ *    partition [0, nx): they are computed once, at enable, by one rule that is the same on every rank -- rank r's
+ *    block starts at the first node column whose x is not left of the left edge of rank r's first cell column, rank
+ *    0's at 0, and rank r's i_hi is rank r+1's i_lo -- so a node column that falls on a cut belongs to exactly one
+ *    slab.  Node column nx-1 (x = DL) is the last slab's and is evaluated at x = DL in that slab's frame, whose right
+ *    halo holds the first slab's particles at x + DL.  The ring's map is the slabs' blocks side by side; nothing is
+ *    added.  A slab may own no node column (i_lo == i_hi, a coarse nx): it still counts the samples, so n_samples,
+ *    t_first and t_last are the same on every rank.  The device allocation is the block, not the grid; nx * ny is
+ *    bounded as in section 2e.
  *    Every call refuses a context that is not a slab with SPHX:Slab:ctx and a slab created for the caller-driven
  *    protocol (rebuild_every == 1) with SPHX:Slab:protocol.  A read, reset or disable waits for the slab's stream(s)
  *    itself, whether sphx_slab_sync has been called for the enqueued steps or not.  Enabling or disabling a sampler
  *    drops a step graph prepared with sphx_slab_graph_prepare (on any slab of an in-process ring: the ring's): the
  *    loops run eagerly until it is prepared again, and the new graph carries the launches.  There is no "sample now"
- *    call and no field map on slabs.
+ *    call on slabs.
  * ---------------------------------------------------------------------------------------------- */
 int sphx_slab_flow_stats_enable(sphx_ctx *ctx, const sphx_flow_stats_config *cfg);
 int sphx_slab_flow_stats_disable(sphx_ctx *ctx);
@@ -672,6 +687,18 @@ int sphx_slab_history_enable(sphx_ctx *ctx, const sphx_history_config *cfg);
 int sphx_slab_history_disable(sphx_ctx *ctx);
 /* The slab's records (fields 4..7: its partials); arguments as sphx_ctx_history_read (SPHX:History:disabled while off). */
 int sphx_slab_history_read(sphx_ctx *ctx, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain);
+/* Config and checks as sphx_ctx_field_map_enable (SPHX:Field:config); nx, ny are the RING's grid, the same on every rank. */
+int sphx_slab_field_map_enable(sphx_ctx *ctx, const sphx_field_map_config *cfg);
+int sphx_slab_field_map_disable(sphx_ctx *ctx);
+/* Clears the planes and the sample count (SPHX:Field:disabled while the map is off, as for the read). */
+int sphx_slab_field_map_reset(sphx_ctx *ctx);
+/* The slab's block: the ring's shape (*nx, *ny), the node columns *i_lo <= i < *i_hi it owns, the six planes of
+ * (*i_hi - *i_lo) * ny doubles each -- node (i, k) at (i - *i_lo) * ny + k -- and the head, as sphx_ctx_field_map_read.
+ * Any output may be NULL; capacity: the doubles each plane given can take, SPHX:Field:capacity when that is less than
+ * the block (call once with every plane NULL to learn the block, then with arrays of its size). */
+int sphx_slab_field_map_read(sphx_ctx *ctx, int capacity, int *nx, int *ny, int *i_lo, int *i_hi, double *count,
+                             double *sum_w, double *sum_ux, double *sum_uy, double *sum_ux2, double *sum_uy2,
+                             int64_t *n_samples, double *t_first, double *t_last);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
-// sphx_field_map.hpp -- velocity-field maps of a resident context (include/sphx.h section 2e) and of every member of a
-// batch (section 2g, k_field_map_b): a slot sampler (sphx_slot_sample.hpp) that interpolates the velocity of the state the step left onto a regular nx x ny grid of nodes
+// sphx_field_map.hpp -- velocity-field maps of a resident context (include/sphx.h section 2e), of every member of a
+// batch (section 2g, k_field_map_b) and of a slab of a ring (section 3a, k_field_map_s): a slot sampler (sphx_slot_sample.hpp) that interpolates the velocity of the state the step left onto a regular nx x ny grid of nodes
 // (both ends included in x and y, the shape of panel (b) of SPH_Poiseuille_postprocess.m:184-201 by default) and adds
 // the sample to running sums per node.
 //
@@ -15,6 +15,17 @@
 // whole skin that binning position lies in the node's cell or one next to it.  The clock stops (or re-bins) at a drift
 // of skin / 2: every state a sample can see -- the one a step slot left, the one a stopped loop left for
 // sphx_ctx_download -- is inside the bound with half the skin to spare.  Wall particles do not move at all.
+//
+// A slab of a ring (k_field_map_s) samples the node columns it owns, in its own open window, with the sweep centred on the
+// node's cell column CLAMPED into the owned columns [own_c0, own_c1): it reads the columns own - 1 .. own + 1 only, where the
+// halo copies carry the finished step's state.  The argument carries over.  An owned node lies in
+// [own_lo, own_hi] up to the rounding of the host's block rule, so the clamp moves the centre by at most one column, and only
+// for a node ON the outer edge of the owned range (x = DL of the last slab; a node column that falls on a cut).  A particle
+// within 2h of such a node was binned within 2h + drift of the edge: in the outermost owned column or in the first halo
+// column beside it, both among the clamped centre's three, because a column is 2h + skin wide and the ring re-bins at a
+// drift of skin / 2 -- the spare half of the skin is many orders of magnitude more than the rounding.  The window is open
+// (half_DL = +inf): the first slab holds the last slab's particles at x - DL and the last slab the first slab's at x + DL, so
+// node 0 and node nx - 1 (x = DL, evaluated there) need no minimum image.
 //
 // Mapping: one thread per node, a wave covers an 8 x 8 tile of nodes (about 4 dp x 4 dp at the default shape, one and a
 // half cells), so the lanes of a wave walk nearly the same candidate runs and their 16-byte loads of pos / vel hit the
@@ -99,8 +110,12 @@ __device__ __forceinline__ void field_columns(const Grid &g, const KernelConst &
 
 // The sample of one channel closing the step slot of parity q, on clock clk, by the gridDim.x workgroups of a grid row; s is the
 // state the step left (pos, vel and the cell ranges of the layout it is stored in); a's planes and head are that channel's own.
+// kSlab: the channel is a slab of a ring -- a.nx, the tiles and the planes are those of the BLOCK of node columns the slab
+// owns, column i of the block is column i_lo + i of the ring's nx_all columns (a.step_x is the ring's), and the sweep is
+// centred on a column the slab owns.  A block may be empty (a.nx = 0, no tiles): the head still counts the sample.
+template <bool kSlab = false>
 __device__ __forceinline__ void field_map_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
-                                               const Walls &w, const FieldMapArgs &a)
+                                               const Walls &w, const FieldMapArgs &a, int i_lo = 0, int nx_all = 0)
 {
     if (!sample_due(clk, q, a.every, a.t_from)) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) note_sample(a.head, clk->t);  // the head, by one thread: plain vector stores
@@ -111,10 +126,13 @@ __device__ __forceinline__ void field_map_body(const Clock *clk, int q, const Gr
     const int i = tx * kFieldTile + (lane >> 3), k = ty * kFieldTile + (lane & 7);
     if (i >= a.nx || k >= a.ny) return;
     // numpy's linspace: i * step, the last node the end itself
-    const double xn = i == a.nx - 1 ? ph.DL : (double)i * a.step_x;
+    double xn;
+    if constexpr (kSlab) xn = i_lo + i == nx_all - 1 ? ph.DL : (double)(i_lo + i) * a.step_x;
+    else xn = i == a.nx - 1 ? ph.DL : (double)i * a.step_x;
     const double yn = k == a.ny - 1 ? ph.DH : (double)k * a.step_y;
     int cx, cy;
     cell_of(g, xn, yn, cx, cy);
+    if constexpr (kSlab) cx = min(max(cx, g.own_c0), g.own_c1 - 1);
     FieldSums S;
     field_columns(g, ph.kc, s.start, cx, cy, xn, yn, S, s.pos, [&](int j) { return s.vel[j]; });
     if (a.with_walls && w.row_any[cy])
@@ -154,6 +172,17 @@ __global__ __launch_bounds__(kFieldBlock) void k_field_map_b(Members mb, int q, 
     a.planes += (size_t)m * kFieldPlanes * (size_t)a.nx * (size_t)a.ny;
     a.head += m;
     field_map_body(mb.clk + m, q, g, ph, member_set(mb, m, s), w, a);
+}
+
+// slab of a ring (sphx_slab_field_map_*): the complete sample of every node of the block of node columns this slab owns
+// (i_lo <= column < i_lo + a.nx of the ring's nx_all; the host fixed the blocks at enable, sphx_samplers.hpp), from the
+// particles it owns and from its halo copies.  Launched behind k_slab_pack3 and in front of everything of phase 3
+// (launch_slab_samplers): s is S[1-q] with the cell ranges of the layout the step ran in.  Every node is owned by one thread of
+// one slab, which adds its candidates in the sweep's column and slot order: no atomics, no ticket.
+__global__ __launch_bounds__(kFieldBlock) void k_field_map_s(const Clock *clk, int q, Grid g, Phys ph, FluidSet s, Walls w,
+                                                             FieldMapArgs a, int i_lo, int nx_all)
+{
+    field_map_body<true>(clk, q, g, ph, s, w, a, i_lo, nx_all);
 }
 
 }  // namespace sphx

@@ -190,6 +190,7 @@ struct sphx_ctx {
     bool is_slab = false;
     int rank = 0, n_ranks = 1, halo_cols = 0, msg_cap = 0;
     int col0 = 0, col1 = 0;  // owned global columns [col0, col1)
+    int ncx_ring = 0;        // ... of the ring's ncx_ring cell columns: rank r owns from (r * ncx_ring) / n_ranks
     DevBuf<double2> kpos, kvel;
     DevBuf<double> kdrho, kmass;
     DevBuf<int> kid, counters, n_new, ticket;  // (ticket: see last_workgroup_out)
@@ -219,7 +220,7 @@ struct sphx_ctx {
     std::vector<const sphx_ctx *> steps_graph_ring;  // the contexts the graph was captured for
     int steps_graph_cur = 0;                          // ... and the state parity it starts from
     // The graph carries the launches of the slab samplers that were on when it was captured (sphx_slab_flow_stats_* /
-    // sphx_slab_history_*): every enable / disable counts up the slab's sampler_epoch, and the graph is replayed only while the
+    // sphx_slab_history_* / sphx_slab_field_map_*): every enable / disable counts up the slab's sampler_epoch, and the graph is replayed only while the
     // epochs of the ring's slabs still add up to what they were at the capture
     int64_t sampler_epoch = 0, steps_graph_epochs = 0;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -2128,6 +2129,7 @@ void slab_setup(sphx_ctx *c, const sphx_params *prm, int n_fluid, int n_total, c
     auto col_lo = [&](int r) { return (int)(((long long)r * ncx_g) / n_ranks); };
     c->col0 = col_lo(rank);
     c->col1 = col_lo(rank + 1);
+    c->ncx_ring = ncx_g;
     for (int r = 0; r < n_ranks; ++r)
         require(col_lo(r + 1) - col_lo(r) >= H + 1, "SPHX:Slab:width",
                 "every slab must own at least halo_cols+1 cell columns (use fewer ranks or a longer channel)");

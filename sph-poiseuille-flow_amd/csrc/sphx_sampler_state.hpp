@@ -51,16 +51,20 @@ struct History {
 };
 
 // Velocity-field map (sphx_ctx_field_map_*, sphx_batch_field_map_*; sphx_field_map.hpp) of a context or of the M members of a
-// batch: one configuration and shape, member m's six planes at m * block(), its head at m.
+// batch: one configuration and shape, member m's six planes at m * block(), its head at m.  Of a slab of a ring
+// (sphx_slab_field_map_*): nx x ny is the ring's grid, the planes hold the block of node columns i_lo <= i < i_hi the slab owns.
 struct FieldMap {
     bool on = false;
     int members = 1;
     sphx_field_map_config cfg{};
     int nx = 0, ny = 0;  // the shape in force (cfg.nx / cfg.ny = 0: the reference's)
+    bool part = false;   // a slab's: the planes are those of the columns [i_lo, i_hi) only (possibly none)
+    int i_lo = 0, i_hi = 0;
     DevBuf<double> planes;
     DevBuf<FieldMapHead> head;
 
-    size_t nodes() const { return (size_t)nx * (size_t)ny; }
+    int cols() const { return part ? i_hi - i_lo : nx;  }  // node columns held
+    size_t nodes() const { return (size_t)cols() * (size_t)ny; }
     size_t block() const { return nodes() * kFieldPlanes; }  // the planes of one member
     void check(const sphx_params &prm, const sphx_field_map_config *cfg, int M);
     void alloc(const FieldMap &checked, int M);

@@ -1,6 +1,6 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
-// and the velocity-field map (2e; 2g); the first two also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// and the velocity-field map (2e; 2g); all three also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp and sphx_field_map.hpp.  What the three share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -166,24 +166,35 @@ void launch_history(sphx_ctx *c, int q, const FluidSet &s, bool rebuild)
                  per_member(c->phys), s, c->tmp_par[c->fuse_ea ? q : 0], c->walls, a);
 }
 
-// k_field_map on state s (pos, vel and the cell ranges of the layout it is stored in) -- of a batch: member 0's -- into c->fmap
-void launch_field_map(sphx_ctx *c, int q, const FluidSet &s, int every)
+// the arguments of a field-map launch into c->fmap over nx node columns (a slab: those of its block)
+FieldMapArgs field_map_args(sphx_ctx *c, int nx, int every)
 {
     const FieldMap &f = c->fmap;
     FieldMapArgs a{};
     a.planes = f.planes.get(); a.head = f.head.get();
-    a.step_x = c->prm.DL / (f.nx - 1); a.step_y = c->prm.DH / (f.ny - 1);
+    a.step_x = c->prm.DL / (nx - 1); a.step_y = c->prm.DH / (f.ny - 1);
     a.dp2 = c->prm.dp * c->prm.dp;
     a.t_from = f.cfg.t_from;
-    a.nx = f.nx; a.ny = f.ny;
+    a.nx = nx; a.ny = f.ny;
     a.tiles_y = (int)div_up((size_t)f.ny, (size_t)kFieldTile);
-    a.n_tiles = (int)div_up((size_t)f.nx, (size_t)kFieldTile) * a.tiles_y;
+    a.n_tiles = (int)div_up((size_t)nx, (size_t)kFieldTile) * a.tiles_y;
     a.every = every;
     a.with_walls = f.cfg.with_walls && c->nw > 0 ? 1 : 0;
-    // workgroups of one channel's sample
-    const unsigned blocks = div_up((size_t)a.n_tiles, (size_t)(kFieldBlock / 64));
-    launch_forms(c, "k_field_map", Forms{k_field_map, k_field_map_b}, blocks, kFieldBlock, 0, q, c->grid, per_member(c->phys), s,
-                 c->walls, a);
+    return a;
+}
+
+// workgroups of one channel's sample (at least one: it writes the head)
+unsigned field_map_blocks(const FieldMapArgs &a)
+{
+    return std::max<unsigned>(div_up((size_t)a.n_tiles, (size_t)(kFieldBlock / 64)), 1u);
+}
+
+// k_field_map on state s (pos, vel and the cell ranges of the layout it is stored in) -- of a batch: member 0's -- into c->fmap
+void launch_field_map(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    const FieldMapArgs a = field_map_args(c, c->fmap.nx, every);
+    launch_forms(c, "k_field_map", Forms{k_field_map, k_field_map_b}, field_map_blocks(a), kFieldBlock, 0, q, c->grid,
+                 per_member(c->phys), s, c->walls, a);
 }
 
 }  // namespace
@@ -454,8 +465,11 @@ void FieldMap::alloc(const FieldMap &checked, int M)
     cfg = checked.cfg;
     nx = checked.nx;
     ny = checked.ny;
+    part = checked.part;
+    i_lo = checked.i_lo;
+    i_hi = checked.i_hi;
     members = M;
-    planes.alloc(block() * M);
+    planes.alloc(std::max<size_t>(block() * M, 1));  // (a slab that owns no node column still has a head)
     head.alloc(M);
 }
 
@@ -467,7 +481,7 @@ void FieldMap::read(hipStream_t st, int stride, double *const out[kFieldPlanes],
     const int M = members;
     std::vector<FieldMapHead> h(M);
     for (int j = 0; j < kFieldPlanes; ++j)
-        if (out[j])
+        if (out[j] && nodes() > 0)
             for (int m = 0; m < M; ++m)
                 SPHX_HIP(hipMemcpyAsync(out[j] + (size_t)m * stride, planes.get() + (size_t)m * block() + (size_t)j * nodes(),
                                         nodes() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -558,6 +572,9 @@ SPHX_EXPORT int sphx_ctx_field_map_read(sphx_ctx *c, int capacity, int *nx, int 
 // sphx_slab_group_run): a slab samples the particles it OWNS, what it keeps are partial sums, and the ring's value is the sum
 // over its slabs.  The configurations, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* identifiers are a
 // context's (sections 2a, 2d); sphx_ctx_flow_stats_* / sphx_ctx_history_* keep refusing a slab.
+// The velocity-field map: a node's sample is a ratio, so partial sums over owned particles cannot be pooled -- the NODES are
+// divided among the slabs instead, a slab computes the complete sample of every node column it owns (field_block) from its
+// owned particles and its halo copies, and the ring's map is the slabs' blocks side by side.
 
 namespace {
 
@@ -568,7 +585,7 @@ namespace {
 // on the slab's stream; both off: nothing is enqueued.
 void launch_slab_samplers(sphx_ctx *c)
 {
-    if (!c->fstats.on && !c->hist.on) return;
+    if (!c->fstats.on && !c->hist.on && !c->fmap.on) return;
     const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
     const FluidSet s = c->view(1 - q, 0);
@@ -579,6 +596,40 @@ void launch_slab_samplers(sphx_ctx *c)
     if (c->hist.on)
         launch_s(c, "k_step_history_s", k_step_history_s, dim3(history_blocks((size_t)c->cap)), dim3(kHistoryBlock), 0, clk, q, c->grid,
                  c->phys, s, c->tmp, c->walls, history_args(c, kHistoryInPlace), c->nf);
+    // (pos, vel and the cell ranges of S[1-q]: the halo copies binned in the columns own - 1 and own + 1, which the clamped sweep
+    //  reads beside the owned ones, were stepped like everything held and carry the finished step's state, DESIGN.md section 5;
+    //  workgroups from the block of node columns, fixed at enable)
+    if (c->fmap.on) {
+        const FieldMap &f = c->fmap;
+        FieldMapArgs a = field_map_args(c, f.cols(), c->fmap.cfg.every);
+        a.step_x = c->prm.DL / (f.nx - 1);  // (the ring's grid, not the block's)
+        a.with_walls = f.cfg.with_walls && c->walls.n > 0 ? 1 : 0;
+        launch_s(c, "k_field_map_s", k_field_map_s, dim3(field_map_blocks(a)), dim3(kFieldBlock), 0, clk, q, c->grid, c->phys, s,
+                 c->walls, a, f.i_lo, f.nx);
+    }
+}
+
+// The block of node columns [i_lo, i_hi) of the ring's nx that slab c samples.  One monotone rule from the global cell-column
+// boundaries, the same arithmetic on every rank: rank r's block starts at the first node column at or right of the left edge
+// of its first cell column, x_i >= ((r * ncx_ring) / n_ranks) * (DL / ncx_ring) with x_i as the kernel and numpy's linspace
+// make it; rank 0 starts at 0 and the last rank ends at nx, so node nx - 1 (x = DL) is the last slab's.  Rank r's i_hi is
+// rank r + 1's i_lo by construction: the blocks partition [0, nx) wherever a node column falls, on a cut included, and no
+// kernel tests ownership in its own frame.
+void field_block(const sphx_ctx *c, int nx, int &i_lo, int &i_hi)
+{
+    const double DL = c->prm.DL, step = DL / (nx - 1), csx = DL / c->ncx_ring;
+    auto first_node = [&](int r) {
+        if (r <= 0) return 0;
+        if (r >= c->n_ranks) return nx;
+        const double edge = (double)(((long long)r * c->ncx_ring) / c->n_ranks) * csx;
+        int i = std::clamp((int)std::ceil(edge / step), 0, nx);
+        auto x_of = [&](int k) { return k == nx - 1 ? DL : (double)k * step; };
+        while (i > 0 && x_of(i - 1) >= edge) --i;   // (the quotient's rounding: settle on the nodes' own coordinates)
+        while (i < nx && x_of(i) < edge) ++i;
+        return i;
+    };
+    i_lo = first_node(c->rank);
+    i_hi = first_node(c->rank + 1);
 }
 
 // a slab of the native loops, or SPHX:Slab:ctx / SPHX:Slab:protocol
@@ -692,6 +743,56 @@ SPHX_EXPORT int sphx_slab_history_read(sphx_ctx *c, int capacity, double *record
     History &h = slab_sampler_on(sampled_slab(c), &sphx_ctx::hist, kHistoryNames);
     slab_settle(c);  // (the records of everything enqueued)
     h.read(c->stream, capacity, records, n_records, n_dropped, drain != 0);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_field_map_enable(sphx_ctx *c, const sphx_field_map_config *cfg)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    FieldMap checked;
+    checked.check(c->prm, cfg, 1);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
+    checked.part = true;
+    field_block(c, checked.nx, checked.i_lo, checked.i_hi);
+    slab_samplers_changed(c);
+    sampler_on(c->fmap, kFieldNames, c->sched, c->stream, [&] { c->fmap.alloc(checked, 1); });
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_field_map_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    if (c->fmap.on) {
+        slab_samplers_changed(c);
+        sampler_off(c->fmap, c->sched, c->stream);
+    }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_field_map_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    FieldMap &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::fmap, kFieldNames);
+    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_field_map_read(sphx_ctx *c, int capacity, int *nx, int *ny, int *i_lo, int *i_hi, double *count,
+                                         double *sum_w, double *sum_ux, double *sum_uy, double *sum_ux2, double *sum_uy2,
+                                         int64_t *n_samples, double *t_first, double *t_last)
+{
+    SPHX_TRY
+    const FieldMap &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::fmap, kFieldNames);
+    field_read(f, c->stream, [c] { slab_settle(c); }, capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples,
+               t_first, t_last);
+    if (i_lo) *i_lo = f.i_lo;
+    if (i_hi) *i_hi = f.i_hi;
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -15,7 +15,8 @@ Layers:
   HipSlabEngine    -- the per-rank compute engine (libsphx slab context)
   SlabDriver       -- step loop = engine.compute -> exchange -> engine.finish
   pool_ring_* / ring_* / all_reduce_ring_*
-                   -- the ring's flow statistics and step history from the slabs' partial sums
+                   -- the ring's flow statistics and step history from the slabs' partial sums, and its field map from the
+                      slabs' blocks of node columns
   bench_main()     -- bench.py's multi-GPU leg
 """
 from __future__ import annotations
@@ -29,7 +30,7 @@ import time
 import numpy as np
 
 from . import capi as _capi
-from .profile import flow_stats_profile
+from .profile import FIELD_MAP_PLANES, field_map_means, flow_stats_profile
 
 HALO_COLS = 4  # four dependent neighbour passes per step, each reaching one >=2h column further
 
@@ -118,8 +119,10 @@ class HipSlabEngine(_capi._Sampled):
     Native engines (the library's own loops) have a context's flow_stats_enable / _disable / _reset / flow_stats_sums(band) and
     history_enable / _disable / history_records(drain) (capi._Sampled; include/sphx.h section 3a), recorded inside run() /
     group_run().  What they return are this slab's PARTIAL sums over the particles it owns: pool_ring_sums / pool_ring_history
-    (ring_flow_stats / ring_history, all_reduce_ring_*) make the ring's.  Enabling or disabling drops a graph made by
-    graph_prepare()."""
+    (ring_flow_stats / ring_history, all_reduce_ring_*) make the ring's.  field_part_enable / _disable / _reset /
+    field_part_sums are the velocity-field map: the complete planes of the node columns this slab owns, a PART of the ring's
+    map, which pool_ring_field_map (ring_field_map, all_reduce_ring_field_map) puts together.  Enabling or disabling drops a
+    graph made by graph_prepare()."""
     _stem, _where = "sphx_slab_", "slab"
 
     def __init__(self, prm, parts, rank, world, device, lanes_per_particle=0, halo_cols=HALO_COLS, t_end=None,
@@ -239,6 +242,50 @@ class HipSlabEngine(_capi._Sampled):
         arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
         capi.check(capi.lib().sphx_slab_graph_prepare(arr, C.c_int(len(engines))))
 
+    # ---- field map (include/sphx.h section 3a): the node columns this slab owns -- a PART of the ring's map ----
+    def field_part_enable(self, nx=0, ny=0, every=1, t_from=0.0, with_walls=False):
+        """A context's field_map_enable (capi._Stepped) for the ring's nx x ny grid; this slab samples the node columns
+        i_lo <= i < i_hi it owns -- every one completely, from its owned particles and its halo copies -- inside run() /
+        group_run().  (Re)configures and zeroes the planes; drops a graph made by graph_prepare()."""
+        cfg = self.capi.field_map_config(nx, ny, every, t_from, with_walls)
+        shape = self.capi.field_map_shape(self.params, nx, ny)
+        self._call("field_map_enable", C.byref(cfg))
+        self._field_part = shape  # (nx, ny) of the ring's grid while the field map is on
+
+    def field_part_disable(self):
+        self._call("field_map_disable")
+        self._field_part = None
+
+    def _field_part_on(self):
+        return _capi._enabled(getattr(self, "_field_part", None), "Field", "the field map is not enabled on this slab")
+
+    def field_part_reset(self):
+        self._field_part_on()
+        self._call("field_map_reset")
+
+    def field_part_sums(self) -> dict:
+        """The raw planes count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2 of this slab's block as [ny, i_hi - i_lo] arrays,
+        plus i_lo, i_hi, nx, ny (the ring's grid) and n_samples, t_first, t_last.  pool_ring_field_map puts the ranks' blocks
+        side by side."""
+        nx, ny = self._field_part_on()
+        gx, gy, lo, hi = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        ns, t0, t1 = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+
+        def read(cap, arrs):
+            self._call("field_map_read", C.c_int(cap), C.byref(gx), C.byref(gy), C.byref(lo), C.byref(hi),
+                       *[_capi.ptr(a) for a in arrs], C.byref(ns), C.byref(t0), C.byref(t1))
+
+        read(0, [None] * len(FIELD_MAP_PLANES))  # the block's range first: it fixes the size of the planes
+        assert (gx.value, gy.value) == (nx, ny), (gx.value, gy.value, nx, ny)
+        cols = hi.value - lo.value
+        arrs = [np.zeros(cols * ny) for _ in FIELD_MAP_PLANES]
+        read(cols * ny, arrs)
+        # node (i, k) at (i - i_lo) * ny + k: the rows of the [ny, cols] array are the y-levels
+        out = {f: np.ascontiguousarray(a.reshape(cols, ny).T) for f, a in zip(FIELD_MAP_PLANES, arrs)}
+        out.update(i_lo=lo.value, i_hi=hi.value, nx=nx, ny=ny, n_samples=int(ns.value), t_first=float(t0.value),
+                   t_last=float(t1.value))
+        return out
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self.capi.lib().sphx_ctx_destroy(self._h)
@@ -306,6 +353,56 @@ def ring_history(engines, drain=False) -> dict:
     return pool_ring_history([e.history_records(drain) for e in engines])
 
 
+def _check_blocks_partition(shapes):
+    """shapes: [(nx, ny, i_lo, i_hi)] per rank -- the blocks of one nx x ny grid, side by side from 0 to nx."""
+    nx, ny = int(shapes[0][0]), int(shapes[0][1])
+    at = 0
+    for r, (gx, gy, lo, hi) in enumerate(shapes):
+        gx, gy, lo, hi = int(gx), int(gy), int(lo), int(hi)
+        if (gx, gy) != (nx, ny):
+            raise ValueError(f"rank {r} maps {gx} x {gy} nodes, rank 0 {nx} x {ny}: the slabs of one ring share the grid")
+        if hi < lo or lo != at:
+            how = "is reversed" if hi < lo else ("overlaps" if lo < at else "leaves a gap behind")
+            raise ValueError(f"rank {r}: block [{lo}, {hi}) {how} the node columns [0, {at}) of the ranks before it")
+        at = hi
+    if at != nx:
+        raise ValueError(f"the blocks end at node column {at}, the grid has {nx}: " + ("a gap" if at < nx else "an overlap"))
+
+
+def _block_shape(part):
+    """(nx, ny, i_lo, i_hi) of one rank's part, whose six planes must be [ny, i_hi - i_lo]"""
+    nx, ny, lo, hi = (int(part[k]) for k in ("nx", "ny", "i_lo", "i_hi"))
+    for k in FIELD_MAP_PLANES:
+        if np.shape(part[k]) != (ny, hi - lo):
+            raise ValueError(f"plane {k} has shape {np.shape(part[k])}, the block [{lo}, {hi}) of {ny} rows needs {(ny, hi - lo)}")
+    return nx, ny, lo, hi
+
+
+def pool_ring_field_map(parts) -> dict:
+    """The ring's field-map planes (the sums dict of capi.Context.field_map_sums: six [ny, nx] planes, n_samples, t_first,
+    t_last) from the ranks' parts (HipSlabEngine.field_part_sums, in rank order): every node column belongs to exactly one
+    slab, which holds its complete sums, so the blocks are placed side by side -- nothing is added.  ValueError when the
+    blocks leave a gap, overlap, do not fit the grid, or n_samples, t_first, t_last differ between the ranks (a slab without
+    a node still counts the samples)."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("the field map of a ring needs the part of at least one slab")
+    _check_blocks_partition([_block_shape(p) for p in parts])
+    ny = int(parts[0]["ny"])
+    _check_heads_agree([tuple(p[k] for k in _HEAD) for p in parts])
+    out = {k: np.ascontiguousarray(np.concatenate([np.asarray(p[k], dtype=np.float64).reshape(ny, -1) for p in parts], axis=1))
+           for k in FIELD_MAP_PLANES}
+    out.update({k: parts[0][k] for k in _HEAD})
+    return out
+
+
+def ring_field_map(engines) -> dict:
+    """The time-averaged velocity-field map of an in-process ring (profile.field_map_means of the pooled planes): what
+    driver.field_figures takes."""
+    p = engines[0].params
+    return field_map_means(p.DL, p.DH, **pool_ring_field_map([e.field_part_sums() for e in engines]))
+
+
 def _all_gathered(dist, row, group):
     """[world x len(row)] float64: every rank's row (control plane: CPU tensors, gloo)."""
     import torch
@@ -344,6 +441,25 @@ def all_reduce_ring_history(records, dist, group=None) -> dict:
     out = rec.copy()
     out[:, _CLOCK_FIELDS:] = _all_reduced(dist, rec[:, _CLOCK_FIELDS:], group)
     return _capi.history_dict(out, records[1])
+
+
+def all_reduce_ring_field_map(part, dist, group=None) -> dict:
+    """One rank per process: the ring's field-map planes from this rank's part, as pool_ring_field_map; every rank gets them.
+    The block ranges and the heads are all-gathered and checked first; then every rank pads its block with zeros to
+    [6, ny, nx] and the padded arrays are all-reduced -- every node has one contributor and x + 0.0 is x, so the result is
+    bit for bit the blocks side by side.  Collective; raises on every rank when the blocks do not partition [0, nx) or the
+    ranks' n_samples, t_first or t_last differ."""
+    nx, ny, lo, hi = _block_shape(part)
+    rows = _all_gathered(dist, [float(v) for v in (nx, ny, lo, hi)] + [float(part[k]) for k in _HEAD], group)
+    _check_blocks_partition([tuple(r[:4]) for r in rows])
+    _check_heads_agree([tuple(r[4:]) for r in rows])
+    padded = np.zeros((len(FIELD_MAP_PLANES), ny, nx))
+    for j, k in enumerate(FIELD_MAP_PLANES):
+        padded[j, :, lo:hi] = part[k]
+    total = _all_reduced(dist, padded, group)
+    out = {k: np.ascontiguousarray(total[j]) for j, k in enumerate(FIELD_MAP_PLANES)}
+    out.update({k: part[k] for k in _HEAD})
+    return out
 
 
 class SlabDriver:

@@ -1,0 +1,70 @@
+"""Worker for test_slab_field_map_host.py (CPU, gloo, two ranks): every rank holds one block of node columns of a particle
+set's Shepard planes; slab.all_reduce_ring_field_map must leave the whole planes on both, bit for bit what
+slab.pool_ring_field_map makes of the two blocks, and must raise on both when the heads differ or the blocks do not partition
+the grid.  Prints OK on every rank that saw all of it."""
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PLANES = ("count", "sum_w", "sum_ux", "sum_uy", "sum_ux2", "sum_uy2")
+
+
+def blocks(cut=5, nx=13, ny=6, n=600, DL=3.0, DH=1.0, h=0.13):
+    profile = importlib.import_module("sph-poiseuille-flow_amd.profile")
+    rng = np.random.default_rng(23)  # (the same on both ranks)
+    pos = np.column_stack([rng.uniform(0, DL, n), rng.uniform(0, DH, n)])
+    vel = np.column_stack([rng.normal(1.0, 0.3, n), rng.normal(0.0, 0.1, n)])
+    f = profile.shepard_field(pos, vel, DL, DH, h, nx, ny)
+    hit = f["S0"] > 0.0
+    z = lambda v: np.where(hit, v, 0.0)
+    whole = dict(zip(PLANES, (hit.astype(np.float64), z(f["S0"]), z(f["u_x"]), z(f["u_y"]), z(f["u_x"] ** 2), z(f["u_y"] ** 2))))
+    head = dict(n_samples=3, t_first=0.125, t_last=0.375)
+    parts = [dict({k: np.ascontiguousarray(whole[k][:, lo:hi]) for k in PLANES}, i_lo=lo, i_hi=hi, nx=nx, ny=ny, **head)
+             for lo, hi in ((0, cut), (cut, nx))]
+    return parts, whole
+
+
+def main():
+    import torch.distributed as dist
+    rank = int(os.environ["RANK"])
+    dist.init_process_group("gloo")
+    slab = importlib.import_module("sph-poiseuille-flow_amd.slab")
+    parts, whole = blocks()
+    ok = True
+
+    got = slab.all_reduce_ring_field_map(parts[rank], dist)
+    want = slab.pool_ring_field_map(parts)
+    ok &= all(got[k].tobytes() == want[k].tobytes() == whole[k].tobytes() and got[k].shape == whole[k].shape for k in PLANES)
+    ok &= (got["n_samples"], got["t_first"], got["t_last"]) == (3, 0.125, 0.375)
+
+    for bad in (dict(n_samples=4), dict(t_first=0.25)):  # rank 1 disagrees: BOTH ranks must hear about it
+        try:
+            slab.all_reduce_ring_field_map(dict(parts[rank], **(bad if rank == 1 else {})), dist)
+            ok = False
+        except ValueError:
+            pass
+    # rank 1's block starts one column late (a gap) or one early (an overlap)
+    for shift in (1, -1):
+        p = parts[rank]
+        if rank == 1:
+            lo = p["i_lo"] + shift
+            p = dict(p, i_lo=lo, **{k: np.ascontiguousarray(whole[k][:, lo:]) for k in PLANES})
+        try:
+            slab.all_reduce_ring_field_map(p, dist)
+            ok = False
+        except ValueError:
+            pass
+
+    print(f"rank {rank}: {'OK' if ok else 'WRONG'}", flush=True)
+    dist.barrier()
+    dist.destroy_process_group()
+    sys.exit(0 if ok else 1)
+
+
+if __name__ == "__main__":
+    main()
