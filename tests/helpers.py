@@ -96,6 +96,65 @@ def field_atol(prm, parts, nb, dt):
                 B=1e-12, zeros=0.0)
 
 
+# ---- the eight modes of the stateless surface on one pair list ----
+def oracle_surface(oracle):
+    """oracle/oracle.py behind the call form of mex_surface.sph_physics_shell_mex(mode, pair columns..., arguments...)."""
+    def phys(mode, *a):
+        if mode in ("density_correction", "advance_shell_step"):
+            return getattr(oracle, mode)(tuple(a[:7]), *a[7:])
+        return getattr(oracle, mode)(tuple(a[:5]) + (a[5], a[5]), *a[6:])  # no W column: the six-column modes do not read it
+    return phys
+
+
+def modes_dt(prm):
+    return 0.25 * prm.h / (prm.c_f + 1.0)
+
+
+def run_modes(phys, prm, parts, nb, h=None, given=None, monitor_nb=None):
+    """The eight modes on the pair list nb, chained as test_reference_anchor.check_modes chains them: density, viscous,
+    transport (12 arguments, then with a coefficient), integration_1st, integration_2nd on the kicked velocity,
+    integration_verlet, advance_shell_step, wall_shear_monitor.  -> {name: output}.  Every mode takes the outputs of the modes
+    before it from `given` (the dict of an earlier run, the oracle's say, so that two sides are compared mode by mode on
+    identical inputs) or, without one, from this run.  h replaces prm.h wherever a mode takes h (a list built with a wider
+    kernel); monitor_nb is the list wall_shear_monitor gets where it is not nb."""
+    nf, nt = parts["n_fluid"], parts["n_total"]
+    mass, pos, vel, wv, drho = (parts[k] for k in ("mass", "pos", "vel", "wall_vel", "drho_dt"))
+    h = prm.h if h is None else h
+    nb = tuple(nb)
+    p6 = nb[:5] + (nb[6],)
+    out = {}
+
+    def put(prefix, names, values):
+        for n, v in zip(names, values):
+            out[prefix + n] = v
+
+    def src(name):
+        return (out if given is None else given)[name]
+
+    put("density.", ("rho", "Vol", "B"), phys("density_correction", *nb, mass, nf, nt, prm.rho0, h, prm.inv_sigma0))
+    rho, Vol, B = src("density.rho"), src("density.Vol"), src("density.B")
+    out["viscous"] = phys("viscous_force", *p6, vel, Vol, B, prm.mu, h, nf, nt, mass, wv)
+    out["transport()"] = phys("transport_correction", *p6, Vol, B, pos, h, nf, nt)
+    for coeff in (0.3, prm.transport_coeff):
+        out[f"transport({coeff})"] = phys("transport_correction", *p6, Vol, B, pos, h, nf, nt, coeff)
+    fp = np.array(src("viscous"), order="F")
+    fp[:nf, 0] += mass[:nf] * prm.gravity_g
+    dt = modes_dt(prm)
+    common = (Vol, B, rho, mass, pos, vel, drho, fp, dt, nf, nt, prm.rho0, prm.p0, prm.c_f, wv)
+    put("int1.", ("rho", "p", "pos", "force", "drho"), phys("integration_1st", *p6, *common))
+    vel_new = vel.copy(order="F")
+    vel_new[:nf] += (fp[:nf] + src("int1.force")[:nf]) / mass[:nf, None] * dt
+    put("int2.", ("pos", "drho", "zeros"),
+        phys("integration_2nd", *p6, Vol, src("int1.rho"), src("int1.pos"), vel_new, dt, nf, nt, wv))
+    put("verlet.", ("rho", "p", "pos", "vel", "drho", "force"), phys("integration_verlet", *p6, *common))
+    tail = (mass, pos, vel, wv, rho, drho, dt, nf, nt, prm.rho0, prm.p0, prm.c_f, prm.mu, h, prm.inv_sigma0, prm.gravity_g)
+    put("advance.", ("rho", "p", "pos", "vel", "drho", "force", "force_prior", "Vol", "B"),
+        phys("advance_shell_step", *nb, *tail))
+    m = nb if monitor_nb is None else tuple(monitor_nb)
+    out["tau"] = np.array(phys("wall_shear_monitor", *m[:5], m[6], pos, vel, wv, Vol, B, nf, prm.DL, prm.DH, prm.mu, h))
+    return out
+
+
 # ---- what several GPU test files share ----
 HISTORY_FIELDS = ("step", "t", "dt", "vmax", "tau_bottom", "tau_top", "kinetic_energy", "u_bulk")
 STATS_FIELDS = ("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2")

@@ -3,7 +3,9 @@
 Tolerance: the reference computes in IEEE double; the HIP kernels use the same formulas and differ only
 in summation order and FMA contraction, so per-mode outputs must agree to rtol 1e-11 (+1e-13 of the
 field's magnitude) -- SURVEY.md section 8c's parity protocol.  Neighbour lists compare as sets: exact on
-membership, 1e-14 relative on dx,dy,r and 1e-12 on W,dW.
+membership, 1e-14 relative on dx,dy,r and 1e-12 on W,dW.  The modes get the list oracle.neighbor_search writes here; lists of
+any other shape (shuffled, either side first, skipped, repeated or coincident rows, empty and long rows) are in
+tests/test_gpu_pair_list_contract.py.
 """
 import numpy as np
 import pytest
