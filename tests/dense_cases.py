@@ -1,0 +1,167 @@
+"""States whose neighbour lists are long, up to the capacity of the device's list rows, and a census that proves it.
+
+The default states (helpers.make_case / make_variant) are lattices with a uniform jitter of at most 0.3 dp: at most 24
+neighbours inside 2h and at most 54 inside the superset radius 2h + 1.05h, a quarter of what a list row holds
+(nl_cap_for in csrc/sphx_resident.hip: 96 / 96 / 96 / 128 / 256 / 512 entries per particle at 1 / 2 / 4 / 8 / 16 / 32 lanes per
+particle, the superset list 1.5 times that).  The cases here pull the fluid towards two centres -- mid-channel and the periodic
+seam next to the bottom wall -- so that lists run to 59 (A), 89 (B) and 106 (C) entries, cell columns hold uneven loads and
+voids open next to the dense cores; and they put an isolated cluster of N particles into a hole, in which every member has
+exactly N - 1 neighbours: the capacity boundary itself.  census() measures, with the oracle and numpy alone, that a case does
+what it is for; tests/test_dense_cases.py asserts it, so a case cannot silently stop doing its job.
+
+Shared by tests/test_dense_cases.py, test_gpu_dense_lists.py, test_slab.py and the switch worker.  A plain module: no
+fixtures."""
+import numpy as np
+
+from helpers import make_variant
+
+# the small state (dp 0.04: 950 fluid particles) and tests/switch_worker.py's state
+SIZES = {"small": dict(dp=0.04, DL=1.5, jitter=0.2, seed=11), "worker": dict(dp=0.025, DL=1.5, jitter=0.25, seed=31)}
+VARIANT = dict(developed=True, rho0=2.5, transport_coeff=0.1)
+PULLS = {"A": (0.55, 0.30), "B": (0.45, 0.40), "C": (0.40, 0.45)}   # name -> (s, R)
+SEAM_Y = 0.12
+# csrc/sphx_resident.hip, nl_cap_for: list entries per particle by lanes per particle; the superset list holds 1.5 x that
+LIST_CAPACITY = {1: 96, 2: 96, 4: 96, 8: 128, 16: 256, 32: 512}
+
+
+def plain(cfgmod, geom, size):
+    """The moving-wall variant the pulls start from: what the dense cases are the opposite of."""
+    return make_variant(cfgmod, geom, **SIZES[size], **VARIANT)
+
+
+def centres(prm):
+    return [(0.5 * prm.DL, 0.5 * prm.DH), (0.0, SEAM_Y)]
+
+
+def pull(prm, parts, centre, s, R):
+    """A copy of parts whose fluid particles within R of centre (nearest periodic image) are pulled towards it: distance r
+    becomes r (s + (1 - s) (r / R)^4), continuous at r = R and a contraction by s at the centre.  x is wrapped into [0, DL), y
+    clipped into the channel.  Keeps n_fluid, the velocities and the row order."""
+    nf = parts["n_fluid"]
+    pos = parts["pos"].copy(order="F")
+    dx = pos[:nf, 0] - centre[0]
+    dx -= prm.DL * np.round(dx / prm.DL)
+    dy = pos[:nf, 1] - centre[1]
+    r = np.hypot(dx, dy)
+    f = np.where(r < R, s + (1.0 - s) * (r / R) ** 4, 1.0)
+    x = centre[0] + f * dx
+    x -= np.floor(x / prm.DL) * prm.DL
+    pos[:nf, 0] = np.where(x >= prm.DL, x - prm.DL, x)
+    pos[:nf, 1] = np.clip(centre[1] + f * dy, 0.0, prm.DH)
+    return dict(parts, pos=pos)
+
+
+def pulled(prm, parts, s, R, at=None):
+    """Both pulls, mid-channel first: (DL / 2, DH / 2) and the seam next to the bottom wall, (0, SEAM_Y); `at` replaces the
+    centres."""
+    for c in (centres(prm) if at is None else at):
+        parts = pull(prm, parts, c, s, R)
+    return parts
+
+
+def patched(cfgmod, geom, size, s, R):
+    prm, parts = plain(cfgmod, geom, size)
+    return prm, pulled(prm, parts, s, R)
+
+
+def A(cfgmod, geom, size):
+    return patched(cfgmod, geom, size, *PULLS["A"])
+
+
+def B(cfgmod, geom, size):
+    return patched(cfgmod, geom, size, *PULLS["B"])
+
+
+def C(cfgmod, geom, size):
+    return patched(cfgmod, geom, size, *PULLS["C"])
+
+
+CASES = {"A": A, "B": B, "C": C}
+
+
+def cluster(cfgmod, geom, n, d_h=1.9, clear_h=3.2):
+    """n particles on a Vogel spiral of diameter d_h h (r_k = d/2 sqrt((k + 0.5) / n), angle k pi (3 - sqrt 5)) at mid-channel
+    of the worker's variant, in a hole: every fluid particle within d/2 + clear_h h of the centre is removed.  d < 2h, so every
+    member has the n - 1 others inside 2h and, the hole being wider than the superset radius, nobody else.  The cluster rows
+    follow the remaining fluid rows (at rest, drho_dt 0, the lattice mass); wall rows come last.  -> (prm, parts), parts with
+    the keys a context takes."""
+    prm, p = plain(cfgmod, geom, "worker")
+    nf, nt = p["n_fluid"], p["n_total"]
+    c = np.array([0.5 * prm.DL, 0.5 * prm.DH])
+    d = d_h * prm.h
+    keep = np.flatnonzero(np.hypot(p["pos"][:nf, 0] - c[0], p["pos"][:nf, 1] - c[1]) > 0.5 * d + clear_h * prm.h)
+    k = np.arange(n)
+    rk, ang = 0.5 * d * np.sqrt((k + 0.5) / n), k * np.pi * (3.0 - np.sqrt(5.0))
+    spiral = np.column_stack([c[0] + rk * np.cos(ang), c[1] + rk * np.sin(ang)])
+    rows = lambda a, new: np.asfortranarray(np.concatenate([a[keep], new, a[nf:]]))
+    z2, z1 = np.zeros((n, 2)), np.zeros(n)
+    parts = dict(n_fluid=len(keep) + n, n_total=len(keep) + n + nt - nf, n_wall=nt - nf, n_cluster=n,
+                 pos=rows(p["pos"], spiral), vel=rows(p["vel"], z2), wall_vel=rows(p["wall_vel"], z2),
+                 drho_dt=rows(p["drho_dt"], z1), mass=rows(p["mass"], np.full(n, prm.rho0 * prm.dp ** 2)))
+    return prm, parts
+
+
+def cluster_rows(parts):
+    nf = parts["n_fluid"]
+    return np.arange(nf - parts["n_cluster"], nf)
+
+
+def list_lengths(oracle, prm, parts, pos=None, radius_h=2.0):
+    """Neighbours (fluid and wall) of every fluid particle inside radius_h h, by the oracle's search."""
+    nf, nt = parts["n_fluid"], parts["n_total"]
+    pos = parts["pos"] if pos is None else pos
+    pi, pj = oracle.neighbor_search(pos, nf, nt, 0.5 * radius_h * prm.h, prm.DL)[:2]
+    i, j = pi.astype(np.int64) - 1, pj.astype(np.int64) - 1
+    return np.bincount(np.concatenate([i, j[j < nf]]), minlength=nf)[:nf]
+
+
+def column_loads(prm, x, skin_h):
+    """Fluid particles per cell column at the column width DL / floor(DL / (2h + skin_h h)) -> (largest column, largest three
+    adjacent columns, periodic)."""
+    ncx = max(int(np.floor(prm.DL / ((2.0 + skin_h) * prm.h))), 1)
+    col = np.minimum((np.asarray(x) / (prm.DL / ncx)).astype(np.int64), ncx - 1)
+    load = np.bincount(col, minlength=ncx)
+    three = load + np.roll(load, 1) + np.roll(load, -1) if ncx >= 3 else np.full(1, load.sum())
+    return int(load.max()), int(three.max())
+
+
+def census(oracle, prm, parts, n_steps, skin_h=1.05):
+    """For k = 0 .. n_steps - 1, at the positions the oracle holds after k steps (those step k + 1 builds its lists from), one
+    array entry per k:
+      list_max, list_min   the longest and the shortest list (radius 2h) of a fluid particle
+      over32, over64       how many fluid particles have more than 32 / 64 neighbours
+      superset_max         the longest list at radius 2h + skin_h h; over144, over192: how many exceed 144 / 192
+      column_max, three_columns_max   column_loads()
+    and lengths0 (every fluid particle's list length at k = 0), vmax, rho_max and finite over the states passed through."""
+    nf = parts["n_fluid"]
+    keys = ("list_max", "list_min", "over32", "over64", "superset_max", "over144", "over192", "column_max", "three_columns_max")
+    out = {k: [] for k in keys}
+    pos, vel, drho, t = parts["pos"], parts["vel"], parts["drho_dt"], 0.0
+    vmax, rho_max, finite = 0.0, 0.0, True
+    for k in range(n_steps):
+        n2 = list_lengths(oracle, prm, parts, pos)
+        ns = list_lengths(oracle, prm, parts, pos, 2.0 + skin_h)
+        if k == 0:
+            out["lengths0"], out["superset0"] = n2, ns
+        cm, c3 = column_loads(prm, pos[:nf, 0], skin_h)
+        for key, v in zip(keys, (n2.max(), n2.min(), np.count_nonzero(n2 > 32), np.count_nonzero(n2 > 64), ns.max(),
+                                 np.count_nonzero(ns > 144), np.count_nonzero(ns > 192), cm, c3)):
+            out[key].append(int(v))
+        if k == n_steps - 1:
+            break
+        st = oracle.run(prm, parts, t_end=1e9, output_interval=1e9, max_steps=1, enable_sort=False, pos=pos, vel=vel,
+                        drho_dt=drho, t0=t, step0=k)
+        pos, vel, drho, t = st["pos"], st["vel"], st["drho_dt"], st["stats"]["t"]
+        finite = finite and all(bool(np.all(np.isfinite(st[f]))) for f in ("pos", "vel", "rho", "p", "drho_dt", "force"))
+        vmax, rho_max = max(vmax, float(st["stats"]["vmax"])), max(rho_max, float(np.max(st["rho"][:nf])))
+    out = {k: (np.array(v) if k in keys else v) for k, v in out.items()}
+    out.update(vmax=vmax, rho_max=rho_max, finite=finite, n_steps=n_steps, skin_h=skin_h)
+    return out
+
+
+def census_line(name, c):
+    """One row of the census table the tests print."""
+    return (f"{name:>16}: list max {c['list_max'][0]:3d} at the start, {c['list_max'].max():3d} over {c['n_steps']} steps, "
+            f"{c['list_max'][-1]:3d} at the end; min {c['list_min'].min():2d}; > 32: {c['over32'][0]:4d}, > 64: {c['over64'][0]:4d}; "
+            f"superset max {c['superset_max'][0]:3d} / {c['superset_max'].max():3d} (> 144: {c['over144'][0]}, > 192: "
+            f"{c['over192'][0]}); column {c['column_max'].max()}, three columns {c['three_columns_max'].max()}; vmax {c['vmax']:.1f}")

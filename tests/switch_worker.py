@@ -1,7 +1,8 @@
 """Child process of tests/test_gpu_switches.py: SPHX_DEBUG_SWITCHES is read once per process, so every switch set runs in a
 fresh one.  Steps the moving-wall variant (helpers.make_variant: moving walls, uneven mass, rho0 = 2.5; 2 880 particles) or,
-with --case NAME, a regime case of tests/regime_cases.py at the same size (left_capped: the same variant mirrored, flowing to
-the left, with c_f = 0.3) across its re-binnings, compares every field with the oracle at the tolerances of test_gpu_resident.py and prints ONE JSON
+with --case NAME, a regime case of tests/regime_cases.py (left_capped: the same variant mirrored, flowing to the left, with
+c_f = 0.3) or a dense case of tests/dense_cases.py (A: the variant pulled towards two centres, lists of up to 69 entries and
+cell columns of up to 219 particles) at the same size across its re-binnings, compares every field with the oracle at the tolerances of test_gpu_resident.py and prints ONE JSON
 line: the kernel forms and the schedule the context chose, the worst error per field, and what failed.  Exit code 0: ran to the
 end (whatever the comparison said).
 
@@ -32,16 +33,18 @@ def main():
     ap.add_argument("--steps", type=int, default=35)
     ap.add_argument("--dynamic", action="store_true", help="dynamic re-binning, every 8th step")
     ap.add_argument("--dump", metavar="DIR", help="also write the downloaded fields and scalars as DIR/*.npy")
-    ap.add_argument("--case", default="", help="a name of tests/regime_cases.py's CASES at its worker size in place of the "
-                                               "moving-wall variant")
+    ap.add_argument("--case", default="", help="a name of tests/regime_cases.py's or tests/dense_cases.py's CASES at its worker "
+                                               "size in place of the moving-wall variant")
     args = ap.parse_args()
     import oracle
     from helpers import assert_close, make_variant
     pkg = importlib.import_module("sph-poiseuille-flow_amd")
     capi = pkg.capi
     if args.case:
+        import dense_cases
         import regime_cases
-        prm, parts = regime_cases.CASES[args.case](pkg.config, pkg.geometry, "worker")
+        cases = dict(regime_cases.CASES, **dense_cases.CASES)
+        prm, parts = cases[args.case](pkg.config, pkg.geometry, "worker")
     else:
         prm, parts = make_variant(pkg.config, pkg.geometry, dp=0.025, DL=1.5, jitter=0.25, seed=31, developed=True, rho0=2.5,
                                   transport_coeff=0.1)

@@ -20,7 +20,11 @@ force-pass, list or clock forms selected here would change nothing above.  test_
 sets that change the force pass, the lists or the clock once more on regime_cases.left_capped at the worker's size (--case):
 the same variant mirrored, c_f = 0.3.  Over its 35 steps the oracle counts 266 to 531 fluid pairs on the cap, 130 crossings of
 the seam to the left and the viscous limit on every step (tests/test_regime_cases.py asserts it); the flow outruns the cell
-skin, so drift-forced re-binnings and their cool-down are on the way as well."""
+skin, so drift-forced re-binnings and their cool-down are on the way as well.
+
+Both states load every cell column alike and keep their lists at a quarter of the capacity.
+test_switch_set_matches_oracle_dense runs the tile forms, both list codings, the compact kernels and the device-decided
+re-binning on dense_cases.A at the worker's size: long lists, uneven columns, voids."""
 import json
 import os
 import subprocess
@@ -71,6 +75,25 @@ def test_switch_set_matches_oracle(switches, lpp, dynamic, forms, fuse_ea, tail_
                          ids=[f"{s or 'none'}-lpp{l}{'-dyn' if d else ''}" for s, l, d, *_ in REGIME_SETS])
 def test_switch_set_matches_oracle_left_capped(switches, lpp, dynamic, forms, fuse_ea, tail_clock):
     _run_set(switches, lpp, dynamic, forms, fuse_ea, tail_clock, "left_capped")
+
+
+# the tile forms and both list codings, the compact kernels and the device-decided re-binning
+DENSE_SETS = [s for s in SETS if (s[0], s[1], s[2]) in {
+    ("", 2, False), ("tiles_be_from_1", 2, False), ("tiles_be_from_1,no_coded_lists", 2, False), ("no_lds_tiles", 2, False),
+    ("", 16, False), ("", 2, True)}]
+assert len(DENSE_SETS) == 6
+
+
+@pytest.mark.parametrize("switches,lpp,dynamic,forms,fuse_ea,tail_clock", DENSE_SETS,
+                         ids=[f"{s or 'none'}-lpp{l}{'-dyn' if d else ''}" for s, l, d, *_ in DENSE_SETS])
+def test_switch_set_matches_oracle_dense(switches, lpp, dynamic, forms, fuse_ea, tail_clock):
+    """dense_cases.A at the worker's size: the variant pulled towards mid-channel and towards the seam next to the bottom
+    wall.  Lists of up to 69 entries and a superset of up to 141 (of 96 and 144 at 2 lanes per particle); the fullest cell
+    column holds 219 particles and the fullest three adjacent ones 560 where every column of the variant holds 160 and 480,
+    so a workgroup's tile layout (three ranges capped at 480 or 464 slots) overflows, entries go out as far codes or index
+    differences, and the columns next to the cores run empty within a few steps (tests/test_dense_cases.py asserts the
+    census)."""
+    _run_set(switches, lpp, dynamic, forms, fuse_ea, tail_clock, "A")
 
 
 def _run_set(switches, lpp, dynamic, forms, fuse_ea, tail_clock, case):

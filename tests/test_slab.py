@@ -121,6 +121,11 @@ def test_slab_hip_two_ranks_half_million_particles():
     # (last in the list: the ids of the cases above stay as they were)
     (2, 0.05, 3.0, 47, dict(calls=[3, 25, 19], graph_after=0, overlap="always")),
     (3, 0.05, 4.5, 36, dict(calls=[4, 32], graph_after=0, rebuild_every=4, overlap="always")),
+    # dense_cases.A's two pulls on the moving-wall variant: one patch on the periodic seam next to the bottom wall, the other
+    # centred on the cut between the two slabs -- lists of 60 entries, halo columns of uneven load, and a burst that carries
+    # particles across both cuts
+    (2, 0.04, 3.0, 27, dict(dense=True, rebuild_every=5)),
+    (2, 0.04, 3.0, 27, dict(dense=True, rebuild_every=5, overlap="always")),
 ])
 def test_slab_native_ring_in_one_process(world, dp, DL, steps, kw):
     """The library's own step loop (sphx_slab_group_run: every slab of the ring in this process, device-to-device
@@ -141,6 +146,15 @@ def test_slab_native_ring_in_one_process(world, dp, DL, steps, kw):
         prm, parts = make_variant(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9,
                                   U_bulk=-0.666667, top_ux=-0.8, bottom_ux=0.3, rho0=2.5, transport_coeff=0.1)
         assert prm.gravity_g < 0 and np.all(parts["vel"][:parts["n_fluid"], 0] < 0)
+    elif kw.pop("dense", False):
+        import dense_cases
+        prm, parts = make_variant(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9,
+                                  rho0=2.5, transport_coeff=0.1)
+        ncx = slab.n_cell_columns(prm)
+        cut = slab.partition(ncx, world)[0][1] * prm.DL / ncx     # where rank 0's columns end and rank 1's begin
+        s_pull, r_pull = dense_cases.PULLS["A"]
+        assert 0.25 * prm.DL < cut < 0.75 * prm.DL
+        parts = dense_cases.pulled(prm, parts, s_pull, r_pull, at=[(cut, 0.5 * prm.DH), (0.0, dense_cases.SEAM_Y)])
     else:
         prm, parts = make_case(pkg.config, pkg.geometry, dp=dp, DL=DL, jitter=0.2, seed=11, developed=True, end_time=1e9)
     nf = parts["n_fluid"]
