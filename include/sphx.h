@@ -565,6 +565,103 @@ int sphx_batch_field_map_read(sphx_batch *batch, int capacity, int *nx, int *ny,
                               double *t_first, double *t_last);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2h. Point probes: the flow at fixed points, step by step, recorded on the device, inside the step loop.  The flow
+ *     statistics (section 2a) and the field map (2e) average time away, the step history (2d) has the time axis and no
+ *     place; a probe is resolved in both.  It is what shows a pulsation -- an acoustic wave sloshing across the channel is a
+ *     line in the spectrum of rho and u_y at a point -- without a download and a host interpolation per step.
+ *
+ *  Points: P of them, (x_p, y_p), 1 <= P <= SPHX_PROBE_MAX_POINTS, given at enable and copied.  x may be any finite value
+ *    and is folded into [0, DL) on the host (x - floor(x / DL) * DL; x = DL and x = -DL become 0); 0 <= y <= DH.
+ *  One sample at a point: the field map's sample at a node (section 2e) plus a density, from pos, vel and mass of the state
+ *    sphx_ctx_download would return and nothing else.  dx = minimum image of x_p - x_j, dy = y_p - y_j; a particle
+ *    contributes when dx^2 + dy^2 < (2h)^2 (no lower cut); W is the two-piece cubic spline of the physics; S0 = sum W,
+ *    S1 = sum W u_x, S2 = sum W u_y over the fluid particles, and Sm = sum m_j W_j.  with_walls = 1: the wall particles
+ *    enter S0, S1 and S2 with their wall velocity, exactly as in the map.  Sm is always the sum over the fluid particles
+ *    alone: the summation density from the fluid; within 2h of a wall it lacks the wall's share.
+ *  Values: SPHX_PROBE_FIELDS = 4 per probe and sample:
+ *    0 weight   S0 * dp^2 (about 1 inside the fluid)
+ *    1 u_x      S1 / S0
+ *    2 u_y      S2 / S0
+ *    3 rho      Sm (p0 * (rho / rho0 - 1) is a pressure)
+ *    Where S0 = 0 (no contributor): weight = 0, rho = 0 and both velocities are NaN -- the series' "no value".
+ *  Records: one per sampled step: `step` and `t` (two doubles, as the history stores them: sphx_status.step and .t after the
+ *    step) and the P x 4 values, in the arrays times[capacity][2] and values[capacity][P][4].  `capacity` records live in
+ *    device memory and are filled in step order; when the buffer is full further records are dropped and counted in
+ *    n_dropped; it does not wrap (the semantics of section 2d).  capacity >= 1, and capacity * P * 4 <= 1 << 27 doubles.
+ *  Gating: as in sections 2a / 2d / 2e.  A step is recorded when its step count (sphx_status.step after it) is a multiple
+ *    of `every` and it ends at t >= t_from.  Dual-rate contexts record once per outer step.  A step slot that did not run
+ *    records nothing.  sphx_ctx_probes_sample appends a record of the state now, without gating.
+ *  Determinism: one wave per probe; a lane adds its candidates in an order that depends on the particle layout only, the
+ *    lanes' sums are reduced in a fixed order; no floating-point atomics.  Two identical runs give bit-identical records;
+ *    another layout (another re-binning phase, e.g. after a stop on the drift bound) changes the summation order only.
+ *  Off by default.  With it off a step slot enqueues exactly the launches it does without this feature; on, every step slot
+ *    ends with one more launch (k_point_probes, behind k_field_map; it skips itself on the steps gated out) that is captured
+ *    in the replayed graphs; enable / disable re-capture them.  Independent of the other three samplers: all four may be on
+ *    at once.  Batches (section 2b) record one series per member: section 2i.
+ *  Errors: SPHX:Probe:config (NULL config or points, n_points out of range, a non-finite coordinate, y outside [0, DH],
+ *    every < 1, capacity < 1 or capacity * n_points * 4 > 1 << 27, non-finite t_from, with_walls not 0 or 1, or the
+ *    allocation fails: the context then goes on without probes), SPHX:Probe:disabled (SPHX_ERR_STATE: a call that needs
+ *    the probes while they are off), SPHX:Probe:capacity (the caller's arrays are smaller than n_records); every call on
+ *    a slab context fails with SPHX_ERR_ARG, SPHX:Probe:slab.  A refused enable leaves running probes, and their
+ *    records, untouched.
+ * ---------------------------------------------------------------------------------------------- */
+
+#define SPHX_PROBE_FIELDS 4
+#define SPHX_PROBE_MAX_POINTS 4096
+
+typedef struct sphx_probes_config {
+    int32_t n_points;      /* P, 1 .. SPHX_PROBE_MAX_POINTS                                          */
+    int32_t every;         /* record every `every`-th completed step (step count % every == 0), >= 1 */
+    int32_t capacity;      /* records the device buffer holds, >= 1                                  */
+    int32_t with_walls;    /* 1: wall particles contribute to S0, S1, S2 with their wall velocity    */
+    double t_from;         /* only steps ending at t >= t_from                                       */
+    const double *points;  /* [n_points][2]: x, y; copied at enable                                  */
+} sphx_probes_config;
+
+/* (Re)configure and empty the buffer; waits for the stream.  Off by default. */
+int sphx_ctx_probes_enable(sphx_ctx *ctx, const sphx_probes_config *cfg);
+/* Stop recording (no-op when off); the records are dropped. */
+int sphx_ctx_probes_disable(sphx_ctx *ctx);
+/* Append one record of the current state (what sphx_ctx_download would return) now, without gating. */
+int sphx_ctx_probes_sample(sphx_ctx *ctx);
+/* The records so far, in step order: times [capacity][2] and values [capacity][n_points][SPHX_PROBE_FIELDS], row-major
+ * (times / values NULL: that array is not copied; both NULL: only the counts are reported and capacity is not checked).
+ * Waits for and settles everything enqueued, like sphx_ctx_download.  drain != 0: the buffer is emptied and n_dropped
+ * zeroed after copying. */
+int sphx_ctx_probes_read(sphx_ctx *ctx, int capacity, double *times, double *values, int *n_points, int *n_records,
+                         int64_t *n_dropped, int drain);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2i. Point probes of a batch (section 2b): the probes of section 2h for every member at once.
+ *
+ *  One config and one set of points for all members; `capacity` is per member.  Every member has its own record buffer,
+ *  n_records and n_dropped, and is recorded on its own clock with the gating of section 2h, so a member that sits out slots
+ *  records nothing in them and its counters are not touched.  A member's records are bit for bit those of a standalone
+ *  context with the same parameters and config that took the same steps: the same wave owns a probe and its lanes add the
+ *  same candidates in the same order.  After a realignment (section 2b) a member's particles are laid out differently,
+ *  which changes the summation order only.  With probes on, every step slot of the batch ends with one recording launch
+ *  for all members (k_point_probes_b, behind the batch's other samplers); off, a slot enqueues exactly the launches it
+ *  does without this feature.  Enable / disable wait for the stream and re-capture the batch's graphs.
+ *  Memory: n_members * capacity * (2 + n_points * 4) doubles; n_members * capacity * n_points * 4 must not exceed
+ *  1 << 27 doubles.  A refused enable leaves running probes, and their records, untouched.
+ *  Errors: SPHX:Batch:null (NULL batch), SPHX:Probe:config (as in section 2h, with the total over the members),
+ *  SPHX:Probe:disabled, SPHX:Probe:capacity (the caller's capacity is below the largest n_records of any member).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* (Re)configure and empty every member's buffer; waits for the stream. */
+int sphx_batch_probes_enable(sphx_batch *batch, const sphx_probes_config *cfg);
+/* Stop recording (no-op when off); the records are dropped. */
+int sphx_batch_probes_disable(sphx_batch *batch);
+/* settles; appends a record of what sphx_batch_download returns, every member, without gating */
+int sphx_batch_probes_sample(sphx_batch *batch);
+/* One call for all members.  times is [n_members][capacity][2] and values [n_members][capacity][n_points][SPHX_PROBE_FIELDS],
+ * row-major: member m's block lies behind member m - 1's, its records fill rows 0 .. n_records[m] - 1 and the other rows are
+ * left as they are.  n_records and n_dropped are [n_members]; any pointer may be NULL.  Settles first, as
+ * sphx_batch_download does.  drain != 0: every member's buffer is emptied and its n_dropped zeroed after copying. */
+int sphx_batch_probes_read(sphx_batch *batch, int capacity, double *times, double *values, int *n_points, int *n_records,
+                           int64_t *n_dropped, int drain);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU).  The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

@@ -53,6 +53,16 @@ class SphxFieldMapConfig(C.Structure):
 HISTORY_FIELDS = ("step", "t", "dt", "vmax", "tau_bottom", "tau_top", "kinetic_energy", "u_bulk")
 
 
+class SphxProbesConfig(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("every", C.c_int32), ("capacity", C.c_int32), ("with_walls", C.c_int32),
+                ("t_from", C.c_double), ("points", _dp)]
+
+
+# the values of a probe (include/sphx.h section 2h), in the order the library writes them
+PROBE_FIELDS = ("weight", "u_x", "u_y", "rho")
+PROBE_MAX_POINTS = 4096
+
+
 class SphxStatus(C.Structure):
     _fields_ = [("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("vmax", C.c_double),
                 ("step", C.c_int64), ("done", C.c_int32), ("device_status", C.c_int32)]
@@ -75,6 +85,7 @@ EXPORTS = [
     "sphx_ctx_history_enable", "sphx_ctx_history_disable", "sphx_ctx_history_read",
     "sphx_ctx_field_map_enable", "sphx_ctx_field_map_disable", "sphx_ctx_field_map_reset", "sphx_ctx_field_map_sample",
     "sphx_ctx_field_map_read",
+    "sphx_ctx_probes_enable", "sphx_ctx_probes_disable", "sphx_ctx_probes_sample", "sphx_ctx_probes_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -88,6 +99,7 @@ EXPORTS = [
     "sphx_batch_history_enable", "sphx_batch_history_disable", "sphx_batch_history_read",
     "sphx_batch_field_map_enable", "sphx_batch_field_map_disable", "sphx_batch_field_map_reset", "sphx_batch_field_map_sample",
     "sphx_batch_field_map_read",
+    "sphx_batch_probes_enable", "sphx_batch_probes_disable", "sphx_batch_probes_sample", "sphx_batch_probes_read",
 ]
 
 _LIB = None
@@ -381,6 +393,49 @@ class _Stepped(_Sampled):
         sums = self.field_map_sums()
         return [field_map_means(p0.DL, p0.DH, **s) for s in sums] if self._many else field_map_means(p0.DL, p0.DH, **sums)
 
+    # ---- point probes (include/sphx.h sections 2h, 2i): the flow at fixed points, one record per sampled step ----
+    def probes_enable(self, points, every=1, capacity=65536, t_from=0.0, with_walls=False):
+        """Record the Shepard sample of the state at the points [P, 2] (x any finite value, folded into [0, DL); 0 <= y <= DH)
+        every `every`-th completed step ending at t >= t_from into a device buffer of `capacity` records ((re)configures and
+        empties it).  Records that find the buffer full are dropped and counted.  A batch: one config and one set of points
+        for all members, `capacity` records per member, each recorded on its own clock."""
+        cfg, pts = probes_config(self._params0(), points, every, capacity, t_from, with_walls, n_members=self._channels())
+        self._call("probes_enable", C.byref(cfg))
+        self._probes = pts  # the folded points [P, 2] while the probes are on
+
+    def probes_disable(self):
+        self._call("probes_disable")
+        self._probes = None
+
+    def _probes_on(self):
+        return _enabled(self._probes, "Probe", f"point probes are not enabled on this {self._where}")
+
+    def probes_sample(self):
+        """Append one record of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
+        self._probes_on()
+        self._call("probes_sample")
+
+    def probes(self, drain=False):
+        """The series so far: points [P, 2] as folded, step (int64) and t [n], weight, u_x, u_y and rho [n, P] (velocities NaN
+        and weight = rho = 0 where a point has no particle within 2h), n_dropped; drain empties the buffer after the copy.
+        p0 * (rho / rho0 - 1) is the pressure of the summation density.  A batch: one such dict per member, from one read of
+        all members."""
+        pts = self._probes_on()
+        m, P = self._channels(), len(pts)
+        n, dropped, np_ = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64), C.c_int(0)
+
+        def read(cap, times, values, drain):
+            self._call("probes_read", C.c_int(cap), ptr(times), ptr(values), C.byref(np_), n.ctypes.data_as(C.POINTER(C.c_int)),
+                       dropped.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(1 if drain else 0))
+
+        read(0, None, None, False)
+        assert np_.value == P, (np_.value, P)
+        cap, want = max(int(n.max()), 1), n.copy()
+        times, values = np.zeros((m, cap, 2)), np.zeros((m, cap, P, len(PROBE_FIELDS)))
+        read(cap, times, values, drain)
+        assert np.array_equal(n, want), (n, want)
+        return self._each([probes_dict(pts, times[k, :n[k]], values[k, :n[k]], int(dropped[k])) for k in range(m)])
+
 
 class Batch(_Stepped):
     """M channels of one geometry stepped by the same launches (sphx_batch, include/sphx.h section 2b).
@@ -420,6 +475,7 @@ class Batch(_Stepped):
             raise SphxError(SPHX_ERR_ARG, "SPHX:Batch:geometry", "mass / wall_vel: shared arrays of n_total rows expected")
         self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
         self._field_map = None   # (nx, ny) while the field map is on
+        self._probes = None      # the folded points [P, 2] while the probes are on
         arr = (SphxParams * m)(*self.params)
         check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
@@ -467,6 +523,7 @@ class Context(_Stepped):
         assert drho_dt.shape == (n_total,) and mass.shape == (n_total,)
         self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
         self._field_map = None   # (nx, ny) while the field map is on
+        self._probes = None      # the folded points [P, 2] while the probes are on
         check(lib().sphx_ctx_create(C.byref(self._h), C.byref(self.params), C.c_int(n_fluid), C.c_int(n_total),
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
@@ -634,6 +691,57 @@ def field_map_config(nx=0, ny=0, every=1, t_from=0.0, with_walls=False, n_member
     if not (isinstance(with_walls, (bool, np.bool_)) or (_is_int(with_walls) and with_walls in (0, 1))):
         raise bad("with_walls must be a bool (or 0 / 1)")
     return SphxFieldMapConfig(nx=int(nx), ny=int(ny), every=every, with_walls=int(with_walls), t_from=t_from)
+
+
+def probes_fold(x, DL):
+    """x folded into [0, DL) as the library folds it: x - floor(x / DL) * DL, and 0 where rounding lands on DL."""
+    x = np.asarray(x, dtype=np.float64)
+    f = x - np.floor(x / DL) * DL
+    return np.where((f >= 0.0) & (f < DL), f, 0.0)
+
+
+def probes_config(prm, points, every=1, capacity=65536, t_from=0.0, with_walls=False, n_members=1):
+    """Checked sphx_probes_config for channels with parameters prm, and the folded points [P, 2] it points to (keep them
+    alive through the call); raises SphxError(SPHX:Probe:config) before anything reaches the device.  n_members: the
+    channels that get `capacity` records each (a batch's members)."""
+    bad = _config_error("Probe")
+    if points is None:
+        raise bad("points must not be None")
+    try:
+        pts = np.array(points, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise bad("points must be an array of (x, y) pairs") from None
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise bad("points must be an array of (x, y) pairs, shape [P, 2]")
+    if not 1 <= len(pts) <= PROBE_MAX_POINTS:
+        raise bad(f"the number of points must be 1 .. {PROBE_MAX_POINTS}")
+    if not np.all(np.isfinite(pts)):
+        raise bad("the coordinates of a point must be finite")
+    if np.any(pts[:, 1] < 0.0) or np.any(pts[:, 1] > prm.DH):
+        raise bad("the y of a point must lie in [0, DH]")
+    every = _check_every(every, bad)
+    if not _is_int(capacity) or capacity < 1 or capacity >= 1 << 31:
+        raise bad("capacity must be an integer >= 1")
+    if n_members * capacity * len(pts) * len(PROBE_FIELDS) > 1 << 27:
+        raise bad(("n_members * " if n_members > 1 else "") + "capacity * n_points * 4 must not exceed 1 << 27 doubles")
+    t_from = _check_t_from(t_from, bad, finite=True)
+    if not (isinstance(with_walls, (bool, np.bool_)) or (_is_int(with_walls) and with_walls in (0, 1))):
+        raise bad("with_walls must be a bool (or 0 / 1)")
+    pts = np.ascontiguousarray(np.column_stack([probes_fold(pts[:, 0], prm.DL), pts[:, 1]]))
+    cfg = SphxProbesConfig(n_points=len(pts), every=every, capacity=int(capacity), with_walls=int(with_walls), t_from=t_from,
+                           points=ptr(pts))
+    return cfg, pts
+
+
+def probes_dict(points, times, values, n_dropped=0) -> dict:
+    """times [n, 2] and values [n, P, 4] -> points, step (int64), t [n] and one [n, P] array per PROBE_FIELDS, plus n_dropped."""
+    times = np.asarray(times, dtype=np.float64).reshape(-1, 2)
+    points = np.array(points, dtype=np.float64).reshape(-1, 2)
+    values = np.asarray(values, dtype=np.float64).reshape(len(times), len(points), len(PROBE_FIELDS))
+    out = dict(points=points, step=times[:, 0].astype(np.int64), t=np.ascontiguousarray(times[:, 1]))
+    out.update({k: np.ascontiguousarray(values[:, :, j]) for j, k in enumerate(PROBE_FIELDS)})
+    out["n_dropped"] = int(n_dropped)
+    return out
 
 
 def history_dict(records, n_dropped=0) -> dict:

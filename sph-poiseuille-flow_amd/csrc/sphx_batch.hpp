@@ -608,3 +608,59 @@ SPHX_EXPORT int sphx_batch_field_map_read(sphx_batch *b, int capacity, int *nx, 
     return SPHX_OK;
     SPHX_CATCH
 }
+
+// ---- point probes of every member (include/sphx.h section 2i) ----
+
+namespace {
+
+// the batch's probes (member 0's, see sphx_ctx::probes)
+Probes &batch_probes(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    Probes &p = b->mem[0]->probes;
+    sampler_check(kProbeNames, false, p.on, need_on, "batch");
+    return p;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_batch_probes_enable(sphx_batch *b, const sphx_probes_config *cfg)
+{
+    SPHX_TRY
+    // (one set of points for the shared geometry; out of device memory: the batch goes on without probes)
+    Probes &p = batch_probes(b, false);
+    probes_enable(p, b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_probes_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    Probes &p = batch_probes(b, false);
+    if (p.on) sampler_off(p, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_probes_sample(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_probes(b, true);
+    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
+    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_probes);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_probes_read(sphx_batch *b, int capacity, double *times, double *values, int *n_points, int *n_records,
+                                       int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    Probes &p = batch_probes(b, true);
+    batch_settle(b);  // (the records of everything enqueued)
+    p.read(b->stream, capacity, times, values, n_records, n_dropped, drain != 0);
+    if (n_points) *n_points = p.cfg.n_points;
+    return SPHX_OK;
+    SPHX_CATCH
+}

@@ -254,6 +254,7 @@ struct sphx_ctx {
     FlowStats fstats;  // (of a batch: member 0's serves every member, the other members' stay off)
     History hist;
     FieldMap fmap;
+    Probes probes;
 
     // Member of a batch (sphx_batch_*): the device arrays are this member's blocks of batch-wide allocations (BatchArena)
     sphx::BatchArena *arena = nullptr;
@@ -2000,7 +2001,7 @@ SPHX_EXPORT int sphx_ctx_profile_read(sphx_ctx *c, int capacity, const char **na
     SPHX_CATCH
 }
 
-#include "sphx_samplers.hpp"  // the slot samplers: launches, lifecycle, sphx_ctx_flow_stats_* / history_* / field_map_*
+#include "sphx_samplers.hpp"  // the slot samplers: launches, lifecycle, sphx_ctx_flow_stats_* / history_* / field_map_* / probes_*
 
 SPHX_EXPORT int sphx_ctx_info(sphx_ctx *c, int *n_fluid, int *n_wall, int *n_cell_x, int *n_cell_y)
 {

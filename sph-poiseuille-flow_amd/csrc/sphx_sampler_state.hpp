@@ -5,6 +5,7 @@
 #include "sphx_flow_stats.hpp"
 #include "sphx_history.hpp"
 #include "sphx_field_map.hpp"
+#include "sphx_probes.hpp"
 
 struct sphx_ctx;
 
@@ -73,7 +74,27 @@ struct FieldMap {
     void read(hipStream_t st, int stride, double *const out[kFieldPlanes], int64_t *n_samples, double *t_first, double *t_last) const;
 };
 
-// the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map (sphx_samplers.hpp)
+// Point probes (sphx_ctx_probes_*, sphx_batch_probes_*; sphx_probes.hpp) of a context or of the M members of a batch: one
+// configuration and one set of points, member m's times at m * cfg.capacity * 2, its values at m * cfg.capacity * row(), its
+// head at m.
+struct Probes {
+    bool on = false;
+    int members = 1;
+    sphx_probes_config cfg{};     // (cfg.points: nullptr -- the points are copied)
+    std::vector<double> folded;   // [n_points][2]: x folded into [0, DL), y
+    DevBuf<double2> points;
+    DevBuf<double> times, values;
+    DevBuf<ProbeHead> head;
+
+    size_t row() const { return (size_t)cfg.n_points * kProbeFields; }  // the values of one record
+    void check(const sphx_params &prm, const sphx_probes_config *cfg, int M);
+    void alloc(const Probes &checked, int M, hipStream_t st);
+    void zero(hipStream_t st) { head.zero(st); }  // (the counters: records beyond n_records are never read)
+    void release() { points.release(); times.release(); values.release(); head.release(); }
+    void read(hipStream_t st, int capacity, double *times, double *values, int *n_records, int64_t *n_dropped, bool drain);
+};
+
+// the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes (sphx_samplers.hpp)
 void launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild);
 
 }  // namespace sphx

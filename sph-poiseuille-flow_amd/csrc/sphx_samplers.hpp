@@ -1,7 +1,7 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
-// and the velocity-field map (2e; 2g); all three also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
-// sphx_history.hpp and sphx_field_map.hpp.  What the three share -- the context check, on / off, the view a slot leaves,
+// the velocity-field map (2e; 2g) -- those three also of a slab of a ring (3a, at the end of this file) -- and the point probes (2h; 2i).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// sphx_history.hpp, sphx_field_map.hpp and sphx_probes.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
 
@@ -23,6 +23,8 @@ constexpr SamplerNames kHistoryNames{"History", "the step history is not availab
                                      "the step history is not enabled on this ", "the record buffer could not be set up: "};
 constexpr SamplerNames kFieldNames{"Field", "field maps are not available on slab contexts", "the field map is not enabled on this ",
                                    "the map could not be set up: "};
+constexpr SamplerNames kProbeNames{"Probe", "point probes are not available on slab contexts", "point probes are not enabled on this ",
+                                   "the record buffer could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
 
@@ -197,6 +199,35 @@ void launch_field_map(sphx_ctx *c, int q, const FluidSet &s, int every)
                  per_member(c->phys), s, c->walls, a);
 }
 
+// the arguments of a probes launch into c->probes
+ProbeArgs probe_args(sphx_ctx *c, int every)
+{
+    const Probes &p = c->probes;
+    ProbeArgs a{};
+    a.points = p.points.get(); a.times = p.times.get(); a.values = p.values.get(); a.head = p.head.get();
+    a.dp2 = c->prm.dp * c->prm.dp;
+    a.t_from = p.cfg.t_from;
+    a.n_points = p.cfg.n_points; a.capacity = p.cfg.capacity;
+    a.every = every;
+    a.with_walls = p.cfg.with_walls && c->nw > 0 ? 1 : 0;
+    return a;
+}
+
+// workgroups of one channel's record: a wave per probe
+unsigned probe_blocks(const ProbeArgs &a)
+{
+    return (unsigned)div_up((size_t)a.n_points, (size_t)kProbeWaves);
+}
+
+// k_point_probes on state s (pos, vel, mass and the cell ranges of the layout it is stored in) -- of a batch: member 0's -- into
+// c->probes
+void launch_probes(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    const ProbeArgs a = probe_args(c, every);
+    launch_forms(c, "k_point_probes", Forms{k_point_probes, k_point_probes_b}, probe_blocks(a), kProbeBlock, 0, q, c->grid,
+                 per_member(c->phys), s, c->walls, a);
+}
+
 }  // namespace
 
 void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
@@ -205,6 +236,7 @@ void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
     if (c->fstats.on) launch_flow_stats(c, q, s, c->fstats.cfg.every);
     if (c->hist.on) launch_history(c, q, s, rebuild);
     if (c->fmap.on) launch_field_map(c, q, s, c->fmap.cfg.every);
+    if (c->probes.on) launch_probes(c, q, s, c->probes.cfg.every);
 }
 
 // ---- flow statistics ----
@@ -563,6 +595,153 @@ SPHX_EXPORT int sphx_ctx_field_map_read(sphx_ctx *c, int capacity, int *nx, int 
     const FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, true);
     field_read(f, c->stream, [c] { settle_owed(c); }, capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples,
                t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- point probes ----
+
+namespace {
+
+// x folded into [0, DL): x - floor(x / DL) * DL, each operation rounded by itself (numpy's value), and 0 where the rounding
+// of a tiny negative x lands on DL
+double probe_fold(double x, double DL)
+{
+#pragma clang fp contract(off)
+    const double k = std::floor(x / DL);
+    const double f = x - k * DL;
+    return f >= 0.0 && f < DL ? f : 0.0;
+}
+
+}  // namespace
+
+// every check of a configuration for M channels with parameters prm (cfg without the pointer, and the folded points);
+// SPHX:Probe:config errors
+void Probes::check(const sphx_params &prm, const sphx_probes_config *cfg, int M)
+{
+    require(cfg != nullptr, "SPHX:Probe:config", "config must not be NULL");
+    require(cfg->points != nullptr, "SPHX:Probe:config", "points must not be NULL");
+    require(cfg->n_points >= 1 && cfg->n_points <= kProbeMaxPoints, "SPHX:Probe:config", "n_points must be 1 .. 4096");
+    require(cfg->every >= 1, "SPHX:Probe:config", "every must be >= 1");
+    require(cfg->capacity >= 1, "SPHX:Probe:config", "capacity must be >= 1");
+    if (!((double)M * (double)cfg->capacity * (double)cfg->n_points * kProbeFields <= (double)kProbeMaxTotal))
+        throw Error(SPHX_ERR_ARG, "SPHX:Probe:config",
+                    std::string(M > 1 ? "n_members * " : "") + "capacity * n_points * 4 must not exceed 1 << 27 doubles");
+    require(std::isfinite(cfg->t_from), "SPHX:Probe:config", "t_from must be finite");
+    require(cfg->with_walls == 0 || cfg->with_walls == 1, "SPHX:Probe:config", "with_walls must be 0 or 1");
+    folded.resize((size_t)cfg->n_points * 2);
+    for (int p = 0; p < cfg->n_points; ++p) {
+        const double x = cfg->points[2 * p], y = cfg->points[2 * p + 1];
+        require(std::isfinite(x) && std::isfinite(y), "SPHX:Probe:config", "the coordinates of a point must be finite");
+        require(y >= 0.0 && y <= prm.DH, "SPHX:Probe:config", "the y of a point must lie in [0, DH]");
+        folded[2 * p] = probe_fold(x, prm.DL);
+        folded[2 * p + 1] = y;
+    }
+    this->cfg = *cfg;
+    this->cfg.points = nullptr;
+}
+
+// the checked configuration and points, and records and heads for M members
+void Probes::alloc(const Probes &checked, int M, hipStream_t st)
+{
+    cfg = checked.cfg;
+    folded = checked.folded;
+    members = M;
+    points.alloc((size_t)cfg.n_points);
+    times.alloc((size_t)M * cfg.capacity * 2);
+    values.alloc((size_t)M * cfg.capacity * row());
+    head.alloc(M);
+    points.upload(reinterpret_cast<const double2 *>(folded.data()), (size_t)cfg.n_points, st);  // (sampler_on waits for st)
+}
+
+// Every member's counts (n_records[m], n_dropped[m], where given) and its filled rows, into times[m][0 .. n_records[m])[2] of a
+// [members][capacity][2] array and values[m][0 .. n_records[m])[row()] of a [members][capacity][row()] array, each where given;
+// drain empties every buffer.  SPHX:Probe:capacity when an array is given and capacity is below the largest count: nothing is
+// copied or drained then.
+void Probes::read(hipStream_t st, int capacity, double *t_out, double *v_out, int *n_records, int64_t *n_dropped, bool drain)
+{
+    const int M = members;
+    std::vector<ProbeHead> h(M);
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(ProbeHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    long long most = 0;
+    for (int m = 0; m < M; ++m) {
+        const long long n = h[m].n_records;
+        if (n < 0 || n > (long long)cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:Probe:state", "internal: record count out of range");
+        most = std::max(most, n);
+    }
+    require((t_out == nullptr && v_out == nullptr) || (long long)capacity >= most, "SPHX:Probe:capacity",
+            "capacity is smaller than the number of records");
+    if ((t_out || v_out) && most > 0) {
+        for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
+            const size_t n = (size_t)h[m].n_records;
+            if (n == 0) continue;
+            if (t_out)
+                SPHX_HIP(hipMemcpyAsync(t_out + (size_t)m * capacity * 2, times.get() + (size_t)m * cfg.capacity * 2, n * 2 * sizeof(double),
+                                        hipMemcpyDeviceToHost, st));
+            if (v_out)
+                SPHX_HIP(hipMemcpyAsync(v_out + (size_t)m * capacity * row(), values.get() + (size_t)m * cfg.capacity * row(),
+                                        n * row() * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+    for (int m = 0; m < M; ++m) {
+        if (n_records) n_records[m] = (int)h[m].n_records;
+        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
+    }
+    if (drain) {
+        zero(st);
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+}
+
+namespace {
+
+// enable for M members of channels with parameters prm on schedule s: every check of cfg first
+void probes_enable(Probes &p, const sphx_params &prm, const sphx_probes_config *cfg, int M, Schedule &s, hipStream_t st)
+{
+    Probes checked;
+    checked.check(prm, cfg, M);
+    sampler_on(p, kProbeNames, s, st, [&] { p.alloc(checked, M, st); });
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_probes_enable(sphx_ctx *c, const sphx_probes_config *cfg)
+{
+    SPHX_TRY
+    Probes &p = sampler_of(c, &sphx_ctx::probes, kProbeNames, false);
+    probes_enable(p, c->prm, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_probes_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    Probes &p = sampler_of(c, &sphx_ctx::probes, kProbeNames, false);
+    if (p.on) sampler_off(p, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_probes_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampler_of(c, &sphx_ctx::probes, kProbeNames, true);
+    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_probes);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_probes_read(sphx_ctx *c, int capacity, double *times, double *values, int *n_points, int *n_records,
+                                     int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    Probes &p = sampler_of(c, &sphx_ctx::probes, kProbeNames, true);
+    settle_owed(c);  // (the records of everything enqueued)
+    p.read(c->stream, capacity, times, values, n_records, n_dropped, drain != 0);
+    if (n_points) *n_points = p.cfg.n_points;
     return SPHX_OK;
     SPHX_CATCH
 }

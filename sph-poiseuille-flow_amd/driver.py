@@ -49,6 +49,8 @@ class RunResult:
     history: dict = None  # run(..., history_every=...): the device-side step history of the whole run (capi.Context.history)
     field_avg: dict = None  # run(..., field_from=...): the device-side time-averaged velocity map (capi.Context.field_map); a
                             # member of run_ensemble / run_sweep(..., field_from=...): its own (capi.Batch.field_map)
+    probes: dict = None  # run / run_sweep(..., probe_points=...): the device-side point-probe series of the whole run
+                         # (capi.Context.probes; probe_figures() turns it into means, RMS and spectral peaks)
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -164,6 +166,80 @@ def field_figures(prm, field):
                 uy_rms=float(np.sqrt(np.mean(uy_ok * uy_ok))) if uy_ok.size else float("nan"), U_max=u_max)
 
 
+def probe_figures(prm, probes, t_from=None):
+    """Figures of a point-probe series (capi.Context.probes / RunResult.probes) per probe, on the host, over the records with
+    t >= t_from (None: all).  A record stands for the interval that ended at its t, so its weight is the time since the record
+    before it (the first record's: the second's).
+      u_x_mean, u_y_mean, p_mean   dt-weighted time means of u_x, u_y and p = p0 (rho / rho0 - 1), [P]
+      u_x_rms, u_y_rms, p_rms      dt-weighted RMS about those means, [P]
+      u_exact                      the analytic profile g / (2 nu) y_p (DH - y_p) at the probes' y, [P]
+      f_peak_uy, f_peak_p          the frequency of the largest line of the spectrum of the fluctuation of u_y and of p, [P]:
+                                   the series resampled (linearly) onto a uniform time grid of its median dt, mean removed,
+                                   numpy.fft.rfft; NaN with fewer than 4 records or a series with a NaN
+      f_bin, n_records             the spectral resolution 1 / (n * median dt) and the records that entered
+    The line to look for is the cross-channel acoustic mode: a pressure wave sloshing between the walls at
+    f = c / (2 DH) with the artificial speed of sound c = c_f |U_bulk| (U_bulk = g DH^2 / (12 nu))."""
+    t = np.asarray(probes["t"], dtype=np.float64)
+    sel = np.ones(len(t), dtype=bool) if t_from is None else t >= t_from
+    t = t[sel]
+    n = len(t)
+    y = np.asarray(probes["points"], dtype=np.float64)[:, 1]
+    P = len(y)
+    series = dict(u_x=np.asarray(probes["u_x"], dtype=np.float64)[sel], u_y=np.asarray(probes["u_y"], dtype=np.float64)[sel],
+                  p=prm.p0 * (np.asarray(probes["rho"], dtype=np.float64)[sel] / prm.rho0 - 1.0))
+    out = dict(u_exact=prm.gravity_g / (2.0 * prm.nu) * y * (prm.DH - y), n_records=n,
+               f_acoustic=prm.c_f * abs(prm.gravity_g * prm.DH ** 2 / (12.0 * prm.nu)) / (2.0 * prm.DH))
+    nan = np.full(P, np.nan)
+    if n >= 2:
+        w = np.diff(t, prepend=t[0] - (t[1] - t[0]))
+    else:
+        w = np.ones(n)
+    wsum = float(np.sum(w))
+    for key, v in series.items():
+        if n == 0 or not wsum > 0.0:
+            out[key + "_mean"], out[key + "_rms"] = nan.copy(), nan.copy()
+            continue
+        # (about the first value: a constant series gives that value exactly)
+        mean = v[0] + (w[:, None] * (v - v[0])).sum(axis=0) / wsum
+        out[key + "_mean"] = mean
+        out[key + "_rms"] = np.sqrt((w[:, None] * (v - mean) ** 2).sum(axis=0) / wsum)
+    dt = float(np.median(np.diff(t))) if n >= 2 else float("nan")
+    out["f_bin"] = float("nan")
+    for key, name in (("u_y", "f_peak_uy"), ("p", "f_peak_p")):
+        out[name] = nan.copy()
+        if n < 4 or not dt > 0.0:
+            continue
+        tu = t[0] + dt * np.arange(int(np.floor((t[-1] - t[0]) / dt)) + 1)
+        freq = np.fft.rfftfreq(len(tu), dt)
+        out["f_bin"] = float(freq[1]) if len(freq) > 1 else float("nan")
+        for k in range(P):
+            v = series[key][:, k]
+            if np.any(np.isnan(v)) or len(freq) < 2:
+                continue
+            u = np.interp(tu, t, v)
+            amp = np.abs(np.fft.rfft(u - u.mean()))
+            out[name][k] = freq[1 + int(np.argmax(amp[1:]))]
+    return out
+
+
+def _concat_probes(points, DL, chunks):
+    """the series of a whole run from the drained chunks (none: an empty series at the points as folded)"""
+    if not chunks:
+        pts = np.array(points, dtype=np.float64).reshape(-1, 2)
+        pts[:, 0] = capi.probes_fold(pts[:, 0], DL)
+        return capi.probes_dict(pts, np.zeros((0, 2)), np.zeros((0, len(pts), len(capi.PROBE_FIELDS))))
+    out = dict(points=chunks[0]["points"])
+    out.update({k: np.concatenate([c[k] for c in chunks]) for k in ("step", "t") + capi.PROBE_FIELDS})
+    out["n_dropped"] = int(sum(c["n_dropped"] for c in chunks))
+    return out
+
+
+def _probes_lost(who, p, t, capacity):
+    """the error of a run whose probe buffer overflowed between two output points"""
+    return RuntimeError(f"{who}the point probes lost {p['n_dropped']} records before t={t:.6f}; the output interval needs "
+                        f"probe_capacity >= {len(p['step']) + p['n_dropped']} (it is {capacity})")
+
+
 def _concat_history(chunks):
     if not chunks:
         return capi.history_dict(np.zeros((0, len(capi.HISTORY_FIELDS))))
@@ -175,7 +251,7 @@ def _concat_history(chunks):
 def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_particle=0, steps_per_graph=0,
         rebuild_every=0, restart_path=None, postprocess_path=None, dual_rate=0, mat_format="auto", average_from=None,
         average_every=1, history_every=None, history_capacity=65536, field_from=None, field_every=1, field_shape=None,
-        field_walls=False):
+        field_walls=False, probe_points=None, probe_every=1, probe_capacity=65536, probe_from=None, probe_walls=False):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -196,7 +272,15 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     t >= field_from into a velocity map on a regular grid (include/sphx.h section 2e; field_shape = (nx, ny), None = the
     reference's 2 round(DL/dp) x 2 round(DH/dp); field_walls: the wall particles contribute with their wall velocity);
     RunResult.field_avg is capi.Context.field_map() at the end (field_figures() turns it into an x-mean profile, its L2
-    and the spread along x).  A map of the final state of any engine: profile.shepard_field(res.pos[:nf], res.vel[:nf], ...)."""
+    and the spread along x).  A map of the final state of any engine: profile.shepard_field(res.pos[:nf], res.vel[:nf], ...).
+    probe_points (resident engine): record, on the device and inside the step loop, the Shepard sample of the flow at these
+    points [P, 2] (include/sphx.h section 2h: weight, u_x, u_y, rho per point) every probe_every-th step ending at
+    t >= probe_from (None: from the start; probe_walls: the wall particles contribute with their wall velocity); the buffer
+    (probe_capacity records) is drained at every output point, so a capacity that holds one output interval suffices --
+    a run that lost records raises RuntimeError and names the capacity needed -- and RunResult.probes is the series of the
+    whole run (probe_figures() turns it into means, RMS and spectral peaks per probe)."""
+    if probe_points is not None and engine != "resident":
+        raise ValueError("probe_points needs the resident engine (the probes are recorded on the device)")
     if field_from is not None and engine != "resident":
         raise ValueError("field_from needs the resident engine (the map is accumulated on the device)")
     if average_from is not None and engine != "resident":
@@ -227,6 +311,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     time_avg = None
     history, history_chunks = None, []
     field_avg = None
+    probes, probe_chunks = None, []
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context.from_parts(prm, parts, t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
@@ -241,6 +326,9 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
             if field_from is not None:
                 fnx, fny = field_shape if field_shape is not None else (0, 0)
                 ctx.field_map_enable(nx=fnx, ny=fny, every=field_every, t_from=field_from, with_walls=field_walls)
+            if probe_points is not None:
+                ctx.probes_enable(probe_points, every=probe_every, capacity=probe_capacity,
+                                  t_from=t_start if probe_from is None else probe_from, with_walls=probe_walls)
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -259,6 +347,10 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                                                    d["vel"][:nf, 0], prm)[1])
                 if history_every is not None:
                     history_chunks.append(ctx.history(drain=True))
+                if probe_points is not None:
+                    probe_chunks.append(ctx.probes(drain=True))
+                    if probe_chunks[-1]["n_dropped"]:
+                        raise _probes_lost("", probe_chunks[-1], t, probe_capacity)
                 if restart_path:
                     restart.save_restart(restart_path, prm.config_signature, dict(d, t=t, step=step), fmt=mat_format)
                 if log:
@@ -274,6 +366,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 history = _concat_history(history_chunks)
             if field_from is not None:
                 field_avg = ctx.field_map()
+            if probe_points is not None:
+                probes = _concat_probes(probe_points, prm.DL, probe_chunks)
         finally:
             ctx.close()
     elif engine == "mex":
@@ -323,7 +417,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                                       fmt=mat_format)
     return _run_result(prm, nf, nt, pos, vel, t=t, steps=int(step), wall_seconds=wall, profile_times=profile_times,
                        mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t, grid_policy=policy,
-                       full_profile_u=full_profiles, n_inner=n_inner, time_avg=time_avg, history=history, field_avg=field_avg)
+                       full_profile_u=full_profiles, n_inner=n_inner, time_avg=time_avg, history=history, field_avg=field_avg,
+                       probes=probes)
 
 
 def _run_result(prm, nf, nt, pos, vel, **fields):
@@ -363,7 +458,7 @@ def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
                        profile_times=list(times), tau_bottom=tau_b, tau_top=tau_t, grid_policy=dict(policy), **extra)
 
 
-def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None):
+def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None, probe=None):
     """The batch run behind run_batch, run_ensemble and run_sweep (`name`, for the refusals): check and default the inputs,
     open the batch with the launch keywords `launch`, enable what was asked for, advance output point by output point, build
     every member's RunResult.
@@ -374,6 +469,9 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                  history, and one that lost records raises RuntimeError
       field      (field_from, field_every, field_shape, field_walls): the velocity map of include/sphx.h section 2g, enabled
                  before the first advance and read once at the end; every member gets a field_avg
+      probe      (probe_points, probe_every, probe_capacity, probe_from, probe_walls): the point probes of include/sphx.h
+                 section 2i, drained at every output point; every member gets its probes, and one that lost records raises
+                 RuntimeError
     -> the members, the wall seconds, the grid policy, with average the raw sums (whole, mid) of all members, and with field the
     raw planes of all members."""
     prms = list(prms)
@@ -393,6 +491,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
     mids = [[mid_profile(pa)] for pa in parts_list] if snapshots else None
     fulls = [[] for _ in range(M)]
     chunks = [[] for _ in range(M)]
+    pchunks = [[] for _ in range(M)]
     t0 = time.perf_counter()
     with capi.Batch.from_parts(prms, parts_list, **launch) as b:
         if history:
@@ -402,6 +501,9 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         if field:
             fnx, fny = field[2] if field[2] is not None else (0, 0)
             b.field_map_enable(nx=fnx, ny=fny, every=field[1], t_from=field[0], with_walls=field[3])
+        if probe:
+            b.probes_enable(probe[0], every=probe[1], capacity=probe[2], t_from=0.0 if probe[3] is None else probe[3],
+                            with_walls=probe[4])
         t = 0.0
         st = None
         while t < p0.t_end - 1e-12:
@@ -422,6 +524,11 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                                            f"the output interval needs history_capacity >= "
                                            f"{len(h['step']) + h['n_dropped']} (it is {history[1]})")
                     chunks[m].append(h)
+            if probe:
+                for m, p in enumerate(b.probes(drain=True)):
+                    if p["n_dropped"]:
+                        raise _probes_lost(f"member {m}: ", p, t, probe[2])
+                    pchunks[m].append(p)
             if log:
                 log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
         wall = time.perf_counter() - t0
@@ -439,6 +546,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                 extra.update(history=_concat_history(chunks[m]))
             if field:
                 extra.update(field_avg=field_map_means(prm.DL, prm.DH, **planes[m]))
+            if probe:
+                extra.update(probes=_concat_probes(probe[0], prm.DL, pchunks[m]))
             members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra))
     return members, wall, policy, sums, planes
 
@@ -550,7 +659,8 @@ def field_table(prms, field_avgs):
 
 def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0, settle_tol=0.05, average_from=None,
               average_every=1, parts_list=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0, log=None,
-              field_from=None, field_every=1, field_shape=None, field_walls=False):
+              field_from=None, field_every=1, field_shape=None, field_walls=False, probe_points=None, probe_every=1,
+              probe_capacity=65536, probe_from=None, probe_walls=False):
     """A parameter sweep: M channels of one geometry that differ in mu, c_f, p0, gravity_g, transport_coeff, stepped as one
     batch (capi.Batch) with every member's step history recorded on the device, inside the step loop (include/sphx.h
     section 2f) as run(history_every=...) does for one channel.  The members advance output point by output point as in
@@ -561,14 +671,16 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     statistics as well, as in run_ensemble -- every average_every-th step ending at t >= average_from -- and each member
     gets a time_avg.  field_from: every member's velocity map as well (include/sphx.h section 2g), with the keywords of
     run(): each member gets a field_avg and the table the columns field_L2, field_x_spread, field_ix, field_uy_rms of
-    field_figures(prm_m, field_avg_m).  A member that lost records to a full buffer raises RuntimeError, which names the member and the
+    field_figures(prm_m, field_avg_m).  probe_points: every member's point probes as well (include/sphx.h section 2i), with
+    the keywords of run(): one set of points for all members, and each member gets its probes.  A member that lost records to a full buffer raises RuntimeError, which names the member and the
     capacity the output interval needed.  Returns a SweepResult."""
     prms = list(prms)
     members, wall, policy, _, planes = _run_batch(
         "run_sweep", prms, parts_list, dict(lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
                                             rebuild_every=rebuild_every), log, history=(history_every, history_capacity),
         average=None if average_from is None else (average_from, average_every),
-        field=_field_request(field_from, field_every, field_shape, field_walls))
+        field=_field_request(field_from, field_every, field_shape, field_walls),
+        probe=None if probe_points is None else (probe_points, probe_every, probe_capacity, probe_from, probe_walls))
     table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
     if planes is not None:
         table.update(field_table(prms, [r.field_avg for r in members]))

@@ -20,6 +20,12 @@
  *   sphx_ctx_mex('field_sample', h)    % add one sample of the current state now
  *   [count, w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples, t_first, t_last] = sphx_ctx_mex('field_read', h)
  *       [ny x nx] matrices over linspace(0, DL, nx) x linspace(0, DH, ny) (field map, include/sphx.h section 2e)
+ *   sphx_ctx_mex('probe_enable', h, points, every, capacity, t_from, with_walls)   % points: [P x 2] (x, y)
+ *   sphx_ctx_mex('probe_disable', h)
+ *   sphx_ctx_mex('probe_sample', h)    % append one record of the current state now
+ *   [step, t, weight, u_x, u_y, rho, n_dropped] = sphx_ctx_mex('probe_read', h, drain)
+ *       step, t: n x 1; weight, u_x, u_y, rho: n x P, one row per recorded step (point probes, include/sphx.h section 2h);
+ *       drain ~= 0 empties the device buffer
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -221,6 +227,66 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 6) plhs[6] = mxCreateDoubleScalar((double)ns);
         if (nlhs > 7) plhs[7] = mxCreateDoubleScalar(t0);
         if (nlhs > 8) plhs[8] = mxCreateDoubleScalar(t1);
+    } else if (strcmp(cmd, "probe_enable") == 0) {
+        sphx_probes_config pc;
+        const mxArray *pts;
+        double *rows;
+        size_t np, k;
+        int rc;
+        arity(cmd, nrhs, 7, nlhs, 0);
+        pts = prhs[2];
+        if (!mxIsDouble(pts) || mxGetNumberOfElements(pts) == 0 || mxGetN(pts) != 2)
+            mexErrMsgIdAndTxt("SPHX:Probe:config", "probe_enable: points must be a double [P x 2] array");
+        np = mxGetM(pts);
+        if (np > SPHX_PROBE_MAX_POINTS) mexErrMsgIdAndTxt("SPHX:Probe:config", "probe_enable: at most %d points", SPHX_PROBE_MAX_POINTS);
+        rows = (double *)mxMalloc(np * 2 * sizeof(double));
+        for (k = 0; k < np; ++k) {  /* MATLAB stores columns; the library takes (x, y) rows */
+            rows[2 * k] = mxGetDoubles(pts)[k];
+            rows[2 * k + 1] = mxGetDoubles(pts)[k + np];
+        }
+        memset(&pc, 0, sizeof(pc));
+        pc.n_points = (int32_t)np;
+        pc.every = (int32_t)mxGetScalar(prhs[3]);
+        pc.capacity = (int32_t)mxGetScalar(prhs[4]);
+        pc.t_from = mxGetScalar(prhs[5]);
+        pc.with_walls = (int32_t)mxGetScalar(prhs[6]);
+        pc.points = rows;
+        rc = sphx_ctx_probes_enable(handle(prhs[1]), &pc);  /* (the points are copied) */
+        mxFree(rows);
+        ok(rc);
+    } else if (strcmp(cmd, "probe_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_probes_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "probe_sample") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_probes_sample(handle(prhs[1])));
+    } else if (strcmp(cmd, "probe_read") == 0) {
+        sphx_ctx *c;
+        int n = 0, got = 0, np = 0, k, p, f, drain, rc;
+        int64_t dropped = 0;
+        double *times, *values;
+        arity(cmd, nrhs, 3, nlhs, 7);
+        c = handle(prhs[1]);
+        drain = mxGetScalar(prhs[2]) != 0.0;
+        ok(sphx_ctx_probes_read(c, 0, NULL, NULL, &np, &n, NULL, 0));
+        times = (double *)mxMalloc((size_t)(n > 0 ? n : 1) * 2 * sizeof(double));
+        values = (double *)mxMalloc((size_t)(n > 0 ? n : 1) * (size_t)np * SPHX_PROBE_FIELDS * sizeof(double));
+        rc = sphx_ctx_probes_read(c, n, times, values, NULL, &got, &dropped, drain);  /* (nothing is stepped in between: got == n) */
+        if (rc != SPHX_OK) { mxFree(times); mxFree(values); ok(rc); }
+        for (f = 0; f < 2 && f < (nlhs > 0 ? nlhs : 1); ++f) {
+            plhs[f] = mxCreateDoubleMatrix((mwSize)got, 1, mxREAL);
+            for (k = 0; k < got; ++k) mxGetDoubles(plhs[f])[k] = times[(size_t)k * 2 + f];
+        }
+        for (f = 0; f < SPHX_PROBE_FIELDS && 2 + f < nlhs; ++f) {  /* the library's rows are records; MATLAB stores columns */
+            double *out;
+            plhs[2 + f] = mxCreateDoubleMatrix((mwSize)got, (mwSize)np, mxREAL);
+            out = mxGetDoubles(plhs[2 + f]);
+            for (k = 0; k < got; ++k)
+                for (p = 0; p < np; ++p) out[(size_t)p * got + k] = values[((size_t)k * np + p) * SPHX_PROBE_FIELDS + f];
+        }
+        mxFree(times);
+        mxFree(values);
+        if (nlhs > 6) plhs[6] = mxCreateDoubleScalar((double)dropped);
     } else if (strcmp(cmd, "destroy") == 0) {
         arity(cmd, nrhs, 2, nlhs, 0);
         sphx_ctx_destroy(handle(prhs[1]));

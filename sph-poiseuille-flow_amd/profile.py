@@ -128,6 +128,53 @@ def field_map_nodes(DL, DH, nx, ny):
     return np.linspace(0.0, DL, nx), np.linspace(0.0, DH, ny)
 
 
+def _shepard_sums(X, Y, pos, vel, DL, h, chunk, mass=None):
+    """S0 = sum W, S1 = sum W u_x, S2 = sum W u_y (and, with mass, Sm = sum m W) at the points (X, Y) over the rows of pos / vel:
+    cubic spline of the physics, every particle within 2h, nearest image in x, no lower cut.  [3 or 4, len(X)]."""
+    sigma, rcut2 = 10.0 / (7.0 * np.pi * h * h), (2.0 * h) * (2.0 * h)
+    px, py, ux, uy = pos[:, 0], pos[:, 1], vel[:, 0], vel[:, 1]
+    S = np.zeros((3 if mass is None else 4, len(X)))
+    for a in range(0, len(X), chunk):
+        dx = X[a:a + chunk, None] - px[None, :]
+        dx -= DL * np.round(dx / DL)  # the nearest image (x in [0, DL): at most one period, the device's single fold)
+        dy = Y[a:a + chunk, None] - py[None, :]
+        r2 = dx * dx + dy * dy
+        q = np.sqrt(r2) / h
+        tq = 2.0 - q
+        W = np.where(q < 1.0, sigma * (1.0 - 1.5 * q * q + 0.75 * q * q * q), sigma * 0.25 * tq * tq * tq)
+        W = np.where(r2 < rcut2, W, 0.0)
+        S[0, a:a + chunk] = W.sum(axis=1)
+        S[1, a:a + chunk] = W @ ux
+        S[2, a:a + chunk] = W @ uy
+        if mass is not None:
+            S[3, a:a + chunk] = W @ mass
+    return S
+
+
+def shepard_points(pos, vel, mass, DL, h, dp, points, wall_pos=None, wall_vel=None, chunk=2048):
+    """One sample of the point probes of include/sphx.h section 2h, in numpy, at the points [P, 2] (x any finite value, folded
+    into [0, DL)): the Shepard sums of shepard_field at arbitrary points plus Sm = sum m_j W_j.  pos / vel / mass: the fluid
+    rows; wall_pos / wall_vel: wall rows that enter S0, S1 and S2 (with_walls) -- never Sm, the summation density from the
+    fluid, which within 2h of a wall lacks the wall's share.
+    Returns points [P, 2] as folded, S0, weight = S0 dp^2, u_x = S1 / S0, u_y = S2 / S0, rho = Sm as [P] arrays; where
+    S0 == 0 the velocities are NaN and weight = rho = 0.  The oracle of the device kernel and the host route for a state
+    that never was on the device."""
+    pos, vel = np.asarray(pos, dtype=np.float64), np.asarray(vel, dtype=np.float64)
+    mass = np.asarray(mass, dtype=np.float64)
+    pts = np.array(points, dtype=np.float64).reshape(-1, 2)
+    f = pts[:, 0] - np.floor(pts[:, 0] / DL) * DL
+    pts[:, 0] = np.where((f >= 0.0) & (f < DL), f, 0.0)
+    if wall_pos is not None:
+        pos = np.concatenate([pos, np.asarray(wall_pos, dtype=np.float64)])
+        vel = np.concatenate([vel, np.asarray(wall_vel, dtype=np.float64)])
+        mass = np.concatenate([mass, np.zeros(len(pos) - len(mass))])
+    S = _shepard_sums(pts[:, 0], pts[:, 1], pos, vel, DL, h, chunk, mass)
+    hit = S[0] > 0.0
+    safe = np.where(hit, S[0], 1.0)
+    return dict(points=pts, S0=S[0], weight=np.where(hit, S[0] * (dp * dp), 0.0), u_x=np.where(hit, S[1] / safe, np.nan),
+                u_y=np.where(hit, S[2] / safe, np.nan), rho=np.where(hit, S[3], 0.0))
+
+
 def shepard_field(pos, vel, DL, DH, h, nx, ny, wall_pos=None, wall_vel=None, chunk=2048, nodes=None):
     """One sample of the field map of include/sphx.h section 2e, in numpy: Shepard interpolation of vel onto the nx x ny
     nodes with the cubic spline of the physics over every particle within 2h (minimum image in x -- the nearest image
@@ -142,22 +189,7 @@ def shepard_field(pos, vel, DL, DH, h, nx, ny, wall_pos=None, wall_vel=None, chu
         vel = np.concatenate([vel, np.asarray(wall_vel, dtype=np.float64)])
     xs, ys = field_map_nodes(DL, DH, nx, ny)
     flat = np.arange(nx * ny) if nodes is None else np.asarray(nodes, dtype=np.int64)
-    X, Y = xs[flat // ny], ys[flat % ny]
-    sigma, half, rcut2 = 10.0 / (7.0 * np.pi * h * h), 0.5 * DL, (2.0 * h) * (2.0 * h)
-    px, py, ux, uy = pos[:, 0], pos[:, 1], vel[:, 0], vel[:, 1]
-    S = np.zeros((3, len(flat)))
-    for a in range(0, len(flat), chunk):
-        dx = X[a:a + chunk, None] - px[None, :]
-        dx -= DL * np.round(dx / DL)  # the nearest image (x in [0, DL): at most one period, the device's single fold)
-        dy = Y[a:a + chunk, None] - py[None, :]
-        r2 = dx * dx + dy * dy
-        q = np.sqrt(r2) / h
-        tq = 2.0 - q
-        W = np.where(q < 1.0, sigma * (1.0 - 1.5 * q * q + 0.75 * q * q * q), sigma * 0.25 * tq * tq * tq)
-        W = np.where(r2 < rcut2, W, 0.0)
-        S[0, a:a + chunk] = W.sum(axis=1)
-        S[1, a:a + chunk] = W @ ux
-        S[2, a:a + chunk] = W @ uy
+    S = _shepard_sums(xs[flat // ny], ys[flat % ny], pos, vel, DL, h, chunk)
     hit = S[0] > 0.0
     safe = np.where(hit, S[0], 1.0)
     fields = dict(S0=S[0], S1=S[1], S2=S[2], u_x=np.where(hit, S[1] / safe, np.nan), u_y=np.where(hit, S[2] / safe, np.nan))
