@@ -602,7 +602,7 @@ int sphx_batch_field_map_read(sphx_batch *batch, int capacity, int *nx, int *ny,
  *    every < 1, capacity < 1 or capacity * n_points * 4 > 1 << 27, non-finite t_from, with_walls not 0 or 1, or the
  *    allocation fails: the context then goes on without probes), SPHX:Probe:disabled (SPHX_ERR_STATE: a call that needs
  *    the probes while they are off), SPHX:Probe:capacity (the caller's arrays are smaller than n_records); every call on
- *    a slab context fails with SPHX_ERR_ARG, SPHX:Probe:slab.  A refused enable leaves running probes, and their
+ *    a slab context fails with SPHX_ERR_ARG, SPHX:Probe:slab (the probes of a ring: sphx_slab_probes_*, section 3a).  A refused enable leaves running probes, and their
  *    records, untouched.
  * ---------------------------------------------------------------------------------------------- */
 
@@ -734,8 +734,8 @@ int sphx_slab_snapshot(sphx_ctx *ctx, int capacity, int *n, double *x, double *y
                        double *vy, double *drho, int *id, int *owned);
 
 /* ------------------------------------------------------------------------------------------------
- * 3a. Samplers of a slab ring: the flow statistics of section 2a, the step history of section 2d and the velocity-field
- *    map of section 2e for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that a ring
+ * 3a. Samplers of a slab ring: the flow statistics of section 2a, the step history of section 2d, the velocity-field
+ *    map of section 2e and the point probes of section 2h (described with their three calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that a ring
  *    reports its time-averaged profile, the settling of its wall shear and its averaged field without a snapshot per
  *    sample.  The config structs, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* / SPHX:Field:*
  *    identifiers are those of sections 2a / 2d / 2e; sphx_ctx_flow_stats_*,
@@ -796,6 +796,29 @@ int sphx_slab_field_map_reset(sphx_ctx *ctx);
 int sphx_slab_field_map_read(sphx_ctx *ctx, int capacity, int *nx, int *ny, int *i_lo, int *i_hi, double *count,
                              double *sum_w, double *sum_ux, double *sum_uy, double *sum_ux2, double *sum_uy2,
                              int64_t *n_samples, double *t_first, double *t_last);
+/* Point probes of a ring (the probes of section 2h; k_point_probes_s).  A probe's sample is a ratio and a density, so, like
+ * the map's nodes, the POINTS are divided among the slabs: cfg holds the RING's whole list, the same on every rank, and a
+ * slab owns the points with edge(r) <= x < edge(r + 1), x as folded into [0, DL) and
+ * edge(r) = ((r * ncx) / n_ranks) * (DL / ncx) the left edge of rank r's first cell column (ncx: the ring's cell columns);
+ * rank 0 owns from 0 and the last rank up to DL.  Every point has exactly one owner -- a point on a cut belongs to the slab
+ * right of it, two equal points to the same slab -- computed once, at enable, by the same arithmetic on every rank.  A slab
+ * records the COMPLETE sample of each probe it owns (weight, u_x, u_y and rho: the masses of its halo copies enter rho) from
+ * the particles it owns and from its halo copies, in its own buffer of `capacity` records with its own n_records and
+ * n_dropped.  A slab that owns no probe still records {step, t} and counts, so every slab's series has the same length and
+ * the same steps.  The ring's series is the slabs' columns put back in the list's order (`index`); nothing is added.
+ * Gating, values, determinism and the SPHX:Probe:config checks are those of section 2h (the bound on
+ * capacity * n_points * 4 is taken with the ring's n_points).  A refused enable leaves running probes, their records and a
+ * prepared graph as they are.  SPHX:Probe:disabled: a read while the probes are off.  sphx_ctx_probes_* keep refusing a
+ * slab (SPHX:Probe:slab). */
+int sphx_slab_probes_enable(sphx_ctx *ctx, const sphx_probes_config *cfg);
+int sphx_slab_probes_disable(sphx_ctx *ctx);
+/* The slab's records: times [capacity][2] and values [capacity][*n_owned][SPHX_PROBE_FIELDS], row-major, as
+ * sphx_ctx_probes_read; index [*n_owned]: the positions of the owned probes in the ring's list of *n_points_ring points,
+ * ascending.  Any output may be NULL.  capacity = 0: only the sizes and counts are reported, nothing is copied or drained
+ * (call once so to learn n_owned and n_records, then with arrays of that size); SPHX:Probe:capacity when an array is given
+ * and capacity is below n_records.  drain != 0: the buffer is emptied and n_dropped zeroed after copying. */
+int sphx_slab_probes_read(sphx_ctx *ctx, int capacity, double *times, double *values, int *index, int *n_points_ring,
+                          int *n_owned, int *n_records, int64_t *n_dropped, int drain);
 
 #ifdef __cplusplus
 }

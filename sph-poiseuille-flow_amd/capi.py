@@ -92,6 +92,7 @@ EXPORTS = [
     "sphx_slab_flow_stats_enable", "sphx_slab_flow_stats_disable", "sphx_slab_flow_stats_reset", "sphx_slab_flow_stats_read",
     "sphx_slab_history_enable", "sphx_slab_history_disable", "sphx_slab_history_read",
     "sphx_slab_field_map_enable", "sphx_slab_field_map_disable", "sphx_slab_field_map_reset", "sphx_slab_field_map_read",
+    "sphx_slab_probes_enable", "sphx_slab_probes_disable", "sphx_slab_probes_read",
     "sphx_batch_create", "sphx_batch_destroy", "sphx_batch_advance", "sphx_batch_enqueue_steps", "sphx_batch_sync",
     "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
     "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",

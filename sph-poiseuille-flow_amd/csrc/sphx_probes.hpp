@@ -1,5 +1,5 @@
-// sphx_probes.hpp -- point probes of a resident context (include/sphx.h section 2h) and of every member of a batch (section
-// 2i, k_point_probes_b): a slot sampler (sphx_slot_sample.hpp) that interpolates the state the step left onto P fixed points
+// sphx_probes.hpp -- point probes of a resident context (include/sphx.h section 2h), of every member of a batch (section
+// 2i, k_point_probes_b) and of a slab of a ring (section 3a, k_point_probes_s): a slot sampler (sphx_slot_sample.hpp) that interpolates the state the step left onto P fixed points
 // and appends one record -- {step, t} and P x kProbeFields values -- to a record buffer in device memory.  The one sampler
 // whose signal is resolved in space AND time.
 //
@@ -44,6 +44,41 @@
 // stream do not overlap, and a kernel boundary publishes the head to the next launch.  The values of the other workgroups are
 // not read by the last one; the release / acquire of last_out_fenced costs a few workgroups a fence on the steps sampled.
 // Up to kProbeBlock / 64 probes fit one workgroup and need no ticket.
+//
+// A slab of a ring (include/sphx.h section 3a, k_point_probes_s = point_probes_body<true>).  The POINTS are divided among the
+// slabs as the map's node columns are (probe_owner, sphx_samplers.hpp: rank r owns edge(r) <= x < edge(r + 1), edge(r) the
+// left edge of its first cell column, decided once on the host); ProbeArgs is unchanged and holds the owned subset, compacted
+// at enable, with the slab's own times / values / head.  A slab computes the complete sample of each probe it owns -- S0, S1,
+// S2 and Sm -- in its own open window (Grid::periodic = 0, half_DL = +inf: min_image is a no-op and the one probe_add stays),
+// with the sweep centred on the point's cell column CLAMPED into the owned columns [own_c0, own_c1), the clamp of
+// field_map_body<true>: it reads the columns own - 1 .. own + 1 only, where the halo copies carry the finished step's state
+// (DESIGN.md section 5).  Why the map's argument carries over from a node to a point:
+//  * no shift: the point is x as the host folded it into [0, DL), and its owner's owned range [own_lo, own_hi) = [edge(r),
+//    edge(r + 1)) contains that very number -- the slab keeps its owned particles at their global x, the first slab holds the
+//    last slab's particles at x - DL and the last slab the first slab's at x + DL, so cell_of on the folded x finds the right
+//    column and a probe at x = 0 (also what x = DL and -DL fold to) or within rounding of DL needs no minimum image;
+//  * a point strictly inside the owned range falls into an owned column and the clamp does nothing;
+//  * a point ON a cut is x = edge(r) = own_lo exactly, owned by rank r.  cell_of computes (x - x0) * inv_csx, which may round
+//    to just below own_c0: the clamp moves the centre up by one column, as for a node column that falls on a cut.  A particle
+//    within 2h of the point was binned within 2h + drift of the edge, i.e. in the outermost owned column or in the first halo
+//    column beside it -- both among the clamped centre's three, because a column is 2h + skin wide and the ring re-bins at a
+//    drift of skin / 2.  The same holds at own_hi for a point within rounding of DL in the last slab (x < DL after the fold,
+//    (x - x0) * inv_csx may round up to own_c1): the spare half of the skin is many orders of magnitude more than the rounding;
+//  * a point within 2h of a cut but off it: its cell is the outermost owned column, the three columns include the first halo
+//    column, and the halo is four columns deep.
+// Sm needs the MASS of a halo copy -- the first sampled value that does.  It is there: s.mass of the view is the layout array
+// fmass_[l] (sphx_ctx::view, sphx_resident.hip:267-270), in slot order with S[1-q].pos / .vel.  Every image inside the window
+// enters it with its particle's mass at creation (slab_setup, sphx_resident.hip:2162-2169, 2189).  At a re-binning the owner
+// sends m = sn.mass[i] with the state (k_slab_pack3, sphx_kernels.hpp:3628, 3647-3654), the receiver stores it beside the
+// kept particles' (kmass, k_slab_unpack3, sphx_kernels.hpp:3639, 3732) and the re-binning chain reorders kmass into the new
+// layout's mass (slab_phase3, sphx_resident.hip:2786-2789).  On a frozen step message A carries 0.0 in the mass block
+// (sphx_kernels.hpp:3597-3598) and the receiver writes pos, vel and drho of the fixed slots only (sphx_kernels.hpp:3705-3710):
+// the mass of a halo copy is not touched between two re-binnings, and a particle's mass never changes.  The sampler runs in
+// front of phase 3, so on a re-binning step it still reads the layout the step ran in.  Fluid candidates read s.mass[j], wall
+// candidates add zero, on a slab as on a context; nothing assumes a uniform mass.
+// A slab that owns no probe launches one workgroup all the same (n_points = 0): no wave owns a probe, thread 0 passes the plain
+// barrier, stamps {step, t} and counts the record, as a block of zero node columns still counts its sample -- every slab's
+// series has the length of its neighbours'.
 #pragma once
 #include "../../include/sphx.h"
 #include "sphx_slot_sample.hpp"
@@ -133,6 +168,9 @@ __device__ __forceinline__ void probe_columns(const Grid &g, const KernelConst &
 // The record of one channel closing the step slot of parity q, on clock clk, by the gridDim.x workgroups of a grid row; s is the
 // state the step left (pos, vel, mass and the cell ranges of the layout it is stored in); a's times / values / head are that
 // channel's own.  Every thread of every workgroup reaches the final barrier.
+// kSlab: the channel is a slab of a ring -- a.points, a.n_points and the values are those of the probes the slab OWNS (possibly
+// none: the one workgroup still stamps and counts the record), and the sweep is centred on a column the slab owns.
+template <bool kSlab = false>
 __device__ __forceinline__ void point_probes_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                                   const Walls &w, const ProbeArgs &a)
 {
@@ -148,6 +186,7 @@ __device__ __forceinline__ void point_probes_body(const Clock *clk, int q, const
         const double xp = pt.x, yp = pt.y;
         int cx, cy;
         cell_of(g, xp, yp, cx, cy);
+        if constexpr (kSlab) cx = min(max(cx, g.own_c0), g.own_c1 - 1);
         cx = __builtin_amdgcn_readfirstlane(cx);
         cy = __builtin_amdgcn_readfirstlane(cy);
         const int cylo = max(cy - 1, 0), cyhi = min(cy + 1, g.ncy - 1);
@@ -225,6 +264,16 @@ __global__ __launch_bounds__(kProbeBlock) void k_point_probes_b(Members mb, int 
     a.values += (size_t)m * (size_t)a.capacity * (size_t)a.n_points * kProbeFields;
     a.head += m;
     point_probes_body(mb.clk + m, q, g, ph, member_set(mb, m, s), w, a);
+}
+
+// slab of a ring (sphx_slab_probes_*): the complete sample -- S0, S1, S2 and Sm -- of every probe this slab owns (the host
+// compacted the owned subset at enable, probe_owner in sphx_samplers.hpp), from the particles it owns and from its halo copies,
+// into the slab's own times / values / head.  Launched behind k_slab_pack3 and in front of everything of phase 3
+// (launch_slab_samplers): s is S[1-q] with the masses and the cell ranges of the layout the step ran in.  gridDim.x is fixed at
+// enable from the owned count, at least 1.
+__global__ __launch_bounds__(kProbeBlock) void k_point_probes_s(const Clock *clk, int q, Grid g, Phys ph, FluidSet s, Walls w, ProbeArgs a)
+{
+    point_probes_body<true>(clk, q, g, ph, s, w, a);
 }
 
 }  // namespace sphx

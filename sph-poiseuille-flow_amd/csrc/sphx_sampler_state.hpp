@@ -76,17 +76,21 @@ struct FieldMap {
 
 // Point probes (sphx_ctx_probes_*, sphx_batch_probes_*; sphx_probes.hpp) of a context or of the M members of a batch: one
 // configuration and one set of points, member m's times at m * cfg.capacity * 2, its values at m * cfg.capacity * row(), its
-// head at m.
+// head at m.  Of a slab of a ring (sphx_slab_probes_*): cfg and folded are the ring's list, the same on every rank; the device
+// holds the probes the slab owns -- those of `index`, in the ring's order -- and their values.
 struct Probes {
     bool on = false;
     int members = 1;
     sphx_probes_config cfg{};     // (cfg.points: nullptr -- the points are copied)
     std::vector<double> folded;   // [n_points][2]: x folded into [0, DL), y
+    bool part = false;            // a slab's: points / values are those of the probes of `index` only (possibly none)
+    std::vector<int> index;       // [n_owned] positions of the owned probes in the ring's list, ascending
     DevBuf<double2> points;
     DevBuf<double> times, values;
     DevBuf<ProbeHead> head;
 
-    size_t row() const { return (size_t)cfg.n_points * kProbeFields; }  // the values of one record
+    int held() const { return part ? (int)index.size() : cfg.n_points; }  // probes on the device
+    size_t row() const { return (size_t)held() * kProbeFields; }          // the values of one record
     void check(const sphx_params &prm, const sphx_probes_config *cfg, int M);
     void alloc(const Probes &checked, int M, hipStream_t st);
     void zero(hipStream_t st) { head.zero(st); }  // (the counters: records beyond n_records are never read)

@@ -1,6 +1,7 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
-// the velocity-field map (2e; 2g) -- those three also of a slab of a ring (3a, at the end of this file) -- and the point probes (2h; 2i).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// the velocity-field map (2e; 2g) and the point probes (2h; 2i) -- all four also of a slab of a ring (3a, at the end of this
+// file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp and sphx_probes.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -207,7 +208,7 @@ ProbeArgs probe_args(sphx_ctx *c, int every)
     a.points = p.points.get(); a.times = p.times.get(); a.values = p.values.get(); a.head = p.head.get();
     a.dp2 = c->prm.dp * c->prm.dp;
     a.t_from = p.cfg.t_from;
-    a.n_points = p.cfg.n_points; a.capacity = p.cfg.capacity;
+    a.n_points = p.held(); a.capacity = p.cfg.capacity;  // (a slab: the probes it owns)
     a.every = every;
     a.with_walls = p.cfg.with_walls && c->nw > 0 ? 1 : 0;
     return a;
@@ -646,12 +647,24 @@ void Probes::alloc(const Probes &checked, int M, hipStream_t st)
 {
     cfg = checked.cfg;
     folded = checked.folded;
+    part = checked.part;
+    index = checked.index;
     members = M;
-    points.alloc((size_t)cfg.n_points);
+    points.alloc(std::max<size_t>((size_t)held(), 1));  // (a slab that owns no probe still has a head and its times)
     times.alloc((size_t)M * cfg.capacity * 2);
-    values.alloc((size_t)M * cfg.capacity * row());
+    values.alloc(std::max<size_t>((size_t)M * cfg.capacity * row(), 1));
     head.alloc(M);
-    points.upload(reinterpret_cast<const double2 *>(folded.data()), (size_t)cfg.n_points, st);  // (sampler_on waits for st)
+    if (!part) {
+        points.upload(reinterpret_cast<const double2 *>(folded.data()), (size_t)cfg.n_points, st);  // (sampler_on waits for st)
+        return;
+    }
+    std::vector<double> own(index.size() * 2);  // the owned subset, compacted in the ring's order
+    for (size_t k = 0; k < index.size(); ++k) {
+        own[2 * k] = folded[2 * (size_t)index[k]];
+        own[2 * k + 1] = folded[2 * (size_t)index[k] + 1];
+    }
+    points.upload(reinterpret_cast<const double2 *>(own.data()), index.size(), st);
+    SPHX_HIP(hipStreamSynchronize(st));  // (`own` goes out of scope here)
 }
 
 // Every member's counts (n_records[m], n_dropped[m], where given) and its filled rows, into times[m][0 .. n_records[m])[2] of a
@@ -754,6 +767,8 @@ SPHX_EXPORT int sphx_ctx_probes_read(sphx_ctx *c, int capacity, double *times, d
 // The velocity-field map: a node's sample is a ratio, so partial sums over owned particles cannot be pooled -- the NODES are
 // divided among the slabs instead, a slab computes the complete sample of every node column it owns (field_block) from its
 // owned particles and its halo copies, and the ring's map is the slabs' blocks side by side.
+// The point probes: the same reasoning with points for nodes -- the POINTS are divided (probe_owner), a slab records the
+// complete sample of every probe it owns, and the ring's series is the slabs' columns back in the list's order.
 
 namespace {
 
@@ -761,10 +776,11 @@ namespace {
 // later) and in front of everything of phase 3: the clock is the finished step's, S[1-q] holds the owned particles' new state,
 // Vol / B (c->tmp) and the layout arrays (cell, mass) are those of the layout the step ran in -- clk->n is still that
 // layout's count (k_slab_unpack3 sets the new one), so a re-binning step needs no src_of.  One self-skipping launch each,
-// on the slab's stream; both off: nothing is enqueued.
+// on the slab's stream, in the order statistics, history, map, probes; all off: nothing is enqueued, and a sampler that is
+// off adds nothing to what the others enqueue.
 void launch_slab_samplers(sphx_ctx *c)
 {
-    if (!c->fstats.on && !c->hist.on && !c->fmap.on) return;
+    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on) return;
     const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
     const FluidSet s = c->view(1 - q, 0);
@@ -786,6 +802,29 @@ void launch_slab_samplers(sphx_ctx *c)
         launch_s(c, "k_field_map_s", k_field_map_s, dim3(field_map_blocks(a)), dim3(kFieldBlock), 0, clk, q, c->grid, c->phys, s,
                  c->walls, a, f.i_lo, f.nx);
     }
+    // (pos, vel, MASS and the cell ranges of S[1-q]: the view's mass is the layout array of the layout the step ran in, which a
+    //  halo copy entered with its particle's mass at the last re-binning -- sphx_probes.hpp; workgroups from the owned probes,
+    //  fixed at enable, at least one: a slab without a probe still stamps and counts the record)
+    if (c->probes.on) {
+        ProbeArgs a = probe_args(c, c->probes.cfg.every);
+        a.with_walls = c->probes.cfg.with_walls && c->walls.n > 0 ? 1 : 0;
+        launch_s(c, "k_point_probes_s", k_point_probes_s, dim3(std::max(probe_blocks(a), 1u)), dim3(kProbeBlock), 0, clk, q, c->grid,
+                 c->phys, s, c->walls, a);
+    }
+}
+
+// The rank of slab c's ring that owns a probe at x, folded into [0, DL): rank r when edge(r) <= x < edge(r + 1), with
+// edge(r) = ((r * ncx_ring) / n_ranks) * (DL / ncx_ring) -- the left edge of rank r's first cell column, the arithmetic of
+// Grid::own_lo (slab_setup) and of field_block -- rank 0 from 0 and the last rank up to DL.  The edges ascend, so every x has
+// exactly one owner, a point ON a cut (rank r's, never rank r - 1's) and both of two equal points included; every rank
+// evaluates the same expression on the same list, and no kernel tests ownership in its own frame.
+int probe_owner(const sphx_ctx *c, double x)
+{
+    const double csx = c->prm.DL / c->ncx_ring;
+    int owner = 0;
+    for (int r = 1; r < c->n_ranks; ++r)
+        if (x >= (double)(((long long)r * c->ncx_ring) / c->n_ranks) * csx) owner = r;
+    return owner;
 }
 
 // The block of node columns [i_lo, i_hi) of the ring's nx that slab c samples.  One monotone rule from the global cell-column
@@ -972,6 +1011,49 @@ SPHX_EXPORT int sphx_slab_field_map_read(sphx_ctx *c, int capacity, int *nx, int
                t_first, t_last);
     if (i_lo) *i_lo = f.i_lo;
     if (i_hi) *i_hi = f.i_hi;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_probes_enable(sphx_ctx *c, const sphx_probes_config *cfg)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    Probes checked;
+    checked.check(c->prm, cfg, 1);  // (a refused configuration leaves running probes and a prepared graph as they are)
+    checked.part = true;
+    for (int p = 0; p < checked.cfg.n_points; ++p)
+        if (probe_owner(c, checked.folded[2 * (size_t)p]) == c->rank) checked.index.push_back(p);
+    slab_samplers_changed(c);
+    sampler_on(c->probes, kProbeNames, c->sched, c->stream, [&] { c->probes.alloc(checked, 1, c->stream); });
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_probes_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    if (c->probes.on) {
+        slab_samplers_changed(c);
+        sampler_off(c->probes, c->sched, c->stream);
+    }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_probes_read(sphx_ctx *c, int capacity, double *times, double *values, int *index, int *n_points_ring,
+                                      int *n_owned, int *n_records, int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    Probes &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::probes, kProbeNames);
+    slab_settle(c);  // (the records of everything enqueued)
+    const bool sizes_only = capacity == 0;  // nothing is copied and nothing drained
+    p.read(c->stream, capacity, sizes_only ? nullptr : times, sizes_only ? nullptr : values, n_records, n_dropped,
+           !sizes_only && drain != 0);
+    if (index) std::copy(p.index.begin(), p.index.end(), index);
+    if (n_points_ring) *n_points_ring = p.cfg.n_points;
+    if (n_owned) *n_owned = p.held();
     return SPHX_OK;
     SPHX_CATCH
 }

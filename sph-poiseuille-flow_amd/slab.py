@@ -15,8 +15,8 @@ Layers:
   HipSlabEngine    -- the per-rank compute engine (libsphx slab context)
   SlabDriver       -- step loop = engine.compute -> exchange -> engine.finish
   pool_ring_* / ring_* / all_reduce_ring_*
-                   -- the ring's flow statistics and step history from the slabs' partial sums, and its field map from the
-                      slabs' blocks of node columns
+                   -- the ring's flow statistics and step history from the slabs' partial sums, its field map from the
+                      slabs' blocks of node columns, and its point probes from the slabs' owned probes
   bench_main()     -- bench.py's multi-GPU leg
 """
 from __future__ import annotations
@@ -121,8 +121,10 @@ class HipSlabEngine(_capi._Sampled):
     group_run().  What they return are this slab's PARTIAL sums over the particles it owns: pool_ring_sums / pool_ring_history
     (ring_flow_stats / ring_history, all_reduce_ring_*) make the ring's.  field_part_enable / _disable / _reset /
     field_part_sums are the velocity-field map: the complete planes of the node columns this slab owns, a PART of the ring's
-    map, which pool_ring_field_map (ring_field_map, all_reduce_ring_field_map) puts together.  Enabling or disabling drops a
-    graph made by graph_prepare()."""
+    map, which pool_ring_field_map (ring_field_map, all_reduce_ring_field_map) puts together.  probes_part_enable / _disable /
+    probes_part_records are the point probes: the complete series of the probes this slab owns, a PART of the ring's, which
+    pool_ring_probes (ring_probes, all_reduce_ring_probes) puts together.  Enabling or disabling drops a graph made by
+    graph_prepare()."""
     _stem, _where = "sphx_slab_", "slab"
 
     def __init__(self, prm, parts, rank, world, device, lanes_per_particle=0, halo_cols=HALO_COLS, t_end=None,
@@ -286,6 +288,43 @@ class HipSlabEngine(_capi._Sampled):
                    t_last=float(t1.value))
         return out
 
+    # ---- point probes (include/sphx.h section 3a): the probes this slab owns -- a PART of the ring's series ----
+    def probes_part_enable(self, points, every=1, capacity=65536, t_from=0.0, with_walls=False):
+        """A context's probes_enable (capi._Stepped) for the RING's points [P, 2], the same on every rank; this slab records
+        the probes it owns -- every one completely, from its owned particles and its halo copies -- inside run() /
+        group_run(), and {step, t} of every sampled step even when it owns none.  (Re)configures and empties the buffer;
+        drops a graph made by graph_prepare()."""
+        cfg, pts = _capi.probes_config(self.params, points, every, capacity, t_from, with_walls)
+        self._call("probes_enable", C.byref(cfg))
+        self._probes_part = pts  # the ring's folded points [P, 2] while the probes are on
+
+    def probes_part_disable(self):
+        self._call("probes_disable")
+        self._probes_part = None
+
+    def probes_part_records(self, drain=False) -> dict:
+        """This slab's series so far: points [P, 2] (the ring's, as folded), index [n_owned] (the owned probes' positions in
+        them, ascending), step (int64) and t [n_records], weight, u_x, u_y and rho as [n_records, n_owned] arrays, n_dropped;
+        drain empties the buffer after the copy.  pool_ring_probes puts the ranks' columns back in the points' order."""
+        pts = _capi._enabled(getattr(self, "_probes_part", None), "Probe", "point probes are not enabled on this slab")
+        ring, own, n, dropped = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+
+        def read(cap, times, values, index, drain):
+            self._call("probes_read", C.c_int(cap), _capi.ptr(times), _capi.ptr(values),
+                       None if index is None else index.ctypes.data_as(C.POINTER(C.c_int)), C.byref(ring), C.byref(own),
+                       C.byref(n), C.byref(dropped), C.c_int(1 if drain else 0))
+
+        read(0, None, None, None, False)  # the sizes first
+        assert ring.value == len(pts), (ring.value, len(pts))
+        k, m = own.value, n.value
+        cap = max(m, 1)
+        times, values, index = np.zeros((cap, 2)), np.zeros((cap, k, len(_capi.PROBE_FIELDS))), np.zeros(k, dtype=np.int32)
+        read(cap, times, values if k else None, index if k else None, drain)
+        assert (own.value, n.value) == (k, m), (own.value, n.value, k, m)
+        out = _capi.probes_dict(pts[index], times[:m], values[:m], int(dropped.value))
+        out.update(points=pts.copy(), index=index.astype(np.int64))
+        return out
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self.capi.lib().sphx_ctx_destroy(self._h)
@@ -403,6 +442,74 @@ def ring_field_map(engines) -> dict:
     return field_map_means(p.DL, p.DH, **pool_ring_field_map([e.field_part_sums() for e in engines]))
 
 
+def _probe_part_shape(part):
+    """(P, n_owned, n_records) of one rank's part of a ring's probes, whose four fields must be [n_records, n_owned] and whose
+    index must ascend inside range(P)"""
+    pts, idx = np.asarray(part["points"], dtype=np.float64), np.asarray(part["index"])
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"points has shape {pts.shape}, [P, 2] expected")
+    if idx.ndim != 1 or (len(idx) and not np.issubdtype(idx.dtype, np.integer)):
+        raise ValueError("index must be a vector of integers")
+    if len(idx) and (idx[0] < 0 or idx[-1] >= len(pts) or np.any(np.diff(idx) <= 0)):
+        raise ValueError(f"index {idx!r} does not ascend inside range({len(pts)})")
+    n = len(np.asarray(part["step"]))
+    if np.shape(part["t"]) != (n,):
+        raise ValueError(f"t has shape {np.shape(part['t'])}, step has {n} records")
+    for k in _capi.PROBE_FIELDS:
+        if np.shape(part[k]) != (n, len(idx)):
+            raise ValueError(f"field {k} has shape {np.shape(part[k])}, {n} records of {len(idx)} owned probes need {(n, len(idx))}")
+    return len(pts), len(idx), n
+
+
+def _check_owners_partition(counts):
+    """counts [P]: how many ranks own each point of the ring's list"""
+    counts = np.asarray(counts)
+    if np.any(counts != 1):
+        nobody, many = np.flatnonzero(counts == 0), np.flatnonzero(counts > 1)
+        raise ValueError(f"the ranks' indices do not partition range({len(counts)}): points {nobody.tolist()} have no owner, "
+                         f"points {many.tolist()} more than one")
+
+
+def pool_ring_probes(parts) -> dict:
+    """The ring's probes (the dict of capi.Context.probes: points, step, t, the four fields as [n_records, P] arrays,
+    n_dropped) from the ranks' parts (HipSlabEngine.probes_part_records, in rank order): every probe belongs to exactly one
+    slab, which holds its complete series, so the columns are put back at their `index` -- nothing is added, a NaN stays
+    where its owner has it.  ValueError when the indices do not partition range(P), or step, t, n_dropped or points differ
+    between the ranks (a slab without a probe still records the steps)."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("the probes of a ring need the part of at least one slab")
+    shapes = [_probe_part_shape(p) for p in parts]
+    P, _, n = shapes[0]
+    first = parts[0]
+    for r, (p, sh) in enumerate(zip(parts, shapes)):
+        if sh[0] != P or not np.array_equal(np.asarray(p["points"], dtype=np.float64), np.asarray(first["points"], dtype=np.float64)):
+            raise ValueError(f"rank {r} holds other points than rank 0: the slabs of one ring share the list")
+        if sh[2] != n or not np.array_equal(p["step"], first["step"]) or not np.array_equal(p["t"], first["t"]):
+            raise ValueError(f"rank {r} recorded steps {np.asarray(p['step'])!r}, rank 0 {np.asarray(first['step'])!r} (or other "
+                             "times): the slabs of one ring record the same steps")
+        if int(p["n_dropped"]) != int(first["n_dropped"]):
+            raise ValueError(f"rank {r} dropped {p['n_dropped']} records, rank 0 {first['n_dropped']}")
+    counts = np.zeros(P, dtype=np.int64)
+    for p in parts:
+        np.add.at(counts, np.asarray(p["index"], dtype=np.int64), 1)
+    _check_owners_partition(counts)
+    out = dict(points=np.array(first["points"], dtype=np.float64), step=np.asarray(first["step"]).astype(np.int64),
+               t=np.array(first["t"], dtype=np.float64))
+    for k in _capi.PROBE_FIELDS:
+        a = np.empty((n, P))
+        for p in parts:
+            a[:, np.asarray(p["index"], dtype=np.int64)] = np.asarray(p[k], dtype=np.float64).reshape(n, -1)
+        out[k] = a
+    out["n_dropped"] = int(first["n_dropped"])
+    return out
+
+
+def ring_probes(engines, drain=False) -> dict:
+    """The point probes of an in-process ring (pool_ring_probes of every slab's records): what driver.probe_figures takes."""
+    return pool_ring_probes([e.probes_part_records(drain) for e in engines])
+
+
 def _all_gathered(dist, row, group):
     """[world x len(row)] float64: every rank's row (control plane: CPU tensors, gloo)."""
     import torch
@@ -459,6 +566,54 @@ def all_reduce_ring_field_map(part, dist, group=None) -> dict:
     total = _all_reduced(dist, padded, group)
     out = {k: np.ascontiguousarray(total[j]) for j, k in enumerate(FIELD_MAP_PLANES)}
     out.update({k: part[k] for k in _HEAD})
+    return out
+
+
+def all_reduce_ring_probes(part, dist, group=None) -> dict:
+    """One rank per process: the ring's probes from this rank's part, as pool_ring_probes; every rank gets them.  The sizes,
+    n_dropped and whether a rank's own part is well formed are all-gathered and checked first, then the points, step and t;
+    the ranks' owner counts per point are all-reduced and must be 1 everywhere.  Then every rank scatters its owned columns
+    into zeros [4, n_records, P] -- a NaN (the velocities of a void probe) goes as 0 with a 1 in a mask that travels
+    along -- and the arrays are all-reduced: every probe has one contributor and x + 0.0 is x, so the result is the columns
+    at their places, and the mask puts the NaNs back; no NaN is ever summed.  Collective; raises on every rank when a part
+    is malformed, the indices do not partition range(P), or step, t, n_dropped or points differ between the ranks."""
+    try:
+        P, k, n = _probe_part_shape(part)
+        why = None
+    except (ValueError, KeyError, TypeError) as e:
+        P, k, n, why = -1, -1, -1, str(e)
+    rows = _all_gathered(dist, [float(P), float(n), float(part.get("n_dropped", -1)) if why is None else -1.0,
+                                0.0 if why is None else 1.0], group)
+    for r, row in enumerate(rows):
+        if row[3] != 0.0:
+            raise ValueError(f"rank {r}'s part is malformed" + (f": {why}" if why else ""))
+    for r, row in enumerate(rows):
+        if tuple(row[:3]) != tuple(rows[0][:3]):
+            raise ValueError(f"rank {r} holds {int(row[0])} points, {int(row[1])} records, {int(row[2])} dropped; rank 0 "
+                             f"{int(rows[0][0])}, {int(rows[0][1])}, {int(rows[0][2])}: the slabs of one ring share the list and "
+                             "record the same steps")
+    pts = np.asarray(part["points"], dtype=np.float64)
+    step, t = np.asarray(part["step"], dtype=np.float64), np.asarray(part["t"], dtype=np.float64)
+    mine = np.concatenate([pts.ravel(), step, t])
+    for r, row in enumerate(_all_gathered(dist, mine, group)):
+        if not np.array_equal(row, mine):  # (every rank compares with its own: one odd rank out makes all of them raise)
+            raise ValueError(f"rank {r} holds other points, steps or times than this rank")
+    idx = np.asarray(part["index"], dtype=np.int64)
+    counts = np.zeros(P)
+    counts[idx] = 1.0
+    _check_owners_partition(_all_reduced(dist, counts, group).astype(np.int64))
+    F = len(_capi.PROBE_FIELDS)
+    padded = np.zeros((2 * F, n, P))  # the fields, and behind them their NaN masks
+    for j, f in enumerate(_capi.PROBE_FIELDS):
+        a = np.asarray(part[f], dtype=np.float64).reshape(n, k)
+        nan = np.isnan(a)
+        padded[j][:, idx] = np.where(nan, 0.0, a)
+        padded[F + j][:, idx] = nan
+    total = _all_reduced(dist, padded, group)
+    out = dict(points=pts.copy(), step=np.asarray(part["step"]).astype(np.int64), t=t.copy())
+    for j, f in enumerate(_capi.PROBE_FIELDS):
+        out[f] = np.where(total[F + j] > 0.0, np.nan, total[j])
+    out["n_dropped"] = int(part["n_dropped"])
     return out
 
 

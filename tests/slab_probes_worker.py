@@ -1,0 +1,91 @@
+"""Worker for test_slab_probes_host.py (CPU, gloo, WORLD_SIZE ranks): every rank holds the columns of the probes it owns of a
+synthetic ring series with void probes (NaN velocities) in it; slab.all_reduce_ring_probes must leave the whole series on every
+rank, what slab.pool_ring_probes makes of the parts, NaNs exactly where the owner has them, and must raise on EVERY rank when
+one rank's steps, times, n_dropped or points differ or the indices do not partition the points.  Prints OK on every rank that
+saw all of it."""
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FIELDS = ("weight", "u_x", "u_y", "rho")
+
+
+def series(world, P=23, n=5):
+    """(parts, whole): a series of n records at P points, some of them void, dealt out to `world` ranks (rank 1 of three owns
+    nothing); the same on every rank"""
+    rng = np.random.default_rng(31)
+    whole = dict(points=np.column_stack([rng.uniform(0, 3, P), rng.uniform(0, 1, P)]), step=np.arange(2, 2 + 2 * n, 2),
+                 t=np.cumsum(rng.uniform(1e-3, 2e-3, n)), n_dropped=3)
+    for k in FIELDS:
+        whole[k] = rng.normal(1.0, 0.5, (n, P))
+    void = rng.random((n, P)) < 0.15
+    void[:, 4] = True                      # a probe that never has a value
+    whole["u_x"][void] = whole["u_y"][void] = np.nan
+    whole["weight"][void] = whole["rho"][void] = 0.0
+    owner = rng.integers(0, world, P)
+    if world == 3:
+        owner[owner == 1] = 2              # a rank with n_owned = 0
+    parts = []
+    for r in range(world):
+        idx = np.flatnonzero(owner == r)
+        parts.append(dict({k: np.ascontiguousarray(whole[k][:, idx]) for k in FIELDS}, points=whole["points"].copy(), index=idx,
+                          step=whole["step"].copy(), t=whole["t"].copy(), n_dropped=3))
+    return parts, whole
+
+
+def same(a, b):
+    return (np.array_equal(a["points"], b["points"]) and np.array_equal(a["step"], b["step"]) and np.array_equal(a["t"], b["t"])
+            and a["n_dropped"] == b["n_dropped"]
+            and all(a[k].shape == b[k].shape and np.array_equal(a[k], b[k], equal_nan=True) for k in FIELDS))
+
+
+def main():
+    import torch.distributed as dist
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    dist.init_process_group("gloo")
+    slab = importlib.import_module("sph-poiseuille-flow_amd.slab")
+    parts, whole = series(world)
+    ok = True
+
+    got = slab.all_reduce_ring_probes(parts[rank], dist)
+    want = slab.pool_ring_probes(parts)
+    ok &= same(got, want) and same(got, whole)
+    ok &= bool(np.isnan(got["u_x"][:, 4]).all()) and got["step"].dtype == np.int64
+    if world == 3:
+        ok &= len(parts[1]["index"]) == 0
+
+    last = world - 1
+    mine = parts[rank]
+    bads = [dict(step=mine["step"] + 1), dict(t=mine["t"] * 2.0), dict(n_dropped=4), dict(points=mine["points"] + 1e-9),
+            dict(step=mine["step"][:-1], t=mine["t"][:-1], **{k: mine[k][:-1] for k in FIELDS})]   # one record fewer
+    for bad in bads:  # the last rank disagrees: EVERY rank must hear about it
+        try:
+            slab.all_reduce_ring_probes(dict(mine, **(bad if rank == last else {})), dist)
+            ok = False
+        except ValueError:
+            pass
+    # the last rank gives a probe away (a gap), or claims one of rank 0's as well (an overlap)
+    idx = mine["index"]
+    gap = dict(mine, index=idx[1:], **{k: mine[k][:, 1:] for k in FIELDS})
+    extra = np.sort(np.append(idx, parts[0]["index"][0]))
+    overlap = dict(mine, index=extra, **{k: whole[k][:, extra] for k in FIELDS})
+    for bad in (gap, overlap):
+        try:
+            slab.all_reduce_ring_probes(bad if rank == last else mine, dist)
+            ok = False
+        except ValueError:
+            pass
+
+    print(f"rank {rank}: {'OK' if ok else 'WRONG'}", flush=True)
+    dist.barrier()
+    dist.destroy_process_group()
+    sys.exit(0 if ok else 1)
+
+
+if __name__ == "__main__":
+    main()
