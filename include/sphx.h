@@ -45,6 +45,16 @@ const char *sphx_last_error_id(void);
 int sphx_device_count(void);
 int sphx_set_device(int device);
 
+/* Diagnostics of the caching pool all device memory comes from.  The pool hands a freed block to the next request of its size
+ * class as it was returned; results must not depend on what it held.
+ * sphx_pool_stats: out = { cached_bytes, cached_blocks, hits, misses }; a hit is an allocation served from the cache, a miss
+ * one that went to hipMalloc, both counted since process start.  No HIP call: all zeros on a machine without a device.
+ * sphx_pool_scrub: fill every cached free block of the current device with the 32-bit `word`, under the pool's lock, and wait
+ * for the device; *n_blocks (may be NULL) = the blocks filled.  Free blocks are in nobody's use, so nothing else changes.
+ * With nothing cached: 0 blocks and no HIP call.  Must not be called while a stream is capturing. */
+int sphx_pool_stats(uint64_t out[4]);
+int sphx_pool_scrub(uint32_t word, uint64_t *n_blocks);
+
 /* ------------------------------------------------------------------------------------------------
  * 1. Stateless MEX-surface entry points (one per gateway call).  Host arrays in, host arrays out;
  *    the work runs in HIP kernels on the current device.

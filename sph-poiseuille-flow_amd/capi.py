@@ -73,6 +73,7 @@ class SphxStatus(C.Structure):
 
 EXPORTS = [
     "sphx_version", "sphx_last_error", "sphx_last_error_id", "sphx_device_count", "sphx_set_device",
+    "sphx_pool_stats", "sphx_pool_scrub",
     "sphx_neighbor_search", "sphx_neighbor_fetch", "sphx_density_correction", "sphx_viscous_force",
     "sphx_transport_correction", "sphx_integration_1st", "sphx_integration_2nd",
     "sphx_integration_verlet", "sphx_advance_shell_step", "sphx_wall_shear_monitor",
@@ -145,6 +146,23 @@ def device_count() -> int:
 
 def set_device(dev: int) -> None:
     check(lib().sphx_set_device(C.c_int(dev)))
+
+
+def pool_stats() -> dict:
+    """The device-memory pool's counters: cached_bytes, cached_blocks, and the allocations served from the cache (hits) and by
+    hipMalloc (misses) since process start.  No device needed: all zeros without one."""
+    out = (C.c_uint64 * 4)()
+    check(lib().sphx_pool_stats(out))
+    return dict(zip(("cached_bytes", "cached_blocks", "hits", "misses"), (int(v) for v in out)))
+
+
+def pool_scrub(word) -> int:
+    """Fill every cached free block of the current device with the 32-bit word; -> the number of blocks filled (0, and no
+    device call, with nothing cached).  A diagnostic: results must not depend on what a recycled block held.  Not while a
+    stream is capturing."""
+    n = C.c_uint64(0)
+    check(lib().sphx_pool_scrub(C.c_uint32(int(word)), C.byref(n)))
+    return int(n.value)
 
 
 def make_params(prm, t_end=None, transport_coeff=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,

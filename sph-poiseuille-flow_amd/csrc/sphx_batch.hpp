@@ -181,7 +181,11 @@ void batch_run(sphx_batch *b, double t_target, std::vector<int64_t> budget)
             const double goal = std::min(t_target, k.t_end);
             if (budget[m] == 0 || !(k.t < goal - 1e-12)) continue;
             const double dt_est = host_dt_unclipped(c, k.vmax);
-            want = std::max<int64_t>(want, (int64_t)std::ceil(std::max(0.0, goal - k.t) / std::max(dt_est, 1e-12)) + 1);
+            // A non-finite max |v| (a NaN or Inf in the state as given) makes the estimate NaN or absurd, and its conversion
+            // to an integer left `want` at 0: a batch whose every member was non-finite took no step and raised nothing.
+            // Such a member asks for one slot; arming its clock raises SPHX_ERR_DIVERGED on the device (prepare_clock).
+            const double n_est = std::ceil(std::max(0.0, goal - k.t) / std::max(dt_est, 1e-12));
+            want = std::max<int64_t>(want, std::isfinite(k.vmax) && n_est < 9e18 ? (int64_t)n_est + 1 : 1);
             if (budget[m] < 0) limited = false;
             else most = std::max(most, budget[m]);
         }

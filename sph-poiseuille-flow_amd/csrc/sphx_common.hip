@@ -47,6 +47,7 @@ struct Pool {
     std::multimap<std::pair<int, size_t>, void *> free_blocks;  // (device, class) -> block
     std::unordered_map<void *, int> owner;                      // block -> the device it was allocated on
     size_t cached = 0;
+    uint64_t hits = 0, misses = 0;  // pool_alloc calls served from the cache / sent to hipMalloc, since process start
     static constexpr size_t kMaxCached = (size_t)4 << 30;
     void trim()
     {
@@ -78,8 +79,10 @@ void *pool_alloc(size_t bytes)
             void *p = it->second;
             P.free_blocks.erase(it);
             P.cached -= cls;
+            ++P.hits;
             return p;
         }
+        ++P.misses;
     }
     void *p = nullptr;
     hipError_t e = hipMalloc(&p, cls);
@@ -116,6 +119,32 @@ void pool_free(void *p, size_t bytes)
     P.cached += cls;
 }
 
+void pool_stats(uint64_t out[4])
+{
+    Pool &P = pool();
+    std::lock_guard<std::mutex> lk(P.m);
+    out[0] = P.cached;
+    out[1] = P.free_blocks.size();
+    out[2] = P.hits;
+    out[3] = P.misses;
+}
+
+uint64_t pool_scrub(uint32_t word)
+{
+    Pool &P = pool();
+    std::lock_guard<std::mutex> lk(P.m);
+    if (P.free_blocks.empty()) return 0;  // nothing cached: no HIP call at all
+    int dev = 0;
+    SPHX_HIP(hipGetDevice(&dev));
+    uint64_t n = 0;
+    // a free block is nobody's (whoever returned it had synchronised its work): the fill races with nothing, and it ends
+    // before the lock is released, so no pool_alloc can hand out a block that is still being filled
+    for (auto it = P.free_blocks.lower_bound({dev, 0}); it != P.free_blocks.end() && it->first.first == dev; ++it, ++n)
+        SPHX_HIP(hipMemsetD32Async((hipDeviceptr_t)it->second, (int)word, it->first.second / sizeof(uint32_t), nullptr));
+    if (n) SPHX_HIP(hipDeviceSynchronize());
+    return n;
+}
+
 void ensure_device()
 {
     int n = 0;
@@ -148,6 +177,24 @@ SPHX_EXPORT int sphx_set_device(int device)
     SPHX_TRY
     sphx::ensure_device();
     SPHX_HIP(hipSetDevice(device));
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_pool_stats(uint64_t out[4])
+{
+    SPHX_TRY
+    sphx::require(out != nullptr, "SPHX:Pool:args", "sphx_pool_stats: out must not be NULL");
+    sphx::pool_stats(out);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_pool_scrub(uint32_t word, uint64_t *n_blocks)
+{
+    SPHX_TRY
+    const uint64_t n = sphx::pool_scrub(word);
+    if (n_blocks) *n_blocks = n;
     return SPHX_OK;
     SPHX_CATCH
 }

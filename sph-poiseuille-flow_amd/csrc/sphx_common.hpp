@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <stdexcept>
@@ -48,6 +49,14 @@ void ensure_device();
 // (every owner here does: the stateless calls before their scope ends, contexts before they are destroyed).
 void *pool_alloc(size_t bytes);
 void pool_free(void *p, size_t bytes);
+// Diagnostics (sphx_pool_stats / sphx_pool_scrub, include/sphx.h).  A block comes back from the pool as it was returned:
+// nothing clears it, so whoever takes one must write every element before it reads or returns it -- results must not depend
+// on what a block held before (tests/test_gpu_pool_history.py holds the library to that).  pool_stats: cached bytes, cached
+// blocks, and the pool_alloc calls served from the cache (hits) and by hipMalloc (misses) since process start; no HIP call.
+// pool_scrub: fills every cached free block of the current device with `word` under the pool's lock, waits for the device
+// and returns the number of blocks filled; the allocation path is untouched.  Not while a stream is capturing.
+void pool_stats(uint64_t out[4]);
+uint64_t pool_scrub(uint32_t word);
 
 template <typename T>
 class DevBuf {

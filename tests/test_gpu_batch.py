@@ -196,6 +196,21 @@ def test_diverging_member_is_named(cfgmod, geom, capi):
     assert "member 2" in e.value.message
 
 
+def test_batch_of_only_diverging_members_raises(cfgmod, geom, capi):
+    """A NaN in EVERY member: the host's step estimate has no finite max |v| to go by.  It used to come out as zero slots --
+    advance() took no step and raised nothing.  Now one slot is enqueued and arming the clocks raises the status."""
+    members = batch_members(cfgmod, geom, 0.05, 1.5, VARIANTS[:3], jitter=0.1)
+    for m, (prm, parts) in enumerate(members):
+        bad = dict(parts, vel=parts["vel"].copy(order="F"))
+        bad["vel"][3, 0] = np.nan
+        members[m] = (prm, bad)
+    with capi.Batch.from_parts(*zip(*members), t_end=1e9) as b:
+        with pytest.raises(capi.SphxError) as e:
+            b.advance(1e9, max_steps=4)
+    assert e.value.code == capi.SPHX_ERR_DIVERGED
+    assert "member 0" in e.value.message
+
+
 def test_run_batch_matches_run(cfgmod, geom, driver):
     prms = [cfgmod.params_from_values(dp=0.025, DL=1.5, mu=mu, end_time=0.004, output_interval=0.002)
             for mu in (0.1, 0.15, 0.2)]

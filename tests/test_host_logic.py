@@ -151,6 +151,22 @@ def test_no_device_means_loud_failure_not_cpu_fallback(capi, mex, cfgmod, geom):
     assert e2.value.code == capi.SPHX_ERR_DEVICE
 
 
+def test_pool_diagnostics_need_no_device(capi):
+    """sphx_pool_stats touches no HIP call and sphx_pool_scrub none while nothing is cached: without a device the counters are
+    all zero and a scrub fills 0 blocks and raises nothing.  With a device (and whatever this process has cached by now) the
+    counters are consistent and a scrub fills no more blocks than are cached."""
+    before = capi.pool_stats()
+    assert list(before) == ["cached_bytes", "cached_blocks", "hits", "misses"]
+    assert all(isinstance(v, int) and v >= 0 for v in before.values())
+    n = capi.pool_scrub(3)
+    after = capi.pool_stats()
+    if capi.device_count() == 0:
+        assert before == dict(cached_bytes=0, cached_blocks=0, hits=0, misses=0)
+        assert n == 0
+    assert 0 <= n <= before["cached_blocks"] and (before["cached_blocks"] == 0) == (before["cached_bytes"] == 0)
+    assert after == before  # a scrub takes nothing from the pool and gives nothing back
+
+
 def test_product_path_never_imports_the_oracle():
     pk = os.path.join(ROOT, "sph-poiseuille-flow_amd")
     for dirpath, _, files in os.walk(pk):
