@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "sphx_device.hpp"
+#include "sphx_xcd_block.hpp"
 
 namespace sphx {
 
@@ -246,15 +247,13 @@ __device__ __forceinline__ double min_image(const Grid &g, double dx)
     return dx;
 }
 
-// Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2).  Give each XCD one
-// contiguous eighth of the particle range instead, so the neighbour columns a block reads are the ones
-// the previous block on the same XCD just pulled into that XCD's L2 (measured at 6 M particles without
-// this: k_forces fetched 4x its algorithmic bytes from HBM, L2 hit rate 36 %).  Speed only.
-__device__ __forceinline__ int xcd_block(int b, int nb)
-{
-    const int per = nb >> 3;
-    return b < (per << 3) ? (b & 7) * per + (b >> 3) : b;
-}
+// (xcd_block(first, j, nb), which block of a pass a workgroup takes: sphx_xcd_block.hpp)
+// A workgroup of a pass: its index j among the pass's workgroups, and the physical block the pass starts at
+struct PassWg {
+    int j, first;
+    __host__ __device__ PassWg(int j, int first = 0) : j(j), first(first) {}
+};
+__device__ __forceinline__ int xcd_block(PassWg b, int nb) { return xcd_block(b.first, b.j, nb); }
 
 // A period of one or two cell columns (DL < 6h): the columns cx-1, cx, cx+1 are not distinct -- the reference meets the
 // same particle as a real and as a ghost entry there and de-duplicates with seen_neighbor
@@ -715,12 +714,13 @@ __device__ __forceinline__ void store_density(const Phys &ph, const FluidTmp &t,
 
 // MODE 0: sweep the cells, write the step's list.  MODE 1: same sweep, also write the superset list.
 // MODE 2: walk the superset list instead of the cells.
-// bid / nblk: the workgroup's index among the nblk workgroups of this pass (the fused launch k_continuity_density runs the
-// pass in a sub-range of its grid).  half: also write the half-step density / pressure (needs the step's dt; the fused
-// launch runs pass A of the NEXT step, whose dt is not known yet -- pass B completes the record there).
+// bid / nblk: the workgroup's index among the nblk workgroups of this pass, and where the pass starts in the grid (the fused
+// launch k_continuity_density runs the pass in a sub-range of its grid; PassWg).  half: also write the half-step density /
+// pressure (needs the step's dt; the fused launch runs pass A of the NEXT step, whose dt is not known yet -- pass B completes
+// the record there).
 template <int LPP, int MODE>
 __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
-                                             const FluidTmp &t, const Walls &w, int bid, int nblk, bool half)
+                                             const FluidTmp &t, const Walls &w, PassWg bid, int nblk, bool half)
 {
     SPHX_PASS_INDEX_AT(bid, nblk);
     // the walk at 16 / 32 lanes: row count, first rows and the clock's words leave first (leading arguments, see ListHead)
@@ -1554,7 +1554,7 @@ __host__ __device__ constexpr int tile_slots(int lpp) { return lpp >= 8 ? 192 : 
 // (CODED: both lists hold slot-coded entries, see kSlotCodes -- the walk copies them as they stand)
 template <int LPP, int TILE = 0, bool CODED = false>
 __device__ __forceinline__ void density_walk_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
-                                                  const FluidTmp &t, const Walls &w, int bid, int nblk, bool half,
+                                                  const FluidTmp &t, const Walls &w, PassWg bid, int nblk, bool half,
                                                   double2 *c_pos = nullptr)
 {
     static_assert(!CODED || TILE == kSlotCodes, "slot-coded lists: the walk stages the whole layout");
@@ -2494,7 +2494,7 @@ struct HistWindow {
 };
 template <int LPP, bool WALK, int TILE, bool CODED = false, bool REBIN = false>
 __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
-                                                const FluidTmp &t, const Walls &w, int do_hist, int tail, int bid, int nb,
+                                                const FluidTmp &t, const Walls &w, int do_hist, int tail, PassWg bid, int nb,
                                                 double2 *c_pos, double2 *c_vel, double *c_vol, int next_half = 0,
                                                 const FluidSet &d = FluidSet{})
 {
@@ -2581,7 +2581,7 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
     };
     if (!WALK) publish_vmax();
     __shared__ int r_start[REBIN ? kFoldCells + 1 : 1], r_wave[REBIN ? kBlock / 64 + 1 : 1];
-    if (REBIN) fold_scan<LPP>(fold, g, s, t, d, bid, sub, r_start, r_wave);
+    if (REBIN) fold_scan<LPP>(fold, g, s, t, d, bid.j, sub, r_start, r_wave);
     if (WALK) {
         const int rows = active ? nn_all : 0, rows_fl = active ? list_fluid_rows(packed) : 0;
         struct Nb {  // what the pass reads of a fluid neighbour
@@ -2754,6 +2754,11 @@ __global__ __launch_bounds__(kBlock) void k_continuity_rebin(Clock *clk, int q, 
 // on the new state s_next, walking the superset list, into the other list / record buffers (t_next) -- without the
 // half-step density and pressure, which need the next step's dt (the tail workgroup of this very launch computes it):
 // pass B of the next step closes that (k_kgc, finish_half); workgroup 2 nb: the clock (continuity_tail).
+// The A half starts at physical block nb and numbers its blocks from there (xcd_block): its lists and records are stored
+// by the XCD that reads them in passes B, CD and E.  kFusedUnaligned (SPHX_DEBUG_SWITCHES=no_xcd_align, a bit of the launch's
+// flag word above the tail's codes) numbers it as if it began at block 0, as it did before.
+constexpr int kFusedTail = 1, kFusedUnaligned = 4;
+__device__ __forceinline__ int fused_first_a(int flags, int nb) { return flags & kFusedUnaligned ? 0 : nb; }
 template <int LPP>
 __global__ __launch_bounds__(kBlock) void k_continuity_density(Clock *clk, int q, int shape, int *e_cnt, int *e_idx, int *a_cnt,
                                                                int *a_idx, int e_stride, int a_stride, Grid g, Phys ph, FluidSet s,
@@ -2763,14 +2768,14 @@ __global__ __launch_bounds__(kBlock) void k_continuity_density(Clock *clk, int q
     //  the two strides side by side: an int in front of a pointer costs a dword of padding, and the last one would miss the preload)
     t.nl_cnt = e_cnt; t.nl_idx = e_idx; t.nl_stride = e_stride;
     t_next.sl_cnt = a_cnt; t_next.sl_idx = a_idx; t_next.nl_stride = a_stride;
-    const int nb = shape_blocks(shape), with_tail = shape_flag(shape);  // (with_tail = 0: kernel timing, the clock must not advance)
+    const int nb = shape_blocks(shape), with_tail = shape_flag(shape) & kFusedTail;  // (with_tail = 0: kernel timing, the clock must not advance)
     const int b = (int)blockIdx.x;
     if (with_tail && b == 2 * nb) {
         continuity_tail(clk, q, ph, t, nb);
         return;
     }
     if (b < nb) continuity_body<LPP, false, 0>(clk, q, g, ph, s, t, w, 0, with_tail, b, nb, nullptr, nullptr, nullptr);
-    else density_body<LPP, 2>(clk, q, g, ph, s_next, t_next, w, b - nb, nb, false);
+    else density_body<LPP, 2>(clk, q, g, ph, s_next, t_next, w, PassWg(b - nb, fused_first_a(shape_flag(shape), nb)), nb, false);
 }
 
 // Batches (Members): pass E of the compact kernels (the tail workgroup of member m is workgroup nb of row m: it waits for the
@@ -2811,8 +2816,9 @@ __global__ __launch_bounds__(kBlock) void k_continuity_density_b(Members mb, int
 // the same with the large-channel forms of the two passes (mid-size channels: 4-8 lanes per particle, clock in the tail)
 template <int LPP>
 __global__ __launch_bounds__(kBlock) void k_continuity_density_w(Clock *clk, int q, Grid g, Phys ph, FluidSet s, FluidTmp t,
-                                                                 Walls w, FluidSet s_next, FluidTmp t_next, int with_tail)
+                                                                 Walls w, FluidSet s_next, FluidTmp t_next, int tail_flags)
 {
+    const int with_tail = tail_flags & kFusedTail;
     const int nb = ((int)gridDim.x - with_tail) / 2;  // (with_tail = 0: kernel timing, the clock must not advance)
     const int b = (int)blockIdx.x;
     if (with_tail && b == 2 * nb) {
@@ -2820,7 +2826,7 @@ __global__ __launch_bounds__(kBlock) void k_continuity_density_w(Clock *clk, int
         return;
     }
     if (b < nb) continuity_body<LPP, true, 0>(clk, q, g, ph, s, t, w, 0, with_tail, b, nb, nullptr, nullptr, nullptr);
-    else density_walk_body<LPP>(clk, q, g, ph, s_next, t_next, w, b - nb, nb, false);
+    else density_walk_body<LPP>(clk, q, g, ph, s_next, t_next, w, PassWg(b - nb, fused_first_a(tail_flags, nb)), nb, false);
 }
 
 // standalone cell histogram (context creation, wall grid, slab steps): same binning as pass E

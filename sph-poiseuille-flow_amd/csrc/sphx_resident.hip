@@ -302,15 +302,18 @@ struct sphx_ctx {
 namespace {
 
 // A/B switches for measurements, all behind ONE environment variable read once per process:
-//   SPHX_DEBUG_SWITCHES=no_tail_clock,no_fuse_ea,no_fold_rebin,no_lds_tiles,no_coded_lists,no_lazy_out,forces_tile_320,log
+//   SPHX_DEBUG_SWITCHES=no_tail_clock,no_fuse_ea,no_fold_rebin,no_lds_tiles,no_coded_lists,no_lazy_out,no_xcd_align,forces_tile_320,log
 // (no_tail_clock: the clock update as a launch of its own on every step; no_fuse_ea: passes E and A in separate launches;
 //  no_fold_rebin: small channels re-bin with the chain k_clock_scan -> k_scatter -> k_reorder behind pass E;
 //  no_lds_tiles: large-channel passes gather from global memory; no_coded_lists: index differences in every list, never tile
-//  slots; no_lazy_out: force, force_prior, rho, p written by every step (FluidTmp::lazy_out); log: forced re-binnings and timer
+//  slots; no_lazy_out: force, force_prior, rho, p written by every step (FluidTmp::lazy_out); no_xcd_align: the A half of the
+//  fused launch, which starts at physical block nb, numbers its blocks as if it started at block 0 (xcd_block, sphx_xcd_block.hpp);
+//  log: forced re-binnings and timer
 //  problems on stderr)
 struct DebugSwitches {
     bool no_fold_rebin = false;
     bool no_tail_clock = false, no_fuse_ea = false, no_lds_tiles = false, no_coded_lists = false, no_lazy_out = false, log = false;
+    bool no_xcd_align = false;
     bool no_slab_overlap = false;  // skinned slabs: the local maxima from pass E's tail workgroup, the all-reduce on the step's only stream (round 3)
     bool full_copyback = false;  // dynamic contexts: the in-place re-binning copies the whole layout back (round 3)
     int tail_limit = 0;  // > 0: largest pass (in workgroups) whose clock update rides in pass E's tail workgroup
@@ -330,6 +333,7 @@ const DebugSwitches &debug_switches()
         d.no_lds_tiles = has("no_lds_tiles");
         d.no_coded_lists = has("no_coded_lists");
         d.no_lazy_out = has("no_lazy_out");
+        d.no_xcd_align = has("no_xcd_align");
         d.log = has("log");
         d.no_slab_overlap = has("no_slab_overlap");
         d.full_copyback = has("full_copyback");
@@ -753,13 +757,14 @@ void launch_fold_rebin(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t,
 void launch_fused_ea(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &sn, const FluidTmp &tn, Tail tail = Tail::Clock)
 {
     const unsigned blocks = 2 * c->n_blocks_particles + (int)tail;
+    const int flags = (int)tail | (debug_switches().no_xcd_align ? kFusedUnaligned : 0);  // (the batch form numbers as before)
     with_lpp(c, [&](auto lpp) {  // 16 / 32 lanes per particle: the compact kernels; fewer: their large-channel forms
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16)
             launch_pass_hot(c, "k_continuity_density", Forms{k_continuity_density<LPP>, k_continuity_density_b<LPP>}, blocks, q,
-                            hot_fused(c->n_blocks_particles, (int)tail, t, tn), s, t, sn, tn, batch_only((int)tail));
+                            hot_fused(c->n_blocks_particles, flags, t, tn), s, t, sn, tn, batch_only((int)tail));
         else if constexpr (LPP >= 2)
-            launch_pass(c, "k_continuity_density", k_continuity_density_w<LPP>, blocks, q, s, t, sn, tn, (int)tail);
+            launch_pass(c, "k_continuity_density", k_continuity_density_w<LPP>, blocks, q, s, t, sn, tn, flags);
         else
             throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fuse", "internal: fused E|A launch at this lane count");
     });

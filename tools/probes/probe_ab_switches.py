@@ -24,14 +24,19 @@ for rep in range(reps):
         env = dict(os.environ, SPHX_DEBUG_SWITCHES=sw)
         if lib:
             env["SPHX_LIB"] = os.path.join(root, lib)
-        p = subprocess.run([sys.executable, "-c", src], env=env, capture_output=True, text=True)
+        try:
+            p = subprocess.run([sys.executable, "-c", src], env=env, capture_output=True, text=True, timeout=600)
+        except subprocess.TimeoutExpired as e:
+            sys.exit(f"[{v or 'default'}] time limit; nothing more is started\n{(e.stderr or b'')[-1500:]}")
+        if p.returncode < 0 or p.returncode in (124, 134, 137, 139):  # ended by a signal: the GPU may be in a bad state
+            sys.exit(f"[{v or 'default'}] exit code {p.returncode}; nothing more is started\n{p.stderr[-1500:]}")
         try:
             r = json.loads(p.stdout.strip().splitlines()[-1])
         except Exception:
             print(f"[{v or 'default'}] FAILED", p.stdout[-500:], p.stderr[-1500:], flush=True)
             continue
         sus = r["sustained"]
-        print(f"[{v or 'default':40s}] {wl} window {1e3 * r['ms_per_step']:8.1f} us/step" +
+        print(f"[{v or 'default':40s}] {wl} window {1e3 * r['ms_per_step']:8.2f} us/step" +
               (f"  sustained {1e3 * sus['ms_per_step']:8.1f} us/step, drift-triggered re-binnings {sus['forced_rebuilds']}" if sus else "") +
               (f"  forced {r['tuning'].get('forced_rebuilds')}" if not sus else "") +
               ("  " + str({a: round(1e3 * b, 1) for a, b in r["kernels_ms"].items()}) if prof else ""), flush=True)
