@@ -672,7 +672,98 @@ int sphx_batch_probes_read(sphx_batch *batch, int capacity, double *times, doubl
                            int64_t *n_dropped, int drain);
 
 /* ------------------------------------------------------------------------------------------------
- * 3. x-slab contexts (multi-GPU).  The channel is cut into n_ranks slabs of whole cell columns; each
+ * 2j. Profile series: the binned velocity profile at every sampled step, recorded on the device, inside the step loop.
+ *     "Flow statistics (section 2a) that record instead of accumulate": the statistics and the field map (2e) average time
+ *     away, the step history (2d) and the point probes (2h) have no y-profile.  The series is what shows a profile DEVELOP
+ *     -- the start-up of plane Poiseuille flow from rest, whose series solution is known in closed form
+ *     (profile.poiseuille_startup) -- without a download and a host binning per sample.
+ *
+ *  One sample: exactly the flow statistics' sample of section 2a -- the same bins (n_bins = 0: the reference's), band 0 the
+ *    whole channel plus up to two x-bands, and per bin and band the five values N, sum u_x, sum u_x^2, sum u_y, sum u_y^2 of
+ *    THAT step, summed exactly in int64 fixed point.  Only pos / vel are sampled.
+ *  Records: one per sampled step: `step` and `t` (two doubles: sphx_status.step and .t after the step) in
+ *    times[capacity][2], and the sample in records[capacity][n_bands + 1][n_bins][SPHX_PROFILE_SERIES_FIELDS].  `capacity`
+ *    records live in device memory and are filled in step order; when the buffer is full further records are dropped and
+ *    counted in n_dropped; it does not wrap (the semantics of sections 2d / 2h).  A record is (n_bands + 1) * n_bins * 5
+ *    doubles: at dp = 0.025 with two bands 3.2 KB, not the 64 B of a history record -- size `capacity` accordingly (the
+ *    wrappers default to 4 096, not the history's 65 536).  Cap: capacity * (n_bands + 1) * n_bins * 5 <= 1 << 27 doubles
+ *    (1 GiB), over all members of a batch.
+ *  Gating: as in section 2a: a step is recorded when its step count (sphx_status.step after it) is a multiple of `every` and
+ *    it ends at t >= t_from.  Dual-rate contexts record once per outer step.  A step slot that did not run records nothing.
+ *    sphx_ctx_profile_series_sample appends a record of the state now, without gating.
+ *  Determinism: a sample is summed exactly and every value of a record is converted from its integer by one thread: two
+ *    identical runs give bit-identical records, independent of particle order, re-binning and host chunking, and adding the
+ *    records of a series in order gives the sums of section 2a (same config) to the bit.  A velocity above the bound of
+ *    section 2a (a non-finite state) makes a later read fail with SPHX:ProfileSeries:range.
+ *  Off by default.  With it off a step slot enqueues exactly the launches it does without this feature; on, every step slot
+ *    ends with one more launch (k_profile_series, behind k_point_probes; it skips itself on the steps gated out) that is
+ *    captured in the replayed graphs; enable / disable re-capture them.  Independent of the other four samplers.
+ *  Errors: SPHX:ProfileSeries:config (NULL config, n_bins < 0, every < 1, capacity < 1, a NaN t_from, n_bands outside
+ *    0..2, a band centre or half-width that is not finite or a negative half-width, n_bins * (n_bands + 1) > 1536, the cap on
+ *    the record buffer, or the allocation fails: the context then goes on without a series), SPHX:ProfileSeries:disabled
+ *    (SPHX_ERR_STATE: a call that needs the series while it is off), SPHX:ProfileSeries:range (SPHX_ERR_STATE),
+ *    SPHX:ProfileSeries:capacity (the caller's arrays are smaller than n_records); every call on a slab context fails with
+ *    SPHX_ERR_ARG, SPHX:ProfileSeries:slab (slab rings have no profile series).  A refused enable leaves a running series,
+ *    and its records, untouched.
+ * ---------------------------------------------------------------------------------------------- */
+
+#define SPHX_PROFILE_SERIES_FIELDS 5
+
+typedef struct sphx_profile_series_config {
+    int32_t n_bins;            /* 0 = max(20, floor(DH/dp + 0.5)), the reference's profile bins;
+                                  n_bins * (n_bands + 1) <= 1536                                          */
+    int32_t every;             /* record every `every`-th completed step (step count % every == 0), >= 1 */
+    int32_t capacity;          /* records the device buffer holds, >= 1                                  */
+    double t_from;             /* only steps ending at t >= t_from                                       */
+    int32_t n_bands;           /* 0..2 x-bands besides the whole channel                                 */
+    double band_x[2], band_hw[2];
+} sphx_profile_series_config;
+
+/* (Re)configure and empty the buffer; waits for the stream.  Off by default. */
+int sphx_ctx_profile_series_enable(sphx_ctx *ctx, const sphx_profile_series_config *cfg);
+/* Stop recording (no-op when off); the records are dropped. */
+int sphx_ctx_profile_series_disable(sphx_ctx *ctx);
+/* Append one record of the current state (what sphx_ctx_download would return) now, without gating. */
+int sphx_ctx_profile_series_sample(sphx_ctx *ctx);
+/* The records so far, in step order: times [capacity][2] and records [capacity][*n_bands][*n_bins][5], row-major, where
+ * *n_bands counts band 0 (times / records NULL: that array is not copied; both NULL: only the shape and the counts are
+ * reported and capacity is not checked).  Waits for and settles everything enqueued, like sphx_ctx_download.  drain != 0:
+ * the buffer is emptied and n_dropped zeroed after copying. */
+int sphx_ctx_profile_series_read(sphx_ctx *ctx, int capacity, double *times, double *records, int *n_bins, int *n_bands,
+                                 int *n_records, int64_t *n_dropped, int drain);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2k. Profile series of a batch (section 2b): the series of section 2j for every member at once.
+ *
+ *  One config for all members (bins and bands come from the shared geometry); `capacity` is per member.  Every member has
+ *  its own record buffer, n_records, n_dropped and range flag, and is recorded on its own clock with the gating of section
+ *  2j, so a member that sits out slots records nothing in them and its counters are not touched.  A member's records are
+ *  bit for bit those of a standalone context with the same parameters and config that took the same steps; realignments
+ *  move particles only and change no record.  With the series on, every step slot of the batch ends with one recording
+ *  launch for all members (k_profile_series_b, behind the batch's other samplers); off, a slot enqueues exactly the
+ *  launches it does without this feature.  Enable / disable wait for the stream and re-capture the batch's graphs.
+ *  Memory: n_members * capacity * (2 + (n_bands + 1) * n_bins * 5) doubles; n_members * capacity * (n_bands + 1) * n_bins * 5
+ *  must not exceed 1 << 27 doubles.  A refused enable leaves a running series, and its records, untouched.
+ *  Errors: SPHX:Batch:null (NULL batch), SPHX:ProfileSeries:config (as in section 2j, with the total over the members),
+ *  SPHX:ProfileSeries:disabled, SPHX:ProfileSeries:capacity (the caller's capacity is below the largest n_records of any
+ *  member); SPHX:ProfileSeries:range names the member whose flag is set.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* (Re)configure and empty every member's buffer; waits for the stream. */
+int sphx_batch_profile_series_enable(sphx_batch *batch, const sphx_profile_series_config *cfg);
+/* Stop recording (no-op when off); the records are dropped. */
+int sphx_batch_profile_series_disable(sphx_batch *batch);
+/* settles; appends a record of what sphx_batch_download returns, every member, without gating */
+int sphx_batch_profile_series_sample(sphx_batch *batch);
+/* One call for all members.  times is [n_members][capacity][2] and records [n_members][capacity][*n_bands][*n_bins][5],
+ * row-major: member m's block lies behind member m - 1's, its records fill rows 0 .. n_records[m] - 1 and the other rows are
+ * left as they are.  n_records and n_dropped are [n_members]; any pointer may be NULL.  Settles first, as
+ * sphx_batch_download does.  drain != 0: every member's buffer is emptied and its n_dropped zeroed after copying. */
+int sphx_batch_profile_series_read(sphx_batch *batch, int capacity, double *times, double *records, int *n_bins, int *n_bands,
+                                   int *n_records, int64_t *n_dropped, int drain);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3. x-slab contexts (multi-GPU). The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is
  *        sphx_slab_compute -> {exchange two messages with the ring neighbours, all-reduce max|v|}

@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from .profile import FIELD_MAP_PLANES, field_map_means, flow_stats_profile
+from .profile import FIELD_MAP_PLANES, STATS_FIELDS, field_map_means, flow_stats_profile, profile_series_profiles
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPHX_LIB") or os.path.join(HERE, "csrc", "libsphx.so")  # SPHX_LIB: experiment builds
@@ -63,6 +63,11 @@ PROBE_FIELDS = ("weight", "u_x", "u_y", "rho")
 PROBE_MAX_POINTS = 4096
 
 
+class SphxProfileSeriesConfig(C.Structure):
+    _fields_ = [("n_bins", C.c_int32), ("every", C.c_int32), ("capacity", C.c_int32), ("t_from", C.c_double),
+                ("n_bands", C.c_int32), ("band_x", C.c_double * 2), ("band_hw", C.c_double * 2)]
+
+
 class SphxStatus(C.Structure):
     _fields_ = [("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("vmax", C.c_double),
                 ("step", C.c_int64), ("done", C.c_int32), ("device_status", C.c_int32)]
@@ -87,6 +92,8 @@ EXPORTS = [
     "sphx_ctx_field_map_enable", "sphx_ctx_field_map_disable", "sphx_ctx_field_map_reset", "sphx_ctx_field_map_sample",
     "sphx_ctx_field_map_read",
     "sphx_ctx_probes_enable", "sphx_ctx_probes_disable", "sphx_ctx_probes_sample", "sphx_ctx_probes_read",
+    "sphx_ctx_profile_series_enable", "sphx_ctx_profile_series_disable", "sphx_ctx_profile_series_sample",
+    "sphx_ctx_profile_series_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -102,6 +109,8 @@ EXPORTS = [
     "sphx_batch_field_map_enable", "sphx_batch_field_map_disable", "sphx_batch_field_map_reset", "sphx_batch_field_map_sample",
     "sphx_batch_field_map_read",
     "sphx_batch_probes_enable", "sphx_batch_probes_disable", "sphx_batch_probes_sample", "sphx_batch_probes_read",
+    "sphx_batch_profile_series_enable", "sphx_batch_profile_series_disable", "sphx_batch_profile_series_sample",
+    "sphx_batch_profile_series_read",
 ]
 
 _LIB = None
@@ -455,6 +464,60 @@ class _Stepped(_Sampled):
         assert np.array_equal(n, want), (n, want)
         return self._each([probes_dict(pts, times[k, :n[k]], values[k, :n[k]], int(dropped[k])) for k in range(m)])
 
+    # ---- profile series (include/sphx.h sections 2j, 2k): the binned velocity profile, one record per sampled step ----
+    def profile_series_enable(self, n_bins=0, every=1, capacity=4096, t_from=0.0, bands=()):
+        """Record the flow statistics' sample of the state -- n_bins y-bins (0: the reference's max(20, round(DH/dp))) of the
+        whole channel (band 0) and of up to two x-bands [(x_centre, half_width), ...] -- every `every`-th completed step ending
+        at t >= t_from into a device buffer of `capacity` records ((re)configures and empties it).  Records that find the
+        buffer full are dropped and counted.  A record is n_bands * n_bins * 5 doubles.  A batch: one config for all members,
+        `capacity` records per member, each recorded on its own clock."""
+        p0 = self._params0()
+        cfg = profile_series_config(p0, n_bins, every, capacity, t_from, bands, n_members=self._channels())
+        self._call("profile_series_enable", C.byref(cfg))
+        # (n_bins, n_bands incl. band 0) while the profile series is on
+        self._profile_series = (int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5))), int(cfg.n_bands) + 1)
+
+    def profile_series_disable(self):
+        self._call("profile_series_disable")
+        self._profile_series = None
+
+    def _series_on(self):
+        return _enabled(self._profile_series, "ProfileSeries", f"the profile series is not enabled on this {self._where}")
+
+    def profile_series_sample(self):
+        """Append one record of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
+        self._series_on()
+        self._call("profile_series_sample")
+
+    def profile_series_sums(self, drain=False):
+        """The raw series so far: step (int64) and t [n], the five STATS_FIELDS (count, sum_ux, sum_ux2, sum_uy, sum_uy2 of
+        each sampled step) as [n, n_bands, n_bins] arrays, n_dropped and the bin centres y_mid; drain empties the buffer
+        after the copy.  A batch: one such dict per member, from one read of all members."""
+        n_bins, n_bands = self._series_on()
+        m = self._channels()
+        n, dropped = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
+        nb, nbd = C.c_int(0), C.c_int(0)
+
+        def read(cap, times, records, drain):
+            self._call("profile_series_read", C.c_int(cap), ptr(times), ptr(records), C.byref(nb), C.byref(nbd),
+                       n.ctypes.data_as(C.POINTER(C.c_int)), dropped.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(1 if drain else 0))
+
+        read(0, None, None, False)
+        assert (nb.value, nbd.value) == (n_bins, n_bands), (nb.value, nbd.value, n_bins, n_bands)
+        cap, want = max(int(n.max()), 1), n.copy()
+        times, records = np.zeros((m, cap, 2)), np.zeros((m, cap, n_bands, n_bins, len(STATS_FIELDS)))
+        read(cap, times, records, drain)
+        assert np.array_equal(n, want), (n, want)
+        DH = self._params0().DH
+        return self._each([profile_series_dict(DH, times[k, :n[k]], records[k, :n[k]], int(dropped[k])) for k in range(m)])
+
+    def profile_series(self, drain=False):
+        """The series so far as profiles (profile.profile_series_profiles): step, t, y_mid and u_mean, u_std, uy_mean, uy_std,
+        count as [n, n_bands, n_bins] arrays, NaN where a bin is empty, n_dropped.  A batch: one such dict per member."""
+        DH = self._params0().DH
+        sums = self.profile_series_sums(drain)
+        return [profile_series_profiles(DH, s) for s in sums] if self._many else profile_series_profiles(DH, sums)
+
 
 class Batch(_Stepped):
     """M channels of one geometry stepped by the same launches (sphx_batch, include/sphx.h section 2b).
@@ -495,6 +558,7 @@ class Batch(_Stepped):
         self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
         self._field_map = None   # (nx, ny) while the field map is on
         self._probes = None      # the folded points [P, 2] while the probes are on
+        self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
         arr = (SphxParams * m)(*self.params)
         check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
@@ -543,6 +607,7 @@ class Context(_Stepped):
         self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
         self._field_map = None   # (nx, ny) while the field map is on
         self._probes = None      # the folded points [P, 2] while the probes are on
+        self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
         check(lib().sphx_ctx_create(C.byref(self._h), C.byref(self.params), C.c_int(n_fluid), C.c_int(n_total),
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
@@ -750,6 +815,42 @@ def probes_config(prm, points, every=1, capacity=65536, t_from=0.0, with_walls=F
     cfg = SphxProbesConfig(n_points=len(pts), every=every, capacity=int(capacity), with_walls=int(with_walls), t_from=t_from,
                            points=ptr(pts))
     return cfg, pts
+
+
+def profile_series_config(prm, n_bins=0, every=1, capacity=4096, t_from=0.0, bands=(), n_members=1) -> SphxProfileSeriesConfig:
+    """Checked sphx_profile_series_config for channels with parameters prm: bins, bands, every and t_from by the checks of
+    flow_stats_config, the record buffer by those of the probes; raises SphxError(SPHX:ProfileSeries:config) before anything
+    reaches the device.  n_members: the channels that get `capacity` records each (a batch's members)."""
+    bad = _config_error("ProfileSeries")
+    try:
+        f = flow_stats_config(n_bins, every, t_from, bands)
+    except SphxError as e:
+        raise bad(e.message) from None
+    if not _is_int(capacity) or capacity < 1 or capacity >= 1 << 31:
+        raise bad("capacity must be an integer >= 1")
+    bins = int(f.n_bins) or max(20, int(np.floor(prm.DH / prm.dp + 0.5)))
+    if bins * (int(f.n_bands) + 1) > 1536:
+        raise bad("n_bins * (number of bands + 1) must not exceed 1536")
+    if n_members * capacity * (int(f.n_bands) + 1) * bins * len(STATS_FIELDS) > 1 << 27:
+        raise bad(("n_members * " if n_members > 1 else "") + "capacity * (n_bands + 1) * n_bins * 5 must not exceed 1 << 27 doubles")
+    cfg = SphxProfileSeriesConfig(n_bins=int(f.n_bins), every=int(f.every), capacity=int(capacity), t_from=float(f.t_from),
+                                  n_bands=int(f.n_bands))
+    for k in range(2):
+        cfg.band_x[k], cfg.band_hw[k] = f.band_x[k], f.band_hw[k]
+    return cfg
+
+
+def profile_series_dict(DH, times, records, n_dropped=0) -> dict:
+    """times [n, 2] and records [n, n_bands, n_bins, 5] -> step (int64), t [n], one [n, n_bands, n_bins] array per STATS_FIELDS,
+    n_dropped and y_mid [n_bins], the bin centres of profile.flow_stats_profile."""
+    times = np.asarray(times, dtype=np.float64).reshape(-1, 2)
+    records = np.asarray(records, dtype=np.float64)
+    assert records.ndim == 4 and records.shape[0] == len(times) and records.shape[3] == len(STATS_FIELDS), records.shape
+    edges = np.linspace(0.0, DH, records.shape[2] + 1)
+    out = dict(step=times[:, 0].astype(np.int64), t=np.ascontiguousarray(times[:, 1]))
+    out.update({k: np.ascontiguousarray(records[:, :, :, j]) for j, k in enumerate(STATS_FIELDS)})
+    out.update(n_dropped=int(n_dropped), y_mid=0.5 * (edges[:-1] + edges[1:]))
+    return out
 
 
 def probes_dict(points, times, values, n_dropped=0) -> dict:

@@ -668,3 +668,57 @@ SPHX_EXPORT int sphx_batch_probes_read(sphx_batch *b, int capacity, double *time
     return SPHX_OK;
     SPHX_CATCH
 }
+
+// ---- profile series of every member (include/sphx.h section 2k) ----
+
+namespace {
+
+// the batch's profile series (member 0's, see sphx_ctx::pseries)
+ProfileSeries &batch_series(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    ProfileSeries &p = b->mem[0]->pseries;
+    sampler_check(kSeriesNames, false, p.on, need_on, "batch");
+    return p;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_batch_profile_series_enable(sphx_batch *b, const sphx_profile_series_config *cfg)
+{
+    SPHX_TRY
+    // (bins and bands come from the shared geometry; out of device memory: the batch goes on without a series)
+    ProfileSeries &p = batch_series(b, false);
+    series_enable(p, b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_profile_series_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    ProfileSeries &p = batch_series(b, false);
+    if (p.on) sampler_off(p, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_profile_series_sample(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_series(b, true);
+    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
+    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_profile_series);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_profile_series_read(sphx_batch *b, int capacity, double *times, double *records, int *n_bins, int *n_bands,
+                                               int *n_records, int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    ProfileSeries &p = batch_series(b, true);
+    series_read(p, b->stream, [b] { batch_settle(b); }, capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
+    return SPHX_OK;
+    SPHX_CATCH
+}

@@ -10,7 +10,8 @@
 // overflow.  A |u| above the bound (only a non-finite state can have one) raises a sticky flag and the read fails.
 // Each workgroup keeps the sample's counters in LDS, adds every non-zero one to the global integer sums with one
 // atomic, and the last workgroup out (last_out_fenced) converts the integer sums to double, adds them to the running
-// sums bin by bin and clears them for the next sample.
+// sums bin by bin and clears them for the next sample.  The binning itself (stats_bin_sample) is shared with the profile
+// series (sphx_profile_series.hpp), which stores the sample as a record where this sampler adds it.
 #pragma once
 #include "sphx_slot_sample.hpp"
 
@@ -118,17 +119,19 @@ struct StatsSlab : StatsOwn {
     __device__ bool mine(int i, double x) const { return owns(g, x, g.own_by_cell ? cell[i] : 0); }
 };
 
-// The sample of one channel closing the step slot of parity q, on clock clk, shared by the gridDim.x workgroups of a grid
-// row; `at` says where the channel's arrays are: a's own pointers (StatsOwn) or a batch member's blocks (StatsMember).
-template <typename At>
-__device__ __forceinline__ void flow_stats_body(const Clock *clk, int q, const FlowStatsArgs &a, const At &at)
+// the fixed-point scales of one sample (stats_scales)
+struct StatsScales {
+    int s1, s2;
+};
+
+// The binning of one sample, stated once for its two finishers -- flow_stats_body adds the sample to running sums,
+// profile_series_body (sphx_profile_series.hpp) stores it as a record: the workgroup's share of the n particles, binned into
+// its LDS counters s_cnt [n_bands][n_bins][kStatsFields], from zeroing them to the barrier behind the particle loop.  range():
+// the sticky flag of the head that owns the sample (looked up only by a thread that raises it).  By every thread of the workgroup.
+template <typename At, typename Range>
+__device__ __forceinline__ StatsScales stats_bin_sample(const FlowStatsArgs &a, const At &at, int n, double vmax, unsigned long long *s_cnt,
+                                                        int nc, Range &&range)
 {
-    if (!sample_due(clk, q, a.every, a.t_from)) return;
-    const int n = clk->n;
-    const double vmax = clk->vmax, t_now = clk->t;
-    extern __shared__ unsigned long long s_cnt[];  // [n_bands][n_bins][kStatsFields]
-    __shared__ int s_last;
-    const int nc = a.n_bands * a.n_bins * kStatsFields;
     for (int k = threadIdx.x; k < nc; k += kStatsBlock) s_cnt[k] = 0ull;
     __syncthreads();
 
@@ -152,14 +155,33 @@ __device__ __forceinline__ void flow_stats_body(const Clock *clk, int q, const F
             if (stats_in_band(p.x, a.DL, a.band_x[b - 1], a.band_hw[b - 1]))
                 stats_add(s_cnt + ((size_t)b * a.n_bins + k) * kStatsFields, ux, ux2, uy, uy2);
     }
-    if (out_of_range) atomicOr(&at.head(a)->range, 1);
+    if (out_of_range) atomicOr(range(), 1);
     __syncthreads();
+    return StatsScales{s1, s2};
+}
+
+// counter k of a sample as the double it stands for: field k % kStatsFields, its scale taken back out
+__device__ __forceinline__ double stats_value(int k, unsigned long long v, const StatsScales &sc)
+{
+    const int f = k % kStatsFields;
+    const int s = f == 0 ? 0 : ((f & 1) ? sc.s1 : sc.s2);
+    return ldexp((double)(long long)v, -s);
+}
+
+// The sample of one channel closing the step slot of parity q, on clock clk, shared by the gridDim.x workgroups of a grid
+// row; `at` says where the channel's arrays are: a's own pointers (StatsOwn) or a batch member's blocks (StatsMember).
+template <typename At>
+__device__ __forceinline__ void flow_stats_body(const Clock *clk, int q, const FlowStatsArgs &a, const At &at)
+{
+    if (!sample_due(clk, q, a.every, a.t_from)) return;
+    const int n = clk->n;
+    const double vmax = clk->vmax, t_now = clk->t;
+    extern __shared__ unsigned long long s_cnt[];  // [n_bands][n_bins][kStatsFields]
+    __shared__ int s_last;
+    const int nc = a.n_bands * a.n_bins * kStatsFields;
+    const StatsScales sc = stats_bin_sample(a, at, n, vmax, s_cnt, nc, [&] { return &at.head(a)->range; });
     // one thread per counter: the running sums grow in sample order, each by its own bin -- no summation tree
-    auto finish = [&](int k, unsigned long long v) {
-        const int f = k % kStatsFields;
-        const int s = f == 0 ? 0 : ((f & 1) ? s1 : s2);
-        at.dsum(a)[k] += ldexp((double)(long long)v, -s);
-    };
+    auto finish = [&](int k, unsigned long long v) { at.dsum(a)[k] += stats_value(k, v, sc); };
     if (gridDim.x == 1) {  // small channels: one workgroup holds the whole sample -- no global sums, no ticket
         for (int k = threadIdx.x; k < nc; k += kStatsBlock)
             if (s_cnt[k]) finish(k, s_cnt[k]);

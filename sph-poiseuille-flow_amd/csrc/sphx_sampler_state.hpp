@@ -6,6 +6,7 @@
 #include "sphx_history.hpp"
 #include "sphx_field_map.hpp"
 #include "sphx_probes.hpp"
+#include "sphx_profile_series.hpp"
 
 struct sphx_ctx;
 
@@ -98,7 +99,29 @@ struct Probes {
     void read(hipStream_t st, int capacity, double *times, double *values, int *n_records, int64_t *n_dropped, bool drain);
 };
 
-// the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes (sphx_samplers.hpp)
+// Profile series (sphx_ctx_profile_series_*, sphx_batch_profile_series_*; sphx_profile_series.hpp) of a context or of the M
+// members of a batch: one configuration, bins and bands as FlowStats has them, member m's int64 sums of the sample in flight
+// at m * block(), its times at m * cfg.capacity * 2, its records at m * cfg.capacity * block(), its head at m.
+struct ProfileSeries {
+    bool on = false;
+    int members = 1;
+    sphx_profile_series_config cfg{};
+    int n_bins = 0, n_bands = 1;  // (n_bands counts band 0)
+    DevBuf<unsigned long long> isum;
+    DevBuf<double> times, records;
+    DevBuf<ProfileSeriesHead> head;
+
+    size_t block() const { return (size_t)n_bands * (size_t)n_bins * kStatsFields; }  // the doubles of one record
+    size_t shmem() const { return block() * sizeof(unsigned long long); }             // the LDS counters of a workgroup
+    void check(const sphx_params &prm, const sphx_profile_series_config *cfg, int M);
+    void alloc(const ProfileSeries &checked, int M);
+    void zero(hipStream_t st) { isum.zero(st); head.zero(st); }  // (the counters: records beyond n_records are never read)
+    void release() { isum.release(); times.release(); records.release(); head.release(); }
+    void read(hipStream_t st, int capacity, double *times, double *records, int *n_records, int64_t *n_dropped, bool drain);
+};
+
+// the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes, profile series
+// (sphx_samplers.hpp)
 void launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild);
 
 }  // namespace sphx

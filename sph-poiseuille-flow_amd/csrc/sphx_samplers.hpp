@@ -1,8 +1,8 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
 // the velocity-field map (2e; 2g) and the point probes (2h; 2i) -- all four also of a slab of a ring (3a, at the end of this
-// file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
-// sphx_history.hpp, sphx_field_map.hpp and sphx_probes.hpp.  What they share -- the context check, on / off, the view a slot leaves,
+// file) -- and the profile series (2j; 2k).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
 
@@ -26,6 +26,8 @@ constexpr SamplerNames kFieldNames{"Field", "field maps are not available on sla
                                    "the map could not be set up: "};
 constexpr SamplerNames kProbeNames{"Probe", "point probes are not available on slab contexts", "point probes are not enabled on this ",
                                    "the record buffer could not be set up: "};
+constexpr SamplerNames kSeriesNames{"ProfileSeries", "the profile series is not available on slab contexts",
+                                    "the profile series is not enabled on this ", "the record buffer could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
 
@@ -229,6 +231,30 @@ void launch_probes(sphx_ctx *c, int q, const FluidSet &s, int every)
                  per_member(c->phys), s, c->walls, a);
 }
 
+// the arguments of a profile-series launch on state s into c->pseries
+ProfileSeriesArgs profile_series_args(sphx_ctx *c, const FluidSet &s, int every)
+{
+    const ProfileSeries &p = c->pseries;
+    ProfileSeriesArgs a{};
+    a.bin.pos = s.pos; a.bin.vel = s.vel;
+    a.bin.isum = p.isum.get();
+    a.bin.DH = c->prm.DH; a.bin.bin_w = c->prm.DH / p.n_bins; a.bin.DL = c->prm.DL;
+    a.bin.t_from = p.cfg.t_from;
+    for (int b = 0; b < 2; ++b) { a.bin.band_x[b] = p.cfg.band_x[b]; a.bin.band_hw[b] = p.cfg.band_hw[b]; }
+    a.bin.n_bins = p.n_bins; a.bin.n_bands = p.n_bands;
+    a.bin.every = every;
+    a.times = p.times.get(); a.records = p.records.get(); a.head = p.head.get();
+    a.capacity = p.cfg.capacity;
+    return a;
+}
+
+// k_profile_series on state s -- of a batch: member 0's -- into c->pseries: the workgroups of a flow-statistics sample
+void launch_profile_series(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    launch_forms(c, "k_profile_series", Forms{k_profile_series, k_profile_series_b}, flow_stats_blocks((size_t)c->nf), kStatsBlock,
+                 c->pseries.shmem(), q, profile_series_args(c, s, every));
+}
+
 }  // namespace
 
 void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
@@ -238,6 +264,7 @@ void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
     if (c->hist.on) launch_history(c, q, s, rebuild);
     if (c->fmap.on) launch_field_map(c, q, s, c->fmap.cfg.every);
     if (c->probes.on) launch_probes(c, q, s, c->probes.cfg.every);
+    if (c->pseries.on) launch_profile_series(c, q, s, c->pseries.cfg.every);
 }
 
 // ---- flow statistics ----
@@ -755,6 +782,152 @@ SPHX_EXPORT int sphx_ctx_probes_read(sphx_ctx *c, int capacity, double *times, d
     settle_owed(c);  // (the records of everything enqueued)
     p.read(c->stream, capacity, times, values, n_records, n_dropped, drain != 0);
     if (n_points) *n_points = p.cfg.n_points;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- profile series ----
+
+// every check of a configuration for M channels with parameters prm (cfg, n_bins, n_bands): the bins and bands by the checks
+// of FlowStats::configure, the record buffer by those of Probes::check; SPHX:ProfileSeries:config errors
+void ProfileSeries::check(const sphx_params &prm, const sphx_profile_series_config *cfg, int M)
+{
+    const char *id = "SPHX:ProfileSeries:config";
+    require(cfg != nullptr, id, "config must not be NULL");
+    require(cfg->n_bins >= 0, id, "n_bins must be >= 0 (0 = the reference's profile bins)");
+    require(cfg->every >= 1, id, "every must be >= 1");
+    require(cfg->capacity >= 1, id, "capacity must be >= 1");
+    require(!std::isnan(cfg->t_from), id, "t_from must not be NaN");
+    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, id, "n_bands must be 0, 1 or 2");
+    for (int b = 0; b < cfg->n_bands; ++b)
+        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, id,
+                "band centres must be finite and half-widths finite and >= 0");
+    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
+    require((int64_t)bins * (cfg->n_bands + 1) <= kStatsMaxBins, id,
+            "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
+    if (!((double)M * (double)cfg->capacity * (double)bins * (cfg->n_bands + 1) * kStatsFields <= (double)kSeriesMaxTotal))
+        throw Error(SPHX_ERR_ARG, id,
+                    std::string(M > 1 ? "n_members * " : "") + "capacity * (n_bands + 1) * n_bins * 5 must not exceed 1 << 27 doubles");
+    this->cfg = *cfg;
+    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
+    n_bins = bins;
+    n_bands = cfg->n_bands + 1;
+}
+
+// the checked configuration, and sums in flight, records and heads for M members
+void ProfileSeries::alloc(const ProfileSeries &checked, int M)
+{
+    cfg = checked.cfg;
+    n_bins = checked.n_bins;
+    n_bands = checked.n_bands;
+    members = M;
+    isum.alloc(block() * M);
+    times.alloc((size_t)M * cfg.capacity * 2);
+    records.alloc((size_t)M * cfg.capacity * block());
+    head.alloc(M);
+}
+
+// Every member's counts (n_records[m], n_dropped[m], where given) and its filled rows, into times[m][0 .. n_records[m])[2] of a
+// [members][capacity][2] array and records[m][0 .. n_records[m])[block()] of a [members][capacity][block()] array, each where
+// given; drain empties every buffer.  SPHX:ProfileSeries:range when a member's sticky flag is up; SPHX:ProfileSeries:capacity
+// when an array is given and capacity is below the largest count: nothing is copied or drained then.
+void ProfileSeries::read(hipStream_t st, int capacity, double *t_out, double *r_out, int *n_records, int64_t *n_dropped, bool drain)
+{
+    const int M = members;
+    std::vector<ProfileSeriesHead> h(M);
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(ProfileSeriesHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    long long most = 0;
+    for (int m = 0; m < M; ++m) {
+        const long long n = h[m].n_records;
+        if (n < 0 || n > (long long)cfg.capacity)
+            throw Error(SPHX_ERR_STATE, "SPHX:ProfileSeries:state", "internal: record count out of range");
+        if (h[m].range)
+            throw Error(SPHX_ERR_STATE, "SPHX:ProfileSeries:range", (M > 1 ? "member " + std::to_string(m) + ": " : std::string()) +
+                                                                    "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
+        most = std::max(most, n);
+    }
+    require((t_out == nullptr && r_out == nullptr) || (long long)capacity >= most, "SPHX:ProfileSeries:capacity",
+            "capacity is smaller than the number of records");
+    if ((t_out || r_out) && most > 0) {
+        for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
+            const size_t n = (size_t)h[m].n_records;
+            if (n == 0) continue;
+            if (t_out)
+                SPHX_HIP(hipMemcpyAsync(t_out + (size_t)m * capacity * 2, times.get() + (size_t)m * cfg.capacity * 2, n * 2 * sizeof(double),
+                                        hipMemcpyDeviceToHost, st));
+            if (r_out)
+                SPHX_HIP(hipMemcpyAsync(r_out + (size_t)m * capacity * block(), records.get() + (size_t)m * cfg.capacity * block(),
+                                        n * block() * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+    for (int m = 0; m < M; ++m) {
+        if (n_records) n_records[m] = (int)h[m].n_records;
+        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
+    }
+    if (drain) {
+        zero(st);
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+}
+
+namespace {
+
+// enable for M members of channels with parameters prm on schedule s: every check of cfg first
+void series_enable(ProfileSeries &p, const sphx_params &prm, const sphx_profile_series_config *cfg, int M, Schedule &s, hipStream_t st)
+{
+    ProfileSeries checked;
+    checked.check(prm, cfg, M);
+    sampler_on(p, kSeriesNames, s, st, [&] { p.alloc(checked, M); });
+}
+
+// settle() -- what is enqueued lands first -- then the read and the shape; shared by contexts and batches
+template <typename Settle>
+void series_read(ProfileSeries &p, hipStream_t st, Settle &&settle, int capacity, double *times, double *records, int *n_bins, int *n_bands,
+                 int *n_records, int64_t *n_dropped, int drain)
+{
+    settle();  // (the records of everything enqueued)
+    p.read(st, capacity, times, records, n_records, n_dropped, drain != 0);
+    if (n_bins) *n_bins = p.n_bins;
+    if (n_bands) *n_bands = p.n_bands;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_profile_series_enable(sphx_ctx *c, const sphx_profile_series_config *cfg)
+{
+    SPHX_TRY
+    ProfileSeries &p = sampler_of(c, &sphx_ctx::pseries, kSeriesNames, false);
+    series_enable(p, c->prm, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_profile_series_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    ProfileSeries &p = sampler_of(c, &sphx_ctx::pseries, kSeriesNames, false);
+    if (p.on) sampler_off(p, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_profile_series_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampler_of(c, &sphx_ctx::pseries, kSeriesNames, true);
+    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_profile_series);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_profile_series_read(sphx_ctx *c, int capacity, double *times, double *records, int *n_bins, int *n_bands,
+                                             int *n_records, int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    ProfileSeries &p = sampler_of(c, &sphx_ctx::pseries, kSeriesNames, true);
+    series_read(p, c->stream, [c] { settle_owed(c); }, capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
     return SPHX_OK;
     SPHX_CATCH
 }

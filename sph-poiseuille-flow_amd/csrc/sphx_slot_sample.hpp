@@ -1,4 +1,4 @@
-// sphx_slot_sample.hpp -- what the slot samplers' kernels share (k_flow_stats, k_step_history, k_field_map, k_point_probes and their batch forms;
+// sphx_slot_sample.hpp -- what the slot samplers' kernels share (k_flow_stats, k_step_history, k_field_map, k_point_probes, k_profile_series and their batch forms;
 // DESIGN.md section 4, "Slot samplers").  A slot sampler is one self-skipping launch at the end of every step slot, behind
 // the slot's clock update: clk->step / t / dt_last / vmax are those of the step just completed, and the state the slot left
 // is what it samples.

@@ -20,7 +20,7 @@ from .geometry import init_particles
 from .mex_surface import sph_neighbor_search_mex, sph_physics_shell_mex
 from . import restart
 from .profile import (compute_mid_channel_profile, field_map_means, final_profile, flow_stats_profile, l2_error, n_profile_bins, pool_field_maps,
-                      pool_flow_stats)
+                      pool_flow_stats, poiseuille_startup, profile_series_profiles)
 
 
 @dataclass
@@ -51,6 +51,9 @@ class RunResult:
                             # member of run_ensemble / run_sweep(..., field_from=...): its own (capi.Batch.field_map)
     probes: dict = None  # run / run_sweep(..., probe_points=...): the device-side point-probe series of the whole run
                          # (capi.Context.probes; probe_figures() turns it into means, RMS and spectral peaks)
+
+    profile_series: dict = None  # run / run_sweep(..., profiles_every=...): the device-side profile series of the whole run
+                                 # (capi.Context.profile_series; profile_series_figures() compares it with the start-up solution)
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -234,10 +237,89 @@ def _concat_probes(points, DL, chunks):
     return out
 
 
+def _records_lost(who, what, option, p, t, capacity):
+    """the error of a run whose record buffer (`what`, sized by `option`) overflowed between two output points"""
+    return RuntimeError(f"{who}{what} lost {p['n_dropped']} records before t={t:.6f}; the output interval needs "
+                        f"{option} >= {len(p['step']) + p['n_dropped']} (it is {capacity})")
+
+
 def _probes_lost(who, p, t, capacity):
-    """the error of a run whose probe buffer overflowed between two output points"""
-    return RuntimeError(f"{who}the point probes lost {p['n_dropped']} records before t={t:.6f}; the output interval needs "
-                        f"probe_capacity >= {len(p['step']) + p['n_dropped']} (it is {capacity})")
+    return _records_lost(who, "the point probes", "probe_capacity", p, t, capacity)
+
+
+def _profiles_lost(who, p, t, capacity):
+    return _records_lost(who, "the profile series", "profiles_capacity", p, t, capacity)
+
+
+_SERIES_KEYS = ("step", "t") + capi.STATS_FIELDS
+
+
+def _concat_profile_series(DH, chunks, who=""):
+    """The raw series of a whole run (capi.profile_series_dict) from the drained chunks, in their order.  A chunk that lost
+    records raises RuntimeError and names the capacity that output interval needed (ceil: a whole number of records); chunks
+    of different bins or bands are refused."""
+    chunks = list(chunks)
+    if not chunks:
+        raise ValueError("_concat_profile_series needs at least one chunk (its shape is the series')")
+    shape = np.asarray(chunks[0]["count"]).shape[1:]
+    for c in chunks:
+        if np.asarray(c["count"]).shape[1:] != shape:
+            raise ValueError(f"{who}profile-series chunks of different shapes (n_bands, n_bins): "
+                             f"{np.asarray(c['count']).shape[1:]} and {shape}")
+        if c["n_dropped"]:
+            need = int(np.ceil(len(c["step"]) + c["n_dropped"]))
+            t = float(c["t"][-1]) if len(c["t"]) else float("nan")
+            raise RuntimeError(f"{who}the profile series lost {c['n_dropped']} records after t={t:.6f}; the output interval "
+                               f"needs profiles_capacity >= {need} (it held {len(c['step'])})")
+    out = {k: np.concatenate([np.asarray(c[k]) for c in chunks]) for k in _SERIES_KEYS}
+    out.update(n_dropped=0, y_mid=np.asarray(chunks[0]["y_mid"], dtype=np.float64))
+    return profile_series_profiles(DH, out) | {k: out[k] for k in capi.STATS_FIELDS}
+
+
+def profile_series_figures(prm, series, band=1, tol=0.02):
+    """Figures of a profile series (capi.Context.profile_series / RunResult.profile_series) of band `band` against the start-up
+    of plane Poiseuille flow from rest, on the host; [n_records] arrays unless said otherwise.
+      L2_startup   relative L2 of u_mean against profile.poiseuille_startup(y_mid, t) per record, over the non-empty bins, by
+                   profile.l2_error's rule (NaN for a record whose bins are all empty)
+      L2_steady    the same against the steady parabola u_exact
+      u_centre     the mean of the two middle bins (the middle bin's value for an odd n_bins)
+      t_developed  the first record time from which L2_steady stays <= tol up to the last record; NaN if never
+      tau_fit      the decay time of U_max - u_centre: minus the inverse slope of a least-squares line through
+                   log |U_max - u_centre| over the records with 0.5 <= t pi^2 nu / DH^2 <= 3 (there the n = 3 mode is below
+                   e^-4 of the first), with U_max taken where u_centre is -- the mean of u_exact over the same middle bins,
+                   U_max (1 - 1 / n_bins^2) for an even n_bins: the difference would otherwise stay in the gap as a constant
+                   and bend the line (1.6 % of tau at 20 bins); NaN with fewer than two such records
+      tau_exact    DH^2 / (pi^2 nu), beside it; U_max = g DH^2 / (8 nu); u_exact [n_bins]"""
+    t = np.asarray(series["t"], dtype=np.float64)
+    y = np.asarray(series["y_mid"], dtype=np.float64)
+    u = np.asarray(series["u_mean"], dtype=np.float64)[:, band, :]
+    g, nu, DH = prm.gravity_g, prm.nu, prm.DH
+    u_exact = g / (2.0 * nu) * y * (DH - y)
+    u_max = g * DH * DH / (8.0 * nu)
+    tau_exact = DH * DH / (np.pi ** 2 * nu)
+    start = poiseuille_startup(y, t, g, nu, DH) if len(t) else np.zeros((len(y), 0))
+
+    def l2(a, b):
+        return l2_error(a, b) if not np.all(np.isnan(a)) else float("nan")
+
+    L2_startup = np.array([l2(u[r], start[:, r]) for r in range(len(t))])
+    L2_steady = np.array([l2(u[r], u_exact) for r in range(len(t))])
+    mid = len(y) // 2
+    centre = (lambda v: v[..., mid]) if len(y) % 2 else (lambda v: 0.5 * (v[..., mid - 1] + v[..., mid]))
+    u_centre = centre(u)
+    t_developed = float("nan")
+    ok = L2_steady <= tol
+    if len(t) and ok[-1]:
+        bad = np.nonzero(~ok)[0]
+        t_developed = float(t[bad[-1] + 1] if len(bad) else t[0])
+    tau_fit = float("nan")
+    gap = np.abs(centre(u_exact) - u_centre)
+    sel = (t / tau_exact >= 0.5) & (t / tau_exact <= 3.0) & np.isfinite(gap) & (gap > 0.0)
+    if np.count_nonzero(sel) >= 2 and np.ptp(t[sel]) > 0.0:
+        slope = np.polyfit(t[sel], np.log(gap[sel]), 1)[0]
+        tau_fit = float(-1.0 / slope) if slope != 0.0 else float("nan")
+    return dict(L2_startup=L2_startup, L2_steady=L2_steady, u_centre=u_centre, t_developed=t_developed, tau_fit=tau_fit,
+                tau_exact=float(tau_exact), U_max=float(u_max), u_exact=u_exact)
 
 
 def _concat_history(chunks):
@@ -251,7 +333,8 @@ def _concat_history(chunks):
 def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_particle=0, steps_per_graph=0,
         rebuild_every=0, restart_path=None, postprocess_path=None, dual_rate=0, mat_format="auto", average_from=None,
         average_every=1, history_every=None, history_capacity=65536, field_from=None, field_every=1, field_shape=None,
-        field_walls=False, probe_points=None, probe_every=1, probe_capacity=65536, probe_from=None, probe_walls=False):
+        field_walls=False, probe_points=None, probe_every=1, probe_capacity=65536, probe_from=None, probe_walls=False,
+        profiles_every=None, profiles_from=None, profiles_capacity=4096, profiles_bands=None):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -278,7 +361,16 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     t >= probe_from (None: from the start; probe_walls: the wall particles contribute with their wall velocity); the buffer
     (probe_capacity records) is drained at every output point, so a capacity that holds one output interval suffices --
     a run that lost records raises RuntimeError and names the capacity needed -- and RunResult.probes is the series of the
-    whole run (probe_figures() turns it into means, RMS and spectral peaks per probe)."""
+    whole run (probe_figures() turns it into means, RMS and spectral peaks per probe).
+    profiles_every (resident engine): record, on the device and inside the step loop, the binned velocity profile (include/sphx.h
+    section 2j: the flow statistics' sample of one step) every profiles_every-th step ending at t >= profiles_from (None: from
+    the start) in the reference's bins, for the whole channel and the bands profiles_bands (None: the mid-channel band (DL/2,
+    max(dp, h)) the output-point profiles use); the buffer (profiles_capacity records) is drained at every output point -- a
+    run that lost records raises RuntimeError and names the capacity needed -- and RunResult.profile_series is the series of
+    the whole run (profile_series_figures() compares it with the start-up solution).  The output-point snapshots are taken
+    as without it."""
+    if profiles_every is not None and engine != "resident":
+        raise ValueError("profiles_every needs the resident engine (the series is recorded on the device)")
     if probe_points is not None and engine != "resident":
         raise ValueError("probe_points needs the resident engine (the probes are recorded on the device)")
     if field_from is not None and engine != "resident":
@@ -312,6 +404,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     history, history_chunks = None, []
     field_avg = None
     probes, probe_chunks = None, []
+    series, series_chunks = None, []
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context.from_parts(prm, parts, t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
@@ -329,6 +422,10 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
             if probe_points is not None:
                 ctx.probes_enable(probe_points, every=probe_every, capacity=probe_capacity,
                                   t_from=t_start if probe_from is None else probe_from, with_walls=probe_walls)
+            if profiles_every is not None:
+                ctx.profile_series_enable(n_bins=n_bins, every=profiles_every, capacity=profiles_capacity,
+                                          t_from=t_start if profiles_from is None else profiles_from,
+                                          bands=[(mid_x, mid_hw)] if profiles_bands is None else profiles_bands)
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -351,6 +448,10 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                     probe_chunks.append(ctx.probes(drain=True))
                     if probe_chunks[-1]["n_dropped"]:
                         raise _probes_lost("", probe_chunks[-1], t, probe_capacity)
+                if profiles_every is not None:
+                    series_chunks.append(ctx.profile_series_sums(drain=True))
+                    if series_chunks[-1]["n_dropped"]:
+                        raise _profiles_lost("", series_chunks[-1], t, profiles_capacity)
                 if restart_path:
                     restart.save_restart(restart_path, prm.config_signature, dict(d, t=t, step=step), fmt=mat_format)
                 if log:
@@ -368,6 +469,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 field_avg = ctx.field_map()
             if probe_points is not None:
                 probes = _concat_probes(probe_points, prm.DL, probe_chunks)
+            if profiles_every is not None:
+                series = _concat_profile_series(prm.DH, series_chunks or [ctx.profile_series_sums()])
         finally:
             ctx.close()
     elif engine == "mex":
@@ -418,7 +521,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     return _run_result(prm, nf, nt, pos, vel, t=t, steps=int(step), wall_seconds=wall, profile_times=profile_times,
                        mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t, grid_policy=policy,
                        full_profile_u=full_profiles, n_inner=n_inner, time_avg=time_avg, history=history, field_avg=field_avg,
-                       probes=probes)
+                       probes=probes, profile_series=series)
 
 
 def _run_result(prm, nf, nt, pos, vel, **fields):
@@ -458,7 +561,8 @@ def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
                        profile_times=list(times), tau_bottom=tau_b, tau_top=tau_t, grid_policy=dict(policy), **extra)
 
 
-def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None, probe=None):
+def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None, probe=None,
+               profiles=None):
     """The batch run behind run_batch, run_ensemble and run_sweep (`name`, for the refusals): check and default the inputs,
     open the batch with the launch keywords `launch`, enable what was asked for, advance output point by output point, build
     every member's RunResult.
@@ -472,6 +576,9 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
       probe      (probe_points, probe_every, probe_capacity, probe_from, probe_walls): the point probes of include/sphx.h
                  section 2i, drained at every output point; every member gets its probes, and one that lost records raises
                  RuntimeError
+      profiles   (profiles_every, profiles_from, profiles_capacity, profiles_bands): the profile series of include/sphx.h
+                 section 2k, drained at every output point; every member gets its profile_series, and one that lost records
+                 raises RuntimeError
     -> the members, the wall seconds, the grid policy, with average the raw sums (whole, mid) of all members, and with field the
     raw planes of all members."""
     prms = list(prms)
@@ -492,6 +599,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
     fulls = [[] for _ in range(M)]
     chunks = [[] for _ in range(M)]
     pchunks = [[] for _ in range(M)]
+    schunks = [[] for _ in range(M)]
     t0 = time.perf_counter()
     with capi.Batch.from_parts(prms, parts_list, **launch) as b:
         if history:
@@ -504,6 +612,10 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         if probe:
             b.probes_enable(probe[0], every=probe[1], capacity=probe[2], t_from=0.0 if probe[3] is None else probe[3],
                             with_walls=probe[4])
+        if profiles:
+            b.profile_series_enable(n_bins=n_bins, every=profiles[0], capacity=profiles[2],
+                                    t_from=0.0 if profiles[1] is None else profiles[1],
+                                    bands=[(mid_x, mid_hw)] if profiles[3] is None else profiles[3])
         t = 0.0
         st = None
         while t < p0.t_end - 1e-12:
@@ -529,12 +641,18 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                     if p["n_dropped"]:
                         raise _probes_lost(f"member {m}: ", p, t, probe[2])
                     pchunks[m].append(p)
+            if profiles:
+                for m, p in enumerate(b.profile_series_sums(drain=True)):
+                    if p["n_dropped"]:
+                        raise _profiles_lost(f"member {m}: ", p, t, profiles[2])
+                    schunks[m].append(p)
             if log:
                 log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
         wall = time.perf_counter() - t0
         policy = _batch_policy(b)
         sums = (b.flow_stats_sums(0), b.flow_stats_sums(1)) if average else None
         planes = b.field_map_sums() if field else None
+        empty_series = b.profile_series_sums() if profiles and not schunks[0] else None
         members = []
         for m, prm in enumerate(prms):
             extra = {}
@@ -548,6 +666,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                 extra.update(field_avg=field_map_means(prm.DL, prm.DH, **planes[m]))
             if probe:
                 extra.update(probes=_concat_probes(probe[0], prm.DL, pchunks[m]))
+            if profiles:
+                extra.update(profile_series=_concat_profile_series(prm.DH, schunks[m] or [empty_series[m]], f"member {m}: "))
             members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra))
     return members, wall, policy, sums, planes
 
@@ -660,7 +780,8 @@ def field_table(prms, field_avgs):
 def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0, settle_tol=0.05, average_from=None,
               average_every=1, parts_list=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0, log=None,
               field_from=None, field_every=1, field_shape=None, field_walls=False, probe_points=None, probe_every=1,
-              probe_capacity=65536, probe_from=None, probe_walls=False):
+              probe_capacity=65536, probe_from=None, probe_walls=False, profiles_every=None, profiles_from=None,
+              profiles_capacity=4096, profiles_bands=None):
     """A parameter sweep: M channels of one geometry that differ in mu, c_f, p0, gravity_g, transport_coeff, stepped as one
     batch (capi.Batch) with every member's step history recorded on the device, inside the step loop (include/sphx.h
     section 2f) as run(history_every=...) does for one channel.  The members advance output point by output point as in
@@ -672,7 +793,9 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     gets a time_avg.  field_from: every member's velocity map as well (include/sphx.h section 2g), with the keywords of
     run(): each member gets a field_avg and the table the columns field_L2, field_x_spread, field_ix, field_uy_rms of
     field_figures(prm_m, field_avg_m).  probe_points: every member's point probes as well (include/sphx.h section 2i), with
-    the keywords of run(): one set of points for all members, and each member gets its probes.  A member that lost records to a full buffer raises RuntimeError, which names the member and the
+    the keywords of run(): one set of points for all members, and each member gets its probes.  profiles_every: every member's
+    profile series as well (include/sphx.h section 2k), with the keywords of run(): each member gets its profile_series and the
+    table the columns t_developed and tau_fit of profile_series_figures(prm_m, series_m).  A member that lost records to a full buffer raises RuntimeError, which names the member and the
     capacity the output interval needed.  Returns a SweepResult."""
     prms = list(prms)
     members, wall, policy, _, planes = _run_batch(
@@ -680,8 +803,12 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
                                             rebuild_every=rebuild_every), log, history=(history_every, history_capacity),
         average=None if average_from is None else (average_from, average_every),
         field=_field_request(field_from, field_every, field_shape, field_walls),
-        probe=None if probe_points is None else (probe_points, probe_every, probe_capacity, probe_from, probe_walls))
+        probe=None if probe_points is None else (probe_points, probe_every, probe_capacity, probe_from, probe_walls),
+        profiles=None if profiles_every is None else (profiles_every, profiles_from, profiles_capacity, profiles_bands))
     table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
     if planes is not None:
         table.update(field_table(prms, [r.field_avg for r in members]))
+    if profiles_every is not None:
+        figs = [profile_series_figures(p, r.profile_series) for p, r in zip(prms, members)]
+        table.update(t_developed=np.array([f["t_developed"] for f in figs]), tau_fit=np.array([f["tau_fit"] for f in figs]))
     return SweepResult(members=members, table=table, wall_seconds=wall, grid_policy=policy)

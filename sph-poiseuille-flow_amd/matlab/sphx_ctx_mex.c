@@ -26,6 +26,13 @@
  *   [step, t, weight, u_x, u_y, rho, n_dropped] = sphx_ctx_mex('probe_read', h, drain)
  *       step, t: n x 1; weight, u_x, u_y, rho: n x P, one row per recorded step (point probes, include/sphx.h section 2h);
  *       drain ~= 0 empties the device buffer
+ *   sphx_ctx_mex('pseries_enable', h, n_bins, every, capacity, t_from, bands)   % bands as for stats_enable
+ *   sphx_ctx_mex('pseries_disable', h)
+ *   sphx_ctx_mex('pseries_sample', h)  % append one record of the current state now
+ *   [step, t, N, sum_ux, sum_ux2, sum_uy, sum_uy2, n_bins, n_bands, n_dropped] = sphx_ctx_mex('pseries_read', h, drain)
+ *       step, t: n x 1; the five sums: n x (n_bands * n_bins), one row per recorded step, band b's bins in the columns
+ *       b * n_bins + (1 .. n_bins) with band 0 the whole channel (profile series, include/sphx.h section 2j: reshape(N, n,
+ *       n_bins, n_bands)); drain ~= 0 empties the device buffer
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -287,6 +294,61 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         mxFree(times);
         mxFree(values);
         if (nlhs > 6) plhs[6] = mxCreateDoubleScalar((double)dropped);
+    } else if (strcmp(cmd, "pseries_enable") == 0) {
+        sphx_profile_series_config sc;
+        const mxArray *b;
+        size_t nb, k;
+        arity(cmd, nrhs, 7, nlhs, 0);
+        b = prhs[6];
+        if (!mxIsDouble(b)) mexErrMsgIdAndTxt("SPHX:ProfileSeries:config", "pseries_enable: bands must be a double [k x 2] array");
+        nb = mxGetNumberOfElements(b) == 0 ? 0 : mxGetM(b);
+        if (nb > 2 || (nb > 0 && mxGetN(b) != 2))
+            mexErrMsgIdAndTxt("SPHX:ProfileSeries:config", "pseries_enable: bands must be [k x 2], k <= 2");
+        memset(&sc, 0, sizeof(sc));
+        sc.n_bins = (int32_t)mxGetScalar(prhs[2]);
+        sc.every = (int32_t)mxGetScalar(prhs[3]);
+        sc.capacity = (int32_t)mxGetScalar(prhs[4]);
+        sc.t_from = mxGetScalar(prhs[5]);
+        sc.n_bands = (int32_t)nb;
+        for (k = 0; k < nb; ++k) { sc.band_x[k] = mxGetDoubles(b)[k]; sc.band_hw[k] = mxGetDoubles(b)[k + nb]; }
+        ok(sphx_ctx_profile_series_enable(handle(prhs[1]), &sc));
+    } else if (strcmp(cmd, "pseries_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_profile_series_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "pseries_sample") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_profile_series_sample(handle(prhs[1])));
+    } else if (strcmp(cmd, "pseries_read") == 0) {
+        sphx_ctx *c;
+        int n = 0, got = 0, n_bins = 0, n_bands = 0, k, j, f, drain, rc;
+        int64_t dropped = 0;
+        size_t row;
+        double *times, *records;
+        arity(cmd, nrhs, 3, nlhs, 10);
+        c = handle(prhs[1]);
+        drain = mxGetScalar(prhs[2]) != 0.0;
+        ok(sphx_ctx_profile_series_read(c, 0, NULL, NULL, &n_bins, &n_bands, &n, NULL, 0));
+        row = (size_t)n_bands * (size_t)n_bins;
+        times = (double *)mxMalloc((size_t)(n > 0 ? n : 1) * 2 * sizeof(double));
+        records = (double *)mxMalloc((size_t)(n > 0 ? n : 1) * row * SPHX_PROFILE_SERIES_FIELDS * sizeof(double));
+        rc = sphx_ctx_profile_series_read(c, n, times, records, NULL, NULL, &got, &dropped, drain);  /* (nothing is stepped in between: got == n) */
+        if (rc != SPHX_OK) { mxFree(times); mxFree(records); ok(rc); }
+        for (f = 0; f < 2 && f < (nlhs > 0 ? nlhs : 1); ++f) {
+            plhs[f] = mxCreateDoubleMatrix((mwSize)got, 1, mxREAL);
+            for (k = 0; k < got; ++k) mxGetDoubles(plhs[f])[k] = times[(size_t)k * 2 + f];
+        }
+        for (f = 0; f < SPHX_PROFILE_SERIES_FIELDS && 2 + f < nlhs; ++f) {  /* the library's rows are records; MATLAB stores columns */
+            double *out;
+            plhs[2 + f] = mxCreateDoubleMatrix((mwSize)got, (mwSize)row, mxREAL);
+            out = mxGetDoubles(plhs[2 + f]);
+            for (k = 0; k < got; ++k)
+                for (j = 0; j < (int)row; ++j) out[(size_t)j * got + k] = records[((size_t)k * row + j) * SPHX_PROFILE_SERIES_FIELDS + f];
+        }
+        mxFree(times);
+        mxFree(records);
+        if (nlhs > 7) plhs[7] = mxCreateDoubleScalar((double)n_bins);
+        if (nlhs > 8) plhs[8] = mxCreateDoubleScalar((double)n_bands);
+        if (nlhs > 9) plhs[9] = mxCreateDoubleScalar((double)dropped);
     } else if (strcmp(cmd, "destroy") == 0) {
         arity(cmd, nrhs, 2, nlhs, 0);
         sphx_ctx_destroy(handle(prhs[1]));

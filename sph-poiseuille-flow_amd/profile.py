@@ -6,6 +6,8 @@ flow_stats_profile: the sums of the device's flow statistics (include/sphx.h sec
 pool_flow_stats: the sums of several channels (the members of a batch, section 2c) as one ensemble-averaged profile.
 shepard_field: one sample of the device's field map (include/sphx.h section 2e) in numpy; field_map_means: its sums as a map.
 pool_field_maps: the planes of several channels (the members of a batch, section 2g) as one ensemble-averaged map.
+poiseuille_startup: the series solution of the start-up of plane Poiseuille flow from rest; profile_series_profiles: the
+records of the device's profile series (include/sphx.h section 2j) as one profile per record.
 """
 from __future__ import annotations
 
@@ -85,6 +87,39 @@ def flow_stats_profile(DH, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples=0,
 
 
 _SUMS = ("count", "sum_ux", "sum_ux2", "sum_uy", "sum_uy2")
+STATS_FIELDS = _SUMS  # the five values per bin and band, in the order the library writes them
+
+
+def profile_series_profiles(DH, sums):
+    """The raw records of a profile series (capi.Context.profile_series_sums: the five STATS_FIELDS as [n_records, n_bands,
+    n_bins] arrays of per-step sums, plus step, t, n_dropped, y_mid) -> one profile per record and band: u_mean, u_std,
+    uy_mean, uy_std and count as [n_records, n_bands, n_bins] arrays by flow_stats_profile's rule applied per record (NaN
+    where a bin is empty), plus step, t, n_dropped, y_mid."""
+    N = np.asarray(sums["count"], dtype=np.float64)
+    out = dict(step=sums["step"], t=sums["t"], n_dropped=int(sums["n_dropped"]), y_mid=sums["y_mid"], count=N)
+    keys = ("u_mean", "u_std", "uy_mean", "uy_std")
+    for k in keys:
+        out[k] = np.full(N.shape, np.nan)
+    for r in range(N.shape[0]):
+        for b in range(N.shape[1]):
+            prof = flow_stats_profile(DH, *[np.asarray(sums[f], dtype=np.float64)[r, b] for f in STATS_FIELDS])
+            for k in keys:
+                out[k][r, b] = prof[k]
+    return out
+
+
+def poiseuille_startup(y, t, g, nu, DH, n_terms=200):
+    """The start-up of plane Poiseuille flow from rest under the body force g (Morris, Fox & Zhu 1997, eq. 21):
+      u(y, t) = g / (2 nu) y (DH - y) - sum over odd n of 4 g DH^2 / (nu pi^3 n^3) sin(n pi y / DH) exp(-n^2 pi^2 nu t / DH^2)
+    with the first n_terms odd n.  Broadcasts over y[:, None] and t[None, :]: -> [len(y), len(t)] (scalars: their shape)."""
+    y, t = np.asarray(y, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    Y = y[:, None] if y.ndim == 1 and t.ndim == 1 else y
+    T = t[None, :] if y.ndim == 1 and t.ndim == 1 else t
+    u = g / (2.0 * nu) * Y * (DH - Y) + 0.0 * T
+    for k in range(n_terms - 1, -1, -1):  # (small terms first)
+        n = 2 * k + 1
+        u = u - 4.0 * g * DH * DH / (nu * np.pi ** 3 * n ** 3) * np.sin(n * np.pi * Y / DH) * np.exp(-(n * np.pi / DH) ** 2 * nu * T)
+    return u
 
 
 def pool_flow_stats(DH, sums_list):
