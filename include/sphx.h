@@ -703,8 +703,8 @@ int sphx_batch_probes_read(sphx_batch *batch, int capacity, double *times, doubl
  *    the record buffer, or the allocation fails: the context then goes on without a series), SPHX:ProfileSeries:disabled
  *    (SPHX_ERR_STATE: a call that needs the series while it is off), SPHX:ProfileSeries:range (SPHX_ERR_STATE),
  *    SPHX:ProfileSeries:capacity (the caller's arrays are smaller than n_records); every call on a slab context fails with
- *    SPHX_ERR_ARG, SPHX:ProfileSeries:slab (slab rings have no profile series).  A refused enable leaves a running series,
- *    and its records, untouched.
+ *    SPHX_ERR_ARG, SPHX:ProfileSeries:slab (the series of a ring: sphx_slab_pseries_*, section 3a).  A refused enable leaves
+ *    a running series, and its records, untouched.
  * ---------------------------------------------------------------------------------------------- */
 
 #define SPHX_PROFILE_SERIES_FIELDS 5
@@ -836,9 +836,10 @@ int sphx_slab_snapshot(sphx_ctx *ctx, int capacity, int *n, double *x, double *y
 
 /* ------------------------------------------------------------------------------------------------
  * 3a. Samplers of a slab ring: the flow statistics of section 2a, the step history of section 2d, the velocity-field
- *    map of section 2e and the point probes of section 2h (described with their three calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that a ring
- *    reports its time-averaged profile, the settling of its wall shear and its averaged field without a snapshot per
- *    sample.  The config structs, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* / SPHX:Field:*
+ *    map of section 2e, the point probes of section 2h and the profile series of section 2j (the last two described with
+ *    their three calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that
+ *    a ring reports its time-averaged profile, the settling of its wall shear, its averaged field and its profile at every
+ *    sampled step without a snapshot per sample.  The config structs, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* / SPHX:Field:*
  *    identifiers are those of sections 2a / 2d / 2e; sphx_ctx_flow_stats_*,
  *    sphx_ctx_history_* and sphx_ctx_field_map_* keep refusing a slab (SPHX:Stats:slab, SPHX:History:slab,
  *    SPHX:Field:slab).
@@ -920,6 +921,25 @@ int sphx_slab_probes_disable(sphx_ctx *ctx);
  * and capacity is below n_records.  drain != 0: the buffer is emptied and n_dropped zeroed after copying. */
 int sphx_slab_probes_read(sphx_ctx *ctx, int capacity, double *times, double *values, int *index, int *n_points_ring,
                           int *n_owned, int *n_records, int64_t *n_dropped, int drain);
+/* Profile series of a ring (the series of section 2j; k_profile_series_s).  The names say pseries: no function of this
+ * header has both "slab" and "profile_series" in its name.  The config, its checks, the record layout, capacity and drops,
+ * drain, the gating and the SPHX:ProfileSeries:* identifiers are those of section 2j.  Like the flow statistics, a slab
+ * bins, at the end of a sampled step, the fluid particles it OWNS, never its halo copies, and a slab's record is the PARTIAL
+ * sample over them: the ring's record is the element-wise sum over the ranks of all five fields, count included -- exact
+ * integers per slab, each converted once, so the ring's record does not depend on how the channel is cut, and per slab the
+ * records added in order are that slab's flow-statistics sums (same config) to the bit.  Band membership goes by x mod DL,
+ * whatever frame a slab keeps x in.  Every slab has its own buffer of `capacity` records with its own n_records and
+ * n_dropped; `step` and `t` come from the clock, so step, t, n_records and n_dropped are the same on every rank, and a slab
+ * that owns nothing in a band (or nothing at all) still stores that band's zeros and counts the record.  A refused enable
+ * leaves a running series, its records and a prepared graph as they are.  SPHX:ProfileSeries:disabled: a read while the
+ * series is off; disable is a no-op then.  There is no "sample now" call.  sphx_ctx_profile_series_* keep refusing a slab
+ * (SPHX:ProfileSeries:slab). */
+int sphx_slab_pseries_enable(sphx_ctx *ctx, const sphx_profile_series_config *cfg);
+int sphx_slab_pseries_disable(sphx_ctx *ctx);
+/* The slab's records (its partial samples); arguments as sphx_ctx_profile_series_read: both arrays NULL reports only the
+ * shape and the counts. */
+int sphx_slab_pseries_read(sphx_ctx *ctx, int capacity, double *times, double *records, int *n_bins, int *n_bands,
+                           int *n_records, int64_t *n_dropped, int drain);
 
 #ifdef __cplusplus
 }

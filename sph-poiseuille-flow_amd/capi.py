@@ -101,6 +101,7 @@ EXPORTS = [
     "sphx_slab_history_enable", "sphx_slab_history_disable", "sphx_slab_history_read",
     "sphx_slab_field_map_enable", "sphx_slab_field_map_disable", "sphx_slab_field_map_reset", "sphx_slab_field_map_read",
     "sphx_slab_probes_enable", "sphx_slab_probes_disable", "sphx_slab_probes_read",
+    "sphx_slab_pseries_enable", "sphx_slab_pseries_disable", "sphx_slab_pseries_read",
     "sphx_batch_create", "sphx_batch_destroy", "sphx_batch_advance", "sphx_batch_enqueue_steps", "sphx_batch_sync",
     "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
     "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",
@@ -208,10 +209,12 @@ _STATE = ("pos", "vel", "drho_dt", "mass", "wall_vel")
 
 
 class _Sampled:
-    """What a context, a batch and a slab of a ring bind alike: the flow statistics' sums and the step history's records.  A
-    subclass names its symbol stem, the word of its "not enabled on this ..." errors and whether it has many channels: a
+    """What a context, a batch and a slab of a ring bind alike: the flow statistics' sums, the step history's records and the
+    profile series' raw records.  A subclass names its symbol stem, the word its profile-series calls carry behind the stem
+    (a slab's are sphx_slab_pseries_*), the word of its "not enabled on this ..." errors and whether it has many channels: a
     context or a slab returns one dict / (records, n_dropped) pair, a batch a list with one entry per member."""
     _stem = _where = None
+    _series = "profile_series_"
     _many = False
 
     def _call(self, name, *args):
@@ -296,6 +299,49 @@ class _Sampled:
         read(cap, rec, drain)
         assert np.array_equal(n, want), (n, want)
         return self._each([(rec[k, :n[k]].copy(), int(dropped[k])) for k in range(m)])
+
+    # ---- profile series (include/sphx.h sections 2j, 2k, 3a): the binned velocity profile, one record per sampled step ----
+    def profile_series_enable(self, n_bins=0, every=1, capacity=4096, t_from=0.0, bands=()):
+        """Record the flow statistics' sample of the state -- n_bins y-bins (0: the reference's max(20, round(DH/dp))) of the
+        whole channel (band 0) and of up to two x-bands [(x_centre, half_width), ...] -- every `every`-th completed step ending
+        at t >= t_from into a device buffer of `capacity` records ((re)configures and empties it).  Records that find the
+        buffer full are dropped and counted.  A record is n_bands * n_bins * 5 doubles.  A batch: one config for all members,
+        `capacity` records per member, each recorded on its own clock.  A slab of a ring: its own buffer, of PARTIAL samples
+        over the particles it owns (slab.pool_ring_profile_series adds the ranks' up)."""
+        p0 = self._params0()
+        cfg = profile_series_config(p0, n_bins, every, capacity, t_from, bands, n_members=self._channels())
+        self._call(self._series + "enable", C.byref(cfg))
+        # (n_bins, n_bands incl. band 0) while the profile series is on
+        self._profile_series = (int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5))), int(cfg.n_bands) + 1)
+
+    def profile_series_disable(self):
+        self._call(self._series + "disable")
+        self._profile_series = None
+
+    def _series_on(self):
+        return _enabled(self._profile_series, "ProfileSeries", f"the profile series is not enabled on this {self._where}")
+
+    def profile_series_sums(self, drain=False):
+        """The raw series so far: step (int64) and t [n], the five STATS_FIELDS (count, sum_ux, sum_ux2, sum_uy, sum_uy2 of
+        each sampled step) as [n, n_bands, n_bins] arrays, n_dropped and the bin centres y_mid; drain empties the buffer
+        after the copy.  A batch: one such dict per member, from one read of all members.  A slab of a ring: its partial sums."""
+        n_bins, n_bands = self._series_on()
+        m = self._channels()
+        n, dropped = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
+        nb, nbd = C.c_int(0), C.c_int(0)
+
+        def read(cap, times, records, drain):
+            self._call(self._series + "read", C.c_int(cap), ptr(times), ptr(records), C.byref(nb), C.byref(nbd),
+                       n.ctypes.data_as(C.POINTER(C.c_int)), dropped.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(1 if drain else 0))
+
+        read(0, None, None, False)
+        assert (nb.value, nbd.value) == (n_bins, n_bands), (nb.value, nbd.value, n_bins, n_bands)
+        cap, want = max(int(n.max()), 1), n.copy()
+        times, records = np.zeros((m, cap, 2)), np.zeros((m, cap, n_bands, n_bins, len(STATS_FIELDS)))
+        read(cap, times, records, drain)
+        assert np.array_equal(n, want), (n, want)
+        DH = self._params0().DH
+        return self._each([profile_series_dict(DH, times[k, :n[k]], records[k, :n[k]], int(dropped[k])) for k in range(m)])
 
 
 class _Stepped(_Sampled):
@@ -464,52 +510,11 @@ class _Stepped(_Sampled):
         assert np.array_equal(n, want), (n, want)
         return self._each([probes_dict(pts, times[k, :n[k]], values[k, :n[k]], int(dropped[k])) for k in range(m)])
 
-    # ---- profile series (include/sphx.h sections 2j, 2k): the binned velocity profile, one record per sampled step ----
-    def profile_series_enable(self, n_bins=0, every=1, capacity=4096, t_from=0.0, bands=()):
-        """Record the flow statistics' sample of the state -- n_bins y-bins (0: the reference's max(20, round(DH/dp))) of the
-        whole channel (band 0) and of up to two x-bands [(x_centre, half_width), ...] -- every `every`-th completed step ending
-        at t >= t_from into a device buffer of `capacity` records ((re)configures and empties it).  Records that find the
-        buffer full are dropped and counted.  A record is n_bands * n_bins * 5 doubles.  A batch: one config for all members,
-        `capacity` records per member, each recorded on its own clock."""
-        p0 = self._params0()
-        cfg = profile_series_config(p0, n_bins, every, capacity, t_from, bands, n_members=self._channels())
-        self._call("profile_series_enable", C.byref(cfg))
-        # (n_bins, n_bands incl. band 0) while the profile series is on
-        self._profile_series = (int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5))), int(cfg.n_bands) + 1)
-
-    def profile_series_disable(self):
-        self._call("profile_series_disable")
-        self._profile_series = None
-
-    def _series_on(self):
-        return _enabled(self._profile_series, "ProfileSeries", f"the profile series is not enabled on this {self._where}")
-
+    # ---- profile series (include/sphx.h sections 2j, 2k): "sample now" and the profiles ----
     def profile_series_sample(self):
         """Append one record of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
         self._series_on()
         self._call("profile_series_sample")
-
-    def profile_series_sums(self, drain=False):
-        """The raw series so far: step (int64) and t [n], the five STATS_FIELDS (count, sum_ux, sum_ux2, sum_uy, sum_uy2 of
-        each sampled step) as [n, n_bands, n_bins] arrays, n_dropped and the bin centres y_mid; drain empties the buffer
-        after the copy.  A batch: one such dict per member, from one read of all members."""
-        n_bins, n_bands = self._series_on()
-        m = self._channels()
-        n, dropped = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
-        nb, nbd = C.c_int(0), C.c_int(0)
-
-        def read(cap, times, records, drain):
-            self._call("profile_series_read", C.c_int(cap), ptr(times), ptr(records), C.byref(nb), C.byref(nbd),
-                       n.ctypes.data_as(C.POINTER(C.c_int)), dropped.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(1 if drain else 0))
-
-        read(0, None, None, False)
-        assert (nb.value, nbd.value) == (n_bins, n_bands), (nb.value, nbd.value, n_bins, n_bands)
-        cap, want = max(int(n.max()), 1), n.copy()
-        times, records = np.zeros((m, cap, 2)), np.zeros((m, cap, n_bands, n_bins, len(STATS_FIELDS)))
-        read(cap, times, records, drain)
-        assert np.array_equal(n, want), (n, want)
-        DH = self._params0().DH
-        return self._each([profile_series_dict(DH, times[k, :n[k]], records[k, :n[k]], int(dropped[k])) for k in range(m)])
 
     def profile_series(self, drain=False):
         """The series so far as profiles (profile.profile_series_profiles): step, t, y_mid and u_mean, u_std, uy_mean, uy_std,

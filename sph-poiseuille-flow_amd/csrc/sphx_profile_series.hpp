@@ -1,5 +1,6 @@
 // sphx_profile_series.hpp -- the profile series of a resident context (include/sphx.h section 2j) and of every member of a
-// batch (section 2k, k_profile_series_b): a slot sampler (sphx_slot_sample.hpp) that bins the state the step left into the
+// batch (section 2k, k_profile_series_b) and of a slab of a ring (section 3a, k_profile_series_s: the particles the slab
+// owns): a slot sampler (sphx_slot_sample.hpp) that bins the state the step left into the
 // reference's profile bins exactly as the flow statistics do (sphx_flow_stats.hpp) and, where they add the sample to running
 // sums, appends it as one record -- {step, t} and n_bands x n_bins x kStatsFields doubles -- to a record buffer in device
 // memory.  "Flow statistics that record instead of accumulate": the velocity profile at every sampled step, the one
@@ -100,6 +101,19 @@ __global__ __launch_bounds__(kStatsBlock) void k_profile_series_b(Members mb, in
     const size_t nc = (size_t)a.bin.n_bands * (size_t)a.bin.n_bins * kStatsFields;
     profile_series_body(mb.clk + m, q, a, StatsMember{mb.part, m}, a.times + (size_t)m * (size_t)a.capacity * 2,
                         a.records + (size_t)m * (size_t)a.capacity * nc, a.head + m);
+}
+
+// slab of a ring (sphx_slab_pseries_*): the particles this slab owns, of the clk->n it holds, into its own records, its own
+// int64 sums, head and ticket -- a PARTIAL record: exact integers converted once, so the ring's record (the slabs' added up,
+// field by field, count included) does not depend on how the channel is cut; a slab that owns nothing in a band stores that
+// band's zeros.  x is in the frame of the slab's window: the first slab may hold x < 0 and the last x >= DL, which
+// stats_in_band's fmod brings back into [0, DL).
+__global__ __launch_bounds__(kStatsBlock) void k_profile_series_s(const Clock *clk, int q, ProfileSeriesArgs a, Grid g, const int *cell)
+{
+    StatsSlab at;
+    at.g = g;
+    at.cell = cell;
+    profile_series_body(clk, q, a, at, a.times, a.records, a.head);
 }
 
 }  // namespace sphx

@@ -1,7 +1,7 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
-// the velocity-field map (2e; 2g) and the point probes (2h; 2i) -- all four also of a slab of a ring (3a, at the end of this
-// file) -- and the profile series (2j; 2k).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// the velocity-field map (2e; 2g), the point probes (2h; 2i) and the profile series (2j; 2k) -- all five also of a slab of a
+// ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -26,7 +26,7 @@ constexpr SamplerNames kFieldNames{"Field", "field maps are not available on sla
                                    "the map could not be set up: "};
 constexpr SamplerNames kProbeNames{"Probe", "point probes are not available on slab contexts", "point probes are not enabled on this ",
                                    "the record buffer could not be set up: "};
-constexpr SamplerNames kSeriesNames{"ProfileSeries", "the profile series is not available on slab contexts",
+constexpr SamplerNames kSeriesNames{"ProfileSeries", "the profile series of a slab is sphx_slab_pseries_* (include/sphx.h section 3a)",
                                     "the profile series is not enabled on this ", "the record buffer could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
@@ -942,6 +942,9 @@ SPHX_EXPORT int sphx_ctx_profile_series_read(sphx_ctx *c, int capacity, double *
 // owned particles and its halo copies, and the ring's map is the slabs' blocks side by side.
 // The point probes: the same reasoning with points for nodes -- the POINTS are divided (probe_owner), a slab records the
 // complete sample of every probe it owns, and the ring's series is the slabs' columns back in the list's order.
+// The profile series: the flow statistics' reasoning -- a record is the slab's PARTIAL sample over the particles it owns, exact
+// integers converted once, and the ring's record is the slabs' records added up field by field (sphx_slab_pseries_*: no
+// function of include/sphx.h carries both "slab" and "profile_series" in its name).
 
 namespace {
 
@@ -949,11 +952,11 @@ namespace {
 // later) and in front of everything of phase 3: the clock is the finished step's, S[1-q] holds the owned particles' new state,
 // Vol / B (c->tmp) and the layout arrays (cell, mass) are those of the layout the step ran in -- clk->n is still that
 // layout's count (k_slab_unpack3 sets the new one), so a re-binning step needs no src_of.  One self-skipping launch each,
-// on the slab's stream, in the order statistics, history, map, probes; all off: nothing is enqueued, and a sampler that is
-// off adds nothing to what the others enqueue.
+// on the slab's stream, in the order statistics, history, map, probes, profile series; all off: nothing is enqueued, and a
+// sampler that is off adds nothing to what the others enqueue.
 void launch_slab_samplers(sphx_ctx *c)
 {
-    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on) return;
+    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on && !c->pseries.on) return;
     const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
     const FluidSet s = c->view(1 - q, 0);
@@ -984,6 +987,10 @@ void launch_slab_samplers(sphx_ctx *c)
         launch_s(c, "k_point_probes_s", k_point_probes_s, dim3(std::max(probe_blocks(a), 1u)), dim3(kProbeBlock), 0, clk, q, c->grid,
                  c->phys, s, c->walls, a);
     }
+    // (the flow statistics' workgroups, from the capacity; the record is the slab's partial sample, into its own buffer)
+    if (c->pseries.on)
+        launch_s(c, "k_profile_series_s", k_profile_series_s, dim3(flow_stats_blocks((size_t)c->cap)), dim3(kStatsBlock), c->pseries.shmem(),
+                 clk, q, profile_series_args(c, s, c->pseries.cfg.every), c->grid, (const int *)s.cell);
 }
 
 // The rank of slab c's ring that owns a probe at x, folded into [0, DL): rank r when edge(r) <= x < edge(r + 1), with
@@ -1227,6 +1234,40 @@ SPHX_EXPORT int sphx_slab_probes_read(sphx_ctx *c, int capacity, double *times, 
     if (index) std::copy(p.index.begin(), p.index.end(), index);
     if (n_points_ring) *n_points_ring = p.cfg.n_points;
     if (n_owned) *n_owned = p.held();
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_pseries_enable(sphx_ctx *c, const sphx_profile_series_config *cfg)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    ProfileSeries checked;
+    checked.check(c->prm, cfg, 1);  // (a refused configuration leaves a running series and a prepared graph as they are)
+    slab_samplers_changed(c);
+    series_enable(c->pseries, c->prm, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_pseries_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    if (c->pseries.on) {
+        slab_samplers_changed(c);
+        sampler_off(c->pseries, c->sched, c->stream);
+    }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_pseries_read(sphx_ctx *c, int capacity, double *times, double *records, int *n_bins, int *n_bands,
+                                       int *n_records, int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    ProfileSeries &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::pseries, kSeriesNames);
+    series_read(p, c->stream, [c] { slab_settle(c); }, capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
     return SPHX_OK;
     SPHX_CATCH
 }

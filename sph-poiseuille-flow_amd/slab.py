@@ -15,8 +15,8 @@ Layers:
   HipSlabEngine    -- the per-rank compute engine (libsphx slab context)
   SlabDriver       -- step loop = engine.compute -> exchange -> engine.finish
   pool_ring_* / ring_* / all_reduce_ring_*
-                   -- the ring's flow statistics and step history from the slabs' partial sums, its field map from the
-                      slabs' blocks of node columns, and its point probes from the slabs' owned probes
+                   -- the ring's flow statistics, step history and profile series from the slabs' partial sums, its field
+                      map from the slabs' blocks of node columns, and its point probes from the slabs' owned probes
   bench_main()     -- bench.py's multi-GPU leg
 """
 from __future__ import annotations
@@ -30,7 +30,7 @@ import time
 import numpy as np
 
 from . import capi as _capi
-from .profile import FIELD_MAP_PLANES, field_map_means, flow_stats_profile
+from .profile import FIELD_MAP_PLANES, field_map_means, flow_stats_profile, profile_series_profiles
 
 HALO_COLS = 4  # four dependent neighbour passes per step, each reaching one >=2h column further
 
@@ -123,9 +123,12 @@ class HipSlabEngine(_capi._Sampled):
     field_part_sums are the velocity-field map: the complete planes of the node columns this slab owns, a PART of the ring's
     map, which pool_ring_field_map (ring_field_map, all_reduce_ring_field_map) puts together.  probes_part_enable / _disable /
     probes_part_records are the point probes: the complete series of the probes this slab owns, a PART of the ring's, which
-    pool_ring_probes (ring_probes, all_reduce_ring_probes) puts together.  Enabling or disabling drops a graph made by
-    graph_prepare()."""
-    _stem, _where = "sphx_slab_", "slab"
+    pool_ring_probes (ring_probes, all_reduce_ring_probes) puts together.  profile_series_enable / _disable /
+    profile_series_sums(drain) are a context's too (capi._Sampled, over sphx_slab_pseries_*): this slab's PARTIAL record of
+    every sampled step, which pool_ring_profile_series (ring_profile_series_sums / ring_profile_series,
+    all_reduce_ring_profile_series) adds up; means of partial sums would mislead, so the engine has no profile_series().
+    Enabling or disabling drops a graph made by graph_prepare()."""
+    _stem, _where, _series = "sphx_slab_", "slab", "pseries_"
 
     def __init__(self, prm, parts, rank, world, device, lanes_per_particle=0, halo_cols=HALO_COLS, t_end=None,
                  pos=None, vel=None, drho_dt=None, native=False, rebuild_every=0, skin_h=0.0, hip_stream=None):
@@ -136,6 +139,7 @@ class HipSlabEngine(_capi._Sampled):
         self.capi = capi
         self.rank, self.world, self.native = rank, world, native
         self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
+        self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
         capi.set_device(device)
         if not native:
             import torch
@@ -392,6 +396,66 @@ def ring_history(engines, drain=False) -> dict:
     return pool_ring_history([e.history_records(drain) for e in engines])
 
 
+def _series_shape(sums):
+    """(n_records, n_bands, n_bins) of one rank's raw profile series, whose five fields must share that shape, step and t
+    hold n_records values and y_mid n_bins"""
+    shape = np.shape(sums["count"])
+    if len(shape) != 3:
+        raise ValueError(f"count has shape {shape}, [n_records, n_bands, n_bins] expected")
+    for k in _SUMS:
+        if np.shape(sums[k]) != shape:
+            raise ValueError(f"field {k} has shape {np.shape(sums[k])}, count {shape}")
+    for k in ("step", "t"):
+        if np.shape(sums[k]) != shape[:1]:
+            raise ValueError(f"{k} has shape {np.shape(sums[k])}, the fields hold {shape[0]} records")
+    if np.shape(sums["y_mid"]) != shape[2:]:
+        raise ValueError(f"y_mid has shape {np.shape(sums['y_mid'])}, the fields hold {shape[2]} bins")
+    return tuple(int(v) for v in shape)
+
+
+def pool_ring_profile_series(sums_list) -> dict:
+    """The ring's raw profile series (the dict of capi.Context.profile_series_sums) from the ranks' partial series
+    (HipSlabEngine.profile_series_sums, in rank order): the five fields added elementwise over the ranks, one rank after the
+    other, count included; step, t, y_mid and n_dropped are rank 0's.  ValueError when the [n_records, n_bands, n_bins] shape,
+    step, t, n_dropped or y_mid differ between the ranks (every slab of a ring records the same steps, a slab that owns
+    nothing in a band its zeros)."""
+    sums_list = list(sums_list)
+    if not sums_list:
+        raise ValueError("the profile series of a ring needs the series of at least one slab")
+    shapes = [_series_shape(s) for s in sums_list]
+    first = sums_list[0]
+    for r, (s, sh) in enumerate(zip(sums_list, shapes)):
+        if sh != shapes[0]:
+            raise ValueError(f"rank {r} holds {sh[0]} records of {sh[1]} bands x {sh[2]} bins, rank 0 {shapes[0][0]} of "
+                             f"{shapes[0][1]} x {shapes[0][2]}: the slabs of one ring share the config and record the same steps")
+        if not np.array_equal(s["step"], first["step"]) or not np.array_equal(s["t"], first["t"]):
+            raise ValueError(f"rank {r} recorded steps {np.asarray(s['step'])!r}, rank 0 {np.asarray(first['step'])!r} (or other "
+                             "times): the slabs of one ring record the same steps")
+        if int(s["n_dropped"]) != int(first["n_dropped"]):
+            raise ValueError(f"rank {r} dropped {s['n_dropped']} records, rank 0 {first['n_dropped']}")
+        if not np.array_equal(s["y_mid"], first["y_mid"]):
+            raise ValueError(f"rank {r} holds other bin centres than rank 0: the slabs of one ring share the bins")
+    out = dict(step=np.asarray(first["step"]).astype(np.int64), t=np.array(first["t"], dtype=np.float64))
+    for k in _SUMS:
+        total = np.array(first[k], dtype=np.float64)
+        for s in sums_list[1:]:
+            total = total + np.asarray(s[k], dtype=np.float64)
+        out[k] = total
+    out.update(n_dropped=int(first["n_dropped"]), y_mid=np.array(first["y_mid"], dtype=np.float64))
+    return out
+
+
+def ring_profile_series_sums(engines, drain=False) -> dict:
+    """The raw profile series of an in-process ring (pool_ring_profile_series of every slab's partial series)."""
+    return pool_ring_profile_series([e.profile_series_sums(drain) for e in engines])
+
+
+def ring_profile_series(engines, drain=False) -> dict:
+    """The profile series of an in-process ring as profiles (profile.profile_series_profiles of the pooled series): what
+    driver.profile_series_figures takes."""
+    return profile_series_profiles(engines[0].params.DH, ring_profile_series_sums(engines, drain))
+
+
 def _check_blocks_partition(shapes):
     """shapes: [(nx, ny, i_lo, i_hi)] per rank -- the blocks of one nx x ny grid, side by side from 0 to nx."""
     nx, ny = int(shapes[0][0]), int(shapes[0][1])
@@ -614,6 +678,39 @@ def all_reduce_ring_probes(part, dist, group=None) -> dict:
     for j, f in enumerate(_capi.PROBE_FIELDS):
         out[f] = np.where(total[F + j] > 0.0, np.nan, total[j])
     out["n_dropped"] = int(part["n_dropped"])
+    return out
+
+
+def all_reduce_ring_profile_series(sums, dist, group=None) -> dict:
+    """One rank per process: the ring's raw profile series from this rank's partial series, as pool_ring_profile_series; every
+    rank gets it.  The sizes, n_dropped and whether a rank's own series is well formed are all-gathered and checked first,
+    then step, t and y_mid; then the five fields, stacked, are all-reduced.  Collective; raises on every rank when a series is
+    malformed or the shape, n_dropped, step, t or y_mid differ between the ranks."""
+    try:
+        shape, why = _series_shape(sums), None
+        dropped = float(int(sums["n_dropped"]))
+    except (ValueError, KeyError, TypeError) as e:
+        shape, dropped, why = (-1, -1, -1), -1.0, str(e)
+    rows = _all_gathered(dist, [float(v) for v in shape] + [dropped, 0.0 if why is None else 1.0], group)
+    for r, row in enumerate(rows):
+        if row[4] != 0.0:
+            raise ValueError(f"rank {r}'s series is malformed" + (f": {why}" if why else ""))
+    for r, row in enumerate(rows):
+        if tuple(row[:4]) != tuple(rows[0][:4]):
+            raise ValueError(f"rank {r} holds {int(row[0])} records of {int(row[1])} bands x {int(row[2])} bins, {int(row[3])} "
+                             f"dropped; rank 0 {int(rows[0][0])} of {int(rows[0][1])} x {int(rows[0][2])}, {int(rows[0][3])}: the "
+                             "slabs of one ring share the config and record the same steps")
+    step, t = np.asarray(sums["step"], dtype=np.float64), np.asarray(sums["t"], dtype=np.float64)
+    y_mid = np.asarray(sums["y_mid"], dtype=np.float64)
+    clock = _all_gathered(dist, np.concatenate([step, t, y_mid]), group)
+    for r, row in enumerate(clock):
+        if not np.array_equal(row, clock[0]):  # (every rank sees every row: one odd rank out makes all of them raise)
+            raise ValueError(f"rank {r} recorded other steps or times (or holds other bin centres) than rank 0: the slabs of one "
+                             "ring record the same steps")
+    total = _all_reduced(dist, np.stack([np.asarray(sums[k], dtype=np.float64) for k in _SUMS]), group)
+    out = dict(step=np.asarray(sums["step"]).astype(np.int64), t=t.copy())
+    out.update({k: np.ascontiguousarray(total[j]) for j, k in enumerate(_SUMS)})
+    out.update(n_dropped=int(sums["n_dropped"]), y_mid=y_mid.copy())
     return out
 
 
