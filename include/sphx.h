@@ -763,6 +763,95 @@ int sphx_batch_profile_series_read(sphx_batch *batch, int capacity, double *time
                                    int *n_records, int64_t *n_dropped, int drain);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2l. Pair statistics: the pair-distance histogram of the fluid particles, counted on the device, inside the step loop.
+ *     The five samplers above describe the velocity field; this one describes the particle ARRANGEMENT: the radial
+ *     distribution function g(r), the mean neighbour count, the width of the first shell and the smallest separation --
+ *     what pairing or clumping, a missing neighbour at the periodic seam or a transport_coeff that is too small show in first.
+ *     It is integer work and therefore EXACT: profile.pair_histogram (numpy) reproduces it count for count.
+ *
+ *  Centres: a fluid particle i with y_margin <= y_i <= DH - y_margin.  Band 0 is the whole channel, bands 1..2 are x-bands
+ *    with the membership rule of section 2a (x mod DL within half_width of the centre, the short way round).
+ *  Partners: every fluid particle j != i (by slot), anywhere; with_walls: also every wall particle, in a histogram of its own.
+ *  Distance: dx = x_i - x_j folded by the minimum image (dx > DL/2 -> dx - DL, dx < -DL/2 -> dx + DL), dy = y_i - y_j,
+ *    r2 = dx*dx + dy*dy rounded after every operation (no fused multiply-add): the very double numpy computes.  Only the
+ *    nearest image counts: a channel shorter than 4h can hold a second image of a partner within 2h, and that one is missed.
+ *  Bins: n_bins uniform bins in r on [0, r_max).  Squared edges e2[k] = (k * (r_max / n_bins))^2 for k < n_bins and
+ *    e2[n_bins] = r_max * r_max; bin k holds e2[k] <= r2 < e2[k+1]; r2 >= e2[n_bins] is not counted; coincident particles
+ *    (r2 = 0) count in bin 0.  Comparisons against e2 decide the bin (numpy: searchsorted(e2, r2, side="right") - 1).
+ *  Limits: r_max = 0 means 2h, otherwise 0 < r_max <= 2h: beyond 2h the sweep of the three cell columns around a centre is no
+ *    longer complete, so it is refused.  1 <= n_bins <= 1024: with three bands and walls that is 6144 counters, which with the
+ *    bands' centres and minima are the 49 200 B of LDS a workgroup of the sampler asks for: every allowed combination fits.
+ *  Sums, per band, over all samples, all int64: `centres`, ff[n_bins] (ordered fluid-fluid pairs: a pair of two centres counts
+ *    twice), fw[n_bins] (fluid-wall pairs; zeros without walls), and r2_min, a double: the smallest fluid-fluid r2 among the
+ *    counted pairs so far, +inf before any.  Per sampler: n_samples, t_first, t_last.
+ *  Gating: as in section 2a: a step is sampled when its step count (sphx_status.step after it) is a multiple of `every` and
+ *    it ends at t >= t_from.  Dual-rate contexts sample once per outer step.  sphx_ctx_pair_dist_sample adds a sample of
+ *    the state now, without gating.
+ *  Determinism: integer sums and a minimum do not depend on the order they arrive in: the sums are independent of particle
+ *    order, layout (lanes_per_particle, skin, dynamic_rebin), re-binning phase and batch membership, to the last count.
+ *  Off by default.  With it off a step slot enqueues exactly the launches it does without this feature; on, every step slot
+ *    ends with one more launch (k_pair_dist, behind k_profile_series; it skips itself on the steps gated out) that is
+ *    captured in the replayed graphs; enable / disable re-capture them.  A sample costs 1.6 to 1.9 cell sweeps of the step's
+ *    density pass: `every` is the control.  Independent of the other five samplers.
+ *  Errors: SPHX:PairDist:config (NULL config, n_bins outside 1..1024, every < 1, a NaN t_from, r_max that is not finite,
+ *    negative or above 2h, a y_margin that is not finite or negative, with_walls not 0 / 1, n_bands outside 0..2, a band
+ *    centre or half-width that is not finite or a negative half-width, or the allocation fails: the context
+ *    then goes on without pair statistics), SPHX:PairDist:band, SPHX:PairDist:capacity (ff or fw given and capacity <
+ *    n_bins), SPHX:PairDist:disabled (SPHX_ERR_STATE: a call that needs the sampler while it is off); every call on a slab
+ *    context fails with SPHX_ERR_ARG, SPHX:PairDist:slab (slab rings have no pair statistics).  A refused enable leaves a
+ *    running sampler, and its sums, untouched.
+ * ---------------------------------------------------------------------------------------------- */
+
+#define SPHX_PAIR_DIST_MAX_BINS 1024
+
+typedef struct sphx_pair_dist_config {
+    int32_t n_bins;            /* 1..1024 uniform bins in r on [0, r_max)                                */
+    int32_t every;             /* sample every `every`-th completed step (step count % every == 0), >= 1 */
+    double t_from;             /* only steps ending at t >= t_from                                       */
+    double r_max;              /* 0 = 2h; otherwise 0 < r_max <= 2h                                      */
+    double y_margin;           /* centres: y_margin <= y <= DH - y_margin, >= 0                          */
+    int32_t with_walls;        /* 1: the wall particles are partners too, in fw                          */
+    int32_t n_bands;           /* 0..2 x-bands besides the whole channel                                 */
+    double band_x[2], band_hw[2];
+} sphx_pair_dist_config;
+
+/* (Re)configure and zero the sums; waits for the stream.  Off by default. */
+int sphx_ctx_pair_dist_enable(sphx_ctx *ctx, const sphx_pair_dist_config *cfg);
+/* Stop sampling (no-op when off); the sums are dropped. */
+int sphx_ctx_pair_dist_disable(sphx_ctx *ctx);
+/* Zero the sums and the sample count; the configuration stays. */
+int sphx_ctx_pair_dist_reset(sphx_ctx *ctx);
+/* Add one sample of the current state (what sphx_ctx_download would return) now, without gating. */
+int sphx_ctx_pair_dist_sample(sphx_ctx *ctx);
+/* The sums of one band so far: ff and fw are [capacity] (capacity >= n_bins where either is given), every pointer may be
+ * NULL.  Waits for and settles everything enqueued, like sphx_ctx_download.  t_first / t_last are NaN before a sample. */
+int sphx_ctx_pair_dist_read(sphx_ctx *ctx, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw, int64_t *centres,
+                            double *r2_min, int64_t *n_samples, double *t_first, double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2m. Pair statistics of a batch (section 2b): the sums of section 2l for every member at once.
+ *
+ *  One config for all members (h, DL, DH and the walls come from the shared geometry).  Every member has its own block of
+ *  sums and its own head and is sampled on its own clock with the gating of section 2l, so a member that sits out slots is
+ *  not sampled in them.  The sums are exact: a member's are those of a standalone context with the same parameters and
+ *  config that took the same steps; realignments move particles between slots only and change no count.  With the sampler
+ *  on, every step slot of the batch ends with one launch for all members (k_pair_dist_b, behind the batch's other
+ *  samplers); off, a slot enqueues exactly the launches it does without this feature.  Memory: n_members blocks of
+ *  (n_bands + 1) * (n_bins * (1 + with_walls) + 2) words of 8 bytes.  A refused enable leaves a running sampler untouched.
+ *  Errors: SPHX:Batch:null (NULL batch) and those of section 2l.
+ * ---------------------------------------------------------------------------------------------- */
+
+int sphx_batch_pair_dist_enable(sphx_batch *batch, const sphx_pair_dist_config *cfg);
+int sphx_batch_pair_dist_disable(sphx_batch *batch);
+int sphx_batch_pair_dist_reset(sphx_batch *batch);
+/* settles; adds a sample of what sphx_batch_download returns, every member, without gating */
+int sphx_batch_pair_dist_sample(sphx_batch *batch);
+/* One call for all members: ff and fw are [n_members][capacity] (member m's bins at m * capacity), centres, r2_min,
+ * n_samples, t_first and t_last are [n_members]; any pointer may be NULL.  Settles first, as sphx_batch_download does. */
+int sphx_batch_pair_dist_read(sphx_batch *batch, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw, int64_t *centres,
+                              double *r2_min, int64_t *n_samples, double *t_first, double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU). The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

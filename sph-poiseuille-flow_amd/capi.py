@@ -8,7 +8,8 @@ import os
 
 import numpy as np
 
-from .profile import FIELD_MAP_PLANES, STATS_FIELDS, field_map_means, flow_stats_profile, profile_series_profiles
+from .profile import (FIELD_MAP_PLANES, STATS_FIELDS, field_map_means, flow_stats_profile, pair_dist_profiles, pair_edges,
+                      profile_series_profiles)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPHX_LIB") or os.path.join(HERE, "csrc", "libsphx.so")  # SPHX_LIB: experiment builds
@@ -68,6 +69,15 @@ class SphxProfileSeriesConfig(C.Structure):
                 ("n_bands", C.c_int32), ("band_x", C.c_double * 2), ("band_hw", C.c_double * 2)]
 
 
+class SphxPairDistConfig(C.Structure):
+    _fields_ = [("n_bins", C.c_int32), ("every", C.c_int32), ("t_from", C.c_double), ("r_max", C.c_double),
+                ("y_margin", C.c_double), ("with_walls", C.c_int32), ("n_bands", C.c_int32), ("band_x", C.c_double * 2),
+                ("band_hw", C.c_double * 2)]
+
+
+PAIR_DIST_MAX_BINS = 1024
+
+
 class SphxStatus(C.Structure):
     _fields_ = [("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("vmax", C.c_double),
                 ("step", C.c_int64), ("done", C.c_int32), ("device_status", C.c_int32)]
@@ -94,6 +104,8 @@ EXPORTS = [
     "sphx_ctx_probes_enable", "sphx_ctx_probes_disable", "sphx_ctx_probes_sample", "sphx_ctx_probes_read",
     "sphx_ctx_profile_series_enable", "sphx_ctx_profile_series_disable", "sphx_ctx_profile_series_sample",
     "sphx_ctx_profile_series_read",
+    "sphx_ctx_pair_dist_enable", "sphx_ctx_pair_dist_disable", "sphx_ctx_pair_dist_reset", "sphx_ctx_pair_dist_sample",
+    "sphx_ctx_pair_dist_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -112,6 +124,8 @@ EXPORTS = [
     "sphx_batch_probes_enable", "sphx_batch_probes_disable", "sphx_batch_probes_sample", "sphx_batch_probes_read",
     "sphx_batch_profile_series_enable", "sphx_batch_profile_series_disable", "sphx_batch_profile_series_sample",
     "sphx_batch_profile_series_read",
+    "sphx_batch_pair_dist_enable", "sphx_batch_pair_dist_disable", "sphx_batch_pair_dist_reset", "sphx_batch_pair_dist_sample",
+    "sphx_batch_pair_dist_read",
 ]
 
 _LIB = None
@@ -523,6 +537,65 @@ class _Stepped(_Sampled):
         sums = self.profile_series_sums(drain)
         return [profile_series_profiles(DH, s) for s in sums] if self._many else profile_series_profiles(DH, sums)
 
+    # ---- pair statistics (include/sphx.h sections 2l, 2m): the pair-distance histogram of the fluid particles ----
+    def pair_dist_enable(self, n_bins=64, every=1, t_from=0.0, r_max=0.0, y_margin=0.0, with_walls=False, bands=()):
+        """Count, every `every`-th completed step ending at t >= t_from, the partners of every fluid particle with
+        y_margin <= y <= DH - y_margin by distance, into n_bins uniform bins in r on [0, r_max) (r_max = 0: 2h; at most 2h): ff
+        (fluid partners), with_walls: fw (wall partners), for the whole channel (band 0) and for the centres in up to two
+        x-bands [(x_centre, half_width), ...].  Integer sums: exact, profile.pair_histogram gives the same counts.
+        (Re)configures and zeroes the sums.  A batch: one config for all members, each sampled on its own clock."""
+        p0 = self._params0()
+        cfg = pair_dist_config(p0, n_bins, every, t_from, r_max, y_margin, with_walls, bands)
+        self._call("pair_dist_enable", C.byref(cfg))
+        # (n_bins, n_bands incl. band 0, r_max in force) while the pair statistics are on
+        self._pair_dist = (int(cfg.n_bins), int(cfg.n_bands) + 1, float(cfg.r_max) or 2.0 * p0.h)
+
+    def pair_dist_disable(self):
+        self._call("pair_dist_disable")
+        self._pair_dist = None
+
+    def _pairs_on(self):
+        return _enabled(self._pair_dist, "PairDist", f"pair statistics are not enabled on this {self._where}")
+
+    def pair_dist_reset(self):
+        self._pairs_on()
+        self._call("pair_dist_reset")
+
+    def pair_dist_sample(self):
+        """Add one sample of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
+        self._pairs_on()
+        self._call("pair_dist_sample")
+
+    def _pair_dist_band(self, band):
+        n_bins, n_bands, r_max = self._pairs_on()
+        if not _is_int(band) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:PairDist:band", f"band must be an integer in 0..{n_bands - 1}")
+        m = self._channels()
+        ff, fw = np.zeros((m, n_bins), dtype=np.int64), np.zeros((m, n_bins), dtype=np.int64)
+        centres, ns = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+        r2, t0, t1 = np.zeros(m), np.zeros(m), np.zeros(m)
+        nb = C.c_int(0)
+        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        self._call("pair_dist_read", C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), i64(ff), i64(fw), i64(centres), ptr(r2), i64(ns),
+                   ptr(t0), ptr(t1))
+        assert nb.value == n_bins, (nb.value, n_bins)
+        r_edges = pair_edges(r_max, n_bins)[0]
+        return [dict(r_edges=r_edges, ff=ff[k].copy(), fw=fw[k].copy(), centres=int(centres[k]), r2_min=float(r2[k]),
+                     r_min=float(np.sqrt(r2[k])), n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k])) for k in range(m)]
+
+    def pair_dist_sums(self):
+        """The raw sums so far, one dict per band (band 0: the whole channel): r_edges [n_bins + 1], ff, fw [n_bins] (int64),
+        centres, r2_min, r_min (+inf before any pair), n_samples, t_first, t_last.  A batch: one such list per member."""
+        n_bands = self._pairs_on()[1]
+        per_band = [self._pair_dist_band(b) for b in range(n_bands)]
+        return self._each([[per_band[b][k] for b in range(n_bands)] for k in range(self._channels())])
+
+    def pair_dist(self, band=0):
+        """One band's sums with the figures of profile.pair_dist_profiles: r_mid, g, g_wall, n_neigh, r_min.  A batch: one such
+        dict per member."""
+        dp = self._params0().dp
+        return self._each([dict(s, **pair_dist_profiles(s, dp)) for s in self._pair_dist_band(band)])
+
 
 class Batch(_Stepped):
     """M channels of one geometry stepped by the same launches (sphx_batch, include/sphx.h section 2b).
@@ -564,6 +637,7 @@ class Batch(_Stepped):
         self._field_map = None   # (nx, ny) while the field map is on
         self._probes = None      # the folded points [P, 2] while the probes are on
         self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
+        self._pair_dist = None   # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
         arr = (SphxParams * m)(*self.params)
         check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
@@ -613,6 +687,7 @@ class Context(_Stepped):
         self._field_map = None   # (nx, ny) while the field map is on
         self._probes = None      # the folded points [P, 2] while the probes are on
         self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
+        self._pair_dist = None   # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
         check(lib().sphx_ctx_create(C.byref(self._h), C.byref(self.params), C.c_int(n_fluid), C.c_int(n_total),
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
@@ -840,6 +915,32 @@ def profile_series_config(prm, n_bins=0, every=1, capacity=4096, t_from=0.0, ban
         raise bad(("n_members * " if n_members > 1 else "") + "capacity * (n_bands + 1) * n_bins * 5 must not exceed 1 << 27 doubles")
     cfg = SphxProfileSeriesConfig(n_bins=int(f.n_bins), every=int(f.every), capacity=int(capacity), t_from=float(f.t_from),
                                   n_bands=int(f.n_bands))
+    for k in range(2):
+        cfg.band_x[k], cfg.band_hw[k] = f.band_x[k], f.band_hw[k]
+    return cfg
+
+
+def pair_dist_config(prm, n_bins=64, every=1, t_from=0.0, r_max=0.0, y_margin=0.0, with_walls=False, bands=()) -> SphxPairDistConfig:
+    """Checked sphx_pair_dist_config for channels with parameters prm; raises SphxError(SPHX:PairDist:config) before anything
+    reaches the device.  every, t_from and the bands by the checks of flow_stats_config."""
+    bad = _config_error("PairDist")
+    if not _is_int(n_bins) or not 1 <= n_bins <= PAIR_DIST_MAX_BINS:
+        raise bad("n_bins must be an integer in 1..1024")
+    try:
+        f = flow_stats_config(0, every, t_from, bands)
+        r_max, y_margin = float(r_max), float(y_margin)
+    except SphxError as e:
+        raise bad(e.message) from None
+    except (TypeError, ValueError):
+        raise bad("r_max and y_margin must be numbers") from None
+    if not (np.isfinite(r_max) and 0.0 <= r_max <= 2.0 * prm.h):
+        raise bad("r_max must be 0 (= 2h) or 0 < r_max <= 2h: beyond 2h the sweep of the three cell columns is not complete")
+    if not (np.isfinite(y_margin) and y_margin >= 0.0):
+        raise bad("y_margin must be finite and >= 0")
+    if not isinstance(with_walls, (bool, np.bool_)) and with_walls not in (0, 1):
+        raise bad("with_walls must be a bool")
+    cfg = SphxPairDistConfig(n_bins=int(n_bins), every=int(f.every), t_from=float(f.t_from), r_max=r_max, y_margin=y_margin,
+                             with_walls=1 if with_walls else 0, n_bands=int(f.n_bands))
     for k in range(2):
         cfg.band_x[k], cfg.band_hw[k] = f.band_x[k], f.band_hw[k]
     return cfg

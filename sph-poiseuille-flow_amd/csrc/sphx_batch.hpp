@@ -722,3 +722,67 @@ SPHX_EXPORT int sphx_batch_profile_series_read(sphx_batch *b, int capacity, doub
     return SPHX_OK;
     SPHX_CATCH
 }
+
+// ---- pair statistics of every member (include/sphx.h section 2m) ----
+
+namespace {
+
+// the batch's pair statistics (member 0's, see sphx_ctx::pairs)
+PairDist &batch_pairs(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    PairDist &p = b->mem[0]->pairs;
+    sampler_check(kPairNames, false, p.on, need_on, "batch");
+    return p;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_batch_pair_dist_enable(sphx_batch *b, const sphx_pair_dist_config *cfg)
+{
+    SPHX_TRY
+    // (h, DL, DH and the walls come from the shared geometry; out of device memory: the batch goes on without pair statistics)
+    PairDist &p = batch_pairs(b, false);
+    pair_dist_enable(p, b->mem[0]->prm, cfg, b->M, b->mem[0]->nw > 0, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_pair_dist_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    PairDist &p = batch_pairs(b, false);
+    if (p.on) sampler_off(p, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_pair_dist_reset(sphx_batch *b)
+{
+    SPHX_TRY
+    PairDist &p = batch_pairs(b, true);
+    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(p, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_pair_dist_sample(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_pairs(b, true);
+    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
+    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_pair_dist);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_pair_dist_read(sphx_batch *b, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw, int64_t *centres,
+                                          double *r2_min, int64_t *n_samples, double *t_first, double *t_last)
+{
+    SPHX_TRY
+    const PairDist &p = batch_pairs(b, true);
+    pair_dist_read(p, b->stream, [b] { batch_settle(b); }, band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}

@@ -7,6 +7,7 @@
 #include "sphx_field_map.hpp"
 #include "sphx_probes.hpp"
 #include "sphx_profile_series.hpp"
+#include "sphx_pair_dist.hpp"
 
 struct sphx_ctx;
 
@@ -120,8 +121,33 @@ struct ProfileSeries {
     void read(hipStream_t st, int capacity, double *times, double *records, int *n_records, int64_t *n_dropped, bool drain);
 };
 
-// the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes, profile series
-// (sphx_samplers.hpp)
+// Pair-distance statistics (sphx_ctx_pair_dist_*, sphx_batch_pair_dist_*; sphx_pair_dist.hpp) of a context or of the M members
+// of a batch: one configuration, member m's integer sums at m * block() -- [n_bands][kinds][n_bins] counts, [n_bands] centres,
+// [n_bands] r2_min bit patterns -- and its head at m.
+struct PairDist {
+    bool on = false;
+    int members = 1;
+    sphx_pair_dist_config cfg{};
+    int n_bins = 0, n_bands = 1;  // (n_bands counts band 0)
+    int kinds = 1;                // 2: a fluid-wall histogram beside the fluid-fluid one
+    double r_max = 0.0;           // the range in force (cfg.r_max = 0: 2h)
+    DevBuf<unsigned long long> sums;
+    DevBuf<PairDistHead> head;
+    std::vector<unsigned long long> empty;  // what zero() writes: zero counts, r2_min = +inf
+
+    size_t counters() const { return (size_t)n_bands * (size_t)kinds * (size_t)n_bins; }
+    size_t block() const { return counters() + 2 * (size_t)n_bands; }                  // the words of one member
+    size_t shmem() const { return block() * sizeof(unsigned long long); }              // the LDS counters of a workgroup
+    void check(const sphx_params &prm, const sphx_pair_dist_config *cfg, int M, bool has_walls);
+    void alloc(const PairDist &checked, int M);
+    void zero(hipStream_t st);
+    void release() { sums.release(); head.release(); }
+    void read(hipStream_t st, int band, int stride, int64_t *ff, int64_t *fw, int64_t *centres, double *r2_min, int64_t *n_samples,
+              double *t_first, double *t_last) const;
+};
+
+// the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes, profile series,
+// pair statistics (sphx_samplers.hpp)
 void launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild);
 
 }  // namespace sphx

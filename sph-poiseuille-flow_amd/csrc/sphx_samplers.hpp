@@ -1,7 +1,7 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
 // the velocity-field map (2e; 2g), the point probes (2h; 2i) and the profile series (2j; 2k) -- all five also of a slab of a
-// ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// ring (3a, at the end of this file) -- and the pair statistics (2l; 2m, sphx_pair_dist.hpp).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -28,6 +28,9 @@ constexpr SamplerNames kProbeNames{"Probe", "point probes are not available on s
                                    "the record buffer could not be set up: "};
 constexpr SamplerNames kSeriesNames{"ProfileSeries", "the profile series of a slab is sphx_slab_pseries_* (include/sphx.h section 3a)",
                                     "the profile series is not enabled on this ", "the record buffer could not be set up: "};
+
+constexpr SamplerNames kPairNames{"PairDist", "pair statistics are not available on slab contexts", "pair statistics are not enabled on this ",
+                                  "the sums could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
 
@@ -255,6 +258,36 @@ void launch_profile_series(sphx_ctx *c, int q, const FluidSet &s, int every)
                  c->pseries.shmem(), q, profile_series_args(c, s, every));
 }
 
+// the arguments of a pair-statistics launch into c->pairs
+PairDistArgs pair_dist_args(sphx_ctx *c, int every)
+{
+    const PairDist &p = c->pairs;
+    PairDistArgs a{};
+    a.sums = p.sums.get(); a.head = p.head.get();
+    a.bin_w = p.r_max / p.n_bins; a.rmax2 = p.r_max * p.r_max;
+    a.y_lo = p.cfg.y_margin; a.y_hi = c->prm.DH - p.cfg.y_margin;
+    a.DL = c->prm.DL; a.t_from = p.cfg.t_from;
+    for (int b = 0; b < 2; ++b) { a.band_x[b] = p.cfg.band_x[b]; a.band_hw[b] = p.cfg.band_hw[b]; }
+    a.n_bins = p.n_bins; a.n_bands = p.n_bands; a.kinds = p.kinds;
+    a.block = (int)p.block();
+    a.every = every;
+    return a;
+}
+
+// workgroups of the sample of a channel that holds n particles: kPairCentres centres a trip
+unsigned pair_dist_blocks(size_t n)
+{
+    return std::clamp<unsigned>(div_up(n, (size_t)kPairCentres), 1u, (unsigned)kPairMaxBlocks);
+}
+
+// k_pair_dist on state s (pos and the cell ranges and binned cells of the layout it is stored in) -- of a batch: member 0's --
+// into c->pairs
+void launch_pair_dist(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    launch_forms(c, "k_pair_dist", Forms{k_pair_dist, k_pair_dist_b}, pair_dist_blocks((size_t)c->nf), kPairBlock, c->pairs.shmem(), q,
+                 c->grid, s, c->walls, pair_dist_args(c, every));
+}
+
 }  // namespace
 
 void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
@@ -265,6 +298,7 @@ void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
     if (c->fmap.on) launch_field_map(c, q, s, c->fmap.cfg.every);
     if (c->probes.on) launch_probes(c, q, s, c->probes.cfg.every);
     if (c->pseries.on) launch_profile_series(c, q, s, c->pseries.cfg.every);
+    if (c->pairs.on) launch_pair_dist(c, q, s, c->pairs.cfg.every);
 }
 
 // ---- flow statistics ----
@@ -928,6 +962,154 @@ SPHX_EXPORT int sphx_ctx_profile_series_read(sphx_ctx *c, int capacity, double *
     SPHX_TRY
     ProfileSeries &p = sampler_of(c, &sphx_ctx::pseries, kSeriesNames, true);
     series_read(p, c->stream, [c] { settle_owed(c); }, capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- pair statistics ----
+
+// every check of a configuration for M channels with parameters prm (cfg, n_bins, n_bands, kinds, r_max); has_walls: the
+// channel holds wall particles (without any, with_walls leaves fw at zero); SPHX:PairDist:config errors
+void PairDist::check(const sphx_params &prm, const sphx_pair_dist_config *cfg, int M, bool has_walls)
+{
+    const char *id = "SPHX:PairDist:config";
+    require(cfg != nullptr, id, "config must not be NULL");
+    require(cfg->n_bins >= 1 && cfg->n_bins <= kPairMaxBins, id, "n_bins must be 1 .. 1024");
+    require(cfg->every >= 1, id, "every must be >= 1");
+    require(!std::isnan(cfg->t_from), id, "t_from must not be NaN");
+    const double two_h = 2.0 * prm.h;
+    require(std::isfinite(cfg->r_max) && cfg->r_max >= 0.0 && cfg->r_max <= two_h, id,
+            "r_max must be 0 (= 2h) or 0 < r_max <= 2h: beyond 2h the sweep of the three cell columns is not complete");
+    require(std::isfinite(cfg->y_margin) && cfg->y_margin >= 0.0, id, "y_margin must be finite and >= 0");
+    require(cfg->with_walls == 0 || cfg->with_walls == 1, id, "with_walls must be 0 or 1");
+    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, id, "n_bands must be 0, 1 or 2");
+    for (int b = 0; b < cfg->n_bands; ++b)
+        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, id,
+                "band centres must be finite and half-widths finite and >= 0");
+    this->cfg = *cfg;
+    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
+    n_bins = cfg->n_bins;
+    n_bands = cfg->n_bands + 1;
+    kinds = cfg->with_walls && has_walls ? 2 : 1;
+    r_max = cfg->r_max > 0.0 ? cfg->r_max : two_h;
+    members = M;
+}
+
+// the checked configuration, and sums and heads for M members
+void PairDist::alloc(const PairDist &checked, int M)
+{
+    cfg = checked.cfg;
+    n_bins = checked.n_bins;
+    n_bands = checked.n_bands;
+    kinds = checked.kinds;
+    r_max = checked.r_max;
+    members = M;
+    empty.assign(block() * M, 0ull);
+    for (int m = 0; m < M; ++m)
+        for (int b = 0; b < n_bands; ++b) empty[(size_t)m * block() + counters() + n_bands + b] = kPairInfBits;
+    sums.alloc(block() * M);
+    head.alloc(M);
+}
+
+// zero counts and centres, r2_min = +inf, no sample (`empty` lives as long as the sampler, and sampler_zero, the only caller,
+// waits for the stream)
+void PairDist::zero(hipStream_t st)
+{
+    SPHX_HIP(hipMemcpyAsync(sums.get(), empty.data(), empty.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    head.zero(st);
+}
+
+// Band `band` of every member's sums (ff / fw: into out[m * stride + bin], where given; fw: zeros without a wall histogram;
+// centres[m], r2_min[m]) and the heads (n_samples[m], t_first[m], t_last[m], where given)
+void PairDist::read(hipStream_t st, int band, int stride, int64_t *ff, int64_t *fw, int64_t *centres, double *r2_min, int64_t *n_samples,
+                    double *t_first, double *t_last) const
+{
+    const int M = members;
+    std::vector<unsigned long long> host(block() * M);
+    std::vector<PairDistHead> h(M);
+    SPHX_HIP(hipMemcpyAsync(host.data(), sums.get(), host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(PairDistHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    for (int m = 0; m < M; ++m) {
+        const unsigned long long *blk = host.data() + (size_t)m * block();
+        const unsigned long long *row = blk + (size_t)band * kinds * n_bins;
+        for (int k = 0; k < n_bins; ++k) {
+            if (ff) ff[(size_t)m * stride + k] = (int64_t)row[k];
+            if (fw) fw[(size_t)m * stride + k] = kinds > 1 ? (int64_t)row[n_bins + k] : 0;
+        }
+        if (centres) centres[m] = (int64_t)blk[counters() + band];
+        if (r2_min) std::memcpy(r2_min + m, blk + counters() + n_bands + band, sizeof(double));
+        read_head(h[m], n_samples ? n_samples + m : nullptr, t_first ? t_first + m : nullptr, t_last ? t_last + m : nullptr);
+    }
+}
+
+namespace {
+
+// enable for M members of channels with parameters prm on schedule s: every check of cfg first
+void pair_dist_enable(PairDist &p, const sphx_params &prm, const sphx_pair_dist_config *cfg, int M, bool has_walls, Schedule &s, hipStream_t st)
+{
+    PairDist checked;
+    checked.check(prm, cfg, M, has_walls);
+    sampler_on(p, kPairNames, s, st, [&] { p.alloc(checked, M); });
+}
+
+// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
+template <typename Settle>
+void pair_dist_read(const PairDist &p, hipStream_t st, Settle &&settle, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw,
+                    int64_t *centres, double *r2_min, int64_t *n_samples, double *t_first, double *t_last)
+{
+    require(band >= 0 && band < p.n_bands, "SPHX:PairDist:band", "band must be 0 (whole channel) .. n_bands");
+    require((ff == nullptr && fw == nullptr) || capacity >= p.n_bins, "SPHX:PairDist:capacity", "capacity is smaller than the number of bins");
+    settle();
+    p.read(st, band, capacity, ff, fw, centres, r2_min, n_samples, t_first, t_last);
+    if (n_bins) *n_bins = p.n_bins;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_pair_dist_enable(sphx_ctx *c, const sphx_pair_dist_config *cfg)
+{
+    SPHX_TRY
+    PairDist &p = sampler_of(c, &sphx_ctx::pairs, kPairNames, false);
+    pair_dist_enable(p, c->prm, cfg, 1, c->nw > 0, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_pair_dist_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    PairDist &p = sampler_of(c, &sphx_ctx::pairs, kPairNames, false);
+    if (p.on) sampler_off(p, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_pair_dist_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    PairDist &p = sampler_of(c, &sphx_ctx::pairs, kPairNames, true);
+    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(p, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_pair_dist_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampler_of(c, &sphx_ctx::pairs, kPairNames, true);
+    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_pair_dist);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_pair_dist_read(sphx_ctx *c, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw, int64_t *centres,
+                                        double *r2_min, int64_t *n_samples, double *t_first, double *t_last)
+{
+    SPHX_TRY
+    const PairDist &p = sampler_of(c, &sphx_ctx::pairs, kPairNames, true);
+    pair_dist_read(p, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -20,7 +20,7 @@ from .geometry import init_particles
 from .mex_surface import sph_neighbor_search_mex, sph_physics_shell_mex
 from . import restart
 from .profile import (compute_mid_channel_profile, field_map_means, final_profile, flow_stats_profile, l2_error, n_profile_bins, pool_field_maps,
-                      pool_flow_stats, poiseuille_startup, profile_series_profiles)
+                      pair_dist_profiles, pool_flow_stats, pool_pair_dist, poiseuille_startup, profile_series_profiles)
 
 
 @dataclass
@@ -54,6 +54,9 @@ class RunResult:
 
     profile_series: dict = None  # run / run_sweep(..., profiles_every=...): the device-side profile series of the whole run
                                  # (capi.Context.profile_series; profile_series_figures() compares it with the start-up solution)
+
+    pair_dist: list = None  # run / run_sweep / run_ensemble(..., pairs_from=...): the device-side pair statistics of the run, one
+                            # dict per band (capi.Context.pair_dist: the integer sums with g, n_neigh, r_min; pair_dist_figures())
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -322,6 +325,44 @@ def profile_series_figures(prm, series, band=1, tol=0.02):
                 tau_exact=float(tau_exact), U_max=float(u_max), u_exact=u_exact)
 
 
+def _pair_bands(prm, bands):
+    """the x-bands of a run's pair statistics: mid-channel and the periodic seam unless given"""
+    hw = max(prm.dp, prm.h)
+    return [(0.5 * prm.DL, hw), (0.0, hw)] if bands is None else bands
+
+
+def _pair_dist_bands(sums, dp):
+    """a channel's sums, one dict per band, each with the figures of profile.pair_dist_profiles"""
+    return [dict(s, **pair_dist_profiles(s, dp)) for s in sums]
+
+
+def pair_dist_figures(prm, pd):
+    """Figures of a run's pair statistics (RunResult.pair_dist, capi.Context.pair_dist_sums(): one dict per band), on the host:
+      r_min_dp   the smallest fluid-fluid separation met, in units of dp (inf before any pair): pairing shows as r_min << dp
+      n_neigh    partners within r_max per centre, band 0
+      sigma1_dp  the width of the first shell: the standard deviation of r over the pairs with r < 1.207 dp (half way between
+                 the lattice's first and second shell, dp and sqrt(2) dp), taken from the mid-points of the bins whose mid-point
+                 lies below that, in units of dp; 0 within a bin width on a lattice, NaN without such a pair
+      seam_dev   with at least two x-bands (band 1 mid-channel, band 2 the periodic seam, the default of run()): the largest
+                 |g_seam - g_mid| over the bins, relative to the largest g of either; NaN otherwise.  A neighbour missed at the
+                 seam shows here."""
+    whole = pd[0]
+    dp = prm.dp
+    prof = [pair_dist_profiles(b, dp) for b in pd]
+    r_mid, ff = prof[0]["r_mid"], np.asarray(whole["ff"], dtype=np.float64)
+    first = r_mid < 1.207 * dp
+    n1 = ff[first].sum()
+    sigma1 = float("nan")
+    if n1 > 0:
+        mean = (ff[first] * r_mid[first]).sum() / n1
+        sigma1 = float(np.sqrt(max((ff[first] * (r_mid[first] - mean) ** 2).sum() / n1, 0.0)) / dp)
+    seam_dev = float("nan")
+    if len(pd) >= 3 and pd[1]["centres"] > 0 and pd[2]["centres"] > 0:
+        top = max(float(np.max(prof[1]["g"])), float(np.max(prof[2]["g"])))
+        seam_dev = float(np.max(np.abs(prof[2]["g"] - prof[1]["g"])) / top) if top > 0 else 0.0
+    return dict(r_min_dp=float(whole["r_min"]) / dp, n_neigh=prof[0]["n_neigh"], sigma1_dp=sigma1, seam_dev=seam_dev)
+
+
 def _concat_history(chunks):
     if not chunks:
         return capi.history_dict(np.zeros((0, len(capi.HISTORY_FIELDS))))
@@ -334,7 +375,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
         rebuild_every=0, restart_path=None, postprocess_path=None, dual_rate=0, mat_format="auto", average_from=None,
         average_every=1, history_every=None, history_capacity=65536, field_from=None, field_every=1, field_shape=None,
         field_walls=False, probe_points=None, probe_every=1, probe_capacity=65536, probe_from=None, probe_walls=False,
-        profiles_every=None, profiles_from=None, profiles_capacity=4096, profiles_bands=None):
+        profiles_every=None, profiles_from=None, profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1,
+        pairs_bins=64, pairs_walls=False, pairs_bands=None):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -368,7 +410,15 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     max(dp, h)) the output-point profiles use); the buffer (profiles_capacity records) is drained at every output point -- a
     run that lost records raises RuntimeError and names the capacity needed -- and RunResult.profile_series is the series of
     the whole run (profile_series_figures() compares it with the start-up solution).  The output-point snapshots are taken
-    as without it."""
+    as without it.
+    pairs_from (resident engine; default off): count, on the device and inside the step loop, the pair-distance histogram of
+    the fluid particles (include/sphx.h section 2l) every pairs_every-th step ending at t >= pairs_from: pairs_bins bins on
+    [0, 2h), centres at least 2h from both walls (so g(r) is a bulk figure), the whole channel and the bands pairs_bands (None:
+    mid-channel and the periodic seam, (DL/2, max(dp, h)) and (0, max(dp, h))), pairs_walls: the fluid-wall histogram too.
+    RunResult.pair_dist is one dict per band; pair_dist_figures() gives r_min, the neighbour count, the width of the first
+    shell and the seam's deviation.  A sample costs 1.6-1.9 cell sweeps of the density pass: pairs_every is the control."""
+    if pairs_from is not None and engine != "resident":
+        raise ValueError("pairs_from needs the resident engine (the pairs are counted on the device)")
     if profiles_every is not None and engine != "resident":
         raise ValueError("profiles_every needs the resident engine (the series is recorded on the device)")
     if probe_points is not None and engine != "resident":
@@ -405,6 +455,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     field_avg = None
     probes, probe_chunks = None, []
     series, series_chunks = None, []
+    pair_dist = None
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context.from_parts(prm, parts, t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
@@ -426,6 +477,9 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 ctx.profile_series_enable(n_bins=n_bins, every=profiles_every, capacity=profiles_capacity,
                                           t_from=t_start if profiles_from is None else profiles_from,
                                           bands=[(mid_x, mid_hw)] if profiles_bands is None else profiles_bands)
+            if pairs_from is not None:
+                ctx.pair_dist_enable(n_bins=pairs_bins, every=pairs_every, t_from=pairs_from, y_margin=2.0 * prm.h,
+                                     with_walls=pairs_walls, bands=_pair_bands(prm, pairs_bands))
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -471,6 +525,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 probes = _concat_probes(probe_points, prm.DL, probe_chunks)
             if profiles_every is not None:
                 series = _concat_profile_series(prm.DH, series_chunks or [ctx.profile_series_sums()])
+            if pairs_from is not None:
+                pair_dist = _pair_dist_bands(ctx.pair_dist_sums(), prm.dp)
         finally:
             ctx.close()
     elif engine == "mex":
@@ -521,7 +577,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     return _run_result(prm, nf, nt, pos, vel, t=t, steps=int(step), wall_seconds=wall, profile_times=profile_times,
                        mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t, grid_policy=policy,
                        full_profile_u=full_profiles, n_inner=n_inner, time_avg=time_avg, history=history, field_avg=field_avg,
-                       probes=probes, profile_series=series)
+                       probes=probes, profile_series=series, pair_dist=pair_dist)
 
 
 def _run_result(prm, nf, nt, pos, vel, **fields):
@@ -562,7 +618,7 @@ def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
 
 
 def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None, probe=None,
-               profiles=None):
+               profiles=None, pairs=None):
     """The batch run behind run_batch, run_ensemble and run_sweep (`name`, for the refusals): check and default the inputs,
     open the batch with the launch keywords `launch`, enable what was asked for, advance output point by output point, build
     every member's RunResult.
@@ -579,6 +635,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
       profiles   (profiles_every, profiles_from, profiles_capacity, profiles_bands): the profile series of include/sphx.h
                  section 2k, drained at every output point; every member gets its profile_series, and one that lost records
                  raises RuntimeError
+      pairs      (pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands): the pair statistics of include/sphx.h section
+                 2m with the margin and the default bands of run(); every member gets its pair_dist
     -> the members, the wall seconds, the grid policy, with average the raw sums (whole, mid) of all members, and with field the
     raw planes of all members."""
     prms = list(prms)
@@ -616,6 +674,9 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
             b.profile_series_enable(n_bins=n_bins, every=profiles[0], capacity=profiles[2],
                                     t_from=0.0 if profiles[1] is None else profiles[1],
                                     bands=[(mid_x, mid_hw)] if profiles[3] is None else profiles[3])
+        if pairs:
+            b.pair_dist_enable(n_bins=pairs[2], every=pairs[1], t_from=float(pairs[0]), y_margin=2.0 * p0.h, with_walls=pairs[3],
+                               bands=_pair_bands(p0, pairs[4]))
         t = 0.0
         st = None
         while t < p0.t_end - 1e-12:
@@ -653,6 +714,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         sums = (b.flow_stats_sums(0), b.flow_stats_sums(1)) if average else None
         planes = b.field_map_sums() if field else None
         empty_series = b.profile_series_sums() if profiles and not schunks[0] else None
+        pair_sums = b.pair_dist_sums() if pairs else None
         members = []
         for m, prm in enumerate(prms):
             extra = {}
@@ -668,8 +730,15 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                 extra.update(probes=_concat_probes(probe[0], prm.DL, pchunks[m]))
             if profiles:
                 extra.update(profile_series=_concat_profile_series(prm.DH, schunks[m] or [empty_series[m]], f"member {m}: "))
+            if pairs:
+                extra.update(pair_dist=_pair_dist_bands(pair_sums[m], prm.dp))
             members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra))
     return members, wall, policy, sums, planes
+
+
+def _pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands):
+    """the `pairs` of _run_batch: None without pairs_from"""
+    return None if pairs_from is None else (pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands)
 
 
 def _field_request(field_from, field_every, field_shape, field_walls):
@@ -707,6 +776,8 @@ class EnsembleResult:
     wall_seconds: float
     grid_policy: dict = field(default_factory=dict)
     pooled_field: dict = None  # with field_from, under the condition of `pooled`: profile.pool_field_maps of the members' planes
+    pooled_pairs: list = None  # with pairs_from, under the condition of `pooled`: profile.pool_pair_dist of the members' sums, one
+                               # dict per band, with the figures of profile.pair_dist_profiles
 
 
 _PHYSICS = ("mu", "c_f", "p0", "gravity_g", "transport_coeff")
@@ -714,14 +785,16 @@ _PHYSICS = ("mu", "c_f", "p0", "gravity_g", "transport_coeff")
 
 def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_per_particle=0, steps_per_graph=0,
                  rebuild_every=0, log=None, history_every=None, field_from=None, field_every=1, field_shape=None,
-                 field_walls=False):
+                 field_walls=False, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False, pairs_bands=None):
     """Time-averaged profiles of M channels of one geometry stepped as one batch (capi.Batch), averaged on the device
     inside the step loop (include/sphx.h section 2c) as run(average_from=...) does for one channel: every
     average_every-th step ending at t >= average_from, whole channel and the mid-channel band (DL/2, max(dp, h)).  The
     members advance output point by output point as in run_batch, so their trajectories are run_batch's; nothing is
     downloaded before the end.  parts_list: the members' initial states (e.g. geometry.perturbed_particles), default the
     lattice.  field_from: every member's velocity map as well (include/sphx.h section 2g), with the keywords of run(): every
-    member gets a field_avg, and members that share their physics a pooled_field.  Returns an EnsembleResult."""
+    member gets a field_avg, and members that share their physics a pooled_field.  pairs_from: every member's pair statistics
+    as well (include/sphx.h section 2m), with the keywords of run(): every member gets a pair_dist, and members that share their
+    physics pooled_pairs (the integers added, the smallest r_min).  Returns an EnsembleResult."""
     prms = list(prms)
     if history_every is not None:
         raise ValueError("run_ensemble records no step history (run_sweep does, for every member)")
@@ -730,9 +803,10 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
     members, wall, policy, (whole, mid), planes = _run_batch(
         "run_ensemble", prms, parts_list, dict(lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
                                                rebuild_every=rebuild_every), log, average=(average_from, average_every),
-        field=_field_request(field_from, field_every, field_shape, field_walls))
+        field=_field_request(field_from, field_every, field_shape, field_walls),
+        pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands))
     p0, M = prms[0], len(prms)
-    pooled = pooled_field = None
+    pooled = pooled_field = pooled_pairs = None
     if all(getattr(p, k) == getattr(p0, k) for p in prms for k in _PHYSICS):
         pw, pm = pool_flow_stats(p0.DH, whole), pool_flow_stats(p0.DH, mid)
         pooled = time_average(p0, pw, pm)
@@ -741,7 +815,10 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
                       L2_std=float(np.std(L2s, ddof=1)) if M > 1 else float("nan"))
         if planes is not None:
             pooled_field = pool_field_maps(p0.DL, p0.DH, planes)
-    return EnsembleResult(members=members, pooled=pooled, wall_seconds=wall, grid_policy=policy, pooled_field=pooled_field)
+        if pairs_from is not None:
+            pooled_pairs = _pair_dist_bands(pool_pair_dist([r.pair_dist for r in members]), p0.dp)
+    return EnsembleResult(members=members, pooled=pooled, wall_seconds=wall, grid_policy=policy, pooled_field=pooled_field,
+                          pooled_pairs=pooled_pairs)
 
 
 @dataclass
@@ -781,7 +858,8 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
               average_every=1, parts_list=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0, log=None,
               field_from=None, field_every=1, field_shape=None, field_walls=False, probe_points=None, probe_every=1,
               probe_capacity=65536, probe_from=None, probe_walls=False, profiles_every=None, profiles_from=None,
-              profiles_capacity=4096, profiles_bands=None):
+              profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False,
+              pairs_bands=None):
     """A parameter sweep: M channels of one geometry that differ in mu, c_f, p0, gravity_g, transport_coeff, stepped as one
     batch (capi.Batch) with every member's step history recorded on the device, inside the step loop (include/sphx.h
     section 2f) as run(history_every=...) does for one channel.  The members advance output point by output point as in
@@ -795,7 +873,10 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     field_figures(prm_m, field_avg_m).  probe_points: every member's point probes as well (include/sphx.h section 2i), with
     the keywords of run(): one set of points for all members, and each member gets its probes.  profiles_every: every member's
     profile series as well (include/sphx.h section 2k), with the keywords of run(): each member gets its profile_series and the
-    table the columns t_developed and tau_fit of profile_series_figures(prm_m, series_m).  A member that lost records to a full buffer raises RuntimeError, which names the member and the
+    table the columns t_developed and tau_fit of profile_series_figures(prm_m, series_m).  pairs_from: every member's pair
+    statistics as well (include/sphx.h section 2m), with the keywords of run(): each member gets its pair_dist and the table the
+    columns r_min_dp, n_neigh, sigma1_dp of pair_dist_figures(prm_m, pair_dist_m) -- the figures that respond to
+    transport_coeff.  A member that lost records to a full buffer raises RuntimeError, which names the member and the
     capacity the output interval needed.  Returns a SweepResult."""
     prms = list(prms)
     members, wall, policy, _, planes = _run_batch(
@@ -804,11 +885,15 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
         average=None if average_from is None else (average_from, average_every),
         field=_field_request(field_from, field_every, field_shape, field_walls),
         probe=None if probe_points is None else (probe_points, probe_every, probe_capacity, probe_from, probe_walls),
-        profiles=None if profiles_every is None else (profiles_every, profiles_from, profiles_capacity, profiles_bands))
+        profiles=None if profiles_every is None else (profiles_every, profiles_from, profiles_capacity, profiles_bands),
+        pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands))
     table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
     if planes is not None:
         table.update(field_table(prms, [r.field_avg for r in members]))
     if profiles_every is not None:
         figs = [profile_series_figures(p, r.profile_series) for p, r in zip(prms, members)]
         table.update(t_developed=np.array([f["t_developed"] for f in figs]), tau_fit=np.array([f["tau_fit"] for f in figs]))
+    if pairs_from is not None:
+        figs = [pair_dist_figures(p, r.pair_dist) for p, r in zip(prms, members)]
+        table.update({k: np.array([f[k] for f in figs]) for k in ("r_min_dp", "n_neigh", "sigma1_dp")})
     return SweepResult(members=members, table=table, wall_seconds=wall, grid_policy=policy)

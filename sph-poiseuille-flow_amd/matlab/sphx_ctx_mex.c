@@ -33,6 +33,12 @@
  *       step, t: n x 1; the five sums: n x (n_bands * n_bins), one row per recorded step, band b's bins in the columns
  *       b * n_bins + (1 .. n_bins) with band 0 the whole channel (profile series, include/sphx.h section 2j: reshape(N, n,
  *       n_bins, n_bands)); drain ~= 0 empties the device buffer
+ *   sphx_ctx_mex('pairs_enable', h, n_bins, every, t_from, r_max, y_margin, with_walls, bands)   % bands as for stats_enable
+ *   sphx_ctx_mex('pairs_disable', h)
+ *   sphx_ctx_mex('pairs_sample', h)  % add one sample of the current state now
+ *   [ff, fw, centres, r2_min, n_samples, t_first, t_last] = sphx_ctx_mex('pairs_read', h, band)
+ *       ff, fw: n_bins x 1 pair counts by distance (pair statistics, include/sphx.h section 2l), as doubles: the library's
+ *       int64 sums are exact in a double up to 2^53
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -349,6 +355,53 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 7) plhs[7] = mxCreateDoubleScalar((double)n_bins);
         if (nlhs > 8) plhs[8] = mxCreateDoubleScalar((double)n_bands);
         if (nlhs > 9) plhs[9] = mxCreateDoubleScalar((double)dropped);
+    } else if (strcmp(cmd, "pairs_enable") == 0) {
+        sphx_pair_dist_config pc;
+        const mxArray *b;
+        size_t nb, k;
+        arity(cmd, nrhs, 9, nlhs, 0);
+        b = prhs[8];
+        if (!mxIsDouble(b)) mexErrMsgIdAndTxt("SPHX:PairDist:config", "pairs_enable: bands must be a double [k x 2] array");
+        nb = mxGetNumberOfElements(b) == 0 ? 0 : mxGetM(b);
+        if (nb > 2 || (nb > 0 && mxGetN(b) != 2)) mexErrMsgIdAndTxt("SPHX:PairDist:config", "pairs_enable: bands must be [k x 2], k <= 2");
+        memset(&pc, 0, sizeof(pc));
+        pc.n_bins = (int32_t)mxGetScalar(prhs[2]);
+        pc.every = (int32_t)mxGetScalar(prhs[3]);
+        pc.t_from = mxGetScalar(prhs[4]);
+        pc.r_max = mxGetScalar(prhs[5]);
+        pc.y_margin = mxGetScalar(prhs[6]);
+        pc.with_walls = mxGetScalar(prhs[7]) != 0.0;
+        pc.n_bands = (int32_t)nb;
+        for (k = 0; k < nb; ++k) { pc.band_x[k] = mxGetDoubles(b)[k]; pc.band_hw[k] = mxGetDoubles(b)[k + nb]; }
+        ok(sphx_ctx_pair_dist_enable(handle(prhs[1]), &pc));
+    } else if (strcmp(cmd, "pairs_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_pair_dist_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "pairs_sample") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_pair_dist_sample(handle(prhs[1])));
+    } else if (strcmp(cmd, "pairs_read") == 0) {
+        sphx_ctx *c;
+        int band, n_bins = 0, k, j, rc;
+        int64_t ns = 0, centres = 0, *cnt;
+        double r2 = 0.0, t0 = 0.0, t1 = 0.0;
+        arity(cmd, nrhs, 3, nlhs, 7);
+        c = handle(prhs[1]);
+        band = (int)mxGetScalar(prhs[2]);
+        ok(sphx_ctx_pair_dist_read(c, band, 0, &n_bins, NULL, NULL, NULL, NULL, NULL, NULL, NULL));
+        cnt = (int64_t *)mxMalloc((size_t)n_bins * 2 * sizeof(int64_t));
+        rc = sphx_ctx_pair_dist_read(c, band, n_bins, NULL, cnt, cnt + n_bins, &centres, &r2, &ns, &t0, &t1);
+        if (rc != SPHX_OK) { mxFree(cnt); ok(rc); }
+        for (k = 0; k < 2 && k < (nlhs > 0 ? nlhs : 1); ++k) {
+            plhs[k] = mxCreateDoubleMatrix((mwSize)n_bins, 1, mxREAL);
+            for (j = 0; j < n_bins; ++j) mxGetDoubles(plhs[k])[j] = (double)cnt[(size_t)k * n_bins + j];
+        }
+        mxFree(cnt);
+        if (nlhs > 2) plhs[2] = mxCreateDoubleScalar((double)centres);
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar(r2);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)ns);
+        if (nlhs > 5) plhs[5] = mxCreateDoubleScalar(t0);
+        if (nlhs > 6) plhs[6] = mxCreateDoubleScalar(t1);
     } else if (strcmp(cmd, "destroy") == 0) {
         arity(cmd, nrhs, 2, nlhs, 0);
         sphx_ctx_destroy(handle(prhs[1]));

@@ -8,6 +8,8 @@ shepard_field: one sample of the device's field map (include/sphx.h section 2e) 
 pool_field_maps: the planes of several channels (the members of a batch, section 2g) as one ensemble-averaged map.
 poiseuille_startup: the series solution of the start-up of plane Poiseuille flow from rest; profile_series_profiles: the
 records of the device's profile series (include/sphx.h section 2j) as one profile per record.
+pair_histogram: one sample of the device's pair statistics (include/sphx.h section 2l) in numpy, count for count;
+pair_dist_profiles: its sums as g(r), the neighbour count and r_min; pool_pair_dist: the sums of several channels as one.
 """
 from __future__ import annotations
 
@@ -285,4 +287,136 @@ def pool_field_maps(DL, DH, sums_list):
         ok = ~np.any(np.isnan(means), axis=0)
         se[ok] = np.std(means[:, ok], axis=0, ddof=1) / np.sqrt(M)
     out.update(u_x_se=se, n_members=M)
+    return out
+
+
+# ---- pair statistics (include/sphx.h sections 2l, 2m) ----
+
+def pair_edges(r_max, n_bins):
+    """(r_edges, e2): the n_bins + 1 bin edges in r and the squared edges the comparisons use: e2[k] = (k * (r_max / n_bins))^2
+    for k < n_bins, e2[n_bins] = r_max * r_max."""
+    e = np.arange(n_bins, dtype=np.float64) * (r_max / n_bins)
+    return np.append(e, r_max), np.append(e * e, r_max * r_max)
+
+
+def in_band(x, DL, x_centre, half_width):
+    """compute_mid_channel_profile's membership (stats_in_band on the device)."""
+    d = np.abs(np.mod(x, DL) - x_centre)
+    return np.minimum(d, DL - d) <= half_width
+
+
+def pair_separations(pos, DL, r_max, wall_pos=None, chunk=512):
+    """Every ordered pair (i, j != i) of the fluid particles pos [n, 2] with r2 < r_max^2, and every (fluid i, wall j) pair of
+    wall_pos: dict(i_ff, r2_ff, i_fw, r2_fw), i the centre's index.  dx = x_i - x_j folded by the minimum image (dx > DL/2 ->
+    dx - DL, dx < -DL/2 -> dx + DL), dy = y_i - y_j, r2 = dx*dx + dy*dy: the doubles the device computes.  Chunked over centres
+    sorted by x; a chunk meets only the partners whose x lies within r_max of its own range (a superset: the exact test is r2)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    rmax2 = r_max * r_max
+    half = DL / 2
+    margin = r_max * (1.0 + 1e-9) + 1e-12 * DL
+
+    def sweep(partners, same):
+        px = np.mod(partners[:, 0], DL)
+        order_p = np.argsort(px, kind="stable")
+        pxs = px[order_p]
+        cx = np.mod(pos[:, 0], DL)
+        order_c = np.argsort(cx, kind="stable")
+        out_i, out_r2 = [], []
+        for a in range(0, len(order_c), chunk):
+            ci = order_c[a:a + chunk]
+            lo, hi = cx[ci[0]] - margin, cx[ci[-1]] + margin
+            if hi - lo >= DL:
+                cand = order_p
+            else:
+                parts = [order_p[np.searchsorted(pxs, lo, "left"):np.searchsorted(pxs, hi, "right")]]
+                if lo < 0.0:
+                    parts.append(order_p[np.searchsorted(pxs, lo + DL, "left"):])
+                if hi > DL:
+                    parts.append(order_p[:np.searchsorted(pxs, hi - DL, "right")])
+                cand = np.unique(np.concatenate(parts))
+            dx = pos[ci, 0][:, None] - partners[cand, 0][None, :]
+            dx = np.where(dx > half, dx - DL, np.where(dx < -half, dx + DL, dx))
+            dy = pos[ci, 1][:, None] - partners[cand, 1][None, :]
+            r2 = dx * dx + dy * dy
+            keep = r2 < rmax2
+            if same:
+                keep &= ci[:, None] != cand[None, :]
+            rows, cols = np.nonzero(keep)
+            out_i.append(ci[rows])
+            out_r2.append(r2[rows, cols])
+        if not out_i:
+            return np.zeros(0, dtype=np.int64), np.zeros(0)
+        return np.concatenate(out_i).astype(np.int64), np.concatenate(out_r2)
+
+    i_ff, r2_ff = sweep(pos, True)
+    if wall_pos is not None and len(wall_pos):
+        i_fw, r2_fw = sweep(np.asarray(wall_pos, dtype=np.float64), False)
+    else:
+        i_fw, r2_fw = np.zeros(0, dtype=np.int64), np.zeros(0)
+    return dict(i_ff=i_ff, r2_ff=r2_ff, i_fw=i_fw, r2_fw=r2_fw, r_max=float(r_max))
+
+
+def pair_histogram(pos, DL, DH, r_max, n_bins, bands=(), y_margin=0.0, wall_pos=None, separations=None):
+    """One sample of the pair statistics of include/sphx.h section 2l in numpy -- the oracle of k_pair_dist.  pos [n, 2]: the
+    fluid particles; bands: [(x_centre, half_width), ...]; wall_pos: the wall particles, or None for no wall histogram.  -> one
+    dict per band (band 0: the whole channel): r_edges [n_bins + 1], ff, fw [n_bins] (int64; ordered pairs, a pair of two
+    centres counts twice), centres, r2_min (the smallest counted fluid-fluid r2, +inf without a pair) and r_min = sqrt(r2_min).
+    Bin k holds e2[k] <= r2 < e2[k+1] (pair_edges): searchsorted(e2, r2, side="right") - 1; r2 >= r_max^2 is not counted.
+    separations: pair_separations(pos, DL, R, wall_pos) of an R >= r_max, to share the pair search between calls."""
+    pos = np.asarray(pos, dtype=np.float64)
+    r_edges, e2 = pair_edges(r_max, n_bins)
+    sep = separations if separations is not None else pair_separations(pos, DL, r_max, wall_pos)
+    assert sep["r_max"] >= r_max
+    centre = (pos[:, 1] >= y_margin) & (pos[:, 1] <= DH - y_margin)
+    members = [centre] + [centre & in_band(pos[:, 0], DL, x, hw) for x, hw in bands]
+    out = []
+    for mine in members:
+        d = dict(r_edges=r_edges, centres=int(np.count_nonzero(mine)))
+        for kind in ("ff", "fw"):
+            i, r2 = sep["i_" + kind], sep["r2_" + kind]
+            if wall_pos is None and kind == "fw":
+                i, r2 = i[:0], r2[:0]
+            take = mine[i] & (r2 < e2[-1])
+            k = np.searchsorted(e2, r2[take], side="right") - 1
+            d[kind] = np.bincount(k, minlength=n_bins).astype(np.int64)
+            if kind == "ff":
+                d["r2_min"] = float(np.min(r2[take])) if np.any(take) else np.inf
+        d["r_min"] = float(np.sqrt(d["r2_min"]))
+        out.append(d)
+    return out
+
+
+def pair_dist_profiles(sums, dp):
+    """The sums of one band (capi.Context.pair_dist_sums()[band], pair_histogram(...)[band]) as figures: r_mid, the radial
+    distribution function g = ff / (centres * pi (e_{k+1}^2 - e_k^2) / dp^2) -- ordered pairs per centre over the particles an
+    ideal lattice of spacing dp puts into the ring --, g_wall the same of fw, n_neigh = sum(ff) / centres and r_min; NaN without
+    a centre."""
+    e = np.asarray(sums["r_edges"], dtype=np.float64)
+    ff, fw = np.asarray(sums["ff"], dtype=np.float64), np.asarray(sums["fw"], dtype=np.float64)
+    c = float(sums["centres"])
+    ring = np.pi * (e[1:] ** 2 - e[:-1] ** 2) / (dp * dp)
+    norm = c * ring if c > 0 else np.full(len(ff), np.nan)
+    return dict(r_mid=0.5 * (e[:-1] + e[1:]), g=ff / norm, g_wall=fw / norm, n_neigh=float(ff.sum() / c) if c > 0 else float("nan"),
+                r_min=float(sums["r_min"]))
+
+
+def pool_pair_dist(sums_list):
+    """The sums of the same band of several channels (the members of a batch or of an ensemble) as one: the integers added,
+    the smallest r_min, all samples (n_samples added, the window from the first t_first to the last t_last).  A list of lists
+    (one list of bands per channel, what capi.Batch.pair_dist_sums returns) is pooled band by band."""
+    sums_list = list(sums_list)
+    assert sums_list, "nothing to pool"
+    if isinstance(sums_list[0], (list, tuple)):
+        return [pool_pair_dist([s[b] for s in sums_list]) for b in range(len(sums_list[0]))]
+    first = sums_list[0]
+    assert all(np.array_equal(s["r_edges"], first["r_edges"]) for s in sums_list), "the channels have different bins"
+    r2 = min(float(s["r2_min"]) for s in sums_list)
+    out = dict(r_edges=np.asarray(first["r_edges"]), ff=sum(np.asarray(s["ff"], dtype=np.int64) for s in sums_list),
+               fw=sum(np.asarray(s["fw"], dtype=np.int64) for s in sums_list), centres=int(sum(int(s["centres"]) for s in sums_list)),
+               r2_min=r2, r_min=float(np.sqrt(r2)))
+    if all("n_samples" in s for s in sums_list):
+        sampled = [s for s in sums_list if s["n_samples"] > 0]
+        out.update(n_samples=int(sum(s["n_samples"] for s in sums_list)),
+                   t_first=min((s["t_first"] for s in sampled), default=float("nan")),
+                   t_last=max((s["t_last"] for s in sampled), default=float("nan")))
     return out
