@@ -798,8 +798,8 @@ int sphx_batch_profile_series_read(sphx_batch *batch, int capacity, double *time
  *    centre or half-width that is not finite or a negative half-width, or the allocation fails: the context
  *    then goes on without pair statistics), SPHX:PairDist:band, SPHX:PairDist:capacity (ff or fw given and capacity <
  *    n_bins), SPHX:PairDist:disabled (SPHX_ERR_STATE: a call that needs the sampler while it is off); every call on a slab
- *    context fails with SPHX_ERR_ARG, SPHX:PairDist:slab (slab rings have no pair statistics).  A refused enable leaves a
- *    running sampler, and its sums, untouched.
+ *    context fails with SPHX_ERR_ARG, SPHX:PairDist:slab (the pair statistics of a ring: sphx_slab_pairs_*, section 3a).  A
+ *    refused enable leaves a running sampler, and its sums, untouched.
  * ---------------------------------------------------------------------------------------------- */
 
 #define SPHX_PAIR_DIST_MAX_BINS 1024
@@ -925,8 +925,8 @@ int sphx_slab_snapshot(sphx_ctx *ctx, int capacity, int *n, double *x, double *y
 
 /* ------------------------------------------------------------------------------------------------
  * 3a. Samplers of a slab ring: the flow statistics of section 2a, the step history of section 2d, the velocity-field
- *    map of section 2e, the point probes of section 2h and the profile series of section 2j (the last two described with
- *    their three calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that
+ *    map of section 2e, the point probes of section 2h, the profile series of section 2j and the pair statistics of
+ *    section 2l (the last three described with their calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that
  *    a ring reports its time-averaged profile, the settling of its wall shear, its averaged field and its profile at every
  *    sampled step without a snapshot per sample.  The config structs, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* / SPHX:Field:*
  *    identifiers are those of sections 2a / 2d / 2e; sphx_ctx_flow_stats_*,
@@ -1029,6 +1029,30 @@ int sphx_slab_pseries_disable(sphx_ctx *ctx);
  * shape and the counts. */
 int sphx_slab_pseries_read(sphx_ctx *ctx, int capacity, double *times, double *records, int *n_bins, int *n_bands,
                            int *n_records, int64_t *n_dropped, int drain);
+/* Pair statistics of a ring (the sampler of section 2l; k_pair_dist_s).  The names say pairs: no function of this header has
+ * both "slab" and "pair_dist" in its name.  The config, its checks and limits, the bins, the gating and the SPHX:PairDist:*
+ * identifiers are those of section 2l.  A sample is a sum over centres, so it is divided like the flow statistics': a slab
+ * counts, at the end of a sampled step, the pairs whose CENTRE it owns (a fluid particle sphx_slab_snapshot marks owned, with
+ * y_margin <= y <= DH - y_margin), and what a read returns are the slab's PARTIAL sums -- the ring's ff, fw and centres are
+ * the element-wise sums over the ranks, its r2_min the minimum over the ranks; n_samples, t_first and t_last come from the
+ * clock and are the same on every rank, also on a slab that owns no centre of a band.  The PARTNERS of a centre are all the
+ * other fluid particles the slab holds, its halo copies included -- they carry the finished step's positions in the cell
+ * columns next to the owned ones, up to the summation order of their own neighbour lists, a few ulps of x -- and, with
+ * with_walls, the wall particles the slab holds.  The slab's window is open: the first slab holds the last slab's particles
+ * at x - DL and the last slab the first slab's at x + DL, so a pair across the periodic seam is counted with its plain dx and
+ * no minimum image; a ring is at least 20h long, so no copy is a centre's own image within r_max <= 2h.  Band membership
+ * goes by x mod DL, whatever frame a slab keeps x in.  Integers and a minimum: the ring's sums do not depend on how the
+ * channel is cut, and where no pair lies within a rounding of a bin edge they are a single context's count for count.  A
+ * refused enable leaves a running sampler, its sums and a prepared graph as they are.  SPHX:PairDist:disabled: a reset or a
+ * read while the sampler is off; disable is a no-op then.  There is no "sample now" call.  sphx_ctx_pair_dist_* keep refusing
+ * a slab (SPHX:PairDist:slab). */
+int sphx_slab_pairs_enable(sphx_ctx *ctx, const sphx_pair_dist_config *cfg);
+int sphx_slab_pairs_disable(sphx_ctx *ctx);
+/* Clears the sums and the sample count; the configuration stays. */
+int sphx_slab_pairs_reset(sphx_ctx *ctx);
+/* The slab's partial sums of one band; arguments as sphx_ctx_pair_dist_read. */
+int sphx_slab_pairs_read(sphx_ctx *ctx, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw, int64_t *centres,
+                         double *r2_min, int64_t *n_samples, double *t_first, double *t_last);
 
 #ifdef __cplusplus
 }

@@ -114,6 +114,7 @@ EXPORTS = [
     "sphx_slab_field_map_enable", "sphx_slab_field_map_disable", "sphx_slab_field_map_reset", "sphx_slab_field_map_read",
     "sphx_slab_probes_enable", "sphx_slab_probes_disable", "sphx_slab_probes_read",
     "sphx_slab_pseries_enable", "sphx_slab_pseries_disable", "sphx_slab_pseries_read",
+    "sphx_slab_pairs_enable", "sphx_slab_pairs_disable", "sphx_slab_pairs_reset", "sphx_slab_pairs_read",
     "sphx_batch_create", "sphx_batch_destroy", "sphx_batch_advance", "sphx_batch_enqueue_steps", "sphx_batch_sync",
     "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
     "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",
@@ -223,12 +224,14 @@ _STATE = ("pos", "vel", "drho_dt", "mass", "wall_vel")
 
 
 class _Sampled:
-    """What a context, a batch and a slab of a ring bind alike: the flow statistics' sums, the step history's records and the
-    profile series' raw records.  A subclass names its symbol stem, the word its profile-series calls carry behind the stem
-    (a slab's are sphx_slab_pseries_*), the word of its "not enabled on this ..." errors and whether it has many channels: a
-    context or a slab returns one dict / (records, n_dropped) pair, a batch a list with one entry per member."""
+    """What a context, a batch and a slab of a ring bind alike: the flow statistics' sums, the step history's records, the
+    profile series' raw records and the pair statistics' sums.  A subclass names its symbol stem, the words its profile-series
+    and pair-statistics calls carry behind the stem (a slab's are sphx_slab_pseries_* and sphx_slab_pairs_*), the word of its
+    "not enabled on this ..." errors and whether it has many channels: a context or a slab returns one dict / (records,
+    n_dropped) pair, a batch a list with one entry per member."""
     _stem = _where = None
     _series = "profile_series_"
+    _pairs = "pair_dist_"
     _many = False
 
     def _call(self, name, *args):
@@ -356,6 +359,49 @@ class _Sampled:
         assert np.array_equal(n, want), (n, want)
         DH = self._params0().DH
         return self._each([profile_series_dict(DH, times[k, :n[k]], records[k, :n[k]], int(dropped[k])) for k in range(m)])
+
+    # ---- pair statistics (include/sphx.h sections 2l, 2m, 3a): what pair_dist_* of a context or a batch and pairs_part_* of a
+    # slab (slab.HipSlabEngine) share -- the argument checks, the calls behind the stem and the read of the integer sums ----
+    def _pairs_enable(self, n_bins, every, t_from, r_max, y_margin, with_walls, bands):
+        p0 = self._params0()
+        cfg = pair_dist_config(p0, n_bins, every, t_from, r_max, y_margin, with_walls, bands)
+        self._call(self._pairs + "enable", C.byref(cfg))
+        # (n_bins, n_bands incl. band 0, r_max in force) while the pair statistics are on
+        self._pair_dist = (int(cfg.n_bins), int(cfg.n_bands) + 1, float(cfg.r_max) or 2.0 * p0.h)
+
+    def _pairs_disable(self):
+        self._call(self._pairs + "disable")
+        self._pair_dist = None
+
+    def _pairs_on(self):
+        return _enabled(self._pair_dist, "PairDist", f"pair statistics are not enabled on this {self._where}")
+
+    def _pairs_reset(self):
+        self._pairs_on()
+        self._call(self._pairs + "reset")
+
+    def _pair_dist_band(self, band):
+        n_bins, n_bands, r_max = self._pairs_on()
+        if not _is_int(band) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:PairDist:band", f"band must be an integer in 0..{n_bands - 1}")
+        m = self._channels()
+        ff, fw = np.zeros((m, n_bins), dtype=np.int64), np.zeros((m, n_bins), dtype=np.int64)
+        centres, ns = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+        r2, t0, t1 = np.zeros(m), np.zeros(m), np.zeros(m)
+        nb = C.c_int(0)
+        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        self._call(self._pairs + "read", C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), i64(ff), i64(fw), i64(centres), ptr(r2), i64(ns),
+                   ptr(t0), ptr(t1))
+        assert nb.value == n_bins, (nb.value, n_bins)
+        r_edges = pair_edges(r_max, n_bins)[0]
+        return [dict(r_edges=r_edges, ff=ff[k].copy(), fw=fw[k].copy(), centres=int(centres[k]), r2_min=float(r2[k]),
+                     r_min=float(np.sqrt(r2[k])), n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k])) for k in range(m)]
+
+    def _pair_dist_bands(self):
+        """every band's sums: one list of band dicts per channel (a context or a slab: the list itself)"""
+        n_bands = self._pairs_on()[1]
+        per_band = [self._pair_dist_band(b) for b in range(n_bands)]
+        return self._each([[per_band[b][k] for b in range(n_bands)] for k in range(self._channels())])
 
 
 class _Stepped(_Sampled):
@@ -544,51 +590,23 @@ class _Stepped(_Sampled):
         (fluid partners), with_walls: fw (wall partners), for the whole channel (band 0) and for the centres in up to two
         x-bands [(x_centre, half_width), ...].  Integer sums: exact, profile.pair_histogram gives the same counts.
         (Re)configures and zeroes the sums.  A batch: one config for all members, each sampled on its own clock."""
-        p0 = self._params0()
-        cfg = pair_dist_config(p0, n_bins, every, t_from, r_max, y_margin, with_walls, bands)
-        self._call("pair_dist_enable", C.byref(cfg))
-        # (n_bins, n_bands incl. band 0, r_max in force) while the pair statistics are on
-        self._pair_dist = (int(cfg.n_bins), int(cfg.n_bands) + 1, float(cfg.r_max) or 2.0 * p0.h)
+        self._pairs_enable(n_bins, every, t_from, r_max, y_margin, with_walls, bands)
 
     def pair_dist_disable(self):
-        self._call("pair_dist_disable")
-        self._pair_dist = None
-
-    def _pairs_on(self):
-        return _enabled(self._pair_dist, "PairDist", f"pair statistics are not enabled on this {self._where}")
+        self._pairs_disable()
 
     def pair_dist_reset(self):
-        self._pairs_on()
-        self._call("pair_dist_reset")
+        self._pairs_reset()
 
     def pair_dist_sample(self):
         """Add one sample of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
         self._pairs_on()
         self._call("pair_dist_sample")
 
-    def _pair_dist_band(self, band):
-        n_bins, n_bands, r_max = self._pairs_on()
-        if not _is_int(band) or not 0 <= band < n_bands:
-            raise SphxError(SPHX_ERR_ARG, "SPHX:PairDist:band", f"band must be an integer in 0..{n_bands - 1}")
-        m = self._channels()
-        ff, fw = np.zeros((m, n_bins), dtype=np.int64), np.zeros((m, n_bins), dtype=np.int64)
-        centres, ns = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
-        r2, t0, t1 = np.zeros(m), np.zeros(m), np.zeros(m)
-        nb = C.c_int(0)
-        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-        self._call("pair_dist_read", C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), i64(ff), i64(fw), i64(centres), ptr(r2), i64(ns),
-                   ptr(t0), ptr(t1))
-        assert nb.value == n_bins, (nb.value, n_bins)
-        r_edges = pair_edges(r_max, n_bins)[0]
-        return [dict(r_edges=r_edges, ff=ff[k].copy(), fw=fw[k].copy(), centres=int(centres[k]), r2_min=float(r2[k]),
-                     r_min=float(np.sqrt(r2[k])), n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k])) for k in range(m)]
-
     def pair_dist_sums(self):
         """The raw sums so far, one dict per band (band 0: the whole channel): r_edges [n_bins + 1], ff, fw [n_bins] (int64),
         centres, r2_min, r_min (+inf before any pair), n_samples, t_first, t_last.  A batch: one such list per member."""
-        n_bands = self._pairs_on()[1]
-        per_band = [self._pair_dist_band(b) for b in range(n_bands)]
-        return self._each([[per_band[b][k] for b in range(n_bands)] for k in range(self._channels())])
+        return self._pair_dist_bands()
 
     def pair_dist(self, band=0):
         """One band's sums with the figures of profile.pair_dist_profiles: r_mid, g, g_wall, n_neigh, r_min.  A batch: one such

@@ -1,5 +1,5 @@
-// sphx_pair_dist.hpp -- pair-distance statistics of a resident context (include/sphx.h section 2l) and of every member of a
-// batch (section 2m, k_pair_dist_b): a slot sampler (sphx_slot_sample.hpp) that counts, for the fluid particles of a band (the
+// sphx_pair_dist.hpp -- pair-distance statistics of a resident context (include/sphx.h section 2l), of every member of a
+// batch (section 2m, k_pair_dist_b) and of a slab of a ring (section 3a, k_pair_dist_s, at the end): a slot sampler (sphx_slot_sample.hpp) that counts, for the fluid particles of a band (the
 // CENTRES), their partners within r_max by distance: the histogram behind g(r), the mean neighbour count, the width of the
 // first shell and the smallest separation.  The one sampler that describes the particle ARRANGEMENT, not the velocity field,
 // and the one whose result is exact: integer counts and a minimum, reproduced count for count by profile.pair_histogram.
@@ -130,6 +130,9 @@ __device__ __forceinline__ void pair_add(const Grid &g, const PairDistArgs &a, u
 
 // The sample of one channel closing the step slot of parity q, on clock clk, by the gridDim.x workgroups of a grid row; s is the
 // state the step left (pos and the cell ranges and binned cells of the layout it is stored in); sums / h are that channel's own.
+// kSlab: the channel is a slab of a ring -- of the clk->n slots it holds only those it owns (owns()) are centres, every held
+// slot is a partner (k_pair_dist_s).
+template <bool kSlab = false>
 __device__ __forceinline__ void pair_dist_body(const Clock *clk, int q, const Grid &g, const FluidSet &s, const Walls &w, const PairDistArgs &a,
                                                unsigned long long *sums, PairDistHead *h)
 {
@@ -149,6 +152,9 @@ __device__ __forceinline__ void pair_dist_body(const Clock *clk, int q, const Gr
     for (long long i0 = (long long)blockIdx.x * kPairCentres + grp; i0 < (long long)n; i0 += (long long)gridDim.x * kPairCentres) {
         const int i = (int)i0;
         const double2 pi = s.pos[i];
+        if constexpr (kSlab) {
+            if (!owns(g, pi.x, s.cell[i])) continue;  // (a halo copy: its owner counts it as a centre)
+        }
         if (!(pi.y >= a.y_lo && pi.y <= a.y_hi)) continue;
         unsigned bands = 1u;
         for (int b = 1; b < a.n_bands; ++b)
@@ -214,6 +220,36 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_dist_b(Members mb, int q, G
 {
     const int m = (int)blockIdx.y;
     pair_dist_body(mb.clk + m, q, g, member_set(mb, m, s), w, a, a.sums + (size_t)m * (size_t)a.block, a.head + m);
+}
+
+// Slab of a ring (sphx_slab_pairs_*): the sample is a sum over CENTRES, so it is divided like the flow statistics' -- a slab
+// counts the pairs whose centre it OWNS (owns(): the column the slot was binned into, own_c0 <= cx < own_c1), the ring's
+// histogram is the element-wise sum of the slabs' and its r2_min their minimum; integers and a minimum, so the ring's sums do
+// not depend on how the channel is cut.  The loop runs over the clk->n slots held, owned and copies alike, with the
+// workgroups of the slab's CAPACITY (a captured step graph outlives a re-binning); a copy is passed over as a centre and
+// met as a partner: every held fluid slot j != i in the columns cx - 1 .. cx + 1 of the layout's cell ranges, and with walls
+// the slab's wall particles in the same columns.
+//
+// Why the three-column sweep still suffices.  The argument above is about the columns a centre and its partner were BINNED
+// into, and a slab bins what it holds, copies included, into one grid of its window (Grid::periodic = 0: neighbour_column
+// leaves out only columns beyond the window).  An owned centre has own_c0 <= cx < own_c1, so cx - 1 and cx + 1 lie in
+// [own_c0 - 1, own_c1]: at most the FIRST halo column on either side, and the window holds halo_cols >= 4 of them.  The halo
+// premise is that the copies binned in own - 1 and own + 1 are complete and carry the finished step's
+// position in front of phase 3, up to the summation order of their own neighbour lists: what the field map and the probes
+// of a slab rely on.  Only pos, cell and start are read.
+//
+// The window is open (half_DL = +inf: min_image is a no-op).  The first slab holds the last slab's particles at x - DL and the
+// last slab the first slab's at x + DL, in the slab's own frame, so a pair across the periodic seam has its plain dx: there
+// is nothing to fold.  A copy can never be the centre's own image within r_max <= 2h: the image lies DL away, and a ring
+// needs n_ranks >= 2 slabs of at least halo_cols + 1 >= 5 columns of >= 2h each (SPHX:Slab:width), so DL >= 20h; nor can one
+// window hold a partner twice, because it covers less than one period (SPHX:Slab:width).  Band membership goes by
+// stats_in_band on the slab-frame x, whose fmod brings x < 0 and x >= DL back into [0, DL), as k_flow_stats_s relies on.
+//
+// The head is noted by thread 0 of workgroup 0 of every slab, whether or not the slab owns a centre of any band: n_samples,
+// t_first and t_last come from the clock and agree between the ranks.
+__global__ __launch_bounds__(kPairBlock) void k_pair_dist_s(const Clock *clk, int q, Grid g, FluidSet s, Walls w, PairDistArgs a)
+{
+    pair_dist_body<true>(clk, q, g, s, w, a, a.sums, a.head);
 }
 
 }  // namespace sphx

@@ -1,7 +1,7 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
-// the velocity-field map (2e; 2g), the point probes (2h; 2i) and the profile series (2j; 2k) -- all five also of a slab of a
-// ring (3a, at the end of this file) -- and the pair statistics (2l; 2m, sphx_pair_dist.hpp).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// the velocity-field map (2e; 2g), the point probes (2h; 2i), the profile series (2j; 2k) and the pair statistics (2l; 2m,
+// sphx_pair_dist.hpp) -- all six also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -29,7 +29,8 @@ constexpr SamplerNames kProbeNames{"Probe", "point probes are not available on s
 constexpr SamplerNames kSeriesNames{"ProfileSeries", "the profile series of a slab is sphx_slab_pseries_* (include/sphx.h section 3a)",
                                     "the profile series is not enabled on this ", "the record buffer could not be set up: "};
 
-constexpr SamplerNames kPairNames{"PairDist", "pair statistics are not available on slab contexts", "pair statistics are not enabled on this ",
+constexpr SamplerNames kPairNames{"PairDist", "the pair statistics of a slab are sphx_slab_pairs_* (include/sphx.h section 3a)",
+                                  "pair statistics are not enabled on this ",
                                   "the sums could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
@@ -1127,6 +1128,10 @@ SPHX_EXPORT int sphx_ctx_pair_dist_read(sphx_ctx *c, int band, int capacity, int
 // The profile series: the flow statistics' reasoning -- a record is the slab's PARTIAL sample over the particles it owns, exact
 // integers converted once, and the ring's record is the slabs' records added up field by field (sphx_slab_pseries_*: no
 // function of include/sphx.h carries both "slab" and "profile_series" in its name).
+// The pair statistics: a sample is a sum over CENTRES, so the flow statistics' reasoning holds for the centres -- a slab counts
+// the pairs whose centre it owns, against every slot it holds, halo copies included (the field map's premise for the
+// partners), and the ring's histogram is the slabs' added up, its r2_min their minimum (sphx_slab_pairs_*: no function of
+// include/sphx.h carries both "slab" and "pair_dist" in its name).
 
 namespace {
 
@@ -1134,11 +1139,11 @@ namespace {
 // later) and in front of everything of phase 3: the clock is the finished step's, S[1-q] holds the owned particles' new state,
 // Vol / B (c->tmp) and the layout arrays (cell, mass) are those of the layout the step ran in -- clk->n is still that
 // layout's count (k_slab_unpack3 sets the new one), so a re-binning step needs no src_of.  One self-skipping launch each,
-// on the slab's stream, in the order statistics, history, map, probes, profile series; all off: nothing is enqueued, and a
-// sampler that is off adds nothing to what the others enqueue.
+// on the slab's stream, in the order statistics, history, map, probes, profile series, pair statistics; all off: nothing is
+// enqueued, and a sampler that is off adds nothing to what the others enqueue.
 void launch_slab_samplers(sphx_ctx *c)
 {
-    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on && !c->pseries.on) return;
+    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on && !c->pseries.on && !c->pairs.on) return;
     const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
     const FluidSet s = c->view(1 - q, 0);
@@ -1173,6 +1178,12 @@ void launch_slab_samplers(sphx_ctx *c)
     if (c->pseries.on)
         launch_s(c, "k_profile_series_s", k_profile_series_s, dim3(flow_stats_blocks((size_t)c->cap)), dim3(kStatsBlock), c->pseries.shmem(),
                  clk, q, profile_series_args(c, s, c->pseries.cfg.every), c->grid, (const int *)s.cell);
+    // (pos, the binned cells and the cell ranges of S[1-q], the halo copies in own - 1 and own + 1 as for the map; the centres
+    //  are the owned slots of the clk->n held, so the workgroups come from the capacity; `kinds` was settled at enable from the
+    //  slab's own wall particles)
+    if (c->pairs.on)
+        launch_s(c, "k_pair_dist_s", k_pair_dist_s, dim3(pair_dist_blocks((size_t)c->cap)), dim3(kPairBlock), c->pairs.shmem(), clk, q,
+                 c->grid, s, c->walls, pair_dist_args(c, c->pairs.cfg.every));
 }
 
 // The rank of slab c's ring that owns a probe at x, folded into [0, DL): rank r when edge(r) <= x < edge(r + 1), with
@@ -1450,6 +1461,50 @@ SPHX_EXPORT int sphx_slab_pseries_read(sphx_ctx *c, int capacity, double *times,
     SPHX_TRY
     ProfileSeries &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::pseries, kSeriesNames);
     series_read(p, c->stream, [c] { slab_settle(c); }, capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_pairs_enable(sphx_ctx *c, const sphx_pair_dist_config *cfg)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    PairDist checked;
+    checked.check(c->prm, cfg, 1, c->walls.n > 0);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
+    slab_samplers_changed(c);
+    pair_dist_enable(c->pairs, c->prm, cfg, 1, c->walls.n > 0, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_pairs_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    if (c->pairs.on) {
+        slab_samplers_changed(c);
+        sampler_off(c->pairs, c->sched, c->stream);
+    }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_pairs_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    PairDist &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::pairs, kPairNames);
+    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(p, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_pairs_read(sphx_ctx *c, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw, int64_t *centres,
+                                     double *r2_min, int64_t *n_samples, double *t_first, double *t_last)
+{
+    SPHX_TRY
+    const PairDist &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::pairs, kPairNames);
+    pair_dist_read(p, c->stream, [c] { slab_settle(c); }, band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }

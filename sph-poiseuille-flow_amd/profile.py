@@ -9,7 +9,8 @@ pool_field_maps: the planes of several channels (the members of a batch, section
 poiseuille_startup: the series solution of the start-up of plane Poiseuille flow from rest; profile_series_profiles: the
 records of the device's profile series (include/sphx.h section 2j) as one profile per record.
 pair_histogram: one sample of the device's pair statistics (include/sphx.h section 2l) in numpy, count for count;
-pair_dist_profiles: its sums as g(r), the neighbour count and r_min; pool_pair_dist: the sums of several channels as one.
+pair_dist_profiles: its sums as g(r), the neighbour count and r_min; pool_pair_dist: the sums of several channels as one;
+pair_histogram_part: the sample of one slab of a ring (the centres it owns against everything it holds).
 """
 from __future__ import annotations
 
@@ -377,6 +378,52 @@ def pair_histogram(pos, DL, DH, r_max, n_bins, bands=(), y_margin=0.0, wall_pos=
             if wall_pos is None and kind == "fw":
                 i, r2 = i[:0], r2[:0]
             take = mine[i] & (r2 < e2[-1])
+            k = np.searchsorted(e2, r2[take], side="right") - 1
+            d[kind] = np.bincount(k, minlength=n_bins).astype(np.int64)
+            if kind == "ff":
+                d["r2_min"] = float(np.min(r2[take])) if np.any(take) else np.inf
+        d["r_min"] = float(np.sqrt(d["r2_min"]))
+        out.append(d)
+    return out
+
+
+def pair_histogram_part(pos, owned, DL, DH, r_max, n_bins, bands=(), y_margin=0.0, wall_pos=None):
+    """One sample of a SLAB's pair statistics (include/sphx.h section 3a) in numpy -- the oracle of k_pair_dist_s.  pos [n, 2]:
+    every fluid particle the slab holds, in the slab's own frame (its halo copies at x - DL or x + DL where they come from
+    across the seam); owned [n] bool: the rows it owns.  The CENTRES are the owned rows with y_margin <= y <= DH - y_margin,
+    the PARTNERS all the other rows and, with wall_pos, the wall particles the slab holds; dx = x_i - x_j as it stands, with no
+    fold: the window is open.  Bands go by in_band, whose mod brings x < 0 and x >= DL back.  -> pair_histogram's list of dicts,
+    the slab's partial sums: slab.pool_ring_pair_dist of the ranks' gives the channel's."""
+    pos = np.asarray(pos, dtype=np.float64)
+    own = np.flatnonzero(np.asarray(owned, dtype=bool))
+    r_edges, e2 = pair_edges(r_max, n_bins)
+    walls = None if wall_pos is None else np.asarray(wall_pos, dtype=np.float64).reshape(-1, 2)
+    centre = (pos[own, 1] >= y_margin) & (pos[own, 1] <= DH - y_margin)
+    members = [centre] + [centre & in_band(pos[own, 0], DL, x, hw) for x, hw in bands]
+
+    def separations(partners, same, chunk=256):
+        """(row of `own`, r2) of every counted pair"""
+        rows, r2s = [np.zeros(0, dtype=np.int64)], [np.zeros(0)]
+        for a in range(0, len(own), chunk):
+            ci = own[a:a + chunk]
+            dx = pos[ci, 0][:, None] - partners[None, :, 0]
+            dy = pos[ci, 1][:, None] - partners[None, :, 1]
+            r2 = dx * dx + dy * dy
+            keep = r2 < e2[-1]
+            if same:
+                keep &= ci[:, None] != np.arange(len(partners))[None, :]
+            i, j = np.nonzero(keep)
+            rows.append(a + i)
+            r2s.append(r2[i, j])
+        return np.concatenate(rows), np.concatenate(r2s)
+
+    sep = dict(ff=separations(pos, True), fw=separations(walls, False) if walls is not None and len(walls) else separations(pos[:0], False))
+    out = []
+    for mine in members:
+        d = dict(r_edges=r_edges, centres=int(np.count_nonzero(mine)))
+        for kind in ("ff", "fw"):
+            i, r2 = sep[kind]
+            take = mine[i]
             k = np.searchsorted(e2, r2[take], side="right") - 1
             d[kind] = np.bincount(k, minlength=n_bins).astype(np.int64)
             if kind == "ff":

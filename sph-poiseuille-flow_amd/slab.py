@@ -15,8 +15,9 @@ Layers:
   HipSlabEngine    -- the per-rank compute engine (libsphx slab context)
   SlabDriver       -- step loop = engine.compute -> exchange -> engine.finish
   pool_ring_* / ring_* / all_reduce_ring_*
-                   -- the ring's flow statistics, step history and profile series from the slabs' partial sums, its field
-                      map from the slabs' blocks of node columns, and its point probes from the slabs' owned probes
+                   -- the ring's flow statistics, step history, profile series and pair statistics from the slabs' partial
+                      sums, its field map from the slabs' blocks of node columns, and its point probes from the slabs'
+                      owned probes
   bench_main()     -- bench.py's multi-GPU leg
 """
 from __future__ import annotations
@@ -30,7 +31,7 @@ import time
 import numpy as np
 
 from . import capi as _capi
-from .profile import FIELD_MAP_PLANES, field_map_means, flow_stats_profile, profile_series_profiles
+from .profile import FIELD_MAP_PLANES, field_map_means, flow_stats_profile, pair_dist_profiles, profile_series_profiles
 
 HALO_COLS = 4  # four dependent neighbour passes per step, each reaching one >=2h column further
 
@@ -127,8 +128,11 @@ class HipSlabEngine(_capi._Sampled):
     profile_series_sums(drain) are a context's too (capi._Sampled, over sphx_slab_pseries_*): this slab's PARTIAL record of
     every sampled step, which pool_ring_profile_series (ring_profile_series_sums / ring_profile_series,
     all_reduce_ring_profile_series) adds up; means of partial sums would mislead, so the engine has no profile_series().
-    Enabling or disabling drops a graph made by graph_prepare()."""
-    _stem, _where, _series = "sphx_slab_", "slab", "pseries_"
+    pairs_part_enable / _disable / _reset / pairs_part_sums are the pair statistics (over sphx_slab_pairs_*): the pairs whose
+    CENTRE this slab owns, against everything it holds -- partial sums, which pool_ring_pair_dist (ring_pair_dist_sums /
+    ring_pair_dist, all_reduce_ring_pair_dist) adds up, taking the smallest r2_min; g(r) of partial sums would mislead, so the
+    engine has no pair_dist().  Enabling or disabling drops a graph made by graph_prepare()."""
+    _stem, _where, _series, _pairs = "sphx_slab_", "slab", "pseries_", "pairs_"
 
     def __init__(self, prm, parts, rank, world, device, lanes_per_particle=0, halo_cols=HALO_COLS, t_end=None,
                  pos=None, vel=None, drho_dt=None, native=False, rebuild_every=0, skin_h=0.0, hip_stream=None):
@@ -140,6 +144,7 @@ class HipSlabEngine(_capi._Sampled):
         self.rank, self.world, self.native = rank, world, native
         self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
         self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
+        self._pair_dist = None  # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
         capi.set_device(device)
         if not native:
             import torch
@@ -329,6 +334,25 @@ class HipSlabEngine(_capi._Sampled):
         out.update(points=pts.copy(), index=index.astype(np.int64))
         return out
 
+    # ---- pair statistics (include/sphx.h section 3a): the pairs whose centre this slab owns -- PARTIAL sums of the ring's ----
+    def pairs_part_enable(self, n_bins=64, every=1, t_from=0.0, r_max=0.0, y_margin=0.0, with_walls=False, bands=()):
+        """A context's pair_dist_enable (capi._Stepped; the same argument checks, capi.pair_dist_config) for the ring: this slab
+        counts, inside run() / group_run(), the partners of every fluid particle it OWNS -- among everything it holds, its halo
+        copies included, and with_walls its wall particles -- and stamps every sampled step even when it owns no centre.
+        (Re)configures and zeroes the sums; drops a graph made by graph_prepare()."""
+        self._pairs_enable(n_bins, every, t_from, r_max, y_margin, with_walls, bands)
+
+    def pairs_part_disable(self):
+        self._pairs_disable()
+
+    def pairs_part_reset(self):
+        self._pairs_reset()
+
+    def pairs_part_sums(self) -> list:
+        """This slab's partial sums so far, one dict per band with the keys of capi.Context.pair_dist_sums: r_edges, ff, fw
+        (int64), centres, r2_min, r_min, n_samples, t_first, t_last.  pool_ring_pair_dist adds the ranks' up."""
+        return self._pair_dist_bands()
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self.capi.lib().sphx_ctx_destroy(self._h)
@@ -454,6 +478,67 @@ def ring_profile_series(engines, drain=False) -> dict:
     """The profile series of an in-process ring as profiles (profile.profile_series_profiles of the pooled series): what
     driver.profile_series_figures takes."""
     return profile_series_profiles(engines[0].params.DH, ring_profile_series_sums(engines, drain))
+
+
+_PAIR_COUNTS = ("ff", "fw")
+
+
+def _pair_bands(part):
+    """one rank's pair statistics as a list of band dicts whose ff and fw hold one count per bin of r_edges"""
+    if isinstance(part, dict) or not len(part):
+        raise ValueError("the pair statistics of a slab are a list with one dict per band, band 0 first")
+    for b, d in enumerate(part):
+        n_bins = len(d["r_edges"]) - 1
+        for k in _PAIR_COUNTS:
+            if np.shape(d[k]) != (n_bins,):
+                raise ValueError(f"band {b}: {k} has shape {np.shape(d[k])}, r_edges bound {n_bins} bins")
+    return list(part)
+
+
+def pool_ring_pair_dist(parts) -> list:
+    """The ring's pair statistics (the list of band dicts of capi.Context.pair_dist_sums) from the ranks' partial sums
+    (HipSlabEngine.pairs_part_sums or profile.pair_histogram_part, in rank order): per band ff, fw and centres added over the
+    ranks -- int64, exact --, the smallest r2_min (r_min its square root), r_edges of rank 0.  n_samples, t_first and t_last,
+    where the parts carry them, are rank 0's and are NOT added: the slabs of one ring sampled the same steps (unlike the
+    members of profile.pool_pair_dist).  ValueError when the number of bands, r_edges, or n_samples, t_first or t_last differ
+    between the ranks."""
+    parts = [_pair_bands(p) for p in parts]
+    if not parts:
+        raise ValueError("the pair statistics of a ring need the sums of at least one slab")
+    first = parts[0]
+    for r, p in enumerate(parts):
+        if len(p) != len(first):
+            raise ValueError(f"rank {r} holds {len(p)} bands, rank 0 {len(first)}: the slabs of one ring share the config")
+        for b, (d, d0) in enumerate(zip(p, first)):
+            if not np.array_equal(d["r_edges"], d0["r_edges"]):
+                raise ValueError(f"rank {r} holds other bin edges than rank 0 (band {b}): the slabs of one ring share the bins")
+            if any((k in d) != (k in d0) for k in _HEAD):
+                raise ValueError(f"rank {r} and rank 0 do not both carry n_samples, t_first and t_last (band {b})")
+            if all(k in d0 for k in _HEAD) and not all(_same(d[k], d0[k]) for k in _HEAD):
+                raise ValueError(f"rank {r} sampled {({k: d[k] for k in _HEAD})}, rank 0 {({k: d0[k] for k in _HEAD})} (band {b}): "
+                                 "the slabs of one ring sample the same steps")
+    out = []
+    for b, d0 in enumerate(first):
+        r2 = min(float(p[b]["r2_min"]) for p in parts)
+        d = dict(r_edges=np.array(d0["r_edges"], dtype=np.float64))
+        for k in _PAIR_COUNTS:
+            d[k] = np.sum([np.asarray(p[b][k], dtype=np.int64) for p in parts], axis=0, dtype=np.int64)
+        d.update(centres=int(sum(int(p[b]["centres"]) for p in parts)), r2_min=r2, r_min=float(np.sqrt(r2)))
+        d.update({k: d0[k] for k in _HEAD if k in d0})
+        out.append(d)
+    return out
+
+
+def ring_pair_dist_sums(engines) -> list:
+    """The pair statistics of an in-process ring, one dict of integer sums per band (pool_ring_pair_dist of every slab's)."""
+    return pool_ring_pair_dist([e.pairs_part_sums() for e in engines])
+
+
+def ring_pair_dist(engines) -> list:
+    """The pair statistics of an in-process ring with the figures of profile.pair_dist_profiles (r_mid, g, g_wall, n_neigh,
+    r_min) in every band's dict: what driver.pair_dist_figures takes."""
+    dp = engines[0].params.dp
+    return [dict(d, **pair_dist_profiles(d, dp)) for d in ring_pair_dist_sums(engines)]
 
 
 def _check_blocks_partition(shapes):
@@ -711,6 +796,50 @@ def all_reduce_ring_profile_series(sums, dist, group=None) -> dict:
     out = dict(step=np.asarray(sums["step"]).astype(np.int64), t=t.copy())
     out.update({k: np.ascontiguousarray(total[j]) for j, k in enumerate(_SUMS)})
     out.update(n_dropped=int(sums["n_dropped"]), y_mid=y_mid.copy())
+    return out
+
+
+def all_reduce_ring_pair_dist(part, dist, group=None) -> list:
+    """One rank per process: the ring's pair statistics from this rank's partial sums (HipSlabEngine.pairs_part_sums), as
+    pool_ring_pair_dist; every rank gets them.  The number of bands and bins, whether a rank's own list is well formed, r_edges
+    and the heads are all-gathered and checked first; then ff, fw and centres of all bands, stacked as int64, are all-reduced
+    with SUM and the bands' r2_min with MIN.  Collective; raises on every rank when a list is malformed or the bands, r_edges,
+    n_samples, t_first or t_last differ between the ranks."""
+    import torch
+    try:
+        bands, why = _pair_bands(part), None
+        shape = (len(bands), len(bands[0]["r_edges"]) - 1)
+        if any(len(d["r_edges"]) - 1 != shape[1] for d in bands):
+            raise ValueError("the bands of one slab share the bins")
+        head = [float(bands[0][k]) for k in _HEAD]
+    except (ValueError, KeyError, TypeError) as e:
+        bands, shape, head, why = None, (-1, -1), [0.0] * len(_HEAD), str(e)
+    rows = _all_gathered(dist, [float(v) for v in shape] + [0.0 if why is None else 1.0], group)
+    for r, row in enumerate(rows):
+        if row[2] != 0.0:
+            raise ValueError(f"rank {r}'s pair statistics are malformed" + (f": {why}" if why else ""))
+    for r, row in enumerate(rows):
+        if tuple(row[:2]) != tuple(rows[0][:2]):
+            raise ValueError(f"rank {r} holds {int(row[0])} bands of {int(row[1])} bins, rank 0 {int(rows[0][0])} of "
+                             f"{int(rows[0][1])}: the slabs of one ring share the config")
+    edges = _all_gathered(dist, np.concatenate([np.asarray(d["r_edges"], dtype=np.float64) for d in bands]), group)
+    for r, row in enumerate(edges):
+        if not np.array_equal(row, edges[0]):  # (every rank sees every row: one odd rank out makes all of them raise)
+            raise ValueError(f"rank {r} holds other bin edges than rank 0: the slabs of one ring share the bins")
+    _check_heads_agree([tuple(h) for h in _all_gathered(dist, head, group)])
+    counts = torch.from_numpy(np.stack([np.concatenate([np.asarray(d[k], dtype=np.int64) for k in _PAIR_COUNTS] +
+                                                       [np.array([int(d["centres"])], dtype=np.int64)]) for d in bands]))
+    dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
+    r2 = torch.tensor([float(d["r2_min"]) for d in bands], dtype=torch.float64)
+    dist.all_reduce(r2, op=dist.ReduceOp.MIN, group=group)
+    counts, r2 = counts.numpy(), r2.numpy()
+    n_bins = shape[1]
+    out = []
+    for b, d0 in enumerate(bands):
+        d = dict(r_edges=np.array(d0["r_edges"], dtype=np.float64), ff=counts[b, :n_bins].copy(), fw=counts[b, n_bins:2 * n_bins].copy(),
+                 centres=int(counts[b, 2 * n_bins]), r2_min=float(r2[b]), r_min=float(np.sqrt(r2[b])))
+        d.update({k: d0[k] for k in _HEAD})
+        out.append(d)
     return out
 
 
