@@ -852,6 +852,96 @@ int sphx_batch_pair_dist_read(sphx_batch *batch, int band, int capacity, int *n_
                               double *r2_min, int64_t *n_samples, double *t_first, double *t_last);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2n. Gradient statistics: the velocity gradient at every fluid particle, estimated and binned on the device, inside the
+ *     step loop: the shear-rate profile du_x/dy (hence the shear stress tau(y) = mu du_x/dy, which the momentum balance makes
+ *     linear in y), the velocity divergence (how weakly compressible the flow really is) and the vorticity.  The step
+ *     history's wall shear (section 2d) is two scalars at the walls; this is the profile across the channel.
+ *
+ *  Estimate: for every fluid particle i, over every other fluid particle j within 2h (nearest image in x, r2 > 1e-24) and,
+ *    with_walls, every wall particle within 2h (with the wall's velocity):
+ *        d = r_i - r_j,  w_j = V_j W'(|d|) / |d|,  V_j = mass_j / rho0 (a wall particle: its volume),  W' the cubic spline's
+ *        M_i = - sum_j w_j d (x) d        A_i = sum_j w_j (v_j - v_i) (x) d        G_i = A_i M_i^-1
+ *    G_ab = d u_a / d x_b: g_xx, g_xy, g_yx, g_yy.  The estimate is exact for any linear velocity field whatever the particle
+ *    arrangement, and first order at the one-sided support next to a wall.  with_walls is off by default: the wall particles
+ *    carry the wall's velocity, not the extrapolated one, and pull the estimate of the wall-adjacent bin down (2.65 against
+ *    the exact 3.80 in units of U_max / DH on the analytic parabola at dp = 0.05; without them 3.56).
+ *  Skipped: a particle with det M_i <= det_min (no partner, or collinear ones), with a component of G_i that is not finite,
+ *    or with one above the sample's bound 2^e > 16 vmax / h in magnitude (vmax: sphx_status.vmax of the step) is counted in
+ *    `skipped` and summed nowhere.  This is not an error.
+ *  Bins and bands: those of section 2a -- n_bins y-bins over [0, DH] (0: the reference's profile bins), y outside dropped,
+ *    band 0 the whole channel, up to two x-bands.  Per bin and band count + skipped equals the flow statistics' count.
+ *  Sums, per bin and band, over all samples, SPHX_GRAD_STATS_FIELDS = 12 doubles in this order: count, sum g_xx, sum g_xy,
+ *    sum g_yx, sum g_yy, sum g_xx^2, sum g_xy^2, sum g_yx^2, sum g_yy^2, sum div^2 (div = g_xx + g_yy), sum omega^2
+ *    (omega = g_yx - g_xy), skipped.  count and skipped are integers held in doubles.  Per sampler: n_samples, t_first, t_last.
+ *  Exactness: a sample is summed in int64 fixed point at power-of-two scales picked from the particle count and the bound, so
+ *    the sums are bit-identical between runs and independent of the workgroups' dispatch order, and a batch member's are a
+ *    standalone context's.  Unlike the pair statistics' counts they DO depend on the order of the particle slots (a particle's
+ *    partners are added in slot order): two layouts of one state agree within floating-point rounding, not bit for bit.
+ *  Limits: n_bins * (n_bands + 1) <= 640, the 61 440 B of LDS counters of a workgroup.
+ *  Gating: as in section 2l.  sphx_ctx_grad_stats_sample adds a sample of the state now, without gating.
+ *  Off by default.  With it off a step slot enqueues exactly the launches it does without this feature; on, every step slot
+ *    ends with one more launch (k_grad_stats, behind k_pair_dist; it skips itself on the steps gated out) that is captured
+ *    in the replayed graphs; enable / disable re-capture them.  A sample costs 2.6 to 3.5 cell sweeps of the step's density
+ *    pass (1.5 to 1.8 samples of the pair statistics): `every` is the control.  Independent of the other six samplers.
+ *  Errors: SPHX:GradStats:config (NULL config, n_bins < 0 or n_bins * (n_bands + 1) > 640, every < 1, a NaN t_from, a det_min
+ *    that is not finite or negative, with_walls not 0 / 1, n_bands outside 0..2, a band centre or half-width that is not
+ *    finite or a negative half-width, or the allocation fails: the context then goes on without gradient statistics),
+ *    SPHX:GradStats:band, SPHX:GradStats:capacity (sums given and capacity < n_bins), SPHX:GradStats:disabled (SPHX_ERR_STATE:
+ *    a call that needs the sampler while it is off); every call on a slab context fails with SPHX_ERR_ARG,
+ *    SPHX:GradStats:slab.  A refused enable leaves a running sampler, and its sums, untouched.
+ * ---------------------------------------------------------------------------------------------- */
+
+#define SPHX_GRAD_STATS_FIELDS 12
+#define SPHX_GRAD_STATS_MAX_BINS 640
+
+typedef struct sphx_grad_stats_config {
+    int32_t n_bins;            /* y-bins over [0, DH]; 0 = the reference's profile bins                  */
+    int32_t every;             /* sample every `every`-th completed step (step count % every == 0), >= 1 */
+    double t_from;             /* only steps ending at t >= t_from                                       */
+    double det_min;            /* a particle with det M <= det_min is skipped; >= 0 (0.05 is a good default) */
+    int32_t with_walls;        /* 1: the wall particles are partners too, with the wall's velocity       */
+    int32_t n_bands;           /* 0..2 x-bands besides the whole channel                                 */
+    double band_x[2], band_hw[2];
+} sphx_grad_stats_config;
+
+/* (Re)configure and zero the sums; waits for the stream.  Off by default. */
+int sphx_ctx_grad_stats_enable(sphx_ctx *ctx, const sphx_grad_stats_config *cfg);
+/* Stop sampling (no-op when off); the sums are dropped. */
+int sphx_ctx_grad_stats_disable(sphx_ctx *ctx);
+/* Zero the sums and the sample count; the configuration stays. */
+int sphx_ctx_grad_stats_reset(sphx_ctx *ctx);
+/* Add one sample of the current state (what sphx_ctx_download would return) now, without gating. */
+int sphx_ctx_grad_stats_sample(sphx_ctx *ctx);
+/* The sums of one band so far: sums is [SPHX_GRAD_STATS_FIELDS][capacity] (field f of bin k at f * capacity + k; capacity >=
+ * n_bins where it is given), every pointer may be NULL.  Waits for and settles everything enqueued, like sphx_ctx_download.
+ * t_first / t_last are NaN before a sample. */
+int sphx_ctx_grad_stats_read(sphx_ctx *ctx, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples, double *t_first,
+                             double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2o. Gradient statistics of a batch (section 2b): the sums of section 2n for every member at once.
+ *
+ *  One config for all members (bins, bands and the walls come from the shared geometry).  Every member has its own block of
+ *  sums and its own head and is sampled on its own clock, with its own rho0, with the gating of section 2n, so a member that
+ *  sits out slots is not sampled in them.  A member's sums are, bit for bit, those of a standalone context with the same
+ *  parameters and config that took the same steps in the same slot order; a realignment reorders a member's slots, after
+ *  which its sums agree within floating-point rounding and its counts exactly.  With the sampler on, every step slot of the
+ *  batch ends with one launch for all members (k_grad_stats_b, behind the batch's other samplers); off, a slot enqueues
+ *  exactly the launches it does without this feature.  A refused enable leaves a running sampler untouched.
+ *  Errors: SPHX:Batch:null (NULL batch) and those of section 2n.
+ * ---------------------------------------------------------------------------------------------- */
+
+int sphx_batch_grad_stats_enable(sphx_batch *batch, const sphx_grad_stats_config *cfg);
+int sphx_batch_grad_stats_disable(sphx_batch *batch);
+int sphx_batch_grad_stats_reset(sphx_batch *batch);
+/* settles; adds a sample of what sphx_batch_download returns, every member, without gating */
+int sphx_batch_grad_stats_sample(sphx_batch *batch);
+/* One call for all members: sums is [n_members][SPHX_GRAD_STATS_FIELDS][capacity], n_samples, t_first and t_last are
+ * [n_members]; any pointer may be NULL.  Settles first, as sphx_batch_download does. */
+int sphx_batch_grad_stats_read(sphx_batch *batch, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples,
+                               double *t_first, double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU). The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

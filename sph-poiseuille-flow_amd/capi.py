@@ -8,8 +8,8 @@ import os
 
 import numpy as np
 
-from .profile import (FIELD_MAP_PLANES, STATS_FIELDS, field_map_means, flow_stats_profile, pair_dist_profiles, pair_edges,
-                      profile_series_profiles)
+from .profile import (FIELD_MAP_PLANES, GRAD_FIELDS, GRAD_MAX_BINS, STATS_FIELDS, field_map_means, flow_stats_profile,
+                      grad_stats_profiles, pair_dist_profiles, pair_edges, profile_series_profiles)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPHX_LIB") or os.path.join(HERE, "csrc", "libsphx.so")  # SPHX_LIB: experiment builds
@@ -78,6 +78,11 @@ class SphxPairDistConfig(C.Structure):
 PAIR_DIST_MAX_BINS = 1024
 
 
+class SphxGradStatsConfig(C.Structure):
+    _fields_ = [("n_bins", C.c_int32), ("every", C.c_int32), ("t_from", C.c_double), ("det_min", C.c_double),
+                ("with_walls", C.c_int32), ("n_bands", C.c_int32), ("band_x", C.c_double * 2), ("band_hw", C.c_double * 2)]
+
+
 class SphxStatus(C.Structure):
     _fields_ = [("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("vmax", C.c_double),
                 ("step", C.c_int64), ("done", C.c_int32), ("device_status", C.c_int32)]
@@ -106,6 +111,8 @@ EXPORTS = [
     "sphx_ctx_profile_series_read",
     "sphx_ctx_pair_dist_enable", "sphx_ctx_pair_dist_disable", "sphx_ctx_pair_dist_reset", "sphx_ctx_pair_dist_sample",
     "sphx_ctx_pair_dist_read",
+    "sphx_ctx_grad_stats_enable", "sphx_ctx_grad_stats_disable", "sphx_ctx_grad_stats_reset", "sphx_ctx_grad_stats_sample",
+    "sphx_ctx_grad_stats_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -127,6 +134,8 @@ EXPORTS = [
     "sphx_batch_profile_series_read",
     "sphx_batch_pair_dist_enable", "sphx_batch_pair_dist_disable", "sphx_batch_pair_dist_reset", "sphx_batch_pair_dist_sample",
     "sphx_batch_pair_dist_read",
+    "sphx_batch_grad_stats_enable", "sphx_batch_grad_stats_disable", "sphx_batch_grad_stats_reset", "sphx_batch_grad_stats_sample",
+    "sphx_batch_grad_stats_read",
 ]
 
 _LIB = None
@@ -614,6 +623,66 @@ class _Stepped(_Sampled):
         dp = self._params0().dp
         return self._each([dict(s, **pair_dist_profiles(s, dp)) for s in self._pair_dist_band(band)])
 
+    # ---- gradient statistics (include/sphx.h sections 2n, 2o): the velocity gradient at the fluid particles, binned ----
+    def grad_stats_enable(self, n_bins=0, every=1, t_from=0.0, det_min=0.05, with_walls=False, bands=()):
+        """Estimate, every `every`-th completed step ending at t >= t_from, the velocity gradient G_ab = d u_a / d x_b at every
+        fluid particle (profile.velocity_gradients) and add g_xx, g_xy, g_yx, g_yy, their squares, div^2 and vort^2 to n_bins
+        y-bins (0: the reference's max(20, round(DH/dp))) of the whole channel (band 0) and of up to two x-bands
+        [(x_centre, half_width), ...].  A particle with det M <= det_min or an estimate out of range is counted in `skipped`.
+        with_walls: the wall particles are partners too, with the wall's velocity -- off by default, because they pull the
+        estimate next to a wall towards the wall's velocity.  (Re)configures and zeroes the sums.  A batch: one config for all
+        members, each sampled on its own clock."""
+        p0 = self._params0()
+        cfg = grad_stats_config(p0, n_bins, every, t_from, det_min, with_walls, bands)
+        self._call("grad_stats_enable", C.byref(cfg))
+        # (n_bins, n_bands incl. band 0) while the gradient statistics are on
+        self._grad_stats = (int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5))), int(cfg.n_bands) + 1)
+
+    def grad_stats_disable(self):
+        self._call("grad_stats_disable")
+        self._grad_stats = None
+
+    def _grads_on(self):
+        return _enabled(getattr(self, "_grad_stats", None), "GradStats", f"gradient statistics are not enabled on this {self._where}")
+
+    def grad_stats_reset(self):
+        self._grads_on()
+        self._call("grad_stats_reset")
+
+    def grad_stats_sample(self):
+        """Add one sample of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
+        self._grads_on()
+        self._call("grad_stats_sample")
+
+    def grad_stats_sums(self, band=0):
+        """The raw sums of one band: the twelve profile.GRAD_FIELDS as [n_bins] arrays (count and skipped hold integers),
+        n_samples, t_first, t_last; a batch: one such dict per member, from one read of all members."""
+        n_bins, n_bands = self._grads_on()
+        if not _is_int(band) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:GradStats:band", f"band must be an integer in 0..{n_bands - 1}")
+        m = self._channels()
+        sums = np.zeros((m, len(GRAD_FIELDS), n_bins))
+        ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
+        nb = C.c_int(0)
+        self._call("grad_stats_read", C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), ptr(sums), ns.ctypes.data_as(C.POINTER(C.c_int64)),
+                   ptr(t0), ptr(t1))
+        assert nb.value == n_bins, (nb.value, n_bins)
+        out = []
+        for k in range(m):
+            d = {f: sums[k, j].copy() for j, f in enumerate(GRAD_FIELDS)}
+            d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
+            out.append(d)
+        return self._each(out)
+
+    def grad_stats(self, band=0):
+        """One band's profiles (profile.grad_stats_profiles): y_mid, count, skipped, the mean and standard deviation of each
+        component (gxx_mean, gxx_std, ... gyy_std; gxy is the shear rate du_x/dy), div_rms, vort_mean, vort_rms, NaN where a bin
+        is empty, plus the raw sums, n_samples, t_first, t_last.  A batch: one such dict per member."""
+        DH = self._params0().DH
+        sums = self.grad_stats_sums(band)
+        per = [dict(s, **grad_stats_profiles(DH, s)) for s in (sums if self._many else [sums])]
+        return self._each(per)
+
 
 class Batch(_Stepped):
     """M channels of one geometry stepped by the same launches (sphx_batch, include/sphx.h section 2b).
@@ -656,6 +725,7 @@ class Batch(_Stepped):
         self._probes = None      # the folded points [P, 2] while the probes are on
         self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
         self._pair_dist = None   # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
+        self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
         arr = (SphxParams * m)(*self.params)
         check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
@@ -706,6 +776,7 @@ class Context(_Stepped):
         self._probes = None      # the folded points [P, 2] while the probes are on
         self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
         self._pair_dist = None   # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
+        self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
         check(lib().sphx_ctx_create(C.byref(self._h), C.byref(self.params), C.c_int(n_fluid), C.c_int(n_total),
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
@@ -959,6 +1030,31 @@ def pair_dist_config(prm, n_bins=64, every=1, t_from=0.0, r_max=0.0, y_margin=0.
         raise bad("with_walls must be a bool")
     cfg = SphxPairDistConfig(n_bins=int(n_bins), every=int(f.every), t_from=float(f.t_from), r_max=r_max, y_margin=y_margin,
                              with_walls=1 if with_walls else 0, n_bands=int(f.n_bands))
+    for k in range(2):
+        cfg.band_x[k], cfg.band_hw[k] = f.band_x[k], f.band_hw[k]
+    return cfg
+
+
+def grad_stats_config(prm, n_bins=0, every=1, t_from=0.0, det_min=0.05, with_walls=False, bands=()) -> SphxGradStatsConfig:
+    """Checked sphx_grad_stats_config for channels with parameters prm; raises SphxError(SPHX:GradStats:config) before anything
+    reaches the device.  n_bins, every, t_from and the bands by the checks of flow_stats_config."""
+    bad = _config_error("GradStats")
+    try:
+        f = flow_stats_config(n_bins, every, t_from, bands)
+        det_min = float(det_min)
+    except SphxError as e:
+        raise bad(e.message) from None
+    except (TypeError, ValueError):
+        raise bad("det_min must be a number") from None
+    if not (np.isfinite(det_min) and det_min >= 0.0):
+        raise bad("det_min must be finite and >= 0")
+    if not isinstance(with_walls, (bool, np.bool_)) and with_walls not in (0, 1):
+        raise bad("with_walls must be a bool")
+    bins = int(f.n_bins) or max(20, int(np.floor(prm.DH / prm.dp + 0.5)))
+    if bins * (int(f.n_bands) + 1) > GRAD_MAX_BINS:
+        raise bad("n_bins * (number of bands + 1) must not exceed 640")
+    cfg = SphxGradStatsConfig(n_bins=int(f.n_bins), every=int(f.every), t_from=float(f.t_from), det_min=det_min,
+                              with_walls=1 if with_walls else 0, n_bands=int(f.n_bands))
     for k in range(2):
         cfg.band_x[k], cfg.band_hw[k] = f.band_x[k], f.band_hw[k]
     return cfg

@@ -786,3 +786,67 @@ SPHX_EXPORT int sphx_batch_pair_dist_read(sphx_batch *b, int band, int capacity,
     return SPHX_OK;
     SPHX_CATCH
 }
+
+// ---- gradient statistics of every member (include/sphx.h section 2o) ----
+
+namespace {
+
+// the batch's gradient statistics (member 0's, see sphx_ctx::grads)
+GradStats &batch_grads(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    GradStats &f = b->mem[0]->grads;
+    sampler_check(kGradNames, false, f.on, need_on, "batch");
+    return f;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_batch_grad_stats_enable(sphx_batch *b, const sphx_grad_stats_config *cfg)
+{
+    SPHX_TRY
+    // (bins, bands and the walls come from the shared geometry; out of device memory: the batch goes on without gradient statistics)
+    GradStats &f = batch_grads(b, false);
+    grad_stats_enable(f, b->mem[0]->prm, cfg, b->M, b->mem[0]->nw > 0, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_grad_stats_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    GradStats &f = batch_grads(b, false);
+    if (f.on) sampler_off(f, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_grad_stats_reset(sphx_batch *b)
+{
+    SPHX_TRY
+    GradStats &f = batch_grads(b, true);
+    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_grad_stats_sample(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_grads(b, true);
+    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
+    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_grad_stats);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_grad_stats_read(sphx_batch *b, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples,
+                                           double *t_first, double *t_last)
+{
+    SPHX_TRY
+    const GradStats &f = batch_grads(b, true);
+    grad_stats_read(f, b->stream, [b] { batch_settle(b); }, band, capacity, n_bins, sums, n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}

@@ -168,6 +168,39 @@ __device__ __forceinline__ double stats_value(int k, unsigned long long v, const
     return ldexp((double)(long long)v, -s);
 }
 
+// The end of a sample whose workgroups have binned their shares into integer LDS counters s_cnt[nc] (behind the barrier that
+// closes the binning), stated once for the samplers that add a sample to running sums -- the flow statistics and the gradient
+// statistics (sphx_grad_stats.hpp): finish(k, v) adds counter k's integer total v to its running sum.  One workgroup holds the
+// whole sample of a small channel: no global sums, no ticket.  Otherwise every workgroup adds its non-zero counters to the
+// global integer sums isum with one atomic each, and the last one out (last_out_fenced on head->ticket) finishes every counter
+// and clears it for the next sample.  By every thread of a workgroup of kThreads.
+template <int kThreads, typename Head, typename Finish>
+__device__ __forceinline__ void stats_finish_sample(const unsigned long long *s_cnt, int nc, unsigned long long *isum, Head *head, double t_now,
+                                                    Finish &&finish)
+{
+    __shared__ int s_last;
+    if (gridDim.x == 1) {  // small channels: one workgroup holds the whole sample -- no global sums, no ticket
+        for (int k = threadIdx.x; k < nc; k += kThreads)
+            if (s_cnt[k]) finish(k, s_cnt[k]);
+        if (threadIdx.x == 0) note_sample(head, t_now);
+        return;
+    }
+    for (int k = threadIdx.x; k < nc; k += kThreads) {
+        const unsigned long long v = s_cnt[k];
+        if (v) atomicAdd(isum + k, v);
+    }
+    last_out_fenced(&head->ticket, s_last);
+    if (!s_last) return;
+    for (int k = threadIdx.x; k < nc; k += kThreads) {
+        const unsigned long long v = atomicExch(isum + k, 0ull);
+        if (v) finish(k, v);
+    }
+    if (threadIdx.x == 0) {
+        note_sample(head, t_now);
+        __hip_atomic_store(&head->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // The sample of one channel closing the step slot of parity q, on clock clk, shared by the gridDim.x workgroups of a grid
 // row; `at` says where the channel's arrays are: a's own pointers (StatsOwn) or a batch member's blocks (StatsMember).
 template <typename At>
@@ -177,31 +210,11 @@ __device__ __forceinline__ void flow_stats_body(const Clock *clk, int q, const F
     const int n = clk->n;
     const double vmax = clk->vmax, t_now = clk->t;
     extern __shared__ unsigned long long s_cnt[];  // [n_bands][n_bins][kStatsFields]
-    __shared__ int s_last;
     const int nc = a.n_bands * a.n_bins * kStatsFields;
     const StatsScales sc = stats_bin_sample(a, at, n, vmax, s_cnt, nc, [&] { return &at.head(a)->range; });
     // one thread per counter: the running sums grow in sample order, each by its own bin -- no summation tree
-    auto finish = [&](int k, unsigned long long v) { at.dsum(a)[k] += stats_value(k, v, sc); };
-    if (gridDim.x == 1) {  // small channels: one workgroup holds the whole sample -- no global sums, no ticket
-        for (int k = threadIdx.x; k < nc; k += kStatsBlock)
-            if (s_cnt[k]) finish(k, s_cnt[k]);
-        if (threadIdx.x == 0) note_sample(at.head(a), t_now);
-        return;
-    }
-    for (int k = threadIdx.x; k < nc; k += kStatsBlock) {
-        const unsigned long long v = s_cnt[k];
-        if (v) atomicAdd(at.isum(a) + k, v);
-    }
-    last_out_fenced(&at.head(a)->ticket, s_last);
-    if (!s_last) return;
-    for (int k = threadIdx.x; k < nc; k += kStatsBlock) {
-        const unsigned long long v = atomicExch(at.isum(a) + k, 0ull);
-        if (v) finish(k, v);
-    }
-    if (threadIdx.x == 0) {
-        note_sample(at.head(a), t_now);
-        __hip_atomic_store(&at.head(a)->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    stats_finish_sample<kStatsBlock>(s_cnt, nc, at.isum(a), at.head(a), t_now,
+                                     [&](int k, unsigned long long v) { at.dsum(a)[k] += stats_value(k, v, sc); });
 }
 
 __global__ __launch_bounds__(kStatsBlock) void k_flow_stats(const Clock *clk, int q, FlowStatsArgs a)

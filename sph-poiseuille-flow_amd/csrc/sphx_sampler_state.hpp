@@ -8,6 +8,7 @@
 #include "sphx_probes.hpp"
 #include "sphx_profile_series.hpp"
 #include "sphx_pair_dist.hpp"
+#include "sphx_grad_stats.hpp"
 
 struct sphx_ctx;
 
@@ -146,8 +147,31 @@ struct PairDist {
               double *t_first, double *t_last) const;
 };
 
+// Gradient statistics (sphx_ctx_grad_stats_*, sphx_batch_grad_stats_*; sphx_grad_stats.hpp) of a context or of the M members of
+// a batch: one configuration, bins and bands as FlowStats has them, member m's int64 sums of the sample in flight and its
+// running sums at m * block() -- [n_bands][n_bins][kGradFields] -- and its head at m.
+struct GradStats {
+    bool on = false;
+    int members = 1;
+    sphx_grad_stats_config cfg{};
+    int n_bins = 0, n_bands = 1;  // (n_bands counts band 0)
+    bool walls = false;           // with_walls, and the channel holds wall particles
+    DevBuf<unsigned long long> isum;
+    DevBuf<double> dsum;
+    DevBuf<GradStatsHead> head;
+
+    size_t row() const { return (size_t)n_bins * kGradFields; }   // the sums of one band ...
+    size_t block() const { return (size_t)n_bands * row(); }      // ... and of one member
+    size_t shmem() const { return block() * sizeof(unsigned long long); }  // the LDS counters of a workgroup
+    void check(const sphx_params &prm, const sphx_grad_stats_config *cfg, bool has_walls);
+    void alloc(const GradStats &checked, int M);
+    void zero(hipStream_t st) { isum.zero(st); dsum.zero(st); head.zero(st); }
+    void release() { isum.release(); dsum.release(); head.release(); }
+    void read(hipStream_t st, int band, int stride, double *sums, int64_t *n_samples, double *t_first, double *t_last) const;
+};
+
 // the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes, profile series,
-// pair statistics (sphx_samplers.hpp)
+// pair statistics, gradient statistics (sphx_samplers.hpp)
 void launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild);
 
 }  // namespace sphx

@@ -1,7 +1,7 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
-// the velocity-field map (2e; 2g), the point probes (2h; 2i), the profile series (2j; 2k) and the pair statistics (2l; 2m,
-// sphx_pair_dist.hpp) -- all six also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// the velocity-field map (2e; 2g), the point probes (2h; 2i), the profile series (2j; 2k), the pair statistics (2l; 2m,
+// sphx_pair_dist.hpp) and the gradient statistics (2n; 2o, sphx_grad_stats.hpp) -- the first six also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -32,6 +32,8 @@ constexpr SamplerNames kSeriesNames{"ProfileSeries", "the profile series of a sl
 constexpr SamplerNames kPairNames{"PairDist", "the pair statistics of a slab are sphx_slab_pairs_* (include/sphx.h section 3a)",
                                   "pair statistics are not enabled on this ",
                                   "the sums could not be set up: "};
+constexpr SamplerNames kGradNames{"GradStats", "gradient statistics are not available on slab contexts",
+                                  "gradient statistics are not enabled on this ", "the sums could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
 
@@ -289,6 +291,36 @@ void launch_pair_dist(sphx_ctx *c, int q, const FluidSet &s, int every)
                  c->grid, s, c->walls, pair_dist_args(c, every));
 }
 
+// the arguments of a gradient-statistics launch into c->grads
+GradStatsArgs grad_stats_args(sphx_ctx *c, int every)
+{
+    const GradStats &f = c->grads;
+    GradStatsArgs a{};
+    a.isum = f.isum.get(); a.dsum = f.dsum.get(); a.head = f.head.get();
+    a.DH = c->prm.DH; a.bin_w = c->prm.DH / f.n_bins; a.DL = c->prm.DL;
+    a.t_from = f.cfg.t_from; a.det_min = f.cfg.det_min;
+    for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
+    a.n_bins = f.n_bins; a.n_bands = f.n_bands;
+    a.block = (int)f.block();
+    a.with_walls = f.walls ? 1 : 0;
+    a.every = every;
+    return a;
+}
+
+// workgroups of the sample of a channel that holds n particles: kGradTrips trips of kGradCentres particles each
+unsigned grad_stats_blocks(size_t n)
+{
+    return std::clamp<unsigned>(div_up(n, (size_t)kGradCentres * kGradTrips), 1u, (unsigned)kGradMaxBlocks);
+}
+
+// k_grad_stats on state s (pos, vel, mass and the cell ranges and binned cells of the layout it is stored in) -- of a batch:
+// member 0's -- into c->grads
+void launch_grad_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    launch_forms(c, "k_grad_stats", Forms{k_grad_stats, k_grad_stats_b}, grad_stats_blocks((size_t)c->nf), kGradBlock, c->grads.shmem(), q,
+                 c->grid, per_member(c->phys), s, c->walls, grad_stats_args(c, every));
+}
+
 }  // namespace
 
 void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
@@ -300,6 +332,7 @@ void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
     if (c->probes.on) launch_probes(c, q, s, c->probes.cfg.every);
     if (c->pseries.on) launch_profile_series(c, q, s, c->pseries.cfg.every);
     if (c->pairs.on) launch_pair_dist(c, q, s, c->pairs.cfg.every);
+    if (c->grads.on) launch_grad_stats(c, q, s, c->grads.cfg.every);
 }
 
 // ---- flow statistics ----
@@ -1111,6 +1144,138 @@ SPHX_EXPORT int sphx_ctx_pair_dist_read(sphx_ctx *c, int band, int capacity, int
     SPHX_TRY
     const PairDist &p = sampler_of(c, &sphx_ctx::pairs, kPairNames, true);
     pair_dist_read(p, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- gradient statistics ----
+
+// every check of a configuration of channels with parameters prm (cfg, n_bins, n_bands, walls); has_walls: the channel holds
+// wall particles (without any, with_walls changes nothing); SPHX:GradStats:config errors
+void GradStats::check(const sphx_params &prm, const sphx_grad_stats_config *cfg, bool has_walls)
+{
+    const char *id = "SPHX:GradStats:config";
+    require(cfg != nullptr, id, "config must not be NULL");
+    require(cfg->n_bins >= 0, id, "n_bins must be >= 0 (0 = the reference's profile bins)");
+    require(cfg->every >= 1, id, "every must be >= 1");
+    require(!std::isnan(cfg->t_from), id, "t_from must not be NaN");
+    require(std::isfinite(cfg->det_min) && cfg->det_min >= 0.0, id, "det_min must be finite and >= 0");
+    require(cfg->with_walls == 0 || cfg->with_walls == 1, id, "with_walls must be 0 or 1");
+    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, id, "n_bands must be 0, 1 or 2");
+    for (int b = 0; b < cfg->n_bands; ++b)
+        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, id,
+                "band centres must be finite and half-widths finite and >= 0");
+    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
+    require((int64_t)bins * (cfg->n_bands + 1) <= kGradMaxBins, id,
+            "n_bins * (n_bands + 1) must not exceed 640 (the per-workgroup LDS counters)");
+    this->cfg = *cfg;
+    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
+    n_bins = bins;
+    n_bands = cfg->n_bands + 1;
+    walls = cfg->with_walls && has_walls;
+}
+
+// the checked configuration, and sums and heads for M members
+void GradStats::alloc(const GradStats &checked, int M)
+{
+    cfg = checked.cfg;
+    n_bins = checked.n_bins;
+    n_bands = checked.n_bands;
+    walls = checked.walls;
+    members = M;
+    isum.alloc(block() * M);
+    dsum.alloc(block() * M);
+    head.alloc(M);
+}
+
+// Band `band` of every member's sums (into sums[(m * kGradFields + field) * stride + bin], where given) and the heads
+// (n_samples[m], t_first[m], t_last[m], where given)
+void GradStats::read(hipStream_t st, int band, int stride, double *sums, int64_t *n_samples, double *t_first, double *t_last) const
+{
+    const int M = members;
+    std::vector<double> host(sums ? (size_t)M * row() : 0);
+    std::vector<GradStatsHead> h(M);
+    if (sums)  // one copy: a row of every member's block
+        SPHX_HIP(hipMemcpy2DAsync(host.data(), row() * sizeof(double), dsum.get() + (size_t)band * row(), block() * sizeof(double),
+                                  row() * sizeof(double), M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(GradStatsHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    if (sums)
+        for (int m = 0; m < M; ++m)
+            for (int j = 0; j < kGradFields; ++j)
+                for (int k = 0; k < n_bins; ++k)
+                    sums[((size_t)m * kGradFields + j) * stride + k] = host[(size_t)m * row() + (size_t)k * kGradFields + j];
+    for (int m = 0; m < M; ++m)
+        read_head(h[m], n_samples ? n_samples + m : nullptr, t_first ? t_first + m : nullptr, t_last ? t_last + m : nullptr);
+}
+
+namespace {
+
+// enable for M members of channels with parameters prm on schedule s: every check of cfg first
+void grad_stats_enable(GradStats &f, const sphx_params &prm, const sphx_grad_stats_config *cfg, int M, bool has_walls, Schedule &s, hipStream_t st)
+{
+    GradStats checked;
+    checked.check(prm, cfg, has_walls);
+    sampler_on(f, kGradNames, s, st, [&] { f.alloc(checked, M); });
+}
+
+// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
+template <typename Settle>
+void grad_stats_read(const GradStats &f, hipStream_t st, Settle &&settle, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples,
+                     double *t_first, double *t_last)
+{
+    require(band >= 0 && band < f.n_bands, "SPHX:GradStats:band", "band must be 0 (whole channel) .. n_bands");
+    require(sums == nullptr || capacity >= f.n_bins, "SPHX:GradStats:capacity", "capacity is smaller than the number of bins");
+    settle();
+    f.read(st, band, capacity, sums, n_samples, t_first, t_last);
+    if (n_bins) *n_bins = f.n_bins;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_grad_stats_enable(sphx_ctx *c, const sphx_grad_stats_config *cfg)
+{
+    SPHX_TRY
+    GradStats &f = sampler_of(c, &sphx_ctx::grads, kGradNames, false);
+    grad_stats_enable(f, c->prm, cfg, 1, c->nw > 0, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_grad_stats_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    GradStats &f = sampler_of(c, &sphx_ctx::grads, kGradNames, false);
+    if (f.on) sampler_off(f, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_grad_stats_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    GradStats &f = sampler_of(c, &sphx_ctx::grads, kGradNames, true);
+    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_grad_stats_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampler_of(c, &sphx_ctx::grads, kGradNames, true);
+    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_grad_stats);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_grad_stats_read(sphx_ctx *c, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples, double *t_first,
+                                         double *t_last)
+{
+    SPHX_TRY
+    const GradStats &f = sampler_of(c, &sphx_ctx::grads, kGradNames, true);
+    grad_stats_read(f, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, sums, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -19,8 +19,9 @@ from . import capi
 from .geometry import init_particles
 from .mex_surface import sph_neighbor_search_mex, sph_physics_shell_mex
 from . import restart
-from .profile import (compute_mid_channel_profile, field_map_means, final_profile, flow_stats_profile, l2_error, n_profile_bins, pool_field_maps,
-                      pair_dist_profiles, pool_flow_stats, pool_pair_dist, poiseuille_startup, profile_series_profiles)
+from .profile import (compute_mid_channel_profile, field_map_means, final_profile, flow_stats_profile, grad_stats_profiles, l2_error,
+                      n_profile_bins, pool_field_maps, pair_dist_profiles, pool_flow_stats, pool_grad_stats, pool_pair_dist,
+                      poiseuille_startup, profile_series_profiles)
 
 
 @dataclass
@@ -57,6 +58,9 @@ class RunResult:
 
     pair_dist: list = None  # run / run_sweep / run_ensemble(..., pairs_from=...): the device-side pair statistics of the run, one
                             # dict per band (capi.Context.pair_dist: the integer sums with g, n_neigh, r_min; pair_dist_figures())
+
+    grad_stats: list = None  # run / run_sweep / run_ensemble(..., gradients_from=...): the device-side gradient statistics of the
+                             # run, one dict per band (capi.Context.grad_stats: the sums with the profiles; grad_figures())
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -363,6 +367,62 @@ def pair_dist_figures(prm, pd):
     return dict(r_min_dp=float(whole["r_min"]) / dp, n_neigh=prof[0]["n_neigh"], sigma1_dp=sigma1, seam_dev=seam_dev)
 
 
+def _grad_bands(prm, bands):
+    """the x-bands of a run's gradient statistics: the mid-channel band of the output-point profiles (band 1) unless given"""
+    return [(0.5 * prm.DL, max(prm.dp, prm.h))] if bands is None else bands
+
+
+def _grad_stats_bands(DH, sums):
+    """a channel's sums, one dict per band, each with the profiles of profile.grad_stats_profiles"""
+    return [dict(s, **grad_stats_profiles(DH, s)) for s in sums]
+
+
+def grad_figures(prm, gs, band=0):
+    """Figures of a run's gradient statistics (RunResult.grad_stats, or [capi.Context.grad_stats_sums(b) for b in bands]: one
+    dict per band), on the host, from band `band`:
+      y_mid, shear    the bin centres and the bin-mean shear rate g_xy = du_x/dy (NaN where a bin is empty)
+      shear_exact     the analytic g / (2 nu) (DH - 2 y) at y_mid; its sign follows the body force, as U_max's does
+      L2_shear        l2_error(shear, shear_exact) over the bins at least 2h from a wall; L2_shear_all over all bins (next to a
+                      wall the support is one-sided and the estimate first order: the wall bins read low)
+      tau, tau_line   mu * shear and (slope, intercept) of its least-squares line over the bins at least 2h from a wall;
+                      tau_fit_residual: the largest |tau - line| over those bins
+      tau_wall_bottom, tau_wall_top   the line extrapolated to the walls, as the stress on each wall: line(0) and -line(DH),
+                      to be read beside tau_target = g rho0 DH / 2 (the momentum balance makes tau linear in y)
+      div_rms         sqrt(sum div^2 / count) over the whole band, in units of |U_max| / DH, U_max = g DH^2 / (8 nu)
+      vort_mean       (sum g_yx - sum g_xy) / count over the whole band (zero by symmetry in plane Poiseuille flow)"""
+    b = gs[band]
+    prof = grad_stats_profiles(prm.DH, b)
+    y, shear = prof["y_mid"], prof["gxy_mean"]
+    exact = prm.gravity_g / (2.0 * prm.nu) * (prm.DH - 2.0 * y)
+    inner = (y >= 2.0 * prm.h) & (y <= prm.DH - 2.0 * prm.h)
+    ok = ~np.isnan(shear)
+    nan = float("nan")
+    tau = prm.mu * shear
+    fit = inner & ok
+    slope = icpt = resid = nan
+    if np.count_nonzero(fit) >= 2:
+        slope, icpt = (float(v) for v in np.polyfit(y[fit], tau[fit], 1))
+        resid = float(np.max(np.abs(tau[fit] - (slope * y[fit] + icpt))))
+    count = float(np.sum(b["count"]))
+    u_max = prm.gravity_g * prm.DH * prm.DH / (8.0 * prm.nu)
+    unit = abs(u_max) / prm.DH
+    return dict(y_mid=y, shear=shear, shear_exact=exact,
+                L2_shear=l2_error(np.where(inner, shear, np.nan), exact) if np.any(fit) else nan,
+                L2_shear_all=l2_error(shear, exact) if np.any(ok) else nan,
+                tau=tau, tau_line=(slope, icpt), tau_fit_residual=resid, tau_wall_bottom=icpt, tau_wall_top=-(slope * prm.DH + icpt),
+                tau_target=prm.gravity_g * prm.rho0 * prm.DH / 2,
+                div_rms=float(np.sqrt(np.sum(b["sum_div2"]) / count) / unit) if count > 0 else nan,
+                vort_mean=float((np.sum(b["sum_gyx"]) - np.sum(b["sum_gxy"])) / count) if count > 0 else nan)
+
+
+def _grad_columns(prms, grads):
+    """The gradient columns of a sweep's table, one [M] array each: L2_shear, tau_wall_dev (the larger deviation of
+    tau_wall_bottom / tau_wall_top from tau_target, relative to |tau_target|) and div_rms of grad_figures(prm_m, grad_stats_m)."""
+    figs = [grad_figures(p, g) for p, g in zip(prms, grads)]
+    dev = [max(abs(f["tau_wall_bottom"] - f["tau_target"]), abs(f["tau_wall_top"] - f["tau_target"])) / abs(f["tau_target"]) for f in figs]
+    return dict(L2_shear=np.array([f["L2_shear"] for f in figs]), tau_wall_dev=np.array(dev), div_rms=np.array([f["div_rms"] for f in figs]))
+
+
 def _concat_history(chunks):
     if not chunks:
         return capi.history_dict(np.zeros((0, len(capi.HISTORY_FIELDS))))
@@ -376,7 +436,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
         average_every=1, history_every=None, history_capacity=65536, field_from=None, field_every=1, field_shape=None,
         field_walls=False, probe_points=None, probe_every=1, probe_capacity=65536, probe_from=None, probe_walls=False,
         profiles_every=None, profiles_from=None, profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1,
-        pairs_bins=64, pairs_walls=False, pairs_bands=None):
+        pairs_bins=64, pairs_walls=False, pairs_bands=None, gradients_from=None, gradients_every=1, gradients_walls=False,
+        gradients_bands=None):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -416,7 +477,15 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     [0, 2h), centres at least 2h from both walls (so g(r) is a bulk figure), the whole channel and the bands pairs_bands (None:
     mid-channel and the periodic seam, (DL/2, max(dp, h)) and (0, max(dp, h))), pairs_walls: the fluid-wall histogram too.
     RunResult.pair_dist is one dict per band; pair_dist_figures() gives r_min, the neighbour count, the width of the first
-    shell and the seam's deviation.  A sample costs 1.6-1.9 cell sweeps of the density pass: pairs_every is the control."""
+    shell and the seam's deviation.  A sample costs 1.6-1.9 cell sweeps of the density pass: pairs_every is the control.
+    gradients_from (resident engine; default off): estimate, on the device and inside the step loop, the velocity gradient at
+    every fluid particle (include/sphx.h section 2n) every gradients_every-th step ending at t >= gradients_from and bin it into
+    the reference's profile bins, for the whole channel and the bands gradients_bands (None: the mid-channel band (DL/2,
+    max(dp, h)) as band 1); gradients_walls: the wall particles are partners too (off: they carry the wall's velocity and pull
+    the wall-adjacent bins down).  RunResult.grad_stats is one dict per band; grad_figures() gives the shear-rate profile and its
+    L2 against the analytic one, tau(y) with its line extrapolated to the walls, div_rms and the mean vorticity."""
+    if gradients_from is not None and engine != "resident":
+        raise ValueError("gradients_from needs the resident engine (the gradients are estimated on the device)")
     if pairs_from is not None and engine != "resident":
         raise ValueError("pairs_from needs the resident engine (the pairs are counted on the device)")
     if profiles_every is not None and engine != "resident":
@@ -456,6 +525,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     probes, probe_chunks = None, []
     series, series_chunks = None, []
     pair_dist = None
+    grad_stats = None
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context.from_parts(prm, parts, t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
@@ -480,6 +550,9 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
             if pairs_from is not None:
                 ctx.pair_dist_enable(n_bins=pairs_bins, every=pairs_every, t_from=pairs_from, y_margin=2.0 * prm.h,
                                      with_walls=pairs_walls, bands=_pair_bands(prm, pairs_bands))
+            if gradients_from is not None:
+                ctx.grad_stats_enable(n_bins=n_bins, every=gradients_every, t_from=gradients_from, with_walls=gradients_walls,
+                                      bands=_grad_bands(prm, gradients_bands))
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -527,6 +600,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 series = _concat_profile_series(prm.DH, series_chunks or [ctx.profile_series_sums()])
             if pairs_from is not None:
                 pair_dist = _pair_dist_bands(ctx.pair_dist_sums(), prm.dp)
+            if gradients_from is not None:
+                grad_stats = _grad_stats_bands(prm.DH, [ctx.grad_stats_sums(b) for b in range(1 + len(_grad_bands(prm, gradients_bands)))])
         finally:
             ctx.close()
     elif engine == "mex":
@@ -577,7 +652,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     return _run_result(prm, nf, nt, pos, vel, t=t, steps=int(step), wall_seconds=wall, profile_times=profile_times,
                        mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t, grid_policy=policy,
                        full_profile_u=full_profiles, n_inner=n_inner, time_avg=time_avg, history=history, field_avg=field_avg,
-                       probes=probes, profile_series=series, pair_dist=pair_dist)
+                       probes=probes, profile_series=series, pair_dist=pair_dist, grad_stats=grad_stats)
 
 
 def _run_result(prm, nf, nt, pos, vel, **fields):
@@ -618,7 +693,7 @@ def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
 
 
 def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None, probe=None,
-               profiles=None, pairs=None):
+               profiles=None, pairs=None, gradients=None):
     """The batch run behind run_batch, run_ensemble and run_sweep (`name`, for the refusals): check and default the inputs,
     open the batch with the launch keywords `launch`, enable what was asked for, advance output point by output point, build
     every member's RunResult.
@@ -637,6 +712,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                  raises RuntimeError
       pairs      (pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands): the pair statistics of include/sphx.h section
                  2m with the margin and the default bands of run(); every member gets its pair_dist
+      gradients  (gradients_from, gradients_every, gradients_walls, gradients_bands): the gradient statistics of include/sphx.h
+                 section 2o in the bins and with the default band of run(); every member gets its grad_stats
     -> the members, the wall seconds, the grid policy, with average the raw sums (whole, mid) of all members, and with field the
     raw planes of all members."""
     prms = list(prms)
@@ -677,6 +754,9 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         if pairs:
             b.pair_dist_enable(n_bins=pairs[2], every=pairs[1], t_from=float(pairs[0]), y_margin=2.0 * p0.h, with_walls=pairs[3],
                                bands=_pair_bands(p0, pairs[4]))
+        if gradients:
+            b.grad_stats_enable(n_bins=n_bins, every=gradients[1], t_from=float(gradients[0]), with_walls=gradients[2],
+                                bands=_grad_bands(p0, gradients[3]))
         t = 0.0
         st = None
         while t < p0.t_end - 1e-12:
@@ -715,6 +795,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         planes = b.field_map_sums() if field else None
         empty_series = b.profile_series_sums() if profiles and not schunks[0] else None
         pair_sums = b.pair_dist_sums() if pairs else None
+        grad_sums = [b.grad_stats_sums(k) for k in range(1 + len(_grad_bands(p0, gradients[3])))] if gradients else None  # [band][member]
         members = []
         for m, prm in enumerate(prms):
             extra = {}
@@ -732,6 +813,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                 extra.update(profile_series=_concat_profile_series(prm.DH, schunks[m] or [empty_series[m]], f"member {m}: "))
             if pairs:
                 extra.update(pair_dist=_pair_dist_bands(pair_sums[m], prm.dp))
+            if gradients:
+                extra.update(grad_stats=_grad_stats_bands(prm.DH, [band[m] for band in grad_sums]))
             members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra))
     return members, wall, policy, sums, planes
 
@@ -739,6 +822,11 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
 def _pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands):
     """the `pairs` of _run_batch: None without pairs_from"""
     return None if pairs_from is None else (pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands)
+
+
+def _gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands):
+    """the `gradients` of _run_batch: None without gradients_from"""
+    return None if gradients_from is None else (gradients_from, gradients_every, gradients_walls, gradients_bands)
 
 
 def _field_request(field_from, field_every, field_shape, field_walls):
@@ -778,6 +866,8 @@ class EnsembleResult:
     pooled_field: dict = None  # with field_from, under the condition of `pooled`: profile.pool_field_maps of the members' planes
     pooled_pairs: list = None  # with pairs_from, under the condition of `pooled`: profile.pool_pair_dist of the members' sums, one
                                # dict per band, with the figures of profile.pair_dist_profiles
+    pooled_grad: list = None   # with gradients_from, under the condition of `pooled`: profile.pool_grad_stats of the members' sums,
+                               # one dict per band
 
 
 _PHYSICS = ("mu", "c_f", "p0", "gravity_g", "transport_coeff")
@@ -785,7 +875,8 @@ _PHYSICS = ("mu", "c_f", "p0", "gravity_g", "transport_coeff")
 
 def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_per_particle=0, steps_per_graph=0,
                  rebuild_every=0, log=None, history_every=None, field_from=None, field_every=1, field_shape=None,
-                 field_walls=False, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False, pairs_bands=None):
+                 field_walls=False, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False, pairs_bands=None,
+                 gradients_from=None, gradients_every=1, gradients_walls=False, gradients_bands=None):
     """Time-averaged profiles of M channels of one geometry stepped as one batch (capi.Batch), averaged on the device
     inside the step loop (include/sphx.h section 2c) as run(average_from=...) does for one channel: every
     average_every-th step ending at t >= average_from, whole channel and the mid-channel band (DL/2, max(dp, h)).  The
@@ -794,7 +885,9 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
     lattice.  field_from: every member's velocity map as well (include/sphx.h section 2g), with the keywords of run(): every
     member gets a field_avg, and members that share their physics a pooled_field.  pairs_from: every member's pair statistics
     as well (include/sphx.h section 2m), with the keywords of run(): every member gets a pair_dist, and members that share their
-    physics pooled_pairs (the integers added, the smallest r_min).  Returns an EnsembleResult."""
+    physics pooled_pairs (the integers added, the smallest r_min).  gradients_from: every member's gradient statistics as well
+    (include/sphx.h section 2o), with the keywords of run(): every member gets a grad_stats, and members that share their physics
+    pooled_grad (profile.pool_grad_stats, one dict per band).  Returns an EnsembleResult."""
     prms = list(prms)
     if history_every is not None:
         raise ValueError("run_ensemble records no step history (run_sweep does, for every member)")
@@ -804,9 +897,10 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
         "run_ensemble", prms, parts_list, dict(lanes_per_particle=lanes_per_particle, steps_per_graph=steps_per_graph,
                                                rebuild_every=rebuild_every), log, average=(average_from, average_every),
         field=_field_request(field_from, field_every, field_shape, field_walls),
-        pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands))
+        pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands),
+        gradients=_gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands))
     p0, M = prms[0], len(prms)
-    pooled = pooled_field = pooled_pairs = None
+    pooled = pooled_field = pooled_pairs = pooled_grad = None
     if all(getattr(p, k) == getattr(p0, k) for p in prms for k in _PHYSICS):
         pw, pm = pool_flow_stats(p0.DH, whole), pool_flow_stats(p0.DH, mid)
         pooled = time_average(p0, pw, pm)
@@ -817,8 +911,10 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
             pooled_field = pool_field_maps(p0.DL, p0.DH, planes)
         if pairs_from is not None:
             pooled_pairs = _pair_dist_bands(pool_pair_dist([r.pair_dist for r in members]), p0.dp)
+        if gradients_from is not None:
+            pooled_grad = [pool_grad_stats(p0.DH, [r.grad_stats[b] for r in members]) for b in range(len(members[0].grad_stats))]
     return EnsembleResult(members=members, pooled=pooled, wall_seconds=wall, grid_policy=policy, pooled_field=pooled_field,
-                          pooled_pairs=pooled_pairs)
+                          pooled_pairs=pooled_pairs, pooled_grad=pooled_grad)
 
 
 @dataclass
@@ -859,7 +955,7 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
               field_from=None, field_every=1, field_shape=None, field_walls=False, probe_points=None, probe_every=1,
               probe_capacity=65536, probe_from=None, probe_walls=False, profiles_every=None, profiles_from=None,
               profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False,
-              pairs_bands=None):
+              pairs_bands=None, gradients_from=None, gradients_every=1, gradients_walls=False, gradients_bands=None):
     """A parameter sweep: M channels of one geometry that differ in mu, c_f, p0, gravity_g, transport_coeff, stepped as one
     batch (capi.Batch) with every member's step history recorded on the device, inside the step loop (include/sphx.h
     section 2f) as run(history_every=...) does for one channel.  The members advance output point by output point as in
@@ -876,7 +972,9 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     table the columns t_developed and tau_fit of profile_series_figures(prm_m, series_m).  pairs_from: every member's pair
     statistics as well (include/sphx.h section 2m), with the keywords of run(): each member gets its pair_dist and the table the
     columns r_min_dp, n_neigh, sigma1_dp of pair_dist_figures(prm_m, pair_dist_m) -- the figures that respond to
-    transport_coeff.  A member that lost records to a full buffer raises RuntimeError, which names the member and the
+    transport_coeff.  gradients_from: every member's gradient statistics as well (include/sphx.h section 2o), with the keywords of
+    run(): each member gets its grad_stats and the table the columns L2_shear, tau_wall_dev, div_rms of
+    grad_figures(prm_m, grad_stats_m).  A member that lost records to a full buffer raises RuntimeError, which names the member and the
     capacity the output interval needed.  Returns a SweepResult."""
     prms = list(prms)
     members, wall, policy, _, planes = _run_batch(
@@ -886,7 +984,8 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
         field=_field_request(field_from, field_every, field_shape, field_walls),
         probe=None if probe_points is None else (probe_points, probe_every, probe_capacity, probe_from, probe_walls),
         profiles=None if profiles_every is None else (profiles_every, profiles_from, profiles_capacity, profiles_bands),
-        pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands))
+        pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands),
+        gradients=_gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands))
     table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
     if planes is not None:
         table.update(field_table(prms, [r.field_avg for r in members]))
@@ -896,4 +995,6 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     if pairs_from is not None:
         figs = [pair_dist_figures(p, r.pair_dist) for p, r in zip(prms, members)]
         table.update({k: np.array([f[k] for f in figs]) for k in ("r_min_dp", "n_neigh", "sigma1_dp")})
+    if gradients_from is not None:
+        table.update(_grad_columns(prms, [r.grad_stats for r in members]))
     return SweepResult(members=members, table=table, wall_seconds=wall, grid_policy=policy)

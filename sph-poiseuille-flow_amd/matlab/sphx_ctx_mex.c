@@ -39,6 +39,12 @@
  *   [ff, fw, centres, r2_min, n_samples, t_first, t_last] = sphx_ctx_mex('pairs_read', h, band)
  *       ff, fw: n_bins x 1 pair counts by distance (pair statistics, include/sphx.h section 2l), as doubles: the library's
  *       int64 sums are exact in a double up to 2^53
+ *   sphx_ctx_mex('grad_enable', h, n_bins, every, t_from, det_min, with_walls, bands)   % bands as for stats_enable
+ *   sphx_ctx_mex('grad_disable', h)
+ *   sphx_ctx_mex('grad_sample', h)   % add one sample of the current state now
+ *   [sums, n_samples, t_first, t_last] = sphx_ctx_mex('grad_read', h, band)
+ *       sums: n_bins x 12, one column per field in the order of include/sphx.h section 2n (gradient statistics): count,
+ *       sum g_xx, g_xy, g_yx, g_yy, their four squares, sum div^2, sum omega^2, skipped
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -402,6 +408,45 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)ns);
         if (nlhs > 5) plhs[5] = mxCreateDoubleScalar(t0);
         if (nlhs > 6) plhs[6] = mxCreateDoubleScalar(t1);
+    } else if (strcmp(cmd, "grad_enable") == 0) {
+        sphx_grad_stats_config gc;
+        const mxArray *b;
+        size_t nb, k;
+        arity(cmd, nrhs, 8, nlhs, 0);
+        b = prhs[7];
+        if (!mxIsDouble(b)) mexErrMsgIdAndTxt("SPHX:GradStats:config", "grad_enable: bands must be a double [k x 2] array");
+        nb = mxGetNumberOfElements(b) == 0 ? 0 : mxGetM(b);
+        if (nb > 2 || (nb > 0 && mxGetN(b) != 2)) mexErrMsgIdAndTxt("SPHX:GradStats:config", "grad_enable: bands must be [k x 2], k <= 2");
+        memset(&gc, 0, sizeof(gc));
+        gc.n_bins = (int32_t)mxGetScalar(prhs[2]);
+        gc.every = (int32_t)mxGetScalar(prhs[3]);
+        gc.t_from = mxGetScalar(prhs[4]);
+        gc.det_min = mxGetScalar(prhs[5]);
+        gc.with_walls = mxGetScalar(prhs[6]) != 0.0;
+        gc.n_bands = (int32_t)nb;
+        for (k = 0; k < nb; ++k) { gc.band_x[k] = mxGetDoubles(b)[k]; gc.band_hw[k] = mxGetDoubles(b)[k + nb]; }
+        ok(sphx_ctx_grad_stats_enable(handle(prhs[1]), &gc));
+    } else if (strcmp(cmd, "grad_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_grad_stats_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "grad_sample") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_grad_stats_sample(handle(prhs[1])));
+    } else if (strcmp(cmd, "grad_read") == 0) {
+        sphx_ctx *c;
+        int band, n_bins = 0;
+        int64_t ns = 0;
+        double t0 = 0.0, t1 = 0.0;
+        arity(cmd, nrhs, 3, nlhs, 4);
+        c = handle(prhs[1]);
+        band = (int)mxGetScalar(prhs[2]);
+        ok(sphx_ctx_grad_stats_read(c, band, 0, &n_bins, NULL, NULL, NULL, NULL));
+        /* [SPHX_GRAD_STATS_FIELDS][n_bins] is the column-major n_bins x 12 matrix */
+        plhs[0] = mxCreateDoubleMatrix((mwSize)n_bins, SPHX_GRAD_STATS_FIELDS, mxREAL);
+        ok(sphx_ctx_grad_stats_read(c, band, n_bins, NULL, mxGetDoubles(plhs[0]), &ns, &t0, &t1));
+        if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)ns);
+        if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(t0);
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar(t1);
     } else if (strcmp(cmd, "destroy") == 0) {
         arity(cmd, nrhs, 2, nlhs, 0);
         sphx_ctx_destroy(handle(prhs[1]));

@@ -11,6 +11,8 @@ records of the device's profile series (include/sphx.h section 2j) as one profil
 pair_histogram: one sample of the device's pair statistics (include/sphx.h section 2l) in numpy, count for count;
 pair_dist_profiles: its sums as g(r), the neighbour count and r_min; pool_pair_dist: the sums of several channels as one;
 pair_histogram_part: the sample of one slab of a ring (the centres it owns against everything it holds).
+velocity_gradients: the renormalised velocity-gradient estimate of the device's gradient statistics (include/sphx.h section 2n)
+in numpy; grad_stats_sums: one binned sample; grad_stats_profiles: the sums as profiles; pool_grad_stats: several channels' as one.
 """
 from __future__ import annotations
 
@@ -466,4 +468,174 @@ def pool_pair_dist(sums_list):
         out.update(n_samples=int(sum(s["n_samples"] for s in sums_list)),
                    t_first=min((s["t_first"] for s in sampled), default=float("nan")),
                    t_last=max((s["t_last"] for s in sampled), default=float("nan")))
+    return out
+
+
+# ---- gradient statistics (include/sphx.h sections 2n, 2o) ----
+
+# the twelve values per bin and band, in the order the library writes them
+GRAD_FIELDS = ("count", "sum_gxx", "sum_gxy", "sum_gyx", "sum_gyy", "sum_gxx2", "sum_gxy2", "sum_gyx2", "sum_gyy2", "sum_div2",
+               "sum_vort2", "skipped")
+GRAD_COMPONENTS = ("gxx", "gxy", "gyx", "gyy")  # G_ab = d u_a / d x_b
+GRAD_MAX_BINS = 640
+
+
+def velocity_gradients(pos, vel, vol, DL, h, wall_pos=None, wall_vel=None, wall_vol=None, chunk=512, acc=np.float64, reverse=False):
+    """The velocity gradient at every fluid particle by the renormalised estimator of include/sphx.h section 2n, in numpy -- the
+    definition k_grad_stats is tested against.  pos, vel [n, 2]: the fluid particles; vol: their volumes V_j = mass_j / rho0 (an
+    array [n] or one number); wall_pos, wall_vel [m, 2] and wall_vol [m]: wall particles that are partners too, with these
+    velocities, or None.  Over every partner j != i with 1e-24 < r2 < (2h)^2, nearest image in x:
+        d = r_i - r_j,  w_j = V_j W'(|d|) / |d|,  M_i = - sum w_j d (x) d,  A_i = sum w_j (v_j - v_i) (x) d,  G_i = A_i M_i^-1
+    -> dict(G [n, 4]: g_xx, g_xy, g_yx, g_yy with G_ab = d u_a / d x_b, NaN where det M_i == 0; det [n]: det M_i).
+    Chunked over particles sorted by x, a chunk against the partners within 2h of its x-range.  acc / reverse exist for the tests alone: the type the
+    per-particle sums are accumulated in and whether the partners are added in reversed order, which together measure the
+    rounding error of these sums (tests/grad_stats_cases.py); no caller in the package sets them."""
+    pos, vel = np.asarray(pos, dtype=np.float64).reshape(-1, 2), np.asarray(vel, dtype=np.float64).reshape(-1, 2)
+    n = len(pos)
+    vol = np.broadcast_to(np.asarray(vol, dtype=np.float64), (n,))
+    sigma_h, rcut2, half = 10.0 / (7.0 * np.pi * h * h) / h, (2.0 * h) * (2.0 * h), DL / 2
+    margin = 2.0 * h * (1.0 + 1e-9) + 1e-12 * DL
+    S = np.zeros((7, n), dtype=acc)  # m11, m12, m22, a11, a12, a21, a22
+    cx = np.mod(pos[:, 0], DL)
+    order_c = np.argsort(cx, kind="stable")
+
+    def sweep(p_pos, p_vel, p_vol, same):
+        px = np.mod(p_pos[:, 0], DL)
+        order_p = np.argsort(px, kind="stable")
+        pxs = px[order_p]
+        for a in range(0, n, chunk):
+            ci = order_c[a:a + chunk]
+            lo, hi = cx[ci[0]] - margin, cx[ci[-1]] + margin
+            if hi - lo >= DL:
+                cand = np.sort(order_p)
+            else:
+                parts = [order_p[np.searchsorted(pxs, lo, "left"):np.searchsorted(pxs, hi, "right")]]
+                if lo < 0.0:
+                    parts.append(order_p[np.searchsorted(pxs, lo + DL, "left"):])
+                if hi > DL:
+                    parts.append(order_p[:np.searchsorted(pxs, hi - DL, "right")])
+                cand = np.unique(np.concatenate(parts))
+            if reverse:
+                cand = cand[::-1]
+            dx = pos[ci, 0][:, None] - p_pos[cand, 0][None, :]
+            dx = np.where(dx > half, dx - DL, np.where(dx < -half, dx + DL, dx))
+            dy = pos[ci, 1][:, None] - p_pos[cand, 1][None, :]
+            r2 = dx * dx + dy * dy
+            keep = (r2 > 1e-24) & (r2 < rcut2)
+            if same:
+                keep &= ci[:, None] != cand[None, :]
+            r = np.sqrt(np.where(keep, r2, 1.0))
+            q = r / h
+            dW = np.where(q < 1.0, sigma_h * (-3.0 * q + 2.25 * q * q), -sigma_h * 0.75 * (2.0 - q) * (2.0 - q))
+            w = np.where(keep, p_vol[cand][None, :] * dW / r, 0.0)
+            dvx = p_vel[cand, 0][None, :] - vel[ci, 0][:, None]
+            dvy = p_vel[cand, 1][None, :] - vel[ci, 1][:, None]
+            wx, wy = w * dx, w * dy
+            for k, term in enumerate((-wx * dx, -wx * dy, -wy * dy, dvx * wx, dvx * wy, dvy * wx, dvy * wy)):
+                S[k, ci] += term.astype(acc, copy=False).sum(axis=1)
+
+    sweep(pos, vel, vol, True)
+    if wall_pos is not None and len(wall_pos):
+        wall_pos = np.asarray(wall_pos, dtype=np.float64).reshape(-1, 2)
+        sweep(wall_pos, np.asarray(wall_vel, dtype=np.float64).reshape(-1, 2),
+              np.broadcast_to(np.asarray(wall_vol, dtype=np.float64), (len(wall_pos),)), False)
+    m11, m12, m22, a11, a12, a21, a22 = S
+    det = m11 * m22 - m12 * m12
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = 1.0 / det
+        G = np.stack([(a11 * m22 - a12 * m12) * inv, (a12 * m11 - a11 * m12) * inv, (a21 * m22 - a22 * m12) * inv,
+                      (a22 * m11 - a21 * m12) * inv], axis=1)
+    return dict(G=G.astype(np.float64), det=det.astype(np.float64))
+
+
+def grad_scales(vmax, h, n):
+    """The fixed-point scales of one sample of the gradient statistics, as the device picks them: with n <= 2^L particles and
+    the bound 2^e > max(16 vmax / h, 2^-60), a component is summed in units of 2^-s1, its square of 2^-s2, div^2 and vort^2 of
+    2^-s3: s1 = 62 - L - e, s2 = 62 - L - 2e, s3 = 60 - L - 2e.  -> dict(s1, s2, s3, bound)."""
+    L = 0
+    while L < 31 and (1 << L) < n:
+        L += 1
+    x = 16.0 * float(vmax) / h
+    e = int(np.frexp(x if x > 2.0 ** -60 else 2.0 ** -60)[1])  # (a NaN vmax leaves the floor)
+    return dict(s1=62 - L - e, s2=62 - L - 2 * e, s3=60 - L - 2 * e, bound=float(np.ldexp(1.0, e)))
+
+
+def grad_stats_sums(pos, vel, vol, DL, DH, h, n_bins, bands=(), det_min=0.05, wall_pos=None, wall_vel=None, wall_vol=None, vmax=None,
+                    gradients=None, quantise=False):
+    """One sample of the gradient statistics of include/sphx.h section 2n in numpy -- the oracle of k_grad_stats: the estimate
+    of velocity_gradients binned with the flow statistics' rules (compute_binned_profile_mean's bins over [0, DH], y outside
+    dropped; band 0 the whole channel, bands [(x_centre, half_width), ...] by in_band).  A particle with det M <= det_min, a
+    component that is not finite or one above the bound of grad_scales(vmax, h, n) is counted in `skipped`, not summed; vmax:
+    the clock's max |v| (None: that of vel).  -> one dict of the GRAD_FIELDS as [n_bins] arrays per band.  gradients: the
+    result of velocity_gradients of the same state, to share it between calls.  quantise (set by the tests alone; no caller in
+    the package sets it): every particle's terms are rounded to the device's fixed-point grid before they are added (a component to 2^-s1, a square to 2^-s2, div^2 and vort^2 to 2^-s3 of
+    grad_scales), as k_grad_stats rounds them: the sums are then the device's up to the rounding of the estimate itself, and
+    a value far below the quantum -- the 1e-16 a symmetric lattice leaves in g_xx -- is the exact zero the device records."""
+    pos, vel = np.asarray(pos, dtype=np.float64).reshape(-1, 2), np.asarray(vel, dtype=np.float64).reshape(-1, 2)
+    g = gradients if gradients is not None else velocity_gradients(pos, vel, vol, DL, h, wall_pos, wall_vel, wall_vol)
+    G, det = g["G"], g["det"]
+    if vmax is None:
+        vmax = float(np.sqrt(np.max(np.sum(vel * vel, axis=1)))) if len(vel) else 0.0
+    sc = grad_scales(vmax, h, len(pos))
+    bound = sc["bound"]
+    with np.errstate(invalid="ignore"):
+        ok = (det > det_min) & np.all(np.abs(G) <= bound, axis=1)  # (a NaN or an infinity fails the comparison)
+    edges = np.linspace(0.0, DH, n_bins + 1)
+    inside = (pos[:, 1] >= edges[0]) & (pos[:, 1] <= edges[-1])
+    bin_id = np.minimum(np.searchsorted(edges, pos[:, 1], side="right") - 1, n_bins - 1)
+    Gz = np.where(ok[:, None], G, 0.0)
+    div, vort = Gz[:, 0] + Gz[:, 3], Gz[:, 2] - Gz[:, 1]
+    values = [np.ones(len(pos))] + [Gz[:, k] for k in range(4)] + [Gz[:, k] * Gz[:, k] for k in range(4)] + [div * div, vort * vort]
+    if quantise:
+        shifts = [0] + [sc["s1"]] * 4 + [sc["s2"]] * 4 + [sc["s3"]] * 2
+        values = [np.ldexp(np.rint(np.ldexp(v, k)), -k) for v, k in zip(values, shifts)]
+    out = []
+    for mine in [inside] + [inside & in_band(pos[:, 0], DL, x, hw) for x, hw in bands]:
+        take, skip = mine & ok, mine & ~ok
+        d = {f: np.bincount(bin_id[take], weights=v[take], minlength=n_bins).astype(np.float64) for f, v in zip(GRAD_FIELDS, values)}
+        d["skipped"] = np.bincount(bin_id[skip], minlength=n_bins).astype(np.float64)
+        out.append(d)
+    return out
+
+
+def grad_stats_profiles(DH, sums):
+    """The sums of one band (capi.Context.grad_stats_sums(band), grad_stats_sums(...)[band]) as profiles: y_mid, count, skipped
+    and per bin the mean and the standard deviation of each component over the particle samples (gxx_mean, gxx_std, ...,
+    sqrt(max(sum g^2 / N - mean^2, 0))), div_rms = sqrt(sum div^2 / N), vort_mean = (sum g_yx - sum g_xy) / N and vort_rms;
+    NaN where a bin has no sample.  n_samples, t_first and t_last are handed on where the sums have them."""
+    s = {f: np.asarray(sums[f], dtype=np.float64).ravel() for f in GRAD_FIELDS}
+    N = s["count"]
+    n_bins = len(N)
+    edges = np.linspace(0.0, DH, n_bins + 1)
+    empty = N == 0
+    Nd = np.where(empty, 1.0, N)
+    out = dict(y_mid=0.5 * (edges[:-1] + edges[1:]), count=N, skipped=s["skipped"])
+    for c in GRAD_COMPONENTS:
+        m = s["sum_" + c] / Nd
+        sd = np.sqrt(np.maximum(s["sum_" + c + "2"] / Nd - m * m, 0.0))
+        out[c + "_mean"], out[c + "_std"] = np.where(empty, np.nan, m), np.where(empty, np.nan, sd)
+    out["div_rms"] = np.where(empty, np.nan, np.sqrt(s["sum_div2"] / Nd))
+    out["vort_mean"] = np.where(empty, np.nan, (s["sum_gyx"] - s["sum_gxy"]) / Nd)
+    out["vort_rms"] = np.where(empty, np.nan, np.sqrt(s["sum_vort2"] / Nd))
+    for k in ("n_samples", "t_first", "t_last"):
+        if k in sums:
+            out[k] = sums[k]
+    return out
+
+
+def pool_grad_stats(DH, sums_list):
+    """The sums of the same band of several channels (the members of a batch or of an ensemble) as one profile: the GRAD_FIELDS
+    added in member order and turned into grad_stats_profiles of the total (with the total's sums beside it); n_samples is the
+    total over the members, t_first / t_last the earliest / latest sample; n_members = M."""
+    sums_list = list(sums_list)
+    if not sums_list:
+        raise ValueError("pool_grad_stats needs the sums of at least one member")
+    total = {f: np.asarray(sums_list[0][f], dtype=np.float64).ravel().copy() for f in GRAD_FIELDS}
+    for member in sums_list[1:]:
+        for f in GRAD_FIELDS:
+            total[f] = total[f] + np.asarray(member[f], dtype=np.float64).ravel()
+    n_samples, t_first, t_last = _window(sums_list)
+    total.update(n_samples=n_samples, t_first=t_first, t_last=t_last)
+    out = grad_stats_profiles(DH, total)
+    out.update({f: total[f] for f in GRAD_FIELDS}, n_members=len(sums_list))
     return out
