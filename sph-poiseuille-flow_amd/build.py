@@ -19,7 +19,12 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 # sphx_resident.hip: the leading scalar / pointer parameters of a kernel, up to 14 dwords, arrive in registers with the wave
 # (csrc/sphx_kernels.hpp, "Leading arguments"); the option counts parameters and stops at the first struct passed by value
-SOURCE_FLAGS = {"sphx_resident.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"]}
+SOURCE_FLAGS = {"sphx_resident.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"],
+                "sphx_devtest.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"]}
+# Test-only second library (csrc/sphx_devtest.hip): the __device__ functions of the headers, each wrapped in a kernel of its own
+# for tests/devtest.py.  Built with sphx_resident.hip's flags from the same headers; never linked into libsphx.so.
+DEVTEST_SOURCE = "sphx_devtest.hip"
+DEVTEST_LIB = os.path.join(CSRC, "libsphx_devtest.so")
 
 
 def _hipcc() -> str:
@@ -54,7 +59,29 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+    build_devtest(force=force, verbose=verbose)
     return LIB
+
+
+def build_devtest(force: bool = False, verbose: bool = False, csrc: str = CSRC, lib: str | None = None) -> str:
+    """The test-only harness library.  csrc / lib: build it from another copy of csrc/ (a deliberately altered header, see
+    profiles/r33_device_formulas.txt) into another file, for tests/devtest.py's SPHX_DEVTEST_LIB."""
+    hipcc = _hipcc()
+    lib = lib or (DEVTEST_LIB if csrc == CSRC else os.path.join(csrc, "libsphx_devtest.so"))
+    src = os.path.join(csrc, DEVTEST_SOURCE)
+    obj = src[:-4] + ".o"
+    hdrs = [os.path.join(csrc, h) for h in HEADERS]
+    if force or _stale(obj, [src, os.path.abspath(__file__)] + hdrs):
+        cmd = [hipcc] + FLAGS + SOURCE_FLAGS[DEVTEST_SOURCE] + ["-c", src, "-o", obj]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    if force or _stale(lib, [obj]):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, obj]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    return lib
 
 
 if __name__ == "__main__":

@@ -74,6 +74,8 @@ __device__ __forceinline__ double spline_W(const KernelConst &kc, double r)
 //     W(q)  = sigma/4       [a^3 - 4 b^3]        q < 1: 1 - 1.5 q^2 + 0.75 q^3,   1 <= q < 2: 0.25 (2 - q)^3
 //     W'(q) = -0.75 sigma/h [a^2 - 4 b^2]        q < 1: -3 q + 2.25 q^2,          1 <= q < 2: -0.75 (2 - q)^2
 // -- the same polynomials as spline_dW / spline_W (sph_physics_mex.c:76-105), differently rounded (a few 1e-16 of sigma).
+// (The compiler fuses 2 - r * inv_h into one multiply-add: q is never rounded, and the clamps act on the exact product.  An r
+//  whose product rounds to 2.0 from below gets a = 1e-16 and the true W' = -0.75 sigma/h 1e-32, not zero.)
 __device__ __forceinline__ double spline_dW_sel(const KernelConst &kc, double r)
 {
     const double q = r * kc.inv_h;
@@ -99,7 +101,9 @@ __device__ __forceinline__ double spline_W_sel(const KernelConst &kc, double r)
 }
 
 // 1/x for a positive normal x of moderate magnitude (here: lengths of order h): hardware estimate + two Newton steps,
-// ~1 ulp, 5 instructions against the 11 of an IEEE division with its scaling and fix-up
+// 5 instructions against the 11 of an IEEE division with its scaling and fix-up.  Measured on gfx950 over 1e-12 .. 1e12, powers
+// of two and every h in use: relative error at most 0.49 ulp (2^-52), powers of two exact; tests/test_gpu_device_formulas.py
+// asserts 2 ulp.  With one Newton step: 7.9 ulp.  Outside the domain (0, subnormal, inf) the result is NaN.
 __device__ __forceinline__ double rcp_nr(double x)
 {
     double y = __builtin_amdgcn_rcp(x);
@@ -109,7 +113,9 @@ __device__ __forceinline__ double rcp_nr(double x)
     return fma(y, e, y);
 }
 
-// 1/sqrt(x) for 1e-24 < x < huge (squared pair distances): hardware estimate + one third-order correction step
+// 1/sqrt(x) for 1e-24 < x < huge (squared pair distances): hardware estimate + one third-order correction step.  Measured on
+// gfx950 over (1e-24, 1e12] and 1e300: relative error at most 0.59 ulp (2^-52) -- numpy's correctly rounded 1.0 / sqrt(x) has
+// 0.73 on the same inputs; asserted at 2 ulp.  With a first-order correction, fma(y * e, 0.5, y): 15.9 ulp.
 __device__ __forceinline__ double rsqrt_nr(double x)
 {
     const double y = __builtin_amdgcn_rsq(x);
