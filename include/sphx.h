@@ -888,7 +888,7 @@ int sphx_batch_pair_dist_read(sphx_batch *batch, int band, int capacity, int *n_
  *    finite or a negative half-width, or the allocation fails: the context then goes on without gradient statistics),
  *    SPHX:GradStats:band, SPHX:GradStats:capacity (sums given and capacity < n_bins), SPHX:GradStats:disabled (SPHX_ERR_STATE:
  *    a call that needs the sampler while it is off); every call on a slab context fails with SPHX_ERR_ARG,
- *    SPHX:GradStats:slab.  A refused enable leaves a running sampler, and its sums, untouched.
+ *    SPHX:GradStats:slab (the gradient statistics of a ring: sphx_slab_gstats_*, section 3a).  A refused enable leaves a running sampler, and its sums, untouched.
  * ---------------------------------------------------------------------------------------------- */
 
 #define SPHX_GRAD_STATS_FIELDS 12
@@ -1015,8 +1015,8 @@ int sphx_slab_snapshot(sphx_ctx *ctx, int capacity, int *n, double *x, double *y
 
 /* ------------------------------------------------------------------------------------------------
  * 3a. Samplers of a slab ring: the flow statistics of section 2a, the step history of section 2d, the velocity-field
- *    map of section 2e, the point probes of section 2h, the profile series of section 2j and the pair statistics of
- *    section 2l (the last three described with their calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that
+ *    map of section 2e, the point probes of section 2h, the profile series of section 2j, the pair statistics of
+ *    section 2l and the gradient statistics of section 2n (the last four described with their calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that
  *    a ring reports its time-averaged profile, the settling of its wall shear, its averaged field and its profile at every
  *    sampled step without a snapshot per sample.  The config structs, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* / SPHX:Field:*
  *    identifiers are those of sections 2a / 2d / 2e; sphx_ctx_flow_stats_*,
@@ -1143,6 +1143,33 @@ int sphx_slab_pairs_reset(sphx_ctx *ctx);
 /* The slab's partial sums of one band; arguments as sphx_ctx_pair_dist_read. */
 int sphx_slab_pairs_read(sphx_ctx *ctx, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw, int64_t *centres,
                          double *r2_min, int64_t *n_samples, double *t_first, double *t_last);
+/* Gradient statistics of a ring (the sampler of section 2n; k_grad_stats_s).  The names say gstats: no function of this header
+ * has both "slab" and "grad" in its name.  The config, its checks and limits (n_bins * (n_bands + 1) <= 640), the bins, the
+ * gating and the SPHX:GradStats:* identifiers are those of section 2n.  A sample is a sum over particles, so it is divided
+ * like the flow statistics': a slab bins, at the end of a sampled step, the estimates of the fluid particles it owns (those
+ * sphx_slab_snapshot marks owned, with 0 <= y <= DH), and what a read returns are the slab's PARTIAL sums -- the ring's twelve
+ * fields, count and skipped included, are the element-wise sums over the ranks; n_samples, t_first and t_last come from the
+ * clock and are the same on every rank, also on a slab that owns no particle of a band.  The PARTNERS of a particle are all
+ * the other fluid particles the slab holds, its halo copies included -- in the cell columns next to the owned ones they carry
+ * the finished step's positions and velocities up to the summation order of their own neighbour lists, a few ulps, and their
+ * particles' masses -- and, with with_walls, the wall particles the slab holds.  The slab's window is open: the first slab
+ * holds the last slab's particles at x - DL and the last slab the first slab's at x + DL, so a partner across the periodic
+ * seam enters with its plain dx and no minimum image; a ring is at least 20h long, so no copy is a particle's own image
+ * within 2h.  Band membership goes by x mod DL, whatever frame a slab keeps x in.  The bound 2^e > 16 vmax / h that decides
+ * between summed and skipped comes from the ring's maximum speed and is the same on every rank; the fixed-point quantum
+ * comes from the number of particles the slab holds and is the slab's own.  The estimate differentiates the copies' state,
+ * so a ring's sums equal a single context's within a few hundred times the copies' few ulps, not to the last bits; count and
+ * skipped are equal wherever no particle sits at a bin or band edge, at det M = det_min or at the bound.  A refused enable
+ * leaves a running sampler, its sums and a prepared graph as they are.  SPHX:GradStats:disabled: a reset or a read while the
+ * sampler is off; disable is a no-op then.  There is no "sample now" call.  sphx_ctx_grad_stats_* keep refusing a slab
+ * (SPHX:GradStats:slab). */
+int sphx_slab_gstats_enable(sphx_ctx *ctx, const sphx_grad_stats_config *cfg);
+int sphx_slab_gstats_disable(sphx_ctx *ctx);
+/* Clears the sums and the sample count; the configuration stays. */
+int sphx_slab_gstats_reset(sphx_ctx *ctx);
+/* The slab's partial sums of one band; arguments as sphx_ctx_grad_stats_read. */
+int sphx_slab_gstats_read(sphx_ctx *ctx, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples, double *t_first,
+                          double *t_last);
 
 #ifdef __cplusplus
 }

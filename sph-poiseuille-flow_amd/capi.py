@@ -122,6 +122,7 @@ EXPORTS = [
     "sphx_slab_probes_enable", "sphx_slab_probes_disable", "sphx_slab_probes_read",
     "sphx_slab_pseries_enable", "sphx_slab_pseries_disable", "sphx_slab_pseries_read",
     "sphx_slab_pairs_enable", "sphx_slab_pairs_disable", "sphx_slab_pairs_reset", "sphx_slab_pairs_read",
+    "sphx_slab_gstats_enable", "sphx_slab_gstats_disable", "sphx_slab_gstats_reset", "sphx_slab_gstats_read",
     "sphx_batch_create", "sphx_batch_destroy", "sphx_batch_advance", "sphx_batch_enqueue_steps", "sphx_batch_sync",
     "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
     "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",
@@ -234,13 +235,14 @@ _STATE = ("pos", "vel", "drho_dt", "mass", "wall_vel")
 
 class _Sampled:
     """What a context, a batch and a slab of a ring bind alike: the flow statistics' sums, the step history's records, the
-    profile series' raw records and the pair statistics' sums.  A subclass names its symbol stem, the words its profile-series
-    and pair-statistics calls carry behind the stem (a slab's are sphx_slab_pseries_* and sphx_slab_pairs_*), the word of its
-    "not enabled on this ..." errors and whether it has many channels: a context or a slab returns one dict / (records,
-    n_dropped) pair, a batch a list with one entry per member."""
+    profile series' raw records and the pair and gradient statistics' sums.  A subclass names its symbol stem, the words its
+    profile-series, pair-statistics and gradient-statistics calls carry behind the stem (a slab's are sphx_slab_pseries_*,
+    sphx_slab_pairs_* and sphx_slab_gstats_*), the word of its "not enabled on this ..." errors and whether it has many
+    channels: a context or a slab returns one dict / (records, n_dropped) pair, a batch a list with one entry per member."""
     _stem = _where = None
     _series = "profile_series_"
     _pairs = "pair_dist_"
+    _grads = "grad_stats_"
     _many = False
 
     def _call(self, name, *args):
@@ -411,6 +413,45 @@ class _Sampled:
         n_bands = self._pairs_on()[1]
         per_band = [self._pair_dist_band(b) for b in range(n_bands)]
         return self._each([[per_band[b][k] for b in range(n_bands)] for k in range(self._channels())])
+
+    # ---- gradient statistics (include/sphx.h sections 2n, 2o, 3a): what grad_stats_* of a context or a batch and grads_part_* of
+    # a slab (slab.HipSlabEngine) share -- the argument checks, the calls behind the stem and the read of the sums ----
+    def _grads_enable(self, n_bins, every, t_from, det_min, with_walls, bands):
+        p0 = self._params0()
+        cfg = grad_stats_config(p0, n_bins, every, t_from, det_min, with_walls, bands)
+        self._call(self._grads + "enable", C.byref(cfg))
+        # (n_bins, n_bands incl. band 0) while the gradient statistics are on
+        self._grad_stats = (int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5))), int(cfg.n_bands) + 1)
+
+    def _grads_disable(self):
+        self._call(self._grads + "disable")
+        self._grad_stats = None
+
+    def _grads_on(self):
+        return _enabled(getattr(self, "_grad_stats", None), "GradStats", f"gradient statistics are not enabled on this {self._where}")
+
+    def _grads_reset(self):
+        self._grads_on()
+        self._call(self._grads + "reset")
+
+    def _grad_stats_band(self, band):
+        """one band's raw sums: one dict per channel"""
+        n_bins, n_bands = self._grads_on()
+        if not _is_int(band) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:GradStats:band", f"band must be an integer in 0..{n_bands - 1}")
+        m = self._channels()
+        sums = np.zeros((m, len(GRAD_FIELDS), n_bins))
+        ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
+        nb = C.c_int(0)
+        self._call(self._grads + "read", C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), ptr(sums), ns.ctypes.data_as(C.POINTER(C.c_int64)),
+                   ptr(t0), ptr(t1))
+        assert nb.value == n_bins, (nb.value, n_bins)
+        out = []
+        for k in range(m):
+            d = {f: sums[k, j].copy() for j, f in enumerate(GRAD_FIELDS)}
+            d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
+            out.append(d)
+        return out
 
 
 class _Stepped(_Sampled):
@@ -632,22 +673,13 @@ class _Stepped(_Sampled):
         with_walls: the wall particles are partners too, with the wall's velocity -- off by default, because they pull the
         estimate next to a wall towards the wall's velocity.  (Re)configures and zeroes the sums.  A batch: one config for all
         members, each sampled on its own clock."""
-        p0 = self._params0()
-        cfg = grad_stats_config(p0, n_bins, every, t_from, det_min, with_walls, bands)
-        self._call("grad_stats_enable", C.byref(cfg))
-        # (n_bins, n_bands incl. band 0) while the gradient statistics are on
-        self._grad_stats = (int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5))), int(cfg.n_bands) + 1)
+        self._grads_enable(n_bins, every, t_from, det_min, with_walls, bands)
 
     def grad_stats_disable(self):
-        self._call("grad_stats_disable")
-        self._grad_stats = None
-
-    def _grads_on(self):
-        return _enabled(getattr(self, "_grad_stats", None), "GradStats", f"gradient statistics are not enabled on this {self._where}")
+        self._grads_disable()
 
     def grad_stats_reset(self):
-        self._grads_on()
-        self._call("grad_stats_reset")
+        self._grads_reset()
 
     def grad_stats_sample(self):
         """Add one sample of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
@@ -657,22 +689,7 @@ class _Stepped(_Sampled):
     def grad_stats_sums(self, band=0):
         """The raw sums of one band: the twelve profile.GRAD_FIELDS as [n_bins] arrays (count and skipped hold integers),
         n_samples, t_first, t_last; a batch: one such dict per member, from one read of all members."""
-        n_bins, n_bands = self._grads_on()
-        if not _is_int(band) or not 0 <= band < n_bands:
-            raise SphxError(SPHX_ERR_ARG, "SPHX:GradStats:band", f"band must be an integer in 0..{n_bands - 1}")
-        m = self._channels()
-        sums = np.zeros((m, len(GRAD_FIELDS), n_bins))
-        ns, t0, t1 = np.zeros(m, dtype=np.int64), np.zeros(m), np.zeros(m)
-        nb = C.c_int(0)
-        self._call("grad_stats_read", C.c_int(int(band)), C.c_int(n_bins), C.byref(nb), ptr(sums), ns.ctypes.data_as(C.POINTER(C.c_int64)),
-                   ptr(t0), ptr(t1))
-        assert nb.value == n_bins, (nb.value, n_bins)
-        out = []
-        for k in range(m):
-            d = {f: sums[k, j].copy() for j, f in enumerate(GRAD_FIELDS)}
-            d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
-            out.append(d)
-        return self._each(out)
+        return self._each(self._grad_stats_band(band))
 
     def grad_stats(self, band=0):
         """One band's profiles (profile.grad_stats_profiles): y_mid, count, skipped, the mean and standard deviation of each

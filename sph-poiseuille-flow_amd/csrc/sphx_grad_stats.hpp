@@ -1,5 +1,5 @@
-// sphx_grad_stats.hpp -- velocity-gradient statistics of a resident context (include/sphx.h section 2n) and of every member of
-// a batch (section 2o, k_grad_stats_b): a slot sampler (sphx_slot_sample.hpp) that estimates the velocity gradient
+// sphx_grad_stats.hpp -- velocity-gradient statistics of a resident context (include/sphx.h section 2n), of every member of
+// a batch (section 2o, k_grad_stats_b) and of a slab of a ring (section 3a, k_grad_stats_s, at the end): a slot sampler (sphx_slot_sample.hpp) that estimates the velocity gradient
 // G_ab = d u_a / d x_b at every fluid particle and bins g_xx, g_xy, g_yx, g_yy, their squares, the squared divergence and the
 // squared vorticity into the flow statistics' y-bins and x-bands.  The one sampler that describes the GRADIENT of the velocity:
 // the shear-rate profile du_x/dy (hence tau(y) = mu du_x/dy), div v and the vorticity.  profile.velocity_gradients is the numpy
@@ -122,6 +122,9 @@ __device__ __forceinline__ double grad_value(int k, unsigned long long v, const 
 // The sample of one channel closing the step slot of parity q, on clock clk, by the gridDim.x workgroups of a grid row; s is the
 // state the step left (pos, vel, mass and the cell ranges and binned cells of the layout it is stored in); isum / dsum / h are
 // that channel's own.
+// kSlab: the channel is a slab of a ring -- of the clk->n slots it holds only those it owns (owns()) are particles of the
+// sample, every held slot is a partner (k_grad_stats_s).
+template <bool kSlab = false>
 __device__ __forceinline__ void grad_stats_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s, const Walls &w,
                                                 const GradStatsArgs &a, unsigned long long *isum, double *dsum, GradStatsHead *h)
 {
@@ -140,6 +143,9 @@ __device__ __forceinline__ void grad_stats_body(const Clock *clk, int q, const G
     for (long long i0 = (long long)blockIdx.x * kGradCentres + grp; i0 < (long long)n; i0 += (long long)gridDim.x * kGradCentres) {
         const int i = (int)i0;
         const double2 pi = s.pos[i];
+        if constexpr (kSlab) {
+            if (!owns(g, pi.x, s.cell[i])) continue;  // (a halo copy: its owner bins it)
+        }
         if (!(pi.y >= 0.0 && pi.y <= a.DH)) continue;  // outside [0, DH]: dropped, as discretize does
         const double2 vi = s.vel[i];
         int cx, cy;
@@ -239,6 +245,50 @@ __global__ __launch_bounds__(kGradBlock) void k_grad_stats_b(Members mb, int q, 
     const Phys ph = mb.ph[m];
     const size_t off = (size_t)m * (size_t)a.block;
     grad_stats_body(mb.clk + m, q, g, ph, member_set(mb, m, s), w, a, a.isum + off, a.dsum + off, a.head + m);
+}
+
+// Slab of a ring (sphx_slab_gstats_*): the sample is a sum over PARTICLES, so it is divided like the flow statistics' -- a slab
+// bins the estimates of the particles it OWNS (owns(): the column the slot was binned into, own_c0 <= cx < own_c1) and the
+// ring's sums are the element-wise sums of the slabs', count and skipped included.  Nothing about the estimate changes:
+// grad_add, the 2 x 2 solve, the quantisation, the LDS counters and stats_finish_sample are the body's.  The loop runs over the
+// clk->n slots held, owned and copies alike, with the workgroups of the slab's CAPACITY (a captured step graph outlives a
+// re-binning); a copy is passed over as a particle of the sample and met as a partner: every held fluid slot j != i in the
+// columns cx - 1 .. cx + 1 of the layout's cell ranges, and with walls the slab's wall particles in the same columns
+// (Walls::a: volume and velocity).
+//
+// Why the three-column sweep still suffices.  The argument of sphx_pair_dist.hpp is about the columns a particle and its
+// partner were BINNED into, and a slab bins what it holds, copies included, into one grid of its window (Grid::periodic = 0:
+// neighbour_column leaves out only columns beyond the window).  An owned particle has own_c0 <= cx < own_c1, so cx - 1 and
+// cx + 1 lie in [own_c0 - 1, own_c1]: at most the FIRST halo column on either side, of the halo_cols >= 4 the window holds.
+//
+// Why the halo copies are usable.  Unlike the pair statistics this sampler reads pos, VEL and MASS of a partner, and it
+// differentiates them.  The copies binned in own - 1 and own + 1 are complete and were stepped like everything held: in front
+// of phase 3 -- where launch_slab_samplers sits, behind k_slab_pack3 -- they carry the finished step's position and velocity
+// up to the summation order of their own neighbour lists, the premise k_field_map_s reads vel on.  The view's mass is the
+// layout array of the layout the step ran in, which a copy entered with its particle's mass at the last re-binning: the
+// premise of k_point_probes_s.  A copy's state is therefore its owner's only to a few ulps, and the estimate amplifies such a
+// difference a few hundred times (tests/slab_grad_stats_cases.py: SENSITIVITY): a ring's sums are a single context's within
+// that, not to the 1e-12 of two single contexts.
+//
+// The window is open (half_DL = +inf: min_image is a no-op).  The first slab holds the last slab's particles at x - DL and the
+// last slab the first slab's at x + DL, in the slab's own frame, so a pair across the periodic seam has its plain dx: there
+// is nothing to fold.  A copy is never the particle's own image within 2h: the image lies DL away, and a ring needs
+// n_ranks >= 2 slabs of at least halo_cols + 1 >= 5 columns of >= 2h each (SPHX:Slab:width), so DL >= 20h; nor does one
+// window hold a partner twice, because it covers less than one period (SPHX:Slab:width).  Band membership goes by
+// stats_in_band on the slab-frame x, whose fmod brings x < 0 and x >= DL back into [0, DL), as k_flow_stats_s relies on.
+//
+// The scales.  clk->vmax at the sampling point is the ring's all-reduced maximum, not the slab's own (k_flow_stats_s and
+// k_profile_series_s quantise with it too), and h is every rank's: the bound 2^e, hence whether a particle is summed or
+// skipped, is decided the same way on every rank.  L comes from the held count clk->n, which bounds the owned count, so no
+// overflow; it differs between the slabs, and with it only the fixed-point quantum 2^-(62-L-e) a slab rounds to.
+//
+// Every slab finishes the sample (stats_finish_sample: the last workgroup out, or the one workgroup of a small slab) and
+// stamps its head, whether or not it owns a particle of any band: n_samples, t_first and t_last come from the clock and agree
+// between the ranks.  The dynamic LDS is k_grad_stats's, up to 61 440 B, which a launch is granted without an attribute of
+// the kernel symbol (k_flow_stats_s asks for as much).
+__global__ __launch_bounds__(kGradBlock) void k_grad_stats_s(const Clock *clk, int q, Grid g, Phys ph, FluidSet s, Walls w, GradStatsArgs a)
+{
+    grad_stats_body<true>(clk, q, g, ph, s, w, a, a.isum, a.dsum, a.head);
 }
 
 }  // namespace sphx

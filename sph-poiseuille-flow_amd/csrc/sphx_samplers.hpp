@@ -1,7 +1,7 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
 // the velocity-field map (2e; 2g), the point probes (2h; 2i), the profile series (2j; 2k), the pair statistics (2l; 2m,
-// sphx_pair_dist.hpp) and the gradient statistics (2n; 2o, sphx_grad_stats.hpp) -- the first six also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// sphx_pair_dist.hpp) and the gradient statistics (2n; 2o, sphx_grad_stats.hpp) -- all seven also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -32,7 +32,7 @@ constexpr SamplerNames kSeriesNames{"ProfileSeries", "the profile series of a sl
 constexpr SamplerNames kPairNames{"PairDist", "the pair statistics of a slab are sphx_slab_pairs_* (include/sphx.h section 3a)",
                                   "pair statistics are not enabled on this ",
                                   "the sums could not be set up: "};
-constexpr SamplerNames kGradNames{"GradStats", "gradient statistics are not available on slab contexts",
+constexpr SamplerNames kGradNames{"GradStats", "the gradient statistics of a slab are sphx_slab_gstats_* (include/sphx.h section 3a)",
                                   "gradient statistics are not enabled on this ", "the sums could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
@@ -1297,6 +1297,10 @@ SPHX_EXPORT int sphx_ctx_grad_stats_read(sphx_ctx *c, int band, int capacity, in
 // the pairs whose centre it owns, against every slot it holds, halo copies included (the field map's premise for the
 // partners), and the ring's histogram is the slabs' added up, its r2_min their minimum (sphx_slab_pairs_*: no function of
 // include/sphx.h carries both "slab" and "pair_dist" in its name).
+// The gradient statistics: a sample is a sum over particles, so a slab bins the estimates of the particles it owns; an estimate
+// takes its partners from every slot the slab holds, halo copies included -- their positions, velocities and masses (the field
+// map's and the probes' premises) -- and the ring's sums are the slabs' added up, count and skipped included
+// (sphx_slab_gstats_*: no function of include/sphx.h carries both "slab" and "grad" in its name).
 
 namespace {
 
@@ -1304,11 +1308,11 @@ namespace {
 // later) and in front of everything of phase 3: the clock is the finished step's, S[1-q] holds the owned particles' new state,
 // Vol / B (c->tmp) and the layout arrays (cell, mass) are those of the layout the step ran in -- clk->n is still that
 // layout's count (k_slab_unpack3 sets the new one), so a re-binning step needs no src_of.  One self-skipping launch each,
-// on the slab's stream, in the order statistics, history, map, probes, profile series, pair statistics; all off: nothing is
-// enqueued, and a sampler that is off adds nothing to what the others enqueue.
+// on the slab's stream, in the order statistics, history, map, probes, profile series, pair statistics, gradient statistics;
+// all off: nothing is enqueued, and a sampler that is off adds nothing to what the others enqueue.
 void launch_slab_samplers(sphx_ctx *c)
 {
-    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on && !c->pseries.on && !c->pairs.on) return;
+    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on && !c->pseries.on && !c->pairs.on && !c->grads.on) return;
     const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
     const FluidSet s = c->view(1 - q, 0);
@@ -1349,6 +1353,12 @@ void launch_slab_samplers(sphx_ctx *c)
     if (c->pairs.on)
         launch_s(c, "k_pair_dist_s", k_pair_dist_s, dim3(pair_dist_blocks((size_t)c->cap)), dim3(kPairBlock), c->pairs.shmem(), clk, q,
                  c->grid, s, c->walls, pair_dist_args(c, c->pairs.cfg.every));
+    // (pos, VEL, MASS, the binned cells and the cell ranges of S[1-q]: the halo copies in own - 1 and own + 1 as for the map,
+    //  their mass as for the probes; the particles of the sample are the owned slots of the clk->n held, so the workgroups come
+    //  from the capacity; with_walls was settled at enable from the slab's own wall particles)
+    if (c->grads.on)
+        launch_s(c, "k_grad_stats_s", k_grad_stats_s, dim3(grad_stats_blocks((size_t)c->cap)), dim3(kGradBlock), c->grads.shmem(), clk, q,
+                 c->grid, c->phys, s, c->walls, grad_stats_args(c, c->grads.cfg.every));
 }
 
 // The rank of slab c's ring that owns a probe at x, folded into [0, DL): rank r when edge(r) <= x < edge(r + 1), with
@@ -1670,6 +1680,50 @@ SPHX_EXPORT int sphx_slab_pairs_read(sphx_ctx *c, int band, int capacity, int *n
     SPHX_TRY
     const PairDist &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::pairs, kPairNames);
     pair_dist_read(p, c->stream, [c] { slab_settle(c); }, band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_gstats_enable(sphx_ctx *c, const sphx_grad_stats_config *cfg)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    GradStats checked;
+    checked.check(c->prm, cfg, c->walls.n > 0);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
+    slab_samplers_changed(c);
+    grad_stats_enable(c->grads, c->prm, cfg, 1, c->walls.n > 0, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_gstats_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    if (c->grads.on) {
+        slab_samplers_changed(c);
+        sampler_off(c->grads, c->sched, c->stream);
+    }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_gstats_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    GradStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::grads, kGradNames);
+    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_gstats_read(sphx_ctx *c, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples, double *t_first,
+                                      double *t_last)
+{
+    SPHX_TRY
+    const GradStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::grads, kGradNames);
+    grad_stats_read(f, c->stream, [c] { slab_settle(c); }, band, capacity, n_bins, sums, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -12,7 +12,8 @@ pair_histogram: one sample of the device's pair statistics (include/sphx.h secti
 pair_dist_profiles: its sums as g(r), the neighbour count and r_min; pool_pair_dist: the sums of several channels as one;
 pair_histogram_part: the sample of one slab of a ring (the centres it owns against everything it holds).
 velocity_gradients: the renormalised velocity-gradient estimate of the device's gradient statistics (include/sphx.h section 2n)
-in numpy; grad_stats_sums: one binned sample; grad_stats_profiles: the sums as profiles; pool_grad_stats: several channels' as one.
+in numpy; grad_stats_sums: one binned sample; grad_stats_profiles: the sums as profiles; pool_grad_stats: several channels' as one;
+grad_stats_sums_part: the sample of one slab of a ring (the particles it owns, estimated from everything it holds).
 """
 from __future__ import annotations
 
@@ -480,7 +481,8 @@ GRAD_COMPONENTS = ("gxx", "gxy", "gyx", "gyy")  # G_ab = d u_a / d x_b
 GRAD_MAX_BINS = 640
 
 
-def velocity_gradients(pos, vel, vol, DL, h, wall_pos=None, wall_vel=None, wall_vol=None, chunk=512, acc=np.float64, reverse=False):
+def velocity_gradients(pos, vel, vol, DL, h, wall_pos=None, wall_vel=None, wall_vol=None, chunk=512, acc=np.float64, reverse=False,
+                       fold=True):
     """The velocity gradient at every fluid particle by the renormalised estimator of include/sphx.h section 2n, in numpy -- the
     definition k_grad_stats is tested against.  pos, vel [n, 2]: the fluid particles; vol: their volumes V_j = mass_j / rho0 (an
     array [n] or one number); wall_pos, wall_vel [m, 2] and wall_vol [m]: wall particles that are partners too, with these
@@ -489,24 +491,27 @@ def velocity_gradients(pos, vel, vol, DL, h, wall_pos=None, wall_vel=None, wall_
     -> dict(G [n, 4]: g_xx, g_xy, g_yx, g_yy with G_ab = d u_a / d x_b, NaN where det M_i == 0; det [n]: det M_i).
     Chunked over particles sorted by x, a chunk against the partners within 2h of its x-range.  acc / reverse exist for the tests alone: the type the
     per-particle sums are accumulated in and whether the partners are added in reversed order, which together measure the
-    rounding error of these sums (tests/grad_stats_cases.py); no caller in the package sets them."""
+    rounding error of these sums (tests/grad_stats_cases.py); no caller in the package sets them.  fold=False: the OPEN window of
+    a slab of a ring (grad_stats_sums_part) -- x is taken as it stands, dx = x_i - x_j with no nearest image, and DL is not used."""
     pos, vel = np.asarray(pos, dtype=np.float64).reshape(-1, 2), np.asarray(vel, dtype=np.float64).reshape(-1, 2)
     n = len(pos)
     vol = np.broadcast_to(np.asarray(vol, dtype=np.float64), (n,))
     sigma_h, rcut2, half = 10.0 / (7.0 * np.pi * h * h) / h, (2.0 * h) * (2.0 * h), DL / 2
     margin = 2.0 * h * (1.0 + 1e-9) + 1e-12 * DL
     S = np.zeros((7, n), dtype=acc)  # m11, m12, m22, a11, a12, a21, a22
-    cx = np.mod(pos[:, 0], DL)
+    cx = np.mod(pos[:, 0], DL) if fold else pos[:, 0]
     order_c = np.argsort(cx, kind="stable")
 
     def sweep(p_pos, p_vel, p_vol, same):
-        px = np.mod(p_pos[:, 0], DL)
+        px = np.mod(p_pos[:, 0], DL) if fold else p_pos[:, 0]
         order_p = np.argsort(px, kind="stable")
         pxs = px[order_p]
         for a in range(0, n, chunk):
             ci = order_c[a:a + chunk]
             lo, hi = cx[ci[0]] - margin, cx[ci[-1]] + margin
-            if hi - lo >= DL:
+            if not fold:
+                cand = np.sort(order_p[np.searchsorted(pxs, lo, "left"):np.searchsorted(pxs, hi, "right")])
+            elif hi - lo >= DL:
                 cand = np.sort(order_p)
             else:
                 parts = [order_p[np.searchsorted(pxs, lo, "left"):np.searchsorted(pxs, hi, "right")]]
@@ -518,7 +523,8 @@ def velocity_gradients(pos, vel, vol, DL, h, wall_pos=None, wall_vel=None, wall_
             if reverse:
                 cand = cand[::-1]
             dx = pos[ci, 0][:, None] - p_pos[cand, 0][None, :]
-            dx = np.where(dx > half, dx - DL, np.where(dx < -half, dx + DL, dx))
+            if fold:
+                dx = np.where(dx > half, dx - DL, np.where(dx < -half, dx + DL, dx))
             dy = pos[ci, 1][:, None] - p_pos[cand, 1][None, :]
             r2 = dx * dx + dy * dy
             keep = (r2 > 1e-24) & (r2 < rcut2)
@@ -573,6 +579,12 @@ def grad_stats_sums(pos, vel, vol, DL, DH, h, n_bins, bands=(), det_min=0.05, wa
     a value far below the quantum -- the 1e-16 a symmetric lattice leaves in g_xx -- is the exact zero the device records."""
     pos, vel = np.asarray(pos, dtype=np.float64).reshape(-1, 2), np.asarray(vel, dtype=np.float64).reshape(-1, 2)
     g = gradients if gradients is not None else velocity_gradients(pos, vel, vol, DL, h, wall_pos, wall_vel, wall_vol)
+    return _grad_stats_binned(pos, vel, g, None, DL, DH, h, n_bins, bands, det_min, vmax, quantise)
+
+
+def _grad_stats_binned(pos, vel, g, rows, DL, DH, h, n_bins, bands, det_min, vmax, quantise):
+    """the estimates g of the particles pos (rows: those that are binned, None: all of them) as one sample's sums per band; the
+    scales are those of len(pos) particles"""
     G, det = g["G"], g["det"]
     if vmax is None:
         vmax = float(np.sqrt(np.max(np.sum(vel * vel, axis=1)))) if len(vel) else 0.0
@@ -582,6 +594,8 @@ def grad_stats_sums(pos, vel, vol, DL, DH, h, n_bins, bands=(), det_min=0.05, wa
         ok = (det > det_min) & np.all(np.abs(G) <= bound, axis=1)  # (a NaN or an infinity fails the comparison)
     edges = np.linspace(0.0, DH, n_bins + 1)
     inside = (pos[:, 1] >= edges[0]) & (pos[:, 1] <= edges[-1])
+    if rows is not None:
+        inside &= np.asarray(rows, dtype=bool)
     bin_id = np.minimum(np.searchsorted(edges, pos[:, 1], side="right") - 1, n_bins - 1)
     Gz = np.where(ok[:, None], G, 0.0)
     div, vort = Gz[:, 0] + Gz[:, 3], Gz[:, 2] - Gz[:, 1]
@@ -596,6 +610,20 @@ def grad_stats_sums(pos, vel, vol, DL, DH, h, n_bins, bands=(), det_min=0.05, wa
         d["skipped"] = np.bincount(bin_id[skip], minlength=n_bins).astype(np.float64)
         out.append(d)
     return out
+
+
+def grad_stats_sums_part(pos, vel, vol, owned, DL, DH, h, n_bins, bands=(), det_min=0.05, wall_pos=None, wall_vel=None, wall_vol=None,
+                         vmax=None, quantise=False):
+    """One sample of a SLAB's gradient statistics (include/sphx.h section 3a) in numpy -- the oracle of k_grad_stats_s.  pos, vel
+    [n, 2] and vol: every fluid particle the slab holds, in the slab's own frame (its halo copies at x - DL or x + DL where they
+    come from across the seam); owned [n] bool: the rows it bins.  The estimate of an owned row takes every other row and, where
+    given, the wall particles the slab holds as partners, with dx = x_i - x_j as it stands and no fold: the window is open
+    (velocity_gradients(fold=False)).  Bands go by in_band, whose mod brings x < 0 and x >= DL back.  The scales are those of the
+    n rows HELD (grad_scales(vmax, h, n)) and vmax is the ring's (None: that of vel, which is the slab's own).  -> grad_stats_sums'
+    list of dicts, the slab's partial sums: slab.pool_ring_grad_stats of the ranks' gives the channel's."""
+    pos, vel = np.asarray(pos, dtype=np.float64).reshape(-1, 2), np.asarray(vel, dtype=np.float64).reshape(-1, 2)
+    g = velocity_gradients(pos, vel, vol, DL, h, wall_pos, wall_vel, wall_vol, fold=False)
+    return _grad_stats_binned(pos, vel, g, owned, DL, DH, h, n_bins, bands, det_min, vmax, quantise)
 
 
 def grad_stats_profiles(DH, sums):

@@ -15,8 +15,8 @@ Layers:
   HipSlabEngine    -- the per-rank compute engine (libsphx slab context)
   SlabDriver       -- step loop = engine.compute -> exchange -> engine.finish
   pool_ring_* / ring_* / all_reduce_ring_*
-                   -- the ring's flow statistics, step history, profile series and pair statistics from the slabs' partial
-                      sums, its field map from the slabs' blocks of node columns, and its point probes from the slabs'
+                   -- the ring's flow statistics, step history, profile series, pair statistics and gradient statistics from
+                      the slabs' partial sums, its field map from the slabs' blocks of node columns, and its point probes from the slabs'
                       owned probes
   bench_main()     -- bench.py's multi-GPU leg
 """
@@ -31,7 +31,8 @@ import time
 import numpy as np
 
 from . import capi as _capi
-from .profile import FIELD_MAP_PLANES, field_map_means, flow_stats_profile, pair_dist_profiles, profile_series_profiles
+from .profile import (FIELD_MAP_PLANES, GRAD_FIELDS, field_map_means, flow_stats_profile, grad_stats_profiles, pair_dist_profiles,
+                      profile_series_profiles)
 
 HALO_COLS = 4  # four dependent neighbour passes per step, each reaching one >=2h column further
 
@@ -131,8 +132,12 @@ class HipSlabEngine(_capi._Sampled):
     pairs_part_enable / _disable / _reset / pairs_part_sums are the pair statistics (over sphx_slab_pairs_*): the pairs whose
     CENTRE this slab owns, against everything it holds -- partial sums, which pool_ring_pair_dist (ring_pair_dist_sums /
     ring_pair_dist, all_reduce_ring_pair_dist) adds up, taking the smallest r2_min; g(r) of partial sums would mislead, so the
-    engine has no pair_dist().  Enabling or disabling drops a graph made by graph_prepare()."""
-    _stem, _where, _series, _pairs = "sphx_slab_", "slab", "pseries_", "pairs_"
+    engine has no pair_dist().
+    grads_part_enable / _disable / _reset / grads_part_sums are the gradient statistics (over sphx_slab_gstats_*): the estimates
+    of the particles this slab OWNS, their partners taken from everything it holds -- partial sums, which pool_ring_grad_stats
+    (ring_grad_stats_sums / ring_grad_stats, all_reduce_ring_grad_stats) adds up; means of partial sums would mislead, so the
+    engine has no grad_stats().  Enabling or disabling drops a graph made by graph_prepare()."""
+    _stem, _where, _series, _pairs, _grads = "sphx_slab_", "slab", "pseries_", "pairs_", "gstats_"
 
     def __init__(self, prm, parts, rank, world, device, lanes_per_particle=0, halo_cols=HALO_COLS, t_end=None,
                  pos=None, vel=None, drho_dt=None, native=False, rebuild_every=0, skin_h=0.0, hip_stream=None):
@@ -145,6 +150,7 @@ class HipSlabEngine(_capi._Sampled):
         self._flow_stats = None  # (n_bins, n_bands incl. band 0) while the flow statistics are on
         self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
         self._pair_dist = None  # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
+        self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
         capi.set_device(device)
         if not native:
             import torch
@@ -353,6 +359,25 @@ class HipSlabEngine(_capi._Sampled):
         (int64), centres, r2_min, r_min, n_samples, t_first, t_last.  pool_ring_pair_dist adds the ranks' up."""
         return self._pair_dist_bands()
 
+    # ---- gradient statistics (include/sphx.h section 3a): the estimates of the particles this slab owns -- PARTIAL sums ----
+    def grads_part_enable(self, n_bins=0, every=1, t_from=0.0, det_min=0.05, with_walls=False, bands=()):
+        """A context's grad_stats_enable (capi._Stepped; the same argument checks, capi.grad_stats_config) for the ring: this
+        slab estimates, inside run() / group_run(), the velocity gradient at every fluid particle it OWNS -- from everything it
+        holds, its halo copies included, and with_walls its wall particles -- bins it, and stamps every sampled step even when
+        it owns no particle of a band.  (Re)configures and zeroes the sums; drops a graph made by graph_prepare()."""
+        self._grads_enable(n_bins, every, t_from, det_min, with_walls, bands)
+
+    def grads_part_disable(self):
+        self._grads_disable()
+
+    def grads_part_reset(self):
+        self._grads_reset()
+
+    def grads_part_sums(self, band=0) -> dict:
+        """This slab's partial sums of one band so far, the dict of capi.Context.grad_stats_sums(band): the twelve
+        profile.GRAD_FIELDS as [n_bins] arrays, n_samples, t_first, t_last.  pool_ring_grad_stats adds the ranks' up."""
+        return self._grad_stats_band(band)[0]
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self.capi.lib().sphx_ctx_destroy(self._h)
@@ -539,6 +564,68 @@ def ring_pair_dist(engines) -> list:
     r_min) in every band's dict: what driver.pair_dist_figures takes."""
     dp = engines[0].params.dp
     return [dict(d, **pair_dist_profiles(d, dp)) for d in ring_pair_dist_sums(engines)]
+
+
+def _grad_shape(sums, r):
+    """n_bins of one rank's gradient sums of one band: the twelve GRAD_FIELDS, one value per bin each"""
+    try:
+        shapes = {np.shape(np.asarray(sums[f])) for f in GRAD_FIELDS}
+    except (KeyError, TypeError, IndexError) as e:
+        raise ValueError(f"rank {r}: the gradient statistics of a slab are a dict with the twelve fields of profile.GRAD_FIELDS ({e!r})")
+    if len(shapes) != 1 or len(next(iter(shapes))) != 1:
+        raise ValueError(f"rank {r}: the twelve fields hold shapes {sorted(shapes)}, one value per bin expected")
+    return next(iter(shapes))[0]
+
+
+def _grad_head(sums, r):
+    """(n_samples, t_first, t_last) of one rank's sums, None where it carries none (profile.grad_stats_sums_part)"""
+    have = [k in sums for k in _HEAD]
+    if any(have) and not all(have):
+        raise ValueError(f"rank {r} carries some of n_samples, t_first and t_last and not the others")
+    return tuple(sums[k] for k in _HEAD) if all(have) else None
+
+
+def pool_ring_grad_stats(sums_list) -> dict:
+    """The ring's gradient statistics of one band (the dict of capi.Context.grad_stats_sums(band)) from the ranks' partial sums
+    (HipSlabEngine.grads_part_sums(band) or one band of profile.grad_stats_sums_part, in rank order): the twelve GRAD_FIELDS
+    added in rank order, count and skipped included.  n_samples, t_first and t_last, where the parts carry them, are rank 0's
+    and are NOT added: the slabs of one ring sampled the same steps (unlike the members of profile.pool_grad_stats).  ValueError
+    for an empty list and when the number of bins, n_samples, t_first or t_last differ between the ranks."""
+    sums_list = list(sums_list)
+    if not sums_list:
+        raise ValueError("the gradient statistics of a ring need the sums of at least one slab")
+    shapes = [_grad_shape(s, r) for r, s in enumerate(sums_list)]
+    heads = [_grad_head(s, r) for r, s in enumerate(sums_list)]
+    for r, n in enumerate(shapes):
+        if n != shapes[0]:
+            raise ValueError(f"rank {r} holds {n} bins, rank 0 {shapes[0]}: the slabs of one ring share the config")
+    for r, h in enumerate(heads):
+        if (h is None) != (heads[0] is None):
+            raise ValueError(f"rank {r} and rank 0 do not both carry n_samples, t_first and t_last")
+    if heads[0] is not None:
+        _check_heads_agree(heads)
+    out = {}
+    for f in GRAD_FIELDS:
+        total = np.array(sums_list[0][f], dtype=np.float64)
+        for s in sums_list[1:]:
+            total = total + np.asarray(s[f], dtype=np.float64)
+        out[f] = total
+    if heads[0] is not None:
+        out.update(dict(zip(_HEAD, heads[0])))
+    return out
+
+
+def ring_grad_stats_sums(engines) -> list:
+    """The gradient statistics of an in-process ring, one dict of pooled sums per band (pool_ring_grad_stats of every slab's)."""
+    n_bands = engines[0]._grads_on()[1]
+    return [pool_ring_grad_stats([e.grads_part_sums(b) for e in engines]) for b in range(n_bands)]
+
+
+def ring_grad_stats(engines) -> list:
+    """The gradient statistics of an in-process ring with the profiles of profile.grad_stats_profiles (y_mid, gxy_mean, div_rms,
+    ...) in every band's dict: what driver.grad_figures takes."""
+    DH = engines[0].params.DH
+    return [dict(d, **grad_stats_profiles(DH, d)) for d in ring_grad_stats_sums(engines)]
 
 
 def _check_blocks_partition(shapes):
@@ -840,6 +927,31 @@ def all_reduce_ring_pair_dist(part, dist, group=None) -> list:
                  centres=int(counts[b, 2 * n_bins]), r2_min=float(r2[b]), r_min=float(np.sqrt(r2[b])))
         d.update({k: d0[k] for k in _HEAD})
         out.append(d)
+    return out
+
+
+def all_reduce_ring_grad_stats(sums, dist, group=None) -> dict:
+    """One rank per process: the ring's gradient statistics of one band from this rank's partial sums
+    (HipSlabEngine.grads_part_sums(band)), as pool_ring_grad_stats; every rank gets them.  Whether a rank's own dict is well
+    formed, the number of bins and the heads are all-gathered and checked first; then the twelve fields, stacked, are
+    all-reduced with SUM.  Collective; raises on every rank when a dict is malformed or the bins, n_samples, t_first or t_last
+    differ between the ranks -- every rank makes the same calls up to the refusal, so the group stays in step."""
+    try:
+        n_bins, why = _grad_shape(sums, "?"), None
+        head = [float(sums[k]) for k in _HEAD]
+    except (ValueError, KeyError, TypeError) as e:
+        n_bins, head, why = -1, [0.0] * len(_HEAD), str(e)
+    rows = _all_gathered(dist, [float(n_bins), 0.0 if why is None else 1.0] + head, group)
+    for r, row in enumerate(rows):
+        if row[1] != 0.0:
+            raise ValueError(f"rank {r}'s gradient statistics are malformed" + (f": {why}" if why else ""))
+    for r, row in enumerate(rows):
+        if row[0] != rows[0][0]:
+            raise ValueError(f"rank {r} holds {int(row[0])} bins, rank 0 {int(rows[0][0])}: the slabs of one ring share the config")
+    _check_heads_agree([tuple(row[2:]) for row in rows])
+    total = _all_reduced(dist, np.stack([np.asarray(sums[f], dtype=np.float64) for f in GRAD_FIELDS]), group)
+    out = {f: total[j] for j, f in enumerate(GRAD_FIELDS)}
+    out.update({k: sums[k] for k in _HEAD})
     return out
 
 
