@@ -942,6 +942,95 @@ int sphx_batch_grad_stats_read(sphx_batch *batch, int band, int capacity, int *n
                                double *t_first, double *t_last);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2p. Particle tracers: chosen particles followed step by step, recorded on the device, inside the step loop.  The other
+ *     samplers are Eulerian -- they report what passes a bin, a node or a point; a tracer record follows the particle.  In
+ *     laminar Poiseuille flow a fluid element never leaves its streamline, so every cross-stream displacement of a tracer is
+ *     numerical, and u_x of a tracer against the analytic u(y) at its own y is the Lagrangian velocity error.
+ *
+ *  Tracers: T of them, 1 <= T <= n_fluid, each a fluid row number of the caller's order (0 <= id < n_fluid: the row of
+ *    sphx_ctx_download), given at enable and copied, in any order.  A duplicate, an id out of range or a wall row
+ *    (n_fluid <= id < n_total) is refused.
+ *  Values: SPHX_TRACER_FIELDS = 4 per tracer and record: x, y, u_x, u_y of the particle, copied from the pos and vel the step
+ *    slot left -- exactly what sphx_ctx_download would return in that row, x wrapped into the period as the state holds it,
+ *    no arithmetic on the values.  Column k of a record is tracer k of the caller's list.
+ *  Records: one per sampled step: `step` and `t` (two doubles, as the probes and the history store them) and the T x 4
+ *    values, in the arrays times[capacity][2] and values[capacity][T][4].  `capacity` records live in device memory and are
+ *    filled in step order; when the buffer is full further records are dropped and counted in n_dropped; it does not wrap
+ *    (the semantics of sections 2d and 2h).  capacity >= 1, and capacity * T * 4 <= 1 << 27 doubles.
+ *  Gating: as in the other samplers.  A step is recorded when its step count (sphx_status.step after it) is a multiple of
+ *    `every` and it ends at t >= t_from.  Dual-rate contexts record once per outer step.  A step slot that did not run
+ *    records nothing.  sphx_ctx_tracers_sample appends a record of the state now, without gating.
+ *  n_missing: every id of the list must be met in exactly one slot of the population.  The kernel counts the tracers it met
+ *    and adds T minus that count to a sticky counter, reported by the read and cleared by enable and by a draining read.  On
+ *    a context and on a member of a batch it is always 0: it is the invariant of the library's id bookkeeping.
+ *  Determinism: a column has exactly one writer and the values are copies: records are bit-identical between runs, between a
+ *    member of a batch and a standalone context, between replayed and eager step slots, and whatever the particle layout.
+ *  Off by default.  With it off a step slot enqueues exactly the launches it does without this feature; on, every step slot
+ *    ends with one more launch (k_tracers, behind the other samplers; it skips itself on the steps gated out) that is captured
+ *    in the replayed graphs; enable / disable re-capture them.  Independent of the other samplers.  Cost: one pass over the
+ *    ids of the population per sampled step (there is no map from id to slot on the device).
+ *  Errors: SPHX:Tracers:config (NULL config or ids, n_tracers outside 1 .. n_fluid, a duplicate id, an id out of range, a
+ *    wall row, every < 1, capacity < 1 or capacity * n_tracers * 4 > 1 << 27, non-finite t_from, or the allocation fails:
+ *    the context then goes on without tracers), SPHX:Tracers:disabled (SPHX_ERR_STATE: a call that needs the tracers while
+ *    they are off), SPHX:Tracers:capacity (the caller's arrays are smaller than n_records); every call on a slab context
+ *    fails with SPHX_ERR_ARG, SPHX:Tracers:slab.  A refused enable leaves running tracers, and their records, untouched.
+ * ---------------------------------------------------------------------------------------------- */
+
+#define SPHX_TRACER_FIELDS 4
+
+typedef struct sphx_tracers_config {
+    int32_t n_tracers;   /* T, 1 .. n_fluid                                                        */
+    int32_t every;       /* record every `every`-th completed step (step count % every == 0), >= 1 */
+    int32_t capacity;    /* records the device buffer holds, >= 1                                  */
+    double t_from;       /* only steps ending at t >= t_from                                       */
+    const int32_t *ids;  /* [n_tracers] fluid rows of the caller's order, 0-based; copied at enable */
+} sphx_tracers_config;
+
+/* (Re)configure and empty the buffer; waits for the stream.  Off by default. */
+int sphx_ctx_tracers_enable(sphx_ctx *ctx, const sphx_tracers_config *cfg);
+/* Stop recording (no-op when off); the records are dropped. */
+int sphx_ctx_tracers_disable(sphx_ctx *ctx);
+/* Append one record of the current state (what sphx_ctx_download would return) now, without gating. */
+int sphx_ctx_tracers_sample(sphx_ctx *ctx);
+/* The records so far, in step order: times [capacity][2] and values [capacity][n_tracers][SPHX_TRACER_FIELDS], row-major
+ * (times / values NULL: that array is not copied; both NULL: only the counts are reported and capacity is not checked);
+ * ids [n_tracers]: the list as given at enable (NULL: not copied).  Waits for and settles everything enqueued, like
+ * sphx_ctx_download.  drain != 0: the buffer is emptied and n_dropped and n_missing zeroed after copying. */
+int sphx_ctx_tracers_read(sphx_ctx *ctx, int capacity, double *times, double *values, int32_t *ids, int *n_tracers,
+                          int *n_records, int64_t *n_dropped, int64_t *n_missing, int drain);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2q. Particle tracers of a batch (section 2b): the tracers of section 2p for every member at once.
+ *
+ *  One config and one id list for all members (they share a geometry, hence the row numbering); `capacity` is per member.
+ *  Every member has its own record buffer, n_records, n_dropped and n_missing, and is recorded on its own clock with the
+ *  gating of section 2p, so a member that sits out slots records nothing in them and its counters are not touched.  A
+ *  member's records are bit for bit those of a standalone context with the same parameters and config that took the same
+ *  steps: the layout decides which thread copies a particle, not what is copied.  After a realignment (section 2b) a member's
+ *  state itself differs from a standalone context's within floating-point rounding, and its records are that state's: what
+ *  sphx_batch_download returns in the tracked rows, bit for bit.  With tracers on, every step slot of the batch ends with one recording launch for all members (k_tracers_b, behind the batch's
+ *  other samplers); off, a slot enqueues exactly the launches it does without this feature.
+ *  Memory: n_members * capacity * (2 + n_tracers * 4) doubles; n_members * capacity * n_tracers * 4 must not exceed
+ *  1 << 27 doubles.  A refused enable leaves running tracers, and their records, untouched.
+ *  Errors: SPHX:Batch:null (NULL batch), SPHX:Tracers:config (as in section 2p, with the total over the members),
+ *  SPHX:Tracers:disabled, SPHX:Tracers:capacity (the caller's capacity is below the largest n_records of any member).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* (Re)configure and empty every member's buffer; waits for the stream. */
+int sphx_batch_tracers_enable(sphx_batch *batch, const sphx_tracers_config *cfg);
+/* Stop recording (no-op when off); the records are dropped. */
+int sphx_batch_tracers_disable(sphx_batch *batch);
+/* settles; appends a record of what sphx_batch_download returns, every member, without gating */
+int sphx_batch_tracers_sample(sphx_batch *batch);
+/* One call for all members.  times is [n_members][capacity][2] and values [n_members][capacity][n_tracers][SPHX_TRACER_FIELDS],
+ * row-major: member m's block lies behind member m - 1's, its records fill rows 0 .. n_records[m] - 1 and the other rows are
+ * left as they are.  ids is [n_tracers]; n_records, n_dropped and n_missing are [n_members]; any pointer may be NULL.
+ * Settles first, as sphx_batch_download does.  drain != 0: every member's buffer is emptied and its counters zeroed after
+ * copying. */
+int sphx_batch_tracers_read(sphx_batch *batch, int capacity, double *times, double *values, int32_t *ids, int *n_tracers,
+                            int *n_records, int64_t *n_dropped, int64_t *n_missing, int drain);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU). The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

@@ -83,6 +83,15 @@ class SphxGradStatsConfig(C.Structure):
                 ("with_walls", C.c_int32), ("n_bands", C.c_int32), ("band_x", C.c_double * 2), ("band_hw", C.c_double * 2)]
 
 
+class SphxTracersConfig(C.Structure):
+    _fields_ = [("n_tracers", C.c_int32), ("every", C.c_int32), ("capacity", C.c_int32), ("t_from", C.c_double),
+                ("ids", C.POINTER(C.c_int32))]
+
+
+# the values of a tracer (include/sphx.h section 2p), in the order the library writes them
+TRACER_FIELDS = ("x", "y", "u_x", "u_y")
+
+
 class SphxStatus(C.Structure):
     _fields_ = [("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("vmax", C.c_double),
                 ("step", C.c_int64), ("done", C.c_int32), ("device_status", C.c_int32)]
@@ -113,6 +122,7 @@ EXPORTS = [
     "sphx_ctx_pair_dist_read",
     "sphx_ctx_grad_stats_enable", "sphx_ctx_grad_stats_disable", "sphx_ctx_grad_stats_reset", "sphx_ctx_grad_stats_sample",
     "sphx_ctx_grad_stats_read",
+    "sphx_ctx_tracers_enable", "sphx_ctx_tracers_disable", "sphx_ctx_tracers_sample", "sphx_ctx_tracers_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -137,6 +147,7 @@ EXPORTS = [
     "sphx_batch_pair_dist_read",
     "sphx_batch_grad_stats_enable", "sphx_batch_grad_stats_disable", "sphx_batch_grad_stats_reset", "sphx_batch_grad_stats_sample",
     "sphx_batch_grad_stats_read",
+    "sphx_batch_tracers_enable", "sphx_batch_tracers_disable", "sphx_batch_tracers_sample", "sphx_batch_tracers_read",
 ]
 
 _LIB = None
@@ -620,6 +631,50 @@ class _Stepped(_Sampled):
         assert np.array_equal(n, want), (n, want)
         return self._each([probes_dict(pts, times[k, :n[k]], values[k, :n[k]], int(dropped[k])) for k in range(m)])
 
+    # ---- particle tracers (include/sphx.h sections 2p, 2q): chosen fluid rows followed, one record per sampled step ----
+    def tracers_enable(self, ids, every=1, capacity=65536, t_from=0.0):
+        """Record x, y, u_x, u_y of the fluid rows `ids` (row numbers of download(), 0-based, any order, no duplicates) every
+        `every`-th completed step ending at t >= t_from into a device buffer of `capacity` records ((re)configures and
+        empties it).  Records that find the buffer full are dropped and counted.  A batch: one config and one id list for all
+        members, `capacity` records per member, each recorded on its own clock."""
+        cfg, ids = tracers_config(self.n_fluid, self.n_total, ids, every, capacity, t_from, n_members=self._channels())
+        self._call("tracers_enable", C.byref(cfg))
+        self._tracers = ids  # the ids [T] (int32) while the tracers are on
+
+    def tracers_disable(self):
+        self._call("tracers_disable")
+        self._tracers = None
+
+    def _tracers_on(self):
+        return _enabled(getattr(self, "_tracers", None), "Tracers", f"particle tracers are not enabled on this {self._where}")
+
+    def tracers_sample(self):
+        """Append one record of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
+        self._tracers_on()
+        self._call("tracers_sample")
+
+    def tracers(self, drain=False):
+        """The series so far: ids [T] as given, step (int64) and t [n], x, y, u_x and u_y [n, T] -- column k is ids[k], the values
+        are the bits download() returns in that row -- n_dropped and n_missing (tracers no slot held: always 0); drain empties
+        the buffer after the copy.  A batch: one such dict per member, from one read of all members."""
+        ids = self._tracers_on()
+        m, T = self._channels(), len(ids)
+        n, dropped, missing = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+        nt_, got = C.c_int(0), np.zeros(T, dtype=np.int32)
+
+        def read(cap, times, values, drain):
+            self._call("tracers_read", C.c_int(cap), ptr(times), ptr(values), got.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nt_),
+                       n.ctypes.data_as(C.POINTER(C.c_int)), dropped.ctypes.data_as(C.POINTER(C.c_int64)),
+                       missing.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(1 if drain else 0))
+
+        read(0, None, None, False)
+        assert nt_.value == T and np.array_equal(got, ids), (nt_.value, T)
+        cap, want = max(int(n.max()), 1), n.copy()
+        times, values = np.zeros((m, cap, 2)), np.zeros((m, cap, T, len(TRACER_FIELDS)))
+        read(cap, times, values, drain)
+        assert np.array_equal(n, want), (n, want)
+        return self._each([tracers_dict(ids, times[k, :n[k]], values[k, :n[k]], int(dropped[k]), int(missing[k])) for k in range(m)])
+
     # ---- profile series (include/sphx.h sections 2j, 2k): "sample now" and the profiles ----
     def profile_series_sample(self):
         """Append one record of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
@@ -743,6 +798,7 @@ class Batch(_Stepped):
         self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
         self._pair_dist = None   # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
         self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
+        self._tracers = None     # the ids [T] (int32) while the tracers are on
         arr = (SphxParams * m)(*self.params)
         check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
@@ -794,6 +850,7 @@ class Context(_Stepped):
         self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
         self._pair_dist = None   # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
         self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
+        self._tracers = None     # the ids [T] (int32) while the tracers are on
         check(lib().sphx_ctx_create(C.byref(self._h), C.byref(self.params), C.c_int(n_fluid), C.c_int(n_total),
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
@@ -1001,6 +1058,52 @@ def probes_config(prm, points, every=1, capacity=65536, t_from=0.0, with_walls=F
     cfg = SphxProbesConfig(n_points=len(pts), every=every, capacity=int(capacity), with_walls=int(with_walls), t_from=t_from,
                            points=ptr(pts))
     return cfg, pts
+
+
+def tracers_config(n_fluid, n_total, ids, every=1, capacity=65536, t_from=0.0, n_members=1):
+    """Checked sphx_tracers_config for channels of n_fluid fluid rows among n_total, and the ids [T] (int32) it points to (keep
+    them alive through the call); raises SphxError(SPHX:Tracers:config) before anything reaches the device.  n_members: the
+    channels that get `capacity` records each (a batch's members)."""
+    bad = _config_error("Tracers")
+    if ids is None:
+        raise bad("ids must not be None")
+    try:
+        raw = np.array(ids)
+    except (TypeError, ValueError):
+        raise bad("ids must be a list of row numbers") from None
+    if raw.ndim != 1 or raw.dtype == np.bool_ or not (np.issubdtype(raw.dtype, np.integer) or raw.size == 0):
+        raise bad("ids must be a one-dimensional list of integer row numbers")
+    if not 1 <= raw.size <= n_fluid:
+        raise bad("the number of tracers must be 1 .. n_fluid")
+    raw = raw.astype(np.int64)
+    if np.any((raw >= n_fluid) & (raw < n_total)):
+        raise bad("a tracer must be a fluid row: rows n_fluid .. n_total - 1 are wall particles")
+    if np.any(raw < 0) or np.any(raw >= n_fluid):
+        raise bad("a tracer id must be a row number in 0 .. n_fluid - 1")
+    if len(np.unique(raw)) != raw.size:
+        raise bad("a row is listed twice")
+    every = _check_every(every, bad)
+    if not _is_int(capacity) or capacity < 1 or capacity >= 1 << 31:
+        raise bad("capacity must be an integer >= 1")
+    if n_members * capacity * raw.size * len(TRACER_FIELDS) > 1 << 27:
+        raise bad(("n_members * " if n_members > 1 else "") + "capacity * n_tracers * 4 must not exceed 1 << 27 doubles")
+    t_from = _check_t_from(t_from, bad, finite=True)
+    out = np.ascontiguousarray(raw, dtype=np.int32)
+    cfg = SphxTracersConfig(n_tracers=len(out), every=every, capacity=int(capacity), t_from=t_from,
+                            ids=out.ctypes.data_as(C.POINTER(C.c_int32)))
+    return cfg, out
+
+
+def tracers_dict(ids, times, values, n_dropped=0, n_missing=0) -> dict:
+    """times [n, 2] and values [n, T, 4] -> ids, step (int64), t [n] and one [n, T] array per TRACER_FIELDS, plus n_dropped and
+    n_missing."""
+    times = np.asarray(times, dtype=np.float64).reshape(-1, 2)
+    ids = np.array(ids, dtype=np.int32).reshape(-1)
+    values = np.asarray(values, dtype=np.float64).reshape(len(times), len(ids), len(TRACER_FIELDS))
+    out = dict(ids=ids, step=times[:, 0].astype(np.int64), t=np.ascontiguousarray(times[:, 1]))
+    out.update({k: np.ascontiguousarray(values[:, :, j]) for j, k in enumerate(TRACER_FIELDS)})
+    out.update(n_dropped=int(n_dropped), n_missing=int(n_missing))
+    return out
 
 
 def profile_series_config(prm, n_bins=0, every=1, capacity=4096, t_from=0.0, bands=(), n_members=1) -> SphxProfileSeriesConfig:

@@ -669,6 +669,60 @@ SPHX_EXPORT int sphx_batch_probes_read(sphx_batch *b, int capacity, double *time
     SPHX_CATCH
 }
 
+// ---- particle tracers of every member (include/sphx.h section 2q) ----
+
+namespace {
+
+// the batch's tracers (member 0's, see sphx_ctx::tracers)
+Tracers &batch_tracers(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    Tracers &t = b->mem[0]->tracers;
+    sampler_check(kTracerNames, false, t.on, need_on, "batch");
+    return t;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_batch_tracers_enable(sphx_batch *b, const sphx_tracers_config *cfg)
+{
+    SPHX_TRY
+    // (one id list for the shared geometry; out of device memory: the batch goes on without tracers)
+    Tracers &t = batch_tracers(b, false);
+    tracers_enable(t, b->mem[0]->nf, b->mem[0]->nt, cfg, b->M, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_tracers_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    Tracers &t = batch_tracers(b, false);
+    if (t.on) sampler_off(t, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_tracers_sample(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_tracers(b, true);
+    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
+    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_tracers);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_tracers_read(sphx_batch *b, int capacity, double *times, double *values, int32_t *ids, int *n_tracers,
+                                        int *n_records, int64_t *n_dropped, int64_t *n_missing, int drain)
+{
+    SPHX_TRY
+    Tracers &t = batch_tracers(b, true);
+    tracers_read(t, b->stream, [b] { batch_settle(b); }, capacity, times, values, ids, n_tracers, n_records, n_dropped, n_missing, drain);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
 // ---- profile series of every member (include/sphx.h section 2k) ----
 
 namespace {

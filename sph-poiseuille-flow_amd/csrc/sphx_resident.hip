@@ -258,6 +258,7 @@ struct sphx_ctx {
     ProfileSeries pseries;
     PairDist pairs;
     GradStats grads;
+    Tracers tracers;
 
     // Member of a batch (sphx_batch_*): the device arrays are this member's blocks of batch-wide allocations (BatchArena)
     sphx::BatchArena *arena = nullptr;

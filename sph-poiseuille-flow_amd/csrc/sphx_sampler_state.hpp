@@ -9,6 +9,7 @@
 #include "sphx_profile_series.hpp"
 #include "sphx_pair_dist.hpp"
 #include "sphx_grad_stats.hpp"
+#include "sphx_tracers.hpp"
 
 struct sphx_ctx;
 
@@ -170,8 +171,30 @@ struct GradStats {
     void read(hipStream_t st, int band, int stride, double *sums, int64_t *n_samples, double *t_first, double *t_last) const;
 };
 
+// Particle tracers (sphx_ctx_tracers_*, sphx_batch_tracers_*; sphx_tracers.hpp) of a context or of the M members of a batch: one
+// configuration and one id list, member m's times at m * cfg.capacity * 2, its values at m * cfg.capacity * row(), its head at
+// m; the table index_of [n_fluid] is shared.
+struct Tracers {
+    bool on = false;
+    int members = 1;
+    sphx_tracers_config cfg{};    // (cfg.ids: nullptr -- the ids are copied)
+    std::vector<int32_t> ids;     // [n_tracers] as the caller gave them
+    int n_fluid = 0;
+    DevBuf<int> index_of;
+    DevBuf<double> times, values;
+    DevBuf<TracerHead> head;
+
+    size_t row() const { return (size_t)cfg.n_tracers * kTracerFields; }  // the values of one record
+    void check(int n_fluid, int n_total, const sphx_tracers_config *cfg, int M);
+    void alloc(const Tracers &checked, int M, hipStream_t st);
+    void zero(hipStream_t st) { head.zero(st); }  // (the counters: records beyond n_records are never read)
+    void release() { index_of.release(); times.release(); values.release(); head.release(); }
+    void read(hipStream_t st, int capacity, double *times, double *values, int *n_records, int64_t *n_dropped, int64_t *n_missing,
+              bool drain);
+};
+
 // the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes, profile series,
-// pair statistics, gradient statistics (sphx_samplers.hpp)
+// pair statistics, gradient statistics, tracers (sphx_samplers.hpp)
 void launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild);
 
 }  // namespace sphx

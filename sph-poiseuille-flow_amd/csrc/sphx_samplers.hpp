@@ -1,7 +1,8 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
 // the velocity-field map (2e; 2g), the point probes (2h; 2i), the profile series (2j; 2k), the pair statistics (2l; 2m,
-// sphx_pair_dist.hpp) and the gradient statistics (2n; 2o, sphx_grad_stats.hpp) -- all seven also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// sphx_pair_dist.hpp) and the gradient statistics (2n; 2o, sphx_grad_stats.hpp) -- all seven also of a slab of a ring (3a, at the end of this file) --
+// and the particle tracers (2p; 2q, sphx_tracers.hpp; contexts and batches).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -34,6 +35,8 @@ constexpr SamplerNames kPairNames{"PairDist", "the pair statistics of a slab are
                                   "the sums could not be set up: "};
 constexpr SamplerNames kGradNames{"GradStats", "the gradient statistics of a slab are sphx_slab_gstats_* (include/sphx.h section 3a)",
                                   "gradient statistics are not enabled on this ", "the sums could not be set up: "};
+constexpr SamplerNames kTracerNames{"Tracers", "particle tracers are not available on slab contexts",
+                                    "particle tracers are not enabled on this ", "the record buffer could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
 
@@ -321,6 +324,30 @@ void launch_grad_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
                  c->grid, per_member(c->phys), s, c->walls, grad_stats_args(c, every));
 }
 
+// the arguments of a tracers launch into c->tracers
+TracerArgs tracer_args(sphx_ctx *c, int every)
+{
+    const Tracers &t = c->tracers;
+    TracerArgs a{};
+    a.index_of = t.index_of.get(); a.times = t.times.get(); a.values = t.values.get(); a.head = t.head.get();
+    a.t_from = t.cfg.t_from;
+    a.n_tracers = t.cfg.n_tracers; a.n_fluid = t.n_fluid; a.n_slots = c->nf; a.capacity = t.cfg.capacity;
+    a.every = every;
+    return a;
+}
+
+// workgroups of the scan of a channel that holds n particles: a grid-stride loop under a fixed cap
+unsigned tracer_blocks(size_t n)
+{
+    return std::clamp<unsigned>(div_up(n, (size_t)kTracerBlock), 1u, (unsigned)kTracerMaxBlocks);
+}
+
+// k_tracers on state s (pos, vel and the ids of the layout it is stored in) -- of a batch: member 0's -- into c->tracers
+void launch_tracers(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    launch_forms(c, "k_tracers", Forms{k_tracers, k_tracers_b}, tracer_blocks((size_t)c->nf), kTracerBlock, 0, q, s, tracer_args(c, every));
+}
+
 }  // namespace
 
 void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
@@ -333,6 +360,7 @@ void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
     if (c->pseries.on) launch_profile_series(c, q, s, c->pseries.cfg.every);
     if (c->pairs.on) launch_pair_dist(c, q, s, c->pairs.cfg.every);
     if (c->grads.on) launch_grad_stats(c, q, s, c->grads.cfg.every);
+    if (c->tracers.on) launch_tracers(c, q, s, c->tracers.cfg.every);
 }
 
 // ---- flow statistics ----
@@ -850,6 +878,154 @@ SPHX_EXPORT int sphx_ctx_probes_read(sphx_ctx *c, int capacity, double *times, d
     settle_owed(c);  // (the records of everything enqueued)
     p.read(c->stream, capacity, times, values, n_records, n_dropped, drain != 0);
     if (n_points) *n_points = p.cfg.n_points;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- particle tracers ----
+
+// every check of a configuration for M channels of n_fluid fluid rows among n_total (cfg without the pointer, and the ids);
+// SPHX:Tracers:config errors
+void Tracers::check(int n_fluid, int n_total, const sphx_tracers_config *cfg, int M)
+{
+    const char *id = "SPHX:Tracers:config";
+    require(cfg != nullptr, id, "config must not be NULL");
+    require(cfg->ids != nullptr, id, "ids must not be NULL");
+    require(cfg->n_tracers >= 1 && cfg->n_tracers <= n_fluid, id, "n_tracers must be 1 .. n_fluid");
+    require(cfg->every >= 1, id, "every must be >= 1");
+    require(cfg->capacity >= 1, id, "capacity must be >= 1");
+    if (!((double)M * (double)cfg->capacity * (double)cfg->n_tracers * kTracerFields <= (double)kTracerMaxTotal))
+        throw Error(SPHX_ERR_ARG, id, std::string(M > 1 ? "n_members * " : "") + "capacity * n_tracers * 4 must not exceed 1 << 27 doubles");
+    require(std::isfinite(cfg->t_from), id, "t_from must be finite");
+    std::vector<char> seen((size_t)n_fluid, 0);
+    ids.assign(cfg->ids, cfg->ids + cfg->n_tracers);
+    for (const int32_t r : ids) {
+        require(r < n_fluid || r >= n_total, id, "a tracer must be a fluid row: rows n_fluid .. n_total - 1 are wall particles");
+        require(r >= 0 && r < n_fluid, id, "a tracer id must be a row number in 0 .. n_fluid - 1");
+        require(!seen[(size_t)r], id, "a row is listed twice");
+        seen[(size_t)r] = 1;
+    }
+    this->cfg = *cfg;
+    this->cfg.ids = nullptr;
+    this->n_fluid = n_fluid;
+}
+
+// the checked configuration and ids, the table, and records and heads for M members
+void Tracers::alloc(const Tracers &checked, int M, hipStream_t st)
+{
+    cfg = checked.cfg;
+    ids = checked.ids;
+    n_fluid = checked.n_fluid;
+    members = M;
+    index_of.alloc((size_t)n_fluid);
+    times.alloc((size_t)M * cfg.capacity * 2);
+    values.alloc((size_t)M * cfg.capacity * row());
+    head.alloc(M);
+    std::vector<int> table((size_t)n_fluid, -1);
+    for (int k = 0; k < cfg.n_tracers; ++k) table[(size_t)ids[(size_t)k]] = k;
+    index_of.upload(table.data(), table.size(), st);
+    SPHX_HIP(hipStreamSynchronize(st));  // (`table` goes out of scope here)
+}
+
+// Every member's counts (n_records[m], n_dropped[m], n_missing[m], where given) and its filled rows, into
+// times[m][0 .. n_records[m])[2] of a [members][capacity][2] array and values[m][0 .. n_records[m])[row()] of a
+// [members][capacity][row()] array, each where given; drain empties every buffer.  SPHX:Tracers:capacity when an array is given
+// and capacity is below the largest count: nothing is copied or drained then.
+void Tracers::read(hipStream_t st, int capacity, double *t_out, double *v_out, int *n_records, int64_t *n_dropped, int64_t *n_missing,
+                   bool drain)
+{
+    const int M = members;
+    std::vector<TracerHead> h(M);
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(TracerHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    long long most = 0;
+    for (int m = 0; m < M; ++m) {
+        const long long n = h[m].n_records;
+        if (n < 0 || n > (long long)cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:Tracers:state", "internal: record count out of range");
+        most = std::max(most, n);
+    }
+    require((t_out == nullptr && v_out == nullptr) || (long long)capacity >= most, "SPHX:Tracers:capacity",
+            "capacity is smaller than the number of records");
+    if ((t_out || v_out) && most > 0) {
+        for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
+            const size_t n = (size_t)h[m].n_records;
+            if (n == 0) continue;
+            if (t_out)
+                SPHX_HIP(hipMemcpyAsync(t_out + (size_t)m * capacity * 2, times.get() + (size_t)m * cfg.capacity * 2, n * 2 * sizeof(double),
+                                        hipMemcpyDeviceToHost, st));
+            if (v_out)
+                SPHX_HIP(hipMemcpyAsync(v_out + (size_t)m * capacity * row(), values.get() + (size_t)m * cfg.capacity * row(),
+                                        n * row() * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+    for (int m = 0; m < M; ++m) {
+        if (n_records) n_records[m] = (int)h[m].n_records;
+        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
+        if (n_missing) n_missing[m] = (int64_t)h[m].n_missing;
+    }
+    if (drain) {
+        zero(st);
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+}
+
+namespace {
+
+// enable for M members of channels of n_fluid fluid rows among n_total on schedule s: every check of cfg first
+void tracers_enable(Tracers &t, int n_fluid, int n_total, const sphx_tracers_config *cfg, int M, Schedule &s, hipStream_t st)
+{
+    Tracers checked;
+    checked.check(n_fluid, n_total, cfg, M);
+    sampler_on(t, kTracerNames, s, st, [&] { t.alloc(checked, M, st); });
+}
+
+// settle() -- what is enqueued lands first -- then the read, the list and its length; shared by contexts and batches
+template <typename Settle>
+void tracers_read(Tracers &t, hipStream_t st, Settle &&settle, int capacity, double *times, double *values, int32_t *ids, int *n_tracers,
+                  int *n_records, int64_t *n_dropped, int64_t *n_missing, int drain)
+{
+    settle();  // (the records of everything enqueued)
+    t.read(st, capacity, times, values, n_records, n_dropped, n_missing, drain != 0);
+    if (ids) std::copy(t.ids.begin(), t.ids.end(), ids);
+    if (n_tracers) *n_tracers = t.cfg.n_tracers;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_tracers_enable(sphx_ctx *c, const sphx_tracers_config *cfg)
+{
+    SPHX_TRY
+    Tracers &t = sampler_of(c, &sphx_ctx::tracers, kTracerNames, false);
+    tracers_enable(t, c->nf, c->nt, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_tracers_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    Tracers &t = sampler_of(c, &sphx_ctx::tracers, kTracerNames, false);
+    if (t.on) sampler_off(t, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_tracers_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampler_of(c, &sphx_ctx::tracers, kTracerNames, true);
+    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_tracers);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_tracers_read(sphx_ctx *c, int capacity, double *times, double *values, int32_t *ids, int *n_tracers,
+                                      int *n_records, int64_t *n_dropped, int64_t *n_missing, int drain)
+{
+    SPHX_TRY
+    Tracers &t = sampler_of(c, &sphx_ctx::tracers, kTracerNames, true);
+    tracers_read(t, c->stream, [c] { settle_owed(c); }, capacity, times, values, ids, n_tracers, n_records, n_dropped, n_missing, drain);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -21,7 +21,7 @@ from .mex_surface import sph_neighbor_search_mex, sph_physics_shell_mex
 from . import restart
 from .profile import (compute_mid_channel_profile, field_map_means, final_profile, flow_stats_profile, grad_stats_profiles, l2_error,
                       n_profile_bins, pool_field_maps, pair_dist_profiles, pool_flow_stats, pool_grad_stats, pool_pair_dist,
-                      poiseuille_startup, profile_series_profiles)
+                      poiseuille_startup, pool_tracers, profile_series_profiles, tracer_profiles, unwrap_tracers)
 
 
 @dataclass
@@ -61,6 +61,9 @@ class RunResult:
 
     grad_stats: list = None  # run / run_sweep / run_ensemble(..., gradients_from=...): the device-side gradient statistics of the
                              # run, one dict per band (capi.Context.grad_stats: the sums with the profiles; grad_figures())
+
+    tracers: dict = None  # run / run_sweep / run_ensemble(..., tracers=...): the device-side tracer series of the whole run
+                          # (capi.Context.tracers: x, y, u_x, u_y of the tracked fluid rows per record; tracer_figures())
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -423,6 +426,72 @@ def _grad_columns(prms, grads):
     return dict(L2_shear=np.array([f["L2_shear"] for f in figs]), tau_wall_dev=np.array(dev), div_rms=np.array([f["div_rms"] for f in figs]))
 
 
+def tracer_ids(tracers, n_fluid, seed=0):
+    """The fluid rows a `tracers=` argument of run / run_sweep / run_ensemble names, as a sorted int64 array: "all" -- every
+    fluid row; an int n, 1 <= n <= n_fluid -- that many rows, a seeded choice (the same rows for the same n, n_fluid and seed);
+    anything else -- the rows themselves, as given (capi.tracers_config checks them).  ValueError for another string, a bool or
+    an n out of range: before any device is touched."""
+    if isinstance(tracers, str):
+        if tracers != "all":
+            raise ValueError(f'tracers must be a list of fluid rows, "all" or a number of rows, not {tracers!r}')
+        return np.arange(n_fluid, dtype=np.int64)
+    if isinstance(tracers, (bool, np.bool_)):
+        raise ValueError('tracers must be a list of fluid rows, "all" or a number of rows, not a bool')
+    if isinstance(tracers, (int, np.integer)):
+        if not 1 <= tracers <= n_fluid:
+            raise ValueError(f"tracers = {int(tracers)}: the number of rows must be 1 .. n_fluid = {n_fluid}")
+        return np.sort(np.random.default_rng(seed).choice(n_fluid, size=int(tracers), replace=False)).astype(np.int64)
+    return tracers
+
+
+def _tracers_request(tracers, tracers_every, tracers_from, tracers_capacity, n_fluid, n_total, n_members=1):
+    """the `tracers` of run / _run_batch -- (ids, every, capacity, t_from), every check made -- or None without tracers=;
+    tracers_capacity None: 65536 records, or as many as the bound on capacity * n_tracers * 4 (over the members) allows"""
+    if tracers is None:
+        return None
+    ids = tracer_ids(tracers, n_fluid)
+    T = max(int(np.size(ids)), 1)
+    if tracers_capacity is None:
+        tracers_capacity = max(min(65536, (1 << 27) // (n_members * T * len(capi.TRACER_FIELDS))), 1)
+    t_from = 0.0 if tracers_from is None else tracers_from
+    _, ids = capi.tracers_config(n_fluid, n_total, ids, tracers_every, tracers_capacity, t_from, n_members=n_members)
+    return ids, tracers_every, tracers_capacity, t_from
+
+
+def _concat_tracers(ids, chunks):
+    """the series of a whole run from the drained chunks (none: an empty series of these ids)"""
+    if not chunks:
+        return capi.tracers_dict(ids, np.zeros((0, 2)), np.zeros((0, len(ids), len(capi.TRACER_FIELDS))))
+    out = dict(ids=chunks[0]["ids"])
+    out.update({k: np.concatenate([c[k] for c in chunks]) for k in ("step", "t") + capi.TRACER_FIELDS})
+    out.update(n_dropped=int(sum(c["n_dropped"] for c in chunks)), n_missing=int(sum(c["n_missing"] for c in chunks)))
+    return out
+
+
+def _tracers_lost(who, p, t, capacity):
+    return _records_lost(who, "the tracers", "tracers_capacity", p, t, capacity)
+
+
+def tracer_figures(prm, tracers, lags=None, y_margin=None):
+    """Figures of a tracer series (capi.Context.tracers / RunResult.tracers), on the host: profile.tracer_profiles of the
+    unwrapped series over the tracers that start at least y_margin (None: 2h) from both walls -- lags, tau, msd_y, msd_x_rel,
+    D_y, y_drift, u_dev_rms, n_tracers, n_records -- plus D_y_nu = D_y / nu, the numerical cross-stream diffusivity in units of
+    the physical one.  In laminar Poiseuille flow a fluid element never leaves its streamline: all of them measure the scheme."""
+    margin = 2.0 * prm.h if y_margin is None else y_margin
+    out = tracer_profiles(unwrap_tracers(tracers, prm.DL), prm.DL, prm.DH, prm.gravity_g, prm.nu, lags=lags, y_margin=margin)
+    out["D_y_nu"] = out["D_y"] / prm.nu
+    return out
+
+
+_TRACER_COLUMNS = ("D_y_nu", "y_drift", "u_dev_rms")
+
+
+def _tracer_columns(prms, series):
+    """The tracer columns of a sweep's table, one [M] array each: D_y_nu, y_drift, u_dev_rms of tracer_figures(prm_m, tracers_m)."""
+    figs = [tracer_figures(p, tr) for p, tr in zip(prms, series)]
+    return {k: np.array([f[k] for f in figs]) for k in _TRACER_COLUMNS}
+
+
 def _concat_history(chunks):
     if not chunks:
         return capi.history_dict(np.zeros((0, len(capi.HISTORY_FIELDS))))
@@ -437,7 +506,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
         field_walls=False, probe_points=None, probe_every=1, probe_capacity=65536, probe_from=None, probe_walls=False,
         profiles_every=None, profiles_from=None, profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1,
         pairs_bins=64, pairs_walls=False, pairs_bands=None, gradients_from=None, gradients_every=1, gradients_walls=False,
-        gradients_bands=None):
+        gradients_bands=None, tracers=None, tracers_every=1, tracers_from=None, tracers_capacity=None):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -483,7 +552,15 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     the reference's profile bins, for the whole channel and the bands gradients_bands (None: the mid-channel band (DL/2,
     max(dp, h)) as band 1); gradients_walls: the wall particles are partners too (off: they carry the wall's velocity and pull
     the wall-adjacent bins down).  RunResult.grad_stats is one dict per band; grad_figures() gives the shear-rate profile and its
-    L2 against the analytic one, tau(y) with its line extrapolated to the walls, div_rms and the mean vorticity."""
+    L2 against the analytic one, tau(y) with its line extrapolated to the walls, div_rms and the mean vorticity.
+    tracers (resident engine; default off): follow, on the device and inside the step loop, chosen fluid rows (include/sphx.h
+    section 2p: x, y, u_x, u_y per tracer, the bits download() returns in that row): a list of rows, "all", or an int -- that many
+    rows, a seeded choice (tracer_ids) -- every tracers_every-th step ending at t >= tracers_from (None: from the start); the
+    buffer (tracers_capacity records; None: 65536, or what the bound on capacity * n_tracers * 4 allows) is drained at every
+    output point -- a run that lost records raises RuntimeError and names the capacity needed -- and RunResult.tracers is the
+    series of the whole run (tracer_figures() gives the cross-stream diffusivity, the drift and the Lagrangian velocity error)."""
+    if tracers is not None and engine != "resident":
+        raise ValueError("tracers needs the resident engine (the tracers are recorded on the device)")
     if gradients_from is not None and engine != "resident":
         raise ValueError("gradients_from needs the resident engine (the gradients are estimated on the device)")
     if pairs_from is not None and engine != "resident":
@@ -500,6 +577,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
         raise ValueError("history_every needs the resident engine (the history is recorded on the device)")
     parts = init_particles(prm) if parts is None else parts
     nf, nt = parts["n_fluid"], parts["n_total"]
+    tracing = _tracers_request(tracers, tracers_every, tracers_from, tracers_capacity, nf, nt)
     t_start, step_start, n_inner = 0.0, 0, 1
     if restart_path and engine != "resident":
         raise ValueError("restart files are handled by the resident engine")
@@ -526,6 +604,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     series, series_chunks = None, []
     pair_dist = None
     grad_stats = None
+    tracer_series, tracer_chunks = None, []
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context.from_parts(prm, parts, t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
@@ -553,6 +632,9 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
             if gradients_from is not None:
                 ctx.grad_stats_enable(n_bins=n_bins, every=gradients_every, t_from=gradients_from, with_walls=gradients_walls,
                                       bands=_grad_bands(prm, gradients_bands))
+            if tracing:
+                ctx.tracers_enable(tracing[0], every=tracing[1], capacity=tracing[2],
+                                   t_from=t_start if tracers_from is None else tracing[3])
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -579,6 +661,10 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                     series_chunks.append(ctx.profile_series_sums(drain=True))
                     if series_chunks[-1]["n_dropped"]:
                         raise _profiles_lost("", series_chunks[-1], t, profiles_capacity)
+                if tracing:
+                    tracer_chunks.append(ctx.tracers(drain=True))
+                    if tracer_chunks[-1]["n_dropped"]:
+                        raise _tracers_lost("", tracer_chunks[-1], t, tracing[2])
                 if restart_path:
                     restart.save_restart(restart_path, prm.config_signature, dict(d, t=t, step=step), fmt=mat_format)
                 if log:
@@ -602,6 +688,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 pair_dist = _pair_dist_bands(ctx.pair_dist_sums(), prm.dp)
             if gradients_from is not None:
                 grad_stats = _grad_stats_bands(prm.DH, [ctx.grad_stats_sums(b) for b in range(1 + len(_grad_bands(prm, gradients_bands)))])
+            if tracing:
+                tracer_series = _concat_tracers(tracing[0], tracer_chunks)
         finally:
             ctx.close()
     elif engine == "mex":
@@ -652,7 +740,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     return _run_result(prm, nf, nt, pos, vel, t=t, steps=int(step), wall_seconds=wall, profile_times=profile_times,
                        mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t, grid_policy=policy,
                        full_profile_u=full_profiles, n_inner=n_inner, time_avg=time_avg, history=history, field_avg=field_avg,
-                       probes=probes, profile_series=series, pair_dist=pair_dist, grad_stats=grad_stats)
+                       probes=probes, profile_series=series, pair_dist=pair_dist, grad_stats=grad_stats, tracers=tracer_series)
 
 
 def _run_result(prm, nf, nt, pos, vel, **fields):
@@ -693,7 +781,7 @@ def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
 
 
 def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None, probe=None,
-               profiles=None, pairs=None, gradients=None):
+               profiles=None, pairs=None, gradients=None, tracers=None):
     """The batch run behind run_batch, run_ensemble and run_sweep (`name`, for the refusals): check and default the inputs,
     open the batch with the launch keywords `launch`, enable what was asked for, advance output point by output point, build
     every member's RunResult.
@@ -714,6 +802,9 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                  2m with the margin and the default bands of run(); every member gets its pair_dist
       gradients  (gradients_from, gradients_every, gradients_walls, gradients_bands): the gradient statistics of include/sphx.h
                  section 2o in the bins and with the default band of run(); every member gets its grad_stats
+      tracers    (tracers, tracers_every, tracers_from, tracers_capacity) as run() takes them: the tracers of include/sphx.h
+                 section 2q, one id list for all members, drained at every output point; every member gets its tracers, and one
+                 that lost records raises RuntimeError
     -> the members, the wall seconds, the grid policy, with average the raw sums (whole, mid) of all members, and with field the
     raw planes of all members."""
     prms = list(prms)
@@ -723,6 +814,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
     parts_list = _batch_inputs(prms, parts_list)
     nf, nt = parts_list[0]["n_fluid"], parts_list[0]["n_total"]
     M = len(prms)
+    tracing = _tracers_request(*tracers, nf, nt, n_members=M) if tracers else None
     n_bins = n_profile_bins(p0.DH, p0.dp)
     mid_x, mid_hw = 0.5 * p0.DL, max(p0.dp, p0.h)
 
@@ -735,6 +827,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
     chunks = [[] for _ in range(M)]
     pchunks = [[] for _ in range(M)]
     schunks = [[] for _ in range(M)]
+    tchunks = [[] for _ in range(M)]
     t0 = time.perf_counter()
     with capi.Batch.from_parts(prms, parts_list, **launch) as b:
         if history:
@@ -757,6 +850,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         if gradients:
             b.grad_stats_enable(n_bins=n_bins, every=gradients[1], t_from=float(gradients[0]), with_walls=gradients[2],
                                 bands=_grad_bands(p0, gradients[3]))
+        if tracing:
+            b.tracers_enable(tracing[0], every=tracing[1], capacity=tracing[2], t_from=tracing[3])
         t = 0.0
         st = None
         while t < p0.t_end - 1e-12:
@@ -787,6 +882,11 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                     if p["n_dropped"]:
                         raise _profiles_lost(f"member {m}: ", p, t, profiles[2])
                     schunks[m].append(p)
+            if tracing:
+                for m, p in enumerate(b.tracers(drain=True)):
+                    if p["n_dropped"]:
+                        raise _tracers_lost(f"member {m}: ", p, t, tracing[2])
+                    tchunks[m].append(p)
             if log:
                 log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
         wall = time.perf_counter() - t0
@@ -815,6 +915,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                 extra.update(pair_dist=_pair_dist_bands(pair_sums[m], prm.dp))
             if gradients:
                 extra.update(grad_stats=_grad_stats_bands(prm.DH, [band[m] for band in grad_sums]))
+            if tracing:
+                extra.update(tracers=_concat_tracers(tracing[0], tchunks[m]))
             members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra))
     return members, wall, policy, sums, planes
 
@@ -868,6 +970,8 @@ class EnsembleResult:
                                # dict per band, with the figures of profile.pair_dist_profiles
     pooled_grad: list = None   # with gradients_from, under the condition of `pooled`: profile.pool_grad_stats of the members' sums,
                                # one dict per band
+    pooled_tracers: dict = None  # with tracers, under the condition of `pooled` and where the members recorded at the same steps
+                                 # and times (profile.pool_tracers refuses others): the members' columns side by side
 
 
 _PHYSICS = ("mu", "c_f", "p0", "gravity_g", "transport_coeff")
@@ -876,7 +980,8 @@ _PHYSICS = ("mu", "c_f", "p0", "gravity_g", "transport_coeff")
 def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_per_particle=0, steps_per_graph=0,
                  rebuild_every=0, log=None, history_every=None, field_from=None, field_every=1, field_shape=None,
                  field_walls=False, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False, pairs_bands=None,
-                 gradients_from=None, gradients_every=1, gradients_walls=False, gradients_bands=None):
+                 gradients_from=None, gradients_every=1, gradients_walls=False, gradients_bands=None, tracers=None, tracers_every=1,
+                 tracers_from=None, tracers_capacity=None):
     """Time-averaged profiles of M channels of one geometry stepped as one batch (capi.Batch), averaged on the device
     inside the step loop (include/sphx.h section 2c) as run(average_from=...) does for one channel: every
     average_every-th step ending at t >= average_from, whole channel and the mid-channel band (DL/2, max(dp, h)).  The
@@ -887,7 +992,9 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
     as well (include/sphx.h section 2m), with the keywords of run(): every member gets a pair_dist, and members that share their
     physics pooled_pairs (the integers added, the smallest r_min).  gradients_from: every member's gradient statistics as well
     (include/sphx.h section 2o), with the keywords of run(): every member gets a grad_stats, and members that share their physics
-    pooled_grad (profile.pool_grad_stats, one dict per band).  Returns an EnsembleResult."""
+    pooled_grad (profile.pool_grad_stats, one dict per band).  tracers: every member's tracers as well (include/sphx.h section
+    2q), with the keywords of run(): one id list for all members, every member gets its tracers, and members that share their
+    physics and whose clocks agreed record by record pooled_tracers (profile.pool_tracers).  Returns an EnsembleResult."""
     prms = list(prms)
     if history_every is not None:
         raise ValueError("run_ensemble records no step history (run_sweep does, for every member)")
@@ -898,9 +1005,10 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
                                                rebuild_every=rebuild_every), log, average=(average_from, average_every),
         field=_field_request(field_from, field_every, field_shape, field_walls),
         pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands),
-        gradients=_gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands))
+        gradients=_gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands),
+        tracers=None if tracers is None else (tracers, tracers_every, tracers_from, tracers_capacity))
     p0, M = prms[0], len(prms)
-    pooled = pooled_field = pooled_pairs = pooled_grad = None
+    pooled = pooled_field = pooled_pairs = pooled_grad = pooled_tracers = None
     if all(getattr(p, k) == getattr(p0, k) for p in prms for k in _PHYSICS):
         pw, pm = pool_flow_stats(p0.DH, whole), pool_flow_stats(p0.DH, mid)
         pooled = time_average(p0, pw, pm)
@@ -913,8 +1021,10 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
             pooled_pairs = _pair_dist_bands(pool_pair_dist([r.pair_dist for r in members]), p0.dp)
         if gradients_from is not None:
             pooled_grad = [pool_grad_stats(p0.DH, [r.grad_stats[b] for r in members]) for b in range(len(members[0].grad_stats))]
+        if tracers is not None and all(np.array_equal(r.tracers[k], members[0].tracers[k]) for r in members for k in ("step", "t")):
+            pooled_tracers = pool_tracers([r.tracers for r in members])
     return EnsembleResult(members=members, pooled=pooled, wall_seconds=wall, grid_policy=policy, pooled_field=pooled_field,
-                          pooled_pairs=pooled_pairs, pooled_grad=pooled_grad)
+                          pooled_pairs=pooled_pairs, pooled_grad=pooled_grad, pooled_tracers=pooled_tracers)
 
 
 @dataclass
@@ -955,7 +1065,8 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
               field_from=None, field_every=1, field_shape=None, field_walls=False, probe_points=None, probe_every=1,
               probe_capacity=65536, probe_from=None, probe_walls=False, profiles_every=None, profiles_from=None,
               profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False,
-              pairs_bands=None, gradients_from=None, gradients_every=1, gradients_walls=False, gradients_bands=None):
+              pairs_bands=None, gradients_from=None, gradients_every=1, gradients_walls=False, gradients_bands=None, tracers=None,
+              tracers_every=1, tracers_from=None, tracers_capacity=None):
     """A parameter sweep: M channels of one geometry that differ in mu, c_f, p0, gravity_g, transport_coeff, stepped as one
     batch (capi.Batch) with every member's step history recorded on the device, inside the step loop (include/sphx.h
     section 2f) as run(history_every=...) does for one channel.  The members advance output point by output point as in
@@ -974,7 +1085,9 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     columns r_min_dp, n_neigh, sigma1_dp of pair_dist_figures(prm_m, pair_dist_m) -- the figures that respond to
     transport_coeff.  gradients_from: every member's gradient statistics as well (include/sphx.h section 2o), with the keywords of
     run(): each member gets its grad_stats and the table the columns L2_shear, tau_wall_dev, div_rms of
-    grad_figures(prm_m, grad_stats_m).  A member that lost records to a full buffer raises RuntimeError, which names the member and the
+    grad_figures(prm_m, grad_stats_m).  tracers: every member's tracers as well (include/sphx.h section 2q), with the keywords of
+    run(): one id list for all members, each member gets its tracers and the table the columns D_y_nu, y_drift, u_dev_rms of
+    tracer_figures(prm_m, tracers_m) -- the Lagrangian figures that respond to transport_coeff.  A member that lost records to a full buffer raises RuntimeError, which names the member and the
     capacity the output interval needed.  Returns a SweepResult."""
     prms = list(prms)
     members, wall, policy, _, planes = _run_batch(
@@ -985,7 +1098,8 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
         probe=None if probe_points is None else (probe_points, probe_every, probe_capacity, probe_from, probe_walls),
         profiles=None if profiles_every is None else (profiles_every, profiles_from, profiles_capacity, profiles_bands),
         pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands),
-        gradients=_gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands))
+        gradients=_gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands),
+        tracers=None if tracers is None else (tracers, tracers_every, tracers_from, tracers_capacity))
     table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
     if planes is not None:
         table.update(field_table(prms, [r.field_avg for r in members]))
@@ -997,4 +1111,6 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
         table.update({k: np.array([f[k] for f in figs]) for k in ("r_min_dp", "n_neigh", "sigma1_dp")})
     if gradients_from is not None:
         table.update(_grad_columns(prms, [r.grad_stats for r in members]))
+    if tracers is not None:
+        table.update(_tracer_columns(prms, [r.tracers for r in members]))
     return SweepResult(members=members, table=table, wall_seconds=wall, grid_policy=policy)

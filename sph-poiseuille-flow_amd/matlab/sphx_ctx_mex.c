@@ -45,6 +45,12 @@
  *   [sums, n_samples, t_first, t_last] = sphx_ctx_mex('grad_read', h, band)
  *       sums: n_bins x 12, one column per field in the order of include/sphx.h section 2n (gradient statistics): count,
  *       sum g_xx, g_xy, g_yx, g_yy, their four squares, sum div^2, sum omega^2, skipped
+ *   sphx_ctx_mex('tracer_enable', h, ids, every, capacity, t_from)   % ids: fluid row numbers as MATLAB counts them (1-based)
+ *   sphx_ctx_mex('tracer_disable', h)
+ *   sphx_ctx_mex('tracer_sample', h)   % append one record of the current state now
+ *   [ids, step, t, x, y, u_x, u_y, n_dropped, n_missing] = sphx_ctx_mex('tracer_read', h, drain)
+ *       ids: T x 1 (1-based, as given); step, t: n x 1; x, y, u_x, u_y: n x T, one row per recorded step, column k the
+ *       particle in row ids(k) of 'download' (particle tracers, include/sphx.h section 2p); drain ~= 0 empties the device buffer
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -306,6 +312,71 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         mxFree(times);
         mxFree(values);
         if (nlhs > 6) plhs[6] = mxCreateDoubleScalar((double)dropped);
+    } else if (strcmp(cmd, "tracer_enable") == 0) {
+        sphx_tracers_config tc;
+        const mxArray *ids;
+        int32_t *rows;
+        size_t nt, k;
+        int rc;
+        arity(cmd, nrhs, 6, nlhs, 0);
+        ids = prhs[2];
+        if (!mxIsDouble(ids) || mxGetNumberOfElements(ids) == 0)
+            mexErrMsgIdAndTxt("SPHX:Tracers:config", "tracer_enable: ids must be a non-empty double vector of fluid row numbers (1-based)");
+        nt = mxGetNumberOfElements(ids);
+        if (nt > 0x7fffffff) mexErrMsgIdAndTxt("SPHX:Tracers:config", "tracer_enable: too many ids");
+        rows = (int32_t *)mxMalloc(nt * sizeof(int32_t));
+        for (k = 0; k < nt; ++k) {  /* MATLAB counts rows from 1, the library from 0; -1: never a valid row */
+            const double r = mxGetDoubles(ids)[k];
+            rows[k] = (r >= 1.0 && r <= 2147483647.0 && r == (double)(int32_t)r) ? (int32_t)r - 1 : -1;
+        }
+        memset(&tc, 0, sizeof(tc));
+        tc.n_tracers = (int32_t)nt;
+        tc.every = (int32_t)mxGetScalar(prhs[3]);
+        tc.capacity = (int32_t)mxGetScalar(prhs[4]);
+        tc.t_from = mxGetScalar(prhs[5]);
+        tc.ids = rows;
+        rc = sphx_ctx_tracers_enable(handle(prhs[1]), &tc);  /* (the ids are copied) */
+        mxFree(rows);
+        ok(rc);
+    } else if (strcmp(cmd, "tracer_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_tracers_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "tracer_sample") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_tracers_sample(handle(prhs[1])));
+    } else if (strcmp(cmd, "tracer_read") == 0) {
+        sphx_ctx *c;
+        int n = 0, got = 0, nt = 0, k, p, f, drain, rc;
+        int64_t dropped = 0, missing = 0;
+        int32_t *ids;
+        double *times, *values;
+        arity(cmd, nrhs, 3, nlhs, 9);
+        c = handle(prhs[1]);
+        drain = mxGetScalar(prhs[2]) != 0.0;
+        ok(sphx_ctx_tracers_read(c, 0, NULL, NULL, NULL, &nt, &n, NULL, NULL, 0));
+        times = (double *)mxMalloc((size_t)(n > 0 ? n : 1) * 2 * sizeof(double));
+        values = (double *)mxMalloc((size_t)(n > 0 ? n : 1) * (size_t)nt * SPHX_TRACER_FIELDS * sizeof(double));
+        ids = (int32_t *)mxMalloc((size_t)nt * sizeof(int32_t));
+        rc = sphx_ctx_tracers_read(c, n, times, values, ids, NULL, &got, &dropped, &missing, drain);  /* (nothing is stepped in between: got == n) */
+        if (rc != SPHX_OK) { mxFree(times); mxFree(values); mxFree(ids); ok(rc); }
+        plhs[0] = mxCreateDoubleMatrix((mwSize)nt, 1, mxREAL);  /* the ids as MATLAB counts them */
+        for (p = 0; p < nt; ++p) mxGetDoubles(plhs[0])[p] = (double)ids[p] + 1.0;
+        for (f = 0; f < 2 && 1 + f < nlhs; ++f) {
+            plhs[1 + f] = mxCreateDoubleMatrix((mwSize)got, 1, mxREAL);
+            for (k = 0; k < got; ++k) mxGetDoubles(plhs[1 + f])[k] = times[(size_t)k * 2 + f];
+        }
+        for (f = 0; f < SPHX_TRACER_FIELDS && 3 + f < nlhs; ++f) {  /* the library's rows are records; MATLAB stores columns */
+            double *out;
+            plhs[3 + f] = mxCreateDoubleMatrix((mwSize)got, (mwSize)nt, mxREAL);
+            out = mxGetDoubles(plhs[3 + f]);
+            for (k = 0; k < got; ++k)
+                for (p = 0; p < nt; ++p) out[(size_t)p * got + k] = values[((size_t)k * nt + p) * SPHX_TRACER_FIELDS + f];
+        }
+        mxFree(times);
+        mxFree(values);
+        mxFree(ids);
+        if (nlhs > 7) plhs[7] = mxCreateDoubleScalar((double)dropped);
+        if (nlhs > 8) plhs[8] = mxCreateDoubleScalar((double)missing);
     } else if (strcmp(cmd, "pseries_enable") == 0) {
         sphx_profile_series_config sc;
         const mxArray *b;

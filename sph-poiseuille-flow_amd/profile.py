@@ -667,3 +667,105 @@ def pool_grad_stats(DH, sums_list):
     out = grad_stats_profiles(DH, total)
     out.update({f: total[f] for f in GRAD_FIELDS}, n_members=len(sums_list))
     return out
+
+
+# ---- particle tracers (include/sphx.h sections 2p / 2q): the Lagrangian view ----
+TRACER_FIELDS = ("x", "y", "u_x", "u_y")  # the four values per tracer and record, in the order the library writes them
+
+
+def tracer_rows(pos, vel, ids):
+    """The definition of a tracer record: x, y, u_x, u_y [T] of the rows `ids` of a downloaded state (pos, vel [n, 2]), copied."""
+    pos, vel = np.asarray(pos, dtype=np.float64), np.asarray(vel, dtype=np.float64)
+    ids = np.asarray(ids, dtype=np.int64).ravel()
+    return dict(x=pos[ids, 0].copy(), y=pos[ids, 1].copy(), u_x=vel[ids, 0].copy(), u_y=vel[ids, 1].copy())
+
+
+def unwrap_tracers(tr, DL):
+    """A copy of the tracers dict tr (capi.tracers_dict: t [n], x, u_x [n, T]) with x_unwrapped [n, T]: record 0 as it is, then
+    the image x + k DL of each x nearest to x_prev + 0.5 (u_prev + u) (t - t_prev), the trapezoidal prediction from the record
+    before.  k DL is added once to the recorded x, so the result is the exact unwrapped position wherever that is
+    representable.  Raises ValueError when |u_x| (t - t_prev) >= DL / 2 for any tracer and record: the series is then too
+    coarse for the nearest image to be the right one."""
+    t = np.asarray(tr["t"], dtype=np.float64)
+    x, u = np.asarray(tr["x"], dtype=np.float64), np.asarray(tr["u_x"], dtype=np.float64)
+    if x.ndim != 2 or x.shape != u.shape or len(t) != len(x):
+        raise ValueError("unwrap_tracers: t [n] and x, u_x [n, T] expected")
+    xu = x.copy()
+    if len(t) > 1:
+        dt = np.diff(t)[:, None]
+        if np.any(dt < 0.0):
+            raise ValueError("unwrap_tracers: t must not decrease")
+        far = np.maximum(np.abs(u[1:]), np.abs(u[:-1])) * dt
+        if np.any(~(far < 0.5 * DL)):
+            r, k = np.argwhere(~(far < 0.5 * DL))[0]
+            raise ValueError(f"unwrap_tracers: the series is too coarse to unwrap: tracer {int(k)} moves {float(far[r, k]):.4g} between "
+                             f"records {int(r)} and {int(r) + 1}, DL / 2 is {0.5 * DL:.4g}")
+        for r in range(1, len(t)):
+            pred = xu[r - 1] + 0.5 * (u[r - 1] + u[r]) * dt[r - 1]
+            xu[r] = x[r] + np.round((pred - x[r]) / DL) * DL
+    return dict(tr, x_unwrapped=xu)
+
+
+def poiseuille_u(y, g, nu, DH):
+    """The analytic steady profile u(y) = g / (2 nu) y (DH - y)."""
+    y = np.asarray(y, dtype=np.float64)
+    return g / (2.0 * nu) * y * (DH - y)
+
+
+def tracer_profiles(tr, DL, DH, g, nu, lags=None, y_margin=0.0):
+    """The Lagrangian figures of a tracers dict, over the tracers whose first recorded y lies at least y_margin from both walls:
+    lags [L] (in records; default 1, 2, 4, ... up to a quarter of the series), tau [L] (the mean time span of a lag), msd_y [L]
+    (mean square of y(r + lag) - y(r) over the tracers and the origins r = 0, lag, 2 lag, ...: windows that do not overlap),
+    msd_x_rel [L] (the same of the unwrapped x displacement minus u_exact(y(r)) * (t(r + lag) - t(r))), D_y (half the
+    least-squares slope of msd_y against tau; one lag: msd_y / (2 tau)), y_drift (the mean of (y_last - y_first) / (t_last -
+    t_first)), u_dev_rms (the r.m.s. of u_x - u_exact(y) along the paths, in units of |U_max| = |g| DH^2 / (8 nu)), n_tracers,
+    n_records.  In laminar Poiseuille flow every one of them is zero for the exact solution."""
+    t = np.asarray(tr["t"], dtype=np.float64)
+    keep = (np.asarray(tr["y"], dtype=np.float64)[0] >= y_margin) & (np.asarray(tr["y"], dtype=np.float64)[0] <= DH - y_margin) \
+        if len(t) else np.zeros(np.asarray(tr["y"]).shape[1:], dtype=bool)
+    R = len(t)
+    if R < 2 or not np.any(keep):
+        raise ValueError("tracer_profiles needs at least two records and one tracer inside the margins")
+    xu = np.asarray(tr["x_unwrapped"] if "x_unwrapped" in tr else unwrap_tracers(tr, DL)["x_unwrapped"], dtype=np.float64)[:, keep]
+    y, u = np.asarray(tr["y"], dtype=np.float64)[:, keep], np.asarray(tr["u_x"], dtype=np.float64)[:, keep]
+    if lags is None:
+        lags = [1]
+        while 2 * lags[-1] <= max((R - 1) // 4, 1):
+            lags.append(2 * lags[-1])
+    lags = np.asarray(lags, dtype=np.int64).ravel()
+    if len(lags) < 1 or np.any(lags < 1) or np.any(lags > R - 1):
+        raise ValueError("tracer_profiles: lags must be record counts in 1 .. n_records - 1")
+    tau, msd_y, msd_x = np.zeros(len(lags)), np.zeros(len(lags)), np.zeros(len(lags))
+    for j, lag in enumerate(lags):
+        r0 = np.arange(0, R - lag, lag)
+        span = (t[r0 + lag] - t[r0])[:, None]
+        dy = y[r0 + lag] - y[r0]
+        dx = xu[r0 + lag] - xu[r0] - poiseuille_u(y[r0], g, nu, DH) * span
+        tau[j], msd_y[j], msd_x[j] = float(np.mean(span)), float(np.mean(dy * dy)), float(np.mean(dx * dx))
+    D_y = 0.5 * float(np.polyfit(tau, msd_y, 1)[0]) if len(lags) > 1 else 0.5 * msd_y[0] / tau[0]
+    U_max = abs(g) * DH * DH / (8.0 * nu)
+    dev = u - poiseuille_u(y, g, nu, DH)
+    return dict(lags=lags, tau=tau, msd_y=msd_y, msd_x_rel=msd_x, D_y=D_y, y_drift=float(np.mean((y[-1] - y[0]) / (t[-1] - t[0]))),
+                u_dev_rms=float(np.sqrt(np.mean(dev * dev))) / U_max, n_tracers=int(np.count_nonzero(keep)), n_records=R)
+
+
+def pool_tracers(tr_list):
+    """The tracer series of several channels (the members of an ensemble) as one: the columns of every member side by side, in
+    member order -- x, y, u_x, u_y (and x_unwrapped where every member has it) [n, M T], ids [M T] and member [M T], the member a
+    column came from.  The members must have recorded the same ids at the same steps and times: ValueError otherwise."""
+    tr_list = list(tr_list)
+    if not tr_list:
+        raise ValueError("pool_tracers needs the series of at least one member")
+    first = tr_list[0]
+    for m, tr in enumerate(tr_list[1:], 1):
+        for k in ("ids", "step", "t"):
+            if not np.array_equal(np.asarray(tr[k]), np.asarray(first[k])):
+                raise ValueError(f"pool_tracers: member {m} differs from member 0 in {k}")
+    T = len(np.asarray(first["ids"]).ravel())
+    fields = TRACER_FIELDS + (("x_unwrapped",) if all("x_unwrapped" in tr for tr in tr_list) else ())
+    out = dict(ids=np.tile(np.asarray(first["ids"]).ravel(), len(tr_list)), member=np.repeat(np.arange(len(tr_list)), T),
+               step=np.asarray(first["step"]).copy(), t=np.asarray(first["t"], dtype=np.float64).copy())
+    out.update({k: np.concatenate([np.asarray(tr[k], dtype=np.float64).reshape(len(out["t"]), T) for tr in tr_list], axis=1) for k in fields})
+    out.update(n_dropped=int(sum(tr.get("n_dropped", 0) for tr in tr_list)), n_missing=int(sum(tr.get("n_missing", 0) for tr in tr_list)),
+               n_members=len(tr_list))
+    return out
