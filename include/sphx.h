@@ -973,7 +973,7 @@ int sphx_batch_grad_stats_read(sphx_batch *batch, int band, int capacity, int *n
  *    wall row, every < 1, capacity < 1 or capacity * n_tracers * 4 > 1 << 27, non-finite t_from, or the allocation fails:
  *    the context then goes on without tracers), SPHX:Tracers:disabled (SPHX_ERR_STATE: a call that needs the tracers while
  *    they are off), SPHX:Tracers:capacity (the caller's arrays are smaller than n_records); every call on a slab context
- *    fails with SPHX_ERR_ARG, SPHX:Tracers:slab.  A refused enable leaves running tracers, and their records, untouched.
+ *    fails with SPHX_ERR_ARG, SPHX:Tracers:slab (the tracers of a ring: sphx_slab_tracers_*, section 3a).  A refused enable leaves running tracers, and their records, untouched.
  * ---------------------------------------------------------------------------------------------- */
 
 #define SPHX_TRACER_FIELDS 4
@@ -1105,7 +1105,7 @@ int sphx_slab_snapshot(sphx_ctx *ctx, int capacity, int *n, double *x, double *y
 /* ------------------------------------------------------------------------------------------------
  * 3a. Samplers of a slab ring: the flow statistics of section 2a, the step history of section 2d, the velocity-field
  *    map of section 2e, the point probes of section 2h, the profile series of section 2j, the pair statistics of
- *    section 2l and the gradient statistics of section 2n (the last four described with their calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that
+ *    section 2l, the gradient statistics of section 2n and the particle tracers of section 2p (the last five described with their calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that
  *    a ring reports its time-averaged profile, the settling of its wall shear, its averaged field and its profile at every
  *    sampled step without a snapshot per sample.  The config structs, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* / SPHX:Field:*
  *    identifiers are those of sections 2a / 2d / 2e; sphx_ctx_flow_stats_*,
@@ -1259,6 +1259,35 @@ int sphx_slab_gstats_reset(sphx_ctx *ctx);
 /* The slab's partial sums of one band; arguments as sphx_ctx_grad_stats_read. */
 int sphx_slab_gstats_read(sphx_ctx *ctx, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples, double *t_first,
                           double *t_last);
+/* Particle tracers of a ring (the tracers of section 2p; k_tracers_s).  The one sampler whose subject moves between the slabs:
+ * OWNERSHIP MOVES WITH THE PARTICLE.  cfg holds the RING's id list, the same on every rank (the rows of the channel the ring was
+ * cut from); the config, its checks and the SPHX:Tracers:config identifier are those of section 2p, the bound
+ * capacity * n_tracers * 4 <= 1 << 27 doubles holding per slab with the ring's n_tracers.  At the end of a sampled step a slab
+ * copies x, y, u_x, u_y of every tracked particle it OWNS at that step -- the fluid particles sphx_slab_snapshot marks owned,
+ * never a halo copy, which is its owner's to record -- into the particle's column of a DENSE row of n_tracers columns, the bits
+ * sphx_slab_snapshot returns for that id, with no arithmetic: x in the slab's own frame as the state holds it, which may be
+ * below 0 on the first slab and at or above DL on the last.  Every fluid row has exactly one owner at every step, so every
+ * column of a record is written by exactly one slab of the ring; ownership changes hands at the ring's re-binnings only.
+ *  Columns a slab did not own: the value buffer is filled with NaN (every byte 0xFF) at enable and the rows a draining read
+ *    hands out are filled again, so a column the slab did not write reads NaN in all four fields.  A particle's x is never NaN.
+ *  n_owned replaces n_missing: the slab stores the number of tracers it met, per record, beside {step, t}.  The ring's
+ *    invariant is that the slabs' n_owned of a record add up to n_tracers: a particle lost or held twice when ownership changes
+ *    hands shows in the record of the very step it happens.  A slab that owns no tracer still records {step, t} with
+ *    n_owned = 0, so step, t, n_records and n_dropped are the same on every rank.
+ *  The ring's series: every column of every record from the one rank where it is not NaN; nothing is added.
+ *  Memory: capacity * (3 + n_tracers * 4) doubles per slab -- the dense form costs n_ranks times a context's ring-wide.
+ *  A refused enable leaves a running series, its records and a prepared graph as they are.  SPHX:Tracers:disabled: a read while
+ *  the tracers are off; disable is a no-op then.  There is no "sample now" call.  sphx_ctx_tracers_* keep refusing a slab
+ *  (SPHX:Tracers:slab). */
+int sphx_slab_tracers_enable(sphx_ctx *ctx, const sphx_tracers_config *cfg);
+int sphx_slab_tracers_disable(sphx_ctx *ctx);
+/* The slab's records: times [capacity][2], values [capacity][*n_tracers][SPHX_TRACER_FIELDS] (row-major, NaN where the slab
+ * was not the owner) and n_owned [capacity]; ids [*n_tracers]: the ring's list as given at enable.  Any output may be NULL.
+ * capacity = 0: only the sizes and counts are reported, nothing is copied or drained; SPHX:Tracers:capacity when an array is
+ * given and capacity is below n_records.  drain != 0: the buffer is emptied, n_dropped zeroed and the rows handed out filled
+ * with NaN again after copying.  Waits for the slab's stream(s) itself. */
+int sphx_slab_tracers_read(sphx_ctx *ctx, int capacity, double *times, double *values, int64_t *n_owned, int32_t *ids,
+                           int *n_tracers, int *n_records, int64_t *n_dropped, int drain);
 
 #ifdef __cplusplus
 }

@@ -133,6 +133,7 @@ EXPORTS = [
     "sphx_slab_pseries_enable", "sphx_slab_pseries_disable", "sphx_slab_pseries_read",
     "sphx_slab_pairs_enable", "sphx_slab_pairs_disable", "sphx_slab_pairs_reset", "sphx_slab_pairs_read",
     "sphx_slab_gstats_enable", "sphx_slab_gstats_disable", "sphx_slab_gstats_reset", "sphx_slab_gstats_read",
+    "sphx_slab_tracers_enable", "sphx_slab_tracers_disable", "sphx_slab_tracers_read",
     "sphx_batch_create", "sphx_batch_destroy", "sphx_batch_advance", "sphx_batch_enqueue_steps", "sphx_batch_sync",
     "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
     "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",

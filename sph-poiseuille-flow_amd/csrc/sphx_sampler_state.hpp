@@ -173,24 +173,29 @@ struct GradStats {
 
 // Particle tracers (sphx_ctx_tracers_*, sphx_batch_tracers_*; sphx_tracers.hpp) of a context or of the M members of a batch: one
 // configuration and one id list, member m's times at m * cfg.capacity * 2, its values at m * cfg.capacity * row(), its head at
-// m; the table index_of [n_fluid] is shared.
+// m; the table index_of [n_fluid] is shared.  Of a slab of a ring (sphx_slab_tracers_*): cfg and ids are the ring's list, the
+// same on every rank; the rows are dense -- T columns, NaN (byte 0xFF, nan_fill) where the slab was not the owner at that
+// step -- and n_owned [capacity] holds the tracers the slab met per record.
 struct Tracers {
     bool on = false;
     int members = 1;
     sphx_tracers_config cfg{};    // (cfg.ids: nullptr -- the ids are copied)
     std::vector<int32_t> ids;     // [n_tracers] as the caller gave them
     int n_fluid = 0;
+    bool part = false;            // a slab's: a column is written only while the slab owns the particle
     DevBuf<int> index_of;
     DevBuf<double> times, values;
+    DevBuf<long long> n_owned;    // (a slab's only)
     DevBuf<TracerHead> head;
 
     size_t row() const { return (size_t)cfg.n_tracers * kTracerFields; }  // the values of one record
     void check(int n_fluid, int n_total, const sphx_tracers_config *cfg, int M);
     void alloc(const Tracers &checked, int M, hipStream_t st);
     void zero(hipStream_t st) { head.zero(st); }  // (the counters: records beyond n_records are never read)
-    void release() { index_of.release(); times.release(); values.release(); head.release(); }
+    void release() { index_of.release(); times.release(); values.release(); n_owned.release(); head.release(); }
+    void nan_fill(hipStream_t st, size_t rows);  // a slab's: the first `rows` rows of values read NaN again
     void read(hipStream_t st, int capacity, double *times, double *values, int *n_records, int64_t *n_dropped, int64_t *n_missing,
-              bool drain);
+              bool drain, int64_t *n_owned = nullptr);
 };
 
 // the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes, profile series,

@@ -1,8 +1,8 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
 // the velocity-field map (2e; 2g), the point probes (2h; 2i), the profile series (2j; 2k), the pair statistics (2l; 2m,
-// sphx_pair_dist.hpp) and the gradient statistics (2n; 2o, sphx_grad_stats.hpp) -- all seven also of a slab of a ring (3a, at the end of this file) --
-// and the particle tracers (2p; 2q, sphx_tracers.hpp; contexts and batches).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// sphx_pair_dist.hpp), the gradient statistics (2n; 2o, sphx_grad_stats.hpp) and the particle tracers (2p; 2q, sphx_tracers.hpp) --
+// all eight also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -35,7 +35,7 @@ constexpr SamplerNames kPairNames{"PairDist", "the pair statistics of a slab are
                                   "the sums could not be set up: "};
 constexpr SamplerNames kGradNames{"GradStats", "the gradient statistics of a slab are sphx_slab_gstats_* (include/sphx.h section 3a)",
                                   "gradient statistics are not enabled on this ", "the sums could not be set up: "};
-constexpr SamplerNames kTracerNames{"Tracers", "particle tracers are not available on slab contexts",
+constexpr SamplerNames kTracerNames{"Tracers", "the tracers of a slab are sphx_slab_tracers_* (include/sphx.h section 3a)",
                                     "particle tracers are not enabled on this ", "the record buffer could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
@@ -916,23 +916,34 @@ void Tracers::alloc(const Tracers &checked, int M, hipStream_t st)
     cfg = checked.cfg;
     ids = checked.ids;
     n_fluid = checked.n_fluid;
+    part = checked.part;
     members = M;
     index_of.alloc((size_t)n_fluid);
     times.alloc((size_t)M * cfg.capacity * 2);
     values.alloc((size_t)M * cfg.capacity * row());
+    if (part) n_owned.alloc((size_t)cfg.capacity);
     head.alloc(M);
+    if (part) nan_fill(st, (size_t)cfg.capacity);
     std::vector<int> table((size_t)n_fluid, -1);
     for (int k = 0; k < cfg.n_tracers; ++k) table[(size_t)ids[(size_t)k]] = k;
     index_of.upload(table.data(), table.size(), st);
     SPHX_HIP(hipStreamSynchronize(st));  // (`table` goes out of scope here)
 }
 
+// A slab's value rows 0 .. rows - 1 read NaN again (every byte 0xFF), enqueued on st: a column is written only by the slab that
+// owns the particle at that step, so what nobody wrote must be recognisable -- and a particle's x is never NaN.
+void Tracers::nan_fill(hipStream_t st, size_t rows)
+{
+    if (rows) SPHX_HIP(hipMemsetAsync(values.get(), 0xFF, rows * row() * sizeof(double), st));
+}
+
 // Every member's counts (n_records[m], n_dropped[m], n_missing[m], where given) and its filled rows, into
 // times[m][0 .. n_records[m])[2] of a [members][capacity][2] array and values[m][0 .. n_records[m])[row()] of a
 // [members][capacity][row()] array, each where given; drain empties every buffer.  SPHX:Tracers:capacity when an array is given
-// and capacity is below the largest count: nothing is copied or drained then.
+// and capacity is below the largest count: nothing is copied or drained then.  A slab's (one channel): owned_out [0 .. n_records)
+// the tracers it met per record, an array like the other two, and a draining read refills the rows it hands out with NaN.
 void Tracers::read(hipStream_t st, int capacity, double *t_out, double *v_out, int *n_records, int64_t *n_dropped, int64_t *n_missing,
-                   bool drain)
+                   bool drain, int64_t *owned_out)
 {
     const int M = members;
     std::vector<TracerHead> h(M);
@@ -944,8 +955,13 @@ void Tracers::read(hipStream_t st, int capacity, double *t_out, double *v_out, i
         if (n < 0 || n > (long long)cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:Tracers:state", "internal: record count out of range");
         most = std::max(most, n);
     }
-    require((t_out == nullptr && v_out == nullptr) || (long long)capacity >= most, "SPHX:Tracers:capacity",
+    if (!part) owned_out = nullptr;
+    require((t_out == nullptr && v_out == nullptr && owned_out == nullptr) || (long long)capacity >= most, "SPHX:Tracers:capacity",
             "capacity is smaller than the number of records");
+    static_assert(sizeof(long long) == sizeof(int64_t), "n_owned is copied as it is");
+    if (owned_out && most > 0)
+        SPHX_HIP(hipMemcpyAsync(owned_out, n_owned.get(), (size_t)most * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (owned_out && !(t_out || v_out)) SPHX_HIP(hipStreamSynchronize(st));
     if ((t_out || v_out) && most > 0) {
         for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
             const size_t n = (size_t)h[m].n_records;
@@ -966,6 +982,7 @@ void Tracers::read(hipStream_t st, int capacity, double *t_out, double *v_out, i
     }
     if (drain) {
         zero(st);
+        if (part) nan_fill(st, (size_t)most);  // (rows beyond n_records were never written: a dropped record stores no value)
         SPHX_HIP(hipStreamSynchronize(st));
     }
 }
@@ -1477,6 +1494,10 @@ SPHX_EXPORT int sphx_ctx_grad_stats_read(sphx_ctx *c, int band, int capacity, in
 // takes its partners from every slot the slab holds, halo copies included -- their positions, velocities and masses (the field
 // map's and the probes' premises) -- and the ring's sums are the slabs' added up, count and skipped included
 // (sphx_slab_gstats_*: no function of include/sphx.h carries both "slab" and "grad" in its name).
+// The particle tracers: the one sampler whose subject moves between the slabs.  A slab copies the tracked particles it OWNS at
+// the sampled step -- the ring's id list and table on every rank, dense rows, NaN where it was not the owner -- and counts
+// them per record (n_owned); every fluid row has one owner at every step, so the ring's record is each column taken from the
+// one rank that wrote it, and the slabs' n_owned add up to T.  The halo is never read.
 
 namespace {
 
@@ -1484,11 +1505,13 @@ namespace {
 // later) and in front of everything of phase 3: the clock is the finished step's, S[1-q] holds the owned particles' new state,
 // Vol / B (c->tmp) and the layout arrays (cell, mass) are those of the layout the step ran in -- clk->n is still that
 // layout's count (k_slab_unpack3 sets the new one), so a re-binning step needs no src_of.  One self-skipping launch each,
-// on the slab's stream, in the order statistics, history, map, probes, profile series, pair statistics, gradient statistics;
+// on the slab's stream, in the order statistics, history, map, probes, profile series, pair statistics, gradient statistics,
+// tracers;
 // all off: nothing is enqueued, and a sampler that is off adds nothing to what the others enqueue.
 void launch_slab_samplers(sphx_ctx *c)
 {
-    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on && !c->pseries.on && !c->pairs.on && !c->grads.on) return;
+    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on && !c->pseries.on && !c->pairs.on && !c->grads.on && !c->tracers.on)
+        return;
     const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
     const FluidSet s = c->view(1 - q, 0);
@@ -1535,6 +1558,14 @@ void launch_slab_samplers(sphx_ctx *c)
     if (c->grads.on)
         launch_s(c, "k_grad_stats_s", k_grad_stats_s, dim3(grad_stats_blocks((size_t)c->cap)), dim3(kGradBlock), c->grads.shmem(), clk, q,
                  c->grid, c->phys, s, c->walls, grad_stats_args(c, c->grads.cfg.every));
+    // (pos, vel, the ids and the binned cells of S[1-q]: only slots the slab OWNS are copied, so nothing is asked of the halo;
+    //  the scan runs over the clk->n held, bounded by the capacity, from which the workgroups come too; the table is the ring's)
+    if (c->tracers.on) {
+        TracerArgs a = tracer_args(c, c->tracers.cfg.every);
+        a.n_slots = c->cap;
+        launch_s(c, "k_tracers_s", k_tracers_s, dim3(tracer_blocks((size_t)c->cap)), dim3(kTracerBlock), 0, clk, q, s, a, c->grid,
+                 c->tracers.n_owned.get());
+    }
 }
 
 // The rank of slab c's ring that owns a probe at x, folded into [0, DL): rank r when edge(r) <= x < edge(r + 1), with
@@ -1900,6 +1931,46 @@ SPHX_EXPORT int sphx_slab_gstats_read(sphx_ctx *c, int band, int capacity, int *
     SPHX_TRY
     const GradStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::grads, kGradNames);
     grad_stats_read(f, c->stream, [c] { slab_settle(c); }, band, capacity, n_bins, sums, n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_tracers_enable(sphx_ctx *c, const sphx_tracers_config *cfg)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    Tracers checked;
+    checked.check(c->nf, c->nt, cfg, 1);  // (a refused configuration leaves a running series and a prepared graph as they are)
+    checked.part = true;
+    slab_samplers_changed(c);
+    sampler_on(c->tracers, kTracerNames, c->sched, c->stream, [&] { c->tracers.alloc(checked, 1, c->stream); });
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_tracers_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    if (c->tracers.on) {
+        slab_samplers_changed(c);
+        sampler_off(c->tracers, c->sched, c->stream);
+    }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_tracers_read(sphx_ctx *c, int capacity, double *times, double *values, int64_t *n_owned, int32_t *ids,
+                                       int *n_tracers, int *n_records, int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    Tracers &t = slab_sampler_on(sampled_slab(c), &sphx_ctx::tracers, kTracerNames);
+    slab_settle(c);  // (the records of everything enqueued)
+    const bool sizes_only = capacity == 0;  // nothing is copied and nothing drained
+    t.read(c->stream, capacity, sizes_only ? nullptr : times, sizes_only ? nullptr : values, n_records, n_dropped, nullptr,
+           !sizes_only && drain != 0, sizes_only ? nullptr : n_owned);
+    if (ids) std::copy(t.ids.begin(), t.ids.end(), ids);
+    if (n_tracers) *n_tracers = t.cfg.n_tracers;
     return SPHX_OK;
     SPHX_CATCH
 }

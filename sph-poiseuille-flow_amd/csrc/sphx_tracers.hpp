@@ -1,5 +1,5 @@
-// sphx_tracers.hpp -- particle tracers of a resident context (include/sphx.h section 2p) and of every member of a batch
-// (section 2q, k_tracers_b): a slot sampler (sphx_slot_sample.hpp) that follows T chosen fluid rows of the caller's numbering
+// sphx_tracers.hpp -- particle tracers of a resident context (include/sphx.h section 2p), of every member of a batch
+// (section 2q, k_tracers_b) and of a slab of a ring (section 3a, k_tracers_s): a slot sampler (sphx_slot_sample.hpp) that follows T chosen fluid rows of the caller's numbering
 // and appends one record -- {step, t} and T x kTracerFields values -- to a record buffer in device memory.  The one sampler
 // that is Lagrangian: the other seven report what passes a bin, a node or a point.
 //
@@ -14,8 +14,8 @@
 // L2).  T = 1 and T = n_fluid run the same code.
 //
 // Bounds.
-//  * Slots: i < min(clk->n, a.n_slots).  clk->n is the population; arrays with slack (a slab's, in the follow-up) hold stale ids
-//    behind it, which would write a column twice.  a.n_slots, the particle count the host allocated the view for, is a second
+//  * Slots: i < min(clk->n, a.n_slots).  clk->n is the population; arrays with slack (a slab's: n_slots is its capacity) hold
+//    stale ids behind it, which would write a column twice.  a.n_slots, the particle count the host allocated the view for, is a second
 //    bound that costs nothing: no word of the clock can send a load past the arrays.
 //  * Table: the id is compared as unsigned against n_fluid in front of the table read, so a negative or foreign id reads nothing.
 //  * Column: 0 <= k < n_tracers is checked although the host built the table: the store's address depends on it.
@@ -54,6 +54,27 @@
 // sticky counter the read reports.  On a context and on a batch member it is always 0: it is the invariant of the id
 // bookkeeping (FluidSet::id through the fold-rebin path, the scatter / reorder chain, the in-place dynamic path, a batch's
 // realignment).  The tracers are counted as MET whether or not the row had room, so a dropped record still checks it.
+//
+// A slab of a ring (include/sphx.h section 3a, k_tracers_s = tracers_body<true>).  OWNERSHIP MOVES WITH THE PARTICLE: a slab
+// holds the particles it owns and halo copies of its neighbours', the copies under their particles' ids, and a particle
+// changes hands at a re-binning (the id lists of message B).  TracerArgs is unchanged -- index_of is the RING's table, the
+// same on every rank, n_fluid the ring's count, n_slots the slab's capacity -- and the scan is the one above with one more
+// condition for a hit: the slab OWNS the slot, owns(g, pos.x, s.cell[i]), the binned column on a skinned slab, which is what
+// sphx_slab_snapshot marks owned and what every other ring sampler sums by.  A halo copy is its owner's to record.  Every
+// fluid row has exactly one owner at every step, so every tracked id has exactly one writer in the whole ring: no premise
+// about the halo's state is needed, the copies are never read.  What is copied are the bits of pos and vel of S[1-q], x in
+// the SLAB'S frame as the state holds it -- the first slab keeps particles it took over from the last one below 0 until they
+// are folded, the last slab may hold x >= DL -- which is what sphx_slab_snapshot returns for that id.
+//  * n_owned replaces n_missing.  "Not met" is normal on a slab, so the stamping thread does not touch the sticky n_missing;
+//    it stores the count of tracers met -- the total that rode in the ticket, fence-free as above -- into n_owned[row], an
+//    int64 array beside {step, t}.  The ring's invariant: the slabs' n_owned of a record add up to T.  A particle lost or
+//    held twice at a re-binning shows in the record of the very step it happens.
+//  * Columns the slab does not own are never written.  The host fills the value buffer with NaN (byte 0xFF) at enable and
+//    refills the rows a draining read hands out, on the slab's stream, so a column nobody wrote reads NaN -- a particle's x
+//    never does -- and the step loop pays nothing for it.
+//  * The dense row costs G times the memory ring-wide; see DESIGN.md section 5 for why it was taken.
+//  * Grid: tracer_blocks(capacity), fixed, so a captured step graph outlives a re-binning.  Launched behind k_slab_pack3 and
+//    in front of everything of phase 3 (launch_slab_samplers): clk->n and s.cell are those of the layout the step ran in.
 #pragma once
 #include "../../include/sphx.h"
 #include "sphx_slot_sample.hpp"
@@ -89,7 +110,11 @@ struct TracerArgs {
 // The record of one channel closing the step slot of parity q, on clock clk, by the gridDim.x workgroups of a grid row; s is the
 // state the step left (pos, vel and the ids of the layout it is stored in); a's times / values / head are that channel's own.
 // Every thread of every workgroup reaches the barrier.
-__device__ __forceinline__ void tracers_body(const Clock *clk, int q, const FluidSet &s, const TracerArgs &a)
+// kSlab: the channel is a slab of a ring -- of the slots it holds only those it owns (owns() on grid g) are copied and
+// counted, and the count goes into n_owned[row] instead of n_missing (k_tracers_s).
+template <bool kSlab = false>
+__device__ __forceinline__ void tracers_body(const Clock *clk, int q, const FluidSet &s, const TracerArgs &a, const Grid *g = nullptr,
+                                             long long *n_owned = nullptr)
 {
     if (!sample_due(clk, q, a.every, a.t_from)) return;
     __shared__ unsigned s_met;
@@ -111,7 +136,8 @@ __device__ __forceinline__ void tracers_body(const Clock *clk, int q, const Flui
             const unsigned id = (unsigned)s.id[i];
             if (id < nf) k = a.index_of[id];
         }
-        const bool hit = k >= 0 && k < a.n_tracers;
+        bool hit = k >= 0 && k < a.n_tracers;
+        if constexpr (kSlab) hit = hit && owns(*g, s.pos[i].x, s.cell[i]);  // (a halo copy: its owner records it)
         if (hit && room) {
             const double2 p = s.pos[i], v = s.vel[i];
             double2 *out = reinterpret_cast<double2 *>(a.values + ((size_t)at * (size_t)a.n_tracers + (size_t)k) * kTracerFields);
@@ -138,8 +164,12 @@ __device__ __forceinline__ void tracers_body(const Clock *clk, int q, const Flui
     } else {
         h->n_dropped += 1;
     }
-    const long long missing = (long long)a.n_tracers - (long long)total;
-    if (missing != 0) h->n_missing += missing;
+    if constexpr (kSlab) {
+        if (room) n_owned[at] = (long long)total;
+    } else {
+        const long long missing = (long long)a.n_tracers - (long long)total;
+        if (missing != 0) h->n_missing += missing;
+    }
 }
 
 // q: parity of the step slot this launch closes
@@ -159,6 +189,14 @@ __global__ __launch_bounds__(kTracerBlock) void k_tracers_b(Members mb, int q, F
     a.values += (size_t)m * (size_t)a.capacity * (size_t)a.n_tracers * kTracerFields;
     a.head += m;
     tracers_body(mb.clk + m, q, member_set(mb, m, s), a);
+}
+
+// slab of a ring (sphx_slab_tracers_*): the tracers this slab OWNS at this step, out of the ring's list, into the slab's own
+// times / values / n_owned / head; the columns it does not own keep the host's NaN fill.  g: the slab's grid (ownership by the
+// binned column); a.n_slots: the slab's capacity; n_owned: [capacity] tracers met per record.
+__global__ __launch_bounds__(kTracerBlock) void k_tracers_s(const Clock *clk, int q, FluidSet s, TracerArgs a, Grid g, long long *n_owned)
+{
+    tracers_body<true>(clk, q, s, a, &g, n_owned);
 }
 
 }  // namespace sphx

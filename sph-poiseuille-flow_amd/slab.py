@@ -136,7 +136,12 @@ class HipSlabEngine(_capi._Sampled):
     grads_part_enable / _disable / _reset / grads_part_sums are the gradient statistics (over sphx_slab_gstats_*): the estimates
     of the particles this slab OWNS, their partners taken from everything it holds -- partial sums, which pool_ring_grad_stats
     (ring_grad_stats_sums / ring_grad_stats, all_reduce_ring_grad_stats) adds up; means of partial sums would mislead, so the
-    engine has no grad_stats().  Enabling or disabling drops a graph made by graph_prepare()."""
+    engine has no grad_stats().
+    tracers_part_enable / _disable / tracers_part_records are the particle tracers (over sphx_slab_tracers_*): ownership moves
+    with the particle, so a slab records, of the ring's id list, the tracked particles it OWNS at each sampled step -- dense
+    records, NaN where it was not the owner, n_owned per record -- a PART of the ring's series, which pool_ring_tracers
+    (ring_tracers, all_reduce_ring_tracers) puts together by taking every column from the one rank that wrote it; the engine
+    has no tracers_enable / tracers / tracers_sample.  Enabling or disabling drops a graph made by graph_prepare()."""
     _stem, _where, _series, _pairs, _grads = "sphx_slab_", "slab", "pseries_", "pairs_", "gstats_"
 
     def __init__(self, prm, parts, rank, world, device, lanes_per_particle=0, halo_cols=HALO_COLS, t_end=None,
@@ -173,7 +178,7 @@ class HipSlabEngine(_capi._Sampled):
                                                C.c_double(0.0), C.c_int64(0), C.c_int(rank), C.c_int(world),
                                                C.c_int(halo_cols),
                                                C.c_void_p(hip_stream if native else self.stream.cuda_stream)))
-        self.n_total_global = nt
+        self.n_fluid_global, self.n_total_global = nf, nt
         if native:
             return
         lay = self.layout()
@@ -377,6 +382,47 @@ class HipSlabEngine(_capi._Sampled):
         """This slab's partial sums of one band so far, the dict of capi.Context.grad_stats_sums(band): the twelve
         profile.GRAD_FIELDS as [n_bins] arrays, n_samples, t_first, t_last.  pool_ring_grad_stats adds the ranks' up."""
         return self._grad_stats_band(band)[0]
+
+    # ---- particle tracers (include/sphx.h section 3a): the tracked particles this slab owns, step by step -- a PART ----
+    def tracers_part_enable(self, ids, every=1, capacity=65536, t_from=0.0):
+        """A context's tracers_enable (capi._Stepped; the same argument checks, capi.tracers_config) for the RING's ids, fluid
+        rows of the channel the ring was cut from, the same list on every rank.  Inside run() / group_run() this slab copies
+        x, y, u_x, u_y of every tracked particle it OWNS at the sampled step -- ownership moves with the particle -- into that
+        particle's column of a dense record, and stamps {step, t} and n_owned even when it owns none.  (Re)configures and
+        empties the buffer; drops a graph made by graph_prepare()."""
+        cfg, ids = _capi.tracers_config(self.n_fluid_global, self.n_total_global, ids, every, capacity, t_from)
+        self._call("tracers_enable", C.byref(cfg))
+        self._tracers_part = ids  # the ring's ids [T] (int32) while the tracers are on
+
+    def tracers_part_disable(self):
+        self._call("tracers_disable")
+        self._tracers_part = None
+
+    def tracers_part_records(self, drain=False) -> dict:
+        """This slab's series so far: ids [T] (the ring's, as given), step (int64) and t [n_records], n_owned [n_records] (int64:
+        the tracers this slab owned at that step), x, y, u_x and u_y as [n_records, T] arrays -- the bits snapshot() returns for
+        that id, x in this slab's frame, NaN where this slab was not the owner -- and n_dropped; drain empties the buffer after
+        the copy.  pool_ring_tracers takes every column from the rank that owned it."""
+        ids = _capi._enabled(getattr(self, "_tracers_part", None), "Tracers", "particle tracers are not enabled on this slab")
+        T = len(ids)
+        nt_, n, dropped, got = C.c_int(0), C.c_int(0), C.c_int64(0), np.zeros(T, dtype=np.int32)
+
+        def read(cap, times, values, owned, drain):
+            self._call("tracers_read", C.c_int(cap), _capi.ptr(times), _capi.ptr(values),
+                       None if owned is None else owned.ctypes.data_as(C.POINTER(C.c_int64)), got.ctypes.data_as(C.POINTER(C.c_int32)),
+                       C.byref(nt_), C.byref(n), C.byref(dropped), C.c_int(1 if drain else 0))
+
+        read(0, None, None, None, False)  # the sizes first
+        assert nt_.value == T and np.array_equal(got, ids), (nt_.value, T)
+        m = n.value
+        cap = max(m, 1)
+        times, values, owned = np.zeros((cap, 2)), np.zeros((cap, T, len(_capi.TRACER_FIELDS))), np.zeros(cap, dtype=np.int64)
+        read(cap, times, values, owned, drain)
+        assert n.value == m, (n.value, m)
+        out = _capi.tracers_dict(ids, times[:m], values[:m], int(dropped.value))
+        del out["n_missing"]  # (a slab has none: "not met" is normal, n_owned says what it met)
+        out["n_owned"] = owned[:m].copy()
+        return out
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -746,6 +792,108 @@ def ring_probes(engines, drain=False) -> dict:
     return pool_ring_probes([e.probes_part_records(drain) for e in engines])
 
 
+def _tracer_part_shape(part):
+    """(T, n_records) of one rank's part of a ring's tracers: ids [T], step, t and n_owned [n_records], the four fields
+    [n_records, T], and in every record as many columns with an x as n_owned says"""
+    ids = np.asarray(part["ids"])
+    if ids.ndim != 1 or (len(ids) and not np.issubdtype(ids.dtype, np.integer)):
+        raise ValueError("ids must be a vector of integers")
+    n = len(np.asarray(part["step"]))
+    for k in ("t", "n_owned"):
+        if np.shape(part[k]) != (n,):
+            raise ValueError(f"{k} has shape {np.shape(part[k])}, step has {n} records")
+    for k in _capi.TRACER_FIELDS:
+        if np.shape(part[k]) != (n, len(ids)):
+            raise ValueError(f"field {k} has shape {np.shape(part[k])}, {n} records of {len(ids)} tracers need {(n, len(ids))}")
+    held = np.count_nonzero(~np.isnan(np.asarray(part["x"], dtype=np.float64)), axis=1).reshape(n)
+    owned = np.asarray(part["n_owned"]).astype(np.int64)
+    if np.any(held != owned):
+        r = int(np.flatnonzero(held != owned)[0])
+        raise ValueError(f"record {r} (step {int(np.asarray(part['step'])[r])}) holds {int(held[r])} columns, its n_owned says "
+                         f"{int(owned[r])}")
+    return len(ids), n
+
+
+def _check_one_owner(ranks_of, step, ids):
+    """ranks_of [n_records, T] (int64): bit r set where rank r wrote the column -- exactly one bit everywhere, or ValueError
+    naming the first record, its step, the id and the ranks"""
+    ranks_of = np.asarray(ranks_of, dtype=np.int64)
+    wrong = (ranks_of == 0) | ((ranks_of & (ranks_of - 1)) != 0)
+    if np.any(wrong):
+        r, k = (int(v) for v in np.argwhere(wrong)[0])
+        who = [b for b in range(63) if (int(ranks_of[r, k]) >> b) & 1]
+        raise ValueError(f"slab ownership broken: record {r} (step {int(np.asarray(step)[r])}), id {int(np.asarray(ids)[k])} is "
+                         + (f"owned by ranks {who}: more than one" if who else "owned by no rank (ranks []): lost")
+                         + f"; {int(np.count_nonzero(wrong))} columns of the series have no owner or more than one")
+
+
+def _owner_of(ranks_of):
+    """the rank whose bit is set, [n_records, T] int64"""
+    out = np.zeros(np.shape(ranks_of), dtype=np.int64)
+    v = np.asarray(ranks_of, dtype=np.int64) >> 1
+    while np.any(v):
+        out += v != 0
+        v = v >> 1
+    return out
+
+
+def _fold_tracers(out, fold_DL):
+    if fold_DL is not None:
+        out["x"] = out["x"] - np.floor(out["x"] / fold_DL) * fold_DL
+    return out
+
+
+def pool_ring_tracers(parts, fold_DL=None) -> dict:
+    """The ring's tracers (the dict of capi.Context.tracers: ids, step, t, x, y, u_x, u_y as [n_records, T] arrays, n_dropped,
+    n_missing) from the ranks' parts (HipSlabEngine.tracers_part_records, in rank order): every fluid row has exactly one owner
+    at every step, which recorded it, so every column of every record is taken from the one rank where its x is not NaN --
+    nothing is added, the bytes survive.  owner [n_records, T] (int64) is the rank each value came from: the migration.
+    x stays in its owner's frame (below 0 on the first slab, at or above DL on the last) unless fold_DL is given: then it is
+    x - floor(x / DL) DL; profile.unwrap_tracers takes either.  n_missing is 0 by construction.  ValueError when a column
+    of a record has no owner or more than one (naming record, step, id and the ranks), when a part's columns of a record are
+    not as many as its n_owned, or when ids, step, t or n_dropped differ between the ranks."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("the tracers of a ring need the part of at least one slab")
+    if len(parts) > 62:
+        raise ValueError("at most 62 ranks")
+    shapes = []
+    for r, p in enumerate(parts):
+        try:
+            shapes.append(_tracer_part_shape(p))
+        except ValueError as e:
+            raise ValueError(f"rank {r}: {e}") from None
+    T, n = shapes[0]
+    first = parts[0]
+    for r, (p, sh) in enumerate(zip(parts, shapes)):
+        if sh[0] != T or not np.array_equal(np.asarray(p["ids"]), np.asarray(first["ids"])):
+            raise ValueError(f"rank {r} tracks other ids than rank 0: the slabs of one ring share the list")
+        if sh[1] != n or not np.array_equal(p["step"], first["step"]) or not np.array_equal(p["t"], first["t"]):
+            raise ValueError(f"rank {r} recorded steps {np.asarray(p['step'])!r}, rank 0 {np.asarray(first['step'])!r} (or other "
+                             "times): the slabs of one ring record the same steps")
+        if int(p["n_dropped"]) != int(first["n_dropped"]):
+            raise ValueError(f"rank {r} dropped {p['n_dropped']} records, rank 0 {first['n_dropped']}")
+    masks = [~np.isnan(np.asarray(p["x"], dtype=np.float64)).reshape(n, T) for p in parts]
+    ranks_of = np.zeros((n, T), dtype=np.int64)
+    for r, m in enumerate(masks):
+        ranks_of += m.astype(np.int64) << r
+    _check_one_owner(ranks_of, first["step"], first["ids"])
+    out = dict(ids=np.array(first["ids"], dtype=np.int32), step=np.asarray(first["step"]).astype(np.int64),
+               t=np.array(first["t"], dtype=np.float64))
+    for k in _capi.TRACER_FIELDS:
+        a = np.empty((n, T))
+        for p, m in zip(parts, masks):
+            a[m] = np.asarray(p[k], dtype=np.float64).reshape(n, T)[m]
+        out[k] = a
+    out.update(n_dropped=int(first["n_dropped"]), n_missing=0, owner=_owner_of(ranks_of))
+    return _fold_tracers(out, fold_DL)
+
+
+def ring_tracers(engines, drain=False, fold_DL=None) -> dict:
+    """The tracers of an in-process ring (pool_ring_tracers of every slab's records): what driver.tracer_figures takes."""
+    return pool_ring_tracers([e.tracers_part_records(drain) for e in engines], fold_DL)
+
+
 def _all_gathered(dist, row, group):
     """[world x len(row)] float64: every rank's row (control plane: CPU tensors, gloo)."""
     import torch
@@ -953,6 +1101,57 @@ def all_reduce_ring_grad_stats(sums, dist, group=None) -> dict:
     out = {f: total[j] for j, f in enumerate(GRAD_FIELDS)}
     out.update({k: sums[k] for k in _HEAD})
     return out
+
+
+def all_reduce_ring_tracers(part, dist, group=None, fold_DL=None) -> dict:
+    """One rank per process: the ring's tracers from this rank's part, as pool_ring_tracers; every rank gets them.  The sizes,
+    n_dropped and whether a rank's own part is well formed (its columns per record as many as its n_owned) are all-gathered
+    and checked first, then ids, step and t.  The values travel as BIT PATTERNS: every rank views its four fields as int64,
+    puts zeros where it was not the owner, and the arrays are all-reduced with SUM, together with a word per column in which
+    rank r sets bit r where it was the owner -- that word must have exactly one bit everywhere, and then every column had one
+    contributor and i + 0 is i, so the result is the owner's bytes, -0.0 included (a float sum would make +0.0 of it).
+    Collective; raises on every rank when a part is malformed, a column of a record has no owner or more than one, or ids,
+    step, t or n_dropped differ between the ranks."""
+    import torch
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    try:
+        if world > 62:
+            raise ValueError("at most 62 ranks")
+        T, n = _tracer_part_shape(part)
+        dropped, why = float(int(part["n_dropped"])), None
+    except (ValueError, KeyError, TypeError) as e:
+        T, n, dropped, why = -1, -1, -1.0, str(e)
+    rows = _all_gathered(dist, [float(T), float(n), dropped, 0.0 if why is None else 1.0], group)
+    for r, row in enumerate(rows):
+        if row[3] != 0.0:
+            raise ValueError(f"rank {r}'s part is malformed" + (f": {why}" if r == rank and why else ""))
+    for r, row in enumerate(rows):
+        if tuple(row[:3]) != tuple(rows[0][:3]):
+            raise ValueError(f"rank {r} holds {int(row[0])} tracers, {int(row[1])} records, {int(row[2])} dropped; rank 0 "
+                             f"{int(rows[0][0])}, {int(rows[0][1])}, {int(rows[0][2])}: the slabs of one ring share the list and "
+                             "record the same steps")
+    ids = np.asarray(part["ids"])
+    step, t = np.asarray(part["step"], dtype=np.float64), np.asarray(part["t"], dtype=np.float64)
+    mine = np.concatenate([ids.astype(np.float64), step, t])
+    for r, row in enumerate(_all_gathered(dist, mine, group)):
+        if not np.array_equal(row, mine):  # (every rank compares with its own: one odd rank out makes all of them raise)
+            raise ValueError(f"rank {r} holds other ids, steps or times than this rank")
+    F = len(_capi.TRACER_FIELDS)
+    mask = ~np.isnan(np.asarray(part["x"], dtype=np.float64)).reshape(n, T)
+    words = np.zeros((F + 1, n, T), dtype=np.int64)
+    for j, k in enumerate(_capi.TRACER_FIELDS):
+        bits = np.ascontiguousarray(np.asarray(part[k], dtype=np.float64).reshape(n, T)).view(np.int64)
+        words[j] = np.where(mask, bits, 0)
+    words[F] = mask.astype(np.int64) << rank
+    total = torch.from_numpy(words)
+    dist.all_reduce(total, op=dist.ReduceOp.SUM, group=group)
+    total = total.numpy()
+    _check_one_owner(total[F], step, ids)
+    out = dict(ids=np.array(ids, dtype=np.int32), step=np.asarray(part["step"]).astype(np.int64), t=t.copy())
+    for j, k in enumerate(_capi.TRACER_FIELDS):
+        out[k] = np.ascontiguousarray(total[j]).view(np.float64)
+    out.update(n_dropped=int(part["n_dropped"]), n_missing=0, owner=_owner_of(total[F]))
+    return _fold_tracers(out, fold_DL)
 
 
 class SlabDriver:

@@ -1,0 +1,116 @@
+"""Worker for test_slab_tracers_host.py (CPU, gloo, WORLD_SIZE ranks): every rank holds a dense part of a synthetic ring series
+of tracers -- NaN where it was not the owner, columns changing owner between records, a rank that owns nothing for a while, a
+value of -0.0 -- and slab.all_reduce_ring_tracers must leave the whole series on every rank, byte for byte what
+slab.pool_ring_tracers makes of the parts, and must raise on EVERY rank when one rank's part is bad.  Prints OK on every rank
+that saw all of it."""
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FIELDS = ("x", "y", "u_x", "u_y")
+DL = 3.0
+
+
+def series(world, T=13, n=7):
+    """(parts, whole): n records of T tracers dealt out to `world` ranks record by record, the same on every rank.  whole has
+    `owner` [n, T]; x is in the owner's frame (some below 0, some at or above DL); u_y[2, 5] is -0.0; with three ranks or more
+    rank 1 owns nothing in records 0 .. 2."""
+    rng = np.random.default_rng(47)
+    whole = dict(ids=rng.permutation(40)[:T].astype(np.int32), step=np.arange(3, 3 + 2 * n, 2).astype(np.int64),
+                 t=np.cumsum(rng.uniform(1e-3, 2e-3, n)), n_dropped=2, n_missing=0)
+    for k in FIELDS:
+        whole[k] = rng.normal(0.5, 0.7, (n, T))
+    whole["x"] = rng.uniform(-0.4, DL + 0.4, (n, T))
+    whole["x"][1, 0], whole["x"][4, 3] = -0.125, DL          # both ends of the frames
+    whole["u_y"][2, 5] = -0.0
+    whole["y"][3, 1] = 0.0
+    owner = rng.integers(0, world, (n, T))
+    if world > 1:
+        owner[:, 2] = np.arange(n) % world                    # a column that changes hands at every record
+    if world >= 3:
+        owner[:3][owner[:3] == 1] = 0                         # rank 1 owns nothing for a while
+    whole["owner"] = owner.astype(np.int64)
+    parts = []
+    for r in range(world):
+        mine = owner == r
+        p = {k: np.where(mine, whole[k], np.nan) for k in FIELDS}
+        for k in FIELDS:                                      # (np.where keeps the sign of a zero; make sure of it)
+            assert p[k][mine].tobytes() == whole[k][mine].tobytes()
+        p.update(ids=whole["ids"].copy(), step=whole["step"].copy(), t=whole["t"].copy(), n_dropped=2,
+                 n_owned=np.count_nonzero(mine, axis=1).astype(np.int64))
+        parts.append(p)
+    return parts, whole
+
+
+def same(a, b, fold=None):
+    """two pooled dicts byte for byte (b's x folded first where asked)"""
+    ok = (np.array_equal(a["ids"], b["ids"]) and np.array_equal(a["step"], b["step"]) and a["t"].tobytes() == b["t"].tobytes()
+          and a["n_dropped"] == b["n_dropped"] and a["n_missing"] == b["n_missing"] == 0 and np.array_equal(a["owner"], b["owner"]))
+    for k in FIELDS:
+        want = b[k]
+        if k == "x" and fold is not None:
+            want = want - np.floor(want / fold) * fold
+        ok = ok and a[k].shape == want.shape and a[k].tobytes() == np.ascontiguousarray(want).tobytes()
+    return bool(ok)
+
+
+def bad_parts(mine, other):
+    """name -> a bad version of the part `mine`; `other` is another rank's part (a column of it is claimed as well)"""
+    n, T = mine["x"].shape
+    out = dict(step=dict(mine, step=mine["step"] + 1), t=dict(mine, t=mine["t"] * 2.0), dropped=dict(mine, n_dropped=3),
+               ids=dict(mine, ids=mine["ids"][::-1].copy()),
+               shorter=dict(mine, step=mine["step"][:-1], t=mine["t"][:-1], n_owned=mine["n_owned"][:-1], **{k: mine[k][:-1] for k in FIELDS}),
+               n_owned=dict(mine, n_owned=mine["n_owned"] + (np.arange(n) == 1)))
+    r, k = (int(v) for v in np.argwhere(~np.isnan(mine["x"]))[0])
+    lost = dict(mine, **{f: mine[f].copy() for f in FIELDS}, n_owned=mine["n_owned"].copy())
+    for f in FIELDS:
+        lost[f][r, k] = np.nan
+    lost["n_owned"][r] -= 1
+    out["lost"] = lost                                         # a column nobody owns, consistently counted
+    r, k = (int(v) for v in np.argwhere(~np.isnan(other["x"]) & np.isnan(mine["x"]))[0])
+    twice = dict(mine, **{f: mine[f].copy() for f in FIELDS}, n_owned=mine["n_owned"].copy())
+    for f in FIELDS:
+        twice[f][r, k] = other[f][r, k]
+    twice["n_owned"][r] += 1
+    out["twice"] = twice                                       # a column two ranks own
+    return out
+
+
+def main():
+    import torch.distributed as dist
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    dist.init_process_group("gloo")
+    slab = importlib.import_module("sph-poiseuille-flow_amd.slab")
+    parts, whole = series(world)
+    ok = True
+
+    got = slab.all_reduce_ring_tracers(parts[rank], dist)
+    ok &= same(got, slab.pool_ring_tracers(parts)) and same(got, whole)
+    ok &= bool(np.signbit(got["u_y"][2, 5])) and got["step"].dtype == np.int64 and got["owner"].dtype == np.int64
+    ok &= same(slab.all_reduce_ring_tracers(parts[rank], dist, fold_DL=DL), whole, fold=DL)
+    if world >= 3:
+        ok &= int(parts[1]["n_owned"][:3].sum()) == 0
+
+    last = world - 1
+    bads = bad_parts(parts[last], parts[0])
+    for name, bad in bads.items():  # the last rank's part is bad: EVERY rank must hear about it
+        try:
+            slab.all_reduce_ring_tracers(bad if rank == last else parts[rank], dist)
+            ok = False
+            print(f"rank {rank}: {name} went through", flush=True)
+        except ValueError:
+            pass
+
+    print(f"rank {rank}: {'OK' if ok else 'WRONG'}", flush=True)
+    dist.barrier()
+    dist.destroy_process_group()
+    sys.exit(0 if ok else 1)
+
+
+if __name__ == "__main__":
+    main()
