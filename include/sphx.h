@@ -1031,6 +1031,103 @@ int sphx_batch_tracers_read(sphx_batch *batch, int capacity, double *times, doub
                             int *n_records, int64_t *n_dropped, int64_t *n_missing, int drain);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2r. Density statistics: the density the next step starts from, re-summed at every fluid particle and binned on the
+ *     device, inside the step loop: the relative deviation delta = rho / rho0 - 1 the weakly compressible method keeps
+ *     small, its profile across the channel and next to the walls, the pressure p0 delta (flat in y in plane Poiseuille
+ *     flow) and the packing sum m / rho.  Section 2n's div v is the rate of compression; this is its state.  The solver's own
+ *     rho is an output field in the layout of the step that wrote it; this is computed from what sphx_ctx_download returns.
+ *
+ *  One sample: for every fluid particle i with 0 <= y_i <= DH (outside: dropped, as in section 2a), over every other fluid
+ *    particle j with 1e-24 < r2 < (2h)^2 (nearest image in x) and every wall particle in the same range -- the walls are
+ *    always in, this is the solver's density:
+ *        s_in  = W(0) + sum over the fluid partners of W(r_ij)          W the cubic spline
+ *        s_ct  = sum over the wall partners of W(r_ij) V_j              V_j the wall particle's volume
+ *        rho_i = s_in rho0 inv_sigma0 + s_ct rho0^2 inv_sigma0 / mass_i   (rho0 where that is <= 1e-12: the step's floor)
+ *        delta_i = rho_i / rho0 - 1      wall_i = s_ct rho0 inv_sigma0 / mass_i      dvol_i = rho0 / rho_i - 1
+ *    rho_i is the density the next step's first pass computes for the same state.
+ *  Outliers: a particle with |delta_i| > delta_bound, or a delta_i that is not finite, is counted in `outliers` and summed
+ *    nowhere, in no histogram.  This is not an error.
+ *  Bins and bands: those of section 2a.  Per bin and band count + outliers equals the flow statistics' count.
+ *  Sums, per bin and band, over all samples, SPHX_DENS_STATS_FIELDS = 8 doubles in this order: count, sum delta, sum delta^2,
+ *    sum dvol, sum wall, outliers, d_min, d_max -- the last two the running extremes of delta over every particle summed so
+ *    far, +inf / -inf before the first.  count and outliers are integers held in doubles.
+ *  Histogram, per band, over all samples: n_hist uniform bins on [-hist_range, hist_range), the particle in bin
+ *    floor((delta + hist_range) * n_hist / (2 hist_range)); `below` and `above` count the particles outside the range.  Per
+ *    band sum(hist) + below + above equals sum(count).  A delta within rounding of an edge may fall either side.
+ *  Per sampler: n_samples, t_first, t_last.
+ *  Exactness: a sample is summed in int64 fixed point at power-of-two scales picked from the particle count (n <= 2^L) and
+ *    delta_bound (2^e >= delta_bound): delta in units of 2^-(62-L-e), delta^2 of 2^-(62-L-2e), dvol of 2^-(61-L-e), wall of
+ *    2^-(61-L); the extremes go through order-preserving integer keys.  The sums are bit-identical between runs and
+ *    independent of the workgroups' dispatch order, and a batch member's are a standalone context's.  They depend on the order
+ *    of the particle slots within the floating-point rounding of s_in and s_ct only.
+ *  Limits: 1 <= n_hist <= 1024, 0 < delta_bound <= 0.5, 0 < hist_range <= delta_bound, and
+ *    (n_bands + 1) * (8 * n_bins + n_hist + 2) <= 7680, the 60 KB of LDS of a workgroup.
+ *  Gating: as in section 2l.  sphx_ctx_dens_stats_sample adds a sample of the state now, without gating.
+ *  Off by default.  With it off a step slot enqueues exactly the launches it does without this feature; on, every step slot
+ *    ends with one more launch (k_dens_stats, the last of the slot; it skips itself on the steps gated out) that is captured
+ *    in the replayed graphs; enable / disable re-capture them.  Independent of the other eight samplers.
+ *  Errors: SPHX:DensStats:config (NULL config, a value outside the limits above, n_bins < 0, every < 1, a NaN t_from, n_bands
+ *    outside 0..2, a band centre or half-width that is not finite or a negative half-width, or the allocation fails: the
+ *    context then goes on without density statistics), SPHX:DensStats:band, SPHX:DensStats:capacity (sums given and capacity <
+ *    n_bins, or hist given and hist_capacity < n_hist), SPHX:DensStats:disabled (SPHX_ERR_STATE: a call that needs the sampler
+ *    while it is off); every call on a slab context fails with SPHX_ERR_ARG, SPHX:DensStats:slab.  A refused enable leaves a
+ *    running sampler, and its sums, untouched.
+ * ---------------------------------------------------------------------------------------------- */
+
+#define SPHX_DENS_STATS_FIELDS 8
+#define SPHX_DENS_STATS_MAX_HIST 1024
+
+typedef struct sphx_dens_stats_config {
+    int32_t n_bins;            /* y-bins over [0, DH]; 0 = the reference's profile bins                  */
+    int32_t every;             /* sample every `every`-th completed step (step count % every == 0), >= 1 */
+    double t_from;             /* only steps ending at t >= t_from                                       */
+    int32_t n_hist;            /* histogram bins on [-hist_range, hist_range), 1..1024 (64 is a good default) */
+    int32_t n_bands;           /* 0..2 x-bands besides the whole channel                                 */
+    double hist_range;         /* 0 < hist_range <= delta_bound (0.05 is a good default)                 */
+    double delta_bound;        /* a particle with |delta| > delta_bound is an outlier; 0 < delta_bound <= 0.5 */
+    double band_x[2], band_hw[2];
+} sphx_dens_stats_config;
+
+/* (Re)configure and zero the sums; waits for the stream.  Off by default. */
+int sphx_ctx_dens_stats_enable(sphx_ctx *ctx, const sphx_dens_stats_config *cfg);
+/* Stop sampling (no-op when off); the sums are dropped. */
+int sphx_ctx_dens_stats_disable(sphx_ctx *ctx);
+/* Zero the sums, the extremes, the histogram and the sample count; the configuration stays. */
+int sphx_ctx_dens_stats_reset(sphx_ctx *ctx);
+/* Add one sample of the current state (what sphx_ctx_download would return) now, without gating. */
+int sphx_ctx_dens_stats_sample(sphx_ctx *ctx);
+/* One band so far: sums is [SPHX_DENS_STATS_FIELDS][capacity] (field f of bin k at f * capacity + k; capacity >= n_bins where
+ * it is given), hist is [hist_capacity] (hist_capacity >= n_hist where it is given), below and above one number each; every
+ * pointer may be NULL.  Waits for and settles everything enqueued, like sphx_ctx_download.  t_first / t_last are NaN before
+ * a sample. */
+int sphx_ctx_dens_stats_read(sphx_ctx *ctx, int band, int capacity, int hist_capacity, int *n_bins, int *n_hist, double *sums,
+                             int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first, double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2s. Density statistics of a batch (section 2b): the sums of section 2r for every member at once.
+ *
+ *  One config for all members (bins, bands, histogram and the walls come from the shared geometry).  Every member has its
+ *  own sums, extremes and histogram and its own head and is sampled on its own clock, with its own rho0, with the gating of
+ *  section 2r, so a member that sits out slots is not sampled in them.  A member's sums are, bit for bit, those of a
+ *  standalone context with the same parameters and config that took the same steps in the same slot order; a realignment
+ *  reorders a member's slots, after which its sums agree within floating-point rounding.  With the sampler on, every step
+ *  slot of the batch ends with one launch for all members (k_dens_stats_b, behind the batch's other samplers); off, a slot
+ *  enqueues exactly the launches it does without this feature.  A refused enable leaves a running sampler untouched.
+ *  Errors: SPHX:Batch:null (NULL batch), SPHX:Batch:member (the read's member outside 0 .. n_members - 1) and those of
+ *  section 2r.
+ * ---------------------------------------------------------------------------------------------- */
+
+int sphx_batch_dens_stats_enable(sphx_batch *batch, const sphx_dens_stats_config *cfg);
+int sphx_batch_dens_stats_disable(sphx_batch *batch);
+int sphx_batch_dens_stats_reset(sphx_batch *batch);
+/* settles; adds a sample of what sphx_batch_download returns, every member, without gating */
+int sphx_batch_dens_stats_sample(sphx_batch *batch);
+/* Section 2r's read of one member.  Settles first, as sphx_batch_download does. */
+int sphx_batch_dens_stats_read(sphx_batch *batch, int member, int band, int capacity, int hist_capacity, int *n_bins, int *n_hist,
+                               double *sums, int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first,
+                               double *t_last);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU). The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

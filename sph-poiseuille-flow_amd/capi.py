@@ -8,8 +8,9 @@ import os
 
 import numpy as np
 
-from .profile import (FIELD_MAP_PLANES, GRAD_FIELDS, GRAD_MAX_BINS, STATS_FIELDS, field_map_means, flow_stats_profile,
-                      grad_stats_profiles, pair_dist_profiles, pair_edges, profile_series_profiles)
+from .profile import (DENS_FIELDS, DENS_MAX_HIST, DENS_MAX_WORDS, FIELD_MAP_PLANES, GRAD_FIELDS, GRAD_MAX_BINS,
+                      STATS_FIELDS, dens_stats_profiles, field_map_means, flow_stats_profile, grad_stats_profiles,
+                      pair_dist_profiles, pair_edges, profile_series_profiles)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPHX_LIB") or os.path.join(HERE, "csrc", "libsphx.so")  # SPHX_LIB: experiment builds
@@ -92,6 +93,11 @@ class SphxTracersConfig(C.Structure):
 TRACER_FIELDS = ("x", "y", "u_x", "u_y")
 
 
+class SphxDensStatsConfig(C.Structure):
+    _fields_ = [("n_bins", C.c_int32), ("every", C.c_int32), ("t_from", C.c_double), ("n_hist", C.c_int32), ("n_bands", C.c_int32),
+                ("hist_range", C.c_double), ("delta_bound", C.c_double), ("band_x", C.c_double * 2), ("band_hw", C.c_double * 2)]
+
+
 class SphxStatus(C.Structure):
     _fields_ = [("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("vmax", C.c_double),
                 ("step", C.c_int64), ("done", C.c_int32), ("device_status", C.c_int32)]
@@ -123,6 +129,8 @@ EXPORTS = [
     "sphx_ctx_grad_stats_enable", "sphx_ctx_grad_stats_disable", "sphx_ctx_grad_stats_reset", "sphx_ctx_grad_stats_sample",
     "sphx_ctx_grad_stats_read",
     "sphx_ctx_tracers_enable", "sphx_ctx_tracers_disable", "sphx_ctx_tracers_sample", "sphx_ctx_tracers_read",
+    "sphx_ctx_dens_stats_enable", "sphx_ctx_dens_stats_disable", "sphx_ctx_dens_stats_reset", "sphx_ctx_dens_stats_sample",
+    "sphx_ctx_dens_stats_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -148,6 +156,8 @@ EXPORTS = [
     "sphx_batch_pair_dist_read",
     "sphx_batch_grad_stats_enable", "sphx_batch_grad_stats_disable", "sphx_batch_grad_stats_reset", "sphx_batch_grad_stats_sample",
     "sphx_batch_grad_stats_read",
+    "sphx_batch_dens_stats_enable", "sphx_batch_dens_stats_disable", "sphx_batch_dens_stats_reset", "sphx_batch_dens_stats_sample",
+    "sphx_batch_dens_stats_read",
     "sphx_batch_tracers_enable", "sphx_batch_tracers_disable", "sphx_batch_tracers_sample", "sphx_batch_tracers_read",
 ]
 
@@ -756,6 +766,70 @@ class _Stepped(_Sampled):
         per = [dict(s, **grad_stats_profiles(DH, s)) for s in (sums if self._many else [sums])]
         return self._each(per)
 
+    # ---- density statistics (include/sphx.h sections 2r, 2s): the summation density at the fluid particles, binned ----
+    def dens_stats_enable(self, n_bins=0, every=1, t_from=0.0, n_hist=64, hist_range=0.05, delta_bound=0.5, bands=()):
+        """Re-sum, every `every`-th completed step ending at t >= t_from, the density the next step starts from at every fluid
+        particle (profile.summation_density, the walls always in) and add delta = rho / rho0 - 1, its square, the volume defect
+        rho0 / rho - 1 and the walls' share of rho / rho0 to n_bins y-bins (0: the reference's max(20, round(DH/dp))) of the
+        whole channel (band 0) and of up to two x-bands [(x_centre, half_width), ...], with the extremes of delta per bin and
+        per band a histogram of delta in n_hist bins on [-hist_range, hist_range).  A particle with |delta| > delta_bound is
+        counted in `outliers`.  (Re)configures and zeroes the sums.  A batch: one config for all members, each sampled on its
+        own clock."""
+        p0 = self._params0()
+        cfg = dens_stats_config(p0, n_bins, every, t_from, n_hist, hist_range, delta_bound, bands)
+        self._call("dens_stats_enable", C.byref(cfg))
+        # (n_bins, n_bands incl. band 0, n_hist, hist_range) while the density statistics are on
+        self._dens_stats = (int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5))), int(cfg.n_bands) + 1, int(cfg.n_hist),
+                            float(cfg.hist_range))
+
+    def dens_stats_disable(self):
+        self._call("dens_stats_disable")
+        self._dens_stats = None
+
+    def _dens_on(self):
+        return _enabled(getattr(self, "_dens_stats", None), "DensStats", f"density statistics are not enabled on this {self._where}")
+
+    def dens_stats_reset(self):
+        self._dens_on()
+        self._call("dens_stats_reset")
+
+    def dens_stats_sample(self):
+        """Add one sample of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
+        self._dens_on()
+        self._call("dens_stats_sample")
+
+    def dens_stats_sums(self, band=0):
+        """The raw sums of one band: the eight profile.DENS_FIELDS as [n_bins] arrays (count and outliers hold integers; d_min /
+        d_max are +inf / -inf in a bin without a particle), hist [n_hist] (int64), below, above, hist_range, n_samples, t_first,
+        t_last; a batch: one such dict per member."""
+        n_bins, n_bands, n_hist, hist_range = self._dens_on()
+        if not _is_int(band) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:DensStats:band", f"band must be an integer in 0..{n_bands - 1}")
+        out = []
+        for k in range(self._channels()):
+            sums, hist = np.zeros((len(DENS_FIELDS), n_bins)), np.zeros(n_hist, dtype=np.int64)
+            below, above, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+            t0, t1, nb, nh = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0)
+            member = (C.c_int(k),) if self._many else ()
+            self._call("dens_stats_read", *member, C.c_int(int(band)), C.c_int(n_bins), C.c_int(n_hist), C.byref(nb), C.byref(nh), ptr(sums),
+                       hist.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(below), C.byref(above), C.byref(ns), C.byref(t0), C.byref(t1))
+            assert (nb.value, nh.value) == (n_bins, n_hist), (nb.value, nh.value, n_bins, n_hist)
+            d = {f: sums[j].copy() for j, f in enumerate(DENS_FIELDS)}
+            d.update(hist=hist, below=int(below.value), above=int(above.value), hist_range=hist_range, n_samples=int(ns.value),
+                     t_first=float(t0.value), t_last=float(t1.value))
+            out.append(d)
+        return self._each(out)
+
+    def dens_stats(self, band=0):
+        """One band's profiles (profile.dens_stats_profiles): y_mid, count, outliers, d_mean, d_std, d_min, d_max, p_mean, p_std,
+        wall_mean, packing, NaN where a bin is empty, hist_centres and hist_density, plus the raw sums, n_samples, t_first,
+        t_last.  A batch: one such dict per member, each with its own p0."""
+        DH = self._params0().DH
+        sums = self.dens_stats_sums(band)
+        prms = self.params if self._many else [self.params]
+        per = [dict(s, **dens_stats_profiles(DH, p.p0, s)) for p, s in zip(prms, sums if self._many else [sums])]
+        return self._each(per)
+
 
 class Batch(_Stepped):
     """M channels of one geometry stepped by the same launches (sphx_batch, include/sphx.h section 2b).
@@ -800,6 +874,7 @@ class Batch(_Stepped):
         self._pair_dist = None   # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
         self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
         self._tracers = None     # the ids [T] (int32) while the tracers are on
+        self._dens_stats = None  # (n_bins, n_bands incl. band 0, n_hist, hist_range) while the density statistics are on
         arr = (SphxParams * m)(*self.params)
         check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
@@ -852,6 +927,7 @@ class Context(_Stepped):
         self._pair_dist = None   # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
         self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
         self._tracers = None     # the ids [T] (int32) while the tracers are on
+        self._dens_stats = None  # (n_bins, n_bands incl. band 0, n_hist, hist_range) while the density statistics are on
         check(lib().sphx_ctx_create(C.byref(self._h), C.byref(self.params), C.c_int(n_fluid), C.c_int(n_total),
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
@@ -1176,6 +1252,33 @@ def grad_stats_config(prm, n_bins=0, every=1, t_from=0.0, det_min=0.05, with_wal
         raise bad("n_bins * (number of bands + 1) must not exceed 640")
     cfg = SphxGradStatsConfig(n_bins=int(f.n_bins), every=int(f.every), t_from=float(f.t_from), det_min=det_min,
                               with_walls=1 if with_walls else 0, n_bands=int(f.n_bands))
+    for k in range(2):
+        cfg.band_x[k], cfg.band_hw[k] = f.band_x[k], f.band_hw[k]
+    return cfg
+
+
+def dens_stats_config(prm, n_bins=0, every=1, t_from=0.0, n_hist=64, hist_range=0.05, delta_bound=0.5, bands=()) -> SphxDensStatsConfig:
+    """Checked sphx_dens_stats_config for channels with parameters prm; raises SphxError(SPHX:DensStats:config) before anything
+    reaches the device.  n_bins, every, t_from and the bands by the checks of flow_stats_config."""
+    bad = _config_error("DensStats")
+    try:
+        f = flow_stats_config(n_bins, every, t_from, bands)
+        hist_range, delta_bound = float(hist_range), float(delta_bound)
+    except SphxError as e:
+        raise bad(e.message) from None
+    except (TypeError, ValueError):
+        raise bad("hist_range and delta_bound must be numbers") from None
+    if not _is_int(n_hist) or not 1 <= n_hist <= DENS_MAX_HIST:
+        raise bad("n_hist must be an integer in 1..1024")
+    if not 0.0 < delta_bound <= 0.5:  # (a NaN fails)
+        raise bad("delta_bound must be in (0, 0.5]")
+    if not 0.0 < hist_range <= delta_bound:
+        raise bad("hist_range must be in (0, delta_bound]")
+    bins = int(f.n_bins) or max(20, int(np.floor(prm.DH / prm.dp + 0.5)))
+    if (int(f.n_bands) + 1) * (8 * bins + int(n_hist) + 2) > DENS_MAX_WORDS:
+        raise bad("(number of bands + 1) * (8 * n_bins + n_hist + 2) must not exceed 7680")
+    cfg = SphxDensStatsConfig(n_bins=int(f.n_bins), every=int(f.every), t_from=float(f.t_from), n_hist=int(n_hist), n_bands=int(f.n_bands),
+                              hist_range=hist_range, delta_bound=delta_bound)
     for k in range(2):
         cfg.band_x[k], cfg.band_hw[k] = f.band_x[k], f.band_hw[k]
     return cfg

@@ -904,3 +904,70 @@ SPHX_EXPORT int sphx_batch_grad_stats_read(sphx_batch *b, int band, int capacity
     return SPHX_OK;
     SPHX_CATCH
 }
+
+// ---- density statistics of every member (include/sphx.h section 2s) ----
+
+namespace {
+
+// the batch's density statistics (member 0's, see sphx_ctx::dens)
+DensStats &batch_dens(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    DensStats &f = b->mem[0]->dens;
+    sampler_check(kDensNames, false, f.on, need_on, "batch");
+    return f;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_batch_dens_stats_enable(sphx_batch *b, const sphx_dens_stats_config *cfg)
+{
+    SPHX_TRY
+    // (bins, bands and the walls come from the shared geometry; out of device memory: the batch goes on without density statistics)
+    DensStats &f = batch_dens(b, false);
+    dens_stats_enable(f, b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_dens_stats_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    DensStats &f = batch_dens(b, false);
+    if (f.on) sampler_off(f, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_dens_stats_reset(sphx_batch *b)
+{
+    SPHX_TRY
+    DensStats &f = batch_dens(b, true);
+    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_dens_stats_sample(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_dens(b, true);
+    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
+    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_dens_stats);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_dens_stats_read(sphx_batch *b, int member, int band, int capacity, int hist_capacity, int *n_bins, int *n_hist,
+                                           double *sums, int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first,
+                                           double *t_last)
+{
+    SPHX_TRY
+    const DensStats &f = batch_dens(b, true);
+    batch_check_member(b, member);
+    dens_stats_read(f, b->stream, [b] { batch_settle(b); }, member, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above,
+                    n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}

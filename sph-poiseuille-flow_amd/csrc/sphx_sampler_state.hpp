@@ -10,6 +10,7 @@
 #include "sphx_pair_dist.hpp"
 #include "sphx_grad_stats.hpp"
 #include "sphx_tracers.hpp"
+#include "sphx_dens_stats.hpp"
 
 struct sphx_ctx;
 
@@ -198,8 +199,35 @@ struct Tracers {
               bool drain, int64_t *n_owned = nullptr);
 };
 
+// Density statistics (sphx_ctx_dens_stats_*, sphx_batch_dens_stats_*; sphx_dens_stats.hpp) of a context or of the M members of
+// a batch: one configuration, bins and bands as FlowStats has them, member m's int64 sums of the sample in flight and its
+// running sums at m * block() -- [n_bands][n_bins][kDensFields], then [n_bands][n_hist + 2] -- its running keys of d_max and
+// -d_min at m * kblock() -- [n_bands][n_bins][kDensKeys], 0: no particle yet -- and its head at m.
+struct DensStats {
+    bool on = false;
+    int members = 1;
+    sphx_dens_stats_config cfg{};
+    int n_bins = 0, n_bands = 1;  // (n_bands counts band 0)
+    int e = -1;                   // 2^e >= cfg.delta_bound
+    DevBuf<unsigned long long> isum, keys;
+    DevBuf<double> dsum;
+    DevBuf<DensStatsHead> head;
+
+    size_t row() const { return (size_t)n_bins * kDensFields; }              // the binned sums of one band
+    size_t hrow() const { return (size_t)cfg.n_hist + 2; }                   // the histogram of one band, below and above
+    size_t block() const { return dens_sum_words(n_bands, n_bins, cfg.n_hist); }  // the sums of one member ...
+    size_t kblock() const { return dens_key_words(n_bands, n_bins); }        // ... and its keys
+    size_t shmem() const { return (block() + kblock()) * sizeof(unsigned long long); }  // the LDS of a workgroup
+    void check(const sphx_params &prm, const sphx_dens_stats_config *cfg);
+    void alloc(const DensStats &checked, int M);
+    void zero(hipStream_t st) { isum.zero(st); keys.zero(st); dsum.zero(st); head.zero(st); }
+    void release() { isum.release(); keys.release(); dsum.release(); head.release(); }
+    void read(hipStream_t st, int m, int band, int stride, double *sums, int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples,
+              double *t_first, double *t_last) const;
+};
+
 // the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes, profile series,
-// pair statistics, gradient statistics, tracers (sphx_samplers.hpp)
+// pair statistics, gradient statistics, tracers, density statistics (sphx_samplers.hpp)
 void launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild);
 
 }  // namespace sphx

@@ -37,6 +37,8 @@ constexpr SamplerNames kGradNames{"GradStats", "the gradient statistics of a sla
                                   "gradient statistics are not enabled on this ", "the sums could not be set up: "};
 constexpr SamplerNames kTracerNames{"Tracers", "the tracers of a slab are sphx_slab_tracers_* (include/sphx.h section 3a)",
                                     "particle tracers are not enabled on this ", "the record buffer could not be set up: "};
+constexpr SamplerNames kDensNames{"DensStats", "density statistics are not available on slab contexts",
+                                  "density statistics are not enabled on this ", "the sums could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
 
@@ -348,6 +350,38 @@ void launch_tracers(sphx_ctx *c, int q, const FluidSet &s, int every)
     launch_forms(c, "k_tracers", Forms{k_tracers, k_tracers_b}, tracer_blocks((size_t)c->nf), kTracerBlock, 0, q, s, tracer_args(c, every));
 }
 
+// the arguments of a density-statistics launch into c->dens
+DensStatsArgs dens_stats_args(sphx_ctx *c, int every)
+{
+    const DensStats &f = c->dens;
+    DensStatsArgs a{};
+    a.isum = f.isum.get(); a.dsum = f.dsum.get(); a.keys = f.keys.get(); a.head = f.head.get();
+    a.DH = c->prm.DH; a.bin_w = c->prm.DH / f.n_bins; a.DL = c->prm.DL;
+    a.t_from = f.cfg.t_from;
+    a.delta_bound = f.cfg.delta_bound; a.hist_range = f.cfg.hist_range;
+    a.hist_scale = (double)f.cfg.n_hist / (2.0 * f.cfg.hist_range);
+    for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
+    a.n_bins = f.n_bins; a.n_bands = f.n_bands; a.n_hist = f.cfg.n_hist;
+    a.block = (int)f.block(); a.kblock = (int)f.kblock();
+    a.e = f.e;
+    a.every = every;
+    return a;
+}
+
+// workgroups of the sample of a channel that holds n particles: kDensTrips trips of kDensCentres particles each
+unsigned dens_stats_blocks(size_t n)
+{
+    return std::clamp<unsigned>(div_up(n, (size_t)kDensCentres * kDensTrips), 1u, (unsigned)kDensMaxBlocks);
+}
+
+// k_dens_stats on state s (pos, mass and the cell ranges and binned cells of the layout it is stored in) -- of a batch: member
+// 0's -- into c->dens
+void launch_dens_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    launch_forms(c, "k_dens_stats", Forms{k_dens_stats, k_dens_stats_b}, dens_stats_blocks((size_t)c->nf), kDensBlock, c->dens.shmem(), q,
+                 c->grid, per_member(c->phys), s, c->walls, dens_stats_args(c, every));
+}
+
 }  // namespace
 
 void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
@@ -361,6 +395,7 @@ void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
     if (c->pairs.on) launch_pair_dist(c, q, s, c->pairs.cfg.every);
     if (c->grads.on) launch_grad_stats(c, q, s, c->grads.cfg.every);
     if (c->tracers.on) launch_tracers(c, q, s, c->tracers.cfg.every);
+    if (c->dens.on) launch_dens_stats(c, q, s, c->dens.cfg.every);
 }
 
 // ---- flow statistics ----
@@ -1469,6 +1504,166 @@ SPHX_EXPORT int sphx_ctx_grad_stats_read(sphx_ctx *c, int band, int capacity, in
     SPHX_TRY
     const GradStats &f = sampler_of(c, &sphx_ctx::grads, kGradNames, true);
     grad_stats_read(f, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, sums, n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- density statistics ----
+
+// every check of a configuration of channels with parameters prm (cfg, n_bins, n_bands, e); SPHX:DensStats:config errors
+void DensStats::check(const sphx_params &prm, const sphx_dens_stats_config *cfg)
+{
+    const char *id = "SPHX:DensStats:config";
+    require(cfg != nullptr, id, "config must not be NULL");
+    require(cfg->n_bins >= 0, id, "n_bins must be >= 0 (0 = the reference's profile bins)");
+    require(cfg->every >= 1, id, "every must be >= 1");
+    require(!std::isnan(cfg->t_from), id, "t_from must not be NaN");
+    require(cfg->n_hist >= 1 && cfg->n_hist <= kDensMaxHist, id, "n_hist must be 1 .. 1024");
+    require(cfg->delta_bound > 0.0 && cfg->delta_bound <= 0.5, id, "delta_bound must be in (0, 0.5]");  // (a NaN fails)
+    require(cfg->hist_range > 0.0 && cfg->hist_range <= cfg->delta_bound, id, "hist_range must be in (0, delta_bound]");
+    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, id, "n_bands must be 0, 1 or 2");
+    for (int b = 0; b < cfg->n_bands; ++b)
+        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, id,
+                "band centres must be finite and half-widths finite and >= 0");
+    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
+    require(((uint64_t)dens_sum_words(cfg->n_bands + 1, bins, cfg->n_hist) + dens_key_words(cfg->n_bands + 1, bins)) * sizeof(unsigned long long)
+                <= kDensMaxShmem,
+            id, "(n_bands + 1) * (8 * n_bins + n_hist + 2) must not exceed 7680 (the 60 KB of LDS of a workgroup)");
+    this->cfg = *cfg;
+    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
+    n_bins = bins;
+    n_bands = cfg->n_bands + 1;
+    // 2^e >= delta_bound: frexp gives delta_bound = m 2^e with 0.5 <= m < 1, and m = 0.5 is the power of two itself
+    int ex = 0;
+    const double m = std::frexp(cfg->delta_bound, &ex);
+    e = m == 0.5 ? ex - 1 : ex;
+}
+
+// the checked configuration, and sums, keys and heads for M members
+void DensStats::alloc(const DensStats &checked, int M)
+{
+    cfg = checked.cfg;
+    n_bins = checked.n_bins;
+    n_bands = checked.n_bands;
+    e = checked.e;
+    members = M;
+    isum.alloc(block() * M);
+    dsum.alloc(block() * M);
+    keys.alloc(kblock() * M);
+    head.alloc(M);
+}
+
+// Band `band` of member m: the binned sums with d_min and d_max behind them (into sums[field * stride + bin], where given),
+// the histogram (hist[0 .. n_hist), below, above, where given) and the head (where given)
+void DensStats::read(hipStream_t st, int m, int band, int stride, double *sums, int64_t *hist, int64_t *below, int64_t *above,
+                     int64_t *n_samples, double *t_first, double *t_last) const
+{
+    std::vector<double> binned(row()), hrow_(hrow());
+    std::vector<unsigned long long> k((size_t)n_bins * kDensKeys);
+    DensStatsHead h{};
+    const double *base = dsum.get() + (size_t)m * block();
+    SPHX_HIP(hipMemcpyAsync(binned.data(), base + (size_t)band * row(), row() * sizeof(double), hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipMemcpyAsync(hrow_.data(), base + (size_t)n_bands * row() + (size_t)band * hrow(), hrow() * sizeof(double),
+                            hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipMemcpyAsync(k.data(), keys.get() + (size_t)m * kblock() + (size_t)band * n_bins * kDensKeys, k.size() * sizeof(unsigned long long),
+                            hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipMemcpyAsync(&h, head.get() + m, sizeof(DensStatsHead), hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    // dens_key back to the double; 0: no particle yet
+    auto unkey = [](unsigned long long key, double none) {
+        if (!key) return none;
+        const unsigned long long b = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
+        double v;
+        std::memcpy(&v, &b, sizeof(v));
+        return v;
+    };
+    const double inf = std::numeric_limits<double>::infinity();
+    if (sums)
+        for (int b = 0; b < n_bins; ++b) {
+            for (int j = 0; j < kDensFields; ++j) sums[(size_t)j * stride + b] = binned[(size_t)b * kDensFields + j];
+            sums[(size_t)kDensFields * stride + b] = -unkey(k[(size_t)b * kDensKeys + 1], -inf);  // d_min (+inf before the first)
+            sums[(size_t)(kDensFields + 1) * stride + b] = unkey(k[(size_t)b * kDensKeys], -inf);  // d_max (-inf before the first)
+        }
+    if (hist)
+        for (int b = 0; b < cfg.n_hist; ++b) hist[b] = (int64_t)hrow_[b];
+    if (below) *below = (int64_t)hrow_[cfg.n_hist];
+    if (above) *above = (int64_t)hrow_[cfg.n_hist + 1];
+    read_head(h, n_samples, t_first, t_last);
+}
+
+namespace {
+
+// enable for M members of channels with parameters prm on schedule s: every check of cfg first
+void dens_stats_enable(DensStats &f, const sphx_params &prm, const sphx_dens_stats_config *cfg, int M, Schedule &s, hipStream_t st)
+{
+    DensStats checked;
+    checked.check(prm, cfg);
+    sampler_on(f, kDensNames, s, st, [&] { f.alloc(checked, M); });
+}
+
+// the argument checks of a read of member m, then settle() -- what is enqueued lands first -- and the read; shared by contexts
+// and batches
+template <typename Settle>
+void dens_stats_read(const DensStats &f, hipStream_t st, Settle &&settle, int m, int band, int capacity, int hist_capacity, int *n_bins,
+                     int *n_hist, double *sums, int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first,
+                     double *t_last)
+{
+    require(band >= 0 && band < f.n_bands, "SPHX:DensStats:band", "band must be 0 (whole channel) .. n_bands");
+    require(sums == nullptr || capacity >= f.n_bins, "SPHX:DensStats:capacity", "capacity is smaller than the number of bins");
+    require(hist == nullptr || hist_capacity >= f.cfg.n_hist, "SPHX:DensStats:capacity",
+            "hist_capacity is smaller than the number of histogram bins");
+    settle();
+    f.read(st, m, band, capacity, sums, hist, below, above, n_samples, t_first, t_last);
+    if (n_bins) *n_bins = f.n_bins;
+    if (n_hist) *n_hist = f.cfg.n_hist;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_dens_stats_enable(sphx_ctx *c, const sphx_dens_stats_config *cfg)
+{
+    SPHX_TRY
+    DensStats &f = sampler_of(c, &sphx_ctx::dens, kDensNames, false);
+    dens_stats_enable(f, c->prm, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_dens_stats_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    DensStats &f = sampler_of(c, &sphx_ctx::dens, kDensNames, false);
+    if (f.on) sampler_off(f, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_dens_stats_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    DensStats &f = sampler_of(c, &sphx_ctx::dens, kDensNames, true);
+    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_dens_stats_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampler_of(c, &sphx_ctx::dens, kDensNames, true);
+    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_dens_stats);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_dens_stats_read(sphx_ctx *c, int band, int capacity, int hist_capacity, int *n_bins, int *n_hist, double *sums,
+                                         int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first, double *t_last)
+{
+    SPHX_TRY
+    const DensStats &f = sampler_of(c, &sphx_ctx::dens, kDensNames, true);
+    dens_stats_read(f, c->stream, [c] { settle_owed(c); }, 0, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above,
+                    n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }

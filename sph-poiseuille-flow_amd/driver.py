@@ -19,8 +19,9 @@ from . import capi
 from .geometry import init_particles
 from .mex_surface import sph_neighbor_search_mex, sph_physics_shell_mex
 from . import restart
-from .profile import (compute_mid_channel_profile, field_map_means, final_profile, flow_stats_profile, grad_stats_profiles, l2_error,
-                      n_profile_bins, pool_field_maps, pair_dist_profiles, pool_flow_stats, pool_grad_stats, pool_pair_dist,
+from .profile import (compute_mid_channel_profile, dens_stats_profiles, field_map_means, final_profile, flow_stats_profile,
+                      grad_stats_profiles, l2_error, n_profile_bins, pool_dens_stats, pool_field_maps, pair_dist_profiles,
+                      pool_flow_stats, pool_grad_stats, pool_pair_dist,
                       poiseuille_startup, pool_tracers, profile_series_profiles, tracer_profiles, unwrap_tracers)
 
 
@@ -64,6 +65,9 @@ class RunResult:
 
     tracers: dict = None  # run / run_sweep / run_ensemble(..., tracers=...): the device-side tracer series of the whole run
                           # (capi.Context.tracers: x, y, u_x, u_y of the tracked fluid rows per record; tracer_figures())
+
+    dens_stats: list = None  # run / run_sweep / run_ensemble(..., density_from=...): the device-side density statistics of the
+                             # run, one dict per band (capi.Context.dens_stats: the sums with the profiles; density_figures())
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -492,6 +496,68 @@ def _tracer_columns(prms, series):
     return {k: np.array([f[k] for f in figs]) for k in _TRACER_COLUMNS}
 
 
+def _dens_bands(prm, bands):
+    """the x-bands of a run's density statistics: the mid-channel band of the output-point profiles (band 1) unless given"""
+    return [(0.5 * prm.DL, max(prm.dp, prm.h))] if bands is None else bands
+
+
+def _dens_stats_bands(prm, sums):
+    """a channel's sums, one dict per band, each with the profiles of profile.dens_stats_profiles"""
+    return [dict(s, **dens_stats_profiles(prm.DH, prm.p0, s)) for s in sums]
+
+
+def density_figures(prm, dens, band=0):
+    """Figures of a run's density statistics (RunResult.dens_stats, or [capi.Context.dens_stats_sums(b) for b in bands]: one dict
+    per band), on the host, from band `band`; delta = rho / rho0 - 1 of the density every step starts from:
+      delta_rms, delta_mean   sqrt(sum delta^2 / N) and sum delta / N over the whole band
+      delta_max    the largest |delta| met: the larger of |d_min| and |d_max| over the bins
+      outliers     the particles left out (|delta| > delta_bound), over the whole band
+      ma2          U_max^2 rho0 / p0 = (U_max / c)^2 with p0 = rho0 c^2, U_max = g DH^2 / (8 nu): the density variation a weakly
+                   compressible flow at this Mach number is expected to show, to read delta_rms and delta_max beside
+      p_spread     the spread (max - min) of the bin means of p = p0 delta over the bins at least 2h from a wall, in units of
+                   rho0 U_max^2: plane Poiseuille flow keeps p flat in y
+      wall_bias    the mean delta of the bins within 2h of a wall minus that of the bins at least 2h from one (by bin centre,
+                   each side weighted by its counts)
+      packing      1 + sum dvol / N over the whole band: the mean of rho0 / rho, the area sum m / rho the particles claim over
+                   the area sum m / rho0 they were given
+    NaN where the band holds no particle (p_spread, wall_bias: where a side has none)."""
+    b = dens[band]
+    prof = dens_stats_profiles(prm.DH, prm.p0, b)
+    y = prof["y_mid"]
+    N = np.asarray(b["count"], dtype=np.float64)
+    total = float(N.sum())
+    nan = float("nan")
+    u_max = prm.gravity_g * prm.DH * prm.DH / (8.0 * prm.nu)
+    inner = (y >= 2.0 * prm.h) & (y <= prm.DH - 2.0 * prm.h)
+    some = N > 0
+
+    def mean(rows):
+        n = float(N[rows & some].sum())
+        return float(np.asarray(b["sum_d"])[rows & some].sum()) / n if n > 0 else nan
+
+    p_in = prof["p_mean"][inner & some]
+    ends = [v for v in (np.abs(np.asarray(b["d_min"])[some]), np.abs(np.asarray(b["d_max"])[some])) if len(v)]
+    return dict(delta_rms=float(np.sqrt(np.sum(b["sum_d2"]) / total)) if total > 0 else nan,
+                delta_mean=float(np.sum(b["sum_d"]) / total) if total > 0 else nan,
+                delta_max=float(max(np.max(v) for v in ends)) if ends else nan,
+                outliers=int(np.sum(b["outliers"])), ma2=float(u_max * u_max * prm.rho0 / prm.p0),
+                p_spread=float((np.max(p_in) - np.min(p_in)) / (prm.rho0 * u_max * u_max)) if len(p_in) else nan,
+                wall_bias=mean(~inner) - mean(inner),
+                packing=float(1.0 + np.sum(b["sum_dvol"]) / total) if total > 0 else nan)
+
+
+def _dens_columns(prms, dens):
+    """The density columns of a sweep's table, one [M] array each: delta_rms, delta_max, p_spread of
+    density_figures(prm_m, dens_stats_m)."""
+    figs = [density_figures(p, d) for p, d in zip(prms, dens)]
+    return {k: np.array([f[k] for f in figs]) for k in ("delta_rms", "delta_max", "p_spread")}
+
+
+def _density_request(density_from, density_every, density_hist, density_bands):
+    """the `density` of _run_batch: None without density_from"""
+    return None if density_from is None else (density_from, density_every, density_hist, density_bands)
+
+
 def _concat_history(chunks):
     if not chunks:
         return capi.history_dict(np.zeros((0, len(capi.HISTORY_FIELDS))))
@@ -506,7 +572,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
         field_walls=False, probe_points=None, probe_every=1, probe_capacity=65536, probe_from=None, probe_walls=False,
         profiles_every=None, profiles_from=None, profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1,
         pairs_bins=64, pairs_walls=False, pairs_bands=None, gradients_from=None, gradients_every=1, gradients_walls=False,
-        gradients_bands=None, tracers=None, tracers_every=1, tracers_from=None, tracers_capacity=None):
+        gradients_bands=None, tracers=None, tracers_every=1, tracers_from=None, tracers_capacity=None, density_from=None,
+        density_every=1, density_hist=(64, 0.05), density_bands=None):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -558,7 +625,15 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     rows, a seeded choice (tracer_ids) -- every tracers_every-th step ending at t >= tracers_from (None: from the start); the
     buffer (tracers_capacity records; None: 65536, or what the bound on capacity * n_tracers * 4 allows) is drained at every
     output point -- a run that lost records raises RuntimeError and names the capacity needed -- and RunResult.tracers is the
-    series of the whole run (tracer_figures() gives the cross-stream diffusivity, the drift and the Lagrangian velocity error)."""
+    series of the whole run (tracer_figures() gives the cross-stream diffusivity, the drift and the Lagrangian velocity error).
+    density_from (resident engine; default off): re-sum, on the device and inside the step loop, the density every step starts
+    from at every fluid particle (include/sphx.h section 2r) every density_every-th step ending at t >= density_from and bin
+    delta = rho / rho0 - 1 into the reference's profile bins, for the whole channel and the bands density_bands (None: the
+    mid-channel band (DL/2, max(dp, h)) as band 1), with a histogram of delta of density_hist = (n_hist, hist_range).
+    RunResult.dens_stats is one dict per band; density_figures() gives delta_rms, delta_max, the spread of the pressure across
+    the channel, the bias next to the walls and the packing."""
+    if density_from is not None and engine != "resident":
+        raise ValueError("density_from needs the resident engine (the density is re-summed on the device)")
     if tracers is not None and engine != "resident":
         raise ValueError("tracers needs the resident engine (the tracers are recorded on the device)")
     if gradients_from is not None and engine != "resident":
@@ -605,6 +680,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     pair_dist = None
     grad_stats = None
     tracer_series, tracer_chunks = None, []
+    dens_stats = None
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context.from_parts(prm, parts, t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
@@ -635,6 +711,9 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
             if tracing:
                 ctx.tracers_enable(tracing[0], every=tracing[1], capacity=tracing[2],
                                    t_from=t_start if tracers_from is None else tracing[3])
+            if density_from is not None:
+                ctx.dens_stats_enable(n_bins=n_bins, every=density_every, t_from=density_from, n_hist=density_hist[0],
+                                      hist_range=density_hist[1], bands=_dens_bands(prm, density_bands))
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -690,6 +769,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 grad_stats = _grad_stats_bands(prm.DH, [ctx.grad_stats_sums(b) for b in range(1 + len(_grad_bands(prm, gradients_bands)))])
             if tracing:
                 tracer_series = _concat_tracers(tracing[0], tracer_chunks)
+            if density_from is not None:
+                dens_stats = _dens_stats_bands(prm, [ctx.dens_stats_sums(b) for b in range(1 + len(_dens_bands(prm, density_bands)))])
         finally:
             ctx.close()
     elif engine == "mex":
@@ -740,7 +821,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     return _run_result(prm, nf, nt, pos, vel, t=t, steps=int(step), wall_seconds=wall, profile_times=profile_times,
                        mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t, grid_policy=policy,
                        full_profile_u=full_profiles, n_inner=n_inner, time_avg=time_avg, history=history, field_avg=field_avg,
-                       probes=probes, profile_series=series, pair_dist=pair_dist, grad_stats=grad_stats, tracers=tracer_series)
+                       probes=probes, profile_series=series, pair_dist=pair_dist, grad_stats=grad_stats, tracers=tracer_series,
+                       dens_stats=dens_stats)
 
 
 def _run_result(prm, nf, nt, pos, vel, **fields):
@@ -781,7 +863,7 @@ def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
 
 
 def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None, probe=None,
-               profiles=None, pairs=None, gradients=None, tracers=None):
+               profiles=None, pairs=None, gradients=None, tracers=None, density=None):
     """The batch run behind run_batch, run_ensemble and run_sweep (`name`, for the refusals): check and default the inputs,
     open the batch with the launch keywords `launch`, enable what was asked for, advance output point by output point, build
     every member's RunResult.
@@ -805,6 +887,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
       tracers    (tracers, tracers_every, tracers_from, tracers_capacity) as run() takes them: the tracers of include/sphx.h
                  section 2q, one id list for all members, drained at every output point; every member gets its tracers, and one
                  that lost records raises RuntimeError
+      density    (density_from, density_every, density_hist, density_bands): the density statistics of include/sphx.h section 2s
+                 in the bins and with the default band of run(); every member gets its dens_stats
     -> the members, the wall seconds, the grid policy, with average the raw sums (whole, mid) of all members, and with field the
     raw planes of all members."""
     prms = list(prms)
@@ -852,6 +936,9 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                                 bands=_grad_bands(p0, gradients[3]))
         if tracing:
             b.tracers_enable(tracing[0], every=tracing[1], capacity=tracing[2], t_from=tracing[3])
+        if density:
+            b.dens_stats_enable(n_bins=n_bins, every=density[1], t_from=float(density[0]), n_hist=density[2][0], hist_range=density[2][1],
+                                bands=_dens_bands(p0, density[3]))
         t = 0.0
         st = None
         while t < p0.t_end - 1e-12:
@@ -896,6 +983,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         empty_series = b.profile_series_sums() if profiles and not schunks[0] else None
         pair_sums = b.pair_dist_sums() if pairs else None
         grad_sums = [b.grad_stats_sums(k) for k in range(1 + len(_grad_bands(p0, gradients[3])))] if gradients else None  # [band][member]
+        dens_sums = [b.dens_stats_sums(k) for k in range(1 + len(_dens_bands(p0, density[3])))] if density else None  # [band][member]
         members = []
         for m, prm in enumerate(prms):
             extra = {}
@@ -917,6 +1005,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                 extra.update(grad_stats=_grad_stats_bands(prm.DH, [band[m] for band in grad_sums]))
             if tracing:
                 extra.update(tracers=_concat_tracers(tracing[0], tchunks[m]))
+            if density:
+                extra.update(dens_stats=_dens_stats_bands(prm, [band[m] for band in dens_sums]))
             members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra))
     return members, wall, policy, sums, planes
 
@@ -970,6 +1060,8 @@ class EnsembleResult:
                                # dict per band, with the figures of profile.pair_dist_profiles
     pooled_grad: list = None   # with gradients_from, under the condition of `pooled`: profile.pool_grad_stats of the members' sums,
                                # one dict per band
+    pooled_density: list = None  # with density_from, under the condition of `pooled`: profile.pool_dens_stats of the members' sums,
+                                 # one dict per band
     pooled_tracers: dict = None  # with tracers, under the condition of `pooled` and where the members recorded at the same steps
                                  # and times (profile.pool_tracers refuses others): the members' columns side by side
 
@@ -981,7 +1073,8 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
                  rebuild_every=0, log=None, history_every=None, field_from=None, field_every=1, field_shape=None,
                  field_walls=False, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False, pairs_bands=None,
                  gradients_from=None, gradients_every=1, gradients_walls=False, gradients_bands=None, tracers=None, tracers_every=1,
-                 tracers_from=None, tracers_capacity=None):
+                 tracers_from=None, tracers_capacity=None, density_from=None, density_every=1, density_hist=(64, 0.05),
+                 density_bands=None):
     """Time-averaged profiles of M channels of one geometry stepped as one batch (capi.Batch), averaged on the device
     inside the step loop (include/sphx.h section 2c) as run(average_from=...) does for one channel: every
     average_every-th step ending at t >= average_from, whole channel and the mid-channel band (DL/2, max(dp, h)).  The
@@ -994,7 +1087,9 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
     (include/sphx.h section 2o), with the keywords of run(): every member gets a grad_stats, and members that share their physics
     pooled_grad (profile.pool_grad_stats, one dict per band).  tracers: every member's tracers as well (include/sphx.h section
     2q), with the keywords of run(): one id list for all members, every member gets its tracers, and members that share their
-    physics and whose clocks agreed record by record pooled_tracers (profile.pool_tracers).  Returns an EnsembleResult."""
+    physics and whose clocks agreed record by record pooled_tracers (profile.pool_tracers).  density_from: every member's density statistics as well
+    (include/sphx.h section 2s), with the keywords of run(): every member gets a dens_stats, and members that share their physics
+    pooled_density (profile.pool_dens_stats, one dict per band).  Returns an EnsembleResult."""
     prms = list(prms)
     if history_every is not None:
         raise ValueError("run_ensemble records no step history (run_sweep does, for every member)")
@@ -1006,9 +1101,10 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
         field=_field_request(field_from, field_every, field_shape, field_walls),
         pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands),
         gradients=_gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands),
-        tracers=None if tracers is None else (tracers, tracers_every, tracers_from, tracers_capacity))
+        tracers=None if tracers is None else (tracers, tracers_every, tracers_from, tracers_capacity),
+        density=_density_request(density_from, density_every, density_hist, density_bands))
     p0, M = prms[0], len(prms)
-    pooled = pooled_field = pooled_pairs = pooled_grad = pooled_tracers = None
+    pooled = pooled_field = pooled_pairs = pooled_grad = pooled_tracers = pooled_density = None
     if all(getattr(p, k) == getattr(p0, k) for p in prms for k in _PHYSICS):
         pw, pm = pool_flow_stats(p0.DH, whole), pool_flow_stats(p0.DH, mid)
         pooled = time_average(p0, pw, pm)
@@ -1023,8 +1119,11 @@ def run_ensemble(prms, *, average_from, parts_list=None, average_every=1, lanes_
             pooled_grad = [pool_grad_stats(p0.DH, [r.grad_stats[b] for r in members]) for b in range(len(members[0].grad_stats))]
         if tracers is not None and all(np.array_equal(r.tracers[k], members[0].tracers[k]) for r in members for k in ("step", "t")):
             pooled_tracers = pool_tracers([r.tracers for r in members])
+        if density_from is not None:
+            pooled_density = [pool_dens_stats(p0.DH, p0.p0, [r.dens_stats[b] for r in members]) for b in range(len(members[0].dens_stats))]
     return EnsembleResult(members=members, pooled=pooled, wall_seconds=wall, grid_policy=policy, pooled_field=pooled_field,
-                          pooled_pairs=pooled_pairs, pooled_grad=pooled_grad, pooled_tracers=pooled_tracers)
+                          pooled_pairs=pooled_pairs, pooled_grad=pooled_grad, pooled_tracers=pooled_tracers,
+                          pooled_density=pooled_density)
 
 
 @dataclass
@@ -1066,7 +1165,8 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
               probe_capacity=65536, probe_from=None, probe_walls=False, profiles_every=None, profiles_from=None,
               profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False,
               pairs_bands=None, gradients_from=None, gradients_every=1, gradients_walls=False, gradients_bands=None, tracers=None,
-              tracers_every=1, tracers_from=None, tracers_capacity=None):
+              tracers_every=1, tracers_from=None, tracers_capacity=None, density_from=None, density_every=1, density_hist=(64, 0.05),
+              density_bands=None):
     """A parameter sweep: M channels of one geometry that differ in mu, c_f, p0, gravity_g, transport_coeff, stepped as one
     batch (capi.Batch) with every member's step history recorded on the device, inside the step loop (include/sphx.h
     section 2f) as run(history_every=...) does for one channel.  The members advance output point by output point as in
@@ -1087,7 +1187,9 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     run(): each member gets its grad_stats and the table the columns L2_shear, tau_wall_dev, div_rms of
     grad_figures(prm_m, grad_stats_m).  tracers: every member's tracers as well (include/sphx.h section 2q), with the keywords of
     run(): one id list for all members, each member gets its tracers and the table the columns D_y_nu, y_drift, u_dev_rms of
-    tracer_figures(prm_m, tracers_m) -- the Lagrangian figures that respond to transport_coeff.  A member that lost records to a full buffer raises RuntimeError, which names the member and the
+    tracer_figures(prm_m, tracers_m) -- the Lagrangian figures that respond to transport_coeff.  density_from: every member's density
+    statistics as well (include/sphx.h section 2s), with the keywords of run(): each member gets its dens_stats and the table the
+    columns delta_rms, delta_max, p_spread of density_figures(prm_m, dens_stats_m).  A member that lost records to a full buffer raises RuntimeError, which names the member and the
     capacity the output interval needed.  Returns a SweepResult."""
     prms = list(prms)
     members, wall, policy, _, planes = _run_batch(
@@ -1099,7 +1201,8 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
         profiles=None if profiles_every is None else (profiles_every, profiles_from, profiles_capacity, profiles_bands),
         pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands),
         gradients=_gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands),
-        tracers=None if tracers is None else (tracers, tracers_every, tracers_from, tracers_capacity))
+        tracers=None if tracers is None else (tracers, tracers_every, tracers_from, tracers_capacity),
+        density=_density_request(density_from, density_every, density_hist, density_bands))
     table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
     if planes is not None:
         table.update(field_table(prms, [r.field_avg for r in members]))
@@ -1113,4 +1216,6 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
         table.update(_grad_columns(prms, [r.grad_stats for r in members]))
     if tracers is not None:
         table.update(_tracer_columns(prms, [r.tracers for r in members]))
+    if density_from is not None:
+        table.update(_dens_columns(prms, [r.dens_stats for r in members]))
     return SweepResult(members=members, table=table, wall_seconds=wall, grid_policy=policy)

@@ -51,6 +51,13 @@
  *   [ids, step, t, x, y, u_x, u_y, n_dropped, n_missing] = sphx_ctx_mex('tracer_read', h, drain)
  *       ids: T x 1 (1-based, as given); step, t: n x 1; x, y, u_x, u_y: n x T, one row per recorded step, column k the
  *       particle in row ids(k) of 'download' (particle tracers, include/sphx.h section 2p); drain ~= 0 empties the device buffer
+ *   sphx_ctx_mex('dens_enable', h, n_bins, every, t_from, n_hist, hist_range, delta_bound, bands)   % bands as for stats_enable
+ *   sphx_ctx_mex('dens_disable', h)
+ *   sphx_ctx_mex('dens_sample', h)   % add one sample of the current state now
+ *   [sums, hist, below, above, n_samples, t_first, t_last] = sphx_ctx_mex('dens_read', h, band)
+ *       sums: n_bins x 8, one column per field in the order of include/sphx.h section 2r (density statistics): count, sum delta,
+ *       sum delta^2, sum dvol, sum wall, outliers, d_min, d_max; hist: n_hist x 1 counts of delta on [-hist_range, hist_range), as
+ *       doubles (exact up to 2^53), below / above: the counts outside
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -518,6 +525,56 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 1) plhs[1] = mxCreateDoubleScalar((double)ns);
         if (nlhs > 2) plhs[2] = mxCreateDoubleScalar(t0);
         if (nlhs > 3) plhs[3] = mxCreateDoubleScalar(t1);
+    } else if (strcmp(cmd, "dens_enable") == 0) {
+        sphx_dens_stats_config dc;
+        const mxArray *b;
+        size_t nb, k;
+        arity(cmd, nrhs, 9, nlhs, 0);
+        b = prhs[8];
+        if (!mxIsDouble(b)) mexErrMsgIdAndTxt("SPHX:DensStats:config", "dens_enable: bands must be a double [k x 2] array");
+        nb = mxGetNumberOfElements(b) == 0 ? 0 : mxGetM(b);
+        if (nb > 2 || (nb > 0 && mxGetN(b) != 2)) mexErrMsgIdAndTxt("SPHX:DensStats:config", "dens_enable: bands must be [k x 2], k <= 2");
+        memset(&dc, 0, sizeof(dc));
+        dc.n_bins = (int32_t)mxGetScalar(prhs[2]);
+        dc.every = (int32_t)mxGetScalar(prhs[3]);
+        dc.t_from = mxGetScalar(prhs[4]);
+        dc.n_hist = (int32_t)mxGetScalar(prhs[5]);
+        dc.hist_range = mxGetScalar(prhs[6]);
+        dc.delta_bound = mxGetScalar(prhs[7]);
+        dc.n_bands = (int32_t)nb;
+        for (k = 0; k < nb; ++k) { dc.band_x[k] = mxGetDoubles(b)[k]; dc.band_hw[k] = mxGetDoubles(b)[k + nb]; }
+        ok(sphx_ctx_dens_stats_enable(handle(prhs[1]), &dc));
+    } else if (strcmp(cmd, "dens_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_dens_stats_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "dens_sample") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_dens_stats_sample(handle(prhs[1])));
+    } else if (strcmp(cmd, "dens_read") == 0) {
+        sphx_ctx *c;
+        int band, n_bins = 0, n_hist = 0, k;
+        int64_t ns = 0, below = 0, above = 0, *hist;
+        double t0 = 0.0, t1 = 0.0;
+        int rc;
+        arity(cmd, nrhs, 3, nlhs, 7);
+        c = handle(prhs[1]);
+        band = (int)mxGetScalar(prhs[2]);
+        ok(sphx_ctx_dens_stats_read(c, band, 0, 0, &n_bins, &n_hist, NULL, NULL, NULL, NULL, NULL, NULL, NULL));
+        /* [SPHX_DENS_STATS_FIELDS][n_bins] is the column-major n_bins x 8 matrix */
+        plhs[0] = mxCreateDoubleMatrix((mwSize)n_bins, SPHX_DENS_STATS_FIELDS, mxREAL);
+        hist = (int64_t *)mxMalloc((size_t)n_hist * sizeof(int64_t));
+        rc = sphx_ctx_dens_stats_read(c, band, n_bins, n_hist, NULL, NULL, mxGetDoubles(plhs[0]), hist, &below, &above, &ns, &t0, &t1);
+        if (rc != SPHX_OK) { mxFree(hist); ok(rc); }
+        if (nlhs > 1) {
+            plhs[1] = mxCreateDoubleMatrix((mwSize)n_hist, 1, mxREAL);
+            for (k = 0; k < n_hist; ++k) mxGetDoubles(plhs[1])[k] = (double)hist[k];
+        }
+        mxFree(hist);
+        if (nlhs > 2) plhs[2] = mxCreateDoubleScalar((double)below);
+        if (nlhs > 3) plhs[3] = mxCreateDoubleScalar((double)above);
+        if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)ns);
+        if (nlhs > 5) plhs[5] = mxCreateDoubleScalar(t0);
+        if (nlhs > 6) plhs[6] = mxCreateDoubleScalar(t1);
     } else if (strcmp(cmd, "destroy") == 0) {
         arity(cmd, nrhs, 2, nlhs, 0);
         sphx_ctx_destroy(handle(prhs[1]));

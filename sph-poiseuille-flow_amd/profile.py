@@ -769,3 +769,209 @@ def pool_tracers(tr_list):
     out.update(n_dropped=int(sum(tr.get("n_dropped", 0) for tr in tr_list)), n_missing=int(sum(tr.get("n_missing", 0) for tr in tr_list)),
                n_members=len(tr_list))
     return out
+
+
+# ---- density statistics (include/sphx.h sections 2r, 2s): the state of compression ----
+
+# the eight values per bin and band, in the order the library writes them; the first six add up over samples and channels
+DENS_FIELDS = ("count", "sum_d", "sum_d2", "sum_dvol", "sum_wall", "outliers", "d_min", "d_max")
+DENS_SUMS = DENS_FIELDS[:6]
+DENS_MAX_HIST = 1024
+DENS_MAX_WORDS = 7680  # (n_bands + 1) * (8 * n_bins + n_hist + 2): the 60 KB of LDS of a workgroup
+
+
+def summation_density(pos, mass, DL, h, rho0, inv_sigma0, wall_pos=None, wall_vol=None, chunk=512, acc=np.float64, reverse=False):
+    """The summation density of every fluid particle as the step's first pass computes it, in numpy -- the definition
+    k_dens_stats is tested against (include/sphx.h section 2r).  pos [n, 2] and mass [n] (or one number): the fluid particles;
+    wall_pos [m, 2] and wall_vol [m]: the wall particles and their volumes, or None.  Over every fluid partner j != i and every
+    wall particle with 1e-24 < r2 < (2h)^2, nearest image in x:
+        s_in = W(0) + sum W(r_ij),  s_ct = sum W(r_ij) V_j,  rho_i = s_in rho0 inv_sigma0 + s_ct rho0^2 inv_sigma0 / mass_i
+    and rho_i = rho0 where that is <= 1e-12 (the step's floor).  -> rho [n], wall [n] = s_ct rho0 inv_sigma0 / mass_i, the walls'
+    share of rho_i / rho0.  Chunked over particles sorted by x, a chunk against the partners within 2h of its x-range.  acc /
+    reverse exist for the tests alone: the type the per-particle sums are accumulated in and whether the partners are added in
+    reversed order, which together measure the rounding error of these sums (tests/dens_stats_cases.py); no caller in the
+    package sets them."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 2)
+    n = len(pos)
+    mass = np.broadcast_to(np.asarray(mass, dtype=np.float64), (n,))
+    sigma, rcut2, half = 10.0 / (7.0 * np.pi * h * h), (2.0 * h) * (2.0 * h), DL / 2
+    margin = 2.0 * h * (1.0 + 1e-9) + 1e-12 * DL
+    S = np.zeros((2, n), dtype=acc)  # s_in without W(0), s_ct
+    cx = np.mod(pos[:, 0], DL)
+    order_c = np.argsort(cx, kind="stable")
+
+    def sweep(p_pos, p_vol, same, row):
+        px = np.mod(p_pos[:, 0], DL)
+        order_p = np.argsort(px, kind="stable")
+        pxs = px[order_p]
+        for a in range(0, n, chunk):
+            ci = order_c[a:a + chunk]
+            lo, hi = cx[ci[0]] - margin, cx[ci[-1]] + margin
+            if hi - lo >= DL:
+                cand = np.sort(order_p)
+            else:
+                parts = [order_p[np.searchsorted(pxs, lo, "left"):np.searchsorted(pxs, hi, "right")]]
+                if lo < 0.0:
+                    parts.append(order_p[np.searchsorted(pxs, lo + DL, "left"):])
+                if hi > DL:
+                    parts.append(order_p[:np.searchsorted(pxs, hi - DL, "right")])
+                cand = np.unique(np.concatenate(parts))
+            if reverse:
+                cand = cand[::-1]
+            dx = pos[ci, 0][:, None] - p_pos[cand, 0][None, :]
+            dx = np.where(dx > half, dx - DL, np.where(dx < -half, dx + DL, dx))
+            dy = pos[ci, 1][:, None] - p_pos[cand, 1][None, :]
+            r2 = dx * dx + dy * dy
+            keep = (r2 > 1e-24) & (r2 < rcut2)
+            if same:
+                keep &= ci[:, None] != cand[None, :]
+            q = np.sqrt(np.where(keep, r2, 1.0)) / h
+            tq = 2.0 - q
+            W = np.where(q < 1.0, sigma * (1.0 - 1.5 * q * q + 0.75 * q * q * q), sigma * 0.25 * tq * tq * tq)
+            term = np.where(keep, W if p_vol is None else W * p_vol[cand][None, :], 0.0)
+            S[row, ci] += term.astype(acc, copy=False).sum(axis=1)
+
+    sweep(pos, None, True, 0)
+    if wall_pos is not None and len(wall_pos):
+        wall_pos = np.asarray(wall_pos, dtype=np.float64).reshape(-1, 2)
+        sweep(wall_pos, np.broadcast_to(np.asarray(wall_vol, dtype=np.float64), (len(wall_pos),)), False, 1)
+    s_in, s_ct = S[0] + acc(sigma), S[1]
+    wall = s_ct * acc(rho0) * acc(inv_sigma0) / mass.astype(acc)
+    rho = s_in * acc(rho0) * acc(inv_sigma0) + wall * acc(rho0)
+    rho = np.where(rho <= 1e-12, acc(rho0), rho)
+    return rho.astype(np.float64), wall.astype(np.float64)
+
+
+def dens_scales(delta_bound, n):
+    """The fixed-point scales of one sample of the density statistics, as the device picks them: with n <= 2^L particles and
+    2^e >= delta_bound (e <= -1 for delta_bound <= 0.5), delta is summed in units of 2^-s_d, delta^2 of 2^-s_d2, dvol of 2^-s_dvol,
+    wall of 2^-s_wall: s_d = 62 - L - e, s_d2 = 62 - L - 2e, s_dvol = 61 - L - e, s_wall = 61 - L.  -> dict(s_d, s_d2, s_dvol,
+    s_wall, e)."""
+    L = 0
+    while L < 31 and (1 << L) < n:
+        L += 1
+    m, e = np.frexp(float(delta_bound))
+    e = int(e) - 1 if m == 0.5 else int(e)
+    return dict(s_d=62 - L - e, s_d2=62 - L - 2 * e, s_dvol=61 - L - e, s_wall=61 - L, e=e)
+
+
+def dens_hist_bin(delta, n_hist, hist_range):
+    """The histogram word of every delta: 0 .. n_hist - 1 the bin floor((delta + hist_range) * (n_hist / (2 hist_range))) of
+    [-hist_range, hist_range), n_hist: below, n_hist + 1: above -- in the device's operation order."""
+    delta = np.asarray(delta, dtype=np.float64)
+    scale = float(n_hist) / (2.0 * hist_range)
+    k = np.clip(np.floor((delta + hist_range) * scale), 0, n_hist - 1).astype(np.int64)
+    return np.where(delta < -hist_range, n_hist, np.where(delta >= hist_range, n_hist + 1, k))
+
+
+def dens_stats_sums(pos, mass, DL, DH, h, rho0, inv_sigma0, n_bins, bands=(), n_hist=64, hist_range=0.05, delta_bound=0.5,
+                    wall_pos=None, wall_vol=None, density=None, quantise=False):
+    """One sample of the density statistics of include/sphx.h section 2r in numpy -- the oracle of k_dens_stats: delta = rho /
+    rho0 - 1, dvol = rho0 / rho - 1 and wall of summation_density binned with the flow statistics' rules
+    (compute_binned_profile_mean's bins over [0, DH], y outside dropped; band 0 the whole channel, bands [(x_centre,
+    half_width), ...] by in_band).  A particle with |delta| > delta_bound or a delta that is not finite is counted in
+    `outliers`, summed nowhere and in no histogram.  -> per band one dict of the DENS_FIELDS as [n_bins] arrays (d_min / d_max:
+    +inf / -inf in an empty bin), hist [n_hist] int64, below, above.  density: (rho, wall) of the same state -- from
+    summation_density, or from a download's mass / Vol -- to share it between calls.  quantise (set by the tests alone; no
+    caller in the package sets it): every particle's terms are rounded to the device's fixed-point grid of dens_scales before
+    they are added, as k_dens_stats rounds them."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 2)
+    n = len(pos)
+    rho, wall = density if density is not None else summation_density(pos, mass, DL, h, rho0, inv_sigma0, wall_pos, wall_vol)
+    rho, wall = np.asarray(rho, dtype=np.float64), np.asarray(wall, dtype=np.float64)
+    delta = rho / rho0 - 1.0
+    with np.errstate(invalid="ignore"):
+        ok = np.abs(delta) <= delta_bound  # (a NaN or an infinity fails the comparison)
+    dz = np.where(ok, delta, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dvol = np.where(ok, rho0 / rho - 1.0, 0.0)
+    values = [np.ones(n), dz, dz * dz, dvol, np.where(ok, wall, 0.0)]
+    if quantise:
+        sc = dens_scales(delta_bound, n)
+        shifts = [0, sc["s_d"], sc["s_d2"], sc["s_dvol"], sc["s_wall"]]
+        values = [np.ldexp(np.rint(np.ldexp(v, k)), -k) for v, k in zip(values, shifts)]
+    edges = np.linspace(0.0, DH, n_bins + 1)
+    inside = (pos[:, 1] >= edges[0]) & (pos[:, 1] <= edges[-1])
+    bin_id = np.minimum(np.searchsorted(edges, pos[:, 1], side="right") - 1, n_bins - 1)
+    word = dens_hist_bin(dz, n_hist, hist_range)
+    out = []
+    for mine in [inside] + [inside & in_band(pos[:, 0], DL, x, hw) for x, hw in bands]:
+        take, skip = mine & ok, mine & ~ok
+        d = {f: np.bincount(bin_id[take], weights=v[take], minlength=n_bins).astype(np.float64) for f, v in zip(DENS_SUMS, values)}
+        d["outliers"] = np.bincount(bin_id[skip], minlength=n_bins).astype(np.float64)
+        d_min, d_max = np.full(n_bins, np.inf), np.full(n_bins, -np.inf)
+        np.minimum.at(d_min, bin_id[take], delta[take])
+        np.maximum.at(d_max, bin_id[take], delta[take])
+        h_all = np.bincount(word[take], minlength=n_hist + 2).astype(np.int64)
+        d.update(d_min=d_min, d_max=d_max, hist=h_all[:n_hist], below=int(h_all[n_hist]), above=int(h_all[n_hist + 1]))
+        out.append(d)
+    return out
+
+
+def add_dens_stats(a, b):
+    """The sums of two samples, or of the same band of two channels, as one: the DENS_SUMS, the histogram, below and above added
+    (a first), the smaller d_min and the larger d_max."""
+    out = {f: np.asarray(a[f], dtype=np.float64) + np.asarray(b[f], dtype=np.float64) for f in DENS_SUMS}
+    out.update(d_min=np.minimum(a["d_min"], b["d_min"]), d_max=np.maximum(a["d_max"], b["d_max"]),
+               hist=np.asarray(a["hist"], dtype=np.int64) + np.asarray(b["hist"], dtype=np.int64),
+               below=int(a["below"]) + int(b["below"]), above=int(a["above"]) + int(b["above"]))
+    return out
+
+
+def dens_stats_profiles(DH, p0, sums, hist_range=None):
+    """The sums of one band (capi.Context.dens_stats_sums(band), dens_stats_sums(...)[band]) as profiles: y_mid, count, outliers
+    and per bin d_mean and d_std (sqrt(max(sum delta^2 / N - mean^2, 0))) of delta = rho / rho0 - 1 over the particle samples,
+    d_min, d_max, the pressure p_mean = p0 d_mean and p_std = p0 d_std, wall_mean (the walls' share of rho / rho0) and packing =
+    1 + sum dvol / N (the mean of rho0 / rho: the area the particles claim over the area they were given); NaN where a bin has
+    no sample.  hist_density: the band's histogram as a probability density over delta, hist / (N_band * bin width) with N_band
+    = sum(hist) + below + above, at hist_centres (hist_range: the sums' own where they carry it); NaN without a particle.
+    n_samples, t_first and t_last are handed on where the sums have them."""
+    s = {f: np.asarray(sums[f], dtype=np.float64).ravel() for f in DENS_FIELDS}
+    N = s["count"]
+    n_bins = len(N)
+    edges = np.linspace(0.0, DH, n_bins + 1)
+    empty = N == 0
+    Nd = np.where(empty, 1.0, N)
+    mean = s["sum_d"] / Nd
+    sd = np.sqrt(np.maximum(s["sum_d2"] / Nd - mean * mean, 0.0))
+    nan = np.nan
+    out = dict(y_mid=0.5 * (edges[:-1] + edges[1:]), count=N, outliers=s["outliers"],
+               d_mean=np.where(empty, nan, mean), d_std=np.where(empty, nan, sd),
+               d_min=np.where(empty, nan, s["d_min"]), d_max=np.where(empty, nan, s["d_max"]),
+               p_mean=np.where(empty, nan, p0 * mean), p_std=np.where(empty, nan, p0 * sd),
+               wall_mean=np.where(empty, nan, s["sum_wall"] / Nd), packing=np.where(empty, nan, 1.0 + s["sum_dvol"] / Nd))
+    hist = np.asarray(sums["hist"], dtype=np.float64).ravel()
+    hist_range = sums.get("hist_range") if hist_range is None else hist_range
+    if hist_range is not None:
+        width = 2.0 * float(hist_range) / len(hist)
+        total = float(hist.sum()) + float(sums["below"]) + float(sums["above"])
+        out["hist_centres"] = -float(hist_range) + width * (np.arange(len(hist)) + 0.5)
+        out["hist_density"] = hist / (total * width) if total > 0 else np.full(len(hist), nan)
+    for k in ("n_samples", "t_first", "t_last"):
+        if k in sums:
+            out[k] = sums[k]
+    return out
+
+
+def pool_dens_stats(DH, p0, sums_list, hist_range=None):
+    """The sums of the same band of several channels (the members of a batch or of an ensemble) as one profile: the DENS_SUMS, the
+    histogram, below and above added in member order, the smallest d_min and the largest d_max, turned into dens_stats_profiles
+    of the total (with the total's sums beside it); n_samples is the total over the members, t_first / t_last the earliest /
+    latest sample; n_members = M."""
+    sums_list = list(sums_list)
+    if not sums_list:
+        raise ValueError("pool_dens_stats needs the sums of at least one member")
+    first = sums_list[0]
+    total = {f: np.array(first[f], dtype=np.float64).ravel() for f in DENS_FIELDS}
+    total.update(hist=np.array(first["hist"], dtype=np.int64).ravel(), below=int(first["below"]), above=int(first["above"]))
+    for member in sums_list[1:]:
+        total = add_dens_stats(total, member)
+    n_samples, t_first, t_last = _window(sums_list)
+    total.update(n_samples=n_samples, t_first=t_first, t_last=t_last)
+    if hist_range is None:
+        hist_range = sums_list[0].get("hist_range")
+    if hist_range is not None:
+        total["hist_range"] = hist_range
+    out = dens_stats_profiles(DH, p0, total)
+    out.update({f: total[f] for f in DENS_FIELDS}, hist=total["hist"], below=total["below"], above=total["above"], n_members=len(sums_list))
+    return out
