@@ -1070,8 +1070,8 @@ int sphx_batch_tracers_read(sphx_batch *batch, int capacity, double *times, doub
  *    outside 0..2, a band centre or half-width that is not finite or a negative half-width, or the allocation fails: the
  *    context then goes on without density statistics), SPHX:DensStats:band, SPHX:DensStats:capacity (sums given and capacity <
  *    n_bins, or hist given and hist_capacity < n_hist), SPHX:DensStats:disabled (SPHX_ERR_STATE: a call that needs the sampler
- *    while it is off); every call on a slab context fails with SPHX_ERR_ARG, SPHX:DensStats:slab.  A refused enable leaves a
- *    running sampler, and its sums, untouched.
+ *    while it is off); every call on a slab context fails with SPHX_ERR_ARG, SPHX:DensStats:slab (the density statistics of a
+ *    ring: sphx_slab_dstats_*, section 3a).  A refused enable leaves a running sampler, and its sums, untouched.
  * ---------------------------------------------------------------------------------------------- */
 
 #define SPHX_DENS_STATS_FIELDS 8
@@ -1202,7 +1202,8 @@ int sphx_slab_snapshot(sphx_ctx *ctx, int capacity, int *n, double *x, double *y
 /* ------------------------------------------------------------------------------------------------
  * 3a. Samplers of a slab ring: the flow statistics of section 2a, the step history of section 2d, the velocity-field
  *    map of section 2e, the point probes of section 2h, the profile series of section 2j, the pair statistics of
- *    section 2l, the gradient statistics of section 2n and the particle tracers of section 2p (the last five described with their calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that
+ *    section 2l, the gradient statistics of section 2n, the particle tracers of section 2p and the density statistics of
+ *    section 2r (the last six described with their calls, at the end) for the slabs of the library's own loops (sphx_slab_run, sphx_slab_group_run), so that
  *    a ring reports its time-averaged profile, the settling of its wall shear, its averaged field and its profile at every
  *    sampled step without a snapshot per sample.  The config structs, their checks, the layouts and the SPHX:Stats:* / SPHX:History:* / SPHX:Field:*
  *    identifiers are those of sections 2a / 2d / 2e; sphx_ctx_flow_stats_*,
@@ -1385,6 +1386,34 @@ int sphx_slab_tracers_disable(sphx_ctx *ctx);
  * with NaN again after copying.  Waits for the slab's stream(s) itself. */
 int sphx_slab_tracers_read(sphx_ctx *ctx, int capacity, double *times, double *values, int64_t *n_owned, int32_t *ids,
                            int *n_tracers, int *n_records, int64_t *n_dropped, int drain);
+/* Density statistics of a ring (the sampler of section 2r; k_dens_stats_s).  The names say dstats: no function of this header
+ * has both "slab" and "dens" in its name.  The config, its checks and limits, the bins, the histogram, the gating and the
+ * SPHX:DensStats:* identifiers are those of section 2r.  A sample is a sum over particles, so it is divided like the flow
+ * statistics': a slab bins, at the end of a sampled step, the re-summed densities of the fluid particles it owns (those
+ * sphx_slab_snapshot marks owned, with 0 <= y <= DH), and what a read returns are the slab's PARTIAL sums -- the ring's count,
+ * outliers, four summed fields, histogram, below and above are the element-wise sums over the ranks, its d_min the smallest and
+ * its d_max the largest of the ranks' (+inf / -inf on a slab that has summed no particle of the bin); n_samples, t_first and
+ * t_last come from the clock and are the same on every rank, also on a slab that owns no particle of a band.  The PARTNERS of
+ * a particle are all the other fluid particles the slab holds, its halo copies included, and the wall particles the slab holds,
+ * always.  Of a partner only the position is read -- in the cell columns next to the owned ones a copy carries the finished
+ * step's position up to the summation order of its own neighbour lists, a few ulps -- and of the particle itself its position
+ * and its mass: nothing is asked of a copy's mass or velocity.  The slab's window is open: the first slab holds the last slab's
+ * particles at x - DL and the last slab the first slab's at x + DL, so a partner across the periodic seam enters with its plain
+ * dx and no minimum image; a ring is at least 20h long, so no copy is a particle's own image within 2h.  Band membership goes
+ * by x mod DL, whatever frame a slab keeps x in.  2^e >= delta_bound, which decides between summed and outlier, comes from the
+ * config and is the same on every rank; the fixed-point quantum comes from the number of particles the slab holds and is the
+ * slab's own.  A density is continuous in the copies' positions, so a ring's sums equal a single context's within the copies'
+ * few ulps times the slope of W, not to the last bits; count, outliers and the histogram are equal wherever no particle sits
+ * at a bin, band or histogram edge or at the bound.  A refused enable leaves a running sampler, its sums and a prepared graph
+ * as they are.  SPHX:DensStats:disabled: a reset or a read while the sampler is off; disable is a no-op then.  There is no
+ * "sample now" call.  sphx_ctx_dens_stats_* keep refusing a slab (SPHX:DensStats:slab). */
+int sphx_slab_dstats_enable(sphx_ctx *ctx, const sphx_dens_stats_config *cfg);
+int sphx_slab_dstats_disable(sphx_ctx *ctx);
+/* Clears the sums, the extremes, the histogram and the sample count; the configuration stays. */
+int sphx_slab_dstats_reset(sphx_ctx *ctx);
+/* The slab's partial sums of one band; arguments as sphx_ctx_dens_stats_read. */
+int sphx_slab_dstats_read(sphx_ctx *ctx, int band, int capacity, int hist_capacity, int *n_bins, int *n_hist, double *sums,
+                          int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first, double *t_last);
 
 #ifdef __cplusplus
 }

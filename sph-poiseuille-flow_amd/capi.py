@@ -142,6 +142,7 @@ EXPORTS = [
     "sphx_slab_pairs_enable", "sphx_slab_pairs_disable", "sphx_slab_pairs_reset", "sphx_slab_pairs_read",
     "sphx_slab_gstats_enable", "sphx_slab_gstats_disable", "sphx_slab_gstats_reset", "sphx_slab_gstats_read",
     "sphx_slab_tracers_enable", "sphx_slab_tracers_disable", "sphx_slab_tracers_read",
+    "sphx_slab_dstats_enable", "sphx_slab_dstats_disable", "sphx_slab_dstats_reset", "sphx_slab_dstats_read",
     "sphx_batch_create", "sphx_batch_destroy", "sphx_batch_advance", "sphx_batch_enqueue_steps", "sphx_batch_sync",
     "sphx_batch_download", "sphx_batch_monitor", "sphx_batch_info", "sphx_batch_graph_stats",
     "sphx_batch_flow_stats_enable", "sphx_batch_flow_stats_disable", "sphx_batch_flow_stats_reset",
@@ -257,14 +258,15 @@ _STATE = ("pos", "vel", "drho_dt", "mass", "wall_vel")
 
 class _Sampled:
     """What a context, a batch and a slab of a ring bind alike: the flow statistics' sums, the step history's records, the
-    profile series' raw records and the pair and gradient statistics' sums.  A subclass names its symbol stem, the words its
-    profile-series, pair-statistics and gradient-statistics calls carry behind the stem (a slab's are sphx_slab_pseries_*,
-    sphx_slab_pairs_* and sphx_slab_gstats_*), the word of its "not enabled on this ..." errors and whether it has many
-    channels: a context or a slab returns one dict / (records, n_dropped) pair, a batch a list with one entry per member."""
+    profile series' raw records and the pair, gradient and density statistics' sums.  A subclass names its symbol stem, the words
+    its profile-series, pair-, gradient- and density-statistics calls carry behind the stem (a slab's are sphx_slab_pseries_*,
+    sphx_slab_pairs_*, sphx_slab_gstats_* and sphx_slab_dstats_*), the word of its "not enabled on this ..." errors and whether it
+    has many channels: a context or a slab returns one dict / (records, n_dropped) pair, a batch a list with one entry per member."""
     _stem = _where = None
     _series = "profile_series_"
     _pairs = "pair_dist_"
     _grads = "grad_stats_"
+    _dens = "dens_stats_"
     _many = False
 
     def _call(self, name, *args):
@@ -472,6 +474,48 @@ class _Sampled:
         for k in range(m):
             d = {f: sums[k, j].copy() for j, f in enumerate(GRAD_FIELDS)}
             d.update(n_samples=int(ns[k]), t_first=float(t0[k]), t_last=float(t1[k]))
+            out.append(d)
+        return out
+
+    # ---- density statistics (include/sphx.h sections 2r, 2s, 3a): what dens_stats_* of a context or a batch and dens_part_* of a
+    # slab (slab.HipSlabEngine) share -- the argument checks, the calls behind the stem and the read of the sums ----
+    def _dens_enable(self, n_bins, every, t_from, n_hist, hist_range, delta_bound, bands):
+        p0 = self._params0()
+        cfg = dens_stats_config(p0, n_bins, every, t_from, n_hist, hist_range, delta_bound, bands)
+        self._call(self._dens + "enable", C.byref(cfg))
+        # (n_bins, n_bands incl. band 0, n_hist, hist_range) while the density statistics are on
+        self._dens_stats = (int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5))), int(cfg.n_bands) + 1, int(cfg.n_hist),
+                            float(cfg.hist_range))
+
+    def _dens_disable(self):
+        self._call(self._dens + "disable")
+        self._dens_stats = None
+
+    def _dens_on(self):
+        return _enabled(getattr(self, "_dens_stats", None), "DensStats", f"density statistics are not enabled on this {self._where}")
+
+    def _dens_reset(self):
+        self._dens_on()
+        self._call(self._dens + "reset")
+
+    def _dens_stats_band(self, band):
+        """one band's raw sums: one dict per channel"""
+        n_bins, n_bands, n_hist, hist_range = self._dens_on()
+        if not _is_int(band) or not 0 <= band < n_bands:
+            raise SphxError(SPHX_ERR_ARG, "SPHX:DensStats:band", f"band must be an integer in 0..{n_bands - 1}")
+        out = []
+        for k in range(self._channels()):
+            sums, hist = np.zeros((len(DENS_FIELDS), n_bins)), np.zeros(n_hist, dtype=np.int64)
+            below, above, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+            t0, t1, nb, nh = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0)
+            member = (C.c_int(k),) if self._many else ()
+            self._call(self._dens + "read", *member, C.c_int(int(band)), C.c_int(n_bins), C.c_int(n_hist), C.byref(nb), C.byref(nh),
+                       ptr(sums), hist.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(below), C.byref(above), C.byref(ns), C.byref(t0),
+                       C.byref(t1))
+            assert (nb.value, nh.value) == (n_bins, n_hist), (nb.value, nh.value, n_bins, n_hist)
+            d = {f: sums[j].copy() for j, f in enumerate(DENS_FIELDS)}
+            d.update(hist=hist, below=int(below.value), above=int(above.value), hist_range=hist_range, n_samples=int(ns.value),
+                     t_first=float(t0.value), t_last=float(t1.value))
             out.append(d)
         return out
 
@@ -775,23 +819,13 @@ class _Stepped(_Sampled):
         per band a histogram of delta in n_hist bins on [-hist_range, hist_range).  A particle with |delta| > delta_bound is
         counted in `outliers`.  (Re)configures and zeroes the sums.  A batch: one config for all members, each sampled on its
         own clock."""
-        p0 = self._params0()
-        cfg = dens_stats_config(p0, n_bins, every, t_from, n_hist, hist_range, delta_bound, bands)
-        self._call("dens_stats_enable", C.byref(cfg))
-        # (n_bins, n_bands incl. band 0, n_hist, hist_range) while the density statistics are on
-        self._dens_stats = (int(cfg.n_bins) or max(20, int(np.floor(p0.DH / p0.dp + 0.5))), int(cfg.n_bands) + 1, int(cfg.n_hist),
-                            float(cfg.hist_range))
+        self._dens_enable(n_bins, every, t_from, n_hist, hist_range, delta_bound, bands)
 
     def dens_stats_disable(self):
-        self._call("dens_stats_disable")
-        self._dens_stats = None
-
-    def _dens_on(self):
-        return _enabled(getattr(self, "_dens_stats", None), "DensStats", f"density statistics are not enabled on this {self._where}")
+        self._dens_disable()
 
     def dens_stats_reset(self):
-        self._dens_on()
-        self._call("dens_stats_reset")
+        self._dens_reset()
 
     def dens_stats_sample(self):
         """Add one sample of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
@@ -802,23 +836,7 @@ class _Stepped(_Sampled):
         """The raw sums of one band: the eight profile.DENS_FIELDS as [n_bins] arrays (count and outliers hold integers; d_min /
         d_max are +inf / -inf in a bin without a particle), hist [n_hist] (int64), below, above, hist_range, n_samples, t_first,
         t_last; a batch: one such dict per member."""
-        n_bins, n_bands, n_hist, hist_range = self._dens_on()
-        if not _is_int(band) or not 0 <= band < n_bands:
-            raise SphxError(SPHX_ERR_ARG, "SPHX:DensStats:band", f"band must be an integer in 0..{n_bands - 1}")
-        out = []
-        for k in range(self._channels()):
-            sums, hist = np.zeros((len(DENS_FIELDS), n_bins)), np.zeros(n_hist, dtype=np.int64)
-            below, above, ns = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-            t0, t1, nb, nh = C.c_double(0.0), C.c_double(0.0), C.c_int(0), C.c_int(0)
-            member = (C.c_int(k),) if self._many else ()
-            self._call("dens_stats_read", *member, C.c_int(int(band)), C.c_int(n_bins), C.c_int(n_hist), C.byref(nb), C.byref(nh), ptr(sums),
-                       hist.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(below), C.byref(above), C.byref(ns), C.byref(t0), C.byref(t1))
-            assert (nb.value, nh.value) == (n_bins, n_hist), (nb.value, nh.value, n_bins, n_hist)
-            d = {f: sums[j].copy() for j, f in enumerate(DENS_FIELDS)}
-            d.update(hist=hist, below=int(below.value), above=int(above.value), hist_range=hist_range, n_samples=int(ns.value),
-                     t_first=float(t0.value), t_last=float(t1.value))
-            out.append(d)
-        return self._each(out)
+        return self._each(self._dens_stats_band(band))
 
     def dens_stats(self, band=0):
         """One band's profiles (profile.dens_stats_profiles): y_mid, count, outliers, d_mean, d_std, d_min, d_max, p_mean, p_std,

@@ -1,5 +1,5 @@
-// sphx_dens_stats.hpp -- density statistics of a resident context (include/sphx.h section 2r) and of every member of a batch
-// (section 2s, k_dens_stats_b): a slot sampler (sphx_slot_sample.hpp) that re-sums, from positions and masses alone, the
+// sphx_dens_stats.hpp -- density statistics of a resident context (include/sphx.h section 2r), of every member of a batch
+// (section 2s, k_dens_stats_b) and of a slab of a ring (section 3a, k_dens_stats_s, at the end): a slot sampler (sphx_slot_sample.hpp) that re-sums, from positions and masses alone, the
 // density the next step will start from at every fluid particle, and bins the relative deviation delta = rho / rho0 - 1, its
 // square, the volume defect rho0 / rho - 1 and the walls' share of rho / rho0 into the flow statistics' y-bins and x-bands, with
 // the running extremes of delta per bin and a histogram of delta per band.  The one sampler that describes the STATE of
@@ -123,6 +123,9 @@ __device__ __forceinline__ double dens_value(int k, int n_binned, unsigned long 
 // The sample of one channel closing the step slot of parity q, on clock clk, by the gridDim.x workgroups of a grid row; s is the
 // state the step left (pos, mass and the cell ranges and binned cells of the layout it is stored in); isum / dsum / keys / h are
 // that channel's own.
+// kSlab: the channel is a slab of a ring -- of the clk->n slots it holds only those it owns (owns()) are particles of the
+// sample, every held slot is a partner (k_dens_stats_s).
+template <bool kSlab = false>
 __device__ __forceinline__ void dens_stats_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s, const Walls &w,
                                                 const DensStatsArgs &a, unsigned long long *isum, double *dsum, unsigned long long *keys,
                                                 DensStatsHead *h)
@@ -143,6 +146,9 @@ __device__ __forceinline__ void dens_stats_body(const Clock *clk, int q, const G
     for (long long i0 = (long long)blockIdx.x * kDensCentres + grp; i0 < (long long)n; i0 += (long long)gridDim.x * kDensCentres) {
         const int i = (int)i0;
         const double2 pi = s.pos[i];
+        if constexpr (kSlab) {
+            if (!owns(g, pi.x, s.cell[i])) continue;  // (a halo copy: its owner bins it)
+        }
         if (!(pi.y >= 0.0 && pi.y <= a.DH)) continue;  // outside [0, DH]: dropped, as discretize does
         int cx, cy;
         binned_cell(g, s, i, cx, cy);
@@ -245,6 +251,50 @@ __global__ __launch_bounds__(kDensBlock) void k_dens_stats_b(Members mb, int q, 
     const Phys ph = mb.ph[m];
     const size_t off = (size_t)m * (size_t)a.block, koff = (size_t)m * (size_t)a.kblock;
     dens_stats_body(mb.clk + m, q, g, ph, member_set(mb, m, s), w, a, a.isum + off, a.dsum + off, a.keys + koff, a.head + m);
+}
+
+// Slab of a ring (sphx_slab_dstats_*): the sample is a sum over PARTICLES, so it is divided like the flow statistics' -- a slab
+// bins the densities of the particles it OWNS (owns(): the column the slot was binned into, own_c0 <= cx < own_c1) and the
+// ring's sums and histograms are the element-wise sums of the slabs', count and outliers included, its d_min / d_max their
+// minimum / maximum.  Nothing about a particle's density changes: the two sums, density_from_sigma, the quantisation, the keys,
+// the LDS counters and stats_finish_sample are the body's.  The loop runs over the clk->n slots held, owned and copies alike,
+// with the workgroups of the slab's CAPACITY (a captured step graph outlives a re-binning); a copy is passed over as a particle
+// of the sample and met as a partner: every held fluid slot j != i in the columns cx - 1 .. cx + 1 of the layout's cell ranges,
+// and -- always, there is no with_walls here -- the slab's wall particles in the same columns (Walls::pos, Walls::a.x).
+//
+// Why the three-column sweep still suffices.  The argument of sphx_pair_dist.hpp is about the columns a particle and its
+// partner were BINNED into, and a slab bins what it holds, copies included, into one grid of its window (Grid::periodic = 0:
+// neighbour_column leaves out only columns beyond the window).  An owned particle has own_c0 <= cx < own_c1, so cx - 1 and
+// cx + 1 lie in [own_c0 - 1, own_c1]: at most the FIRST halo column on either side, of the halo_cols >= 4 the window holds.
+// The slab's wall particles are binned into the same grid and cover the whole window, halo columns included.
+//
+// Why the halo copies are usable.  Of a partner only the POSITION is read -- a fluid partner contributes W(r_ij), a wall
+// partner W(r_ij) V_j with the wall's own volume -- and of the particle itself pos and mass_i, which is an owned slot's: the
+// density is mass_i times a number density, so nothing is asked of a copy's mass or velocity.  The copies binned in own - 1 and
+// own + 1 are complete and were stepped like everything held: in front of phase 3 -- where launch_slab_samplers sits, behind
+// k_slab_pack3 -- they carry the finished step's position up to the summation order of their own neighbour lists, the premise
+// k_pair_dist_s counts pairs on.  Unlike a count, W(r) is continuous in the copy's position: a copy that is a few ulps off
+// moves its partners' densities by as little, amplified by the slope of W (tests/slab_dens_stats_cases.py: SENSITIVITY); a
+// MISSING copy, or one a period off, changes every partner's density by a whole W(r).
+//
+// The window is open (half_DL = +inf: min_image is a no-op).  The first slab holds the last slab's particles at x - DL and the
+// last slab the first slab's at x + DL, in the slab's own frame, so a pair across the periodic seam has its plain dx: there
+// is nothing to fold.  A copy is never the particle's own image within 2h: the image lies DL away, and a ring needs
+// n_ranks >= 2 slabs of at least halo_cols + 1 >= 5 columns of >= 2h each (SPHX:Slab:width), so DL >= 20h; nor does one
+// window hold a partner twice, because it covers less than one period (SPHX:Slab:width).  Band membership goes by
+// stats_in_band on the slab-frame x, whose fmod brings x < 0 and x >= DL back into [0, DL), as k_flow_stats_s relies on.
+//
+// The scales.  e comes from the configuration's delta_bound and is every rank's: whether a particle is summed or an outlier
+// is decided the same way on every rank.  L comes from the held count clk->n, which bounds the owned count, so no overflow; it
+// differs between the slabs, and with it only the fixed-point quantum a slab rounds to.  The keys of d_min / d_max are exact.
+//
+// Every slab finishes the sample (stats_finish_sample: the last workgroup out, or the one workgroup of a small slab) and
+// stamps its head, whether or not it owns a particle of any band: n_samples, t_first and t_last come from the clock and agree
+// between the ranks.  The dynamic LDS is k_dens_stats's, up to kDensMaxShmem, which a launch is granted without an attribute
+// of the kernel symbol (k_flow_stats_s asks for as much).
+__global__ __launch_bounds__(kDensBlock) void k_dens_stats_s(const Clock *clk, int q, Grid g, Phys ph, FluidSet s, Walls w, DensStatsArgs a)
+{
+    dens_stats_body<true>(clk, q, g, ph, s, w, a, a.isum, a.dsum, a.keys, a.head);
 }
 
 }  // namespace sphx

@@ -1,8 +1,8 @@
 // sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
 // the velocity-field map (2e; 2g), the point probes (2h; 2i), the profile series (2j; 2k), the pair statistics (2l; 2m,
-// sphx_pair_dist.hpp), the gradient statistics (2n; 2o, sphx_grad_stats.hpp) and the particle tracers (2p; 2q, sphx_tracers.hpp) --
-// all eight also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// sphx_pair_dist.hpp), the gradient statistics (2n; 2o, sphx_grad_stats.hpp), the particle tracers (2p; 2q, sphx_tracers.hpp) and
+// the density statistics (2r; 2s, sphx_dens_stats.hpp) -- all nine also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -37,7 +37,7 @@ constexpr SamplerNames kGradNames{"GradStats", "the gradient statistics of a sla
                                   "gradient statistics are not enabled on this ", "the sums could not be set up: "};
 constexpr SamplerNames kTracerNames{"Tracers", "the tracers of a slab are sphx_slab_tracers_* (include/sphx.h section 3a)",
                                     "particle tracers are not enabled on this ", "the record buffer could not be set up: "};
-constexpr SamplerNames kDensNames{"DensStats", "density statistics are not available on slab contexts",
+constexpr SamplerNames kDensNames{"DensStats", "the density statistics of a slab are sphx_slab_dstats_* (include/sphx.h section 3a)",
                                   "density statistics are not enabled on this ", "the sums could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
@@ -1689,6 +1689,10 @@ SPHX_EXPORT int sphx_ctx_dens_stats_read(sphx_ctx *c, int band, int capacity, in
 // takes its partners from every slot the slab holds, halo copies included -- their positions, velocities and masses (the field
 // map's and the probes' premises) -- and the ring's sums are the slabs' added up, count and skipped included
 // (sphx_slab_gstats_*: no function of include/sphx.h carries both "slab" and "grad" in its name).
+// The density statistics: the gradient statistics' reasoning -- a slab bins the re-summed densities of the particles it owns; a
+// density takes its partners' POSITIONS from every slot the slab holds, halo copies included (the pair statistics' premise),
+// and the slab's wall particles, always; the ring's sums and histograms are the slabs' added up, d_min / d_max their minimum /
+// maximum (sphx_slab_dstats_*: no function of include/sphx.h carries both "slab" and "dens" in its name).
 // The particle tracers: the one sampler whose subject moves between the slabs.  A slab copies the tracked particles it OWNS at
 // the sampled step -- the ring's id list and table on every rank, dense rows, NaN where it was not the owner -- and counts
 // them per record (n_owned); every fluid row has one owner at every step, so the ring's record is each column taken from the
@@ -1701,11 +1705,12 @@ namespace {
 // Vol / B (c->tmp) and the layout arrays (cell, mass) are those of the layout the step ran in -- clk->n is still that
 // layout's count (k_slab_unpack3 sets the new one), so a re-binning step needs no src_of.  One self-skipping launch each,
 // on the slab's stream, in the order statistics, history, map, probes, profile series, pair statistics, gradient statistics,
-// tracers;
+// tracers, density statistics;
 // all off: nothing is enqueued, and a sampler that is off adds nothing to what the others enqueue.
 void launch_slab_samplers(sphx_ctx *c)
 {
-    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on && !c->pseries.on && !c->pairs.on && !c->grads.on && !c->tracers.on)
+    if (!c->fstats.on && !c->hist.on && !c->fmap.on && !c->probes.on && !c->pseries.on && !c->pairs.on && !c->grads.on && !c->tracers.on &&
+        !c->dens.on)
         return;
     const int q = c->sched.cur;
     const Clock *clk = c->clock.get();
@@ -1761,6 +1766,12 @@ void launch_slab_samplers(sphx_ctx *c)
         launch_s(c, "k_tracers_s", k_tracers_s, dim3(tracer_blocks((size_t)c->cap)), dim3(kTracerBlock), 0, clk, q, s, a, c->grid,
                  c->tracers.n_owned.get());
     }
+    // (pos, the binned cells and the cell ranges of S[1-q], the halo copies in own - 1 and own + 1 as for the pair statistics;
+    //  MASS of the owned slot alone; the slab's wall particles always; the particles of the sample are the owned slots of the
+    //  clk->n held, so the workgroups come from the capacity)
+    if (c->dens.on)
+        launch_s(c, "k_dens_stats_s", k_dens_stats_s, dim3(dens_stats_blocks((size_t)c->cap)), dim3(kDensBlock), c->dens.shmem(), clk, q,
+                 c->grid, c->phys, s, c->walls, dens_stats_args(c, c->dens.cfg.every));
 }
 
 // The rank of slab c's ring that owns a probe at x, folded into [0, DL): rank r when edge(r) <= x < edge(r + 1), with
@@ -2126,6 +2137,51 @@ SPHX_EXPORT int sphx_slab_gstats_read(sphx_ctx *c, int band, int capacity, int *
     SPHX_TRY
     const GradStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::grads, kGradNames);
     grad_stats_read(f, c->stream, [c] { slab_settle(c); }, band, capacity, n_bins, sums, n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_dstats_enable(sphx_ctx *c, const sphx_dens_stats_config *cfg)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    DensStats checked;
+    checked.check(c->prm, cfg);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
+    slab_samplers_changed(c);
+    dens_stats_enable(c->dens, c->prm, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_dstats_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampled_slab(c);
+    if (c->dens.on) {
+        slab_samplers_changed(c);
+        sampler_off(c->dens, c->sched, c->stream);
+    }
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_dstats_reset(sphx_ctx *c)
+{
+    SPHX_TRY
+    DensStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::dens, kDensNames);
+    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
+    sampler_zero(f, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_slab_dstats_read(sphx_ctx *c, int band, int capacity, int hist_capacity, int *n_bins, int *n_hist, double *sums,
+                                      int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first, double *t_last)
+{
+    SPHX_TRY
+    const DensStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::dens, kDensNames);
+    dens_stats_read(f, c->stream, [c] { slab_settle(c); }, 0, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above,
+                    n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -14,6 +14,8 @@ pair_histogram_part: the sample of one slab of a ring (the centres it owns again
 velocity_gradients: the renormalised velocity-gradient estimate of the device's gradient statistics (include/sphx.h section 2n)
 in numpy; grad_stats_sums: one binned sample; grad_stats_profiles: the sums as profiles; pool_grad_stats: several channels' as one;
 grad_stats_sums_part: the sample of one slab of a ring (the particles it owns, estimated from everything it holds).
+summation_density: the density of the device's density statistics (include/sphx.h section 2r) in numpy (fold=False: the open
+window of a slab); dens_stats_sums: one binned sample; dens_stats_sums_part: the sample of one slab of a ring.
 """
 from __future__ import annotations
 
@@ -771,7 +773,7 @@ def pool_tracers(tr_list):
     return out
 
 
-# ---- density statistics (include/sphx.h sections 2r, 2s): the state of compression ----
+# ---- density statistics (include/sphx.h sections 2r, 2s, 3a): the state of compression ----
 
 # the eight values per bin and band, in the order the library writes them; the first six add up over samples and channels
 DENS_FIELDS = ("count", "sum_d", "sum_d2", "sum_dvol", "sum_wall", "outliers", "d_min", "d_max")
@@ -780,7 +782,8 @@ DENS_MAX_HIST = 1024
 DENS_MAX_WORDS = 7680  # (n_bands + 1) * (8 * n_bins + n_hist + 2): the 60 KB of LDS of a workgroup
 
 
-def summation_density(pos, mass, DL, h, rho0, inv_sigma0, wall_pos=None, wall_vol=None, chunk=512, acc=np.float64, reverse=False):
+def summation_density(pos, mass, DL, h, rho0, inv_sigma0, wall_pos=None, wall_vol=None, chunk=512, acc=np.float64, reverse=False,
+                      fold=True):
     """The summation density of every fluid particle as the step's first pass computes it, in numpy -- the definition
     k_dens_stats is tested against (include/sphx.h section 2r).  pos [n, 2] and mass [n] (or one number): the fluid particles;
     wall_pos [m, 2] and wall_vol [m]: the wall particles and their volumes, or None.  Over every fluid partner j != i and every
@@ -790,24 +793,27 @@ def summation_density(pos, mass, DL, h, rho0, inv_sigma0, wall_pos=None, wall_vo
     share of rho_i / rho0.  Chunked over particles sorted by x, a chunk against the partners within 2h of its x-range.  acc /
     reverse exist for the tests alone: the type the per-particle sums are accumulated in and whether the partners are added in
     reversed order, which together measure the rounding error of these sums (tests/dens_stats_cases.py); no caller in the
-    package sets them."""
+    package sets them.  fold=False: the OPEN window of a slab of a ring (dens_stats_sums_part) -- x is taken as it stands, dx =
+    x_i - x_j with no nearest image, and DL is not used."""
     pos = np.asarray(pos, dtype=np.float64).reshape(-1, 2)
     n = len(pos)
     mass = np.broadcast_to(np.asarray(mass, dtype=np.float64), (n,))
     sigma, rcut2, half = 10.0 / (7.0 * np.pi * h * h), (2.0 * h) * (2.0 * h), DL / 2
     margin = 2.0 * h * (1.0 + 1e-9) + 1e-12 * DL
     S = np.zeros((2, n), dtype=acc)  # s_in without W(0), s_ct
-    cx = np.mod(pos[:, 0], DL)
+    cx = np.mod(pos[:, 0], DL) if fold else pos[:, 0]
     order_c = np.argsort(cx, kind="stable")
 
     def sweep(p_pos, p_vol, same, row):
-        px = np.mod(p_pos[:, 0], DL)
+        px = np.mod(p_pos[:, 0], DL) if fold else p_pos[:, 0]
         order_p = np.argsort(px, kind="stable")
         pxs = px[order_p]
         for a in range(0, n, chunk):
             ci = order_c[a:a + chunk]
             lo, hi = cx[ci[0]] - margin, cx[ci[-1]] + margin
-            if hi - lo >= DL:
+            if not fold:
+                cand = np.sort(order_p[np.searchsorted(pxs, lo, "left"):np.searchsorted(pxs, hi, "right")])
+            elif hi - lo >= DL:
                 cand = np.sort(order_p)
             else:
                 parts = [order_p[np.searchsorted(pxs, lo, "left"):np.searchsorted(pxs, hi, "right")]]
@@ -819,7 +825,8 @@ def summation_density(pos, mass, DL, h, rho0, inv_sigma0, wall_pos=None, wall_vo
             if reverse:
                 cand = cand[::-1]
             dx = pos[ci, 0][:, None] - p_pos[cand, 0][None, :]
-            dx = np.where(dx > half, dx - DL, np.where(dx < -half, dx + DL, dx))
+            if fold:
+                dx = np.where(dx > half, dx - DL, np.where(dx < -half, dx + DL, dx))
             dy = pos[ci, 1][:, None] - p_pos[cand, 1][None, :]
             r2 = dx * dx + dy * dy
             keep = (r2 > 1e-24) & (r2 < rcut2)
@@ -876,8 +883,14 @@ def dens_stats_sums(pos, mass, DL, DH, h, rho0, inv_sigma0, n_bins, bands=(), n_
     caller in the package sets it): every particle's terms are rounded to the device's fixed-point grid of dens_scales before
     they are added, as k_dens_stats rounds them."""
     pos = np.asarray(pos, dtype=np.float64).reshape(-1, 2)
-    n = len(pos)
     rho, wall = density if density is not None else summation_density(pos, mass, DL, h, rho0, inv_sigma0, wall_pos, wall_vol)
+    return _dens_stats_binned(pos, rho, wall, None, DL, DH, rho0, n_bins, bands, n_hist, hist_range, delta_bound, quantise)
+
+
+def _dens_stats_binned(pos, rho, wall, rows, DL, DH, rho0, n_bins, bands, n_hist, hist_range, delta_bound, quantise):
+    """the densities (rho, wall) of the particles pos (rows: those that are binned, None: all of them) as one sample's sums per
+    band; the scales are those of len(pos) particles"""
+    n = len(pos)
     rho, wall = np.asarray(rho, dtype=np.float64), np.asarray(wall, dtype=np.float64)
     delta = rho / rho0 - 1.0
     with np.errstate(invalid="ignore"):
@@ -892,6 +905,8 @@ def dens_stats_sums(pos, mass, DL, DH, h, rho0, inv_sigma0, n_bins, bands=(), n_
         values = [np.ldexp(np.rint(np.ldexp(v, k)), -k) for v, k in zip(values, shifts)]
     edges = np.linspace(0.0, DH, n_bins + 1)
     inside = (pos[:, 1] >= edges[0]) & (pos[:, 1] <= edges[-1])
+    if rows is not None:
+        inside &= np.asarray(rows, dtype=bool)
     bin_id = np.minimum(np.searchsorted(edges, pos[:, 1], side="right") - 1, n_bins - 1)
     word = dens_hist_bin(dz, n_hist, hist_range)
     out = []
@@ -906,6 +921,20 @@ def dens_stats_sums(pos, mass, DL, DH, h, rho0, inv_sigma0, n_bins, bands=(), n_
         d.update(d_min=d_min, d_max=d_max, hist=h_all[:n_hist], below=int(h_all[n_hist]), above=int(h_all[n_hist + 1]))
         out.append(d)
     return out
+
+
+def dens_stats_sums_part(pos, mass, owned, DL, DH, h, rho0, inv_sigma0, n_bins, bands=(), n_hist=64, hist_range=0.05, delta_bound=0.5,
+                         wall_pos=None, wall_vol=None, quantise=False):
+    """One sample of a SLAB's density statistics (include/sphx.h section 3a) in numpy -- the oracle of k_dens_stats_s.  pos [n, 2]
+    and mass: every fluid particle the slab holds, in the slab's own frame (its halo copies at x - DL or x + DL where they come
+    from across the seam); owned [n] bool: the rows it bins.  The density of an owned row takes every other row and the wall
+    particles the slab holds (wall_pos, wall_vol, in the same frame) as partners, with dx = x_i - x_j as it stands and no fold:
+    the window is open (summation_density(fold=False)).  Bands go by in_band, whose mod brings x < 0 and x >= DL back.  The
+    scales are those of the n rows HELD (dens_scales(delta_bound, n)).  -> dens_stats_sums' list of dicts, the slab's partial
+    sums: slab.pool_ring_dens_stats of the ranks' gives the channel's."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 2)
+    rho, wall = summation_density(pos, mass, DL, h, rho0, inv_sigma0, wall_pos, wall_vol, fold=False)
+    return _dens_stats_binned(pos, rho, wall, owned, DL, DH, rho0, n_bins, bands, n_hist, hist_range, delta_bound, quantise)
 
 
 def add_dens_stats(a, b):

@@ -15,7 +15,7 @@ Layers:
   HipSlabEngine    -- the per-rank compute engine (libsphx slab context)
   SlabDriver       -- step loop = engine.compute -> exchange -> engine.finish
   pool_ring_* / ring_* / all_reduce_ring_*
-                   -- the ring's flow statistics, step history, profile series, pair statistics and gradient statistics from
+                   -- the ring's flow statistics, step history, profile series, pair, gradient and density statistics from
                       the slabs' partial sums, its field map from the slabs' blocks of node columns, and its point probes from the slabs'
                       owned probes
   bench_main()     -- bench.py's multi-GPU leg
@@ -31,7 +31,8 @@ import time
 import numpy as np
 
 from . import capi as _capi
-from .profile import (FIELD_MAP_PLANES, GRAD_FIELDS, field_map_means, flow_stats_profile, grad_stats_profiles, pair_dist_profiles,
+from .profile import (DENS_FIELDS, DENS_SUMS, FIELD_MAP_PLANES, GRAD_FIELDS, dens_stats_profiles, field_map_means, flow_stats_profile,
+                      grad_stats_profiles, pair_dist_profiles,
                       profile_series_profiles)
 
 HALO_COLS = 4  # four dependent neighbour passes per step, each reaching one >=2h column further
@@ -141,8 +142,13 @@ class HipSlabEngine(_capi._Sampled):
     with the particle, so a slab records, of the ring's id list, the tracked particles it OWNS at each sampled step -- dense
     records, NaN where it was not the owner, n_owned per record -- a PART of the ring's series, which pool_ring_tracers
     (ring_tracers, all_reduce_ring_tracers) puts together by taking every column from the one rank that wrote it; the engine
-    has no tracers_enable / tracers / tracers_sample.  Enabling or disabling drops a graph made by graph_prepare()."""
-    _stem, _where, _series, _pairs, _grads = "sphx_slab_", "slab", "pseries_", "pairs_", "gstats_"
+    has no tracers_enable / tracers / tracers_sample.
+    dens_part_enable / _disable / _reset / dens_part_sums are the density statistics (over sphx_slab_dstats_*): the re-summed
+    densities of the particles this slab OWNS, their partners' positions taken from everything it holds, its wall particles
+    always in -- partial sums, which pool_ring_dens_stats (ring_dens_stats_sums / ring_dens_stats, all_reduce_ring_dens_stats)
+    adds up, taking the smallest d_min and the largest d_max; means of partial sums would mislead, so the engine has no
+    dens_stats().  Enabling or disabling drops a graph made by graph_prepare()."""
+    _stem, _where, _series, _pairs, _grads, _dens = "sphx_slab_", "slab", "pseries_", "pairs_", "gstats_", "dstats_"
 
     def __init__(self, prm, parts, rank, world, device, lanes_per_particle=0, halo_cols=HALO_COLS, t_end=None,
                  pos=None, vel=None, drho_dt=None, native=False, rebuild_every=0, skin_h=0.0, hip_stream=None):
@@ -156,6 +162,7 @@ class HipSlabEngine(_capi._Sampled):
         self._profile_series = None  # (n_bins, n_bands incl. band 0) while the profile series is on
         self._pair_dist = None  # (n_bins, n_bands incl. band 0, r_max) while the pair statistics are on
         self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
+        self._dens_stats = None  # (n_bins, n_bands incl. band 0, n_hist, hist_range) while the density statistics are on
         capi.set_device(device)
         if not native:
             import torch
@@ -424,6 +431,26 @@ class HipSlabEngine(_capi._Sampled):
         out["n_owned"] = owned[:m].copy()
         return out
 
+    # ---- density statistics (include/sphx.h section 3a): the densities of the particles this slab owns -- PARTIAL sums ----
+    def dens_part_enable(self, n_bins=0, every=1, t_from=0.0, n_hist=64, hist_range=0.05, delta_bound=0.5, bands=()):
+        """A context's dens_stats_enable (capi._Stepped; the same argument checks, capi.dens_stats_config) for the ring: this
+        slab re-sums, inside run() / group_run(), the density at every fluid particle it OWNS -- from the positions of
+        everything it holds, its halo copies and its wall particles included -- bins it, and stamps every sampled step even
+        when it owns no particle of a band.  (Re)configures and zeroes the sums; drops a graph made by graph_prepare()."""
+        self._dens_enable(n_bins, every, t_from, n_hist, hist_range, delta_bound, bands)
+
+    def dens_part_disable(self):
+        self._dens_disable()
+
+    def dens_part_reset(self):
+        self._dens_reset()
+
+    def dens_part_sums(self, band=0) -> dict:
+        """This slab's partial sums of one band so far, the dict of capi.Context.dens_stats_sums(band): the eight
+        profile.DENS_FIELDS as [n_bins] arrays (d_min / d_max: +inf / -inf where it has summed no particle), hist, below, above,
+        hist_range, n_samples, t_first, t_last.  pool_ring_dens_stats puts the ranks' together."""
+        return self._dens_stats_band(band)[0]
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self.capi.lib().sphx_ctx_destroy(self._h)
@@ -674,6 +701,75 @@ def ring_grad_stats(engines) -> list:
     return [dict(d, **grad_stats_profiles(DH, d)) for d in ring_grad_stats_sums(engines)]
 
 
+def _dens_shape(sums, r):
+    """(n_bins, n_hist) of one rank's density sums of one band: the eight DENS_FIELDS, one value per bin each, and the histogram"""
+    try:
+        shapes = {np.shape(np.asarray(sums[f])) for f in DENS_FIELDS}
+        hist = np.shape(np.asarray(sums["hist"]))
+        int(sums["below"]), int(sums["above"])
+    except (KeyError, TypeError, IndexError, ValueError) as e:
+        raise ValueError(f"rank {r}: the density statistics of a slab are a dict with the eight fields of profile.DENS_FIELDS, hist, "
+                         f"below and above ({e!r})")
+    if len(shapes) != 1 or len(next(iter(shapes))) != 1:
+        raise ValueError(f"rank {r}: the eight fields hold shapes {sorted(shapes)}, one value per bin expected")
+    if len(hist) != 1:
+        raise ValueError(f"rank {r}: hist has shape {hist}, one count per histogram bin expected")
+    return next(iter(shapes))[0], hist[0]
+
+
+def pool_ring_dens_stats(sums_list) -> dict:
+    """The ring's density statistics of one band (the dict of capi.Context.dens_stats_sums(band)) from the ranks' partial sums
+    (HipSlabEngine.dens_part_sums(band) or one band of profile.dens_stats_sums_part, in rank order): count, outliers, the four
+    summed fields, hist, below and above added in rank order; d_min the smallest and d_max the largest of the ranks', +inf /
+    -inf (a slab that has summed no particle of the bin) being the empty state.  hist_range, n_samples, t_first and t_last,
+    where the parts carry them, are rank 0's and are NOT added: the slabs of one ring sampled the same steps (unlike the members
+    of profile.pool_dens_stats).  ValueError for an empty list and when the number of bins or of histogram bins, n_samples,
+    t_first or t_last differ between the ranks."""
+    sums_list = list(sums_list)
+    if not sums_list:
+        raise ValueError("the density statistics of a ring need the sums of at least one slab")
+    shapes = [_dens_shape(s, r) for r, s in enumerate(sums_list)]
+    heads = [_grad_head(s, r) for r, s in enumerate(sums_list)]
+    for r, n in enumerate(shapes):
+        if n != shapes[0]:
+            raise ValueError(f"rank {r} holds {n[0]} bins and {n[1]} histogram bins, rank 0 {shapes[0][0]} and {shapes[0][1]}: "
+                             "the slabs of one ring share the config")
+    for r, h in enumerate(heads):
+        if (h is None) != (heads[0] is None):
+            raise ValueError(f"rank {r} and rank 0 do not both carry n_samples, t_first and t_last")
+    if heads[0] is not None:
+        _check_heads_agree(heads)
+    out = {}
+    for f in DENS_SUMS:
+        total = np.array(sums_list[0][f], dtype=np.float64)
+        for s in sums_list[1:]:
+            total = total + np.asarray(s[f], dtype=np.float64)
+        out[f] = total
+    out["d_min"] = np.min([np.asarray(s["d_min"], dtype=np.float64) for s in sums_list], axis=0)
+    out["d_max"] = np.max([np.asarray(s["d_max"], dtype=np.float64) for s in sums_list], axis=0)
+    out["hist"] = np.sum([np.asarray(s["hist"], dtype=np.int64) for s in sums_list], axis=0, dtype=np.int64)
+    out["below"] = sum(int(s["below"]) for s in sums_list)
+    out["above"] = sum(int(s["above"]) for s in sums_list)
+    if "hist_range" in sums_list[0]:
+        out["hist_range"] = sums_list[0]["hist_range"]
+    if heads[0] is not None:
+        out.update(dict(zip(_HEAD, heads[0])))
+    return out
+
+
+def ring_dens_stats_sums(engines) -> list:
+    """The density statistics of an in-process ring, one dict of pooled sums per band (pool_ring_dens_stats of every slab's)."""
+    n_bands = engines[0]._dens_on()[1]
+    return [pool_ring_dens_stats([e.dens_part_sums(b) for e in engines]) for b in range(n_bands)]
+
+
+def ring_dens_stats(engines) -> list:
+    """The density statistics of an in-process ring with the profiles of profile.dens_stats_profiles (y_mid, d_mean, d_std,
+    p_mean, packing, hist_density, ...) in every band's dict: what driver.density_figures takes."""
+    prm = engines[0].params
+    return [dict(d, **dens_stats_profiles(prm.DH, prm.p0, d)) for d in ring_dens_stats_sums(engines)]
+
+
 def _check_blocks_partition(shapes):
     """shapes: [(nx, ny, i_lo, i_hi)] per rank -- the blocks of one nx x ny grid, side by side from 0 to nx."""
     nx, ny = int(shapes[0][0]), int(shapes[0][1])
@@ -903,10 +999,10 @@ def _all_gathered(dist, row, group):
     return [r.numpy() for r in rows]
 
 
-def _all_reduced(dist, a, group):
+def _all_reduced(dist, a, group, op=None):
     import torch
     t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).copy())
-    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM if op is None else op, group=group)
     return t.numpy()
 
 
@@ -1152,6 +1248,41 @@ def all_reduce_ring_tracers(part, dist, group=None, fold_DL=None) -> dict:
         out[k] = np.ascontiguousarray(total[j]).view(np.float64)
     out.update(n_dropped=int(part["n_dropped"]), n_missing=0, owner=_owner_of(total[F]))
     return _fold_tracers(out, fold_DL)
+
+
+def all_reduce_ring_dens_stats(sums, dist, group=None) -> dict:
+    """One rank per process: the ring's density statistics of one band from this rank's partial sums
+    (HipSlabEngine.dens_part_sums(band)), as pool_ring_dens_stats; every rank gets them.  Whether a rank's own dict is well
+    formed, the numbers of bins and of histogram bins and the heads are all-gathered and checked first; then count, outliers and
+    the four summed fields, stacked, and the histogram with below and above behind it are all-reduced with SUM (the counts as
+    float64, exact below 2^53), d_min with MIN and d_max with MAX.  Collective; raises on every rank when a dict is malformed or
+    the bins, n_samples, t_first or t_last differ between the ranks -- every rank makes the same calls up to the refusal, so the
+    group stays in step."""
+    try:
+        (n_bins, n_hist), why = _dens_shape(sums, "?"), None
+        head = [float(sums[k]) for k in _HEAD]
+    except (ValueError, KeyError, TypeError) as e:
+        n_bins, n_hist, head, why = -1, -1, [0.0] * len(_HEAD), str(e)
+    rows = _all_gathered(dist, [float(n_bins), float(n_hist), 0.0 if why is None else 1.0] + head, group)
+    for r, row in enumerate(rows):
+        if row[2] != 0.0:
+            raise ValueError(f"rank {r}'s density statistics are malformed" + (f": {why}" if why else ""))
+    for r, row in enumerate(rows):
+        if row[0] != rows[0][0] or row[1] != rows[0][1]:
+            raise ValueError(f"rank {r} holds {int(row[0])} bins and {int(row[1])} histogram bins, rank 0 {int(rows[0][0])} and "
+                             f"{int(rows[0][1])}: the slabs of one ring share the config")
+    _check_heads_agree([tuple(row[3:]) for row in rows])
+    total = _all_reduced(dist, np.stack([np.asarray(sums[f], dtype=np.float64) for f in DENS_SUMS]), group)
+    counts = np.concatenate([np.asarray(sums["hist"], dtype=np.float64), [float(sums["below"]), float(sums["above"])]])
+    counts = np.rint(_all_reduced(dist, counts, group)).astype(np.int64)
+    out = {f: total[j] for j, f in enumerate(DENS_SUMS)}
+    out["d_min"] = _all_reduced(dist, sums["d_min"], group, dist.ReduceOp.MIN)
+    out["d_max"] = _all_reduced(dist, sums["d_max"], group, dist.ReduceOp.MAX)
+    out.update(hist=counts[:n_hist], below=int(counts[n_hist]), above=int(counts[n_hist + 1]))
+    if "hist_range" in sums:
+        out["hist_range"] = sums["hist_range"]
+    out.update({k: sums[k] for k in _HEAD})
+    return out
 
 
 class SlabDriver:
