@@ -14,10 +14,12 @@ Layers:
                       through host memory for CPU tests and single-GPU rehearsals)
   HipSlabEngine    -- the per-rank compute engine (libsphx slab context)
   SlabDriver       -- step loop = engine.compute -> exchange -> engine.finish
-  pool_ring_* / ring_* / all_reduce_ring_*
-                   -- the ring's flow statistics, step history, profile series, pair, gradient and density statistics from
-                      the slabs' partial sums, its field map from the slabs' blocks of node columns, and its point probes from the slabs'
-                      owned probes
+  pool_ring_*      -- the one rule per sampler: the ring's flow statistics, step history, profile series, pair, gradient and
+                      density statistics from the slabs' partial sums, its field map from the slabs' blocks of node columns, its
+                      point probes and tracers from the columns the slabs own -- a pure function of the list of the ranks' parts
+  ring_* / all_reduce_ring_*
+                   -- that rule on the parts of an in-process ring / of one rank per process: one gather of the parts over the
+                      control-plane group (_ring_parts), then the pool form on every rank
   bench_main()     -- bench.py's multi-GPU leg
 """
 from __future__ import annotations
@@ -473,22 +475,86 @@ def _same(a, b):
     return a == b or (a != a and b != b)  # (no sample yet: the times are NaN on every rank)
 
 
-def _check_heads_agree(heads):
+def _check_heads_agree(heads, where=""):
     """heads: [(n_samples, t_first, t_last)] per rank -- every slab of a ring samples the same steps."""
     for r, h in enumerate(heads):
         if not all(_same(x, y) for x, y in zip(h, heads[0])):
-            raise ValueError(f"rank {r} sampled {dict(zip(_HEAD, h))}, rank 0 {dict(zip(_HEAD, heads[0]))}: "
+            raise ValueError(f"rank {r} sampled {dict(zip(_HEAD, h))}, rank 0 {dict(zip(_HEAD, heads[0]))}{where}: "
                              "the slabs of one ring sample the same steps")
+
+
+def _rank_shapes(parts, shape, what):
+    """[shape(part)] of the ranks' parts, of which a ring has at least one.  A part that is not a slab's `what` -- shape()
+    refuses it, or it lacks a key -- is a ValueError naming the rank."""
+    if not parts:
+        raise ValueError(f"{what} of a ring: the part of at least one slab is needed")
+    shapes = []
+    for r, p in enumerate(parts):
+        try:
+            shapes.append(shape(p))
+        except (ValueError, KeyError, TypeError, IndexError) as e:
+            raise ValueError(f"rank {r}: malformed {what}: {e if isinstance(e, ValueError) else repr(e)}") from None
+    return shapes
+
+
+def _shared_shape(part, fields, ndim):
+    """the one shape, of ndim axes, that the named fields of a part all hold"""
+    shape = np.shape(part[fields[0]])
+    if len(shape) != ndim:
+        raise ValueError(f"{fields[0]} has shape {shape}, {ndim} axes expected")
+    for k in fields[1:]:
+        if np.shape(part[k]) != shape:
+            raise ValueError(f"field {k} has shape {np.shape(part[k])}, {fields[0]} {shape}")
+    return tuple(int(v) for v in shape)
+
+
+def _part_head(part):
+    """(n_samples, t_first, t_last) of one rank's part, None where it carries none of them (a part made by profile.*_part)"""
+    have = [k in part for k in _HEAD]
+    if any(have) and not all(have):
+        raise ValueError("it carries some of n_samples, t_first and t_last and not the others")
+    return tuple(part[k] for k in _HEAD) if all(have) else None
+
+
+def _ring_head(parts, where="") -> dict:
+    """{n_samples, t_first, t_last} of a ring: rank 0's, which every rank's must equal -- they are NOT added, the slabs of one
+    ring sampled the same steps -- or {} where no rank carries them.  ValueError where some ranks do and others do not."""
+    heads = _rank_shapes(parts, _part_head, "head")
+    for r, h in enumerate(heads):
+        if (h is None) != (heads[0] is None):
+            raise ValueError(f"rank {r} and rank 0 do not both carry n_samples, t_first and t_last{where}")
+    if heads[0] is None:
+        return {}
+    _check_heads_agree(heads, where)
+    return dict(zip(_HEAD, heads[0]))
+
+
+def _added(arrays):
+    """the ranks' arrays added elementwise into float64, one rank after the other: ((a0 + a1) + a2) ..."""
+    total = np.array(arrays[0], dtype=np.float64)
+    for a in arrays[1:]:
+        total = total + np.asarray(a, dtype=np.float64)
+    return total
+
+
+def _pool_additive(parts, fields, shape, what):
+    """The rule the additive samplers share -> (the pooled fields, the ring's head): at least one part; shape(part) of every
+    rank is rank 0's; the head on all ranks or on none, and equal (_ring_head); the named fields added elementwise into float64
+    one rank after the other, ((p0 + p1) + p2) ..."""
+    shapes = _rank_shapes(parts, shape, what)
+    for r, sh in enumerate(shapes):
+        if sh != shapes[0]:
+            raise ValueError(f"rank {r} holds {what} of shape {sh}, rank 0 {shapes[0]}: the slabs of one ring share the config "
+                             "and record the same steps")
+    return {f: _added([p[f] for p in parts]) for f in fields}, _ring_head(parts)
 
 
 def pool_ring_sums(sums_list) -> dict:
     """The ring's flow-statistics sums of one band from the ranks' partial sums (HipSlabEngine.flow_stats_sums, in rank
-    order): every array added elementwise, count included; n_samples, t_first and t_last must agree between the ranks."""
-    sums_list = list(sums_list)
-    _check_heads_agree([tuple(s[k] for k in _HEAD) for s in sums_list])
-    out = {k: np.sum([np.asarray(s[k], dtype=np.float64) for s in sums_list], axis=0) for k in _SUMS}
-    out.update({k: sums_list[0][k] for k in _HEAD})
-    return out
+    order): every array added elementwise in rank order, count included; n_samples, t_first and t_last are rank 0's.
+    ValueError for an empty list and when the number of bins, n_samples, t_first or t_last differ between the ranks."""
+    sums, head = _pool_additive(list(sums_list), _SUMS, lambda s: _shared_shape(s, _SUMS, 1), "flow statistics")
+    return dict(sums, **head)
 
 
 def _check_steps_agree(steps_list):
@@ -497,14 +563,26 @@ def _check_steps_agree(steps_list):
             raise ValueError(f"rank {r} recorded steps {st!r}, rank 0 {steps_list[0]!r}: the slabs of one ring record the same steps")
 
 
+def _check_records_agree(parts):
+    """step, t and n_dropped of every rank's series are rank 0's: every slab of a ring records the same steps, even one that owns
+    nothing, and capacity and drops are per slab and agree"""
+    first = parts[0]
+    for r, p in enumerate(parts):
+        if not np.array_equal(p["step"], first["step"]) or not np.array_equal(p["t"], first["t"]):
+            raise ValueError(f"rank {r} recorded steps {np.asarray(p['step'])!r}, rank 0 {np.asarray(first['step'])!r} (or other "
+                             "times): the slabs of one ring record the same steps")
+        if int(p["n_dropped"]) != int(first["n_dropped"]):
+            raise ValueError(f"rank {r} dropped {p['n_dropped']} records, rank 0 {first['n_dropped']}")
+
+
 def pool_ring_history(records_list) -> dict:
     """The ring's step history (capi.history_dict's form) from the ranks' (records [n x 8], n_dropped) pairs
-    (HipSlabEngine.history_records, in rank order): step, t, dt, vmax of rank 0, the other fields summed over the ranks;
+    (HipSlabEngine.history_records, in rank order): step, t, dt, vmax of rank 0, the other fields added in rank order;
     the ranks' step columns must agree.  n_dropped is rank 0's (capacity and drops are per slab and agree)."""
     recs = [np.asarray(r, dtype=np.float64).reshape(-1, len(_capi.HISTORY_FIELDS)) for r, _ in records_list]
     _check_steps_agree([r[:, 0] for r in recs])
     out = recs[0].copy()
-    out[:, _CLOCK_FIELDS:] = np.sum([r[:, _CLOCK_FIELDS:] for r in recs], axis=0)
+    out[:, _CLOCK_FIELDS:] = _added([r[:, _CLOCK_FIELDS:] for r in recs])
     return _capi.history_dict(out, records_list[0][1])
 
 
@@ -519,50 +597,32 @@ def ring_history(engines, drain=False) -> dict:
 
 
 def _series_shape(sums):
-    """(n_records, n_bands, n_bins) of one rank's raw profile series, whose five fields must share that shape, step and t
-    hold n_records values and y_mid n_bins"""
-    shape = np.shape(sums["count"])
-    if len(shape) != 3:
-        raise ValueError(f"count has shape {shape}, [n_records, n_bands, n_bins] expected")
-    for k in _SUMS:
-        if np.shape(sums[k]) != shape:
-            raise ValueError(f"field {k} has shape {np.shape(sums[k])}, count {shape}")
+    """[n_records, n_bands, n_bins] of one rank's raw profile series, whose five fields must share that shape, step and t
+    hold n_records values and y_mid n_bins; n_dropped is an integer"""
+    shape = _shared_shape(sums, _SUMS, 3)
     for k in ("step", "t"):
         if np.shape(sums[k]) != shape[:1]:
             raise ValueError(f"{k} has shape {np.shape(sums[k])}, the fields hold {shape[0]} records")
     if np.shape(sums["y_mid"]) != shape[2:]:
         raise ValueError(f"y_mid has shape {np.shape(sums['y_mid'])}, the fields hold {shape[2]} bins")
-    return tuple(int(v) for v in shape)
+    int(sums["n_dropped"])
+    return shape
 
 
 def pool_ring_profile_series(sums_list) -> dict:
     """The ring's raw profile series (the dict of capi.Context.profile_series_sums) from the ranks' partial series
     (HipSlabEngine.profile_series_sums, in rank order): the five fields added elementwise over the ranks, one rank after the
-    other, count included; step, t, y_mid and n_dropped are rank 0's.  ValueError when the [n_records, n_bands, n_bins] shape,
-    step, t, n_dropped or y_mid differ between the ranks (every slab of a ring records the same steps, a slab that owns
-    nothing in a band its zeros)."""
+    other, count included; step, t, y_mid and n_dropped are rank 0's.  ValueError for an empty list and when the [n_records,
+    n_bands, n_bins] shape, step, t, n_dropped or y_mid differ between the ranks (every slab of a ring records the same steps, a
+    slab that owns nothing in a band its zeros)."""
     sums_list = list(sums_list)
-    if not sums_list:
-        raise ValueError("the profile series of a ring needs the series of at least one slab")
-    shapes = [_series_shape(s) for s in sums_list]
+    sums, _ = _pool_additive(sums_list, _SUMS, _series_shape, "profile series")  # (a series carries no head)
+    _check_records_agree(sums_list)
     first = sums_list[0]
-    for r, (s, sh) in enumerate(zip(sums_list, shapes)):
-        if sh != shapes[0]:
-            raise ValueError(f"rank {r} holds {sh[0]} records of {sh[1]} bands x {sh[2]} bins, rank 0 {shapes[0][0]} of "
-                             f"{shapes[0][1]} x {shapes[0][2]}: the slabs of one ring share the config and record the same steps")
-        if not np.array_equal(s["step"], first["step"]) or not np.array_equal(s["t"], first["t"]):
-            raise ValueError(f"rank {r} recorded steps {np.asarray(s['step'])!r}, rank 0 {np.asarray(first['step'])!r} (or other "
-                             "times): the slabs of one ring record the same steps")
-        if int(s["n_dropped"]) != int(first["n_dropped"]):
-            raise ValueError(f"rank {r} dropped {s['n_dropped']} records, rank 0 {first['n_dropped']}")
+    for r, s in enumerate(sums_list):
         if not np.array_equal(s["y_mid"], first["y_mid"]):
             raise ValueError(f"rank {r} holds other bin centres than rank 0: the slabs of one ring share the bins")
-    out = dict(step=np.asarray(first["step"]).astype(np.int64), t=np.array(first["t"], dtype=np.float64))
-    for k in _SUMS:
-        total = np.array(first[k], dtype=np.float64)
-        for s in sums_list[1:]:
-            total = total + np.asarray(s[k], dtype=np.float64)
-        out[k] = total
+    out = dict(step=np.asarray(first["step"]).astype(np.int64), t=np.array(first["t"], dtype=np.float64), **sums)
     out.update(n_dropped=int(first["n_dropped"]), y_mid=np.array(first["y_mid"], dtype=np.float64))
     return out
 
@@ -582,15 +642,19 @@ _PAIR_COUNTS = ("ff", "fw")
 
 
 def _pair_bands(part):
-    """one rank's pair statistics as a list of band dicts whose ff and fw hold one count per bin of r_edges"""
+    """(n_bands, n_bins) of one rank's pair statistics: a list of band dicts whose ff and fw hold one count per bin of r_edges,
+    every band as many bins as band 0; centres is an integer and r2_min a number"""
     if isinstance(part, dict) or not len(part):
         raise ValueError("the pair statistics of a slab are a list with one dict per band, band 0 first")
+    n_bins = len(part[0]["r_edges"]) - 1
     for b, d in enumerate(part):
-        n_bins = len(d["r_edges"]) - 1
+        if len(d["r_edges"]) - 1 != n_bins:
+            raise ValueError(f"band {b} holds {len(d['r_edges']) - 1} bins, band 0 {n_bins}: the bands of one slab share the bins")
         for k in _PAIR_COUNTS:
             if np.shape(d[k]) != (n_bins,):
                 raise ValueError(f"band {b}: {k} has shape {np.shape(d[k])}, r_edges bound {n_bins} bins")
-    return list(part)
+        int(d["centres"]), float(d["r2_min"])
+    return len(part), n_bins
 
 
 def pool_ring_pair_dist(parts) -> list:
@@ -598,31 +662,26 @@ def pool_ring_pair_dist(parts) -> list:
     (HipSlabEngine.pairs_part_sums or profile.pair_histogram_part, in rank order): per band ff, fw and centres added over the
     ranks -- int64, exact --, the smallest r2_min (r_min its square root), r_edges of rank 0.  n_samples, t_first and t_last,
     where the parts carry them, are rank 0's and are NOT added: the slabs of one ring sampled the same steps (unlike the
-    members of profile.pool_pair_dist).  ValueError when the number of bands, r_edges, or n_samples, t_first or t_last differ
-    between the ranks."""
-    parts = [_pair_bands(p) for p in parts]
-    if not parts:
-        raise ValueError("the pair statistics of a ring need the sums of at least one slab")
-    first = parts[0]
-    for r, p in enumerate(parts):
-        if len(p) != len(first):
-            raise ValueError(f"rank {r} holds {len(p)} bands, rank 0 {len(first)}: the slabs of one ring share the config")
-        for b, (d, d0) in enumerate(zip(p, first)):
+    members of profile.pool_pair_dist).  ValueError for an empty list and when the number of bands or of bins, r_edges, or
+    n_samples, t_first or t_last differ between the ranks, or between the bands of one slab the number of bins."""
+    parts = list(parts)
+    shapes = _rank_shapes(parts, _pair_bands, "pair statistics")
+    for r, sh in enumerate(shapes):
+        if sh != shapes[0]:
+            raise ValueError(f"rank {r} holds {sh[0]} bands of {sh[1]} bins, rank 0 {shapes[0][0]} of {shapes[0][1]}: the slabs of "
+                             "one ring share the config")
+    out = []
+    for b, d0 in enumerate(parts[0]):
+        band = [p[b] for p in parts]
+        for r, d in enumerate(band):
             if not np.array_equal(d["r_edges"], d0["r_edges"]):
                 raise ValueError(f"rank {r} holds other bin edges than rank 0 (band {b}): the slabs of one ring share the bins")
-            if any((k in d) != (k in d0) for k in _HEAD):
-                raise ValueError(f"rank {r} and rank 0 do not both carry n_samples, t_first and t_last (band {b})")
-            if all(k in d0 for k in _HEAD) and not all(_same(d[k], d0[k]) for k in _HEAD):
-                raise ValueError(f"rank {r} sampled {({k: d[k] for k in _HEAD})}, rank 0 {({k: d0[k] for k in _HEAD})} (band {b}): "
-                                 "the slabs of one ring sample the same steps")
-    out = []
-    for b, d0 in enumerate(first):
-        r2 = min(float(p[b]["r2_min"]) for p in parts)
+        head = _ring_head(band, f" (band {b})")
+        r2 = min(float(d["r2_min"]) for d in band)
         d = dict(r_edges=np.array(d0["r_edges"], dtype=np.float64))
         for k in _PAIR_COUNTS:
-            d[k] = np.sum([np.asarray(p[b][k], dtype=np.int64) for p in parts], axis=0, dtype=np.int64)
-        d.update(centres=int(sum(int(p[b]["centres"]) for p in parts)), r2_min=r2, r_min=float(np.sqrt(r2)))
-        d.update({k: d0[k] for k in _HEAD if k in d0})
+            d[k] = np.sum([np.asarray(p[k], dtype=np.int64) for p in band], axis=0, dtype=np.int64)
+        d.update(centres=int(sum(int(p["centres"]) for p in band)), r2_min=r2, r_min=float(np.sqrt(r2)), **head)
         out.append(d)
     return out
 
@@ -639,53 +698,15 @@ def ring_pair_dist(engines) -> list:
     return [dict(d, **pair_dist_profiles(d, dp)) for d in ring_pair_dist_sums(engines)]
 
 
-def _grad_shape(sums, r):
-    """n_bins of one rank's gradient sums of one band: the twelve GRAD_FIELDS, one value per bin each"""
-    try:
-        shapes = {np.shape(np.asarray(sums[f])) for f in GRAD_FIELDS}
-    except (KeyError, TypeError, IndexError) as e:
-        raise ValueError(f"rank {r}: the gradient statistics of a slab are a dict with the twelve fields of profile.GRAD_FIELDS ({e!r})")
-    if len(shapes) != 1 or len(next(iter(shapes))) != 1:
-        raise ValueError(f"rank {r}: the twelve fields hold shapes {sorted(shapes)}, one value per bin expected")
-    return next(iter(shapes))[0]
-
-
-def _grad_head(sums, r):
-    """(n_samples, t_first, t_last) of one rank's sums, None where it carries none (profile.grad_stats_sums_part)"""
-    have = [k in sums for k in _HEAD]
-    if any(have) and not all(have):
-        raise ValueError(f"rank {r} carries some of n_samples, t_first and t_last and not the others")
-    return tuple(sums[k] for k in _HEAD) if all(have) else None
-
-
 def pool_ring_grad_stats(sums_list) -> dict:
     """The ring's gradient statistics of one band (the dict of capi.Context.grad_stats_sums(band)) from the ranks' partial sums
-    (HipSlabEngine.grads_part_sums(band) or one band of profile.grad_stats_sums_part, in rank order): the twelve GRAD_FIELDS
-    added in rank order, count and skipped included.  n_samples, t_first and t_last, where the parts carry them, are rank 0's
-    and are NOT added: the slabs of one ring sampled the same steps (unlike the members of profile.pool_grad_stats).  ValueError
-    for an empty list and when the number of bins, n_samples, t_first or t_last differ between the ranks."""
-    sums_list = list(sums_list)
-    if not sums_list:
-        raise ValueError("the gradient statistics of a ring need the sums of at least one slab")
-    shapes = [_grad_shape(s, r) for r, s in enumerate(sums_list)]
-    heads = [_grad_head(s, r) for r, s in enumerate(sums_list)]
-    for r, n in enumerate(shapes):
-        if n != shapes[0]:
-            raise ValueError(f"rank {r} holds {n} bins, rank 0 {shapes[0]}: the slabs of one ring share the config")
-    for r, h in enumerate(heads):
-        if (h is None) != (heads[0] is None):
-            raise ValueError(f"rank {r} and rank 0 do not both carry n_samples, t_first and t_last")
-    if heads[0] is not None:
-        _check_heads_agree(heads)
-    out = {}
-    for f in GRAD_FIELDS:
-        total = np.array(sums_list[0][f], dtype=np.float64)
-        for s in sums_list[1:]:
-            total = total + np.asarray(s[f], dtype=np.float64)
-        out[f] = total
-    if heads[0] is not None:
-        out.update(dict(zip(_HEAD, heads[0])))
-    return out
+    (HipSlabEngine.grads_part_sums(band) or one band of profile.grad_stats_sums_part, in rank order): the twelve GRAD_FIELDS,
+    one value per bin each, added in rank order, count and skipped included.  n_samples, t_first and t_last, where the parts
+    carry them, are rank 0's and are NOT added: the slabs of one ring sampled the same steps (unlike the members of
+    profile.pool_grad_stats).  ValueError for an empty list and when the number of bins, n_samples, t_first or t_last differ
+    between the ranks."""
+    sums, head = _pool_additive(list(sums_list), GRAD_FIELDS, lambda s: _shared_shape(s, GRAD_FIELDS, 1), "gradient statistics")
+    return dict(sums, **head)
 
 
 def ring_grad_stats_sums(engines) -> list:
@@ -701,20 +722,11 @@ def ring_grad_stats(engines) -> list:
     return [dict(d, **grad_stats_profiles(DH, d)) for d in ring_grad_stats_sums(engines)]
 
 
-def _dens_shape(sums, r):
-    """(n_bins, n_hist) of one rank's density sums of one band: the eight DENS_FIELDS, one value per bin each, and the histogram"""
-    try:
-        shapes = {np.shape(np.asarray(sums[f])) for f in DENS_FIELDS}
-        hist = np.shape(np.asarray(sums["hist"]))
-        int(sums["below"]), int(sums["above"])
-    except (KeyError, TypeError, IndexError, ValueError) as e:
-        raise ValueError(f"rank {r}: the density statistics of a slab are a dict with the eight fields of profile.DENS_FIELDS, hist, "
-                         f"below and above ({e!r})")
-    if len(shapes) != 1 or len(next(iter(shapes))) != 1:
-        raise ValueError(f"rank {r}: the eight fields hold shapes {sorted(shapes)}, one value per bin expected")
-    if len(hist) != 1:
-        raise ValueError(f"rank {r}: hist has shape {hist}, one count per histogram bin expected")
-    return next(iter(shapes))[0], hist[0]
+def _dens_shape(sums):
+    """(n_bins, n_hist) of one rank's density sums of one band: the eight DENS_FIELDS, one value per bin each, the histogram, and
+    below and above, integers"""
+    int(sums["below"]), int(sums["above"])
+    return _shared_shape(sums, DENS_FIELDS, 1) + _shared_shape(sums, ("hist",), 1)
 
 
 def pool_ring_dens_stats(sums_list) -> dict:
@@ -726,25 +738,7 @@ def pool_ring_dens_stats(sums_list) -> dict:
     of profile.pool_dens_stats).  ValueError for an empty list and when the number of bins or of histogram bins, n_samples,
     t_first or t_last differ between the ranks."""
     sums_list = list(sums_list)
-    if not sums_list:
-        raise ValueError("the density statistics of a ring need the sums of at least one slab")
-    shapes = [_dens_shape(s, r) for r, s in enumerate(sums_list)]
-    heads = [_grad_head(s, r) for r, s in enumerate(sums_list)]
-    for r, n in enumerate(shapes):
-        if n != shapes[0]:
-            raise ValueError(f"rank {r} holds {n[0]} bins and {n[1]} histogram bins, rank 0 {shapes[0][0]} and {shapes[0][1]}: "
-                             "the slabs of one ring share the config")
-    for r, h in enumerate(heads):
-        if (h is None) != (heads[0] is None):
-            raise ValueError(f"rank {r} and rank 0 do not both carry n_samples, t_first and t_last")
-    if heads[0] is not None:
-        _check_heads_agree(heads)
-    out = {}
-    for f in DENS_SUMS:
-        total = np.array(sums_list[0][f], dtype=np.float64)
-        for s in sums_list[1:]:
-            total = total + np.asarray(s[f], dtype=np.float64)
-        out[f] = total
+    out, head = _pool_additive(sums_list, DENS_SUMS, _dens_shape, "density statistics")
     out["d_min"] = np.min([np.asarray(s["d_min"], dtype=np.float64) for s in sums_list], axis=0)
     out["d_max"] = np.max([np.asarray(s["d_max"], dtype=np.float64) for s in sums_list], axis=0)
     out["hist"] = np.sum([np.asarray(s["hist"], dtype=np.int64) for s in sums_list], axis=0, dtype=np.int64)
@@ -752,9 +746,7 @@ def pool_ring_dens_stats(sums_list) -> dict:
     out["above"] = sum(int(s["above"]) for s in sums_list)
     if "hist_range" in sums_list[0]:
         out["hist_range"] = sums_list[0]["hist_range"]
-    if heads[0] is not None:
-        out.update(dict(zip(_HEAD, heads[0])))
-    return out
+    return dict(out, **head)
 
 
 def ring_dens_stats_sums(engines) -> list:
@@ -802,9 +794,7 @@ def pool_ring_field_map(parts) -> dict:
     blocks leave a gap, overlap, do not fit the grid, or n_samples, t_first, t_last differ between the ranks (a slab without
     a node still counts the samples)."""
     parts = list(parts)
-    if not parts:
-        raise ValueError("the field map of a ring needs the part of at least one slab")
-    _check_blocks_partition([_block_shape(p) for p in parts])
+    _check_blocks_partition(_rank_shapes(parts, _block_shape, "field map"))
     ny = int(parts[0]["ny"])
     _check_heads_agree([tuple(p[k] for k in _HEAD) for p in parts])
     out = {k: np.ascontiguousarray(np.concatenate([np.asarray(p[k], dtype=np.float64).reshape(ny, -1) for p in parts], axis=1))
@@ -836,6 +826,7 @@ def _probe_part_shape(part):
     for k in _capi.PROBE_FIELDS:
         if np.shape(part[k]) != (n, len(idx)):
             raise ValueError(f"field {k} has shape {np.shape(part[k])}, {n} records of {len(idx)} owned probes need {(n, len(idx))}")
+    int(part["n_dropped"])
     return len(pts), len(idx), n
 
 
@@ -855,19 +846,12 @@ def pool_ring_probes(parts) -> dict:
     where its owner has it.  ValueError when the indices do not partition range(P), or step, t, n_dropped or points differ
     between the ranks (a slab without a probe still records the steps)."""
     parts = list(parts)
-    if not parts:
-        raise ValueError("the probes of a ring need the part of at least one slab")
-    shapes = [_probe_part_shape(p) for p in parts]
-    P, _, n = shapes[0]
+    P, _, n = _rank_shapes(parts, _probe_part_shape, "probes")[0]
     first = parts[0]
-    for r, (p, sh) in enumerate(zip(parts, shapes)):
-        if sh[0] != P or not np.array_equal(np.asarray(p["points"], dtype=np.float64), np.asarray(first["points"], dtype=np.float64)):
+    for r, p in enumerate(parts):
+        if not np.array_equal(np.asarray(p["points"], dtype=np.float64), np.asarray(first["points"], dtype=np.float64)):
             raise ValueError(f"rank {r} holds other points than rank 0: the slabs of one ring share the list")
-        if sh[2] != n or not np.array_equal(p["step"], first["step"]) or not np.array_equal(p["t"], first["t"]):
-            raise ValueError(f"rank {r} recorded steps {np.asarray(p['step'])!r}, rank 0 {np.asarray(first['step'])!r} (or other "
-                             "times): the slabs of one ring record the same steps")
-        if int(p["n_dropped"]) != int(first["n_dropped"]):
-            raise ValueError(f"rank {r} dropped {p['n_dropped']} records, rank 0 {first['n_dropped']}")
+    _check_records_agree(parts)
     counts = np.zeros(P, dtype=np.int64)
     for p in parts:
         np.add.at(counts, np.asarray(p["index"], dtype=np.int64), 1)
@@ -907,36 +891,21 @@ def _tracer_part_shape(part):
         r = int(np.flatnonzero(held != owned)[0])
         raise ValueError(f"record {r} (step {int(np.asarray(part['step'])[r])}) holds {int(held[r])} columns, its n_owned says "
                          f"{int(owned[r])}")
+    int(part["n_dropped"])
     return len(ids), n
 
 
-def _check_one_owner(ranks_of, step, ids):
-    """ranks_of [n_records, T] (int64): bit r set where rank r wrote the column -- exactly one bit everywhere, or ValueError
-    naming the first record, its step, the id and the ranks"""
-    ranks_of = np.asarray(ranks_of, dtype=np.int64)
-    wrong = (ranks_of == 0) | ((ranks_of & (ranks_of - 1)) != 0)
+def _one_owner(masks, step, ids):
+    """masks [world, n_records, T]: where rank r wrote the column -> owner [n_records, T] (int64), the one rank that did;
+    ValueError naming the first record, its step, the id and the ranks where none did or more than one"""
+    wrong = np.count_nonzero(masks, axis=0) != 1
     if np.any(wrong):
         r, k = (int(v) for v in np.argwhere(wrong)[0])
-        who = [b for b in range(63) if (int(ranks_of[r, k]) >> b) & 1]
+        who = np.flatnonzero(masks[:, r, k]).tolist()
         raise ValueError(f"slab ownership broken: record {r} (step {int(np.asarray(step)[r])}), id {int(np.asarray(ids)[k])} is "
                          + (f"owned by ranks {who}: more than one" if who else "owned by no rank (ranks []): lost")
                          + f"; {int(np.count_nonzero(wrong))} columns of the series have no owner or more than one")
-
-
-def _owner_of(ranks_of):
-    """the rank whose bit is set, [n_records, T] int64"""
-    out = np.zeros(np.shape(ranks_of), dtype=np.int64)
-    v = np.asarray(ranks_of, dtype=np.int64) >> 1
-    while np.any(v):
-        out += v != 0
-        v = v >> 1
-    return out
-
-
-def _fold_tracers(out, fold_DL):
-    if fold_DL is not None:
-        out["x"] = out["x"] - np.floor(out["x"] / fold_DL) * fold_DL
-    return out
+    return np.argmax(masks, axis=0).astype(np.int64)
 
 
 def pool_ring_tracers(parts, fold_DL=None) -> dict:
@@ -949,31 +918,14 @@ def pool_ring_tracers(parts, fold_DL=None) -> dict:
     of a record has no owner or more than one (naming record, step, id and the ranks), when a part's columns of a record are
     not as many as its n_owned, or when ids, step, t or n_dropped differ between the ranks."""
     parts = list(parts)
-    if not parts:
-        raise ValueError("the tracers of a ring need the part of at least one slab")
-    if len(parts) > 62:
-        raise ValueError("at most 62 ranks")
-    shapes = []
-    for r, p in enumerate(parts):
-        try:
-            shapes.append(_tracer_part_shape(p))
-        except ValueError as e:
-            raise ValueError(f"rank {r}: {e}") from None
-    T, n = shapes[0]
+    T, n = _rank_shapes(parts, _tracer_part_shape, "tracers")[0]
     first = parts[0]
-    for r, (p, sh) in enumerate(zip(parts, shapes)):
-        if sh[0] != T or not np.array_equal(np.asarray(p["ids"]), np.asarray(first["ids"])):
+    for r, p in enumerate(parts):
+        if not np.array_equal(np.asarray(p["ids"]), np.asarray(first["ids"])):
             raise ValueError(f"rank {r} tracks other ids than rank 0: the slabs of one ring share the list")
-        if sh[1] != n or not np.array_equal(p["step"], first["step"]) or not np.array_equal(p["t"], first["t"]):
-            raise ValueError(f"rank {r} recorded steps {np.asarray(p['step'])!r}, rank 0 {np.asarray(first['step'])!r} (or other "
-                             "times): the slabs of one ring record the same steps")
-        if int(p["n_dropped"]) != int(first["n_dropped"]):
-            raise ValueError(f"rank {r} dropped {p['n_dropped']} records, rank 0 {first['n_dropped']}")
-    masks = [~np.isnan(np.asarray(p["x"], dtype=np.float64)).reshape(n, T) for p in parts]
-    ranks_of = np.zeros((n, T), dtype=np.int64)
-    for r, m in enumerate(masks):
-        ranks_of += m.astype(np.int64) << r
-    _check_one_owner(ranks_of, first["step"], first["ids"])
+    _check_records_agree(parts)
+    masks = np.stack([~np.isnan(np.asarray(p["x"], dtype=np.float64)).reshape(n, T) for p in parts])
+    owner = _one_owner(masks, first["step"], first["ids"])
     out = dict(ids=np.array(first["ids"], dtype=np.int32), step=np.asarray(first["step"]).astype(np.int64),
                t=np.array(first["t"], dtype=np.float64))
     for k in _capi.TRACER_FIELDS:
@@ -981,8 +933,10 @@ def pool_ring_tracers(parts, fold_DL=None) -> dict:
         for p, m in zip(parts, masks):
             a[m] = np.asarray(p[k], dtype=np.float64).reshape(n, T)[m]
         out[k] = a
-    out.update(n_dropped=int(first["n_dropped"]), n_missing=0, owner=_owner_of(ranks_of))
-    return _fold_tracers(out, fold_DL)
+    if fold_DL is not None:
+        out["x"] = out["x"] - np.floor(out["x"] / fold_DL) * fold_DL
+    out.update(n_dropped=int(first["n_dropped"]), n_missing=0, owner=owner)
+    return out
 
 
 def ring_tracers(engines, drain=False, fold_DL=None) -> dict:
@@ -990,299 +944,59 @@ def ring_tracers(engines, drain=False, fold_DL=None) -> dict:
     return pool_ring_tracers([e.tracers_part_records(drain) for e in engines], fold_DL)
 
 
-def _all_gathered(dist, row, group):
-    """[world x len(row)] float64: every rank's row (control plane: CPU tensors, gloo)."""
-    import torch
-    mine = torch.tensor(np.asarray(row, dtype=np.float64))
-    rows = [torch.empty_like(mine) for _ in range(dist.get_world_size(group))]
-    dist.all_gather(rows, mine, group=group)
-    return [r.numpy() for r in rows]
-
-
-def _all_reduced(dist, a, group, op=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).copy())
-    dist.all_reduce(t, op=dist.ReduceOp.SUM if op is None else op, group=group)
-    return t.numpy()
+# ---- one rank per process: gather the parts, then the pool form.  Every rank runs the same pure function on the same list, so
+# all of them get the same result or the same ValueError, and a refusal leaves the group in step: there is one collective ----
+def _ring_parts(dist, part, group=None) -> list:
+    """Every rank's part in rank order, on every rank: ONE all_gather_object over the control-plane group (the gloo group that
+    join_native_ring uses; the parts travel pickled).  A rank holds `world` parts while it pools."""
+    parts = [None] * dist.get_world_size(group)
+    dist.all_gather_object(parts, part, group=group)
+    return parts
 
 
 def all_reduce_ring_sums(sums, dist, group=None) -> dict:
-    """One rank per process: the ring's sums from this rank's (pool_ring_sums over the control-plane group that
-    join_native_ring uses -- float64 on the CPU); every rank gets them.  Collective; raises on every rank when the ranks'
-    n_samples, t_first or t_last differ."""
-    _check_heads_agree([tuple(h) for h in _all_gathered(dist, [float(sums[k]) for k in _HEAD], group)])
-    total = _all_reduced(dist, np.stack([np.asarray(sums[k], dtype=np.float64) for k in _SUMS]), group)
-    out = {k: total[j] for j, k in enumerate(_SUMS)}
-    out.update({k: sums[k] for k in _HEAD})
-    return out
+    """One rank per process: pool_ring_sums of every rank's sums of one band, on every rank.  Collective."""
+    return pool_ring_sums(_ring_parts(dist, sums, group))
 
 
 def all_reduce_ring_history(records, dist, group=None) -> dict:
-    """One rank per process: the ring's step history from this rank's (records, n_dropped) pair, as pool_ring_history; every
-    rank gets it.  Collective; raises on every rank when the ranks' step columns differ."""
-    rec = np.asarray(records[0], dtype=np.float64).reshape(-1, len(_capi.HISTORY_FIELDS))
-    counts = _all_gathered(dist, [float(len(rec))], group)
-    if any(c[0] != counts[0][0] for c in counts):
-        raise ValueError(f"the ranks hold {[int(c[0]) for c in counts]} records: the slabs of one ring record the same steps")
-    _check_steps_agree(_all_gathered(dist, rec[:, 0], group))
-    out = rec.copy()
-    out[:, _CLOCK_FIELDS:] = _all_reduced(dist, rec[:, _CLOCK_FIELDS:], group)
-    return _capi.history_dict(out, records[1])
+    """One rank per process: pool_ring_history of every rank's (records, n_dropped) pair, on every rank.  Collective."""
+    return pool_ring_history(_ring_parts(dist, records, group))
 
 
 def all_reduce_ring_field_map(part, dist, group=None) -> dict:
-    """One rank per process: the ring's field-map planes from this rank's part, as pool_ring_field_map; every rank gets them.
-    The block ranges and the heads are all-gathered and checked first; then every rank pads its block with zeros to
-    [6, ny, nx] and the padded arrays are all-reduced -- every node has one contributor and x + 0.0 is x, so the result is
-    bit for bit the blocks side by side.  Collective; raises on every rank when the blocks do not partition [0, nx) or the
-    ranks' n_samples, t_first or t_last differ."""
-    nx, ny, lo, hi = _block_shape(part)
-    rows = _all_gathered(dist, [float(v) for v in (nx, ny, lo, hi)] + [float(part[k]) for k in _HEAD], group)
-    _check_blocks_partition([tuple(r[:4]) for r in rows])
-    _check_heads_agree([tuple(r[4:]) for r in rows])
-    padded = np.zeros((len(FIELD_MAP_PLANES), ny, nx))
-    for j, k in enumerate(FIELD_MAP_PLANES):
-        padded[j, :, lo:hi] = part[k]
-    total = _all_reduced(dist, padded, group)
-    out = {k: np.ascontiguousarray(total[j]) for j, k in enumerate(FIELD_MAP_PLANES)}
-    out.update({k: part[k] for k in _HEAD})
-    return out
+    """One rank per process: pool_ring_field_map of every rank's block, on every rank.  Collective."""
+    return pool_ring_field_map(_ring_parts(dist, part, group))
 
 
 def all_reduce_ring_probes(part, dist, group=None) -> dict:
-    """One rank per process: the ring's probes from this rank's part, as pool_ring_probes; every rank gets them.  The sizes,
-    n_dropped and whether a rank's own part is well formed are all-gathered and checked first, then the points, step and t;
-    the ranks' owner counts per point are all-reduced and must be 1 everywhere.  Then every rank scatters its owned columns
-    into zeros [4, n_records, P] -- a NaN (the velocities of a void probe) goes as 0 with a 1 in a mask that travels
-    along -- and the arrays are all-reduced: every probe has one contributor and x + 0.0 is x, so the result is the columns
-    at their places, and the mask puts the NaNs back; no NaN is ever summed.  Collective; raises on every rank when a part
-    is malformed, the indices do not partition range(P), or step, t, n_dropped or points differ between the ranks."""
-    try:
-        P, k, n = _probe_part_shape(part)
-        why = None
-    except (ValueError, KeyError, TypeError) as e:
-        P, k, n, why = -1, -1, -1, str(e)
-    rows = _all_gathered(dist, [float(P), float(n), float(part.get("n_dropped", -1)) if why is None else -1.0,
-                                0.0 if why is None else 1.0], group)
-    for r, row in enumerate(rows):
-        if row[3] != 0.0:
-            raise ValueError(f"rank {r}'s part is malformed" + (f": {why}" if why else ""))
-    for r, row in enumerate(rows):
-        if tuple(row[:3]) != tuple(rows[0][:3]):
-            raise ValueError(f"rank {r} holds {int(row[0])} points, {int(row[1])} records, {int(row[2])} dropped; rank 0 "
-                             f"{int(rows[0][0])}, {int(rows[0][1])}, {int(rows[0][2])}: the slabs of one ring share the list and "
-                             "record the same steps")
-    pts = np.asarray(part["points"], dtype=np.float64)
-    step, t = np.asarray(part["step"], dtype=np.float64), np.asarray(part["t"], dtype=np.float64)
-    mine = np.concatenate([pts.ravel(), step, t])
-    for r, row in enumerate(_all_gathered(dist, mine, group)):
-        if not np.array_equal(row, mine):  # (every rank compares with its own: one odd rank out makes all of them raise)
-            raise ValueError(f"rank {r} holds other points, steps or times than this rank")
-    idx = np.asarray(part["index"], dtype=np.int64)
-    counts = np.zeros(P)
-    counts[idx] = 1.0
-    _check_owners_partition(_all_reduced(dist, counts, group).astype(np.int64))
-    F = len(_capi.PROBE_FIELDS)
-    padded = np.zeros((2 * F, n, P))  # the fields, and behind them their NaN masks
-    for j, f in enumerate(_capi.PROBE_FIELDS):
-        a = np.asarray(part[f], dtype=np.float64).reshape(n, k)
-        nan = np.isnan(a)
-        padded[j][:, idx] = np.where(nan, 0.0, a)
-        padded[F + j][:, idx] = nan
-    total = _all_reduced(dist, padded, group)
-    out = dict(points=pts.copy(), step=np.asarray(part["step"]).astype(np.int64), t=t.copy())
-    for j, f in enumerate(_capi.PROBE_FIELDS):
-        out[f] = np.where(total[F + j] > 0.0, np.nan, total[j])
-    out["n_dropped"] = int(part["n_dropped"])
-    return out
+    """One rank per process: pool_ring_probes of every rank's part, on every rank.  Collective."""
+    return pool_ring_probes(_ring_parts(dist, part, group))
 
 
 def all_reduce_ring_profile_series(sums, dist, group=None) -> dict:
-    """One rank per process: the ring's raw profile series from this rank's partial series, as pool_ring_profile_series; every
-    rank gets it.  The sizes, n_dropped and whether a rank's own series is well formed are all-gathered and checked first,
-    then step, t and y_mid; then the five fields, stacked, are all-reduced.  Collective; raises on every rank when a series is
-    malformed or the shape, n_dropped, step, t or y_mid differ between the ranks."""
-    try:
-        shape, why = _series_shape(sums), None
-        dropped = float(int(sums["n_dropped"]))
-    except (ValueError, KeyError, TypeError) as e:
-        shape, dropped, why = (-1, -1, -1), -1.0, str(e)
-    rows = _all_gathered(dist, [float(v) for v in shape] + [dropped, 0.0 if why is None else 1.0], group)
-    for r, row in enumerate(rows):
-        if row[4] != 0.0:
-            raise ValueError(f"rank {r}'s series is malformed" + (f": {why}" if why else ""))
-    for r, row in enumerate(rows):
-        if tuple(row[:4]) != tuple(rows[0][:4]):
-            raise ValueError(f"rank {r} holds {int(row[0])} records of {int(row[1])} bands x {int(row[2])} bins, {int(row[3])} "
-                             f"dropped; rank 0 {int(rows[0][0])} of {int(rows[0][1])} x {int(rows[0][2])}, {int(rows[0][3])}: the "
-                             "slabs of one ring share the config and record the same steps")
-    step, t = np.asarray(sums["step"], dtype=np.float64), np.asarray(sums["t"], dtype=np.float64)
-    y_mid = np.asarray(sums["y_mid"], dtype=np.float64)
-    clock = _all_gathered(dist, np.concatenate([step, t, y_mid]), group)
-    for r, row in enumerate(clock):
-        if not np.array_equal(row, clock[0]):  # (every rank sees every row: one odd rank out makes all of them raise)
-            raise ValueError(f"rank {r} recorded other steps or times (or holds other bin centres) than rank 0: the slabs of one "
-                             "ring record the same steps")
-    total = _all_reduced(dist, np.stack([np.asarray(sums[k], dtype=np.float64) for k in _SUMS]), group)
-    out = dict(step=np.asarray(sums["step"]).astype(np.int64), t=t.copy())
-    out.update({k: np.ascontiguousarray(total[j]) for j, k in enumerate(_SUMS)})
-    out.update(n_dropped=int(sums["n_dropped"]), y_mid=y_mid.copy())
-    return out
+    """One rank per process: pool_ring_profile_series of every rank's partial series, on every rank.  Collective."""
+    return pool_ring_profile_series(_ring_parts(dist, sums, group))
 
 
 def all_reduce_ring_pair_dist(part, dist, group=None) -> list:
-    """One rank per process: the ring's pair statistics from this rank's partial sums (HipSlabEngine.pairs_part_sums), as
-    pool_ring_pair_dist; every rank gets them.  The number of bands and bins, whether a rank's own list is well formed, r_edges
-    and the heads are all-gathered and checked first; then ff, fw and centres of all bands, stacked as int64, are all-reduced
-    with SUM and the bands' r2_min with MIN.  Collective; raises on every rank when a list is malformed or the bands, r_edges,
-    n_samples, t_first or t_last differ between the ranks."""
-    import torch
-    try:
-        bands, why = _pair_bands(part), None
-        shape = (len(bands), len(bands[0]["r_edges"]) - 1)
-        if any(len(d["r_edges"]) - 1 != shape[1] for d in bands):
-            raise ValueError("the bands of one slab share the bins")
-        head = [float(bands[0][k]) for k in _HEAD]
-    except (ValueError, KeyError, TypeError) as e:
-        bands, shape, head, why = None, (-1, -1), [0.0] * len(_HEAD), str(e)
-    rows = _all_gathered(dist, [float(v) for v in shape] + [0.0 if why is None else 1.0], group)
-    for r, row in enumerate(rows):
-        if row[2] != 0.0:
-            raise ValueError(f"rank {r}'s pair statistics are malformed" + (f": {why}" if why else ""))
-    for r, row in enumerate(rows):
-        if tuple(row[:2]) != tuple(rows[0][:2]):
-            raise ValueError(f"rank {r} holds {int(row[0])} bands of {int(row[1])} bins, rank 0 {int(rows[0][0])} of "
-                             f"{int(rows[0][1])}: the slabs of one ring share the config")
-    edges = _all_gathered(dist, np.concatenate([np.asarray(d["r_edges"], dtype=np.float64) for d in bands]), group)
-    for r, row in enumerate(edges):
-        if not np.array_equal(row, edges[0]):  # (every rank sees every row: one odd rank out makes all of them raise)
-            raise ValueError(f"rank {r} holds other bin edges than rank 0: the slabs of one ring share the bins")
-    _check_heads_agree([tuple(h) for h in _all_gathered(dist, head, group)])
-    counts = torch.from_numpy(np.stack([np.concatenate([np.asarray(d[k], dtype=np.int64) for k in _PAIR_COUNTS] +
-                                                       [np.array([int(d["centres"])], dtype=np.int64)]) for d in bands]))
-    dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
-    r2 = torch.tensor([float(d["r2_min"]) for d in bands], dtype=torch.float64)
-    dist.all_reduce(r2, op=dist.ReduceOp.MIN, group=group)
-    counts, r2 = counts.numpy(), r2.numpy()
-    n_bins = shape[1]
-    out = []
-    for b, d0 in enumerate(bands):
-        d = dict(r_edges=np.array(d0["r_edges"], dtype=np.float64), ff=counts[b, :n_bins].copy(), fw=counts[b, n_bins:2 * n_bins].copy(),
-                 centres=int(counts[b, 2 * n_bins]), r2_min=float(r2[b]), r_min=float(np.sqrt(r2[b])))
-        d.update({k: d0[k] for k in _HEAD})
-        out.append(d)
-    return out
+    """One rank per process: pool_ring_pair_dist of every rank's list of band dicts, on every rank.  Collective."""
+    return pool_ring_pair_dist(_ring_parts(dist, part, group))
 
 
 def all_reduce_ring_grad_stats(sums, dist, group=None) -> dict:
-    """One rank per process: the ring's gradient statistics of one band from this rank's partial sums
-    (HipSlabEngine.grads_part_sums(band)), as pool_ring_grad_stats; every rank gets them.  Whether a rank's own dict is well
-    formed, the number of bins and the heads are all-gathered and checked first; then the twelve fields, stacked, are
-    all-reduced with SUM.  Collective; raises on every rank when a dict is malformed or the bins, n_samples, t_first or t_last
-    differ between the ranks -- every rank makes the same calls up to the refusal, so the group stays in step."""
-    try:
-        n_bins, why = _grad_shape(sums, "?"), None
-        head = [float(sums[k]) for k in _HEAD]
-    except (ValueError, KeyError, TypeError) as e:
-        n_bins, head, why = -1, [0.0] * len(_HEAD), str(e)
-    rows = _all_gathered(dist, [float(n_bins), 0.0 if why is None else 1.0] + head, group)
-    for r, row in enumerate(rows):
-        if row[1] != 0.0:
-            raise ValueError(f"rank {r}'s gradient statistics are malformed" + (f": {why}" if why else ""))
-    for r, row in enumerate(rows):
-        if row[0] != rows[0][0]:
-            raise ValueError(f"rank {r} holds {int(row[0])} bins, rank 0 {int(rows[0][0])}: the slabs of one ring share the config")
-    _check_heads_agree([tuple(row[2:]) for row in rows])
-    total = _all_reduced(dist, np.stack([np.asarray(sums[f], dtype=np.float64) for f in GRAD_FIELDS]), group)
-    out = {f: total[j] for j, f in enumerate(GRAD_FIELDS)}
-    out.update({k: sums[k] for k in _HEAD})
-    return out
+    """One rank per process: pool_ring_grad_stats of every rank's sums of one band, on every rank.  Collective."""
+    return pool_ring_grad_stats(_ring_parts(dist, sums, group))
 
 
 def all_reduce_ring_tracers(part, dist, group=None, fold_DL=None) -> dict:
-    """One rank per process: the ring's tracers from this rank's part, as pool_ring_tracers; every rank gets them.  The sizes,
-    n_dropped and whether a rank's own part is well formed (its columns per record as many as its n_owned) are all-gathered
-    and checked first, then ids, step and t.  The values travel as BIT PATTERNS: every rank views its four fields as int64,
-    puts zeros where it was not the owner, and the arrays are all-reduced with SUM, together with a word per column in which
-    rank r sets bit r where it was the owner -- that word must have exactly one bit everywhere, and then every column had one
-    contributor and i + 0 is i, so the result is the owner's bytes, -0.0 included (a float sum would make +0.0 of it).
-    Collective; raises on every rank when a part is malformed, a column of a record has no owner or more than one, or ids,
-    step, t or n_dropped differ between the ranks."""
-    import torch
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    try:
-        if world > 62:
-            raise ValueError("at most 62 ranks")
-        T, n = _tracer_part_shape(part)
-        dropped, why = float(int(part["n_dropped"])), None
-    except (ValueError, KeyError, TypeError) as e:
-        T, n, dropped, why = -1, -1, -1.0, str(e)
-    rows = _all_gathered(dist, [float(T), float(n), dropped, 0.0 if why is None else 1.0], group)
-    for r, row in enumerate(rows):
-        if row[3] != 0.0:
-            raise ValueError(f"rank {r}'s part is malformed" + (f": {why}" if r == rank and why else ""))
-    for r, row in enumerate(rows):
-        if tuple(row[:3]) != tuple(rows[0][:3]):
-            raise ValueError(f"rank {r} holds {int(row[0])} tracers, {int(row[1])} records, {int(row[2])} dropped; rank 0 "
-                             f"{int(rows[0][0])}, {int(rows[0][1])}, {int(rows[0][2])}: the slabs of one ring share the list and "
-                             "record the same steps")
-    ids = np.asarray(part["ids"])
-    step, t = np.asarray(part["step"], dtype=np.float64), np.asarray(part["t"], dtype=np.float64)
-    mine = np.concatenate([ids.astype(np.float64), step, t])
-    for r, row in enumerate(_all_gathered(dist, mine, group)):
-        if not np.array_equal(row, mine):  # (every rank compares with its own: one odd rank out makes all of them raise)
-            raise ValueError(f"rank {r} holds other ids, steps or times than this rank")
-    F = len(_capi.TRACER_FIELDS)
-    mask = ~np.isnan(np.asarray(part["x"], dtype=np.float64)).reshape(n, T)
-    words = np.zeros((F + 1, n, T), dtype=np.int64)
-    for j, k in enumerate(_capi.TRACER_FIELDS):
-        bits = np.ascontiguousarray(np.asarray(part[k], dtype=np.float64).reshape(n, T)).view(np.int64)
-        words[j] = np.where(mask, bits, 0)
-    words[F] = mask.astype(np.int64) << rank
-    total = torch.from_numpy(words)
-    dist.all_reduce(total, op=dist.ReduceOp.SUM, group=group)
-    total = total.numpy()
-    _check_one_owner(total[F], step, ids)
-    out = dict(ids=np.array(ids, dtype=np.int32), step=np.asarray(part["step"]).astype(np.int64), t=t.copy())
-    for j, k in enumerate(_capi.TRACER_FIELDS):
-        out[k] = np.ascontiguousarray(total[j]).view(np.float64)
-    out.update(n_dropped=int(part["n_dropped"]), n_missing=0, owner=_owner_of(total[F]))
-    return _fold_tracers(out, fold_DL)
+    """One rank per process: pool_ring_tracers of every rank's part, on every rank.  Collective."""
+    return pool_ring_tracers(_ring_parts(dist, part, group), fold_DL)
 
 
 def all_reduce_ring_dens_stats(sums, dist, group=None) -> dict:
-    """One rank per process: the ring's density statistics of one band from this rank's partial sums
-    (HipSlabEngine.dens_part_sums(band)), as pool_ring_dens_stats; every rank gets them.  Whether a rank's own dict is well
-    formed, the numbers of bins and of histogram bins and the heads are all-gathered and checked first; then count, outliers and
-    the four summed fields, stacked, and the histogram with below and above behind it are all-reduced with SUM (the counts as
-    float64, exact below 2^53), d_min with MIN and d_max with MAX.  Collective; raises on every rank when a dict is malformed or
-    the bins, n_samples, t_first or t_last differ between the ranks -- every rank makes the same calls up to the refusal, so the
-    group stays in step."""
-    try:
-        (n_bins, n_hist), why = _dens_shape(sums, "?"), None
-        head = [float(sums[k]) for k in _HEAD]
-    except (ValueError, KeyError, TypeError) as e:
-        n_bins, n_hist, head, why = -1, -1, [0.0] * len(_HEAD), str(e)
-    rows = _all_gathered(dist, [float(n_bins), float(n_hist), 0.0 if why is None else 1.0] + head, group)
-    for r, row in enumerate(rows):
-        if row[2] != 0.0:
-            raise ValueError(f"rank {r}'s density statistics are malformed" + (f": {why}" if why else ""))
-    for r, row in enumerate(rows):
-        if row[0] != rows[0][0] or row[1] != rows[0][1]:
-            raise ValueError(f"rank {r} holds {int(row[0])} bins and {int(row[1])} histogram bins, rank 0 {int(rows[0][0])} and "
-                             f"{int(rows[0][1])}: the slabs of one ring share the config")
-    _check_heads_agree([tuple(row[3:]) for row in rows])
-    total = _all_reduced(dist, np.stack([np.asarray(sums[f], dtype=np.float64) for f in DENS_SUMS]), group)
-    counts = np.concatenate([np.asarray(sums["hist"], dtype=np.float64), [float(sums["below"]), float(sums["above"])]])
-    counts = np.rint(_all_reduced(dist, counts, group)).astype(np.int64)
-    out = {f: total[j] for j, f in enumerate(DENS_SUMS)}
-    out["d_min"] = _all_reduced(dist, sums["d_min"], group, dist.ReduceOp.MIN)
-    out["d_max"] = _all_reduced(dist, sums["d_max"], group, dist.ReduceOp.MAX)
-    out.update(hist=counts[:n_hist], below=int(counts[n_hist]), above=int(counts[n_hist + 1]))
-    if "hist_range" in sums:
-        out["hist_range"] = sums["hist_range"]
-    out.update({k: sums[k] for k in _HEAD})
-    return out
+    """One rank per process: pool_ring_dens_stats of every rank's sums of one band, on every rank.  Collective."""
+    return pool_ring_dens_stats(_ring_parts(dist, sums, group))
 
 
 class SlabDriver:

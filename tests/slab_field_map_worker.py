@@ -1,7 +1,7 @@
 """Worker for test_slab_field_map_host.py (CPU, gloo, two ranks): every rank holds one block of node columns of a particle
 set's Shepard planes; slab.all_reduce_ring_field_map must leave the whole planes on both, bit for bit what
 slab.pool_ring_field_map makes of the two blocks, and must raise on both when the heads differ or the blocks do not partition
-the grid.  Prints OK on every rank that saw all of it."""
+the grid -- after which a good call still gives the whole planes.  Prints OK on every rank that saw all of it."""
 import importlib
 import os
 import sys
@@ -59,6 +59,8 @@ def main():
             ok = False
         except ValueError:
             pass
+    again = slab.all_reduce_ring_field_map(parts[rank], dist)  # (the refusals left the group in step)
+    ok &= all(again[k].tobytes() == want[k].tobytes() for k in PLANES)
 
     print(f"rank {rank}: {'OK' if ok else 'WRONG'}", flush=True)
     dist.barrier()

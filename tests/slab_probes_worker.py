@@ -1,8 +1,8 @@
 """Worker for test_slab_probes_host.py (CPU, gloo, WORLD_SIZE ranks): every rank holds the columns of the probes it owns of a
 synthetic ring series with void probes (NaN velocities) in it; slab.all_reduce_ring_probes must leave the whole series on every
 rank, what slab.pool_ring_probes makes of the parts, NaNs exactly where the owner has them, and must raise on EVERY rank when
-one rank's steps, times, n_dropped or points differ or the indices do not partition the points.  Prints OK on every rank that
-saw all of it."""
+one rank's steps, times, n_dropped or points differ or the indices do not partition the points -- after which a good call
+still gives the whole series.  Prints OK on every rank that saw all of it."""
 import importlib
 import os
 import sys
@@ -80,6 +80,7 @@ def main():
             ok = False
         except ValueError:
             pass
+    ok &= same(slab.all_reduce_ring_probes(mine, dist), want)  # (the refusals left the group in step)
 
     print(f"rank {rank}: {'OK' if ok else 'WRONG'}", flush=True)
     dist.barrier()

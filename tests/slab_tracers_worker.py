@@ -1,8 +1,8 @@
 """Worker for test_slab_tracers_host.py (CPU, gloo, WORLD_SIZE ranks): every rank holds a dense part of a synthetic ring series
 of tracers -- NaN where it was not the owner, columns changing owner between records, a rank that owns nothing for a while, a
 value of -0.0 -- and slab.all_reduce_ring_tracers must leave the whole series on every rank, byte for byte what
-slab.pool_ring_tracers makes of the parts, and must raise on EVERY rank when one rank's part is bad.  Prints OK on every rank
-that saw all of it."""
+slab.pool_ring_tracers makes of the parts, and must raise on EVERY rank when one rank's part is bad -- after which a good call
+still gives the whole series.  Prints OK on every rank that saw all of it."""
 import importlib
 import os
 import sys
@@ -105,6 +105,7 @@ def main():
             print(f"rank {rank}: {name} went through", flush=True)
         except ValueError:
             pass
+    ok &= same(slab.all_reduce_ring_tracers(parts[rank], dist), got)  # (the refusals left the group in step)
 
     print(f"rank {rank}: {'OK' if ok else 'WRONG'}", flush=True)
     dist.barrier()

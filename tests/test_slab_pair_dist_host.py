@@ -108,6 +108,22 @@ def test_pool_ring_pair_dist_refuses_ranks_that_disagree(profmod, slab):
     assert slab.pool_ring_pair_dist(unsampled)[0]["n_samples"] == 0
 
 
+def test_pool_ring_pair_dist_refuses_a_slab_whose_bands_do_not_share_their_bins(profmod, slab):
+    """what only the collective form used to refuse: every rank alike holds a band with fewer bins than its band 0, so the
+    ranks agree with each other and each band's arrays fit its own r_edges"""
+    parts, _ = worker.partial_sums(profmod, 3)
+
+    def narrowed(p):
+        return [dict(d, r_edges=d["r_edges"][:-1], ff=d["ff"][:-1], fw=d["fw"][:-1]) if b == 1 else d for b, d in enumerate(p)]
+
+    with pytest.raises(ValueError, match="rank 0.*share the bins"):
+        slab.pool_ring_pair_dist([narrowed(p) for p in parts])
+    with pytest.raises(ValueError, match="rank 2.*share the bins"):
+        slab.pool_ring_pair_dist([parts[0], parts[1], narrowed(parts[2])])
+    with pytest.raises(ValueError, match="rank 1.*centres"):  # a band that lacks a key is a refusal too, not a KeyError
+        slab.pool_ring_pair_dist([parts[0], [{k: v for k, v in d.items() if k != "centres"} for d in parts[1]], parts[2]])
+
+
 def test_all_reduce_ring_pair_dist_in_two_gloo_processes():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",

@@ -98,6 +98,14 @@ def test_pool_ring_probes_refuses_ranks_that_disagree(slab):
             slab.pool_ring_probes([parts[0], dict(p, **bad), parts[2]])
 
 
+def test_pool_ring_probes_refuses_a_part_that_lacks_a_key(slab):
+    """what only the collective form used to turn into a refusal: a malformed part is a ValueError naming the rank"""
+    parts, _ = worker.series(3)
+    for key in ("n_dropped", "rho", "index"):
+        with pytest.raises(ValueError, match="rank 2.*" + key):
+            slab.pool_ring_probes([parts[0], parts[1], {k: v for k, v in parts[2].items() if k != key}])
+
+
 @pytest.mark.parametrize("world,port", [(2, 29593), (3, 29594)])
 def test_all_reduce_ring_probes_in_gloo_processes(world, port):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")

@@ -86,6 +86,14 @@ def test_pool_ring_profile_series_refuses_ranks_that_disagree(slab):
         slab.pool_ring_profile_series([dict(p, sum_uy=p["sum_uy"][:-1])])
 
 
+def test_pool_ring_profile_series_refuses_a_series_that_lacks_a_key(slab):
+    """what only the collective form used to turn into a refusal: a malformed series is a ValueError naming the rank"""
+    parts, _, _ = worker.partial_series(3)
+    for key in ("n_dropped", "sum_ux2", "y_mid"):
+        with pytest.raises(ValueError, match="rank 1.*" + key):
+            slab.pool_ring_profile_series([parts[0], {k: v for k, v in parts[1].items() if k != key}, parts[2]])
+
+
 def test_all_reduce_ring_profile_series_in_two_gloo_processes():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",

@@ -1,7 +1,7 @@
 """Samplers of a slab ring (include/sphx.h section 3a) without a GPU: the C ABI declares and exports the seven entry points, the
 engine has a context's argument checks, slab.pool_ring_sums / pool_ring_history make the unsplit channel's sums out of the
-ranks' partial sums and refuse ranks that disagree, and slab.all_reduce_ring_sums / _history do the same between two gloo
-processes on the CPU."""
+ranks' partial sums and refuse ranks that disagree, and slab.all_reduce_ring_sums / _history do the same between two and three
+gloo processes on the CPU -- three, so that the order of the float sums shows."""
 import importlib
 import os
 import re
@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import slab_samplers_worker as worker
 from helpers import HISTORY_FIELDS, STATS_FIELDS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -120,10 +121,40 @@ def test_pool_ring_history_refuses_ranks_that_disagree(slab):
         slab.pool_ring_history([recs[0], (recs[1][0][:-1], 0)])
 
 
-def test_all_reduce_ring_sums_and_history_in_two_gloo_processes():
+def test_pool_ring_sums_refuses_a_rank_with_other_bins(slab):
+    parts, _ = _three_ranks()
+    parts[1] = dict(parts[1], **{f: parts[1][f][:-1] for f in STATS_FIELDS})
+    with pytest.raises(ValueError, match="rank 1"):
+        slab.pool_ring_sums(parts)
+    with pytest.raises(ValueError, match="at least one slab"):
+        slab.pool_ring_sums([])
+
+
+def _gloo_workers(world, port):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", "29597", WORKER]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), WORKER]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    assert r.stdout.count("OK") == 2, r.stdout
+    assert r.stdout.count("OK") == world, r.stdout
+
+
+def test_all_reduce_ring_sums_and_history_in_two_gloo_processes():
+    _gloo_workers(2, 29597)
+
+
+def test_all_reduce_ring_sums_and_history_add_in_rank_order_in_three_gloo_processes(slab):
+    """Two terms cannot tell a summation order; these three can: (a + b) + c != a + (b + c) in the worker's parts, and what every
+    rank gets must be pool_ring_sums / pool_ring_history of the parts, which add one rank after the other."""
+    sums, recs = worker.ring_parts(3)
+    assert len(sums[0]["count"]) <= 48 and len(recs[0][0]) < 10
+    for f in STATS_FIELDS[1:]:
+        a, b, c = (s[f] for s in sums)
+        assert np.any((a + b) + c != a + (b + c)), f
+        assert np.array_equal(slab.pool_ring_sums(sums)[f], (a + b) + c), f
+    a, b, c = (r[0][:, worker.ADDITIVE:] for r in recs)
+    assert np.any((a + b) + c != a + (b + c))
+    pooled = slab.pool_ring_history(recs)
+    for j, k in enumerate(HISTORY_FIELDS[worker.ADDITIVE:]):
+        assert np.array_equal(pooled[k], ((a + b) + c)[:, j]), k
+    _gloo_workers(3, 29595)

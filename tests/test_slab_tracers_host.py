@@ -110,6 +110,25 @@ def test_pool_ring_tracers_refuses_ranks_that_disagree(slab):
             slab.pool_ring_tracers([parts[0], bads[name], parts[2]])
 
 
+def test_pool_ring_tracers_refuses_a_part_that_lacks_a_key(slab):
+    """what only the collective form used to turn into a refusal: a malformed part is a ValueError naming the rank"""
+    parts, _ = worker.series(3)
+    for key in ("n_dropped", "n_owned", "u_y"):
+        with pytest.raises(ValueError, match="rank 1.*" + key):
+            slab.pool_ring_tracers([parts[0], {k: v for k, v in parts[1].items() if k != key}, parts[2]])
+
+
+def test_pool_ring_tracers_takes_more_ranks_than_a_word_has_bits(slab):
+    """no cap on the world: 70 ranks, one record, every rank the owner of one column"""
+    world = 70
+    ids = np.arange(world, dtype=np.int32)
+    x = np.arange(world, dtype=np.float64)[None, :] + 0.5
+    parts = [dict({k: np.where(ids == r, x, np.nan) for k in FIELDS}, ids=ids, step=np.array([4]), t=np.array([0.5]),
+                  n_owned=np.array([1]), n_dropped=0) for r in range(world)]
+    got = slab.pool_ring_tracers(parts)
+    assert np.array_equal(got["owner"], ids[None, :].astype(np.int64)) and np.array_equal(got["x"], x)
+
+
 def test_pooled_series_goes_into_unwrap_tracers_in_either_frame(slab, profmod):
     parts, _ = worker.series(4)
     a = profmod.unwrap_tracers(slab.pool_ring_tracers(parts), worker.DL)
