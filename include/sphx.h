@@ -51,9 +51,21 @@ int sphx_set_device(int device);
  * one that went to hipMalloc, both counted since process start.  No HIP call: all zeros on a machine without a device.
  * sphx_pool_scrub: fill every cached free block of the current device with the 32-bit `word`, under the pool's lock, and wait
  * for the device; *n_blocks (may be NULL) = the blocks filled.  Free blocks are in nobody's use, so nothing else changes.
- * With nothing cached: 0 blocks and no HIP call.  Must not be called while a stream is capturing. */
+ * With nothing cached: 0 blocks and no HIP call.  Must not be called while a stream is capturing.
+ * sphx_pool_poison_on_free: test support, off by default.  on != 0: from now on a block that goes back into the cache is first
+ * filled with the 32-bit `word`, on a non-blocking stream the pool owns; that stream alone is waited for, under the pool's lock,
+ * before the block can be handed out again, so a late fill never overwrites a later owner.  Work the former owner left in
+ * flight on its own streams is NOT waited for: it races with the fill, and a block released too early shows as wrong numbers
+ * in its former owner's results -- or in its next owner's: a filled block is handed out before older blocks of its size class.
+ * Blocks that go straight to hipFree are not filled, nor are blocks freed on a thread that is
+ * inside one of the library's own stream captures.  on == 0: the free path is as before and makes no HIP call.  Toggling makes
+ * no HIP call.  Must not be called while a stream is capturing; the mode costs a stream wait per free and is not for timed runs.
+ * sphx_pool_poison_stats: out = { blocks filled, fills skipped inside a capture }, both counted since process start.  No HIP
+ * call: zeros on a machine without a device. */
 int sphx_pool_stats(uint64_t out[4]);
 int sphx_pool_scrub(uint32_t word, uint64_t *n_blocks);
+int sphx_pool_poison_on_free(int on, uint32_t word);
+int sphx_pool_poison_stats(uint64_t out[2]);
 
 /* ------------------------------------------------------------------------------------------------
  * 1. Stateless MEX-surface entry points (one per gateway call).  Host arrays in, host arrays out;
@@ -198,7 +210,8 @@ void sphx_ctx_destroy(sphx_ctx *ctx);
 
 /* Run steps until t >= t_target - 1e-12 (one pass of the inner while of SPH_Poiseuille.m:250; dt is
  * clipped by remain = min(t_target - t, t_end - t), :252) or until max_steps steps have been taken
- * (max_steps <= 0: unlimited).  Blocks until the device is idle. */
+ * (max_steps <= 0: unlimited).  Blocks until the device is idle.  Steps of sphx_ctx_enqueue_steps still in flight are
+ * waited for first, and the steps such a batch still owes are taken (see sphx_ctx_download): max_steps counts from there. */
 int sphx_ctx_advance(sphx_ctx *ctx, double t_target, int64_t max_steps, sphx_status *status);
 
 /* Enqueue exactly n_steps steps without host synchronisation (benchmark / pipelined use), dt clipped
@@ -229,7 +242,8 @@ int sphx_ctx_download(sphx_ctx *ctx, double *pos, double *vel, double *rho, doub
 int sphx_ctx_monitor(sphx_ctx *ctx, double *tau_bottom, double *tau_top, double *n_pairs);
 
 /* The neighbour list the context currently holds, in the MEX convention and the caller's original
- * row numbering (two-phase like sphx_neighbor_search / sphx_neighbor_fetch). */
+ * row numbering (two-phase like sphx_neighbor_search / sphx_neighbor_fetch).  Like sphx_ctx_download it first waits for
+ * everything enqueued and takes the steps still owed: the list is that of the state download hands out. */
 int sphx_ctx_neighbor_list(sphx_ctx *ctx, size_t *n_pairs);
 
 /* Average device time (ms) of each per-step kernel since the last call, measured with HIP events on

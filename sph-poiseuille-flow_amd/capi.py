@@ -108,7 +108,7 @@ class SphxStatus(C.Structure):
 
 EXPORTS = [
     "sphx_version", "sphx_last_error", "sphx_last_error_id", "sphx_device_count", "sphx_set_device",
-    "sphx_pool_stats", "sphx_pool_scrub",
+    "sphx_pool_stats", "sphx_pool_scrub", "sphx_pool_poison_on_free", "sphx_pool_poison_stats",
     "sphx_neighbor_search", "sphx_neighbor_fetch", "sphx_density_correction", "sphx_viscous_force",
     "sphx_transport_correction", "sphx_integration_1st", "sphx_integration_2nd",
     "sphx_integration_verlet", "sphx_advance_shell_step", "sphx_wall_shear_monitor",
@@ -221,6 +221,20 @@ def pool_scrub(word) -> int:
     n = C.c_uint64(0)
     check(lib().sphx_pool_scrub(C.c_uint32(int(word)), C.byref(n)))
     return int(n.value)
+
+
+def pool_poison_on_free(on, word=3) -> None:
+    """Test support, off by default: while on, every block that goes back into the pool's cache is first filled with the 32-bit
+    word on a stream of the pool's own, which alone is waited for.  Work its former owner left in flight races with the fill,
+    so a block released too early shows as wrong numbers (tests/test_gpu_live_neighbours.py).  Not while a stream is capturing."""
+    check(lib().sphx_pool_poison_on_free(C.c_int(1 if on else 0), C.c_uint32(int(word))))
+
+
+def pool_poison_stats() -> dict:
+    """Blocks filled by the poison-at-free mode and fills skipped inside a stream capture, since process start.  No device needed."""
+    out = (C.c_uint64 * 2)()
+    check(lib().sphx_pool_poison_stats(out))
+    return dict(filled=int(out[0]), skipped_in_capture=int(out[1]))
 
 
 def make_params(prm, t_end=None, transport_coeff=None, lanes_per_particle=0, steps_per_graph=0, rebuild_every=0,

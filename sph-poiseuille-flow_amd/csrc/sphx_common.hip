@@ -48,6 +48,11 @@ struct Pool {
     std::unordered_map<void *, int> owner;                      // block -> the device it was allocated on
     size_t cached = 0;
     uint64_t hits = 0, misses = 0;  // pool_alloc calls served from the cache / sent to hipMalloc, since process start
+    // poison at free (sphx_pool_poison_on_free, test support): off by default, and then pool_free makes no HIP call
+    bool poison = false;
+    uint32_t poison_word = 0;
+    uint64_t poisoned = 0, poison_skipped = 0;                  // blocks filled / fills skipped inside a capture, since process start
+    std::unordered_map<int, hipStream_t> poison_streams;        // device -> the pool's own non-blocking stream, made on first use
     static constexpr size_t kMaxCached = (size_t)4 << 30;
     void trim()
     {
@@ -64,7 +69,35 @@ Pool &pool()
     return *p;
 }
 
+thread_local int g_capturing = 0;  // CaptureScope depth of this thread
+
+// Fill a block on its way into the cache with the poison word, on the pool's own stream of the block's device, and wait for
+// that stream alone (the pool's lock is held): the fill has ended before any later owner can take the block.  Work the
+// former owner left in flight on its own streams is not waited for -- it races with the fill, which is what the mode is for.
+void poison_block(Pool &P, void *p, size_t cls, int dev)
+{
+    if (g_capturing) { ++P.poison_skipped; return; }
+    int cur = 0;
+    SPHX_HIP(hipGetDevice(&cur));
+    if (cur != dev) SPHX_HIP(hipSetDevice(dev));
+    hipError_t e = hipSuccess;
+    auto it = P.poison_streams.find(dev);
+    if (it == P.poison_streams.end()) {
+        hipStream_t st = nullptr;
+        e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+        if (e == hipSuccess) it = P.poison_streams.emplace(dev, st).first;
+    }
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)p, (int)P.poison_word, cls / sizeof(uint32_t), it->second);
+    if (e == hipSuccess) e = hipStreamSynchronize(it->second);
+    if (cur != dev) (void)hipSetDevice(cur);
+    SPHX_HIP(e);
+    ++P.poisoned;
+}
+
 }  // namespace
+
+CaptureScope::CaptureScope() { ++g_capturing; }
+CaptureScope::~CaptureScope() { --g_capturing; }
 
 void *pool_alloc(size_t bytes)
 {
@@ -115,7 +148,19 @@ void pool_free(void *p, size_t bytes)
         (void)hipFree(p);
         return;
     }
-    P.free_blocks.insert({{it->second, cls}, p});
+    const std::pair<int, size_t> key{it->second, cls};
+    if (P.poison) {
+        try {
+            poison_block(P, p, cls, it->second);
+        } catch (const Error &) { /* pool_free runs in destructors: a fill that failed leaves the block as it was returned */
+            (void)hipGetLastError();
+        }
+        // ... and goes to the FRONT of its class: the next request of that size gets the block released last, so a neighbour
+        // takes a block released too early while its former owner is still at work, not an older one out of a warm cache
+        P.free_blocks.insert(P.free_blocks.lower_bound(key), {key, p});
+    } else {
+        P.free_blocks.insert({key, p});
+    }
     P.cached += cls;
 }
 
@@ -127,6 +172,22 @@ void pool_stats(uint64_t out[4])
     out[1] = P.free_blocks.size();
     out[2] = P.hits;
     out[3] = P.misses;
+}
+
+void pool_poison_on_free(bool on, uint32_t word)
+{
+    Pool &P = pool();
+    std::lock_guard<std::mutex> lk(P.m);
+    P.poison = on;
+    P.poison_word = word;
+}
+
+void pool_poison_stats(uint64_t out[2])
+{
+    Pool &P = pool();
+    std::lock_guard<std::mutex> lk(P.m);
+    out[0] = P.poisoned;
+    out[1] = P.poison_skipped;
 }
 
 uint64_t pool_scrub(uint32_t word)
@@ -195,6 +256,23 @@ SPHX_EXPORT int sphx_pool_scrub(uint32_t word, uint64_t *n_blocks)
     SPHX_TRY
     const uint64_t n = sphx::pool_scrub(word);
     if (n_blocks) *n_blocks = n;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_pool_poison_on_free(int on, uint32_t word)
+{
+    SPHX_TRY
+    sphx::pool_poison_on_free(on != 0, word);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_pool_poison_stats(uint64_t out[2])
+{
+    SPHX_TRY
+    sphx::require(out != nullptr, "SPHX:Pool:args", "sphx_pool_poison_stats: out must not be NULL");
+    sphx::pool_poison_stats(out);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -57,6 +57,23 @@ void pool_free(void *p, size_t bytes);
 // and returns the number of blocks filled; the allocation path is untouched.  Not while a stream is capturing.
 void pool_stats(uint64_t out[4]);
 uint64_t pool_scrub(uint32_t word);
+// Poison at free (sphx_pool_poison_on_free / sphx_pool_poison_stats, test support; off by default, and then pool_free is
+// unchanged and makes no HIP call).  On: a block entering the cache is first filled with `word` on a non-blocking stream the
+// pool owns, and that stream alone is waited for under the pool's lock -- no later owner can be overwritten by a late fill,
+// while work the former owner left in flight races with the fill and shows in the bytes it produces.  A filled block is
+// handed out before older blocks of its class, so the next taker of that size is the one that meets the former owner.  The invariant this
+// makes visible: a block returns to the pool only after every stream that was given it has been waited for
+// (tests/test_gpu_live_neighbours.py).  Blocks that go straight to hipFree are not filled, nor are blocks freed on a thread
+// that is inside one of the library's stream captures (a CaptureScope): those are counted in out[1], the fills in out[0].
+void pool_poison_on_free(bool on, uint32_t word);
+void pool_poison_stats(uint64_t out[2]);
+// Marks the calling thread as inside a hipStreamBeginCapture / hipStreamEndCapture pair of the library for its lifetime.
+struct CaptureScope {
+    CaptureScope();
+    ~CaptureScope();
+    CaptureScope(const CaptureScope &) = delete;
+    CaptureScope &operator=(const CaptureScope &) = delete;
+};
 
 template <typename T>
 class DevBuf {

@@ -587,7 +587,7 @@ private:
         hipLaunchKernelGGL(inc_rank, dim3(row_blocks()), dim3(kBlock), 0, 0, I_, (const int *)row_.get(),
                            (const unsigned *)arrival.get(), ent_.get());
         SPHX_HIP(hipGetLastError());
-        SPHX_HIP(hipDeviceSynchronize());  // the build's scratch arrays go back to the pool here
+        SPHX_HIP(hipStreamSynchronize(nullptr));  // the build's scratch arrays go back to the pool here
     }
     DevBuf<double> first_, second_, dx_, dy_, r_, W_, dW_;
     DevBuf<int> row_;
@@ -659,7 +659,7 @@ struct Modes {
         hipLaunchKernelGGL(g_kick, dim3(ga()), dim3(kBlock), 0, 0, nf, nt, vel, force_prior, (const double *)force_out, mass, dt, vel_out);
         second_half(Vol, rho_h.get(), pos_h.get(), vel_out, dt, wall_vel, rho0, p0, 1, pos_out, drho_out, rho_out, p_out);
         SPHX_HIP(hipGetLastError());
-        SPHX_HIP(hipDeviceSynchronize());  // the half-step arrays die here
+        SPHX_HIP(hipStreamSynchronize(nullptr));  // the half-step arrays die here
     }
 };
 
@@ -672,10 +672,13 @@ struct Up {  // host array -> device copy
 void check_counts(int nf, int nt, const char *id) { require(nf > 0 && nt >= nf, id, "Invalid n_fluid/n_total."); }
 void check_pairs(size_t n_pairs, const char *id) { require(n_pairs <= (size_t)2147483647, id, "Pair count exceeds INT_MAX."); }
 
+// Every kernel and copy of the stateless modes runs on the null stream, so that stream is the one to wait for before their
+// arrays go back to the pool.  Not the device: a device-wide wait is refused while ANY thread captures a stream (another
+// thread's context capturing its step graph, include/sphx.h "one caller thread per context") and spoils that capture.
 void finish()
 {
     SPHX_HIP(hipGetLastError());
-    SPHX_HIP(hipDeviceSynchronize());
+    SPHX_HIP(hipStreamSynchronize(nullptr));
 }
 
 }  // namespace

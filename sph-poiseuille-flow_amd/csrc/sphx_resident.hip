@@ -929,24 +929,27 @@ Schedule::Graph &capture_slots(Schedule &s, hipStream_t st, int K, int n, const 
         SPHX_HIP(hipStreamSynchronize(st));  // earlier batches may still be replaying the graphs about to be destroyed
         s.drop_graphs();
     }
-    SPHX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    try {
-        int q = s.cur, l = s.lay, p = s.pos;
-        for (int j = 0; j < n; ++j) {
-            const bool rebuild = p == K - 1;
-            slot(q, l, p, rebuild);
-            if (rebuild) { l ^= 1; p = 0; }
-            else ++p;
-            q ^= 1;
-        }
-    } catch (...) {
-        hipGraph_t junk = nullptr;
-        (void)hipStreamEndCapture(st, &junk);
-        if (junk) (void)hipGraphDestroy(junk);
-        throw;
-    }
     hipGraph_t g = nullptr;
-    SPHX_HIP(hipStreamEndCapture(st, &g));
+    {
+        CaptureScope capturing;  // (a pool_free on this thread in here is not poison-filled: a fill cannot join a capture)
+        SPHX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        try {
+            int q = s.cur, l = s.lay, p = s.pos;
+            for (int j = 0; j < n; ++j) {
+                const bool rebuild = p == K - 1;
+                slot(q, l, p, rebuild);
+                if (rebuild) { l ^= 1; p = 0; }
+                else ++p;
+                q ^= 1;
+            }
+        } catch (...) {
+            hipGraph_t junk = nullptr;
+            (void)hipStreamEndCapture(st, &junk);
+            if (junk) (void)hipGraphDestroy(junk);
+            throw;
+        }
+        SPHX_HIP(hipStreamEndCapture(st, &g));
+    }
     hipGraphExec_t exec = nullptr;
     const hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
@@ -1664,12 +1667,16 @@ SPHX_EXPORT void sphx_ctx_destroy(sphx_ctx *ctx)
     delete ctx;
 }
 
+static void settle_owed(sphx_ctx *c);
+
 SPHX_EXPORT int sphx_ctx_advance(sphx_ctx *c, double t_target, int64_t max_steps, sphx_status *status)
 {
     SPHX_TRY
     require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
     require(!c->is_slab, "SPHX:Ctx:slab", "slab contexts are advanced with sphx_slab_compute/finish");
-    read_clock(c);  // steps enqueued with sphx_ctx_enqueue_steps may still be in flight
+    // steps enqueued with sphx_ctx_enqueue_steps may still be in flight, and a batch of them that stopped early (stale grid)
+    // still owes steps: they are taken first, as sphx_ctx_sync would -- "exactly n_steps" holds whatever call comes next
+    settle_owed(c);
     for (int guard = 0; guard < 1000000; ++guard) {
         if (c->h_clock->need_rebuild && c->h_clock->status == 0) forced_rebuild(c);
         arm_clock(c, t_target, (long long)max_steps, c->sched.cur, (const double *)nullptr);
@@ -1889,7 +1896,7 @@ SPHX_EXPORT int sphx_ctx_neighbor_list(sphx_ctx *c, size_t *n_pairs)
     SPHX_TRY
     require(c != nullptr && n_pairs != nullptr, "SPHX:Ctx:null", "ctx / n_pairs must not be NULL");
     require(!c->is_slab, "SPHX:Ctx:slab", "pair lists are not available on a slab context");
-    read_clock(c);
+    settle_owed(c);  // (the list of the last step of everything enqueued, like the state sphx_ctx_download hands out)
     if (c->h_clock->need_rebuild && c->h_clock->status == 0) forced_rebuild(c);
     emit_pairs(c, true);
     *n_pairs = c->pl_n;
@@ -3185,21 +3192,25 @@ template <typename T> void slab_graph_prepare(T &t)
         c->a_interior_done = false;  // (the graph's first step sweeps / walks everything)
     }
     auto restore_streams = [&]() { size_t r = 0; for (sphx_ctx *c : t) c->stream = own_streams[r++]; };
-    const hipError_t e_begin = hipStreamBeginCapture(s0, hipStreamCaptureModeRelaxed);
-    if (e_begin != hipSuccess) { restore_streams(); SPHX_HIP(e_begin); }
-    t.captured = true;
-    try {
-        for (int k = 0; k < kSlabGraphSteps; ++k) slab_step(t);
-    } catch (...) {
-        abandon_capture(s0);
+    hipError_t e_end = hipSuccess;
+    {
+        CaptureScope capturing;
+        const hipError_t e_begin = hipStreamBeginCapture(s0, hipStreamCaptureModeRelaxed);
+        if (e_begin != hipSuccess) { restore_streams(); SPHX_HIP(e_begin); }
+        t.captured = true;
+        try {
+            for (int k = 0; k < kSlabGraphSteps; ++k) slab_step(t);
+        } catch (...) {
+            abandon_capture(s0);
+            restore_streams();
+            for (sphx_ctx *c : t) { c->sched.cur = cur0; c->slab_steps_enqueued = enq0; }
+            throw;
+        }
+        t.captured = false;
         restore_streams();
-        for (sphx_ctx *c : t) { c->sched.cur = cur0; c->slab_steps_enqueued = enq0; }
-        throw;
+        for (sphx_ctx *c : t) { c->slab_steps_enqueued -= kSlabGraphSteps; c->a_interior_done = false; }  // nothing has executed
+        e_end = hipStreamEndCapture(s0, &g);
     }
-    t.captured = false;
-    restore_streams();
-    for (sphx_ctx *c : t) { c->slab_steps_enqueued -= kSlabGraphSteps; c->a_interior_done = false; }  // nothing has executed
-    const hipError_t e_end = hipStreamEndCapture(s0, &g);
     if (e_end != hipSuccess) { (void)hipGetLastError(); if (g) (void)hipGraphDestroy(g); SPHX_HIP(e_end); }
     hipGraphExec_t exec = nullptr;
     const hipError_t e_inst = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);

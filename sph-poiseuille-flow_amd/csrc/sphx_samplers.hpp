@@ -58,6 +58,16 @@ S &sampler_of(sphx_ctx *c, S sphx_ctx::*which, const SamplerNames &n, bool need_
     return c->*which;
 }
 
+// ... for a change of its setting (enable, disable): what is enqueued lands first, the steps a batch of
+// sphx_ctx_enqueue_steps still owes included, as for a read or a reset -- they were asked for under the old setting
+template <typename S>
+S &sampler_to_change(sphx_ctx *c, S sphx_ctx::*which, const SamplerNames &n)
+{
+    S &x = sampler_of(c, which, n, false);
+    settle_owed(c);
+    return x;
+}
+
 // The replayed graphs of schedule s carry a sampler's launch (and its arguments) or not: a change of the setting waits for
 // what is enqueued and drops them, so the next enqueue captures them again.
 template <typename S>
@@ -487,7 +497,7 @@ void stats_read(const FlowStats &f, hipStream_t st, Settle &&settle, int band, i
 SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_config *cfg)
 {
     SPHX_TRY
-    FlowStats &f = sampler_of(c, &sphx_ctx::fstats, kStatsNames, false);
+    FlowStats &f = sampler_to_change(c, &sphx_ctx::fstats, kStatsNames);
     stats_enable(f, c->prm, cfg, 1, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -496,7 +506,7 @@ SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_co
 SPHX_EXPORT int sphx_ctx_flow_stats_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    FlowStats &f = sampler_of(c, &sphx_ctx::fstats, kStatsNames, false);
+    FlowStats &f = sampler_to_change(c, &sphx_ctx::fstats, kStatsNames);
     if (f.on) sampler_off(f, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -603,7 +613,7 @@ void history_enable(History &h, const sphx_history_config *cfg, int M, Schedule 
 SPHX_EXPORT int sphx_ctx_history_enable(sphx_ctx *c, const sphx_history_config *cfg)
 {
     SPHX_TRY
-    History &h = sampler_of(c, &sphx_ctx::hist, kHistoryNames, false);
+    History &h = sampler_to_change(c, &sphx_ctx::hist, kHistoryNames);
     history_enable(h, cfg, 1, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -612,7 +622,7 @@ SPHX_EXPORT int sphx_ctx_history_enable(sphx_ctx *c, const sphx_history_config *
 SPHX_EXPORT int sphx_ctx_history_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    History &h = sampler_of(c, &sphx_ctx::hist, kHistoryNames, false);
+    History &h = sampler_to_change(c, &sphx_ctx::hist, kHistoryNames);
     if (h.on) sampler_off(h, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -712,7 +722,7 @@ void field_read(const FieldMap &f, hipStream_t st, Settle &&settle, int capacity
 SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_config *cfg)
 {
     SPHX_TRY
-    FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, false);
+    FieldMap &f = sampler_to_change(c, &sphx_ctx::fmap, kFieldNames);
     field_enable(f, c->prm, cfg, 1, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -721,7 +731,7 @@ SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_conf
 SPHX_EXPORT int sphx_ctx_field_map_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, false);
+    FieldMap &f = sampler_to_change(c, &sphx_ctx::fmap, kFieldNames);
     if (f.on) sampler_off(f, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -881,7 +891,7 @@ void probes_enable(Probes &p, const sphx_params &prm, const sphx_probes_config *
 SPHX_EXPORT int sphx_ctx_probes_enable(sphx_ctx *c, const sphx_probes_config *cfg)
 {
     SPHX_TRY
-    Probes &p = sampler_of(c, &sphx_ctx::probes, kProbeNames, false);
+    Probes &p = sampler_to_change(c, &sphx_ctx::probes, kProbeNames);
     probes_enable(p, c->prm, cfg, 1, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -890,7 +900,7 @@ SPHX_EXPORT int sphx_ctx_probes_enable(sphx_ctx *c, const sphx_probes_config *cf
 SPHX_EXPORT int sphx_ctx_probes_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    Probes &p = sampler_of(c, &sphx_ctx::probes, kProbeNames, false);
+    Probes &p = sampler_to_change(c, &sphx_ctx::probes, kProbeNames);
     if (p.on) sampler_off(p, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1048,7 +1058,7 @@ void tracers_read(Tracers &t, hipStream_t st, Settle &&settle, int capacity, dou
 SPHX_EXPORT int sphx_ctx_tracers_enable(sphx_ctx *c, const sphx_tracers_config *cfg)
 {
     SPHX_TRY
-    Tracers &t = sampler_of(c, &sphx_ctx::tracers, kTracerNames, false);
+    Tracers &t = sampler_to_change(c, &sphx_ctx::tracers, kTracerNames);
     tracers_enable(t, c->nf, c->nt, cfg, 1, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1057,7 +1067,7 @@ SPHX_EXPORT int sphx_ctx_tracers_enable(sphx_ctx *c, const sphx_tracers_config *
 SPHX_EXPORT int sphx_ctx_tracers_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    Tracers &t = sampler_of(c, &sphx_ctx::tracers, kTracerNames, false);
+    Tracers &t = sampler_to_change(c, &sphx_ctx::tracers, kTracerNames);
     if (t.on) sampler_off(t, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1194,7 +1204,7 @@ void series_read(ProfileSeries &p, hipStream_t st, Settle &&settle, int capacity
 SPHX_EXPORT int sphx_ctx_profile_series_enable(sphx_ctx *c, const sphx_profile_series_config *cfg)
 {
     SPHX_TRY
-    ProfileSeries &p = sampler_of(c, &sphx_ctx::pseries, kSeriesNames, false);
+    ProfileSeries &p = sampler_to_change(c, &sphx_ctx::pseries, kSeriesNames);
     series_enable(p, c->prm, cfg, 1, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1203,7 +1213,7 @@ SPHX_EXPORT int sphx_ctx_profile_series_enable(sphx_ctx *c, const sphx_profile_s
 SPHX_EXPORT int sphx_ctx_profile_series_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    ProfileSeries &p = sampler_of(c, &sphx_ctx::pseries, kSeriesNames, false);
+    ProfileSeries &p = sampler_to_change(c, &sphx_ctx::pseries, kSeriesNames);
     if (p.on) sampler_off(p, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1332,7 +1342,7 @@ void pair_dist_read(const PairDist &p, hipStream_t st, Settle &&settle, int band
 SPHX_EXPORT int sphx_ctx_pair_dist_enable(sphx_ctx *c, const sphx_pair_dist_config *cfg)
 {
     SPHX_TRY
-    PairDist &p = sampler_of(c, &sphx_ctx::pairs, kPairNames, false);
+    PairDist &p = sampler_to_change(c, &sphx_ctx::pairs, kPairNames);
     pair_dist_enable(p, c->prm, cfg, 1, c->nw > 0, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1341,7 +1351,7 @@ SPHX_EXPORT int sphx_ctx_pair_dist_enable(sphx_ctx *c, const sphx_pair_dist_conf
 SPHX_EXPORT int sphx_ctx_pair_dist_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    PairDist &p = sampler_of(c, &sphx_ctx::pairs, kPairNames, false);
+    PairDist &p = sampler_to_change(c, &sphx_ctx::pairs, kPairNames);
     if (p.on) sampler_off(p, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1464,7 +1474,7 @@ void grad_stats_read(const GradStats &f, hipStream_t st, Settle &&settle, int ba
 SPHX_EXPORT int sphx_ctx_grad_stats_enable(sphx_ctx *c, const sphx_grad_stats_config *cfg)
 {
     SPHX_TRY
-    GradStats &f = sampler_of(c, &sphx_ctx::grads, kGradNames, false);
+    GradStats &f = sampler_to_change(c, &sphx_ctx::grads, kGradNames);
     grad_stats_enable(f, c->prm, cfg, 1, c->nw > 0, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1473,7 +1483,7 @@ SPHX_EXPORT int sphx_ctx_grad_stats_enable(sphx_ctx *c, const sphx_grad_stats_co
 SPHX_EXPORT int sphx_ctx_grad_stats_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    GradStats &f = sampler_of(c, &sphx_ctx::grads, kGradNames, false);
+    GradStats &f = sampler_to_change(c, &sphx_ctx::grads, kGradNames);
     if (f.on) sampler_off(f, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1623,7 +1633,7 @@ void dens_stats_read(const DensStats &f, hipStream_t st, Settle &&settle, int m,
 SPHX_EXPORT int sphx_ctx_dens_stats_enable(sphx_ctx *c, const sphx_dens_stats_config *cfg)
 {
     SPHX_TRY
-    DensStats &f = sampler_of(c, &sphx_ctx::dens, kDensNames, false);
+    DensStats &f = sampler_to_change(c, &sphx_ctx::dens, kDensNames);
     dens_stats_enable(f, c->prm, cfg, 1, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
@@ -1632,7 +1642,7 @@ SPHX_EXPORT int sphx_ctx_dens_stats_enable(sphx_ctx *c, const sphx_dens_stats_co
 SPHX_EXPORT int sphx_ctx_dens_stats_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    DensStats &f = sampler_of(c, &sphx_ctx::dens, kDensNames, false);
+    DensStats &f = sampler_to_change(c, &sphx_ctx::dens, kDensNames);
     if (f.on) sampler_off(f, c->sched, c->stream);
     return SPHX_OK;
     SPHX_CATCH
