@@ -268,6 +268,10 @@ int sphx_ctx_grid_policy(sphx_ctx *ctx, int *rebuild_every, double *skin, int64_
 /* The launch shape the context chose (lanes cooperating per particle, steps per hipGraph replay). */
 int sphx_ctx_tuning(sphx_ctx *ctx, int *lanes_per_particle, int *steps_per_graph);
 
+/* Threads per workgroup of the compact step kernels (16 / 32 lanes per particle): 64, 128 or 256.  256 for every context
+ * that does not run them, and for batches, slabs and dynamic contexts. */
+int sphx_ctx_block_size(sphx_ctx *ctx, int *block_size);
+
 /* The launch schedule the context runs: fuse_ea = pass E of a step and pass A of the next one share a launch
  * (three launches per step), tail_clock = the clock update rides in the last launch of a step, dynamic = the device
  * decides when to re-bin; rebins = re-binnings carried out by step slots so far (scheduled ones; dynamic contexts:

@@ -115,7 +115,7 @@ EXPORTS = [
     "sphx_ctx_create", "sphx_ctx_destroy", "sphx_ctx_advance", "sphx_ctx_enqueue_steps", "sphx_ctx_sync",
     "sphx_ctx_prepare_steps", "sphx_ctx_graph_stats",
     "sphx_ctx_download", "sphx_ctx_monitor", "sphx_ctx_neighbor_list", "sphx_ctx_profile_enable",
-    "sphx_ctx_profile_read", "sphx_ctx_info", "sphx_ctx_tuning", "sphx_ctx_substeps", "sphx_ctx_schedule", "sphx_ctx_kernel_forms", "sphx_ctx_grid_policy", "sphx_ctx_time_kernel",
+    "sphx_ctx_profile_read", "sphx_ctx_info", "sphx_ctx_tuning", "sphx_ctx_block_size", "sphx_ctx_substeps", "sphx_ctx_schedule", "sphx_ctx_kernel_forms", "sphx_ctx_grid_policy", "sphx_ctx_time_kernel",
     "sphx_ctx_flow_stats_enable", "sphx_ctx_flow_stats_disable", "sphx_ctx_flow_stats_reset", "sphx_ctx_flow_stats_sample",
     "sphx_ctx_flow_stats_read",
     "sphx_ctx_history_enable", "sphx_ctx_history_disable", "sphx_ctx_history_read",
@@ -998,7 +998,16 @@ class Context(_Stepped):
     def tuning(self):
         a, b = C.c_int(0), C.c_int(0)
         check(lib().sphx_ctx_tuning(self._h, C.byref(a), C.byref(b)))
-        return dict(lanes_per_particle=a.value, steps_per_graph=b.value)
+        return dict(lanes_per_particle=a.value, steps_per_graph=b.value, block_size=self.block_size())
+
+    def block_size(self) -> int:
+        """Threads per workgroup of the compact step kernels (sphx_ctx_block_size); 256 with a library from before the choice."""
+        f = getattr(lib(), "sphx_ctx_block_size", None)
+        if f is None:
+            return 256
+        n = C.c_int(0)
+        check(f(self._h, C.byref(n)))
+        return n.value
 
     def schedule(self):
         """Launch schedule in force and the re-binnings carried out by step slots so far (sphx_ctx_schedule)."""

@@ -360,16 +360,23 @@ __device__ __forceinline__ double tracked_drift2(const Grid &g, const FluidSet &
 }
 // ... and its maximum over the workgroup -> t.dpart[blk]: the largest drift from the binning positions bounds how stale the cell
 // grid may get (Clock::drift).  Every thread of the workgroup calls this (one barrier).
+// BLK: the threads of the workgroup.  A one-wave workgroup (BLK = 64) has no workgroup epilogue: the wave's maximum is the entry,
+// no LDS, no barrier.
+template <int BLK = kBlock>
 __device__ __forceinline__ void store_block_drift(const FluidTmp &t, int blk, double d2)
 {
     d2 = wave_max(d2);
-    __shared__ double s_d2[kBlock / 64];
-    if ((threadIdx.x & 63) == 0) s_d2[threadIdx.x >> 6] = d2;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double m = s_d2[0];
-        for (int k = 1; k < kBlock / 64; ++k) m = fmax(m, s_d2[k]);
-        t.dpart[blk] = m;
+    if constexpr (BLK == 64) {
+        if (threadIdx.x == 0) t.dpart[blk] = d2;
+    } else {
+        __shared__ double s_d2[BLK / 64];
+        if ((threadIdx.x & 63) == 0) s_d2[threadIdx.x >> 6] = d2;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double m = s_d2[0];
+            for (int k = 1; k < BLK / 64; ++k) m = fmax(m, s_d2[k]);
+            t.dpart[blk] = m;
+        }
     }
 }
 
@@ -614,11 +621,13 @@ __device__ __forceinline__ void list_push_w(const LaneGroup<LPP> &lg, int *idx, 
 
 // Prologue shared by the passes: everything whose address does not depend on the clock is requested
 // BEFORE the run flag is looked at, so the clock read overlaps the particle's own loads.
-#define SPHX_PASS_INDEX_AT(bid, nblk)                                      \
+// (threads: those of the workgroup -- the compact passes take it as a template parameter, BLK; nblk counts workgroups of that size)
+#define SPHX_PASS_INDEX_BLK(bid, nblk, threads)                            \
     const int blk = xcd_block((bid), (nblk));                              \
-    const int tid = blk * kBlock + threadIdx.x;                            \
+    const int tid = blk * (threads) + threadIdx.x;                         \
     const int i = tid / LPP, sub = tid % LPP;                              \
     const bool in_cap = i < t.cap
+#define SPHX_PASS_INDEX_AT(bid, nblk) SPHX_PASS_INDEX_BLK(bid, nblk, kBlock)
 #define SPHX_PASS_INDEX() SPHX_PASS_INDEX_AT((int)blockIdx.x, (int)gridDim.x)
 
 // Compact kernels at 16 and 32 lanes per particle (kRowsAhead): a pass is a chain of dependent memory round trips behind a launch,
@@ -718,11 +727,11 @@ __device__ __forceinline__ void store_density(const Phys &ph, const FluidTmp &t,
 // launch k_continuity_density runs the pass in a sub-range of its grid; PassWg).  half: also write the half-step density /
 // pressure (needs the step's dt; the fused launch runs pass A of the NEXT step, whose dt is not known yet -- pass B completes
 // the record there).
-template <int LPP, int MODE>
+template <int LPP, int MODE, int BLK = kBlock>
 __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                              const FluidTmp &t, const Walls &w, PassWg bid, int nblk, bool half)
 {
-    SPHX_PASS_INDEX_AT(bid, nblk);
+    SPHX_PASS_INDEX_BLK(bid, nblk, BLK);
     // the walk at 16 / 32 lanes: row count, first rows and the clock's words leave first (leading arguments, see ListHead)
     constexpr bool kHot = MODE == 2 && kRowsAhead<LPP>;
     constexpr int kAhead = kHot ? 64 / LPP : 2;
@@ -913,10 +922,10 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
 // does not touch -- launched right behind k_slab_pack3; part = 2: the rest (boundary workgroups), behind k_slab_unpack3.
 // part rides in the walk kernels' cond_fresh argument: bits 4 and up (kPassPartShift).
 constexpr int kPassPartShift = 4;
-template <int LPP>
+template <int LPP, int BLK = kBlock>
 __device__ __forceinline__ bool slab_part_skips(const Grid &g, const FluidSet &s, int blk, int part)
 {
-    const int first = blk * (kBlock / LPP), last = first + kBlock / LPP - 1;
+    const int first = blk * (BLK / LPP), last = first + BLK / LPP - 1;
     const int lo = s.start[(g.own_c0 + 1) * g.ncy], hi = s.start[(g.own_c1 - 1) * g.ncy];
     const bool interior = first >= lo && last < hi;
     return interior != (part == 1);
@@ -926,15 +935,15 @@ __device__ __forceinline__ bool slab_part_skips(const Grid &g, const FluidSet &s
 // 0 = only on a grid that is not fresh.  Measured at 6 M particles, average pass A per step: two launches of which one
 // returns 786 us; one kernel holding both bodies 891 us (it runs at the register budget of the bigger one); one
 // body deciding per candidate at run time 795 us.
-template <int LPP, int MODE>
+template <int LPP, int MODE, int BLK = kBlock>
 __device__ __forceinline__ void density_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                              const FluidTmp &t, const Walls &w, int cond_fresh, int nblk)
 {
     const int part = cond_fresh >= 0 ? cond_fresh >> kPassPartShift : 0;
     if (part) cond_fresh &= (1 << kPassPartShift) - 1;
     if (cond_fresh >= 0 && (clk->fresh != 0) != (cond_fresh != 0)) return;
-    if (MODE == 2 && part && slab_part_skips<LPP>(g, s, xcd_block((int)blockIdx.x, nblk), part)) return;
-    density_body<LPP, MODE>(clk, q, g, ph, s, t, w, (int)blockIdx.x, nblk, true);
+    if (MODE == 2 && part && slab_part_skips<LPP, BLK>(g, s, xcd_block((int)blockIdx.x, nblk), part)) return;
+    density_body<LPP, MODE, BLK>(clk, q, g, ph, s, t, w, (int)blockIdx.x, nblk, true);
 }
 template <int LPP, int MODE>
 __global__ __launch_bounds__(kBlock) void k_density(const Clock *clk, int q, Grid g, Phys ph,
@@ -942,14 +951,14 @@ __global__ __launch_bounds__(kBlock) void k_density(const Clock *clk, int q, Gri
 {
     density_pass<LPP, MODE>(clk, q, g, ph, s, t, w, cond_fresh, (int)gridDim.x);
 }
-// The walk at 16 / 32 lanes per particle with leading arguments (shape: cond_fresh)
-template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_density_walk(const Clock *clk, int q, int shape, int *sl_cnt, int *sl_idx, int nl_stride,
+// The walk at 16 / 32 lanes per particle with leading arguments (shape: cond_fresh), in workgroups of BLK threads
+template <int LPP, int BLK = kBlock>
+__global__ __launch_bounds__(BLK) void k_density_walk(const Clock *clk, int q, int shape, int *sl_cnt, int *sl_idx, int nl_stride,
                                                          int cap, double2 *pos, double *mass, Grid g, Phys ph, FluidSet s,
                                                          FluidTmp t, Walls w)
 {
     t.sl_cnt = sl_cnt; t.sl_idx = sl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; s.mass = mass;
-    density_pass<LPP, 2>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
+    density_pass<LPP, 2, BLK>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
 }
 // Contexts whose re-binning step is folded into passes CD and E (k_forces_hist, k_continuity_rebin): nobody counts the cell
 // histogram back down there (k_scatter's atomicSub did), and the tail workgroup of pass E advances the clock while the other
@@ -978,11 +987,11 @@ __global__ __launch_bounds__(kBlock) void k_density_b(Members mb, int q, Grid g,
 // particle is m/rho0), so the walk does not branch.
 // ---------------------------------------------------------------------------------------------
 // finish_half: pass A of this step ran inside the previous step's fused launch and left {p_half, rho_half} open
-template <int LPP>
+template <int LPP, int BLK = kBlock>
 __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                          const FluidTmp &t, const Walls &w, int finish_half, int nblk)
 {
-    SPHX_PASS_INDEX_AT((int)blockIdx.x, nblk);
+    SPHX_PASS_INDEX_BLK((int)blockIdx.x, nblk, BLK);
     ListHead head;
     if (kRowsAhead<LPP>) {
         head.request(clk, q, t.nl_cnt, t.nl_idx, t.nl_stride, tid);
@@ -1044,12 +1053,12 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
         }
     }
 }
-template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_kgc(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride, int cap,
+template <int LPP, int BLK = kBlock>
+__global__ __launch_bounds__(BLK) void k_kgc(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride, int cap,
                                                 double2 *pos, double4 *a, Grid g, Phys ph, FluidSet s, FluidTmp t, Walls w)
 {
     t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; t.a = a;  // shape: finish_half
-    kgc_pass<LPP>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
+    kgc_pass<LPP, BLK>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
 }
 template <int LPP>
 __global__ __launch_bounds__(kBlock) void k_kgc_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w, int finish_half)
@@ -1074,11 +1083,12 @@ __global__ __launch_bounds__(kBlock) void k_kgc_b(Members mb, int q, Grid g, Flu
 // position, so the cell histogram is taken here instead of in pass E, which then finds it complete.  A particle that lands
 // further than one cell from where it was binned raises the grid flag: pass E of this step looks for the members of a new cell
 // only that far (rebin_near), and its tail workgroup turns the flag into SPHX_ERR_GRID.
-template <int LPP, bool HIST = false>
+// BLK: the threads of the workgroup (HIST stays at 256)
+template <int LPP, bool HIST = false, int BLK = kBlock>
 __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                             const FluidTmp &t, const Walls &w, int later, int nblk)
 {
-    SPHX_PASS_INDEX_AT((int)blockIdx.x, nblk);
+    SPHX_PASS_INDEX_BLK((int)blockIdx.x, nblk, BLK);
     ListHead head;
     if (kRowsAhead<LPP>) {
         head.request(clk, q, t.nl_cnt, t.nl_idx, t.nl_stride, tid);
@@ -1245,9 +1255,10 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
             if (!rebin_near(g, c_binned, h_cell)) atomicOr(t.flags, 1);
         }
     }
+    static_assert(!HIST || BLK == kBlock, "the histogram epilogue is written for 256 threads");
     __shared__ int s_hc[HIST ? kBlock / LPP : 1];
     if (HIST && sub == 0) s_hc[threadIdx.x / LPP] = h_cell;
-    store_block_drift(t, blk, d2);  // (its barrier also closes s_hc)
+    store_block_drift<BLK>(t, blk, d2);  // (its barrier also closes s_hc)
     // HIST: a workgroup's particles are neighbours in the old ordering and land in two or three cells: one atomic per cell and
     // workgroup instead of one per particle (fifteen particles of a cell, in as many workgroups on eight L2s, queue up on one word)
     if (HIST && threadIdx.x < kBlock / LPP) {
@@ -1263,12 +1274,12 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
         if (c >= 0 && first) atomicAdd(&t.count[c], same);
     }
 }
-template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_forces(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride, int cap,
+template <int LPP, int BLK = kBlock>
+__global__ __launch_bounds__(BLK) void k_forces(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride, int cap,
                                                    double2 *pos, double2 *vel, Grid g, Phys ph, FluidSet s, FluidTmp t, Walls w)
 {
     t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; s.vel = vel;  // shape: later
-    forces_pass<LPP>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
+    forces_pass<LPP, false, BLK>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
 }
 template <int LPP>
 __global__ __launch_bounds__(kBlock) void k_forces_hist(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride,
@@ -2265,8 +2276,118 @@ __device__ __forceinline__ void clock_step(Clock *clk, Clock c, int q, const Phy
 // back for the next step.  Nobody waits for the tail, so it cannot deadlock whatever the dispatch order; a grid
 // barrier (all wait for all) was measured at 70-90 us for 600 workgroups, this costs the tail ~1-2 us.
 // rebuilt: the step ends with a fresh grid (k_continuity_rebin), as k_clock_scan's argument of that name
+// A tail of fewer than 256 threads (BLK = 64 / 128: the passes run in smaller workgroups, so there are two to four times as many
+// entries and a quarter to a half of the threads): a thread asks for ALL of its entries of a round -- 1 024 per workgroup --
+// before it looks at any, and polls again only those that came back empty.  One polling round trip per entry and thread, as
+// at 256 threads, would be five to nineteen of them one behind the other.  The bounded spin and `lost` are the same.
+template <int BLK>
+__device__ __forceinline__ void continuity_tail_small(Clock *clk, int q, const Phys &ph, const FluidTmp &t, int nb, int rebuilt)
+{
+    static_assert(BLK == 64 || BLK == 128, "the tail of 256 threads is continuity_tail's own");
+    if (!clk->run[q]) {
+        if (threadIdx.x == 0) clk->run[1 - q] = 0;  // idle slot keeps the following slots idle
+        return;
+    }
+    Clock c0;
+    int fl = 0;
+    if (threadIdx.x == 0) { c0 = *clk; fl = *t.flags; }
+    double m = 0.0, d = 0.0;
+    int lost = 0;
+    const bool track = t.half_skin >= 0.0;
+    constexpr int kPer = 1024 / BLK;  // entries a thread has in flight
+    for (int base = 0; base < nb; base += BLK * kPer) {
+        unsigned long long bits[kPer];
+        double dv[kPer];
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const int k = base + j * BLK + (int)threadIdx.x;
+            const int kk = min(k, nb - 1);  // (a thread without an entry asks for the last one and drops the answer)
+            bits[j] = __hip_atomic_load(reinterpret_cast<unsigned long long *>(&t.vpart[kk]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            dv[j] = track ? t.dpart[kk] : 0.0;  // written by pass CD, a kernel ago
+        }
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const int k = base + j * BLK + (int)threadIdx.x;
+            if (k < nb) {
+                unsigned long long *slot = reinterpret_cast<unsigned long long *>(&t.vpart[k]);
+                unsigned long long b = bits[j];
+                unsigned spins = 0;
+                while (b == kVpartEmpty) {
+                    __builtin_amdgcn_s_sleep(2);
+                    if (++spins > (1u << 22)) { lost = 1; break; }  // never hang the device on a protocol bug
+                    b = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                if (b != kVpartEmpty) m = fmax(m, __longlong_as_double((long long)b));
+                d = fmax(d, dv[j]);
+                __hip_atomic_store(slot, kVpartEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    m = wave_max(m);
+    d = wave_max(d);
+    lost = __any(lost) ? 1 : 0;
+    if constexpr (BLK > 64) {
+        __shared__ double s_m[BLK / 64], s_d[BLK / 64];
+        __shared__ int s_l[BLK / 64];
+        if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_d[threadIdx.x >> 6] = d; s_l[threadIdx.x >> 6] = lost; }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int k = 1; k < BLK / 64; ++k) { m = fmax(m, s_m[k]); d = fmax(d, s_d[k]); lost |= s_l[k]; }
+    }
+    if (threadIdx.x == 0) {
+        if (lost) c0.status = SPHX_ERR_DIVERGED;
+        clock_step(clk, c0, q, ph, sqrt(m), fl, -1, track ? sqrt(d) : -1.0, rebuilt, t.half_skin);
+    }
+}
+// ... and a tail of more than 256 threads: continuity_tail's own loop, one polling
+// round trip per entry and thread, with BLK threads
+template <int BLK>
+__device__ __forceinline__ void continuity_tail_wide(Clock *clk, int q, const Phys &ph, const FluidTmp &t, int nb, int rebuilt)
+{
+    static_assert(BLK > kBlock && BLK % 64 == 0, "the tail of 256 threads is continuity_tail's own");
+    if (!clk->run[q]) {
+        if (threadIdx.x == 0) clk->run[1 - q] = 0;  // idle slot keeps the following slots idle
+        return;
+    }
+    Clock c0;
+    int fl = 0;
+    if (threadIdx.x == 0) { c0 = *clk; fl = *t.flags; }
+    double m = 0.0, d = 0.0;
+    int lost = 0;
+    const bool track = t.half_skin >= 0.0;
+    for (int k = threadIdx.x; k < nb; k += BLK) {
+        if (track) d = fmax(d, t.dpart[k]);  // written by pass CD, a kernel ago
+        unsigned long long *slot = reinterpret_cast<unsigned long long *>(&t.vpart[k]);
+        unsigned long long bits;
+        unsigned spins = 0;
+        while ((bits = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == kVpartEmpty) {
+            __builtin_amdgcn_s_sleep(2);
+            if (++spins > (1u << 22)) { lost = 1; break; }  // never hang the device on a protocol bug
+        }
+        if (!lost) m = fmax(m, __longlong_as_double((long long)bits));
+        __hip_atomic_store(slot, kVpartEmpty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    m = wave_max(m);
+    d = wave_max(d);
+    lost = __any(lost) ? 1 : 0;
+    __shared__ double s_m[BLK / 64], s_d[BLK / 64];
+    __shared__ int s_l[BLK / 64];
+    if ((threadIdx.x & 63) == 0) { s_m[threadIdx.x >> 6] = m; s_d[threadIdx.x >> 6] = d; s_l[threadIdx.x >> 6] = lost; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < BLK / 64; ++k) { m = fmax(m, s_m[k]); d = fmax(d, s_d[k]); lost |= s_l[k]; }
+        if (lost) c0.status = SPHX_ERR_DIVERGED;
+        clock_step(clk, c0, q, ph, sqrt(m), fl, -1, track ? sqrt(d) : -1.0, rebuilt, t.half_skin);
+    }
+}
+template <int BLK = kBlock>
 __device__ __forceinline__ void continuity_tail(Clock *clk, int q, const Phys &ph, const FluidTmp &t, int nb, int rebuilt = 0)
 {
+    if constexpr (BLK != kBlock) {
+        if constexpr (BLK < kBlock) continuity_tail_small<BLK>(clk, q, ph, t, nb, rebuilt);
+        else continuity_tail_wide<BLK>(clk, q, ph, t, nb, rebuilt);
+        return;
+    }
     if (!clk->run[q]) {
         if (threadIdx.x == 0) clk->run[1 - q] = 0;  // idle slot keeps the following slots idle
         return;
@@ -2492,7 +2613,8 @@ struct HistWindow {
         }
     }
 };
-template <int LPP, bool WALK, int TILE, bool CODED = false, bool REBIN = false>
+// BLK: the threads of the workgroup (other than 256: the compact form without the re-binning)
+template <int LPP, bool WALK, int TILE, bool CODED = false, bool REBIN = false, int BLK = kBlock>
 __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                                 const FluidTmp &t, const Walls &w, int do_hist, int tail, PassWg bid, int nb,
                                                 double2 *c_pos, double2 *c_vel, double *c_vol, int next_half = 0,
@@ -2500,8 +2622,9 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
 {
     static_assert(!CODED || (WALK && TILE == kSlotCodes), "slot-coded lists: this pass stages the whole layout");
     static_assert(!REBIN || (!WALK && TILE == 0 && LPP >= 16), "the folded re-binning belongs to the compact kernels");
+    static_assert(BLK == kBlock || (!WALK && !REBIN && LPP >= 16), "smaller workgroups: the compact passes only");
     const int blk = xcd_block(bid, nb);
-    const int tid = blk * kBlock + threadIdx.x;
+    const int tid = blk * BLK + threadIdx.x;
     const int i = tid / LPP, sub = tid % LPP;
     const bool in_cap = i < t.cap;
     if (WALK && beyond_population<LPP>(clk, t, blk)) {  // nothing here: only the workgroup's entry of the max |v|^2 reduction is owed
@@ -2566,17 +2689,24 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
             if (v2 != v2) v2 = INFINITY;  // NaN poisons the max on purpose
         }
         v2 = wave_max(v2);
-        __shared__ double s_max[kBlock / 64];
-        if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v2;
-        __syncthreads();
-        if (threadIdx.x == 0 && !next_half) {  // (an inner sub-step leaves the "ready" slots of the step's last pass E alone)
-            double m = s_max[0];
-            for (int k = 1; k < kBlock / 64; ++k) m = fmax(m, s_max[k]);
+        auto store = [&](int k, double m) {
             if (tail)
-                __hip_atomic_store(reinterpret_cast<unsigned long long *>(&t.vpart[blk]), (unsigned long long)__double_as_longlong(m),
+                __hip_atomic_store(reinterpret_cast<unsigned long long *>(&t.vpart[k]), (unsigned long long)__double_as_longlong(m),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else
-                t.vpart[blk] = m;
+                t.vpart[k] = m;
+        };
+        if constexpr (BLK == 64) {  // one wave: its maximum is the workgroup's -- no LDS, no barrier
+            if (threadIdx.x == 0 && !next_half) store(blk, v2);
+        } else {
+            __shared__ double s_max[BLK / 64];
+            if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v2;
+            __syncthreads();
+            if (threadIdx.x == 0 && !next_half) {  // (an inner sub-step leaves the "ready" slots of the step's last pass E alone)
+                double m = s_max[0];
+                for (int k = 1; k < BLK / 64; ++k) m = fmax(m, s_max[k]);
+                store(blk, m);
+            }
         }
     };
     if (!WALK) publish_vmax();
@@ -2716,19 +2846,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WALK ? 8
 }
 
 // Pass E of the compact kernels at 16 / 32 lanes per particle with leading arguments (shape: the workgroups of the pass, tail)
-template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_continuity_compact(Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride,
+template <int LPP, int BLK = kBlock>
+__global__ __launch_bounds__(BLK) void k_continuity_compact(Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride,
                                                                int cap, double2 *pos, double2 *veln, Grid g, Phys ph, FluidSet s,
                                                                FluidTmp t, Walls w, int do_hist, int next_half)
 {
     t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; t.veln = veln;
     const int nb = shape_blocks(shape), tail = shape_flag(shape);
     if (tail && (int)blockIdx.x == nb) {
-        if (tail == 2) slab_seal_tail(clk, q, t, nb);
-        else continuity_tail(clk, q, ph, t, nb);
+        if constexpr (BLK == kBlock) {
+            if (tail == 2) { slab_seal_tail(clk, q, t, nb); return; }  // (slabs run 256 threads)
+        }
+        continuity_tail<BLK>(clk, q, ph, t, nb);
         return;
     }
-    continuity_body<LPP, false, 0>(clk, q, g, ph, s, t, w, do_hist, tail, (int)blockIdx.x, nb, nullptr, nullptr, nullptr, next_half);
+    continuity_body<LPP, false, 0, false, false, BLK>(clk, q, g, ph, s, t, w, do_hist, tail, (int)blockIdx.x, nb, nullptr, nullptr, nullptr,
+                                                      next_half);
 }
 
 // Small channels, the step that re-bins: pass E with the re-binning folded in (continuity_body, REBIN) and the clock in the tail
@@ -2759,8 +2892,8 @@ __global__ __launch_bounds__(kBlock) void k_continuity_rebin(Clock *clk, int q, 
 // flag word above the tail's codes) numbers it as if it began at block 0, as it did before.
 constexpr int kFusedTail = 1, kFusedUnaligned = 4;
 __device__ __forceinline__ int fused_first_a(int flags, int nb) { return flags & kFusedUnaligned ? 0 : nb; }
-template <int LPP>
-__global__ __launch_bounds__(kBlock) void k_continuity_density(Clock *clk, int q, int shape, int *e_cnt, int *e_idx, int *a_cnt,
+template <int LPP, int BLK = kBlock>
+__global__ __launch_bounds__(BLK) void k_continuity_density(Clock *clk, int q, int shape, int *e_cnt, int *e_idx, int *a_cnt,
                                                                int *a_idx, int e_stride, int a_stride, Grid g, Phys ph, FluidSet s,
                                                                FluidTmp t, Walls w, FluidSet s_next, FluidTmp t_next)
 {
@@ -2771,11 +2904,11 @@ __global__ __launch_bounds__(kBlock) void k_continuity_density(Clock *clk, int q
     const int nb = shape_blocks(shape), with_tail = shape_flag(shape) & kFusedTail;  // (with_tail = 0: kernel timing, the clock must not advance)
     const int b = (int)blockIdx.x;
     if (with_tail && b == 2 * nb) {
-        continuity_tail(clk, q, ph, t, nb);
+        continuity_tail<BLK>(clk, q, ph, t, nb);
         return;
     }
-    if (b < nb) continuity_body<LPP, false, 0>(clk, q, g, ph, s, t, w, 0, with_tail, b, nb, nullptr, nullptr, nullptr);
-    else density_body<LPP, 2>(clk, q, g, ph, s_next, t_next, w, PassWg(b - nb, fused_first_a(shape_flag(shape), nb)), nb, false);
+    if (b < nb) continuity_body<LPP, false, 0, false, false, BLK>(clk, q, g, ph, s, t, w, 0, with_tail, b, nb, nullptr, nullptr, nullptr);
+    else density_body<LPP, 2, BLK>(clk, q, g, ph, s_next, t_next, w, PassWg(b - nb, fused_first_a(shape_flag(shape), nb)), nb, false);
 }
 
 // Batches (Members): pass E of the compact kernels (the tail workgroup of member m is workgroup nb of row m: it waits for the

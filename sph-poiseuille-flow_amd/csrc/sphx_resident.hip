@@ -174,8 +174,13 @@ struct sphx_ctx {
 
     FluidTmp tmp{};
     Walls walls{};
-    int n_blocks_particles = 0;  // grid of the LPP kernels (capacity based)
+    int n_blocks_particles = 0;  // grid of the LPP kernels (capacity based), in workgroups of 256 threads
     int n_blocks_flat = 0;       // grid of one-thread-per-particle kernels
+    // Compact step kernels (16 / 32 lanes per particle): threads per workgroup of the passes that are not part of the re-binning
+    // step (pick_block), and the workgroups of such a pass.  vpart / dpart hold one entry per workgroup of THAT size (n_vpart =
+    // n_blocks_pass); the 256-thread kernels of the re-binning step fill every entry they cover.
+    int block = kBlock;
+    int n_blocks_pass = 0;
 
     int64_t chunk_slots = 128;   // slots enqueued between two host looks at the clock (adaptive, see advance)
     bool profiling = false;
@@ -313,6 +318,8 @@ namespace {
 //  no_lds_tiles: large-channel passes gather from global memory; no_coded_lists: index differences in every list, never tile
 //  slots; no_lazy_out: force, force_prior, rho, p written by every step (FluidTmp::lazy_out); no_xcd_align: the A half of the
 //  fused launch, which starts at physical block nb, numbers its blocks as if it started at block 0 (xcd_block, sphx_xcd_block.hpp);
+//  block_64 / block_128 / block_256: the compact passes in workgroups of that many threads whatever pick_block says (block_256:
+//  the launches as they were before the block size became a choice);
 //  log: forced re-binnings and timer
 //  problems on stderr)
 struct DebugSwitches {
@@ -323,6 +330,7 @@ struct DebugSwitches {
     bool full_copyback = false;  // dynamic contexts: the in-place re-binning copies the whole layout back (round 3)
     int tail_limit = 0;  // > 0: largest pass (in workgroups) whose clock update rides in pass E's tail workgroup
     int forces_tile = 0;    // 320: the old tile size of the slot-coded force pass
+    int block = 0;          // block_64 / block_128 / block_256: threads per workgroup of the compact passes (0: pick_block)
     int tiles_be_from = 0;  // > 0: passes B, E and A stage LDS tiles from this many resident particles (2 lanes per particle)
 };
 const DebugSwitches &debug_switches()
@@ -347,6 +355,8 @@ const DebugSwitches &debug_switches()
         for (int from : {1, 250000, 500000, 750000, 1000000, 1500000, 3000000})
             if (has(("tiles_be_from_" + std::to_string(from)).c_str())) d.tiles_be_from = from;
         if (has("forces_tile_320")) d.forces_tile = 320;
+        for (int b : {64, 128, 256, 320, 384, 512, 1024})
+            if (has(("block_" + std::to_string(b)).c_str())) d.block = b;
         return d;
     }();
     return sw;
@@ -456,6 +466,22 @@ void with_lpp(const sphx_ctx *c, F &&f)
     }
 }
 
+// f(std::integral_constant<int, BLK>) for the context's block size (compact kernels)
+template <typename F>
+void with_block(const sphx_ctx *c, F &&f)
+{
+    switch (c->block) {
+        case 64: f(std::integral_constant<int, 64>{}); break;
+        case 128: f(std::integral_constant<int, 128>{}); break;
+        case 256: f(std::integral_constant<int, 256>{}); break;
+        case 320: f(std::integral_constant<int, 320>{}); break;
+        case 384: f(std::integral_constant<int, 384>{}); break;
+        case 512: f(std::integral_constant<int, 512>{}); break;
+        case 1024: f(std::integral_constant<int, 1024>{}); break;
+        default: throw Error(SPHX_ERR_STATE, "SPHX:Ctx:block", "internal: block size must be 64, 128, 256, 512 or 1024");
+    }
+}
+
 // The form of a large-channel ("_w") kernel, handed to f as compile-time TILE / CODED: slot-coded lists (2 lanes per particle,
 // every pass with a tile: the CODED forms of the same kernels) on a tile of TILE_CODED slots, an LDS tile of TILE_LDS slots
 // (tile_ranges), or gathers from global memory
@@ -558,11 +584,17 @@ auto hot_fused(unsigned nblk, int flag, const FluidTmp &t, const FluidTmp &tn)  
     return std::make_tuple(pass_shape((int)nblk, flag), t.nl_cnt, t.nl_idx, tn.sl_cnt, tn.sl_idx, t.nl_stride, tn.nl_stride);
 }
 template <typename K, typename KB, typename... H, typename... X>
+void launch_pass_hot_blk(sphx_ctx *c, const char *name, Forms<K, KB> k, unsigned blocks, unsigned block, int q, const std::tuple<H...> &hot,
+                         const FluidSet &s, const FluidTmp &t, X... extra)
+{
+    std::apply([&](auto... h) { launch_forms(c, name, k, blocks, block, 0, q, per_member(h)..., c->grid, per_member(c->phys), s, t, c->walls, extra...); },
+               hot);
+}
+template <typename K, typename KB, typename... H, typename... X>
 void launch_pass_hot(sphx_ctx *c, const char *name, Forms<K, KB> k, unsigned blocks, int q, const std::tuple<H...> &hot, const FluidSet &s,
                      const FluidTmp &t, X... extra)
 {
-    std::apply([&](auto... h) { launch_forms(c, name, k, blocks, kBlock, 0, q, per_member(h)..., c->grid, per_member(c->phys), s, t, c->walls, extra...); },
-               hot);
+    launch_pass_hot_blk(c, name, k, blocks, kBlock, q, hot, s, t, extra...);
 }
 
 // 16 / 32 lanes per particle (small channels) run the compact kernels (32-bit lists); fewer lanes (large channels) the "_w"
@@ -584,8 +616,12 @@ void launch_pass_a(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Pas
             else if (mode == PassA::SweepBuild && c->fold_rebin) launch_pass(c, sweep_name, k_density_zero<LPP>, np, q, s, t, cond_sweep);
             else if (sweeps) launch_pass(c, sweep_name, Forms{k_density<LPP, 1>, k_density_b<LPP, 1>}, np, q, s, t, cond_sweep);
             if (walks)
-                launch_pass_hot(c, "k_density_walk", Forms{k_density_walk<LPP>, k_density_b<LPP, 2>}, np, q, hot_walk(np, cond_walk, s, t), s, t,
-                                batch_only(cond_walk));
+                with_block(c, [&](auto blk) {
+                    constexpr int BLK = decltype(blk)::value;
+                    const unsigned nb = c->n_blocks_pass;
+                    launch_pass_hot_blk(c, "k_density_walk", Forms{k_density_walk<LPP, BLK>, k_density_b<LPP, 2>}, nb, BLK, q,
+                                        hot_walk(nb, cond_walk, s, t), s, t, batch_only(cond_walk));
+                });
         } else {
             // the cell sweep: mode 0 writes the step's list, mode 1 the superset list as well
             // the build variant of a dynamic context is idle on four steps out of five: a grid-stride launch of an eighth
@@ -605,6 +641,16 @@ void launch_pass_a(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Pas
     });
 }
 
+// The temporaries as a compact pass at the context's block size gets them.  The kernels of the re-binning step (k_forces_hist,
+// k_continuity_rebin) always run 256 threads, so a context whose other passes do not has two sets of per-workgroup maxima in
+// vpart / dpart: the first n_blocks_particles entries for the 256-thread kernels, n_blocks_pass entries behind them for the
+// passes.  Pass CD and pass E (with its tail) of one step always run at the same size, so a tail finds its step's entries.
+FluidTmp pass_tmp(const sphx_ctx *c, FluidTmp t)
+{
+    if (c->lpp >= 16 && c->block != kBlock) { t.vpart += c->n_blocks_particles; t.dpart += c->n_blocks_particles; t.n_vpart = c->n_blocks_pass; }
+    return t;
+}
+
 void launch_pass_b(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t)
 {
     const unsigned np = c->n_blocks_particles;
@@ -612,7 +658,12 @@ void launch_pass_b(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t)
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16)
-            launch_pass_hot(c, "k_kgc", Forms{k_kgc<LPP>, k_kgc_b<LPP>}, np, q, hot_kgc(np, finish_half, s, t), s, t, batch_only(finish_half));
+            with_block(c, [&](auto blk) {
+                constexpr int BLK = decltype(blk)::value;
+                const unsigned nb = c->n_blocks_pass;
+                launch_pass_hot_blk(c, "k_kgc", Forms{k_kgc<LPP, BLK>, k_kgc_b<LPP>}, nb, BLK, q, hot_kgc(nb, finish_half, s, t), s, t,
+                                    batch_only(finish_half));
+            });
         else
             with_form<LPP, kSlotCodes, tile_slots(LPP)>(c, c->lds_tiles_be, [&](auto tile, auto coded) {
                 launch_pass(c, "k_kgc", k_kgc_w<LPP, decltype(tile)::value, decltype(coded)::value>, np, q, s, t, finish_half);
@@ -620,14 +671,19 @@ void launch_pass_b(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t)
     });
 }
 
-void launch_pass_cd(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Rate rate = Rate::Outer)
+void launch_pass_cd(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t_, Rate rate = Rate::Outer)
 {
+    const FluidTmp t = pass_tmp(c, t_);
     const unsigned np = c->n_blocks_particles;
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16) {
-            launch_pass_hot(c, rate == Rate::Inner ? "k_forces_inner" : "k_forces", Forms{k_forces<LPP>, k_forces_b<LPP>}, np, q,
-                            hot_forces(np, (int)rate, s, t), s, t, batch_only((int)rate));
+            with_block(c, [&](auto blk) {
+                constexpr int BLK = decltype(blk)::value;
+                const unsigned nb = c->n_blocks_pass;
+                launch_pass_hot_blk(c, rate == Rate::Inner ? "k_forces_inner" : "k_forces", Forms{k_forces<LPP, BLK>, k_forces_b<LPP>}, nb, BLK, q,
+                                    hot_forces(nb, (int)rate, s, t), s, t, batch_only((int)rate));
+            });
         } else {
             auto forces = [&](auto tile, auto coded) {
                 launch_pass(c, "k_forces", k_forces_w<LPP, decltype(tile)::value, decltype(coded)::value>, np, q, s, t);
@@ -641,16 +697,21 @@ void launch_pass_cd(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Ra
     });
 }
 
-void launch_pass_e(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, Tail tail = Tail::None, Hist hist = Hist::None,
+void launch_pass_e(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t_, Tail tail = Tail::None, Hist hist = Hist::None,
                    Rate rate = Rate::Outer)
 {
+    const FluidTmp t = pass_tmp(c, t_);
     const unsigned ne = c->n_blocks_particles + (tail != Tail::None ? 1 : 0);
     const char *name = rate == Rate::Inner ? "k_continuity_inner" : tail != Tail::None ? "k_continuity_clock" : "k_continuity";
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16)
-            launch_pass_hot(c, name, Forms{k_continuity_compact<LPP>, k_continuity_b<LPP>}, ne, q,
-                            hot_continuity(c->n_blocks_particles, (int)tail, s, t), s, t, (int)hist, batch_only((int)tail), single_only((int)rate));
+            with_block(c, [&](auto blk) {
+                constexpr int BLK = decltype(blk)::value;
+                const unsigned nb = c->n_blocks_pass;
+                launch_pass_hot_blk(c, name, Forms{k_continuity_compact<LPP, BLK>, k_continuity_b<LPP>}, nb + (tail != Tail::None ? 1 : 0), BLK, q,
+                                    hot_continuity(nb, (int)tail, s, t), s, t, (int)hist, batch_only((int)tail), single_only((int)rate));
+            });
         else
             with_form<LPP, kSlotCodes, tile_slots(LPP)>(c, c->lds_tiles_be, [&](auto tile, auto coded) {
                 launch_pass(c, name, k_continuity<LPP, true, decltype(tile)::value, decltype(coded)::value>, ne, q, s, t, (int)hist, (int)tail, 0);
@@ -750,6 +811,7 @@ void launch_fold_rebin(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t,
     with_lpp(c, [&](auto lpp) {
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16) {
+            // (256 threads whatever the block size of the other passes, with per-workgroup maxima of their own: pass_tmp)
             const unsigned np = c->n_blocks_particles;
             launch_pass_hot(c, "k_forces_hist", Forms{k_forces_hist<LPP>}, np, q, hot_forces(np, 0, s, t), s, t);
             launch_pass_hot(c, "k_continuity_rebin", Forms{k_continuity_rebin<LPP>}, np + 1, q, hot_continuity(np, 1, s, t), s, t, d);
@@ -759,15 +821,20 @@ void launch_fold_rebin(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t,
     });
 }
 // Pass E of a step and pass A of the next in one launch.  Tail::None: without the clock workgroup (kernel timing)
-void launch_fused_ea(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t, const FluidSet &sn, const FluidTmp &tn, Tail tail = Tail::Clock)
+void launch_fused_ea(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t_, const FluidSet &sn, const FluidTmp &tn, Tail tail = Tail::Clock)
 {
-    const unsigned blocks = 2 * c->n_blocks_particles + (int)tail;
+    const FluidTmp t = pass_tmp(c, t_);
+    const bool compact = c->lpp >= 16;
+    const unsigned nb = compact ? c->n_blocks_pass : c->n_blocks_particles, blocks = 2 * nb + (int)tail;
     const int flags = (int)tail | (debug_switches().no_xcd_align ? kFusedUnaligned : 0);  // (the batch form numbers as before)
     with_lpp(c, [&](auto lpp) {  // 16 / 32 lanes per particle: the compact kernels; fewer: their large-channel forms
         constexpr int LPP = decltype(lpp)::value;
         if constexpr (LPP >= 16)
-            launch_pass_hot(c, "k_continuity_density", Forms{k_continuity_density<LPP>, k_continuity_density_b<LPP>}, blocks, q,
-                            hot_fused(c->n_blocks_particles, flags, t, tn), s, t, sn, tn, batch_only((int)tail));
+            with_block(c, [&](auto blk) {
+                constexpr int BLK = decltype(blk)::value;
+                launch_pass_hot_blk(c, "k_continuity_density", Forms{k_continuity_density<LPP, BLK>, k_continuity_density_b<LPP>}, blocks, BLK, q,
+                                    hot_fused(nb, flags, t, tn), s, t, sn, tn, batch_only((int)tail));
+            });
         else if constexpr (LPP >= 2)
             launch_pass(c, "k_continuity_density", k_continuity_density_w<LPP>, blocks, q, s, t, sn, tn, flags);
         else
@@ -1187,6 +1254,31 @@ int pick_lpp(int nf)
     return lpp;
 }
 
+// Threads per workgroup of the compact passes (k_kgc, k_forces, k_continuity_density, k_continuity_compact, k_density_walk).
+// A pass of 256-thread workgroups gets slower by 1.3 us/step where it stops fitting one workgroup per compute unit (256 of
+// them: 243 workgroups 12.0 us/step, 257 workgroups 13.3).  Smaller workgroups do not help -- every workgroup costs dispatch
+// time: C2 at 128 threads +0.1..0.5, at 64 +1.4 us/step -- and neither do 150 workgroups of 512 threads (+0.7: eight waves on
+// every compute unit that has any).  What helps is the smallest workgroup with which the pass fits the 256 compute units
+// again, where that is one wave more: C2's 1 200 waves as 240 workgroups of 320 threads, 13.51 against 13.94 us/step; six
+// waves (384 threads, 200 workgroups) are back at 14.03.  profiles/r44_block_size.txt.
+// Only the three-launch step with the folded re-binning (fold_rebin, ctx_alloc checks that it agrees): its re-binning kernels
+// keep 256 threads and per-workgroup maxima of their own (pass_tmp).  Batches, slabs, dynamic contexts: 256.
+// (called from ctx_alloc, with tail_clock decided)
+int pick_block(const sphx_ctx *c)
+{
+    const DebugSwitches &dbg = debug_switches();
+    const Grid &g = c->grid;
+    const bool three_launches = c->tail_clock && c->lpp >= 16 && !c->arena && !dbg.no_fuse_ea && !dbg.no_fold_rebin &&
+                                dual_rate_substeps(c->prm) == 1 && g.periodic && g.ncx >= 3 && g.ncells < kFoldCells &&
+                                g.ncells <= kBigScanCells && 5 * (size_t)c->n_blocks_particles <= (size_t)(4 * kMaxTile);
+    if (!three_launches) return kBlock;
+    if (dbg.block > 0) return dbg.block;
+    // (taken where it is worth 2 %: C2, 1 200 waves, -2.8 % and -4.4 % on the 20-step line; at 1 083 waves it is 1.3 %, so not
+    //  there, and nothing in between has been measured: the class begins half-way)
+    const size_t waves = div_up((size_t)c->cap * c->lpp, (size_t)64);
+    return (waves > 4 * 256 + 128 && waves <= 5 * 256) ? 320 : kBlock;
+}
+
 // rows of the per-lane neighbour list: >= 96 entries per particle (fluid ring ~30-45 + wall ring up to ~20)
 int nl_cap_for(int lpp) { return std::max(96 / lpp, 16); }
 
@@ -1253,11 +1345,15 @@ void ctx_alloc(sphx_ctx *c, int cap)
     dev_alloc(c, c->drhon, cap); dev_alloc(c, c->rho_out, cap); dev_alloc(c, c->p_out, cap); dev_alloc(c, c->fvol, cap); c->fvol.zero(c->stream);
     c->posn.zero(c->stream); c->veln.zero(c->stream); c->ffp.zero(c->stream); c->ff.zero(c->stream);
     c->fa.zero(c->stream); c->fB.zero(c->stream); c->drhon.zero(c->stream); c->rho_out.zero(c->stream); c->p_out.zero(c->stream);
-    c->n_vpart = c->n_blocks_particles;
-    dev_alloc(c, c->vpart, c->n_vpart);
     // Small channels with a skin: move steps are 4 launches, the clock update rides in pass E (continuity_tail);
     // vpart entries then double as "ready" flags and start out empty (all ones)
-    c->tail_clock = c->skin > 0.0 && !c->is_slab && !c->dyn && c->n_vpart <= tail_clock_limit() && !debug_switches().no_tail_clock;
+    c->tail_clock = c->skin > 0.0 && !c->is_slab && !c->dyn && c->n_blocks_particles <= tail_clock_limit() && !debug_switches().no_tail_clock;
+    c->block = pick_block(c);
+    c->n_blocks_pass = (int)div_up((size_t)cap * c->lpp, (size_t)c->block);
+    // vpart / dpart: one entry per workgroup.  Passes of another size than 256 threads keep theirs behind those of the 256-thread
+    // kernels (pass_tmp): whichever kernels run a step, its tail workgroup collects what the same step's workgroups left
+    c->n_vpart = c->n_blocks_particles + (c->block != kBlock ? c->n_blocks_pass : 0);
+    dev_alloc(c, c->vpart, c->n_vpart);
     // (skinned slabs: the same hand-over feeds slab_seal_tail)
     const bool vpart_flags = c->tail_clock || (c->is_slab && c->rebuild_every > 1);
     SPHX_HIP(hipMemsetAsync(c->vpart.get(), vpart_flags ? 0xFF : 0, (size_t)c->n_vpart * sizeof(double), c->stream));
@@ -1268,7 +1364,8 @@ void ctx_alloc(sphx_ctx *c, int cap)
     dev_alloc(c, c->cellid, cap); dev_alloc(c, c->count, (size_t)g.ncells + 1); dev_alloc(c, c->perm, cap); dev_alloc(c, c->src_of, cap);
     c->count.zero(c->stream);
     const int nl_cap = nl_cap_for(c->lpp);
-    const size_t stride = (size_t)c->n_blocks_particles * kBlock;  // one list column per launched lane
+    // one list column per launched lane, of the 256-thread kernels and of the passes at the context's block size
+    const size_t stride = std::max((size_t)c->n_blocks_particles * kBlock, (size_t)c->n_blocks_pass * c->block);
     dev_alloc(c, c->nl_idx, stride * nl_cap);
     dev_alloc(c, c->nl_cnt, stride);
     c->nl_cnt.zero(c->stream);
@@ -1294,6 +1391,7 @@ void ctx_alloc(sphx_ctx *c, int cap)
                       c->skin > 0.0 ? c->half_skin() : -1.0, c->fvol.get(), c->nl_pk.get(), c->sl_pk.get(), c->is_slab ? 1 : 0, nullptr, 0, nullptr};
     // (2 = never: a slab hands out its state only, sphx_slab_snapshot; the dual-rate loop, which reads force_prior in its
     //  inner sub-steps, runs on the compact kernels only)
+    c->tmp.n_vpart = c->n_blocks_particles;  // (the entries of the 256-thread kernels; pass_tmp for the others)
     c->tmp.lazy_out = (c->walk_kernels && !debug_switches().no_lazy_out) ? (c->is_slab ? 2 : 1) : 0;
     if (c->walk_kernels) {  // (zeros = empty layouts until the first cell sweep has run)
         dev_alloc(c, c->tmap, 8 * (size_t)c->n_blocks_particles); c->tmap.zero(c->stream);
@@ -1322,6 +1420,8 @@ void ctx_alloc(sphx_ctx *c, int cap)
     // columns (the +-1 columns of a cell are distinct) small enough for every workgroup to scan in LDS (kFoldCells)
     c->fold_rebin = c->fuse_ea && c->lpp >= 16 && c->n_in == 1 && !c->arena && !c->big_scan && c->n_vtiles == 0 &&
                     g.periodic && g.ncx >= 3 && g.ncells < kFoldCells && !debug_switches().no_fold_rebin;
+    if (c->block != kBlock && !c->fold_rebin)
+        throw Error(SPHX_ERR_STATE, "SPHX:Ctx:block", "internal: a block size other than 256 without the folded re-binning step");
 
     dev_alloc(c, c->tau_part, (size_t)2 * c->n_blocks_flat);
     dev_alloc(c, c->tau_out, 2);
@@ -2051,6 +2151,15 @@ SPHX_EXPORT int sphx_ctx_tuning(sphx_ctx *c, int *lanes_per_particle, int *steps
     require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
     if (lanes_per_particle) *lanes_per_particle = c->lpp;
     if (steps_per_graph) *steps_per_graph = c->spg;
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_block_size(sphx_ctx *c, int *block_size)
+{
+    SPHX_TRY
+    require(c != nullptr && block_size != nullptr, "SPHX:Ctx:null", "ctx / block_size must not be NULL");
+    *block_size = c->block;
     return SPHX_OK;
     SPHX_CATCH
 }
