@@ -646,6 +646,22 @@ __device__ __forceinline__ void list_push_w(const LaneGroup<LPP> &lg, int *idx, 
 template <int LPP>
 constexpr bool kRowsAhead = LPP >= 16;
 __device__ __forceinline__ void requests_issued() { asm volatile("" ::: "memory"); }
+// What a wave of these kernels issues besides its pairs' arithmetic is paid once per four (two) particles, and where a SIMD holds
+// two waves of a pass the second one's instructions queue behind the first's: the pass heads keep them few.
+//   own_slot: the particle's own records are loaded from slot min(i, cap - 1) without a test.  Every `in_cap ? load : default`
+//   was an exec-mask region of its own (save, branch, restore, the defaults moved in front); slot cap - 1 exists, lanes beyond
+//   the population (i >= clk->n, so every lane beyond cap) are never `active`, and a group's lanes share i, so what they load
+//   reaches no sum and no store.  Records only the lead lane uses are loaded by all of the group: one line, one request.
+//   pair_dx: the minimum-image fold of a pair, skipped by a wave in which no lane's pair crosses the periodic seam -- nearly
+//   every wave -- for one compare and one scalar branch; otherwise min_image as everywhere else, so the same bits either way.
+template <int LPP>
+__device__ __forceinline__ int own_slot(int i, int cap) { return kRowsAhead<LPP> ? min(i, cap - 1) : i; }
+template <int LPP>
+__device__ __forceinline__ double pair_dx(const Grid &g, double dx)
+{
+    if (kRowsAhead<LPP> && !__any(fabs(dx) > g.half_DL)) return dx;
+    return min_image(g, dx);
+}
 // Leading arguments.  The single-channel forms of these kernels take what wave 1 forms its first addresses from -- the clock,
 // the number of workgroups of the pass, the row counts, the list and its stride, and as many own-record pointers as fit -- as
 // plain parameters IN FRONT of the structs: built with -amdgpu-kernarg-preload-count the first 14 dwords of the argument
@@ -750,10 +766,11 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
                         "s"(t.vol), "s"(w.pos), "s"(w.a), "s"(g.DL), "s"(g.half_DL), "s"(ph.kc.rcut2), "s"(ph.kc.inv_h),
                         "s"(ph.kc.sigma), "s"(ph.w0), "s"(ph.rho0), "s"(ph.inv_sigma0), "s"(run_h), "s"(n_h), "s"(dt_h));
     }
-    const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
+    const int io = kHot ? own_slot<LPP>(i, t.cap) : i;  // (the walk at 16 / 32 lanes: no test around the own records)
+    const double2 pi = (kHot || in_cap) ? s.pos[io] : make_double2(0.0, 0.0);
     const int ci = in_cap ? s.cell[i] : 0;
-    const bool lead = in_cap && sub == 0;  // the lane that finishes the particle
-    const double mass_i = lead ? s.mass[i] : 1.0, drho_i = lead ? s.drho[i] : 0.0;
+    const bool lead = kHot || (in_cap && sub == 0);  // the lane that finishes the particle
+    const double mass_i = lead ? s.mass[io] : 1.0, drho_i = lead ? s.drho[io] : 0.0;
     // list-walking variant: row count and the first two rows are requested here as well (a lane rarely owns more
     // at 32 lanes per particle): count -> entry -> position becomes {count, entries} -> position
     // (kRowsAhead: the first kAhead rows -- 64 candidates; the superset list holds about 48 of them at skin 1.05 h, so three
@@ -784,7 +801,7 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
                 bool acc = false;
                 if (has) {
                     const bool wall = (e & kWallBit) != 0;
-                    const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
+                    const double dx = pair_dx<LPP>(g, xi - pj.x), dy = yi - pj.y;
                     const double r2 = dx * dx + dy * dy;
                     if (r2 > kR2Min && r2 < ph.kc.rcut2) {
                         acc = true;
@@ -867,7 +884,7 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
             if (v < nfl) {
                 k = ranges_index(lo[0], lo[1], lo[2], n0, n1, v);
                 const double2 pj = s.pos[k];
-                const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
+                const double dx = pair_dx<LPP>(g, xi - pj.x), dy = yi - pj.y;
                 const double r2 = dx * dx + dy * dy;
                 if (r2 > kR2Min && r2 < ph.kc.rcut2) {
                     acc = true;
@@ -891,7 +908,7 @@ __device__ __forceinline__ void density_body(const Clock *clk, int q, const Grid
                     k = ranges_index(wlo[0], wlo[1], wlo[2], w0, w1, v);
                     const double2 pj = w.pos[k];
                     const double Volj = w.a[k].x;  // requested with the position, not after the distance test
-                    const double dx = min_image(g, xi - pj.x), dy = yi - pj.y;
+                    const double dx = pair_dx<LPP>(g, xi - pj.x), dy = yi - pj.y;
                     const double r2 = dx * dx + dy * dy;
                     if (r2 > kR2Min && r2 < ph.kc.rcut2) {
                         acc = true;
@@ -999,10 +1016,12 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
                         "s"(g.half_DL), "s"(ph.kc.h), "s"(ph.kc.inv_h), "s"(ph.kc.sigma_over_h), "s"(ph.rho0), "s"(ph.p0), "s"(head.run),
                         "s"(head.n), "s"(head.dt));
     }
-    const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
-    const bool closes = finish_half && in_cap && sub == 0;
-    const double4 a_own = closes ? t.a[i] : make_double4(0.0, 0.0, 0.0, 0.0);
-    const double drho_own = closes ? s.drho[i] : 0.0;
+    constexpr bool kOwn = kRowsAhead<LPP>;  // (own_slot: no test around the own records)
+    const int io = own_slot<LPP>(i, t.cap);
+    const double2 pi = (kOwn || in_cap) ? s.pos[io] : make_double2(0.0, 0.0);
+    const bool closes = finish_half && (kOwn || (in_cap && sub == 0));
+    const double4 a_own = closes ? t.a[io] : make_double4(0.0, 0.0, 0.0, 0.0);
+    const double drho_own = closes ? s.drho[io] : 0.0;
     const int nn_all = list_rows(kRowsAhead<LPP> ? head.packed : t.nl_cnt[tid]);
     const FirstRows<LPP> first = kRowsAhead<LPP> ? FirstRows<LPP>(head.e0, head.e1) : FirstRows<LPP>(t.nl_idx, t.nl_stride, tid);
     const double dt = kRowsAhead<LPP> ? head.dt : clk->dt;
@@ -1019,7 +1038,7 @@ __device__ __forceinline__ void kgc_pass(const Clock *clk, int q, const Grid &g,
             Volj = *(wall ? &w.a[k].x : (const double *)&t.vol[k]);
         };
         auto term = [&](const double2 pj, double Volj) {
-            kgc_moment_add(ph.kc, min_image(g, xi - pj.x), yi - pj.y, Volj, a11, a12, a21, a22);
+            kgc_moment_add(ph.kc, pair_dx<LPP>(g, xi - pj.x), yi - pj.y, Volj, a11, a12, a21, a22);
         };
         if (kRowsAhead<LPP>) {  // rows 0 and 1: both rows' records in one wave
             const int e0 = nn_all > 0 ? first.e0 : 0, e1 = nn_all > 1 ? first.e1 : 0;
@@ -1096,18 +1115,21 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
                         "s"(w.pos), "s"(w.a), "s"(g.DL), "s"(g.half_DL), "s"(ph.kc.h), "s"(ph.kc.inv_h), "s"(ph.kc.sigma_over_h),
                         "s"(ph.mu), "s"(ph.c_f), "s"(ph.g), "s"(ph.tc), "s"(ph.DL), "s"(head.run), "s"(head.n), "s"(head.dt));
     }
-    const int c_binned = (HIST && in_cap && sub == 0) ? s.cell[i] : 0;
-    const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
-    const double2 vi = in_cap ? s.vel[i] : make_double2(0.0, 0.0);
-    const double4 ai = in_cap ? t.a[i] : make_double4(1.0, 0.0, 0.0, 0.0);
-    const double4 Bi = in_cap ? t.B[i] : make_double4(1.0, 0.0, 0.0, 1.0);
-    const double mi = in_cap ? s.mass[i] : 1.0;
+    constexpr bool kOwn = kRowsAhead<LPP>;  // (own_slot: no test around the own records)
+    const int io = own_slot<LPP>(i, t.cap);
+    const bool own = kOwn || in_cap, own_lead = kOwn || (in_cap && sub == 0);
+    const int c_binned = (HIST && own_lead) ? s.cell[io] : 0;
+    const double2 pi = own ? s.pos[io] : make_double2(0.0, 0.0);
+    const double2 vi = own ? s.vel[io] : make_double2(0.0, 0.0);
+    const double4 ai = own ? t.a[io] : make_double4(1.0, 0.0, 0.0, 0.0);
+    const double4 Bi = own ? t.B[io] : make_double4(1.0, 0.0, 0.0, 1.0);
+    const double mi = own ? s.mass[io] : 1.0;
     const int nn_all = list_rows(kRowsAhead<LPP> ? head.packed : t.nl_cnt[tid]);
     const FirstRows<LPP> first = kRowsAhead<LPP> ? FirstRows<LPP>(head.e0, head.e1) : FirstRows<LPP>(t.nl_idx, t.nl_stride, tid);
     const bool tracked = s.posb != nullptr;
-    const double2 pb = (tracked && in_cap && sub == 0) ? s.posb[i] : make_double2(0.0, 0.0);
-    const double2 fp_own = (later && in_cap) ? t.fp[i] : make_double2(0.0, 0.0);
-    const double2 p_now = (later && in_cap && sub == 0) ? t.posn[i] : make_double2(0.0, 0.0);
+    const double2 pb = (tracked && own_lead) ? s.posb[io] : make_double2(0.0, 0.0);
+    const double2 fp_own = (later && own) ? t.fp[io] : make_double2(0.0, 0.0);
+    const double2 p_now = (later && own_lead) ? t.posn[io] : make_double2(0.0, 0.0);
     const double dt = kRowsAhead<LPP> ? head.dt : clk->dt;
     const int run_q = kRowsAhead<LPP> ? head.run : clk->run[q], n_now = kRowsAhead<LPP> ? head.n : clk->n;
     if (kRowsAhead<LPP>) requests_issued();
@@ -1126,7 +1148,7 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     double2 pj0 = make_double2(0.0, 0.0), pj1 = pj0;
     double4 aj0 = make_double4(0.0, 0.0, 0.0, 0.0), aj1 = aj0;
     auto fluid_term = [&](const double2 pj, const double2 vj, const double4 aj, const double4 Bj) {
-        const auto [r, ex, ey] = pair_geom(min_image(g, xi - pj.x), yi - pj.y);
+        const auto [r, ex, ey] = pair_geom(pair_dx<LPP>(g, xi - pj.x), yi - pj.y);
         const double dW = spline_dW_in(ph.kc, r);
         const double Volj = aj.x;
         const double tx = (b11i + Bj.x) * ex + (b12i + Bj.y) * ey;
@@ -1155,7 +1177,7 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
         py -= (p_face * ty) * dWVj;
     };
     auto wall_term = [&](const double2 pj, const double4 wj) {
-        const WallPair wp = wall_pair(ph.kc, min_image(g, xi - pj.x), yi - pj.y, wj.x, Bi);
+        const WallPair wp = wall_pair(ph.kc, pair_dx<LPP>(g, xi - pj.x), yi - pj.y, wj.x, Bi);
         const double coeff = 4.0 * wp.eBe * ph.mu * wp.dWVj * rcp_nr(wp.r + 0.01 * h);
         ax += coeff * (vxi - wj.y);
         ay += coeff * (vyi - wj.z);
@@ -1218,7 +1240,7 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
     if (active) {
         const double acx = fpx * inv_m, acy = fpy * inv_m;
         auto wall_pressure = [&](const double2 pj, double Volw) {
-            wall_pressure_add(ph.kc, min_image(g, xi - pj.x), yi - pj.y, Volw, Bi, acx, acy, p_i, rhoh_i, px, py);
+            wall_pressure_add(ph.kc, pair_dx<LPP>(g, xi - pj.x), yi - pj.y, Volw, Bi, acx, acy, p_i, rhoh_i, px, py);
         };
         if (kRowsAhead<LPP>) {  // (the prefetched rows from registers; lanes with more wall rows read the rest again)
             if (first_wall <= 0 && nn_all > 0) wall_pressure(pj0, aj0.x);
@@ -2484,12 +2506,13 @@ struct FoldRebin {
     __device__ __forceinline__ int slot(int v) const { return ranges_index(lo[0], lo[1], lo[2], n[0], n[1], v); }
 };
 // load: what the prologue requests ...
-__device__ __forceinline__ void fold_load(FoldRebin &r, const Grid &g, const FluidSet &s, const FluidTmp &t, int i, bool in_cap, bool lead)
+// (io: the particle's own slot, own_slot -- every lane loads, only the lead lane of an active particle uses cold and mass)
+__device__ __forceinline__ void fold_load(FoldRebin &r, const Grid &g, const FluidSet &s, const FluidTmp &t, int io)
 {
-    r.cnew = in_cap ? t.cellid[i] : 0;
-    r.id = in_cap ? s.id[i] : 0;
-    r.cold = lead ? s.cell[i] : 0;
-    r.mass = lead ? s.mass[i] : 0.0;
+    r.cnew = t.cellid[io];
+    r.id = s.id[io];
+    r.cold = s.cell[io];
+    r.mass = s.mass[io];
 #pragma unroll
     for (int j = 0; j < FoldRebin::kPer; ++j) r.hist[j] = t.count[min((int)threadIdx.x * FoldRebin::kPer + j, g.ncells)];
 }
@@ -2645,22 +2668,23 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
     }
     const int run_first = head.run, n_first = head.n;
     const double dt_first = head.dt;
-    const double2 pi = in_cap ? s.pos[i] : make_double2(0.0, 0.0);
-    const double2 vi = in_cap ? t.veln[i] : make_double2(0.0, 0.0);
+    const int io = kAhead ? own_slot<LPP>(i, t.cap) : i;  // (the compact form: no test around the own records)
+    const double2 pi = (kAhead || in_cap) ? s.pos[io] : make_double2(0.0, 0.0);
+    const double2 vi = (kAhead || in_cap) ? t.veln[io] : make_double2(0.0, 0.0);
     const int packed = kAhead ? head.packed : t.nl_cnt[tid];
     const int nn_all = list_rows(packed);
     // (WALK: the first two words of the packed fluid rows, see FluidTmp::nl_pk)
     const FirstRows<LPP> first = kAhead ? FirstRows<LPP>(head.e0, head.e1) : FirstRows<LPP>(WALK ? t.nl_pk : t.nl_idx, t.nl_stride, tid);
-    const bool lead = in_cap && sub == 0;
-    const double4 a_own = lead ? t.a[i] : make_double4(0.0, 0.0, 0.0, 0.0);
+    const bool lead = kAhead || (in_cap && sub == 0);
+    const double4 a_own = lead ? t.a[io] : make_double4(0.0, 0.0, 0.0, 0.0);
     const double rhoh_i = a_own.z;
-    const double2 pn = (lead && (do_hist || REBIN)) ? t.posn[i] : make_double2(0.0, 0.0);  // (requested whenever a histogram is possible)
+    const double2 pn = (lead && (do_hist || REBIN)) ? t.posn[io] : make_double2(0.0, 0.0);  // (requested whenever a histogram is possible)
     FoldRebin fold;
-    if (REBIN) fold_load(fold, g, s, t, i, in_cap, lead);
+    if (REBIN) fold_load(fold, g, s, t, io);
     const TileMap layout = (WALK && TILE > 0) ? tile_map_of(t, blk) : TileMap{0, 0, 0, 0, 0, 0};
     const double dt = kAhead ? dt_first : clk->dt;
     const bool want_out = !WALK || step_outputs_wanted(clk, t);
-    const int cell_own = (g.own_by_cell && lead) ? s.cell[i] : 0;
+    const int cell_own = (g.own_by_cell && lead) ? s.cell[io] : 0;
     if (kAhead) requests_issued();
     if (REBIN) fold_runs(fold, g, s);
     if (!(kAhead ? run_first : clk->run[q])) return;
@@ -2754,7 +2778,7 @@ __device__ __forceinline__ void continuity_body(Clock *clk, int q, const Grid &g
         });
     } else if (active) {
         auto term = [&](const double2 pj, const double2 vj, double Volj) {
-            continuity_add(ph.kc, min_image(g, xi - pj.x), yi - pj.y, vxi, vyi, vj.x, vj.y, Volj, rate);
+            continuity_add(ph.kc, pair_dx<LPP>(g, xi - pj.x), yi - pj.y, vxi, vyi, vj.x, vj.y, Volj, rate);
         };
         if (kAhead) {
             // rows 0 and 1: both rows' records in one wave -- position, volume and velocity of either kind of neighbour through
