@@ -1146,6 +1146,87 @@ int sphx_batch_dens_stats_read(sphx_batch *batch, int member, int band, int capa
                                double *t_last);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2t. Mode amplitudes: the flow projected on the channel's own modes at every sampled step, recorded on the device, inside
+ *     the step loop.  The other samplers describe the flow in y-bins, at nodes, at points, per particle and per pair; this
+ *     one says which LENGTH SCALES carry a signal.  The channel is periodic in x and has walls in y, so its acoustic
+ *     eigenmodes and the eigenfunctions of its viscous start-up are products of exp(i 2 pi m x / DL) with cos(n pi y / DH)
+ *     or sin(n pi y / DH): the sine coefficients of u_x are the terms of the start-up series (profile.poiseuille_startup),
+ *     the amplitudes of the count are the structure factor.
+ *
+ *  One sample: with thx = 2 pi x_i / DL and thy = pi y_i / DH of fluid particle i, for every mode 0 <= m <= mx,
+ *    0 <= n <= ny, every field f -- n (q = 1), ux (q = u_x), uy (q = u_y) -- and every basis k -- cc = cos(m thx) cos(n thy),
+ *    sc = sin cos, cs = cos sin, ss = sin sin -- the sum S[m][n][f][k] = sum_i q_i * basis_k(i) over ALL fluid particles,
+ *    unweighted (the fluid masses are equal: mass * n is the density mode); walls are never in.  Only pos / vel are sampled.
+ *  Records: one per sampled step: `step` and `t` in times[capacity][2] and the sample in
+ *    records[capacity][mx + 1][ny + 1][SPHX_MODE_FIELDS][SPHX_MODE_BASES], filled in step order; a full buffer drops and
+ *    counts further records in n_dropped, it does not wrap (the semantics of section 2j).  mx, ny <= 16.  Cap:
+ *    capacity * (mx + 1) * (ny + 1) * 12 <= 1 << 27 doubles (1 GiB), over all members of a batch.
+ *  Gating: as in section 2j.  sphx_ctx_modes_sample appends a record of the state now, without gating.
+ *  Determinism: every term q_i * basis_k(i) is rounded once to int64 fixed point and depends on particle i alone, and the
+ *    integers are added exactly: a record is bit-identical whatever the particle order, layout, lanes per particle,
+ *    re-binning phase or workgroup count.  m = 0 and n = 0 are exact: S[0][0][n][cc] is the particle count and every sine sum
+ *    of a zero mode is 0.  A velocity above the bound of section 2a (a non-finite state) makes a later read fail with
+ *    SPHX:Modes:range.
+ *  Off by default.  With it off a step slot enqueues exactly the launches it does without this feature; on, every step slot
+ *    ends with one more launch (k_modes, behind the other samplers; it skips itself on the steps gated out) that is captured
+ *    in the replayed graphs; enable / disable re-capture them.  Independent of the other samplers.
+ *  Errors: SPHX:Modes:config (NULL config, mx or ny outside 0..16, every < 1, capacity < 1, a NaN t_from, the cap on the
+ *    record buffer, or the allocation fails: the context then goes on without the sampler), SPHX:Modes:disabled
+ *    (SPHX_ERR_STATE), SPHX:Modes:range (SPHX_ERR_STATE), SPHX:Modes:capacity (the caller's arrays are smaller than
+ *    n_records); every call on a slab context fails with SPHX_ERR_ARG, SPHX:Modes:slab.  A refused enable leaves a running
+ *    sampler, and its records, untouched.
+ * ---------------------------------------------------------------------------------------------- */
+
+#define SPHX_MODE_FIELDS 3 /* n, ux, uy */
+#define SPHX_MODE_BASES 4  /* cc, sc, cs, ss */
+#define SPHX_MODES_MAX 16
+
+typedef struct sphx_modes_config {
+    int32_t mx, ny;            /* modes 0 .. mx in x and 0 .. ny in y, each 0 .. 16                      */
+    int32_t every;             /* record every `every`-th completed step (step count % every == 0), >= 1 */
+    int32_t capacity;          /* records the device buffer holds, >= 1                                  */
+    double t_from;             /* only steps ending at t >= t_from                                       */
+} sphx_modes_config;
+
+/* (Re)configure and empty the buffer; waits for the stream.  Off by default. */
+int sphx_ctx_modes_enable(sphx_ctx *ctx, const sphx_modes_config *cfg);
+/* Stop recording (no-op when off); the records are dropped. */
+int sphx_ctx_modes_disable(sphx_ctx *ctx);
+/* Append one record of the current state (what sphx_ctx_download would return) now, without gating. */
+int sphx_ctx_modes_sample(sphx_ctx *ctx);
+/* The records so far, in step order: times [capacity][2] and records [capacity][*mx + 1][*ny + 1][3][4], row-major (times /
+ * records NULL: that array is not copied; both NULL: only the shape and the counts are reported and capacity is not
+ * checked).  Waits for and settles everything enqueued, like sphx_ctx_download.  drain != 0: the buffer is emptied and
+ * n_dropped zeroed after copying. */
+int sphx_ctx_modes_read(sphx_ctx *ctx, int capacity, double *times, double *records, int *mx, int *ny, int *n_records,
+                        int64_t *n_dropped, int drain);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2u. Mode amplitudes of a batch (section 2b): the records of section 2t for every member at once.
+ *
+ *  One config for all members; `capacity` is per member.  Every member has its own record buffer, n_records, n_dropped and
+ *  range flag, and is recorded on its own clock with the gating of section 2t, so a member that sits out slots records
+ *  nothing in them and its counters are not touched.  A member's records are bit for bit those of a standalone context
+ *  with the same parameters and config that took the same steps.  With the sampler on, every step slot of the batch ends
+ *  with one recording launch for all members (k_modes_b, behind the batch's other samplers); off, a slot enqueues exactly the
+ *  launches it does without this feature.  n_members * capacity * (mx + 1) * (ny + 1) * 12 must not exceed 1 << 27 doubles.
+ *  Errors: SPHX:Batch:null (NULL batch), SPHX:Modes:config (as in section 2t, with the total over the members),
+ *  SPHX:Modes:disabled, SPHX:Modes:capacity (the caller's capacity is below the largest n_records of any member);
+ *  SPHX:Modes:range names the member whose flag is set.
+ * ---------------------------------------------------------------------------------------------- */
+
+int sphx_batch_modes_enable(sphx_batch *batch, const sphx_modes_config *cfg);
+int sphx_batch_modes_disable(sphx_batch *batch);
+/* settles; appends a record of what sphx_batch_download returns, every member, without gating */
+int sphx_batch_modes_sample(sphx_batch *batch);
+/* One call for all members.  times is [n_members][capacity][2] and records [n_members][capacity][*mx + 1][*ny + 1][3][4],
+ * row-major: member m's block lies behind member m - 1's, its records fill rows 0 .. n_records[m] - 1 and the other rows are
+ * left as they are.  n_records and n_dropped are [n_members]; any pointer may be NULL.  Settles first, as
+ * sphx_batch_download does.  drain != 0: every member's buffer is emptied and its n_dropped zeroed after copying. */
+int sphx_batch_modes_read(sphx_batch *batch, int capacity, double *times, double *records, int *mx, int *ny, int *n_records,
+                          int64_t *n_dropped, int drain);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. x-slab contexts (multi-GPU). The channel is cut into n_ranks slabs of whole cell columns; each
  *    rank (one process per GPU) holds its columns plus halo_cols columns of copies on either side.
  *    The reference has no counterpart (single process).  One step is

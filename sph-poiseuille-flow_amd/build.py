@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["sphx_common.hip", "sphx_pairlist.hip", "sphx_resident.hip"]
 HEADERS = ["sphx_common.hpp", "sphx_device.hpp", "sphx_kernels.hpp", "sphx_slot_sample.hpp", "sphx_flow_stats.hpp", "sphx_history.hpp", "sphx_field_map.hpp",
-           "sphx_probes.hpp", "sphx_profile_series.hpp", "sphx_pair_dist.hpp", "sphx_grad_stats.hpp", "sphx_tracers.hpp", "sphx_dens_stats.hpp", "sphx_sampler_state.hpp", "sphx_samplers.hpp", "sphx_batch.hpp", "sphx_xcd_block.hpp", os.path.join("..", "..", "include", "sphx.h")]
+           "sphx_probes.hpp", "sphx_profile_series.hpp", "sphx_pair_dist.hpp", "sphx_grad_stats.hpp", "sphx_tracers.hpp", "sphx_dens_stats.hpp", "sphx_modes.hpp", "sphx_sampler_state.hpp", "sphx_samplers.hpp", "sphx_batch.hpp", "sphx_xcd_block.hpp", os.path.join("..", "..", "include", "sphx.h")]
 LIB = os.path.join(CSRC, "libsphx.so")
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]

@@ -98,6 +98,16 @@ class SphxDensStatsConfig(C.Structure):
                 ("hist_range", C.c_double), ("delta_bound", C.c_double), ("band_x", C.c_double * 2), ("band_hw", C.c_double * 2)]
 
 
+class SphxModesConfig(C.Structure):
+    _fields_ = [("mx", C.c_int32), ("ny", C.c_int32), ("every", C.c_int32), ("capacity", C.c_int32), ("t_from", C.c_double)]
+
+
+# the fields and bases of a mode (include/sphx.h section 2t), in the order the library writes them
+MODE_FIELDS = ("n", "ux", "uy")
+MODE_BASES = ("cc", "sc", "cs", "ss")
+MODES_MAX = 16
+
+
 class SphxStatus(C.Structure):
     _fields_ = [("t", C.c_double), ("dt_last", C.c_double), ("dt_next", C.c_double), ("vmax", C.c_double),
                 ("step", C.c_int64), ("done", C.c_int32), ("device_status", C.c_int32)]
@@ -131,6 +141,7 @@ EXPORTS = [
     "sphx_ctx_tracers_enable", "sphx_ctx_tracers_disable", "sphx_ctx_tracers_sample", "sphx_ctx_tracers_read",
     "sphx_ctx_dens_stats_enable", "sphx_ctx_dens_stats_disable", "sphx_ctx_dens_stats_reset", "sphx_ctx_dens_stats_sample",
     "sphx_ctx_dens_stats_read",
+    "sphx_ctx_modes_enable", "sphx_ctx_modes_disable", "sphx_ctx_modes_sample", "sphx_ctx_modes_read",
     "sphx_slab_create", "sphx_slab_layout", "sphx_slab_local_vmax", "sphx_slab_prepare", "sphx_slab_compute",
     "sphx_slab_finish", "sphx_slab_sync", "sphx_slab_snapshot", "sphx_comm_available", "sphx_comm_unique_id", "sphx_comm_selftest", "sphx_comm_selftest_graph", "sphx_slab_comm_init",
     "sphx_slab_comm_destroy", "sphx_slab_run", "sphx_slab_group_run", "sphx_slab_graph_prepare",
@@ -160,6 +171,7 @@ EXPORTS = [
     "sphx_batch_dens_stats_enable", "sphx_batch_dens_stats_disable", "sphx_batch_dens_stats_reset", "sphx_batch_dens_stats_sample",
     "sphx_batch_dens_stats_read",
     "sphx_batch_tracers_enable", "sphx_batch_tracers_disable", "sphx_batch_tracers_sample", "sphx_batch_tracers_read",
+    "sphx_batch_modes_enable", "sphx_batch_modes_disable", "sphx_batch_modes_sample", "sphx_batch_modes_read",
 ]
 
 _LIB = None
@@ -862,6 +874,51 @@ class _Stepped(_Sampled):
         per = [dict(s, **dens_stats_profiles(DH, p.p0, s)) for p, s in zip(prms, sums if self._many else [sums])]
         return self._each(per)
 
+    # ---- mode amplitudes (include/sphx.h sections 2t, 2u): the flow on the channel's modes, one record per sampled step ----
+    def modes_enable(self, mx=4, ny=8, every=1, capacity=4096, t_from=0.0):
+        """Record, every `every`-th completed step ending at t >= t_from, the sums of 1, u_x and u_y over the fluid particles
+        times cos / sin(m 2 pi x / DL) cos / sin(n pi y / DH) for 0 <= m <= mx, 0 <= n <= ny (profile.mode_sums) into a
+        device buffer of `capacity` records ((re)configures and empties it).  Records that find the buffer full are dropped
+        and counted.  A record is (mx + 1) * (ny + 1) * 12 doubles.  A batch: one config for all members, `capacity` records
+        per member, each recorded on its own clock."""
+        cfg = modes_config(mx, ny, every, capacity, t_from, n_members=self._channels())
+        self._call("modes_enable", C.byref(cfg))
+        self._modes = (int(cfg.mx), int(cfg.ny))  # (mx, ny) while the mode amplitudes are on
+
+    def modes_disable(self):
+        self._call("modes_disable")
+        self._modes = None
+
+    def _modes_on(self):
+        return _enabled(self._modes, "Modes", f"mode amplitudes are not enabled on this {self._where}")
+
+    def modes_sample(self):
+        """Append one record of the current state (what download() returns) now, whatever the gating; a batch: of every member."""
+        self._modes_on()
+        self._call("modes_sample")
+
+    def modes(self, drain=False):
+        """The records so far: step (int64) and t [n], the three MODE_FIELDS n, ux, uy as [n, mx + 1, ny + 1, 4] arrays (last
+        axis: MODE_BASES cc, sc, cs, ss) and n_dropped; drain empties the buffer after the copy.  A batch: one such dict per
+        member, from one read of all members."""
+        mx, ny = self._modes_on()
+        m = self._channels()
+        n, dropped = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int64)
+        gx, gy = C.c_int(0), C.c_int(0)
+
+        def read(cap, times, records, drain):
+            self._call("modes_read", C.c_int(cap), ptr(times), ptr(records), C.byref(gx), C.byref(gy),
+                       n.ctypes.data_as(C.POINTER(C.c_int)), dropped.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(1 if drain else 0))
+
+        read(0, None, None, False)
+        assert (gx.value, gy.value) == (mx, ny), (gx.value, gy.value, mx, ny)
+        cap, want = max(int(n.max()), 1), n.copy()
+        times = np.zeros((m, cap, 2))
+        records = np.zeros((m, cap, mx + 1, ny + 1, len(MODE_FIELDS), len(MODE_BASES)))
+        read(cap, times, records, drain)
+        assert np.array_equal(n, want), (n, want)
+        return self._each([modes_dict(times[k, :n[k]], records[k, :n[k]], int(dropped[k])) for k in range(m)])
+
 
 class Batch(_Stepped):
     """M channels of one geometry stepped by the same launches (sphx_batch, include/sphx.h section 2b).
@@ -907,6 +964,7 @@ class Batch(_Stepped):
         self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
         self._tracers = None     # the ids [T] (int32) while the tracers are on
         self._dens_stats = None  # (n_bins, n_bands incl. band 0, n_hist, hist_range) while the density statistics are on
+        self._modes = None       # (mx, ny) while the mode amplitudes are on
         arr = (SphxParams * m)(*self.params)
         check(lib().sphx_batch_create(C.byref(self._h), C.c_int(m), arr, C.c_int(n_fluid), C.c_int(n_total),
                                       ptr(states[0]), ptr(states[1]), ptr(states[2]), ptr(mass), ptr(wall_vel),
@@ -960,6 +1018,7 @@ class Context(_Stepped):
         self._grad_stats = None  # (n_bins, n_bands incl. band 0) while the gradient statistics are on
         self._tracers = None     # the ids [T] (int32) while the tracers are on
         self._dens_stats = None  # (n_bins, n_bands incl. band 0, n_hist, hist_range) while the density statistics are on
+        self._modes = None       # (mx, ny) while the mode amplitudes are on
         check(lib().sphx_ctx_create(C.byref(self._h), C.byref(self.params), C.c_int(n_fluid), C.c_int(n_total),
                                     ptr(pos), ptr(vel), ptr(drho_dt), ptr(mass), ptr(wall_vel),
                                     C.c_double(t0), C.c_int64(step0)))
@@ -1323,6 +1382,36 @@ def dens_stats_config(prm, n_bins=0, every=1, t_from=0.0, n_hist=64, hist_range=
     for k in range(2):
         cfg.band_x[k], cfg.band_hw[k] = f.band_x[k], f.band_hw[k]
     return cfg
+
+
+def modes_config(mx=4, ny=8, every=1, capacity=4096, t_from=0.0, n_members=1) -> SphxModesConfig:
+    """Checked sphx_modes_config; raises SphxError(SPHX:Modes:config) before anything reaches the device.  n_members: the
+    channels that get `capacity` records each (a batch's members)."""
+    bad = _config_error("Modes")
+    for name, v in (("mx", mx), ("ny", ny)):
+        if not _is_int(v) or not 0 <= v <= MODES_MAX:
+            raise bad(f"{name} must be an integer in 0..16")
+    try:
+        f = flow_stats_config(0, every, t_from, ())
+    except SphxError as e:
+        raise bad(e.message) from None
+    if not _is_int(capacity) or capacity < 1 or capacity >= 1 << 31:
+        raise bad("capacity must be an integer >= 1")
+    if n_members * capacity * (mx + 1) * (ny + 1) * len(MODE_FIELDS) * len(MODE_BASES) > 1 << 27:
+        raise bad(("n_members * " if n_members > 1 else "") + "capacity * (mx + 1) * (ny + 1) * 12 must not exceed 1 << 27 doubles")
+    return SphxModesConfig(mx=int(mx), ny=int(ny), every=int(f.every), capacity=int(capacity), t_from=float(f.t_from))
+
+
+def modes_dict(times, records, n_dropped=0) -> dict:
+    """times [n, 2] and records [n, mx + 1, ny + 1, 3, 4] -> step (int64), t [n], one [n, mx + 1, ny + 1, 4] array per
+    MODE_FIELDS (last axis: MODE_BASES) and n_dropped."""
+    times = np.asarray(times, dtype=np.float64).reshape(-1, 2)
+    records = np.asarray(records, dtype=np.float64)
+    assert records.ndim == 5 and records.shape[0] == len(times) and records.shape[3:] == (len(MODE_FIELDS), len(MODE_BASES)), records.shape
+    out = dict(step=times[:, 0].astype(np.int64), t=np.ascontiguousarray(times[:, 1]))
+    out.update({k: np.ascontiguousarray(records[:, :, :, j, :]) for j, k in enumerate(MODE_FIELDS)})
+    out["n_dropped"] = int(n_dropped)
+    return out
 
 
 def profile_series_dict(DH, times, records, n_dropped=0) -> dict:

@@ -971,3 +971,57 @@ SPHX_EXPORT int sphx_batch_dens_stats_read(sphx_batch *b, int member, int band, 
     return SPHX_OK;
     SPHX_CATCH
 }
+
+// ---- mode amplitudes of every member (include/sphx.h section 2u) ----
+
+namespace {
+
+// the batch's mode amplitudes (member 0's, see sphx_ctx::modes)
+Modes &batch_modes(sphx_batch *b, bool need_on)
+{
+    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
+    Modes &p = b->mem[0]->modes;
+    sampler_check(kModesNames, false, p.on, need_on, "batch");
+    return p;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_batch_modes_enable(sphx_batch *b, const sphx_modes_config *cfg)
+{
+    SPHX_TRY
+    // (out of device memory: the batch goes on without the sampler)
+    Modes &p = batch_modes(b, false);
+    modes_enable(p, cfg, b->M, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_modes_disable(sphx_batch *b)
+{
+    SPHX_TRY
+    Modes &p = batch_modes(b, false);
+    if (p.on) sampler_off(p, b->sched, b->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_modes_sample(sphx_batch *b)
+{
+    SPHX_TRY
+    batch_modes(b, true);
+    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
+    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_modes);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_batch_modes_read(sphx_batch *b, int capacity, double *times, double *records, int *mx, int *ny, int *n_records,
+                                      int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    Modes &p = batch_modes(b, true);
+    modes_read(p, b->stream, [b] { batch_settle(b); }, capacity, times, records, mx, ny, n_records, n_dropped, drain);
+    return SPHX_OK;
+    SPHX_CATCH
+}

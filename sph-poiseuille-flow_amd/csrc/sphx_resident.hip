@@ -265,6 +265,7 @@ struct sphx_ctx {
     GradStats grads;
     Tracers tracers;
     DensStats dens;
+    Modes modes;
 
     // Member of a batch (sphx_batch_*): the device arrays are this member's blocks of batch-wide allocations (BatchArena)
     sphx::BatchArena *arena = nullptr;
@@ -2118,7 +2119,7 @@ SPHX_EXPORT int sphx_ctx_profile_read(sphx_ctx *c, int capacity, const char **na
     SPHX_CATCH
 }
 
-#include "sphx_samplers.hpp"  // the slot samplers: launches, lifecycle, sphx_ctx_flow_stats_* / history_* / field_map_* / probes_* / profile_series_* / pair_dist_* / grad_stats_* / tracers_* / dens_stats_*
+#include "sphx_samplers.hpp"  // the slot samplers: launches, lifecycle, sphx_ctx_flow_stats_* / history_* / field_map_* / probes_* / profile_series_* / pair_dist_* / grad_stats_* / tracers_* / dens_stats_* / modes_*
 
 SPHX_EXPORT int sphx_ctx_info(sphx_ctx *c, int *n_fluid, int *n_wall, int *n_cell_x, int *n_cell_y)
 {

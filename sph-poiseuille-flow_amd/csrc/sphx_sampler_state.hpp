@@ -11,6 +11,7 @@
 #include "sphx_grad_stats.hpp"
 #include "sphx_tracers.hpp"
 #include "sphx_dens_stats.hpp"
+#include "sphx_modes.hpp"
 
 struct sphx_ctx;
 
@@ -226,8 +227,29 @@ struct DensStats {
               double *t_first, double *t_last) const;
 };
 
+// Mode amplitudes (sphx_ctx_modes_*, sphx_batch_modes_*; sphx_modes.hpp) of a context or of the M members of a batch: one
+// configuration, member m's int64 sums of the sample in flight at m * block(), its times at m * cfg.capacity * 2, its records
+// at m * cfg.capacity * block(), its head at m.
+struct Modes {
+    bool on = false;
+    int members = 1;
+    sphx_modes_config cfg{};
+    DevBuf<unsigned long long> isum;
+    DevBuf<double> times, records;
+    DevBuf<ModesHead> head;
+
+    size_t block() const { return (size_t)(cfg.mx + 1) * (size_t)(cfg.ny + 1) * kModeSums; }  // the doubles of one record
+    size_t shmem() const { return block() * sizeof(unsigned long long); }                     // the LDS counters of a workgroup
+    int groups() const { return (cfg.mx + 1) * modes_runs(cfg.ny); }                          // what a workgroup serves one of
+    void check(const sphx_modes_config *cfg, int M);
+    void alloc(const Modes &checked, int M);
+    void zero(hipStream_t st) { isum.zero(st); head.zero(st); }  // (the counters: records beyond n_records are never read)
+    void release() { isum.release(); times.release(); records.release(); head.release(); }
+    void read(hipStream_t st, int capacity, double *times, double *records, int *n_records, int64_t *n_dropped, bool drain);
+};
+
 // the samplers that are on, behind step slot q, which ran on layout l: statistics, history, field map, probes, profile series,
-// pair statistics, gradient statistics, tracers, density statistics (sphx_samplers.hpp)
+// pair statistics, gradient statistics, tracers, density statistics, mode amplitudes (sphx_samplers.hpp)
 void launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild);
 
 }  // namespace sphx

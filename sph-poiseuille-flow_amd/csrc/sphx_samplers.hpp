@@ -2,7 +2,8 @@
 // translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
 // the velocity-field map (2e; 2g), the point probes (2h; 2i), the profile series (2j; 2k), the pair statistics (2l; 2m,
 // sphx_pair_dist.hpp), the gradient statistics (2n; 2o, sphx_grad_stats.hpp), the particle tracers (2p; 2q, sphx_tracers.hpp) and
-// the density statistics (2r; 2s, sphx_dens_stats.hpp) -- all nine also of a slab of a ring (3a, at the end of this file).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
+// the density statistics (2r; 2s, sphx_dens_stats.hpp) -- all nine also of a slab of a ring (3a, at the end of this file) -- and
+// the mode amplitudes (2t; 2u, sphx_modes.hpp).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
 // sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
 // "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
 #pragma once
@@ -39,6 +40,8 @@ constexpr SamplerNames kTracerNames{"Tracers", "the tracers of a slab are sphx_s
                                     "particle tracers are not enabled on this ", "the record buffer could not be set up: "};
 constexpr SamplerNames kDensNames{"DensStats", "the density statistics of a slab are sphx_slab_dstats_* (include/sphx.h section 3a)",
                                   "density statistics are not enabled on this ", "the sums could not be set up: "};
+constexpr SamplerNames kModesNames{"Modes", "mode amplitudes are not available on slab contexts", "mode amplitudes are not enabled on this ",
+                                   "the record buffer could not be set up: "};
 
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
 
@@ -392,6 +395,36 @@ void launch_dens_stats(sphx_ctx *c, int q, const FluidSet &s, int every)
                  c->grid, per_member(c->phys), s, c->walls, dens_stats_args(c, every));
 }
 
+// the arguments of a mode-amplitudes launch on state s into c->modes
+ModesArgs modes_args(sphx_ctx *c, const FluidSet &s, int every)
+{
+    const Modes &p = c->modes;
+    ModesArgs a{};
+    a.pos = s.pos; a.vel = s.vel;
+    a.isum = p.isum.get(); a.times = p.times.get(); a.records = p.records.get(); a.head = p.head.get();
+    a.DL = c->prm.DL; a.DH = c->prm.DH;
+    a.t_from = p.cfg.t_from;
+    a.mx = p.cfg.mx; a.ny = p.cfg.ny;
+    a.n_groups = p.groups();
+    a.every = every;
+    a.capacity = p.cfg.capacity;
+    return a;
+}
+
+// workgroups of the sample of a channel that holds n particles: chunks x groups, every group over every chunk
+unsigned modes_blocks(size_t n, int groups)
+{
+    const unsigned most = std::max(1u, (unsigned)kModesMaxBlocks / (unsigned)groups);
+    return std::clamp<unsigned>(div_up(n, (size_t)kModesBlock * kModesPerThread), 1u, most) * (unsigned)groups;
+}
+
+// k_modes on state s -- of a batch: member 0's -- into c->modes
+void launch_modes(sphx_ctx *c, int q, const FluidSet &s, int every)
+{
+    launch_forms(c, "k_modes", Forms{k_modes, k_modes_b}, modes_blocks((size_t)c->nf, c->modes.groups()), kModesBlock, c->modes.shmem(), q,
+                 modes_args(c, s, every));
+}
+
 }  // namespace
 
 void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
@@ -406,6 +439,7 @@ void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
     if (c->grads.on) launch_grad_stats(c, q, s, c->grads.cfg.every);
     if (c->tracers.on) launch_tracers(c, q, s, c->tracers.cfg.every);
     if (c->dens.on) launch_dens_stats(c, q, s, c->dens.cfg.every);
+    if (c->modes.on) launch_modes(c, q, s, c->modes.cfg.every);
 }
 
 // ---- flow statistics ----
@@ -1674,6 +1708,140 @@ SPHX_EXPORT int sphx_ctx_dens_stats_read(sphx_ctx *c, int band, int capacity, in
     const DensStats &f = sampler_of(c, &sphx_ctx::dens, kDensNames, true);
     dens_stats_read(f, c->stream, [c] { settle_owed(c); }, 0, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above,
                     n_samples, t_first, t_last);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+// ---- mode amplitudes ----
+
+// every check of a configuration for M channels (cfg): the modes by the kernel's limits, the record buffer by the checks of
+// ProfileSeries::check; SPHX:Modes:config errors
+void Modes::check(const sphx_modes_config *cfg, int M)
+{
+    const char *id = "SPHX:Modes:config";
+    require(cfg != nullptr, id, "config must not be NULL");
+    require(cfg->mx >= 0 && cfg->mx <= kModesMax, id, "mx must be 0 .. 16");
+    require(cfg->ny >= 0 && cfg->ny <= kModesMax, id, "ny must be 0 .. 16");
+    require(cfg->every >= 1, id, "every must be >= 1");
+    require(cfg->capacity >= 1, id, "capacity must be >= 1");
+    require(!std::isnan(cfg->t_from), id, "t_from must not be NaN");
+    if (!((double)M * (double)cfg->capacity * (double)(cfg->mx + 1) * (double)(cfg->ny + 1) * kModeSums <= (double)kSeriesMaxTotal))
+        throw Error(SPHX_ERR_ARG, id,
+                    std::string(M > 1 ? "n_members * " : "") + "capacity * (mx + 1) * (ny + 1) * 12 must not exceed 1 << 27 doubles");
+    this->cfg = *cfg;
+}
+
+// the checked configuration, and sums in flight, records and heads for M members
+void Modes::alloc(const Modes &checked, int M)
+{
+    cfg = checked.cfg;
+    members = M;
+    isum.alloc(block() * M);
+    times.alloc((size_t)M * cfg.capacity * 2);
+    records.alloc((size_t)M * cfg.capacity * block());
+    head.alloc(M);
+}
+
+// Every member's counts (n_records[m], n_dropped[m], where given) and its filled rows, into times[m][0 .. n_records[m])[2] of a
+// [members][capacity][2] array and records[m][0 .. n_records[m])[block()] of a [members][capacity][block()] array, each where
+// given; drain empties every buffer.  SPHX:Modes:range when a member's sticky flag is up; SPHX:Modes:capacity when an array is
+// given and capacity is below the largest count: nothing is copied or drained then.
+void Modes::read(hipStream_t st, int capacity, double *t_out, double *r_out, int *n_records, int64_t *n_dropped, bool drain)
+{
+    const int M = members;
+    std::vector<ModesHead> h(M);
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(ModesHead) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    long long most = 0;
+    for (int m = 0; m < M; ++m) {
+        const long long n = h[m].n_records;
+        if (n < 0 || n > (long long)cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:Modes:state", "internal: record count out of range");
+        if (h[m].range)
+            throw Error(SPHX_ERR_STATE, "SPHX:Modes:range", (M > 1 ? "member " + std::to_string(m) + ": " : std::string()) +
+                                                            "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
+        most = std::max(most, n);
+    }
+    require((t_out == nullptr && r_out == nullptr) || (long long)capacity >= most, "SPHX:Modes:capacity",
+            "capacity is smaller than the number of records");
+    if ((t_out || r_out) && most > 0) {
+        for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
+            const size_t n = (size_t)h[m].n_records;
+            if (n == 0) continue;
+            if (t_out)
+                SPHX_HIP(hipMemcpyAsync(t_out + (size_t)m * capacity * 2, times.get() + (size_t)m * cfg.capacity * 2, n * 2 * sizeof(double),
+                                        hipMemcpyDeviceToHost, st));
+            if (r_out)
+                SPHX_HIP(hipMemcpyAsync(r_out + (size_t)m * capacity * block(), records.get() + (size_t)m * cfg.capacity * block(),
+                                        n * block() * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+    for (int m = 0; m < M; ++m) {
+        if (n_records) n_records[m] = (int)h[m].n_records;
+        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
+    }
+    if (drain) {
+        zero(st);
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+}
+
+namespace {
+
+// enable for M members on schedule s: every check of cfg first
+void modes_enable(Modes &p, const sphx_modes_config *cfg, int M, Schedule &s, hipStream_t st)
+{
+    Modes checked;
+    checked.check(cfg, M);
+    sampler_on(p, kModesNames, s, st, [&] { p.alloc(checked, M); });
+}
+
+// settle() -- what is enqueued lands first -- then the read and the shape; shared by contexts and batches
+template <typename Settle>
+void modes_read(Modes &p, hipStream_t st, Settle &&settle, int capacity, double *times, double *records, int *mx, int *ny, int *n_records,
+                int64_t *n_dropped, int drain)
+{
+    settle();  // (the records of everything enqueued)
+    p.read(st, capacity, times, records, n_records, n_dropped, drain != 0);
+    if (mx) *mx = p.cfg.mx;
+    if (ny) *ny = p.cfg.ny;
+}
+
+}  // namespace
+
+SPHX_EXPORT int sphx_ctx_modes_enable(sphx_ctx *c, const sphx_modes_config *cfg)
+{
+    SPHX_TRY
+    Modes &p = sampler_to_change(c, &sphx_ctx::modes, kModesNames);
+    modes_enable(p, cfg, 1, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_modes_disable(sphx_ctx *c)
+{
+    SPHX_TRY
+    Modes &p = sampler_to_change(c, &sphx_ctx::modes, kModesNames);
+    if (p.on) sampler_off(p, c->sched, c->stream);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_modes_sample(sphx_ctx *c)
+{
+    SPHX_TRY
+    sampler_of(c, &sphx_ctx::modes, kModesNames, true);
+    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_modes);
+    return SPHX_OK;
+    SPHX_CATCH
+}
+
+SPHX_EXPORT int sphx_ctx_modes_read(sphx_ctx *c, int capacity, double *times, double *records, int *mx, int *ny, int *n_records,
+                                    int64_t *n_dropped, int drain)
+{
+    SPHX_TRY
+    Modes &p = sampler_of(c, &sphx_ctx::modes, kModesNames, true);
+    modes_read(p, c->stream, [c] { settle_owed(c); }, capacity, times, records, mx, ny, n_records, n_dropped, drain);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -19,7 +19,7 @@ from . import capi
 from .geometry import init_particles
 from .mex_surface import sph_neighbor_search_mex, sph_physics_shell_mex
 from . import restart
-from .profile import (compute_mid_channel_profile, dens_stats_profiles, field_map_means, final_profile, flow_stats_profile,
+from .profile import (compute_mid_channel_profile, dens_stats_profiles, mode_b_exact, field_map_means, final_profile, flow_stats_profile,
                       grad_stats_profiles, l2_error, n_profile_bins, pool_dens_stats, pool_field_maps, pair_dist_profiles,
                       pool_flow_stats, pool_grad_stats, pool_pair_dist,
                       poiseuille_startup, pool_tracers, profile_series_profiles, tracer_profiles, unwrap_tracers)
@@ -68,6 +68,9 @@ class RunResult:
 
     dens_stats: list = None  # run / run_sweep / run_ensemble(..., density_from=...): the device-side density statistics of the
                              # run, one dict per band (capi.Context.dens_stats: the sums with the profiles; density_figures())
+
+    modes: dict = None  # run / run_sweep(..., modes_every=...): the device-side mode amplitudes of the whole run
+                        # (capi.Context.modes: n, ux, uy per record and mode; mode_figures())
 
     def L2_time_mean(self, last=5):
         """L2 of the whole-channel profile averaged over the last `last` output points: the instantaneous profile of
@@ -263,6 +266,81 @@ def _probes_lost(who, p, t, capacity):
 
 def _profiles_lost(who, p, t, capacity):
     return _records_lost(who, "the profile series", "profiles_capacity", p, t, capacity)
+
+
+def _modes_lost(who, p, t, capacity):
+    return _records_lost(who, "the mode amplitudes", "modes_capacity", p, t, capacity)
+
+
+_MODE_KEYS = ("step", "t") + capi.MODE_FIELDS
+
+
+def _concat_modes(chunks):
+    """the mode amplitudes of a whole run (capi.modes_dict) from the drained chunks, in their order (at least one: its shape
+    is the series')"""
+    out = {k: np.concatenate([np.asarray(c[k]) for c in chunks]) for k in _MODE_KEYS}
+    out["n_dropped"] = int(sum(c["n_dropped"] for c in chunks))
+    return out
+
+
+def mode_figures(prm, modes):
+    """Figures of the mode amplitudes of a run (capi.Context.modes / RunResult.modes: n, ux, uy as [n_records, mx + 1, ny + 1, 4],
+    bases cc, sc, cs, ss) on the host, with N = n[:, 0, 0, cc] the particle count of a record.
+      b [n_records, ny + 1]       the sine coefficients of u_x across the channel, (2 / N) ux[:, 0, n, cs]
+      b_exact [n_records, ny + 1] those of the start-up of plane Poiseuille flow from rest (profile.mode_b_exact): for odd n
+                                  32 U_max / (n pi)^3 (1 - exp(-t / tau_exact[n])), one exponential per mode; 0 for even n
+      tau_fit [ny + 1]            the decay time of mode n: minus the inverse slope of a least-squares line through
+                                  log |b_exact(inf) - b| over the records with 0 < t <= 2 tau_exact[n]; NaN for even n and
+                                  with fewer than two such records
+      tau_exact [ny + 1]          DH^2 / (nu n^2 pi^2) (inf for n = 0)
+      S [mx + 1, ny + 1]          the structure factor, the time mean of (cc^2 + sc^2 + cs^2 + ss^2) / N of the field n
+      E_uy [mx + 1, ny + 1]       the same of the field uy, in U_max^2
+      f_peak [mx + 1, ny + 1]     the frequency of the largest line of the summed spectra of the four fluctuating amplitudes
+                                  of the field n (records resampled to the median dt, numpy.fft.rfft); NaN with fewer than 4
+                                  records
+      f_box [mx + 1, ny + 1]      the box's acoustic mode beside it, c sqrt((m / DL)^2 + (n / (2 DH))^2) with the artificial
+                                  speed of sound c = c_f |U_bulk| of probe_figures; f_bin: the resolution of f_peak
+    U_max = g DH^2 / (8 nu)."""
+    t = np.asarray(modes["t"], dtype=np.float64)
+    cnt, ux, uy = (np.asarray(modes[k], dtype=np.float64) for k in capi.MODE_FIELDS)
+    R, MX, NY = cnt.shape[0], cnt.shape[1], cnt.shape[2]
+    g, nu, DH, DL = prm.gravity_g, prm.nu, prm.DH, prm.DL
+    u_max = g * DH * DH / (8.0 * nu)
+    N = cnt[:, 0, 0, 0]
+    n = np.arange(NY)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        b = 2.0 * ux[:, 0, :, 2] / N[:, None]
+        tau_exact = np.where(n > 0, DH * DH / (nu * np.maximum(n, 1) ** 2 * np.pi ** 2), np.inf)
+        S = np.mean((cnt ** 2).sum(axis=3) / N[:, None, None], axis=0) if R else np.full((MX, NY), np.nan)
+        E_uy = np.mean((uy ** 2).sum(axis=3) / N[:, None, None], axis=0) / u_max ** 2 if R else np.full((MX, NY), np.nan)
+    b_exact = mode_b_exact(n[None, :], t[:, None], g, nu, DH)
+    b_inf = np.where(n % 2 == 1, 32.0 * u_max / (np.maximum(n, 1) * np.pi) ** 3, 0.0)
+    tau_fit = np.full(NY, np.nan)
+    for k in range(1, NY, 2):
+        gap = np.abs(b_inf[k] - b[:, k])
+        sel = (t > 0.0) & (t <= 2.0 * tau_exact[k]) & np.isfinite(gap) & (gap > 0.0)
+        if np.count_nonzero(sel) >= 2 and np.ptp(t[sel]) > 0.0:
+            slope = np.polyfit(t[sel], np.log(gap[sel]), 1)[0]
+            tau_fit[k] = -1.0 / slope if slope != 0.0 else np.nan
+    c = prm.c_f * abs(g * DH ** 2 / (12.0 * nu))
+    f_box = c * np.sqrt((np.arange(MX)[:, None] / DL) ** 2 + (n[None, :] / (2.0 * DH)) ** 2)
+    f_peak, f_bin = np.full((MX, NY), np.nan), float("nan")
+    dt = float(np.median(np.diff(t))) if R >= 2 else float("nan")
+    if R >= 4 and dt > 0.0:
+        tu = t[0] + dt * np.arange(int(np.floor((t[-1] - t[0]) / dt)) + 1)
+        freq = np.fft.rfftfreq(len(tu), dt)
+        if len(freq) >= 2:
+            f_bin = float(freq[1])
+            for m in range(MX):
+                for k in range(NY):
+                    power = np.zeros(len(freq))
+                    for q in range(4):
+                        v = np.interp(tu, t, cnt[:, m, k, q])
+                        power += np.abs(np.fft.rfft(v - v.mean())) ** 2
+                    if np.all(np.isfinite(power)) and power[1:].max() > 0.0:
+                        f_peak[m, k] = freq[1 + int(np.argmax(power[1:]))]
+    return dict(b=b, b_exact=b_exact, tau_fit=tau_fit, tau_exact=tau_exact, S=S, E_uy=E_uy, f_peak=f_peak, f_box=f_box, f_bin=f_bin,
+                U_max=float(u_max))
 
 
 _SERIES_KEYS = ("step", "t") + capi.STATS_FIELDS
@@ -573,7 +651,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
         profiles_every=None, profiles_from=None, profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1,
         pairs_bins=64, pairs_walls=False, pairs_bands=None, gradients_from=None, gradients_every=1, gradients_walls=False,
         gradients_bands=None, tracers=None, tracers_every=1, tracers_from=None, tracers_capacity=None, density_from=None,
-        density_every=1, density_hist=(64, 0.05), density_bands=None):
+        density_every=1, density_hist=(64, 0.05), density_bands=None, modes_every=None, modes=(4, 8), modes_from=0.0,
+        modes_capacity=4096):
     """Run to prm.t_end and return the final profile and L2 (SPH_Poiseuille.m:246-307 + postprocess :42).
 
     restart_path (resident engine): the reference's restart.mat protocol -- resume from it when
@@ -631,7 +710,14 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     delta = rho / rho0 - 1 into the reference's profile bins, for the whole channel and the bands density_bands (None: the
     mid-channel band (DL/2, max(dp, h)) as band 1), with a histogram of delta of density_hist = (n_hist, hist_range).
     RunResult.dens_stats is one dict per band; density_figures() gives delta_rms, delta_max, the spread of the pressure across
-    the channel, the bias next to the walls and the packing."""
+    the channel, the bias next to the walls and the packing.
+    modes_every (resident engine; default off): project, on the device and inside the step loop, the count, u_x and u_y of the
+    fluid particles on the channel's modes (include/sphx.h section 2t: modes = (mx, ny)) every modes_every-th step ending at
+    t >= modes_from; the buffer (modes_capacity records) is drained at every output point -- a run that lost records raises
+    RuntimeError and names the capacity needed -- and RunResult.modes is the series of the whole run (mode_figures() gives the
+    start-up coefficients b_n(t) beside the closed form, their decay times, the structure factor and the spectral peaks)."""
+    if modes_every is not None and engine != "resident":
+        raise ValueError("modes_every needs the resident engine (the amplitudes are summed on the device)")
     if density_from is not None and engine != "resident":
         raise ValueError("density_from needs the resident engine (the density is re-summed on the device)")
     if tracers is not None and engine != "resident":
@@ -681,6 +767,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
     grad_stats = None
     tracer_series, tracer_chunks = None, []
     dens_stats = None
+    mode_series, mode_chunks = None, []
     t0 = time.perf_counter()
     if engine == "resident":
         ctx = capi.Context.from_parts(prm, parts, t0=t_start, step0=step_start, lanes_per_particle=lanes_per_particle,
@@ -714,6 +801,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
             if density_from is not None:
                 ctx.dens_stats_enable(n_bins=n_bins, every=density_every, t_from=density_from, n_hist=density_hist[0],
                                       hist_range=density_hist[1], bands=_dens_bands(prm, density_bands))
+            if modes_every is not None:
+                ctx.modes_enable(mx=modes[0], ny=modes[1], every=modes_every, capacity=modes_capacity, t_from=modes_from)
             while t < prm.t_end - 1e-12:
                 target = min(t + prm.output_interval, prm.t_end)
                 while t < target - 1e-12:
@@ -744,6 +833,10 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                     tracer_chunks.append(ctx.tracers(drain=True))
                     if tracer_chunks[-1]["n_dropped"]:
                         raise _tracers_lost("", tracer_chunks[-1], t, tracing[2])
+                if modes_every is not None:
+                    mode_chunks.append(ctx.modes(drain=True))
+                    if mode_chunks[-1]["n_dropped"]:
+                        raise _modes_lost("", mode_chunks[-1], t, modes_capacity)
                 if restart_path:
                     restart.save_restart(restart_path, prm.config_signature, dict(d, t=t, step=step), fmt=mat_format)
                 if log:
@@ -771,6 +864,8 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                 tracer_series = _concat_tracers(tracing[0], tracer_chunks)
             if density_from is not None:
                 dens_stats = _dens_stats_bands(prm, [ctx.dens_stats_sums(b) for b in range(1 + len(_dens_bands(prm, density_bands)))])
+            if modes_every is not None:
+                mode_series = _concat_modes(mode_chunks or [ctx.modes()])
         finally:
             ctx.close()
     elif engine == "mex":
@@ -822,7 +917,7 @@ def run(prm, engine="resident", log=None, log_every=0, parts=None, lanes_per_par
                        mid_profile_u=mid_profiles, tau_bottom=tau_b, tau_top=tau_t, grid_policy=policy,
                        full_profile_u=full_profiles, n_inner=n_inner, time_avg=time_avg, history=history, field_avg=field_avg,
                        probes=probes, profile_series=series, pair_dist=pair_dist, grad_stats=grad_stats, tracers=tracer_series,
-                       dens_stats=dens_stats)
+                       dens_stats=dens_stats, modes=mode_series)
 
 
 def _run_result(prm, nf, nt, pos, vel, **fields):
@@ -863,7 +958,7 @@ def _batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra):
 
 
 def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=None, history=None, field=None, probe=None,
-               profiles=None, pairs=None, gradients=None, tracers=None, density=None):
+               profiles=None, pairs=None, gradients=None, tracers=None, density=None, modes=None):
     """The batch run behind run_batch, run_ensemble and run_sweep (`name`, for the refusals): check and default the inputs,
     open the batch with the launch keywords `launch`, enable what was asked for, advance output point by output point, build
     every member's RunResult.
@@ -889,6 +984,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                  that lost records raises RuntimeError
       density    (density_from, density_every, density_hist, density_bands): the density statistics of include/sphx.h section 2s
                  in the bins and with the default band of run(); every member gets its dens_stats
+      modes      (modes_every, (mx, ny), modes_from, modes_capacity): the mode amplitudes of include/sphx.h section 2u, drained
+                 at every output point; every member gets its modes, and one that lost records raises RuntimeError
     -> the members, the wall seconds, the grid policy, with average the raw sums (whole, mid) of all members, and with field the
     raw planes of all members."""
     prms = list(prms)
@@ -912,6 +1009,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
     pchunks = [[] for _ in range(M)]
     schunks = [[] for _ in range(M)]
     tchunks = [[] for _ in range(M)]
+    mchunks = [[] for _ in range(M)]
     t0 = time.perf_counter()
     with capi.Batch.from_parts(prms, parts_list, **launch) as b:
         if history:
@@ -939,6 +1037,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         if density:
             b.dens_stats_enable(n_bins=n_bins, every=density[1], t_from=float(density[0]), n_hist=density[2][0], hist_range=density[2][1],
                                 bands=_dens_bands(p0, density[3]))
+        if modes:
+            b.modes_enable(mx=modes[1][0], ny=modes[1][1], every=modes[0], capacity=modes[3], t_from=modes[2])
         t = 0.0
         st = None
         while t < p0.t_end - 1e-12:
@@ -974,6 +1074,11 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                     if p["n_dropped"]:
                         raise _tracers_lost(f"member {m}: ", p, t, tracing[2])
                     tchunks[m].append(p)
+            if modes:
+                for m, p in enumerate(b.modes(drain=True)):
+                    if p["n_dropped"]:
+                        raise _modes_lost(f"member {m}: ", p, t, modes[3])
+                    mchunks[m].append(p)
             if log:
                 log(f"output point: t={t:.6f}, steps={[s['step'] for s in st]}")
         wall = time.perf_counter() - t0
@@ -981,6 +1086,7 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
         sums = (b.flow_stats_sums(0), b.flow_stats_sums(1)) if average else None
         planes = b.field_map_sums() if field else None
         empty_series = b.profile_series_sums() if profiles and not schunks[0] else None
+        empty_modes = b.modes() if modes and not mchunks[0] else None
         pair_sums = b.pair_dist_sums() if pairs else None
         grad_sums = [b.grad_stats_sums(k) for k in range(1 + len(_grad_bands(p0, gradients[3])))] if gradients else None  # [band][member]
         dens_sums = [b.dens_stats_sums(k) for k in range(1 + len(_dens_bands(p0, density[3])))] if density else None  # [band][member]
@@ -1007,6 +1113,8 @@ def _run_batch(name, prms, parts_list, launch, log, snapshots=False, average=Non
                 extra.update(tracers=_concat_tracers(tracing[0], tchunks[m]))
             if density:
                 extra.update(dens_stats=_dens_stats_bands(prm, [band[m] for band in dens_sums]))
+            if modes:
+                extra.update(modes=_concat_modes(mchunks[m] or [empty_modes[m]]))
             members.append(_batch_member_result(b, m, prm, nf, nt, st, times, wall, policy, **extra))
     return members, wall, policy, sums, planes
 
@@ -1166,7 +1274,7 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
               profiles_capacity=4096, profiles_bands=None, pairs_from=None, pairs_every=1, pairs_bins=64, pairs_walls=False,
               pairs_bands=None, gradients_from=None, gradients_every=1, gradients_walls=False, gradients_bands=None, tracers=None,
               tracers_every=1, tracers_from=None, tracers_capacity=None, density_from=None, density_every=1, density_hist=(64, 0.05),
-              density_bands=None):
+              density_bands=None, modes_every=None, modes=(4, 8), modes_from=0.0, modes_capacity=4096):
     """A parameter sweep: M channels of one geometry that differ in mu, c_f, p0, gravity_g, transport_coeff, stepped as one
     batch (capi.Batch) with every member's step history recorded on the device, inside the step loop (include/sphx.h
     section 2f) as run(history_every=...) does for one channel.  The members advance output point by output point as in
@@ -1189,7 +1297,10 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
     run(): one id list for all members, each member gets its tracers and the table the columns D_y_nu, y_drift, u_dev_rms of
     tracer_figures(prm_m, tracers_m) -- the Lagrangian figures that respond to transport_coeff.  density_from: every member's density
     statistics as well (include/sphx.h section 2s), with the keywords of run(): each member gets its dens_stats and the table the
-    columns delta_rms, delta_max, p_spread of density_figures(prm_m, dens_stats_m).  A member that lost records to a full buffer raises RuntimeError, which names the member and the
+    columns delta_rms, delta_max, p_spread of density_figures(prm_m, dens_stats_m).  modes_every: every member's mode amplitudes
+    as well (include/sphx.h section 2u), with the keywords of run(): each member gets its modes and the table the columns
+    tau1_fit, tau3_fit, the decay times of the first two start-up modes of mode_figures(prm_m, modes_m) (NaN where modes[1]
+    does not reach the mode).  A member that lost records to a full buffer raises RuntimeError, which names the member and the
     capacity the output interval needed.  Returns a SweepResult."""
     prms = list(prms)
     members, wall, policy, _, planes = _run_batch(
@@ -1202,7 +1313,8 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
         pairs=_pairs_request(pairs_from, pairs_every, pairs_bins, pairs_walls, pairs_bands),
         gradients=_gradients_request(gradients_from, gradients_every, gradients_walls, gradients_bands),
         tracers=None if tracers is None else (tracers, tracers_every, tracers_from, tracers_capacity),
-        density=_density_request(density_from, density_every, density_hist, density_bands))
+        density=_density_request(density_from, density_every, density_hist, density_bands),
+        modes=None if modes_every is None else (modes_every, modes, modes_from, modes_capacity))
     table = sweep_table(prms, [r.history for r in members], [r.steps for r in members], history_from, settle_tol)
     if planes is not None:
         table.update(field_table(prms, [r.field_avg for r in members]))
@@ -1218,4 +1330,7 @@ def run_sweep(prms, *, history_every=1, history_capacity=65536, history_from=0.0
         table.update(_tracer_columns(prms, [r.tracers for r in members]))
     if density_from is not None:
         table.update(_dens_columns(prms, [r.dens_stats for r in members]))
+    if modes_every is not None:
+        taus = [mode_figures(p, r.modes)["tau_fit"] for p, r in zip(prms, members)]
+        table.update({f"tau{k}_fit": np.array([tf[k] if len(tf) > k else np.nan for tf in taus]) for k in (1, 3)})
     return SweepResult(members=members, table=table, wall_seconds=wall, grid_policy=policy)

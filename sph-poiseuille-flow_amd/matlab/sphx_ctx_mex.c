@@ -58,6 +58,13 @@
  *       sums: n_bins x 8, one column per field in the order of include/sphx.h section 2r (density statistics): count, sum delta,
  *       sum delta^2, sum dvol, sum wall, outliers, d_min, d_max; hist: n_hist x 1 counts of delta on [-hist_range, hist_range), as
  *       doubles (exact up to 2^53), below / above: the counts outside
+ *   sphx_ctx_mex('modes_enable', h, mx, ny, every, capacity, t_from)
+ *   sphx_ctx_mex('modes_disable', h)
+ *   sphx_ctx_mex('modes_sample', h)  % append one record of the current state now
+ *   [step, t, n, ux, uy, mx, ny, n_dropped] = sphx_ctx_mex('modes_read', h, drain)
+ *       step, t: n_records x 1; n, ux, uy: n_records x ((mx + 1) * (ny + 1) * 4), one row per recorded step, the sums of 1, u_x,
+ *       u_y times the bases cc, sc, cs, ss of mode (m, n) in the columns (m * (ny + 1) + n) * 4 + (1 .. 4) (mode amplitudes,
+ *       include/sphx.h section 2t: reshape(ux, n_records, 4, ny + 1, mx + 1)); drain ~= 0 empties the device buffer
  *   sphx_ctx_mex('destroy', h)
  * cfg is the struct SPH_Poiseuille.m builds at :175-196 (fields DL, DH, dp, h, rho0, mu, c_f, p0, inv_sigma0,
  * gravity_g, transport_coeff, t_end, sort_interval).  Never built with MATLAB in this repository (there is none in the
@@ -575,6 +582,56 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
         if (nlhs > 4) plhs[4] = mxCreateDoubleScalar((double)ns);
         if (nlhs > 5) plhs[5] = mxCreateDoubleScalar(t0);
         if (nlhs > 6) plhs[6] = mxCreateDoubleScalar(t1);
+    } else if (strcmp(cmd, "modes_enable") == 0) {
+        sphx_modes_config mc;
+        arity(cmd, nrhs, 7, nlhs, 0);
+        memset(&mc, 0, sizeof(mc));
+        mc.mx = (int32_t)mxGetScalar(prhs[2]);
+        mc.ny = (int32_t)mxGetScalar(prhs[3]);
+        mc.every = (int32_t)mxGetScalar(prhs[4]);
+        mc.capacity = (int32_t)mxGetScalar(prhs[5]);
+        mc.t_from = mxGetScalar(prhs[6]);
+        ok(sphx_ctx_modes_enable(handle(prhs[1]), &mc));
+    } else if (strcmp(cmd, "modes_disable") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_modes_disable(handle(prhs[1])));
+    } else if (strcmp(cmd, "modes_sample") == 0) {
+        arity(cmd, nrhs, 2, nlhs, 0);
+        ok(sphx_ctx_modes_sample(handle(prhs[1])));
+    } else if (strcmp(cmd, "modes_read") == 0) {
+        sphx_ctx *c;
+        int n = 0, got = 0, mx = 0, ny = 0, k, j, f, drain, rc;
+        int64_t dropped = 0;
+        size_t row;
+        double *times, *records;
+        arity(cmd, nrhs, 3, nlhs, 8);
+        c = handle(prhs[1]);
+        drain = mxGetScalar(prhs[2]) != 0.0;
+        ok(sphx_ctx_modes_read(c, 0, NULL, NULL, &mx, &ny, &n, NULL, 0));
+        row = (size_t)(mx + 1) * (size_t)(ny + 1) * SPHX_MODE_BASES;  /* the values of one field of one record */
+        times = (double *)mxMalloc((size_t)(n > 0 ? n : 1) * 2 * sizeof(double));
+        records = (double *)mxMalloc((size_t)(n > 0 ? n : 1) * row * SPHX_MODE_FIELDS * sizeof(double));
+        rc = sphx_ctx_modes_read(c, n, times, records, NULL, NULL, &got, &dropped, drain);  /* (nothing is stepped in between: got == n) */
+        if (rc != SPHX_OK) { mxFree(times); mxFree(records); ok(rc); }
+        for (f = 0; f < 2 && f < (nlhs > 0 ? nlhs : 1); ++f) {
+            plhs[f] = mxCreateDoubleMatrix((mwSize)got, 1, mxREAL);
+            for (k = 0; k < got; ++k) mxGetDoubles(plhs[f])[k] = times[(size_t)k * 2 + f];
+        }
+        for (f = 0; f < SPHX_MODE_FIELDS && 2 + f < nlhs; ++f) {  /* the library's rows are records; MATLAB stores columns */
+            double *out;
+            plhs[2 + f] = mxCreateDoubleMatrix((mwSize)got, (mwSize)row, mxREAL);
+            out = mxGetDoubles(plhs[2 + f]);
+            for (k = 0; k < got; ++k)
+                for (j = 0; j < (int)row; ++j) {
+                    const size_t mode = (size_t)j / SPHX_MODE_BASES, b = (size_t)j % SPHX_MODE_BASES;
+                    out[(size_t)j * got + k] = records[(size_t)k * row * SPHX_MODE_FIELDS + (mode * SPHX_MODE_FIELDS + f) * SPHX_MODE_BASES + b];
+                }
+        }
+        mxFree(times);
+        mxFree(records);
+        if (nlhs > 5) plhs[5] = mxCreateDoubleScalar((double)mx);
+        if (nlhs > 6) plhs[6] = mxCreateDoubleScalar((double)ny);
+        if (nlhs > 7) plhs[7] = mxCreateDoubleScalar((double)dropped);
     } else if (strcmp(cmd, "destroy") == 0) {
         arity(cmd, nrhs, 2, nlhs, 0);
         sphx_ctx_destroy(handle(prhs[1]));

@@ -16,6 +16,8 @@ in numpy; grad_stats_sums: one binned sample; grad_stats_profiles: the sums as p
 grad_stats_sums_part: the sample of one slab of a ring (the particles it owns, estimated from everything it holds).
 summation_density: the density of the device's density statistics (include/sphx.h section 2r) in numpy (fold=False: the open
 window of a slab); dens_stats_sums: one binned sample; dens_stats_sums_part: the sample of one slab of a ring.
+mode_sums: one sample of the device's mode amplitudes (include/sphx.h section 2t) in numpy, the definition; mode_scales: the
+fixed-point scales of a sample; mode_b_exact: the sine coefficients of the start-up of plane Poiseuille flow, mode by mode.
 """
 from __future__ import annotations
 
@@ -1004,3 +1006,54 @@ def pool_dens_stats(DH, p0, sums_list, hist_range=None):
     out = dens_stats_profiles(DH, p0, total)
     out.update({f: total[f] for f in DENS_FIELDS}, hist=total["hist"], below=total["below"], above=total["above"], n_members=len(sums_list))
     return out
+
+
+# the fields and bases of a mode (include/sphx.h section 2t), in the order of the last axes of a record
+MODE_FIELDS = ("n", "ux", "uy")
+MODE_BASES = ("cc", "sc", "cs", "ss")
+
+
+def mode_sums(pos, vel, DL, DH, mx, ny, acc=np.float64):
+    """One sample of the device's mode amplitudes (include/sphx.h section 2t) in numpy -- the definition: for the fluid rows
+    pos / vel [N, 2], thx = 2 pi x / DL and thy = pi y / DH, and for 0 <= m <= mx, 0 <= n <= ny
+      S[m, n, f, k] = sum_i q_i basis_k(i),  q = 1, u_x, u_y,  basis = cos(m thx) cos(n thy), sin cos, cos sin, sin sin.
+    -> dict of n, ux, uy as [mx + 1, ny + 1, 4] float64 arrays and abs_n, abs_ux, abs_uy, the sums of |q_i| a comparison is
+    relative to (the sums themselves cancel to ~0 for most modes).  acc: the float type the terms are formed and added in."""
+    pos, vel = np.asarray(pos, dtype=acc), np.asarray(vel, dtype=acc)
+    two, pi = acc(2.0), np.arccos(acc(-1.0))
+    thx = two * pi * pos[:, 0] / acc(DL)
+    thy = pi * pos[:, 1] / acc(DH)
+    m = np.arange(mx + 1, dtype=acc)[:, None]
+    n = np.arange(ny + 1, dtype=acc)[:, None]
+    bx = (np.cos(m * thx[None, :]), np.sin(m * thx[None, :]))  # [mx + 1, N] each
+    by = (np.cos(n * thy[None, :]), np.sin(n * thy[None, :]))  # [ny + 1, N]
+    q = dict(n=np.ones(len(pos), dtype=acc), ux=vel[:, 0], uy=vel[:, 1])
+    out = {}
+    for f in MODE_FIELDS:
+        S = np.zeros((mx + 1, ny + 1, len(MODE_BASES)), dtype=acc)
+        for k, (ix, iy) in enumerate(((0, 0), (1, 0), (0, 1), (1, 1))):
+            S[:, :, k] = (bx[ix] * q[f][None, :]) @ by[iy].T
+        out[f] = S.astype(np.float64)
+        out["abs_" + f] = float(np.abs(q[f]).sum())
+    return out
+
+
+def mode_scales(vmax, n):
+    """The fixed-point scales of one sample of the mode amplitudes, as the device picks them: with n <= 2^L particles and the
+    bound 2^e > max(2 vmax, 2^-60), the field n is summed in units of 2^-s0, ux and uy of 2^-s1: s0 = 62 - L, s1 = 62 - L - e.
+    -> dict(s0, s1, bound)."""
+    L = 0
+    while L < 31 and (1 << L) < n:
+        L += 1
+    x = 2.0 * float(vmax)
+    e = int(np.frexp(x if x > 2.0 ** -60 else 2.0 ** -60)[1])  # (a NaN vmax leaves the floor)
+    return dict(s0=62 - L, s1=62 - L - e, bound=float(np.ldexp(1.0, e)))
+
+
+def mode_b_exact(n, t, g, nu, DH):
+    """The sine coefficient b_n(t) of u_x of the start-up of plane Poiseuille flow from rest (poiseuille_startup, term by
+    term): b_n(inf) (1 - exp(-nu n^2 pi^2 t / DH^2)) with b_n(inf) = 32 U_max / (n pi)^3 = 4 g DH^2 / (nu pi^3 n^3) for odd n,
+    0 for even n.  Broadcasts over n and t."""
+    n, t = np.asarray(n, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    b_inf = np.where(n % 2 == 1, 4.0 * g * DH * DH / (nu * np.pi ** 3 * np.maximum(n, 1.0) ** 3), 0.0)
+    return b_inf * (1.0 - np.exp(-nu * (n * np.pi / DH) ** 2 * t))
