@@ -4,7 +4,7 @@
 // context runs as its "_b" form on a grid of (workgroups of one member) x M, member = blockIdx.y (Members,
 // sphx_kernels.hpp).  Each member is an sphx_ctx whose device arrays are its blocks of batch-wide allocations (BatchArena):
 // the cold paths -- creation, initial sort, downloads, monitors -- are the single-context code run on that member.  So is the
-// step: the batch enqueues a context's step slot (ctx_slot: launch_step, then the slot's flow statistics) on member 0, which
+// step: the batch enqueues a context's step slot (ctx_slot: launch_step, then the slot samplers that are on) on member 0, which
 // carries the member table, and the launch layer puts every kernel into its batch form (launch_forms).  The host
 // schedule (re-binning slots, graph phases) is the batch's; every member has its own clock, so a member that has reached
 // its target, used up its steps or stopped on the drift bound sits out the rest of the call.  When a call leaves members at
@@ -28,8 +28,8 @@ struct sphx_batch {
     int64_t epoch_slot = 0;           // sched.slot when the members' epochs were set
     int64_t n_realign = 0;
     std::vector<int64_t> pending;     // per member: step count the sphx_batch_enqueue_steps calls since the last sync aim for
-    // (flow statistics, sphx_batch_flow_stats_*, step history, sphx_batch_history_*, and field map, sphx_batch_field_map_*:
-    //  mem[0]->fstats / hist / fmap, for all M members)
+    // (the ten slot samplers, sphx_batch_flow_stats_* ... sphx_batch_modes_*: mem[0]'s sampler members, for all M members --
+    //  batch_owner, at the end of this file)
 
     ~sphx_batch()
     {
@@ -227,31 +227,13 @@ void batch_check_member(const sphx_batch *b, int m)
         throw Error(SPHX_ERR_ARG, "SPHX:Batch:member", "member " + std::to_string(m) + " out of range [0, " + std::to_string(b->M) + ")");
 }
 
-// the batch's flow statistics (member 0's, see sphx_ctx::fstats)
-FlowStats &batch_stats(sphx_batch *b, bool need_on)
+// The batch as the owner of its samplers (sphx_samplers.hpp): member 0's sampler members serve all M members on the batch's
+// schedule and stream.  An enable checks and goes on -- there is nothing to settle beyond the stream synchronisation of
+// sampler_off; a reset, a sample and a read settle what sphx_batch_enqueue_steps still owes first.
+Owner batch_owner(sphx_batch *b)
 {
     require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    FlowStats &f = b->mem[0]->fstats;
-    sampler_check(kStatsNames, false, f.on, need_on, "batch");
-    return f;
-}
-
-// the batch's step history (member 0's, see sphx_ctx::hist)
-History &batch_history(sphx_batch *b, bool need_on)
-{
-    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    History &h = b->mem[0]->hist;
-    sampler_check(kHistoryNames, false, h.on, need_on, "batch");
-    return h;
-}
-
-// the batch's field map (member 0's, see sphx_ctx::fmap)
-FieldMap &batch_field_map(sphx_batch *b, bool need_on)
-{
-    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    FieldMap &f = b->mem[0]->fmap;
-    sampler_check(kFieldNames, false, f.on, need_on, "batch");
-    return f;
+    return Owner{b->mem[0], b->sched, b->stream, b->M, "batch", b->mem[0]->nw > 0, [b] { batch_settle(b); }, false, {}};
 }
 
 // argument checks (no device): shared fields, refused modes, the kernel forms members of this size would run
@@ -477,13 +459,18 @@ SPHX_EXPORT int sphx_batch_graph_stats(sphx_batch *b, int64_t *slots_replayed, i
     SPHX_CATCH
 }
 
-// ---- flow statistics of every member (include/sphx.h section 2c) ----
+// ---- the slot samplers of every member: a context's (sphx_samplers.hpp) over batch_owner ----
+// One configuration for all members -- bins, bands, shapes, points, ids and the walls come from the shared geometry -- each
+// member sampled on its own clock.  Out of device memory on enable: the batch goes on without the sampler.  A "sample now" is
+// taken with every member at the batch's phase: the state sphx_batch_download would return.
+
+// ---- flow statistics (include/sphx.h section 2c) ----
 
 SPHX_EXPORT int sphx_batch_flow_stats_enable(sphx_batch *b, const sphx_flow_stats_config *cfg)
 {
     SPHX_TRY
-    // (bins and bands come from the shared geometry; out of device memory: the batch goes on without statistics)
-    stats_enable(batch_stats(b, false), b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::fstats, o.c->prm, cfg);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -491,8 +478,7 @@ SPHX_EXPORT int sphx_batch_flow_stats_enable(sphx_batch *b, const sphx_flow_stat
 SPHX_EXPORT int sphx_batch_flow_stats_disable(sphx_batch *b)
 {
     SPHX_TRY
-    FlowStats &f = batch_stats(b, false);
-    if (f.on) sampler_off(f, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::fstats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -500,9 +486,7 @@ SPHX_EXPORT int sphx_batch_flow_stats_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_flow_stats_reset(sphx_batch *b)
 {
     SPHX_TRY
-    FlowStats &f = batch_stats(b, true);
-    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, b->stream);
+    sampler_reset(batch_owner(b), &sphx_ctx::fstats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -510,9 +494,7 @@ SPHX_EXPORT int sphx_batch_flow_stats_reset(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_flow_stats_sample(sphx_batch *b)
 {
     SPHX_TRY
-    batch_stats(b, true);
-    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
-    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_flow_stats);
+    sampler_sample(batch_owner(b), &sphx_ctx::fstats, launch_flow_stats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -522,21 +504,18 @@ SPHX_EXPORT int sphx_batch_flow_stats_read(sphx_batch *b, int band, int capacity
                                            double *t_first, double *t_last)
 {
     SPHX_TRY
-    const FlowStats &f = batch_stats(b, true);
-    stats_read(f, b->stream, [b] { batch_settle(b); }, band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples,
-               t_first, t_last);
+    stats_read(batch_owner(b), band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
 
-// ---- step history of every member (include/sphx.h section 2f) ----
+// ---- step history (include/sphx.h section 2f) ----
 
 SPHX_EXPORT int sphx_batch_history_enable(sphx_batch *b, const sphx_history_config *cfg)
 {
     SPHX_TRY
-    // (out of device memory: the batch goes on without a history)
-    History &h = batch_history(b, false);
-    history_enable(h, cfg, b->M, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::hist, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -544,8 +523,7 @@ SPHX_EXPORT int sphx_batch_history_enable(sphx_batch *b, const sphx_history_conf
 SPHX_EXPORT int sphx_batch_history_disable(sphx_batch *b)
 {
     SPHX_TRY
-    History &h = batch_history(b, false);
-    if (h.on) sampler_off(h, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::hist);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -553,21 +531,19 @@ SPHX_EXPORT int sphx_batch_history_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_history_read(sphx_batch *b, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    History &h = batch_history(b, true);
-    batch_settle(b);  // (the records of everything enqueued)
-    h.read(b->stream, capacity, records, n_records, n_dropped, drain != 0);
+    const Owner o = batch_owner(b);
+    sampler_settled(o, &sphx_ctx::hist).read(o.st, capacity, records, n_records, n_dropped, drain != 0);
     return SPHX_OK;
     SPHX_CATCH
 }
 
-// ---- velocity-field map of every member (include/sphx.h section 2g) ----
+// ---- velocity-field map (include/sphx.h section 2g) ----
 
 SPHX_EXPORT int sphx_batch_field_map_enable(sphx_batch *b, const sphx_field_map_config *cfg)
 {
     SPHX_TRY
-    // (the shape comes from the shared geometry; out of device memory: the batch goes on without a map)
-    FieldMap &f = batch_field_map(b, false);
-    field_enable(f, b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::fmap, o.c->prm, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -575,8 +551,7 @@ SPHX_EXPORT int sphx_batch_field_map_enable(sphx_batch *b, const sphx_field_map_
 SPHX_EXPORT int sphx_batch_field_map_disable(sphx_batch *b)
 {
     SPHX_TRY
-    FieldMap &f = batch_field_map(b, false);
-    if (f.on) sampler_off(f, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::fmap);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -584,9 +559,7 @@ SPHX_EXPORT int sphx_batch_field_map_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_field_map_reset(sphx_batch *b)
 {
     SPHX_TRY
-    FieldMap &f = batch_field_map(b, true);
-    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, b->stream);
+    sampler_reset(batch_owner(b), &sphx_ctx::fmap);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -594,9 +567,7 @@ SPHX_EXPORT int sphx_batch_field_map_reset(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_field_map_sample(sphx_batch *b)
 {
     SPHX_TRY
-    batch_field_map(b, true);
-    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
-    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_field_map);
+    sampler_sample(batch_owner(b), &sphx_ctx::fmap, launch_field_map);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -606,34 +577,18 @@ SPHX_EXPORT int sphx_batch_field_map_read(sphx_batch *b, int capacity, int *nx, 
                                           double *t_last)
 {
     SPHX_TRY
-    const FieldMap &f = batch_field_map(b, true);
-    field_read(f, b->stream, [b] { batch_settle(b); }, capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples,
-               t_first, t_last);
+    field_read(batch_owner(b), capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
 
-// ---- point probes of every member (include/sphx.h section 2i) ----
-
-namespace {
-
-// the batch's probes (member 0's, see sphx_ctx::probes)
-Probes &batch_probes(sphx_batch *b, bool need_on)
-{
-    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    Probes &p = b->mem[0]->probes;
-    sampler_check(kProbeNames, false, p.on, need_on, "batch");
-    return p;
-}
-
-}  // namespace
+// ---- point probes (include/sphx.h section 2i) ----
 
 SPHX_EXPORT int sphx_batch_probes_enable(sphx_batch *b, const sphx_probes_config *cfg)
 {
     SPHX_TRY
-    // (one set of points for the shared geometry; out of device memory: the batch goes on without probes)
-    Probes &p = batch_probes(b, false);
-    probes_enable(p, b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::probes, o.c->prm, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -641,8 +596,7 @@ SPHX_EXPORT int sphx_batch_probes_enable(sphx_batch *b, const sphx_probes_config
 SPHX_EXPORT int sphx_batch_probes_disable(sphx_batch *b)
 {
     SPHX_TRY
-    Probes &p = batch_probes(b, false);
-    if (p.on) sampler_off(p, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::probes);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -650,9 +604,7 @@ SPHX_EXPORT int sphx_batch_probes_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_probes_sample(sphx_batch *b)
 {
     SPHX_TRY
-    batch_probes(b, true);
-    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
-    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_probes);
+    sampler_sample(batch_owner(b), &sphx_ctx::probes, launch_probes);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -661,35 +613,21 @@ SPHX_EXPORT int sphx_batch_probes_read(sphx_batch *b, int capacity, double *time
                                        int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    Probes &p = batch_probes(b, true);
-    batch_settle(b);  // (the records of everything enqueued)
-    p.read(b->stream, capacity, times, values, n_records, n_dropped, drain != 0);
+    const Owner o = batch_owner(b);
+    Probes &p = sampler_settled(o, &sphx_ctx::probes);  // (the records of everything enqueued)
+    p.read(o.st, capacity, times, values, n_records, n_dropped, drain != 0);
     if (n_points) *n_points = p.cfg.n_points;
     return SPHX_OK;
     SPHX_CATCH
 }
 
-// ---- particle tracers of every member (include/sphx.h section 2q) ----
-
-namespace {
-
-// the batch's tracers (member 0's, see sphx_ctx::tracers)
-Tracers &batch_tracers(sphx_batch *b, bool need_on)
-{
-    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    Tracers &t = b->mem[0]->tracers;
-    sampler_check(kTracerNames, false, t.on, need_on, "batch");
-    return t;
-}
-
-}  // namespace
+// ---- particle tracers (include/sphx.h section 2q) ----
 
 SPHX_EXPORT int sphx_batch_tracers_enable(sphx_batch *b, const sphx_tracers_config *cfg)
 {
     SPHX_TRY
-    // (one id list for the shared geometry; out of device memory: the batch goes on without tracers)
-    Tracers &t = batch_tracers(b, false);
-    tracers_enable(t, b->mem[0]->nf, b->mem[0]->nt, cfg, b->M, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::tracers, o.c->nf, o.c->nt, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -697,8 +635,7 @@ SPHX_EXPORT int sphx_batch_tracers_enable(sphx_batch *b, const sphx_tracers_conf
 SPHX_EXPORT int sphx_batch_tracers_disable(sphx_batch *b)
 {
     SPHX_TRY
-    Tracers &t = batch_tracers(b, false);
-    if (t.on) sampler_off(t, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::tracers);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -706,9 +643,7 @@ SPHX_EXPORT int sphx_batch_tracers_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_tracers_sample(sphx_batch *b)
 {
     SPHX_TRY
-    batch_tracers(b, true);
-    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
-    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_tracers);
+    sampler_sample(batch_owner(b), &sphx_ctx::tracers, launch_tracers);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -717,33 +652,18 @@ SPHX_EXPORT int sphx_batch_tracers_read(sphx_batch *b, int capacity, double *tim
                                         int *n_records, int64_t *n_dropped, int64_t *n_missing, int drain)
 {
     SPHX_TRY
-    Tracers &t = batch_tracers(b, true);
-    tracers_read(t, b->stream, [b] { batch_settle(b); }, capacity, times, values, ids, n_tracers, n_records, n_dropped, n_missing, drain);
+    tracers_read(batch_owner(b), capacity, times, values, ids, n_tracers, n_records, n_dropped, n_missing, drain);
     return SPHX_OK;
     SPHX_CATCH
 }
 
-// ---- profile series of every member (include/sphx.h section 2k) ----
-
-namespace {
-
-// the batch's profile series (member 0's, see sphx_ctx::pseries)
-ProfileSeries &batch_series(sphx_batch *b, bool need_on)
-{
-    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    ProfileSeries &p = b->mem[0]->pseries;
-    sampler_check(kSeriesNames, false, p.on, need_on, "batch");
-    return p;
-}
-
-}  // namespace
+// ---- profile series (include/sphx.h section 2k) ----
 
 SPHX_EXPORT int sphx_batch_profile_series_enable(sphx_batch *b, const sphx_profile_series_config *cfg)
 {
     SPHX_TRY
-    // (bins and bands come from the shared geometry; out of device memory: the batch goes on without a series)
-    ProfileSeries &p = batch_series(b, false);
-    series_enable(p, b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::pseries, o.c->prm, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -751,8 +671,7 @@ SPHX_EXPORT int sphx_batch_profile_series_enable(sphx_batch *b, const sphx_profi
 SPHX_EXPORT int sphx_batch_profile_series_disable(sphx_batch *b)
 {
     SPHX_TRY
-    ProfileSeries &p = batch_series(b, false);
-    if (p.on) sampler_off(p, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::pseries);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -760,9 +679,7 @@ SPHX_EXPORT int sphx_batch_profile_series_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_profile_series_sample(sphx_batch *b)
 {
     SPHX_TRY
-    batch_series(b, true);
-    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
-    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_profile_series);
+    sampler_sample(batch_owner(b), &sphx_ctx::pseries, launch_profile_series);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -771,33 +688,18 @@ SPHX_EXPORT int sphx_batch_profile_series_read(sphx_batch *b, int capacity, doub
                                                int *n_records, int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    ProfileSeries &p = batch_series(b, true);
-    series_read(p, b->stream, [b] { batch_settle(b); }, capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
+    series_read(batch_owner(b), capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
     return SPHX_OK;
     SPHX_CATCH
 }
 
-// ---- pair statistics of every member (include/sphx.h section 2m) ----
-
-namespace {
-
-// the batch's pair statistics (member 0's, see sphx_ctx::pairs)
-PairDist &batch_pairs(sphx_batch *b, bool need_on)
-{
-    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    PairDist &p = b->mem[0]->pairs;
-    sampler_check(kPairNames, false, p.on, need_on, "batch");
-    return p;
-}
-
-}  // namespace
+// ---- pair statistics (include/sphx.h section 2m) ----
 
 SPHX_EXPORT int sphx_batch_pair_dist_enable(sphx_batch *b, const sphx_pair_dist_config *cfg)
 {
     SPHX_TRY
-    // (h, DL, DH and the walls come from the shared geometry; out of device memory: the batch goes on without pair statistics)
-    PairDist &p = batch_pairs(b, false);
-    pair_dist_enable(p, b->mem[0]->prm, cfg, b->M, b->mem[0]->nw > 0, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::pairs, o.c->prm, cfg, o.has_walls);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -805,8 +707,7 @@ SPHX_EXPORT int sphx_batch_pair_dist_enable(sphx_batch *b, const sphx_pair_dist_
 SPHX_EXPORT int sphx_batch_pair_dist_disable(sphx_batch *b)
 {
     SPHX_TRY
-    PairDist &p = batch_pairs(b, false);
-    if (p.on) sampler_off(p, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::pairs);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -814,9 +715,7 @@ SPHX_EXPORT int sphx_batch_pair_dist_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_pair_dist_reset(sphx_batch *b)
 {
     SPHX_TRY
-    PairDist &p = batch_pairs(b, true);
-    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(p, b->stream);
+    sampler_reset(batch_owner(b), &sphx_ctx::pairs);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -824,9 +723,7 @@ SPHX_EXPORT int sphx_batch_pair_dist_reset(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_pair_dist_sample(sphx_batch *b)
 {
     SPHX_TRY
-    batch_pairs(b, true);
-    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
-    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_pair_dist);
+    sampler_sample(batch_owner(b), &sphx_ctx::pairs, launch_pair_dist);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -835,33 +732,18 @@ SPHX_EXPORT int sphx_batch_pair_dist_read(sphx_batch *b, int band, int capacity,
                                           double *r2_min, int64_t *n_samples, double *t_first, double *t_last)
 {
     SPHX_TRY
-    const PairDist &p = batch_pairs(b, true);
-    pair_dist_read(p, b->stream, [b] { batch_settle(b); }, band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
+    pair_dist_read(batch_owner(b), band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
 
-// ---- gradient statistics of every member (include/sphx.h section 2o) ----
-
-namespace {
-
-// the batch's gradient statistics (member 0's, see sphx_ctx::grads)
-GradStats &batch_grads(sphx_batch *b, bool need_on)
-{
-    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    GradStats &f = b->mem[0]->grads;
-    sampler_check(kGradNames, false, f.on, need_on, "batch");
-    return f;
-}
-
-}  // namespace
+// ---- gradient statistics (include/sphx.h section 2o) ----
 
 SPHX_EXPORT int sphx_batch_grad_stats_enable(sphx_batch *b, const sphx_grad_stats_config *cfg)
 {
     SPHX_TRY
-    // (bins, bands and the walls come from the shared geometry; out of device memory: the batch goes on without gradient statistics)
-    GradStats &f = batch_grads(b, false);
-    grad_stats_enable(f, b->mem[0]->prm, cfg, b->M, b->mem[0]->nw > 0, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::grads, o.c->prm, cfg, o.has_walls);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -869,8 +751,7 @@ SPHX_EXPORT int sphx_batch_grad_stats_enable(sphx_batch *b, const sphx_grad_stat
 SPHX_EXPORT int sphx_batch_grad_stats_disable(sphx_batch *b)
 {
     SPHX_TRY
-    GradStats &f = batch_grads(b, false);
-    if (f.on) sampler_off(f, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::grads);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -878,9 +759,7 @@ SPHX_EXPORT int sphx_batch_grad_stats_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_grad_stats_reset(sphx_batch *b)
 {
     SPHX_TRY
-    GradStats &f = batch_grads(b, true);
-    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, b->stream);
+    sampler_reset(batch_owner(b), &sphx_ctx::grads);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -888,9 +767,7 @@ SPHX_EXPORT int sphx_batch_grad_stats_reset(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_grad_stats_sample(sphx_batch *b)
 {
     SPHX_TRY
-    batch_grads(b, true);
-    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
-    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_grad_stats);
+    sampler_sample(batch_owner(b), &sphx_ctx::grads, launch_grad_stats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -899,33 +776,18 @@ SPHX_EXPORT int sphx_batch_grad_stats_read(sphx_batch *b, int band, int capacity
                                            double *t_first, double *t_last)
 {
     SPHX_TRY
-    const GradStats &f = batch_grads(b, true);
-    grad_stats_read(f, b->stream, [b] { batch_settle(b); }, band, capacity, n_bins, sums, n_samples, t_first, t_last);
+    grad_stats_read(batch_owner(b), band, capacity, n_bins, sums, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
 
-// ---- density statistics of every member (include/sphx.h section 2s) ----
-
-namespace {
-
-// the batch's density statistics (member 0's, see sphx_ctx::dens)
-DensStats &batch_dens(sphx_batch *b, bool need_on)
-{
-    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    DensStats &f = b->mem[0]->dens;
-    sampler_check(kDensNames, false, f.on, need_on, "batch");
-    return f;
-}
-
-}  // namespace
+// ---- density statistics (include/sphx.h section 2s) ----
 
 SPHX_EXPORT int sphx_batch_dens_stats_enable(sphx_batch *b, const sphx_dens_stats_config *cfg)
 {
     SPHX_TRY
-    // (bins, bands and the walls come from the shared geometry; out of device memory: the batch goes on without density statistics)
-    DensStats &f = batch_dens(b, false);
-    dens_stats_enable(f, b->mem[0]->prm, cfg, b->M, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::dens, o.c->prm, cfg);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -933,8 +795,7 @@ SPHX_EXPORT int sphx_batch_dens_stats_enable(sphx_batch *b, const sphx_dens_stat
 SPHX_EXPORT int sphx_batch_dens_stats_disable(sphx_batch *b)
 {
     SPHX_TRY
-    DensStats &f = batch_dens(b, false);
-    if (f.on) sampler_off(f, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::dens);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -942,9 +803,7 @@ SPHX_EXPORT int sphx_batch_dens_stats_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_dens_stats_reset(sphx_batch *b)
 {
     SPHX_TRY
-    DensStats &f = batch_dens(b, true);
-    batch_settle(b);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, b->stream);
+    sampler_reset(batch_owner(b), &sphx_ctx::dens);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -952,9 +811,7 @@ SPHX_EXPORT int sphx_batch_dens_stats_reset(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_dens_stats_sample(sphx_batch *b)
 {
     SPHX_TRY
-    batch_dens(b, true);
-    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
-    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_dens_stats);
+    sampler_sample(batch_owner(b), &sphx_ctx::dens, launch_dens_stats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -964,35 +821,21 @@ SPHX_EXPORT int sphx_batch_dens_stats_read(sphx_batch *b, int member, int band, 
                                            double *t_last)
 {
     SPHX_TRY
-    const DensStats &f = batch_dens(b, true);
+    const Owner o = batch_owner(b);
+    sampler_of(o, &sphx_ctx::dens, true);
     batch_check_member(b, member);
-    dens_stats_read(f, b->stream, [b] { batch_settle(b); }, member, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above,
-                    n_samples, t_first, t_last);
+    dens_stats_read(o, member, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
 
-// ---- mode amplitudes of every member (include/sphx.h section 2u) ----
-
-namespace {
-
-// the batch's mode amplitudes (member 0's, see sphx_ctx::modes)
-Modes &batch_modes(sphx_batch *b, bool need_on)
-{
-    require(b != nullptr, "SPHX:Batch:null", "batch must not be NULL");
-    Modes &p = b->mem[0]->modes;
-    sampler_check(kModesNames, false, p.on, need_on, "batch");
-    return p;
-}
-
-}  // namespace
+// ---- mode amplitudes (include/sphx.h section 2u) ----
 
 SPHX_EXPORT int sphx_batch_modes_enable(sphx_batch *b, const sphx_modes_config *cfg)
 {
     SPHX_TRY
-    // (out of device memory: the batch goes on without the sampler)
-    Modes &p = batch_modes(b, false);
-    modes_enable(p, cfg, b->M, b->sched, b->stream);
+    const Owner o = batch_owner(b);
+    sampler_enable(o, &sphx_ctx::modes, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1000,8 +843,7 @@ SPHX_EXPORT int sphx_batch_modes_enable(sphx_batch *b, const sphx_modes_config *
 SPHX_EXPORT int sphx_batch_modes_disable(sphx_batch *b)
 {
     SPHX_TRY
-    Modes &p = batch_modes(b, false);
-    if (p.on) sampler_off(p, b->sched, b->stream);
+    sampler_disable(batch_owner(b), &sphx_ctx::modes);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1009,9 +851,7 @@ SPHX_EXPORT int sphx_batch_modes_disable(sphx_batch *b)
 SPHX_EXPORT int sphx_batch_modes_sample(sphx_batch *b)
 {
     SPHX_TRY
-    batch_modes(b, true);
-    // (settled, every member is at the batch's phase: the state sphx_batch_download would return)
-    sample_now(b->mem[0], b->sched, [b] { batch_settle(b); }, launch_modes);
+    sampler_sample(batch_owner(b), &sphx_ctx::modes, launch_modes);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1020,8 +860,7 @@ SPHX_EXPORT int sphx_batch_modes_read(sphx_batch *b, int capacity, double *times
                                       int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    Modes &p = batch_modes(b, true);
-    modes_read(p, b->stream, [b] { batch_settle(b); }, capacity, times, records, mx, ny, n_records, n_dropped, drain);
+    modes_read(batch_owner(b), capacity, times, records, mx, ny, n_records, n_dropped, drain);
     return SPHX_OK;
     SPHX_CATCH
 }

@@ -1,73 +1,69 @@
-// sphx_samplers.hpp -- the slot samplers of a context ("Slot samplers"), part of the sphx_resident.hip
-// translation unit: flow statistics (include/sphx.h section 2a; of a batch: 2c, sphx_batch.hpp), the step history (2d; 2f)
-// the velocity-field map (2e; 2g), the point probes (2h; 2i), the profile series (2j; 2k), the pair statistics (2l; 2m,
-// sphx_pair_dist.hpp), the gradient statistics (2n; 2o, sphx_grad_stats.hpp), the particle tracers (2p; 2q, sphx_tracers.hpp) and
-// the density statistics (2r; 2s, sphx_dens_stats.hpp) -- all nine also of a slab of a ring (3a, at the end of this file) -- and
-// the mode amplitudes (2t; 2u, sphx_modes.hpp).  Their state is in sphx_sampler_state.hpp, their kernels in sphx_flow_stats.hpp,
-// sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp and sphx_profile_series.hpp.  What they share -- the context check, on / off, the view a slot leaves,
-// "sample now", the head read-out -- comes first, then each sampler's launch and entry points.
+// sphx_samplers.hpp -- the ten slot samplers ("Slot samplers"), part of the sphx_resident.hip translation
+// unit: flow statistics (include/sphx.h section 2a; of a batch: 2c), the step history (2d; 2f), the velocity-field map (2e; 2g),
+// the point probes (2h; 2i), the profile series (2j; 2k), the pair statistics (2l; 2m), the gradient statistics (2n; 2o), the
+// particle tracers (2p; 2q) and the density statistics (2r; 2s) -- all nine also of a slab of a ring (3a, at the end of this
+// file) -- and the mode amplitudes (2t; 2u).  Their state, shapes and names are in sphx_sampler_state.hpp, their kernels in
+// sphx_flow_stats.hpp, sphx_history.hpp, sphx_field_map.hpp, sphx_probes.hpp, sphx_profile_series.hpp, sphx_pair_dist.hpp,
+// sphx_grad_stats.hpp, sphx_tracers.hpp, sphx_dens_stats.hpp and sphx_modes.hpp, a batch's entry points in sphx_batch.hpp.
+// What the ten share comes first and is stated once: the owner of a sampler (a context, a batch or a slab: admission, settle,
+// what a change of setting costs), the lifecycle over it (enable, disable, reset, sample), the view a slot leaves, the head
+// read-out, the record-ring read of the five samplers that keep records, and the bins-and-bands check of the five that bin.
+// Then each sampler's launch, and per sampler what is its own: check, alloc, read and the entry points.
 #pragma once
 
 namespace {
 
 // ---- shared ----
 
-// identifier stem (SPHX:<stem>:slab / :disabled / :config) and message texts of a sampler
-struct SamplerNames {
-    const char *stem;
-    const char *no_slab;
-    const char *off;        // ... "context" or "batch"
-    const char *no_memory;  // enable, out of device memory: SPHX_ERR_ARG / SPHX:<stem>:config with this text in front of the
-                            // allocator's; nullptr: the allocator's error goes out as it is
-};
-constexpr SamplerNames kStatsNames{"Stats", "flow statistics are not available on slab contexts",
-                                   "flow statistics are not enabled on this ", nullptr};
-constexpr SamplerNames kHistoryNames{"History", "the step history is not available on slab contexts",
-                                     "the step history is not enabled on this ", "the record buffer could not be set up: "};
-constexpr SamplerNames kFieldNames{"Field", "field maps are not available on slab contexts", "the field map is not enabled on this ",
-                                   "the map could not be set up: "};
-constexpr SamplerNames kProbeNames{"Probe", "point probes are not available on slab contexts", "point probes are not enabled on this ",
-                                   "the record buffer could not be set up: "};
-constexpr SamplerNames kSeriesNames{"ProfileSeries", "the profile series of a slab is sphx_slab_pseries_* (include/sphx.h section 3a)",
-                                    "the profile series is not enabled on this ", "the record buffer could not be set up: "};
-
-constexpr SamplerNames kPairNames{"PairDist", "the pair statistics of a slab are sphx_slab_pairs_* (include/sphx.h section 3a)",
-                                  "pair statistics are not enabled on this ",
-                                  "the sums could not be set up: "};
-constexpr SamplerNames kGradNames{"GradStats", "the gradient statistics of a slab are sphx_slab_gstats_* (include/sphx.h section 3a)",
-                                  "gradient statistics are not enabled on this ", "the sums could not be set up: "};
-constexpr SamplerNames kTracerNames{"Tracers", "the tracers of a slab are sphx_slab_tracers_* (include/sphx.h section 3a)",
-                                    "particle tracers are not enabled on this ", "the record buffer could not be set up: "};
-constexpr SamplerNames kDensNames{"DensStats", "the density statistics of a slab are sphx_slab_dstats_* (include/sphx.h section 3a)",
-                                  "density statistics are not enabled on this ", "the sums could not be set up: "};
-constexpr SamplerNames kModesNames{"Modes", "mode amplitudes are not available on slab contexts", "mode amplitudes are not enabled on this ",
-                                   "the record buffer could not be set up: "};
-
 std::string sampler_id(const SamplerNames &n, const char *leaf) { return std::string("SPHX:") + n.stem + ":" + leaf; }
 
-// no sampler on slabs; need_on: the call needs it enabled on this `where` ("context" / "batch")
-void sampler_check(const SamplerNames &n, bool is_slab, bool on, bool need_on, const char *where)
-{
-    if (is_slab) throw Error(SPHX_ERR_ARG, sampler_id(n, "slab"), n.no_slab);
-    if (need_on && !on) throw Error(SPHX_ERR_STATE, sampler_id(n, "disabled"), std::string(n.off) + where);
-}
+// How an entry point reaches a sampler: the owner of the call.  ctx_owner(c), batch_owner(b) (sphx_batch.hpp) and slab_owner(c)
+// make one and raise the owner's own refusals while they do (SPHX:Ctx:null; SPHX:Batch:null; SPHX:Slab:ctx, SPHX:Slab:protocol).
+struct Owner {
+    sphx_ctx *c;                     // whose sampler members are used (a batch: member 0, which serves every member)
+    Schedule &sched;                 // whose replayed graphs carry the samplers' launches
+    hipStream_t st;
+    int M;                           // channels sampled
+    const char *where;               // "context" / "batch" / "slab": the last word of SPHX:<stem>:disabled
+    bool has_walls;                  // the channel (a slab: this slab) holds wall particles
+    std::function<void()> settle;    // what is enqueued, and the steps still owed, have run: the state a download returns
+    bool context;                    // a context's entry points refuse a slab context (SPHX:<stem>:slab), and a change of
+                                     // setting settles first, whatever comes of it, as a read or a reset does: the steps a
+                                     // batch of sphx_ctx_enqueue_steps still owes were asked for under the old setting
+    std::function<void()> changing;  // a slab: in front of on / off (slab_samplers_changed); else empty
+};
 
-// the checked sampler `which` of context c
-template <typename S>
-S &sampler_of(sphx_ctx *c, S sphx_ctx::*which, const SamplerNames &n, bool need_on)
+Owner ctx_owner(sphx_ctx *c)
 {
     require(c != nullptr, "SPHX:Ctx:null", "ctx must not be NULL");
-    sampler_check(n, c->is_slab, (c->*which).on, need_on, "context");
-    return c->*which;
+    return Owner{c, c->sched, c->stream, 1, "context", c->nw > 0, [c] { settle_owed(c); }, true, {}};
 }
 
-// ... for a change of its setting (enable, disable): what is enqueued lands first, the steps a batch of
-// sphx_ctx_enqueue_steps still owes included, as for a read or a reset -- they were asked for under the old setting
+// sampler `which` of owner o; need_on: the call needs it enabled (SPHX:<stem>:disabled)
 template <typename S>
-S &sampler_to_change(sphx_ctx *c, S sphx_ctx::*which, const SamplerNames &n)
+S &sampler_of(const Owner &o, S sphx_ctx::*which, bool need_on)
 {
-    S &x = sampler_of(c, which, n, false);
-    settle_owed(c);
+    S &x = o.c->*which;
+    if (o.context && o.c->is_slab) throw Error(SPHX_ERR_ARG, sampler_id(S::names, "slab"), S::names.no_slab);
+    if (need_on && !x.on) throw Error(SPHX_ERR_STATE, sampler_id(S::names, "disabled"), std::string(S::names.off) + o.where);
+    return x;
+}
+
+// ... for a change of its setting (enable, disable)
+template <typename S>
+S &sampler_to_change(const Owner &o, S sphx_ctx::*which)
+{
+    S &x = sampler_of(o, which, false);
+    if (o.context) o.settle();
+    return x;
+}
+
+// ... enabled, and everything enqueued has landed: for a reset, a sample or a read without argument checks of its own
+template <typename S>
+S &sampler_settled(const Owner &o, S sphx_ctx::*which)
+{
+    S &x = sampler_of(o, which, true);
+    o.settle();
     return x;
 }
 
@@ -89,23 +85,54 @@ void sampler_zero(S &x, hipStream_t st)
     SPHX_HIP(hipStreamSynchronize(st));
 }
 
-// On, with what alloc() sets up, zeroed.  The caller has made every check of the configuration: a refused enable leaves a
-// running sampler untouched.  Out of device memory the sampler stays off with nothing allocated; flow statistics hand the
-// allocator's error on as it is, history and field map report theirs as a configuration error (SamplerNames::no_memory).
-template <typename S, typename Alloc>
-void sampler_on(S &x, const SamplerNames &n, Schedule &s, hipStream_t st, Alloc &&alloc)
+// The enable tail: on, with the CHECKED shape and what alloc() sets up from it, zeroed.  The caller has made every check of the
+// configuration: a refused enable leaves a running sampler -- and a slab's prepared step graph -- untouched.  Out of device
+// memory the sampler stays off with nothing allocated; flow statistics hand the allocator's error on as it is, the others
+// report theirs as a configuration error (SamplerNames::no_memory).
+template <typename S, typename Shape>
+void sampler_on(const Owner &o, S sphx_ctx::*which, const Shape &checked)
 {
-    sampler_off(x, s, st);
+    S &x = o.c->*which;
+    if (o.changing) o.changing();
+    sampler_off(x, o.sched, o.st);
     try {
-        alloc();
-        sampler_zero(x, st);
+        x.alloc(checked, o.M, o.st);
+        sampler_zero(x, o.st);
     } catch (const Error &e) {
         x.release();
         (void)hipGetLastError();
-        if (!n.no_memory) throw;
-        throw Error(SPHX_ERR_ARG, sampler_id(n, "config"), std::string(n.no_memory) + e.what());
+        if (!S::names.no_memory) throw;
+        throw Error(SPHX_ERR_ARG, sampler_id(S::names, "config"), std::string(S::names.no_memory) + e.what());
     }
     x.on = true;
+}
+
+// Enable with the configuration check(args...) accepts: every check first, so a refusal changes nothing.  (A batch: bins,
+// bands, shapes, points, ids and the walls come from the shared geometry; out of device memory it goes on without the sampler.)
+template <typename S, typename... Args>
+void sampler_enable(const Owner &o, S sphx_ctx::*which, Args &&...args)
+{
+    sampler_to_change(o, which);
+    S checked;
+    checked.check(args...);
+    sampler_on(o, which, checked);
+}
+
+// off, where it is on (a slab whose sampler is off: nothing is touched)
+template <typename S>
+void sampler_disable(const Owner &o, S sphx_ctx::*which)
+{
+    S &x = sampler_to_change(o, which);
+    if (!x.on) return;
+    if (o.changing) o.changing();
+    sampler_off(x, o.sched, o.st);
+}
+
+// (the samples of everything enqueued land before the sums are cleared)
+template <typename S>
+void sampler_reset(const Owner &o, S sphx_ctx::*which)
+{
+    sampler_zero(sampler_settled(o, which), o.st);
 }
 
 // The state step slot q, which ran on layout l, leaves: S[1-q] on every schedule (a re-binning step reorders into S[1-q]
@@ -116,13 +143,13 @@ FluidSet slot_end_view(sphx_ctx *c, int q, int l, bool rebuild)
     return c->dyn ? c->view(1 - q, 0) : c->view(1 - q, rebuild ? 1 - l : l);
 }
 
-// a sample of the state now: settle() what is owed -- the state a download would return -- then launch(c, q, state, every)
-// with every = 0 on the current view of schedule s
-template <typename Settle, typename Launch>
-void sample_now(sphx_ctx *c, const Schedule &s, Settle &&settle, Launch &&launch)
+// A sample of the state now: settled -- the state a download would return; of a batch: every member at the batch's phase --
+// then launch(c, q, state, every) with every = 0 on the current view of the owner's schedule
+template <typename S, typename Launch>
+void sampler_sample(const Owner &o, S sphx_ctx::*which, Launch &&launch)
 {
-    settle();
-    launch(c, 0, c->view(s.cur, s.lay), 0);
+    sampler_settled(o, which);
+    launch(o.c, 0, o.c->view(o.sched.cur, o.sched.lay), 0);
     SPHX_HIP(hipGetLastError());
 }
 
@@ -136,6 +163,107 @@ void read_head(const Head &h, int64_t *n_samples, double *t_first, double *t_las
     if (t_last) *t_last = h.n_samples ? h.t_last : nan;
 }
 
+// SPHX:<stem>:range: member m's sticky flag is up
+[[noreturn]] void throw_range(const SamplerNames &n, int M, int m)
+{
+    throw Error(SPHX_ERR_STATE, sampler_id(n, "range"), (M > 1 ? "member " + std::to_string(m) + ": " : std::string()) +
+                                                            "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
+}
+
+// the sticky range flag of a head that has one
+template <typename Head> auto head_range(const Head &h, int) -> decltype(h.range != 0) { return h.range != 0; }
+template <typename Head> bool head_range(const Head &, long) { return false; }
+
+// One block of a record ring: member m's rows of `width` doubles at dev + m * cfg.capacity * width, wanted -- where out is
+// given -- at out + m * capacity * width of a [members][capacity][width] array
+struct RingBlock {
+    double *out = nullptr;
+    const double *dev = nullptr;
+    size_t width = 0;
+};
+
+enum class RingStage { Rows, Counts, Drain };  // where ring_read calls its hook
+
+// The read of record ring x (History, Probes, Tracers, ProfileSeries, Modes) of M = x.members members: every member's counts
+// (n_records[m], n_dropped[m], where given) and its filled rows 0 .. n_records[m] of the blocks a and b, each where its out is
+// given; drain empties every ring.  SPHX:<stem>:state when a count is out of range, SPHX:<stem>:range when a member's sticky
+// flag is up (the heads that have one), SPHX:<stem>:capacity when an array is asked for -- a's, b's or, `more`, one of the
+// hook's -- and capacity is below the largest count `most`: nothing is copied or drained then.  hook(stage, heads, most) is for
+// what is a sampler's own: Rows -- behind the capacity check, in front of the row copies; Counts -- with the counts; Drain --
+// behind the zeroing of a draining read, in front of its synchronisation.
+template <typename S, typename Head, typename Hook>
+void ring_read(S &x, const DevBuf<Head> &head, hipStream_t st, int capacity, RingBlock a, RingBlock b, bool more, int *n_records,
+               int64_t *n_dropped, bool drain, Hook &&hook)
+{
+    const int M = x.members;
+    std::vector<Head> h(M);
+    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(Head) * M, hipMemcpyDeviceToHost, st));
+    SPHX_HIP(hipStreamSynchronize(st));
+    long long most = 0;
+    for (int m = 0; m < M; ++m) {
+        const long long n = h[m].n_records;
+        if (n < 0 || n > (long long)x.cfg.capacity)
+            throw Error(SPHX_ERR_STATE, sampler_id(S::names, "state"), "internal: record count out of range");
+        if (head_range(h[m], 0)) throw_range(S::names, M, m);
+        most = std::max(most, n);
+    }
+    const bool rows = a.out || b.out;
+    if ((rows || more) && (long long)capacity < most)
+        throw Error(SPHX_ERR_ARG, sampler_id(S::names, "capacity"), "capacity is smaller than the number of records");
+    hook(RingStage::Rows, h, most);
+    if (rows && most > 0) {
+        for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
+            const size_t n = (size_t)h[m].n_records;
+            if (n == 0) continue;
+            for (const RingBlock &k : {a, b})
+                if (k.out)
+                    SPHX_HIP(hipMemcpyAsync(k.out + (size_t)m * capacity * k.width, k.dev + (size_t)m * x.cfg.capacity * k.width,
+                                            n * k.width * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+    for (int m = 0; m < M; ++m) {
+        if (n_records) n_records[m] = (int)h[m].n_records;
+        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
+    }
+    hook(RingStage::Counts, h, most);
+    if (drain) {
+        x.zero(st);
+        hook(RingStage::Drain, h, most);
+        SPHX_HIP(hipStreamSynchronize(st));
+    }
+}
+
+// ... of a sampler with nothing of its own
+template <typename S, typename Head>
+void ring_read(S &x, const DevBuf<Head> &head, hipStream_t st, int capacity, RingBlock a, RingBlock b, int *n_records, int64_t *n_dropped,
+               bool drain)
+{
+    ring_read(x, head, st, capacity, a, b, false, n_records, n_dropped, drain, [](RingStage, const std::vector<Head> &, long long) {});
+}
+
+// The bins and bands in force of a sampler that bins over y and over x-bands, and the unused bands of cfg -- the shape's copy --
+// zeroed: n_bands 0 .. 2, centres and half-widths finite; n_bins as given (its range is the caller's check) or, 0, the
+// reference's profile bins.  SPHX:<stem>:config (id) errors; the LDS limit that follows is the sampler's own.
+template <typename Cfg>
+void bins_and_bands(const char *id, const sphx_params &prm, Cfg &cfg, int &n_bins, int &n_bands)
+{
+    require(cfg.n_bands >= 0 && cfg.n_bands <= 2, id, "n_bands must be 0, 1 or 2");
+    for (int b = 0; b < cfg.n_bands; ++b)
+        require(std::isfinite(cfg.band_x[b]) && std::isfinite(cfg.band_hw[b]) && cfg.band_hw[b] >= 0.0, id,
+                "band centres must be finite and half-widths finite and >= 0");
+    for (int b = cfg.n_bands; b < 2; ++b) { cfg.band_x[b] = 0.0; cfg.band_hw[b] = 0.0; }
+    n_bins = cfg.n_bins > 0 ? cfg.n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
+    n_bands = cfg.n_bands + 1;
+}
+
+// the bands of cfg into the kernel arguments a
+template <typename Args, typename Cfg>
+void fill_bands(Args &a, const Cfg &cfg)
+{
+    for (int b = 0; b < 2; ++b) { a.band_x[b] = cfg.band_x[b]; a.band_hw[b] = cfg.band_hw[b]; }
+}
+
 // ---- launches: every >= 1 = the in-loop sample closing step slot q, 0 = a sample of the state now ----
 
 // the arguments of a flow-statistics launch on state s into c->fstats
@@ -147,7 +275,7 @@ FlowStatsArgs flow_stats_args(sphx_ctx *c, const FluidSet &s, int every)
     a.isum = f.isum.get(); a.dsum = f.dsum.get(); a.head = f.head.get();
     a.DH = c->prm.DH; a.bin_w = c->prm.DH / f.n_bins; a.DL = c->prm.DL;
     a.t_from = f.cfg.t_from;
-    for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
+    fill_bands(a, f.cfg);
     a.n_bins = f.n_bins; a.n_bands = f.n_bands;
     a.every = every;
     return a;
@@ -264,7 +392,7 @@ ProfileSeriesArgs profile_series_args(sphx_ctx *c, const FluidSet &s, int every)
     a.bin.isum = p.isum.get();
     a.bin.DH = c->prm.DH; a.bin.bin_w = c->prm.DH / p.n_bins; a.bin.DL = c->prm.DL;
     a.bin.t_from = p.cfg.t_from;
-    for (int b = 0; b < 2; ++b) { a.bin.band_x[b] = p.cfg.band_x[b]; a.bin.band_hw[b] = p.cfg.band_hw[b]; }
+    fill_bands(a.bin, p.cfg);
     a.bin.n_bins = p.n_bins; a.bin.n_bands = p.n_bands;
     a.bin.every = every;
     a.times = p.times.get(); a.records = p.records.get(); a.head = p.head.get();
@@ -288,7 +416,7 @@ PairDistArgs pair_dist_args(sphx_ctx *c, int every)
     a.bin_w = p.r_max / p.n_bins; a.rmax2 = p.r_max * p.r_max;
     a.y_lo = p.cfg.y_margin; a.y_hi = c->prm.DH - p.cfg.y_margin;
     a.DL = c->prm.DL; a.t_from = p.cfg.t_from;
-    for (int b = 0; b < 2; ++b) { a.band_x[b] = p.cfg.band_x[b]; a.band_hw[b] = p.cfg.band_hw[b]; }
+    fill_bands(a, p.cfg);
     a.n_bins = p.n_bins; a.n_bands = p.n_bands; a.kinds = p.kinds;
     a.block = (int)p.block();
     a.every = every;
@@ -317,7 +445,7 @@ GradStatsArgs grad_stats_args(sphx_ctx *c, int every)
     a.isum = f.isum.get(); a.dsum = f.dsum.get(); a.head = f.head.get();
     a.DH = c->prm.DH; a.bin_w = c->prm.DH / f.n_bins; a.DL = c->prm.DL;
     a.t_from = f.cfg.t_from; a.det_min = f.cfg.det_min;
-    for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
+    fill_bands(a, f.cfg);
     a.n_bins = f.n_bins; a.n_bands = f.n_bands;
     a.block = (int)f.block();
     a.with_walls = f.walls ? 1 : 0;
@@ -373,7 +501,7 @@ DensStatsArgs dens_stats_args(sphx_ctx *c, int every)
     a.t_from = f.cfg.t_from;
     a.delta_bound = f.cfg.delta_bound; a.hist_range = f.cfg.hist_range;
     a.hist_scale = (double)f.cfg.n_hist / (2.0 * f.cfg.hist_range);
-    for (int b = 0; b < 2; ++b) { a.band_x[b] = f.cfg.band_x[b]; a.band_hw[b] = f.cfg.band_hw[b]; }
+    fill_bands(a, f.cfg);
     a.n_bins = f.n_bins; a.n_bands = f.n_bands; a.n_hist = f.cfg.n_hist;
     a.block = (int)f.block(); a.kblock = (int)f.kblock();
     a.e = f.e;
@@ -445,31 +573,22 @@ void sphx::launch_slot_samplers(sphx_ctx *c, int q, int l, bool rebuild)
 // ---- flow statistics ----
 
 // the checked configuration cfg of channels with parameters prm (cfg, n_bins, n_bands); SPHX:Stats:config errors
-void FlowStats::configure(const sphx_params &prm, const sphx_flow_stats_config *cfg)
+void FlowStatsShape::check(const sphx_params &prm, const sphx_flow_stats_config *cfg)
 {
     require(cfg != nullptr, "SPHX:Stats:config", "config must not be NULL");
     require(cfg->n_bins >= 0, "SPHX:Stats:config", "n_bins must be >= 0 (0 = the reference's profile bins)");
     require(cfg->every >= 1, "SPHX:Stats:config", "every must be >= 1");
     require(!std::isnan(cfg->t_from), "SPHX:Stats:config", "t_from must not be NaN");
-    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, "SPHX:Stats:config", "n_bands must be 0, 1 or 2");
-    for (int b = 0; b < cfg->n_bands; ++b)
-        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, "SPHX:Stats:config",
-                "band centres must be finite and half-widths finite and >= 0");
-    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
-    require((int64_t)bins * (cfg->n_bands + 1) <= kStatsMaxBins, "SPHX:Stats:config",
-            "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
     this->cfg = *cfg;
-    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
-    n_bins = bins;
-    n_bands = cfg->n_bands + 1;
+    bins_and_bands("SPHX:Stats:config", prm, this->cfg, n_bins, n_bands);
+    require((int64_t)n_bins * n_bands <= kStatsMaxBins, "SPHX:Stats:config",
+            "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
 }
 
-// the checked configuration, and sums and heads for M members
-void FlowStats::alloc(const FlowStats &checked, int M)
+// the checked shape, and sums and heads for M members
+void FlowStats::alloc(const FlowStatsShape &checked, int M, hipStream_t)
 {
-    cfg = checked.cfg;
-    n_bins = checked.n_bins;
-    n_bands = checked.n_bands;
+    static_cast<FlowStatsShape &>(*this) = checked;
     members = M;
     isum.alloc(block() * M);
     dsum.alloc(block() * M);
@@ -490,9 +609,7 @@ void FlowStats::read(hipStream_t st, int band, int stride, bool sums, double *co
     SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(FlowStatsHead) * M, hipMemcpyDeviceToHost, st));
     SPHX_HIP(hipStreamSynchronize(st));
     for (int m = 0; m < M; ++m)
-        if (h[m].range)
-            throw Error(SPHX_ERR_STATE, "SPHX:Stats:range", (M > 1 ? "member " + std::to_string(m) + ": " : std::string()) +
-                                                           "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
+        if (h[m].range) throw_range(names, M, m);
     for (int j = 0; j < kStatsFields; ++j)
         if (out[j])
             for (int m = 0; m < M; ++m)
@@ -503,26 +620,18 @@ void FlowStats::read(hipStream_t st, int band, int stride, bool sums, double *co
 
 namespace {
 
-// enable for M members on schedule s: every check of cfg first
-void stats_enable(FlowStats &f, const sphx_params &prm, const sphx_flow_stats_config *cfg, int M, Schedule &s, hipStream_t st)
+// the argument checks of a read, then what is enqueued lands, and the read
+void stats_read(const Owner &o, int band, int capacity, int *n_bins, double *count, double *sum_ux, double *sum_ux2, double *sum_uy,
+                double *sum_uy2, int64_t *n_samples, double *t_first, double *t_last)
 {
-    FlowStats checked;
-    checked.configure(prm, cfg);
-    sampler_on(f, kStatsNames, s, st, [&] { f.alloc(checked, M); });
-}
-
-// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
-template <typename Settle>
-void stats_read(const FlowStats &f, hipStream_t st, Settle &&settle, int band, int capacity, int *n_bins, double *count, double *sum_ux,
-                double *sum_ux2, double *sum_uy, double *sum_uy2, int64_t *n_samples, double *t_first, double *t_last)
-{
+    const FlowStats &f = sampler_of(o, &sphx_ctx::fstats, true);
     require(band >= 0 && band < f.n_bands, "SPHX:Stats:band", "band must be 0 (whole channel) .. n_bands");
     double *const out[kStatsFields] = {count, sum_ux, sum_ux2, sum_uy, sum_uy2};
     bool any = false;
-    for (double *o : out) any = any || o != nullptr;
+    for (double *p : out) any = any || p != nullptr;
     require(!any || capacity >= f.n_bins, "SPHX:Stats:capacity", "capacity is smaller than the number of bins");
-    settle();
-    f.read(st, band, capacity, any, out, n_samples, t_first, t_last);
+    o.settle();
+    f.read(o.st, band, capacity, any, out, n_samples, t_first, t_last);
     if (n_bins) *n_bins = f.n_bins;
 }
 
@@ -531,8 +640,8 @@ void stats_read(const FlowStats &f, hipStream_t st, Settle &&settle, int band, i
 SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_config *cfg)
 {
     SPHX_TRY
-    FlowStats &f = sampler_to_change(c, &sphx_ctx::fstats, kStatsNames);
-    stats_enable(f, c->prm, cfg, 1, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::fstats, o.c->prm, cfg);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -540,8 +649,7 @@ SPHX_EXPORT int sphx_ctx_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_co
 SPHX_EXPORT int sphx_ctx_flow_stats_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    FlowStats &f = sampler_to_change(c, &sphx_ctx::fstats, kStatsNames);
-    if (f.on) sampler_off(f, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::fstats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -549,9 +657,7 @@ SPHX_EXPORT int sphx_ctx_flow_stats_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_flow_stats_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    FlowStats &f = sampler_of(c, &sphx_ctx::fstats, kStatsNames, true);
-    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, c->stream);
+    sampler_reset(ctx_owner(c), &sphx_ctx::fstats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -559,8 +665,7 @@ SPHX_EXPORT int sphx_ctx_flow_stats_reset(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_flow_stats_sample(sphx_ctx *c)
 {
     SPHX_TRY
-    sampler_of(c, &sphx_ctx::fstats, kStatsNames, true);
-    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_flow_stats);
+    sampler_sample(ctx_owner(c), &sphx_ctx::fstats, launch_flow_stats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -570,9 +675,7 @@ SPHX_EXPORT int sphx_ctx_flow_stats_read(sphx_ctx *c, int band, int capacity, in
                                          double *t_first, double *t_last)
 {
     SPHX_TRY
-    const FlowStats &f = sampler_of(c, &sphx_ctx::fstats, kStatsNames, true);
-    stats_read(f, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples,
-               t_first, t_last);
+    stats_read(ctx_owner(c), band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -580,7 +683,7 @@ SPHX_EXPORT int sphx_ctx_flow_stats_read(sphx_ctx *c, int band, int capacity, in
 // ---- step history ----
 
 // every check of a configuration for M channels; SPHX:History:config errors
-void History::check(const sphx_history_config *cfg, int M)
+void HistoryShape::check(const sphx_history_config *cfg, int M)
 {
     require(cfg != nullptr, "SPHX:History:config", "config must not be NULL");
     require(cfg->every >= 1, "SPHX:History:config", "every must be >= 1");
@@ -588,67 +691,30 @@ void History::check(const sphx_history_config *cfg, int M)
     require((int64_t)M * cfg->capacity <= kHistoryMaxTotal, "SPHX:History:config",
             "n_members * capacity must not exceed 1 << 24 records");
     require(std::isfinite(cfg->t_from), "SPHX:History:config", "t_from must be finite");
+    this->cfg = *cfg;
 }
 
-// the checked configuration, and records, partials and heads for M members
-void History::alloc(const sphx_history_config &checked, int M)
+// the checked shape, and records, partials and heads for M members
+void History::alloc(const HistoryShape &checked, int M, hipStream_t)
 {
-    records.alloc((size_t)M * checked.capacity * kHistoryFields);
+    static_cast<HistoryShape &>(*this) = checked;
+    members = M;
+    records.alloc((size_t)M * cfg.capacity * kHistoryFields);
     part.alloc((size_t)M * kHistoryMaxBlocks * kHistorySums);
     head.alloc(M);
-    cfg = checked;
-    members = M;
 }
 
-// Every member's counts (n_records[m], n_dropped[m], where given) and, with `records`, its filled rows into
-// records[m][0 .. n_records[m])[kHistoryFields] of a [members][capacity][kHistoryFields] array; drain empties every buffer.
-// SPHX:History:capacity when `records` is given and capacity is below the largest count: nothing is copied or drained then.
+// Every member's counts and, with `out`, its filled rows into out[m][0 .. n_records[m])[kHistoryFields] (ring_read)
 void History::read(hipStream_t st, int capacity, double *out, int *n_records, int64_t *n_dropped, bool drain)
 {
-    const int M = members;
-    std::vector<HistoryHead> h(M);
-    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(HistoryHead) * M, hipMemcpyDeviceToHost, st));
-    SPHX_HIP(hipStreamSynchronize(st));
-    long long most = 0;
-    for (int m = 0; m < M; ++m) {
-        const long long n = h[m].n_records;
-        if (n < 0 || n > (long long)cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:History:state", "internal: record count out of range");
-        most = std::max(most, n);
-    }
-    require(out == nullptr || (long long)capacity >= most, "SPHX:History:capacity", "capacity is smaller than the number of records");
-    if (out && most > 0) {
-        for (int m = 0; m < M; ++m)  // only the filled rows of each member's block
-            if (h[m].n_records > 0)
-                SPHX_HIP(hipMemcpyAsync(out + (size_t)m * capacity * kHistoryFields, records.get() + (size_t)m * cfg.capacity * kHistoryFields,
-                                        (size_t)h[m].n_records * kHistoryFields * sizeof(double), hipMemcpyDeviceToHost, st));
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
-    for (int m = 0; m < M; ++m) {
-        if (n_records) n_records[m] = (int)h[m].n_records;
-        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
-    }
-    if (drain) {
-        zero(st);
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
+    ring_read(*this, head, st, capacity, {out, records.get(), (size_t)kHistoryFields}, {}, n_records, n_dropped, drain);
 }
-
-namespace {
-
-// enable for M members on schedule s: every check of cfg first
-void history_enable(History &h, const sphx_history_config *cfg, int M, Schedule &s, hipStream_t st)
-{
-    History::check(cfg, M);
-    sampler_on(h, kHistoryNames, s, st, [&] { h.alloc(*cfg, M); });
-}
-
-}  // namespace
 
 SPHX_EXPORT int sphx_ctx_history_enable(sphx_ctx *c, const sphx_history_config *cfg)
 {
     SPHX_TRY
-    History &h = sampler_to_change(c, &sphx_ctx::hist, kHistoryNames);
-    history_enable(h, cfg, 1, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::hist, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -656,8 +722,7 @@ SPHX_EXPORT int sphx_ctx_history_enable(sphx_ctx *c, const sphx_history_config *
 SPHX_EXPORT int sphx_ctx_history_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    History &h = sampler_to_change(c, &sphx_ctx::hist, kHistoryNames);
-    if (h.on) sampler_off(h, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::hist);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -665,9 +730,8 @@ SPHX_EXPORT int sphx_ctx_history_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_history_read(sphx_ctx *c, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    History &h = sampler_of(c, &sphx_ctx::hist, kHistoryNames, true);
-    settle_owed(c);  // (the records of everything enqueued)
-    h.read(c->stream, capacity, records, n_records, n_dropped, drain != 0);
+    const Owner o = ctx_owner(c);
+    sampler_settled(o, &sphx_ctx::hist).read(o.st, capacity, records, n_records, n_dropped, drain != 0);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -675,7 +739,7 @@ SPHX_EXPORT int sphx_ctx_history_read(sphx_ctx *c, int capacity, double *records
 // ---- velocity-field map ----
 
 // every check of a configuration for M channels with parameters prm (cfg and the shape in force); SPHX:Field:config errors
-void FieldMap::check(const sphx_params &prm, const sphx_field_map_config *cfg, int M)
+void FieldMapShape::check(const sphx_params &prm, const sphx_field_map_config *cfg, int M)
 {
     require(cfg != nullptr, "SPHX:Field:config", "config must not be NULL");
     require(cfg->nx == 0 || cfg->nx >= 2, "SPHX:Field:config", "nx must be 0 (the reference's shape) or >= 2");
@@ -694,15 +758,10 @@ void FieldMap::check(const sphx_params &prm, const sphx_field_map_config *cfg, i
     ny = (int)gy;
 }
 
-// the checked configuration and shape, and planes and heads for M members
-void FieldMap::alloc(const FieldMap &checked, int M)
+// the checked shape, and planes and heads for M members
+void FieldMap::alloc(const FieldMapShape &checked, int M, hipStream_t)
 {
-    cfg = checked.cfg;
-    nx = checked.nx;
-    ny = checked.ny;
-    part = checked.part;
-    i_lo = checked.i_lo;
-    i_hi = checked.i_hi;
+    static_cast<FieldMapShape &>(*this) = checked;
     members = M;
     planes.alloc(std::max<size_t>(block() * M, 1));  // (a slab that owns no node column still has a head)
     head.alloc(M);
@@ -728,27 +787,20 @@ void FieldMap::read(hipStream_t st, int stride, double *const out[kFieldPlanes],
 
 namespace {
 
-// enable for M members of channels with parameters prm on schedule s: every check of cfg first
-void field_enable(FieldMap &f, const sphx_params &prm, const sphx_field_map_config *cfg, int M, Schedule &s, hipStream_t st)
+// the argument checks of a read, then what is enqueued lands, and the read
+const FieldMap &field_read(const Owner &o, int capacity, int *nx, int *ny, double *count, double *sum_w, double *sum_ux, double *sum_uy,
+                           double *sum_ux2, double *sum_uy2, int64_t *n_samples, double *t_first, double *t_last)
 {
-    FieldMap checked;
-    checked.check(prm, cfg, M);
-    sampler_on(f, kFieldNames, s, st, [&] { f.alloc(checked, M); });
-}
-
-// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
-template <typename Settle>
-void field_read(const FieldMap &f, hipStream_t st, Settle &&settle, int capacity, int *nx, int *ny, double *count, double *sum_w,
-                double *sum_ux, double *sum_uy, double *sum_ux2, double *sum_uy2, int64_t *n_samples, double *t_first, double *t_last)
-{
+    const FieldMap &f = sampler_of(o, &sphx_ctx::fmap, true);
     double *const out[kFieldPlanes] = {count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2};
     bool any = false;
-    for (double *o : out) any = any || o != nullptr;
+    for (double *p : out) any = any || p != nullptr;
     require(!any || (size_t)std::max(capacity, 0) >= f.nodes(), "SPHX:Field:capacity", "capacity is smaller than nx * ny");
-    settle();  // (the samples of everything enqueued)
-    f.read(st, capacity, out, n_samples, t_first, t_last);
+    o.settle();  // (the samples of everything enqueued)
+    f.read(o.st, capacity, out, n_samples, t_first, t_last);
     if (nx) *nx = f.nx;
     if (ny) *ny = f.ny;
+    return f;
 }
 
 }  // namespace
@@ -756,8 +808,8 @@ void field_read(const FieldMap &f, hipStream_t st, Settle &&settle, int capacity
 SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_config *cfg)
 {
     SPHX_TRY
-    FieldMap &f = sampler_to_change(c, &sphx_ctx::fmap, kFieldNames);
-    field_enable(f, c->prm, cfg, 1, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::fmap, o.c->prm, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -765,8 +817,7 @@ SPHX_EXPORT int sphx_ctx_field_map_enable(sphx_ctx *c, const sphx_field_map_conf
 SPHX_EXPORT int sphx_ctx_field_map_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    FieldMap &f = sampler_to_change(c, &sphx_ctx::fmap, kFieldNames);
-    if (f.on) sampler_off(f, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::fmap);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -774,9 +825,7 @@ SPHX_EXPORT int sphx_ctx_field_map_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_field_map_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, true);
-    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, c->stream);
+    sampler_reset(ctx_owner(c), &sphx_ctx::fmap);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -784,8 +833,7 @@ SPHX_EXPORT int sphx_ctx_field_map_reset(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_field_map_sample(sphx_ctx *c)
 {
     SPHX_TRY
-    sampler_of(c, &sphx_ctx::fmap, kFieldNames, true);
-    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_field_map);
+    sampler_sample(ctx_owner(c), &sphx_ctx::fmap, launch_field_map);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -795,9 +843,7 @@ SPHX_EXPORT int sphx_ctx_field_map_read(sphx_ctx *c, int capacity, int *nx, int 
                                         double *t_last)
 {
     SPHX_TRY
-    const FieldMap &f = sampler_of(c, &sphx_ctx::fmap, kFieldNames, true);
-    field_read(f, c->stream, [c] { settle_owed(c); }, capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples,
-               t_first, t_last);
+    field_read(ctx_owner(c), capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -820,7 +866,7 @@ double probe_fold(double x, double DL)
 
 // every check of a configuration for M channels with parameters prm (cfg without the pointer, and the folded points);
 // SPHX:Probe:config errors
-void Probes::check(const sphx_params &prm, const sphx_probes_config *cfg, int M)
+void ProbesShape::check(const sphx_params &prm, const sphx_probes_config *cfg, int M)
 {
     require(cfg != nullptr, "SPHX:Probe:config", "config must not be NULL");
     require(cfg->points != nullptr, "SPHX:Probe:config", "points must not be NULL");
@@ -844,13 +890,10 @@ void Probes::check(const sphx_params &prm, const sphx_probes_config *cfg, int M)
     this->cfg.points = nullptr;
 }
 
-// the checked configuration and points, and records and heads for M members
-void Probes::alloc(const Probes &checked, int M, hipStream_t st)
+// the checked shape, and points, records and heads for M members
+void Probes::alloc(const ProbesShape &checked, int M, hipStream_t st)
 {
-    cfg = checked.cfg;
-    folded = checked.folded;
-    part = checked.part;
-    index = checked.index;
+    static_cast<ProbesShape &>(*this) = checked;
     members = M;
     points.alloc(std::max<size_t>((size_t)held(), 1));  // (a slab that owns no probe still has a head and its times)
     times.alloc((size_t)M * cfg.capacity * 2);
@@ -869,64 +912,18 @@ void Probes::alloc(const Probes &checked, int M, hipStream_t st)
     SPHX_HIP(hipStreamSynchronize(st));  // (`own` goes out of scope here)
 }
 
-// Every member's counts (n_records[m], n_dropped[m], where given) and its filled rows, into times[m][0 .. n_records[m])[2] of a
-// [members][capacity][2] array and values[m][0 .. n_records[m])[row()] of a [members][capacity][row()] array, each where given;
-// drain empties every buffer.  SPHX:Probe:capacity when an array is given and capacity is below the largest count: nothing is
-// copied or drained then.
+// Every member's counts and its filled rows, into times[m][0 .. n_records[m])[2] and values[m][0 .. n_records[m])[row()], each
+// where given (ring_read)
 void Probes::read(hipStream_t st, int capacity, double *t_out, double *v_out, int *n_records, int64_t *n_dropped, bool drain)
 {
-    const int M = members;
-    std::vector<ProbeHead> h(M);
-    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(ProbeHead) * M, hipMemcpyDeviceToHost, st));
-    SPHX_HIP(hipStreamSynchronize(st));
-    long long most = 0;
-    for (int m = 0; m < M; ++m) {
-        const long long n = h[m].n_records;
-        if (n < 0 || n > (long long)cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:Probe:state", "internal: record count out of range");
-        most = std::max(most, n);
-    }
-    require((t_out == nullptr && v_out == nullptr) || (long long)capacity >= most, "SPHX:Probe:capacity",
-            "capacity is smaller than the number of records");
-    if ((t_out || v_out) && most > 0) {
-        for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
-            const size_t n = (size_t)h[m].n_records;
-            if (n == 0) continue;
-            if (t_out)
-                SPHX_HIP(hipMemcpyAsync(t_out + (size_t)m * capacity * 2, times.get() + (size_t)m * cfg.capacity * 2, n * 2 * sizeof(double),
-                                        hipMemcpyDeviceToHost, st));
-            if (v_out)
-                SPHX_HIP(hipMemcpyAsync(v_out + (size_t)m * capacity * row(), values.get() + (size_t)m * cfg.capacity * row(),
-                                        n * row() * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
-    for (int m = 0; m < M; ++m) {
-        if (n_records) n_records[m] = (int)h[m].n_records;
-        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
-    }
-    if (drain) {
-        zero(st);
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
+    ring_read(*this, head, st, capacity, {t_out, times.get(), 2}, {v_out, values.get(), row()}, n_records, n_dropped, drain);
 }
-
-namespace {
-
-// enable for M members of channels with parameters prm on schedule s: every check of cfg first
-void probes_enable(Probes &p, const sphx_params &prm, const sphx_probes_config *cfg, int M, Schedule &s, hipStream_t st)
-{
-    Probes checked;
-    checked.check(prm, cfg, M);
-    sampler_on(p, kProbeNames, s, st, [&] { p.alloc(checked, M, st); });
-}
-
-}  // namespace
 
 SPHX_EXPORT int sphx_ctx_probes_enable(sphx_ctx *c, const sphx_probes_config *cfg)
 {
     SPHX_TRY
-    Probes &p = sampler_to_change(c, &sphx_ctx::probes, kProbeNames);
-    probes_enable(p, c->prm, cfg, 1, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::probes, o.c->prm, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -934,8 +931,7 @@ SPHX_EXPORT int sphx_ctx_probes_enable(sphx_ctx *c, const sphx_probes_config *cf
 SPHX_EXPORT int sphx_ctx_probes_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    Probes &p = sampler_to_change(c, &sphx_ctx::probes, kProbeNames);
-    if (p.on) sampler_off(p, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::probes);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -943,8 +939,7 @@ SPHX_EXPORT int sphx_ctx_probes_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_probes_sample(sphx_ctx *c)
 {
     SPHX_TRY
-    sampler_of(c, &sphx_ctx::probes, kProbeNames, true);
-    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_probes);
+    sampler_sample(ctx_owner(c), &sphx_ctx::probes, launch_probes);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -953,9 +948,9 @@ SPHX_EXPORT int sphx_ctx_probes_read(sphx_ctx *c, int capacity, double *times, d
                                      int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    Probes &p = sampler_of(c, &sphx_ctx::probes, kProbeNames, true);
-    settle_owed(c);  // (the records of everything enqueued)
-    p.read(c->stream, capacity, times, values, n_records, n_dropped, drain != 0);
+    const Owner o = ctx_owner(c);
+    Probes &p = sampler_settled(o, &sphx_ctx::probes);  // (the records of everything enqueued)
+    p.read(o.st, capacity, times, values, n_records, n_dropped, drain != 0);
     if (n_points) *n_points = p.cfg.n_points;
     return SPHX_OK;
     SPHX_CATCH
@@ -965,7 +960,7 @@ SPHX_EXPORT int sphx_ctx_probes_read(sphx_ctx *c, int capacity, double *times, d
 
 // every check of a configuration for M channels of n_fluid fluid rows among n_total (cfg without the pointer, and the ids);
 // SPHX:Tracers:config errors
-void Tracers::check(int n_fluid, int n_total, const sphx_tracers_config *cfg, int M)
+void TracersShape::check(int n_fluid, int n_total, const sphx_tracers_config *cfg, int M)
 {
     const char *id = "SPHX:Tracers:config";
     require(cfg != nullptr, id, "config must not be NULL");
@@ -989,13 +984,10 @@ void Tracers::check(int n_fluid, int n_total, const sphx_tracers_config *cfg, in
     this->n_fluid = n_fluid;
 }
 
-// the checked configuration and ids, the table, and records and heads for M members
-void Tracers::alloc(const Tracers &checked, int M, hipStream_t st)
+// the checked shape, the table, and records and heads for M members
+void Tracers::alloc(const TracersShape &checked, int M, hipStream_t st)
 {
-    cfg = checked.cfg;
-    ids = checked.ids;
-    n_fluid = checked.n_fluid;
-    part = checked.part;
+    static_cast<TracersShape &>(*this) = checked;
     members = M;
     index_of.alloc((size_t)n_fluid);
     times.alloc((size_t)M * cfg.capacity * 2);
@@ -1016,73 +1008,35 @@ void Tracers::nan_fill(hipStream_t st, size_t rows)
     if (rows) SPHX_HIP(hipMemsetAsync(values.get(), 0xFF, rows * row() * sizeof(double), st));
 }
 
-// Every member's counts (n_records[m], n_dropped[m], n_missing[m], where given) and its filled rows, into
-// times[m][0 .. n_records[m])[2] of a [members][capacity][2] array and values[m][0 .. n_records[m])[row()] of a
-// [members][capacity][row()] array, each where given; drain empties every buffer.  SPHX:Tracers:capacity when an array is given
-// and capacity is below the largest count: nothing is copied or drained then.  A slab's (one channel): owned_out [0 .. n_records)
-// the tracers it met per record, an array like the other two, and a draining read refills the rows it hands out with NaN.
+// Every member's counts (with n_missing[m], where given) and its filled rows, into times[m][0 .. n_records[m])[2] and
+// values[m][0 .. n_records[m])[row()], each where given (ring_read).  A slab's (one channel): owned_out [0 .. n_records) the
+// tracers it met per record, an array like the other two, and a draining read refills the rows it hands out with NaN.
 void Tracers::read(hipStream_t st, int capacity, double *t_out, double *v_out, int *n_records, int64_t *n_dropped, int64_t *n_missing,
                    bool drain, int64_t *owned_out)
 {
-    const int M = members;
-    std::vector<TracerHead> h(M);
-    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(TracerHead) * M, hipMemcpyDeviceToHost, st));
-    SPHX_HIP(hipStreamSynchronize(st));
-    long long most = 0;
-    for (int m = 0; m < M; ++m) {
-        const long long n = h[m].n_records;
-        if (n < 0 || n > (long long)cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:Tracers:state", "internal: record count out of range");
-        most = std::max(most, n);
-    }
     if (!part) owned_out = nullptr;
-    require((t_out == nullptr && v_out == nullptr && owned_out == nullptr) || (long long)capacity >= most, "SPHX:Tracers:capacity",
-            "capacity is smaller than the number of records");
     static_assert(sizeof(long long) == sizeof(int64_t), "n_owned is copied as it is");
-    if (owned_out && most > 0)
-        SPHX_HIP(hipMemcpyAsync(owned_out, n_owned.get(), (size_t)most * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (owned_out && !(t_out || v_out)) SPHX_HIP(hipStreamSynchronize(st));
-    if ((t_out || v_out) && most > 0) {
-        for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
-            const size_t n = (size_t)h[m].n_records;
-            if (n == 0) continue;
-            if (t_out)
-                SPHX_HIP(hipMemcpyAsync(t_out + (size_t)m * capacity * 2, times.get() + (size_t)m * cfg.capacity * 2, n * 2 * sizeof(double),
-                                        hipMemcpyDeviceToHost, st));
-            if (v_out)
-                SPHX_HIP(hipMemcpyAsync(v_out + (size_t)m * capacity * row(), values.get() + (size_t)m * cfg.capacity * row(),
-                                        n * row() * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
-    for (int m = 0; m < M; ++m) {
-        if (n_records) n_records[m] = (int)h[m].n_records;
-        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
-        if (n_missing) n_missing[m] = (int64_t)h[m].n_missing;
-    }
-    if (drain) {
-        zero(st);
-        if (part) nan_fill(st, (size_t)most);  // (rows beyond n_records were never written: a dropped record stores no value)
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
+    ring_read(*this, head, st, capacity, {t_out, times.get(), 2}, {v_out, values.get(), row()}, owned_out != nullptr, n_records, n_dropped,
+              drain, [&](RingStage stage, const std::vector<TracerHead> &h, long long most) {
+                  if (stage == RingStage::Rows && owned_out) {
+                      if (most > 0) SPHX_HIP(hipMemcpyAsync(owned_out, n_owned.get(), (size_t)most * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+                      if (!(t_out || v_out)) SPHX_HIP(hipStreamSynchronize(st));
+                  }
+                  if (stage == RingStage::Counts && n_missing)
+                      for (int m = 0; m < members; ++m) n_missing[m] = (int64_t)h[m].n_missing;
+                  // (rows beyond n_records were never written: a dropped record stores no value)
+                  if (stage == RingStage::Drain && part) nan_fill(st, (size_t)most);
+              });
 }
 
 namespace {
 
-// enable for M members of channels of n_fluid fluid rows among n_total on schedule s: every check of cfg first
-void tracers_enable(Tracers &t, int n_fluid, int n_total, const sphx_tracers_config *cfg, int M, Schedule &s, hipStream_t st)
+// what is enqueued lands, then the read, the list and its length
+void tracers_read(const Owner &o, int capacity, double *times, double *values, int32_t *ids, int *n_tracers, int *n_records,
+                  int64_t *n_dropped, int64_t *n_missing, int drain)
 {
-    Tracers checked;
-    checked.check(n_fluid, n_total, cfg, M);
-    sampler_on(t, kTracerNames, s, st, [&] { t.alloc(checked, M, st); });
-}
-
-// settle() -- what is enqueued lands first -- then the read, the list and its length; shared by contexts and batches
-template <typename Settle>
-void tracers_read(Tracers &t, hipStream_t st, Settle &&settle, int capacity, double *times, double *values, int32_t *ids, int *n_tracers,
-                  int *n_records, int64_t *n_dropped, int64_t *n_missing, int drain)
-{
-    settle();  // (the records of everything enqueued)
-    t.read(st, capacity, times, values, n_records, n_dropped, n_missing, drain != 0);
+    Tracers &t = sampler_settled(o, &sphx_ctx::tracers);  // (the records of everything enqueued)
+    t.read(o.st, capacity, times, values, n_records, n_dropped, n_missing, drain != 0);
     if (ids) std::copy(t.ids.begin(), t.ids.end(), ids);
     if (n_tracers) *n_tracers = t.cfg.n_tracers;
 }
@@ -1092,8 +1046,8 @@ void tracers_read(Tracers &t, hipStream_t st, Settle &&settle, int capacity, dou
 SPHX_EXPORT int sphx_ctx_tracers_enable(sphx_ctx *c, const sphx_tracers_config *cfg)
 {
     SPHX_TRY
-    Tracers &t = sampler_to_change(c, &sphx_ctx::tracers, kTracerNames);
-    tracers_enable(t, c->nf, c->nt, cfg, 1, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::tracers, o.c->nf, o.c->nt, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1101,8 +1055,7 @@ SPHX_EXPORT int sphx_ctx_tracers_enable(sphx_ctx *c, const sphx_tracers_config *
 SPHX_EXPORT int sphx_ctx_tracers_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    Tracers &t = sampler_to_change(c, &sphx_ctx::tracers, kTracerNames);
-    if (t.on) sampler_off(t, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::tracers);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1110,8 +1063,7 @@ SPHX_EXPORT int sphx_ctx_tracers_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_tracers_sample(sphx_ctx *c)
 {
     SPHX_TRY
-    sampler_of(c, &sphx_ctx::tracers, kTracerNames, true);
-    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_tracers);
+    sampler_sample(ctx_owner(c), &sphx_ctx::tracers, launch_tracers);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1120,17 +1072,16 @@ SPHX_EXPORT int sphx_ctx_tracers_read(sphx_ctx *c, int capacity, double *times, 
                                       int *n_records, int64_t *n_dropped, int64_t *n_missing, int drain)
 {
     SPHX_TRY
-    Tracers &t = sampler_of(c, &sphx_ctx::tracers, kTracerNames, true);
-    tracers_read(t, c->stream, [c] { settle_owed(c); }, capacity, times, values, ids, n_tracers, n_records, n_dropped, n_missing, drain);
+    tracers_read(ctx_owner(c), capacity, times, values, ids, n_tracers, n_records, n_dropped, n_missing, drain);
     return SPHX_OK;
     SPHX_CATCH
 }
 
 // ---- profile series ----
 
-// every check of a configuration for M channels with parameters prm (cfg, n_bins, n_bands): the bins and bands by the checks
-// of FlowStats::configure, the record buffer by those of Probes::check; SPHX:ProfileSeries:config errors
-void ProfileSeries::check(const sphx_params &prm, const sphx_profile_series_config *cfg, int M)
+// every check of a configuration for M channels with parameters prm (cfg, n_bins, n_bands): the bins and bands as the flow
+// statistics have them, the record buffer by the checks of ProbesShape::check; SPHX:ProfileSeries:config errors
+void ProfileSeriesShape::check(const sphx_params &prm, const sphx_profile_series_config *cfg, int M)
 {
     const char *id = "SPHX:ProfileSeries:config";
     require(cfg != nullptr, id, "config must not be NULL");
@@ -1138,28 +1089,18 @@ void ProfileSeries::check(const sphx_params &prm, const sphx_profile_series_conf
     require(cfg->every >= 1, id, "every must be >= 1");
     require(cfg->capacity >= 1, id, "capacity must be >= 1");
     require(!std::isnan(cfg->t_from), id, "t_from must not be NaN");
-    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, id, "n_bands must be 0, 1 or 2");
-    for (int b = 0; b < cfg->n_bands; ++b)
-        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, id,
-                "band centres must be finite and half-widths finite and >= 0");
-    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
-    require((int64_t)bins * (cfg->n_bands + 1) <= kStatsMaxBins, id,
-            "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
-    if (!((double)M * (double)cfg->capacity * (double)bins * (cfg->n_bands + 1) * kStatsFields <= (double)kSeriesMaxTotal))
+    this->cfg = *cfg;
+    bins_and_bands(id, prm, this->cfg, n_bins, n_bands);
+    require((int64_t)n_bins * n_bands <= kStatsMaxBins, id, "n_bins * (n_bands + 1) must not exceed 1536 (the per-workgroup LDS counters)");
+    if (!((double)M * (double)cfg->capacity * (double)n_bins * n_bands * kStatsFields <= (double)kSeriesMaxTotal))
         throw Error(SPHX_ERR_ARG, id,
                     std::string(M > 1 ? "n_members * " : "") + "capacity * (n_bands + 1) * n_bins * 5 must not exceed 1 << 27 doubles");
-    this->cfg = *cfg;
-    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
-    n_bins = bins;
-    n_bands = cfg->n_bands + 1;
 }
 
-// the checked configuration, and sums in flight, records and heads for M members
-void ProfileSeries::alloc(const ProfileSeries &checked, int M)
+// the checked shape, and sums in flight, records and heads for M members
+void ProfileSeries::alloc(const ProfileSeriesShape &checked, int M, hipStream_t)
 {
-    cfg = checked.cfg;
-    n_bins = checked.n_bins;
-    n_bands = checked.n_bands;
+    static_cast<ProfileSeriesShape &>(*this) = checked;
     members = M;
     isum.alloc(block() * M);
     times.alloc((size_t)M * cfg.capacity * 2);
@@ -1167,68 +1108,21 @@ void ProfileSeries::alloc(const ProfileSeries &checked, int M)
     head.alloc(M);
 }
 
-// Every member's counts (n_records[m], n_dropped[m], where given) and its filled rows, into times[m][0 .. n_records[m])[2] of a
-// [members][capacity][2] array and records[m][0 .. n_records[m])[block()] of a [members][capacity][block()] array, each where
-// given; drain empties every buffer.  SPHX:ProfileSeries:range when a member's sticky flag is up; SPHX:ProfileSeries:capacity
-// when an array is given and capacity is below the largest count: nothing is copied or drained then.
+// Every member's counts and its filled rows, into times[m][0 .. n_records[m])[2] and records[m][0 .. n_records[m])[block()],
+// each where given (ring_read; SPHX:ProfileSeries:range when a member's sticky flag is up)
 void ProfileSeries::read(hipStream_t st, int capacity, double *t_out, double *r_out, int *n_records, int64_t *n_dropped, bool drain)
 {
-    const int M = members;
-    std::vector<ProfileSeriesHead> h(M);
-    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(ProfileSeriesHead) * M, hipMemcpyDeviceToHost, st));
-    SPHX_HIP(hipStreamSynchronize(st));
-    long long most = 0;
-    for (int m = 0; m < M; ++m) {
-        const long long n = h[m].n_records;
-        if (n < 0 || n > (long long)cfg.capacity)
-            throw Error(SPHX_ERR_STATE, "SPHX:ProfileSeries:state", "internal: record count out of range");
-        if (h[m].range)
-            throw Error(SPHX_ERR_STATE, "SPHX:ProfileSeries:range", (M > 1 ? "member " + std::to_string(m) + ": " : std::string()) +
-                                                                    "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
-        most = std::max(most, n);
-    }
-    require((t_out == nullptr && r_out == nullptr) || (long long)capacity >= most, "SPHX:ProfileSeries:capacity",
-            "capacity is smaller than the number of records");
-    if ((t_out || r_out) && most > 0) {
-        for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
-            const size_t n = (size_t)h[m].n_records;
-            if (n == 0) continue;
-            if (t_out)
-                SPHX_HIP(hipMemcpyAsync(t_out + (size_t)m * capacity * 2, times.get() + (size_t)m * cfg.capacity * 2, n * 2 * sizeof(double),
-                                        hipMemcpyDeviceToHost, st));
-            if (r_out)
-                SPHX_HIP(hipMemcpyAsync(r_out + (size_t)m * capacity * block(), records.get() + (size_t)m * cfg.capacity * block(),
-                                        n * block() * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
-    for (int m = 0; m < M; ++m) {
-        if (n_records) n_records[m] = (int)h[m].n_records;
-        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
-    }
-    if (drain) {
-        zero(st);
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
+    ring_read(*this, head, st, capacity, {t_out, times.get(), 2}, {r_out, records.get(), block()}, n_records, n_dropped, drain);
 }
 
 namespace {
 
-// enable for M members of channels with parameters prm on schedule s: every check of cfg first
-void series_enable(ProfileSeries &p, const sphx_params &prm, const sphx_profile_series_config *cfg, int M, Schedule &s, hipStream_t st)
+// what is enqueued lands, then the read and the shape
+void series_read(const Owner &o, int capacity, double *times, double *records, int *n_bins, int *n_bands, int *n_records,
+                 int64_t *n_dropped, int drain)
 {
-    ProfileSeries checked;
-    checked.check(prm, cfg, M);
-    sampler_on(p, kSeriesNames, s, st, [&] { p.alloc(checked, M); });
-}
-
-// settle() -- what is enqueued lands first -- then the read and the shape; shared by contexts and batches
-template <typename Settle>
-void series_read(ProfileSeries &p, hipStream_t st, Settle &&settle, int capacity, double *times, double *records, int *n_bins, int *n_bands,
-                 int *n_records, int64_t *n_dropped, int drain)
-{
-    settle();  // (the records of everything enqueued)
-    p.read(st, capacity, times, records, n_records, n_dropped, drain != 0);
+    ProfileSeries &p = sampler_settled(o, &sphx_ctx::pseries);  // (the records of everything enqueued)
+    p.read(o.st, capacity, times, records, n_records, n_dropped, drain != 0);
     if (n_bins) *n_bins = p.n_bins;
     if (n_bands) *n_bands = p.n_bands;
 }
@@ -1238,8 +1132,8 @@ void series_read(ProfileSeries &p, hipStream_t st, Settle &&settle, int capacity
 SPHX_EXPORT int sphx_ctx_profile_series_enable(sphx_ctx *c, const sphx_profile_series_config *cfg)
 {
     SPHX_TRY
-    ProfileSeries &p = sampler_to_change(c, &sphx_ctx::pseries, kSeriesNames);
-    series_enable(p, c->prm, cfg, 1, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::pseries, o.c->prm, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1247,8 +1141,7 @@ SPHX_EXPORT int sphx_ctx_profile_series_enable(sphx_ctx *c, const sphx_profile_s
 SPHX_EXPORT int sphx_ctx_profile_series_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    ProfileSeries &p = sampler_to_change(c, &sphx_ctx::pseries, kSeriesNames);
-    if (p.on) sampler_off(p, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::pseries);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1256,8 +1149,7 @@ SPHX_EXPORT int sphx_ctx_profile_series_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_profile_series_sample(sphx_ctx *c)
 {
     SPHX_TRY
-    sampler_of(c, &sphx_ctx::pseries, kSeriesNames, true);
-    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_profile_series);
+    sampler_sample(ctx_owner(c), &sphx_ctx::pseries, launch_profile_series);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1266,17 +1158,16 @@ SPHX_EXPORT int sphx_ctx_profile_series_read(sphx_ctx *c, int capacity, double *
                                              int *n_records, int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    ProfileSeries &p = sampler_of(c, &sphx_ctx::pseries, kSeriesNames, true);
-    series_read(p, c->stream, [c] { settle_owed(c); }, capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
+    series_read(ctx_owner(c), capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
     return SPHX_OK;
     SPHX_CATCH
 }
 
 // ---- pair statistics ----
 
-// every check of a configuration for M channels with parameters prm (cfg, n_bins, n_bands, kinds, r_max); has_walls: the
+// every check of a configuration of channels with parameters prm (cfg, n_bins, n_bands, kinds, r_max); has_walls: the
 // channel holds wall particles (without any, with_walls leaves fw at zero); SPHX:PairDist:config errors
-void PairDist::check(const sphx_params &prm, const sphx_pair_dist_config *cfg, int M, bool has_walls)
+void PairDistShape::check(const sphx_params &prm, const sphx_pair_dist_config *cfg, bool has_walls)
 {
     const char *id = "SPHX:PairDist:config";
     require(cfg != nullptr, id, "config must not be NULL");
@@ -1288,27 +1179,16 @@ void PairDist::check(const sphx_params &prm, const sphx_pair_dist_config *cfg, i
             "r_max must be 0 (= 2h) or 0 < r_max <= 2h: beyond 2h the sweep of the three cell columns is not complete");
     require(std::isfinite(cfg->y_margin) && cfg->y_margin >= 0.0, id, "y_margin must be finite and >= 0");
     require(cfg->with_walls == 0 || cfg->with_walls == 1, id, "with_walls must be 0 or 1");
-    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, id, "n_bands must be 0, 1 or 2");
-    for (int b = 0; b < cfg->n_bands; ++b)
-        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, id,
-                "band centres must be finite and half-widths finite and >= 0");
     this->cfg = *cfg;
-    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
-    n_bins = cfg->n_bins;
-    n_bands = cfg->n_bands + 1;
+    bins_and_bands(id, prm, this->cfg, n_bins, n_bands);
     kinds = cfg->with_walls && has_walls ? 2 : 1;
     r_max = cfg->r_max > 0.0 ? cfg->r_max : two_h;
-    members = M;
 }
 
-// the checked configuration, and sums and heads for M members
-void PairDist::alloc(const PairDist &checked, int M)
+// the checked shape, and sums and heads for M members
+void PairDist::alloc(const PairDistShape &checked, int M, hipStream_t)
 {
-    cfg = checked.cfg;
-    n_bins = checked.n_bins;
-    n_bands = checked.n_bands;
-    kinds = checked.kinds;
-    r_max = checked.r_max;
+    static_cast<PairDistShape &>(*this) = checked;
     members = M;
     empty.assign(block() * M, 0ull);
     for (int m = 0; m < M; ++m)
@@ -1351,23 +1231,15 @@ void PairDist::read(hipStream_t st, int band, int stride, int64_t *ff, int64_t *
 
 namespace {
 
-// enable for M members of channels with parameters prm on schedule s: every check of cfg first
-void pair_dist_enable(PairDist &p, const sphx_params &prm, const sphx_pair_dist_config *cfg, int M, bool has_walls, Schedule &s, hipStream_t st)
+// the argument checks of a read, then what is enqueued lands, and the read
+void pair_dist_read(const Owner &o, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw, int64_t *centres, double *r2_min,
+                    int64_t *n_samples, double *t_first, double *t_last)
 {
-    PairDist checked;
-    checked.check(prm, cfg, M, has_walls);
-    sampler_on(p, kPairNames, s, st, [&] { p.alloc(checked, M); });
-}
-
-// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
-template <typename Settle>
-void pair_dist_read(const PairDist &p, hipStream_t st, Settle &&settle, int band, int capacity, int *n_bins, int64_t *ff, int64_t *fw,
-                    int64_t *centres, double *r2_min, int64_t *n_samples, double *t_first, double *t_last)
-{
+    const PairDist &p = sampler_of(o, &sphx_ctx::pairs, true);
     require(band >= 0 && band < p.n_bands, "SPHX:PairDist:band", "band must be 0 (whole channel) .. n_bands");
     require((ff == nullptr && fw == nullptr) || capacity >= p.n_bins, "SPHX:PairDist:capacity", "capacity is smaller than the number of bins");
-    settle();
-    p.read(st, band, capacity, ff, fw, centres, r2_min, n_samples, t_first, t_last);
+    o.settle();
+    p.read(o.st, band, capacity, ff, fw, centres, r2_min, n_samples, t_first, t_last);
     if (n_bins) *n_bins = p.n_bins;
 }
 
@@ -1376,8 +1248,8 @@ void pair_dist_read(const PairDist &p, hipStream_t st, Settle &&settle, int band
 SPHX_EXPORT int sphx_ctx_pair_dist_enable(sphx_ctx *c, const sphx_pair_dist_config *cfg)
 {
     SPHX_TRY
-    PairDist &p = sampler_to_change(c, &sphx_ctx::pairs, kPairNames);
-    pair_dist_enable(p, c->prm, cfg, 1, c->nw > 0, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::pairs, o.c->prm, cfg, o.has_walls);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1385,8 +1257,7 @@ SPHX_EXPORT int sphx_ctx_pair_dist_enable(sphx_ctx *c, const sphx_pair_dist_conf
 SPHX_EXPORT int sphx_ctx_pair_dist_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    PairDist &p = sampler_to_change(c, &sphx_ctx::pairs, kPairNames);
-    if (p.on) sampler_off(p, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::pairs);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1394,9 +1265,7 @@ SPHX_EXPORT int sphx_ctx_pair_dist_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_pair_dist_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    PairDist &p = sampler_of(c, &sphx_ctx::pairs, kPairNames, true);
-    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(p, c->stream);
+    sampler_reset(ctx_owner(c), &sphx_ctx::pairs);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1404,8 +1273,7 @@ SPHX_EXPORT int sphx_ctx_pair_dist_reset(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_pair_dist_sample(sphx_ctx *c)
 {
     SPHX_TRY
-    sampler_of(c, &sphx_ctx::pairs, kPairNames, true);
-    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_pair_dist);
+    sampler_sample(ctx_owner(c), &sphx_ctx::pairs, launch_pair_dist);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1414,8 +1282,7 @@ SPHX_EXPORT int sphx_ctx_pair_dist_read(sphx_ctx *c, int band, int capacity, int
                                         double *r2_min, int64_t *n_samples, double *t_first, double *t_last)
 {
     SPHX_TRY
-    const PairDist &p = sampler_of(c, &sphx_ctx::pairs, kPairNames, true);
-    pair_dist_read(p, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
+    pair_dist_read(ctx_owner(c), band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1424,7 +1291,7 @@ SPHX_EXPORT int sphx_ctx_pair_dist_read(sphx_ctx *c, int band, int capacity, int
 
 // every check of a configuration of channels with parameters prm (cfg, n_bins, n_bands, walls); has_walls: the channel holds
 // wall particles (without any, with_walls changes nothing); SPHX:GradStats:config errors
-void GradStats::check(const sphx_params &prm, const sphx_grad_stats_config *cfg, bool has_walls)
+void GradStatsShape::check(const sphx_params &prm, const sphx_grad_stats_config *cfg, bool has_walls)
 {
     const char *id = "SPHX:GradStats:config";
     require(cfg != nullptr, id, "config must not be NULL");
@@ -1433,27 +1300,16 @@ void GradStats::check(const sphx_params &prm, const sphx_grad_stats_config *cfg,
     require(!std::isnan(cfg->t_from), id, "t_from must not be NaN");
     require(std::isfinite(cfg->det_min) && cfg->det_min >= 0.0, id, "det_min must be finite and >= 0");
     require(cfg->with_walls == 0 || cfg->with_walls == 1, id, "with_walls must be 0 or 1");
-    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, id, "n_bands must be 0, 1 or 2");
-    for (int b = 0; b < cfg->n_bands; ++b)
-        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, id,
-                "band centres must be finite and half-widths finite and >= 0");
-    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
-    require((int64_t)bins * (cfg->n_bands + 1) <= kGradMaxBins, id,
-            "n_bins * (n_bands + 1) must not exceed 640 (the per-workgroup LDS counters)");
     this->cfg = *cfg;
-    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
-    n_bins = bins;
-    n_bands = cfg->n_bands + 1;
+    bins_and_bands(id, prm, this->cfg, n_bins, n_bands);
+    require((int64_t)n_bins * n_bands <= kGradMaxBins, id, "n_bins * (n_bands + 1) must not exceed 640 (the per-workgroup LDS counters)");
     walls = cfg->with_walls && has_walls;
 }
 
-// the checked configuration, and sums and heads for M members
-void GradStats::alloc(const GradStats &checked, int M)
+// the checked shape, and sums and heads for M members
+void GradStats::alloc(const GradStatsShape &checked, int M, hipStream_t)
 {
-    cfg = checked.cfg;
-    n_bins = checked.n_bins;
-    n_bands = checked.n_bands;
-    walls = checked.walls;
+    static_cast<GradStatsShape &>(*this) = checked;
     members = M;
     isum.alloc(block() * M);
     dsum.alloc(block() * M);
@@ -1483,23 +1339,14 @@ void GradStats::read(hipStream_t st, int band, int stride, double *sums, int64_t
 
 namespace {
 
-// enable for M members of channels with parameters prm on schedule s: every check of cfg first
-void grad_stats_enable(GradStats &f, const sphx_params &prm, const sphx_grad_stats_config *cfg, int M, bool has_walls, Schedule &s, hipStream_t st)
+// the argument checks of a read, then what is enqueued lands, and the read
+void grad_stats_read(const Owner &o, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples, double *t_first, double *t_last)
 {
-    GradStats checked;
-    checked.check(prm, cfg, has_walls);
-    sampler_on(f, kGradNames, s, st, [&] { f.alloc(checked, M); });
-}
-
-// the argument checks of a read, then settle() -- what is enqueued lands first -- and the read; shared by contexts and batches
-template <typename Settle>
-void grad_stats_read(const GradStats &f, hipStream_t st, Settle &&settle, int band, int capacity, int *n_bins, double *sums, int64_t *n_samples,
-                     double *t_first, double *t_last)
-{
+    const GradStats &f = sampler_of(o, &sphx_ctx::grads, true);
     require(band >= 0 && band < f.n_bands, "SPHX:GradStats:band", "band must be 0 (whole channel) .. n_bands");
     require(sums == nullptr || capacity >= f.n_bins, "SPHX:GradStats:capacity", "capacity is smaller than the number of bins");
-    settle();
-    f.read(st, band, capacity, sums, n_samples, t_first, t_last);
+    o.settle();
+    f.read(o.st, band, capacity, sums, n_samples, t_first, t_last);
     if (n_bins) *n_bins = f.n_bins;
 }
 
@@ -1508,8 +1355,8 @@ void grad_stats_read(const GradStats &f, hipStream_t st, Settle &&settle, int ba
 SPHX_EXPORT int sphx_ctx_grad_stats_enable(sphx_ctx *c, const sphx_grad_stats_config *cfg)
 {
     SPHX_TRY
-    GradStats &f = sampler_to_change(c, &sphx_ctx::grads, kGradNames);
-    grad_stats_enable(f, c->prm, cfg, 1, c->nw > 0, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::grads, o.c->prm, cfg, o.has_walls);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1517,8 +1364,7 @@ SPHX_EXPORT int sphx_ctx_grad_stats_enable(sphx_ctx *c, const sphx_grad_stats_co
 SPHX_EXPORT int sphx_ctx_grad_stats_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    GradStats &f = sampler_to_change(c, &sphx_ctx::grads, kGradNames);
-    if (f.on) sampler_off(f, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::grads);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1526,9 +1372,7 @@ SPHX_EXPORT int sphx_ctx_grad_stats_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_grad_stats_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    GradStats &f = sampler_of(c, &sphx_ctx::grads, kGradNames, true);
-    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, c->stream);
+    sampler_reset(ctx_owner(c), &sphx_ctx::grads);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1536,8 +1380,7 @@ SPHX_EXPORT int sphx_ctx_grad_stats_reset(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_grad_stats_sample(sphx_ctx *c)
 {
     SPHX_TRY
-    sampler_of(c, &sphx_ctx::grads, kGradNames, true);
-    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_grad_stats);
+    sampler_sample(ctx_owner(c), &sphx_ctx::grads, launch_grad_stats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1546,8 +1389,7 @@ SPHX_EXPORT int sphx_ctx_grad_stats_read(sphx_ctx *c, int band, int capacity, in
                                          double *t_last)
 {
     SPHX_TRY
-    const GradStats &f = sampler_of(c, &sphx_ctx::grads, kGradNames, true);
-    grad_stats_read(f, c->stream, [c] { settle_owed(c); }, band, capacity, n_bins, sums, n_samples, t_first, t_last);
+    grad_stats_read(ctx_owner(c), band, capacity, n_bins, sums, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1555,7 +1397,7 @@ SPHX_EXPORT int sphx_ctx_grad_stats_read(sphx_ctx *c, int band, int capacity, in
 // ---- density statistics ----
 
 // every check of a configuration of channels with parameters prm (cfg, n_bins, n_bands, e); SPHX:DensStats:config errors
-void DensStats::check(const sphx_params &prm, const sphx_dens_stats_config *cfg)
+void DensStatsShape::check(const sphx_params &prm, const sphx_dens_stats_config *cfg)
 {
     const char *id = "SPHX:DensStats:config";
     require(cfg != nullptr, id, "config must not be NULL");
@@ -1565,31 +1407,21 @@ void DensStats::check(const sphx_params &prm, const sphx_dens_stats_config *cfg)
     require(cfg->n_hist >= 1 && cfg->n_hist <= kDensMaxHist, id, "n_hist must be 1 .. 1024");
     require(cfg->delta_bound > 0.0 && cfg->delta_bound <= 0.5, id, "delta_bound must be in (0, 0.5]");  // (a NaN fails)
     require(cfg->hist_range > 0.0 && cfg->hist_range <= cfg->delta_bound, id, "hist_range must be in (0, delta_bound]");
-    require(cfg->n_bands >= 0 && cfg->n_bands <= 2, id, "n_bands must be 0, 1 or 2");
-    for (int b = 0; b < cfg->n_bands; ++b)
-        require(std::isfinite(cfg->band_x[b]) && std::isfinite(cfg->band_hw[b]) && cfg->band_hw[b] >= 0.0, id,
-                "band centres must be finite and half-widths finite and >= 0");
-    const int bins = cfg->n_bins > 0 ? cfg->n_bins : std::max(20, (int)std::floor(prm.DH / prm.dp + 0.5));
-    require(((uint64_t)dens_sum_words(cfg->n_bands + 1, bins, cfg->n_hist) + dens_key_words(cfg->n_bands + 1, bins)) * sizeof(unsigned long long)
+    this->cfg = *cfg;
+    bins_and_bands(id, prm, this->cfg, n_bins, n_bands);
+    require(((uint64_t)dens_sum_words(n_bands, n_bins, cfg->n_hist) + dens_key_words(n_bands, n_bins)) * sizeof(unsigned long long)
                 <= kDensMaxShmem,
             id, "(n_bands + 1) * (8 * n_bins + n_hist + 2) must not exceed 7680 (the 60 KB of LDS of a workgroup)");
-    this->cfg = *cfg;
-    for (int b = cfg->n_bands; b < 2; ++b) { this->cfg.band_x[b] = 0.0; this->cfg.band_hw[b] = 0.0; }
-    n_bins = bins;
-    n_bands = cfg->n_bands + 1;
     // 2^e >= delta_bound: frexp gives delta_bound = m 2^e with 0.5 <= m < 1, and m = 0.5 is the power of two itself
     int ex = 0;
     const double m = std::frexp(cfg->delta_bound, &ex);
     e = m == 0.5 ? ex - 1 : ex;
 }
 
-// the checked configuration, and sums, keys and heads for M members
-void DensStats::alloc(const DensStats &checked, int M)
+// the checked shape, and sums, keys and heads for M members
+void DensStats::alloc(const DensStatsShape &checked, int M, hipStream_t)
 {
-    cfg = checked.cfg;
-    n_bins = checked.n_bins;
-    n_bands = checked.n_bands;
-    e = checked.e;
+    static_cast<DensStatsShape &>(*this) = checked;
     members = M;
     isum.alloc(block() * M);
     dsum.alloc(block() * M);
@@ -1637,27 +1469,17 @@ void DensStats::read(hipStream_t st, int m, int band, int stride, double *sums, 
 
 namespace {
 
-// enable for M members of channels with parameters prm on schedule s: every check of cfg first
-void dens_stats_enable(DensStats &f, const sphx_params &prm, const sphx_dens_stats_config *cfg, int M, Schedule &s, hipStream_t st)
+// the argument checks of a read of member m, then what is enqueued lands, and the read
+void dens_stats_read(const Owner &o, int m, int band, int capacity, int hist_capacity, int *n_bins, int *n_hist, double *sums, int64_t *hist,
+                     int64_t *below, int64_t *above, int64_t *n_samples, double *t_first, double *t_last)
 {
-    DensStats checked;
-    checked.check(prm, cfg);
-    sampler_on(f, kDensNames, s, st, [&] { f.alloc(checked, M); });
-}
-
-// the argument checks of a read of member m, then settle() -- what is enqueued lands first -- and the read; shared by contexts
-// and batches
-template <typename Settle>
-void dens_stats_read(const DensStats &f, hipStream_t st, Settle &&settle, int m, int band, int capacity, int hist_capacity, int *n_bins,
-                     int *n_hist, double *sums, int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first,
-                     double *t_last)
-{
+    const DensStats &f = sampler_of(o, &sphx_ctx::dens, true);
     require(band >= 0 && band < f.n_bands, "SPHX:DensStats:band", "band must be 0 (whole channel) .. n_bands");
     require(sums == nullptr || capacity >= f.n_bins, "SPHX:DensStats:capacity", "capacity is smaller than the number of bins");
     require(hist == nullptr || hist_capacity >= f.cfg.n_hist, "SPHX:DensStats:capacity",
             "hist_capacity is smaller than the number of histogram bins");
-    settle();
-    f.read(st, m, band, capacity, sums, hist, below, above, n_samples, t_first, t_last);
+    o.settle();
+    f.read(o.st, m, band, capacity, sums, hist, below, above, n_samples, t_first, t_last);
     if (n_bins) *n_bins = f.n_bins;
     if (n_hist) *n_hist = f.cfg.n_hist;
 }
@@ -1667,8 +1489,8 @@ void dens_stats_read(const DensStats &f, hipStream_t st, Settle &&settle, int m,
 SPHX_EXPORT int sphx_ctx_dens_stats_enable(sphx_ctx *c, const sphx_dens_stats_config *cfg)
 {
     SPHX_TRY
-    DensStats &f = sampler_to_change(c, &sphx_ctx::dens, kDensNames);
-    dens_stats_enable(f, c->prm, cfg, 1, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::dens, o.c->prm, cfg);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1676,8 +1498,7 @@ SPHX_EXPORT int sphx_ctx_dens_stats_enable(sphx_ctx *c, const sphx_dens_stats_co
 SPHX_EXPORT int sphx_ctx_dens_stats_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    DensStats &f = sampler_to_change(c, &sphx_ctx::dens, kDensNames);
-    if (f.on) sampler_off(f, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::dens);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1685,9 +1506,7 @@ SPHX_EXPORT int sphx_ctx_dens_stats_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_dens_stats_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    DensStats &f = sampler_of(c, &sphx_ctx::dens, kDensNames, true);
-    settle_owed(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, c->stream);
+    sampler_reset(ctx_owner(c), &sphx_ctx::dens);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1695,8 +1514,7 @@ SPHX_EXPORT int sphx_ctx_dens_stats_reset(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_dens_stats_sample(sphx_ctx *c)
 {
     SPHX_TRY
-    sampler_of(c, &sphx_ctx::dens, kDensNames, true);
-    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_dens_stats);
+    sampler_sample(ctx_owner(c), &sphx_ctx::dens, launch_dens_stats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1705,9 +1523,7 @@ SPHX_EXPORT int sphx_ctx_dens_stats_read(sphx_ctx *c, int band, int capacity, in
                                          int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first, double *t_last)
 {
     SPHX_TRY
-    const DensStats &f = sampler_of(c, &sphx_ctx::dens, kDensNames, true);
-    dens_stats_read(f, c->stream, [c] { settle_owed(c); }, 0, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above,
-                    n_samples, t_first, t_last);
+    dens_stats_read(ctx_owner(c), 0, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1715,8 +1531,8 @@ SPHX_EXPORT int sphx_ctx_dens_stats_read(sphx_ctx *c, int band, int capacity, in
 // ---- mode amplitudes ----
 
 // every check of a configuration for M channels (cfg): the modes by the kernel's limits, the record buffer by the checks of
-// ProfileSeries::check; SPHX:Modes:config errors
-void Modes::check(const sphx_modes_config *cfg, int M)
+// ProfileSeriesShape::check; SPHX:Modes:config errors
+void ModesShape::check(const sphx_modes_config *cfg, int M)
 {
     const char *id = "SPHX:Modes:config";
     require(cfg != nullptr, id, "config must not be NULL");
@@ -1731,10 +1547,10 @@ void Modes::check(const sphx_modes_config *cfg, int M)
     this->cfg = *cfg;
 }
 
-// the checked configuration, and sums in flight, records and heads for M members
-void Modes::alloc(const Modes &checked, int M)
+// the checked shape, and sums in flight, records and heads for M members
+void Modes::alloc(const ModesShape &checked, int M, hipStream_t)
 {
-    cfg = checked.cfg;
+    static_cast<ModesShape &>(*this) = checked;
     members = M;
     isum.alloc(block() * M);
     times.alloc((size_t)M * cfg.capacity * 2);
@@ -1742,67 +1558,20 @@ void Modes::alloc(const Modes &checked, int M)
     head.alloc(M);
 }
 
-// Every member's counts (n_records[m], n_dropped[m], where given) and its filled rows, into times[m][0 .. n_records[m])[2] of a
-// [members][capacity][2] array and records[m][0 .. n_records[m])[block()] of a [members][capacity][block()] array, each where
-// given; drain empties every buffer.  SPHX:Modes:range when a member's sticky flag is up; SPHX:Modes:capacity when an array is
-// given and capacity is below the largest count: nothing is copied or drained then.
+// Every member's counts and its filled rows, into times[m][0 .. n_records[m])[2] and records[m][0 .. n_records[m])[block()],
+// each where given (ring_read; SPHX:Modes:range when a member's sticky flag is up)
 void Modes::read(hipStream_t st, int capacity, double *t_out, double *r_out, int *n_records, int64_t *n_dropped, bool drain)
 {
-    const int M = members;
-    std::vector<ModesHead> h(M);
-    SPHX_HIP(hipMemcpyAsync(h.data(), head.get(), sizeof(ModesHead) * M, hipMemcpyDeviceToHost, st));
-    SPHX_HIP(hipStreamSynchronize(st));
-    long long most = 0;
-    for (int m = 0; m < M; ++m) {
-        const long long n = h[m].n_records;
-        if (n < 0 || n > (long long)cfg.capacity) throw Error(SPHX_ERR_STATE, "SPHX:Modes:state", "internal: record count out of range");
-        if (h[m].range)
-            throw Error(SPHX_ERR_STATE, "SPHX:Modes:range", (M > 1 ? "member " + std::to_string(m) + ": " : std::string()) +
-                                                            "a sampled velocity exceeded twice the clock's max |v| (non-finite state?)");
-        most = std::max(most, n);
-    }
-    require((t_out == nullptr && r_out == nullptr) || (long long)capacity >= most, "SPHX:Modes:capacity",
-            "capacity is smaller than the number of records");
-    if ((t_out || r_out) && most > 0) {
-        for (int m = 0; m < M; ++m) {  // only the filled rows of each member's block
-            const size_t n = (size_t)h[m].n_records;
-            if (n == 0) continue;
-            if (t_out)
-                SPHX_HIP(hipMemcpyAsync(t_out + (size_t)m * capacity * 2, times.get() + (size_t)m * cfg.capacity * 2, n * 2 * sizeof(double),
-                                        hipMemcpyDeviceToHost, st));
-            if (r_out)
-                SPHX_HIP(hipMemcpyAsync(r_out + (size_t)m * capacity * block(), records.get() + (size_t)m * cfg.capacity * block(),
-                                        n * block() * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
-    for (int m = 0; m < M; ++m) {
-        if (n_records) n_records[m] = (int)h[m].n_records;
-        if (n_dropped) n_dropped[m] = (int64_t)h[m].n_dropped;
-    }
-    if (drain) {
-        zero(st);
-        SPHX_HIP(hipStreamSynchronize(st));
-    }
+    ring_read(*this, head, st, capacity, {t_out, times.get(), 2}, {r_out, records.get(), block()}, n_records, n_dropped, drain);
 }
 
 namespace {
 
-// enable for M members on schedule s: every check of cfg first
-void modes_enable(Modes &p, const sphx_modes_config *cfg, int M, Schedule &s, hipStream_t st)
+// what is enqueued lands, then the read and the shape
+void modes_read(const Owner &o, int capacity, double *times, double *records, int *mx, int *ny, int *n_records, int64_t *n_dropped, int drain)
 {
-    Modes checked;
-    checked.check(cfg, M);
-    sampler_on(p, kModesNames, s, st, [&] { p.alloc(checked, M); });
-}
-
-// settle() -- what is enqueued lands first -- then the read and the shape; shared by contexts and batches
-template <typename Settle>
-void modes_read(Modes &p, hipStream_t st, Settle &&settle, int capacity, double *times, double *records, int *mx, int *ny, int *n_records,
-                int64_t *n_dropped, int drain)
-{
-    settle();  // (the records of everything enqueued)
-    p.read(st, capacity, times, records, n_records, n_dropped, drain != 0);
+    Modes &p = sampler_settled(o, &sphx_ctx::modes);  // (the records of everything enqueued)
+    p.read(o.st, capacity, times, records, n_records, n_dropped, drain != 0);
     if (mx) *mx = p.cfg.mx;
     if (ny) *ny = p.cfg.ny;
 }
@@ -1812,8 +1581,8 @@ void modes_read(Modes &p, hipStream_t st, Settle &&settle, int capacity, double 
 SPHX_EXPORT int sphx_ctx_modes_enable(sphx_ctx *c, const sphx_modes_config *cfg)
 {
     SPHX_TRY
-    Modes &p = sampler_to_change(c, &sphx_ctx::modes, kModesNames);
-    modes_enable(p, cfg, 1, c->sched, c->stream);
+    const Owner o = ctx_owner(c);
+    sampler_enable(o, &sphx_ctx::modes, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1821,8 +1590,7 @@ SPHX_EXPORT int sphx_ctx_modes_enable(sphx_ctx *c, const sphx_modes_config *cfg)
 SPHX_EXPORT int sphx_ctx_modes_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    Modes &p = sampler_to_change(c, &sphx_ctx::modes, kModesNames);
-    if (p.on) sampler_off(p, c->sched, c->stream);
+    sampler_disable(ctx_owner(c), &sphx_ctx::modes);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1830,8 +1598,7 @@ SPHX_EXPORT int sphx_ctx_modes_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_ctx_modes_sample(sphx_ctx *c)
 {
     SPHX_TRY
-    sampler_of(c, &sphx_ctx::modes, kModesNames, true);
-    sample_now(c, c->sched, [c] { settle_owed(c); }, launch_modes);
+    sampler_sample(ctx_owner(c), &sphx_ctx::modes, launch_modes);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1840,8 +1607,7 @@ SPHX_EXPORT int sphx_ctx_modes_read(sphx_ctx *c, int capacity, double *times, do
                                     int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    Modes &p = sampler_of(c, &sphx_ctx::modes, kModesNames, true);
-    modes_read(p, c->stream, [c] { settle_owed(c); }, capacity, times, records, mx, ny, n_records, n_dropped, drain);
+    modes_read(ctx_owner(c), capacity, times, records, mx, ny, n_records, n_dropped, drain);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -1989,15 +1755,6 @@ void field_block(const sphx_ctx *c, int nx, int &i_lo, int &i_hi)
     i_hi = first_node(c->rank + 1);
 }
 
-// a slab of the native loops, or SPHX:Slab:ctx / SPHX:Slab:protocol
-sphx_ctx *sampled_slab(sphx_ctx *c)
-{
-    require(c != nullptr && c->is_slab, "SPHX:Slab:ctx", "not a slab context");
-    require(c->rebuild_every > 1, "SPHX:Slab:protocol",
-            "the samplers of a slab live in sphx_slab_run / sphx_slab_group_run (a slab created with rebuild_every != 1)");
-    return c;
-}
-
 // everything enqueued for slab c has run: its stream (a replayed ring graph runs ahead of it, release_from_first) and, where it
 // has one, its second stream
 void slab_settle(sphx_ctx *c)
@@ -2016,11 +1773,14 @@ void slab_samplers_changed(sphx_ctx *c)
     if (c->steps_graph) { (void)hipGraphExecDestroy(c->steps_graph); c->steps_graph = nullptr; }
 }
 
-template <typename S>
-S &slab_sampler_on(sphx_ctx *c, S sphx_ctx::*which, const SamplerNames &n)
+// a slab of the native loops, or SPHX:Slab:ctx / SPHX:Slab:protocol.  A configuration is checked in full before anything is
+// changed: a refused one leaves a running sampler and a prepared step graph as they are
+Owner slab_owner(sphx_ctx *c)
 {
-    if (!(c->*which).on) throw Error(SPHX_ERR_STATE, sampler_id(n, "disabled"), std::string(n.off) + "slab");
-    return c->*which;
+    require(c != nullptr && c->is_slab, "SPHX:Slab:ctx", "not a slab context");
+    require(c->rebuild_every > 1, "SPHX:Slab:protocol",
+            "the samplers of a slab live in sphx_slab_run / sphx_slab_group_run (a slab created with rebuild_every != 1)");
+    return Owner{c, c->sched, c->stream, 1, "slab", c->walls.n > 0, [c] { slab_settle(c); }, false, [c] { slab_samplers_changed(c); }};
 }
 
 }  // namespace
@@ -2028,11 +1788,8 @@ S &slab_sampler_on(sphx_ctx *c, S sphx_ctx::*which, const SamplerNames &n)
 SPHX_EXPORT int sphx_slab_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_config *cfg)
 {
     SPHX_TRY
-    sampled_slab(c);
-    FlowStats checked;
-    checked.configure(c->prm, cfg);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
-    slab_samplers_changed(c);
-    stats_enable(c->fstats, c->prm, cfg, 1, c->sched, c->stream);
+    const Owner o = slab_owner(c);
+    sampler_enable(o, &sphx_ctx::fstats, o.c->prm, cfg);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2040,11 +1797,7 @@ SPHX_EXPORT int sphx_slab_flow_stats_enable(sphx_ctx *c, const sphx_flow_stats_c
 SPHX_EXPORT int sphx_slab_flow_stats_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    sampled_slab(c);
-    if (c->fstats.on) {
-        slab_samplers_changed(c);
-        sampler_off(c->fstats, c->sched, c->stream);
-    }
+    sampler_disable(slab_owner(c), &sphx_ctx::fstats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2052,9 +1805,7 @@ SPHX_EXPORT int sphx_slab_flow_stats_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_slab_flow_stats_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    FlowStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::fstats, kStatsNames);
-    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, c->stream);
+    sampler_reset(slab_owner(c), &sphx_ctx::fstats);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2064,9 +1815,7 @@ SPHX_EXPORT int sphx_slab_flow_stats_read(sphx_ctx *c, int band, int capacity, i
                                           double *t_first, double *t_last)
 {
     SPHX_TRY
-    const FlowStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::fstats, kStatsNames);
-    stats_read(f, c->stream, [c] { slab_settle(c); }, band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples,
-               t_first, t_last);
+    stats_read(slab_owner(c), band, capacity, n_bins, count, sum_ux, sum_ux2, sum_uy, sum_uy2, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2074,10 +1823,8 @@ SPHX_EXPORT int sphx_slab_flow_stats_read(sphx_ctx *c, int band, int capacity, i
 SPHX_EXPORT int sphx_slab_history_enable(sphx_ctx *c, const sphx_history_config *cfg)
 {
     SPHX_TRY
-    sampled_slab(c);
-    History::check(cfg, 1);
-    slab_samplers_changed(c);
-    history_enable(c->hist, cfg, 1, c->sched, c->stream);
+    const Owner o = slab_owner(c);
+    sampler_enable(o, &sphx_ctx::hist, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2085,11 +1832,7 @@ SPHX_EXPORT int sphx_slab_history_enable(sphx_ctx *c, const sphx_history_config 
 SPHX_EXPORT int sphx_slab_history_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    sampled_slab(c);
-    if (c->hist.on) {
-        slab_samplers_changed(c);
-        sampler_off(c->hist, c->sched, c->stream);
-    }
+    sampler_disable(slab_owner(c), &sphx_ctx::hist);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2097,9 +1840,8 @@ SPHX_EXPORT int sphx_slab_history_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_slab_history_read(sphx_ctx *c, int capacity, double *records, int *n_records, int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    History &h = slab_sampler_on(sampled_slab(c), &sphx_ctx::hist, kHistoryNames);
-    slab_settle(c);  // (the records of everything enqueued)
-    h.read(c->stream, capacity, records, n_records, n_dropped, drain != 0);
+    const Owner o = slab_owner(c);
+    sampler_settled(o, &sphx_ctx::hist).read(o.st, capacity, records, n_records, n_dropped, drain != 0);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2107,13 +1849,12 @@ SPHX_EXPORT int sphx_slab_history_read(sphx_ctx *c, int capacity, double *record
 SPHX_EXPORT int sphx_slab_field_map_enable(sphx_ctx *c, const sphx_field_map_config *cfg)
 {
     SPHX_TRY
-    sampled_slab(c);
-    FieldMap checked;
-    checked.check(c->prm, cfg, 1);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
+    const Owner o = slab_owner(c);
+    FieldMapShape checked;
+    checked.check(c->prm, cfg, o.M);
     checked.part = true;
     field_block(c, checked.nx, checked.i_lo, checked.i_hi);
-    slab_samplers_changed(c);
-    sampler_on(c->fmap, kFieldNames, c->sched, c->stream, [&] { c->fmap.alloc(checked, 1); });
+    sampler_on(o, &sphx_ctx::fmap, checked);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2121,11 +1862,7 @@ SPHX_EXPORT int sphx_slab_field_map_enable(sphx_ctx *c, const sphx_field_map_con
 SPHX_EXPORT int sphx_slab_field_map_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    sampled_slab(c);
-    if (c->fmap.on) {
-        slab_samplers_changed(c);
-        sampler_off(c->fmap, c->sched, c->stream);
-    }
+    sampler_disable(slab_owner(c), &sphx_ctx::fmap);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2133,9 +1870,7 @@ SPHX_EXPORT int sphx_slab_field_map_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_slab_field_map_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    FieldMap &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::fmap, kFieldNames);
-    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, c->stream);
+    sampler_reset(slab_owner(c), &sphx_ctx::fmap);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2145,9 +1880,8 @@ SPHX_EXPORT int sphx_slab_field_map_read(sphx_ctx *c, int capacity, int *nx, int
                                          int64_t *n_samples, double *t_first, double *t_last)
 {
     SPHX_TRY
-    const FieldMap &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::fmap, kFieldNames);
-    field_read(f, c->stream, [c] { slab_settle(c); }, capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples,
-               t_first, t_last);
+    const FieldMap &f = field_read(slab_owner(c), capacity, nx, ny, count, sum_w, sum_ux, sum_uy, sum_ux2, sum_uy2, n_samples, t_first,
+                                   t_last);
     if (i_lo) *i_lo = f.i_lo;
     if (i_hi) *i_hi = f.i_hi;
     return SPHX_OK;
@@ -2157,14 +1891,13 @@ SPHX_EXPORT int sphx_slab_field_map_read(sphx_ctx *c, int capacity, int *nx, int
 SPHX_EXPORT int sphx_slab_probes_enable(sphx_ctx *c, const sphx_probes_config *cfg)
 {
     SPHX_TRY
-    sampled_slab(c);
-    Probes checked;
-    checked.check(c->prm, cfg, 1);  // (a refused configuration leaves running probes and a prepared graph as they are)
+    const Owner o = slab_owner(c);
+    ProbesShape checked;
+    checked.check(c->prm, cfg, o.M);
     checked.part = true;
     for (int p = 0; p < checked.cfg.n_points; ++p)
         if (probe_owner(c, checked.folded[2 * (size_t)p]) == c->rank) checked.index.push_back(p);
-    slab_samplers_changed(c);
-    sampler_on(c->probes, kProbeNames, c->sched, c->stream, [&] { c->probes.alloc(checked, 1, c->stream); });
+    sampler_on(o, &sphx_ctx::probes, checked);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2172,11 +1905,7 @@ SPHX_EXPORT int sphx_slab_probes_enable(sphx_ctx *c, const sphx_probes_config *c
 SPHX_EXPORT int sphx_slab_probes_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    sampled_slab(c);
-    if (c->probes.on) {
-        slab_samplers_changed(c);
-        sampler_off(c->probes, c->sched, c->stream);
-    }
+    sampler_disable(slab_owner(c), &sphx_ctx::probes);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2185,11 +1914,10 @@ SPHX_EXPORT int sphx_slab_probes_read(sphx_ctx *c, int capacity, double *times, 
                                       int *n_owned, int *n_records, int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    Probes &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::probes, kProbeNames);
-    slab_settle(c);  // (the records of everything enqueued)
+    const Owner o = slab_owner(c);
+    Probes &p = sampler_settled(o, &sphx_ctx::probes);  // (the records of everything enqueued)
     const bool sizes_only = capacity == 0;  // nothing is copied and nothing drained
-    p.read(c->stream, capacity, sizes_only ? nullptr : times, sizes_only ? nullptr : values, n_records, n_dropped,
-           !sizes_only && drain != 0);
+    p.read(o.st, capacity, sizes_only ? nullptr : times, sizes_only ? nullptr : values, n_records, n_dropped, !sizes_only && drain != 0);
     if (index) std::copy(p.index.begin(), p.index.end(), index);
     if (n_points_ring) *n_points_ring = p.cfg.n_points;
     if (n_owned) *n_owned = p.held();
@@ -2200,11 +1928,8 @@ SPHX_EXPORT int sphx_slab_probes_read(sphx_ctx *c, int capacity, double *times, 
 SPHX_EXPORT int sphx_slab_pseries_enable(sphx_ctx *c, const sphx_profile_series_config *cfg)
 {
     SPHX_TRY
-    sampled_slab(c);
-    ProfileSeries checked;
-    checked.check(c->prm, cfg, 1);  // (a refused configuration leaves a running series and a prepared graph as they are)
-    slab_samplers_changed(c);
-    series_enable(c->pseries, c->prm, cfg, 1, c->sched, c->stream);
+    const Owner o = slab_owner(c);
+    sampler_enable(o, &sphx_ctx::pseries, o.c->prm, cfg, o.M);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2212,11 +1937,7 @@ SPHX_EXPORT int sphx_slab_pseries_enable(sphx_ctx *c, const sphx_profile_series_
 SPHX_EXPORT int sphx_slab_pseries_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    sampled_slab(c);
-    if (c->pseries.on) {
-        slab_samplers_changed(c);
-        sampler_off(c->pseries, c->sched, c->stream);
-    }
+    sampler_disable(slab_owner(c), &sphx_ctx::pseries);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2225,8 +1946,7 @@ SPHX_EXPORT int sphx_slab_pseries_read(sphx_ctx *c, int capacity, double *times,
                                        int *n_records, int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    ProfileSeries &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::pseries, kSeriesNames);
-    series_read(p, c->stream, [c] { slab_settle(c); }, capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
+    series_read(slab_owner(c), capacity, times, records, n_bins, n_bands, n_records, n_dropped, drain);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2234,11 +1954,8 @@ SPHX_EXPORT int sphx_slab_pseries_read(sphx_ctx *c, int capacity, double *times,
 SPHX_EXPORT int sphx_slab_pairs_enable(sphx_ctx *c, const sphx_pair_dist_config *cfg)
 {
     SPHX_TRY
-    sampled_slab(c);
-    PairDist checked;
-    checked.check(c->prm, cfg, 1, c->walls.n > 0);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
-    slab_samplers_changed(c);
-    pair_dist_enable(c->pairs, c->prm, cfg, 1, c->walls.n > 0, c->sched, c->stream);
+    const Owner o = slab_owner(c);
+    sampler_enable(o, &sphx_ctx::pairs, o.c->prm, cfg, o.has_walls);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2246,11 +1963,7 @@ SPHX_EXPORT int sphx_slab_pairs_enable(sphx_ctx *c, const sphx_pair_dist_config 
 SPHX_EXPORT int sphx_slab_pairs_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    sampled_slab(c);
-    if (c->pairs.on) {
-        slab_samplers_changed(c);
-        sampler_off(c->pairs, c->sched, c->stream);
-    }
+    sampler_disable(slab_owner(c), &sphx_ctx::pairs);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2258,9 +1971,7 @@ SPHX_EXPORT int sphx_slab_pairs_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_slab_pairs_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    PairDist &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::pairs, kPairNames);
-    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(p, c->stream);
+    sampler_reset(slab_owner(c), &sphx_ctx::pairs);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2269,8 +1980,7 @@ SPHX_EXPORT int sphx_slab_pairs_read(sphx_ctx *c, int band, int capacity, int *n
                                      double *r2_min, int64_t *n_samples, double *t_first, double *t_last)
 {
     SPHX_TRY
-    const PairDist &p = slab_sampler_on(sampled_slab(c), &sphx_ctx::pairs, kPairNames);
-    pair_dist_read(p, c->stream, [c] { slab_settle(c); }, band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
+    pair_dist_read(slab_owner(c), band, capacity, n_bins, ff, fw, centres, r2_min, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2278,11 +1988,8 @@ SPHX_EXPORT int sphx_slab_pairs_read(sphx_ctx *c, int band, int capacity, int *n
 SPHX_EXPORT int sphx_slab_gstats_enable(sphx_ctx *c, const sphx_grad_stats_config *cfg)
 {
     SPHX_TRY
-    sampled_slab(c);
-    GradStats checked;
-    checked.check(c->prm, cfg, c->walls.n > 0);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
-    slab_samplers_changed(c);
-    grad_stats_enable(c->grads, c->prm, cfg, 1, c->walls.n > 0, c->sched, c->stream);
+    const Owner o = slab_owner(c);
+    sampler_enable(o, &sphx_ctx::grads, o.c->prm, cfg, o.has_walls);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2290,11 +1997,7 @@ SPHX_EXPORT int sphx_slab_gstats_enable(sphx_ctx *c, const sphx_grad_stats_confi
 SPHX_EXPORT int sphx_slab_gstats_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    sampled_slab(c);
-    if (c->grads.on) {
-        slab_samplers_changed(c);
-        sampler_off(c->grads, c->sched, c->stream);
-    }
+    sampler_disable(slab_owner(c), &sphx_ctx::grads);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2302,9 +2005,7 @@ SPHX_EXPORT int sphx_slab_gstats_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_slab_gstats_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    GradStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::grads, kGradNames);
-    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, c->stream);
+    sampler_reset(slab_owner(c), &sphx_ctx::grads);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2313,8 +2014,7 @@ SPHX_EXPORT int sphx_slab_gstats_read(sphx_ctx *c, int band, int capacity, int *
                                       double *t_last)
 {
     SPHX_TRY
-    const GradStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::grads, kGradNames);
-    grad_stats_read(f, c->stream, [c] { slab_settle(c); }, band, capacity, n_bins, sums, n_samples, t_first, t_last);
+    grad_stats_read(slab_owner(c), band, capacity, n_bins, sums, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2322,11 +2022,8 @@ SPHX_EXPORT int sphx_slab_gstats_read(sphx_ctx *c, int band, int capacity, int *
 SPHX_EXPORT int sphx_slab_dstats_enable(sphx_ctx *c, const sphx_dens_stats_config *cfg)
 {
     SPHX_TRY
-    sampled_slab(c);
-    DensStats checked;
-    checked.check(c->prm, cfg);  // (a refused configuration leaves a running sampler and a prepared graph as they are)
-    slab_samplers_changed(c);
-    dens_stats_enable(c->dens, c->prm, cfg, 1, c->sched, c->stream);
+    const Owner o = slab_owner(c);
+    sampler_enable(o, &sphx_ctx::dens, o.c->prm, cfg);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2334,11 +2031,7 @@ SPHX_EXPORT int sphx_slab_dstats_enable(sphx_ctx *c, const sphx_dens_stats_confi
 SPHX_EXPORT int sphx_slab_dstats_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    sampled_slab(c);
-    if (c->dens.on) {
-        slab_samplers_changed(c);
-        sampler_off(c->dens, c->sched, c->stream);
-    }
+    sampler_disable(slab_owner(c), &sphx_ctx::dens);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2346,9 +2039,7 @@ SPHX_EXPORT int sphx_slab_dstats_disable(sphx_ctx *c)
 SPHX_EXPORT int sphx_slab_dstats_reset(sphx_ctx *c)
 {
     SPHX_TRY
-    DensStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::dens, kDensNames);
-    slab_settle(c);  // (the samples of everything enqueued land before the sums are cleared)
-    sampler_zero(f, c->stream);
+    sampler_reset(slab_owner(c), &sphx_ctx::dens);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2357,9 +2048,7 @@ SPHX_EXPORT int sphx_slab_dstats_read(sphx_ctx *c, int band, int capacity, int h
                                       int64_t *hist, int64_t *below, int64_t *above, int64_t *n_samples, double *t_first, double *t_last)
 {
     SPHX_TRY
-    const DensStats &f = slab_sampler_on(sampled_slab(c), &sphx_ctx::dens, kDensNames);
-    dens_stats_read(f, c->stream, [c] { slab_settle(c); }, 0, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above,
-                    n_samples, t_first, t_last);
+    dens_stats_read(slab_owner(c), 0, band, capacity, hist_capacity, n_bins, n_hist, sums, hist, below, above, n_samples, t_first, t_last);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2367,12 +2056,11 @@ SPHX_EXPORT int sphx_slab_dstats_read(sphx_ctx *c, int band, int capacity, int h
 SPHX_EXPORT int sphx_slab_tracers_enable(sphx_ctx *c, const sphx_tracers_config *cfg)
 {
     SPHX_TRY
-    sampled_slab(c);
-    Tracers checked;
-    checked.check(c->nf, c->nt, cfg, 1);  // (a refused configuration leaves a running series and a prepared graph as they are)
+    const Owner o = slab_owner(c);
+    TracersShape checked;
+    checked.check(c->nf, c->nt, cfg, o.M);
     checked.part = true;
-    slab_samplers_changed(c);
-    sampler_on(c->tracers, kTracerNames, c->sched, c->stream, [&] { c->tracers.alloc(checked, 1, c->stream); });
+    sampler_on(o, &sphx_ctx::tracers, checked);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2380,11 +2068,7 @@ SPHX_EXPORT int sphx_slab_tracers_enable(sphx_ctx *c, const sphx_tracers_config 
 SPHX_EXPORT int sphx_slab_tracers_disable(sphx_ctx *c)
 {
     SPHX_TRY
-    sampled_slab(c);
-    if (c->tracers.on) {
-        slab_samplers_changed(c);
-        sampler_off(c->tracers, c->sched, c->stream);
-    }
+    sampler_disable(slab_owner(c), &sphx_ctx::tracers);
     return SPHX_OK;
     SPHX_CATCH
 }
@@ -2393,10 +2077,10 @@ SPHX_EXPORT int sphx_slab_tracers_read(sphx_ctx *c, int capacity, double *times,
                                        int *n_tracers, int *n_records, int64_t *n_dropped, int drain)
 {
     SPHX_TRY
-    Tracers &t = slab_sampler_on(sampled_slab(c), &sphx_ctx::tracers, kTracerNames);
-    slab_settle(c);  // (the records of everything enqueued)
+    const Owner o = slab_owner(c);
+    Tracers &t = sampler_settled(o, &sphx_ctx::tracers);  // (the records of everything enqueued)
     const bool sizes_only = capacity == 0;  // nothing is copied and nothing drained
-    t.read(c->stream, capacity, sizes_only ? nullptr : times, sizes_only ? nullptr : values, n_records, n_dropped, nullptr,
+    t.read(o.st, capacity, sizes_only ? nullptr : times, sizes_only ? nullptr : values, n_records, n_dropped, nullptr,
            !sizes_only && drain != 0, sizes_only ? nullptr : n_owned);
     if (ids) std::copy(t.ids.begin(), t.ids.end(), ids);
     if (n_tracers) *n_tracers = t.cfg.n_tracers;
