@@ -156,16 +156,29 @@ __device__ __forceinline__ void continuity_add(const KernelConst &kc, double dx,
 }
 
 // What the wall viscous and transport terms of pass CD share (Bi = {b11, b12, b21, b22} of the particle; a wall particle has
-// no B of its own): the distance, dW Vol_w, t = B_i e and e . t
+// no B of its own): the distance, dW Vol_w, t = B_i e and e . t -- and the unit vector, for a caller that keeps the pair for
+// its wall pressure term (wall_pressure_from)
 struct WallPair {
-    double r, dWVj, tx, ty, eBe;
+    double r, dWVj, tx, ty, eBe, ex, ey;
 };
 __device__ __forceinline__ WallPair wall_pair(const KernelConst &kc, double dx, double dy, double Volw, const double4 &Bi)
 {
     const auto [r, ex, ey] = pair_geom(dx, dy);
     const double dWVj = spline_dW_in(kc, r) * Volw;
     const double tx = Bi.x * ex + Bi.y * ey, ty = Bi.z * ex + Bi.w * ey;
-    return WallPair{r, dWVj, tx, ty, ex * tx + ey * ty};
+    return WallPair{r, dWVj, tx, ty, ex * tx + ey * ty, ex, ey};
+}
+
+// The part of the wall pressure term that needs the particle's acceleration, for a pair whose geometry the caller kept from
+// wall_pair: wall_pressure_add's expressions in its order on the values it would compute again from the same operands, so
+// the same bits (the compact force pass at 16 / 32 lanes per particle visits its prefetched wall rows once)
+__device__ __forceinline__ void wall_pressure_from(const WallPair &wp, double acx, double acy, double p_i, double rhoh_i, double &px,
+                                                   double &py)
+{
+    const double face = -(acx * wp.ex + acy * wp.ey);
+    const double p_wall = p_i + rhoh_i * wp.r * fmax(0.0, face);
+    px -= (p_i + p_wall) * wp.dWVj * wp.tx;
+    py -= (p_i + p_wall) * wp.dWVj * wp.ty;
 }
 
 // wall pressure term of pass CD (sph_physics_mex.c:931-934): the wall's pressure mirrors the particle's, raised by the

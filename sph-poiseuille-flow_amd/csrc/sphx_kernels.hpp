@@ -1103,7 +1103,12 @@ __global__ __launch_bounds__(kBlock) void k_kgc_b(Members mb, int q, Grid g, Flu
 // further than one cell from where it was binned raises the grid flag: pass E of this step looks for the members of a new cell
 // only that far (rebin_near), and its tail workgroup turns the flag into SPHX_ERR_GRID.
 // BLK: the threads of the workgroup (HIST stays at 256)
-template <int LPP, bool HIST = false, int BLK = kBlock>
+// WP (kept wall pairs, 16 / 32 lanes per particle; WP = false: SPHX_DEBUG_SWITCHES=no_wall_paths, the pair built twice as
+// before): a prefetched wall row keeps what wall_pair made of it -- in place of the position and the volume -- and the second
+// loop forms the wall pressure from that (wall_pressure_from) instead of building the pair again.  Rows beyond the prefetched
+// ones are read and built again as before.  (later: the first loop builds the pair of a prefetched wall row all the same and
+// leaves out its viscous and transport terms.)
+template <int LPP, bool HIST = false, int BLK = kBlock, bool WP = true>
 __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid &g, const Phys &ph, const FluidSet &s,
                                             const FluidTmp &t, const Walls &w, int later, int nblk)
 {
@@ -1184,7 +1189,67 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
         ix -= 2.0 * wp.dWVj * wp.tx;
         iy -= 2.0 * wp.dWVj * wp.ty;
     };
-    if (active) {
+    // (wall_term in two halves, for a prefetched wall row whose pair is kept for the second loop)
+    auto wall_pair_of = [&](const double2 pj, const double4 wj) {
+        return wall_pair(ph.kc, pair_dx<LPP>(g, xi - pj.x), yi - pj.y, wj.x, Bi);
+    };
+    auto wall_apply = [&](const WallPair &wp, const double4 wj) {
+        const double coeff = 4.0 * wp.eBe * ph.mu * wp.dWVj * rcp_nr(wp.r + 0.01 * h);
+        ax += coeff * (vxi - wj.y);
+        ay += coeff * (vyi - wj.z);
+        ix -= 2.0 * wp.dWVj * wp.tx;
+        iy -= 2.0 * wp.dWVj * wp.ty;
+    };
+    constexpr bool kKeep = kRowsAhead<LPP> && WP;
+    bool kept0 = false, kept1 = false;  // kKeep: the prefetched row is a wall row, and this is its pair
+    WallPair wp0, wp1;
+    if (kKeep && active) {  // both kinds of row as below; a prefetched wall row keeps its pair, not its position and volume
+        const bool has0 = nn_all > 0, has1 = nn_all > 1;
+        const bool w0 = has0 && (first.e0 & kWallBit) != 0, w1 = has1 && (first.e1 & kWallBit) != 0;
+        const int k0 = has0 ? (first.e0 & (kWallBit - 1)) : i, k1 = has1 ? (first.e1 & (kWallBit - 1)) : i;
+        const int kf0 = w0 ? i : k0, kf1 = w1 ? i : k1;
+        const double2 qj0 = (w0 ? w.pos : (const double2 *)s.pos)[k0];
+        const double4 cj0 = (w0 ? w.a : (const double4 *)t.a)[k0];
+        const double2 vj0 = s.vel[kf0];
+        const double4 Bj0 = t.B[kf0];
+        const double2 qj1 = (w1 ? w.pos : (const double2 *)s.pos)[k1];
+        const double4 cj1 = (w1 ? w.a : (const double4 *)t.a)[k1];
+        const double2 vj1 = s.vel[kf1];
+        const double4 Bj1 = t.B[kf1];
+        requests_issued();
+        if (has0) {
+            if (!w0) fluid_term(qj0, vj0, cj0, Bj0);
+            else {
+                kept0 = true;
+                wp0 = wall_pair_of(qj0, cj0);
+                if (!later) wall_apply(wp0, cj0);  // (wall entries contribute to the pressure part in the second loop only)
+            }
+        }
+        if (has1) {
+            if (!w1) fluid_term(qj1, vj1, cj1, Bj1);
+            else {
+                kept1 = true;
+                wp1 = wall_pair_of(qj1, cj1);
+                if (!later) wall_apply(wp1, cj1);
+            }
+        }
+        for (int m = 2; m < nn_all; ++m) {
+            const int e = t.nl_idx[(size_t)m * t.nl_stride + tid];
+            const int k = e & (kWallBit - 1);
+            if (!(e & kWallBit)) {
+                const double2 pj = s.pos[k], vj = s.vel[k];
+                const double4 aj = t.a[k], Bj = t.B[k];
+                fluid_term(pj, vj, aj, Bj);
+            } else {
+                first_wall = min(first_wall, m);
+                if (later) continue;
+                const double2 pj = w.pos[k];
+                const double4 wj = w.a[k];
+                wall_term(pj, wj);
+            }
+        }
+    }
+    if (!kKeep && active) {
         if (kRowsAhead<LPP>) {
             const bool has0 = nn_all > 0, has1 = nn_all > 1;
             const bool w0 = has0 && (first.e0 & kWallBit) != 0, w1 = has1 && (first.e1 & kWallBit) != 0;
@@ -1242,7 +1307,10 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
         auto wall_pressure = [&](const double2 pj, double Volw) {
             wall_pressure_add(ph.kc, pair_dx<LPP>(g, xi - pj.x), yi - pj.y, Volw, Bi, acx, acy, p_i, rhoh_i, px, py);
         };
-        if (kRowsAhead<LPP>) {  // (the prefetched rows from registers; lanes with more wall rows read the rest again)
+        if (kKeep) {  // (the prefetched rows from their kept pairs; first_wall counts from row 2 here)
+            if (kept0) wall_pressure_from(wp0, acx, acy, p_i, rhoh_i, px, py);
+            if (kept1) wall_pressure_from(wp1, acx, acy, p_i, rhoh_i, px, py);
+        } else if (kRowsAhead<LPP>) {  // (the prefetched rows from registers; lanes with more wall rows read the rest again)
             if (first_wall <= 0 && nn_all > 0) wall_pressure(pj0, aj0.x);
             if (first_wall <= 1 && nn_all > 1) wall_pressure(pj1, aj1.x);
         }
@@ -1296,27 +1364,27 @@ __device__ __forceinline__ void forces_pass(const Clock *clk, int q, const Grid 
         if (c >= 0 && first) atomicAdd(&t.count[c], same);
     }
 }
-template <int LPP, int BLK = kBlock>
+template <int LPP, int BLK = kBlock, bool WP = true>
 __global__ __launch_bounds__(BLK) void k_forces(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride, int cap,
                                                    double2 *pos, double2 *vel, Grid g, Phys ph, FluidSet s, FluidTmp t, Walls w)
 {
     t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; s.vel = vel;  // shape: later
-    forces_pass<LPP, false, BLK>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
+    forces_pass<LPP, false, BLK, WP>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
 }
-template <int LPP>
+template <int LPP, bool WP = true>
 __global__ __launch_bounds__(kBlock) void k_forces_hist(const Clock *clk, int q, int shape, int *nl_cnt, int *nl_idx, int nl_stride,
                                                         int cap, double2 *pos, double2 *vel, Grid g, Phys ph, FluidSet s, FluidTmp t,
                                                         Walls w)
 {
     t.nl_cnt = nl_cnt; t.nl_idx = nl_idx; t.nl_stride = nl_stride; t.cap = cap; s.pos = pos; s.vel = vel;
-    forces_pass<LPP, true>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
+    forces_pass<LPP, true, kBlock, WP>(clk, q, g, ph, s, t, w, shape_flag(shape), shape_blocks(shape));
 }
-template <int LPP>
+template <int LPP, bool WP = true>
 __global__ __launch_bounds__(kBlock) void k_forces_b(Members mb, int q, Grid g, FluidSet s, FluidTmp t, Walls w, int later)
 {
     const int m = (int)blockIdx.y;
     const Phys ph = mb.ph[m];
-    forces_pass<LPP>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, later, (int)gridDim.x);
+    forces_pass<LPP, false, kBlock, WP>(mb.clk + m, q, g, ph, member_set(mb, m, s), member_tmp(mb, m, t), w, later, (int)gridDim.x);
 }
 
 // =================================================================================================

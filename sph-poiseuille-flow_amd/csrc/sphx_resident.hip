@@ -313,7 +313,7 @@ struct sphx_ctx {
 namespace {
 
 // A/B switches for measurements, all behind ONE environment variable read once per process:
-//   SPHX_DEBUG_SWITCHES=no_tail_clock,no_fuse_ea,no_fold_rebin,no_lds_tiles,no_coded_lists,no_lazy_out,no_xcd_align,forces_tile_320,log
+//   SPHX_DEBUG_SWITCHES=no_tail_clock,no_fuse_ea,no_fold_rebin,no_lds_tiles,no_coded_lists,no_lazy_out,no_xcd_align,no_wall_paths,forces_tile_320,log
 // (no_tail_clock: the clock update as a launch of its own on every step; no_fuse_ea: passes E and A in separate launches;
 //  no_fold_rebin: small channels re-bin with the chain k_clock_scan -> k_scatter -> k_reorder behind pass E;
 //  no_lds_tiles: large-channel passes gather from global memory; no_coded_lists: index differences in every list, never tile
@@ -321,12 +321,15 @@ namespace {
 //  fused launch, which starts at physical block nb, numbers its blocks as if it started at block 0 (xcd_block, sphx_xcd_block.hpp);
 //  block_64 / block_128 / block_256: the compact passes in workgroups of that many threads whatever pick_block says (block_256:
 //  the launches as they were before the block size became a choice);
+//  no_wall_paths: pass CD at 16 / 32 lanes per particle builds the pair of a prefetched wall row twice, as before the kept pairs
+//  (forces_pass, WP; sphx_kernels.hpp);
 //  log: forced re-binnings and timer
 //  problems on stderr)
 struct DebugSwitches {
     bool no_fold_rebin = false;
     bool no_tail_clock = false, no_fuse_ea = false, no_lds_tiles = false, no_coded_lists = false, no_lazy_out = false, log = false;
     bool no_xcd_align = false;
+    bool no_wall_paths = false;
     bool no_slab_overlap = false;  // skinned slabs: the local maxima from pass E's tail workgroup, the all-reduce on the step's only stream (round 3)
     bool full_copyback = false;  // dynamic contexts: the in-place re-binning copies the whole layout back (round 3)
     int tail_limit = 0;  // > 0: largest pass (in workgroups) whose clock update rides in pass E's tail workgroup
@@ -348,6 +351,7 @@ const DebugSwitches &debug_switches()
         d.no_coded_lists = has("no_coded_lists");
         d.no_lazy_out = has("no_lazy_out");
         d.no_xcd_align = has("no_xcd_align");
+        d.no_wall_paths = has("no_wall_paths");
         d.log = has("log");
         d.no_slab_overlap = has("no_slab_overlap");
         d.full_copyback = has("full_copyback");
@@ -481,6 +485,14 @@ void with_block(const sphx_ctx *c, F &&f)
         case 1024: f(std::integral_constant<int, 1024>{}); break;
         default: throw Error(SPHX_ERR_STATE, "SPHX:Ctx:block", "internal: block size must be 64, 128, 256, 512 or 1024");
     }
+}
+
+// f(std::bool_constant<WP>): the compact pass CD with its kept wall pairs, or (no_wall_paths) in its earlier form
+template <typename F>
+void with_wall_paths(F &&f)
+{
+    if (debug_switches().no_wall_paths) f(std::false_type{});
+    else f(std::true_type{});
 }
 
 // The form of a large-channel ("_w") kernel, handed to f as compile-time TILE / CODED: slot-coded lists (2 lanes per particle,
@@ -682,8 +694,11 @@ void launch_pass_cd(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t_, R
             with_block(c, [&](auto blk) {
                 constexpr int BLK = decltype(blk)::value;
                 const unsigned nb = c->n_blocks_pass;
-                launch_pass_hot_blk(c, rate == Rate::Inner ? "k_forces_inner" : "k_forces", Forms{k_forces<LPP, BLK>, k_forces_b<LPP>}, nb, BLK, q,
-                                    hot_forces(nb, (int)rate, s, t), s, t, batch_only((int)rate));
+                with_wall_paths([&](auto wp) {
+                    constexpr bool WP = decltype(wp)::value;
+                    launch_pass_hot_blk(c, rate == Rate::Inner ? "k_forces_inner" : "k_forces", Forms{k_forces<LPP, BLK, WP>, k_forces_b<LPP, WP>}, nb,
+                                        BLK, q, hot_forces(nb, (int)rate, s, t), s, t, batch_only((int)rate));
+                });
             });
         } else {
             auto forces = [&](auto tile, auto coded) {
@@ -814,7 +829,9 @@ void launch_fold_rebin(sphx_ctx *c, int q, const FluidSet &s, const FluidTmp &t,
         if constexpr (LPP >= 16) {
             // (256 threads whatever the block size of the other passes, with per-workgroup maxima of their own: pass_tmp)
             const unsigned np = c->n_blocks_particles;
-            launch_pass_hot(c, "k_forces_hist", Forms{k_forces_hist<LPP>}, np, q, hot_forces(np, 0, s, t), s, t);
+            with_wall_paths([&](auto wp) {
+                launch_pass_hot(c, "k_forces_hist", Forms{k_forces_hist<LPP, decltype(wp)::value>}, np, q, hot_forces(np, 0, s, t), s, t);
+            });
             launch_pass_hot(c, "k_continuity_rebin", Forms{k_continuity_rebin<LPP>}, np + 1, q, hot_continuity(np, 1, s, t), s, t, d);
         } else {
             throw Error(SPHX_ERR_STATE, "SPHX:Ctx:fold", "internal: folded re-binning step at this lane count");
